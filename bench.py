@@ -11,10 +11,13 @@ selects the other single-GPU-sized configurations (1 GB mixed scripts, one 1.25 
 scaling, no collective on the data path) and the token ids are gathered to rank 0 over RCCL at the end
 of every step, as the north star prescribes.
 
-Also reported on rank 0 at N = 1: `host_to_host` (SURVEY §8d's metric proper: host-resident text to
-host-resident ids through wp_linear_encode, upload and download included), the sibling `fast` path's
-device rate, the roofline of the dominant kernel, the SA/LCP stage against the HBM peak and the CPU
-baseline.  Prints ONE JSON line on rank 0; exits non-zero if the ids differ from the CPU port's.
+A plain run sets up, warms up, times `--steps` steps and prints ONE JSON line on rank 0 (`value`, `ms_per_step`,
+the stage times, the roofline of the dominant kernel and the SA/LCP stage against the HBM peak, all taken from
+the timed steps themselves).  `--full` adds, on rank 0 at N = 1, the measurements and checks that take runs of
+their own: `host_to_host` (SURVEY §8d's metric proper: host-resident text to host-resident ids through
+wp_linear_encode, upload and download included), the shard stream, the sibling `fast` path's device rate and the
+CPU baseline; it exits non-zero if the ids differ from the CPU port's.  `--dump-outputs DIR` writes the ids of
+the last timed step (see _dump_outputs) so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -49,6 +52,9 @@ CPU_CALIBRATION = ("build container (8 vCPU Xeon 2.1 GHz), config-2 synthetic 10
                    "reference's published laptops: 9.4-18.9 MB/s")
 
 _DevView = W.DeviceIds  # zero-copy torch view of a device buffer owned by the library
+
+DUMP_SAMPLE = 1 << 21  # --dump-outputs: ids kept at fixed seeded positions
+DUMP_BLOCKS = 1 << 16  # --dump-outputs: blocks of consecutive ids summed
 
 CONFIGS = {
     2: ("english", 100.0, 29000, "configs[1]: %.0f MB English-shaped synthetic shard per GPU (SURVEY 8d config 2)"),
@@ -121,6 +127,37 @@ def _cpu_baseline(text, vocab, target_bytes):
             "calibration": CPU_CALIBRATION}, ids
 
 
+def _dump_outputs(out_dir, ids):
+    """--dump-outputs: the ids the timed path delivered in its last step (numpy int32; all shards in shard order
+    with N > 1) as float arrays, about 25 MB at most:
+      n_ids.npy           [count]
+      ids_sample.npy      the ids at DUMP_SAMPLE fixed positions (all of them for a shorter stream), float32 while
+                          every id is exact in it, else float64
+      ids_sample_pos.npy  those positions (seeded: the same for every run with the same count), float64
+      ids_block_sums.npy  [blocks, 2] per block of consecutive ids: sum of the ids and sum of id * (1 + offset in
+                          the block), float64; together they cover every id and its place"""
+    os.makedirs(out_dir, exist_ok=True)
+    ids = np.ascontiguousarray(ids, dtype=np.int32)
+    n = len(ids)
+    if n <= DUMP_SAMPLE:
+        pos = np.arange(n, dtype=np.int64)
+    else:
+        pos = np.sort(np.random.default_rng(20240611).choice(n, DUMP_SAMPLE, replace=False))
+    sample = ids[pos]
+    v = ids.astype(np.int64)
+    exact32 = n == 0 or int(np.abs(v).max()) < (1 << 24)
+    bs = max(1, -(-n // DUMP_BLOCKS))
+    starts = np.arange(0, n, bs)
+    sums = np.zeros((len(starts), 2), dtype=np.float64)
+    if n:
+        sums[:, 0] = np.add.reduceat(v, starts)
+        sums[:, 1] = np.add.reduceat(v * (np.arange(n, dtype=np.int64) % bs + 1), starts)
+    np.save(os.path.join(out_dir, "n_ids.npy"), np.array([n], dtype=np.float64))
+    np.save(os.path.join(out_dir, "ids_sample.npy"), sample.astype(np.float32 if exact32 else np.float64))
+    np.save(os.path.join(out_dir, "ids_sample_pos.npy"), pos.astype(np.float64))
+    np.save(os.path.join(out_dir, "ids_block_sums.npy"), sums)
+
+
 def _self_launch(n):
     """`python bench.py --gpus N` without a launcher around it: start the N ranks as children
     (`python -m torch.distributed.run --nproc-per-node N bench.py <same arguments>`, the driver's own form),
@@ -169,12 +206,19 @@ def main():
     ap.add_argument("--mb", type=float, default=None, help="shard size per GPU in MB (1 MB = 1e6 bytes); default: the configuration's")
     ap.add_argument("--vocab-size", type=int, default=None)
     ap.add_argument("--seed", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also the host-to-host, shard-stream and fast-path measurements, the CPU baseline and the check "
+                         "of the ids against the CPU port (rank 0, N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the ids of the last one as DIR/<name>.npy (rank 0)")
     ap.add_argument("--cpu-sample-mb", type=float, default=64.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the host-to-host and fast-path measurements")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the ids check")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the host-to-host and fast-path measurements")
     ap.add_argument("--text-file", default=None, help="optional local corpus instead of the synthetic shard")
     ap.add_argument("--vocab-file", default=None)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: this process becomes the launcher (it has not touched the GPU and
@@ -274,7 +318,7 @@ def main():
             gather.step(view, n_ids, before_collective=torch.cuda.current_stream().synchronize,
                         counts_known=steps_done[0] > 0)
         steps_done[0] += 1
-        return n_ids
+        return d_ids, n_ids
 
     def fence():
         if distributed:
@@ -287,9 +331,9 @@ def main():
     stage_ms = {}
     radix_ms = radix_elems = radix_launches = digit_bytes = radix_bytes = 0
     t0 = time.perf_counter()
-    n_ids = 0
+    d_ids, n_ids = None, 0
     for _ in range(args.steps):
-        n_ids = step()
+        d_ids, n_ids = step()
         st = vocab_h.stats()
         radix_ms += st["ms_radix_scatter"]
         radix_elems += st["radix_pass_elems"]
@@ -301,6 +345,14 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     st = vocab_h.stats()
+    if args.dump_outputs and rank == 0:
+        # the last timed step's ids, before anything else encodes into the handle's buffer
+        if distributed:
+            last_ids = gather.result()
+        else:
+            last_ids = (torch.as_tensor(_DevView(d_ids, n_ids), device=dev).cpu().numpy() if n_ids
+                        else np.zeros(0, dtype=np.int32))
+        _dump_outputs(args.dump_outputs, last_ids)
 
     t = torch.tensor([dt, float(nbytes)], dtype=torch.float64, device=cdev)
     if distributed:
@@ -381,7 +433,7 @@ def main():
                                    "frac": round(sa_bytes / 1e9 / (sa_ms / 1e3) / HBM_PEAK_GBPS, 4),
                                    "per_symbol": {"radix_pass": RADIX_BYTES_PER_ELEM, "digit_bytes_total": round(dig / n_sym, 2),
                                                   "split": split, "rank_store_window": RANK_STORE_BYTES, "round_entry": ROUND_BYTES}}
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             # SURVEY 8(d)'s metric proper: host-resident text -> host-resident ids (pageable source, ids into a pinned
             # block of the library's pool), wall clock around wp_linear_encode
             vocab_h.encode(text[:1 << 20])
@@ -424,7 +476,7 @@ def main():
             same = bool(f_n == l_n and (f_n == 0 or torch.equal(fast_ids, torch.as_tensor(_DevView(l_ptr, l_n), device=dev))))
             out["fast_path"] = {"ms_per_step": round(fw * 1e3, 3), "MB_per_s": round(nbytes / 1e6 / fw, 1),
                                 "ids_equal_linear_on_device": same}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cb, cpu_ids = _cpu_baseline(text, vocab, int(args.cpu_sample_mb * 1e6))
             out["cpu_baseline"] = cb
             # the sample is a whitespace-cut prefix of the shard: its ids are a prefix of the GPU's

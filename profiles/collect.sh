@@ -16,7 +16,7 @@ for C in FETCH_SIZE WRITE_SIZE; do
     python3 "$R/bench.py" --steps 1 --warmup 1 --no-cpu-baseline --no-extras > "$OUT/${TAG}_pmc_$C.log" 2>&1
 done
 cd "$R"
-python3 bench.py --steps 10 --warmup 3 > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
+python3 bench.py --full --steps 10 --warmup 3 > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
 cat "$OUT/${TAG}_bench.json"
 python3 profiles/pmc_summary.py "$OUT" "$TAG" > "$OUT/${TAG}_pmc_kernels.txt" || true
 python3 profiles/make_traffic_json.py "$OUT" "$TAG" > "$OUT/${TAG}_traffic.json" || true
@@ -30,7 +30,7 @@ for CFG in 3 5; do
       python3 "$R/bench.py" --config $CFG --steps 1 --warmup 1 --no-cpu-baseline --no-extras > "$OUT/${TAG}c${CFG}_pmc_$C.log" 2>&1
   done
   cd "$R"
-  python3 bench.py --config $CFG --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/${TAG}_config${CFG}_bench.json" 2> "$OUT/${TAG}_config${CFG}_bench.err"
+  python3 bench.py --full --config $CFG --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/${TAG}_config${CFG}_bench.json" 2> "$OUT/${TAG}_config${CFG}_bench.err"
   python3 profiles/pmc_summary.py "$OUT" "${TAG}c${CFG}" > "$OUT/${TAG}_config${CFG}_pmc_kernels.txt" || true
 done
-python3 bench.py --config 4 --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/${TAG}_config4_bench.json" 2> "$OUT/${TAG}_config4_bench.err"
+python3 bench.py --full --config 4 --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/${TAG}_config4_bench.json" 2> "$OUT/${TAG}_config4_bench.err"

@@ -247,6 +247,43 @@ def test_bench_self_launch_two_ranks():
     assert out["config"]["id_gather"].startswith("gloo") and out["value"] > 0
 
 
+def test_bench_dump_outputs_are_the_oracles_ids(tmp_path):
+    """`bench.py --dump-outputs DIR` (a plain run: no --full) writes the ids of its last timed step: the count, the
+    ids at fixed seeded positions and per-block sums, all equal to the CPU oracle's ids of the same shard; two runs
+    write the same arrays."""
+    import json
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("dump%d" % run)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--mb", "12", "--steps", "2", "--warmup", "1",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, env=env, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = json.loads(r.stdout.strip())
+        assert out["steps"] == 2 and out["ms_per_step"] > 0 and "cpu_baseline" not in out and "host_to_host" not in out
+        dumps.append({f[:-4]: np.load(d / f) for f in os.listdir(d)})
+    text, vocab = synth.parallel_corpus("english", 12e6, 2, 29000, 0)
+    exp = O.Vocab(vocab).encode(text, threads=8)
+    got = dumps[0]
+    assert sorted(got) == ["ids_block_sums", "ids_sample", "ids_sample_pos", "n_ids"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert int(got["n_ids"][0]) == len(exp) == out["config"]["ids_per_step_rank0"]
+    pos = got["ids_sample_pos"].astype(np.int64)
+    assert len(pos) == min(len(exp), 1 << 21) and np.array_equal(got["ids_sample"].astype(np.int64), exp[pos])
+    bs = -(-len(exp) // (1 << 16))  # (bench.py: DUMP_BLOCKS blocks at most)
+    v = exp.astype(np.int64)
+    starts = np.arange(0, len(exp), bs)
+    assert np.array_equal(got["ids_block_sums"][:, 0], np.add.reduceat(v, starts).astype(np.float64))
+    assert np.array_equal(got["ids_block_sums"][:, 1],
+                          np.add.reduceat(v * (np.arange(len(v)) % bs + 1), starts).astype(np.float64))
+    for k in got:
+        assert np.array_equal(got[k], dumps[1][k]), k
+
+
 def test_calls_keep_the_current_device_and_trim_releases(corpus):
     """Every entry point of the C ABI leaves the calling thread's current HIP device as it found it (a handle on
     another GPU, wp_linear_encode_multi and wp_vocab_destroy all switch devices inside), and wp_trim gives the

@@ -219,7 +219,8 @@ typedef struct {
 int wp_get_stats(const wp_vocab *v, wp_stats *out);
 
 /* ---- debug fetch (WP_OPT_KEEP_DEBUG): copies device intermediates to host ----
- * which: 0 S (dense symbols as int32, n), 1 SA (n), 2 rank (n), 3 lcp (n-1; -1 = "at least
+ * which: 0 S (dense symbols as int32, n), 1 SA (n), 2 rank (n; the full inverse SA is kept only with this option —
+ * the default layout otherwise stores ranks for the suffixes of needed groups alone), 3 lcp (n-1; -1 = "at least
  * sorted_depth"), 4 best_prefix (n), 5 best_suffix (n), 6 code points (n_text) */
 int wp_linear_debug_fetch(const wp_vocab *v, int which, int32_t *out, size_t capacity,
                           size_t *n_out);

@@ -33,7 +33,15 @@ inline unsigned cdiv(size_t a, size_t b) { return static_cast<unsigned>((a + b -
 // a computed table (radix offsets, rank destinations, token ids, list slots) check it first; a violation is
 // counted per site and skipped instead of faulting the GPU, and the encode fails with the counts.
 // Release build: the checks compile to nothing.
-enum BoundSite { kSiteRadixScatter = 0, kSiteRankStore = 1, kSiteTokenId = 2, kSiteListSlot = 3, kBoundSites = 4 };
+// (kSiteKeyStep counts no address: step starts that break the key-space step table's invariant, scanline.h)
+enum BoundSite {
+  kSiteRadixScatter = 0,
+  kSiteRankStore = 1,
+  kSiteTokenId = 2,
+  kSiteListSlot = 3,
+  kSiteKeyStep = 4,
+  kBoundSites = 5
+};
 #ifdef WP_DEBUG_BOUNDS
 __device__ unsigned int g_wp_oob[kBoundSites];
 __device__ __forceinline__ bool wp_in_bounds(bool ok, int site) {

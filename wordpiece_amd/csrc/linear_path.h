@@ -53,15 +53,15 @@ struct LinearPath {
   // ---- derived
   hipStream_t st, st2;
   const HostVocab &hv;
-  bool full, prune, use_trie, window_store, use_digit_bytes, staged_possible, sparse_emit;
+  bool full, prune, use_trie, key_lookup, window_store, use_digit_bytes, staged_possible, sparse_emit;
   uint32_t need_depth;
-  int M, P, bucket_shift, bucket_shift_all, hb_n, win_mid;
-  unsigned sl_tiles, sl_groups, nbuckets, nbuckets_all;
+  int M, P, P_cap, bucket_shift, bucket_shift_all, key_shift, key_shift_all, hb_n, win_mid;
+  unsigned sl_tiles, sl_groups, nbuckets, nbuckets_all, nkbuckets, nkbuckets_all;
   size_t radix_words, emit_tiles, walk_blocks, claim_size, list_cap;
 
   // ---- device buffers.  n-sized "slabs" of 4 bytes per symbol change roles from stage to stage (see plan()).
   SymT *d_sym = nullptr, *d_vsym = nullptr;
-  Key0 *KA = nullptr, *KB = nullptr;           // round-0 keys, ping-pong
+  Key0 *KA = nullptr, *KB = nullptr;           // round-0 keys, ping-pong (key_lookup: KA keeps them for the walk, X0 / KB ping-pong)
   uint32_t *VA = nullptr, *VB = nullptr;       // round-0 values (suffix starts), ping-pong
   uint32_t *X0 = nullptr, *X1 = nullptr;       // scratch pair of the rank store; walk stage: see walk()
   uint8_t *DG0 = nullptr, *DG1 = nullptr;      // digit bytes
@@ -90,6 +90,10 @@ struct LinearPath {
   uint32_t *d_ps0 = nullptr, *d_ps1 = nullptr, *d_pv0 = nullptr, *d_pv1 = nullptr, *d_bidx = nullptr;
   int2 *d_bfast = nullptr, *d_bfast_all = nullptr;
   uint32_t *d_bidx_all = nullptr;
+  // the step table in key space (scanline.h): starts, values, indices; the ends of the needed groups
+  uint32_t *d_gend = nullptr, *d_kstart = nullptr, *d_kbidx = nullptr, *d_kbidx_all = nullptr;
+  int32_t *d_kval_p = nullptr, *d_kval_s = nullptr;
+  int2 *d_kbfast = nullptr, *d_kbfast_all = nullptr;
 
   // ---- state handed from stage to stage
   SymbolCode code;
@@ -101,9 +105,10 @@ struct LinearPath {
   Key0 *keys = nullptr, *other_keys = nullptr;
   uint32_t *vals = nullptr, *other_vals = nullptr, *slots = nullptr, *other_slots = nullptr, *adep = nullptr, *other_dep = nullptr;
   uint32_t *avals = nullptr, *spare_vals = nullptr;
-  bool classified = false;
-  size_t n_act = 0, n_large = 0, n_large_groups = 0;
+  bool classified = false, anchors_queued = false;
+  size_t n_act = 0, n_large = 0, n_large_groups = 0, n_groups = 0;
   StepTable steps{}, steps_all{};  // (steps_all: for the kernels that look up EVERY position of a stretch, scanlines())
+  StepTable ksteps{}, ksteps_all{};  // the same in key space (key_lookup)
 
   LinearPath(const wp_vocab *v_, Context *c_, wp_stats &S_, Arena &ar_, Arena &aa_, const uint8_t *text, size_t nb,
              const uint32_t *tile_prefix, size_t n_text_, size_t n_, uint32_t *cps, uint8_t *cls, int bits_, bool text_only_)
@@ -116,9 +121,14 @@ struct LinearPath {
     prune = !full && (M > 0 || text_only);
     // default layout: the needed groups are resolved along the token trie (trie.h) instead of by doubling rounds
     use_trie = text_only && !full && M > 0;
+    // ... and the walk finds its steps by the round-0 key of a position, through rank[] only for the keys of needed
+    // groups: no inverse suffix array for the whole text (scanline.h, "the step table in key space").  The debug views
+    // (which keep LCPs) keep the full rank table.
+    key_lookup = use_trie && !v->keep_debug && kKeyBits <= 32;
     sl_tiles = cdiv(n, kSlTile);
     sl_groups = cdiv(sl_tiles, kSlGroup);
     P = kStepsPerMark * M + 1;  // steps of the scanline result (scanline.h)
+    P_cap = P + 2 * M + 2;      // ... and two per needed group (at most one group per eligible token) with key_lookup
     // buckets of the step table's index: about four per step (most lookups then end at the bucket entry, scanline.h)
     const int bucket_bits = std::min(kStepBucketBitsMax, std::max(kStepBucketBits, bit_length(4 * static_cast<size_t>(P))));
     bucket_shift = std::max(0, bit_length(n) - bucket_bits);
@@ -129,7 +139,14 @@ struct LinearPath {
     // fine index: config 3, 9.3 against 9.8 ms)
     bucket_shift_all = std::max(0, bit_length(n) - kStepBucketBits);
     nbuckets_all = static_cast<unsigned>(((n - 1) >> bucket_shift_all) + 1);
-    radix_words = std::max(radix_tmp_words<uint64_t>(n), radix_tmp_words<uint32_t>(std::max<size_t>(n, kStepsPerMark * std::max(M, 1) + 1)));
+    // the key-space indices: as many buckets, on the top bits of the key (entropy-coded: near-uniform)
+    const int kb = std::min(kKeyBits, std::max(1, bit_length(n - 1) - bucket_shift));
+    const int kb_all = std::min(kKeyBits, std::max(1, bit_length(n - 1) - bucket_shift_all));
+    key_shift = kKeyBits - kb;
+    key_shift_all = kKeyBits - kb_all;
+    nkbuckets = 1u << kb;
+    nkbuckets_all = 1u << kb_all;
+    radix_words = std::max(radix_tmp_words<uint64_t>(n), radix_tmp_words<uint32_t>(std::max<size_t>(n, static_cast<size_t>(P_cap))));
     emit_tiles = cdiv(std::max<size_t>(n_text, 1), kScanTile);
     walk_blocks = cdiv(std::max<size_t>(n_text, 1), kBlock);  // (at most one anchor per position)
     sparse_emit = v->sparse_emit || EnvOptions::get().sparse_emit;
@@ -264,32 +281,42 @@ struct LinearPath {
       d_tmin_b = ref ? ar.take<int32_t>(sl_tiles + 1) : nullptr;
       d_gmin_f = ref ? ar.take<int32_t>(sl_groups + 1) : nullptr;
       d_gmin_b = ref ? ar.take<int32_t>(sl_groups + 1) : nullptr;
-      d_ps0 = ar.take<uint32_t>(P + 1);
-      d_ps1 = ar.take<uint32_t>(P + 1);
-      d_pv0 = ar.take<uint32_t>(P + 1);
-      d_pv1 = ar.take<uint32_t>(P + 1);
-      d_pval_p = ar.take<int32_t>(P + 1);
-      d_pval_s = ar.take<int32_t>(P + 1);
+      d_ps0 = ar.take<uint32_t>(P_cap + 1);
+      d_ps1 = ar.take<uint32_t>(P_cap + 1);
+      d_pv0 = ar.take<uint32_t>(P_cap + 1);
+      d_pv1 = ar.take<uint32_t>(P_cap + 1);
+      d_pval_p = ar.take<int32_t>(P_cap + 1);
+      d_pval_s = ar.take<int32_t>(P_cap + 1);
       d_bidx = ar.take<uint32_t>(static_cast<size_t>(nbuckets) + 2);
       d_bfast = ar.take<int2>(static_cast<size_t>(nbuckets) + 1);
       d_bidx_all = bucket_shift_all != bucket_shift ? ar.take<uint32_t>(static_cast<size_t>(nbuckets_all) + 2) : nullptr;
       d_bfast_all = bucket_shift_all != bucket_shift ? ar.take<int2>(static_cast<size_t>(nbuckets_all) + 1) : nullptr;
+      d_gend = key_lookup ? ar.take<uint32_t>(M + 4) : nullptr;
+      d_kstart = key_lookup ? ar.take<uint32_t>(P_cap + 1) : nullptr;
+      d_kval_p = key_lookup ? ar.take<int32_t>(P_cap + 1) : nullptr;
+      d_kval_s = key_lookup ? ar.take<int32_t>(P_cap + 1) : nullptr;
+      d_kbidx = key_lookup ? ar.take<uint32_t>(static_cast<size_t>(nkbuckets) + 2) : nullptr;
+      d_kbfast = key_lookup ? ar.take<int2>(static_cast<size_t>(nkbuckets) + 1) : nullptr;
+      d_kbidx_all = (key_lookup && key_shift_all != key_shift) ? ar.take<uint32_t>(static_cast<size_t>(nkbuckets_all) + 2) : nullptr;
+      d_kbfast_all = (key_lookup && key_shift_all != key_shift) ? ar.take<int2>(static_cast<size_t>(nkbuckets_all) + 1) : nullptr;
       if (pass == 0) ar.commit();
     }
     ar.arm(st);
   }
 
   // side stream: the anchor list (and the cleared emit array of the sparse id path) only need the class bytes; they
-  // run next to the small latency-bound kernels of the scanline stage, not next to the radix passes
-  void launch_anchors() {
+  // run next to the small latency-bound kernels of the scanline stage, not next to the radix passes (key_lookup: on
+  // the main stream, next to the needed-group searches and the trie round of the side stream, ranks_round0)
+  void launch_anchors(hipStream_t as) {
+    anchors_queued = true;
     const unsigned atiles = cdiv(n_text, kAnchorTile);
-    if (!staged_possible) WP_HIP(hipMemsetAsync(d_emit, 0x80, n_text * sizeof(int32_t), st2));
-    hipLaunchKernelGGL(anchor_count_kernel, dim3(atiles), dim3(kBlock), 0, st2, d_cls, static_cast<const uint8_t *>(nullptr),
+    if (!staged_possible) WP_HIP(hipMemsetAsync(d_emit, 0x80, n_text * sizeof(int32_t), as));
+    hipLaunchKernelGGL(anchor_count_kernel, dim3(atiles), dim3(kBlock), 0, as, d_cls, static_cast<const uint8_t *>(nullptr),
                        n_text, d_anchor_cnt);
-    device_exclusive_scan(d_anchor_cnt, d_anchor_cnt, atiles, d_anchor_tmp, c->d_scalars + 10, st2);
-    hipLaunchKernelGGL(anchor_write_kernel, dim3(atiles), dim3(kBlock), 0, st2, d_cls, static_cast<const uint8_t *>(nullptr),
+    device_exclusive_scan(d_anchor_cnt, d_anchor_cnt, atiles, d_anchor_tmp, c->d_scalars + 10, as);
+    hipLaunchKernelGGL(anchor_write_kernel, dim3(atiles), dim3(kBlock), 0, as, d_cls, static_cast<const uint8_t *>(nullptr),
                        n_text, d_anchor_cnt, d_anchors);
-    hipLaunchKernelGGL(anchor_gap_kernel, dim3(std::min<size_t>(atiles, 1024)), dim3(kBlock), 0, st2, d_anchors,
+    hipLaunchKernelGGL(anchor_gap_kernel, dim3(std::min<size_t>(atiles, 1024)), dim3(kBlock), 0, as, d_anchors,
                        c->d_scalars + 10, n_text, d_cls, hv.soft.empty() ? 1 : 0, c->d_scalars + 11);
   }
 
@@ -364,6 +391,23 @@ struct LinearPath {
     db.dg0 = DG0;
     db.dg1 = DG1;
     db.dg0_ready = DG0 != nullptr && !hist_in_keys;
+    if (key_lookup) {  // (no rank store: the last pass leaves no digits; the keys go X0 <-> KB so that KA survives)
+      Key0 *sk = reinterpret_cast<Key0 *>(X0);
+      cur = radix_sort_pairs<Key0>(sk, VA, KB, VB, n, 0, kKeyBits, d_radix_tmp, radix_words, st, &c->rstats, true,
+                                   code.uniform_bits ? 0 : 8, db, true, hist_in_keys ? &sort_plan : nullptr, KA);
+      S.hist_in_keys = hist_in_keys ? 1 : 0;
+      keys = cur ? KB : sk;
+      other_keys = cur ? sk : KB;
+      vals = cur ? VB : VA;
+      other_vals = cur ? VA : VB;
+      slots = AS0;
+      other_slots = AS1;
+      adep = AD0;
+      other_dep = AD1;
+      avals = LA;
+      spare_vals = LB;
+      return;
+    }
     if (window_store) {  // the last pass leaves the first digit of the rank store's destination partition
       db.tail_bit = kWinBits;
       db.tail_mask = (1u << (win_mid - kWinBits)) - 1u;
@@ -483,6 +527,10 @@ struct LinearPath {
       hipLaunchKernelGGL(needed_list_clamp_kernel, dim3(1), dim3(1), 0, st2, c->d_scalars + 4, static_cast<uint32_t>(list_cap),
                          c->d_scalars + 8);
       hipLaunchKernelGGL(needed_list_close_kernel, dim3(1), dim3(1), 0, st2, c->d_scalars + 4, d_ghead);
+      if (key_lookup) {  // (the group heads are overwritten by the trie round: the group ends are taken now)
+        hipLaunchKernelGGL(group_starts_kernel, dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st2, d_gfirst, d_ghead, c->d_scalars + 4, n,
+                           d_ps0 + P, d_gend);
+      }
       if (M > 0) {
         if (!use_trie) hipLaunchKernelGGL(needed_need_kernel, dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st2, nl);
         hipLaunchKernelGGL(needed_fill_kernel, dim3(1024), dim3(kBlock), 0, st2, nl, vals, n);
@@ -497,6 +545,18 @@ struct LinearPath {
     };
     // (they start when the sort ends, beside the first partition pass's histogram: started beside its scatter instead,
     // which is bandwidth-bound, they cost the scatter more than they cost the histogram now — measured)
+    if (key_lookup) {
+      // No rank store: the needed-group searches and the trie round (side stream) are the critical path now, and the
+      // anchor list (main stream: class bytes only) runs beside them.  The trie round stores a rank for every entry
+      // of the needed list — the only ranks anything reads (walk.h, step_value).
+      fork();
+      enqueue_needed_groups(nullptr);
+      trie_round_sort();
+      if (n_text > 0) launch_anchors(st);
+      WP_LAUNCH_CHECK();
+      trie_round_finish();
+      return;
+    }
     if (prune) {
       fork();
       enqueue_needed_groups(nullptr);
@@ -571,6 +631,7 @@ struct LinearPath {
   void trie_round_finish() {
     WP_HIP(hipEventSynchronize(c->evs[2]));
     n_act = c->h_scalars[4];
+    n_groups = c->h_scalars[5];
     n_large_groups = classified ? c->h_scalars[6] : 0;
     n_large = classified ? c->h_scalars[7] : 0;
     if (c->h_scalars[8] > list_cap) throw ListOverflow{c->h_scalars[8]};  // (the list was kept empty: nothing ran on it)
@@ -753,8 +814,11 @@ struct LinearPath {
     if (M > 0) {
       hipLaunchKernelGGL(mark_cover_kernel, dim3(4), dim3(kCoverThreads), 0, st, d_minfo, d_rf, d_rb, M, d_cover_f, d_cover_b);
     }
-    if (n_text > 0) launch_anchors();
+    if (n_text > 0 && !anchors_queued) launch_anchors(st2);
     hipLaunchKernelGGL(piece_starts_kernel, dim3(cdiv(std::max(M, 1), kBlock)), dim3(kBlock), 0, st, mv, n, d_ps0);
+    // (key_lookup: the starts of the needed groups wait behind the marks' starts, group_starts_kernel; extra starts
+    // leave the slot-space step function as it is — every value is evaluated at its own start)
+    const int P = this->P + (key_lookup ? 2 * static_cast<int>(n_groups) : 0);
     const int pc = radix_sort_pairs<uint32_t>(d_ps0, d_pv0, d_ps1, d_pv1, P, 0, bit_length(n), d_radix_tmp, radix_words, st, nullptr);
     uint32_t *pstart = pc ? d_ps1 : d_ps0;
     hipLaunchKernelGGL(piece_values_kernel, dim3(cdiv(static_cast<size_t>(P) * kWave, kBlock)), dim3(kBlock), 0, st, mv, pstart, P,
@@ -774,9 +838,40 @@ struct LinearPath {
       WP_LAUNCH_CHECK();
       steps_all = StepTable{pstart, d_pval_p, d_pval_s, d_bidx_all, bucket_shift_all, pack_steps, d_bfast_all};
     }
+    if (key_lookup) key_steps(pstart, P, pack_steps);
+  }
+
+  // the step table in key space (scanline.h) from the slot-space one: starts by the sorted keys, the entries inside
+  // needed groups answer kStepNeeded, two bucket indices on the top bits of the key
+  void key_steps(const uint32_t *pstart, int P, int pack_steps) {
+    const uint32_t *skeys = reinterpret_cast<const uint32_t *>(keys);
+    hipLaunchKernelGGL(key_steps_kernel, dim3(cdiv(P, kBlock)), dim3(kBlock), 0, st, pstart, d_pval_p, d_pval_s, P, skeys, d_kstart,
+                       d_kval_p, d_kval_s);
+    if (n_groups > 0) {
+      hipLaunchKernelGGL(key_steps_needed_kernel, dim3(cdiv(n_groups, kBlock)), dim3(kBlock), 0, st, d_gfirst, d_gend,
+                         static_cast<uint32_t>(n_groups), pstart, P, d_kval_p, d_kval_s);
+    }
+#ifdef WP_DEBUG_BOUNDS
+    hipLaunchKernelGGL(key_steps_check_kernel, dim3(cdiv(P, kBlock)), dim3(kBlock), 0, st, pstart, P, skeys, d_kval_p, d_kval_s);
+#endif
+    hipLaunchKernelGGL(piece_bucket_kernel, dim3(cdiv(nkbuckets + 1, kBlock)), dim3(kBlock), 0, st, d_kstart, P, key_shift, nkbuckets,
+                       d_kbidx);
+    hipLaunchKernelGGL(piece_bucket_fast_kernel, dim3(cdiv(nkbuckets, kBlock)), dim3(kBlock), 0, st, d_kbidx, d_kval_p, d_kval_s,
+                       nkbuckets, d_kbfast);
+    ksteps = StepTable{d_kstart, d_kval_p, d_kval_s, d_kbidx, key_shift, pack_steps, d_kbfast};
+    ksteps_all = ksteps;
+    if (key_shift_all != key_shift) {
+      hipLaunchKernelGGL(piece_bucket_kernel, dim3(cdiv(nkbuckets_all + 1, kBlock)), dim3(kBlock), 0, st, d_kstart, P, key_shift_all,
+                         nkbuckets_all, d_kbidx_all);
+      hipLaunchKernelGGL(piece_bucket_fast_kernel, dim3(cdiv(nkbuckets_all, kBlock)), dim3(kBlock), 0, st, d_kbidx_all, d_kval_p,
+                         d_kval_s, nkbuckets_all, d_kbfast_all);
+      ksteps_all = StepTable{d_kstart, d_kval_p, d_kval_s, d_kbidx_all, key_shift_all, pack_steps, d_kbfast_all};
+    }
+    WP_LAUNCH_CHECK();
   }
 
   // words longer than a lane should walk (walk.h, "long words"): pointer doubling instead.  Scratch: the slabs of the sort.
+  // (KA holds the round-0 keys of the key-space lookup: the walk's scratch stays out of it in every layout)
   void walk_long_words(const WalkArgs &wa, size_t n_anchors) {
     const uint32_t lw_cap = static_cast<uint32_t>(n_text / kMaxAnchorGap + 2);
     LongWord *d_lw = reinterpret_cast<LongWord *>(d_tile_scratch);
@@ -803,12 +898,13 @@ struct LinearPath {
     const uint32_t total = static_cast<uint32_t>(total64);  // <= n_text < 2^31
     WP_HIP(hipMemcpyAsync(d_lw_off, h_off.data(), sizeof(uint32_t) * (nw + 1), hipMemcpyHostToDevice, st));
     WP_HIP(hipMemsetAsync(d_lw_fail, 0, sizeof(uint32_t) * nw, st));
-    int32_t *d_lid = reinterpret_cast<int32_t *>(X0);
-    uint32_t *jump_a = X1, *jump_b = reinterpret_cast<uint32_t *>(KA);
+    int32_t *d_lid = reinterpret_cast<int32_t *>(VA);
+    uint32_t *jump_a = X1, *jump_b = X0;
     uint8_t *d_mark = reinterpret_cast<uint8_t *>(KB);
     const dim3 grid(cdiv(total, kBlock));
     WalkArgs wa_all = wa;  // (every position of the long words is looked up: the small index)
     wa_all.steps = steps_all;
+    wa_all.ksteps = ksteps_all;
     hipLaunchKernelGGL(long_word_next_kernel, grid, dim3(kBlock), 0, st, wa_all, d_lw, d_lw_off, nw, total, d_lid, jump_a, d_mark);
     WP_HIP(hipStreamSynchronize(st));  // h_off is a stack-owned upload source
     for (uint32_t reach = 1; reach < longest; reach *= 2) {  // after r rounds: chain prefixes of length 2^r
@@ -826,7 +922,7 @@ struct LinearPath {
   // long stretches without class-rule anchors ("soft" spacing chars): anchors from the matches themselves, inside the
   // long gaps of the class rule only (walk.h).  Returns the number of anchors.
   size_t cover_anchors(WalkArgs &wa) {
-    uint32_t *d_reach = X0, *d_reach_tiles = d_tile_scratch;
+    uint32_t *d_reach = VA, *d_reach_tiles = d_tile_scratch;
     uint8_t *d_aflags = reinterpret_cast<uint8_t *>(X1);
     const unsigned rtiles = cdiv(n_text, kReachTile), atiles = cdiv(n_text, kAnchorTile);
     uint32_t *d_wp_tiles = d_reach_tiles + rtiles + 1;  // first word-prefix position at or behind each tile
@@ -852,14 +948,15 @@ struct LinearPath {
     return c->h_scalars[10];
   }
 
-  // ---- greedy walk + id stream (linear.cpp:215-316).  Slabs: ids VB, id lists KA, wide list / counts KB VA (X0 / X1
-  // hold the coverage rule's reach / flags or the long words' scratch) --------------------------------------------------
+  // ---- greedy walk + id stream (linear.cpp:215-316).  Slabs: round-0 keys KA (key_lookup), ids VB, id lists X0, wide
+  // list / counts KB VA (VA / X1 hold the coverage rule's reach / flags; VA X1 X0 KB the long words' scratch) ----------
   int32_t *walk(size_t *n_ids_out) {
     int32_t *d_ids = reinterpret_cast<int32_t *>(VB);
     *n_ids_out = 0;
     if (n_text == 0) return d_ids;
     WalkArgs wa{d_cls, n_text, d_rank, steps, c->d_tok_len, hv.unk_id, d_emit, nullptr, nullptr, nullptr,
-                hv.soft.empty() ? 1 : 0, static_cast<int32_t>(hv.tokens.size())};
+                hv.soft.empty() ? 1 : 0, static_cast<int32_t>(hv.tokens.size()),
+                key_lookup ? reinterpret_cast<const uint32_t *>(KA) : nullptr, ksteps};
     S.anchor_mode = 0;
     join();  // (the anchor list of the side stream)
     fetch_scalars(c, 12);
@@ -880,7 +977,7 @@ struct LinearPath {
     // one lane per anchor (a grid sized for the worst case, every position an anchor, costs 0.35 ms of empty workgroups)
     const size_t acap = std::max<size_t>(n_anchors, 1);
     if (staged) {
-      int32_t *d_ctmp = reinterpret_cast<int32_t *>(KA);
+      int32_t *d_ctmp = reinterpret_cast<int32_t *>(X0);
       const unsigned sblocks = cdiv(acap, static_cast<size_t>(kWbWords));
       // stretches of more than kWideMin positions (class rule, hard spacing chars only: one word each) go to a whole
       // wave each first (walk.h, wide walk)
@@ -891,6 +988,7 @@ struct LinearPath {
                            c->d_scalars + 10, n_text, d_wide_list, c->d_scalars + 13);
         WalkArgs wa_all = wa;  // (every position of the wide words is looked up: the small index)
         wa_all.steps = steps_all;
+        wa_all.ksteps = ksteps_all;
         hipLaunchKernelGGL(walk_wide_kernel, dim3(std::min<size_t>(cdiv(acap, kBlock / kWave), 8192)), dim3(kBlock), 0, st, wa_all, d_anchors,
                            c->d_scalars + 10, d_wide_list, c->d_scalars + 13, d_wide_cnt);
         hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_lean_kernel<true>), dim3(sblocks), dim3(kBlock), 0, st, wa, d_anchors,
@@ -935,9 +1033,10 @@ struct LinearPath {
       WP_HIP(hipMemcpyFromSymbol(oob, HIP_SYMBOL(g_wp_oob), sizeof(oob)));
       const unsigned int zero[kBoundSites] = {};
       WP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_wp_oob), zero, sizeof(zero)));
-      if (oob[0] | oob[1] | oob[2] | oob[3]) {
+      if (oob[0] | oob[1] | oob[2] | oob[3] | oob[4]) {
         throw HipError("debug bounds: out-of-range addresses skipped: radix scatter " + std::to_string(oob[0]) + ", rank store " +
-                       std::to_string(oob[1]) + ", token id " + std::to_string(oob[2]) + ", list slot " + std::to_string(oob[3]));
+                       std::to_string(oob[1]) + ", token id " + std::to_string(oob[2]) + ", list slot " + std::to_string(oob[3]) +
+                       "; key-space step starts inside a run of equal keys " + std::to_string(oob[4]));
       }
       S.reserved0 = 1;  // this is the bounds-checking build
     }

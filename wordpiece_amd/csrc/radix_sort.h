@@ -531,7 +531,10 @@ template <typename KeyT>
 int radix_sort_ranges(KeyT *k0, uint32_t *v0, KeyT *k1, uint32_t *v1, size_t n, const BitRange *ranges,
                       int nranges, uint32_t *tmp, size_t tmp_words, hipStream_t st, RadixStats *stats,
                       bool identity_vals = false, int uniform_low_bits = 0, DigitBytes db = DigitBytes(),
-                      bool input_order_free = false, const RadixPlan *first_hist = nullptr) {
+                      bool input_order_free = false, const RadixPlan *first_hist = nullptr,
+                      const KeyT *k_first = nullptr) {
+  // k_first != nullptr: the first pass reads its keys there instead of k0, which the later passes use as the second
+  // buffer of the ping-pong — the input keys survive the sort (linear_path.h: the walk's key-space lookup reads them)
   // input_order_free: nothing depends on the order the input is in (a sort from scratch, NOT one pass of a sort that a
   // caller runs as several calls, like the second partition pass of the rank store): the first pass may rank by atomics
   int cur = 0;
@@ -558,7 +561,8 @@ int radix_sort_ranges(KeyT *k0, uint32_t *v0, KeyT *k1, uint32_t *v1, size_t n, 
   for (size_t pi = 0; pi < passes.size(); pi++) {
     const int pass = static_cast<int>(pi), b = passes[pi].bit;
     const uint32_t mask = passes[pi].mask;
-    KeyT *ki = cur ? k1 : k0, *ko = cur ? k0 : k1;
+    const KeyT *ki = (pi == 0 && k_first) ? k_first : (cur ? k1 : k0);
+    KeyT *ko = cur ? k0 : k1;
     uint32_t *vi = cur ? v1 : v0, *vo = cur ? v0 : v1;
     uint32_t *chunk_sums = chunk_sums0 + cs_words * static_cast<size_t>(pass % kMaxZeroedPasses);
     if (pass >= kMaxZeroedPasses) WP_HIP(hipMemsetAsync(chunk_sums, 0, sizeof(uint32_t) * cs_words, st));
@@ -619,10 +623,10 @@ template <typename KeyT>
 int radix_sort_pairs(KeyT *k0, uint32_t *v0, KeyT *k1, uint32_t *v1, size_t n, int begin_bit, int end_bit,
                      uint32_t *tmp, size_t tmp_words, hipStream_t st, RadixStats *stats, bool identity_vals = false,
                      int uniform_low_bits = 0, DigitBytes db = DigitBytes(), bool input_order_free = false,
-                     const RadixPlan *first_hist = nullptr) {
+                     const RadixPlan *first_hist = nullptr, const KeyT *k_first = nullptr) {
   BitRange r{begin_bit, end_bit};
   return radix_sort_ranges<KeyT>(k0, v0, k1, v1, n, &r, 1, tmp, tmp_words, st, stats, identity_vals,
-                                 uniform_low_bits, db, input_order_free, first_hist);
+                                 uniform_low_bits, db, input_order_free, first_hist, k_first);
 }
 
 }  // namespace wp

@@ -462,7 +462,9 @@ __global__ __launch_bounds__(kBlock) void piece_bucket_kernel(const uint32_t *__
 // for most slots, and a short binary search over those few starts plus one value load for the others, instead of
 // rank -> bucket pair -> starts -> value.  (Measured and dropped: a 32-byte record per bucket with one or two inner
 // starts, which makes the second case one more load as well — the walk was 4 % slower with it.)
-constexpr int32_t kStepSlow = static_cast<int32_t>(0x80000000u);  // (values are -1 or >= 0; a slow entry is < -1)
+constexpr int32_t kStepSlow = static_cast<int32_t>(0x80000000u);  // (values are >= -2; a slow entry is < -2)
+// value of the key-space step table (below) for the round-0 key of a needed group: the answer depends on the slot
+constexpr int32_t kStepNeeded = -2;
 __global__ __launch_bounds__(kBlock) void piece_bucket_fast_kernel(const uint32_t *__restrict__ bidx,
                                                                    const int32_t *__restrict__ pval_prefix,
                                                                    const int32_t *__restrict__ pval_suffix, unsigned nbuckets,
@@ -502,10 +504,11 @@ __device__ __forceinline__ int step_lookup(const StepTable &st, uint32_t r) {
   return lo - 1;
 }
 
-// value of the step containing SA slot r, for a word-prefix position or not (linear.cpp:243-250's two arrays)
+// value of the step containing SA slot r, for a word-prefix position or not (linear.cpp:243-250's two arrays).
+// The same function serves the key-space table (below), whose values may also be kStepNeeded.
 __device__ __forceinline__ int32_t step_raw(const StepTable &st, uint32_t r, bool prefix) {
   const int2 e = st.bfast[r >> st.shift];
-  if (e.x >= -1) return prefix ? e.x : e.y;
+  if (e.x >= kStepNeeded) return prefix ? e.x : e.y;
   const int n = e.x & 0x7fffffff;
   int lo = e.y, hi = e.y + n;
   while (lo < hi) {  // first step of the bucket with start > r
@@ -513,6 +516,80 @@ __device__ __forceinline__ int32_t step_raw(const StepTable &st, uint32_t r, boo
     if (st.pstart[md] <= r) lo = md + 1; else hi = md;
   }
   return prefix ? st.pval_prefix[lo - 1] : st.pval_suffix[lo - 1];
+}
+
+// ---- the step table in key space (default layout: S = text . 1, trie refinement) --------------------------------------
+// A suffix's slot is its rank, and the step values change from slot to slot only at a boundary between two distinct
+// round-0 keys (the reach of a short token is a range of keys, prune.h) or inside a needed group (long tokens, trie.h).
+// So outside the needed groups a position's value depends on its round-0 key alone, and the walk looks it up by that
+// key (walk.h, step_value) — no inverse suffix array is needed.  The slot-space list of step starts carries, besides the
+// marks' starts, the first slot of every needed group and the first slot behind it (group_starts_kernel), so that
+//   kstart[k] = sorted_keys[pstart[k]]  (kstart[0] = 0),   kval[k] = pval[k], or kStepNeeded inside a needed group,
+// is a step function of the key: the last entry with kstart <= K gives the value of the last slot of key K's run,
+// which is the value of every slot of that run, or kStepNeeded for a needed key.  (Equal keys may repeat in kstart;
+// for a run that is not a needed group they carry equal values — key_steps_check_kernel counts the exceptions.)
+
+// slot-space starts of the needed groups, behind the marks' starts: group g covers slots [gfirst[g], gfirst[g] + its
+// list entries); gend gets the end (ghead: list positions of the groups, ghead[n_groups] = list length)
+__global__ __launch_bounds__(kBlock) void group_starts_kernel(const uint32_t *__restrict__ gfirst,
+                                                              const uint32_t *__restrict__ ghead,
+                                                              const uint32_t *__restrict__ totals, size_t n,
+                                                              uint32_t *__restrict__ pstart_tail, uint32_t *__restrict__ gend) {
+  const uint32_t g = blockIdx.x * kBlock + threadIdx.x;
+  if (g >= totals[1]) return;
+  const uint32_t f = gfirst[g], e = f + (ghead[g + 1] - ghead[g]);
+  const uint32_t last = static_cast<uint32_t>(n - 1);
+  pstart_tail[2 * static_cast<size_t>(g)] = f;
+  pstart_tail[2 * static_cast<size_t>(g) + 1] = min(e, last);  // (e == n: a start inside the group, harmless)
+  gend[g] = e;
+}
+
+__global__ __launch_bounds__(kBlock) void key_steps_kernel(const uint32_t *__restrict__ pstart, const int32_t *__restrict__ pval_prefix,
+                                                           const int32_t *__restrict__ pval_suffix, int P,
+                                                           const uint32_t *__restrict__ sorted_keys, uint32_t *__restrict__ kstart,
+                                                           int32_t *__restrict__ kval_prefix, int32_t *__restrict__ kval_suffix) {
+  const int k = blockIdx.x * kBlock + threadIdx.x;
+  if (k >= P) return;
+  kstart[k] = k == 0 ? 0u : sorted_keys[pstart[k]];
+  kval_prefix[k] = pval_prefix[k];
+  kval_suffix[k] = pval_suffix[k];
+}
+
+// first index in [0, P) with pstart >= x
+__device__ __forceinline__ int starts_lower_bound(const uint32_t *__restrict__ pstart, int P, uint32_t x) {
+  int lo = 0, hi = P;
+  while (lo < hi) {
+    const int md = (lo + hi) >> 1;
+    if (pstart[md] < x) lo = md + 1; else hi = md;
+  }
+  return lo;
+}
+
+// the entries whose start lies inside a needed group answer kStepNeeded (one thread per group)
+__global__ __launch_bounds__(kBlock) void key_steps_needed_kernel(const uint32_t *__restrict__ gfirst,
+                                                                  const uint32_t *__restrict__ gend, uint32_t n_groups,
+                                                                  const uint32_t *__restrict__ pstart, int P,
+                                                                  int32_t *__restrict__ kval_prefix, int32_t *__restrict__ kval_suffix) {
+  const uint32_t g = blockIdx.x * kBlock + threadIdx.x;
+  if (g >= n_groups) return;
+  const int k0 = starts_lower_bound(pstart, P, gfirst[g]), k1 = starts_lower_bound(pstart, P, gend[g]);
+  for (int k = k0; k < k1; k++) {
+    kval_prefix[k] = kStepNeeded;
+    kval_suffix[k] = kStepNeeded;
+  }
+}
+
+// bounds-checking build: a step that starts strictly inside a run of equal keys that is not a needed group must carry
+// the values of the step before it (else the key-space table would be wrong for that run)
+__global__ __launch_bounds__(kBlock) void key_steps_check_kernel(const uint32_t *__restrict__ pstart, int P,
+                                                                 const uint32_t *__restrict__ sorted_keys,
+                                                                 const int32_t *__restrict__ kval_prefix,
+                                                                 const int32_t *__restrict__ kval_suffix) {
+  const int k = blockIdx.x * kBlock + threadIdx.x;
+  if (k == 0 || k >= P) return;
+  const uint32_t s = pstart[k];
+  if (s == 0 || kval_prefix[k] == kStepNeeded || sorted_keys[s - 1] != sorted_keys[s]) return;
+  wp_in_bounds(kval_prefix[k] == kval_prefix[k - 1] && kval_suffix[k] == kval_suffix[k - 1], kSiteKeyStep);
 }
 
 // debug / parity: expand the step functions to the reference's per-slot arrays

@@ -32,7 +32,29 @@ struct WalkArgs {
   const uint32_t *ns_from_tile;  // with aflags: first non-space position >= t * kReachTile (n_text: none)
   int all_hard;  // no spacing char occurs inside an eligible multi-char token (every sane vocabulary)
   int32_t n_tokens;  // vocab lines (debug build: range check of the ids that come out of the step table)
+  // default layout: the step table in key space and the round-0 key of every position (scanline.h); nullptr: every
+  // lookup goes through rank[] (reference layout, debug views).  rank[] then only holds the slots of needed groups.
+  const uint32_t *pkey;
+  StepTable ksteps;
 };
+
+// The value of the step for text position q, from the loads issued for it: the position's round-0 key and rank (the
+// rank is loaded whether it is needed or not: the key-space answer decides that only after two more loads, and a load
+// behind that branch would add a whole chain to the lanes that take it).  The slot-space table answers only for the
+// keys of needed groups — and for every position when the key-space table is off.
+__device__ __forceinline__ int32_t step_value_of(const WalkArgs &a, uint32_t key, uint32_t r, bool prefix) {
+  if (a.pkey) {
+    const int32_t v = step_raw(a.ksteps, key, prefix);
+    if (v != kStepNeeded) return v;
+  }
+  return step_raw(a.steps, r, prefix);
+}
+__device__ __forceinline__ uint32_t step_key(const WalkArgs &a, size_t q) { return a.pkey ? a.pkey[q] : 0u; }
+__device__ __forceinline__ int32_t step_value(const WalkArgs &a, size_t q, bool prefix) {
+  const uint32_t key = step_key(a, q);
+  const uint32_t r = rank_of(a.rank[q]);
+  return step_value_of(a, key, r, prefix);
+}
 
 __device__ __forceinline__ bool w_space(const WalkArgs &a, size_t p) { return a.cls[p] & kClsSpace; }
 __device__ __forceinline__ bool w_word_prefix(const WalkArgs &a, size_t p) {  // linear.cpp:215-219
@@ -189,8 +211,9 @@ __device__ __forceinline__ bool walk_finish(const WalkArgs &a, WalkState &s, Out
 template <typename Out>
 __device__ __forceinline__ bool walk_step(const WalkArgs &a, WalkState &s, Out &o) {
   const StepWin W = step_window(a, s.p);
+  const uint32_t key = step_key(a, s.p);
   const uint32_t r = rank_of(a.rank[s.p]);
-  return walk_finish(a, s, o, W, step_raw(a.steps, r, step_word_prefix(a, W, s.p)));
+  return walk_finish(a, s, o, W, step_value_of(a, key, r, step_word_prefix(a, W, s.p)));
 }
 
 template <typename Out>
@@ -410,7 +433,7 @@ __global__ __launch_bounds__(kBlock) void reach_kernel(WalkArgs a, uint32_t *__r
     if (q < a.n_text) {
       uint32_t r = static_cast<uint32_t>(q);
       if (!w_space(a, q)) {
-        const int32_t raw = step_raw(a.steps, rank_of(a.rank[q]), (a.cls[q] & kClsWordPrefix) != 0);
+        const int32_t raw = step_value(a, q, (a.cls[q] & kClsWordPrefix) != 0);
         if (step_id(a.steps, raw) != -1) r += static_cast<uint32_t>(step_len(a.steps, raw, a.tok_len));
       }
       reach[q] = r;
@@ -623,7 +646,7 @@ __global__ __launch_bounds__(kBlock) void long_word_next_kernel(WalkArgs a, cons
   int32_t id = -2;
   uint32_t nx = j;
   if (!w_space(a, p)) {
-    const int32_t raw = step_raw(a.steps, rank_of(a.rank[p]), (a.cls[p] & kClsWordPrefix) != 0);
+    const int32_t raw = step_value(a, p, (a.cls[p] & kClsWordPrefix) != 0);
     id = step_id(a.steps, raw);
     if (id != -1) {
       const uint32_t len = static_cast<uint32_t>(step_len(a.steps, raw, a.tok_len));
@@ -765,7 +788,7 @@ __global__ __launch_bounds__(kBlock) void walk_wide_kernel(WalkArgs a, const uin
         id[j] = -1;
         jp[j] = kEnd;
         if (q < e) {
-          const int32_t raw = step_raw(a.steps, rank_of(a.rank[q]), (a.cls[q] & kClsWordPrefix) != 0);
+          const int32_t raw = step_value(a, q, (a.cls[q] & kClsWordPrefix) != 0);
           int32_t t = step_id(a.steps, raw);
           if (!wp_in_bounds(t >= -1 && t < a.n_tokens, kSiteTokenId)) t = -1;
           id[j] = t;
@@ -1024,10 +1047,11 @@ __global__ __launch_bounds__(kBlock) void walk_lean_kernel(WalkArgs a, const uin
     if (active) {
       bool done = true;
       if (p < end) {
+        const uint32_t key = step_key(a, p);
         const uint32_t r = rank_of(a.rank[p]);
         uint32_t cw[4];  // class bytes of p .. p + 15 (the array has 16 bytes of slack behind the text)
         __builtin_memcpy(cw, a.cls + p, 16);
-        const int32_t raw = step_raw(a.steps, r, (cw[0] & kClsWordPrefix) != 0);
+        const int32_t raw = step_value_of(a, key, r, (cw[0] & kClsWordPrefix) != 0);
         const int32_t id = step_id(a.steps, raw);
         bool fast = id >= 0 && wp_in_bounds(id < a.n_tokens, kSiteTokenId);
         uint32_t len = 0, p2 = 0, f = 0;

@@ -173,6 +173,10 @@ int64_t wp_vocab_token_utf8(const wp_vocab *v, int64_t i, char *buf, size_t cap)
                                  kernels contribute ids (words longer than a lane walks);
                                  otherwise every workgroup of the walk leaves one compact id list.
                                  Same token ids either way (also env WP_SPARSE_EMIT=1). */
+#define WP_OPT_INDEXED_ROUND0 12 /* 1: round 0 of the suffix sort moves (key, index) records in the default
+                                 layout too.  Default 0: there it sorts the keys alone and takes the
+                                 positions it needs from a candidate list the key builder leaves (the
+                                 suffixes whose key is the key of a long token).  Same token ids. */
 int wp_set_option(wp_vocab *v, int option, int64_t value);
 
 /* ---- statistics of the last encode on this handle (for bench.py / roofline) ---- */
@@ -204,7 +208,8 @@ typedef struct {
                                  eligible token longer than the key — the only ones that go on to
                                  round 1 (-1: every tied group does, e.g. full depth)          */
   int32_t key_bits;           /* bits of the codeword stream in a round-0 key; keys of up to 32 bits
-                                 are sorted as 8-byte (key, index) records, longer ones as 12-byte */
+                                 are sorted as 4-byte keys alone (default layout, see round0_keys_only)
+                                 or as 8-byte (key, index) records, longer ones as 12-byte records */
   int32_t staged_emit;        /* 1: ids left the walk as per-workgroup lists (see WP_OPT_SPARSE_EMIT) */
   int32_t rank_in_pass;       /* 1: the ranks of round 0 were computed inside the first partition pass of the rank
                                  store (one more full-size launch of the radix scatter, not in radix_passes) */
@@ -215,6 +220,9 @@ typedef struct {
   int32_t hist_in_keys;       /* 1: the key builder took the histogram of the sort's first pass (no digit bytes for it) */
   int64_t radix_pass_bytes;   /* algorithmic bytes of the counted radix scatter launches: record read (without the index
                                  column where the pass makes it up) + record written + digit byte written */
+  int64_t round0_candidates;  /* keys-only round 0: suffixes whose key is the key of a long token (the candidate list the
+                                 needed groups take their positions from); -1 when round 0 sorted (key, index) records */
+  int32_t round0_keys_only;   /* 1: round 0 sorted the keys alone (no index column; WP_OPT_INDEXED_ROUND0 turns it off) */
 } wp_stats;
 int wp_get_stats(const wp_vocab *v, wp_stats *out);
 

@@ -40,7 +40,8 @@ enum BoundSite {
   kSiteTokenId = 2,
   kSiteListSlot = 3,
   kSiteKeyStep = 4,
-  kBoundSites = 5
+  kSiteCandRun = 5,  // (no address either: a long token's key whose candidate run is not as long as its group)
+  kBoundSites = 6
 };
 #ifdef WP_DEBUG_BOUNDS
 __device__ unsigned int g_wp_oob[kBoundSites];

@@ -139,14 +139,15 @@ static int bit_length(uint64_t v) {
 }
 
 constexpr int kScalars = 32;
+constexpr int kScalarCand = 24;  // d_scalars word: entries of the keys-only round 0's candidate list (linear_path.h)
 
 struct Context {
   int device = 0;
   hipStream_t stream = nullptr;
   hipStream_t stream2 = nullptr;  // side stream: latency-bound helpers overlap the bandwidth-bound kernels
   hipStream_t stream3 = nullptr;  // second side stream: the large-group path of the trie round beside its LDS sort
-  hipEvent_t evs[7] = {};         // fork / join / scalars fetched / side stream done with the sorted keys / partition passes queued /
-                                  // trie nodes known / large groups sorted
+  hipEvent_t evs[9] = {};         // fork / join / scalars fetched / side stream done with the sorted keys / partition passes queued /
+                                  // trie nodes known / large groups sorted / key builder done / candidate count fetched
   // vocab tables on the device
   uint32_t *d_stream = nullptr, *d_elig_start = nullptr, *d_elig_info = nullptr, *d_soft = nullptr;
   uint32_t *d_vocab_word_idx = nullptr, *d_vocab_word_bits = nullptr;  // the vocabulary's words of the alphabet bitmap
@@ -224,6 +225,7 @@ struct wp_vocab {
   bool arena_guard = false;
   bool sparse_emit = false;  // WP_OPT_SPARSE_EMIT: ids through the per-position emit array even where per-workgroup lists would do
   bool vocab_in_s = false;  // WP_OPT_VOCAB_IN_S: always the reference's S = text . 1 . vocab layout
+  bool indexed_round0 = false;  // WP_OPT_INDEXED_ROUND0: the (key, index) round-0 sort also where keys alone would do
   int n_devices = 1;  // WP_OPT_DEVICES: GPUs wp_linear_encode shards a host buffer over (-1: all visible)
   wp_stats stats{};
   ~wp_vocab();

@@ -588,6 +588,106 @@ __device__ __forceinline__ size_t wave_key_gallop(const Key0 *__restrict__ keys,
   return n;  // (not reached: the second phase always returns)
 }
 
+// ---- long-token keys (keys-only round 0 of the key-space lookup, linear_path.h) --------------------------------------
+// Only the suffixes whose round-0 key is the key of a long eligible token (prune.h: its code stream is longer than
+// the key) ever need their text position after round 0: they are the members of the needed groups (and of the
+// singletons / groups over the depth cap with such a key).  The key builder tests every key it makes against the set
+// of those keys — a 2-hash bitmap filter in LDS first, the exact set (open addressing in an L2-resident table) for
+// the few that pass — and leaves (slot of the key in the table, position) for each member: a "candidate list"
+// that lets the round-0 sort drop its value column.  A workgroup writes its members at the start of its own tile's
+// range of the list and their count per workgroup; a scan and cand_compact_kernel pack them (one atomic per
+// workgroup on one counter serialised: 19.5 k of them made the key builder 0.15 ms slower on 1e8 symbols).
+// (32-bit keys only: the key-space lookup needs kKeyBits <= 32.)
+constexpr int kCandFilterBits = 17;                                    // 2^17 bits: 16 KB of LDS
+constexpr uint32_t kCandFilterWords = (1u << kCandFilterBits) / 32u;
+struct CandSet {
+  const uint32_t *filter = nullptr;            // kCandFilterWords words; nullptr: no candidate list
+  const unsigned long long *table = nullptr;   // (1 << 32) | key per occupied slot, 0 = empty; 2^table_bits slots
+  int table_bits = 0;
+  uint32_t *slot = nullptr, *pos = nullptr;    // the list: slot of the key in the table, text position (n entries)
+  uint32_t *bcount = nullptr;                  // per workgroup: members written from slot / pos [blockIdx.x * tile] on
+  size_t tile = 0;                             // positions per workgroup of the key builder
+};
+__host__ __device__ inline uint32_t cand_hash(uint32_t key, int bits) { return (key * 0x9E3779B1u) >> (32 - bits); }
+__device__ __forceinline__ uint32_t cand_f1(uint32_t key) { return (key * 0x85EBCA6Bu) >> (32 - kCandFilterBits); }
+__device__ __forceinline__ uint32_t cand_f2(uint32_t key) { return (key * 0xC2B2AE35u) >> (32 - kCandFilterBits); }
+__device__ __forceinline__ bool cand_filter_hit(const uint32_t *f, uint32_t key) {
+  const uint32_t a = cand_f1(key), b = cand_f2(key);
+  return ((f[a >> 5] >> (a & 31u)) & (f[b >> 5] >> (b & 31u)) & 1u) != 0u;
+}
+// slot of key in the exact set, or ~0u (the table is at most half full: the probe ends at an empty slot)
+__device__ __forceinline__ uint32_t cand_find(const unsigned long long *__restrict__ table, int bits, uint32_t key) {
+  const uint32_t mask = (1u << bits) - 1u;
+  const unsigned long long want = (1ull << 32) | key;
+  for (uint32_t h = cand_hash(key, bits);; h = (h + 1u) & mask) {
+    const unsigned long long e = table[h];
+    if (e == want) return h;
+    if (e == 0ull) return ~0u;
+  }
+}
+__device__ __forceinline__ void cand_load_filter(const CandSet &cs, uint32_t *sfilter, int threads) {
+  for (uint32_t i = threadIdx.x; i < kCandFilterWords; i += static_cast<uint32_t>(threads)) sfilter[i] = cs.filter[i];
+}
+// Every thread of the workgroup: its ITEMS keys at positions pos0 + j * step (< n) against the set; the members go to
+// the workgroup's own range of the list (at most one per position of its tile: the range cannot overflow).  Call from
+// every thread (two barriers), after the filter is in LDS.
+template <int ITEMS, int THREADS, typename K>
+__device__ __forceinline__ void cand_append(const CandSet &cs, const uint32_t *sfilter, const K (&k)[ITEMS], size_t pos0,
+                                            size_t step, size_t n, uint32_t *swave) {
+  constexpr int WAVES = THREADS / kWave;
+  // (the probes of the exact set loop over the lane's own filter hits: a loop over j with a probe inside serialised
+  // ITEMS L2 round trips per wave, since nearly every wave has some lane past the filter at every j)
+  uint32_t pass = 0, hit = 0;
+#pragma unroll
+  for (int j = 0; j < ITEMS; j++) {
+    if (pos0 + j * step < n && cand_filter_hit(sfilter, static_cast<uint32_t>(k[j]))) pass |= 1u << j;
+  }
+  while (pass) {
+    const int j = __ffs(pass) - 1;
+    pass &= pass - 1u;
+    if (cand_find(cs.table, cs.table_bits, static_cast<uint32_t>(k[j])) != ~0u) hit |= 1u << j;
+  }
+  const uint32_t cnt = static_cast<uint32_t>(__popc(hit));
+  const uint32_t inc = wave_incl_sum(cnt);
+  const int lane = lane_id(), w = wave_id();
+  if (lane == kWave - 1) swave[w] = inc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t tot = 0;
+    for (int i = 0; i < WAVES; i++) {
+      const uint32_t c = swave[i];
+      swave[i] = tot;
+      tot += c;
+    }
+    cs.bcount[blockIdx.x] = tot;
+  }
+  __syncthreads();
+  size_t off = static_cast<size_t>(blockIdx.x) * cs.tile + swave[w] + inc - cnt;
+  while (hit) {
+    const int j = __ffs(hit) - 1;
+    hit &= hit - 1u;
+    if (wp_in_bounds(off < n, kSiteListSlot) && off < n) {  // (cannot fail: no more members than positions below n)
+      cs.slot[off] = cand_find(cs.table, cs.table_bits, static_cast<uint32_t>(k[j]));
+      cs.pos[off] = static_cast<uint32_t>(pos0 + j * step);
+    }
+    off++;
+  }
+}
+
+// packs the workgroups' ranges (bcount: counts, boff: their exclusive scan) into one list; one workgroup per range
+__global__ __launch_bounds__(kBlock) void cand_compact_kernel(const uint32_t *__restrict__ slot, const uint32_t *__restrict__ pos,
+                                                              const uint32_t *__restrict__ bcount,
+                                                              const uint32_t *__restrict__ boff, size_t tile, size_t n,
+                                                              uint32_t *__restrict__ slot_out, uint32_t *__restrict__ pos_out) {
+  const size_t src = static_cast<size_t>(blockIdx.x) * tile, dst = boff[blockIdx.x];
+  const uint32_t c = bcount[blockIdx.x];
+  for (uint32_t i = threadIdx.x; i < c; i += kBlock) {
+    if (!wp_in_bounds(src + i < n && dst + i < n, kSiteListSlot) || src + i >= n || dst + i >= n) continue;
+    slot_out[dst + i] = slot[src + i];
+    pos_out[dst + i] = pos[src + i];
+  }
+}
+
 // Round-0 keys: the first 63 bits of the codeword stream of every suffix (most significant bit
 // first).  Positions past the end read symbol 0, whose codeword is the smallest, so a shorter
 // suffix sorts first.
@@ -600,10 +700,12 @@ constexpr int kKeyItems = 8;
 constexpr int kKeyTile = kBlock * kKeyItems;
 constexpr int kKeyHalo = 64;
 __device__ __forceinline__ int key_pad(int p) { return p + (p >> 3); }
-template <typename SymT>
+// CAND: the candidate list (decode.h, CandSet) — a template parameter so that the plain form keeps its LDS footprint
+// (16 KB more for the filter: config 3's builder, which takes no list, was 3 % slower with it)
+template <typename SymT, bool CAND>
 __global__ __launch_bounds__(kBlock) void build_keys0_kernel(const SymT *__restrict__ sym, size_t n, DevCode code,
                                                              Key0 *__restrict__ keys,
-                                                             uint8_t *__restrict__ dig0) {
+                                                             uint8_t *__restrict__ dig0, CandSet cs) {
   constexpr int kSymSlots = kKeyTile + kKeyHalo;
   __shared__ uint32_t ss[kSymSlots + kSymSlots / 8 + 1];
   __shared__ uint32_t stab[256];  // (len << 16) | codeword
@@ -644,6 +746,16 @@ __global__ __launch_bounds__(kBlock) void build_keys0_kernel(const SymT *__restr
     }
   }
   __syncthreads();
+  if (CAND) {  // the candidate list: the keys this thread stores, against the long-token set
+    __shared__ uint32_t sfilter[kCandFilterWords];
+    __shared__ uint32_t swave[kBlock / kWave + 1];
+    cand_load_filter(cs, sfilter, kBlock);
+    __syncthreads();
+    Key0 kk[kKeyItems];
+#pragma unroll
+    for (int j = 0; j < kKeyItems; j++) kk[j] = skey[key_pad(j * kBlock + threadIdx.x)];
+    cand_append<kKeyItems, kBlock>(cs, sfilter, kk, base + threadIdx.x, kBlock, n, swave);
+  }
 #pragma unroll
   for (int j = 0; j < kKeyItems; j++) {
     const int li = j * kBlock + threadIdx.x;
@@ -677,11 +789,14 @@ constexpr int kKeys8MinLen = (kKeyBits + kKeys8Items) / (kKeys8Items + 1);
 __global__ __launch_bounds__(kKeys8Threads) void build_keys0_u8_kernel(const uint8_t *__restrict__ sym, size_t n, DevCode code,
                                                                 Key0 *__restrict__ keys, uint8_t *__restrict__ dig0,
                                                                 uint32_t *__restrict__ hist_table,
-                                                                uint32_t *__restrict__ hist_chunk_sums) {
+                                                                uint32_t *__restrict__ hist_chunk_sums, CandSet cs) {
   static_assert(sizeof(Key0) == 4, "register form of the key builder: 32-bit keys");
   __shared__ uint32_t stab[256];  // (len << 16) | codeword
   constexpr int WAVES = kKeys8Threads / kWave;
   __shared__ uint32_t shist[WAVES][kRadixBins];
+  __shared__ uint32_t sfilter[kCandFilterWords];  // (the candidate list's filter, when cs.filter)
+  __shared__ uint32_t swave[WAVES + 1];
+  if (cs.filter) cand_load_filter(cs, sfilter, kKeys8Threads);
   const int ub = code.uniform_bits > 0 ? code.uniform_bits : 0;
   if (threadIdx.x < 256) {
     if (hist_table) {
@@ -759,8 +874,7 @@ __global__ __launch_bounds__(kKeys8Threads) void build_keys0_u8_kernel(const uin
       if (cnt) atomicAdd(&hist_chunk_sums[static_cast<size_t>(blockIdx.x / kColChunk) * kRadixBins + threadIdx.x], cnt);
     }
   }
-  if (p0 >= n) return;
-  if (p0 + kKeys8Items <= n) {
+  if (p0 < n && p0 + kKeys8Items <= n) {
 #pragma unroll
     for (int q = 0; q < kKeys8Items / 4; q++) {
       *reinterpret_cast<uint4 *>(keys + p0 + 4 * q) = make_uint4(k[4 * q], k[4 * q + 1], k[4 * q + 2], k[4 * q + 3]);
@@ -773,7 +887,7 @@ __global__ __launch_bounds__(kKeys8Threads) void build_keys0_u8_kernel(const uin
       }
       *reinterpret_cast<uint4 *>(dig0 + p0) = make_uint4(d[0], d[1], d[2], d[3]);
     }
-  } else {
+  } else if (p0 < n) {
 #pragma unroll
     for (int j = 0; j < kKeys8Items; j++) {
       if (p0 + j < n) {
@@ -782,6 +896,8 @@ __global__ __launch_bounds__(kKeys8Threads) void build_keys0_u8_kernel(const uin
       }
     }
   }
+  // (behind the key stores: they leave while the workgroup waits for its place in the list; the filter: barrier above)
+  if (cs.filter) cand_append<kKeys8Items, kKeys8Threads>(cs, sfilter, k, p0, 1, n, swave);
 }
 
 }  // namespace wp

@@ -148,6 +148,7 @@ int wp_set_option(wp_vocab *v, int option, int64_t value) {
     case WP_OPT_ARENA_GUARD: v->arena_guard = value != 0; return WP_OK;
     case WP_OPT_VOCAB_IN_S: v->vocab_in_s = value != 0; return WP_OK;
     case WP_OPT_SPARSE_EMIT: v->sparse_emit = value != 0; return WP_OK;
+    case WP_OPT_INDEXED_ROUND0: v->indexed_round0 = value != 0; return WP_OK;
     case WP_OPT_DEVICES: v->n_devices = value < 0 ? -1 : static_cast<int>(std::max<int64_t>(value, 1)); return WP_OK;
   }
   g_last_error = "unknown option";

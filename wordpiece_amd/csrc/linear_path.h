@@ -53,7 +53,7 @@ struct LinearPath {
   // ---- derived
   hipStream_t st, st2;
   const HostVocab &hv;
-  bool full, prune, use_trie, key_lookup, window_store, use_digit_bytes, staged_possible, sparse_emit;
+  bool full, prune, use_trie, key_lookup, keys_only, window_store, use_digit_bytes, staged_possible, sparse_emit;
   uint32_t need_depth;
   int M, P, P_cap, bucket_shift, bucket_shift_all, key_shift, key_shift_all, hb_n, win_mid;
   unsigned sl_tiles, sl_groups, nbuckets, nbuckets_all, nkbuckets, nkbuckets_all;
@@ -62,7 +62,7 @@ struct LinearPath {
   // ---- device buffers.  n-sized "slabs" of 4 bytes per symbol change roles from stage to stage (see plan()).
   SymT *d_sym = nullptr, *d_vsym = nullptr;
   Key0 *KA = nullptr, *KB = nullptr;           // round-0 keys, ping-pong (key_lookup: KA keeps them for the walk, X0 / KB ping-pong)
-  uint32_t *VA = nullptr, *VB = nullptr;       // round-0 values (suffix starts), ping-pong
+  uint32_t *VA = nullptr, *VB = nullptr;       // round-0 values (suffix starts), ping-pong (keys_only: the candidate list)
   uint32_t *X0 = nullptr, *X1 = nullptr;       // scratch pair of the rank store; walk stage: see walk()
   uint8_t *DG0 = nullptr, *DG1 = nullptr;      // digit bytes
   RankEntry *d_rank = nullptr;
@@ -94,6 +94,12 @@ struct LinearPath {
   uint32_t *d_gend = nullptr, *d_kstart = nullptr, *d_kbidx = nullptr, *d_kbidx_all = nullptr;
   int32_t *d_kval_p = nullptr, *d_kval_s = nullptr;
   int2 *d_kbfast = nullptr, *d_kbfast_all = nullptr;
+  // keys-only round 0 (decode.h, CandSet): the long-token key set, the runs of its slots in the sorted candidate list,
+  // and per needed group the start of its run
+  unsigned long long *d_cand_table = nullptr;
+  uint32_t *d_cand_filter = nullptr, *d_cand_lo = nullptr, *d_cand_hi = nullptr, *d_gcand = nullptr;
+  uint32_t *d_cand_bcnt = nullptr, *d_cand_boff = nullptr, *d_cand_scan = nullptr;  // per key-builder workgroup
+  int cand_bits = 0;
 
   // ---- state handed from stage to stage
   SymbolCode code;
@@ -109,6 +115,9 @@ struct LinearPath {
   size_t n_act = 0, n_large = 0, n_large_groups = 0, n_groups = 0;
   StepTable steps{}, steps_all{};  // (steps_all: for the kernels that look up EVERY position of a stretch, scanlines())
   StepTable ksteps{}, ksteps_all{};  // the same in key space (key_lookup)
+  CandSet cand{};                    // keys_only: the set and the list the key builder appends to
+  CandRuns cand_runs{};              // keys_only: the sorted list as the needed-group kernels read it
+  size_t n_cand = 0;
 
   LinearPath(const wp_vocab *v_, Context *c_, wp_stats &S_, Arena &ar_, Arena &aa_, const uint8_t *text, size_t nb,
              const uint32_t *tile_prefix, size_t n_text_, size_t n_, uint32_t *cps, uint8_t *cls, int bits_, bool text_only_)
@@ -125,6 +134,12 @@ struct LinearPath {
     // groups: no inverse suffix array for the whole text (scanline.h, "the step table in key space").  The debug views
     // (which keep LCPs) keep the full rank table.
     key_lookup = use_trie && !v->keep_debug && kKeyBits <= 32;
+    // ... and then round 0 sorts the keys alone: the only suffixes whose position is read after it (the members of the
+    // needed groups) come from the key builder's candidate list (decode.h, CandSet; WP_OPT_INDEXED_ROUND0: the
+    // (key, index) sort as before)
+    // 8-bit symbols only: with 32-bit symbols (config 3: 1 GB of mixed scripts, 120 k tokens) the list holds a third of
+    // the suffixes and its test, packing and sort cost more than the value column (33.1 against 31.1 ms per step)
+    keys_only = key_lookup && !v->indexed_round0 && sizeof(SymT) == 1;
     sl_tiles = cdiv(n, kSlTile);
     sl_groups = cdiv(sl_tiles, kSlGroup);
     P = kStepsPerMark * M + 1;  // steps of the scanline result (scanline.h)
@@ -157,6 +172,7 @@ struct LinearPath {
     use_digit_bytes = n > kRadixSmallN;
     claim_size = 1024;  // hash table of claimed key ranges (prune.h): a power of two >= 2 M
     while (claim_size < 2 * static_cast<size_t>(std::max(M, 1))) claim_size *= 2;
+    cand_bits = bit_length(claim_size - 1);  // the long-token key set: as many slots (at most half of them taken)
     // Round 0 stores a rank for every position: a permutation.  From 2^22 symbols on the list is partitioned by ALL
     // destination bits above kWinBits (one or two radix passes over 8-byte records) and every 2^kWinBits-slot window of
     // the rank table is assembled in LDS and written with full-width stores (window_store_kernel).
@@ -177,6 +193,8 @@ struct LinearPath {
     S.full_depth = full;
     S.trie_refine = use_trie ? 1 : 0;
     S.key_bits = kKeyBits;
+    S.round0_keys_only = keys_only ? 1 : 0;
+    S.round0_candidates = keys_only ? 0 : -1;
   }
 
   // st2 starts after everything queued on st so far / st continues after everything queued on st2
@@ -252,7 +270,9 @@ struct LinearPath {
       d_agg = ar.take<RerankAgg>(rr_tiles_l + 1);
       d_chunk_agg = ar.take<RerankAgg>(cdiv(rr_tiles_l, kRrChunk) + 1);
       d_radix_tmp = ar.take<uint32_t>(radix_words);
-      d_radix_tmp2 = use_trie ? ar.take<uint32_t>(radix_tmp_words<uint64_t>(lc)) : nullptr;
+      // (keys_only: first the candidate sort — any length up to n — on the side stream beside round 0)
+      d_radix_tmp2 = use_trie ? ar.take<uint32_t>(std::max(radix_tmp_words<uint64_t>(lc), keys_only ? radix_tmp_words<uint32_t>(n) : 0))
+                              : nullptr;
       // vocabulary-sized
       d_claim = ar.take<uint32_t>(claim_size);
       d_claim_need = ar.take<uint32_t>(claim_size);
@@ -299,6 +319,14 @@ struct LinearPath {
       d_kbfast = key_lookup ? ar.take<int2>(static_cast<size_t>(nkbuckets) + 1) : nullptr;
       d_kbidx_all = (key_lookup && key_shift_all != key_shift) ? ar.take<uint32_t>(static_cast<size_t>(nkbuckets_all) + 2) : nullptr;
       d_kbfast_all = (key_lookup && key_shift_all != key_shift) ? ar.take<int2>(static_cast<size_t>(nkbuckets_all) + 1) : nullptr;
+      d_cand_table = keys_only ? ar.take<unsigned long long>(claim_size) : nullptr;
+      d_cand_filter = keys_only ? ar.take<uint32_t>(kCandFilterWords) : nullptr;
+      d_cand_lo = keys_only ? ar.take<uint32_t>(claim_size) : nullptr;
+      d_cand_hi = keys_only ? ar.take<uint32_t>(claim_size) : nullptr;
+      d_gcand = keys_only ? ar.take<uint32_t>(M + 4) : nullptr;
+      d_cand_bcnt = keys_only ? ar.take<uint32_t>(cdiv(n, kKeyTile) + 2) : nullptr;  // (the generic builder's tiles: the smaller)
+      d_cand_boff = keys_only ? ar.take<uint32_t>(cdiv(n, kKeyTile) + 2) : nullptr;
+      d_cand_scan = keys_only ? ar.take<uint32_t>(cdiv(cdiv(n, kKeyTile), kScanTile) + 8) : nullptr;
       if (pass == 0) ar.commit();
     }
     ar.arm(st);
@@ -368,19 +396,50 @@ struct LinearPath {
                     code.uniform_bits ? code.uniform_bits : -code.lo_bits};
     S.symbols_per_key = static_cast<int32_t>(kKeyBits / std::max(1.0, code.avg_bits));
     // 8-bit symbols with no codeword shorter than kKeys8MinLen bits (every ordinary text): the register form
+    if (keys_only) {  // the long-token key set of this encode (prune.h); the builder's candidates go to VA / VB
+      WP_HIP(hipMemsetAsync(d_cand_table, 0, claim_size * sizeof(unsigned long long), st));
+      WP_HIP(hipMemsetAsync(d_cand_filter, 0, kCandFilterWords * sizeof(uint32_t), st));
+      hipLaunchKernelGGL(long_key_set_kernel, dim3(cdiv(static_cast<size_t>(M) * kWave, kBlock)), dim3(kBlock), 0, st, c->d_stream,
+                         c->d_elig_start, c->d_elig_info, M, c->d_lut, dcode, d_cand_table, cand_bits, d_cand_filter);
+      cand.filter = d_cand_filter;
+      cand.table = d_cand_table;
+      cand.table_bits = cand_bits;
+      cand.slot = VA;
+      cand.pos = VB;
+      cand.bcount = d_cand_bcnt;
+    }
+    size_t cand_blocks = 0;
     int min_len = code.uniform_bits ? code.uniform_bits : 99;
     for (uint8_t l : code.len) min_len = std::min<int>(min_len, l);
     if (sizeof(SymT) == 1 && min_len >= kKeys8MinLen) {
+      cand.tile = kKeys8Tile;
+      cand_blocks = cdiv(n, kKeys8Tile);
       if (n > kRadixSmallN) {  // its tiles are the tiles of the round-0 sort: the first digit's histogram comes along
         sort_plan = radix_plan<Key0>(n, d_radix_tmp, radix_words, st);
         hist_in_keys = true;
       }
       hipLaunchKernelGGL(build_keys0_u8_kernel, dim3(cdiv(n, kKeys8Tile)), dim3(kKeys8Threads), 0, st,
                          reinterpret_cast<const uint8_t *>(d_sym), n, dcode, KA, hist_in_keys ? nullptr : DG0,
-                         hist_in_keys ? sort_plan.table : nullptr, hist_in_keys ? sort_plan.chunk_sums0 : nullptr);
+                         hist_in_keys ? sort_plan.table : nullptr, hist_in_keys ? sort_plan.chunk_sums0 : nullptr, cand);
     } else {
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(build_keys0_kernel<SymT>), dim3(cdiv(n, kKeyTile)), dim3(kBlock), 0, st, d_sym, n, dcode,
-                         KA, DG0);
+      cand.tile = kKeyTile;
+      cand_blocks = cdiv(n, kKeyTile);
+      if (keys_only) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(build_keys0_kernel<SymT, true>), dim3(cdiv(n, kKeyTile)), dim3(kBlock), 0, st, d_sym, n,
+                           dcode, KA, DG0, cand);
+      } else {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(build_keys0_kernel<SymT, false>), dim3(cdiv(n, kKeyTile)), dim3(kBlock), 0, st, d_sym, n,
+                           dcode, KA, DG0, cand);
+      }
+    }
+    if (keys_only) {  // the list packed into X1 / trie nodes by slot on the side stream; the host learns its length while the sort runs
+      WP_HIP(hipEventRecord(c->evs[7], st));
+      WP_HIP(hipStreamWaitEvent(st2, c->evs[7], 0));
+      device_exclusive_scan(d_cand_bcnt, d_cand_boff, cand_blocks, d_cand_scan, c->d_scalars + kScalarCand, st2);
+      hipLaunchKernelGGL(cand_compact_kernel, dim3(cand_blocks), dim3(kBlock), 0, st2, VA, VB, d_cand_bcnt, d_cand_boff, cand.tile, n,
+                         X1, d_node_of_slot);
+      WP_HIP(hipMemcpyAsync(c->h_scalars + kScalarCand, c->d_scalars + kScalarCand, sizeof(uint32_t), hipMemcpyDeviceToHost, st2));
+      WP_HIP(hipEventRecord(c->evs[8], st2));
     }
     WP_LAUNCH_CHECK();
   }
@@ -393,13 +452,14 @@ struct LinearPath {
     db.dg0_ready = DG0 != nullptr && !hist_in_keys;
     if (key_lookup) {  // (no rank store: the last pass leaves no digits; the keys go X0 <-> KB so that KA survives)
       Key0 *sk = reinterpret_cast<Key0 *>(X0);
-      cur = radix_sort_pairs<Key0>(sk, VA, KB, VB, n, 0, kKeyBits, d_radix_tmp, radix_words, st, &c->rstats, true,
-                                   code.uniform_bits ? 0 : 8, db, true, hist_in_keys ? &sort_plan : nullptr, KA);
+      cur = radix_sort_pairs<Key0>(sk, keys_only ? nullptr : VA, KB, keys_only ? nullptr : VB, n, 0, kKeyBits, d_radix_tmp, radix_words,
+                                   st, &c->rstats, true, code.uniform_bits ? 0 : 8, db, true, hist_in_keys ? &sort_plan : nullptr, KA);
       S.hist_in_keys = hist_in_keys ? 1 : 0;
       keys = cur ? KB : sk;
       other_keys = cur ? sk : KB;
-      vals = cur ? VB : VA;
-      other_vals = cur ? VA : VB;
+      vals = keys_only ? nullptr : (cur ? VB : VA);
+      other_vals = keys_only ? nullptr : (cur ? VA : VB);
+      if (keys_only) sort_candidates();
       slots = AS0;
       other_slots = AS1;
       adep = AD0;
@@ -427,6 +487,34 @@ struct LinearPath {
     other_dep = AD1;
     avals = LA;
     spare_vals = LB;
+  }
+
+  // The candidate list (X1 slots, trie nodes by slot: positions; both unused until the trie round) sorted by slot on the
+  // side stream, beside the keys-only passes (a few percent of their bytes), and the run of every slot.  The host reads
+  // the list length, known long before the queued passes end.  Ping-pong through VA / VB.
+  void sort_candidates() {
+    WP_HIP(hipEventSynchronize(c->evs[8]));
+    n_cand = c->h_scalars[kScalarCand];
+    S.round0_candidates = static_cast<int64_t>(n_cand);
+    WP_HIP(hipMemsetAsync(d_cand_lo, 0, claim_size * sizeof(uint32_t), st2));
+    WP_HIP(hipMemsetAsync(d_cand_hi, 0, claim_size * sizeof(uint32_t), st2));
+    const uint32_t *sorted_slot = X1, *sorted_pos = d_node_of_slot;
+    if (n_cand > 1) {
+      const int cc = radix_sort_pairs<uint32_t>(X1, d_node_of_slot, VA, VB, n_cand, 0, cand_bits, d_radix_tmp2,
+                                                std::max(radix_tmp_words<uint64_t>(list_cap), radix_tmp_words<uint32_t>(n)), st2, nullptr,
+                                                false, cand_bits, DigitBytes(), true);
+      sorted_slot = cc ? VA : X1;
+      sorted_pos = cc ? VB : d_node_of_slot;
+    }
+    if (n_cand > 0) {
+      hipLaunchKernelGGL(cand_runs_kernel, dim3(cdiv(n_cand, kBlock)), dim3(kBlock), 0, st2, sorted_slot, n_cand, d_cand_lo, d_cand_hi);
+    }
+    WP_LAUNCH_CHECK();
+    cand_runs.table = d_cand_table;
+    cand_runs.bits = cand_bits;
+    cand_runs.lo = d_cand_lo;
+    cand_runs.hi = d_cand_hi;
+    cand_runs.pos = sorted_pos;
   }
 
   // after every rerank: classify the new groups (large ones take the global path next round)
@@ -512,7 +600,8 @@ struct LinearPath {
       WP_HIP(hipMemsetAsync(d_claim, 0xff, claim_size * sizeof(uint32_t), st2));
       WP_HIP(hipMemsetAsync(d_claim_need, 0, claim_size * sizeof(uint32_t), st2));
       NeededList nl{slots, avals, AG, adep, d_ghead, d_gfirst, d_gdep, reinterpret_cast<unsigned long long *>(c->d_scalars + 4),
-                    static_cast<uint32_t *>(nullptr), need_depth, d_claim_need, d_gclaim, d_gneed0};
+                    static_cast<uint32_t *>(nullptr), need_depth, d_claim_need, d_gclaim, d_gneed0,
+                    keys_only ? d_gcand : nullptr, keys_only ? cand_runs.pos : nullptr, keys_only ? n_cand : 0};
       const TokenTrie trie{c->d_lt_chain_len, c->d_lt_chain_off, c->d_lt_child_begin, c->d_lt_child_node, d_child_sym};
       if (use_trie) {  // the vocabulary stream and the trie's child labels as dense symbols of this encode's alphabet
         const size_t ns = hv.stream.size(), nc = hv.lt_child_cp.size();
@@ -522,7 +611,8 @@ struct LinearPath {
       if (M > 0) {  // (no eligible token at all: every tied group retires)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(need_groups_kernel<SymT>), dim3(cdiv(static_cast<size_t>(M) * kWave, kBlock)),
                            dim3(kBlock), 0, st2, keys, vals, n, d_sym, c->d_stream, c->d_elig_start, c->d_elig_info, M, c->d_lut, dcode,
-                           d_claim, static_cast<uint32_t>(claim_size - 1), nl, text_only ? d_rng_lo : nullptr, d_rng_hi, d_rng_long);
+                           d_claim, static_cast<uint32_t>(claim_size - 1), nl, text_only ? d_rng_lo : nullptr, d_rng_hi, d_rng_long,
+                           cand_runs);
       }
       hipLaunchKernelGGL(needed_list_clamp_kernel, dim3(1), dim3(1), 0, st2, c->d_scalars + 4, static_cast<uint32_t>(list_cap),
                          c->d_scalars + 8);
@@ -535,7 +625,8 @@ struct LinearPath {
         if (!use_trie) hipLaunchKernelGGL(needed_need_kernel, dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st2, nl);
         hipLaunchKernelGGL(needed_fill_kernel, dim3(1024), dim3(kBlock), 0, st2, nl, vals, n);
         if (use_trie) {
-          hipLaunchKernelGGL(HIP_KERNEL_NAME(trie_group_start_kernel<SymT>), dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st2, vals, d_gfirst,
+          hipLaunchKernelGGL(HIP_KERNEL_NAME(trie_group_start_kernel<SymT>), dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st2, vals,
+                             keys_only ? cand_runs.pos : nullptr, d_gcand, d_gfirst,
                              d_gdep, c->d_scalars + 4, d_sym, n, d_vsym, trie, d_gnode, d_gdone);
         }
       }
@@ -1033,10 +1124,11 @@ struct LinearPath {
       WP_HIP(hipMemcpyFromSymbol(oob, HIP_SYMBOL(g_wp_oob), sizeof(oob)));
       const unsigned int zero[kBoundSites] = {};
       WP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_wp_oob), zero, sizeof(zero)));
-      if (oob[0] | oob[1] | oob[2] | oob[3] | oob[4]) {
+      if (oob[0] | oob[1] | oob[2] | oob[3] | oob[4] | oob[5]) {
         throw HipError("debug bounds: out-of-range addresses skipped: radix scatter " + std::to_string(oob[0]) + ", rank store " +
                        std::to_string(oob[1]) + ", token id " + std::to_string(oob[2]) + ", list slot " + std::to_string(oob[3]) +
-                       "; key-space step starts inside a run of equal keys " + std::to_string(oob[4]));
+                       "; key-space step starts inside a run of equal keys " + std::to_string(oob[4]) +
+                       "; candidate runs unlike their group " + std::to_string(oob[5]));
       }
       S.reserved0 = 1;  // this is the bounds-checking build
     }

@@ -63,6 +63,52 @@ __device__ inline bool wave_token_key(const uint32_t *__restrict__ cps, uint32_t
   return total > static_cast<uint32_t>(kKeyBits) || len > static_cast<uint32_t>(kWave);
 }
 
+// The long-token key set of this encode (decode.h, CandSet): one wave per eligible token, the same key and the same
+// "long" test as need_groups_kernel, so the set holds exactly the keys that kernel can claim groups for.
+// table: 2^bits slots, cleared to 0 (at least twice as many slots as tokens); filter: kCandFilterWords words, cleared.
+__global__ __launch_bounds__(kBlock) void long_key_set_kernel(const uint32_t *__restrict__ vocab_cps,
+                                                              const uint32_t *__restrict__ tok_start,
+                                                              const uint32_t *__restrict__ tok_info, int M,
+                                                              const uint32_t *__restrict__ lut_excl, DevCode code,
+                                                              unsigned long long *__restrict__ table, int bits,
+                                                              uint32_t *__restrict__ filter) {
+  const int m = static_cast<int>((static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x) >> 6);
+  if (m >= M) return;
+  uint64_t key = 0;
+  int kb = 0;
+  uint32_t whole = 0;
+  const uint32_t len = tok_info[m] & 0x0fffffffu;
+  if (!wave_token_key(vocab_cps + tok_start[m], len, lut_excl, code, key, kb, whole) || lane_id() != 0) return;
+  const uint32_t k32 = static_cast<uint32_t>(key);
+  const unsigned long long entry = (1ull << 32) | k32;
+  const uint32_t mask = (1u << bits) - 1u;
+  for (uint32_t h = cand_hash(k32, bits);; h = (h + 1u) & mask) {
+    const unsigned long long old = atomicCAS(&table[h], 0ull, entry);
+    if (old == 0ull || old == entry) break;
+  }
+  const uint32_t a = cand_f1(k32), b = cand_f2(k32);
+  atomicOr(&filter[a >> 5], 1u << (a & 31u));
+  atomicOr(&filter[b >> 5], 1u << (b & 31u));
+}
+
+// The candidate list sorted by slot: the run of every slot, [lo[s], hi[s]) (both cleared to 0 beforehand)
+__global__ __launch_bounds__(kBlock) void cand_runs_kernel(const uint32_t *__restrict__ slot, size_t m,
+                                                           uint32_t *__restrict__ lo, uint32_t *__restrict__ hi) {
+  const size_t i = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= m) return;
+  const uint32_t s = slot[i];
+  if (i == 0 || slot[i - 1] != s) lo[s] = static_cast<uint32_t>(i);
+  if (i + 1 == m || slot[i + 1] != s) hi[s] = static_cast<uint32_t>(i + 1);
+}
+
+// The sorted candidate list, as need_groups_kernel reads it (pos == nullptr: the round-0 sort kept its index column)
+struct CandRuns {
+  const unsigned long long *table = nullptr;
+  int bits = 0;
+  const uint32_t *lo = nullptr, *hi = nullptr;  // run of each slot
+  const uint32_t *pos = nullptr;                // text positions, in slot order
+};
+
 // suffix at text position v against the token (dense symbols through lut): -1 / +1 = the suffix sorts
 // before / behind every string that starts with the token, 0 = the token is a prefix of the suffix
 template <typename SymT>
@@ -94,6 +140,11 @@ struct NeededList {
   // in the group's slot of the claim table: claim_need, by atomic max); gclaim: that slot, gneed: the result per
   // group (needed_need_kernel) — what DepthRule::gneed_in starts from
   uint32_t *claim_need, *gclaim, *gneed;
+  // keys-only round 0: per group, where its members' run starts in the sorted candidate list (CandRuns), and the list's
+  // positions (nullptr: the members' positions are the round-0 sort's values)
+  uint32_t *gcand;
+  const uint32_t *cand_pos;
+  size_t cand_cap;  // entries of cand_pos
 };
 
 template <typename SymT>
@@ -107,7 +158,7 @@ __global__ __launch_bounds__(kBlock) void need_groups_kernel(const Key0 *__restr
                                                              uint32_t *__restrict__ claim, uint32_t claim_mask,
                                                              NeededList out, uint32_t *__restrict__ rng_lo,
                                                              uint32_t *__restrict__ rng_hi,
-                                                             uint8_t *__restrict__ rng_long) {
+                                                             uint8_t *__restrict__ rng_long, CandRuns cr) {
   const int m = static_cast<int>((static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x) >> 6);
   const int lane = lane_id();
   if (m >= M) return;
@@ -133,11 +184,19 @@ __global__ __launch_bounds__(kBlock) void need_groups_kernel(const Key0 *__restr
   }
   const size_t first = wave_key_lower_bound(keys, 0, n, key, 2);
   const size_t last = wave_key_gallop(keys, first, n, key + 1);
+  // keys-only round 0: the suffixes of this key are the run of its slot in the candidate list
+  uint32_t crun = 0;
+  if (cr.pos && lane == 0 && last > first) {
+    const uint32_t s = cand_find(cr.table, cr.bits, static_cast<uint32_t>(key));
+    const bool found = s != ~0u;
+    crun = found ? cr.lo[s] : 0u;
+    wp_in_bounds(found && cr.hi[s] - cr.lo[s] == last - first, kSiteCandRun);
+  }
   if (last - first < 2) {  // no such suffix, or a single one: nothing to refine
     if (rng_lo && lane == 0) {
       size_t lb = first, ubd = first;
       if (last > first) {
-        const int cmp = suffix_vs_token(sym, n, vals[first], cps, len, lut_excl);
+        const int cmp = suffix_vs_token(sym, n, cr.pos ? cr.pos[crun] : vals[first], cps, len, lut_excl);
         lb = cmp < 0 ? first + 1 : first;
         ubd = cmp <= 0 ? first + 1 : first;
       }
@@ -182,6 +241,7 @@ __global__ __launch_bounds__(kBlock) void need_groups_kernel(const Key0 *__restr
     out.gfirst[g] = static_cast<uint32_t>(first);
     out.gdepth[g] = depth;
     out.gclaim[g] = claim_slot;
+    if (out.gcand) out.gcand[g] = crun;
   }
 }
 
@@ -228,7 +288,16 @@ __global__ __launch_bounds__(kBlock) void needed_fill_kernel(NeededList out, con
     }
     const uint32_t k = out.gfirst[lo] + static_cast<uint32_t>(p - out.ghead[lo]);
     if (!wp_in_bounds(k < n, kSiteListSlot)) continue;
-    const uint32_t v = sorted_vals[k];
+    // (keys-only round 0: the member at the same offset of the group's candidate run — the order inside a group is
+    // free, the trie round's segmented sort puts it in place)
+    uint32_t v;
+    if (out.cand_pos) {
+      const size_t ci = static_cast<size_t>(out.gcand[lo]) + (p - out.ghead[lo]);
+      if (!wp_in_bounds(ci < out.cand_cap, kSiteListSlot) || ci >= out.cand_cap) continue;
+      v = out.cand_pos[ci];
+    } else {
+      v = sorted_vals[k];
+    }
     out.slots[p] = k;
     out.vals[p] = v;
     out.gid[p] = lo;

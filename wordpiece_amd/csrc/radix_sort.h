@@ -293,7 +293,9 @@ __device__ __forceinline__ unsigned xcd_tile(unsigned b, unsigned ntiles) {
 // vin == nullptr: the values are the element indices (the identity), made up here instead of read.
 // RBITS: bits of the digit that can be set (the ranking takes one ballot per bit: a 6-bit digit — the second
 // destination-partition pass of the rank store — ranks with 6 ballots instead of 8).
-template <typename KeyT, int ITEMS, bool STABLE = true, int RBITS = kRadixBits>
+// VALS = false: keys only — no value column is read, staged or written (vin / vout unused): half the LDS staging and
+// 9 instead of 17 bytes per element with 32-bit keys (the round-0 sort of the key-space lookup, linear_path.h).
+template <typename KeyT, int ITEMS, bool STABLE = true, int RBITS = kRadixBits, bool VALS = true>
 __global__ __launch_bounds__(kBlock) void radix_scatter_kernel(
     const KeyT *__restrict__ kin, const uint32_t *__restrict__ vin, KeyT *__restrict__ kout,
     uint32_t *__restrict__ vout, size_t n, int begin_bit, uint32_t mask,
@@ -311,7 +313,7 @@ __global__ __launch_bounds__(kBlock) void radix_scatter_kernel(
   __shared__ uint32_t gbase[kRadixBins];
   __shared__ uint32_t ssum[8];
   __shared__ KeyT skeys[TILE];
-  __shared__ uint32_t svals[TILE];
+  __shared__ uint32_t svals[VALS ? TILE : 1];
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const unsigned tile = xcd_tile(blockIdx.x, gridDim.x);
@@ -338,7 +340,7 @@ __global__ __launch_bounds__(kBlock) void radix_scatter_kernel(
 #pragma unroll
   for (int r = 0; r < ITEMS; r++) {
     const size_t i = wave_base + static_cast<size_t>(r) * kWave + lane;
-    val[r] = i < n ? (vin ? vin[i] : static_cast<uint32_t>(i)) : 0u;
+    val[r] = (VALS && i < n) ? (vin ? vin[i] : static_cast<uint32_t>(i)) : 0u;
   }
   volatile uint32_t *mycnt = wcnt[w];
 #pragma unroll
@@ -394,7 +396,7 @@ __global__ __launch_bounds__(kBlock) void radix_scatter_kernel(
     const uint32_t d = i < n ? (static_cast<uint32_t>(key[r] >> begin_bit) & mask) : kOob;
     const uint32_t pos = dstart[d] + wcnt[w][d] + rnk[r];
     skeys[pos] = key[r];
-    svals[pos] = val[r];
+    if (VALS) svals[pos] = val[r];
   }
   __syncthreads();
 #pragma unroll
@@ -405,11 +407,25 @@ __global__ __launch_bounds__(kBlock) void radix_scatter_kernel(
       const uint32_t d = static_cast<uint32_t>(kk >> begin_bit) & mask;
       const size_t o = static_cast<size_t>(gbase[d]) + k;
       if (!wp_in_bounds(o < n, kSiteRadixScatter)) continue;
-      const uint32_t vv = svals[k];
+      const uint32_t vv = VALS ? svals[k] : 0u;
       kout[o] = kk;
-      vout[o] = vv;
-      if (dout) dout[o] = static_cast<uint8_t>((dig_from_val ? vv >> next_bit : static_cast<uint32_t>(kk >> next_bit)) & next_mask);
+      if (VALS) vout[o] = vv;
+      if (dout) dout[o] = static_cast<uint8_t>((VALS && dig_from_val ? vv >> next_bit : static_cast<uint32_t>(kk >> next_bit)) & next_mask);
     }
+  }
+}
+
+// one scatter launch, with or without the value column
+template <typename KeyT, int ITEMS, bool STABLE, int RBITS = kRadixBits>
+void launch_radix_scatter(bool keys_only, unsigned ntiles, hipStream_t st, const KeyT *ki, const uint32_t *vi, KeyT *ko,
+                          uint32_t *vo, size_t n, int b, uint32_t mask, const uint32_t *table, uint8_t *dgo, int nbit,
+                          uint32_t nmask, int from_val) {
+  if (keys_only) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(radix_scatter_kernel<KeyT, ITEMS, STABLE, RBITS, false>), dim3(ntiles), dim3(kBlock), 0, st,
+                       ki, vi, ko, vo, n, b, mask, table, dgo, nbit, nmask, from_val);
+  } else {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(radix_scatter_kernel<KeyT, ITEMS, STABLE, RBITS, true>), dim3(ntiles), dim3(kBlock), 0, st,
+                       ki, vi, ko, vo, n, b, mask, table, dgo, nbit, nmask, from_val);
   }
 }
 
@@ -537,8 +553,11 @@ int radix_sort_ranges(KeyT *k0, uint32_t *v0, KeyT *k1, uint32_t *v1, size_t n, 
   // buffer of the ping-pong — the input keys survive the sort (linear_path.h: the walk's key-space lookup reads them)
   // input_order_free: nothing depends on the order the input is in (a sort from scratch, NOT one pass of a sort that a
   // caller runs as several calls, like the second partition pass of the rank store): the first pass may rank by atomics
+  // v0 == v1 == nullptr: keys only (no value column anywhere; a tail of digit bytes from the values is not possible)
   int cur = 0;
   if (n == 0) return cur;
+  const bool keys_only = v0 == nullptr && v1 == nullptr;
+  if (keys_only && db.tail_from_val) throw std::logic_error("radix sort: keys-only sort with digit bytes from the values");
   const RadixPlan plan = first_hist ? *first_hist : radix_plan<KeyT>(n, tmp, tmp_words, st);
   const bool small = plan.small;
   if (small) {
@@ -592,18 +611,16 @@ int radix_sort_ranges(KeyT *k0, uint32_t *v0, KeyT *k1, uint32_t *v1, size_t n, 
     if (stats) stats->spans.begin(st);
     const bool made_up_index = identity_vals;
     const uint32_t *vsrc = identity_vals ? static_cast<const uint32_t *>(nullptr) : vi;
+    constexpr int kI = RadixCfg<KeyT>::kItems;
     if (small) {
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(radix_scatter_kernel<KeyT, RadixCfg<KeyT>::kSmallItems, true>), dim3(ntiles),
-                         dim3(kBlock), 0, st, ki, vsrc, ko, vo, n, b, mask, table, dgo, nbit, nmask, from_val);
+      launch_radix_scatter<KeyT, RadixCfg<KeyT>::kSmallItems, true>(keys_only, ntiles, st, ki, vsrc, ko, vo, n, b, mask, table,
+                                                                   dgo, nbit, nmask, from_val);
     } else if (pi == 0 && input_order_free) {  // (no earlier order to keep: ranks by LDS atomics)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(radix_scatter_kernel<KeyT, RadixCfg<KeyT>::kItems, false>), dim3(ntiles),
-                         dim3(kBlock), 0, st, ki, vsrc, ko, vo, n, b, mask, table, dgo, nbit, nmask, from_val);
+      launch_radix_scatter<KeyT, kI, false>(keys_only, ntiles, st, ki, vsrc, ko, vo, n, b, mask, table, dgo, nbit, nmask, from_val);
     } else if (sizeof(KeyT) == 4 && mask < 64u) {  // (a digit of at most 6 bits)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(radix_scatter_kernel<KeyT, RadixCfg<KeyT>::kItems, true, 6>), dim3(ntiles),
-                         dim3(kBlock), 0, st, ki, vsrc, ko, vo, n, b, mask, table, dgo, nbit, nmask, from_val);
+      launch_radix_scatter<KeyT, kI, true, 6>(keys_only, ntiles, st, ki, vsrc, ko, vo, n, b, mask, table, dgo, nbit, nmask, from_val);
     } else {
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(radix_scatter_kernel<KeyT, RadixCfg<KeyT>::kItems, true>), dim3(ntiles),
-                         dim3(kBlock), 0, st, ki, vsrc, ko, vo, n, b, mask, table, dgo, nbit, nmask, from_val);
+      launch_radix_scatter<KeyT, kI, true>(keys_only, ntiles, st, ki, vsrc, ko, vo, n, b, mask, table, dgo, nbit, nmask, from_val);
     }
     identity_vals = false;
     WP_LAUNCH_CHECK();
@@ -612,7 +629,8 @@ int radix_sort_ranges(KeyT *k0, uint32_t *v0, KeyT *k1, uint32_t *v1, size_t n, 
       stats->passes++;
       stats->elems += static_cast<long long>(n);
       if (dgo) stats->digit_bytes += static_cast<long long>(n);
-      stats->bytes += static_cast<long long>(n) * static_cast<long long>(2 * sizeof(KeyT) + 4 + (made_up_index ? 0 : 4) + (dgo ? 1 : 0));
+      const long long vbytes = keys_only ? 0 : 4 + (made_up_index ? 0 : 4);  // (value written, and read unless made up)
+      stats->bytes += static_cast<long long>(n) * (static_cast<long long>(2 * sizeof(KeyT)) + vbytes + (dgo ? 1 : 0));
     }
     cur ^= 1;
   }

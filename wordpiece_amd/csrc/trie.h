@@ -100,8 +100,11 @@ __device__ __forceinline__ uint32_t trie_descend(const TokenTrie &t, const SymT 
 
 // one thread per needed group: the node its members share — they agree on the first gdepth[g] symbols (the whole
 // codewords of the round-0 key), so that stretch of the path is walked once per group instead of once per entry
+// (cand_pos != nullptr: keys-only round 0 — a member's position is the first of the group's candidate run, gcand)
 template <typename SymT>
 __global__ __launch_bounds__(kBlock) void trie_group_start_kernel(const uint32_t *__restrict__ sorted_vals,
+                                                                  const uint32_t *__restrict__ cand_pos,
+                                                                  const uint32_t *__restrict__ gcand,
                                                                   const uint32_t *__restrict__ gfirst,
                                                                   const uint32_t *__restrict__ gdepth,
                                                                   const uint32_t *__restrict__ sizes_dev,
@@ -112,7 +115,10 @@ __global__ __launch_bounds__(kBlock) void trie_group_start_kernel(const uint32_t
   if (g >= sizes_dev[1]) return;
   const uint32_t d = gdepth[g];
   uint32_t left = 0, node = 0;
-  if (d) node = trie_descend(t, sym, n, vsym, 0u, static_cast<size_t>(sorted_vals[gfirst[g]]), d, left);
+  if (d) {
+    const uint32_t member = cand_pos ? cand_pos[gcand[g]] : sorted_vals[gfirst[g]];
+    node = trie_descend(t, sym, n, vsym, 0u, static_cast<size_t>(member), d, left);
+  }
   gnode[g] = node;
   gdone[g] = d - left;  // symbols of the shared stretch that are behind `node` (all of them, when a token carries the key)
 }

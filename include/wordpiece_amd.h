@@ -67,6 +67,29 @@ int wp_linear_encode(wp_vocab *v, const char *utf8, size_t nbytes, int32_t **ids
 int wp_linear_encode_device(wp_vocab *v, const void *d_utf8, size_t nbytes,
                             const int32_t **d_ids, size_t *n_ids);
 
+/* ---- token offsets (an addition: TF Text tokenize_with_offsets, HF Encoding.offsets) ----
+ * The ids of wp_linear_encode plus the span of the input each id came from: offsets[2k], offsets[2k + 1] =
+ * [begin, end) of id k, in `unit`.  A token matched at code point p spans [p, p + its length in code points,
+ * without "##"); an [UNK] (or id -1 when the vocab has none) spans the word it replaces: from the first token its
+ * rollback drops (or the failing position) to where the walk resumes (the next word-prefix position, or the end
+ * of the text; the blanks behind it excluded).  Spans are increasing and disjoint; every non-blank code point lies
+ * in exactly one.
+ *   WP_OFFSETS_BYTES: byte offsets into `utf8` — a span runs from the first byte of its first code point to one past
+ *     the last byte of its last one; a dropped invalid byte inside a span belongs to it, one between spans to none.
+ *     nbytes > UINT32_MAX fails with WP_ERR_TOO_LARGE.
+ *   WP_OFFSETS_CODE_POINTS: positions in the decoded text (for valid UTF-8: Python str indices).
+ * Any other unit fails with WP_ERR_ARG.  Empty text gives 0 ids without a device.  Both entry points encode on the
+ * handle's own device: WP_OPT_DEVICES does not shard them. */
+#define WP_OFFSETS_BYTES 0
+#define WP_OFFSETS_CODE_POINTS 1
+/* host text in; ids and offsets out as two blocks (free each with wp_free) */
+int wp_linear_encode_offsets(wp_vocab *v, const char *utf8, size_t nbytes, int unit, int32_t **ids,
+                             uint32_t **offsets, size_t *n_ids);
+/* device text (same buffer contract as wp_linear_encode_device); `d_ids` and `d_offsets` (2 * n_ids uint32) are
+ * owned by the handle and valid until its next call */
+int wp_linear_encode_offsets_device(wp_vocab *v, const void *d_utf8, size_t nbytes, int unit,
+                                    const int32_t **d_ids, const uint32_t **d_offsets, size_t *n_ids);
+
 /* The same call sharded over several GPUs of the node, behind the boundary: the reference's own
  * precedent is the in-library chunking at whitespace of linear.cpp:283-299 (thread chunks) and
  * linear.cpp:355-367 (encodeExternal batches).  The text is cut at ASCII whitespace into one shard
@@ -223,6 +246,7 @@ typedef struct {
   int64_t round0_candidates;  /* keys-only round 0: suffixes whose key is the key of a long token (the candidate list the
                                  needed groups take their positions from); -1 when round 0 sorted (key, index) records */
   int32_t round0_keys_only;   /* 1: round 0 sorted the keys alone (no index column; WP_OPT_INDEXED_ROUND0 turns it off) */
+  int32_t offsets_unit;       /* the unit of the last encode's offsets (WP_OFFSETS_*), -1: an ids-only encode        */
 } wp_stats;
 int wp_get_stats(const wp_vocab *v, wp_stats *out);
 

@@ -24,6 +24,8 @@ WP_OPT_FULL_DEPTH, WP_OPT_DEVICE, WP_OPT_KEEP_DEBUG, WP_OPT_STAGE_TIMING, WP_OPT
 WP_OPT_COVER_ANCHORS, WP_OPT_ARENA_GUARD, WP_OPT_DEVICES, WP_OPT_VOCAB_IN_S = 7, 8, 9, 10
 WP_OPT_SPARSE_EMIT = 11
 WP_OPT_INDEXED_ROUND0 = 12
+WP_OFFSETS_BYTES, WP_OFFSETS_CODE_POINTS = 0, 1
+_OFFSET_UNITS = {"byte": WP_OFFSETS_BYTES, "char": WP_OFFSETS_CODE_POINTS}
 
 # every symbol include/wordpiece_amd.h declares (checked by the CPU test-suite)
 ABI_SYMBOLS = [
@@ -33,6 +35,7 @@ ABI_SYMBOLS = [
     "wp_get_stats", "wp_linear_debug_fetch", "wp_free", "wp_last_error", "wp_device_count",
     "wp_linear_encode_multi", "wp_reserve", "wp_fast_encode", "wp_fast_encode_device", "wp_fast_encode_file",
     "wp_fast_encode_external", "wp_vocab_token_utf8", "wp_trim", "wp_linear_encode_batch", "wp_linear_encode_stream",
+    "wp_linear_encode_offsets", "wp_linear_encode_offsets_device",
 ]
 
 
@@ -55,7 +58,7 @@ class Stats(C.Structure):
                 ("needed_after_round0", C.c_int64), ("key_bits", C.c_int32), ("staged_emit", C.c_int32),
                 ("rank_in_pass", C.c_int32), ("trie_refine", C.c_int32), ("arena_bytes", C.c_int64),
                 ("list_retries", C.c_int32), ("hist_in_keys", C.c_int32), ("radix_pass_bytes", C.c_int64),
-                ("round0_candidates", C.c_int64), ("round0_keys_only", C.c_int32)]
+                ("round0_candidates", C.c_int64), ("round0_keys_only", C.c_int32), ("offsets_unit", C.c_int32)]
 
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_ if k != "active_per_round"}
@@ -92,6 +95,11 @@ def lib():
         L.wp_vocab_token_len.restype = C.c_int64
         L.wp_linear_encode.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(i32p), C.POINTER(C.c_size_t)]
         L.wp_linear_encode_device.argtypes = [vp, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
+        u32p = C.POINTER(C.c_uint32)
+        L.wp_linear_encode_offsets.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, C.POINTER(i32p), C.POINTER(u32p),
+                                               C.POINTER(C.c_size_t)]
+        L.wp_linear_encode_offsets_device.argtypes = [vp, vp, C.c_size_t, C.c_int, C.POINTER(vp), C.POINTER(vp),
+                                                      C.POINTER(C.c_size_t)]
         L.wp_linear_encode_multi.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.POINTER(i32p),
                                              C.POINTER(C.c_size_t)]
         L.wp_reserve.argtypes = [vp, C.c_size_t]
@@ -177,6 +185,30 @@ class Vocab:
         n = C.c_size_t()
         _check(lib().wp_linear_encode(self._h, b, len(b), C.byref(ids), C.byref(n)))
         return _adopt_ids(ids, n.value)
+
+    def encode_with_offsets(self, text, unit="byte"):
+        """Host UTF-8 bytes/str -> (ids: numpy int32 [n], offsets: numpy uint32 [n, 2]) (wp_linear_encode_offsets):
+        offsets[k] = [begin, end) of id k in the input, unit "byte" (offsets into the UTF-8 bytes) or "char" (code
+        points: str indices for valid UTF-8).  Both arrays are views of the library's blocks."""
+        b = _bytes(text)
+        ids = C.POINTER(C.c_int32)()
+        offs = C.POINTER(C.c_uint32)()
+        n = C.c_size_t()
+        _check(lib().wp_linear_encode_offsets(self._h, b, len(b), _offset_unit(unit), C.byref(ids), C.byref(offs),
+                                              C.byref(n)))
+        if n.value == 0:
+            return np.zeros(0, dtype=np.int32), np.zeros((0, 2), dtype=np.uint32)
+        return _adopt_ids(ids, n.value), _adopt_block(offs, (n.value, 2))
+
+    def encode_device_with_offsets(self, d_ptr, nbytes, unit="byte"):
+        """Text already in HBM -> (device pointer of int32 ids, device pointer of uint32 [n, 2] offsets, n); both
+        buffers are owned by the handle and valid until the next call (wp_linear_encode_offsets_device)."""
+        d_ids = C.c_void_p()
+        d_offs = C.c_void_p()
+        n = C.c_size_t()
+        _check(lib().wp_linear_encode_offsets_device(self._h, C.c_void_p(d_ptr), nbytes, _offset_unit(unit), C.byref(d_ids),
+                                                     C.byref(d_offs), C.byref(n)))
+        return d_ids.value, d_offs.value, n.value
 
     def fast_encode(self, text):
         """word_piece::fast::encode on the GPU (wp_fast_encode): host bytes/str -> numpy int32 ids."""
@@ -268,10 +300,12 @@ class Vocab:
         _check(lib().wp_linear_encode_device(self._h, C.c_void_p(d_ptr), nbytes, C.byref(d_ids), C.byref(n)))
         return d_ids.value, n.value
 
-    def encode_tensor(self, text, copy=True):
+    def encode_tensor(self, text, copy=True, offsets=False, unit="byte"):
         """On-device consumer path: `text` is a uint8 torch tensor on the GPU of this
         handle; returns the ids as an int32 torch tensor on the same device.  copy=False returns a
         zero-copy view of the library's buffer, valid until the next call on this handle.
+        offsets=True: returns (ids, offsets), offsets an (n, 2) tensor of [begin, end) per id in `unit`
+        (encode_with_offsets) on the same device (copy=False: a uint32 view of the library's buffer).
         (Import torch before the first call into this package: both load a HIP runtime, and torch only
         sees the GPU through its own copy.)"""
         import torch
@@ -284,6 +318,14 @@ class Vocab:
             padded[:nbytes] = text
             text = padded
         torch.cuda.current_stream(text.device).synchronize()  # the library runs on its own HIP streams
+        if offsets:
+            d_ids, d_offs, n = self.encode_device_with_offsets(text.data_ptr(), nbytes, unit)
+            if n == 0:
+                return (torch.zeros(0, dtype=torch.int32, device=text.device),
+                        torch.zeros((0, 2), dtype=torch.uint32, device=text.device))
+            ids = torch.as_tensor(DeviceIds(d_ids, n), device=text.device)
+            offs = torch.as_tensor(DeviceIds(d_offs, n, cols=2), device=text.device).view(torch.uint32)
+            return (ids.clone(), offs.clone()) if copy else (ids, offs)
         d_ids, n = self.encode_device(text.data_ptr(), nbytes)
         if n == 0:
             return torch.zeros(0, dtype=torch.int32, device=text.device)
@@ -303,17 +345,28 @@ def _adopt_ids(ids, n):
     array (and every view of it) is gone."""
     if n == 0:
         return np.zeros(0, dtype=np.int32)
-    out = np.ctypeslib.as_array(ids, shape=(n,))
-    weakref.finalize(out.base if out.base is not None else out, lib().wp_free, ids)  # the bottom of the view chain
+    return _adopt_block(ids, (n,))
+
+
+def _adopt_block(ptr, shape):
+    out = np.ctypeslib.as_array(ptr, shape=shape)
+    weakref.finalize(out.base if out.base is not None else out, lib().wp_free, ptr)  # the bottom of the view chain
     return out
+
+
+def _offset_unit(unit):
+    if unit not in _OFFSET_UNITS:
+        raise WordPieceError("offsets unit must be 'byte' or 'char', not %r" % (unit,))
+    return _OFFSET_UNITS[unit]
 
 
 class DeviceIds:
     """`__cuda_array_interface__` view of an id buffer in HBM owned by the library (torch.as_tensor,
     cupy.asarray, numba … accept it without a copy)."""
 
-    def __init__(self, ptr, n):
-        self.__cuda_array_interface__ = {"shape": (n,), "typestr": "<i4", "data": (ptr, False), "version": 2}
+    def __init__(self, ptr, n, cols=0):
+        shape = (n, cols) if cols else (n,)
+        self.__cuda_array_interface__ = {"shape": shape, "typestr": "<i4", "data": (ptr, False), "version": 2}
 
 
 class _Linear:

@@ -41,7 +41,8 @@ enum BoundSite {
   kSiteListSlot = 3,
   kSiteKeyStep = 4,
   kSiteCandRun = 5,  // (no address either: a long token's key whose candidate run is not as long as its group)
-  kBoundSites = 6
+  kSiteSpan = 6,     // offsets mode: the code point -> byte table and spans outside the text (offsets.h)
+  kBoundSites = 7
 };
 #ifdef WP_DEBUG_BOUNDS
 __device__ unsigned int g_wp_oob[kBoundSites];

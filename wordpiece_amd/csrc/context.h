@@ -182,6 +182,7 @@ struct Context {
   hipEvent_t ev[8] = {};
   // results / debug views of the last call (device pointers into the arenas)
   const int32_t *d_ids = nullptr;
+  const uint32_t *d_offs = nullptr;  // offsets mode: [begin, end) per id (linear_path.h, offsets.h)
   struct {
     const void *sym = nullptr;
     int sym_bytes = 0;
@@ -331,6 +332,7 @@ static void release_arenas(Context *c) {
   c->b_buf.release();
   c->fmt_buf.release();
   c->d_ids = nullptr;
+  c->d_offs = nullptr;
   c->dbg = {};
 }
 
@@ -347,6 +349,7 @@ static void park_context(std::unique_ptr<Context> c) {
       release_arenas(c.get());
     }
     c->d_ids = nullptr;
+    c->d_offs = nullptr;
     c->dbg = {};
     std::lock_guard<std::mutex> g(g_pool_mu);
     if (context_pool().size() < kPoolContexts) {

@@ -498,6 +498,62 @@ int wp_linear_encode(wp_vocab *v, const char *utf8, size_t nbytes, int32_t **ids
   });
 }
 
+// offsets mode (include/wordpiece_amd.h): the unit and the byte unit's size limit, before any memory is touched
+static void check_offsets_call(int unit, size_t nbytes) {
+  if (unit != WP_OFFSETS_BYTES && unit != WP_OFFSETS_CODE_POINTS) throw std::invalid_argument("offsets unit must be 0 (bytes) or 1 (code points)");
+  if (unit == WP_OFFSETS_BYTES && nbytes > static_cast<size_t>(UINT32_MAX)) {
+    throw std::length_error("byte offsets need nbytes <= UINT32_MAX");
+  }
+}
+
+int wp_linear_encode_offsets(wp_vocab *v, const char *utf8, size_t nbytes, int unit, int32_t **ids, uint32_t **offsets,
+                             size_t *n_ids) {
+  return guarded([&] {
+    *ids = nullptr;
+    *offsets = nullptr;
+    *n_ids = 0;
+    check_offsets_call(unit, nbytes);
+    if (nbytes == 0) return;  // (no device needed, as wp_linear_encode)
+    const auto t_all = wp_clock::now();
+    Context *c = get_context(v);  // (the handle's own device: never sharded)
+    upload_text(c, utf8, nbytes);
+    size_t n = 0;
+    encode_on_device(v, c, static_cast<const uint8_t *>(c->text_buf.p), nbytes, &n, v->stats, unit);
+    const auto t0 = wp_clock::now();
+    if (n) {
+      PinnedBlock bi(n * sizeof(int32_t)), bo(n * 2 * sizeof(uint32_t));
+      WP_HIP(hipMemcpyAsync(bi.p, c->d_ids, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+      WP_HIP(hipMemcpyAsync(bo.p, c->d_offs, n * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+      WP_HIP(hipStreamSynchronize(c->stream));
+      *ids = static_cast<int32_t *>(bi.release());
+      *offsets = static_cast<uint32_t *>(bo.release());
+      *n_ids = n;
+    }
+    v->stats.n_devices = 1;
+    v->stats.ms_d2h = ms_since(t0);
+    v->stats.ms_host_total = ms_since(t_all);
+  });
+}
+
+int wp_linear_encode_offsets_device(wp_vocab *v, const void *d_utf8, size_t nbytes, int unit, const int32_t **d_ids,
+                                    const uint32_t **d_offsets, size_t *n_ids) {
+  return guarded([&] {
+    *d_ids = nullptr;
+    *d_offsets = nullptr;
+    *n_ids = 0;
+    check_offsets_call(unit, nbytes);
+    if (nbytes == 0) return;
+    if ((reinterpret_cast<uintptr_t>(d_utf8) & 3u) != 0) throw std::invalid_argument("device text must be 4-byte aligned");
+    size_t n = 0;
+    Context *c = get_context(v);
+    encode_on_device(v, c, static_cast<const uint8_t *>(d_utf8), nbytes, &n, v->stats, unit);
+    v->stats.n_devices = 1;
+    *d_ids = n ? c->d_ids : nullptr;
+    *d_offsets = n ? c->d_offs : nullptr;
+    *n_ids = n;
+  });
+}
+
 int wp_reserve(wp_vocab *v, size_t nbytes) {
   return guarded([&] {
     Context *c = get_context(v);

@@ -151,13 +151,14 @@ static void encode_fast_on_device(const wp_vocab *v, Context *c, const uint8_t *
                        d_anchors, c->d_scalars + 10, acap, d_lid, d_blk_cnt,  // (d_lid: the long-word id buffer, idle here)
                        static_cast<const uint32_t *>(nullptr));
     device_exclusive_scan(d_blk_cnt, d_blk_off, sblocks, d_emit_tmp, c->d_scalars + 9, st);
-    hipLaunchKernelGGL(emit_gather_kernel, dim3(sblocks), dim3(kBlock), 0, st, d_anchors, c->d_scalars + 10, acap, d_lid,
-                       d_blk_cnt, d_blk_off, d_ids, words);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(emit_gather_kernel<false>), dim3(sblocks), dim3(kBlock), 0, st, d_anchors, c->d_scalars + 10, acap, d_lid,
+                       d_blk_cnt, d_blk_off, d_ids, words, static_cast<const uint2 *>(nullptr), static_cast<uint2 *>(nullptr));
   } else {
     hipLaunchKernelGGL(fast_walk_kernel, dim3(wblocks), dim3(kBlock), 0, st, fa, d_anchors, c->d_scalars + 10, acap);
     hipLaunchKernelGGL(emit_count_kernel, dim3(tiles), dim3(kBlock), 0, st, d_emit, n_text, d_emit_cnt);
     device_exclusive_scan(d_emit_cnt, d_emit_cnt, tiles, d_emit_tmp, c->d_scalars + 9, st);
-    hipLaunchKernelGGL(emit_write_kernel, dim3(tiles), dim3(kBlock), 0, st, d_emit, n_text, d_emit_cnt, d_ids);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(emit_write_kernel<false>), dim3(tiles), dim3(kBlock), 0, st, d_emit, n_text, d_emit_cnt, d_ids,
+                       static_cast<const uint2 *>(nullptr), static_cast<uint2 *>(nullptr));
   }
   S.staged_emit = staged ? 1 : 0;
   WP_LAUNCH_CHECK();

@@ -15,6 +15,7 @@
 #include "local_sort.h"
 #include "prune.h"
 #include "trie.h"
+#include "offsets.h"
 #include "walk.h"
 
 namespace wp {
@@ -49,6 +50,7 @@ struct LinearPath {
   uint8_t *d_cls;
   int bits;
   bool text_only;
+  int offs_unit;  // offsets mode (wp_linear_encode_offsets): WP_OFFSETS_BYTES / WP_OFFSETS_CODE_POINTS; -1: ids only
 
   // ---- derived
   hipStream_t st, st2;
@@ -100,6 +102,10 @@ struct LinearPath {
   uint32_t *d_cand_filter = nullptr, *d_cand_lo = nullptr, *d_cand_hi = nullptr, *d_gcand = nullptr;
   uint32_t *d_cand_bcnt = nullptr, *d_cand_boff = nullptr, *d_cand_scan = nullptr;  // per key-builder workgroup
   int cand_bits = 0;
+  // offsets mode: the spans of the walk (per stretch, walk.h), their compact list beside the id lists, the result,
+  // and the first byte of every code point (byte unit)
+  uint2 *d_ospill = nullptr, *d_cspan = nullptr, *d_offs = nullptr;
+  uint32_t *d_byte_of = nullptr;
 
   // ---- state handed from stage to stage
   SymbolCode code;
@@ -120,9 +126,11 @@ struct LinearPath {
   size_t n_cand = 0;
 
   LinearPath(const wp_vocab *v_, Context *c_, wp_stats &S_, Arena &ar_, Arena &aa_, const uint8_t *text, size_t nb,
-             const uint32_t *tile_prefix, size_t n_text_, size_t n_, uint32_t *cps, uint8_t *cls, int bits_, bool text_only_)
+             const uint32_t *tile_prefix, size_t n_text_, size_t n_, uint32_t *cps, uint8_t *cls, int bits_, bool text_only_,
+             int offs_unit_)
       : v(v_), c(c_), S(S_), ar(ar_), aa(aa_), d_text(text), nbytes(nb), d_tile_prefix(tile_prefix), n_text(n_text_), n(n_),
-        d_cps(cps), d_cls(cls), bits(bits_), text_only(text_only_), st(c_->stream), st2(c_->stream2), hv(v_->hv) {
+        d_cps(cps), d_cls(cls), bits(bits_), text_only(text_only_), offs_unit(offs_unit_), st(c_->stream), st2(c_->stream2),
+        hv(v_->hv) {
     full = v->full_depth || hv.n_dup_eligible > 0 || v->lcp_kasai;
     need_depth = static_cast<uint32_t>(std::min<int64_t>(hv.longest + 1, 0x7fffffff));
     M = static_cast<int>(hv.elig_id.size());
@@ -327,6 +335,12 @@ struct LinearPath {
       d_cand_bcnt = keys_only ? ar.take<uint32_t>(cdiv(n, kKeyTile) + 2) : nullptr;  // (the generic builder's tiles: the smaller)
       d_cand_boff = keys_only ? ar.take<uint32_t>(cdiv(n, kKeyTile) + 2) : nullptr;
       d_cand_scan = keys_only ? ar.take<uint32_t>(cdiv(cdiv(n, kKeyTile), kScanTile) + 8) : nullptr;
+      // offsets mode only (the ids-only layout is unchanged): 8 + 8 + 8 (+ 4 in bytes) B per text position
+      const bool offs = offs_unit >= 0;
+      d_ospill = offs ? ar.take<uint2>(n_text + 16) : nullptr;
+      d_cspan = offs ? ar.take<uint2>(n_text + 16) : nullptr;
+      d_offs = offs ? ar.take<uint2>(n_text + 1) : nullptr;
+      d_byte_of = offs_unit == WP_OFFSETS_BYTES ? ar.take<uint32_t>(n_text + 1) : nullptr;
       if (pass == 0) ar.commit();
     }
     ar.arm(st);
@@ -1005,7 +1019,16 @@ struct LinearPath {
     }
     hipLaunchKernelGGL(long_word_mark_kernel, grid, dim3(kBlock), 0, st, jump_a, total, d_mark);
     hipLaunchKernelGGL(long_word_fail_kernel, grid, dim3(kBlock), 0, st, d_lid, d_mark, d_lw_off, nw, total, d_lw_fail);
-    hipLaunchKernelGGL(long_word_emit_kernel, grid, dim3(kBlock), 0, st, wa, d_lw, d_lw_off, nw, total, d_lid, d_mark, d_lw_fail);
+    if (offs_unit >= 0) {  // (the [UNK] of a failed word spans the word: up to its first blank)
+      uint32_t *d_lw_end = d_lw_fail + lw_cap;
+      WP_HIP(hipMemsetAsync(d_lw_end, 0xff, sizeof(uint32_t) * nw, st));
+      hipLaunchKernelGGL(long_word_end_kernel, grid, dim3(kBlock), 0, st, d_lw, d_lw_off, nw, total, d_lid, d_lw_end);
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(long_word_emit_kernel<true>), grid, dim3(kBlock), 0, st, wa, d_lw, d_lw_off, nw, total, d_lid,
+                         d_mark, d_lw_fail, d_ospill, static_cast<const uint32_t *>(d_lw_end));
+    } else {
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(long_word_emit_kernel<false>), grid, dim3(kBlock), 0, st, wa, d_lw, d_lw_off, nw, total, d_lid,
+                         d_mark, d_lw_fail, static_cast<uint2 *>(nullptr), static_cast<const uint32_t *>(nullptr));
+    }
     WP_LAUNCH_CHECK();
     S.anchor_mode = 2;
   }
@@ -1067,6 +1090,7 @@ struct LinearPath {
     S.n_anchors = static_cast<int64_t>(n_anchors);
     // one lane per anchor (a grid sized for the worst case, every position an anchor, costs 0.35 ms of empty workgroups)
     const size_t acap = std::max<size_t>(n_anchors, 1);
+    const bool offs = offs_unit >= 0;
     if (staged) {
       int32_t *d_ctmp = reinterpret_cast<int32_t *>(X0);
       const unsigned sblocks = cdiv(acap, static_cast<size_t>(kWbWords));
@@ -1080,23 +1104,54 @@ struct LinearPath {
         WalkArgs wa_all = wa;  // (every position of the wide words is looked up: the small index)
         wa_all.steps = steps_all;
         wa_all.ksteps = ksteps_all;
-        hipLaunchKernelGGL(walk_wide_kernel, dim3(std::min<size_t>(cdiv(acap, kBlock / kWave), 8192)), dim3(kBlock), 0, st, wa_all, d_anchors,
-                           c->d_scalars + 10, d_wide_list, c->d_scalars + 13, d_wide_cnt);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_lean_kernel<true>), dim3(sblocks), dim3(kBlock), 0, st, wa, d_anchors,
-                           c->d_scalars + 10, acap, d_ctmp, d_blk_cnt, d_wide_cnt);
+        const dim3 wgrid(std::min<size_t>(cdiv(acap, kBlock / kWave), 8192));
+        if (offs) {
+          hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_wide_kernel<true>), wgrid, dim3(kBlock), 0, st, wa_all, d_anchors, c->d_scalars + 10,
+                             d_wide_list, c->d_scalars + 13, d_wide_cnt, d_ospill);
+          hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_lean_kernel<true, true>), dim3(sblocks), dim3(kBlock), 0, st, wa, d_anchors,
+                             c->d_scalars + 10, acap, d_ctmp, d_blk_cnt, d_wide_cnt, d_ospill, d_cspan);
+        } else {
+          hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_wide_kernel<false>), wgrid, dim3(kBlock), 0, st, wa_all, d_anchors, c->d_scalars + 10,
+                             d_wide_list, c->d_scalars + 13, d_wide_cnt, static_cast<uint2 *>(nullptr));
+          hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_lean_kernel<true, false>), dim3(sblocks), dim3(kBlock), 0, st, wa, d_anchors,
+                             c->d_scalars + 10, acap, d_ctmp, d_blk_cnt, d_wide_cnt, static_cast<uint2 *>(nullptr),
+                             static_cast<uint2 *>(nullptr));
+        }
+      } else if (offs) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_lean_kernel<false, true>), dim3(sblocks), dim3(kBlock), 0, st, wa, d_anchors,
+                           c->d_scalars + 10, acap, d_ctmp, d_blk_cnt, static_cast<const uint32_t *>(nullptr), d_ospill, d_cspan);
       } else {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_lean_kernel<false>), dim3(sblocks), dim3(kBlock), 0, st, wa, d_anchors,
-                           c->d_scalars + 10, acap, d_ctmp, d_blk_cnt, static_cast<const uint32_t *>(nullptr));
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_lean_kernel<false, false>), dim3(sblocks), dim3(kBlock), 0, st, wa, d_anchors,
+                           c->d_scalars + 10, acap, d_ctmp, d_blk_cnt, static_cast<const uint32_t *>(nullptr),
+                           static_cast<uint2 *>(nullptr), static_cast<uint2 *>(nullptr));
       }
       device_exclusive_scan(d_blk_cnt, d_blk_off, sblocks, d_emit_tmp, c->d_scalars + 9, st);
-      hipLaunchKernelGGL(emit_gather_kernel, dim3(sblocks), dim3(kBlock), 0, st, d_anchors, c->d_scalars + 10, acap, d_ctmp, d_blk_cnt,
-                         d_blk_off, d_ids, kWbWords);
+      if (offs) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(emit_gather_kernel<true>), dim3(sblocks), dim3(kBlock), 0, st, d_anchors, c->d_scalars + 10,
+                           acap, d_ctmp, d_blk_cnt, d_blk_off, d_ids, kWbWords, static_cast<const uint2 *>(d_cspan), d_offs);
+      } else {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(emit_gather_kernel<false>), dim3(sblocks), dim3(kBlock), 0, st, d_anchors, c->d_scalars + 10,
+                           acap, d_ctmp, d_blk_cnt, d_blk_off, d_ids, kWbWords, static_cast<const uint2 *>(nullptr),
+                           static_cast<uint2 *>(nullptr));
+      }
     } else {
-      hipLaunchKernelGGL(walk_kernel, dim3(cdiv(acap, kBlock)), dim3(kBlock), 0, st, wa, d_anchors, c->d_scalars + 10, acap);
+      if (offs) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_kernel<true>), dim3(cdiv(acap, kBlock)), dim3(kBlock), 0, st, wa, d_anchors,
+                           c->d_scalars + 10, acap, d_ospill);
+      } else {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_kernel<false>), dim3(cdiv(acap, kBlock)), dim3(kBlock), 0, st, wa, d_anchors,
+                           c->d_scalars + 10, acap, static_cast<uint2 *>(nullptr));
+      }
       const unsigned tiles = cdiv(n_text, kScanTile);
       hipLaunchKernelGGL(emit_count_kernel, dim3(tiles), dim3(kBlock), 0, st, d_emit, n_text, d_emit_cnt);
       device_exclusive_scan(d_emit_cnt, d_emit_cnt, tiles, d_emit_tmp, c->d_scalars + 9, st);
-      hipLaunchKernelGGL(emit_write_kernel, dim3(tiles), dim3(kBlock), 0, st, d_emit, n_text, d_emit_cnt, d_ids);
+      if (offs) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(emit_write_kernel<true>), dim3(tiles), dim3(kBlock), 0, st, d_emit, n_text, d_emit_cnt, d_ids,
+                           static_cast<const uint2 *>(d_ospill), d_offs);
+      } else {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(emit_write_kernel<false>), dim3(tiles), dim3(kBlock), 0, st, d_emit, n_text, d_emit_cnt, d_ids,
+                           static_cast<const uint2 *>(nullptr), static_cast<uint2 *>(nullptr));
+      }
     }
     S.staged_emit = staged ? 1 : 0;
     WP_LAUNCH_CHECK();
@@ -1105,6 +1160,19 @@ struct LinearPath {
 
   // guard zones, bounds counters, the id count, statistics, debug views
   void finish(int32_t *d_ids, size_t *n_ids_out) {
+    c->d_offs = nullptr;
+    if (offs_unit >= 0 && n_text > 0) {
+      fetch_scalars(c, 10);
+      const size_t n_ids = c->h_scalars[9];
+      if (offs_unit == WP_OFFSETS_BYTES && n_ids > 0) {  // code points -> bytes
+        hipLaunchKernelGGL(cp_byte_kernel, dim3(cdiv(nbytes, kDecTile)), dim3(kBlock), 0, st, d_text, nbytes, d_tile_prefix, n_text,
+                           d_byte_of);
+        hipLaunchKernelGGL(span_bytes_kernel, dim3(cdiv(n_ids, kBlock)), dim3(kBlock), 0, st, d_offs, n_ids,
+                           static_cast<const uint32_t *>(d_byte_of), d_text, n_text);
+        WP_LAUNCH_CHECK();
+      }
+      c->d_offs = reinterpret_cast<const uint32_t *>(d_offs);
+    }
     if (ar.guard) {  // debugging aid: no kernel may have written outside the buffer it was given
       static const uint32_t init[2] = {0u, 0xffffffffu};
       WP_HIP(hipMemcpyAsync(c->d_scalars + 16, init, sizeof(init), hipMemcpyHostToDevice, st));
@@ -1124,11 +1192,11 @@ struct LinearPath {
       WP_HIP(hipMemcpyFromSymbol(oob, HIP_SYMBOL(g_wp_oob), sizeof(oob)));
       const unsigned int zero[kBoundSites] = {};
       WP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_wp_oob), zero, sizeof(zero)));
-      if (oob[0] | oob[1] | oob[2] | oob[3] | oob[4] | oob[5]) {
+      if (oob[0] | oob[1] | oob[2] | oob[3] | oob[4] | oob[5] | oob[6]) {
         throw HipError("debug bounds: out-of-range addresses skipped: radix scatter " + std::to_string(oob[0]) + ", rank store " +
                        std::to_string(oob[1]) + ", token id " + std::to_string(oob[2]) + ", list slot " + std::to_string(oob[3]) +
                        "; key-space step starts inside a run of equal keys " + std::to_string(oob[4]) +
-                       "; candidate runs unlike their group " + std::to_string(oob[5]));
+                       "; candidate runs unlike their group " + std::to_string(oob[5]) + "; offsets " + std::to_string(oob[6]));
       }
       S.reserved0 = 1;  // this is the bounds-checking build
     }
@@ -1195,14 +1263,17 @@ struct LinearPath {
 
 // The whole device path on context c (the calling thread has c's device current).  d_text must be
 // 4-byte aligned and readable up to the next multiple of 16.  S: statistics of this call.
+// offs_unit >= 0 (offsets mode, WP_OFFSETS_*): c->d_offs also holds the span of every id, [begin, end) as two uint32
 static void encode_on_device(const wp_vocab *v, Context *c, const uint8_t *d_text, size_t nbytes, size_t *n_ids_out,
-                             wp_stats &S) {
+                             wp_stats &S, int offs_unit = -1) {
   hipStream_t st = c->stream;
   const HostVocab &hv = v->hv;
   std::memset(&S, 0, sizeof(S));
+  S.offsets_unit = -1;
   S.n_bytes = static_cast<int64_t>(nbytes);
   S.longest_token = hv.longest;
   c->d_ids = nullptr;
+  c->d_offs = nullptr;
   c->dbg = {};
   *n_ids_out = 0;
   if (nbytes == 0) return;  // linear.cpp:323-325
@@ -1210,6 +1281,8 @@ static void encode_on_device(const wp_vocab *v, Context *c, const uint8_t *d_tex
   // linear.cpp:104-106, checked below once the code points are counted — in 64 bits, since the tile
   // prefix itself is 32-bit and wraps for inputs beyond 4 G code points)
   const bool guard = v->arena_guard || EnvOptions::get().arena_guard;
+  S.offsets_unit = offs_unit;
+  c->d_offs = nullptr;
 
   c->rstats.passes = 0;
   c->rstats.elems = 0;
@@ -1277,9 +1350,11 @@ static void encode_on_device(const wp_vocab *v, Context *c, const uint8_t *d_tex
     Arena ab(&c->b_buf, guard);
     try {
       if (sigma <= 255) {
-        LinearPath<uint8_t>(v, c, S, ab, aa, d_text, nbytes, d_tile_cnt, n_text, n, d_cps, d_cls, bits, text_only).run(n_ids_out);
+        LinearPath<uint8_t>(v, c, S, ab, aa, d_text, nbytes, d_tile_cnt, n_text, n, d_cps, d_cls, bits, text_only,
+                                 offs_unit).run(n_ids_out);
       } else {
-        LinearPath<uint32_t>(v, c, S, ab, aa, d_text, nbytes, d_tile_cnt, n_text, n, d_cps, d_cls, bits, text_only).run(n_ids_out);
+        LinearPath<uint32_t>(v, c, S, ab, aa, d_text, nbytes, d_tile_cnt, n_text, n, d_cps, d_cls, bits, text_only,
+                                 offs_unit).run(n_ids_out);
       }
       S.list_retries = attempt;
       return;

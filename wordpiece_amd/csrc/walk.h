@@ -9,6 +9,8 @@
 // next one, so the union of all threads' steps is exactly the reference's sequential walk.
 // Tokens are emitted into a text-order array (one slot per code point) and stream-compacted.
 #pragma once
+#include <type_traits>
+
 #include "primitives.h"
 #include "scanline.h"
 #include "suffix_array.h"
@@ -113,6 +115,65 @@ struct StagedOut {
   }
 };
 
+// ---- offsets mode (wp_linear_encode_offsets): the span [begin, end) of every id, in code points ----------------
+// A token matched at p: [p, p + len).  An [UNK]: [since, resume) — since = the first token its rollback drops (or the
+// failing position), resume = where the walk goes on (the next word-prefix position, or the end of the text).
+// The span Out types below record it beside each id; walk_finish and the kernels pick them by OutSpans<Out>, so the
+// ids-only instantiations (StagedOut, SparseOut) stay the code they were.
+template <typename Out>
+struct OutSpans {
+  static constexpr bool value = false;
+};
+
+// SparseOut + spans[begin] = {begin, end}: position-indexed like emit[], read where emit[] holds an id (no clearing)
+struct SparseSpanOut {
+  int32_t *emit;
+  const int32_t *tok_len;
+  uint2 *spans;
+  __device__ __forceinline__ void push_span(size_t b, size_t e, int32_t id) {
+    emit[b] = id;
+    spans[b] = make_uint2(static_cast<uint32_t>(b), static_cast<uint32_t>(e));
+  }
+  __device__ __forceinline__ void word_start() {}
+  __device__ __forceinline__ void rollback(size_t since, size_t p) {
+    size_t q = since;
+    while (q < p) {
+      const int32_t t = emit[q];
+      emit[q] = kNoEmit;
+      q += static_cast<size_t>(tok_len[t]);
+    }
+  }
+};
+template <>
+struct OutSpans<SparseSpanOut> {
+  static constexpr bool value = true;
+};
+
+// StagedOut + the span of id j at spans[j] (spans = the stretch's own range of a global scratch array, as the spill
+// of ids; no LDS column: the lean walk's LDS already limits its occupancy)
+struct StagedSpanOut {
+  int32_t *stage;
+  int32_t *spill;
+  uint32_t c = 0, mark = 0;
+  uint32_t stride = kBlock;
+  uint2 *spans = nullptr;
+  __device__ __forceinline__ void push_span(size_t b, size_t e, int32_t id) {
+    spans[c] = make_uint2(static_cast<uint32_t>(b), static_cast<uint32_t>(e));
+    if (c < static_cast<uint32_t>(kStageIds)) {
+      stage[c * stride] = id;
+    } else {
+      spill[c] = id;
+    }
+    c++;
+  }
+  __device__ __forceinline__ void word_start() { mark = c; }
+  __device__ __forceinline__ void rollback(size_t, size_t) { c = mark; }
+};
+template <>
+struct OutSpans<StagedSpanOut> {
+  static constexpr bool value = true;
+};
+
 // One step of a lane's walk: the token at s.p (or the [UNK] of its word) and what follows it up to the next
 // token start.  Returns true when the lane's stretch of text ends (end of text, or the next anchor).
 struct WalkState {
@@ -161,8 +222,14 @@ __device__ __forceinline__ bool walk_finish(const WalkArgs &a, WalkState &s, Out
   int32_t id = step_id(a.steps, raw);
   if (!wp_in_bounds(id >= -1 && id < a.n_tokens, kSiteTokenId)) id = -1;
   if (id != -1) {
-    o.push(p, id);
-    p += static_cast<size_t>(step_len(a.steps, raw, a.tok_len));
+    if constexpr (OutSpans<Out>::value) {
+      const size_t len = static_cast<size_t>(step_len(a.steps, raw, a.tok_len));
+      o.push_span(p, p + len, id);
+      p += len;
+    } else {
+      o.push(p, id);
+      p += static_cast<size_t>(step_len(a.steps, raw, a.tok_len));
+    }
     if (p < end && word_prefix(p)) {
       s.since = p;
       o.word_start();
@@ -170,7 +237,7 @@ __device__ __forceinline__ bool walk_finish(const WalkArgs &a, WalkState &s, Out
   } else {
     // roll back this word's tokens (linear.cpp:257-262), then [UNK]
     o.rollback(s.since, p);
-    o.push(p, a.unk_id);
+    if constexpr (!OutSpans<Out>::value) o.push(p, a.unk_id);
     ++p;
     while (p < end && !word_prefix(p)) {
       ++p;
@@ -181,6 +248,7 @@ __device__ __forceinline__ bool walk_finish(const WalkArgs &a, WalkState &s, Out
         break;
       }
     }
+    if constexpr (OutSpans<Out>::value) o.push_span(s.since, p, a.unk_id);  // (at since: the word it replaces)
     s.since = p;
     o.word_start();
   }
@@ -677,16 +745,33 @@ __global__ __launch_bounds__(kBlock) void long_word_fail_kernel(const int32_t *_
   if (j < total && mark[j] && id[j] == -1) word_fail[long_word_of(off, nw, j)] = 1u;
 }
 
+// OFFS: spans beside the ids (SparseSpanOut's layout); the [UNK] of a failed word goes to the word's begin, and its
+// span ends at the word's blank boundary (wend[w], long_word_end_kernel; none: the stretch's end)
+template <bool OFFS = false>
 __global__ __launch_bounds__(kBlock) void long_word_emit_kernel(WalkArgs a, const LongWord *__restrict__ list,
                                                                 const uint32_t *__restrict__ off, uint32_t nw,
                                                                 uint32_t total, const int32_t *__restrict__ id,
                                                                 const uint8_t *__restrict__ mark,
-                                                                const uint32_t *__restrict__ word_fail) {
+                                                                const uint32_t *__restrict__ word_fail,
+                                                                uint2 *__restrict__ spans, const uint32_t *__restrict__ wend) {
   const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
   if (j >= total || !mark[j]) return;
   const uint32_t w = long_word_of(off, nw, j);
   const size_t p = static_cast<size_t>(list[w].begin) + (j - off[w]);
   const int32_t t = id[j];
+  if (OFFS) {
+    if (word_fail[w]) {
+      if (t == -1) {
+        const uint32_t b = list[w].begin;
+        a.emit[b] = a.unk_id;
+        spans[b] = make_uint2(b, min(wend[w], list[w].end));
+      }
+    } else if (t >= 0) {
+      a.emit[p] = t;
+      spans[p] = make_uint2(static_cast<uint32_t>(p), static_cast<uint32_t>(p) + static_cast<uint32_t>(a.tok_len[t]));
+    }
+    return;
+  }
   if (word_fail[w]) {
     if (t == -1) a.emit[p] = a.unk_id;  // the one [UNK] of the word, where its chain broke
   } else if (t >= 0) {
@@ -694,8 +779,29 @@ __global__ __launch_bounds__(kBlock) void long_word_emit_kernel(WalkArgs a, cons
   }
 }
 
+// offsets mode: wend[w] = the first blank of long word w (a stretch is the word and the blanks behind it: one
+// transition; cleared to 0xffffffff by the caller — no blank: the stretch's end)
+__global__ __launch_bounds__(kBlock) void long_word_end_kernel(const LongWord *__restrict__ list, const uint32_t *__restrict__ off,
+                                                               uint32_t nw, uint32_t total, const int32_t *__restrict__ id,
+                                                               uint32_t *__restrict__ wend) {
+  const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+  if (j >= total || id[j] != -2) return;
+  const uint32_t w = long_word_of(off, nw, j);
+  if (j > off[w] && id[j - 1] != -2) wend[w] = list[w].begin + (j - off[w]);
+}
+
+template <bool OFFS = false>
 __global__ __launch_bounds__(kBlock) void walk_kernel(WalkArgs a, const uint32_t *__restrict__ anchors,
-                                                      const uint32_t *__restrict__ n_anchors_dev, size_t cap) {
+                                                      const uint32_t *__restrict__ n_anchors_dev, size_t cap,
+                                                      uint2 *__restrict__ spans) {
+  using Out = typename std::conditional<OFFS, SparseSpanOut, SparseOut>::type;
+  auto out = [&] {
+    if constexpr (OFFS) {
+      return SparseSpanOut{a.emit, a.tok_len, spans};
+    } else {
+      return SparseOut{a.emit, a.tok_len};
+    }
+  };
   const size_t k = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (k == 0 && !a.aflags && !a.all_hard) {
     // the reference skips leading whitespace first (linear.cpp:227-229); if the first real
@@ -704,13 +810,13 @@ __global__ __launch_bounds__(kBlock) void walk_kernel(WalkArgs a, const uint32_t
     // the coverage rule, a word-prefix position no match reaches, since spaces match nothing.)
     size_t q = 0;
     while (q < a.n_text && w_space(a, q)) ++q;
-    SparseOut o{a.emit, a.tok_len};
+    Out o = out();
     if (q < a.n_text && q != 0 && !w_anchor(a, q)) walk_from(a, q, o);
   }
   if (k >= cap || k >= *n_anchors_dev) return;
   const uint32_t start = anchors[k];
   if (start & kAnchorSkip) return;  // a long word: long_word_* kernels
-  SparseOut o{a.emit, a.tok_len};
+  Out o = out();
   walk_from(a, start, o);
 }
 
@@ -741,11 +847,13 @@ __global__ __launch_bounds__(kBlock) void wide_collect_kernel(const uint32_t *__
   }
 }
 
+// OFFS: the span of every id beside it, at spans[start + j] (the word's own stretch, as its ids in emit)
+template <bool OFFS = false>
 __global__ __launch_bounds__(kBlock) void walk_wide_kernel(WalkArgs a, const uint32_t *__restrict__ anchors,
                                                            const uint32_t *__restrict__ n_anchors_dev,
                                                            const uint32_t *__restrict__ list,
                                                            const uint32_t *__restrict__ count,
-                                                           uint32_t *__restrict__ wide_cnt) {
+                                                           uint32_t *__restrict__ wide_cnt, uint2 *__restrict__ spans) {
   constexpr int WAVES = kBlock / kWave;
   constexpr uint32_t kEnd = 0xffffu;  // successor of a position behind the word's end
   __shared__ uint16_t s_jump_mem[WAVES][2][kWideWindow];
@@ -827,6 +935,7 @@ __global__ __launch_bounds__(kBlock) void walk_wide_kernel(WalkArgs a, const uin
           const bool on = s_mark[wv][i] != 0 && id[j] >= 0;
           const uint64_t m = __ballot(on);
           if (on) out[c + static_cast<uint32_t>(__popcll(m & lt))] = id[j];
+          if (OFFS && on) spans[start + c + static_cast<uint32_t>(__popcll(m & lt))] = make_uint2(pos + i, pos + jp[j]);
           c += static_cast<uint32_t>(__popcll(m));
         }
         pos = land == kEnd ? e : pos + land;
@@ -835,6 +944,7 @@ __global__ __launch_bounds__(kBlock) void walk_wide_kernel(WalkArgs a, const uin
     }
     if (failed) {  // the one [UNK] of the word
       if (lane == 0) out[0] = a.unk_id;
+      if (OFFS && lane == 0) spans[start] = make_uint2(start, e);  // (the whole word: up to its blanks)
       c = 1;
     }
     if (lane == 0) wide_cnt[k] = c | kWideFlag;
@@ -844,11 +954,13 @@ __global__ __launch_bounds__(kBlock) void walk_wide_kernel(WalkArgs a, const uin
 // the lists of a workgroup's words, one behind the other, at ctmp[position of its first anchor ...]: thread t
 // appends words kPer * t ... (cnt[w]: ids of word w, | kWideFlag: all of them in the word's own stretch of emit — those
 // are copied by whole waves afterwards, coalesced: a wide word has hundreds of ids, woff keeps where they go)
-template <int WORDS, bool WIDE>
+// OFFS: the spans of the ids (spans[word start + j]) make a second list beside ctmp, at cspan[same index]
+template <int WORDS, bool WIDE, bool OFFS = false>
 __device__ __forceinline__ void assemble_word_lists(const int32_t *__restrict__ emit, const uint32_t *__restrict__ anchors, size_t a0,
                                                     size_t na, const int32_t *stage, const uint32_t *cnt, uint32_t *sm,
                                                     int32_t *__restrict__ ctmp, uint32_t *__restrict__ blk_cnt,
-                                                    uint32_t *woff, const uint32_t *wstart) {
+                                                    uint32_t *woff, const uint32_t *wstart, const uint2 *__restrict__ spans = nullptr,
+                                                    uint2 *__restrict__ cspan = nullptr) {
   constexpr int kPer = WORDS / kBlock;
   uint32_t mine = 0;
 #pragma unroll
@@ -866,6 +978,10 @@ __device__ __forceinline__ void assemble_word_lists(const int32_t *__restrict__ 
       const int32_t *spill = c > static_cast<uint32_t>(kStageIds) ? emit + anchors[a0 + wq] : nullptr;
       for (uint32_t j = 0; j < c; j++) {
         ctmp[base + ex + j] = j < static_cast<uint32_t>(kStageIds) ? stage[j * WORDS + wq] : spill[j];
+      }
+      if (OFFS) {
+        const uint2 *sp = spans + anchors[a0 + wq];
+        for (uint32_t j = 0; j < c; j++) cspan[base + ex + j] = sp[j];
       }
     }
     ex += c;
@@ -905,6 +1021,15 @@ __device__ __forceinline__ void assemble_word_lists(const int32_t *__restrict__ 
           for (int q = 0; q < kC; q++) {
             const uint32_t j = done + static_cast<uint32_t>(q) * kWave + lane;
             if (j < c[u]) dst[u][j] = v[u][q];
+          }
+        }
+        if (OFFS) {
+#pragma unroll
+          for (int u = 0; u < kW; u++) {
+            const int wq = w0 + u * kStride;
+            const uint2 *ssrc = spans + (wq < WORDS ? wstart[wq] : 0u);
+            uint2 *sdst = cspan + base + (wq < WORDS ? woff[wq] : 0u);
+            for (uint32_t j = done + lane; j < min(c[u], done + kC * kWave); j += kWave) sdst[j] = ssrc[j];
           }
         }
         done += kC * kWave;
@@ -1001,11 +1126,15 @@ __global__ __launch_bounds__(kBlock) void walk_balanced_kernel(Args a, const uin
 // landing position — which carries its word-prefix and anchor bits (anchor_write_kernel) — comes out of the 16 by
 // one field extract, positions are 32-bit.  Everything else (no token: [UNK] and roll back; blank runs; a landing
 // position beyond the window) goes through the generic walk_finish, which redoes the step from the same state.
-template <bool WIDE>
+// OFFS (offsets mode): every id's span goes to spans[word start + j] (StagedSpanOut) and leaves in a second list,
+// cspan, beside ctmp.
+template <bool WIDE, bool OFFS = false>
 __global__ __launch_bounds__(kBlock) void walk_lean_kernel(WalkArgs a, const uint32_t *__restrict__ anchors,
                                                            const uint32_t *__restrict__ n_anchors_dev, size_t cap,
                                                            int32_t *__restrict__ ctmp, uint32_t *__restrict__ blk_cnt,
-                                                           const uint32_t *__restrict__ wide_cnt) {
+                                                           const uint32_t *__restrict__ wide_cnt, uint2 *__restrict__ spans,
+                                                           uint2 *__restrict__ cspan) {
+  using Out = typename std::conditional<OFFS, StagedSpanOut, StagedOut>::type;
   __shared__ int32_t stage[kStageIds * kWbWords];
   __shared__ uint32_t cnt[kWbWords];
   __shared__ uint32_t woff[WIDE ? kWbWords : 1], wstart[WIDE ? kWbWords : 1];  // (assemble_word_lists)
@@ -1023,14 +1152,15 @@ __global__ __launch_bounds__(kBlock) void walk_lean_kernel(WalkArgs a, const uin
   const bool stop_at_blank = !a.aflags && a.all_hard;  // (walk_finish: the position behind the blanks is an anchor of its own)
   int widx = wbase + lane;
   uint32_t p = 0, since = 0;
-  StagedOut o{stage + widx, a.emit, 0, 0, kWbWords};
+  Out o{stage + widx, a.emit, 0, 0, kWbWords};
   // a word is taken: where it starts; false: a wide word (walk_wide_kernel has its ids), nothing to walk
   auto take = [&](int wd) {
     widx = wd;
     const size_t k = a0 + static_cast<size_t>(wd);
     const uint32_t start = anchors[k];
     p = since = start;
-    o = StagedOut{stage + wd, a.emit + start, 0, 0, kWbWords};
+    o = Out{stage + wd, a.emit + start, 0, 0, kWbWords};
+    if constexpr (OFFS) o.spans = spans + start;
     if (WIDE) {
       const uint32_t hi = k + 1 < static_cast<size_t>(*n_anchors_dev) ? anchors[k + 1] : end;
       if (hi - start > kWideMin) {
@@ -1083,7 +1213,11 @@ __global__ __launch_bounds__(kBlock) void walk_lean_kernel(WalkArgs a, const uin
           }
         }
         if (fast) {
-          o.push(p, id);
+          if constexpr (OFFS) {
+            o.push_span(p, p + len, id);
+          } else {
+            o.push(p, id);
+          }
           p = p2;
           done = p2 >= end || (f & kClsAnchor);
           if (!done && (f & kClsWordPrefix)) {
@@ -1116,21 +1250,27 @@ __global__ __launch_bounds__(kBlock) void walk_lean_kernel(WalkArgs a, const uin
     if (!__ballot(active) && next >= mine) break;
   }
   __syncthreads();
-  assemble_word_lists<kWbWords, WIDE>(a.emit, anchors, a0, na, stage, cnt, sm, ctmp, blk_cnt, woff, wstart);
+  assemble_word_lists<kWbWords, WIDE, OFFS>(a.emit, anchors, a0, na, stage, cnt, sm, ctmp, blk_cnt, woff, wstart, spans, cspan);
 }
 
 // ids[blk_off[b] ...] = the list of workgroup b (of the walk kernel, which took `words` anchors per workgroup)
+// (OFFS: and the spans list beside it, cspan -> offs)
+template <bool OFFS = false>
 __global__ __launch_bounds__(kBlock) void emit_gather_kernel(const uint32_t *__restrict__ anchors,
                                                              const uint32_t *__restrict__ n_anchors_dev, size_t cap,
                                                              const int32_t *__restrict__ ctmp,
                                                              const uint32_t *__restrict__ blk_cnt,
                                                              const uint32_t *__restrict__ blk_off,
-                                                             int32_t *__restrict__ ids, int words) {
+                                                             int32_t *__restrict__ ids, int words,
+                                                             const uint2 *__restrict__ cspan, uint2 *__restrict__ offs) {
   const size_t k0 = static_cast<size_t>(blockIdx.x) * words;
   if (k0 >= cap || k0 >= *n_anchors_dev) return;
   const size_t base = anchors[k0], off = blk_off[blockIdx.x];
   const uint32_t cnt = blk_cnt[blockIdx.x];
   for (uint32_t j = threadIdx.x; j < cnt; j += kBlock) ids[off + j] = ctmp[base + j];
+  if (OFFS) {
+    for (uint32_t j = threadIdx.x; j < cnt; j += kBlock) offs[off + j] = cspan[base + j];
+  }
 }
 
 // ---- compaction of emit[] into the id stream ----------------------------------------------------
@@ -1149,9 +1289,12 @@ __global__ __launch_bounds__(kBlock) void emit_count_kernel(const int32_t *__res
   if (threadIdx.x == 0) tile_counts[blockIdx.x] = tot;
 }
 
+// (OFFS: the spans beside the ids, from the position-indexed spans[] of SparseSpanOut / long_word_emit_kernel)
+template <bool OFFS = false>
 __global__ __launch_bounds__(kBlock) void emit_write_kernel(const int32_t *__restrict__ emit, size_t n,
                                                             const uint32_t *__restrict__ tile_prefix,
-                                                            int32_t *__restrict__ ids) {
+                                                            int32_t *__restrict__ ids, const uint2 *__restrict__ spans,
+                                                            uint2 *__restrict__ offs) {
   __shared__ uint32_t sm[8];
   const size_t base = static_cast<size_t>(blockIdx.x) * kScanTile + static_cast<size_t>(threadIdx.x) * kScanItems;
   int32_t v[kScanItems];
@@ -1166,7 +1309,10 @@ __global__ __launch_bounds__(kBlock) void emit_write_kernel(const int32_t *__res
   size_t o = static_cast<size_t>(block_excl_sum(c, sm, tot)) + tile_prefix[blockIdx.x];
 #pragma unroll
   for (int j = 0; j < kScanItems; j++) {
-    if (v[j] != kNoEmit) ids[o++] = v[j];
+    if (v[j] != kNoEmit) {
+      if (OFFS) offs[o] = spans[base + j];
+      ids[o++] = v[j];
+    }
   }
 }
 

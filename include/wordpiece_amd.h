@@ -200,6 +200,9 @@ int64_t wp_vocab_token_utf8(const wp_vocab *v, int64_t i, char *buf, size_t cap)
                                  layout too.  Default 0: there it sorts the keys alone and takes the
                                  positions it needs from a candidate list the key builder leaves (the
                                  suffixes whose key is the key of a long token).  Same token ids. */
+#define WP_OPT_SORT_BLANKS 13 /* 1: that keys-only round 0 sorts every suffix.  Default 0: in texts where
+                                 blanks (is_space) are common it leaves out the suffixes that start at one,
+                                 which the walk never looks up (wp_stats.round0_sorted).  Same token ids. */
 int wp_set_option(wp_vocab *v, int option, int64_t value);
 
 /* ---- statistics of the last encode on this handle (for bench.py / roofline) ---- */
@@ -247,6 +250,8 @@ typedef struct {
                                  needed groups take their positions from); -1 when round 0 sorted (key, index) records */
   int32_t round0_keys_only;   /* 1: round 0 sorted the keys alone (no index column; WP_OPT_INDEXED_ROUND0 turns it off) */
   int32_t offsets_unit;       /* the unit of the last encode's offsets (WP_OFFSETS_*), -1: an ids-only encode        */
+  int64_t round0_sorted;      /* suffixes in round 0's sorted array: n_total, or fewer when the keys-only round 0 left out
+                                 the blank-start suffixes (see WP_OPT_SORT_BLANKS)                                     */
 } wp_stats;
 int wp_get_stats(const wp_vocab *v, wp_stats *out);
 

@@ -1,0 +1,233 @@
+"""GPU tests (-m gpu) of the keys-only round 0 without the blank-start suffixes (csrc/radix_sort.h, RadixDrop and the
+dropping first pass; csrc/decode.h, blank_bits_kernel; csrc/linear_path.h, n_sorted): the walk never looks up a suffix
+that starts at a blank, so the sort leaves them out and slot space holds the others alone.  Ids (and offsets) against
+the oracle, WP_OPT_SORT_BLANKS=1 and WP_OPT_INDEXED_ROUND0=1 on the golden vectors, on texts made of every is_space
+character, on all-blank and blank-free texts and on slices of configs 2 and 5; wp_stats.round0_sorted against the kept
+count computed here, and no drop where blanks are rare (config 5); the bounds-checking build (kSiteBlankLookup,
+kSiteKeyStep, kSiteRadixScatter) on every walk form: lean and generic, wide words, long words, coverage anchors."""
+import json
+import os
+import random
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import oracle_lib as O
+import wordpiece_amd as W
+from wordpiece_amd import synth
+
+pytestmark = pytest.mark.gpu
+HERE = os.path.dirname(os.path.abspath(__file__))
+PKG = os.path.dirname(os.path.abspath(W.__file__))
+
+BLANKS = " \t\n\v\f\r"
+SPACE_TOKEN = "▁"
+BIG = 3 << 20  # bytes: above the 2^21 symbols from which the key builder takes the sort's first histogram
+
+
+def _kept(text):
+    """Suffixes the sort keeps: the non-blank positions of the text and the terminal one."""
+    s = text.decode("utf-8")
+    arr = np.frombuffer(s.encode("utf-32-le"), dtype=np.uint32)
+    blank = np.isin(arr, np.array([ord(c) for c in BLANKS + SPACE_TOKEN], dtype=np.uint32))
+    return int(arr.size - blank.sum()) + 1
+
+
+def _letters_vocab(rng, n_words=3000):
+    letters = "abcdefghijklmnopqrstuvwxyz"
+    words = sorted({"".join(rng.choice(letters) for _ in range(rng.randint(2, 12))) for _ in range(n_words)})
+    vocab = ["[UNK]"] + list(letters) + ["##" + c for c in letters] + words + ["##" + w[:3] for w in words[:400]]
+    return sorted(set(vocab)), words
+
+
+def _blank_runs_case(seed, nbytes=BIG, space_token=False):
+    """Words separated by runs of every is_space character (U+2581 too, when asked), leading and trailing blanks;
+    tokens that start with a blank (never matched: the walk skips blanks first) and long tokens in the vocabulary."""
+    rng = random.Random(seed)
+    vocab, words = _letters_vocab(rng)
+    blanks = BLANKS + (SPACE_TOKEN if space_token else "")
+    vocab += [" " + w for w in words[:50]] + ["\t" + w for w in words[50:60]]
+    if space_token:
+        vocab += [SPACE_TOKEN + w for w in words[60:200]] + [SPACE_TOKEN]
+    parts, size = ["".join(rng.choice(blanks) for _ in range(5))], 0
+    while size < nbytes:
+        w = rng.choice(words) if rng.random() < 0.8 else "".join(rng.choice("abcdefghijklmnopqrstuvwxyz")
+                                                               for _ in range(rng.randint(1, 20)))
+        sep = "".join(rng.choice(blanks) for _ in range(rng.choice((1, 1, 1, 2, 3, 17))))
+        parts.append(w + sep)
+        size += len(w) + len(sep)
+    parts.append("".join(rng.choice(blanks) for _ in range(9)))
+    return "".join(parts).encode(), sorted(set(vocab))
+
+
+def _all_blank_case(seed, nbytes=BIG):
+    rng = random.Random(seed)
+    vocab, _ = _letters_vocab(rng, 200)
+    return "".join(rng.choice(BLANKS) for _ in range(nbytes)).encode(), vocab
+
+
+def _no_blank_case(seed, nbytes=BIG):
+    """Words glued by punctuation only: not one blank, every suffix is kept."""
+    rng = random.Random(seed)
+    vocab, words = _letters_vocab(rng)
+    vocab = sorted(set(vocab + [".", ","]))
+    parts, size = [], 0
+    while size < nbytes:
+        w = rng.choice(words)
+        parts.append(w + rng.choice(".,"))
+        size += len(w) + 1
+    return "".join(parts).encode(), vocab
+
+
+def _long_words_case(seed, word_len, n_blank, nbytes=BIG):
+    """Words of word_len letters with a run of n_blank blanks behind each: stretches for the wide walk (more than 48
+    positions) or the long-word doubling (more than 2048), with blanks common enough for the drop."""
+    rng = random.Random(seed)
+    letters = "abcdefghijklmnopqrstuvwxyz"
+    vocab = ["[UNK]"] + list(letters) + ["##" + c for c in letters]
+    vocab += ["".join(rng.choice(letters) for _ in range(rng.randint(2, 9))) for _ in range(300)]
+    vocab += ["##" + "".join(rng.choice(letters) for _ in range(rng.randint(2, 9))) for _ in range(300)]
+    parts, size = [], 0
+    while size < nbytes:
+        w = "".join(rng.choice(letters) for _ in range(rng.randint(word_len // 2, word_len)))
+        sep = "".join(rng.choice(BLANKS) for _ in range(n_blank))
+        parts.append(w + sep)
+        size += len(w) + len(sep)
+    return "".join(parts).encode(), sorted(set(vocab))
+
+
+def _golden_cases():
+    out = []
+    for name in ("reference_tests_cpp.json", "survey_probed_cases.json"):
+        with open(os.path.join(HERE, "golden", name)) as f:
+            for case in json.load(f)["cases"]:
+                out.append((bytes.fromhex(case["text_hex"]), [bytes.fromhex(w) for w in case["vocab_hex"]]))
+    return out
+
+
+def _three_ways(text, vocab, offsets=False):
+    """ids (and byte offsets) of the default handle, WP_OPT_SORT_BLANKS=1 and WP_OPT_INDEXED_ROUND0=1; the default
+    handle's statistics"""
+    res, st = [], None
+    for opt in (None, W.WP_OPT_SORT_BLANKS, W.WP_OPT_INDEXED_ROUND0):
+        gv = W.Vocab(vocab)
+        if opt is not None:
+            gv.set_option(opt, 1)
+        if offsets:
+            ids, offs = gv.encode_with_offsets(text)
+            res.append((np.array(ids), np.array(offs)))
+        else:
+            res.append((gv.encode(text), None))
+        if opt is None:
+            st = gv.stats()
+    return res, st
+
+
+def _check(text, vocab, exp=None, offsets=False):
+    (a, oa), (b, ob), (c, oc) = _three_ways(text, vocab, offsets)[0]
+    if exp is not None:
+        assert np.array_equal(a, exp), (len(text), vocab[:5])
+    assert np.array_equal(a, b) and np.array_equal(a, c), (len(text), vocab[:5])
+    if offsets:
+        assert np.array_equal(oa, ob) and np.array_equal(oa, oc), (len(text), vocab[:5])
+
+
+def test_golden_vectors_ids_and_offsets():
+    """The option plumbing on the golden vectors: these texts are far below the 2^21 symbols from which the sort can
+    leave blanks out, so all three handles take the same round 0 here (the larger inputs below reach the drop)."""
+    n = 0
+    for text, vocab in _golden_cases():
+        try:
+            exp = O.Vocab(vocab).encode(text, threads=1)
+            W.Vocab(vocab)
+        except Exception:  # (vocabularies the library or the oracle refuses)
+            continue
+        for offsets in (False, True):
+            _check(text, vocab, exp, offsets)
+        n += 1
+    assert n > 10, n
+
+
+@pytest.mark.parametrize("case", ["blank_runs", "space_token", "all_blank", "no_blank"])
+def test_blank_shapes_against_oracle(case):
+    text, vocab = {"blank_runs": lambda: _blank_runs_case(101),
+                   "space_token": lambda: _blank_runs_case(102, space_token=True),
+                   "all_blank": lambda: _all_blank_case(103),
+                   "no_blank": lambda: _no_blank_case(104)}[case]()
+    exp = O.Vocab(vocab).encode(text, threads=8)
+    for offsets in (False, True):
+        _check(text, vocab, exp, offsets)
+    gv = W.Vocab(vocab)
+    gv.encode(text)
+    st = gv.stats()
+    assert st["round0_keys_only"] == 1 and st["hist_in_keys"] == 1, case
+    assert st["round0_sorted"] == _kept(text), (case, st["round0_sorted"], _kept(text), st["n_total"])
+    # pass 1 reads n keys and writes the kept ones with their next digit; passes 2 and 3 move keys and digits, pass 4
+    # the keys alone
+    n, k = st["n_total"], st["round0_sorted"]
+    assert st["radix_pass_elems"] == n + 3 * k
+    assert st["radix_pass_bytes"] == 4 * n + 5 * k + 9 * k + 9 * k + 8 * k
+    off = W.Vocab(vocab)
+    off.set_option(W.WP_OPT_SORT_BLANKS, 1)
+    off.encode(text)
+    assert off.stats()["round0_sorted"] == off.stats()["n_total"]
+
+
+@pytest.mark.parametrize("config", [2, 5])
+def test_config_slices(config):
+    """16-32 MB slices of configs 2 and 5 against the sort with the blanks and the indexed sort; the kept count — and
+    config 5, whose text is 0.2 % blanks, below the share from which the drop pays, sorts every suffix."""
+    if config == 2:
+        text, vocab = synth.english_corpus(24 << 20, seed=2, vocab_size=29000)
+    else:
+        text, vocab = synth.deep_prefix_corpus(16 << 20, seed=2)
+    _check(text, vocab)
+    gv = W.Vocab(vocab)
+    gv.encode(text)
+    st = gv.stats()
+    if config == 2:
+        assert st["round0_sorted"] == _kept(text)
+        assert st["round0_sorted"] < 0.9 * st["n_total"]
+    else:
+        assert st["round0_sorted"] == st["n_total"] and _kept(text) > 0.99 * st["n_total"]
+
+
+def test_bounds_build(tmp_path):
+    """The blank shapes, a config-2 slice, wide words, long words and coverage anchors in the bounds-checking build, every
+    one with blanks dropped: no step value used at a blank (kSiteBlankLookup), no broken key-space step (kSiteKeyStep),
+    no scatter out of range (kSiteRadixScatter) — the encode fails if any is counted."""
+    dbg = os.path.join(PKG, "libwordpiece_amd_dbg.so")
+    assert os.path.exists(dbg), "run `python -m wordpiece_amd.build`"
+    script = tmp_path / "blank_drop_dbg_run.py"
+    script.write_text('''
+import os, sys
+sys.path.insert(0, %r); sys.path.insert(0, %r)
+import torch
+import numpy as np
+import oracle_lib as O, wordpiece_amd as W
+from wordpiece_amd import synth
+import test_gpu_blank_drop as T
+# (text, vocab, options, anchor mode: 0 class rule, 1 coverage anchors, 2 long words by pointer doubling)
+cases = [T._blank_runs_case(111) + ({}, 0), T._blank_runs_case(112, space_token=True) + ({}, 0),
+         T._all_blank_case(113) + ({}, 0), synth.english_corpus(8 << 20, seed=7, vocab_size=29000) + ({}, 0),
+         T._long_words_case(115, 160, 12) + ({}, 0), T._long_words_case(116, 4000, 400) + ({}, 2),
+         T._blank_runs_case(117) + ({W.WP_OPT_COVER_ANCHORS: 1}, 1)]
+for text, vocab, opts, mode in cases:
+    gv = W.Vocab(vocab)
+    for k, val in opts.items():
+        gv.set_option(k, val)
+    ids = gv.encode(text)
+    st = gv.stats()
+    assert st["reserved0"] == 1, "not the bounds-checking build"
+    assert st["anchor_mode"] == mode, (st["anchor_mode"], mode)
+    assert st["round0_sorted"] == T._kept(text) < st["n_total"], (st["round0_sorted"], T._kept(text), st["n_total"])
+    assert np.array_equal(ids, O.Vocab(vocab).encode(text, threads=8))
+    ids2, _ = gv.encode_with_offsets(text)
+    assert np.array_equal(np.array(ids2), ids)
+print("BLANK_DROP_DEBUG_OK")
+''' % (os.path.dirname(PKG), HERE))
+    env = dict(os.environ, WP_LIB=dbg)
+    r = subprocess.run([sys.executable, str(script)], capture_output=True, text=True, timeout=900, env=env)
+    assert r.returncode == 0 and "BLANK_DROP_DEBUG_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]

@@ -24,6 +24,7 @@ WP_OPT_FULL_DEPTH, WP_OPT_DEVICE, WP_OPT_KEEP_DEBUG, WP_OPT_STAGE_TIMING, WP_OPT
 WP_OPT_COVER_ANCHORS, WP_OPT_ARENA_GUARD, WP_OPT_DEVICES, WP_OPT_VOCAB_IN_S = 7, 8, 9, 10
 WP_OPT_SPARSE_EMIT = 11
 WP_OPT_INDEXED_ROUND0 = 12
+WP_OPT_SORT_BLANKS = 13
 WP_OFFSETS_BYTES, WP_OFFSETS_CODE_POINTS = 0, 1
 _OFFSET_UNITS = {"byte": WP_OFFSETS_BYTES, "char": WP_OFFSETS_CODE_POINTS}
 
@@ -58,7 +59,8 @@ class Stats(C.Structure):
                 ("needed_after_round0", C.c_int64), ("key_bits", C.c_int32), ("staged_emit", C.c_int32),
                 ("rank_in_pass", C.c_int32), ("trie_refine", C.c_int32), ("arena_bytes", C.c_int64),
                 ("list_retries", C.c_int32), ("hist_in_keys", C.c_int32), ("radix_pass_bytes", C.c_int64),
-                ("round0_candidates", C.c_int64), ("round0_keys_only", C.c_int32), ("offsets_unit", C.c_int32)]
+                ("round0_candidates", C.c_int64), ("round0_keys_only", C.c_int32), ("offsets_unit", C.c_int32),
+                ("round0_sorted", C.c_int64)]
 
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_ if k != "active_per_round"}

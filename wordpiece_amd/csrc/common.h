@@ -42,7 +42,8 @@ enum BoundSite {
   kSiteKeyStep = 4,
   kSiteCandRun = 5,  // (no address either: a long token's key whose candidate run is not as long as its group)
   kSiteSpan = 6,     // offsets mode: the code point -> byte table and spans outside the text (offsets.h)
-  kBoundSites = 7
+  kSiteBlankLookup = 7,  // (no address: the walk used a step value at a blank, whose suffix round 0 dropped; walk.h)
+  kBoundSites = 8
 };
 #ifdef WP_DEBUG_BOUNDS
 __device__ unsigned int g_wp_oob[kBoundSites];

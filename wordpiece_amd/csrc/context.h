@@ -140,14 +140,16 @@ static int bit_length(uint64_t v) {
 
 constexpr int kScalars = 32;
 constexpr int kScalarCand = 24;  // d_scalars word: entries of the keys-only round 0's candidate list (linear_path.h)
+constexpr int kScalarKept = 25;  // d_scalars word: suffixes the keys-only round 0 kept (not blank-start; radix_sort.h, RadixDrop)
 
 struct Context {
   int device = 0;
   hipStream_t stream = nullptr;
   hipStream_t stream2 = nullptr;  // side stream: latency-bound helpers overlap the bandwidth-bound kernels
   hipStream_t stream3 = nullptr;  // second side stream: the large-group path of the trie round beside its LDS sort
-  hipEvent_t evs[9] = {};         // fork / join / scalars fetched / side stream done with the sorted keys / partition passes queued /
-                                  // trie nodes known / large groups sorted / key builder done / candidate count fetched
+  hipEvent_t evs[11] = {};        // fork / join / scalars fetched / side stream done with the sorted keys / partition passes queued /
+                                  // trie nodes known / large groups sorted / key builder done / candidate count fetched /
+                                  // spine of round 0's first pass done / its kept count fetched
   // vocab tables on the device
   uint32_t *d_stream = nullptr, *d_elig_start = nullptr, *d_elig_info = nullptr, *d_soft = nullptr;
   uint32_t *d_vocab_word_idx = nullptr, *d_vocab_word_bits = nullptr;  // the vocabulary's words of the alphabet bitmap
@@ -175,6 +177,9 @@ struct Context {
   bool code_cached = false;
   uint32_t code_alphabet = 0;
   int code_bits = 0, code_lo = 0, code_uses = 0;
+  // share of blanks in the histogram the cached code was built from (8-bit symbols): whether the keys-only round 0
+  // leaves the blank-start suffixes out (linear_path.h, kBlankDropMinShare) — a speed decision only, never a result
+  double code_blank_share = 0.0;
   uint8_t *h_code = nullptr;     // pinned staging of the same (the upload needs no host wait: every encode ends with one)
   uint32_t *d_symhist = nullptr;  // 256 counters
   uint32_t *h_scalars = nullptr;                                         // pinned mirror
@@ -227,6 +232,7 @@ struct wp_vocab {
   bool sparse_emit = false;  // WP_OPT_SPARSE_EMIT: ids through the per-position emit array even where per-workgroup lists would do
   bool vocab_in_s = false;  // WP_OPT_VOCAB_IN_S: always the reference's S = text . 1 . vocab layout
   bool indexed_round0 = false;  // WP_OPT_INDEXED_ROUND0: the (key, index) round-0 sort also where keys alone would do
+  bool sort_blanks = false;     // WP_OPT_SORT_BLANKS: the keys-only round 0 sorts the blank-start suffixes too
   int n_devices = 1;  // WP_OPT_DEVICES: GPUs wp_linear_encode shards a host buffer over (-1: all visible)
   wp_stats stats{};
   ~wp_vocab();

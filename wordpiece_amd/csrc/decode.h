@@ -631,9 +631,10 @@ __device__ __forceinline__ void cand_load_filter(const CandSet &cs, uint32_t *sf
 // Every thread of the workgroup: its ITEMS keys at positions pos0 + j * step (< n) against the set; the members go to
 // the workgroup's own range of the list (at most one per position of its tile: the range cannot overflow).  Call from
 // every thread (two barriers), after the filter is in LDS.
+// skip: bit j set = key j is not a member whatever its key (a suffix the round-0 sort drops)
 template <int ITEMS, int THREADS, typename K>
 __device__ __forceinline__ void cand_append(const CandSet &cs, const uint32_t *sfilter, const K (&k)[ITEMS], size_t pos0,
-                                            size_t step, size_t n, uint32_t *swave) {
+                                            size_t step, size_t n, uint32_t *swave, uint32_t skip = 0) {
   constexpr int WAVES = THREADS / kWave;
   // (the probes of the exact set loop over the lane's own filter hits: a loop over j with a probe inside serialised
   // ITEMS L2 round trips per wave, since nearly every wave has some lane past the filter at every j)
@@ -642,6 +643,7 @@ __device__ __forceinline__ void cand_append(const CandSet &cs, const uint32_t *s
   for (int j = 0; j < ITEMS; j++) {
     if (pos0 + j * step < n && cand_filter_hit(sfilter, static_cast<uint32_t>(k[j]))) pass |= 1u << j;
   }
+  pass &= ~skip;
   while (pass) {
     const int j = __ffs(pass) - 1;
     pass &= pass - 1u;
@@ -786,17 +788,22 @@ constexpr int kKeys8MinLen = (kKeyBits + kKeys8Items) / (kKeys8Items + 1);
 // sort's first digit — the low byte of the keys — is taken right here (per-wave LDS counters: the tail of a compressed
 // codeword stream is near-uniform) and written as that sort's tile row and chunk sums (radix_sort.h, RadixPlan): one
 // launch and one byte written and read per key less than through the digit bytes (dig0 is nullptr then).
+// blank_bits != nullptr (with hist_table): the sort drops the blank-start suffixes (radix_sort.h, key_is_blank) — every
+// key is still written (the walk reads KA[p]), but the histogram and the candidate list take the kept keys alone.
 __global__ __launch_bounds__(kKeys8Threads) void build_keys0_u8_kernel(const uint8_t *__restrict__ sym, size_t n, DevCode code,
                                                                 Key0 *__restrict__ keys, uint8_t *__restrict__ dig0,
                                                                 uint32_t *__restrict__ hist_table,
-                                                                uint32_t *__restrict__ hist_chunk_sums, CandSet cs) {
+                                                                uint32_t *__restrict__ hist_chunk_sums, CandSet cs,
+                                                                const uint32_t *__restrict__ blank_bits) {
   static_assert(sizeof(Key0) == 4, "register form of the key builder: 32-bit keys");
   __shared__ uint32_t stab[256];  // (len << 16) | codeword
   constexpr int WAVES = kKeys8Threads / kWave;
   __shared__ uint32_t shist[WAVES][kRadixBins];
   __shared__ uint32_t sfilter[kCandFilterWords];  // (the candidate list's filter, when cs.filter)
   __shared__ uint32_t swave[WAVES + 1];
+  __shared__ uint32_t sblank[kBlankWords];
   if (cs.filter) cand_load_filter(cs, sfilter, kKeys8Threads);
+  if (blank_bits && threadIdx.x < kBlankWords) sblank[threadIdx.x] = blank_bits[threadIdx.x];
   const int ub = code.uniform_bits > 0 ? code.uniform_bits : 0;
   if (threadIdx.x < 256) {
     if (hist_table) {
@@ -859,11 +866,16 @@ __global__ __launch_bounds__(kKeys8Threads) void build_keys0_u8_kernel(const uin
     key = ((e & 0xffffu) << (kKeyBits - l)) | (key >> l);
     k[j] = key;
   }
+  uint32_t blank = 0;  // bit j: key j is dropped by the sort
+  if (blank_bits) {
+#pragma unroll
+    for (int j = 0; j < kKeys8Items; j++) blank |= key_is_blank(sblank, k[j]) ? 1u << j : 0u;
+  }
   if (hist_table) {
     const int wv = threadIdx.x >> 6;
 #pragma unroll
     for (int j = 0; j < kKeys8Items; j++) {
-      if (p0 + j < n) atomicAdd(&shist[wv][k[j] & 0xffu], 1u);
+      if (p0 + j < n && !((blank >> j) & 1u)) atomicAdd(&shist[wv][k[j] & 0xffu], 1u);
     }
     __syncthreads();
     if (threadIdx.x < kRadixBins) {
@@ -897,7 +909,35 @@ __global__ __launch_bounds__(kKeys8Threads) void build_keys0_u8_kernel(const uin
     }
   }
   // (behind the key stores: they leave while the workgroup waits for its place in the list; the filter: barrier above)
-  if (cs.filter) cand_append<kKeys8Items, kKeys8Threads>(cs, sfilter, k, p0, 1, n, swave);
+  if (cs.filter) cand_append<kKeys8Items, kKeys8Threads>(cs, sfilter, k, p0, 1, n, swave, blank);
+}
+
+// The blank table of this encode (radix_sort.h, key_is_blank): bit t is set when the codeword that the 12-bit prefix t
+// begins with is the symbol of a blank — is_space, the walk's w_space (linear.cpp:227-229, 268-270).  With 8-bit
+// symbols, symbol and code point are 1:1: the dense symbols of the seven blank code points come from the alphabet's
+// lut.  One workgroup, a word per thread.
+__global__ __launch_bounds__(kBlankWords) void blank_bits_kernel(const uint32_t *__restrict__ lut, DevCode code,
+                                                                 uint32_t *__restrict__ bits) {
+  constexpr uint32_t kBlankCps[7] = {0x09, 0x0A, 0x0B, 0x0C, 0x0D, 0x20, kSpaceToken};
+  uint32_t cw[7], len[7];
+#pragma unroll
+  for (int b = 0; b < 7; b++) {
+    const uint32_t c = kBlankCps[b];
+    const bool used = lut[c + 1] != lut[c];  // (lut[c] = used code points below c)
+    const uint32_t s = lut[c] + 1u;           // its dense symbol
+    const int ub = code.uniform_bits > 0 ? code.uniform_bits : 0;
+    len[b] = !used ? 0u : ub ? static_cast<uint32_t>(ub) : code.len[s];
+    cw[b] = !used ? 0u : ub ? s : code.cw[s];
+  }
+  uint32_t word = 0;
+  for (int j = 0; j < 32; j++) {
+    const uint32_t t = threadIdx.x * 32u + static_cast<uint32_t>(j);
+#pragma unroll
+    for (int b = 0; b < 7; b++) {
+      if (len[b] && len[b] <= static_cast<uint32_t>(kBlankBits) && (t >> (kBlankBits - len[b])) == cw[b]) word |= 1u << j;
+    }
+  }
+  bits[threadIdx.x] = word;
 }
 
 }  // namespace wp

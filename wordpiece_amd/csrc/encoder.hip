@@ -149,6 +149,7 @@ int wp_set_option(wp_vocab *v, int option, int64_t value) {
     case WP_OPT_VOCAB_IN_S: v->vocab_in_s = value != 0; return WP_OK;
     case WP_OPT_SPARSE_EMIT: v->sparse_emit = value != 0; return WP_OK;
     case WP_OPT_INDEXED_ROUND0: v->indexed_round0 = value != 0; return WP_OK;
+    case WP_OPT_SORT_BLANKS: v->sort_blanks = value != 0; return WP_OK;
     case WP_OPT_DEVICES: v->n_devices = value < 0 ? -1 : static_cast<int>(std::max<int64_t>(value, 1)); return WP_OK;
   }
   g_last_error = "unknown option";
@@ -420,6 +421,7 @@ void encode_multi(wp_vocab *v, const char *utf8, size_t nbytes, const std::vecto
     S.radix_pass_elems += T.radix_pass_elems;
     S.radix_digit_bytes += T.radix_digit_bytes;
     S.radix_pass_bytes += T.radix_pass_bytes;
+    S.round0_sorted += T.round0_sorted;
     S.ms_total = std::max(S.ms_total, T.ms_total);
     S.ms_decode = std::max(S.ms_decode, T.ms_decode);
     S.ms_sa = std::max(S.ms_sa, T.ms_sa);

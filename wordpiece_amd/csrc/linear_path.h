@@ -35,6 +35,11 @@ __global__ void needed_list_clamp_kernel(uint32_t *__restrict__ totals, uint32_t
   }
 }
 
+// The keys-only round 0 leaves the blank-start suffixes out only where the code's symbol histogram shows at least this
+// share of blanks: the test of every key (builder and first pass) costs about as much as sorting a few percent fewer
+// keys saves (config 2, 14.9 % blanks: 0.15 ms per step gained; config 5, 0.2 %: 1.5 % slower with the drop on).
+constexpr double kBlankDropMinShare = 1.0 / 16;
+
 template <typename SymT>
 struct LinearPath {
   // ---- what the decode phase hands over
@@ -102,6 +107,7 @@ struct LinearPath {
   uint32_t *d_cand_filter = nullptr, *d_cand_lo = nullptr, *d_cand_hi = nullptr, *d_gcand = nullptr;
   uint32_t *d_cand_bcnt = nullptr, *d_cand_boff = nullptr, *d_cand_scan = nullptr;  // per key-builder workgroup
   int cand_bits = 0;
+  uint32_t *d_blank_bits = nullptr;  // keys-only round 0: which keys start with a blank (radix_sort.h, key_is_blank)
   // offsets mode: the spans of the walk (per stretch, walk.h), their compact list beside the id lists, the result,
   // and the first byte of every code point (byte unit)
   uint2 *d_ospill = nullptr, *d_cspan = nullptr, *d_offs = nullptr;
@@ -113,6 +119,10 @@ struct LinearPath {
   DigitBytes db;
   RadixPlan sort_plan;        // round-0 sort: set up ahead of it when the key builder takes its first histogram
   bool hist_in_keys = false;
+  // keys-only round 0 drops the suffixes that start at a blank (the walk never looks them up): the sorted array and
+  // slot space then hold n_sorted <= n suffixes; text-position arrays stay sized by n
+  bool drop_blanks = false;
+  size_t n_sorted = 0;
   int cur = 0, rounds = 1;
   Key0 *keys = nullptr, *other_keys = nullptr;
   uint32_t *vals = nullptr, *other_vals = nullptr, *slots = nullptr, *other_slots = nullptr, *adep = nullptr, *other_dep = nullptr;
@@ -203,6 +213,8 @@ struct LinearPath {
     S.key_bits = kKeyBits;
     S.round0_keys_only = keys_only ? 1 : 0;
     S.round0_candidates = keys_only ? 0 : -1;
+    n_sorted = n;
+    S.round0_sorted = static_cast<int64_t>(n);
   }
 
   // st2 starts after everything queued on st so far / st continues after everything queued on st2
@@ -335,6 +347,7 @@ struct LinearPath {
       d_cand_bcnt = keys_only ? ar.take<uint32_t>(cdiv(n, kKeyTile) + 2) : nullptr;  // (the generic builder's tiles: the smaller)
       d_cand_boff = keys_only ? ar.take<uint32_t>(cdiv(n, kKeyTile) + 2) : nullptr;
       d_cand_scan = keys_only ? ar.take<uint32_t>(cdiv(cdiv(n, kKeyTile), kScanTile) + 8) : nullptr;
+      d_blank_bits = keys_only ? ar.take<uint32_t>(kBlankWords) : nullptr;
       // offsets mode only (the ids-only layout is unchanged): 8 + 8 + 8 (+ 4 in bytes) B per text position
       const bool offs = offs_unit >= 0;
       d_ospill = offs ? ar.take<uint2>(n_text + 16) : nullptr;
@@ -370,6 +383,9 @@ struct LinearPath {
     const bool reuse_code = c->code_cached && c->code_alphabet == static_cast<uint32_t>(S.alphabet) && c->code_bits == bits &&
                             c->code_lo == lo_bits && c->code_uses < kCodeReuse;
     if (!reuse_code) WP_HIP(hipMemsetAsync(c->d_symhist, 0, sizeof(uint32_t) * 256, st));
+    // (8-bit symbols: lut[] of the blank code points, to find their share in the histogram below)
+    constexpr uint32_t kBlankCpRuns[3][2] = {{0x09, 7}, {0x20, 2}, {kSpaceToken, 2}};  // first, words: lut[c .. c + words)
+    uint32_t h_blank_lut[3][7] = {};
     hipLaunchKernelGGL(HIP_KERNEL_NAME(decode_write_kernel<SymT>), dim3(cdiv(nbytes, kDecTile)), dim3(kBlock), 0, st, d_text,
                        nbytes, d_tile_prefix, c->d_lut, d_sym, d_cls, d_cps, c->d_cls_bmp, c->d_soft,
                        static_cast<int>(hv.soft.size()), reuse_code ? nullptr : c->d_symhist, lo_bits);
@@ -382,6 +398,12 @@ struct LinearPath {
       // frequencies of symbol >> lo_bits -> optimal order-preserving code (host, <= 256 items) -> device tables
       std::vector<uint32_t> h32(256);
       WP_HIP(hipMemcpyAsync(h32.data(), c->d_symhist, sizeof(uint32_t) * 256, hipMemcpyDeviceToHost, st));
+      if (sizeof(SymT) == 1) {
+        for (int r = 0; r < 3; r++) {
+          WP_HIP(hipMemcpyAsync(h_blank_lut[r], c->d_lut + kBlankCpRuns[r][0], sizeof(uint32_t) * kBlankCpRuns[r][1],
+                                hipMemcpyDeviceToHost, st));
+        }
+      }
       WP_HIP(hipStreamSynchronize(st));
       const size_t nitems = (static_cast<size_t>(S.alphabet) >> lo_bits) + 1;  // dense symbols 0..sigma
       std::vector<uint64_t> freq(nitems);
@@ -397,6 +419,18 @@ struct LinearPath {
       c->code_bits = bits;
       c->code_lo = lo_bits;
       c->code_uses = 0;
+      // the blanks' share of the histogram: symbol s of a used code point c is lut[c] + 1 (lut[c + 1] != lut[c])
+      uint64_t all = 0, blank = 0;
+      for (size_t i = 0; i < nitems; i++) all += freq[i];
+      if (sizeof(SymT) == 1) {
+        for (int r = 0; r < 3; r++) {
+          for (uint32_t k = 0; k + 1 < kBlankCpRuns[r][1]; k++) {
+            const uint32_t cp = kBlankCpRuns[r][0] + k, s = h_blank_lut[r][k] + 1u;
+            if (is_space(cp) && h_blank_lut[r][k + 1] != h_blank_lut[r][k] && s < nitems) blank += freq[s];
+          }
+        }
+      }
+      c->code_blank_share = all ? static_cast<double>(blank) / static_cast<double>(all) : 0.0;
       if (!code.uniform_bits) {
         const size_t blob_bytes = 512 + 256 + kDecodeTableBytes;
         std::memset(c->h_code, 0, blob_bytes);
@@ -432,9 +466,16 @@ struct LinearPath {
         sort_plan = radix_plan<Key0>(n, d_radix_tmp, radix_words, st);
         hist_in_keys = true;
       }
+      // keys alone and a histogram the builder takes: the sort may drop the blank-start suffixes (sort_round0) — where
+      // they are common enough to pay for the blank test of every key in the builder and the first pass
+      drop_blanks = keys_only && hist_in_keys && !v->sort_blanks && c->code_blank_share >= kBlankDropMinShare;
+      if (drop_blanks) {
+        hipLaunchKernelGGL(blank_bits_kernel, dim3(1), dim3(kBlankWords), 0, st, c->d_lut, dcode, d_blank_bits);
+      }
       hipLaunchKernelGGL(build_keys0_u8_kernel, dim3(cdiv(n, kKeys8Tile)), dim3(kKeys8Threads), 0, st,
                          reinterpret_cast<const uint8_t *>(d_sym), n, dcode, KA, hist_in_keys ? nullptr : DG0,
-                         hist_in_keys ? sort_plan.table : nullptr, hist_in_keys ? sort_plan.chunk_sums0 : nullptr, cand);
+                         hist_in_keys ? sort_plan.table : nullptr, hist_in_keys ? sort_plan.chunk_sums0 : nullptr, cand,
+                         drop_blanks ? d_blank_bits : nullptr);
     } else {
       cand.tile = kKeyTile;
       cand_blocks = cdiv(n, kKeyTile);
@@ -466,8 +507,20 @@ struct LinearPath {
     db.dg0_ready = DG0 != nullptr && !hist_in_keys;
     if (key_lookup) {  // (no rank store: the last pass leaves no digits; the keys go X0 <-> KB so that KA survives)
       Key0 *sk = reinterpret_cast<Key0 *>(X0);
+      // drop_blanks: the first pass leaves the non-blank keys alone; the host learns their number (n_sorted) from its
+      // spine, on the side stream while its scatter runs, and queues the later passes over them
+      RadixDrop drop;
+      drop.blank_bits = d_blank_bits;
+      drop.d_kept = c->d_scalars + kScalarKept;
+      drop.h_kept = c->h_scalars + kScalarKept;
+      drop.side = st2;
+      drop.spine_done = c->evs[9];
+      drop.copied = c->evs[10];
       cur = radix_sort_pairs<Key0>(sk, keys_only ? nullptr : VA, KB, keys_only ? nullptr : VB, n, 0, kKeyBits, d_radix_tmp, radix_words,
-                                   st, &c->rstats, true, code.uniform_bits ? 0 : 8, db, true, hist_in_keys ? &sort_plan : nullptr, KA);
+                                   st, &c->rstats, true, code.uniform_bits ? 0 : 8, db, true, hist_in_keys ? &sort_plan : nullptr, KA,
+                                   drop_blanks ? &drop : nullptr);
+      if (drop_blanks) n_sorted = drop.kept;
+      S.round0_sorted = static_cast<int64_t>(n_sorted);
       S.hist_in_keys = hist_in_keys ? 1 : 0;
       keys = cur ? KB : sk;
       other_keys = cur ? sk : KB;
@@ -624,7 +677,7 @@ struct LinearPath {
       }
       if (M > 0) {  // (no eligible token at all: every tied group retires)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(need_groups_kernel<SymT>), dim3(cdiv(static_cast<size_t>(M) * kWave, kBlock)),
-                           dim3(kBlock), 0, st2, keys, vals, n, d_sym, c->d_stream, c->d_elig_start, c->d_elig_info, M, c->d_lut, dcode,
+                           dim3(kBlock), 0, st2, keys, vals, n_sorted, n, d_sym, c->d_stream, c->d_elig_start, c->d_elig_info, M, c->d_lut, dcode,
                            d_claim, static_cast<uint32_t>(claim_size - 1), nl, text_only ? d_rng_lo : nullptr, d_rng_hi, d_rng_long,
                            cand_runs);
       }
@@ -632,12 +685,12 @@ struct LinearPath {
                          c->d_scalars + 8);
       hipLaunchKernelGGL(needed_list_close_kernel, dim3(1), dim3(1), 0, st2, c->d_scalars + 4, d_ghead);
       if (key_lookup) {  // (the group heads are overwritten by the trie round: the group ends are taken now)
-        hipLaunchKernelGGL(group_starts_kernel, dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st2, d_gfirst, d_ghead, c->d_scalars + 4, n,
-                           d_ps0 + P, d_gend);
+        hipLaunchKernelGGL(group_starts_kernel, dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st2, d_gfirst, d_ghead, c->d_scalars + 4,
+                           n_sorted, d_ps0 + P, d_gend);
       }
       if (M > 0) {
         if (!use_trie) hipLaunchKernelGGL(needed_need_kernel, dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st2, nl);
-        hipLaunchKernelGGL(needed_fill_kernel, dim3(1024), dim3(kBlock), 0, st2, nl, vals, n);
+        hipLaunchKernelGGL(needed_fill_kernel, dim3(1024), dim3(kBlock), 0, st2, nl, vals, n_sorted);
         if (use_trie) {
           hipLaunchKernelGGL(HIP_KERNEL_NAME(trie_group_start_kernel<SymT>), dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st2, vals,
                              keys_only ? cand_runs.pos : nullptr, d_gcand, d_gfirst,
@@ -920,11 +973,14 @@ struct LinearPath {
       hipLaunchKernelGGL(mark_cover_kernel, dim3(4), dim3(kCoverThreads), 0, st, d_minfo, d_rf, d_rb, M, d_cover_f, d_cover_b);
     }
     if (n_text > 0 && !anchors_queued) launch_anchors(st2);
-    hipLaunchKernelGGL(piece_starts_kernel, dim3(cdiv(std::max(M, 1), kBlock)), dim3(kBlock), 0, st, mv, n, d_ps0);
+    hipLaunchKernelGGL(piece_starts_kernel, dim3(cdiv(std::max(M, 1), kBlock)), dim3(kBlock), 0, st, mv, n_sorted, d_ps0);
     // (key_lookup: the starts of the needed groups wait behind the marks' starts, group_starts_kernel; extra starts
     // leave the slot-space step function as it is — every value is evaluated at its own start)
     const int P = this->P + (key_lookup ? 2 * static_cast<int>(n_groups) : 0);
     const int pc = radix_sort_pairs<uint32_t>(d_ps0, d_pv0, d_ps1, d_pv1, P, 0, bit_length(n), d_radix_tmp, radix_words, st, nullptr);
+    // (slot space holds n_sorted slots: the indices need no bucket behind them; the arena was planned for n)
+    nbuckets = static_cast<unsigned>(((n_sorted - 1) >> bucket_shift) + 1);
+    nbuckets_all = static_cast<unsigned>(((n_sorted - 1) >> bucket_shift_all) + 1);
     uint32_t *pstart = pc ? d_ps1 : d_ps0;
     hipLaunchKernelGGL(piece_values_kernel, dim3(cdiv(static_cast<size_t>(P) * kWave, kBlock)), dim3(kBlock), 0, st, mv, pstart, P,
                        d_pval_p, d_pval_s, pack_steps);
@@ -1070,7 +1126,7 @@ struct LinearPath {
     if (n_text == 0) return d_ids;
     WalkArgs wa{d_cls, n_text, d_rank, steps, c->d_tok_len, hv.unk_id, d_emit, nullptr, nullptr, nullptr,
                 hv.soft.empty() ? 1 : 0, static_cast<int32_t>(hv.tokens.size()),
-                key_lookup ? reinterpret_cast<const uint32_t *>(KA) : nullptr, ksteps};
+                key_lookup ? reinterpret_cast<const uint32_t *>(KA) : nullptr, ksteps, drop_blanks ? 1 : 0};
     S.anchor_mode = 0;
     join();  // (the anchor list of the side stream)
     fetch_scalars(c, 12);
@@ -1192,11 +1248,12 @@ struct LinearPath {
       WP_HIP(hipMemcpyFromSymbol(oob, HIP_SYMBOL(g_wp_oob), sizeof(oob)));
       const unsigned int zero[kBoundSites] = {};
       WP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_wp_oob), zero, sizeof(zero)));
-      if (oob[0] | oob[1] | oob[2] | oob[3] | oob[4] | oob[5] | oob[6]) {
+      if (oob[0] | oob[1] | oob[2] | oob[3] | oob[4] | oob[5] | oob[6] | oob[7]) {
         throw HipError("debug bounds: out-of-range addresses skipped: radix scatter " + std::to_string(oob[0]) + ", rank store " +
                        std::to_string(oob[1]) + ", token id " + std::to_string(oob[2]) + ", list slot " + std::to_string(oob[3]) +
                        "; key-space step starts inside a run of equal keys " + std::to_string(oob[4]) +
-                       "; candidate runs unlike their group " + std::to_string(oob[5]) + "; offsets " + std::to_string(oob[6]));
+                       "; candidate runs unlike their group " + std::to_string(oob[5]) + "; offsets " + std::to_string(oob[6]) +
+                       "; step values used at blanks " + std::to_string(oob[7]));
       }
       S.reserved0 = 1;  // this is the bounds-checking build
     }

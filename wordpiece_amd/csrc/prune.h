@@ -148,8 +148,9 @@ struct NeededList {
 };
 
 template <typename SymT>
+// (ns: the sorted keys — slot space; n: the symbols)
 __global__ __launch_bounds__(kBlock) void need_groups_kernel(const Key0 *__restrict__ keys,
-                                                             const uint32_t *__restrict__ vals, size_t n,
+                                                             const uint32_t *__restrict__ vals, size_t ns, size_t n,
                                                              const SymT *__restrict__ sym,
                                                              const uint32_t *__restrict__ vocab_cps,
                                                              const uint32_t *__restrict__ tok_start,
@@ -171,10 +172,10 @@ __global__ __launch_bounds__(kBlock) void need_groups_kernel(const Key0 *__restr
   if (!is_long) {
     if (!rng_lo) return;
     // (the whole wave searches: wave_key_lower_bound)
-    const size_t lb = wave_key_lower_bound(keys, 0, n, key, 2);
+    const size_t lb = wave_key_lower_bound(keys, 0, ns, key, 2);
     const uint64_t step = 1ull << (kKeyBits - bits);
     const uint64_t above = key + step;  // first key that no longer starts with the stream
-    const size_t ubd = (bits == 0 || (above >> kKeyBits) != 0) ? n : wave_key_gallop(keys, lb, n, above);
+    const size_t ubd = (bits == 0 || (above >> kKeyBits) != 0) ? ns : wave_key_gallop(keys, lb, ns, above);
     if (lane == 0) {
       rng_lo[m] = static_cast<uint32_t>(lb);
       rng_hi[m] = static_cast<uint32_t>(ubd);
@@ -182,8 +183,8 @@ __global__ __launch_bounds__(kBlock) void need_groups_kernel(const Key0 *__restr
     }
     return;
   }
-  const size_t first = wave_key_lower_bound(keys, 0, n, key, 2);
-  const size_t last = wave_key_gallop(keys, first, n, key + 1);
+  const size_t first = wave_key_lower_bound(keys, 0, ns, key, 2);
+  const size_t last = wave_key_gallop(keys, first, ns, key + 1);
   // keys-only round 0: the suffixes of this key are the run of its slot in the candidate list
   uint32_t crun = 0;
   if (cr.pos && lane == 0 && last > first) {

@@ -46,6 +46,15 @@ struct RadixCfg {
 };
 constexpr size_t kRadixSmallN = size_t(1) << 21;
 
+// Keys whose first codeword is a blank symbol (the round-0 sort drops them, linear_path.h): one bit per value of the
+// key's top kBlankBits bits — codewords have at most 12 bits and are prefix-free, so those bits decide the first symbol.
+constexpr int kBlankBits = 12;
+constexpr int kBlankWords = (1 << kBlankBits) / 32;
+__device__ __forceinline__ bool key_is_blank(const uint32_t *tab, uint32_t key) {
+  const uint32_t t = key >> (32 - kBlankBits);
+  return ((tab[t >> 5] >> (t & 31u)) & 1u) != 0u;
+}
+
 // Lanes of the wave holding the same digit, as (mismatch_lo, mismatch_hi) complemented.  Per digit
 // bit: one ballot, and "my bit differs from lane l's bit" = ballot ^ sign-extended(my bit), OR-ed
 // into a per-lane mismatch mask (6 vector ops per bit).
@@ -176,13 +185,14 @@ __global__ __launch_bounds__(kBlock) void radix_hist_kernel(const KeyT *__restri
 }
 
 // single workgroup of 1024 threads = kSpineParts chunk ranges x kRadixBins digits:
-// chunk_pre[chunk][d] = exclusive prefix of chunk_sums in (digit, chunk) order
+// chunk_pre[chunk][d] = exclusive prefix of chunk_sums in (digit, chunk) order; total_out != nullptr: the number of
+// elements the histogram counted (a first pass that drops keys: the length of the sort's later passes)
 constexpr int kSpineThreads = 1024;
 constexpr int kSpineParts = kSpineThreads / kRadixBins;
 constexpr int kSpineBatch = 16;
 __global__ __launch_bounds__(kSpineThreads) void radix_spine_kernel(const uint32_t *__restrict__ chunk_sums,
                                                                     uint32_t *__restrict__ chunk_pre,
-                                                                    unsigned nchunks) {
+                                                                    unsigned nchunks, uint32_t *__restrict__ total_out) {
   __shared__ uint32_t part[kSpineParts][kRadixBins];
   __shared__ uint32_t wtot[kRadixBins / kWave];
   const int d = threadIdx.x & (kRadixBins - 1), q = threadIdx.x / kRadixBins;
@@ -214,6 +224,7 @@ __global__ __launch_bounds__(kSpineThreads) void radix_spine_kernel(const uint32
     uint32_t base_d = inc - total;
     for (int i = 0; i < (d >> 6); i++) base_d += wtot[i];
     part[0][d] = base_d;  // every thread has finished reading part[][] (barrier above)
+    if (total_out && d == kRadixBins - 1) *total_out = base_d + total;
   }
   __syncthreads();
   uint32_t run = part[0][d] + before;
@@ -295,11 +306,14 @@ __device__ __forceinline__ unsigned xcd_tile(unsigned b, unsigned ntiles) {
 // destination-partition pass of the rank store — ranks with 6 ballots instead of 8).
 // VALS = false: keys only — no value column is read, staged or written (vin / vout unused): half the LDS staging and
 // 9 instead of 17 bytes per element with 32-bit keys (the round-0 sort of the key-space lookup, linear_path.h).
-template <typename KeyT, int ITEMS, bool STABLE = true, int RBITS = kRadixBits, bool VALS = true>
+// DROP (first pass, 32-bit keys alone): keys whose first codeword is a blank symbol (key_is_blank on blank_bits) take
+// no rank and are not written — the kept keys leave contiguous, by offsets from a histogram of the kept keys alone.
+template <typename KeyT, int ITEMS, bool STABLE = true, int RBITS = kRadixBits, bool VALS = true, bool DROP = false>
 __global__ __launch_bounds__(kBlock) void radix_scatter_kernel(
     const KeyT *__restrict__ kin, const uint32_t *__restrict__ vin, KeyT *__restrict__ kout,
     uint32_t *__restrict__ vout, size_t n, int begin_bit, uint32_t mask,
-    const uint32_t *__restrict__ goff, uint8_t *__restrict__ dout, int next_bit, uint32_t next_mask, int dig_from_val) {
+    const uint32_t *__restrict__ goff, uint8_t *__restrict__ dout, int next_bit, uint32_t next_mask, int dig_from_val,
+    const uint32_t *__restrict__ blank_bits) {
   // dout != nullptr: also leave the next pass's digit of every key as one byte at its new position,
   // so that the next histogram reads 1 byte per key instead of the key (a pass is the
   // 12-byte record read and written; this adds 1 + 1).  dig_from_val: the digit is taken from the
@@ -308,7 +322,9 @@ __global__ __launch_bounds__(kBlock) void radix_scatter_kernel(
   constexpr int WAVES = kBlock / kWave;
   constexpr uint32_t kOob = (1u << RBITS) - 1u;  // bin of the slots past the end: the last one that can hold keys
   static_assert(STABLE || RBITS == kRadixBits, "the first-pass form counts the slots past the end in the top bin");
+  static_assert(!DROP || (!STABLE && !VALS && sizeof(KeyT) == 4), "dropping keys: first pass over 32-bit keys alone");
   __shared__ uint32_t wcnt[WAVES][kRadixBins];
+  __shared__ uint32_t sblank[DROP ? kBlankWords : 1];
   __shared__ uint32_t dstart[kRadixBins];
   __shared__ uint32_t gbase[kRadixBins];
   __shared__ uint32_t ssum[8];
@@ -325,6 +341,9 @@ __global__ __launch_bounds__(kBlock) void radix_scatter_kernel(
   for (int i = 0; i < WAVES; i++) {
 #pragma unroll
     for (int q = 0; q < kBinsPerThread; q++) wcnt[i][q * kBlock + tid] = 0;
+  }
+  if (DROP) {
+    for (int i = tid; i < kBlankWords; i += kBlock) sblank[i] = blank_bits[i];
   }
   __syncthreads();
 
@@ -343,13 +362,18 @@ __global__ __launch_bounds__(kBlock) void radix_scatter_kernel(
     val[r] = (VALS && i < n) ? (vin ? vin[i] : static_cast<uint32_t>(i)) : 0u;
   }
   volatile uint32_t *mycnt = wcnt[w];
+  uint32_t kept = 0;  // DROP: bit r = key r takes a rank (in range and not a blank)
 #pragma unroll
   for (int r = 0; r < ITEMS; r++) {
     size_t i = wave_base + static_cast<size_t>(r) * kWave + lane;
     // out-of-range slots (only at the very end of the last tile) take the top bin: they are the
     // last keys in tile order, hence rank after every valid key and are never written back
     const uint32_t d = i < n ? (static_cast<uint32_t>(key[r] >> begin_bit) & mask) : kOob;
-    if (STABLE) {
+    if (DROP) {
+      const bool keep = i < n && !key_is_blank(sblank, static_cast<uint32_t>(key[r]));
+      kept |= keep ? 1u << r : 0u;
+      rnk[r] = keep ? atomicAdd(&wcnt[w][d], 1u) : 0u;
+    } else if (STABLE) {
       rnk[r] = wave_rank_digit<RBITS>(mycnt, d, lane);
     } else {
       // (out-of-range slots of the last tile share the top bin with real keys here: they must still rank behind
@@ -357,7 +381,7 @@ __global__ __launch_bounds__(kBlock) void radix_scatter_kernel(
       rnk[r] = i < n ? atomicAdd(&wcnt[w][d], 1u) : 0u;
     }
   }
-  if (!STABLE && wave_base + static_cast<size_t>(ITEMS) * kWave > n) {  // (wave-uniform: the wave that holds the end)
+  if (!STABLE && !DROP && wave_base + static_cast<size_t>(ITEMS) * kWave > n) {  // (wave-uniform: the wave that holds the end)
 #pragma unroll
     for (int r = 0; r < ITEMS; r++) {
       size_t i = wave_base + static_cast<size_t>(r) * kWave + lane;
@@ -393,16 +417,18 @@ __global__ __launch_bounds__(kBlock) void radix_scatter_kernel(
 #pragma unroll
   for (int r = 0; r < ITEMS; r++) {
     size_t i = wave_base + static_cast<size_t>(r) * kWave + lane;
+    if (DROP && !((kept >> r) & 1u)) continue;
     const uint32_t d = i < n ? (static_cast<uint32_t>(key[r] >> begin_bit) & mask) : kOob;
     const uint32_t pos = dstart[d] + wcnt[w][d] + rnk[r];
     skeys[pos] = key[r];
     if (VALS) svals[pos] = val[r];
   }
   __syncthreads();
+  const uint32_t out_count = DROP ? all : tile_count;  // (DROP: the kept keys of the tile)
 #pragma unroll
   for (int j = 0; j < ITEMS; j++) {
     const uint32_t k = static_cast<uint32_t>(j) * kBlock + tid;
-    if (k < tile_count) {
+    if (k < out_count) {
       const KeyT kk = skeys[k];
       const uint32_t d = static_cast<uint32_t>(kk >> begin_bit) & mask;
       const size_t o = static_cast<size_t>(gbase[d]) + k;
@@ -415,17 +441,25 @@ __global__ __launch_bounds__(kBlock) void radix_scatter_kernel(
   }
 }
 
-// one scatter launch, with or without the value column
+// one scatter launch, with or without the value column; blank_bits != nullptr: the dropping first pass (keys only)
 template <typename KeyT, int ITEMS, bool STABLE, int RBITS = kRadixBits>
 void launch_radix_scatter(bool keys_only, unsigned ntiles, hipStream_t st, const KeyT *ki, const uint32_t *vi, KeyT *ko,
                           uint32_t *vo, size_t n, int b, uint32_t mask, const uint32_t *table, uint8_t *dgo, int nbit,
-                          uint32_t nmask, int from_val) {
-  if (keys_only) {
+                          uint32_t nmask, int from_val, const uint32_t *blank_bits = nullptr) {
+  if (blank_bits) {
+    if constexpr (sizeof(KeyT) == 4 && !STABLE && RBITS == kRadixBits) {
+      if (!keys_only) throw std::logic_error("radix sort: keys are dropped in a keys-only pass only");
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(radix_scatter_kernel<KeyT, ITEMS, false, RBITS, false, true>), dim3(ntiles), dim3(kBlock), 0,
+                         st, ki, vi, ko, vo, n, b, mask, table, dgo, nbit, nmask, from_val, blank_bits);
+    } else {
+      throw std::logic_error("radix sort: keys are dropped in the first pass over 32-bit keys only");
+    }
+  } else if (keys_only) {
     hipLaunchKernelGGL(HIP_KERNEL_NAME(radix_scatter_kernel<KeyT, ITEMS, STABLE, RBITS, false>), dim3(ntiles), dim3(kBlock), 0, st,
-                       ki, vi, ko, vo, n, b, mask, table, dgo, nbit, nmask, from_val);
+                       ki, vi, ko, vo, n, b, mask, table, dgo, nbit, nmask, from_val, static_cast<const uint32_t *>(nullptr));
   } else {
     hipLaunchKernelGGL(HIP_KERNEL_NAME(radix_scatter_kernel<KeyT, ITEMS, STABLE, RBITS, true>), dim3(ntiles), dim3(kBlock), 0, st,
-                       ki, vi, ko, vo, n, b, mask, table, dgo, nbit, nmask, from_val);
+                       ki, vi, ko, vo, n, b, mask, table, dgo, nbit, nmask, from_val, static_cast<const uint32_t *>(nullptr));
   }
 }
 
@@ -542,13 +576,25 @@ RadixPlan radix_plan(size_t n, uint32_t *tmp, size_t tmp_words, hipStream_t st) 
   return p;
 }
 
+// A first pass that drops keys (key_is_blank; linear_path.h: the blank-start suffixes of round 0).  The caller's
+// histogram of that pass (first_hist) counts the kept keys alone; its spine leaves their number in d_kept, which the
+// side stream copies to h_kept while the pass's scatter runs; the host waits for that copy only to size the later
+// passes, which then run over the kept keys.
+struct RadixDrop {
+  const uint32_t *blank_bits = nullptr;          // kBlankWords words
+  uint32_t *d_kept = nullptr, *h_kept = nullptr;  // a device scalar and its pinned host mirror
+  hipStream_t side = nullptr;
+  hipEvent_t spine_done = nullptr, copied = nullptr;
+  size_t kept = 0;  // out: the length of the sorted array
+};
+
 // first_hist: the plan of this sort, made by the caller, with the first pass's histogram already in it
 template <typename KeyT>
 int radix_sort_ranges(KeyT *k0, uint32_t *v0, KeyT *k1, uint32_t *v1, size_t n, const BitRange *ranges,
                       int nranges, uint32_t *tmp, size_t tmp_words, hipStream_t st, RadixStats *stats,
                       bool identity_vals = false, int uniform_low_bits = 0, DigitBytes db = DigitBytes(),
                       bool input_order_free = false, const RadixPlan *first_hist = nullptr,
-                      const KeyT *k_first = nullptr) {
+                      const KeyT *k_first = nullptr, RadixDrop *drop = nullptr) {
   // k_first != nullptr: the first pass reads its keys there instead of k0, which the later passes use as the second
   // buffer of the ping-pong — the input keys survive the sort (linear_path.h: the walk's key-space lookup reads them)
   // input_order_free: nothing depends on the order the input is in (a sort from scratch, NOT one pass of a sort that a
@@ -560,11 +606,15 @@ int radix_sort_ranges(KeyT *k0, uint32_t *v0, KeyT *k1, uint32_t *v1, size_t n, 
   if (keys_only && db.tail_from_val) throw std::logic_error("radix sort: keys-only sort with digit bytes from the values");
   const RadixPlan plan = first_hist ? *first_hist : radix_plan<KeyT>(n, tmp, tmp_words, st);
   const bool small = plan.small;
+  if (drop && (small || !first_hist || !input_order_free || !keys_only)) {
+    throw std::logic_error("radix sort: keys are dropped in a full-size keys-only sort whose caller took the first histogram");
+  }
   if (small) {
     stats = nullptr;  // the roofline statistics describe the full-size configuration only
     db = DigitBytes();
   }
-  const unsigned ntiles = plan.ntiles, nchunks = plan.nchunks;
+  unsigned ntiles = plan.ntiles, nchunks = plan.nchunks;
+  size_t len = n;  // elements of this pass: n, then the kept ones behind a dropping first pass
   const size_t cs_words = plan.cs_words;
   uint32_t *table = plan.table, *chunk_pre = plan.chunk_pre, *chunk_sums0 = plan.chunk_sums0;
   struct Pass {
@@ -577,7 +627,18 @@ int radix_sort_ranges(KeyT *k0, uint32_t *v0, KeyT *k1, uint32_t *v1, size_t n, 
       passes.push_back({b, (1u << std::min(kRadixBits, ranges[r].end - b)) - 1u});
     }
   }
+  if (drop && passes.size() < 2) throw std::logic_error("radix sort: a dropping sort learns its length behind the first pass");
+  if (drop) drop->kept = n;
+  bool drop_dgo = false;
   for (size_t pi = 0; pi < passes.size(); pi++) {
+    if (drop && pi == 1) {  // (the first scatter is queued: its run hides the wait for the count)
+      WP_HIP(hipEventSynchronize(drop->copied));
+      len = *drop->h_kept;
+      drop->kept = len;
+      if (len == 0) break;
+      ntiles = cdiv(len, RadixCfg<KeyT>::kTile);
+      nchunks = cdiv(ntiles, kColChunk);
+    }
     const int pass = static_cast<int>(pi), b = passes[pi].bit;
     const uint32_t mask = passes[pi].mask;
     const KeyT *ki = (pi == 0 && k_first) ? k_first : (cur ? k1 : k0);
@@ -597,15 +658,23 @@ int radix_sort_ranges(KeyT *k0, uint32_t *v0, KeyT *k1, uint32_t *v1, size_t n, 
       // (the caller has taken this histogram)
     } else if (small) {
       hipLaunchKernelGGL(HIP_KERNEL_NAME(radix_hist_kernel<KeyT, RadixCfg<KeyT>::kSmallItems>), dim3(ntiles),
-                         dim3(kBlock), 0, st, ki, dgi, n, b, mask, table, chunk_sums, 0);
+                         dim3(kBlock), 0, st, ki, dgi, len, b, mask, table, chunk_sums, 0);
     } else {
       hipLaunchKernelGGL(HIP_KERNEL_NAME(radix_hist_kernel<KeyT, RadixCfg<KeyT>::kItems>), dim3(ntiles),
-                         dim3(kBlock), 0, st, ki, dgi, n, b, mask, table, chunk_sums, b < uniform_low_bits ? 1 : kHistSkewMode);
+                         dim3(kBlock), 0, st, ki, dgi, len, b, mask, table, chunk_sums, b < uniform_low_bits ? 1 : kHistSkewMode);
     }
+    const bool dropping = drop && pi == 0;
     if (small && kRadixBins == kBlock) {
       hipLaunchKernelGGL(radix_apply_small_kernel, dim3(nchunks), dim3(kRadixBins), 0, st, table, chunk_sums, nchunks, ntiles);
     } else {
-      hipLaunchKernelGGL(radix_spine_kernel, dim3(1), dim3(kSpineThreads), 0, st, chunk_sums, chunk_pre, nchunks);
+      hipLaunchKernelGGL(radix_spine_kernel, dim3(1), dim3(kSpineThreads), 0, st, chunk_sums, chunk_pre, nchunks,
+                         dropping ? drop->d_kept : static_cast<uint32_t *>(nullptr));
+      if (dropping) {
+        WP_HIP(hipEventRecord(drop->spine_done, st));
+        WP_HIP(hipStreamWaitEvent(drop->side, drop->spine_done, 0));
+        WP_HIP(hipMemcpyAsync(drop->h_kept, drop->d_kept, sizeof(uint32_t), hipMemcpyDeviceToHost, drop->side));
+        WP_HIP(hipEventRecord(drop->copied, drop->side));
+      }
       hipLaunchKernelGGL(radix_apply_kernel, dim3(nchunks), dim3(kRadixBins), 0, st, table, chunk_pre, ntiles);
     }
     if (stats) stats->spans.begin(st);
@@ -613,26 +682,36 @@ int radix_sort_ranges(KeyT *k0, uint32_t *v0, KeyT *k1, uint32_t *v1, size_t n, 
     const uint32_t *vsrc = identity_vals ? static_cast<const uint32_t *>(nullptr) : vi;
     constexpr int kI = RadixCfg<KeyT>::kItems;
     if (small) {
-      launch_radix_scatter<KeyT, RadixCfg<KeyT>::kSmallItems, true>(keys_only, ntiles, st, ki, vsrc, ko, vo, n, b, mask, table,
+      launch_radix_scatter<KeyT, RadixCfg<KeyT>::kSmallItems, true>(keys_only, ntiles, st, ki, vsrc, ko, vo, len, b, mask, table,
                                                                    dgo, nbit, nmask, from_val);
     } else if (pi == 0 && input_order_free) {  // (no earlier order to keep: ranks by LDS atomics)
-      launch_radix_scatter<KeyT, kI, false>(keys_only, ntiles, st, ki, vsrc, ko, vo, n, b, mask, table, dgo, nbit, nmask, from_val);
+      launch_radix_scatter<KeyT, kI, false>(keys_only, ntiles, st, ki, vsrc, ko, vo, len, b, mask, table, dgo, nbit, nmask, from_val,
+                                            dropping ? drop->blank_bits : nullptr);
     } else if (sizeof(KeyT) == 4 && mask < 64u) {  // (a digit of at most 6 bits)
-      launch_radix_scatter<KeyT, kI, true, 6>(keys_only, ntiles, st, ki, vsrc, ko, vo, n, b, mask, table, dgo, nbit, nmask, from_val);
+      launch_radix_scatter<KeyT, kI, true, 6>(keys_only, ntiles, st, ki, vsrc, ko, vo, len, b, mask, table, dgo, nbit, nmask, from_val);
     } else {
-      launch_radix_scatter<KeyT, kI, true>(keys_only, ntiles, st, ki, vsrc, ko, vo, n, b, mask, table, dgo, nbit, nmask, from_val);
+      launch_radix_scatter<KeyT, kI, true>(keys_only, ntiles, st, ki, vsrc, ko, vo, len, b, mask, table, dgo, nbit, nmask, from_val);
     }
     identity_vals = false;
     WP_LAUNCH_CHECK();
     if (stats) {
       stats->spans.end(st);
       stats->passes++;
-      stats->elems += static_cast<long long>(n);
-      if (dgo) stats->digit_bytes += static_cast<long long>(n);
+      stats->elems += static_cast<long long>(len);
+      // (a dropping pass reads len keys and writes the kept ones: counted as written when the count is known, below)
+      const long long written = dropping ? 0 : static_cast<long long>(len);
+      if (dgo) stats->digit_bytes += written;
       const long long vbytes = keys_only ? 0 : 4 + (made_up_index ? 0 : 4);  // (value written, and read unless made up)
-      stats->bytes += static_cast<long long>(n) * (static_cast<long long>(2 * sizeof(KeyT)) + vbytes + (dgo ? 1 : 0));
+      stats->bytes += static_cast<long long>(len) * (static_cast<long long>(sizeof(KeyT)) + vbytes) +
+                      written * (static_cast<long long>(sizeof(KeyT)) + (dgo ? 1 : 0));
+      if (dropping) drop_dgo = dgo != nullptr;
     }
     cur ^= 1;
+  }
+  if (drop && stats) {  // the first pass's writes: the kept keys and their digit bytes
+    const long long kept = static_cast<long long>(drop->kept);
+    if (drop_dgo) stats->digit_bytes += kept;
+    stats->bytes += kept * (static_cast<long long>(sizeof(KeyT)) + (drop_dgo ? 1 : 0));
   }
   return cur;
 }
@@ -641,10 +720,10 @@ template <typename KeyT>
 int radix_sort_pairs(KeyT *k0, uint32_t *v0, KeyT *k1, uint32_t *v1, size_t n, int begin_bit, int end_bit,
                      uint32_t *tmp, size_t tmp_words, hipStream_t st, RadixStats *stats, bool identity_vals = false,
                      int uniform_low_bits = 0, DigitBytes db = DigitBytes(), bool input_order_free = false,
-                     const RadixPlan *first_hist = nullptr, const KeyT *k_first = nullptr) {
+                     const RadixPlan *first_hist = nullptr, const KeyT *k_first = nullptr, RadixDrop *drop = nullptr) {
   BitRange r{begin_bit, end_bit};
   return radix_sort_ranges<KeyT>(k0, v0, k1, v1, n, &r, 1, tmp, tmp_words, st, stats, identity_vals,
-                                 uniform_low_bits, db, input_order_free, first_hist, k_first);
+                                 uniform_low_bits, db, input_order_free, first_hist, k_first, drop);
 }
 
 }  // namespace wp

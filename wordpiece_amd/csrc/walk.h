@@ -38,7 +38,19 @@ struct WalkArgs {
   // lookup goes through rank[] (reference layout, debug views).  rank[] then only holds the slots of needed groups.
   const uint32_t *pkey;
   StepTable ksteps;
+  int blanks_dropped;  // round 0 sorted no blank-start suffix: the key-space table has no answer for a blank position
 };
+
+// bounds-checking build: the walk uses a step value at a blank position although round 0 dropped those suffixes
+// (every lookup site stands on non-blanks: the walks skip blanks before a lookup, linear.cpp:227-229, 268-270)
+__device__ __forceinline__ void check_blank_lookup(const WalkArgs &a, uint8_t cls) {
+#ifdef WP_DEBUG_BOUNDS
+  if (a.blanks_dropped) wp_in_bounds(!(cls & kClsSpace), kSiteBlankLookup);
+#else
+  (void)a;
+  (void)cls;
+#endif
+}
 
 // The value of the step for text position q, from the loads issued for it: the position's round-0 key and rank (the
 // rank is loaded whether it is needed or not: the key-space answer decides that only after two more loads, and a load
@@ -53,6 +65,7 @@ __device__ __forceinline__ int32_t step_value_of(const WalkArgs &a, uint32_t key
 }
 __device__ __forceinline__ uint32_t step_key(const WalkArgs &a, size_t q) { return a.pkey ? a.pkey[q] : 0u; }
 __device__ __forceinline__ int32_t step_value(const WalkArgs &a, size_t q, bool prefix) {
+  check_blank_lookup(a, a.cls[q]);
   const uint32_t key = step_key(a, q);
   const uint32_t r = rank_of(a.rank[q]);
   return step_value_of(a, key, r, prefix);
@@ -279,6 +292,7 @@ __device__ __forceinline__ bool walk_finish(const WalkArgs &a, WalkState &s, Out
 template <typename Out>
 __device__ __forceinline__ bool walk_step(const WalkArgs &a, WalkState &s, Out &o) {
   const StepWin W = step_window(a, s.p);
+  check_blank_lookup(a, step_cb(a, W, s.p));
   const uint32_t key = step_key(a, s.p);
   const uint32_t r = rank_of(a.rank[s.p]);
   return walk_finish(a, s, o, W, step_value_of(a, key, r, step_word_prefix(a, W, s.p)));
@@ -1182,6 +1196,7 @@ __global__ __launch_bounds__(kBlock) void walk_lean_kernel(WalkArgs a, const uin
         uint32_t cw[4];  // class bytes of p .. p + 15 (the array has 16 bytes of slack behind the text)
         __builtin_memcpy(cw, a.cls + p, 16);
         const int32_t raw = step_value_of(a, key, r, (cw[0] & kClsWordPrefix) != 0);
+        check_blank_lookup(a, static_cast<uint8_t>(cw[0]));
         const int32_t id = step_id(a.steps, raw);
         bool fast = id >= 0 && wp_in_bounds(id < a.n_tokens, kSiteTokenId);
         uint32_t len = 0, p2 = 0, f = 0;

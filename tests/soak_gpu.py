@@ -12,64 +12,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch  # noqa: F401,E402
 import oracle_lib as O  # noqa: E402
 import wordpiece_amd as W  # noqa: E402
-
-
-def make_case(rng, k):
-    kind = k % 8
-    if kind == 0:    # tiny alphabet, long repetitive text, long tokens (streams far beyond the 32-bit key)
-        alpha, tok_max, text_len = "ab", 40, rng.randint(100, 20000)
-    elif kind == 1:  # skewed alphabet: one very frequent symbol (1-2 bit code) and rare ones (12-bit codes)
-        alpha, tok_max, text_len = "a" * 40 + "bcdefghijklmnopqrstuvwxyzABCDEFGH", 12, rng.randint(50, 8000)
-    elif kind == 2:  # spacing chars inside tokens (soft), punctuation, CJK
-        alpha, tok_max, text_len = "ab-, .c中文▁", 6, rng.randint(0, 3000)
-    elif kind == 3:  # words with shared long prefixes
-        alpha, tok_max, text_len = "abc ", 30, rng.randint(200, 30000)
-    elif kind == 4:  # wide alphabet (> 255 symbols: u32 symbols, split code)
-        alpha, tok_max, text_len = "".join(chr(c) for c in range(0x400, 0x400 + 300)) + " ab", 8, rng.randint(50, 5000)
-    elif kind == 5:  # big case: full-size radix tiles and digit bytes (n > 2^21)
-        alpha, tok_max, text_len = "etaoinshr dlu ", 20, rng.randint(2_200_000, 5_200_000)  # (> 2^22: LDS-window rank store, ranks inside its first pass)
-    elif kind == 6:  # invalid UTF-8 sprinkled in
-        alpha, tok_max, text_len = "ab c", 10, rng.randint(10, 2000)
-    else:
-        alpha, tok_max, text_len = "abcdefgh ij", 18, rng.randint(0, 6000)
-    nt = rng.randint(1, 40)
-    vocab = set()
-    base = "".join(rng.choice(alpha.replace(" ", "")) for _ in range(tok_max)) if kind in (0, 3) else None
-    while len(vocab) < nt:
-        ln = rng.randint(1, tok_max)
-        if base is not None and rng.random() < 0.6:
-            w = base[:ln]  # prefixes of one long word: many long tokens with one key
-        else:
-            w = "".join(rng.choice(alpha) for _ in range(ln))
-        if not w.strip():
-            continue
-        if rng.random() < 0.4:
-            w = "##" + w
-        vocab.add(w)
-    vocab = sorted(vocab)
-    rng.shuffle(vocab)
-    if rng.random() < 0.4:
-        vocab.append("[UNK]")
-    if kind == 3 or kind == 0:
-        words = [w.lstrip("#") for w in vocab if w != "[UNK]"] + [base]
-        parts = []
-        n = 0
-        while n < text_len:
-            w = rng.choice(words)
-            cut = rng.randint(1, len(w))
-            piece = w[:cut] + (rng.choice(words)[:rng.randint(0, 8)] if rng.random() < 0.5 else "")
-            parts.append(piece)
-            n += len(piece) + 1
-        text = " ".join(parts)
-    else:
-        text = "".join(rng.choice(alpha) for _ in range(text_len))
-    tb = text.encode("utf8")
-    if kind == 6:
-        bb = bytearray(tb)
-        for _ in range(rng.randint(1, 6)):
-            bb.insert(rng.randint(0, len(bb)), rng.choice([0xff, 0xc0, 0x80, 0xe2, 0xf0]))
-        tb = bytes(bb)
-    return tb, vocab
+from round0_cases import make_case  # noqa: E402  (shared with tests/test_gpu_round0_edges.py)
 
 
 def main():

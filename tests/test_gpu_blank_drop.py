@@ -17,29 +17,13 @@ import pytest
 import oracle_lib as O
 import wordpiece_amd as W
 from wordpiece_amd import synth
+from round0_cases import BLANKS, SPACE_TOKEN, check as _check, kept as _kept, letters_vocab as _letters_vocab  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(os.path.abspath(W.__file__))
 
-BLANKS = " \t\n\v\f\r"
-SPACE_TOKEN = "▁"
 BIG = 3 << 20  # bytes: above the 2^21 symbols from which the key builder takes the sort's first histogram
-
-
-def _kept(text):
-    """Suffixes the sort keeps: the non-blank positions of the text and the terminal one."""
-    s = text.decode("utf-8")
-    arr = np.frombuffer(s.encode("utf-32-le"), dtype=np.uint32)
-    blank = np.isin(arr, np.array([ord(c) for c in BLANKS + SPACE_TOKEN], dtype=np.uint32))
-    return int(arr.size - blank.sum()) + 1
-
-
-def _letters_vocab(rng, n_words=3000):
-    letters = "abcdefghijklmnopqrstuvwxyz"
-    words = sorted({"".join(rng.choice(letters) for _ in range(rng.randint(2, 12))) for _ in range(n_words)})
-    vocab = ["[UNK]"] + list(letters) + ["##" + c for c in letters] + words + ["##" + w[:3] for w in words[:400]]
-    return sorted(set(vocab)), words
 
 
 def _blank_runs_case(seed, nbytes=BIG, space_token=False):
@@ -105,33 +89,6 @@ def _golden_cases():
             for case in json.load(f)["cases"]:
                 out.append((bytes.fromhex(case["text_hex"]), [bytes.fromhex(w) for w in case["vocab_hex"]]))
     return out
-
-
-def _three_ways(text, vocab, offsets=False):
-    """ids (and byte offsets) of the default handle, WP_OPT_SORT_BLANKS=1 and WP_OPT_INDEXED_ROUND0=1; the default
-    handle's statistics"""
-    res, st = [], None
-    for opt in (None, W.WP_OPT_SORT_BLANKS, W.WP_OPT_INDEXED_ROUND0):
-        gv = W.Vocab(vocab)
-        if opt is not None:
-            gv.set_option(opt, 1)
-        if offsets:
-            ids, offs = gv.encode_with_offsets(text)
-            res.append((np.array(ids), np.array(offs)))
-        else:
-            res.append((gv.encode(text), None))
-        if opt is None:
-            st = gv.stats()
-    return res, st
-
-
-def _check(text, vocab, exp=None, offsets=False):
-    (a, oa), (b, ob), (c, oc) = _three_ways(text, vocab, offsets)[0]
-    if exp is not None:
-        assert np.array_equal(a, exp), (len(text), vocab[:5])
-    assert np.array_equal(a, b) and np.array_equal(a, c), (len(text), vocab[:5])
-    if offsets:
-        assert np.array_equal(oa, ob) and np.array_equal(oa, oc), (len(text), vocab[:5])
 
 
 def test_golden_vectors_ids_and_offsets():

@@ -43,7 +43,10 @@ enum BoundSite {
   kSiteCandRun = 5,  // (no address either: a long token's key whose candidate run is not as long as its group)
   kSiteSpan = 6,     // offsets mode: the code point -> byte table and spans outside the text (offsets.h)
   kSiteBlankLookup = 7,  // (no address: the walk used a step value at a blank, whose suffix round 0 dropped; walk.h)
-  kBoundSites = 8
+  // (no address: the sorted array of round 0 in the default layout — a descent, a key the blank table marks although
+  // blanks were dropped, or a multiset unlike the kept keys of the unsorted array; linear_path.h, sorted_check_kernel)
+  kSiteSortOrder = 8,
+  kBoundSites = 9
 };
 #ifdef WP_DEBUG_BOUNDS
 __device__ unsigned int g_wp_oob[kBoundSites];

@@ -40,6 +40,65 @@ __global__ void needed_list_clamp_kernel(uint32_t *__restrict__ totals, uint32_t
 // keys saves (config 2, 14.9 % blanks: 0.15 ms per step gained; config 5, 0.2 %: 1.5 % slower with the drop on).
 constexpr double kBlankDropMinShare = 1.0 / 16;
 
+#ifdef WP_DEBUG_BOUNDS
+// The sorted array of round 0 in the default layout (no debug view shows it, and the walk finds its steps by key value,
+// so the ids can be right over a wrong array), counted under kSiteSortOrder:
+//   descents sorted[i] > sorted[i + 1];
+//   keys the blank table marks (blanks dropped: none may be left);
+//   the sorted array against the keys the sort had to keep of the unsorted array (which survives the sort), as multisets:
+//   count, wrapping sum and xor of each side.  Kept: every key where no blanks were dropped, else the positions whose
+//   class byte (written by the decode, not derived from the code) is no blank, and the terminal one.
+__device__ unsigned int g_wp_sorted_sig[6];  // count, sum, xor: the sorted array | the kept keys of the unsorted one
+__global__ __launch_bounds__(kBlock) void sorted_check_kernel(const uint32_t *__restrict__ sorted, size_t n_sorted,
+                                                              const uint32_t *__restrict__ unsorted, size_t n,
+                                                              const uint8_t *__restrict__ cls, size_t n_text,
+                                                              const uint32_t *__restrict__ blank_bits) {
+  __shared__ uint32_t acc[7];
+  if (threadIdx.x < 7) acc[threadIdx.x] = 0u;
+  __syncthreads();
+  uint32_t bad = 0, cnt[2] = {0, 0}, sum[2] = {0, 0}, x[2] = {0, 0};
+  const size_t first = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x, stride = static_cast<size_t>(gridDim.x) * kBlock;
+  for (size_t i = first; i < n_sorted; i += stride) {
+    const uint32_t k = sorted[i];
+    if (i + 1 < n_sorted && k > sorted[i + 1]) bad++;
+    if (blank_bits && key_is_blank(blank_bits, k)) bad++;
+    cnt[0]++;
+    sum[0] += k;
+    x[0] ^= k;
+  }
+  for (size_t i = first; i < n; i += stride) {
+    if (blank_bits && i < n_text && (cls[i] & kClsSpace)) continue;
+    const uint32_t k = unsorted[i];
+    cnt[1]++;
+    sum[1] += k;
+    x[1] ^= k;
+  }
+  if (bad) atomicAdd(&acc[6], bad);
+  for (int s = 0; s < 2; s++) {
+    if (cnt[s]) {
+      atomicAdd(&acc[3 * s], cnt[s]);
+      atomicAdd(&acc[3 * s + 1], sum[s]);
+      atomicXor(&acc[3 * s + 2], x[s]);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 6 && acc[threadIdx.x]) {
+    if (threadIdx.x % 3 == 2) {
+      atomicXor(&g_wp_sorted_sig[threadIdx.x], acc[threadIdx.x]);
+    } else {
+      atomicAdd(&g_wp_sorted_sig[threadIdx.x], acc[threadIdx.x]);
+    }
+  }
+  if (threadIdx.x == 6 && acc[6]) atomicAdd(&g_wp_oob[kSiteSortOrder], acc[6]);
+}
+__global__ void sorted_check_close_kernel() {
+  bool same = true;
+  for (int j = 0; j < 3; j++) same = same && g_wp_sorted_sig[j] == g_wp_sorted_sig[3 + j];
+  wp_in_bounds(same, kSiteSortOrder);
+  for (int j = 0; j < 6; j++) g_wp_sorted_sig[j] = 0u;
+}
+#endif
+
 template <typename SymT>
 struct LinearPath {
   // ---- what the decode phase hands over
@@ -524,6 +583,15 @@ struct LinearPath {
       S.hist_in_keys = hist_in_keys ? 1 : 0;
       keys = cur ? KB : sk;
       other_keys = cur ? sk : KB;
+#ifdef WP_DEBUG_BOUNDS
+      if constexpr (sizeof(Key0) == 4) {
+        hipLaunchKernelGGL(sorted_check_kernel, dim3(std::min<size_t>(cdiv(n, kBlock), 1024)), dim3(kBlock), 0, st,
+                           reinterpret_cast<const uint32_t *>(keys), n_sorted, reinterpret_cast<const uint32_t *>(KA), n, d_cls, n_text,
+                           drop_blanks ? d_blank_bits : static_cast<const uint32_t *>(nullptr));
+        hipLaunchKernelGGL(sorted_check_close_kernel, dim3(1), dim3(1), 0, st);
+        WP_LAUNCH_CHECK();
+      }
+#endif
       vals = keys_only ? nullptr : (cur ? VB : VA);
       other_vals = keys_only ? nullptr : (cur ? VA : VB);
       if (keys_only) sort_candidates();
@@ -1248,12 +1316,13 @@ struct LinearPath {
       WP_HIP(hipMemcpyFromSymbol(oob, HIP_SYMBOL(g_wp_oob), sizeof(oob)));
       const unsigned int zero[kBoundSites] = {};
       WP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_wp_oob), zero, sizeof(zero)));
-      if (oob[0] | oob[1] | oob[2] | oob[3] | oob[4] | oob[5] | oob[6] | oob[7]) {
+      if (oob[0] | oob[1] | oob[2] | oob[3] | oob[4] | oob[5] | oob[6] | oob[7] | oob[8]) {
         throw HipError("debug bounds: out-of-range addresses skipped: radix scatter " + std::to_string(oob[0]) + ", rank store " +
                        std::to_string(oob[1]) + ", token id " + std::to_string(oob[2]) + ", list slot " + std::to_string(oob[3]) +
                        "; key-space step starts inside a run of equal keys " + std::to_string(oob[4]) +
                        "; candidate runs unlike their group " + std::to_string(oob[5]) + "; offsets " + std::to_string(oob[6]) +
-                       "; step values used at blanks " + std::to_string(oob[7]));
+                       "; step values used at blanks " + std::to_string(oob[7]) +
+                       "; round-0 sorted array: descents, blank keys left, multiset unlike the kept keys " + std::to_string(oob[8]));
       }
       S.reserved0 = 1;  // this is the bounds-checking build
     }

@@ -90,6 +90,54 @@ int wp_linear_encode_offsets(wp_vocab *v, const char *utf8, size_t nbytes, int u
 int wp_linear_encode_offsets_device(wp_vocab *v, const void *d_utf8, size_t nbytes, int unit,
                                     const int32_t **d_ids, const uint32_t **d_offsets, size_t *n_ids);
 
+/* ---- documents (an addition: TF Text RaggedTensor.row_splits, HF BatchEncoding / tokenizer(padding=, truncation=)) ----
+ * Many documents in one call.  Input is the joined form: the documents back to back, each followed by one '\n' (a
+ * corpus file with one document per line).  The rows are given
+ *   explicitly: doc_off[0..n_docs] (increasing, doc_off[0] == 0, doc_off[n_docs] == nbytes); document i is bytes
+ *     [doc_off[i], doc_off[i + 1] - 1) and byte doc_off[i + 1] - 1 must be '\n' (a document may itself hold '\n': a blank
+ *     like any other).  Anything else fails with WP_ERR_ARG before ids are produced (host entry points check on the
+ *     host, device entry points by a kernel);
+ *   or as the lines of the text (doc_off == NULL; n_docs is ignored): a text that does not end in '\n' has a last
+ *     line that runs to the end, one that does has no extra empty row.
+ * Result for n_rows documents: ids (n_ids) and row_splits (n_rows + 1, row_splits[0] == 0, row_splits[n_rows] == n_ids)
+ * — row i is ids[row_splits[i] .. row_splits[i + 1]) — and, with unit WP_OFFSETS_* (-1: none, offsets NULL), offsets
+ * as wp_linear_encode_offsets gives them but relative to the start of the id's own document.  Row i and its offsets
+ * are exactly what wp_linear_encode_offsets(document i) returns (an empty document, or one of blanks or invalid bytes
+ * only, is an empty row); the rows concatenated are wp_linear_encode of the joined text.
+ * Normally that is one encode of the joined text plus a few kernels over the spans (wp_stats.rows_route == 1).  Three
+ * kinds of vocabulary could match differently in the joined text than in a document of its own and are encoded
+ * document by document instead (rows_route == 0, same results, one encode per document): an eligible token that holds
+ * U+000A, a token that holds U+0000 / U+0001, duplicate eligible lines.
+ * Limits: those of the joined text as one encode, and nbytes <= UINT32_MAX in every unit (WP_ERR_TOO_LARGE).  Like the
+ * offsets calls these run on the handle's own device (WP_OPT_DEVICES does not shard them).  Empty input (nbytes == 0,
+ * or explicit rows that are all empty) needs no device in the host entry points. */
+/* tf_text tokenize_with_offsets on a batch -> RaggedTensor (values, row_splits); HF BatchEncoding.input_ids /
+ * .offset_mapping.  Host text in; ids, row_splits and offsets out as blocks of their own (free each with wp_free; ids
+ * and offsets NULL when n_ids == 0, offsets NULL when unit == -1). */
+int wp_linear_encode_rows(wp_vocab *v, const char *utf8, size_t nbytes, const int64_t *doc_off, size_t n_docs, int unit,
+                          int32_t **ids, int64_t **row_splits, uint32_t **offsets, size_t *n_ids, size_t *n_rows);
+/* the same with the text (buffer contract of wp_linear_encode_device) and doc_off (8-byte aligned, or NULL) in device
+ * memory; the results stay there, owned by the handle and valid until its next call */
+int wp_linear_encode_rows_device(wp_vocab *v, const void *d_utf8, size_t nbytes, const int64_t *d_doc_off, size_t n_docs,
+                                 int unit, const int32_t **d_ids, const int64_t **d_row_splits, const uint32_t **d_offsets,
+                                 size_t *n_ids, size_t *n_rows);
+/* HF tokenizer(batch, padding="max_length", truncation=True, max_length=) / tf_text pad_model_inputs: row r of
+ * input_ids[n_rows, max_len] is [cls] + T[:keep] + [sep] + pad..., T the ids of document r, keep = min(len(T),
+ * max_len - number of specials); lengths[r] = keep + number of specials (the attention mask is arange(max_len) <
+ * lengths[:, None]).  cls_id / sep_id -1: none; the ids are not range-checked against the vocabulary.  max_len < 1 or
+ * smaller than the number of specials fails with WP_ERR_ARG.  wp_stats.rows_truncated counts the rows that lost ids.
+ * Host text in, two blocks out (free each with wp_free). */
+int wp_linear_encode_padded(wp_vocab *v, const char *utf8, size_t nbytes, const int64_t *doc_off, size_t n_docs,
+                            int max_len, int32_t cls_id, int32_t sep_id, int32_t pad_id, int32_t **input_ids,
+                            int32_t **lengths, size_t *n_rows);
+/* the same from device memory into caller-owned device buffers (a training loop's batch tensor: no copy): d_input_ids
+ * holds capacity_rows * max_len int32, d_lengths capacity_rows; nothing beyond n_rows rows is touched.  More rows than
+ * capacity_rows fails with WP_ERR_ARG, the needed count in *n_rows and nothing written.  The call returns when the
+ * batch is complete. */
+int wp_linear_encode_padded_device(wp_vocab *v, const void *d_utf8, size_t nbytes, const int64_t *d_doc_off, size_t n_docs,
+                                   int max_len, int32_t cls_id, int32_t sep_id, int32_t pad_id, int32_t *d_input_ids,
+                                   int32_t *d_lengths, size_t capacity_rows, size_t *n_rows);
+
 /* The same call sharded over several GPUs of the node, behind the boundary: the reference's own
  * precedent is the in-library chunking at whitespace of linear.cpp:283-299 (thread chunks) and
  * linear.cpp:355-367 (encodeExternal batches).  The text is cut at ASCII whitespace into one shard
@@ -252,6 +300,10 @@ typedef struct {
   int32_t offsets_unit;       /* the unit of the last encode's offsets (WP_OFFSETS_*), -1: an ids-only encode        */
   int64_t round0_sorted;      /* suffixes in round 0's sorted array: n_total, or fewer when the keys-only round 0 left out
                                  the blank-start suffixes (see WP_OPT_SORT_BLANKS)                                     */
+  int64_t n_rows, rows_truncated; /* documents calls (wp_linear_encode_rows / _padded): the number of rows, and the rows that
+                                 lost ids to max_len in a padded call; n_rows -1: the last call was no documents call      */
+  int32_t rows_route;         /* documents calls: 1 = one pass over the joined text, 0 = one encode per document (see the
+                                 section "documents"); -1: the last call was no documents call                          */
 } wp_stats;
 int wp_get_stats(const wp_vocab *v, wp_stats *out);
 

@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "wp_linear_encode_multi", "wp_reserve", "wp_fast_encode", "wp_fast_encode_device", "wp_fast_encode_file",
     "wp_fast_encode_external", "wp_vocab_token_utf8", "wp_trim", "wp_linear_encode_batch", "wp_linear_encode_stream",
     "wp_linear_encode_offsets", "wp_linear_encode_offsets_device",
+    "wp_linear_encode_rows", "wp_linear_encode_rows_device", "wp_linear_encode_padded", "wp_linear_encode_padded_device",
 ]
 
 
@@ -60,7 +61,8 @@ class Stats(C.Structure):
                 ("rank_in_pass", C.c_int32), ("trie_refine", C.c_int32), ("arena_bytes", C.c_int64),
                 ("list_retries", C.c_int32), ("hist_in_keys", C.c_int32), ("radix_pass_bytes", C.c_int64),
                 ("round0_candidates", C.c_int64), ("round0_keys_only", C.c_int32), ("offsets_unit", C.c_int32),
-                ("round0_sorted", C.c_int64)]
+                ("round0_sorted", C.c_int64), ("n_rows", C.c_int64), ("rows_truncated", C.c_int64),
+                ("rows_route", C.c_int32)]
 
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_ if k != "active_per_round"}
@@ -102,6 +104,15 @@ def lib():
                                                C.POINTER(C.c_size_t)]
         L.wp_linear_encode_offsets_device.argtypes = [vp, vp, C.c_size_t, C.c_int, C.POINTER(vp), C.POINTER(vp),
                                                       C.POINTER(C.c_size_t)]
+        i64p = C.POINTER(C.c_int64)
+        L.wp_linear_encode_rows.argtypes = [vp, C.c_char_p, C.c_size_t, i64p, C.c_size_t, C.c_int, C.POINTER(i32p),
+                                            C.POINTER(i64p), C.POINTER(u32p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.wp_linear_encode_rows_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.POINTER(vp), C.POINTER(vp),
+                                                   C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.wp_linear_encode_padded.argtypes = [vp, C.c_char_p, C.c_size_t, i64p, C.c_size_t, C.c_int, C.c_int32, C.c_int32,
+                                              C.c_int32, C.POINTER(i32p), C.POINTER(i32p), C.POINTER(C.c_size_t)]
+        L.wp_linear_encode_padded_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int32, C.c_int32,
+                                                     C.c_int32, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.wp_linear_encode_multi.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.POINTER(i32p),
                                              C.POINTER(C.c_size_t)]
         L.wp_reserve.argtypes = [vp, C.c_size_t]
@@ -211,6 +222,112 @@ class Vocab:
         _check(lib().wp_linear_encode_offsets_device(self._h, C.c_void_p(d_ptr), nbytes, _offset_unit(unit), C.byref(d_ids),
                                                      C.byref(d_offs), C.byref(n)))
         return d_ids.value, d_offs.value, n.value
+
+    def encode_rows(self, docs=None, text=None, doc_offsets=None, offsets=None):
+        """Many documents in one call (wp_linear_encode_rows) -> (ids int32 [n], row_splits int64 [n_rows + 1]) and,
+        with offsets="byte" / "char", offsets uint32 [n, 2] relative to the id's own document; row i is
+        ids[row_splits[i]:row_splits[i + 1]] and equals encode_with_offsets(document i).  `docs`: a list of str / bytes
+        (joined here, join_docs); or `text` in joined form (every document followed by one "\\n") with `doc_offsets`
+        (int64 [n_docs + 1]), or alone: the rows are its lines.  The arrays are views of the library's blocks."""
+        b, off = _docs_arg(docs, text, doc_offsets)
+        unit = -1 if offsets is None else _offset_unit(offsets)
+        ids, splits, offs = C.POINTER(C.c_int32)(), C.POINTER(C.c_int64)(), C.POINTER(C.c_uint32)()
+        n, rows = C.c_size_t(), C.c_size_t()
+        _check(lib().wp_linear_encode_rows(self._h, b, len(b), _i64_ptr(off), 0 if off is None else len(off) - 1, unit,
+                                           C.byref(ids), C.byref(splits), C.byref(offs), C.byref(n), C.byref(rows)))
+        out = (_adopt_ids(ids, n.value), _adopt_block(splits, (rows.value + 1,)))
+        if offsets is None:
+            return out
+        return out + (_adopt_block(offs, (n.value, 2)) if n.value else np.zeros((0, 2), dtype=np.uint32),)
+
+    def encode_padded(self, docs=None, text=None, doc_offsets=None, max_len=128, cls_id=None, sep_id=None, pad_id=0):
+        """Padded batch (wp_linear_encode_padded) -> (input_ids int32 [n_rows, max_len], lengths int32 [n_rows]): row r is
+        [cls] + ids of document r cut to fit + [sep] + pad...; lengths[r] counts everything but the padding (attention
+        mask: arange(max_len) < lengths[:, None]).  Documents as in encode_rows."""
+        b, off = _docs_arg(docs, text, doc_offsets)
+        ids, lens = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)()
+        rows = C.c_size_t()
+        _check(lib().wp_linear_encode_padded(self._h, b, len(b), _i64_ptr(off), 0 if off is None else len(off) - 1,
+                                             int(max_len), _special(cls_id), _special(sep_id), int(pad_id), C.byref(ids),
+                                             C.byref(lens), C.byref(rows)))
+        if rows.value == 0:
+            return np.zeros((0, int(max_len)), dtype=np.int32), np.zeros(0, dtype=np.int32)
+        return _adopt_block(ids, (rows.value, int(max_len))), _adopt_block(lens, (rows.value,))
+
+    def _rows_tensor_args(self, text, doc_offsets):
+        import torch
+        if text.dtype != torch.uint8 or not text.is_cuda or not text.is_contiguous():
+            raise WordPieceError("a documents call on tensors needs a contiguous uint8 CUDA/HIP text tensor")
+        nbytes = text.numel()
+        if text.data_ptr() % 4 != 0 or nbytes % 4 != 0:  # (as encode_tensor: the decoder reads whole aligned words)
+            padded = torch.zeros((nbytes + 19) // 16 * 16, dtype=torch.uint8, device=text.device)
+            padded[:nbytes] = text
+            text = padded
+        if doc_offsets is not None:
+            if doc_offsets.dtype != torch.int64 or doc_offsets.device != text.device or doc_offsets.dim() != 1 or \
+                    doc_offsets.numel() < 1:
+                raise WordPieceError("doc_offsets must be a 1-d int64 tensor on the text's device")
+            doc_offsets = doc_offsets.contiguous()
+        torch.cuda.current_stream(text.device).synchronize()  # the library runs on its own HIP streams
+        return text, nbytes, doc_offsets
+
+    def encode_rows_tensor(self, text, doc_offsets=None, offsets=None, copy=True):
+        """encode_rows for a uint8 text tensor in joined form (and an optional int64 offsets tensor) on this handle's
+        GPU (wp_linear_encode_rows_device) -> tensors there: (ids int32 [n], row_splits int64 [n_rows + 1][, offsets
+        uint32 [n, 2]]).  copy=False: views of the library's buffers, valid until the next call on this handle."""
+        import torch
+        text, nbytes, doc_offsets = self._rows_tensor_args(text, doc_offsets)
+        unit = -1 if offsets is None else _offset_unit(offsets)
+        d_ids, d_splits, d_offs = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        n, rows = C.c_size_t(), C.c_size_t()
+        _check(lib().wp_linear_encode_rows_device(
+            self._h, C.c_void_p(text.data_ptr()), nbytes, None if doc_offsets is None else C.c_void_p(doc_offsets.data_ptr()),
+            0 if doc_offsets is None else doc_offsets.numel() - 1, unit, C.byref(d_ids), C.byref(d_splits), C.byref(d_offs),
+            C.byref(n), C.byref(rows)))
+        dev = text.device
+        ids = torch.as_tensor(DeviceIds(d_ids.value, n.value), device=dev) if n.value else \
+            torch.zeros(0, dtype=torch.int32, device=dev)
+        splits = torch.as_tensor(DeviceIds(d_splits.value, rows.value + 1, typestr="<i8"), device=dev)
+        out = (ids, splits)
+        if offsets is not None:
+            out += (torch.as_tensor(DeviceIds(d_offs.value, n.value, cols=2), device=dev).view(torch.uint32) if n.value else
+                    torch.zeros((0, 2), dtype=torch.uint32, device=dev),)
+        return tuple(t.clone() for t in out) if copy else out
+
+    def encode_padded_tensor(self, text, doc_offsets=None, max_len=128, cls_id=None, sep_id=None, pad_id=0, n_rows=None,
+                             out=None):
+        """encode_padded for tensors on this handle's GPU (wp_linear_encode_padded_device) -> (input_ids int32
+        [n_rows, max_len], lengths int32 [n_rows]) written by the library into torch.empty tensors (no copy).  The row
+        count of explicit offsets is known; in lines mode pass `n_rows` (an upper bound will do) or the call runs twice
+        when the first guess was too small.  out=(input_ids, lengths): caller-owned tensors to write into (views of the
+        first n_rows rows are returned)."""
+        import torch
+        text, nbytes, doc_offsets = self._rows_tensor_args(text, doc_offsets)
+        max_len = int(max_len)
+        cap = doc_offsets.numel() - 1 if doc_offsets is not None else int(n_rows) if n_rows is not None else nbytes // 32 + 1
+        rows = C.c_size_t()
+        for _ in range(2):
+            if out is not None:
+                ids, lens = out
+                if ids.dtype != torch.int32 or lens.dtype != torch.int32 or not ids.is_contiguous() or \
+                        not lens.is_contiguous() or ids.device != text.device or lens.device != text.device or \
+                        ids.dim() != 2 or ids.shape[1] != max_len:
+                    raise WordPieceError("out must be contiguous int32 tensors [rows, max_len] and [rows] on the text's device")
+                cap = min(ids.shape[0], lens.numel())
+            else:
+                ids = torch.empty((cap, max_len), dtype=torch.int32, device=text.device)
+                lens = torch.empty(cap, dtype=torch.int32, device=text.device)
+            torch.cuda.current_stream(text.device).synchronize()
+            rc = lib().wp_linear_encode_padded_device(
+                self._h, C.c_void_p(text.data_ptr()), nbytes, None if doc_offsets is None else C.c_void_p(doc_offsets.data_ptr()),
+                0 if doc_offsets is None else doc_offsets.numel() - 1, max_len, _special(cls_id), _special(sep_id), int(pad_id),
+                C.c_void_p(ids.data_ptr()), C.c_void_p(lens.data_ptr()), cap, C.byref(rows))
+            if rc != 0 and out is None and rows.value > cap:  # (lines mode, guess too small: the call said how many)
+                cap = rows.value
+                continue
+            _check(rc)
+            break
+        return ids[:rows.value], lens[:rows.value]
 
     def fast_encode(self, text):
         """word_piece::fast::encode on the GPU (wp_fast_encode): host bytes/str -> numpy int32 ids."""
@@ -356,6 +473,39 @@ def _adopt_block(ptr, shape):
     return out
 
 
+def join_docs(docs):
+    """The joined form of a list of documents (str / bytes): every document followed by one "\\n" -> (bytes, int64
+    offsets [n_docs + 1]); document i is bytes[offsets[i]:offsets[i + 1] - 1]."""
+    bs = [_bytes(d) for d in docs]
+    off = np.zeros(len(bs) + 1, dtype=np.int64)
+    if bs:
+        off[1:] = np.cumsum([len(b) + 1 for b in bs])
+    return b"".join(b + b"\n" for b in bs), off
+
+
+def _docs_arg(docs, text, doc_offsets):
+    if (docs is None) == (text is None):
+        raise WordPieceError("give either docs or text")
+    if docs is not None:
+        if doc_offsets is not None:
+            raise WordPieceError("doc_offsets go with text, not with docs")
+        return join_docs(docs)
+    if doc_offsets is None:
+        return _bytes(text), None
+    off = np.ascontiguousarray(doc_offsets, dtype=np.int64)
+    if off.ndim != 1 or len(off) < 1:
+        raise WordPieceError("doc_offsets must be a 1-d array of n_docs + 1 entries")
+    return _bytes(text), off
+
+
+def _i64_ptr(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def _special(i):
+    return -1 if i is None else int(i)
+
+
 def _offset_unit(unit):
     if unit not in _OFFSET_UNITS:
         raise WordPieceError("offsets unit must be 'byte' or 'char', not %r" % (unit,))
@@ -366,9 +516,9 @@ class DeviceIds:
     """`__cuda_array_interface__` view of an id buffer in HBM owned by the library (torch.as_tensor,
     cupy.asarray, numba … accept it without a copy)."""
 
-    def __init__(self, ptr, n, cols=0):
+    def __init__(self, ptr, n, cols=0, typestr="<i4"):
         shape = (n, cols) if cols else (n,)
-        self.__cuda_array_interface__ = {"shape": shape, "typestr": "<i4", "data": (ptr, False), "version": 2}
+        self.__cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (ptr, False), "version": 2}
 
 
 class _Linear:

@@ -141,6 +141,21 @@ static int bit_length(uint64_t v) {
 constexpr int kScalars = 32;
 constexpr int kScalarCand = 24;  // d_scalars word: entries of the keys-only round 0's candidate list (linear_path.h)
 constexpr int kScalarKept = 25;  // d_scalars word: suffixes the keys-only round 0 kept (not blank-start; radix_sort.h, RadixDrop)
+// documents calls (rows.h): lines of the text / boundaries of explicit rows that fail the check / rows a padded call cut
+constexpr int kScalarRows = 21, kScalarRowsBad = 22, kScalarRowsCut = 23;
+
+// A documents call (wp_linear_encode_rows / _padded) as encode_on_device sees it: how the rows are given, and where it
+// left the row structure (device pointers into the arenas, valid like c->d_ids until the handle's next call).
+struct RowsCall {
+  const long long *d_doc_off = nullptr;  // explicit rows: n_docs + 1 starts in device memory; nullptr: the lines of the text
+  size_t n_docs = 0;
+  int unit = -1;                   // unit of the offsets the caller asked for (-1: none; the spans are then left in code points)
+  size_t capacity = SIZE_MAX;      // rows the caller has room for: more is std::invalid_argument once the count is known
+  size_t n_rows = 0;               // out: the number of rows (set before the capacity check)
+  const long long *d_starts = nullptr;      // out: n_rows + 1 document starts in bytes
+  const long long *d_row_splits = nullptr;  // out: n_rows + 1
+  uint32_t *d_line_cnt = nullptr;  // lines mode: line ends per tile, scanned (phase A arena)
+};
 
 struct Context {
   int device = 0;
@@ -163,6 +178,8 @@ struct Context {
   DeviceBuffer text_buf, a_buf, b_buf, fmt_buf;  // fmt_buf: id text of encodeExternal
   // wp_linear_encode_batch: second text buffer, two id staging buffers and the copy streams of the shard pipeline
   DeviceBuffer text_buf2, ids_stage[2];
+  // documents calls: explicit row starts of a host call, results of the per-document route, padded batch of a host call
+  DeviceBuffer rows_in, rows_out, pad_buf;
   hipStream_t up_stream = nullptr, down_stream = nullptr;
   hipEvent_t pipe_ev[4] = {};  // ids staged [2], ids downloaded [2]
   uint32_t *d_used = nullptr, *d_lut = nullptr, *d_scan_tmp = nullptr;  // bitmap of the code points in use (kCpWords), lut (kCpTableSize), per-word prefixes (kCpWords)
@@ -261,7 +278,7 @@ static void destroy_context(Context *c) {
   if (!c) return;
   const bool owns = c->stream || c->stream2 || c->stream3 || c->d_used || c->d_lut || c->d_scan_tmp || c->d_scalars || c->d_code ||
                     c->d_symhist || c->h_scalars || c->h_code || c->d_stream || c->text_buf.p || c->a_buf.p ||
-                    c->b_buf.p || c->fmt_buf.p;
+                    c->b_buf.p || c->fmt_buf.p || c->rows_in.p || c->rows_out.p || c->pad_buf.p;
   if (!owns) return;
   DeviceGuard keep;
   (void)hipSetDevice(c->device);
@@ -283,6 +300,9 @@ static void destroy_context(Context *c) {
   c->text_buf2.release();
   c->ids_stage[0].release();
   c->ids_stage[1].release();
+  c->rows_in.release();
+  c->rows_out.release();
+  c->pad_buf.release();
   for (auto &e : c->pipe_ev) {
     if (e) (void)hipEventDestroy(e);
     e = nullptr;
@@ -330,6 +350,9 @@ static std::vector<std::unique_ptr<Context>> &context_pool() {
 }
 
 static void release_arenas(Context *c) {
+  c->rows_in.release();
+  c->rows_out.release();
+  c->pad_buf.release();
   c->text_buf2.release();
   c->ids_stage[0].release();
   c->ids_stage[1].release();
@@ -350,7 +373,8 @@ static void park_context(std::unique_ptr<Context> c) {
   if (!no_pool && hipStreamSynchronize(c->stream) == hipSuccess && hipStreamSynchronize(c->stream2) == hipSuccess &&
       hipStreamSynchronize(c->stream3) == hipSuccess) {
     free_vocab_tables(c.get());
-    if (c->text_buf.cap + c->text_buf2.cap + c->ids_stage[0].cap + c->ids_stage[1].cap + c->a_buf.cap + c->b_buf.cap + c->fmt_buf.cap >
+    if (c->text_buf.cap + c->text_buf2.cap + c->ids_stage[0].cap + c->ids_stage[1].cap + c->a_buf.cap + c->b_buf.cap + c->fmt_buf.cap +
+            c->rows_in.cap + c->rows_out.cap + c->pad_buf.cap >
         kPoolArenaBytes) {
       release_arenas(c.get());
     }

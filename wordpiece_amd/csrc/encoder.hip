@@ -556,6 +556,362 @@ int wp_linear_encode_offsets_device(wp_vocab *v, const void *d_utf8, size_t nbyt
   });
 }
 
+}  // extern "C"
+
+// ---- documents (include/wordpiece_amd.h, section "documents"; kernels: rows.h) --------------------------------------
+namespace {
+struct RowsResult {  // device pointers, valid until the handle's next call
+  const int32_t *d_ids = nullptr;
+  const long long *d_row_splits = nullptr;
+  const uint32_t *d_offs = nullptr;
+  size_t n_ids = 0, n_rows = 0;
+};
+
+// A vocabulary that can match differently inside a joined text than in a document of its own: an eligible token with
+// U+000A matches across the separator; a token with U+0000 / U+0001 can match into the 1 . vocab tail of S, which only
+// the end of a text has; with duplicate eligible lines the copy a match at the end of a text names depends on what
+// follows it.  Such batches are encoded document by document.
+bool rows_per_document(const wp_vocab *v) { return v->hv.newline_in_token || v->hv.low_cp || v->hv.n_dup_eligible > 0; }
+
+void check_rows_call(int unit, size_t nbytes) {
+  if (unit != -1 && unit != WP_OFFSETS_BYTES && unit != WP_OFFSETS_CODE_POINTS) {
+    throw std::invalid_argument("offsets unit must be -1 (none), 0 (bytes) or 1 (code points)");
+  }
+  // (row membership goes through the 32-bit first-byte table of the code points in every unit)
+  if (nbytes > static_cast<size_t>(UINT32_MAX)) throw std::length_error("a documents call needs nbytes <= UINT32_MAX");
+}
+
+int padded_specials(int max_len, int32_t cls_id, int32_t sep_id) {
+  const int specials = (cls_id >= 0 ? 1 : 0) + (sep_id >= 0 ? 1 : 0);
+  if (max_len < 1 || max_len < specials) throw std::invalid_argument("max_len must be at least 1 and at least the number of specials");
+  return specials;
+}
+
+void check_doc_off_host(const char *utf8, size_t nbytes, const int64_t *doc_off, size_t n_docs) {
+  bool ok = doc_off[0] == 0 && static_cast<uint64_t>(doc_off[n_docs]) == nbytes && doc_off[n_docs] >= 0;
+  for (size_t i = 1; ok && i <= n_docs; i++) {
+    ok = doc_off[i] > doc_off[i - 1] && static_cast<uint64_t>(doc_off[i]) <= nbytes && utf8[doc_off[i] - 1] == '\n';
+  }
+  if (!ok) throw std::invalid_argument("document offsets must increase from 0 to nbytes with a '\\n' in front of each");
+}
+
+// The per-document route: the rows' starts come to the host (explicit: checked and copied; lines: found by the kernels
+// of the joined route), every document is copied into the context's second text buffer (a document starts at any byte,
+// the decoder wants 4-byte alignment) and encoded through the existing ids-only / offsets path, and the assembled result
+// goes back into c->rows_out.  A correctness route: it syncs per document.
+void rows_by_document(wp_vocab *v, Context *c, const uint8_t *d_text, size_t nbytes, const long long *d_doc_off, size_t n_docs,
+                      int unit, size_t capacity, RowsResult &out) {
+  hipStream_t st = c->stream;
+  WP_HIP(hipMemsetAsync(c->d_scalars + kScalarRows, 0, 3 * sizeof(uint32_t), st));
+  size_t n_rows = n_docs;
+  std::vector<long long> starts;
+  if (d_doc_off) {
+    hipLaunchKernelGGL(rows_check_kernel, dim3(cdiv(n_docs + 1, kBlock)), dim3(kBlock), 0, st, d_text, nbytes, d_doc_off, n_docs,
+                       c->d_scalars + kScalarRowsBad);
+    WP_LAUNCH_CHECK();
+    fetch_scalars(c, 24);
+    if (c->h_scalars[kScalarRowsBad] != 0) {
+      throw std::invalid_argument("document offsets must increase from 0 to nbytes with a '\\n' in front of each");
+    }
+    out.n_rows = n_rows;
+    if (n_rows > capacity) throw std::invalid_argument("capacity_rows is smaller than the number of rows");
+    starts.resize(n_rows + 1);
+    WP_HIP(hipMemcpyAsync(starts.data(), d_doc_off, (n_rows + 1) * sizeof(long long), hipMemcpyDeviceToHost, st));
+    WP_HIP(hipStreamSynchronize(st));
+  } else {
+    const unsigned tiles = cdiv(nbytes, kLineTile);
+    const size_t tmp_words = cdiv(tiles, kScanTile) + 8;
+    c->rows_in.ensure((tiles + 1 + tmp_words) * sizeof(uint32_t));
+    uint32_t *d_cnt = static_cast<uint32_t *>(c->rows_in.p);
+    hipLaunchKernelGGL(line_count_kernel, dim3(tiles), dim3(kBlock), 0, st, d_text, nbytes, d_cnt);
+    device_exclusive_scan(d_cnt, d_cnt, tiles, d_cnt + tiles + 1, c->d_scalars + kScalarRows, st);
+    fetch_scalars(c, 24);
+    n_rows = c->h_scalars[kScalarRows];
+    out.n_rows = n_rows;
+    if (n_rows > capacity) throw std::invalid_argument("capacity_rows is smaller than the number of rows");
+    c->rows_out.ensure((n_rows + 1) * sizeof(long long));
+    hipLaunchKernelGGL(line_write_kernel, dim3(tiles), dim3(kBlock), 0, st, d_text, nbytes, static_cast<const uint32_t *>(d_cnt), n_rows,
+                       static_cast<long long *>(c->rows_out.p));
+    WP_LAUNCH_CHECK();
+    starts.resize(n_rows + 1);
+    WP_HIP(hipMemcpyAsync(starts.data(), c->rows_out.p, (n_rows + 1) * sizeof(long long), hipMemcpyDeviceToHost, st));
+    WP_HIP(hipStreamSynchronize(st));
+  }
+  uint8_t last = '\n';
+  WP_HIP(hipMemcpyAsync(&last, d_text + nbytes - 1, 1, hipMemcpyDeviceToHost, st));
+  WP_HIP(hipStreamSynchronize(st));
+  auto doc_end = [&](size_t i) {  // (a last line without a separator runs to the end of the text)
+    return static_cast<size_t>(starts[i + 1]) - ((i + 1 == n_rows && last != '\n') ? 0 : 1);
+  };
+  size_t longest = 0;
+  for (size_t i = 0; i < n_rows; i++) longest = std::max(longest, doc_end(i) - static_cast<size_t>(starts[i]));
+  c->text_buf2.ensure(longest + 64);
+  std::vector<int32_t> h_ids;
+  std::vector<uint32_t> h_offs;
+  std::vector<long long> splits(n_rows + 1, 0);
+  wp_stats last_stats;
+  std::memset(&last_stats, 0, sizeof(last_stats));
+  int32_t guard_zones = 0;
+  for (size_t i = 0; i < n_rows; i++) {
+    splits[i] = static_cast<long long>(h_ids.size());
+    const size_t a = static_cast<size_t>(starts[i]), len = doc_end(i) - a;
+    if (len == 0) continue;
+    char *dst = static_cast<char *>(c->text_buf2.p);
+    WP_HIP(hipMemsetAsync(dst + (len & ~static_cast<size_t>(15)), 0, 32, st));
+    WP_HIP(hipMemcpyAsync(dst, d_text + a, len, hipMemcpyDeviceToDevice, st));
+    size_t n = 0;
+    encode_on_device(v, c, reinterpret_cast<const uint8_t *>(dst), len, &n, last_stats, unit);
+    guard_zones = std::max(guard_zones, last_stats.guard_zones);
+    if (n == 0) continue;
+    const size_t at = h_ids.size();
+    h_ids.resize(at + n);
+    WP_HIP(hipMemcpyAsync(h_ids.data() + at, c->d_ids, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (unit >= 0) {
+      h_offs.resize(2 * (at + n));
+      WP_HIP(hipMemcpyAsync(h_offs.data() + 2 * at, c->d_offs, 2 * n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    }
+    WP_HIP(hipStreamSynchronize(st));
+  }
+  const size_t n_ids = h_ids.size();
+  splits[n_rows] = static_cast<long long>(n_ids);
+  // result block: row_splits | offsets | ids
+  const size_t split_bytes = (n_rows + 1) * sizeof(long long), offs_bytes = unit >= 0 ? n_ids * 2 * sizeof(uint32_t) : 0;
+  c->rows_out.ensure(split_bytes + offs_bytes + n_ids * sizeof(int32_t) + 16);
+  char *base = static_cast<char *>(c->rows_out.p);
+  WP_HIP(hipMemcpyAsync(base, splits.data(), split_bytes, hipMemcpyHostToDevice, st));
+  if (offs_bytes) WP_HIP(hipMemcpyAsync(base + split_bytes, h_offs.data(), offs_bytes, hipMemcpyHostToDevice, st));
+  if (n_ids) WP_HIP(hipMemcpyAsync(base + split_bytes + offs_bytes, h_ids.data(), n_ids * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  WP_HIP(hipStreamSynchronize(st));
+  c->d_ids = nullptr;  // (the arenas hold the last document only)
+  c->d_offs = nullptr;
+  out.d_row_splits = reinterpret_cast<const long long *>(base);
+  out.d_offs = (offs_bytes && n_ids) ? reinterpret_cast<const uint32_t *>(base + split_bytes) : nullptr;
+  out.d_ids = n_ids ? reinterpret_cast<const int32_t *>(base + split_bytes + offs_bytes) : nullptr;
+  out.n_ids = n_ids;
+  v->stats = last_stats;  // (of the last non-empty document; the sums of the call below)
+  v->stats.guard_zones = guard_zones;
+  v->stats.n_bytes = static_cast<int64_t>(nbytes);
+  v->stats.n_ids = static_cast<int64_t>(n_ids);
+  v->stats.n_rows = static_cast<int64_t>(n_rows);
+  v->stats.rows_route = 0;
+}
+
+// both routes: d_text as wp_linear_encode_device wants it, nbytes > 0; d_doc_off in device memory or nullptr (lines)
+void rows_on_device(wp_vocab *v, Context *c, const uint8_t *d_text, size_t nbytes, const long long *d_doc_off, size_t n_docs, int unit,
+                    size_t capacity, RowsResult &out) {
+  if (rows_per_document(v)) {
+    rows_by_document(v, c, d_text, nbytes, d_doc_off, n_docs, unit, capacity, out);
+  } else {
+    RowsCall rc;
+    rc.d_doc_off = d_doc_off;
+    rc.n_docs = n_docs;
+    rc.unit = unit;
+    rc.capacity = capacity;
+    size_t n = 0;
+    try {  // (row membership comes from the spans: without a unit they stay in code points, which need no second pass)
+      encode_on_device(v, c, d_text, nbytes, &n, v->stats, unit >= 0 ? unit : WP_OFFSETS_CODE_POINTS, &rc);
+    } catch (...) {
+      out.n_rows = rc.n_rows;
+      throw;
+    }
+    out.d_ids = n ? c->d_ids : nullptr;
+    out.d_row_splits = rc.d_row_splits;
+    out.d_offs = (n && unit >= 0) ? c->d_offs : nullptr;
+    out.n_ids = n;
+    out.n_rows = rc.n_rows;
+  }
+  v->stats.offsets_unit = unit;
+  v->stats.n_devices = 1;
+}
+
+// the padded batch of a rows result, into device buffers of n_rows * max_len and n_rows int32; waits for it
+void pack_on_device(wp_vocab *v, Context *c, const RowsResult &r, int max_len, int32_t cls_id, int32_t sep_id, int32_t pad_id,
+                    int32_t *d_input_ids, int32_t *d_lengths) {
+  v->stats.rows_truncated = 0;
+  if (r.n_rows == 0) return;
+  int lanes = 4;
+  while (lanes < kWave && lanes < max_len) lanes *= 2;
+  WP_HIP(hipMemsetAsync(c->d_scalars + kScalarRowsCut, 0, sizeof(uint32_t), c->stream));
+  hipLaunchKernelGGL(pack_rows_kernel, dim3(cdiv(r.n_rows, static_cast<size_t>(kBlock / lanes))), dim3(kBlock), 0, c->stream, r.d_ids,
+                     r.d_row_splits, r.n_rows, max_len, cls_id, sep_id, pad_id, lanes, d_input_ids, d_lengths,
+                     c->d_scalars + kScalarRowsCut);
+  WP_LAUNCH_CHECK();
+  fetch_scalars(c, 24);
+  v->stats.rows_truncated = c->h_scalars[kScalarRowsCut];
+}
+
+// explicit row starts of a host call, into device memory
+const long long *upload_doc_off(Context *c, const int64_t *doc_off, size_t n_docs) {
+  if (!doc_off) return nullptr;
+  c->rows_in.ensure((n_docs + 1) * sizeof(int64_t));
+  WP_HIP(hipMemcpyAsync(c->rows_in.p, doc_off, (n_docs + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+  return static_cast<const long long *>(c->rows_in.p);
+}
+
+void *zeroed(size_t bytes) {
+  void *p = std::calloc(std::max<size_t>(bytes, 1), 1);
+  if (!p) throw std::bad_alloc();
+  return p;
+}
+}  // namespace
+
+extern "C" {
+
+int wp_linear_encode_rows(wp_vocab *v, const char *utf8, size_t nbytes, const int64_t *doc_off, size_t n_docs, int unit,
+                          int32_t **ids, int64_t **row_splits, uint32_t **offsets, size_t *n_ids, size_t *n_rows) {
+  return guarded([&] {
+    *ids = nullptr;
+    *row_splits = nullptr;
+    if (offsets) *offsets = nullptr;
+    *n_ids = 0;
+    *n_rows = 0;
+    check_rows_call(unit, nbytes);
+    if (unit >= 0 && !offsets) throw std::invalid_argument("offsets asked for without a place to return them");
+    if (doc_off) check_doc_off_host(utf8, nbytes, doc_off, n_docs);
+    if (nbytes == 0 || (doc_off && nbytes == n_docs)) {  // no text, or empty documents only: no device needed
+      const size_t rows = doc_off ? n_docs : 0;
+      *row_splits = static_cast<int64_t *>(zeroed((rows + 1) * sizeof(int64_t)));
+      *n_rows = rows;
+      return;
+    }
+    const auto t_all = wp_clock::now();
+    Context *c = get_context(v);
+    upload_text(c, utf8, nbytes);
+    const long long *d_doc_off = upload_doc_off(c, doc_off, n_docs);
+    RowsResult r;
+    rows_on_device(v, c, static_cast<const uint8_t *>(c->text_buf.p), nbytes, d_doc_off, n_docs, unit, SIZE_MAX, r);
+    const auto t0 = wp_clock::now();
+    PinnedBlock bs((r.n_rows + 1) * sizeof(int64_t));
+    WP_HIP(hipMemcpyAsync(bs.p, r.d_row_splits, (r.n_rows + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    std::unique_ptr<PinnedBlock> bi, bo;
+    if (r.n_ids) {
+      bi.reset(new PinnedBlock(r.n_ids * sizeof(int32_t)));
+      WP_HIP(hipMemcpyAsync(bi->p, r.d_ids, r.n_ids * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+      if (unit >= 0) {
+        bo.reset(new PinnedBlock(r.n_ids * 2 * sizeof(uint32_t)));
+        WP_HIP(hipMemcpyAsync(bo->p, r.d_offs, r.n_ids * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+      }
+    }
+    WP_HIP(hipStreamSynchronize(c->stream));
+    *row_splits = static_cast<int64_t *>(bs.release());
+    if (bi) *ids = static_cast<int32_t *>(bi->release());
+    if (bo) *offsets = static_cast<uint32_t *>(bo->release());
+    *n_ids = r.n_ids;
+    *n_rows = r.n_rows;
+    v->stats.ms_d2h = ms_since(t0);
+    v->stats.ms_host_total = ms_since(t_all);
+  });
+}
+
+int wp_linear_encode_rows_device(wp_vocab *v, const void *d_utf8, size_t nbytes, const int64_t *d_doc_off, size_t n_docs,
+                                 int unit, const int32_t **d_ids, const int64_t **d_row_splits, const uint32_t **d_offsets,
+                                 size_t *n_ids, size_t *n_rows) {
+  return guarded([&] {
+    *d_ids = nullptr;
+    *d_row_splits = nullptr;
+    if (d_offsets) *d_offsets = nullptr;
+    *n_ids = 0;
+    *n_rows = 0;
+    check_rows_call(unit, nbytes);
+    if (unit >= 0 && !d_offsets) throw std::invalid_argument("offsets asked for without a place to return them");
+    if ((reinterpret_cast<uintptr_t>(d_utf8) & 3u) != 0) throw std::invalid_argument("device text must be 4-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_doc_off) & 7u) != 0) throw std::invalid_argument("device document offsets must be 8-byte aligned");
+    Context *c = get_context(v);
+    if (nbytes == 0) {  // no text: no rows (explicit rows cannot end at 0 unless there are none)
+      if (d_doc_off && n_docs != 0) throw std::invalid_argument("document offsets must increase from 0 to nbytes");
+      c->rows_out.ensure(sizeof(int64_t));
+      WP_HIP(hipMemsetAsync(c->rows_out.p, 0, sizeof(int64_t), c->stream));
+      WP_HIP(hipStreamSynchronize(c->stream));
+      *d_row_splits = static_cast<const int64_t *>(c->rows_out.p);
+      return;
+    }
+    RowsResult r;
+    rows_on_device(v, c, static_cast<const uint8_t *>(d_utf8), nbytes, reinterpret_cast<const long long *>(d_doc_off), n_docs, unit,
+                   SIZE_MAX, r);
+    *d_ids = r.d_ids;
+    *d_row_splits = reinterpret_cast<const int64_t *>(r.d_row_splits);
+    if (d_offsets) *d_offsets = r.d_offs;
+    *n_ids = r.n_ids;
+    *n_rows = r.n_rows;
+  });
+}
+
+int wp_linear_encode_padded(wp_vocab *v, const char *utf8, size_t nbytes, const int64_t *doc_off, size_t n_docs, int max_len,
+                            int32_t cls_id, int32_t sep_id, int32_t pad_id, int32_t **input_ids, int32_t **lengths,
+                            size_t *n_rows) {
+  return guarded([&] {
+    *input_ids = nullptr;
+    *lengths = nullptr;
+    *n_rows = 0;
+    check_rows_call(-1, nbytes);
+    const int specials = padded_specials(max_len, cls_id, sep_id);
+    if (doc_off) check_doc_off_host(utf8, nbytes, doc_off, n_docs);
+    if (nbytes == 0 || (doc_off && nbytes == n_docs)) {  // rows of specials and padding only: no device needed
+      const size_t rows = doc_off ? n_docs : 0;
+      int32_t *out = static_cast<int32_t *>(zeroed(rows * static_cast<size_t>(max_len) * sizeof(int32_t)));
+      int32_t *len = static_cast<int32_t *>(zeroed(rows * sizeof(int32_t)));
+      for (size_t r = 0; r < rows; r++) {
+        int32_t *row = out + r * static_cast<size_t>(max_len);
+        int col = 0;
+        if (cls_id >= 0) row[col++] = cls_id;
+        if (sep_id >= 0) row[col++] = sep_id;
+        while (col < max_len) row[col++] = pad_id;
+        len[r] = specials;
+      }
+      *input_ids = out;
+      *lengths = len;
+      *n_rows = rows;
+      return;
+    }
+    const auto t_all = wp_clock::now();
+    Context *c = get_context(v);
+    upload_text(c, utf8, nbytes);
+    const long long *d_doc_off = upload_doc_off(c, doc_off, n_docs);
+    RowsResult r;
+    rows_on_device(v, c, static_cast<const uint8_t *>(c->text_buf.p), nbytes, d_doc_off, n_docs, -1, SIZE_MAX, r);
+    const size_t cells = r.n_rows * static_cast<size_t>(max_len);
+    c->pad_buf.ensure((cells + r.n_rows) * sizeof(int32_t));
+    int32_t *d_out = static_cast<int32_t *>(c->pad_buf.p), *d_len = d_out + cells;
+    pack_on_device(v, c, r, max_len, cls_id, sep_id, pad_id, d_out, d_len);
+    PinnedBlock bi(cells * sizeof(int32_t)), bl(r.n_rows * sizeof(int32_t));
+    WP_HIP(hipMemcpyAsync(bi.p, d_out, cells * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    WP_HIP(hipMemcpyAsync(bl.p, d_len, r.n_rows * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    WP_HIP(hipStreamSynchronize(c->stream));
+    *input_ids = static_cast<int32_t *>(bi.release());
+    *lengths = static_cast<int32_t *>(bl.release());
+    *n_rows = r.n_rows;
+    v->stats.ms_host_total = ms_since(t_all);
+  });
+}
+
+int wp_linear_encode_padded_device(wp_vocab *v, const void *d_utf8, size_t nbytes, const int64_t *d_doc_off, size_t n_docs,
+                                   int max_len, int32_t cls_id, int32_t sep_id, int32_t pad_id, int32_t *d_input_ids,
+                                   int32_t *d_lengths, size_t capacity_rows, size_t *n_rows) {
+  return guarded([&] {
+    *n_rows = 0;
+    check_rows_call(-1, nbytes);
+    (void)padded_specials(max_len, cls_id, sep_id);
+    if ((reinterpret_cast<uintptr_t>(d_utf8) & 3u) != 0) throw std::invalid_argument("device text must be 4-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_doc_off) & 7u) != 0) throw std::invalid_argument("device document offsets must be 8-byte aligned");
+    if (nbytes == 0) {
+      if (d_doc_off && n_docs != 0) throw std::invalid_argument("document offsets must increase from 0 to nbytes");
+      return;
+    }
+    if (!d_input_ids || !d_lengths) throw std::invalid_argument("null output buffer");
+    Context *c = get_context(v);
+    RowsResult r;
+    try {
+      rows_on_device(v, c, static_cast<const uint8_t *>(d_utf8), nbytes, reinterpret_cast<const long long *>(d_doc_off), n_docs, -1,
+                     capacity_rows, r);
+    } catch (...) {
+      *n_rows = r.n_rows;  // (too many rows for the caller's buffers: the count it needs)
+      throw;
+    }
+    pack_on_device(v, c, r, max_len, cls_id, sep_id, pad_id, d_input_ids, d_lengths);
+    *n_rows = r.n_rows;
+  });
+}
+
 int wp_reserve(wp_vocab *v, size_t nbytes) {
   return guarded([&] {
     Context *c = get_context(v);

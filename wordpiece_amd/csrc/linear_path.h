@@ -16,6 +16,7 @@
 #include "prune.h"
 #include "trie.h"
 #include "offsets.h"
+#include "rows.h"
 #include "walk.h"
 
 namespace wp {
@@ -115,6 +116,7 @@ struct LinearPath {
   int bits;
   bool text_only;
   int offs_unit;  // offsets mode (wp_linear_encode_offsets): WP_OFFSETS_BYTES / WP_OFFSETS_CODE_POINTS; -1: ids only
+  RowsCall *rows;  // a documents call (rows.h; offsets mode is on): the row structure is built behind the spans; else nullptr
 
   // ---- derived
   hipStream_t st, st2;
@@ -171,6 +173,9 @@ struct LinearPath {
   // and the first byte of every code point (byte unit)
   uint2 *d_ospill = nullptr, *d_cspan = nullptr, *d_offs = nullptr;
   uint32_t *d_byte_of = nullptr;
+  // documents call: the starts of the lines (lines mode), the row splits, the start of every row in the offsets' unit
+  long long *d_line_starts = nullptr, *d_row_splits = nullptr;
+  uint32_t *d_row_base = nullptr;
 
   // ---- state handed from stage to stage
   SymbolCode code;
@@ -196,9 +201,9 @@ struct LinearPath {
 
   LinearPath(const wp_vocab *v_, Context *c_, wp_stats &S_, Arena &ar_, Arena &aa_, const uint8_t *text, size_t nb,
              const uint32_t *tile_prefix, size_t n_text_, size_t n_, uint32_t *cps, uint8_t *cls, int bits_, bool text_only_,
-             int offs_unit_)
+             int offs_unit_, RowsCall *rows_ = nullptr)
       : v(v_), c(c_), S(S_), ar(ar_), aa(aa_), d_text(text), nbytes(nb), d_tile_prefix(tile_prefix), n_text(n_text_), n(n_),
-        d_cps(cps), d_cls(cls), bits(bits_), text_only(text_only_), offs_unit(offs_unit_), st(c_->stream), st2(c_->stream2),
+        d_cps(cps), d_cls(cls), bits(bits_), text_only(text_only_), offs_unit(offs_unit_), rows(rows_), st(c_->stream), st2(c_->stream2),
         hv(v_->hv) {
     full = v->full_depth || hv.n_dup_eligible > 0 || v->lcp_kasai;
     need_depth = static_cast<uint32_t>(std::min<int64_t>(hv.longest + 1, 0x7fffffff));
@@ -412,7 +417,11 @@ struct LinearPath {
       d_ospill = offs ? ar.take<uint2>(n_text + 16) : nullptr;
       d_cspan = offs ? ar.take<uint2>(n_text + 16) : nullptr;
       d_offs = offs ? ar.take<uint2>(n_text + 1) : nullptr;
-      d_byte_of = offs_unit == WP_OFFSETS_BYTES ? ar.take<uint32_t>(n_text + 1) : nullptr;
+      d_byte_of = (offs_unit == WP_OFFSETS_BYTES || rows) ? ar.take<uint32_t>(n_text + 1) : nullptr;
+      // documents call: 8 (+ 8 in lines mode, + 4 with offsets) B per row
+      d_line_starts = (rows && !rows->d_doc_off) ? ar.take<long long>(rows->n_rows + 1) : nullptr;
+      d_row_splits = rows ? ar.take<long long>(rows->n_rows + 1) : nullptr;
+      d_row_base = (rows && rows->unit >= 0) ? ar.take<uint32_t>(rows->n_rows + 1) : nullptr;
       if (pass == 0) ar.commit();
     }
     ar.arm(st);
@@ -1282,20 +1291,54 @@ struct LinearPath {
     return d_ids;
   }
 
+  // documents call (rows.h): the starts of the rows, then row_splits[] (and the rows' starts in the offsets' unit) from
+  // the spans, which are still in code points here
+  void row_structure(size_t n_ids) {
+    const size_t n_rows = rows->n_rows;
+    const long long *d_starts = rows->d_doc_off;
+    if (!d_starts) {
+      hipLaunchKernelGGL(line_write_kernel, dim3(cdiv(nbytes, kLineTile)), dim3(kBlock), 0, st, d_text, nbytes,
+                         static_cast<const uint32_t *>(rows->d_line_cnt), n_rows, d_line_starts);
+      d_starts = d_line_starts;
+    }
+    if (n_ids > 0) {
+      hipLaunchKernelGGL(cp_byte_kernel, dim3(cdiv(nbytes, kDecTile)), dim3(kBlock), 0, st, d_text, nbytes, d_tile_prefix, n_text,
+                         d_byte_of);
+      hipLaunchKernelGGL(row_splits_kernel, dim3(cdiv(n_rows + 1, kBlock)), dim3(kBlock), 0, st, d_starts, n_rows,
+                         static_cast<const uint32_t *>(d_byte_of), n_text, static_cast<const uint2 *>(d_offs), n_ids, rows->unit,
+                         d_row_splits, d_row_base);
+    } else {
+      WP_HIP(hipMemsetAsync(d_row_splits, 0, (n_rows + 1) * sizeof(long long), st));
+    }
+    WP_LAUNCH_CHECK();
+    rows->d_starts = d_starts;
+    rows->d_row_splits = d_row_splits;
+  }
+
   // guard zones, bounds counters, the id count, statistics, debug views
   void finish(int32_t *d_ids, size_t *n_ids_out) {
     c->d_offs = nullptr;
     if (offs_unit >= 0 && n_text > 0) {
       fetch_scalars(c, 10);
       const size_t n_ids = c->h_scalars[9];
+      if (rows) row_structure(n_ids);
       if (offs_unit == WP_OFFSETS_BYTES && n_ids > 0) {  // code points -> bytes
-        hipLaunchKernelGGL(cp_byte_kernel, dim3(cdiv(nbytes, kDecTile)), dim3(kBlock), 0, st, d_text, nbytes, d_tile_prefix, n_text,
-                           d_byte_of);
+        if (!rows) {  // (a documents call has built byte_of[] for its row splits)
+          hipLaunchKernelGGL(cp_byte_kernel, dim3(cdiv(nbytes, kDecTile)), dim3(kBlock), 0, st, d_text, nbytes, d_tile_prefix, n_text,
+                             d_byte_of);
+        }
         hipLaunchKernelGGL(span_bytes_kernel, dim3(cdiv(n_ids, kBlock)), dim3(kBlock), 0, st, d_offs, n_ids,
                            static_cast<const uint32_t *>(d_byte_of), d_text, n_text);
         WP_LAUNCH_CHECK();
       }
+      if (rows && rows->unit >= 0 && n_ids > 0) {  // offsets relative to the id's own document: one pass over the spans
+        hipLaunchKernelGGL(rebase_kernel, dim3(cdiv(n_ids, kRebaseTile)), dim3(kBlock), 0, st, d_offs, n_ids,
+                           static_cast<const long long *>(d_row_splits), rows->n_rows, static_cast<const uint32_t *>(d_row_base));
+        WP_LAUNCH_CHECK();
+      }
       c->d_offs = reinterpret_cast<const uint32_t *>(d_offs);
+    } else if (rows) {  // (a text without one code point: every row is empty)
+      row_structure(0);
     }
     if (ar.guard) {  // debugging aid: no kernel may have written outside the buffer it was given
       static const uint32_t init[2] = {0u, 0xffffffffu};
@@ -1391,11 +1434,13 @@ struct LinearPath {
 // 4-byte aligned and readable up to the next multiple of 16.  S: statistics of this call.
 // offs_unit >= 0 (offsets mode, WP_OFFSETS_*): c->d_offs also holds the span of every id, [begin, end) as two uint32
 static void encode_on_device(const wp_vocab *v, Context *c, const uint8_t *d_text, size_t nbytes, size_t *n_ids_out,
-                             wp_stats &S, int offs_unit = -1) {
+                             wp_stats &S, int offs_unit = -1, RowsCall *rows = nullptr) {
   hipStream_t st = c->stream;
   const HostVocab &hv = v->hv;
   std::memset(&S, 0, sizeof(S));
   S.offsets_unit = -1;
+  S.n_rows = -1;
+  S.rows_route = -1;
   S.n_bytes = static_cast<int64_t>(nbytes);
   S.longest_token = hv.longest;
   c->d_ids = nullptr;
@@ -1423,11 +1468,17 @@ static void encode_on_device(const wp_vocab *v, Context *c, const uint8_t *d_tex
   Arena aa(&c->a_buf, guard);
   uint32_t *d_tile_cnt = nullptr, *d_cnt_tmp = nullptr, *d_cps = nullptr;
   uint8_t *d_cls = nullptr;
+  const unsigned line_tiles = cdiv(nbytes, kLineTile);
+  uint32_t *d_line_tmp = nullptr;
   for (int pass = 0; pass < 2; pass++) {
     d_tile_cnt = aa.take<uint32_t>(dec_tiles + 1);
     d_cnt_tmp = aa.take<uint32_t>(cdiv(dec_tiles, kScanTile) + 8);
     d_cps = v->keep_debug ? aa.take<uint32_t>(nbytes + 1) : nullptr;  // raw code points: debug copy only
     d_cls = aa.take<uint8_t>(nbytes + 32);  // (the walk reads 16 class bytes from any position on)
+    if (rows && !rows->d_doc_off) {  // lines mode of a documents call: line ends per tile and the scan's scratch
+      rows->d_line_cnt = aa.take<uint32_t>(line_tiles + 1);
+      d_line_tmp = aa.take<uint32_t>(cdiv(line_tiles, kScanTile) + 8);
+    }
     if (pass == 0) aa.commit();
   }
   aa.arm(st);
@@ -1445,8 +1496,27 @@ static void encode_on_device(const wp_vocab *v, Context *c, const uint8_t *d_tex
   // alphabet: bitmap -> per-word prefixes + sigma -> lut (dense symbol of a used code point c = lut[c] + 1)
   hipLaunchKernelGGL(alphabet_prefix_kernel, dim3(1), dim3(kAlphaThreads), 0, st, c->d_used, c->d_scan_tmp, c->d_scalars + 1);
   hipLaunchKernelGGL(alphabet_lut_kernel, dim3(kCpTableSize / kBlock), dim3(kBlock), 0, st, c->d_used, c->d_scan_tmp, c->d_lut);
+  if (rows) {  // the rows of a documents call: counted (lines) or checked (explicit) beside the decode, fetched with its scalars
+    if (rows->d_doc_off) {
+      hipLaunchKernelGGL(rows_check_kernel, dim3(cdiv(rows->n_docs + 1, kBlock)), dim3(kBlock), 0, st, d_text, nbytes, rows->d_doc_off,
+                         rows->n_docs, c->d_scalars + kScalarRowsBad);
+    } else {
+      hipLaunchKernelGGL(line_count_kernel, dim3(line_tiles), dim3(kBlock), 0, st, d_text, nbytes, rows->d_line_cnt);
+      device_exclusive_scan(rows->d_line_cnt, rows->d_line_cnt, line_tiles, d_line_tmp, c->d_scalars + kScalarRows, st);
+    }
+  }
   WP_LAUNCH_CHECK();
-  fetch_scalars(c, 22);
+  fetch_scalars(c, rows ? 24 : 22);
+  if (rows) {
+    if (rows->d_doc_off && c->h_scalars[kScalarRowsBad] != 0) {
+      throw std::invalid_argument("document offsets: " + std::to_string(c->h_scalars[kScalarRowsBad]) +
+                                  " boundaries are not increasing from 0 to nbytes with a '\\n' in front of each");
+    }
+    rows->n_rows = rows->d_doc_off ? rows->n_docs : c->h_scalars[kScalarRows];
+    if (rows->n_rows > rows->capacity) throw std::invalid_argument("capacity_rows is smaller than the number of rows");
+    S.n_rows = static_cast<int64_t>(rows->n_rows);
+    S.rows_route = 1;
+  }
   unsigned long long n_text64;
   std::memcpy(&n_text64, c->h_scalars + 14, sizeof(n_text64));
   if (n_text64 + 1 + hv.stream.size() > 2000000000ull) throw std::length_error("64bit not implemented");  // linear.cpp:104-106
@@ -1477,10 +1547,10 @@ static void encode_on_device(const wp_vocab *v, Context *c, const uint8_t *d_tex
     try {
       if (sigma <= 255) {
         LinearPath<uint8_t>(v, c, S, ab, aa, d_text, nbytes, d_tile_cnt, n_text, n, d_cps, d_cls, bits, text_only,
-                                 offs_unit).run(n_ids_out);
+                                 offs_unit, rows).run(n_ids_out);
       } else {
         LinearPath<uint32_t>(v, c, S, ab, aa, d_text, nbytes, d_tile_cnt, n_text, n, d_cps, d_cls, bits, text_only,
-                                 offs_unit).run(n_ids_out);
+                                 offs_unit, rows).run(n_ids_out);
       }
       S.list_retries = attempt;
       return;

@@ -161,6 +161,8 @@ struct HostVocab {
 
   bool space_in_token = false;  // an eligible multi-char token holds a space: a match can reach across whitespace,
                                 // so the text must not be cut into independent shards (SURVEY 8e caveat, Q13)
+  bool newline_in_token = false;  // an eligible token holds U+000A: a match can reach across the separator of a joined
+                                  // text of documents, so such a batch is encoded document by document (rows.h)
   bool low_cp = false;  // some token holds code point 0 or 1 (1 is the separator of S, linear.cpp:92,99):
                         // such vocabularies always go through the reference's S = text . 1 . vocab layout
 
@@ -175,6 +177,7 @@ struct HostVocab {
     n_dup_eligible = 0;
     low_cp = false;
     space_in_token = false;
+    newline_in_token = false;
     std::vector<uint32_t> starts(tokens.size());
     std::vector<size_t> elig;
     for (size_t i = 0; i < tokens.size(); i++) {
@@ -187,6 +190,9 @@ struct HostVocab {
       }
       if (!t.is_special && !t.is_malformed) {  // linear.cpp:179
         elig.push_back(i);
+        for (uint32_t c : t.word) {
+          if (c == 0x0au) newline_in_token = true;
+        }
         if (t.word.size() > 1) {
           for (uint32_t c : t.word) {
             if (is_spacing_char(c)) soft.push_back(c);

@@ -78,6 +78,11 @@ int wp_linear_encode_device(wp_vocab *v, const void *d_utf8, size_t nbytes,
  *     the last byte of its last one; a dropped invalid byte inside a span belongs to it, one between spans to none.
  *     nbytes > UINT32_MAX fails with WP_ERR_TOO_LARGE.
  *   WP_OFFSETS_CODE_POINTS: positions in the decoded text (for valid UTF-8: Python str indices).
+ *   With WP_OPT_NORMALIZE the meaning is unchanged: offsets refer to the text the caller passed, not to the normalised
+ *     copy.  A span the walk reports as normalised code points [b, e) runs from the start of the source code point of b
+ *     to the end of the source code point of e - 1; all code points one source code point expands into share its span.
+ *     A source code point the rule drops (a combining mark, a cleaned control) inside a span belongs to it, one behind
+ *     the last kept code point of a span or between spans to none — the rule for dropped invalid bytes.
  * Any other unit fails with WP_ERR_ARG.  Empty text gives 0 ids without a device.  Both entry points encode on the
  * handle's own device: WP_OPT_DEVICES does not shard them. */
 #define WP_OFFSETS_BYTES 0
@@ -251,7 +256,42 @@ int64_t wp_vocab_token_utf8(const wp_vocab *v, int64_t i, char *buf, size_t cap)
 #define WP_OPT_SORT_BLANKS 13 /* 1: that keys-only round 0 sorts every suffix.  Default 0: in texts where
                                  blanks (is_space) are common it leaves out the suffixes that start at one,
                                  which the walk never looks up (wp_stats.round0_sorted).  Same token ids. */
+#define WP_OPT_NORMALIZE 14   /* WP_NORM_* flags (default 0: none): every encode of the handle first normalises its
+                                 text on the device — what BERT's BasicTokenizer does in front of WordPiece, apart from
+                                 the punctuation and CJK splitting that the walk's character classes already do.  The
+                                 rule is defined per code point, in the order clean, lower, strip:
+                                   WP_NORM_CLEAN          drop U+0000, U+FFFD and every Cc / Cf code point except U+0009,
+                                                          U+000A, U+000D (kept as they are); every Zs becomes U+0020
+                                   WP_NORM_LOWER          Python's chr(c).lower() of the single code point
+                                   WP_NORM_STRIP_ACCENTS  canonical decomposition (NFD) of what is left, then drop Mn;
+                                                          Hangul syllables become their 2-3 jamo, as in BERT
+                                 WP_NORM_BERT_UNCASED is do_lower_case=True; WP_NORM_CLEAN alone is what cased BERT does.
+                                 A code point gives at most 3 code points and at most 3x its UTF-8 bytes.  Two known
+                                 differences from a whole-string implementation: U+03A3 always becomes U+03C3 (no final
+                                 sigma), and neighbouring combining marks are not reordered by class (visible only
+                                 between the 23 combining marks that are not Mn).  The vocabulary is NOT normalised: its
+                                 lines are matched as given (an uncased vocabulary is lower case already).  Ids are those
+                                 of the normalised text; offsets refer to the text the caller passed (see "token
+                                 offsets"); documents calls keep their contract.  A value with unknown bits fails with
+                                 WP_ERR_ARG.  The pre-pass sizes its buffer from a count it waits for: one more host
+                                 wait per encode, in front of the decoder's own (the pipelined calls overlap a little less
+                                 with the option on).  The tables follow the Unicode version of the generator's Python
+                                 (csrc/normalize_tables.h). */
+#define WP_NORM_CLEAN 1
+#define WP_NORM_LOWER 2
+#define WP_NORM_STRIP_ACCENTS 4
+#define WP_NORM_BERT_UNCASED 7
 int wp_set_option(wp_vocab *v, int option, int64_t value);
+
+/* ---- the normalisation stage on its own (WP_OPT_NORMALIZE's pre-pass; `flags` as there, 0 copies the valid UTF-8) ----
+ * The rule for one code point, on the host, from the tables the kernels read: the number of code points (0..3) it
+ * gives, in out[].  Surrogates, values >= 0x110000 and unknown flag bits: -1.  Needs no device. */
+int wp_normalize_cp(int flags, uint32_t cp, uint32_t out[3]);
+/* The normalised text of a device buffer (buffer contract of wp_linear_encode_device), on the handle's device: *d_out
+ * is owned by the handle and valid until its next call; invalid sequences are dropped.  nbytes == 0 gives 0 bytes. */
+int wp_normalize_device(wp_vocab *v, const void *d_utf8, size_t nbytes, int flags, const void **d_out, size_t *out_bytes);
+/* host text in, a malloc'd block out (free with wp_free; NULL when it is empty); empty text needs no device */
+int wp_normalize(wp_vocab *v, const char *utf8, size_t nbytes, int flags, char **out, size_t *out_bytes);
 
 /* ---- statistics of the last encode on this handle (for bench.py / roofline) ---- */
 typedef struct {
@@ -306,6 +346,16 @@ typedef struct {
                                  section "documents"); -1: the last call was no documents call                          */
 } wp_stats;
 int wp_get_stats(const wp_vocab *v, wp_stats *out);
+/* WP_OPT_NORMALIZE's part of the statistics of the last encode, in a struct of its own: wp_stats keeps its size and its
+ * last field for callers built against it */
+typedef struct {
+  int32_t normalize;          /* WP_OPT_NORMALIZE flags the last encode ran with (0: none)                              */
+  int64_t norm_bytes;         /* bytes of the normalised text the encode ran on (0 without the option); wp_stats.n_bytes
+                                 stays the caller's byte count                                                          */
+  double ms_normalize;        /* WP_OPT_STAGE_TIMING: device time of the normalisation pre-pass (part of
+                                 wp_stats.ms_total)                                                                     */
+} wp_norm_stats;
+int wp_get_norm_stats(const wp_vocab *v, wp_norm_stats *out);
 
 /* ---- debug fetch (WP_OPT_KEEP_DEBUG): copies device intermediates to host ----
  * which: 0 S (dense symbols as int32, n), 1 SA (n), 2 rank (n; the full inverse SA is kept only with this option —

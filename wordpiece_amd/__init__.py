@@ -25,6 +25,8 @@ WP_OPT_COVER_ANCHORS, WP_OPT_ARENA_GUARD, WP_OPT_DEVICES, WP_OPT_VOCAB_IN_S = 7,
 WP_OPT_SPARSE_EMIT = 11
 WP_OPT_INDEXED_ROUND0 = 12
 WP_OPT_SORT_BLANKS = 13
+WP_OPT_NORMALIZE = 14
+WP_NORM_CLEAN, WP_NORM_LOWER, WP_NORM_STRIP_ACCENTS, WP_NORM_BERT_UNCASED = 1, 2, 4, 7
 WP_OFFSETS_BYTES, WP_OFFSETS_CODE_POINTS = 0, 1
 _OFFSET_UNITS = {"byte": WP_OFFSETS_BYTES, "char": WP_OFFSETS_CODE_POINTS}
 
@@ -38,6 +40,7 @@ ABI_SYMBOLS = [
     "wp_fast_encode_external", "wp_vocab_token_utf8", "wp_trim", "wp_linear_encode_batch", "wp_linear_encode_stream",
     "wp_linear_encode_offsets", "wp_linear_encode_offsets_device",
     "wp_linear_encode_rows", "wp_linear_encode_rows_device", "wp_linear_encode_padded", "wp_linear_encode_padded_device",
+    "wp_normalize_cp", "wp_normalize_device", "wp_normalize", "wp_get_norm_stats",
 ]
 
 
@@ -68,6 +71,11 @@ class Stats(C.Structure):
         d = {k: getattr(self, k) for k, _ in self._fields_ if k != "active_per_round"}
         d["active_per_round"] = [int(x) for x in self.active_per_round[:max(self.rounds, 0)]]
         return d
+
+
+class NormStats(C.Structure):
+    """wp_norm_stats: WP_OPT_NORMALIZE's part of the statistics (Vocab.stats() merges it into its dict)."""
+    _fields_ = [("normalize", C.c_int32), ("norm_bytes", C.c_int64), ("ms_normalize", C.c_double)]
 
 
 _TEXT_SOURCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t))
@@ -128,8 +136,12 @@ def lib():
         L.wp_vocab_token_utf8.restype = C.c_int64
         L.wp_linear_encode_file.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(i32p), C.POINTER(C.c_size_t)]
         L.wp_linear_encode_external.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t]
+        L.wp_normalize_cp.argtypes = [C.c_int, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.wp_normalize_device.argtypes = [vp, vp, C.c_size_t, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t)]
+        L.wp_normalize.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t)]
         L.wp_set_option.argtypes = [vp, C.c_int, C.c_int64]
         L.wp_get_stats.argtypes = [vp, C.POINTER(Stats)]
+        L.wp_get_norm_stats.argtypes = [vp, C.POINTER(NormStats)]
         L.wp_linear_debug_fetch.argtypes = [vp, C.c_int, i32p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.wp_free.argtypes = [vp]
         L.wp_free.restype = None
@@ -151,7 +163,7 @@ def _bytes(x):
 class Vocab:
     """Opaque vocabulary handle (wp_vocab): parsed like utils.cpp:81-137, cached on the device."""
 
-    def __init__(self, lines=None, file=None, device=None):
+    def __init__(self, lines=None, file=None, device=None, normalize=0):
         self._h = C.c_void_p()
         if file is not None:
             _check(lib().wp_vocab_from_file(_bytes(file), C.byref(self._h)))
@@ -164,6 +176,9 @@ class Vocab:
                                                 C.byref(self._h)))
         if device is not None:
             self.set_option(WP_OPT_DEVICE, device)
+        if normalize:  # WP_NORM_* flags: every encode of this handle normalises its text on the device first
+            self.set_option(WP_OPT_NORMALIZE, normalize)
+        self._normalize = int(normalize)
 
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:
@@ -185,11 +200,52 @@ class Vocab:
 
     def set_option(self, opt, value):
         _check(lib().wp_set_option(self._h, opt, int(value)))
+        if opt == WP_OPT_NORMALIZE:
+            self._normalize = int(value)
+
+    def normalize(self, text, flags=None):
+        """The normalisation pre-pass alone (wp_normalize): host UTF-8 bytes/str -> the normalised UTF-8 as bytes.
+        flags: WP_NORM_* (default: the handle's WP_OPT_NORMALIZE)."""
+        b = _bytes(text)
+        out = C.c_void_p()
+        n = C.c_size_t()
+        _check(lib().wp_normalize(self._h, b, len(b), self._normalize if flags is None else int(flags), C.byref(out), C.byref(n)))
+        if n.value == 0:
+            return b""
+        try:
+            return C.string_at(out, n.value)
+        finally:
+            lib().wp_free(out)
+
+    def normalize_tensor(self, text, flags=None, copy=True):
+        """The pre-pass alone on a uint8 text tensor on this handle's GPU (wp_normalize_device) -> a uint8 tensor there.
+        copy=False: a view of the library's buffer, valid until the next call on this handle."""
+        import torch
+        if text.dtype != torch.uint8 or not text.is_cuda or not text.is_contiguous():
+            raise WordPieceError("normalize_tensor needs a contiguous uint8 CUDA/HIP tensor")
+        nbytes = text.numel()
+        if text.data_ptr() % 4 != 0 or nbytes % 4 != 0:  # (as encode_tensor: the decoder reads whole aligned words)
+            padded = torch.zeros((nbytes + 19) // 16 * 16, dtype=torch.uint8, device=text.device)
+            padded[:nbytes] = text
+            text = padded
+        torch.cuda.current_stream(text.device).synchronize()  # the library runs on its own HIP streams
+        d_out = C.c_void_p()
+        n = C.c_size_t()
+        _check(lib().wp_normalize_device(self._h, C.c_void_p(text.data_ptr()), nbytes,
+                                         self._normalize if flags is None else int(flags), C.byref(d_out), C.byref(n)))
+        if n.value == 0:
+            return torch.zeros(0, dtype=torch.uint8, device=text.device)
+        view = torch.as_tensor(DeviceIds(d_out.value, n.value, typestr="|u1"), device=text.device)
+        return view.clone() if copy else view
 
     def stats(self):
         s = Stats()
         _check(lib().wp_get_stats(self._h, C.byref(s)))
-        return s.as_dict()
+        d = s.as_dict()
+        ns = NormStats()
+        _check(lib().wp_get_norm_stats(self._h, C.byref(ns)))
+        d.update({k: getattr(ns, k) for k, _ in ns._fields_})
+        return d
 
     def encode(self, text):
         """Host UTF-8 bytes/str -> numpy int32 ids (wp_linear_encode)."""
@@ -471,6 +527,14 @@ def _adopt_block(ptr, shape):
     out = np.ctypeslib.as_array(ptr, shape=shape)
     weakref.finalize(out.base if out.base is not None else out, lib().wp_free, ptr)  # the bottom of the view chain
     return out
+
+
+def normalize_cp(flags, cp):
+    """The normalisation rule for one code point, from the tables the kernels read (wp_normalize_cp; no GPU needed):
+    the list of 0..3 code points it gives, or None for a surrogate, a value >= 0x110000 or unknown flag bits."""
+    out = (C.c_uint32 * 3)()
+    n = lib().wp_normalize_cp(int(flags), int(cp), out)
+    return None if n < 0 else [int(out[i]) for i in range(n)]
 
 
 def join_docs(docs):

@@ -143,6 +143,7 @@ constexpr int kScalarCand = 24;  // d_scalars word: entries of the keys-only rou
 constexpr int kScalarKept = 25;  // d_scalars word: suffixes the keys-only round 0 kept (not blank-start; radix_sort.h, RadixDrop)
 // documents calls (rows.h): lines of the text / boundaries of explicit rows that fail the check / rows a padded call cut
 constexpr int kScalarRows = 21, kScalarRowsBad = 22, kScalarRowsCut = 23;
+constexpr int kScalarSrcRows = 26;  // lines of the caller's text in a documents call on normalised text (normalize.h)
 
 // A documents call (wp_linear_encode_rows / _padded) as encode_on_device sees it: how the rows are given, and where it
 // left the row structure (device pointers into the arenas, valid like c->d_ids until the handle's next call).
@@ -180,6 +181,11 @@ struct Context {
   DeviceBuffer text_buf2, ids_stage[2];
   // documents calls: explicit row starts of a host call, results of the per-document route, padded batch of a host call
   DeviceBuffer rows_in, rows_out, pad_buf;
+  // WP_OPT_NORMALIZE (normalize.h): the tables (uploaded with the first normalising call), the normalised text, the
+  // tile counts of the pre-pass, and the source of every normalised code point (offsets mode)
+  uint16_t *d_norm_index = nullptr;
+  uint32_t *d_norm_pages = nullptr, *d_norm_pool = nullptr;
+  DeviceBuffer norm_buf, norm_aux, norm_map;
   hipStream_t up_stream = nullptr, down_stream = nullptr;
   hipEvent_t pipe_ev[4] = {};  // ids staged [2], ids downloaded [2]
   uint32_t *d_used = nullptr, *d_lut = nullptr, *d_scan_tmp = nullptr;  // bitmap of the code points in use (kCpWords), lut (kCpTableSize), per-word prefixes (kCpWords)
@@ -239,6 +245,13 @@ struct DeviceGuard {
 
 using namespace wp;
 
+// the statistics of an encode as the device path fills them: wp_stats and, behind it, what wp_get_norm_stats hands out
+struct EncodeStats : wp_stats {
+  int32_t normalize;
+  int64_t norm_bytes;
+  double ms_normalize;
+};
+
 struct wp_vocab {
   HostVocab hv;
   std::unique_ptr<Context> ctx;                  // the handle's own device context
@@ -250,8 +263,9 @@ struct wp_vocab {
   bool vocab_in_s = false;  // WP_OPT_VOCAB_IN_S: always the reference's S = text . 1 . vocab layout
   bool indexed_round0 = false;  // WP_OPT_INDEXED_ROUND0: the (key, index) round-0 sort also where keys alone would do
   bool sort_blanks = false;     // WP_OPT_SORT_BLANKS: the keys-only round 0 sorts the blank-start suffixes too
+  int normalize = 0;  // WP_OPT_NORMALIZE: WP_NORM_* flags of the pre-pass in front of every encode (normalize.h); 0: none
   int n_devices = 1;  // WP_OPT_DEVICES: GPUs wp_linear_encode shards a host buffer over (-1: all visible)
-  wp_stats stats{};
+  EncodeStats stats{};
   ~wp_vocab();
 };
 
@@ -285,7 +299,9 @@ static void destroy_context(Context *c) {
   free_vocab_tables(c);
   for (void **p : {reinterpret_cast<void **>(&c->d_used), reinterpret_cast<void **>(&c->d_lut),
                    reinterpret_cast<void **>(&c->d_scan_tmp), reinterpret_cast<void **>(&c->d_scalars),
-                   reinterpret_cast<void **>(&c->d_code), reinterpret_cast<void **>(&c->d_symhist)}) {
+                   reinterpret_cast<void **>(&c->d_code), reinterpret_cast<void **>(&c->d_symhist),
+                   reinterpret_cast<void **>(&c->d_norm_index), reinterpret_cast<void **>(&c->d_norm_pages),
+                   reinterpret_cast<void **>(&c->d_norm_pool)}) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
   }
@@ -303,6 +319,9 @@ static void destroy_context(Context *c) {
   c->rows_in.release();
   c->rows_out.release();
   c->pad_buf.release();
+  c->norm_buf.release();
+  c->norm_aux.release();
+  c->norm_map.release();
   for (auto &e : c->pipe_ev) {
     if (e) (void)hipEventDestroy(e);
     e = nullptr;
@@ -350,6 +369,9 @@ static std::vector<std::unique_ptr<Context>> &context_pool() {
 }
 
 static void release_arenas(Context *c) {
+  c->norm_buf.release();
+  c->norm_aux.release();
+  c->norm_map.release();
   c->rows_in.release();
   c->rows_out.release();
   c->pad_buf.release();
@@ -374,7 +396,7 @@ static void park_context(std::unique_ptr<Context> c) {
       hipStreamSynchronize(c->stream3) == hipSuccess) {
     free_vocab_tables(c.get());
     if (c->text_buf.cap + c->text_buf2.cap + c->ids_stage[0].cap + c->ids_stage[1].cap + c->a_buf.cap + c->b_buf.cap + c->fmt_buf.cap +
-            c->rows_in.cap + c->rows_out.cap + c->pad_buf.cap >
+            c->rows_in.cap + c->rows_out.cap + c->pad_buf.cap + c->norm_buf.cap + c->norm_aux.cap + c->norm_map.cap >
         kPoolArenaBytes) {
       release_arenas(c.get());
     }

@@ -150,14 +150,52 @@ int wp_set_option(wp_vocab *v, int option, int64_t value) {
     case WP_OPT_SPARSE_EMIT: v->sparse_emit = value != 0; return WP_OK;
     case WP_OPT_INDEXED_ROUND0: v->indexed_round0 = value != 0; return WP_OK;
     case WP_OPT_SORT_BLANKS: v->sort_blanks = value != 0; return WP_OK;
+    case WP_OPT_NORMALIZE:
+      if (value < 0 || (value & ~static_cast<int64_t>(kNormKnownFlags)) != 0) {
+        g_last_error = "WP_OPT_NORMALIZE: unknown flag bits (WP_NORM_CLEAN | WP_NORM_LOWER | WP_NORM_STRIP_ACCENTS)";
+        return WP_ERR_ARG;
+      }
+      v->normalize = static_cast<int>(value);
+      return WP_OK;
     case WP_OPT_DEVICES: v->n_devices = value < 0 ? -1 : static_cast<int>(std::max<int64_t>(value, 1)); return WP_OK;
   }
   g_last_error = "unknown option";
   return WP_ERR_ARG;
 }
 
+int wp_normalize_cp(int flags, uint32_t cp, uint32_t out[3]) {
+  if (flags < 0 || (flags & ~kNormKnownFlags) != 0 || cp >= 0x110000u || (cp >= 0xd800u && cp < 0xe000u)) return -1;
+  uint32_t o[3] = {0, 0, 0};
+  const int n = norm_cp(host_norm_tables(), flags, cp, o);
+  for (int i = 0; i < n; i++) out[i] = o[i];
+  return n;
+}
+
+int wp_normalize_device(wp_vocab *v, const void *d_utf8, size_t nbytes, int flags, const void **d_out, size_t *out_bytes) {
+  return guarded([&] {
+    *d_out = nullptr;
+    *out_bytes = 0;
+    if (flags < 0 || (flags & ~kNormKnownFlags) != 0) throw std::invalid_argument("normalize: unknown flag bits");
+    if (nbytes == 0) return;
+    if ((reinterpret_cast<uintptr_t>(d_utf8) & 3u) != 0) throw std::invalid_argument("device text must be 4-byte aligned");
+    Context *c = get_context(v);
+    NormResult r;
+    normalize_on_device(c, static_cast<const uint8_t *>(d_utf8), nbytes, flags, false, false, r);
+    WP_HIP(hipStreamSynchronize(c->stream));
+    *d_out = r.nbytes ? r.text : nullptr;
+    *out_bytes = r.nbytes;
+  });
+}
+
 int wp_get_stats(const wp_vocab *v, wp_stats *out) {
   *out = v->stats;
+  return WP_OK;
+}
+
+int wp_get_norm_stats(const wp_vocab *v, wp_norm_stats *out) {
+  out->normalize = v->stats.normalize;
+  out->norm_bytes = v->stats.norm_bytes;
+  out->ms_normalize = v->stats.ms_normalize;
   return WP_OK;
 }
 
@@ -268,7 +306,8 @@ bool ascii_space(uint8_t b) { return (b >= 0x09 && b <= 0x0d) || b == 0x20; }
 // balanced by code points rather than bytes: the cost of a shard follows its symbol count, and a
 // mixed-script corpus has 1-3 bytes per code point depending on where one looks.  Code points are
 // estimated from every 64th 4 KB page (lead bytes = bytes that are not 10xxxxxx).
-std::vector<size_t> shard_cuts(const char *utf8, size_t nbytes, int parts) {
+// kept_only: cut only at the blanks WP_NORM_CLEAN keeps (it drops U+000B and U+000C, which then join their neighbours).
+std::vector<size_t> shard_cuts(const char *utf8, size_t nbytes, int parts, bool kept_only = false) {
   std::vector<size_t> cuts(static_cast<size_t>(parts) + 1, nbytes);
   cuts[0] = 0;
   if (parts <= 1) return cuts;
@@ -294,7 +333,7 @@ std::vector<size_t> shard_cuts(const char *utf8, size_t nbytes, int parts) {
     const double span = cum[i + 1] - cum[i];
     size_t pos = i * blk + (span > 0 ? static_cast<size_t>((want - cum[i]) / span * static_cast<double>(blk)) : 0);
     pos = std::max(pos, cuts[static_cast<size_t>(r) - 1]);
-    while (pos < nbytes && !ascii_space(b[pos])) pos++;
+    while (pos < nbytes && (!ascii_space(b[pos]) || (kept_only && (b[pos] == 0x0b || b[pos] == 0x0c)))) pos++;
     cuts[static_cast<size_t>(r)] = std::min(pos, nbytes);
   }
   return cuts;
@@ -311,7 +350,7 @@ void encode_multi(wp_vocab *v, const char *utf8, size_t nbytes, const std::vecto
                                                         : devices_in;
   const int G = static_cast<int>(devices.size());
   const auto t_all = wp_clock::now();
-  const std::vector<size_t> cuts = shard_cuts(utf8, nbytes, G);
+  const std::vector<size_t> cuts = shard_cuts(utf8, nbytes, G, (v->normalize & WP_NORM_CLEAN) != 0);
   if (v->multi.size() < static_cast<size_t>(G)) v->multi.resize(static_cast<size_t>(G));
   for (int g = 0; g < G; g++) {  // (contexts are made on the calling thread: a failure here is a plain exception)
     if (cuts[static_cast<size_t>(g)] == cuts[static_cast<size_t>(g) + 1]) continue;  // an empty shard needs none
@@ -320,7 +359,7 @@ void encode_multi(wp_vocab *v, const char *utf8, size_t nbytes, const std::vecto
     if (!v->multi[static_cast<size_t>(g)]) v->multi[static_cast<size_t>(g)] = make_context(v, devices[static_cast<size_t>(g)]);
   }
   std::vector<size_t> counts(static_cast<size_t>(G), 0);
-  std::vector<wp_stats> stats(static_cast<size_t>(G));
+  std::vector<EncodeStats> stats(static_cast<size_t>(G));
   std::vector<std::string> errors(static_cast<size_t>(G));
   std::vector<int> codes(static_cast<size_t>(G), WP_OK);
   auto work = [&](int g) {
@@ -328,7 +367,7 @@ void encode_multi(wp_vocab *v, const char *utf8, size_t nbytes, const std::vecto
     const size_t lo = cuts[static_cast<size_t>(g)], hi = cuts[static_cast<size_t>(g) + 1];
     codes[static_cast<size_t>(g)] = guarded([&] {
       WP_HIP(hipSetDevice(c->device));
-      std::memset(&stats[static_cast<size_t>(g)], 0, sizeof(wp_stats));
+      std::memset(&stats[static_cast<size_t>(g)], 0, sizeof(EncodeStats));
       if (hi == lo) return;
       upload_text(c, utf8 + lo, hi - lo);
       encode_on_device(v, c, static_cast<const uint8_t *>(c->text_buf.p), hi - lo, &counts[static_cast<size_t>(g)],
@@ -357,7 +396,7 @@ void encode_multi(wp_vocab *v, const char *utf8, size_t nbytes, const std::vecto
     int own = -1;  // the first non-empty shard runs on the calling thread
     for (int g = 0; g < G; g++) {
       if (cuts[static_cast<size_t>(g)] == cuts[static_cast<size_t>(g) + 1]) {
-        std::memset(&stats[static_cast<size_t>(g)], 0, sizeof(wp_stats));
+        std::memset(&stats[static_cast<size_t>(g)], 0, sizeof(EncodeStats));
         continue;
       }
       if (own < 0) {
@@ -406,10 +445,10 @@ void encode_multi(wp_vocab *v, const char *utf8, size_t nbytes, const std::vecto
     *n_ids = total;
   }
   // statistics of the call: sums over the shards, the slowest shard's device times
-  wp_stats &S = v->stats;
+  EncodeStats &S = v->stats;
   S = stats[0];
   for (int g = 1; g < G; g++) {
-    const wp_stats &T = stats[static_cast<size_t>(g)];
+    const EncodeStats &T = stats[static_cast<size_t>(g)];
     S.n_bytes += T.n_bytes;
     S.n_text += T.n_text;
     S.n_total += T.n_total;
@@ -422,6 +461,8 @@ void encode_multi(wp_vocab *v, const char *utf8, size_t nbytes, const std::vecto
     S.radix_digit_bytes += T.radix_digit_bytes;
     S.radix_pass_bytes += T.radix_pass_bytes;
     S.round0_sorted += T.round0_sorted;
+    S.norm_bytes += T.norm_bytes;
+    S.ms_normalize = std::max(S.ms_normalize, T.ms_normalize);
     S.ms_total = std::max(S.ms_total, T.ms_total);
     S.ms_decode = std::max(S.ms_decode, T.ms_decode);
     S.ms_sa = std::max(S.ms_sa, T.ms_sa);
@@ -429,6 +470,7 @@ void encode_multi(wp_vocab *v, const char *utf8, size_t nbytes, const std::vecto
     S.ms_scan = std::max(S.ms_scan, T.ms_scan);
     S.ms_walk = std::max(S.ms_walk, T.ms_walk);
   }
+  S.normalize = v->normalize;  // (shard 0 may have been empty)
   S.n_devices = G;
   S.ms_d2h = ms_since(t_d2h);
   S.ms_host_total = ms_since(t_all);
@@ -534,6 +576,26 @@ int wp_linear_encode_offsets(wp_vocab *v, const char *utf8, size_t nbytes, int u
     v->stats.n_devices = 1;
     v->stats.ms_d2h = ms_since(t0);
     v->stats.ms_host_total = ms_since(t_all);
+  });
+}
+
+int wp_normalize(wp_vocab *v, const char *utf8, size_t nbytes, int flags, char **out, size_t *out_bytes) {
+  return guarded([&] {
+    *out = nullptr;
+    *out_bytes = 0;
+    if (flags < 0 || (flags & ~kNormKnownFlags) != 0) throw std::invalid_argument("normalize: unknown flag bits");
+    if (nbytes == 0) return;  // (no device needed)
+    Context *c = get_context(v);
+    upload_text(c, utf8, nbytes);
+    NormResult r;
+    normalize_on_device(c, static_cast<const uint8_t *>(c->text_buf.p), nbytes, flags, false, false, r);
+    if (r.nbytes) {
+      PinnedBlock b(r.nbytes);
+      WP_HIP(hipMemcpyAsync(b.p, r.text, r.nbytes, hipMemcpyDeviceToHost, c->stream));
+      WP_HIP(hipStreamSynchronize(c->stream));
+      *out = static_cast<char *>(b.release());
+      *out_bytes = r.nbytes;
+    }
   });
 }
 
@@ -649,9 +711,10 @@ void rows_by_document(wp_vocab *v, Context *c, const uint8_t *d_text, size_t nby
   std::vector<int32_t> h_ids;
   std::vector<uint32_t> h_offs;
   std::vector<long long> splits(n_rows + 1, 0);
-  wp_stats last_stats;
+  EncodeStats last_stats;
   std::memset(&last_stats, 0, sizeof(last_stats));
   int32_t guard_zones = 0;
+  int64_t norm_bytes = 0;  // (WP_OPT_NORMALIZE: every document is normalised by its own encode)
   for (size_t i = 0; i < n_rows; i++) {
     splits[i] = static_cast<long long>(h_ids.size());
     const size_t a = static_cast<size_t>(starts[i]), len = doc_end(i) - a;
@@ -662,6 +725,7 @@ void rows_by_document(wp_vocab *v, Context *c, const uint8_t *d_text, size_t nby
     size_t n = 0;
     encode_on_device(v, c, reinterpret_cast<const uint8_t *>(dst), len, &n, last_stats, unit);
     guard_zones = std::max(guard_zones, last_stats.guard_zones);
+    norm_bytes += last_stats.norm_bytes;
     if (n == 0) continue;
     const size_t at = h_ids.size();
     h_ids.resize(at + n);
@@ -690,6 +754,8 @@ void rows_by_document(wp_vocab *v, Context *c, const uint8_t *d_text, size_t nby
   out.n_ids = n_ids;
   v->stats = last_stats;  // (of the last non-empty document; the sums of the call below)
   v->stats.guard_zones = guard_zones;
+  v->stats.normalize = v->normalize;
+  v->stats.norm_bytes = norm_bytes;
   v->stats.n_bytes = static_cast<int64_t>(nbytes);
   v->stats.n_ids = static_cast<int64_t>(n_ids);
   v->stats.n_rows = static_cast<int64_t>(n_rows);
@@ -965,7 +1031,7 @@ void encode_pipeline(wp_vocab *v, Next &&next, Deliver &&deliver) {
       return e.what()[0] ? e.what() : "upload failed";
     }
   };
-  wp_stats total{};
+  EncodeStats total{};
   const char *cur_text = nullptr, *next_text = nullptr;
   size_t cur_len = 0, next_len = 0;
   bool have = next(0, &cur_text, &cur_len);
@@ -992,7 +1058,7 @@ void encode_pipeline(wp_vocab *v, Next &&next, Deliver &&deliver) {
       }
     } wait_up{next_up};
     size_t n = 0;
-    wp_stats st{};
+    EncodeStats st{};
     if (cur_len) encode_on_device(v, c, static_cast<const uint8_t *>(tb[slot]->p), cur_len, &n, st);
     std::unique_ptr<PinnedBlock> blk(new PinnedBlock(std::max<size_t>(n, 1) * sizeof(int32_t)));
     if (n) {
@@ -1018,6 +1084,9 @@ void encode_pipeline(wp_vocab *v, Next &&next, Deliver &&deliver) {
     total.n_total += st.n_total;
     total.n_ids += st.n_ids;
     total.ms_total += st.ms_total;
+    total.normalize = std::max(total.normalize, st.normalize);
+    total.norm_bytes += st.norm_bytes;
+    total.ms_normalize += st.ms_normalize;
     total.rounds = std::max(total.rounds, st.rounds);
     if (next_up.valid()) {
       const std::string err = next_up.get();

@@ -3,12 +3,13 @@
 #pragma once
 #include "context.h"
 #include "fast.h"
+#include "normalize.h"
 #include "walk.h"
 
 namespace wp {
 
 static void encode_fast_on_device(const wp_vocab *v, Context *c, const uint8_t *d_text, size_t nbytes, size_t *n_ids_out,
-                                  wp_stats &S) {
+                                  EncodeStats &S) {
   hipStream_t st = c->stream;
   const HostVocab &hv = v->hv;
   std::memset(&S, 0, sizeof(S));
@@ -19,6 +20,16 @@ static void encode_fast_on_device(const wp_vocab *v, Context *c, const uint8_t *
   c->dbg = {};
   *n_ids_out = 0;
   if (nbytes == 0) return;  // fast.cpp:154-156
+  NormResult norm;
+  if (v->normalize != 0) {  // WP_OPT_NORMALIZE: the words are those of the normalised text
+    normalize_on_device(c, d_text, nbytes, v->normalize, false, v->stage_timing, norm);
+    S.normalize = v->normalize;
+    S.norm_bytes = static_cast<int64_t>(norm.nbytes);
+    S.ms_normalize = norm.ms;
+    if (norm.nbytes == 0) return;
+    d_text = norm.text;
+    nbytes = norm.nbytes;
+  }
   Arena aa(&c->a_buf, v->arena_guard || EnvOptions::get().arena_guard);
   if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[0], st));
   const unsigned dec_tiles = cdiv(nbytes, kDecTile);
@@ -183,7 +194,7 @@ static void encode_fast_on_device(const wp_vocab *v, Context *c, const uint8_t *
     };
     S.ms_decode = span(0, 2);
     S.ms_walk = span(2, 3);
-    S.ms_total = span(0, 3);
+    S.ms_total = span(0, 3) + S.ms_normalize;
   }
   c->d_ids = d_ids;
   *n_ids_out = n_ids;

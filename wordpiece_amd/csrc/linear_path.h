@@ -16,6 +16,7 @@
 #include "prune.h"
 #include "trie.h"
 #include "offsets.h"
+#include "normalize.h"
 #include "rows.h"
 #include "walk.h"
 
@@ -105,7 +106,7 @@ struct LinearPath {
   // ---- what the decode phase hands over
   const wp_vocab *v;
   Context *c;
-  wp_stats &S;
+  EncodeStats &S;
   Arena &ar, &aa;
   const uint8_t *d_text;
   size_t nbytes;
@@ -117,6 +118,7 @@ struct LinearPath {
   bool text_only;
   int offs_unit;  // offsets mode (wp_linear_encode_offsets): WP_OFFSETS_BYTES / WP_OFFSETS_CODE_POINTS; -1: ids only
   RowsCall *rows;  // a documents call (rows.h; offsets mode is on): the row structure is built behind the spans; else nullptr
+  const NormMap *nmap;  // offsets mode on normalised text (normalize.h): d_text is the normalised copy, spans go back through this
 
   // ---- derived
   hipStream_t st, st2;
@@ -199,11 +201,11 @@ struct LinearPath {
   CandRuns cand_runs{};              // keys_only: the sorted list as the needed-group kernels read it
   size_t n_cand = 0;
 
-  LinearPath(const wp_vocab *v_, Context *c_, wp_stats &S_, Arena &ar_, Arena &aa_, const uint8_t *text, size_t nb,
+  LinearPath(const wp_vocab *v_, Context *c_, EncodeStats &S_, Arena &ar_, Arena &aa_, const uint8_t *text, size_t nb,
              const uint32_t *tile_prefix, size_t n_text_, size_t n_, uint32_t *cps, uint8_t *cls, int bits_, bool text_only_,
-             int offs_unit_, RowsCall *rows_ = nullptr)
+             int offs_unit_, RowsCall *rows_ = nullptr, const NormMap *nmap_ = nullptr)
       : v(v_), c(c_), S(S_), ar(ar_), aa(aa_), d_text(text), nbytes(nb), d_tile_prefix(tile_prefix), n_text(n_text_), n(n_),
-        d_cps(cps), d_cls(cls), bits(bits_), text_only(text_only_), offs_unit(offs_unit_), rows(rows_), st(c_->stream), st2(c_->stream2),
+        d_cps(cps), d_cls(cls), bits(bits_), text_only(text_only_), offs_unit(offs_unit_), rows(rows_), nmap(nmap_), st(c_->stream), st2(c_->stream2),
         hv(v_->hv) {
     full = v->full_depth || hv.n_dup_eligible > 0 || v->lcp_kasai;
     need_depth = static_cast<uint32_t>(std::min<int64_t>(hv.longest + 1, 0x7fffffff));
@@ -417,9 +419,11 @@ struct LinearPath {
       d_ospill = offs ? ar.take<uint2>(n_text + 16) : nullptr;
       d_cspan = offs ? ar.take<uint2>(n_text + 16) : nullptr;
       d_offs = offs ? ar.take<uint2>(n_text + 1) : nullptr;
-      d_byte_of = (offs_unit == WP_OFFSETS_BYTES || rows) ? ar.take<uint32_t>(n_text + 1) : nullptr;
+      // (normalised text: the spans go back to the source through nmap, byte_of[] is only needed for the rows)
+      d_byte_of = ((offs_unit == WP_OFFSETS_BYTES && !nmap) || rows) ? ar.take<uint32_t>(n_text + 1) : nullptr;
       // documents call: 8 (+ 8 in lines mode, + 4 with offsets) B per row
-      d_line_starts = (rows && !rows->d_doc_off) ? ar.take<long long>(rows->n_rows + 1) : nullptr;
+      // (normalised text: explicit rows are carried from source bytes to normalised bytes into the same array)
+      d_line_starts = (rows && (!rows->d_doc_off || nmap)) ? ar.take<long long>(rows->n_rows + 1) : nullptr;
       d_row_splits = rows ? ar.take<long long>(rows->n_rows + 1) : nullptr;
       d_row_base = (rows && rows->unit >= 0) ? ar.take<uint32_t>(rows->n_rows + 1) : nullptr;
       if (pass == 0) ar.commit();
@@ -1297,6 +1301,9 @@ struct LinearPath {
     const size_t n_rows = rows->n_rows;
     const long long *d_starts = rows->d_doc_off;
     if (!d_starts) {
+      // (normalised text: a last line of dropped code points only is a row of the source that the normalised text has
+      // no line for — it starts, empty, at the end)
+      if (nmap) hipLaunchKernelGGL(norm_fill_starts_kernel, dim3(cdiv(n_rows + 1, kBlock)), dim3(kBlock), 0, st, d_line_starts, n_rows + 1, static_cast<long long>(nbytes));
       hipLaunchKernelGGL(line_write_kernel, dim3(cdiv(nbytes, kLineTile)), dim3(kBlock), 0, st, d_text, nbytes,
                          static_cast<const uint32_t *>(rows->d_line_cnt), n_rows, d_line_starts);
       d_starts = d_line_starts;
@@ -1304,9 +1311,18 @@ struct LinearPath {
     if (n_ids > 0) {
       hipLaunchKernelGGL(cp_byte_kernel, dim3(cdiv(nbytes, kDecTile)), dim3(kBlock), 0, st, d_text, nbytes, d_tile_prefix, n_text,
                          d_byte_of);
+      if (nmap && rows->d_doc_off) {  // explicit rows are bytes of the source
+        hipLaunchKernelGGL(norm_doc_starts_kernel, dim3(cdiv(n_rows + 1, kBlock)), dim3(kBlock), 0, st, rows->d_doc_off, n_rows, *nmap,
+                           static_cast<const uint32_t *>(d_byte_of), nbytes, d_line_starts);
+        d_starts = d_line_starts;
+      }
       hipLaunchKernelGGL(row_splits_kernel, dim3(cdiv(n_rows + 1, kBlock)), dim3(kBlock), 0, st, d_starts, n_rows,
                          static_cast<const uint32_t *>(d_byte_of), n_text, static_cast<const uint2 *>(d_offs), n_ids, rows->unit,
                          d_row_splits, d_row_base);
+      if (nmap && d_row_base) {  // the rows' starts in the caller's text
+        hipLaunchKernelGGL(norm_row_base_kernel, dim3(cdiv(n_rows + 1, kBlock)), dim3(kBlock), 0, st, d_starts, n_rows,
+                           static_cast<const uint32_t *>(d_byte_of), n_text, *nmap, rows->unit, d_row_base);
+      }
     } else {
       WP_HIP(hipMemsetAsync(d_row_splits, 0, (n_rows + 1) * sizeof(long long), st));
     }
@@ -1322,7 +1338,12 @@ struct LinearPath {
       fetch_scalars(c, 10);
       const size_t n_ids = c->h_scalars[9];
       if (rows) row_structure(n_ids);
-      if (offs_unit == WP_OFFSETS_BYTES && n_ids > 0) {  // code points -> bytes
+      if (nmap) {  // normalised code points -> the caller's text, in either unit (a documents call without offsets: not needed)
+        if (n_ids > 0 && (!rows || rows->unit >= 0)) {
+          hipLaunchKernelGGL(span_source_kernel, dim3(cdiv(n_ids, kBlock)), dim3(kBlock), 0, st, d_offs, n_ids, *nmap, offs_unit);
+          WP_LAUNCH_CHECK();
+        }
+      } else if (offs_unit == WP_OFFSETS_BYTES && n_ids > 0) {  // code points -> bytes
         if (!rows) {  // (a documents call has built byte_of[] for its row splits)
           hipLaunchKernelGGL(cp_byte_kernel, dim3(cdiv(nbytes, kDecTile)), dim3(kBlock), 0, st, d_text, nbytes, d_tile_prefix, n_text,
                              d_byte_of);
@@ -1389,7 +1410,7 @@ struct LinearPath {
       S.ms_lcp = span(3, 4);
       S.ms_scan = span(4, 5);
       S.ms_walk = span(5, 6);
-      S.ms_total = span(0, 6);
+      S.ms_total = span(0, 6) + S.ms_normalize;
       S.ms_radix_scatter = c->rstats.spans.resolve();
     }
     c->d_ids = d_ids;
@@ -1434,7 +1455,7 @@ struct LinearPath {
 // 4-byte aligned and readable up to the next multiple of 16.  S: statistics of this call.
 // offs_unit >= 0 (offsets mode, WP_OFFSETS_*): c->d_offs also holds the span of every id, [begin, end) as two uint32
 static void encode_on_device(const wp_vocab *v, Context *c, const uint8_t *d_text, size_t nbytes, size_t *n_ids_out,
-                             wp_stats &S, int offs_unit = -1, RowsCall *rows = nullptr) {
+                             EncodeStats &S, int offs_unit = -1, RowsCall *rows = nullptr) {
   hipStream_t st = c->stream;
   const HostVocab &hv = v->hv;
   std::memset(&S, 0, sizeof(S));
@@ -1455,6 +1476,27 @@ static void encode_on_device(const wp_vocab *v, Context *c, const uint8_t *d_tex
   S.offsets_unit = offs_unit;
   c->d_offs = nullptr;
 
+  // ---------------- WP_OPT_NORMALIZE: the text is rewritten first, everything below runs on the copy ----------------
+  const uint8_t *src_text = d_text;  // what the caller passed: explicit rows are checked, lines counted, against it
+  const size_t src_bytes = nbytes;
+  NormResult norm;
+  const NormMap *nmap = nullptr;
+  if (v->normalize != 0) {
+    normalize_on_device(c, d_text, nbytes, v->normalize, offs_unit >= 0, v->stage_timing, norm);
+    S.normalize = v->normalize;
+    S.norm_bytes = static_cast<int64_t>(norm.nbytes);
+    S.ms_normalize = norm.ms;
+    if (norm.nbytes == 0) {
+      if (!rows) return;  // nothing is left: no ids
+      // (a documents call still has its one empty row to report: the lines of a single blank)
+      WP_HIP(hipMemsetAsync(c->norm_buf.p, 0x20, 1, st));
+      norm.nbytes = 1;
+    }
+    d_text = norm.text;
+    nbytes = norm.nbytes;
+    if (offs_unit >= 0) nmap = &norm.map;
+  }
+
   c->rstats.passes = 0;
   c->rstats.elems = 0;
   c->rstats.digit_bytes = 0;
@@ -1468,8 +1510,8 @@ static void encode_on_device(const wp_vocab *v, Context *c, const uint8_t *d_tex
   Arena aa(&c->a_buf, guard);
   uint32_t *d_tile_cnt = nullptr, *d_cnt_tmp = nullptr, *d_cps = nullptr;
   uint8_t *d_cls = nullptr;
-  const unsigned line_tiles = cdiv(nbytes, kLineTile);
-  uint32_t *d_line_tmp = nullptr;
+  const unsigned line_tiles = cdiv(nbytes, kLineTile), src_line_tiles = cdiv(src_bytes, kLineTile);
+  uint32_t *d_line_tmp = nullptr, *d_src_line_cnt = nullptr;
   for (int pass = 0; pass < 2; pass++) {
     d_tile_cnt = aa.take<uint32_t>(dec_tiles + 1);
     d_cnt_tmp = aa.take<uint32_t>(cdiv(dec_tiles, kScanTile) + 8);
@@ -1478,6 +1520,7 @@ static void encode_on_device(const wp_vocab *v, Context *c, const uint8_t *d_tex
     if (rows && !rows->d_doc_off) {  // lines mode of a documents call: line ends per tile and the scan's scratch
       rows->d_line_cnt = aa.take<uint32_t>(line_tiles + 1);
       d_line_tmp = aa.take<uint32_t>(cdiv(line_tiles, kScanTile) + 8);
+      if (v->normalize != 0) d_src_line_cnt = aa.take<uint32_t>(src_line_tiles + 1 + cdiv(src_line_tiles, kScanTile) + 8);
     }
     if (pass == 0) aa.commit();
   }
@@ -1498,21 +1541,26 @@ static void encode_on_device(const wp_vocab *v, Context *c, const uint8_t *d_tex
   hipLaunchKernelGGL(alphabet_lut_kernel, dim3(kCpTableSize / kBlock), dim3(kBlock), 0, st, c->d_used, c->d_scan_tmp, c->d_lut);
   if (rows) {  // the rows of a documents call: counted (lines) or checked (explicit) beside the decode, fetched with its scalars
     if (rows->d_doc_off) {
-      hipLaunchKernelGGL(rows_check_kernel, dim3(cdiv(rows->n_docs + 1, kBlock)), dim3(kBlock), 0, st, d_text, nbytes, rows->d_doc_off,
+      hipLaunchKernelGGL(rows_check_kernel, dim3(cdiv(rows->n_docs + 1, kBlock)), dim3(kBlock), 0, st, src_text, src_bytes, rows->d_doc_off,
                          rows->n_docs, c->d_scalars + kScalarRowsBad);
     } else {
+      if (v->normalize != 0) {  // the rows are the lines of the caller's text (a last line may normalise to nothing)
+        hipLaunchKernelGGL(line_count_kernel, dim3(src_line_tiles), dim3(kBlock), 0, st, src_text, src_bytes, d_src_line_cnt);
+        device_exclusive_scan(d_src_line_cnt, d_src_line_cnt, src_line_tiles, d_src_line_cnt + src_line_tiles + 1,
+                              c->d_scalars + kScalarSrcRows, st);
+      }
       hipLaunchKernelGGL(line_count_kernel, dim3(line_tiles), dim3(kBlock), 0, st, d_text, nbytes, rows->d_line_cnt);
       device_exclusive_scan(rows->d_line_cnt, rows->d_line_cnt, line_tiles, d_line_tmp, c->d_scalars + kScalarRows, st);
     }
   }
   WP_LAUNCH_CHECK();
-  fetch_scalars(c, rows ? 24 : 22);
+  fetch_scalars(c, rows ? (v->normalize != 0 ? kScalarSrcRows + 1 : 24) : 22);
   if (rows) {
     if (rows->d_doc_off && c->h_scalars[kScalarRowsBad] != 0) {
       throw std::invalid_argument("document offsets: " + std::to_string(c->h_scalars[kScalarRowsBad]) +
                                   " boundaries are not increasing from 0 to nbytes with a '\\n' in front of each");
     }
-    rows->n_rows = rows->d_doc_off ? rows->n_docs : c->h_scalars[kScalarRows];
+    rows->n_rows = rows->d_doc_off ? rows->n_docs : c->h_scalars[v->normalize != 0 ? kScalarSrcRows : kScalarRows];
     if (rows->n_rows > rows->capacity) throw std::invalid_argument("capacity_rows is smaller than the number of rows");
     S.n_rows = static_cast<int64_t>(rows->n_rows);
     S.rows_route = 1;
@@ -1547,10 +1595,10 @@ static void encode_on_device(const wp_vocab *v, Context *c, const uint8_t *d_tex
     try {
       if (sigma <= 255) {
         LinearPath<uint8_t>(v, c, S, ab, aa, d_text, nbytes, d_tile_cnt, n_text, n, d_cps, d_cls, bits, text_only,
-                                 offs_unit, rows).run(n_ids_out);
+                                 offs_unit, rows, nmap).run(n_ids_out);
       } else {
         LinearPath<uint32_t>(v, c, S, ab, aa, d_text, nbytes, d_tile_cnt, n_text, n, d_cps, d_cls, bits, text_only,
-                                 offs_unit, rows).run(n_ids_out);
+                                 offs_unit, rows, nmap).run(n_ids_out);
       }
       S.list_retries = attempt;
       return;

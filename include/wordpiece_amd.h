@@ -356,6 +356,20 @@ typedef struct {
                                  wp_stats.ms_total)                                                                     */
 } wp_norm_stats;
 int wp_get_norm_stats(const wp_vocab *v, wp_norm_stats *out);
+/* The walk's part of the statistics of the last encode (Linear or fast), in a struct of its own for the same reason:
+ * which of the walk's variants produced the ids.  Taken from values the host holds or fetches anyway (no extra wait).
+ * Sharded and pipelined calls report the sums of the two counts, the largest gap and the first text's `lean`. */
+typedef struct {
+  int64_t n_wide_words;   /* stretches [anchor, next anchor) of more than 48 positions that a whole wave walked (Linear,
+                             class rule with hard spacing chars only; 0: the wide walk did not run)                     */
+  int64_t n_long_words;   /* words of more than 2048 positions walked by pointer doubling (wp_stats.anchor_mode == 2)    */
+  int32_t lean;           /* 1: the Linear path's list-building walk kernel; 0: the per-position walk kernel of
+                             WP_OPT_SPARSE_EMIT / long words, or the fast path's kernels                                 */
+  int32_t max_anchor_gap; /* the largest distance between neighbouring class-rule anchors (text start and end included),
+                             as the gap kernel reports it: when no spacing char occurs inside a token (and always in
+                             the fast path) a distance above 2048 is measured up to the first blank and stops at 2049 */
+} wp_walk_stats;
+int wp_get_walk_stats(const wp_vocab *v, wp_walk_stats *out);
 
 /* ---- debug fetch (WP_OPT_KEEP_DEBUG): copies device intermediates to host ----
  * which: 0 S (dense symbols as int32, n), 1 SA (n), 2 rank (n; the full inverse SA is kept only with this option —

@@ -116,3 +116,30 @@ def test_stats_struct_matches_header():
         assert C.sizeof(pytype) == C.sizeof(want), name
     for name, value in re.findall(r"#define (WP_OPT_\w+) (\d+)", hdr):
         assert getattr(W, name) == int(value), name
+
+
+def test_walk_stats_struct_matches_header(tmp_path):
+    """wp_walk_stats is a struct of its own (wp_stats keeps its size and its last field): the ctypes mirror follows the
+    header's fields, and both mirrors have the sizes and offsets a C compiler gives the header's structs."""
+    import ctypes as C
+    import subprocess
+    hdr = open(os.path.join(ROOT, "include", "wordpiece_amd.h")).read()
+    body = hdr[hdr.rindex("typedef struct {", 0, hdr.index("} wp_walk_stats;")):hdr.index("} wp_walk_stats;")]
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S).replace("typedef struct {", "")
+    fields = [tuple(decl.split()) for decl in body.split(";") if decl.strip()]
+    widths = {"int64_t": C.c_int64, "int32_t": C.c_int32}
+    assert [(name, widths[ctype]) for ctype, name in fields] == list(W.WalkStats._fields_)
+    assert [name for _, name in fields] == ["n_wide_words", "n_long_words", "lean", "max_anchor_gap"]
+    assert [f[0] for f in W.Stats._fields_][-1] == "rows_route"
+    src = tmp_path / "sz.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "wordpiece_amd.h"\n'
+                   'int main(void) { printf("%zu %zu %zu %zu %zu\\n", sizeof(wp_stats), offsetof(wp_stats, rows_route), '
+                   'sizeof(wp_walk_stats), offsetof(wp_walk_stats, lean), offsetof(wp_walk_stats, max_anchor_gap)); return 0; }\n')
+    exe = tmp_path / "sz"
+    subprocess.run([os.environ.get("CC", "gcc"), "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)], check=True)
+    got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
+    assert got == [C.sizeof(W.Stats), W.Stats.rows_route.offset, C.sizeof(W.WalkStats), W.WalkStats.lean.offset,
+                   W.WalkStats.max_anchor_gap.offset]
+    # without a device the statistics of a handle that never encoded are zero
+    ws = W.Vocab(["a"]).walk_stats()
+    assert ws == dict(n_wide_words=0, n_long_words=0, lean=0, max_anchor_gap=0)

@@ -40,7 +40,7 @@ ABI_SYMBOLS = [
     "wp_fast_encode_external", "wp_vocab_token_utf8", "wp_trim", "wp_linear_encode_batch", "wp_linear_encode_stream",
     "wp_linear_encode_offsets", "wp_linear_encode_offsets_device",
     "wp_linear_encode_rows", "wp_linear_encode_rows_device", "wp_linear_encode_padded", "wp_linear_encode_padded_device",
-    "wp_normalize_cp", "wp_normalize_device", "wp_normalize", "wp_get_norm_stats",
+    "wp_normalize_cp", "wp_normalize_device", "wp_normalize", "wp_get_norm_stats", "wp_get_walk_stats",
 ]
 
 
@@ -76,6 +76,12 @@ class Stats(C.Structure):
 class NormStats(C.Structure):
     """wp_norm_stats: WP_OPT_NORMALIZE's part of the statistics (Vocab.stats() merges it into its dict)."""
     _fields_ = [("normalize", C.c_int32), ("norm_bytes", C.c_int64), ("ms_normalize", C.c_double)]
+
+
+class WalkStats(C.Structure):
+    """wp_walk_stats: which variant of the walk produced the ids of the last encode (Vocab.walk_stats())."""
+    _fields_ = [("n_wide_words", C.c_int64), ("n_long_words", C.c_int64), ("lean", C.c_int32),
+                ("max_anchor_gap", C.c_int32)]
 
 
 _TEXT_SOURCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t))
@@ -142,6 +148,7 @@ def lib():
         L.wp_set_option.argtypes = [vp, C.c_int, C.c_int64]
         L.wp_get_stats.argtypes = [vp, C.POINTER(Stats)]
         L.wp_get_norm_stats.argtypes = [vp, C.POINTER(NormStats)]
+        L.wp_get_walk_stats.argtypes = [vp, C.POINTER(WalkStats)]
         L.wp_linear_debug_fetch.argtypes = [vp, C.c_int, i32p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.wp_free.argtypes = [vp]
         L.wp_free.restype = None
@@ -246,6 +253,13 @@ class Vocab:
         _check(lib().wp_get_norm_stats(self._h, C.byref(ns)))
         d.update({k: getattr(ns, k) for k, _ in ns._fields_})
         return d
+
+    def walk_stats(self):
+        """wp_walk_stats of the last encode (Linear or fast) as a dict: n_wide_words, n_long_words, lean,
+        max_anchor_gap."""
+        ws = WalkStats()
+        _check(lib().wp_get_walk_stats(self._h, C.byref(ws)))
+        return {k: int(getattr(ws, k)) for k, _ in ws._fields_}
 
     def encode(self, text):
         """Host UTF-8 bytes/str -> numpy int32 ids (wp_linear_encode)."""

@@ -245,11 +245,13 @@ struct DeviceGuard {
 
 using namespace wp;
 
-// the statistics of an encode as the device path fills them: wp_stats and, behind it, what wp_get_norm_stats hands out
+// the statistics of an encode as the device path fills them: wp_stats and, behind it, what wp_get_norm_stats and
+// wp_get_walk_stats hand out
 struct EncodeStats : wp_stats {
   int32_t normalize;
   int64_t norm_bytes;
   double ms_normalize;
+  wp_walk_stats walk;
 };
 
 struct wp_vocab {

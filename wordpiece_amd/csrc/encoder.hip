@@ -199,6 +199,11 @@ int wp_get_norm_stats(const wp_vocab *v, wp_norm_stats *out) {
   return WP_OK;
 }
 
+int wp_get_walk_stats(const wp_vocab *v, wp_walk_stats *out) {
+  *out = v->stats.walk;
+  return WP_OK;
+}
+
 int wp_linear_encode_device(wp_vocab *v, const void *d_utf8, size_t nbytes, const int32_t **d_ids, size_t *n_ids) {
   return guarded([&] {
     if ((reinterpret_cast<uintptr_t>(d_utf8) & 3u) != 0) throw std::invalid_argument("device text must be 4-byte aligned");
@@ -463,6 +468,9 @@ void encode_multi(wp_vocab *v, const char *utf8, size_t nbytes, const std::vecto
     S.round0_sorted += T.round0_sorted;
     S.norm_bytes += T.norm_bytes;
     S.ms_normalize = std::max(S.ms_normalize, T.ms_normalize);
+    S.walk.n_wide_words += T.walk.n_wide_words;
+    S.walk.n_long_words += T.walk.n_long_words;
+    S.walk.max_anchor_gap = std::max(S.walk.max_anchor_gap, T.walk.max_anchor_gap);
     S.ms_total = std::max(S.ms_total, T.ms_total);
     S.ms_decode = std::max(S.ms_decode, T.ms_decode);
     S.ms_sa = std::max(S.ms_sa, T.ms_sa);
@@ -1087,6 +1095,10 @@ void encode_pipeline(wp_vocab *v, Next &&next, Deliver &&deliver) {
     total.normalize = std::max(total.normalize, st.normalize);
     total.norm_bytes += st.norm_bytes;
     total.ms_normalize += st.ms_normalize;
+    total.walk.n_wide_words += st.walk.n_wide_words;
+    total.walk.n_long_words += st.walk.n_long_words;
+    total.walk.max_anchor_gap = std::max(total.walk.max_anchor_gap, st.walk.max_anchor_gap);
+    if (i == 0) total.walk.lean = st.walk.lean;
     total.rounds = std::max(total.rounds, st.rounds);
     if (next_up.valid()) {
       const std::string err = next_up.get();

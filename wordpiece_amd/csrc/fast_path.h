@@ -105,6 +105,7 @@ static void encode_fast_on_device(const wp_vocab *v, Context *c, const uint8_t *
   fetch_scalars(c, 12);
   const size_t n_anchors = c->h_scalars[10], max_gap = c->h_scalars[11];
   S.n_anchors = static_cast<int64_t>(n_anchors);
+  S.walk.max_anchor_gap = static_cast<int32_t>(max_gap);  // (wp_walk_stats: no wide walk here, and no lean kernel)
   if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[2], st));
   FastArgs fa{d_cps, d_cls, n_text,
               TrieView{c->d_trie_key, c->d_trie_child, c->d_trie_id, static_cast<uint32_t>(hv.trie_key.size() - 1)},
@@ -120,6 +121,7 @@ static void encode_fast_on_device(const wp_vocab *v, Context *c, const uint8_t *
     fetch_scalars(c, 13);
     const uint32_t nw = std::min(c->h_scalars[12], lw_cap);
     if (nw > 0) {
+      S.walk.n_long_words = static_cast<int64_t>(nw);
       std::vector<LongWord> h_lw(nw);
       WP_HIP(hipMemcpyAsync(h_lw.data(), d_lw, sizeof(LongWord) * nw, hipMemcpyDeviceToHost, st));
       WP_HIP(hipStreamSynchronize(st));

@@ -124,6 +124,7 @@ struct LinearPath {
   hipStream_t st, st2;
   const HostVocab &hv;
   bool full, prune, use_trie, key_lookup, keys_only, window_store, use_digit_bytes, staged_possible, sparse_emit;
+  bool wide_ran = false;  // the walk took the wide branch: scalar 13 holds its count of words (wp_walk_stats)
   uint32_t need_depth;
   int M, P, P_cap, bucket_shift, bucket_shift_all, key_shift, key_shift_all, hb_n, win_mid;
   unsigned sl_tiles, sl_groups, nbuckets, nbuckets_all, nkbuckets, nkbuckets_all;
@@ -1125,6 +1126,7 @@ struct LinearPath {
     fetch_scalars(c, 13);
     const uint32_t nw = std::min(c->h_scalars[12], lw_cap);
     if (nw == 0) return;
+    S.walk.n_long_words = static_cast<int64_t>(nw);
     std::vector<LongWord> h_lw(nw);
     WP_HIP(hipMemcpyAsync(h_lw.data(), d_lw, sizeof(LongWord) * nw, hipMemcpyDeviceToHost, st));
     WP_HIP(hipStreamSynchronize(st));
@@ -1213,6 +1215,7 @@ struct LinearPath {
     fetch_scalars(c, 12);
     size_t n_anchors = c->h_scalars[10];
     const size_t max_anchor_gap = c->h_scalars[11];
+    S.walk.max_anchor_gap = static_cast<int32_t>(max_anchor_gap);
     const bool all_hard = hv.soft.empty();
     bool staged = staged_possible && max_anchor_gap <= kMaxAnchorGap;
     if (staged_possible && !staged) WP_HIP(hipMemsetAsync(d_emit, 0x80, n_text * sizeof(int32_t), st));  // long words after all
@@ -1235,6 +1238,7 @@ struct LinearPath {
       // wave each first (walk.h, wide walk)
       if (S.anchor_mode == 0 && all_hard && max_anchor_gap > kWideMin) {
         uint32_t *d_wide_list = reinterpret_cast<uint32_t *>(KB), *d_wide_cnt = VA;
+        wide_ran = true;
         WP_HIP(hipMemsetAsync(c->d_scalars + 13, 0, sizeof(uint32_t), st));
         hipLaunchKernelGGL(wide_collect_kernel, dim3(std::min<size_t>(cdiv(acap, kBlock), 2048)), dim3(kBlock), 0, st, d_anchors,
                            c->d_scalars + 10, n_text, d_wide_list, c->d_scalars + 13);
@@ -1291,6 +1295,7 @@ struct LinearPath {
       }
     }
     S.staged_emit = staged ? 1 : 0;
+    S.walk.lean = staged ? 1 : 0;  // (every list-building walk of this path is walk_lean_kernel)
     WP_LAUNCH_CHECK();
     return d_ids;
   }
@@ -1394,6 +1399,7 @@ struct LinearPath {
     fetch_scalars(c, 20);
     const size_t n_ids = n_text > 0 ? c->h_scalars[9] : 0;
     S.n_ids = static_cast<int64_t>(n_ids);
+    S.walk.n_wide_words = wide_ran ? static_cast<int64_t>(c->h_scalars[13]) : 0;  // (cleared only when that branch runs)
     S.radix_passes = c->rstats.passes;
     S.radix_pass_elems = c->rstats.elems;
     S.radix_digit_bytes = c->rstats.digit_bytes;

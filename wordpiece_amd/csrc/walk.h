@@ -603,7 +603,15 @@ __global__ __launch_bounds__(kBlock) void cover_flags_kernel(const uint8_t *__re
       const uint8_t cp = p ? cls[p - 1] : 0;
       const bool wp = p == 0 || (c & kClsSpacing) || (cp & kClsSpacing);
       const bool covered_rule = p < ga || p >= gb;
-      const bool anchor = covered_rule ? (wp && cover <= static_cast<int32_t>(p)) : (p == 0 || w_hard(c) || w_hard(cp));
+      bool anchor = covered_rule ? (wp && cover <= static_cast<int32_t>(p)) : (p == 0 || w_hard(c) || w_hard(cp));
+      // the walk starts at the first position that is no blank (linear.cpp:227-229).  Behind soft blanks the class rule
+      // makes it no anchor, and where the coverage rule does not reach (leading blanks short of a long gap) nobody
+      // would walk the first word: it is an anchor of its own.  (Longer leading runs are a long gap: covered_rule.)
+      if (!covered_rule && !anchor && !(c & kClsSpace) && (cp & kClsSpace) && p <= kMaxAnchorGap) {
+        size_t q = p - 1;
+        while (q > 0 && (cls[q - 1] & kClsSpace)) --q;
+        anchor = q == 0;
+      }
       const bool flag = !(c & kClsSpace) && anchor;
       aflags[p] = flag ? 1 : 0;
       set += flag ? 1u : 0u;
@@ -821,7 +829,8 @@ __global__ __launch_bounds__(kBlock) void walk_kernel(WalkArgs a, const uint32_t
     // the reference skips leading whitespace first (linear.cpp:227-229); if the first real
     // position is not an anchor by itself, this thread owns it.  (Only with soft spacing chars under
     // the class rule: otherwise that position always is an anchor — behind a hard space, or, under
-    // the coverage rule, a word-prefix position no match reaches, since spaces match nothing.)
+    // the coverage rule, flagged by cover_flags_kernel: a word-prefix position no match reaches, since
+    // spaces match nothing, or the text's first non-blank where the class rule stands.)
     size_t q = 0;
     while (q < a.n_text && w_space(a, q)) ++q;
     Out o = out();

@@ -143,6 +143,53 @@ int wp_linear_encode_padded_device(wp_vocab *v, const void *d_utf8, size_t nbyte
                                    int max_len, int32_t cls_id, int32_t sep_id, int32_t pad_id, int32_t *d_input_ids,
                                    int32_t *d_lengths, size_t capacity_rows, size_t *n_rows);
 
+/* ---- model inputs (an addition: HF tokenizer(a, b, truncation=, stride=, return_overflowing_tokens=, padding="max_length")) ----
+ * The rows of a documents call (same joined input, explicit rows or lines, both routes, WP_OPT_NORMALIZE as there) become
+ * SAMPLES: with pairs == 0 row s is sample s (sequence A only); with pairs == 1 rows 2s, 2s + 1 are A and B of sample s
+ * (an odd number of rows fails with WP_ERR_ARG before anything is written).  T_A, T_B: the ids of those rows exactly as
+ * wp_linear_encode_rows gives them, la, lb their lengths; specials = (cls_id >= 0) + (sep_id >= 0) * (pairs ? 2 : 1);
+ * B = max_len - specials is the id budget of an output row.
+ * An output row is [cls] A' [sep], or [cls] A' [sep] B' [sep] for pairs (an empty B' keeps its [sep]), then pad_id up
+ * to max_len.  token_type_ids: 0 for [cls], A' and the first [sep], 1 for B' and the second [sep], 0 for the padding.
+ * lengths[r] counts everything but the padding; sample[r] is the sample of output row r (HF
+ * overflow_to_sample_mapping).  With unit WP_OFFSETS_* offsets[r][col] = [begin, end) of that id relative to its own
+ * document, as wp_linear_encode_rows gives it; specials and padding get (0, 0).
+ * stride == -1: one output row per sample, sample[r] == r.
+ *   WP_TRUNC_LONGEST_FIRST: what HF's fast (Rust) tokenizer does, not the loop of the slow one: if la + lb <= B all is
+ *     kept; else the shorter side (A on a tie) keeps min(short, max(B - long, B / 2)) and the longer one the rest of B:
+ *       la <= lb: ka = min(la, max(B - lb, B / 2)), kb = min(lb, B - ka);  else kb = min(lb, max(B - la, B / 2)), ka = min(la, B - kb)
+ *     e.g. (la, lb, B) = (5, 5, 7) -> (3, 4), (6, 5, 7) -> (4, 3), (4, 10, 7) -> (3, 4).  pairs == 0: ka = min(la, B).
+ *   WP_TRUNC_ONLY_FIRST / WP_TRUNC_ONLY_SECOND: window 0 of the windows below, taken with stride 0.
+ * stride >= 0 (WP_TRUNC_ONLY_FIRST / _SECOND only): one side is cut into windows (A / B; A when pairs == 0), the other
+ *   is fixed and repeated in every window.  st = max(stride, 0).  The fixed side keeps kF = min(lF, B - st - 1) ids (0
+ *   without pairs); W = B - kF >= st + 1 is the window size and step = W - st >= 1.  A windowed side of l ids gives 1
+ *   window if l <= W, else 1 + ceil((l - W) / step); window j holds its ids [j * step, min(l, j * step + W)).  The
+ *   windows of sample s are consecutive output rows, in order, in front of those of sample s + 1.  Where the fixed side
+ *   fits this is HF's [encoding] + encoding.overflowing; where it does not, HF raises and this call cuts it to
+ *   B - st - 1 ids, so that it is a total function.
+ * WP_ERR_ARG, in the host entry point before a device is touched: spec NULL, an unknown truncation, stride < -1, pairs
+ * not 0 / 1, max_len < 1 or B < 0, WP_TRUNC_LONGEST_FIRST with stride >= 0, WP_TRUNC_ONLY_SECOND with pairs == 0,
+ * WP_TRUNC_ONLY_FIRST / _SECOND with B < st + 1 (no room for a window), an odd number of rows for pairs (device entry
+ * point, lines mode: once the lines are counted, before any output is written), a unit other than -1, 0, 1.
+ * WP_ERR_TOO_LARGE: more output rows than UINT32_MAX, more samples than INT32_MAX, or a batch whose size overflows size_t.
+ * Empty input (nbytes == 0, or explicit rows that are all empty) needs no device in the host entry point. */
+#define WP_TRUNC_LONGEST_FIRST 0
+#define WP_TRUNC_ONLY_FIRST 1
+#define WP_TRUNC_ONLY_SECOND 2
+typedef struct { int32_t max_len, cls_id, sep_id, pad_id, pairs, truncation, stride, unit; } wp_inputs_spec;
+typedef struct { int32_t *input_ids, *token_type_ids, *lengths, *sample; uint32_t *offsets; } wp_inputs;
+/* host text in; five blocks out: input_ids, token_type_ids [n_out, max_len], lengths, sample [n_out], offsets
+ * [n_out, max_len, 2] (free each with wp_free; offsets NULL when spec->unit == -1, all NULL when n_out == 0) */
+int wp_linear_encode_inputs(wp_vocab *v, const char *utf8, size_t nbytes, const int64_t *doc_off, size_t n_docs,
+                            const wp_inputs_spec *spec, wp_inputs *out, size_t *n_out, size_t *n_samples);
+/* device text and doc_off (contracts of wp_linear_encode_rows_device) into caller-owned device buffers of
+ * capacity_rows rows (offsets: 8-byte aligned; may be NULL when unit == -1); nothing behind n_out rows is touched; too
+ * little room: WP_ERR_ARG, the needed count in *n_out, nothing written.  The call returns when the batch is complete:
+ * without windows it waits as often as wp_linear_encode_padded_device, with windows once more (for the row count). */
+int wp_linear_encode_inputs_device(wp_vocab *v, const void *d_utf8, size_t nbytes, const int64_t *d_doc_off, size_t n_docs,
+                                   const wp_inputs_spec *spec, const wp_inputs *d_out, size_t capacity_rows,
+                                   size_t *n_out, size_t *n_samples);
+
 /* The same call sharded over several GPUs of the node, behind the boundary: the reference's own
  * precedent is the in-library chunking at whitespace of linear.cpp:283-299 (thread chunks) and
  * linear.cpp:355-367 (encodeExternal batches).  The text is cut at ASCII whitespace into one shard
@@ -370,6 +417,16 @@ typedef struct {
                              the fast path) a distance above 2048 is measured up to the first blank and stops at 2049 */
 } wp_walk_stats;
 int wp_get_walk_stats(const wp_vocab *v, wp_walk_stats *out);
+/* The model-inputs part of the statistics of the last call, in a struct of its own for the same reason.  After an
+ * inputs call wp_stats.n_rows, rows_route, offsets_unit and n_ids mean what they mean after a rows call and
+ * rows_truncated is 0. */
+typedef struct {
+  int64_t n_samples, n_out;  /* samples and output rows; n_out -1: the last call was no inputs call                     */
+  int64_t n_cut;             /* samples that lost ids for good (truncation, or a fixed side cut to leave a window room)  */
+  int64_t n_windowed;        /* samples with more than one window                                                        */
+  int32_t pairs, truncation, stride, reserved; /* of the call's wp_inputs_spec                                          */
+} wp_inputs_stats;
+int wp_get_inputs_stats(const wp_vocab *v, wp_inputs_stats *out);
 
 /* ---- debug fetch (WP_OPT_KEEP_DEBUG): copies device intermediates to host ----
  * which: 0 S (dense symbols as int32, n), 1 SA (n), 2 rank (n; the full inverse SA is kept only with this option —

@@ -29,6 +29,9 @@ WP_OPT_NORMALIZE = 14
 WP_NORM_CLEAN, WP_NORM_LOWER, WP_NORM_STRIP_ACCENTS, WP_NORM_BERT_UNCASED = 1, 2, 4, 7
 WP_OFFSETS_BYTES, WP_OFFSETS_CODE_POINTS = 0, 1
 _OFFSET_UNITS = {"byte": WP_OFFSETS_BYTES, "char": WP_OFFSETS_CODE_POINTS}
+WP_TRUNC_LONGEST_FIRST, WP_TRUNC_ONLY_FIRST, WP_TRUNC_ONLY_SECOND = 0, 1, 2
+_TRUNCATIONS = {"longest_first": WP_TRUNC_LONGEST_FIRST, "only_first": WP_TRUNC_ONLY_FIRST,
+                "only_second": WP_TRUNC_ONLY_SECOND}
 
 # every symbol include/wordpiece_amd.h declares (checked by the CPU test-suite)
 ABI_SYMBOLS = [
@@ -41,6 +44,7 @@ ABI_SYMBOLS = [
     "wp_linear_encode_offsets", "wp_linear_encode_offsets_device",
     "wp_linear_encode_rows", "wp_linear_encode_rows_device", "wp_linear_encode_padded", "wp_linear_encode_padded_device",
     "wp_normalize_cp", "wp_normalize_device", "wp_normalize", "wp_get_norm_stats", "wp_get_walk_stats",
+    "wp_linear_encode_inputs", "wp_linear_encode_inputs_device", "wp_get_inputs_stats",
 ]
 
 
@@ -82,6 +86,24 @@ class WalkStats(C.Structure):
     """wp_walk_stats: which variant of the walk produced the ids of the last encode (Vocab.walk_stats())."""
     _fields_ = [("n_wide_words", C.c_int64), ("n_long_words", C.c_int64), ("lean", C.c_int32),
                 ("max_anchor_gap", C.c_int32)]
+
+
+class InputsSpec(C.Structure):
+    """wp_inputs_spec: the arguments of an inputs call."""
+    _fields_ = [("max_len", C.c_int32), ("cls_id", C.c_int32), ("sep_id", C.c_int32), ("pad_id", C.c_int32),
+                ("pairs", C.c_int32), ("truncation", C.c_int32), ("stride", C.c_int32), ("unit", C.c_int32)]
+
+
+class Inputs(C.Structure):
+    """wp_inputs: the five blocks of a batch of model inputs (host blocks out, or caller-owned device buffers in)."""
+    _fields_ = [("input_ids", C.c_void_p), ("token_type_ids", C.c_void_p), ("lengths", C.c_void_p), ("sample", C.c_void_p),
+                ("offsets", C.c_void_p)]
+
+
+class InputsStats(C.Structure):
+    """wp_inputs_stats: the model-inputs part of the statistics of the last call (Vocab.inputs_stats())."""
+    _fields_ = [("n_samples", C.c_int64), ("n_out", C.c_int64), ("n_cut", C.c_int64), ("n_windowed", C.c_int64),
+                ("pairs", C.c_int32), ("truncation", C.c_int32), ("stride", C.c_int32), ("reserved", C.c_int32)]
 
 
 _TEXT_SOURCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t))
@@ -127,6 +149,12 @@ def lib():
                                               C.c_int32, C.POINTER(i32p), C.POINTER(i32p), C.POINTER(C.c_size_t)]
         L.wp_linear_encode_padded_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int32, C.c_int32,
                                                      C.c_int32, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.wp_linear_encode_inputs.argtypes = [vp, C.c_char_p, C.c_size_t, i64p, C.c_size_t, C.POINTER(InputsSpec),
+                                              C.POINTER(Inputs), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.wp_linear_encode_inputs_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(InputsSpec),
+                                                     C.POINTER(Inputs), C.c_size_t, C.POINTER(C.c_size_t),
+                                                     C.POINTER(C.c_size_t)]
+        L.wp_get_inputs_stats.argtypes = [vp, C.POINTER(InputsStats)]
         L.wp_linear_encode_multi.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.POINTER(i32p),
                                              C.POINTER(C.c_size_t)]
         L.wp_reserve.argtypes = [vp, C.c_size_t]
@@ -399,6 +427,110 @@ class Vocab:
             break
         return ids[:rows.value], lens[:rows.value]
 
+    def inputs_stats(self):
+        """wp_inputs_stats of the last call as a dict (n_out -1: it was no inputs call)."""
+        s = InputsStats()
+        _check(lib().wp_get_inputs_stats(self._h, C.byref(s)))
+        return {k: int(getattr(s, k)) for k, _ in s._fields_ if k != "reserved"}
+
+    def encode_inputs(self, a=None, b=None, text=None, doc_offsets=None, pairs=None, max_len=128, cls_id=None, sep_id=None,
+                      pad_id=0, truncation="longest_first", stride=None, offsets=None):
+        """Model inputs (wp_linear_encode_inputs) -> a dict of numpy arrays: input_ids, token_type_ids int32 [n_out,
+        max_len], lengths, sample int32 [n_out] and, with offsets="byte" / "char", offsets uint32 [n_out, max_len, 2].
+        Row r is [cls] A' [sep] (B' [sep]) pad...; `a` (and `b`, of the same length, for pairs) are lists of str / bytes,
+        interleaved and joined here; or `text` in joined form (with `doc_offsets`, or alone: its lines) and `pairs`
+        (True: rows 2s, 2s + 1 are A and B of sample s).  truncation: "longest_first", "only_first", "only_second";
+        stride=None: one row per sample; stride >= 0 (only_first / only_second): every sample gives as many overlapping
+        windows as cover its windowed side, sample[r] names the sample of row r."""
+        if a is not None:
+            if text is not None or doc_offsets is not None or pairs is not None:
+                raise WordPieceError("text, doc_offsets and pairs go with the joined form, not with a / b")
+            if b is not None and len(b) != len(a):
+                raise WordPieceError("a and b must have the same length")
+            pairs = b is not None
+            docs = [d for ab in zip(a, b) for d in ab] if pairs else list(a)
+            bt, off = join_docs(docs)
+        else:
+            if b is not None:
+                raise WordPieceError("b goes with a")
+            if text is None:
+                raise WordPieceError("give either a (and b) or text")
+            bt, off = _docs_arg(None, text, doc_offsets)
+        spec = _inputs_spec(max_len, cls_id, sep_id, pad_id, pairs, truncation, stride, offsets)
+        out = Inputs()
+        n, ns = C.c_size_t(), C.c_size_t()
+        _check(lib().wp_linear_encode_inputs(self._h, bt, len(bt), _i64_ptr(off), 0 if off is None else len(off) - 1,
+                                             C.byref(spec), C.byref(out), C.byref(n), C.byref(ns)))
+        rows, L = n.value, int(max_len)
+        i32p = C.POINTER(C.c_int32)
+        if rows == 0:
+            res = {"input_ids": np.zeros((0, L), np.int32), "token_type_ids": np.zeros((0, L), np.int32),
+                   "lengths": np.zeros(0, np.int32), "sample": np.zeros(0, np.int32)}
+            if offsets is not None:
+                res["offsets"] = np.zeros((0, L, 2), np.uint32)
+            return res
+        res = {"input_ids": _adopt_block(C.cast(out.input_ids, i32p), (rows, L)),
+               "token_type_ids": _adopt_block(C.cast(out.token_type_ids, i32p), (rows, L)),
+               "lengths": _adopt_block(C.cast(out.lengths, i32p), (rows,)),
+               "sample": _adopt_block(C.cast(out.sample, i32p), (rows,))}
+        if offsets is not None:
+            res["offsets"] = _adopt_block(C.cast(out.offsets, C.POINTER(C.c_uint32)), (rows, L, 2))
+        return res
+
+    def encode_inputs_tensor(self, text, doc_offsets=None, pairs=False, max_len=128, cls_id=None, sep_id=None, pad_id=0,
+                             truncation="longest_first", stride=None, offsets=None, n_out=None, out=None):
+        """encode_inputs for tensors on this handle's GPU (wp_linear_encode_inputs_device) -> a dict of tensors written by
+        the library into torch.empty tensors (no copy); offsets come as int32 [n_out, max_len, 2] viewed as uint32.
+        Without windows the row count of explicit offsets is known; otherwise pass `n_out` (an upper bound will do) or
+        the call runs twice when the first guess was too small.  out=dict of caller-owned tensors (the same keys) to
+        write into: views of the first n_out rows are returned."""
+        import torch
+        text, nbytes, doc_offsets = self._rows_tensor_args(text, doc_offsets)
+        L = int(max_len)
+        spec = _inputs_spec(L, cls_id, sep_id, pad_id, pairs, truncation, stride, offsets)
+        keys = ["input_ids", "token_type_ids", "lengths", "sample"] + (["offsets"] if offsets is not None else [])
+        if n_out is not None:
+            cap = int(n_out)
+        elif doc_offsets is not None:
+            cap = (doc_offsets.numel() - 1) // (2 if pairs else 1)
+        else:
+            cap = nbytes // 32 + 1
+        dev = text.device
+        rows, ns = C.c_size_t(), C.c_size_t()
+        for _ in range(2):
+            if out is not None:
+                t = {k: out[k] for k in keys}
+                for k in keys:
+                    x = t[k]
+                    shape_ok = (x.dim() == 1 if k in ("lengths", "sample") else
+                                x.dim() == 2 and x.shape[1] == L if k != "offsets" else
+                                x.dim() == 3 and x.shape[1] == L and x.shape[2] == 2)
+                    if x.dtype not in ((torch.int32, torch.uint32) if k == "offsets" else (torch.int32,)) or \
+                            not x.is_contiguous() or x.device != dev or not shape_ok:
+                        raise WordPieceError("out must hold contiguous int32 tensors [rows, max_len], [rows] (offsets: "
+                                             "[rows, max_len, 2], int32 or uint32) on the text's device")
+                cap = min(x.shape[0] for x in t.values())
+            else:
+                t = {"input_ids": torch.empty((cap, L), dtype=torch.int32, device=dev),
+                     "token_type_ids": torch.empty((cap, L), dtype=torch.int32, device=dev),
+                     "lengths": torch.empty(cap, dtype=torch.int32, device=dev),
+                     "sample": torch.empty(cap, dtype=torch.int32, device=dev)}
+                if offsets is not None:
+                    t["offsets"] = torch.empty((cap, L, 2), dtype=torch.int32, device=dev).view(torch.uint32)
+            bufs = Inputs(*[t[k].data_ptr() if k in t else None
+                            for k in ("input_ids", "token_type_ids", "lengths", "sample", "offsets")])
+            torch.cuda.current_stream(dev).synchronize()
+            rc = lib().wp_linear_encode_inputs_device(
+                self._h, C.c_void_p(text.data_ptr()), nbytes, None if doc_offsets is None else C.c_void_p(doc_offsets.data_ptr()),
+                0 if doc_offsets is None else doc_offsets.numel() - 1, C.byref(spec), C.byref(bufs), cap, C.byref(rows),
+                C.byref(ns))
+            if rc != 0 and out is None and rows.value > cap:  # (guess too small: the call said how many)
+                cap = rows.value
+                continue
+            _check(rc)
+            break
+        return {k: t[k][:rows.value] for k in keys}
+
     def fast_encode(self, text):
         """word_piece::fast::encode on the GPU (wp_fast_encode): host bytes/str -> numpy int32 ids."""
         b = _bytes(text)
@@ -582,6 +714,13 @@ def _i64_ptr(a):
 
 def _special(i):
     return -1 if i is None else int(i)
+
+
+def _inputs_spec(max_len, cls_id, sep_id, pad_id, pairs, truncation, stride, offsets):
+    if truncation not in _TRUNCATIONS:
+        raise WordPieceError("truncation must be one of %s, not %r" % (", ".join(sorted(_TRUNCATIONS)), truncation))
+    return InputsSpec(int(max_len), _special(cls_id), _special(sep_id), int(pad_id), 0 if pairs is None else int(pairs), _TRUNCATIONS[truncation],
+                      -1 if stride is None else int(stride), -1 if offsets is None else _offset_unit(offsets))
 
 
 def _offset_unit(unit):

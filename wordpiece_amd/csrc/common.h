@@ -46,7 +46,8 @@ enum BoundSite {
   // (no address: the sorted array of round 0 in the default layout — a descent, a key the blank table marks although
   // blanks were dropped, or a multiset unlike the kept keys of the unsorted array; linear_path.h, sorted_check_kernel)
   kSiteSortOrder = 8,
-  kBoundSites = 9
+  kSiteInputs = 9,  // model inputs: the gathers of the packer from the ids and their spans (inputs.h)
+  kBoundSites = 10
 };
 #ifdef WP_DEBUG_BOUNDS
 __device__ unsigned int g_wp_oob[kBoundSites];

@@ -144,6 +144,8 @@ constexpr int kScalarKept = 25;  // d_scalars word: suffixes the keys-only round
 // documents calls (rows.h): lines of the text / boundaries of explicit rows that fail the check / rows a padded call cut
 constexpr int kScalarRows = 21, kScalarRowsBad = 22, kScalarRowsCut = 23;
 constexpr int kScalarSrcRows = 26;  // lines of the caller's text in a documents call on normalised text (normalize.h)
+// model inputs (inputs.h): samples that lost ids / the number of output rows, 64 bits (words 28, 29) / samples with windows
+constexpr int kScalarInCut = 27, kScalarInRows = 28, kScalarInWindowed = 30;
 
 // A documents call (wp_linear_encode_rows / _padded) as encode_on_device sees it: how the rows are given, and where it
 // left the row structure (device pointers into the arenas, valid like c->d_ids until the handle's next call).
@@ -181,6 +183,7 @@ struct Context {
   DeviceBuffer text_buf2, ids_stage[2];
   // documents calls: explicit row starts of a host call, results of the per-document route, padded batch of a host call
   DeviceBuffer rows_in, rows_out, pad_buf;
+  DeviceBuffer inputs_buf;  // model inputs: window counts and records per sample (inputs.h)
   // WP_OPT_NORMALIZE (normalize.h): the tables (uploaded with the first normalising call), the normalised text, the
   // tile counts of the pre-pass, and the source of every normalised code point (offsets mode)
   uint16_t *d_norm_index = nullptr;
@@ -252,6 +255,8 @@ struct EncodeStats : wp_stats {
   int64_t norm_bytes;
   double ms_normalize;
   wp_walk_stats walk;
+  wp_inputs_stats inputs;  // wp_get_inputs_stats: filled by an inputs call (inputs_call 1), zero otherwise
+  int32_t inputs_call;
 };
 
 struct wp_vocab {
@@ -294,7 +299,7 @@ static void destroy_context(Context *c) {
   if (!c) return;
   const bool owns = c->stream || c->stream2 || c->stream3 || c->d_used || c->d_lut || c->d_scan_tmp || c->d_scalars || c->d_code ||
                     c->d_symhist || c->h_scalars || c->h_code || c->d_stream || c->text_buf.p || c->a_buf.p ||
-                    c->b_buf.p || c->fmt_buf.p || c->rows_in.p || c->rows_out.p || c->pad_buf.p;
+                    c->b_buf.p || c->fmt_buf.p || c->rows_in.p || c->rows_out.p || c->pad_buf.p || c->inputs_buf.p;
   if (!owns) return;
   DeviceGuard keep;
   (void)hipSetDevice(c->device);
@@ -321,6 +326,7 @@ static void destroy_context(Context *c) {
   c->rows_in.release();
   c->rows_out.release();
   c->pad_buf.release();
+  c->inputs_buf.release();
   c->norm_buf.release();
   c->norm_aux.release();
   c->norm_map.release();
@@ -377,6 +383,7 @@ static void release_arenas(Context *c) {
   c->rows_in.release();
   c->rows_out.release();
   c->pad_buf.release();
+  c->inputs_buf.release();
   c->text_buf2.release();
   c->ids_stage[0].release();
   c->ids_stage[1].release();
@@ -398,7 +405,7 @@ static void park_context(std::unique_ptr<Context> c) {
       hipStreamSynchronize(c->stream3) == hipSuccess) {
     free_vocab_tables(c.get());
     if (c->text_buf.cap + c->text_buf2.cap + c->ids_stage[0].cap + c->ids_stage[1].cap + c->a_buf.cap + c->b_buf.cap + c->fmt_buf.cap +
-            c->rows_in.cap + c->rows_out.cap + c->pad_buf.cap + c->norm_buf.cap + c->norm_aux.cap + c->norm_map.cap >
+            c->rows_in.cap + c->rows_out.cap + c->pad_buf.cap + c->inputs_buf.cap + c->norm_buf.cap + c->norm_aux.cap + c->norm_map.cap >
         kPoolArenaBytes) {
       release_arenas(c.get());
     }

@@ -22,6 +22,7 @@
 #include "context.h"
 #include "fast_path.h"
 #include "format.h"
+#include "inputs.h"
 #include "linear_path.h"
 
 
@@ -201,6 +202,12 @@ int wp_get_norm_stats(const wp_vocab *v, wp_norm_stats *out) {
 
 int wp_get_walk_stats(const wp_vocab *v, wp_walk_stats *out) {
   *out = v->stats.walk;
+  return WP_OK;
+}
+
+int wp_get_inputs_stats(const wp_vocab *v, wp_inputs_stats *out) {
+  *out = v->stats.inputs;
+  if (!v->stats.inputs_call) out->n_out = -1;
   return WP_OK;
 }
 
@@ -983,6 +990,271 @@ int wp_linear_encode_padded_device(wp_vocab *v, const void *d_utf8, size_t nbyte
     }
     pack_on_device(v, c, r, max_len, cls_id, sep_id, pad_id, d_input_ids, d_lengths);
     *n_rows = r.n_rows;
+  });
+}
+
+}  // extern "C"
+
+// ---- model inputs (include/wordpiece_amd.h, section "model inputs"; kernels: inputs.h) -------------------------------
+namespace {
+// every argument rule that needs neither the text nor a device
+InputsGeom check_inputs_spec(const wp_inputs_spec *spec, size_t nbytes) {
+  if (!spec) throw std::invalid_argument("inputs: spec is NULL");
+  check_rows_call(spec->unit, nbytes);
+  if (spec->truncation != WP_TRUNC_LONGEST_FIRST && spec->truncation != WP_TRUNC_ONLY_FIRST && spec->truncation != WP_TRUNC_ONLY_SECOND) {
+    throw std::invalid_argument("inputs: unknown truncation strategy");
+  }
+  if (spec->stride < -1) throw std::invalid_argument("inputs: stride must be -1 (no windows) or at least 0");
+  if (spec->pairs != 0 && spec->pairs != 1) throw std::invalid_argument("inputs: pairs must be 0 or 1");
+  InputsGeom g;
+  g.max_len = spec->max_len;
+  g.head = spec->cls_id >= 0 ? 1 : 0;
+  g.nsep = spec->sep_id >= 0 ? 1 : 0;
+  const int specials = g.head + g.nsep * (spec->pairs ? 2 : 1);
+  if (spec->max_len < 1 || spec->max_len < specials) {
+    throw std::invalid_argument("max_len must be at least 1 and at least the number of specials");
+  }
+  g.budget = spec->max_len - specials;
+  g.pairs = spec->pairs;
+  g.truncation = spec->truncation;
+  g.stride = spec->stride;
+  g.cls_id = spec->cls_id;
+  g.sep_id = spec->sep_id;
+  g.pad_id = spec->pad_id;
+  if (spec->truncation == WP_TRUNC_LONGEST_FIRST) {
+    if (spec->stride >= 0) throw std::invalid_argument("inputs: windows (stride >= 0) need the truncation only_first or only_second");
+  } else {
+    if (spec->truncation == WP_TRUNC_ONLY_SECOND && !spec->pairs) throw std::invalid_argument("inputs: only_second needs pairs");
+    if (static_cast<long long>(g.budget) < static_cast<long long>(std::max(spec->stride, 0)) + 1) {
+      throw std::invalid_argument("inputs: max_len leaves no room for a window");
+    }
+  }
+  return g;
+}
+
+void check_inputs_rows(const InputsGeom &g, size_t n_rows) {
+  if (g.pairs && (n_rows & 1) != 0) throw std::invalid_argument("inputs: pairs need an even number of rows");
+}
+
+// n_out * max_len cells of 8 bytes must be addressable
+void check_inputs_size(size_t n_out, int max_len) {
+  if (n_out > static_cast<size_t>(UINT32_MAX) || n_out > SIZE_MAX / 8 / static_cast<size_t>(max_len)) {
+    throw std::length_error("inputs: too many output rows");
+  }
+}
+
+// The model inputs of a rows result.  place(n_out) names the buffers of the batch once the number of output rows is
+// known (and throws where they do not fit); returns n_out.  Waits for the batch.  Without windows the host waits once,
+// behind the packer (as pack_on_device does); with windows once more, for the row count.
+size_t inputs_on_device(wp_vocab *v, Context *c, const RowsResult &r, const InputsGeom &g, int unit,
+                        const std::function<wp_inputs(size_t)> &place) {
+  hipStream_t st = c->stream;
+  const size_t n_samples = r.n_rows / (g.pairs ? 2 : 1);
+  v->stats.rows_truncated = 0;
+  v->stats.inputs_call = 1;
+  wp_inputs_stats &is = v->stats.inputs;
+  is = wp_inputs_stats{};
+  is.n_samples = static_cast<int64_t>(n_samples);
+  is.pairs = g.pairs;
+  is.truncation = g.truncation;
+  is.stride = g.stride;
+  if (n_samples > static_cast<size_t>(INT32_MAX)) throw std::length_error("inputs: too many samples");
+  if (n_samples == 0) {
+    (void)place(0);
+    return 0;
+  }
+  const bool windows = g.stride >= 0;
+  // scratch: a record per sample | window counts (scanned in place) | the scan's tile sums
+  const size_t scan_words = cdiv(n_samples, kScanTile) + 8;
+  c->inputs_buf.ensure(n_samples * sizeof(InputsRec) + (n_samples + scan_words) * sizeof(uint32_t));
+  InputsRec *d_rec = static_cast<InputsRec *>(c->inputs_buf.p);
+  uint32_t *d_win = reinterpret_cast<uint32_t *>(d_rec + n_samples), *d_tmp = d_win + n_samples;
+  WP_HIP(hipMemsetAsync(c->d_scalars + kScalarInCut, 0, (kScalarInWindowed + 1 - kScalarInCut) * sizeof(uint32_t), st));
+  hipLaunchKernelGGL(inputs_plan_kernel, dim3(cdiv(n_samples, kBlock)), dim3(kBlock), 0, st, r.d_row_splits, n_samples, g, d_win, d_rec,
+                     c->d_scalars + kScalarInCut, c->d_scalars + kScalarInWindowed);
+  WP_LAUNCH_CHECK();
+  size_t n_out = n_samples;
+  if (windows) {
+    device_exclusive_scan(d_win, d_win, n_samples, d_tmp, nullptr, st, nullptr,
+                          reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarInRows));
+    fetch_scalars(c, kScalarInWindowed + 1);
+    unsigned long long total;
+    std::memcpy(&total, c->h_scalars + kScalarInRows, sizeof(total));
+    if (total > static_cast<unsigned long long>(UINT32_MAX)) throw std::length_error("inputs: too many output rows");
+    n_out = static_cast<size_t>(total);
+  }
+  check_inputs_size(n_out, g.max_len);
+  is.n_out = static_cast<int64_t>(n_out);
+  const wp_inputs o = place(n_out);
+  int lanes = 4;
+  while (lanes < kWave && lanes < g.max_len) lanes *= 2;
+  hipLaunchKernelGGL(inputs_pack_kernel, dim3(cdiv(n_out, static_cast<size_t>(kBlock / lanes))), dim3(kBlock), 0, st, r.d_ids,
+                     reinterpret_cast<const uint2 *>(r.d_offs), r.n_ids, r.d_row_splits, static_cast<const InputsRec *>(d_rec),
+                     windows ? static_cast<const uint32_t *>(d_win) : nullptr, n_samples, n_out, g, lanes, o.input_ids, o.token_type_ids,
+                     unit >= 0 ? reinterpret_cast<uint2 *>(o.offsets) : nullptr, o.lengths, o.sample);
+  WP_LAUNCH_CHECK();
+  if (windows) {
+    WP_HIP(hipStreamSynchronize(st));
+  } else {
+    fetch_scalars(c, kScalarInWindowed + 1);
+  }
+#ifdef WP_DEBUG_BOUNDS
+  {
+    unsigned int oob = 0;
+    WP_HIP(hipMemcpyFromSymbol(&oob, HIP_SYMBOL(g_wp_oob), sizeof(oob), kSiteInputs * sizeof(unsigned int)));
+    if (oob != 0) {
+      const unsigned int zero = 0;
+      WP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_wp_oob), &zero, sizeof(zero), kSiteInputs * sizeof(unsigned int)));
+      throw HipError("debug bounds: model inputs: " + std::to_string(oob) + " gathers outside the id list skipped");
+    }
+  }
+#endif
+  is.n_cut = c->h_scalars[kScalarInCut];
+  is.n_windowed = c->h_scalars[kScalarInWindowed];
+  return n_out;
+}
+
+size_t count_lines_host(const char *utf8, size_t nbytes) {
+  if (nbytes == 0) return 0;
+  size_t n = utf8[nbytes - 1] != '\n' ? 1 : 0;
+  for (const char *p = utf8, *end = utf8 + nbytes; (p = static_cast<const char *>(std::memchr(p, '\n', end - p))) != nullptr; p++) n++;
+  return n;
+}
+}  // namespace
+
+extern "C" {
+
+int wp_linear_encode_inputs(wp_vocab *v, const char *utf8, size_t nbytes, const int64_t *doc_off, size_t n_docs,
+                            const wp_inputs_spec *spec, wp_inputs *out, size_t *n_out, size_t *n_samples) {
+  return guarded([&] {
+    if (!out || !n_out || !n_samples) throw std::invalid_argument("inputs: null result pointer");
+    *out = wp_inputs{};
+    *n_out = 0;
+    *n_samples = 0;
+    const InputsGeom g = check_inputs_spec(spec, nbytes);
+    const int unit = spec->unit;
+    if (doc_off) check_doc_off_host(utf8, nbytes, doc_off, n_docs);
+    const size_t rows = doc_off ? n_docs : count_lines_host(utf8, nbytes);
+    check_inputs_rows(g, rows);
+    const size_t max_len = static_cast<size_t>(g.max_len);
+    if (nbytes == 0 || (doc_off && nbytes == n_docs)) {  // rows of specials and padding only: no device needed
+      const size_t n = rows / (g.pairs ? 2 : 1);
+      check_inputs_size(n, g.max_len);
+      int32_t *ids = static_cast<int32_t *>(zeroed(n * max_len * sizeof(int32_t)));
+      int32_t *tt = static_cast<int32_t *>(zeroed(n * max_len * sizeof(int32_t)));
+      int32_t *len = static_cast<int32_t *>(zeroed(n * sizeof(int32_t)));
+      int32_t *sample = static_cast<int32_t *>(zeroed(n * sizeof(int32_t)));
+      for (size_t r = 0; r < n; r++) {
+        int32_t *row = ids + r * max_len;
+        int col = 0;
+        if (g.head) row[col++] = g.cls_id;
+        if (g.nsep) row[col++] = g.sep_id;
+        if (g.pairs && g.nsep) {
+          tt[r * max_len + col] = 1;
+          row[col++] = g.sep_id;
+        }
+        len[r] = col;
+        while (col < g.max_len) row[col++] = g.pad_id;
+        sample[r] = static_cast<int32_t>(r);
+      }
+      out->input_ids = ids;
+      out->token_type_ids = tt;
+      out->lengths = len;
+      out->sample = sample;
+      if (unit >= 0) out->offsets = static_cast<uint32_t *>(zeroed(n * max_len * 2 * sizeof(uint32_t)));
+      *n_out = n;
+      *n_samples = n;
+      return;
+    }
+    const auto t_all = wp_clock::now();
+    Context *c = get_context(v);
+    upload_text(c, utf8, nbytes);
+    const long long *d_doc_off = upload_doc_off(c, doc_off, n_docs);
+    RowsResult r;
+    rows_on_device(v, c, static_cast<const uint8_t *>(c->text_buf.p), nbytes, d_doc_off, n_docs, unit, SIZE_MAX, r);
+    check_inputs_rows(g, r.n_rows);
+    size_t cells = 0;
+    const size_t n = inputs_on_device(v, c, r, g, unit, [&](size_t rows_out) {
+      cells = rows_out * max_len;  // offsets | input_ids | token_type_ids | lengths | sample
+      const size_t offs_bytes = unit >= 0 ? cells * 2 * sizeof(uint32_t) : 0;
+      c->pad_buf.ensure(offs_bytes + (2 * cells + 2 * rows_out) * sizeof(int32_t) + 16);
+      wp_inputs o{};
+      char *base = static_cast<char *>(c->pad_buf.p);
+      o.offsets = unit >= 0 ? reinterpret_cast<uint32_t *>(base) : nullptr;
+      o.input_ids = reinterpret_cast<int32_t *>(base + offs_bytes);
+      o.token_type_ids = o.input_ids + cells;
+      o.lengths = o.token_type_ids + cells;
+      o.sample = o.lengths + rows_out;
+      return o;
+    });
+    *n_samples = r.n_rows / (g.pairs ? 2 : 1);
+    *n_out = n;
+    if (n == 0) return;
+    char *base = static_cast<char *>(c->pad_buf.p);
+    const size_t offs_bytes = unit >= 0 ? cells * 2 * sizeof(uint32_t) : 0;
+    const int32_t *d_ids = reinterpret_cast<const int32_t *>(base + offs_bytes);
+    PinnedBlock bi(cells * sizeof(int32_t)), bt(cells * sizeof(int32_t)), bl(n * sizeof(int32_t)), bs(n * sizeof(int32_t));
+    std::unique_ptr<PinnedBlock> bo;
+    WP_HIP(hipMemcpyAsync(bi.p, d_ids, cells * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    WP_HIP(hipMemcpyAsync(bt.p, d_ids + cells, cells * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    WP_HIP(hipMemcpyAsync(bl.p, d_ids + 2 * cells, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    WP_HIP(hipMemcpyAsync(bs.p, d_ids + 2 * cells + n, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (unit >= 0) {
+      bo.reset(new PinnedBlock(offs_bytes));
+      WP_HIP(hipMemcpyAsync(bo->p, base, offs_bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    WP_HIP(hipStreamSynchronize(c->stream));
+    out->input_ids = static_cast<int32_t *>(bi.release());
+    out->token_type_ids = static_cast<int32_t *>(bt.release());
+    out->lengths = static_cast<int32_t *>(bl.release());
+    out->sample = static_cast<int32_t *>(bs.release());
+    if (bo) out->offsets = static_cast<uint32_t *>(bo->release());
+    v->stats.ms_host_total = ms_since(t_all);
+  });
+}
+
+int wp_linear_encode_inputs_device(wp_vocab *v, const void *d_utf8, size_t nbytes, const int64_t *d_doc_off, size_t n_docs,
+                                   const wp_inputs_spec *spec, const wp_inputs *d_out, size_t capacity_rows, size_t *n_out,
+                                   size_t *n_samples) {
+  return guarded([&] {
+    if (!n_out || !n_samples) throw std::invalid_argument("inputs: null result pointer");
+    *n_out = 0;
+    *n_samples = 0;
+    const InputsGeom g = check_inputs_spec(spec, nbytes);
+    const int unit = spec->unit;
+    if ((reinterpret_cast<uintptr_t>(d_utf8) & 3u) != 0) throw std::invalid_argument("device text must be 4-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_doc_off) & 7u) != 0) throw std::invalid_argument("device document offsets must be 8-byte aligned");
+    if (d_doc_off) check_inputs_rows(g, n_docs);
+    if (nbytes == 0) {
+      if (d_doc_off && n_docs != 0) throw std::invalid_argument("document offsets must increase from 0 to nbytes");
+      return;
+    }
+    if (!d_out || !d_out->input_ids || !d_out->token_type_ids || !d_out->lengths || !d_out->sample || (unit >= 0 && !d_out->offsets)) {
+      throw std::invalid_argument("null output buffer");
+    }
+    if ((reinterpret_cast<uintptr_t>(d_out->offsets) & 7u) != 0) throw std::invalid_argument("the offsets buffer must be 8-byte aligned");
+    const size_t mult = g.pairs ? 2 : 1;
+    // without windows the rows say how many output rows there are: too little room is found before the encode
+    const size_t rows_cap = (g.stride >= 0 || capacity_rows > (SIZE_MAX - 1) / 2) ? SIZE_MAX : capacity_rows * mult + (mult - 1);
+    Context *c = get_context(v);
+    RowsResult r;
+    try {
+      rows_on_device(v, c, static_cast<const uint8_t *>(d_utf8), nbytes, reinterpret_cast<const long long *>(d_doc_off), n_docs, unit,
+                     rows_cap, r);
+    } catch (...) {
+      check_inputs_rows(g, r.n_rows);
+      *n_out = *n_samples = r.n_rows / mult;  // (too many rows for the caller's buffers: the count it needs)
+      throw;
+    }
+    check_inputs_rows(g, r.n_rows);
+    *n_samples = r.n_rows / mult;
+    *n_out = inputs_on_device(v, c, r, g, unit, [&](size_t rows_out) {
+      if (rows_out > capacity_rows) {
+        *n_out = rows_out;
+        throw std::invalid_argument("capacity_rows is smaller than the number of output rows");
+      }
+      return *d_out;
+    });
   });
 }
 

@@ -190,6 +190,62 @@ int wp_linear_encode_inputs_device(wp_vocab *v, const void *d_utf8, size_t nbyte
                                    const wp_inputs_spec *spec, const wp_inputs *d_out, size_t capacity_rows,
                                    size_t *n_out, size_t *n_samples);
 
+/* ---- masking (an addition: tf_text mask_language_model, HF DataCollatorForLanguageModeling / ForWholeWordMask, Encoding.word_ids()) ----
+ * The masked-language-model transform of a batch in[n_rows][max_len] of int32 ids with an optional lengths[n_rows]: what
+ * the padded / inputs calls produce, or any id batch the caller made.  lengths == NULL: every column is inside; a given
+ * length is clamped to [0, max_len].  V = wp_vocab_size, f(x) = wp_vocab_token_flags(x).  For row r, column c, x = in[r][c]:
+ *   outside(c): c >= len_r, or x < 0, or x >= V, or x equals one of cls_id, sep_id, pad_id that is >= 0
+ *   solo(c):    !outside && (f(x) & 6)                — a special or malformed token ([UNK] and its kin) is a word of its own
+ *   cont(c):    !outside && !solo && !(f(x) & 1)      — a "##" token
+ *   start(c):   !outside(c) && (!cont(c) || c == 0 || outside(c - 1) || solo(c - 1))   — a window that begins inside a word begins a word
+ *   word_ids[r][c]: -1 if outside, else (the number of start(c') for o < c' <= c) - 1, o the last outside column before c
+ *     (-1 if none): the count restarts behind every special, so sequence B of a pair starts at 0 again (HF word_ids())
+ *   w(c): the last c' <= c with start(c');  the selection unit u(c) is w(c) with whole_word == 1, c with whole_word == 0;
+ *     a unit is selectable when !solo(u(c))
+ *   selected(c): !outside(c) && selectable && draw(seed, row_base + r, u(c), 0) < select_q32
+ *   a selected c: labels = x;  t = draw(seed, row_base + r, c, 1);  t < mask_q32: out = mask_id;  else
+ *     t < mask_q32 + random_q32: out = (draw(seed, row_base + r, c, 2) * V) >> 32;  else out = x
+ *   any other c: out = x, labels = ignore_id
+ * Every cell of the n_rows rows is written, padding included; nothing behind row n_rows is.  `out` may be the buffer
+ * `in` is (a cell is read before it is written, and no other cell is read for it).
+ * select_q32, mask_q32, random_q32: probabilities times 2^32, in [0, 2^32] (2^32: always; a draw is a 32-bit value and
+ * the comparison is made in 64 bits); mask_q32 + random_q32 <= 2^32.  The draw is part of the contract — the same
+ * seed gives the same batch on every device and in every release.  All arithmetic mod 2^64, G = 0x9E3779B97F4A7C15:
+ *   mix(x): x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31
+ *   draw(seed, row, col, stream) = mix(mix(seed + G * (row + 1)) + G * (4 * col + stream + 1)) >> 32
+ * row_base: the row number of row 0, so that a batch masked in slices gives the rows the whole batch would give.
+ * The word-ids calls read max_len, cls_id, sep_id and pad_id of the spec only.
+ * WP_ERR_ARG (host entry points: before a device is touched): spec NULL, a required pointer NULL, max_len < 1,
+ * whole_word not 0 / 1, a q32 above 2^32, mask_q32 + random_q32 > 2^32, mask_id < 0 (mask calls).  WP_ERR_TOO_LARGE:
+ * n_rows > INT32_MAX, or n_rows * max_len overflows.  n_rows == 0 needs no device and gives NULL blocks.  The device
+ * calls run on the handle's device and stream, wait once (for the counters) and return when the batch is complete. */
+typedef struct { int32_t max_len, cls_id, sep_id, pad_id, mask_id, ignore_id, whole_word, reserved;
+                 uint64_t select_q32, mask_q32, random_q32, seed, row_base; } wp_mask_spec;
+/* host ids in; word_ids [n_rows, max_len] out as a block (free with wp_free) */
+int wp_word_ids(wp_vocab *v, const int32_t *input_ids, const int32_t *lengths, size_t n_rows, const wp_mask_spec *spec,
+                int32_t **word_ids);
+/* device ids in, a caller-owned device buffer of n_rows * max_len int32 out */
+int wp_word_ids_device(wp_vocab *v, const int32_t *d_input_ids, const int32_t *d_lengths, size_t n_rows,
+                       const wp_mask_spec *spec, int32_t *d_word_ids);
+/* host ids in; masked, labels and (word_ids != NULL) word_ids [n_rows, max_len] out as blocks (free each with wp_free) */
+int wp_mlm_mask(wp_vocab *v, const int32_t *input_ids, const int32_t *lengths, size_t n_rows, const wp_mask_spec *spec,
+                int32_t **masked, int32_t **labels, int32_t **word_ids);
+/* device ids in, caller-owned device buffers out (d_masked may be d_input_ids; d_word_ids may be NULL: not wanted) */
+int wp_mlm_mask_device(wp_vocab *v, const int32_t *d_input_ids, const int32_t *d_lengths, size_t n_rows,
+                       const wp_mask_spec *spec, int32_t *d_masked, int32_t *d_labels, int32_t *d_word_ids);
+/* The statistics of the last mask or word-ids call, in a struct of its own (wp_stats keeps its size).  n_random and
+ * n_kept count the branch taken, not whether the id changed.  A word-ids call fills n_rows and n_words only.  The other
+ * statistics (wp_stats, wp_inputs_stats, ...) keep what the last encode left: a mask call runs no encode. */
+typedef struct {
+  int64_t n_rows;            /* rows of the call; -1: the last call was no mask call                                      */
+  int64_t n_words;           /* cells with start(c)                                                                       */
+  int64_t n_selected;        /* selected cells                                                                            */
+  int64_t n_selected_units;  /* selected units: words with whole_word == 1, cells with 0                                  */
+  int64_t n_masked, n_random, n_kept; /* selected cells by the branch they took                                            */
+  int32_t whole_word, reserved; /* of the call's wp_mask_spec                                                             */
+} wp_mask_stats;
+int wp_get_mask_stats(const wp_vocab *v, wp_mask_stats *out);
+
 /* The same call sharded over several GPUs of the node, behind the boundary: the reference's own
  * precedent is the in-library chunking at whitespace of linear.cpp:283-299 (thread chunks) and
  * linear.cpp:355-367 (encodeExternal batches).  The text is cut at ASCII whitespace into one shard

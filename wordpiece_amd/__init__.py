@@ -45,6 +45,7 @@ ABI_SYMBOLS = [
     "wp_linear_encode_rows", "wp_linear_encode_rows_device", "wp_linear_encode_padded", "wp_linear_encode_padded_device",
     "wp_normalize_cp", "wp_normalize_device", "wp_normalize", "wp_get_norm_stats", "wp_get_walk_stats",
     "wp_linear_encode_inputs", "wp_linear_encode_inputs_device", "wp_get_inputs_stats",
+    "wp_word_ids", "wp_word_ids_device", "wp_mlm_mask", "wp_mlm_mask_device", "wp_get_mask_stats",
 ]
 
 
@@ -106,6 +107,21 @@ class InputsStats(C.Structure):
                 ("pairs", C.c_int32), ("truncation", C.c_int32), ("stride", C.c_int32), ("reserved", C.c_int32)]
 
 
+class MaskSpec(C.Structure):
+    """wp_mask_spec: the arguments of a mask or word-ids call (probabilities as q32: p * 2^32, see q32())."""
+    _fields_ = [("max_len", C.c_int32), ("cls_id", C.c_int32), ("sep_id", C.c_int32), ("pad_id", C.c_int32),
+                ("mask_id", C.c_int32), ("ignore_id", C.c_int32), ("whole_word", C.c_int32), ("reserved", C.c_int32),
+                ("select_q32", C.c_uint64), ("mask_q32", C.c_uint64), ("random_q32", C.c_uint64), ("seed", C.c_uint64),
+                ("row_base", C.c_uint64)]
+
+
+class MaskStats(C.Structure):
+    """wp_mask_stats: the statistics of the last mask or word-ids call (Vocab.mask_stats())."""
+    _fields_ = [("n_rows", C.c_int64), ("n_words", C.c_int64), ("n_selected", C.c_int64), ("n_selected_units", C.c_int64),
+                ("n_masked", C.c_int64), ("n_random", C.c_int64), ("n_kept", C.c_int64), ("whole_word", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 _TEXT_SOURCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t))
 _IDS_SINK = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.c_size_t)
 
@@ -155,6 +171,12 @@ def lib():
                                                      C.POINTER(Inputs), C.c_size_t, C.POINTER(C.c_size_t),
                                                      C.POINTER(C.c_size_t)]
         L.wp_get_inputs_stats.argtypes = [vp, C.POINTER(InputsStats)]
+        L.wp_word_ids.argtypes = [vp, i32p, i32p, C.c_size_t, C.POINTER(MaskSpec), C.POINTER(i32p)]
+        L.wp_word_ids_device.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(MaskSpec), vp]
+        L.wp_mlm_mask.argtypes = [vp, i32p, i32p, C.c_size_t, C.POINTER(MaskSpec), C.POINTER(i32p), C.POINTER(i32p),
+                                  C.POINTER(i32p)]
+        L.wp_mlm_mask_device.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(MaskSpec), vp, vp, vp]
+        L.wp_get_mask_stats.argtypes = [vp, C.POINTER(MaskStats)]
         L.wp_linear_encode_multi.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.POINTER(i32p),
                                              C.POINTER(C.c_size_t)]
         L.wp_reserve.argtypes = [vp, C.c_size_t]
@@ -209,6 +231,7 @@ class Vocab:
                 off[1:] = np.cumsum([len(w) for w in ls])
             _check(lib().wp_vocab_create_packed(b"".join(ls), off.ctypes.data_as(C.POINTER(C.c_int64)), len(ls),
                                                 C.byref(self._h)))
+        self._device = None if device is None else int(device)  # (None: the device that is current at the first call)
         if device is not None:
             self.set_option(WP_OPT_DEVICE, device)
         if normalize:  # WP_NORM_* flags: every encode of this handle normalises its text on the device first
@@ -237,6 +260,8 @@ class Vocab:
         _check(lib().wp_set_option(self._h, opt, int(value)))
         if opt == WP_OPT_NORMALIZE:
             self._normalize = int(value)
+        if opt == WP_OPT_DEVICE:
+            self._device = int(value)
 
     def normalize(self, text, flags=None):
         """The normalisation pre-pass alone (wp_normalize): host UTF-8 bytes/str -> the normalised UTF-8 as bytes.
@@ -531,6 +556,94 @@ class Vocab:
             break
         return {k: t[k][:rows.value] for k in keys}
 
+    def mask_stats(self):
+        """wp_mask_stats of the last call as a dict (n_rows -1: it was no mask or word-ids call)."""
+        s = MaskStats()
+        _check(lib().wp_get_mask_stats(self._h, C.byref(s)))
+        return {k: int(getattr(s, k)) for k, _ in s._fields_ if k != "reserved"}
+
+    def word_ids(self, input_ids, lengths=None, cls_id=None, sep_id=None, pad_id=None):
+        """The word index of every cell of an id batch (wp_word_ids): input_ids int32 [n_rows, max_len] (and lengths
+        [n_rows]) -> numpy int32 [n_rows, max_len], -1 for specials, padding and ids outside the vocabulary; the count
+        restarts behind every special (HF Encoding.word_ids())."""
+        ids, lens = _mask_batch(input_ids, lengths)
+        spec = MaskSpec(max_len=ids.shape[1], cls_id=_special(cls_id), sep_id=_special(sep_id), pad_id=_special(pad_id))
+        out = C.POINTER(C.c_int32)()
+        _check(lib().wp_word_ids(self._h, _i32_ptr(ids), _i32_ptr(lens), ids.shape[0], C.byref(spec), C.byref(out)))
+        return _adopt_block(out, ids.shape) if ids.shape[0] else np.zeros(ids.shape, np.int32)
+
+    def mask_inputs(self, input_ids, lengths=None, mask_id=None, prob=0.15, mask_share=0.8, random_share=0.1,
+                    whole_word=True, seed=0, row_base=0, ignore_id=-100, cls_id=None, sep_id=None, pad_id=None,
+                    word_ids=False):
+        """The masked-language-model transform of an id batch (wp_mlm_mask): input_ids int32 [n_rows, max_len] (and
+        lengths [n_rows]) -> a dict of numpy int32 arrays of that shape: input_ids (masked), labels (ignore_id where
+        nothing is to be predicted) and, with word_ids=True, word_ids.  About `prob` of the cells are selected, whole
+        words at a time (whole_word=False: cell by cell); of those mask_share become mask_id, random_share a uniform
+        id of the vocabulary, the rest stay.  The same seed gives the same batch; row_base is the row number of row 0
+        (a slice of a batch gives the rows of the whole batch).  cls_id / sep_id / pad_id: never selected, and words
+        do not run across them."""
+        ids, lens = _mask_batch(input_ids, lengths)
+        spec = _mask_spec(ids.shape[1], mask_id, prob, mask_share, random_share, whole_word, seed, row_base, ignore_id, cls_id,
+                          sep_id, pad_id)
+        i32p = C.POINTER(C.c_int32)
+        masked, labels, wids = i32p(), i32p(), i32p()
+        _check(lib().wp_mlm_mask(self._h, _i32_ptr(ids), _i32_ptr(lens), ids.shape[0], C.byref(spec), C.byref(masked),
+                                 C.byref(labels), C.byref(wids) if word_ids else None))
+        if ids.shape[0] == 0:
+            return {k: np.zeros(ids.shape, np.int32) for k in ["input_ids", "labels"] + (["word_ids"] if word_ids else [])}
+        res = {"input_ids": _adopt_block(masked, ids.shape), "labels": _adopt_block(labels, ids.shape)}
+        if word_ids:
+            res["word_ids"] = _adopt_block(wids, ids.shape)
+        return res
+
+    def _mask_tensor_args(self, input_ids, lengths):
+        import torch
+        if isinstance(input_ids, dict):  # what encode_inputs_tensor returns
+            if lengths is None:
+                lengths = input_ids.get("lengths")
+            input_ids = input_ids["input_ids"]
+        if input_ids.dtype != torch.int32 or not input_ids.is_cuda or not input_ids.is_contiguous() or input_ids.dim() != 2:
+            raise WordPieceError("a mask call on tensors needs a contiguous int32 CUDA/HIP tensor [n_rows, max_len]")
+        if lengths is not None and (lengths.dtype != torch.int32 or lengths.device != input_ids.device or
+                                    not lengths.is_contiguous() or lengths.shape != (input_ids.shape[0],)):
+            raise WordPieceError("lengths must be a contiguous int32 tensor [n_rows] on the device of input_ids")
+        if self._device is not None and input_ids.device.index != self._device:  # (raw pointers go to the handle's device)
+            raise WordPieceError("the tensors lie on %s, the handle on device %d" % (input_ids.device, self._device))
+        return input_ids, lengths
+
+    def word_ids_tensor(self, input_ids, lengths=None, cls_id=None, sep_id=None, pad_id=None):
+        """word_ids for an int32 tensor [n_rows, max_len] on this handle's GPU (or the dict encode_inputs_tensor returns)
+        -> an int32 tensor there (wp_word_ids_device); nothing leaves the device."""
+        import torch
+        ids, lens = self._mask_tensor_args(input_ids, lengths)
+        spec = MaskSpec(max_len=ids.shape[1], cls_id=_special(cls_id), sep_id=_special(sep_id), pad_id=_special(pad_id))
+        out = torch.empty_like(ids)
+        torch.cuda.current_stream(ids.device).synchronize()  # the library runs on its own HIP streams
+        _check(lib().wp_word_ids_device(self._h, C.c_void_p(ids.data_ptr()), None if lens is None else C.c_void_p(lens.data_ptr()),
+                                        ids.shape[0], C.byref(spec), C.c_void_p(out.data_ptr())))
+        return out
+
+    def mask_inputs_tensor(self, input_ids, lengths=None, mask_id=None, prob=0.15, mask_share=0.8, random_share=0.1,
+                           whole_word=True, seed=0, row_base=0, ignore_id=-100, cls_id=None, sep_id=None, pad_id=None,
+                           word_ids=False, in_place=False):
+        """mask_inputs for an int32 tensor [n_rows, max_len] on this handle's GPU, or the dict encode_inputs_tensor
+        returns (its lengths are used unless others are given) -> a dict of int32 tensors there: input_ids, labels[,
+        word_ids] (wp_mlm_mask_device); nothing leaves the device.  in_place=True: the masked ids overwrite the tensor
+        that was passed (which is then also the dict's input_ids)."""
+        import torch
+        ids, lens = self._mask_tensor_args(input_ids, lengths)
+        spec = _mask_spec(ids.shape[1], mask_id, prob, mask_share, random_share, whole_word, seed, row_base, ignore_id, cls_id,
+                          sep_id, pad_id)
+        res = {"input_ids": ids if in_place else torch.empty_like(ids), "labels": torch.empty_like(ids)}
+        if word_ids:
+            res["word_ids"] = torch.empty_like(ids)
+        torch.cuda.current_stream(ids.device).synchronize()  # the library runs on its own HIP streams
+        _check(lib().wp_mlm_mask_device(self._h, C.c_void_p(ids.data_ptr()), None if lens is None else C.c_void_p(lens.data_ptr()),
+                                        ids.shape[0], C.byref(spec), C.c_void_p(res["input_ids"].data_ptr()),
+                                        C.c_void_p(res["labels"].data_ptr()),
+                                        C.c_void_p(res["word_ids"].data_ptr()) if word_ids else None))
+        return res
+
     def fast_encode(self, text):
         """word_piece::fast::encode on the GPU (wp_fast_encode): host bytes/str -> numpy int32 ids."""
         b = _bytes(text)
@@ -710,6 +823,38 @@ def _docs_arg(docs, text, doc_offsets):
 
 def _i64_ptr(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def q32(p):
+    """A share p in [0, 1] as the C ABI takes it: min(floor(p * 2^32), 2^32)."""
+    return min(int(p * 4294967296.0), 1 << 32)
+
+
+def _mask_batch(input_ids, lengths):
+    ids = np.ascontiguousarray(input_ids, dtype=np.int32)
+    if ids.ndim != 2:
+        raise WordPieceError("input_ids must be a 2-d array [n_rows, max_len]")
+    lens = None
+    if lengths is not None:
+        lens = np.ascontiguousarray(lengths, dtype=np.int32)
+        if lens.shape != (ids.shape[0],):
+            raise WordPieceError("lengths must be a 1-d array of n_rows entries")
+    return ids, lens
+
+
+def _i32_ptr(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _mask_spec(max_len, mask_id, prob, mask_share, random_share, whole_word, seed, row_base, ignore_id, cls_id, sep_id, pad_id):
+    if mask_id is None:
+        raise WordPieceError("mask_id is required")
+    for name, p in (("prob", prob), ("mask_share", mask_share), ("random_share", random_share)):
+        if not 0.0 <= p <= 1.0:
+            raise WordPieceError("%s must lie in [0, 1], not %r" % (name, p))
+    return MaskSpec(int(max_len), _special(cls_id), _special(sep_id), _special(pad_id), int(mask_id), int(ignore_id),
+                    int(whole_word), 0, q32(prob), q32(mask_share), q32(random_share), int(seed) & (2 ** 64 - 1),
+                    int(row_base) & (2 ** 64 - 1))
 
 
 def _special(i):

@@ -47,7 +47,8 @@ enum BoundSite {
   // blanks were dropped, or a multiset unlike the kept keys of the unsorted array; linear_path.h, sorted_check_kernel)
   kSiteSortOrder = 8,
   kSiteInputs = 9,  // model inputs: the gathers of the packer from the ids and their spans (inputs.h)
-  kBoundSites = 10
+  kSiteMask = 10,   // masking: the lookup of an id's class byte (mask.h)
+  kBoundSites = 11
 };
 #ifdef WP_DEBUG_BOUNDS
 __device__ unsigned int g_wp_oob[kBoundSites];

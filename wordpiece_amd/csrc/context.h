@@ -138,7 +138,8 @@ static int bit_length(uint64_t v) {
   return b;
 }
 
-constexpr int kScalars = 32;
+constexpr int kScalars = 48;
+constexpr int kScalarMask = 32;  // d_scalars words 32..43: the six 64-bit counters of a mask call (mask.h, MaskCounter)
 constexpr int kScalarCand = 24;  // d_scalars word: entries of the keys-only round 0's candidate list (linear_path.h)
 constexpr int kScalarKept = 25;  // d_scalars word: suffixes the keys-only round 0 kept (not blank-start; radix_sort.h, RadixDrop)
 // documents calls (rows.h): lines of the text / boundaries of explicit rows that fail the check / rows a padded call cut
@@ -175,6 +176,7 @@ struct Context {
   uint32_t *d_lt_chain_len = nullptr, *d_lt_chain_off = nullptr, *d_lt_child_begin = nullptr, *d_lt_child_cp = nullptr,
            *d_lt_child_node = nullptr, *d_elig_node = nullptr, *d_elig_subtree = nullptr;  // the token trie (vocab.h, trie.h)
   int32_t *d_elig_id = nullptr, *d_tok_len = nullptr;
+  uint8_t *d_tok_class = nullptr;  // wp_vocab_token_flags of every id, one byte each: uploaded by the first mask call (mask.h)
   unsigned long long *d_trie_key = nullptr;  // the fast path's token trie (vocab.h)
   uint32_t *d_trie_child = nullptr;
   int32_t *d_trie_id = nullptr;
@@ -257,6 +259,8 @@ struct EncodeStats : wp_stats {
   wp_walk_stats walk;
   wp_inputs_stats inputs;  // wp_get_inputs_stats: filled by an inputs call (inputs_call 1), zero otherwise
   int32_t inputs_call;
+  wp_mask_stats mask;  // wp_get_mask_stats: filled by a mask or word-ids call (mask_call 1), zero otherwise
+  int32_t mask_call;
 };
 
 struct wp_vocab {
@@ -282,6 +286,7 @@ static void free_vocab_tables(Context *c) {
   for (void **p : {reinterpret_cast<void **>(&c->d_stream), reinterpret_cast<void **>(&c->d_elig_start),
                    reinterpret_cast<void **>(&c->d_elig_info), reinterpret_cast<void **>(&c->d_soft),
                    reinterpret_cast<void **>(&c->d_elig_id), reinterpret_cast<void **>(&c->d_tok_len),
+                   reinterpret_cast<void **>(&c->d_tok_class),
                    reinterpret_cast<void **>(&c->d_trie_key), reinterpret_cast<void **>(&c->d_trie_child),
                    reinterpret_cast<void **>(&c->d_trie_id), reinterpret_cast<void **>(&c->d_vocab_word_idx),
                    reinterpret_cast<void **>(&c->d_vocab_word_bits), reinterpret_cast<void **>(&c->d_cls_bmp),

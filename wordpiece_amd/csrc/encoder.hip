@@ -24,6 +24,7 @@
 #include "format.h"
 #include "inputs.h"
 #include "linear_path.h"
+#include "mask.h"
 
 
 wp_vocab::~wp_vocab() {
@@ -990,6 +991,218 @@ int wp_linear_encode_padded_device(wp_vocab *v, const void *d_utf8, size_t nbyte
     }
     pack_on_device(v, c, r, max_len, cls_id, sep_id, pad_id, d_input_ids, d_lengths);
     *n_rows = r.n_rows;
+  });
+}
+
+}  // extern "C"
+
+// ---- masking (include/wordpiece_amd.h, section "masking"; kernel: mask.h) --------------------------------------------
+namespace {
+constexpr unsigned long long kQ32One = 1ull << 32;
+
+// every argument rule of a mask (mask_call) or word-ids call that needs no device
+MaskGeom check_mask_spec(const wp_vocab *v, const wp_mask_spec *spec, size_t n_rows, bool mask_call) {
+  if (!spec) throw std::invalid_argument("mask: spec is NULL");
+  if (spec->max_len < 1) throw std::invalid_argument("mask: max_len must be at least 1");
+  MaskGeom g{};
+  g.max_len = spec->max_len;
+  g.cls_id = spec->cls_id;
+  g.sep_id = spec->sep_id;
+  g.pad_id = spec->pad_id;
+  g.vocab_size = static_cast<long long>(v->hv.tokens.size());
+  if (mask_call) {
+    if (spec->whole_word != 0 && spec->whole_word != 1) throw std::invalid_argument("mask: whole_word must be 0 or 1");
+    if (spec->select_q32 > kQ32One) throw std::invalid_argument("mask: select_q32 must be at most 2^32");
+    if (spec->mask_q32 > kQ32One) throw std::invalid_argument("mask: mask_q32 must be at most 2^32");
+    if (spec->random_q32 > kQ32One) throw std::invalid_argument("mask: random_q32 must be at most 2^32");
+    if (spec->mask_q32 + spec->random_q32 > kQ32One) throw std::invalid_argument("mask: mask_q32 + random_q32 must be at most 2^32");
+    if (spec->mask_id < 0) throw std::invalid_argument("mask: mask_id must be at least 0");
+    g.mask_id = spec->mask_id;
+    g.ignore_id = spec->ignore_id;
+    g.whole_word = spec->whole_word;
+    g.select_q32 = spec->select_q32;
+    g.mask_q32 = spec->mask_q32;
+    g.random_q32 = spec->random_q32;
+    g.seed = spec->seed;
+    g.row_base = spec->row_base;
+  }
+  if (n_rows > static_cast<size_t>(INT32_MAX)) throw std::length_error("mask: more rows than INT32_MAX");
+  if (n_rows > SIZE_MAX / sizeof(int32_t) / static_cast<size_t>(spec->max_len)) {
+    throw std::length_error("mask: n_rows * max_len is too large");
+  }
+  return g;
+}
+
+// the statistics of a mask or word-ids call before its counters are known (all there is to say of a call without rows)
+wp_mask_stats &begin_mask_stats(wp_vocab *v, size_t n_rows, int whole_word) {
+  v->stats.mask_call = 1;
+  v->stats.mask = wp_mask_stats{};
+  v->stats.mask.n_rows = static_cast<int64_t>(n_rows);
+  v->stats.mask.whole_word = whole_word;
+  return v->stats.mask;
+}
+
+// One launch of mask_kernel over device buffers on c's stream, one wait (for the counters), the statistics of the call.
+// d_masked == nullptr: the word-ids form.
+void mask_on_device(wp_vocab *v, Context *c, const int32_t *d_in, const int32_t *d_lengths, size_t n_rows, const MaskGeom &g,
+                    int32_t *d_masked, int32_t *d_labels, int32_t *d_word_ids) {
+  const bool mask_call = d_masked != nullptr;
+  wp_mask_stats &ms = begin_mask_stats(v, n_rows, mask_call ? g.whole_word : 0);
+  if (n_rows == 0) return;
+  hipStream_t st = c->stream;
+  if (!c->d_tok_class) {  // one byte per id: wp_vocab_token_flags
+    std::vector<uint8_t> cls(v->hv.tokens.size());
+    for (size_t i = 0; i < cls.size(); i++) {
+      const HostToken &t = v->hv.tokens[i];
+      cls[i] = static_cast<uint8_t>((t.is_prefix ? 1 : 0) | (t.is_special ? 2 : 0) | (t.is_malformed ? 4 : 0));
+    }
+    c->d_tok_class = upload(cls, st);
+    WP_HIP(hipStreamSynchronize(st));  // cls is a local
+  }
+  unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarMask);
+  WP_HIP(hipMemsetAsync(d_cnt, 0, kMaskCounters * sizeof(unsigned long long), st));
+  int lanes = 4;
+  while (lanes < kWave && lanes < g.max_len) lanes *= 2;
+  const size_t n_blocks = (n_rows + static_cast<size_t>(kBlock / lanes) - 1) / static_cast<size_t>(kBlock / lanes);
+  const dim3 grid(static_cast<unsigned>(std::min<size_t>(n_blocks, kMaskMaxGrid))), block(kBlock);
+  if (!mask_call) {
+    hipLaunchKernelGGL((mask_kernel<false, true>), grid, block, 0, st, d_in, d_lengths, n_rows, n_blocks, g, lanes,
+                       c->d_tok_class, d_masked, d_labels,
+                       d_word_ids, d_cnt);
+  } else if (d_word_ids) {
+    hipLaunchKernelGGL((mask_kernel<true, true>), grid, block, 0, st, d_in, d_lengths, n_rows, n_blocks, g, lanes,
+                       c->d_tok_class, d_masked, d_labels,
+                       d_word_ids, d_cnt);
+  } else {
+    hipLaunchKernelGGL((mask_kernel<true, false>), grid, block, 0, st, d_in, d_lengths, n_rows, n_blocks, g, lanes,
+                       c->d_tok_class, d_masked, d_labels,
+                       d_word_ids, d_cnt);
+  }
+  WP_LAUNCH_CHECK();
+  unsigned long long *h_cnt = reinterpret_cast<unsigned long long *>(c->h_scalars + kScalarMask);
+  WP_HIP(hipMemcpyAsync(h_cnt, d_cnt, kMaskCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  WP_HIP(hipStreamSynchronize(st));
+#ifdef WP_DEBUG_BOUNDS
+  {
+    unsigned int oob = 0;
+    WP_HIP(hipMemcpyFromSymbol(&oob, HIP_SYMBOL(g_wp_oob), sizeof(oob), kSiteMask * sizeof(unsigned int)));
+    if (oob != 0) {
+      const unsigned int zero = 0;
+      WP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_wp_oob), &zero, sizeof(zero), kSiteMask * sizeof(unsigned int)));
+      throw HipError("debug bounds: masking: " + std::to_string(oob) + " class lookups outside the vocabulary skipped");
+    }
+  }
+#endif
+  ms.n_words = static_cast<int64_t>(h_cnt[kMaskWords]);
+  ms.n_selected = static_cast<int64_t>(h_cnt[kMaskSelected]);
+  ms.n_selected_units = static_cast<int64_t>(h_cnt[kMaskUnits]);
+  ms.n_masked = static_cast<int64_t>(h_cnt[kMaskMasked]);
+  ms.n_random = static_cast<int64_t>(h_cnt[kMaskRandom]);
+  ms.n_kept = static_cast<int64_t>(h_cnt[kMaskKept]);
+}
+
+// the host entry points: ids (and lengths) up, one launch, 1..3 blocks of n_rows * max_len int32 down
+void mask_from_host(wp_vocab *v, const int32_t *input_ids, const int32_t *lengths, size_t n_rows, const MaskGeom &g, int32_t **masked,
+                    int32_t **labels, int32_t **word_ids) {
+  const size_t cells = n_rows * static_cast<size_t>(g.max_len);
+  Context *c = get_context(v);
+  const int n_out = (masked ? 2 : 0) + (word_ids ? 1 : 0);
+  // ids | outputs | lengths
+  c->pad_buf.ensure((cells * (1 + static_cast<size_t>(n_out)) + n_rows) * sizeof(int32_t) + 16);
+  int32_t *d_in = static_cast<int32_t *>(c->pad_buf.p);
+  int32_t *d_masked = masked ? d_in + cells : nullptr, *d_labels = masked ? d_in + 2 * cells : nullptr;
+  int32_t *d_wid = word_ids ? d_in + (masked ? 3 : 1) * cells : nullptr;
+  int32_t *d_len = lengths ? d_in + (1 + static_cast<size_t>(n_out)) * cells : nullptr;
+  WP_HIP(hipMemcpyAsync(d_in, input_ids, cells * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  if (lengths) WP_HIP(hipMemcpyAsync(d_len, lengths, n_rows * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  mask_on_device(v, c, d_in, d_len, n_rows, g, d_masked, d_labels, d_wid);
+  std::unique_ptr<PinnedBlock> bm, bl, bw;
+  if (masked) {
+    bm.reset(new PinnedBlock(cells * sizeof(int32_t)));
+    bl.reset(new PinnedBlock(cells * sizeof(int32_t)));
+    WP_HIP(hipMemcpyAsync(bm->p, d_masked, cells * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    WP_HIP(hipMemcpyAsync(bl->p, d_labels, cells * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  }
+  if (word_ids) {
+    bw.reset(new PinnedBlock(cells * sizeof(int32_t)));
+    WP_HIP(hipMemcpyAsync(bw->p, d_wid, cells * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  }
+  WP_HIP(hipStreamSynchronize(c->stream));
+  if (masked) {
+    *masked = static_cast<int32_t *>(bm->release());
+    *labels = static_cast<int32_t *>(bl->release());
+  }
+  if (word_ids) *word_ids = static_cast<int32_t *>(bw->release());
+}
+}  // namespace
+
+extern "C" {
+
+int wp_get_mask_stats(const wp_vocab *v, wp_mask_stats *out) {
+  *out = v->stats.mask;
+  if (!v->stats.mask_call) out->n_rows = -1;
+  return WP_OK;
+}
+
+int wp_word_ids(wp_vocab *v, const int32_t *input_ids, const int32_t *lengths, size_t n_rows, const wp_mask_spec *spec,
+                int32_t **word_ids) {
+  return guarded([&] {
+    if (!word_ids) throw std::invalid_argument("mask: word_ids is NULL");
+    *word_ids = nullptr;
+    const MaskGeom g = check_mask_spec(v, spec, n_rows, false);
+    if (n_rows != 0 && !input_ids) throw std::invalid_argument("mask: input_ids is NULL");
+    if (n_rows == 0) {
+      begin_mask_stats(v, 0, 0);
+      return;
+    }
+    mask_from_host(v, input_ids, lengths, n_rows, g, nullptr, nullptr, word_ids);
+  });
+}
+
+int wp_word_ids_device(wp_vocab *v, const int32_t *d_input_ids, const int32_t *d_lengths, size_t n_rows,
+                       const wp_mask_spec *spec, int32_t *d_word_ids) {
+  return guarded([&] {
+    const MaskGeom g = check_mask_spec(v, spec, n_rows, false);
+    if (n_rows != 0 && !d_input_ids) throw std::invalid_argument("mask: input_ids is NULL");
+    if (n_rows != 0 && !d_word_ids) throw std::invalid_argument("mask: word_ids is NULL");
+    if (n_rows == 0) {
+      begin_mask_stats(v, 0, 0);
+      return;
+    }
+    mask_on_device(v, get_context(v), d_input_ids, d_lengths, n_rows, g, nullptr, nullptr, d_word_ids);
+  });
+}
+
+int wp_mlm_mask(wp_vocab *v, const int32_t *input_ids, const int32_t *lengths, size_t n_rows, const wp_mask_spec *spec,
+                int32_t **masked, int32_t **labels, int32_t **word_ids) {
+  return guarded([&] {
+    if (!masked) throw std::invalid_argument("mask: masked is NULL");
+    if (!labels) throw std::invalid_argument("mask: labels is NULL");
+    *masked = nullptr;
+    *labels = nullptr;
+    if (word_ids) *word_ids = nullptr;
+    const MaskGeom g = check_mask_spec(v, spec, n_rows, true);
+    if (n_rows != 0 && !input_ids) throw std::invalid_argument("mask: input_ids is NULL");
+    if (n_rows == 0) {
+      begin_mask_stats(v, 0, g.whole_word);
+      return;
+    }
+    mask_from_host(v, input_ids, lengths, n_rows, g, masked, labels, word_ids);
+  });
+}
+
+int wp_mlm_mask_device(wp_vocab *v, const int32_t *d_input_ids, const int32_t *d_lengths, size_t n_rows,
+                       const wp_mask_spec *spec, int32_t *d_masked, int32_t *d_labels, int32_t *d_word_ids) {
+  return guarded([&] {
+    const MaskGeom g = check_mask_spec(v, spec, n_rows, true);
+    if (n_rows != 0 && !d_input_ids) throw std::invalid_argument("mask: input_ids is NULL");
+    if (n_rows != 0 && !d_masked) throw std::invalid_argument("mask: masked is NULL");
+    if (n_rows != 0 && !d_labels) throw std::invalid_argument("mask: labels is NULL");
+    if (n_rows == 0) {
+      begin_mask_stats(v, 0, g.whole_word);
+      return;
+    }
+    mask_on_device(v, get_context(v), d_input_ids, d_lengths, n_rows, g, d_masked, d_labels, d_word_ids);
   });
 }
 

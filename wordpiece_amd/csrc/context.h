@@ -1,6 +1,7 @@
 // context.h — what a vocabulary handle owns on a device: streams, vocabulary tables, bump arenas, the pool of parked
 // contexts (the C ABI itself is in encoder.hip; the device path in linear_path.h and fast_path.h).
 #pragma once
+#include <array>
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -55,6 +56,14 @@ struct DeviceBuffer {
     cap = 0;
   }
 };
+
+// A text in device memory.  The decoder reads 16 bytes at a time and ahead of the end of the text: the buffer of a text of
+// `len` bytes has room for text_room(len), and holds 32 zero bytes from len & ~15 on (queued in front of the copy of the
+// text, which overwrites the first len & 15 of them).
+static size_t text_room(size_t len) { return len + 64; }
+static void zero_text_tail(void *d_text, size_t len, hipStream_t st) {
+  WP_HIP(hipMemsetAsync(static_cast<char *>(d_text) + (len & ~static_cast<size_t>(15)), 0, 32, st));
+}
 
 // Guard zones (WP_OPT_ARENA_GUARD / env WP_ARENA_GUARD=1, a debugging aid): every arena allocation is
 // followed by kGuardBytes of a fixed pattern; after the encode a kernel checks that every zone is
@@ -138,15 +147,82 @@ static int bit_length(uint64_t v) {
   return b;
 }
 
+// ---- the device scalar block ----------------------------------------------------------------------------------------
+// c->d_scalars: kScalars 32-bit words that kernels and scans leave their totals in; c->h_scalars: the pinned mirror the
+// host reads them from.  Every word has a name here and nowhere else; no call site names a number.  An encode clears
+// the whole block when it starts (and the pre-pass of WP_OPT_NORMALIZE in front of it does the same, see below).
 constexpr int kScalars = 48;
-constexpr int kScalarMask = 32;  // d_scalars words 32..43: the six 64-bit counters of a mask call (mask.h, MaskCounter)
-constexpr int kScalarCand = 24;  // d_scalars word: entries of the keys-only round 0's candidate list (linear_path.h)
-constexpr int kScalarKept = 25;  // d_scalars word: suffixes the keys-only round 0 kept (not blank-start; radix_sort.h, RadixDrop)
+constexpr int kScalarCps = 0;       // code points of the text, 32 bits: the decode scan (linear, fast) -> host
+constexpr int kScalarAlphabet = 1;  // alphabet size: alphabet_prefix_kernel -> host
+constexpr int kScalarInvalid = 2;   // invalid sequences, 64 bits (words 2, 3): decode_count_kernel / norm_count_kernel -> host
+// The active list of the refinement (linear_path.h).  The kernels are given d_scalars + kScalarList (needed_list_*,
+// group_starts, trie and sort kernels), + kScalarListGroups or + kScalarListLargeGroups (large_groups_*) and index from
+// there; NeededList takes words 0, 1 of the block as one 64-bit word, large_groups_kernel words 2, 3.
+constexpr int kScalarList = 4;
+constexpr int kScalarListEntries = kScalarList + 0;       // entries of the list -> host after every round
+constexpr int kScalarListGroups = kScalarList + 1;        // its groups -> host (trie round)
+constexpr int kScalarListLargeGroups = kScalarList + 2;   // groups too large for the LDS sort: classify_groups -> host
+constexpr int kScalarListLargeEntries = kScalarList + 3;  // their entries
+constexpr int kScalarListWanted = 8;  // the length the needed list asked for: needed_list_clamp_kernel -> host (ListOverflow)
+constexpr int kScalarIds = 9;         // number of ids: the emit scan (linear, fast) -> host
+constexpr int kScalarAnchors = 10;    // number of anchors: the anchor scan -> the walk kernels and the host
+constexpr int kScalarAnchorGap = 11;  // largest anchor gap: anchor_gap kernels -> host
+constexpr int kScalarLongWords = 12;  // long words: long_word_collect kernels -> host
+constexpr int kScalarWideWords = 13;  // wide words: wide_collect / walk_wide kernels -> host (cleared only when that branch runs)
+constexpr int kScalarCps64 = 14;      // code points of the text, 64 bits (words 14, 15): the decode scan -> host (size limit)
+constexpr int kScalarGuard = 16;      // arena guard (guard_check_kernel gets + kScalarGuard, host writes {0, ~0} first):
+constexpr int kScalarGuardBad = kScalarGuard + 0;    //   damaged zones -> host
+constexpr int kScalarGuardFirst = kScalarGuard + 1;  //   1 + index of the first one -> host
+constexpr int kScalarFree18 = 18;      // words 18, 19: free (still inside the download behind the walk)
+constexpr int kScalarAlphaWord0 = 20;  // first word of the text's alphabet bitmap before the vocabulary marks it: copy -> host
 // documents calls (rows.h): lines of the text / boundaries of explicit rows that fail the check / rows a padded call cut
 constexpr int kScalarRows = 21, kScalarRowsBad = 22, kScalarRowsCut = 23;
+constexpr int kScalarCand = 24;  // d_scalars word: entries of the keys-only round 0's candidate list (linear_path.h)
+constexpr int kScalarKept = 25;  // d_scalars word: suffixes the keys-only round 0 kept (not blank-start; radix_sort.h, RadixDrop)
 constexpr int kScalarSrcRows = 26;  // lines of the caller's text in a documents call on normalised text (normalize.h)
 // model inputs (inputs.h): samples that lost ids / the number of output rows, 64 bits (words 28, 29) / samples with windows
 constexpr int kScalarInCut = 27, kScalarInRows = 28, kScalarInWindowed = 30;
+constexpr int kScalarFree31 = 31;  // free
+constexpr int kScalarMask = 32;    // d_scalars words 32..43: the six 64-bit counters of a mask call (mask.h, MaskCounter)
+constexpr int kScalarFree44 = 44;  // words 44..47: free
+// normalize_on_device runs in front of the encode, which clears the block again: while it runs, four slots mean
+constexpr int kScalarNormBytes = kScalarCps;           // bytes of the normalised text, 32 bits: its scan
+constexpr int kScalarNormCps = kScalarAlphabet;        // code points of the normalised text (offsets mode) -> host
+constexpr int kScalarNormSrcCps = kScalarListEntries;  // code points of the source text (offsets mode)
+constexpr int kScalarNormBytes64 = kScalarCps64;       // bytes of the normalised text, 64 bits -> host
+// (kScalarInvalid keeps its meaning there)
+
+// the table in order: {first word, words}; a range of an even number of words holds 64-bit values
+struct ScalarRange {
+  int first, words;
+};
+constexpr ScalarRange kScalarLayout[] = {
+    {kScalarCps, 1},         {kScalarAlphabet, 1},   {kScalarInvalid, 2},         {kScalarListEntries, 1},
+    {kScalarListGroups, 1},  {kScalarListLargeGroups, 1}, {kScalarListLargeEntries, 1}, {kScalarListWanted, 1},
+    {kScalarIds, 1},         {kScalarAnchors, 1},    {kScalarAnchorGap, 1},       {kScalarLongWords, 1},
+    {kScalarWideWords, 1},   {kScalarCps64, 2},      {kScalarGuardBad, 1},        {kScalarGuardFirst, 1},
+    {kScalarFree18, 2},      {kScalarAlphaWord0, 1}, {kScalarRows, 1},            {kScalarRowsBad, 1},
+    {kScalarRowsCut, 1},     {kScalarCand, 1},       {kScalarKept, 1},            {kScalarSrcRows, 1},
+    {kScalarInCut, 1},       {kScalarInRows, 2},     {kScalarInWindowed, 1},      {kScalarFree31, 1},
+    {kScalarMask, 12},       {kScalarFree44, 4}};
+// one past the last word of the range `slot` lies in: where a download or a clear "through" that slot ends
+constexpr int scalar_end(int slot) {
+  for (const ScalarRange &r : kScalarLayout) {
+    if (slot < r.first + r.words) return r.first + r.words;
+  }
+  return kScalars;
+}
+// every word belongs to exactly one range (no gap, no overlap, nothing past kScalars); 64-bit values are 8-byte aligned
+constexpr bool scalar_layout_ok() {
+  int at = 0;
+  for (const ScalarRange &r : kScalarLayout) {
+    if (r.first != at || r.words < 1 || (r.words % 2 == 0 && r.first % 2 != 0)) return false;
+    at += r.words;
+  }
+  return at == kScalars;
+}
+static_assert(scalar_layout_ok(), "the scalar table must cover d_scalars word by word, 64-bit slots on even words");
+static_assert(kScalarList % 2 == 0 && kScalarListLargeGroups % 2 == 0, "both halves of the list block are also read as 64-bit words");
 
 // A documents call (wp_linear_encode_rows / _padded) as encode_on_device sees it: how the rows are given, and where it
 // left the row structure (device pointers into the arenas, valid like c->d_ids until the handle's next call).
@@ -161,14 +237,30 @@ struct RowsCall {
   uint32_t *d_line_cnt = nullptr;  // lines mode: line ends per tile, scanned (phase A arena)
 };
 
+// c->evs: the events that order the streams of an encode (no timing)
+//   kEvFork / kEvJoin          the side stream may start / is done
+//   kEvScalars                 the scalars of a refinement round are in the pinned mirror
+//   kEvKeysFree                the side stream is done with the sorted keys
+//   kEvPartition               the partition passes are queued
+//   kEvTrieNodes               the trie nodes of the groups are known
+//   kEvLargeSorted             the large groups are sorted
+//   kEvKeysBuilt               the key builder is done
+//   kEvCandCount               the candidate count is in the pinned mirror
+//   kEvSpine / kEvKept         the spine of round 0's first pass is done / its kept count is in the pinned mirror
+enum SideEvent { kEvFork, kEvJoin, kEvScalars, kEvKeysFree, kEvPartition, kEvTrieNodes, kEvLargeSorted, kEvKeysBuilt, kEvCandCount,
+                 kEvSpine, kEvKept, kSideEvents };
+// c->ev: the marks of WP_OPT_STAGE_TIMING in the order an encode passes them: its start / code points counted / symbols,
+// classes and keys written / suffix array refined / LCP / scanlines / walk (the fast path: start, counted, symbols,
+// walked).  normalize_on_device: its start, and its end in the mark the encode behind it records next.
+enum TimingMark { kMarkStart, kMarkCounted, kMarkSymbols, kMarkSorted, kMarkLcp, kMarkScanned, kMarkWalked, kMarkNormStart,
+                  kTimingMarks, kMarkNormEnd = kMarkStart };
+
 struct Context {
   int device = 0;
   hipStream_t stream = nullptr;
   hipStream_t stream2 = nullptr;  // side stream: latency-bound helpers overlap the bandwidth-bound kernels
   hipStream_t stream3 = nullptr;  // second side stream: the large-group path of the trie round beside its LDS sort
-  hipEvent_t evs[11] = {};        // fork / join / scalars fetched / side stream done with the sorted keys / partition passes queued /
-                                  // trie nodes known / large groups sorted / key builder done / candidate count fetched /
-                                  // spine of round 0's first pass done / its kept count fetched
+  hipEvent_t evs[kSideEvents] = {};  // order between the streams of an encode (SideEvent)
   // vocab tables on the device
   uint32_t *d_stream = nullptr, *d_elig_start = nullptr, *d_elig_info = nullptr, *d_soft = nullptr;
   uint32_t *d_vocab_word_idx = nullptr, *d_vocab_word_bits = nullptr;  // the vocabulary's words of the alphabet bitmap
@@ -212,7 +304,7 @@ struct Context {
   uint32_t *d_symhist = nullptr;  // 256 counters
   uint32_t *h_scalars = nullptr;                                         // pinned mirror
   RadixStats rstats;
-  hipEvent_t ev[8] = {};
+  hipEvent_t ev[kTimingMarks] = {};  // WP_OPT_STAGE_TIMING (TimingMark)
   // results / debug views of the last call (device pointers into the arenas)
   const int32_t *d_ids = nullptr;
   const uint32_t *d_offs = nullptr;  // offsets mode: [begin, end) per id (linear_path.h, offsets.h)
@@ -226,6 +318,11 @@ struct Context {
     int32_t *best_scratch = nullptr;  // room for 2n int32 (debug expansion of the step functions)
     size_t n = 0, n_text = 0;
   } dbg;
+  // every DeviceBuffer above, for destroy_context, release_arenas and park_context: a new buffer is one more name here
+  std::array<DeviceBuffer *, 14> buffers() {
+    return {&text_buf, &a_buf,    &b_buf,   &fmt_buf,    &text_buf2, &ids_stage[0], &ids_stage[1],
+            &rows_in,  &rows_out, &pad_buf, &inputs_buf, &norm_buf,  &norm_aux,     &norm_map};
+  }
   Context() = default;
   Context(const Context &) = delete;
   Context &operator=(const Context &) = delete;
@@ -245,6 +342,19 @@ struct DeviceGuard {
   DeviceGuard(const DeviceGuard &) = delete;
   DeviceGuard &operator=(const DeviceGuard &) = delete;
 };
+
+#ifdef WP_DEBUG_BOUNDS
+// the bounds-checking build: reads the counters of `count` sites from `first` on into oob (the kernels that count there
+// are over) and, where any counted, clears them for the next call
+static void take_oob(int first, int count, unsigned int *oob) {
+  WP_HIP(hipMemcpyFromSymbol(oob, HIP_SYMBOL(g_wp_oob), count * sizeof(unsigned int), first * sizeof(unsigned int)));
+  bool any = false;
+  for (int i = 0; i < count; i++) any = any || oob[i] != 0;
+  if (!any) return;
+  const unsigned int zero[kBoundSites] = {};
+  WP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_wp_oob), zero, count * sizeof(unsigned int), first * sizeof(unsigned int)));
+}
+#endif
 
 }  // namespace wp
 
@@ -282,78 +392,52 @@ struct wp_vocab {
 
 namespace wp {
 
+// hipFree of raw device pointers, each cleared as it is released
+template <typename... T>
+static void free_dev(T *&...p) {
+  (((p ? (void)hipFree(p) : (void)0), p = nullptr), ...);
+}
+
+// the tables of a vocabulary: they go when the handle is destroyed (a parked context gets the next handle's); a new
+// table is one more name here
 static void free_vocab_tables(Context *c) {
-  for (void **p : {reinterpret_cast<void **>(&c->d_stream), reinterpret_cast<void **>(&c->d_elig_start),
-                   reinterpret_cast<void **>(&c->d_elig_info), reinterpret_cast<void **>(&c->d_soft),
-                   reinterpret_cast<void **>(&c->d_elig_id), reinterpret_cast<void **>(&c->d_tok_len),
-                   reinterpret_cast<void **>(&c->d_tok_class),
-                   reinterpret_cast<void **>(&c->d_trie_key), reinterpret_cast<void **>(&c->d_trie_child),
-                   reinterpret_cast<void **>(&c->d_trie_id), reinterpret_cast<void **>(&c->d_vocab_word_idx),
-                   reinterpret_cast<void **>(&c->d_vocab_word_bits), reinterpret_cast<void **>(&c->d_cls_bmp),
-                   reinterpret_cast<void **>(&c->d_lt_chain_len), reinterpret_cast<void **>(&c->d_lt_chain_off),
-                   reinterpret_cast<void **>(&c->d_lt_child_begin), reinterpret_cast<void **>(&c->d_lt_child_cp),
-                   reinterpret_cast<void **>(&c->d_lt_child_node), reinterpret_cast<void **>(&c->d_elig_node),
-                   reinterpret_cast<void **>(&c->d_elig_subtree)}) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
+  free_dev(c->d_stream, c->d_elig_start, c->d_elig_info, c->d_soft, c->d_elig_id, c->d_tok_len, c->d_tok_class, c->d_trie_key,
+           c->d_trie_child, c->d_trie_id, c->d_vocab_word_idx, c->d_vocab_word_bits, c->d_cls_bmp, c->d_lt_chain_len,
+           c->d_lt_chain_off, c->d_lt_child_begin, c->d_lt_child_cp, c->d_lt_child_node, c->d_elig_node, c->d_elig_subtree);
+}
+
+template <size_t N>
+static void destroy_events(hipEvent_t (&events)[N]) {
+  for (auto &e : events) {
+    if (e) (void)hipEventDestroy(e);
+    e = nullptr;
   }
 }
 
 // idempotent: every resource is cleared as it is released (runs from ~Context too)
 static void destroy_context(Context *c) {
   if (!c) return;
-  const bool owns = c->stream || c->stream2 || c->stream3 || c->d_used || c->d_lut || c->d_scan_tmp || c->d_scalars || c->d_code ||
-                    c->d_symhist || c->h_scalars || c->h_code || c->d_stream || c->text_buf.p || c->a_buf.p ||
-                    c->b_buf.p || c->fmt_buf.p || c->rows_in.p || c->rows_out.p || c->pad_buf.p || c->inputs_buf.p;
+  bool owns = c->stream || c->stream2 || c->stream3 || c->d_used || c->d_lut || c->d_scan_tmp || c->d_scalars || c->d_code ||
+              c->d_symhist || c->h_scalars || c->h_code || c->d_stream;
+  for (DeviceBuffer *b : c->buffers()) owns = owns || b->p;
   if (!owns) return;
   DeviceGuard keep;
   (void)hipSetDevice(c->device);
   free_vocab_tables(c);
-  for (void **p : {reinterpret_cast<void **>(&c->d_used), reinterpret_cast<void **>(&c->d_lut),
-                   reinterpret_cast<void **>(&c->d_scan_tmp), reinterpret_cast<void **>(&c->d_scalars),
-                   reinterpret_cast<void **>(&c->d_code), reinterpret_cast<void **>(&c->d_symhist),
-                   reinterpret_cast<void **>(&c->d_norm_index), reinterpret_cast<void **>(&c->d_norm_pages),
-                   reinterpret_cast<void **>(&c->d_norm_pool)}) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-  }
+  // the tables of the context itself: they stay while it is parked
+  free_dev(c->d_used, c->d_lut, c->d_scan_tmp, c->d_scalars, c->d_code, c->d_symhist, c->d_norm_index, c->d_norm_pages, c->d_norm_pool);
   if (c->h_scalars) (void)hipHostFree(c->h_scalars);
   if (c->h_code) (void)hipHostFree(c->h_code);
   c->h_scalars = nullptr;
   c->h_code = nullptr;
-  c->text_buf.release();
-  c->a_buf.release();
-  c->b_buf.release();
-  c->fmt_buf.release();
-  c->text_buf2.release();
-  c->ids_stage[0].release();
-  c->ids_stage[1].release();
-  c->rows_in.release();
-  c->rows_out.release();
-  c->pad_buf.release();
-  c->inputs_buf.release();
-  c->norm_buf.release();
-  c->norm_aux.release();
-  c->norm_map.release();
-  for (auto &e : c->pipe_ev) {
-    if (e) (void)hipEventDestroy(e);
-    e = nullptr;
+  for (DeviceBuffer *b : c->buffers()) b->release();
+  destroy_events(c->pipe_ev);
+  destroy_events(c->ev);
+  destroy_events(c->evs);
+  for (hipStream_t *s : {&c->up_stream, &c->down_stream, &c->stream3, &c->stream2, &c->stream}) {
+    if (*s) (void)hipStreamDestroy(*s);
+    *s = nullptr;
   }
-  if (c->up_stream) (void)hipStreamDestroy(c->up_stream);
-  if (c->down_stream) (void)hipStreamDestroy(c->down_stream);
-  c->up_stream = c->down_stream = nullptr;
-  for (auto &e : c->ev) {
-    if (e) (void)hipEventDestroy(e);
-    e = nullptr;
-  }
-  for (auto &e : c->evs) {
-    if (e) (void)hipEventDestroy(e);
-    e = nullptr;
-  }
-  if (c->stream3) (void)hipStreamDestroy(c->stream3);
-  if (c->stream2) (void)hipStreamDestroy(c->stream2);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  c->stream = c->stream2 = c->stream3 = nullptr;
 }
 Context::~Context() { destroy_context(this); }
 
@@ -382,20 +466,7 @@ static std::vector<std::unique_ptr<Context>> &context_pool() {
 }
 
 static void release_arenas(Context *c) {
-  c->norm_buf.release();
-  c->norm_aux.release();
-  c->norm_map.release();
-  c->rows_in.release();
-  c->rows_out.release();
-  c->pad_buf.release();
-  c->inputs_buf.release();
-  c->text_buf2.release();
-  c->ids_stage[0].release();
-  c->ids_stage[1].release();
-  c->text_buf.release();
-  c->a_buf.release();
-  c->b_buf.release();
-  c->fmt_buf.release();
+  for (DeviceBuffer *b : c->buffers()) b->release();
   c->d_ids = nullptr;
   c->d_offs = nullptr;
   c->dbg = {};
@@ -409,11 +480,9 @@ static void park_context(std::unique_ptr<Context> c) {
   if (!no_pool && hipStreamSynchronize(c->stream) == hipSuccess && hipStreamSynchronize(c->stream2) == hipSuccess &&
       hipStreamSynchronize(c->stream3) == hipSuccess) {
     free_vocab_tables(c.get());
-    if (c->text_buf.cap + c->text_buf2.cap + c->ids_stage[0].cap + c->ids_stage[1].cap + c->a_buf.cap + c->b_buf.cap + c->fmt_buf.cap +
-            c->rows_in.cap + c->rows_out.cap + c->pad_buf.cap + c->inputs_buf.cap + c->norm_buf.cap + c->norm_aux.cap + c->norm_map.cap >
-        kPoolArenaBytes) {
-      release_arenas(c.get());
-    }
+    size_t held = 0;
+    for (DeviceBuffer *b : c->buffers()) held += b->cap;
+    if (held > kPoolArenaBytes) release_arenas(c.get());
     c->d_ids = nullptr;
     c->d_offs = nullptr;
     c->dbg = {};
@@ -453,13 +522,18 @@ static void upload_vocab_tables(Context *c, const HostVocab &hv) {
   WP_HIP(hipStreamSynchronize(c->stream));
 }
 
-// a context (streams, vocab tables, scratch) on `device` (< 0: the calling thread's current device): a parked
-// one if there is any, else a fresh one
-static std::unique_ptr<Context> make_context(const wp_vocab *v, int device) {
+static int device_count_or_throw() {
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count == 0) {
     throw HipError("no HIP device available: the Linear WordPiece path has no CPU fallback");
   }
+  return count;
+}
+
+// a context (streams, vocab tables, scratch) on `device` (< 0: the calling thread's current device): a parked
+// one if there is any, else a fresh one
+static std::unique_ptr<Context> make_context(const wp_vocab *v, int device) {
+  const int count = device_count_or_throw();
   if (device >= 0) {
     if (device >= count) throw std::invalid_argument("no such HIP device: " + std::to_string(device));
   } else {
@@ -507,10 +581,18 @@ static Context *get_context(wp_vocab *v) {
   return v->ctx.get();
 }
 
-// copies `count` device scalars (from d_scalars) to the pinned mirror and waits
-static void fetch_scalars(Context *c, int count) {
-  WP_HIP(hipMemcpyAsync(c->h_scalars, c->d_scalars, sizeof(uint32_t) * count, hipMemcpyDeviceToHost, c->stream));
+// queues the copy of the device scalars from word 0 through slot `last` to the pinned mirror
+static void queue_scalars(Context *c, int last, hipStream_t st) {
+  WP_HIP(hipMemcpyAsync(c->h_scalars, c->d_scalars, sizeof(uint32_t) * scalar_end(last), hipMemcpyDeviceToHost, st));
+}
+// the same on the context's stream, and waits
+static void fetch_scalars(Context *c, int last) {
+  queue_scalars(c, last, c->stream);
   WP_HIP(hipStreamSynchronize(c->stream));
+}
+// queues the clearing of the device scalars from slot `first` through slot `last`
+static void clear_scalars(Context *c, int first, int last, hipStream_t st) {
+  WP_HIP(hipMemsetAsync(c->d_scalars + first, 0, sizeof(uint32_t) * (scalar_end(last) - first), st));
 }
 
 }  // namespace wp

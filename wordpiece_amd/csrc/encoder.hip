@@ -63,6 +63,22 @@ static int guarded(F &&f) {
   }
 }
 
+// ---- argument rules that several entry points share -----------------------------------------------------------------
+static void check_device_text(const void *d_utf8) {
+  if ((reinterpret_cast<uintptr_t>(d_utf8) & 3u) != 0) throw std::invalid_argument("device text must be 4-byte aligned");
+}
+static void check_device_doc_off(const void *d_doc_off) {
+  if ((reinterpret_cast<uintptr_t>(d_doc_off) & 7u) != 0) throw std::invalid_argument("device document offsets must be 8-byte aligned");
+}
+// a device documents call without text has no rows: explicit rows cannot end at 0 unless there are none
+static void check_doc_off_without_text(const void *d_doc_off, size_t n_docs) {
+  if (d_doc_off && n_docs != 0) throw std::invalid_argument("document offsets must increase from 0 to nbytes");
+}
+static bool known_norm_flags(int64_t flags) { return flags >= 0 && (flags & ~static_cast<int64_t>(kNormKnownFlags)) == 0; }
+
+// wp_vocab_token_flags, and the class byte of an id on the device (mask.h)
+static int32_t token_flags(const HostToken &t) { return (t.is_prefix ? 1 : 0) | (t.is_special ? 2 : 0) | (t.is_malformed ? 4 : 0); }
+
 static int vocab_from_lines(const std::vector<std::pair<const char *, size_t>> &lines, wp_vocab **out) {
   if (!out) {
     g_last_error = "null output pointer";
@@ -126,8 +142,7 @@ void wp_vocab_destroy(wp_vocab *v) {
 int64_t wp_vocab_size(const wp_vocab *v) { return static_cast<int64_t>(v->hv.tokens.size()); }
 int32_t wp_vocab_unk_id(const wp_vocab *v) { return v->hv.unk_id; }
 int32_t wp_vocab_token_flags(const wp_vocab *v, int64_t i) {
-  const HostToken &t = v->hv.tokens[static_cast<size_t>(i)];
-  return (t.is_prefix ? 1 : 0) | (t.is_special ? 2 : 0) | (t.is_malformed ? 4 : 0);
+  return token_flags(v->hv.tokens[static_cast<size_t>(i)]);
 }
 int64_t wp_vocab_token_len(const wp_vocab *v, int64_t i) {
   return static_cast<int64_t>(v->hv.tokens[static_cast<size_t>(i)].word.size());
@@ -153,7 +168,7 @@ int wp_set_option(wp_vocab *v, int option, int64_t value) {
     case WP_OPT_INDEXED_ROUND0: v->indexed_round0 = value != 0; return WP_OK;
     case WP_OPT_SORT_BLANKS: v->sort_blanks = value != 0; return WP_OK;
     case WP_OPT_NORMALIZE:
-      if (value < 0 || (value & ~static_cast<int64_t>(kNormKnownFlags)) != 0) {
+      if (!known_norm_flags(value)) {
         g_last_error = "WP_OPT_NORMALIZE: unknown flag bits (WP_NORM_CLEAN | WP_NORM_LOWER | WP_NORM_STRIP_ACCENTS)";
         return WP_ERR_ARG;
       }
@@ -166,7 +181,7 @@ int wp_set_option(wp_vocab *v, int option, int64_t value) {
 }
 
 int wp_normalize_cp(int flags, uint32_t cp, uint32_t out[3]) {
-  if (flags < 0 || (flags & ~kNormKnownFlags) != 0 || cp >= 0x110000u || (cp >= 0xd800u && cp < 0xe000u)) return -1;
+  if (!known_norm_flags(flags) || cp >= 0x110000u || (cp >= 0xd800u && cp < 0xe000u)) return -1;
   uint32_t o[3] = {0, 0, 0};
   const int n = norm_cp(host_norm_tables(), flags, cp, o);
   for (int i = 0; i < n; i++) out[i] = o[i];
@@ -177,9 +192,9 @@ int wp_normalize_device(wp_vocab *v, const void *d_utf8, size_t nbytes, int flag
   return guarded([&] {
     *d_out = nullptr;
     *out_bytes = 0;
-    if (flags < 0 || (flags & ~kNormKnownFlags) != 0) throw std::invalid_argument("normalize: unknown flag bits");
+    if (!known_norm_flags(flags)) throw std::invalid_argument("normalize: unknown flag bits");
     if (nbytes == 0) return;
-    if ((reinterpret_cast<uintptr_t>(d_utf8) & 3u) != 0) throw std::invalid_argument("device text must be 4-byte aligned");
+    check_device_text(d_utf8);
     Context *c = get_context(v);
     NormResult r;
     normalize_on_device(c, static_cast<const uint8_t *>(d_utf8), nbytes, flags, false, false, r);
@@ -214,7 +229,7 @@ int wp_get_inputs_stats(const wp_vocab *v, wp_inputs_stats *out) {
 
 int wp_linear_encode_device(wp_vocab *v, const void *d_utf8, size_t nbytes, const int32_t **d_ids, size_t *n_ids) {
   return guarded([&] {
-    if ((reinterpret_cast<uintptr_t>(d_utf8) & 3u) != 0) throw std::invalid_argument("device text must be 4-byte aligned");
+    check_device_text(d_utf8);
     size_t n = 0;
     Context *c = get_context(v);
     encode_on_device(v, c, static_cast<const uint8_t *>(d_utf8), nbytes, &n, v->stats);
@@ -303,14 +318,66 @@ struct PinnedBlock {  // returns the block to the pool unless release()d to the 
   }
 };
 
+// Device ranges on their way to the caller as pinned blocks.  add() takes a block from id_pool() and queues the copy on
+// the stream; finish() waits once and only then stores the blocks through the caller's out-pointers.  Whatever throws
+// before that, every block goes back to the pool.
+class Downloads {
+  hipStream_t st;
+  std::vector<std::pair<void *, void *>> items;  // block, the caller's pointer to hand it over through
+
+ public:
+  explicit Downloads(hipStream_t stream) : st(stream) {}
+  ~Downloads() {
+    for (auto &it : items) id_pool().give_back(it.first);
+  }
+  template <typename T>
+  void add(T **out, const void *d_src, size_t bytes) {
+    items.reserve(items.size() + 1);
+    items.emplace_back(id_pool().take(bytes), out);
+    WP_HIP(hipMemcpyAsync(items.back().first, d_src, bytes, hipMemcpyDeviceToHost, st));
+  }
+  void finish() {
+    WP_HIP(hipStreamSynchronize(st));
+    for (auto &it : items) std::memcpy(it.second, &it.first, sizeof(void *));  // (*out = block, for every T * alike)
+    items.clear();
+  }
+};
+
 using wp_clock = std::chrono::steady_clock;
 double ms_since(wp_clock::time_point t0) { return std::chrono::duration<double, std::milli>(wp_clock::now() - t0).count(); }
 
-// uploads [utf8, utf8 + nbytes) into c's text buffer (padded as the decoder expects) on c's stream
-void upload_text(Context *c, const char *utf8, size_t nbytes) {
-  c->text_buf.ensure(nbytes + 64);
-  WP_HIP(hipMemsetAsync(static_cast<char *>(c->text_buf.p) + (nbytes & ~static_cast<size_t>(15)), 0, 32, c->stream));
-  WP_HIP(hipMemcpyAsync(c->text_buf.p, utf8, nbytes, hipMemcpyHostToDevice, c->stream));
+// uploads [utf8, utf8 + nbytes) into a text buffer (grown and padded as the decoder expects: context.h) on stream st
+void upload_text(DeviceBuffer &buf, hipStream_t st, const char *utf8, size_t nbytes) {
+  buf.ensure(text_room(nbytes));
+  zero_text_tail(buf.p, nbytes, st);
+  WP_HIP(hipMemcpyAsync(buf.p, utf8, nbytes, hipMemcpyHostToDevice, st));
+}
+void upload_text(Context *c, const char *utf8, size_t nbytes) { upload_text(c->text_buf, c->stream, utf8, nbytes); }
+
+// lanes of a wave that share a row of max_len cells (pack_rows_kernel, inputs_pack_kernel, mask_kernel)
+int lanes_for(int max_len) {
+  int lanes = 4;
+  while (lanes < kWave && lanes < max_len) lanes *= 2;
+  return lanes;
+}
+
+// The batch of a call whose documents are all empty, on the host: n rows of specials and padding, and their lengths.
+// token_types / sample: the two further arrays of an inputs call (nullptr: a padded call); second_sep: its pair form.
+void fill_empty_rows(size_t n, int max_len, int32_t cls_id, int32_t sep_id, int32_t pad_id, bool second_sep, int32_t *ids,
+                     int32_t *lengths, int32_t *token_types, int32_t *sample) {
+  for (size_t r = 0; r < n; r++) {
+    int32_t *row = ids + r * static_cast<size_t>(max_len);
+    int col = 0;
+    if (cls_id >= 0) row[col++] = cls_id;
+    if (sep_id >= 0) row[col++] = sep_id;
+    if (second_sep && sep_id >= 0) {
+      token_types[r * static_cast<size_t>(max_len) + col] = 1;
+      row[col++] = sep_id;
+    }
+    lengths[r] = col;
+    while (col < max_len) row[col++] = pad_id;
+    if (sample) sample[r] = static_cast<int32_t>(r);
+  }
 }
 
 bool ascii_space(uint8_t b) { return (b >= 0x09 && b <= 0x0d) || b == 0x20; }
@@ -498,10 +565,7 @@ std::vector<int> resolve_devices(const int *devices, int n_devices) {
     out.assign(devices, devices + n_devices);
     return out;
   }
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count == 0) {
-    throw HipError("no HIP device available: the Linear WordPiece path has no CPU fallback");
-  }
+  const int count = device_count_or_throw();
   const int want = n_devices <= 0 ? count : std::min(n_devices, count);
   for (int d = 0; d < want; d++) out.push_back(d);
   return out;
@@ -545,10 +609,9 @@ int wp_linear_encode(wp_vocab *v, const char *utf8, size_t nbytes, int32_t **ids
     encode_on_device(v, c, static_cast<const uint8_t *>(c->text_buf.p), nbytes, &n, v->stats);
     t0 = wp_clock::now();
     if (n) {
-      PinnedBlock blk(n * sizeof(int32_t));
-      WP_HIP(hipMemcpyAsync(blk.p, c->d_ids, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-      WP_HIP(hipStreamSynchronize(c->stream));
-      *ids = static_cast<int32_t *>(blk.release());
+      Downloads down(c->stream);
+      down.add(ids, c->d_ids, n * sizeof(int32_t));
+      down.finish();
       *n_ids = n;
     }
     v->stats.n_devices = 1;
@@ -581,12 +644,10 @@ int wp_linear_encode_offsets(wp_vocab *v, const char *utf8, size_t nbytes, int u
     encode_on_device(v, c, static_cast<const uint8_t *>(c->text_buf.p), nbytes, &n, v->stats, unit);
     const auto t0 = wp_clock::now();
     if (n) {
-      PinnedBlock bi(n * sizeof(int32_t)), bo(n * 2 * sizeof(uint32_t));
-      WP_HIP(hipMemcpyAsync(bi.p, c->d_ids, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-      WP_HIP(hipMemcpyAsync(bo.p, c->d_offs, n * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-      WP_HIP(hipStreamSynchronize(c->stream));
-      *ids = static_cast<int32_t *>(bi.release());
-      *offsets = static_cast<uint32_t *>(bo.release());
+      Downloads down(c->stream);
+      down.add(ids, c->d_ids, n * sizeof(int32_t));
+      down.add(offsets, c->d_offs, n * 2 * sizeof(uint32_t));
+      down.finish();
       *n_ids = n;
     }
     v->stats.n_devices = 1;
@@ -599,17 +660,16 @@ int wp_normalize(wp_vocab *v, const char *utf8, size_t nbytes, int flags, char *
   return guarded([&] {
     *out = nullptr;
     *out_bytes = 0;
-    if (flags < 0 || (flags & ~kNormKnownFlags) != 0) throw std::invalid_argument("normalize: unknown flag bits");
+    if (!known_norm_flags(flags)) throw std::invalid_argument("normalize: unknown flag bits");
     if (nbytes == 0) return;  // (no device needed)
     Context *c = get_context(v);
     upload_text(c, utf8, nbytes);
     NormResult r;
     normalize_on_device(c, static_cast<const uint8_t *>(c->text_buf.p), nbytes, flags, false, false, r);
     if (r.nbytes) {
-      PinnedBlock b(r.nbytes);
-      WP_HIP(hipMemcpyAsync(b.p, r.text, r.nbytes, hipMemcpyDeviceToHost, c->stream));
-      WP_HIP(hipStreamSynchronize(c->stream));
-      *out = static_cast<char *>(b.release());
+      Downloads down(c->stream);
+      down.add(out, r.text, r.nbytes);
+      down.finish();
       *out_bytes = r.nbytes;
     }
   });
@@ -623,7 +683,7 @@ int wp_linear_encode_offsets_device(wp_vocab *v, const void *d_utf8, size_t nbyt
     *n_ids = 0;
     check_offsets_call(unit, nbytes);
     if (nbytes == 0) return;
-    if ((reinterpret_cast<uintptr_t>(d_utf8) & 3u) != 0) throw std::invalid_argument("device text must be 4-byte aligned");
+    check_device_text(d_utf8);
     size_t n = 0;
     Context *c = get_context(v);
     encode_on_device(v, c, static_cast<const uint8_t *>(d_utf8), nbytes, &n, v->stats, unit);
@@ -680,22 +740,22 @@ void check_doc_off_host(const char *utf8, size_t nbytes, const int64_t *doc_off,
 void rows_by_document(wp_vocab *v, Context *c, const uint8_t *d_text, size_t nbytes, const long long *d_doc_off, size_t n_docs,
                       int unit, size_t capacity, RowsResult &out) {
   hipStream_t st = c->stream;
-  WP_HIP(hipMemsetAsync(c->d_scalars + kScalarRows, 0, 3 * sizeof(uint32_t), st));
+  clear_scalars(c, kScalarRows, kScalarRowsCut, st);
   size_t n_rows = n_docs;
-  std::vector<long long> starts;
+  const void *d_starts = d_doc_off;
+  auto check_capacity = [&] {
+    out.n_rows = n_rows;
+    if (n_rows > capacity) throw std::invalid_argument("capacity_rows is smaller than the number of rows");
+  };
   if (d_doc_off) {
     hipLaunchKernelGGL(rows_check_kernel, dim3(cdiv(n_docs + 1, kBlock)), dim3(kBlock), 0, st, d_text, nbytes, d_doc_off, n_docs,
                        c->d_scalars + kScalarRowsBad);
     WP_LAUNCH_CHECK();
-    fetch_scalars(c, 24);
+    fetch_scalars(c, kScalarRowsCut);
     if (c->h_scalars[kScalarRowsBad] != 0) {
       throw std::invalid_argument("document offsets must increase from 0 to nbytes with a '\\n' in front of each");
     }
-    out.n_rows = n_rows;
-    if (n_rows > capacity) throw std::invalid_argument("capacity_rows is smaller than the number of rows");
-    starts.resize(n_rows + 1);
-    WP_HIP(hipMemcpyAsync(starts.data(), d_doc_off, (n_rows + 1) * sizeof(long long), hipMemcpyDeviceToHost, st));
-    WP_HIP(hipStreamSynchronize(st));
+    check_capacity();
   } else {
     const unsigned tiles = cdiv(nbytes, kLineTile);
     const size_t tmp_words = cdiv(tiles, kScanTile) + 8;
@@ -703,18 +763,18 @@ void rows_by_document(wp_vocab *v, Context *c, const uint8_t *d_text, size_t nby
     uint32_t *d_cnt = static_cast<uint32_t *>(c->rows_in.p);
     hipLaunchKernelGGL(line_count_kernel, dim3(tiles), dim3(kBlock), 0, st, d_text, nbytes, d_cnt);
     device_exclusive_scan(d_cnt, d_cnt, tiles, d_cnt + tiles + 1, c->d_scalars + kScalarRows, st);
-    fetch_scalars(c, 24);
+    fetch_scalars(c, kScalarRowsCut);
     n_rows = c->h_scalars[kScalarRows];
-    out.n_rows = n_rows;
-    if (n_rows > capacity) throw std::invalid_argument("capacity_rows is smaller than the number of rows");
+    check_capacity();
     c->rows_out.ensure((n_rows + 1) * sizeof(long long));
     hipLaunchKernelGGL(line_write_kernel, dim3(tiles), dim3(kBlock), 0, st, d_text, nbytes, static_cast<const uint32_t *>(d_cnt), n_rows,
                        static_cast<long long *>(c->rows_out.p));
     WP_LAUNCH_CHECK();
-    starts.resize(n_rows + 1);
-    WP_HIP(hipMemcpyAsync(starts.data(), c->rows_out.p, (n_rows + 1) * sizeof(long long), hipMemcpyDeviceToHost, st));
-    WP_HIP(hipStreamSynchronize(st));
+    d_starts = c->rows_out.p;
   }
+  std::vector<long long> starts(n_rows + 1);
+  WP_HIP(hipMemcpyAsync(starts.data(), d_starts, (n_rows + 1) * sizeof(long long), hipMemcpyDeviceToHost, st));
+  WP_HIP(hipStreamSynchronize(st));
   uint8_t last = '\n';
   WP_HIP(hipMemcpyAsync(&last, d_text + nbytes - 1, 1, hipMemcpyDeviceToHost, st));
   WP_HIP(hipStreamSynchronize(st));
@@ -723,7 +783,7 @@ void rows_by_document(wp_vocab *v, Context *c, const uint8_t *d_text, size_t nby
   };
   size_t longest = 0;
   for (size_t i = 0; i < n_rows; i++) longest = std::max(longest, doc_end(i) - static_cast<size_t>(starts[i]));
-  c->text_buf2.ensure(longest + 64);
+  c->text_buf2.ensure(text_room(longest));
   std::vector<int32_t> h_ids;
   std::vector<uint32_t> h_offs;
   std::vector<long long> splits(n_rows + 1, 0);
@@ -736,7 +796,7 @@ void rows_by_document(wp_vocab *v, Context *c, const uint8_t *d_text, size_t nby
     const size_t a = static_cast<size_t>(starts[i]), len = doc_end(i) - a;
     if (len == 0) continue;
     char *dst = static_cast<char *>(c->text_buf2.p);
-    WP_HIP(hipMemsetAsync(dst + (len & ~static_cast<size_t>(15)), 0, 32, st));
+    zero_text_tail(dst, len, st);
     WP_HIP(hipMemcpyAsync(dst, d_text + a, len, hipMemcpyDeviceToDevice, st));
     size_t n = 0;
     encode_on_device(v, c, reinterpret_cast<const uint8_t *>(dst), len, &n, last_stats, unit);
@@ -784,11 +844,7 @@ void rows_on_device(wp_vocab *v, Context *c, const uint8_t *d_text, size_t nbyte
   if (rows_per_document(v)) {
     rows_by_document(v, c, d_text, nbytes, d_doc_off, n_docs, unit, capacity, out);
   } else {
-    RowsCall rc;
-    rc.d_doc_off = d_doc_off;
-    rc.n_docs = n_docs;
-    rc.unit = unit;
-    rc.capacity = capacity;
+    RowsCall rc{d_doc_off, n_docs, unit, capacity};
     size_t n = 0;
     try {  // (row membership comes from the spans: without a unit they stay in code points, which need no second pass)
       encode_on_device(v, c, d_text, nbytes, &n, v->stats, unit >= 0 ? unit : WP_OFFSETS_CODE_POINTS, &rc);
@@ -811,23 +867,27 @@ void pack_on_device(wp_vocab *v, Context *c, const RowsResult &r, int max_len, i
                     int32_t *d_input_ids, int32_t *d_lengths) {
   v->stats.rows_truncated = 0;
   if (r.n_rows == 0) return;
-  int lanes = 4;
-  while (lanes < kWave && lanes < max_len) lanes *= 2;
-  WP_HIP(hipMemsetAsync(c->d_scalars + kScalarRowsCut, 0, sizeof(uint32_t), c->stream));
+  const int lanes = lanes_for(max_len);
+  clear_scalars(c, kScalarRowsCut, kScalarRowsCut, c->stream);
   hipLaunchKernelGGL(pack_rows_kernel, dim3(cdiv(r.n_rows, static_cast<size_t>(kBlock / lanes))), dim3(kBlock), 0, c->stream, r.d_ids,
                      r.d_row_splits, r.n_rows, max_len, cls_id, sep_id, pad_id, lanes, d_input_ids, d_lengths,
                      c->d_scalars + kScalarRowsCut);
   WP_LAUNCH_CHECK();
-  fetch_scalars(c, 24);
+  fetch_scalars(c, kScalarRowsCut);
   v->stats.rows_truncated = c->h_scalars[kScalarRowsCut];
 }
 
-// explicit row starts of a host call, into device memory
-const long long *upload_doc_off(Context *c, const int64_t *doc_off, size_t n_docs) {
-  if (!doc_off) return nullptr;
-  c->rows_in.ensure((n_docs + 1) * sizeof(int64_t));
-  WP_HIP(hipMemcpyAsync(c->rows_in.p, doc_off, (n_docs + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-  return static_cast<const long long *>(c->rows_in.p);
+// the host form of a documents call as far as its rows: the text and the explicit row starts go up, then rows_on_device
+Context *rows_from_host(wp_vocab *v, const char *utf8, size_t nbytes, const int64_t *doc_off, size_t n_docs, int unit, RowsResult &r) {
+  Context *c = get_context(v);
+  upload_text(c, utf8, nbytes);
+  if (doc_off) {
+    c->rows_in.ensure((n_docs + 1) * sizeof(int64_t));
+    WP_HIP(hipMemcpyAsync(c->rows_in.p, doc_off, (n_docs + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+  }
+  rows_on_device(v, c, static_cast<const uint8_t *>(c->text_buf.p), nbytes, doc_off ? static_cast<const long long *>(c->rows_in.p) : nullptr,
+                 n_docs, unit, SIZE_MAX, r);
+  return c;
 }
 
 void *zeroed(size_t bytes) {
@@ -857,27 +917,14 @@ int wp_linear_encode_rows(wp_vocab *v, const char *utf8, size_t nbytes, const in
       return;
     }
     const auto t_all = wp_clock::now();
-    Context *c = get_context(v);
-    upload_text(c, utf8, nbytes);
-    const long long *d_doc_off = upload_doc_off(c, doc_off, n_docs);
     RowsResult r;
-    rows_on_device(v, c, static_cast<const uint8_t *>(c->text_buf.p), nbytes, d_doc_off, n_docs, unit, SIZE_MAX, r);
+    Context *c = rows_from_host(v, utf8, nbytes, doc_off, n_docs, unit, r);
     const auto t0 = wp_clock::now();
-    PinnedBlock bs((r.n_rows + 1) * sizeof(int64_t));
-    WP_HIP(hipMemcpyAsync(bs.p, r.d_row_splits, (r.n_rows + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    std::unique_ptr<PinnedBlock> bi, bo;
-    if (r.n_ids) {
-      bi.reset(new PinnedBlock(r.n_ids * sizeof(int32_t)));
-      WP_HIP(hipMemcpyAsync(bi->p, r.d_ids, r.n_ids * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-      if (unit >= 0) {
-        bo.reset(new PinnedBlock(r.n_ids * 2 * sizeof(uint32_t)));
-        WP_HIP(hipMemcpyAsync(bo->p, r.d_offs, r.n_ids * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-      }
-    }
-    WP_HIP(hipStreamSynchronize(c->stream));
-    *row_splits = static_cast<int64_t *>(bs.release());
-    if (bi) *ids = static_cast<int32_t *>(bi->release());
-    if (bo) *offsets = static_cast<uint32_t *>(bo->release());
+    Downloads down(c->stream);
+    down.add(row_splits, r.d_row_splits, (r.n_rows + 1) * sizeof(int64_t));
+    if (r.n_ids) down.add(ids, r.d_ids, r.n_ids * sizeof(int32_t));
+    if (r.n_ids && unit >= 0) down.add(offsets, r.d_offs, r.n_ids * 2 * sizeof(uint32_t));
+    down.finish();
     *n_ids = r.n_ids;
     *n_rows = r.n_rows;
     v->stats.ms_d2h = ms_since(t0);
@@ -896,11 +943,11 @@ int wp_linear_encode_rows_device(wp_vocab *v, const void *d_utf8, size_t nbytes,
     *n_rows = 0;
     check_rows_call(unit, nbytes);
     if (unit >= 0 && !d_offsets) throw std::invalid_argument("offsets asked for without a place to return them");
-    if ((reinterpret_cast<uintptr_t>(d_utf8) & 3u) != 0) throw std::invalid_argument("device text must be 4-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(d_doc_off) & 7u) != 0) throw std::invalid_argument("device document offsets must be 8-byte aligned");
+    check_device_text(d_utf8);
+    check_device_doc_off(d_doc_off);
     Context *c = get_context(v);
     if (nbytes == 0) {  // no text: no rows (explicit rows cannot end at 0 unless there are none)
-      if (d_doc_off && n_docs != 0) throw std::invalid_argument("document offsets must increase from 0 to nbytes");
+      check_doc_off_without_text(d_doc_off, n_docs);
       c->rows_out.ensure(sizeof(int64_t));
       WP_HIP(hipMemsetAsync(c->rows_out.p, 0, sizeof(int64_t), c->stream));
       WP_HIP(hipStreamSynchronize(c->stream));
@@ -926,41 +973,29 @@ int wp_linear_encode_padded(wp_vocab *v, const char *utf8, size_t nbytes, const 
     *lengths = nullptr;
     *n_rows = 0;
     check_rows_call(-1, nbytes);
-    const int specials = padded_specials(max_len, cls_id, sep_id);
+    (void)padded_specials(max_len, cls_id, sep_id);
     if (doc_off) check_doc_off_host(utf8, nbytes, doc_off, n_docs);
     if (nbytes == 0 || (doc_off && nbytes == n_docs)) {  // rows of specials and padding only: no device needed
       const size_t rows = doc_off ? n_docs : 0;
       int32_t *out = static_cast<int32_t *>(zeroed(rows * static_cast<size_t>(max_len) * sizeof(int32_t)));
       int32_t *len = static_cast<int32_t *>(zeroed(rows * sizeof(int32_t)));
-      for (size_t r = 0; r < rows; r++) {
-        int32_t *row = out + r * static_cast<size_t>(max_len);
-        int col = 0;
-        if (cls_id >= 0) row[col++] = cls_id;
-        if (sep_id >= 0) row[col++] = sep_id;
-        while (col < max_len) row[col++] = pad_id;
-        len[r] = specials;
-      }
+      fill_empty_rows(rows, max_len, cls_id, sep_id, pad_id, false, out, len, nullptr, nullptr);
       *input_ids = out;
       *lengths = len;
       *n_rows = rows;
       return;
     }
     const auto t_all = wp_clock::now();
-    Context *c = get_context(v);
-    upload_text(c, utf8, nbytes);
-    const long long *d_doc_off = upload_doc_off(c, doc_off, n_docs);
     RowsResult r;
-    rows_on_device(v, c, static_cast<const uint8_t *>(c->text_buf.p), nbytes, d_doc_off, n_docs, -1, SIZE_MAX, r);
+    Context *c = rows_from_host(v, utf8, nbytes, doc_off, n_docs, -1, r);
     const size_t cells = r.n_rows * static_cast<size_t>(max_len);
     c->pad_buf.ensure((cells + r.n_rows) * sizeof(int32_t));
     int32_t *d_out = static_cast<int32_t *>(c->pad_buf.p), *d_len = d_out + cells;
     pack_on_device(v, c, r, max_len, cls_id, sep_id, pad_id, d_out, d_len);
-    PinnedBlock bi(cells * sizeof(int32_t)), bl(r.n_rows * sizeof(int32_t));
-    WP_HIP(hipMemcpyAsync(bi.p, d_out, cells * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    WP_HIP(hipMemcpyAsync(bl.p, d_len, r.n_rows * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    WP_HIP(hipStreamSynchronize(c->stream));
-    *input_ids = static_cast<int32_t *>(bi.release());
-    *lengths = static_cast<int32_t *>(bl.release());
+    Downloads down(c->stream);
+    down.add(input_ids, d_out, cells * sizeof(int32_t));
+    down.add(lengths, d_len, r.n_rows * sizeof(int32_t));
+    down.finish();
     *n_rows = r.n_rows;
     v->stats.ms_host_total = ms_since(t_all);
   });
@@ -973,10 +1008,10 @@ int wp_linear_encode_padded_device(wp_vocab *v, const void *d_utf8, size_t nbyte
     *n_rows = 0;
     check_rows_call(-1, nbytes);
     (void)padded_specials(max_len, cls_id, sep_id);
-    if ((reinterpret_cast<uintptr_t>(d_utf8) & 3u) != 0) throw std::invalid_argument("device text must be 4-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(d_doc_off) & 7u) != 0) throw std::invalid_argument("device document offsets must be 8-byte aligned");
+    check_device_text(d_utf8);
+    check_device_doc_off(d_doc_off);
     if (nbytes == 0) {
-      if (d_doc_off && n_docs != 0) throw std::invalid_argument("document offsets must increase from 0 to nbytes");
+      check_doc_off_without_text(d_doc_off, n_docs);
       return;
     }
     if (!d_input_ids || !d_lengths) throw std::invalid_argument("null output buffer");
@@ -1052,17 +1087,13 @@ void mask_on_device(wp_vocab *v, Context *c, const int32_t *d_in, const int32_t 
   hipStream_t st = c->stream;
   if (!c->d_tok_class) {  // one byte per id: wp_vocab_token_flags
     std::vector<uint8_t> cls(v->hv.tokens.size());
-    for (size_t i = 0; i < cls.size(); i++) {
-      const HostToken &t = v->hv.tokens[i];
-      cls[i] = static_cast<uint8_t>((t.is_prefix ? 1 : 0) | (t.is_special ? 2 : 0) | (t.is_malformed ? 4 : 0));
-    }
+    for (size_t i = 0; i < cls.size(); i++) cls[i] = static_cast<uint8_t>(token_flags(v->hv.tokens[i]));
     c->d_tok_class = upload(cls, st);
     WP_HIP(hipStreamSynchronize(st));  // cls is a local
   }
   unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarMask);
   WP_HIP(hipMemsetAsync(d_cnt, 0, kMaskCounters * sizeof(unsigned long long), st));
-  int lanes = 4;
-  while (lanes < kWave && lanes < g.max_len) lanes *= 2;
+  const int lanes = lanes_for(g.max_len);
   const size_t n_blocks = (n_rows + static_cast<size_t>(kBlock / lanes) - 1) / static_cast<size_t>(kBlock / lanes);
   const dim3 grid(static_cast<unsigned>(std::min<size_t>(n_blocks, kMaskMaxGrid))), block(kBlock);
   if (!mask_call) {
@@ -1085,12 +1116,8 @@ void mask_on_device(wp_vocab *v, Context *c, const int32_t *d_in, const int32_t 
 #ifdef WP_DEBUG_BOUNDS
   {
     unsigned int oob = 0;
-    WP_HIP(hipMemcpyFromSymbol(&oob, HIP_SYMBOL(g_wp_oob), sizeof(oob), kSiteMask * sizeof(unsigned int)));
-    if (oob != 0) {
-      const unsigned int zero = 0;
-      WP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_wp_oob), &zero, sizeof(zero), kSiteMask * sizeof(unsigned int)));
-      throw HipError("debug bounds: masking: " + std::to_string(oob) + " class lookups outside the vocabulary skipped");
-    }
+    take_oob(kSiteMask, 1, &oob);
+    if (oob != 0) throw HipError("debug bounds: masking: " + std::to_string(oob) + " class lookups outside the vocabulary skipped");
   }
 #endif
   ms.n_words = static_cast<int64_t>(h_cnt[kMaskWords]);
@@ -1116,23 +1143,13 @@ void mask_from_host(wp_vocab *v, const int32_t *input_ids, const int32_t *length
   WP_HIP(hipMemcpyAsync(d_in, input_ids, cells * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
   if (lengths) WP_HIP(hipMemcpyAsync(d_len, lengths, n_rows * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
   mask_on_device(v, c, d_in, d_len, n_rows, g, d_masked, d_labels, d_wid);
-  std::unique_ptr<PinnedBlock> bm, bl, bw;
+  Downloads down(c->stream);
   if (masked) {
-    bm.reset(new PinnedBlock(cells * sizeof(int32_t)));
-    bl.reset(new PinnedBlock(cells * sizeof(int32_t)));
-    WP_HIP(hipMemcpyAsync(bm->p, d_masked, cells * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    WP_HIP(hipMemcpyAsync(bl->p, d_labels, cells * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    down.add(masked, d_masked, cells * sizeof(int32_t));
+    down.add(labels, d_labels, cells * sizeof(int32_t));
   }
-  if (word_ids) {
-    bw.reset(new PinnedBlock(cells * sizeof(int32_t)));
-    WP_HIP(hipMemcpyAsync(bw->p, d_wid, cells * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  }
-  WP_HIP(hipStreamSynchronize(c->stream));
-  if (masked) {
-    *masked = static_cast<int32_t *>(bm->release());
-    *labels = static_cast<int32_t *>(bl->release());
-  }
-  if (word_ids) *word_ids = static_cast<int32_t *>(bw->release());
+  if (word_ids) down.add(word_ids, d_wid, cells * sizeof(int32_t));
+  down.finish();
 }
 }  // namespace
 
@@ -1282,7 +1299,7 @@ size_t inputs_on_device(wp_vocab *v, Context *c, const RowsResult &r, const Inpu
   c->inputs_buf.ensure(n_samples * sizeof(InputsRec) + (n_samples + scan_words) * sizeof(uint32_t));
   InputsRec *d_rec = static_cast<InputsRec *>(c->inputs_buf.p);
   uint32_t *d_win = reinterpret_cast<uint32_t *>(d_rec + n_samples), *d_tmp = d_win + n_samples;
-  WP_HIP(hipMemsetAsync(c->d_scalars + kScalarInCut, 0, (kScalarInWindowed + 1 - kScalarInCut) * sizeof(uint32_t), st));
+  clear_scalars(c, kScalarInCut, kScalarInWindowed, st);
   hipLaunchKernelGGL(inputs_plan_kernel, dim3(cdiv(n_samples, kBlock)), dim3(kBlock), 0, st, r.d_row_splits, n_samples, g, d_win, d_rec,
                      c->d_scalars + kScalarInCut, c->d_scalars + kScalarInWindowed);
   WP_LAUNCH_CHECK();
@@ -1290,7 +1307,7 @@ size_t inputs_on_device(wp_vocab *v, Context *c, const RowsResult &r, const Inpu
   if (windows) {
     device_exclusive_scan(d_win, d_win, n_samples, d_tmp, nullptr, st, nullptr,
                           reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarInRows));
-    fetch_scalars(c, kScalarInWindowed + 1);
+    fetch_scalars(c, kScalarInWindowed);
     unsigned long long total;
     std::memcpy(&total, c->h_scalars + kScalarInRows, sizeof(total));
     if (total > static_cast<unsigned long long>(UINT32_MAX)) throw std::length_error("inputs: too many output rows");
@@ -1299,8 +1316,7 @@ size_t inputs_on_device(wp_vocab *v, Context *c, const RowsResult &r, const Inpu
   check_inputs_size(n_out, g.max_len);
   is.n_out = static_cast<int64_t>(n_out);
   const wp_inputs o = place(n_out);
-  int lanes = 4;
-  while (lanes < kWave && lanes < g.max_len) lanes *= 2;
+  const int lanes = lanes_for(g.max_len);
   hipLaunchKernelGGL(inputs_pack_kernel, dim3(cdiv(n_out, static_cast<size_t>(kBlock / lanes))), dim3(kBlock), 0, st, r.d_ids,
                      reinterpret_cast<const uint2 *>(r.d_offs), r.n_ids, r.d_row_splits, static_cast<const InputsRec *>(d_rec),
                      windows ? static_cast<const uint32_t *>(d_win) : nullptr, n_samples, n_out, g, lanes, o.input_ids, o.token_type_ids,
@@ -1309,17 +1325,13 @@ size_t inputs_on_device(wp_vocab *v, Context *c, const RowsResult &r, const Inpu
   if (windows) {
     WP_HIP(hipStreamSynchronize(st));
   } else {
-    fetch_scalars(c, kScalarInWindowed + 1);
+    fetch_scalars(c, kScalarInWindowed);
   }
 #ifdef WP_DEBUG_BOUNDS
   {
     unsigned int oob = 0;
-    WP_HIP(hipMemcpyFromSymbol(&oob, HIP_SYMBOL(g_wp_oob), sizeof(oob), kSiteInputs * sizeof(unsigned int)));
-    if (oob != 0) {
-      const unsigned int zero = 0;
-      WP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_wp_oob), &zero, sizeof(zero), kSiteInputs * sizeof(unsigned int)));
-      throw HipError("debug bounds: model inputs: " + std::to_string(oob) + " gathers outside the id list skipped");
-    }
+    take_oob(kSiteInputs, 1, &oob);
+    if (oob != 0) throw HipError("debug bounds: model inputs: " + std::to_string(oob) + " gathers outside the id list skipped");
   }
 #endif
   is.n_cut = c->h_scalars[kScalarInCut];
@@ -1353,45 +1365,28 @@ int wp_linear_encode_inputs(wp_vocab *v, const char *utf8, size_t nbytes, const 
     if (nbytes == 0 || (doc_off && nbytes == n_docs)) {  // rows of specials and padding only: no device needed
       const size_t n = rows / (g.pairs ? 2 : 1);
       check_inputs_size(n, g.max_len);
-      int32_t *ids = static_cast<int32_t *>(zeroed(n * max_len * sizeof(int32_t)));
-      int32_t *tt = static_cast<int32_t *>(zeroed(n * max_len * sizeof(int32_t)));
-      int32_t *len = static_cast<int32_t *>(zeroed(n * sizeof(int32_t)));
-      int32_t *sample = static_cast<int32_t *>(zeroed(n * sizeof(int32_t)));
-      for (size_t r = 0; r < n; r++) {
-        int32_t *row = ids + r * max_len;
-        int col = 0;
-        if (g.head) row[col++] = g.cls_id;
-        if (g.nsep) row[col++] = g.sep_id;
-        if (g.pairs && g.nsep) {
-          tt[r * max_len + col] = 1;
-          row[col++] = g.sep_id;
-        }
-        len[r] = col;
-        while (col < g.max_len) row[col++] = g.pad_id;
-        sample[r] = static_cast<int32_t>(r);
-      }
-      out->input_ids = ids;
-      out->token_type_ids = tt;
-      out->lengths = len;
-      out->sample = sample;
-      if (unit >= 0) out->offsets = static_cast<uint32_t *>(zeroed(n * max_len * 2 * sizeof(uint32_t)));
+      wp_inputs h{};
+      h.input_ids = static_cast<int32_t *>(zeroed(n * max_len * sizeof(int32_t)));
+      h.token_type_ids = static_cast<int32_t *>(zeroed(n * max_len * sizeof(int32_t)));
+      h.lengths = static_cast<int32_t *>(zeroed(n * sizeof(int32_t)));
+      h.sample = static_cast<int32_t *>(zeroed(n * sizeof(int32_t)));
+      fill_empty_rows(n, g.max_len, g.cls_id, g.sep_id, g.pad_id, g.pairs != 0, h.input_ids, h.lengths, h.token_type_ids, h.sample);
+      if (unit >= 0) h.offsets = static_cast<uint32_t *>(zeroed(n * max_len * 2 * sizeof(uint32_t)));
+      *out = h;
       *n_out = n;
       *n_samples = n;
       return;
     }
     const auto t_all = wp_clock::now();
-    Context *c = get_context(v);
-    upload_text(c, utf8, nbytes);
-    const long long *d_doc_off = upload_doc_off(c, doc_off, n_docs);
     RowsResult r;
-    rows_on_device(v, c, static_cast<const uint8_t *>(c->text_buf.p), nbytes, d_doc_off, n_docs, unit, SIZE_MAX, r);
+    Context *c = rows_from_host(v, utf8, nbytes, doc_off, n_docs, unit, r);
     check_inputs_rows(g, r.n_rows);
     size_t cells = 0;
+    wp_inputs o{};  // the batch in c->pad_buf
     const size_t n = inputs_on_device(v, c, r, g, unit, [&](size_t rows_out) {
       cells = rows_out * max_len;  // offsets | input_ids | token_type_ids | lengths | sample
       const size_t offs_bytes = unit >= 0 ? cells * 2 * sizeof(uint32_t) : 0;
       c->pad_buf.ensure(offs_bytes + (2 * cells + 2 * rows_out) * sizeof(int32_t) + 16);
-      wp_inputs o{};
       char *base = static_cast<char *>(c->pad_buf.p);
       o.offsets = unit >= 0 ? reinterpret_cast<uint32_t *>(base) : nullptr;
       o.input_ids = reinterpret_cast<int32_t *>(base + offs_bytes);
@@ -1403,25 +1398,13 @@ int wp_linear_encode_inputs(wp_vocab *v, const char *utf8, size_t nbytes, const 
     *n_samples = r.n_rows / (g.pairs ? 2 : 1);
     *n_out = n;
     if (n == 0) return;
-    char *base = static_cast<char *>(c->pad_buf.p);
-    const size_t offs_bytes = unit >= 0 ? cells * 2 * sizeof(uint32_t) : 0;
-    const int32_t *d_ids = reinterpret_cast<const int32_t *>(base + offs_bytes);
-    PinnedBlock bi(cells * sizeof(int32_t)), bt(cells * sizeof(int32_t)), bl(n * sizeof(int32_t)), bs(n * sizeof(int32_t));
-    std::unique_ptr<PinnedBlock> bo;
-    WP_HIP(hipMemcpyAsync(bi.p, d_ids, cells * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    WP_HIP(hipMemcpyAsync(bt.p, d_ids + cells, cells * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    WP_HIP(hipMemcpyAsync(bl.p, d_ids + 2 * cells, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    WP_HIP(hipMemcpyAsync(bs.p, d_ids + 2 * cells + n, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    if (unit >= 0) {
-      bo.reset(new PinnedBlock(offs_bytes));
-      WP_HIP(hipMemcpyAsync(bo->p, base, offs_bytes, hipMemcpyDeviceToHost, c->stream));
-    }
-    WP_HIP(hipStreamSynchronize(c->stream));
-    out->input_ids = static_cast<int32_t *>(bi.release());
-    out->token_type_ids = static_cast<int32_t *>(bt.release());
-    out->lengths = static_cast<int32_t *>(bl.release());
-    out->sample = static_cast<int32_t *>(bs.release());
-    if (bo) out->offsets = static_cast<uint32_t *>(bo->release());
+    Downloads down(c->stream);
+    down.add(&out->input_ids, o.input_ids, cells * sizeof(int32_t));
+    down.add(&out->token_type_ids, o.token_type_ids, cells * sizeof(int32_t));
+    down.add(&out->lengths, o.lengths, n * sizeof(int32_t));
+    down.add(&out->sample, o.sample, n * sizeof(int32_t));
+    if (unit >= 0) down.add(&out->offsets, o.offsets, cells * 2 * sizeof(uint32_t));
+    down.finish();
     v->stats.ms_host_total = ms_since(t_all);
   });
 }
@@ -1435,11 +1418,11 @@ int wp_linear_encode_inputs_device(wp_vocab *v, const void *d_utf8, size_t nbyte
     *n_samples = 0;
     const InputsGeom g = check_inputs_spec(spec, nbytes);
     const int unit = spec->unit;
-    if ((reinterpret_cast<uintptr_t>(d_utf8) & 3u) != 0) throw std::invalid_argument("device text must be 4-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(d_doc_off) & 7u) != 0) throw std::invalid_argument("device document offsets must be 8-byte aligned");
+    check_device_text(d_utf8);
+    check_device_doc_off(d_doc_off);
     if (d_doc_off) check_inputs_rows(g, n_docs);
     if (nbytes == 0) {
-      if (d_doc_off && n_docs != 0) throw std::invalid_argument("document offsets must increase from 0 to nbytes");
+      check_doc_off_without_text(d_doc_off, n_docs);
       return;
     }
     if (!d_out || !d_out->input_ids || !d_out->token_type_ids || !d_out->lengths || !d_out->sample || (unit >= 0 && !d_out->offsets)) {
@@ -1479,7 +1462,7 @@ int wp_reserve(wp_vocab *v, size_t nbytes) {
     // a larger alphabet or the reference layout, grows them as before)
     const size_t n = nbytes + 1 + v->hv.stream.size();
     const size_t per_symbol = (v->keep_debug || v->vocab_in_s || v->full_depth) ? 108 : 56;
-    c->text_buf.ensure(nbytes + 64, false);
+    c->text_buf.ensure(text_room(nbytes), false);
     c->a_buf.ensure(nbytes + nbytes / 512 + (size_t(1) << 20) + (v->keep_debug ? 4 * nbytes : 0), false);
     c->b_buf.ensure(per_symbol * n + (v->keep_debug ? 4 * n : 0) + (size_t(64) << 20), false);
     PinnedBlock warm(nbytes + (size_t(1) << 20));  // about a quarter of an id per byte, 4 bytes each
@@ -1514,9 +1497,7 @@ void encode_pipeline(wp_vocab *v, Next &&next, Deliver &&deliver) {
       if (len == 0) return "";
       const auto t_up = wp_clock::now();
       WP_HIP(hipSetDevice(device));
-      char *dst = static_cast<char *>(tb[slot]->p);
-      WP_HIP(hipMemsetAsync(dst + (len & ~static_cast<size_t>(15)), 0, 32, c->up_stream));
-      WP_HIP(hipMemcpyAsync(dst, text, len, hipMemcpyHostToDevice, c->up_stream));
+      upload_text(*tb[slot], c->up_stream, text, len);  // (the buffer has its room already: grown on the calling thread)
       WP_HIP(hipStreamSynchronize(c->up_stream));
       up_us += static_cast<long long>(ms_since(t_up) * 1e3);
       return "";
@@ -1529,7 +1510,7 @@ void encode_pipeline(wp_vocab *v, Next &&next, Deliver &&deliver) {
   size_t cur_len = 0, next_len = 0;
   bool have = next(0, &cur_text, &cur_len);
   if (have) {
-    tb[0]->ensure(cur_len + 64);
+    tb[0]->ensure(text_room(cur_len));
     const std::string err = upload(cur_text, cur_len, 0);
     if (!err.empty()) throw HipError(err);
   }
@@ -1541,7 +1522,7 @@ void encode_pipeline(wp_vocab *v, Next &&next, Deliver &&deliver) {
     const bool more = next(i + 1, &next_text, &next_len);
     std::future<std::string> next_up;
     if (more) {
-      tb[slot ^ 1]->ensure(next_len + 64);  // (the encode that read this buffer, of text i - 1, is over)
+      tb[slot ^ 1]->ensure(text_room(next_len));  // (the encode that read this buffer, of text i - 1, is over)
       next_up = std::async(std::launch::async, upload, next_text, next_len, slot ^ 1);
     }
     struct Wait {  // the helper must be done with the text buffers before anything unwinds
@@ -1698,17 +1679,21 @@ struct MappedFile {
   }
 };
 
-int wp_linear_encode_file(const char *text_file, const char *vocab_file, int32_t **ids, size_t *n_ids) {
+// the one-shot file forms: vocabulary and text from files, through wp_linear_encode or wp_fast_encode
+static int encode_file(int (*encode)(wp_vocab *, const char *, size_t, int32_t **, size_t *), const char *text_file,
+                       const char *vocab_file, int32_t **ids, size_t *n_ids) {
   wp_vocab *v = nullptr;
   int rc = wp_vocab_from_file(vocab_file, &v);
   if (rc != WP_OK) return rc;
   std::unique_ptr<wp_vocab> guard(v);
-  rc = guarded([&] {
+  return guarded([&] {
     MappedFile mm(text_file);
-    int r2 = wp_linear_encode(v, mm.data, mm.size, ids, n_ids);
-    if (r2 != WP_OK) throw std::runtime_error(g_last_error);
+    if (encode(v, mm.data, mm.size, ids, n_ids) != WP_OK) throw std::runtime_error(g_last_error);
   });
-  return rc;
+}
+
+int wp_linear_encode_file(const char *text_file, const char *vocab_file, int32_t **ids, size_t *n_ids) {
+  return encode_file(wp_linear_encode, text_file, vocab_file, ids, n_ids);
 }
 
 // Host side of encodeExternal (linear.cpp:343-374): same batch rule and file format as the reference.
@@ -1777,9 +1762,7 @@ static int encode_external_impl(const char *text_file, const char *vocab_file, c
       }
       Context *c = get_context(v);
       hipStream_t st = c->stream;
-      c->text_buf.ensure(batch + 64);
-      WP_HIP(hipMemsetAsync(static_cast<char *>(c->text_buf.p) + (batch & ~static_cast<size_t>(15)), 0, 32, st));
-      WP_HIP(hipMemcpyAsync(c->text_buf.p, begin, batch, hipMemcpyHostToDevice, st));
+      upload_text(c, begin, batch);
       size_t n = 0;
       if (fast) {
         encode_fast_on_device(v, c, static_cast<const uint8_t *>(c->text_buf.p), batch, &n, v->stats);
@@ -1791,28 +1774,26 @@ static int encode_external_impl(const char *text_file, const char *vocab_file, c
         const size_t tiles = cdiv(n, kFmtTile);
         const size_t head = (tiles * (sizeof(uint32_t) + sizeof(unsigned long long)) + 8 + 255) & ~static_cast<size_t>(255);
         c->fmt_buf.ensure(head + n * 7);  // typical: <= 6 digits + space; grown below if the ids are longer
-        auto layout = [&](uint32_t *&tb, unsigned long long *&to, unsigned long long *&total, char *&text) {
+        uint32_t *tb;
+        unsigned long long *to, *total;
+        char *d_out;
+        auto count_bytes = [&] {  // lays the buffer out (tile offsets | total | tile byte counts | text) and counts into it
           char *base = static_cast<char *>(c->fmt_buf.p);
           to = reinterpret_cast<unsigned long long *>(base);
           total = to + tiles;
           tb = reinterpret_cast<uint32_t *>(total + 1);
-          text = base + head;
+          d_out = base + head;
+          hipLaunchKernelGGL(fmt_count_kernel, dim3(tiles), dim3(kBlock), 0, st, c->d_ids, n, tb);
+          hipLaunchKernelGGL(fmt_offsets_kernel, dim3(1), dim3(1024), 0, st, tb, tiles, to, total);
         };
-        uint32_t *tb;
-        unsigned long long *to, *total;
-        char *d_out;
-        layout(tb, to, total, d_out);
-        hipLaunchKernelGGL(fmt_count_kernel, dim3(tiles), dim3(kBlock), 0, st, c->d_ids, n, tb);
-        hipLaunchKernelGGL(fmt_offsets_kernel, dim3(1), dim3(1024), 0, st, tb, tiles, to, total);
+        count_bytes();
         WP_LAUNCH_CHECK();
         unsigned long long nbytes_out = 0;
         WP_HIP(hipMemcpyAsync(&nbytes_out, total, sizeof(nbytes_out), hipMemcpyDeviceToHost, st));
         WP_HIP(hipStreamSynchronize(st));
         if (head + nbytes_out > c->fmt_buf.cap) {  // longer ids than assumed: regrow and redo the (cheap) counts
           c->fmt_buf.ensure(head + nbytes_out);
-          layout(tb, to, total, d_out);
-          hipLaunchKernelGGL(fmt_count_kernel, dim3(tiles), dim3(kBlock), 0, st, c->d_ids, n, tb);
-          hipLaunchKernelGGL(fmt_offsets_kernel, dim3(1), dim3(1024), 0, st, tb, tiles, to, total);
+          count_bytes();
         }
         hipLaunchKernelGGL(fmt_write_kernel, dim3(tiles), dim3(kBlock), 0, st, c->d_ids, n, to, d_out);
         WP_LAUNCH_CHECK();
@@ -1846,7 +1827,7 @@ int wp_linear_encode_external(const char *text_file, const char *vocab_file, con
 // ---- word_piece::fast (fast.cpp:152-220) ----------------------------------------------------------------
 int wp_fast_encode_device(wp_vocab *v, const void *d_utf8, size_t nbytes, const int32_t **d_ids, size_t *n_ids) {
   return guarded([&] {
-    if ((reinterpret_cast<uintptr_t>(d_utf8) & 3u) != 0) throw std::invalid_argument("device text must be 4-byte aligned");
+    check_device_text(d_utf8);
     size_t n = 0;
     Context *c = get_context(v);
     encode_fast_on_device(v, c, static_cast<const uint8_t *>(d_utf8), nbytes, &n, v->stats);
@@ -1866,10 +1847,9 @@ int wp_fast_encode(wp_vocab *v, const char *utf8, size_t nbytes, int32_t **ids, 
     size_t n = 0;
     encode_fast_on_device(v, c, static_cast<const uint8_t *>(c->text_buf.p), nbytes, &n, v->stats);
     if (n) {
-      PinnedBlock blk(n * sizeof(int32_t));
-      WP_HIP(hipMemcpyAsync(blk.p, c->d_ids, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-      WP_HIP(hipStreamSynchronize(c->stream));
-      *ids = static_cast<int32_t *>(blk.release());
+      Downloads down(c->stream);
+      down.add(ids, c->d_ids, n * sizeof(int32_t));
+      down.finish();
       *n_ids = n;
     }
     v->stats.ms_host_total = ms_since(t_all);
@@ -1877,14 +1857,7 @@ int wp_fast_encode(wp_vocab *v, const char *utf8, size_t nbytes, int32_t **ids, 
 }
 
 int wp_fast_encode_file(const char *text_file, const char *vocab_file, int32_t **ids, size_t *n_ids) {
-  wp_vocab *v = nullptr;
-  int rc = wp_vocab_from_file(vocab_file, &v);
-  if (rc != WP_OK) return rc;
-  std::unique_ptr<wp_vocab> guard(v);
-  return guarded([&] {
-    MappedFile mm(text_file);
-    if (wp_fast_encode(v, mm.data, mm.size, ids, n_ids) != WP_OK) throw std::runtime_error(g_last_error);
-  });
+  return encode_file(wp_fast_encode, text_file, vocab_file, ids, n_ids);
 }
 
 int wp_fast_encode_external(const char *text_file, const char *vocab_file, const char *out_file, size_t memory_limit) {

@@ -31,7 +31,7 @@ static void encode_fast_on_device(const wp_vocab *v, Context *c, const uint8_t *
     nbytes = norm.nbytes;
   }
   Arena aa(&c->a_buf, v->arena_guard || EnvOptions::get().arena_guard);
-  if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[0], st));
+  if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[kMarkStart], st));
   const unsigned dec_tiles = cdiv(nbytes, kDecTile);
   uint32_t *d_tile_cnt = nullptr, *d_cnt_tmp = nullptr, *d_cps = nullptr;
   uint8_t *d_cls = nullptr;
@@ -45,23 +45,23 @@ static void encode_fast_on_device(const wp_vocab *v, Context *c, const uint8_t *
   aa.arm(st);
   WP_HIP(hipMemsetAsync(c->d_scalars, 0, sizeof(uint32_t) * kScalars, st));
   hipLaunchKernelGGL(decode_count_kernel<false>, dim3(dec_tiles), dim3(kBlock), 0, st, d_text, nbytes, d_tile_cnt,
-                     reinterpret_cast<unsigned long long *>(c->d_scalars + 2), static_cast<uint32_t *>(nullptr));
-  device_exclusive_scan(d_tile_cnt, d_tile_cnt, dec_tiles, d_cnt_tmp, c->d_scalars + 0, st, nullptr,
-                        reinterpret_cast<unsigned long long *>(c->d_scalars + 14));
+                     reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarInvalid), static_cast<uint32_t *>(nullptr));
+  device_exclusive_scan(d_tile_cnt, d_tile_cnt, dec_tiles, d_cnt_tmp, c->d_scalars + kScalarCps, st, nullptr,
+                        reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarCps64));
   WP_LAUNCH_CHECK();
-  fetch_scalars(c, 16);
+  fetch_scalars(c, kScalarCps64);
   unsigned long long n_text64;
-  std::memcpy(&n_text64, c->h_scalars + 14, sizeof(n_text64));
+  std::memcpy(&n_text64, c->h_scalars + kScalarCps64, sizeof(n_text64));
   // positions are 32-bit and bit 31 of an anchor entry is the skip flag of the sparse / long-word walk (walk.h,
   // kAnchorSkip): the same kind of limit as linear.cpp:104-106, never silent truncation
   if (n_text64 >= (1ull << 31)) throw std::length_error("64bit not implemented (fast path: text of 2^31 or more code points)");
-  const size_t n_text = c->h_scalars[0];
+  const size_t n_text = c->h_scalars[kScalarCps];
   unsigned long long dropped;
-  std::memcpy(&dropped, c->h_scalars + 2, sizeof(dropped));
+  std::memcpy(&dropped, c->h_scalars + kScalarInvalid, sizeof(dropped));
   if (dropped != 0) std::cerr << "WARNING Input contains invalid unicode characters." << std::endl;
   S.n_text = static_cast<int64_t>(n_text);
   S.n_total = static_cast<int64_t>(n_text);
-  if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[1], st));
+  if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[kMarkCounted], st));
   if (n_text == 0) return;
 
   Arena ar(&c->b_buf, aa.guard);
@@ -97,16 +97,16 @@ static void encode_fast_on_device(const wp_vocab *v, Context *c, const uint8_t *
                      d_tile_cnt, static_cast<const uint32_t *>(nullptr), static_cast<uint32_t *>(nullptr), d_cls, d_cps,
                      c->d_cls_bmp, static_cast<const uint32_t *>(nullptr), 0, static_cast<uint32_t *>(nullptr), 0);
   hipLaunchKernelGGL(fast_anchor_count_kernel, dim3(atiles), dim3(kBlock), 0, st, d_cls, n_text, d_anchor_cnt);
-  device_exclusive_scan(d_anchor_cnt, d_anchor_cnt, atiles, d_anchor_tmp, c->d_scalars + 10, st);
+  device_exclusive_scan(d_anchor_cnt, d_anchor_cnt, atiles, d_anchor_tmp, c->d_scalars + kScalarAnchors, st);
   hipLaunchKernelGGL(fast_anchor_write_kernel, dim3(atiles), dim3(kBlock), 0, st, d_cls, n_text, d_anchor_cnt, d_anchors);
   hipLaunchKernelGGL(fast_anchor_gap_kernel, dim3(std::min<size_t>(atiles, 1024)), dim3(kBlock), 0, st, d_anchors,
-                     c->d_scalars + 10, n_text, d_cls, c->d_scalars + 11);
+                     c->d_scalars + kScalarAnchors, n_text, d_cls, c->d_scalars + kScalarAnchorGap);
   WP_LAUNCH_CHECK();
-  fetch_scalars(c, 12);
-  const size_t n_anchors = c->h_scalars[10], max_gap = c->h_scalars[11];
+  fetch_scalars(c, kScalarAnchorGap);
+  const size_t n_anchors = c->h_scalars[kScalarAnchors], max_gap = c->h_scalars[kScalarAnchorGap];
   S.n_anchors = static_cast<int64_t>(n_anchors);
   S.walk.max_anchor_gap = static_cast<int32_t>(max_gap);  // (wp_walk_stats: no wide walk here, and no lean kernel)
-  if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[2], st));
+  if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[kMarkSymbols], st));
   FastArgs fa{d_cps, d_cls, n_text,
               TrieView{c->d_trie_key, c->d_trie_child, c->d_trie_id, static_cast<uint32_t>(hv.trie_key.size() - 1)},
               c->d_tok_len, hv.unk_id, static_cast<uint32_t>(std::min<uint64_t>(static_cast<uint64_t>(hv.fast_max_len), n_text)),
@@ -116,10 +116,10 @@ static void encode_fast_on_device(const wp_vocab *v, Context *c, const uint8_t *
   if (!staged) WP_HIP(hipMemsetAsync(d_emit, 0x80, n_text * sizeof(int32_t), st));
   if (max_gap > kMaxAnchorGap) {  // long words: pointer doubling instead of one lane per word (walk.h)
     hipLaunchKernelGGL(fast_long_word_collect_kernel, dim3(std::min<size_t>(cdiv(std::max<size_t>(n_anchors, 1), kBlock), 2048)),
-                       dim3(kBlock), 0, st, d_anchors, c->d_scalars + 10, n_text, d_cls, d_lw, lw_cap, c->d_scalars + 12);
+                       dim3(kBlock), 0, st, d_anchors, c->d_scalars + kScalarAnchors, n_text, d_cls, d_lw, lw_cap, c->d_scalars + kScalarLongWords);
     WP_LAUNCH_CHECK();
-    fetch_scalars(c, 13);
-    const uint32_t nw = std::min(c->h_scalars[12], lw_cap);
+    fetch_scalars(c, kScalarLongWords);
+    const uint32_t nw = std::min(c->h_scalars[kScalarLongWords], lw_cap);
     if (nw > 0) {
       S.walk.n_long_words = static_cast<int64_t>(nw);
       std::vector<LongWord> h_lw(nw);
@@ -161,32 +161,33 @@ static void encode_fast_on_device(const wp_vocab *v, Context *c, const uint8_t *
     const int words = kWbWords;
     const unsigned sblocks = cdiv(acap, static_cast<size_t>(words));
     hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_balanced_kernel<FastArgs, FastStep, false>), dim3(sblocks), dim3(kBlock), 0, st, fa,
-                       d_anchors, c->d_scalars + 10, acap, d_lid, d_blk_cnt,  // (d_lid: the long-word id buffer, idle here)
+                       d_anchors, c->d_scalars + kScalarAnchors, acap, d_lid, d_blk_cnt,  // (d_lid: the long-word id buffer, idle here)
                        static_cast<const uint32_t *>(nullptr));
-    device_exclusive_scan(d_blk_cnt, d_blk_off, sblocks, d_emit_tmp, c->d_scalars + 9, st);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(emit_gather_kernel<false>), dim3(sblocks), dim3(kBlock), 0, st, d_anchors, c->d_scalars + 10, acap, d_lid,
-                       d_blk_cnt, d_blk_off, d_ids, words, static_cast<const uint2 *>(nullptr), static_cast<uint2 *>(nullptr));
+    device_exclusive_scan(d_blk_cnt, d_blk_off, sblocks, d_emit_tmp, c->d_scalars + kScalarIds, st);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(emit_gather_kernel<false>), dim3(sblocks), dim3(kBlock), 0, st, d_anchors,
+                       c->d_scalars + kScalarAnchors, acap, d_lid, d_blk_cnt, d_blk_off, d_ids, words,
+                       static_cast<const uint2 *>(nullptr), static_cast<uint2 *>(nullptr));
   } else {
-    hipLaunchKernelGGL(fast_walk_kernel, dim3(wblocks), dim3(kBlock), 0, st, fa, d_anchors, c->d_scalars + 10, acap);
+    hipLaunchKernelGGL(fast_walk_kernel, dim3(wblocks), dim3(kBlock), 0, st, fa, d_anchors, c->d_scalars + kScalarAnchors, acap);
     hipLaunchKernelGGL(emit_count_kernel, dim3(tiles), dim3(kBlock), 0, st, d_emit, n_text, d_emit_cnt);
-    device_exclusive_scan(d_emit_cnt, d_emit_cnt, tiles, d_emit_tmp, c->d_scalars + 9, st);
+    device_exclusive_scan(d_emit_cnt, d_emit_cnt, tiles, d_emit_tmp, c->d_scalars + kScalarIds, st);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(emit_write_kernel<false>), dim3(tiles), dim3(kBlock), 0, st, d_emit, n_text, d_emit_cnt, d_ids,
                        static_cast<const uint2 *>(nullptr), static_cast<uint2 *>(nullptr));
   }
   S.staged_emit = staged ? 1 : 0;
   WP_LAUNCH_CHECK();
-  if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[3], st));
+  if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[kMarkWalked], st));
   if (ar.guard) {
     static const uint32_t init[2] = {0u, 0xffffffffu};
-    WP_HIP(hipMemcpyAsync(c->d_scalars + 16, init, sizeof(init), hipMemcpyHostToDevice, st));
-    ar.check(st, c->d_scalars + 16);
-    aa.check(st, c->d_scalars + 16);
-    fetch_scalars(c, 18);
-    if (c->h_scalars[16] != 0) throw HipError("arena guard: guard zone overwritten in the fast path");
+    WP_HIP(hipMemcpyAsync(c->d_scalars + kScalarGuard, init, sizeof(init), hipMemcpyHostToDevice, st));
+    ar.check(st, c->d_scalars + kScalarGuard);
+    aa.check(st, c->d_scalars + kScalarGuard);
+    fetch_scalars(c, kScalarGuardFirst);
+    if (c->h_scalars[kScalarGuardBad] != 0) throw HipError("arena guard: guard zone overwritten in the fast path");
     S.guard_zones = static_cast<int32_t>(ar.zones.size() + aa.zones.size());
   }
-  fetch_scalars(c, 10);
-  const size_t n_ids = c->h_scalars[9];
+  fetch_scalars(c, kScalarIds);
+  const size_t n_ids = c->h_scalars[kScalarIds];
   S.n_ids = static_cast<int64_t>(n_ids);
   if (v->stage_timing) {
     auto span = [&](int a, int b) {
@@ -194,9 +195,9 @@ static void encode_fast_on_device(const wp_vocab *v, Context *c, const uint8_t *
       WP_HIP(hipEventElapsedTime(&ms, c->ev[a], c->ev[b]));
       return static_cast<double>(ms);
     };
-    S.ms_decode = span(0, 2);
-    S.ms_walk = span(2, 3);
-    S.ms_total = span(0, 3) + S.ms_normalize;
+    S.ms_decode = span(kMarkStart, kMarkSymbols);
+    S.ms_walk = span(kMarkSymbols, kMarkWalked);
+    S.ms_total = span(kMarkStart, kMarkWalked) + S.ms_normalize;
   }
   c->d_ids = d_ids;
   *n_ids_out = n_ids;

@@ -286,12 +286,12 @@ struct LinearPath {
 
   // st2 starts after everything queued on st so far / st continues after everything queued on st2
   void fork() {
-    WP_HIP(hipEventRecord(c->evs[0], st));
-    WP_HIP(hipStreamWaitEvent(st2, c->evs[0], 0));
+    WP_HIP(hipEventRecord(c->evs[kEvFork], st));
+    WP_HIP(hipStreamWaitEvent(st2, c->evs[kEvFork], 0));
   }
   void join() {
-    WP_HIP(hipEventRecord(c->evs[1], st2));
-    WP_HIP(hipStreamWaitEvent(st, c->evs[1], 0));
+    WP_HIP(hipEventRecord(c->evs[kEvJoin], st2));
+    WP_HIP(hipStreamWaitEvent(st, c->evs[kEvJoin], 0));
   }
 
   // ---- HBM layout (arena B) -------------------------------------------------------------------------------------
@@ -441,11 +441,11 @@ struct LinearPath {
     if (!staged_possible) WP_HIP(hipMemsetAsync(d_emit, 0x80, n_text * sizeof(int32_t), as));
     hipLaunchKernelGGL(anchor_count_kernel, dim3(atiles), dim3(kBlock), 0, as, d_cls, static_cast<const uint8_t *>(nullptr),
                        n_text, d_anchor_cnt);
-    device_exclusive_scan(d_anchor_cnt, d_anchor_cnt, atiles, d_anchor_tmp, c->d_scalars + 10, as);
+    device_exclusive_scan(d_anchor_cnt, d_anchor_cnt, atiles, d_anchor_tmp, c->d_scalars + kScalarAnchors, as);
     hipLaunchKernelGGL(anchor_write_kernel, dim3(atiles), dim3(kBlock), 0, as, d_cls, static_cast<const uint8_t *>(nullptr),
                        n_text, d_anchor_cnt, d_anchors);
     hipLaunchKernelGGL(anchor_gap_kernel, dim3(std::min<size_t>(atiles, 1024)), dim3(kBlock), 0, as, d_anchors,
-                       c->d_scalars + 10, n_text, d_cls, hv.soft.empty() ? 1 : 0, c->d_scalars + 11);
+                       c->d_scalars + kScalarAnchors, n_text, d_cls, hv.soft.empty() ? 1 : 0, c->d_scalars + kScalarAnchorGap);
   }
 
   // ---- S build: dense symbols, symbol code, round-0 keys (linear.cpp:77-103) -----------------------------------------
@@ -561,13 +561,13 @@ struct LinearPath {
       }
     }
     if (keys_only) {  // the list packed into X1 / trie nodes by slot on the side stream; the host learns its length while the sort runs
-      WP_HIP(hipEventRecord(c->evs[7], st));
-      WP_HIP(hipStreamWaitEvent(st2, c->evs[7], 0));
+      WP_HIP(hipEventRecord(c->evs[kEvKeysBuilt], st));
+      WP_HIP(hipStreamWaitEvent(st2, c->evs[kEvKeysBuilt], 0));
       device_exclusive_scan(d_cand_bcnt, d_cand_boff, cand_blocks, d_cand_scan, c->d_scalars + kScalarCand, st2);
       hipLaunchKernelGGL(cand_compact_kernel, dim3(cand_blocks), dim3(kBlock), 0, st2, VA, VB, d_cand_bcnt, d_cand_boff, cand.tile, n,
                          X1, d_node_of_slot);
       WP_HIP(hipMemcpyAsync(c->h_scalars + kScalarCand, c->d_scalars + kScalarCand, sizeof(uint32_t), hipMemcpyDeviceToHost, st2));
-      WP_HIP(hipEventRecord(c->evs[8], st2));
+      WP_HIP(hipEventRecord(c->evs[kEvCandCount], st2));
     }
     WP_LAUNCH_CHECK();
   }
@@ -587,8 +587,8 @@ struct LinearPath {
       drop.d_kept = c->d_scalars + kScalarKept;
       drop.h_kept = c->h_scalars + kScalarKept;
       drop.side = st2;
-      drop.spine_done = c->evs[9];
-      drop.copied = c->evs[10];
+      drop.spine_done = c->evs[kEvSpine];
+      drop.copied = c->evs[kEvKept];
       cur = radix_sort_pairs<Key0>(sk, keys_only ? nullptr : VA, KB, keys_only ? nullptr : VB, n, 0, kKeyBits, d_radix_tmp, radix_words,
                                    st, &c->rstats, true, code.uniform_bits ? 0 : 8, db, true, hist_in_keys ? &sort_plan : nullptr, KA,
                                    drop_blanks ? &drop : nullptr);
@@ -642,7 +642,7 @@ struct LinearPath {
   // side stream, beside the keys-only passes (a few percent of their bytes), and the run of every slot.  The host reads
   // the list length, known long before the queued passes end.  Ping-pong through VA / VB.
   void sort_candidates() {
-    WP_HIP(hipEventSynchronize(c->evs[8]));
+    WP_HIP(hipEventSynchronize(c->evs[kEvCandCount]));
     n_cand = c->h_scalars[kScalarCand];
     S.round0_candidates = static_cast<int64_t>(n_cand);
     WP_HIP(hipMemsetAsync(d_cand_lo, 0, claim_size * sizeof(uint32_t), st2));
@@ -671,10 +671,11 @@ struct LinearPath {
   bool classify_groups(size_t list_len) {
     if (list_len <= static_cast<size_t>(kLsMaxGroup)) return false;  // no group can be large
     const size_t cap = list_len / 2 + 1;                              // a group has >= 2 entries
-    WP_HIP(hipMemsetAsync(c->d_scalars + 6, 0, 2 * sizeof(uint32_t), st2));
+    clear_scalars(c, kScalarListLargeGroups, kScalarListLargeEntries, st2);
     hipLaunchKernelGGL(large_groups_kernel, dim3(std::min<size_t>(cdiv(cap, kBlock), 2048)), dim3(kBlock), 0, st2, d_ghead,
-                       c->d_scalars + 5, reinterpret_cast<unsigned long long *>(c->d_scalars + 6), d_lg_head, d_lg_off);
-    hipLaunchKernelGGL(large_groups_close_kernel, dim3(1), dim3(1), 0, st2, c->d_scalars + 6, d_lg_off);
+                       c->d_scalars + kScalarListGroups, reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarListLargeGroups),
+                       d_lg_head, d_lg_off);
+    hipLaunchKernelGGL(large_groups_close_kernel, dim3(1), dim3(1), 0, st2, c->d_scalars + kScalarListLargeGroups, d_lg_off);
     return true;
   }
 
@@ -748,7 +749,7 @@ struct LinearPath {
       if (start_after) WP_HIP(hipStreamWaitEvent(st2, start_after, 0));
       WP_HIP(hipMemsetAsync(d_claim, 0xff, claim_size * sizeof(uint32_t), st2));
       WP_HIP(hipMemsetAsync(d_claim_need, 0, claim_size * sizeof(uint32_t), st2));
-      NeededList nl{slots, avals, AG, adep, d_ghead, d_gfirst, d_gdep, reinterpret_cast<unsigned long long *>(c->d_scalars + 4),
+      NeededList nl{slots, avals, AG, adep, d_ghead, d_gfirst, d_gdep, reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarList),
                     static_cast<uint32_t *>(nullptr), need_depth, d_claim_need, d_gclaim, d_gneed0,
                     keys_only ? d_gcand : nullptr, keys_only ? cand_runs.pos : nullptr, keys_only ? n_cand : 0};
       const TokenTrie trie{c->d_lt_chain_len, c->d_lt_chain_off, c->d_lt_child_begin, c->d_lt_child_node, d_child_sym};
@@ -763,11 +764,11 @@ struct LinearPath {
                            d_claim, static_cast<uint32_t>(claim_size - 1), nl, text_only ? d_rng_lo : nullptr, d_rng_hi, d_rng_long,
                            cand_runs);
       }
-      hipLaunchKernelGGL(needed_list_clamp_kernel, dim3(1), dim3(1), 0, st2, c->d_scalars + 4, static_cast<uint32_t>(list_cap),
-                         c->d_scalars + 8);
-      hipLaunchKernelGGL(needed_list_close_kernel, dim3(1), dim3(1), 0, st2, c->d_scalars + 4, d_ghead);
+      hipLaunchKernelGGL(needed_list_clamp_kernel, dim3(1), dim3(1), 0, st2, c->d_scalars + kScalarList, static_cast<uint32_t>(list_cap),
+                         c->d_scalars + kScalarListWanted);
+      hipLaunchKernelGGL(needed_list_close_kernel, dim3(1), dim3(1), 0, st2, c->d_scalars + kScalarList, d_ghead);
       if (key_lookup) {  // (the group heads are overwritten by the trie round: the group ends are taken now)
-        hipLaunchKernelGGL(group_starts_kernel, dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st2, d_gfirst, d_ghead, c->d_scalars + 4,
+        hipLaunchKernelGGL(group_starts_kernel, dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st2, d_gfirst, d_ghead, c->d_scalars + kScalarList,
                            n_sorted, d_ps0 + P, d_gend);
       }
       if (M > 0) {
@@ -776,11 +777,11 @@ struct LinearPath {
         if (use_trie) {
           hipLaunchKernelGGL(HIP_KERNEL_NAME(trie_group_start_kernel<SymT>), dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st2, vals,
                              keys_only ? cand_runs.pos : nullptr, d_gcand, d_gfirst,
-                             d_gdep, c->d_scalars + 4, d_sym, n, d_vsym, trie, d_gnode, d_gdone);
+                             d_gdep, c->d_scalars + kScalarList, d_sym, n, d_vsym, trie, d_gnode, d_gdone);
         }
       }
       // (from here on the side stream no longer reads the sorted keys and suffixes: the rank store may reuse them)
-      WP_HIP(hipEventRecord(c->evs[3], st2));
+      WP_HIP(hipEventRecord(c->evs[kEvKeysFree], st2));
       if (use_trie) trie_round_sizes();
     };
     // (they start when the sort ends, beside the first partition pass's histogram: started beside its scatter instead,
@@ -816,18 +817,18 @@ struct LinearPath {
       hipLaunchKernelGGL(HIP_KERNEL_NAME(rerank_apply_kernel<SymT, true>), dim3(tiles), dim3(kBlock), 0, st, LK2, vals,
                          static_cast<const uint32_t *>(nullptr), static_cast<const uint32_t *>(nullptr), d_tdep, n, d_agg, d_sym, n,
                          dcode.first_len, dcode.uniform_bits, rule, d_sa, d_hd_n, d_lcp, slots, avals, AG, adep, d_ghead, d_gdepth,
-                         c->d_scalars + 4);
+                         c->d_scalars + kScalarList);
     }
     uint32_t *rank_vals = slot_ranks ? nullptr : reinterpret_cast<uint32_t *>(d_hd_n);
     auto keys_free = [&] {  // pair b of the rank store holds the sorted keys: the side stream's searches in them must be over
-      if (prune) WP_HIP(hipStreamWaitEvent(st, c->evs[3], 0));
+      if (prune) WP_HIP(hipStreamWaitEvent(st, c->evs[kEvKeysFree], 0));
     };
     // The trie round (side stream) starts when the partition passes are through: its small latency-bound kernels run
     // beside the window store — beside the radix passes they took a quarter of the passes' bandwidth for the same gain.
     auto start_trie_round = [&] {
       if (!use_trie) return;
-      WP_HIP(hipEventRecord(c->evs[4], st));
-      WP_HIP(hipStreamWaitEvent(st2, c->evs[4], 0));
+      WP_HIP(hipEventRecord(c->evs[kEvPartition], st));
+      WP_HIP(hipStreamWaitEvent(st2, c->evs[kEvPartition], 0));
       trie_round_sort();
     };
     if (window_store) {
@@ -856,25 +857,26 @@ struct LinearPath {
   int trie_rb() const { return bit_length(hv.lt_chain_len.size() + 1); }  // second keys: 1 + trie node
   void trie_round_sizes() {
     classified = classify_groups(list_cap);  // (side stream: the table of large groups)
-    WP_HIP(hipMemcpyAsync(c->h_scalars, c->d_scalars, sizeof(uint32_t) * 12, hipMemcpyDeviceToHost, st2));
-    WP_HIP(hipEventRecord(c->evs[2], st2));
+    queue_scalars(c, kScalarAnchorGap, st2);
+    WP_HIP(hipEventRecord(c->evs[kEvScalars], st2));
   }
   void trie_round_sort() {
     const TokenTrie trie{c->d_lt_chain_len, c->d_lt_chain_off, c->d_lt_child_begin, c->d_lt_child_node, d_child_sym};
     // (sizes are read on the device: the launches do not wait for the host to learn them)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(trie_walk_kernel<SymT>), dim3(std::min<size_t>(cdiv(list_cap, kBlock), 16384)), dim3(kBlock), 0,
-                       st2, avals, AG, d_gnode, d_gdone, c->d_scalars + 4, d_sym, n, d_vsym, trie, adep);
-    WP_HIP(hipEventRecord(c->evs[5], st2));  // (the large-group path starts from here, beside the LDS sort: trie_round_finish)
-    hipLaunchKernelGGL(local_sort_kernel, dim3(cdiv(list_cap, kLsT)), dim3(kBlock), 0, st2, avals, AG, adep, c->d_scalars + 4,
+                       st2, avals, AG, d_gnode, d_gdone, c->d_scalars + kScalarList, d_sym, n, d_vsym, trie, adep);
+    WP_HIP(hipEventRecord(c->evs[kEvTrieNodes], st2));  // (the large-group path starts from here, beside the LDS sort: trie_round_finish)
+    hipLaunchKernelGGL(local_sort_kernel, dim3(cdiv(list_cap, kLsT)), dim3(kBlock), 0, st2, avals, AG, adep, c->d_scalars + kScalarList,
                        d_ghead, d_rank, n, trie_rb(), LK0, spare_vals, adep);
   }
   void trie_round_finish() {
-    WP_HIP(hipEventSynchronize(c->evs[2]));
-    n_act = c->h_scalars[4];
-    n_groups = c->h_scalars[5];
-    n_large_groups = classified ? c->h_scalars[6] : 0;
-    n_large = classified ? c->h_scalars[7] : 0;
-    if (c->h_scalars[8] > list_cap) throw ListOverflow{c->h_scalars[8]};  // (the list was kept empty: nothing ran on it)
+    WP_HIP(hipEventSynchronize(c->evs[kEvScalars]));
+    n_act = c->h_scalars[kScalarListEntries];
+    n_groups = c->h_scalars[kScalarListGroups];
+    n_large_groups = classified ? c->h_scalars[kScalarListLargeGroups] : 0;
+    n_large = classified ? c->h_scalars[kScalarListLargeEntries] : 0;
+    // (an overflowing list was kept empty: nothing ran on it)
+    if (c->h_scalars[kScalarListWanted] > list_cap) throw ListOverflow{c->h_scalars[kScalarListWanted]};
     S.active_per_round[0] = static_cast<int64_t>(n);
     uint64_t *skeys = LK0;
     RankEntry *hd = reinterpret_cast<RankEntry *>(LK1);
@@ -883,7 +885,7 @@ struct LinearPath {
       const int rb = trie_rb();
       if (n_large > 0) {  // (second side stream: other list positions than the LDS sort's, scratch of its own)
         hipStream_t st3 = c->stream3;
-        WP_HIP(hipStreamWaitEvent(st3, c->evs[5], 0));
+        WP_HIP(hipStreamWaitEvent(st3, c->evs[kEvTrieNodes], 0));
         const int lgb = bit_length(n_large_groups > 0 ? n_large_groups - 1 : 0);
         hipLaunchKernelGGL(large_extract_kernel, dim3(cdiv(cdiv(n_large, kLxSpan), kBlock / kWave)), dim3(kBlock), 0, st3, avals, adep,
                            d_lg_head, d_lg_off, static_cast<uint32_t>(n_large_groups), n_large, d_rank, n, rb, LK1, LV0, LPOS, adep);
@@ -891,8 +893,8 @@ struct LinearPath {
                                                   radix_tmp_words<uint64_t>(list_cap), st3, nullptr);
         hipLaunchKernelGGL(large_writeback_kernel, dim3(std::min<size_t>(cdiv(n_large, kBlock), 8192)), dim3(kBlock), 0, st3,
                            lc ? LK2 : LK1, lc ? LV1 : LV0, LPOS, n_large, AG, rb, skeys, spare_vals);
-        WP_HIP(hipEventRecord(c->evs[6], st3));
-        WP_HIP(hipStreamWaitEvent(st2, c->evs[6], 0));
+        WP_HIP(hipEventRecord(c->evs[kEvLargeSorted], st3));
+        WP_HIP(hipStreamWaitEvent(st2, c->evs[kEvLargeSorted], 0));
       }
       DepthRule rrule{need_depth, 0, nullptr, nullptr, 1, d_node_of_slot};  // final round: every group retires
       const unsigned tiles = cdiv(n_act, kRrTile);
@@ -902,7 +904,7 @@ struct LinearPath {
       hipLaunchKernelGGL(rerank_prefix_kernel, dim3(cdiv(tiles, kRrChunk)), dim3(kBlock), 0, st2, d_agg, d_chunk_agg, tiles);
       hipLaunchKernelGGL(HIP_KERNEL_NAME(rerank_apply_kernel<SymT, false>), dim3(tiles), dim3(kBlock), 0, st2, skeys, spare_vals, slots,
                          adep, d_tdep, n_act, d_agg, d_sym, n, dcode.first_len, dcode.uniform_bits, rrule, d_sa, hd, d_lcp,
-                         other_slots, avals, AG, other_dep, d_ghead, d_gdepth, c->d_scalars + 4);
+                         other_slots, avals, AG, other_dep, d_ghead, d_gdepth, c->d_scalars + kScalarList);
     }
     join();  // the rank table is complete (main stream) and the new ranks are known (side stream)
     if (n_act > 0) {
@@ -916,18 +918,19 @@ struct LinearPath {
   // LDS segmented sort of the next round are queued first — the sort reads its sizes on the device and gets a grid for
   // the largest possible list — and only then does the host wait for the copy: the round trip hides behind the sort.
   void next_round_begin(size_t upper, int rb) {
-    WP_HIP(hipMemcpyAsync(c->h_scalars, c->d_scalars, sizeof(uint32_t) * 12, hipMemcpyDeviceToHost, st));
-    WP_HIP(hipEventRecord(c->evs[2], st));
+    queue_scalars(c, kScalarAnchorGap, st);
+    WP_HIP(hipEventRecord(c->evs[kEvScalars], st));
     fork();  // the large-group path of the next round (side stream) may start from here
     if (upper > 0) {
-      hipLaunchKernelGGL(local_sort_kernel, dim3(cdiv(upper, kLsT)), dim3(kBlock), 0, st, avals, AG, adep, c->d_scalars + 4, d_ghead,
+      hipLaunchKernelGGL(local_sort_kernel, dim3(cdiv(upper, kLsT)), dim3(kBlock), 0, st, avals, AG, adep, c->d_scalars + kScalarList, d_ghead,
                          d_rank, n, rb, LK0, spare_vals, static_cast<const uint32_t *>(nullptr));
     }
-    WP_HIP(hipEventSynchronize(c->evs[2]));
-    n_act = c->h_scalars[4];
-    n_large_groups = classified ? c->h_scalars[6] : 0;
-    n_large = classified ? c->h_scalars[7] : 0;
-    if (c->h_scalars[8] > list_cap) throw ListOverflow{c->h_scalars[8]};  // (the list was kept empty: nothing ran on it)
+    WP_HIP(hipEventSynchronize(c->evs[kEvScalars]));
+    n_act = c->h_scalars[kScalarListEntries];
+    n_large_groups = classified ? c->h_scalars[kScalarListLargeGroups] : 0;
+    n_large = classified ? c->h_scalars[kScalarListLargeEntries] : 0;
+    // (an overflowing list was kept empty: nothing ran on it)
+    if (c->h_scalars[kScalarListWanted] > list_cap) throw ListOverflow{c->h_scalars[kScalarListWanted]};
   }
 
   // ---- rounds >= 1 over the active list --------------------------------------------------------------------------
@@ -993,7 +996,7 @@ struct LinearPath {
       hipLaunchKernelGGL(rerank_prefix_kernel, dim3(cdiv(tiles, kRrChunk)), dim3(kBlock), 0, st, d_agg, d_chunk_agg, tiles);
       hipLaunchKernelGGL(HIP_KERNEL_NAME(rerank_apply_kernel<SymT, false>), dim3(tiles), dim3(kBlock), 0, st, skeys, svals, slots,
                          adep, d_tdep, n_act, d_agg, d_sym, n, dcode.first_len, dcode.uniform_bits, rrule, d_sa, hd, d_lcp,
-                         other_slots, nvals, AG, other_dep, d_ghead, d_gdepth, c->d_scalars + 4);
+                         other_slots, nvals, AG, other_dep, d_ghead, d_gdepth, c->d_scalars + kScalarList);
       fork();
       // (scratch of the partitioned store: behind the rank entries in their buffer, and the sorted keys)
       store_ranks(svals, hd, reinterpret_cast<uint32_t *>(hd) + list_cap + 2, reinterpret_cast<uint32_t *>(skeys), n_act);
@@ -1121,10 +1124,10 @@ struct LinearPath {
     uint32_t *d_lw_off = d_tile_scratch + 2 * static_cast<size_t>(lw_cap);
     uint32_t *d_lw_fail = d_lw_off + lw_cap + 1;
     hipLaunchKernelGGL(long_word_collect_kernel, dim3(std::min<size_t>(cdiv(std::max<size_t>(n_anchors, 1), kBlock), 2048)),
-                       dim3(kBlock), 0, st, d_anchors, c->d_scalars + 10, n_text, d_cls, d_lw, lw_cap, c->d_scalars + 12);
+                       dim3(kBlock), 0, st, d_anchors, c->d_scalars + kScalarAnchors, n_text, d_cls, d_lw, lw_cap, c->d_scalars + kScalarLongWords);
     WP_LAUNCH_CHECK();
-    fetch_scalars(c, 13);
-    const uint32_t nw = std::min(c->h_scalars[12], lw_cap);
+    fetch_scalars(c, kScalarLongWords);
+    const uint32_t nw = std::min(c->h_scalars[kScalarLongWords], lw_cap);
     if (nw == 0) return;
     S.walk.n_long_words = static_cast<int64_t>(nw);
     std::vector<LongWord> h_lw(nw);
@@ -1182,7 +1185,7 @@ struct LinearPath {
     uint32_t *d_ns_tiles = d_wp_tiles + rtiles + 1;     // same for non-space positions
     uint32_t *d_gap_a = d_ns_tiles + rtiles + 1, *d_gap_b = d_gap_a + rtiles + 1;  // where the coverage rule applies
     // (the class-rule anchor list is still in d_anchors: the coverage rule is only needed inside its long gaps)
-    hipLaunchKernelGGL(gap_tiles_kernel, dim3(cdiv(rtiles, kBlock)), dim3(kBlock), 0, st, d_anchors, c->d_scalars + 10, n_text, rtiles,
+    hipLaunchKernelGGL(gap_tiles_kernel, dim3(cdiv(rtiles, kBlock)), dim3(kBlock), 0, st, d_anchors, c->d_scalars + kScalarAnchors, n_text, rtiles,
                        v->cover_anchors ? 1 : 0, d_gap_a, d_gap_b);
     hipLaunchKernelGGL(reach_kernel, dim3(rtiles), dim3(kBlock), 0, st, wa, d_reach, d_reach_tiles, d_gap_a, d_gap_b);
     hipLaunchKernelGGL(reach_spine_kernel, dim3(1), dim3(1024), 0, st, d_reach_tiles, static_cast<size_t>(rtiles));
@@ -1190,15 +1193,15 @@ struct LinearPath {
     hipLaunchKernelGGL(cover_flags_kernel, dim3(rtiles), dim3(kBlock), 0, st, d_cls, d_reach, d_reach_tiles, n_text, d_aflags,
                        d_wp_tiles, d_ns_tiles, d_gap_a, d_gap_b, d_anchor_cnt);
     hipLaunchKernelGGL(suffix_min_kernel, dim3(2), dim3(1024), 0, st, d_wp_tiles, d_ns_tiles, static_cast<size_t>(rtiles));
-    device_exclusive_scan(d_anchor_cnt, d_anchor_cnt, atiles, d_anchor_tmp, c->d_scalars + 10, st);  // (counted by cover_flags_kernel)
+    device_exclusive_scan(d_anchor_cnt, d_anchor_cnt, atiles, d_anchor_tmp, c->d_scalars + kScalarAnchors, st);  // (counted by cover_flags_kernel)
     hipLaunchKernelGGL(anchor_write_kernel, dim3(atiles), dim3(kBlock), 0, st, d_cls, d_aflags, n_text, d_anchor_cnt, d_anchors);
     WP_LAUNCH_CHECK();
-    fetch_scalars(c, 11);
+    fetch_scalars(c, kScalarAnchors);
     wa.aflags = d_aflags;
     wa.wp_from_tile = d_wp_tiles;
     wa.ns_from_tile = d_ns_tiles;
     S.anchor_mode = 1;
-    return c->h_scalars[10];
+    return c->h_scalars[kScalarAnchors];
   }
 
   // ---- greedy walk + id stream (linear.cpp:215-316).  Slabs: round-0 keys KA (key_lookup), ids VB, id lists X0, wide
@@ -1212,9 +1215,9 @@ struct LinearPath {
                 key_lookup ? reinterpret_cast<const uint32_t *>(KA) : nullptr, ksteps, drop_blanks ? 1 : 0};
     S.anchor_mode = 0;
     join();  // (the anchor list of the side stream)
-    fetch_scalars(c, 12);
-    size_t n_anchors = c->h_scalars[10];
-    const size_t max_anchor_gap = c->h_scalars[11];
+    fetch_scalars(c, kScalarAnchorGap);
+    size_t n_anchors = c->h_scalars[kScalarAnchors];
+    const size_t max_anchor_gap = c->h_scalars[kScalarAnchorGap];
     S.walk.max_anchor_gap = static_cast<int32_t>(max_anchor_gap);
     const bool all_hard = hv.soft.empty();
     bool staged = staged_possible && max_anchor_gap <= kMaxAnchorGap;
@@ -1239,53 +1242,53 @@ struct LinearPath {
       if (S.anchor_mode == 0 && all_hard && max_anchor_gap > kWideMin) {
         uint32_t *d_wide_list = reinterpret_cast<uint32_t *>(KB), *d_wide_cnt = VA;
         wide_ran = true;
-        WP_HIP(hipMemsetAsync(c->d_scalars + 13, 0, sizeof(uint32_t), st));
+        clear_scalars(c, kScalarWideWords, kScalarWideWords, st);
         hipLaunchKernelGGL(wide_collect_kernel, dim3(std::min<size_t>(cdiv(acap, kBlock), 2048)), dim3(kBlock), 0, st, d_anchors,
-                           c->d_scalars + 10, n_text, d_wide_list, c->d_scalars + 13);
+                           c->d_scalars + kScalarAnchors, n_text, d_wide_list, c->d_scalars + kScalarWideWords);
         WalkArgs wa_all = wa;  // (every position of the wide words is looked up: the small index)
         wa_all.steps = steps_all;
         wa_all.ksteps = ksteps_all;
         const dim3 wgrid(std::min<size_t>(cdiv(acap, kBlock / kWave), 8192));
         if (offs) {
-          hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_wide_kernel<true>), wgrid, dim3(kBlock), 0, st, wa_all, d_anchors, c->d_scalars + 10,
-                             d_wide_list, c->d_scalars + 13, d_wide_cnt, d_ospill);
+          hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_wide_kernel<true>), wgrid, dim3(kBlock), 0, st, wa_all, d_anchors, c->d_scalars + kScalarAnchors,
+                             d_wide_list, c->d_scalars + kScalarWideWords, d_wide_cnt, d_ospill);
           hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_lean_kernel<true, true>), dim3(sblocks), dim3(kBlock), 0, st, wa, d_anchors,
-                             c->d_scalars + 10, acap, d_ctmp, d_blk_cnt, d_wide_cnt, d_ospill, d_cspan);
+                             c->d_scalars + kScalarAnchors, acap, d_ctmp, d_blk_cnt, d_wide_cnt, d_ospill, d_cspan);
         } else {
-          hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_wide_kernel<false>), wgrid, dim3(kBlock), 0, st, wa_all, d_anchors, c->d_scalars + 10,
-                             d_wide_list, c->d_scalars + 13, d_wide_cnt, static_cast<uint2 *>(nullptr));
+          hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_wide_kernel<false>), wgrid, dim3(kBlock), 0, st, wa_all, d_anchors, c->d_scalars + kScalarAnchors,
+                             d_wide_list, c->d_scalars + kScalarWideWords, d_wide_cnt, static_cast<uint2 *>(nullptr));
           hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_lean_kernel<true, false>), dim3(sblocks), dim3(kBlock), 0, st, wa, d_anchors,
-                             c->d_scalars + 10, acap, d_ctmp, d_blk_cnt, d_wide_cnt, static_cast<uint2 *>(nullptr),
+                             c->d_scalars + kScalarAnchors, acap, d_ctmp, d_blk_cnt, d_wide_cnt, static_cast<uint2 *>(nullptr),
                              static_cast<uint2 *>(nullptr));
         }
       } else if (offs) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_lean_kernel<false, true>), dim3(sblocks), dim3(kBlock), 0, st, wa, d_anchors,
-                           c->d_scalars + 10, acap, d_ctmp, d_blk_cnt, static_cast<const uint32_t *>(nullptr), d_ospill, d_cspan);
+                           c->d_scalars + kScalarAnchors, acap, d_ctmp, d_blk_cnt, static_cast<const uint32_t *>(nullptr), d_ospill, d_cspan);
       } else {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_lean_kernel<false, false>), dim3(sblocks), dim3(kBlock), 0, st, wa, d_anchors,
-                           c->d_scalars + 10, acap, d_ctmp, d_blk_cnt, static_cast<const uint32_t *>(nullptr),
+                           c->d_scalars + kScalarAnchors, acap, d_ctmp, d_blk_cnt, static_cast<const uint32_t *>(nullptr),
                            static_cast<uint2 *>(nullptr), static_cast<uint2 *>(nullptr));
       }
-      device_exclusive_scan(d_blk_cnt, d_blk_off, sblocks, d_emit_tmp, c->d_scalars + 9, st);
+      device_exclusive_scan(d_blk_cnt, d_blk_off, sblocks, d_emit_tmp, c->d_scalars + kScalarIds, st);
       if (offs) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(emit_gather_kernel<true>), dim3(sblocks), dim3(kBlock), 0, st, d_anchors, c->d_scalars + 10,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(emit_gather_kernel<true>), dim3(sblocks), dim3(kBlock), 0, st, d_anchors, c->d_scalars + kScalarAnchors,
                            acap, d_ctmp, d_blk_cnt, d_blk_off, d_ids, kWbWords, static_cast<const uint2 *>(d_cspan), d_offs);
       } else {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(emit_gather_kernel<false>), dim3(sblocks), dim3(kBlock), 0, st, d_anchors, c->d_scalars + 10,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(emit_gather_kernel<false>), dim3(sblocks), dim3(kBlock), 0, st, d_anchors, c->d_scalars + kScalarAnchors,
                            acap, d_ctmp, d_blk_cnt, d_blk_off, d_ids, kWbWords, static_cast<const uint2 *>(nullptr),
                            static_cast<uint2 *>(nullptr));
       }
     } else {
       if (offs) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_kernel<true>), dim3(cdiv(acap, kBlock)), dim3(kBlock), 0, st, wa, d_anchors,
-                           c->d_scalars + 10, acap, d_ospill);
+                           c->d_scalars + kScalarAnchors, acap, d_ospill);
       } else {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_kernel<false>), dim3(cdiv(acap, kBlock)), dim3(kBlock), 0, st, wa, d_anchors,
-                           c->d_scalars + 10, acap, static_cast<uint2 *>(nullptr));
+                           c->d_scalars + kScalarAnchors, acap, static_cast<uint2 *>(nullptr));
       }
       const unsigned tiles = cdiv(n_text, kScanTile);
       hipLaunchKernelGGL(emit_count_kernel, dim3(tiles), dim3(kBlock), 0, st, d_emit, n_text, d_emit_cnt);
-      device_exclusive_scan(d_emit_cnt, d_emit_cnt, tiles, d_emit_tmp, c->d_scalars + 9, st);
+      device_exclusive_scan(d_emit_cnt, d_emit_cnt, tiles, d_emit_tmp, c->d_scalars + kScalarIds, st);
       if (offs) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(emit_write_kernel<true>), dim3(tiles), dim3(kBlock), 0, st, d_emit, n_text, d_emit_cnt, d_ids,
                            static_cast<const uint2 *>(d_ospill), d_offs);
@@ -1340,8 +1343,8 @@ struct LinearPath {
   void finish(int32_t *d_ids, size_t *n_ids_out) {
     c->d_offs = nullptr;
     if (offs_unit >= 0 && n_text > 0) {
-      fetch_scalars(c, 10);
-      const size_t n_ids = c->h_scalars[9];
+      fetch_scalars(c, kScalarIds);
+      const size_t n_ids = c->h_scalars[kScalarIds];
       if (rows) row_structure(n_ids);
       if (nmap) {  // normalised code points -> the caller's text, in either unit (a documents call without offsets: not needed)
         if (n_ids > 0 && (!rows || rows->unit >= 0)) {
@@ -1368,13 +1371,13 @@ struct LinearPath {
     }
     if (ar.guard) {  // debugging aid: no kernel may have written outside the buffer it was given
       static const uint32_t init[2] = {0u, 0xffffffffu};
-      WP_HIP(hipMemcpyAsync(c->d_scalars + 16, init, sizeof(init), hipMemcpyHostToDevice, st));
-      ar.check(st, c->d_scalars + 16);
-      aa.check(st, c->d_scalars + 16);
-      fetch_scalars(c, 18);
-      if (c->h_scalars[16] != 0) {
-        throw HipError("arena guard: " + std::to_string(c->h_scalars[16]) + " guard zone(s) overwritten, first behind allocation #" +
-                       std::to_string(c->h_scalars[17] - 1));
+      WP_HIP(hipMemcpyAsync(c->d_scalars + kScalarGuard, init, sizeof(init), hipMemcpyHostToDevice, st));
+      ar.check(st, c->d_scalars + kScalarGuard);
+      aa.check(st, c->d_scalars + kScalarGuard);
+      fetch_scalars(c, kScalarGuardFirst);
+      if (c->h_scalars[kScalarGuardBad] != 0) {
+        throw HipError("arena guard: " + std::to_string(c->h_scalars[kScalarGuardBad]) + " guard zone(s) overwritten, first behind allocation #" +
+                       std::to_string(c->h_scalars[kScalarGuardFirst] - 1));
       }
       S.guard_zones = static_cast<int32_t>(ar.zones.size() + aa.zones.size());
     }
@@ -1382,9 +1385,7 @@ struct LinearPath {
     {
       unsigned int oob[kBoundSites] = {};
       WP_HIP(hipStreamSynchronize(st));
-      WP_HIP(hipMemcpyFromSymbol(oob, HIP_SYMBOL(g_wp_oob), sizeof(oob)));
-      const unsigned int zero[kBoundSites] = {};
-      WP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_wp_oob), zero, sizeof(zero)));
+      take_oob(0, kBoundSites, oob);
       if (oob[0] | oob[1] | oob[2] | oob[3] | oob[4] | oob[5] | oob[6] | oob[7] | oob[8]) {
         throw HipError("debug bounds: out-of-range addresses skipped: radix scatter " + std::to_string(oob[0]) + ", rank store " +
                        std::to_string(oob[1]) + ", token id " + std::to_string(oob[2]) + ", list slot " + std::to_string(oob[3]) +
@@ -1396,10 +1397,10 @@ struct LinearPath {
       S.reserved0 = 1;  // this is the bounds-checking build
     }
 #endif
-    fetch_scalars(c, 20);
-    const size_t n_ids = n_text > 0 ? c->h_scalars[9] : 0;
+    fetch_scalars(c, kScalarFree18);
+    const size_t n_ids = n_text > 0 ? c->h_scalars[kScalarIds] : 0;
     S.n_ids = static_cast<int64_t>(n_ids);
-    S.walk.n_wide_words = wide_ran ? static_cast<int64_t>(c->h_scalars[13]) : 0;  // (cleared only when that branch runs)
+    S.walk.n_wide_words = wide_ran ? static_cast<int64_t>(c->h_scalars[kScalarWideWords]) : 0;  // (cleared only when that branch runs)
     S.radix_passes = c->rstats.passes;
     S.radix_pass_elems = c->rstats.elems;
     S.radix_digit_bytes = c->rstats.digit_bytes;
@@ -1411,12 +1412,12 @@ struct LinearPath {
         WP_HIP(hipEventElapsedTime(&ms, c->ev[a], c->ev[b]));
         return static_cast<double>(ms);
       };
-      S.ms_decode = span(0, 2);
-      S.ms_sa = span(2, 3);
-      S.ms_lcp = span(3, 4);
-      S.ms_scan = span(4, 5);
-      S.ms_walk = span(5, 6);
-      S.ms_total = span(0, 6) + S.ms_normalize;
+      S.ms_decode = span(kMarkStart, kMarkSymbols);
+      S.ms_sa = span(kMarkSymbols, kMarkSorted);
+      S.ms_lcp = span(kMarkSorted, kMarkLcp);
+      S.ms_scan = span(kMarkLcp, kMarkScanned);
+      S.ms_walk = span(kMarkScanned, kMarkWalked);
+      S.ms_total = span(kMarkStart, kMarkWalked) + S.ms_normalize;
       S.ms_radix_scatter = c->rstats.spans.resolve();
     }
     c->d_ids = d_ids;
@@ -1436,23 +1437,23 @@ struct LinearPath {
   void run(size_t *n_ids_out) {
     plan();
     symbols_and_keys();
-    if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[2], st));
+    if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[kMarkSymbols], st));
     sort_round0();
     ranks_round0();
     refine();
-    if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[3], st));
+    if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[kMarkSorted], st));
     if (v->lcp_kasai) {  // alternative LCP builder: chunked Kasai exactly as linear.cpp:18-70
       const size_t chunk = 64;
       hipLaunchKernelGGL(HIP_KERNEL_NAME(kasai_kernel<SymT>), dim3(cdiv(cdiv(n, chunk), kBlock)), dim3(kBlock), 0, st, d_sym, d_sa,
                          d_rank, n, chunk, d_lcp);
       WP_LAUNCH_CHECK();
     }
-    if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[4], st));
+    if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[kMarkLcp], st));
     scanlines();
-    if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[5], st));
+    if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[kMarkScanned], st));
     size_t n_ids = 0;
     int32_t *d_ids = walk(&n_ids);
-    if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[6], st));
+    if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[kMarkWalked], st));
     finish(d_ids, n_ids_out);
   }
 };
@@ -1509,7 +1510,7 @@ static void encode_on_device(const wp_vocab *v, Context *c, const uint8_t *d_tex
   c->rstats.bytes = 0;
   c->rstats.spans.on = v->stage_timing;
   c->rstats.spans.used = 0;
-  if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[0], st));
+  if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[kMarkStart], st));
 
   // ---------------- phase A: decode ----------------
   const unsigned dec_tiles = cdiv(nbytes, kDecTile);
@@ -1534,16 +1535,16 @@ static void encode_on_device(const wp_vocab *v, Context *c, const uint8_t *d_tex
   WP_HIP(hipMemsetAsync(c->d_scalars, 0, sizeof(uint32_t) * kScalars, st));
   WP_HIP(hipMemsetAsync(c->d_used, 0, sizeof(uint32_t) * kCpWords, st));
   hipLaunchKernelGGL(decode_count_kernel<true>, dim3(dec_tiles), dim3(kBlock), 0, st, d_text, nbytes, d_tile_cnt,
-                     reinterpret_cast<unsigned long long *>(c->d_scalars + 2), c->d_used);
-  device_exclusive_scan(d_tile_cnt, d_tile_cnt, dec_tiles, d_cnt_tmp, c->d_scalars + 0, st, nullptr,
-                        reinterpret_cast<unsigned long long *>(c->d_scalars + 14));
+                     reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarInvalid), c->d_used);
+  device_exclusive_scan(d_tile_cnt, d_tile_cnt, dec_tiles, d_cnt_tmp, c->d_scalars + kScalarCps, st, nullptr,
+                        reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarCps64));
   // does the text itself hold code point 0 or 1 (the separator)?  (read before the vocab marks its symbols)
   // (bits 0 and 1 of the first bitmap word)
-  WP_HIP(hipMemcpyAsync(c->d_scalars + 20, c->d_used, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+  WP_HIP(hipMemcpyAsync(c->d_scalars + kScalarAlphaWord0, c->d_used, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
   hipLaunchKernelGGL(vocab_alphabet_kernel, dim3(cdiv(hv.used_word_idx.size(), kBlock)), dim3(kBlock), 0, st,
                      c->d_vocab_word_idx, c->d_vocab_word_bits, static_cast<uint32_t>(hv.used_word_idx.size()), c->d_used);
   // alphabet: bitmap -> per-word prefixes + sigma -> lut (dense symbol of a used code point c = lut[c] + 1)
-  hipLaunchKernelGGL(alphabet_prefix_kernel, dim3(1), dim3(kAlphaThreads), 0, st, c->d_used, c->d_scan_tmp, c->d_scalars + 1);
+  hipLaunchKernelGGL(alphabet_prefix_kernel, dim3(1), dim3(kAlphaThreads), 0, st, c->d_used, c->d_scan_tmp, c->d_scalars + kScalarAlphabet);
   hipLaunchKernelGGL(alphabet_lut_kernel, dim3(kCpTableSize / kBlock), dim3(kBlock), 0, st, c->d_used, c->d_scan_tmp, c->d_lut);
   if (rows) {  // the rows of a documents call: counted (lines) or checked (explicit) beside the decode, fetched with its scalars
     if (rows->d_doc_off) {
@@ -1560,7 +1561,7 @@ static void encode_on_device(const wp_vocab *v, Context *c, const uint8_t *d_tex
     }
   }
   WP_LAUNCH_CHECK();
-  fetch_scalars(c, rows ? (v->normalize != 0 ? kScalarSrcRows + 1 : 24) : 22);
+  fetch_scalars(c, rows ? (v->normalize != 0 ? kScalarSrcRows : kScalarRowsCut) : kScalarRows);
   if (rows) {
     if (rows->d_doc_off && c->h_scalars[kScalarRowsBad] != 0) {
       throw std::invalid_argument("document offsets: " + std::to_string(c->h_scalars[kScalarRowsBad]) +
@@ -1572,20 +1573,20 @@ static void encode_on_device(const wp_vocab *v, Context *c, const uint8_t *d_tex
     S.rows_route = 1;
   }
   unsigned long long n_text64;
-  std::memcpy(&n_text64, c->h_scalars + 14, sizeof(n_text64));
+  std::memcpy(&n_text64, c->h_scalars + kScalarCps64, sizeof(n_text64));
   if (n_text64 + 1 + hv.stream.size() > 2000000000ull) throw std::length_error("64bit not implemented");  // linear.cpp:104-106
-  const size_t n_text = c->h_scalars[0];
+  const size_t n_text = c->h_scalars[kScalarCps];
   // Layout of S.  The reference concatenates the whole vocabulary behind the text in every call and batch
   // (linear.cpp:77-101, 333, 347, 367).  Here the vocabulary normally stays out of the suffix sort: S = text . 1,
   // and the tokens come in through their code streams (prune.h).  The reference's layout is kept for the true
   // suffix array (full depth, duplicate vocab lines), for texts or tokens that hold the code points 0 / 1
   // (they sort around the separator), and on request (WP_OPT_VOCAB_IN_S).
   const bool full_sa = v->full_depth || hv.n_dup_eligible > 0 || v->lcp_kasai;
-  const bool text_only = !full_sa && !v->vocab_in_s && !EnvOptions::get().vocab_in_s && !hv.low_cp && (c->h_scalars[20] & 3u) == 0;
+  const bool text_only = !full_sa && !v->vocab_in_s && !EnvOptions::get().vocab_in_s && !hv.low_cp && (c->h_scalars[kScalarAlphaWord0] & 3u) == 0;
   S.vocab_in_s = text_only ? 0 : 1;
-  const uint32_t sigma = c->h_scalars[1];
+  const uint32_t sigma = c->h_scalars[kScalarAlphabet];
   unsigned long long dropped;
-  std::memcpy(&dropped, c->h_scalars + 2, sizeof(dropped));
+  std::memcpy(&dropped, c->h_scalars + kScalarInvalid, sizeof(dropped));
   if (dropped != 0) std::cerr << "WARNING Input contains invalid unicode characters." << std::endl;
 
   const size_t n = n_text + 1 + (text_only ? 0 : hv.stream.size());  // total_length, linear.cpp:77-82
@@ -1593,7 +1594,7 @@ static void encode_on_device(const wp_vocab *v, Context *c, const uint8_t *d_tex
   S.n_total = static_cast<int64_t>(n);
   S.alphabet = sigma;
   if (n > 2000000000ull) throw std::length_error("64bit not implemented");  // linear.cpp:104-106
-  if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[1], st));
+  if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[kMarkCounted], st));
 
   const int bits = std::max(1, bit_length(sigma));  // symbols are 1..sigma, 0 = past the end
   for (int attempt = 0;; attempt++) {
@@ -1620,7 +1621,7 @@ static void encode_on_device(const wp_vocab *v, Context *c, const uint8_t *d_tex
       c->rstats.digit_bytes = 0;
       c->rstats.bytes = 0;
       c->rstats.spans.used = 0;
-      WP_HIP(hipMemsetAsync(c->d_scalars + 4, 0, sizeof(uint32_t) * 10, st));  // (list sizes, overflow flag, walk counters)
+      clear_scalars(c, kScalarListEntries, kScalarWideWords, st);  // (list sizes, overflow flag, walk counters)
     }
   }
 }

@@ -487,7 +487,9 @@ int wp_get_inputs_stats(const wp_vocab *v, wp_inputs_stats *out);
 /* ---- debug fetch (WP_OPT_KEEP_DEBUG): copies device intermediates to host ----
  * which: 0 S (dense symbols as int32, n), 1 SA (n), 2 rank (n; the full inverse SA is kept only with this option —
  * the default layout otherwise stores ranks for the suffixes of needed groups alone), 3 lcp (n-1; -1 = "at least
- * sorted_depth"), 4 best_prefix (n), 5 best_suffix (n), 6 code points (n_text) */
+ * sorted_depth"), 4 best_prefix (n), 5 best_suffix (n), 6 code points (n_text), 7 class bytes (n_text, as int32:
+ * 1 is_space, 2 is_spacing_char, 4 soft spacing char, 8 is_punctuation; the Linear path's anchor kernels add 16 at a
+ * word-prefix position and 32 at an anchor of the walk) */
 int wp_linear_debug_fetch(const wp_vocab *v, int which, int32_t *out, size_t capacity,
                           size_t *n_out);
 

@@ -314,6 +314,7 @@ struct Context {
     const uint32_t *sa = nullptr, *cps = nullptr;
     const RankEntry *rank = nullptr;
     const int32_t *lcp = nullptr;
+    const uint8_t *cls = nullptr;  // class byte per text position (n_text; kept only with WP_OPT_KEEP_DEBUG)
     StepTable steps{};
     int32_t *best_scratch = nullptr;  // room for 2n int32 (debug expansion of the step functions)
     size_t n = 0, n_text = 0;

@@ -1920,12 +1920,17 @@ int wp_linear_debug_fetch(const wp_vocab *v, int which, int32_t *out, size_t cap
         src = d.cps;
         cnt = d.n_text;
         break;
+      case 7:
+        if (!d.cls) throw std::invalid_argument("class bytes are kept only with WP_OPT_KEEP_DEBUG");
+        src = d.cls;
+        cnt = d.n_text;
+        break;
       default: throw std::invalid_argument("unknown debug array");
     }
     if (cnt > capacity) throw std::invalid_argument("debug buffer too small");
     *n_out = cnt;
     if (cnt == 0) return;
-    if (which == 0 && d.sym_bytes == 1) {
+    if ((which == 0 && d.sym_bytes == 1) || which == 7) {
       std::vector<uint8_t> tmp(cnt);
       WP_HIP(hipMemcpy(tmp.data(), src, cnt, hipMemcpyDeviceToHost));
       for (size_t i = 0; i < cnt; i++) out[i] = tmp[i];

@@ -1429,6 +1429,7 @@ struct LinearPath {
     c->dbg.steps = steps;
     c->dbg.best_scratch = d_dbg_best;
     c->dbg.cps = d_cps;
+    c->dbg.cls = v->keep_debug ? d_cls : nullptr;
     c->dbg.n = n;
     c->dbg.n_text = n_text;
     *n_ids_out = n_ids;

@@ -473,6 +473,25 @@ typedef struct {
                              the fast path) a distance above 2048 is measured up to the first blank and stops at 2049 */
 } wp_walk_stats;
 int wp_get_walk_stats(const wp_vocab *v, wp_walk_stats *out);
+/* The refinement's part of the statistics of the last encode, in a struct of its own for the same reason: what the
+ * stage between round 0 and the walk ran on (the needed groups along the token trie by default, the first doubling
+ * round otherwise).  Taken from values the host holds at that point (no extra wait, no extra kernel).  All zero when
+ * the stage was not reached (an empty text, the fast path); the four counts are zero when nothing was on the list.  Sharded and pipelined calls report the sums
+ * of the four counts and the first text's other fields. */
+typedef struct {
+  int64_t n_groups;         /* groups on the list of the first refinement round (trie round: the needed groups)         */
+  int64_t n_entries;        /* its entries; wp_stats.needed_after_round0 when round 0 was pruned                         */
+  int64_t n_large_groups;   /* groups of more than 2048 entries, sorted by the global radix path instead of in LDS;
+                               0 when the list was too short for one (no classification ran)                             */
+  int64_t n_large_entries;  /* their entries                                                                             */
+  int64_t trie_nodes;       /* nodes of the trie of the long tokens (a property of the vocabulary)                       */
+  int32_t sort_bits;        /* bits of the second key the segmented sort ran with: bit_length(trie_nodes + 1) in the trie
+                               round, bit_length(n_total) in a doubling round                                            */
+  int32_t key_lookup;       /* 1: the walk looked its steps up by round-0 key and no full rank table was built           */
+  int32_t symbol_bytes;     /* width of a dense symbol: 1 (alphabets up to 255), else 4                                  */
+  int32_t reserved;
+} wp_refine_stats;
+int wp_get_refine_stats(const wp_vocab *v, wp_refine_stats *out);
 /* The model-inputs part of the statistics of the last call, in a struct of its own for the same reason.  After an
  * inputs call wp_stats.n_rows, rows_route, offsets_unit and n_ids mean what they mean after a rows call and
  * rows_truncated is 0. */

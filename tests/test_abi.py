@@ -143,3 +143,34 @@ def test_walk_stats_struct_matches_header(tmp_path):
     # without a device the statistics of a handle that never encoded are zero
     ws = W.Vocab(["a"]).walk_stats()
     assert ws == dict(n_wide_words=0, n_long_words=0, lean=0, max_anchor_gap=0)
+
+
+def test_refine_stats_struct_matches_header(tmp_path):
+    """wp_refine_stats is a struct of its own (wp_stats keeps its size and its last field): the ctypes mirror follows the
+    header's fields, and both mirrors have the sizes and offsets a C compiler gives the header's structs."""
+    import ctypes as C
+    import subprocess
+    hdr = open(os.path.join(ROOT, "include", "wordpiece_amd.h")).read()
+    body = hdr[hdr.rindex("typedef struct {", 0, hdr.index("} wp_refine_stats;")):hdr.index("} wp_refine_stats;")]
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S).replace("typedef struct {", "")
+    fields = [tuple(decl.split()) for decl in body.split(";") if decl.strip()]
+    widths = {"int64_t": C.c_int64, "int32_t": C.c_int32}
+    assert [(name, widths[ctype]) for ctype, name in fields] == list(W.RefineStats._fields_)
+    assert [name for _, name in fields] == ["n_groups", "n_entries", "n_large_groups", "n_large_entries", "trie_nodes",
+                                            "sort_bits", "key_lookup", "symbol_bytes", "reserved"]
+    assert [f[0] for f in W.Stats._fields_][-1] == "rows_route"
+    probe = ["sizeof(wp_stats)", "offsetof(wp_stats, rows_route)", "sizeof(wp_walk_stats)", "sizeof(wp_refine_stats)"] + \
+            ["offsetof(wp_refine_stats, %s)" % name for _, name in fields]
+    src = tmp_path / "sz.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "wordpiece_amd.h"\nint main(void) {\n' +
+                   "".join('  printf("%%zu ", (size_t)%s);\n' % p for p in probe) + "  return 0;\n}\n")
+    exe = tmp_path / "sz"
+    subprocess.run([os.environ.get("CC", "gcc"), "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)], check=True)
+    got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
+    assert got == [C.sizeof(W.Stats), W.Stats.rows_route.offset, C.sizeof(W.WalkStats), C.sizeof(W.RefineStats)] + \
+                  [getattr(W.RefineStats, name).offset for _, name in fields]
+    assert C.sizeof(W.RefineStats) == 56
+    # without a device the statistics of a handle that never encoded are zero
+    rs = W.Vocab(["a"]).refine_stats()
+    assert rs == dict(n_groups=0, n_entries=0, n_large_groups=0, n_large_entries=0, trie_nodes=0, sort_bits=0, key_lookup=0,
+                      symbol_bytes=0)

@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "wp_linear_encode_offsets", "wp_linear_encode_offsets_device",
     "wp_linear_encode_rows", "wp_linear_encode_rows_device", "wp_linear_encode_padded", "wp_linear_encode_padded_device",
     "wp_normalize_cp", "wp_normalize_device", "wp_normalize", "wp_get_norm_stats", "wp_get_walk_stats",
+    "wp_get_refine_stats",
     "wp_linear_encode_inputs", "wp_linear_encode_inputs_device", "wp_get_inputs_stats",
     "wp_word_ids", "wp_word_ids_device", "wp_mlm_mask", "wp_mlm_mask_device", "wp_get_mask_stats",
 ]
@@ -87,6 +88,13 @@ class WalkStats(C.Structure):
     """wp_walk_stats: which variant of the walk produced the ids of the last encode (Vocab.walk_stats())."""
     _fields_ = [("n_wide_words", C.c_int64), ("n_long_words", C.c_int64), ("lean", C.c_int32),
                 ("max_anchor_gap", C.c_int32)]
+
+
+class RefineStats(C.Structure):
+    """wp_refine_stats: what the refinement between round 0 and the walk ran on in the last encode (Vocab.refine_stats())."""
+    _fields_ = [("n_groups", C.c_int64), ("n_entries", C.c_int64), ("n_large_groups", C.c_int64),
+                ("n_large_entries", C.c_int64), ("trie_nodes", C.c_int64), ("sort_bits", C.c_int32),
+                ("key_lookup", C.c_int32), ("symbol_bytes", C.c_int32), ("reserved", C.c_int32)]
 
 
 class InputsSpec(C.Structure):
@@ -199,6 +207,7 @@ def lib():
         L.wp_get_stats.argtypes = [vp, C.POINTER(Stats)]
         L.wp_get_norm_stats.argtypes = [vp, C.POINTER(NormStats)]
         L.wp_get_walk_stats.argtypes = [vp, C.POINTER(WalkStats)]
+        L.wp_get_refine_stats.argtypes = [vp, C.POINTER(RefineStats)]
         L.wp_linear_debug_fetch.argtypes = [vp, C.c_int, i32p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.wp_free.argtypes = [vp]
         L.wp_free.restype = None
@@ -313,6 +322,13 @@ class Vocab:
         ws = WalkStats()
         _check(lib().wp_get_walk_stats(self._h, C.byref(ws)))
         return {k: int(getattr(ws, k)) for k, _ in ws._fields_}
+
+    def refine_stats(self):
+        """wp_refine_stats of the last encode as a dict: n_groups, n_entries, n_large_groups, n_large_entries,
+        trie_nodes, sort_bits, key_lookup, symbol_bytes."""
+        rs = RefineStats()
+        _check(lib().wp_get_refine_stats(self._h, C.byref(rs)))
+        return {k: int(getattr(rs, k)) for k, _ in rs._fields_ if k != "reserved"}
 
     def encode(self, text):
         """Host UTF-8 bytes/str -> numpy int32 ids (wp_linear_encode)."""

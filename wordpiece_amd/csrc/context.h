@@ -362,12 +362,13 @@ static void take_oob(int first, int count, unsigned int *oob) {
 using namespace wp;
 
 // the statistics of an encode as the device path fills them: wp_stats and, behind it, what wp_get_norm_stats and
-// wp_get_walk_stats hand out
+// wp_get_walk_stats / wp_get_refine_stats hand out
 struct EncodeStats : wp_stats {
   int32_t normalize;
   int64_t norm_bytes;
   double ms_normalize;
   wp_walk_stats walk;
+  wp_refine_stats refine;  // which refinement ran (linear_path.h: trie_round_finish / doubling_rounds)
   wp_inputs_stats inputs;  // wp_get_inputs_stats: filled by an inputs call (inputs_call 1), zero otherwise
   int32_t inputs_call;
   wp_mask_stats mask;  // wp_get_mask_stats: filled by a mask or word-ids call (mask_call 1), zero otherwise

@@ -221,6 +221,11 @@ int wp_get_walk_stats(const wp_vocab *v, wp_walk_stats *out) {
   return WP_OK;
 }
 
+int wp_get_refine_stats(const wp_vocab *v, wp_refine_stats *out) {
+  *out = v->stats.refine;
+  return WP_OK;
+}
+
 int wp_get_inputs_stats(const wp_vocab *v, wp_inputs_stats *out) {
   *out = v->stats.inputs;
   if (!v->stats.inputs_call) out->n_out = -1;
@@ -546,6 +551,10 @@ void encode_multi(wp_vocab *v, const char *utf8, size_t nbytes, const std::vecto
     S.walk.n_wide_words += T.walk.n_wide_words;
     S.walk.n_long_words += T.walk.n_long_words;
     S.walk.max_anchor_gap = std::max(S.walk.max_anchor_gap, T.walk.max_anchor_gap);
+    S.refine.n_groups += T.refine.n_groups;
+    S.refine.n_entries += T.refine.n_entries;
+    S.refine.n_large_groups += T.refine.n_large_groups;
+    S.refine.n_large_entries += T.refine.n_large_entries;
     S.ms_total = std::max(S.ms_total, T.ms_total);
     S.ms_decode = std::max(S.ms_decode, T.ms_decode);
     S.ms_sa = std::max(S.ms_sa, T.ms_sa);
@@ -1565,6 +1574,14 @@ void encode_pipeline(wp_vocab *v, Next &&next, Deliver &&deliver) {
     total.walk.n_long_words += st.walk.n_long_words;
     total.walk.max_anchor_gap = std::max(total.walk.max_anchor_gap, st.walk.max_anchor_gap);
     if (i == 0) total.walk.lean = st.walk.lean;
+    {
+      const wp_refine_stats sum = total.refine;
+      if (i == 0) total.refine = st.refine;  // (the first text's other fields)
+      total.refine.n_groups = sum.n_groups + st.refine.n_groups;
+      total.refine.n_entries = sum.n_entries + st.refine.n_entries;
+      total.refine.n_large_groups = sum.n_large_groups + st.refine.n_large_groups;
+      total.refine.n_large_entries = sum.n_large_entries + st.refine.n_large_entries;
+    }
     total.rounds = std::max(total.rounds, st.rounds);
     if (next_up.valid()) {
       const std::string err = next_up.get();

@@ -869,6 +869,17 @@ struct LinearPath {
     hipLaunchKernelGGL(local_sort_kernel, dim3(cdiv(list_cap, kLsT)), dim3(kBlock), 0, st2, avals, AG, adep, c->d_scalars + kScalarList,
                        d_ghead, d_rank, n, trie_rb(), LK0, spare_vals, adep);
   }
+  // wp_refine_stats: the list of the first refinement round as the host has just learnt it, and what it is sorted with
+  void refine_stats(size_t groups, int rbits) {
+    S.refine.n_groups = static_cast<int64_t>(groups);
+    S.refine.n_entries = static_cast<int64_t>(n_act);
+    S.refine.n_large_groups = static_cast<int64_t>(n_large_groups);
+    S.refine.n_large_entries = static_cast<int64_t>(n_large);
+    S.refine.trie_nodes = static_cast<int64_t>(hv.lt_chain_len.size());
+    S.refine.sort_bits = rbits;
+    S.refine.key_lookup = key_lookup ? 1 : 0;
+    S.refine.symbol_bytes = static_cast<int32_t>(sizeof(SymT));
+  }
   void trie_round_finish() {
     WP_HIP(hipEventSynchronize(c->evs[kEvScalars]));
     n_act = c->h_scalars[kScalarListEntries];
@@ -878,6 +889,7 @@ struct LinearPath {
     // (an overflowing list was kept empty: nothing ran on it)
     if (c->h_scalars[kScalarListWanted] > list_cap) throw ListOverflow{c->h_scalars[kScalarListWanted]};
     S.active_per_round[0] = static_cast<int64_t>(n);
+    refine_stats(n_groups, trie_rb());
     uint64_t *skeys = LK0;
     RankEntry *hd = reinterpret_cast<RankEntry *>(LK1);
     if (n_act > 0) {
@@ -955,6 +967,7 @@ struct LinearPath {
     const DepthRule rule{need_depth, full ? 1 : 0, nullptr, nullptr, 0, nullptr};
     next_round_begin(std::min(n, list_cap), rb);
     S.active_per_round[0] = static_cast<int64_t>(n);
+    refine_stats(c->h_scalars[kScalarListGroups], rb);  // (the list behind round 0: what the first doubling round runs on)
     // behind a pruned round 0 every group carries the depth its own tokens need (DepthRule, prune.h)
     uint32_t *gneed_cur = d_gneed0, *gneed_nxt = d_gneed1;
     const bool group_need = prune && M > 0;

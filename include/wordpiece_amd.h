@@ -246,6 +246,56 @@ typedef struct {
 } wp_mask_stats;
 int wp_get_mask_stats(const wp_vocab *v, wp_mask_stats *out);
 
+/* ---- detokenize (an addition: ids back to text; tokenizers.decoders.WordPiece(prefix="##", cleanup=...), which is what HF
+ * Tokenizer.decode runs; "decode" names the UTF-8 stage in this library, hence the other word) ----
+ * That decoder works token by token: the first token stands as it is, a later one loses a leading "##" or else gets one
+ * space in front, and with cleanup each such per-token string goes through the chain
+ *   " ." -> ".", " ?" -> "?", " !" -> "!", " ," -> ",", " ' " -> "'", " n't" -> "n't", " 'm" -> "'m",
+ *   " do not" -> " don't", " 's" -> "'s", " 've" -> "'ve", " 're" -> "'re"          (in this order, over bytes)
+ * so the text of a row is a plain concatenation of per-id byte strings.  line(i) = wp_vocab_token_utf8(i) with "##" put
+ * back in front when bit 0 of wp_vocab_token_flags(i) is clear; C = the chain with cleanup == 1, the identity with 0:
+ *   form0(i) = C(line(i))                                  — the first kept cell of a row
+ *   form1(i) = C(line(i) without its leading "##")         — a later cell, continuation token
+ *   form1(i) = C(" " + line(i))                            — a later cell, any other token
+ * (The whole-string clean-up that `transformers` may apply on top of Tokenizer.decode works across tokens and is out of
+ * scope.)  V = wp_vocab_size.  For a cell x of row r:
+ *   dropped: x < 0, x >= V, or wp_vocab_token_flags(x) & 4 (malformed) — the ids word_piece::fast::decode skips
+ *   skipped: not dropped, and x is one of skip_ids[0 .. n_skip) (n_skip <= 8): [CLS], [SEP], [PAD] ... (skip_special_tokens)
+ *   kept:    neither.  The row's text: form0 of its first kept cell, form1 of every later kept cell, then, with
+ *   terminator in 0..255, that one byte (empty rows included; -1: nothing).  With '\n' the text is the joined documents
+ *   form wp_linear_encode_rows takes, and text_off its doc_off.
+ * Result: text, n_bytes bytes, the rows back to back; text_off, int64[n_rows + 1], text_off[0] == 0, text_off[n_rows] ==
+ * n_bytes.  Two layouts of the rows, one set of kernels (csrc/detok.h):
+ *   ragged (max_len == 0): ids[row_splits[n_rows]] with row_splits[0 .. n_rows] as wp_linear_encode_rows returns them:
+ *     row_splits[0] == 0, no descent — checked on the host by the host entry point, in a kernel by the device entry
+ *     point, which fails with WP_ERR_ARG before text is produced; lengths is not read
+ *   padded (max_len >= 1): ids[n_rows][max_len] with lengths[n_rows] (NULL: full rows), each clamped to [0, max_len];
+ *     the cells behind a row's length are no cells: not in the text, not in the statistics; row_splits is not read
+ * WP_ERR_ARG (host entry point: before a device is touched): spec NULL, cleanup not 0 / 1, terminator outside [-1, 255],
+ * n_skip outside [0, 8], max_len < 0, a required pointer NULL (a ragged call without row_splits, ids NULL where there
+ * are cells, an out-pointer), bad row_splits, a device pointer that is not aligned to its element.  WP_ERR_TOO_LARGE:
+ * n_rows > INT32_MAX, more than INT32_MAX cells (n_rows * max_len is computed without overflow), or a text of 2^32
+ * bytes or more, found from a 64-bit total before the write pass runs.  The size rules are checked before the pointers.
+ * n_rows == 0: the host entry point needs no device and gives text == NULL, n_bytes == 0 and a one-entry text_off (0).
+ * text == NULL also for n_bytes == 0 with rows.  The device call runs on the handle's device and stream and returns when
+ * the text is complete (it waits for the total to size the text, and a ragged call for the check of row_splits).
+ * The pieces are a per-context table built by a handle's first detokenize call, for both cleanup values at once. */
+typedef struct { int32_t max_len, cleanup, terminator, n_skip; int32_t skip_ids[8]; } wp_detok_spec;
+/* host ids in; text and text_off out as blocks (free each with wp_free) */
+int wp_detokenize(wp_vocab *v, const int32_t *ids, const int64_t *row_splits, const int32_t *lengths, size_t n_rows,
+                  const wp_detok_spec *spec, char **text, int64_t **text_off, size_t *n_bytes);
+/* device ids in; text and text_off in device memory, owned by the handle until its next call */
+int wp_detokenize_device(wp_vocab *v, const int32_t *d_ids, const int64_t *d_row_splits, const int32_t *d_lengths,
+                         size_t n_rows, const wp_detok_spec *spec, const void **d_text, const int64_t **d_text_off,
+                         size_t *n_bytes);
+/* form `form` (0 / 1) of id with cleanup 0 / 1: the host statement of the table the kernels read, without a device.
+ * Returns the byte length and copies at most cap bytes; -1: id out of range or malformed, another form or cleanup. */
+int64_t wp_detok_piece(const wp_vocab *v, int64_t id, int form, int cleanup, char *buf, size_t cap);
+/* The statistics of the last detokenize call, in a struct of its own (wp_stats keeps its size); every other statistic
+ * keeps what the last encode left.  n_cells = n_kept + n_skipped + n_dropped (padded: the cells below the lengths). */
+typedef struct { int64_t n_rows, n_cells, n_kept, n_skipped, n_dropped, n_bytes; } wp_detok_stats;
+int wp_get_detok_stats(const wp_vocab *v, wp_detok_stats *out); /* n_rows == -1: no such call yet */
+
 /* The same call sharded over several GPUs of the node, behind the boundary: the reference's own
  * precedent is the in-library chunking at whitespace of linear.cpp:283-299 (thread chunks) and
  * linear.cpp:355-367 (encodeExternal batches).  The text is cut at ASCII whitespace into one shard

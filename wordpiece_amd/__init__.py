@@ -47,6 +47,7 @@ ABI_SYMBOLS = [
     "wp_get_refine_stats",
     "wp_linear_encode_inputs", "wp_linear_encode_inputs_device", "wp_get_inputs_stats",
     "wp_word_ids", "wp_word_ids_device", "wp_mlm_mask", "wp_mlm_mask_device", "wp_get_mask_stats",
+    "wp_detokenize", "wp_detokenize_device", "wp_detok_piece", "wp_get_detok_stats",
 ]
 
 
@@ -130,6 +131,18 @@ class MaskStats(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class DetokSpec(C.Structure):
+    """wp_detok_spec: the arguments of a detokenize call (max_len 0: ragged rows; terminator -1: none)."""
+    _fields_ = [("max_len", C.c_int32), ("cleanup", C.c_int32), ("terminator", C.c_int32), ("n_skip", C.c_int32),
+                ("skip_ids", C.c_int32 * 8)]
+
+
+class DetokStats(C.Structure):
+    """wp_detok_stats: the statistics of the last detokenize call (Vocab.detok_stats())."""
+    _fields_ = [("n_rows", C.c_int64), ("n_cells", C.c_int64), ("n_kept", C.c_int64), ("n_skipped", C.c_int64),
+                ("n_dropped", C.c_int64), ("n_bytes", C.c_int64)]
+
+
 _TEXT_SOURCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t))
 _IDS_SINK = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.c_size_t)
 
@@ -185,6 +198,13 @@ def lib():
                                   C.POINTER(i32p)]
         L.wp_mlm_mask_device.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(MaskSpec), vp, vp, vp]
         L.wp_get_mask_stats.argtypes = [vp, C.POINTER(MaskStats)]
+        L.wp_detokenize.argtypes = [vp, i32p, C.POINTER(C.c_int64), i32p, C.c_size_t, C.POINTER(DetokSpec),
+                                    C.POINTER(C.c_void_p), C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.c_size_t)]
+        L.wp_detokenize_device.argtypes = [vp, vp, vp, vp, C.c_size_t, C.POINTER(DetokSpec), C.POINTER(C.c_void_p),
+                                           C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        L.wp_detok_piece.argtypes = [vp, C.c_int64, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
+        L.wp_detok_piece.restype = C.c_int64
+        L.wp_get_detok_stats.argtypes = [vp, C.POINTER(DetokStats)]
         L.wp_linear_encode_multi.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.POINTER(i32p),
                                              C.POINTER(C.c_size_t)]
         L.wp_reserve.argtypes = [vp, C.c_size_t]
@@ -660,6 +680,114 @@ class Vocab:
                                         C.c_void_p(res["word_ids"].data_ptr()) if word_ids else None))
         return res
 
+    def detok_stats(self):
+        """wp_detok_stats of the last detokenize call as a dict (n_rows -1: no such call yet)."""
+        s = DetokStats()
+        _check(lib().wp_get_detok_stats(self._h, C.byref(s)))
+        return {k: int(getattr(s, k)) for k, _ in s._fields_}
+
+    def detok_piece(self, id, form, cleanup=True):
+        """The bytes id `id` contributes to a row's text (wp_detok_piece; no GPU needed): form 0 as the first kept
+        token of a row, form 1 behind another; None for an id out of range, a malformed one or another form."""
+        n = lib().wp_detok_piece(self._h, int(id), int(form), int(cleanup), None, 0)
+        if n < 0:
+            return None
+        buf = C.create_string_buffer(max(int(n), 1))
+        lib().wp_detok_piece(self._h, int(id), int(form), int(cleanup), buf, n)
+        return buf.raw[:n]
+
+    def detokenize(self, ids, row_splits=None, lengths=None, skip_ids=(), cleanup=True, terminator=None, raw=False):
+        """Ids back to text on the GPU (wp_detokenize), as tokenizers' WordPiece decoder gives it row by row: a 1-d
+        int32 array with row_splits [n_rows + 1] (what encode_rows returns; without row_splits: one row), or a 2-d
+        array [n_rows, max_len] with optional lengths -> a list of n_rows str (invalid UTF-8, which only a cut through
+        a token's bytes by the clean-up could give, is replaced).  skip_ids: up to 8 ids left out ([CLS], [SEP],
+        [PAD]: skip_special_tokens); ids outside the vocabulary and malformed ones are always dropped.  terminator: a
+        byte (int or 1-char str) behind every row of the raw text.  raw=True: (text bytes, text_off int64 [n_rows + 1])
+        as the library returns them."""
+        a = np.ascontiguousarray(ids, dtype=np.int32)
+        splits = lens = None
+        if a.ndim == 2:
+            if row_splits is not None:
+                raise WordPieceError("row_splits go with a 1-d ids array")
+            n_rows, max_len = a.shape
+            if max_len < 1:
+                raise WordPieceError("a padded batch needs max_len >= 1")
+            if lengths is not None:
+                lens = np.ascontiguousarray(lengths, dtype=np.int32)
+                if lens.shape != (n_rows,):
+                    raise WordPieceError("lengths must be a 1-d array of n_rows entries")
+        elif a.ndim == 1:
+            if lengths is not None:
+                raise WordPieceError("lengths go with a 2-d ids array")
+            splits = np.array([0, len(a)], dtype=np.int64) if row_splits is None else \
+                np.ascontiguousarray(row_splits, dtype=np.int64)
+            if splits.ndim != 1 or len(splits) < 1:
+                raise WordPieceError("row_splits must be a 1-d array of n_rows + 1 entries")
+            if len(splits) > 1 and splits[-1] > len(a):
+                raise WordPieceError("row_splits end behind the ids")
+            n_rows, max_len = len(splits) - 1, 0
+        else:
+            raise WordPieceError("ids must be a 1-d or 2-d array")
+        spec = _detok_spec(max_len, skip_ids, cleanup, terminator)
+        text, off, nb = C.c_void_p(), C.POINTER(C.c_int64)(), C.c_size_t()
+        _check(lib().wp_detokenize(self._h, _i32_ptr(a), _i64_ptr(splits), _i32_ptr(lens), n_rows, C.byref(spec), C.byref(text),
+                                   C.byref(off), C.byref(nb)))
+        text_off = _adopt_block(off, (n_rows + 1,))
+        data = b""
+        if text.value:
+            data = C.string_at(text.value, nb.value)
+            lib().wp_free(text)
+        if raw:
+            return data, text_off
+        t = 1 if spec.terminator >= 0 else 0
+        return [data[text_off[r]:text_off[r + 1] - t].decode("utf-8", "replace") for r in range(n_rows)]
+
+    def detokenize_tensor(self, ids, row_splits=None, lengths=None, skip_ids=(), cleanup=True, terminator=None, copy=True):
+        """detokenize for tensors on this handle's GPU (wp_detokenize_device): ids int32 [n] with row_splits int64
+        [n_rows + 1] (what encode_rows_tensor returns; without row_splits: one row), or ids int32 [n_rows, max_len] with
+        optional lengths int32 [n_rows] -> (text uint8 [n_bytes], text_off int64 [n_rows + 1]) there; nothing leaves
+        the device.  copy=False: views of the library's buffers, valid until the next call on this handle."""
+        import torch
+        if ids.dtype != torch.int32 or not ids.is_cuda or not ids.is_contiguous() or ids.dim() not in (1, 2):
+            raise WordPieceError("detokenize on tensors needs a contiguous int32 CUDA/HIP tensor [n] or [n_rows, max_len]")
+        if self._device is not None and ids.device.index != self._device:  # (raw pointers go to the handle's device)
+            raise WordPieceError("the tensors lie on %s, the handle on device %d" % (ids.device, self._device))
+        dev = ids.device
+        if ids.dim() == 2:
+            if row_splits is not None:
+                raise WordPieceError("row_splits go with a 1-d ids tensor")
+            n_rows, max_len = ids.shape
+            if max_len < 1:
+                raise WordPieceError("a padded batch needs max_len >= 1")
+            if lengths is not None and (lengths.dtype != torch.int32 or lengths.device != dev or not lengths.is_contiguous() or
+                                        lengths.shape != (n_rows,)):
+                raise WordPieceError("lengths must be a contiguous int32 tensor [n_rows] on the device of ids")
+            rows = lengths
+        else:
+            if lengths is not None:
+                raise WordPieceError("lengths go with a 2-d ids tensor")
+            if row_splits is None:
+                row_splits = torch.tensor([0, ids.numel()], dtype=torch.int64, device=dev)
+            if row_splits.dtype != torch.int64 or row_splits.device != dev or row_splits.dim() != 1 or row_splits.numel() < 1:
+                raise WordPieceError("row_splits must be a 1-d int64 tensor on the device of ids")
+            rows = row_splits = row_splits.contiguous()
+            n_rows, max_len = row_splits.numel() - 1, 0
+        for t in (ids, rows):  # (a view of a tensor may start anywhere)
+            if t is not None and t.data_ptr() % t.element_size() != 0:
+                raise WordPieceError("the tensors must be aligned to their element size")
+        spec = _detok_spec(max_len, skip_ids, cleanup, terminator)
+        d_text, d_off, nb = C.c_void_p(), C.c_void_p(), C.c_size_t()
+        torch.cuda.current_stream(dev).synchronize()  # the library runs on its own HIP streams
+        _check(lib().wp_detokenize_device(
+            self._h, C.c_void_p(ids.data_ptr()) if ids.numel() else None,
+            C.c_void_p(row_splits.data_ptr()) if max_len == 0 else None,
+            C.c_void_p(lengths.data_ptr()) if max_len and lengths is not None else None, n_rows, C.byref(spec),
+            C.byref(d_text), C.byref(d_off), C.byref(nb)))
+        text = torch.as_tensor(DeviceIds(d_text.value, nb.value, typestr="|u1"), device=dev) if nb.value else \
+            torch.zeros(0, dtype=torch.uint8, device=dev)
+        off = torch.as_tensor(DeviceIds(d_off.value, n_rows + 1, typestr="<i8"), device=dev)
+        return (text.clone(), off.clone()) if copy else (text, off)
+
     def fast_encode(self, text):
         """word_piece::fast::encode on the GPU (wp_fast_encode): host bytes/str -> numpy int32 ids."""
         b = _bytes(text)
@@ -871,6 +999,18 @@ def _mask_spec(max_len, mask_id, prob, mask_share, random_share, whole_word, see
     return MaskSpec(int(max_len), _special(cls_id), _special(sep_id), _special(pad_id), int(mask_id), int(ignore_id),
                     int(whole_word), 0, q32(prob), q32(mask_share), q32(random_share), int(seed) & (2 ** 64 - 1),
                     int(row_base) & (2 ** 64 - 1))
+
+
+def _detok_spec(max_len, skip_ids, cleanup, terminator):
+    skip = [int(i) for i in skip_ids]
+    if len(skip) > 8:
+        raise WordPieceError("at most 8 skip ids")
+    if isinstance(terminator, (str, bytes)):
+        if len(_bytes(terminator)) != 1:
+            raise WordPieceError("the terminator is one byte")
+        terminator = _bytes(terminator)[0]
+    return DetokSpec(int(max_len), int(bool(cleanup)), -1 if terminator is None else int(terminator), len(skip),
+                     (C.c_int32 * 8)(*skip))
 
 
 def _special(i):

@@ -48,7 +48,8 @@ enum BoundSite {
   kSiteSortOrder = 8,
   kSiteInputs = 9,  // model inputs: the gathers of the packer from the ids and their spans (inputs.h)
   kSiteMask = 10,   // masking: the lookup of an id's class byte (mask.h)
-  kBoundSites = 11
+  kSiteDetok = 11,  // detokenize: the record gather, the pool gather and the store of the text (detok.h)
+  kBoundSites = 12
 };
 #ifdef WP_DEBUG_BOUNDS
 __device__ unsigned int g_wp_oob[kBoundSites];

@@ -11,6 +11,7 @@
 #include "../../include/wordpiece_amd.h"
 #include "code.h"
 #include "decode.h"
+#include "detok.h"
 #include "radix_sort.h"
 #include "scanline.h"
 #include "suffix_array.h"
@@ -151,7 +152,7 @@ static int bit_length(uint64_t v) {
 // c->d_scalars: kScalars 32-bit words that kernels and scans leave their totals in; c->h_scalars: the pinned mirror the
 // host reads them from.  Every word has a name here and nowhere else; no call site names a number.  An encode clears
 // the whole block when it starts (and the pre-pass of WP_OPT_NORMALIZE in front of it does the same, see below).
-constexpr int kScalars = 48;
+constexpr int kScalars = 56;
 constexpr int kScalarCps = 0;       // code points of the text, 32 bits: the decode scan (linear, fast) -> host
 constexpr int kScalarAlphabet = 1;  // alphabet size: alphabet_prefix_kernel -> host
 constexpr int kScalarInvalid = 2;   // invalid sequences, 64 bits (words 2, 3): decode_count_kernel / norm_count_kernel -> host
@@ -184,7 +185,10 @@ constexpr int kScalarSrcRows = 26;  // lines of the caller's text in a documents
 constexpr int kScalarInCut = 27, kScalarInRows = 28, kScalarInWindowed = 30;
 constexpr int kScalarFree31 = 31;  // free
 constexpr int kScalarMask = 32;    // d_scalars words 32..43: the six 64-bit counters of a mask call (mask.h, MaskCounter)
-constexpr int kScalarFree44 = 44;  // words 44..47: free
+// detokenize (detok.h): the last entry of row_splits given in device memory, 64 bits (words 44, 45) / its violations
+constexpr int kScalarDetokLast = 44, kScalarDetokBad = 46;
+constexpr int kScalarFree47 = 47;  // free
+constexpr int kScalarDetok = 48;   // d_scalars words 48..55: the four 64-bit totals of a detokenize call (detok.h, DetokCounter)
 // normalize_on_device runs in front of the encode, which clears the block again: while it runs, four slots mean
 constexpr int kScalarNormBytes = kScalarCps;           // bytes of the normalised text, 32 bits: its scan
 constexpr int kScalarNormCps = kScalarAlphabet;        // code points of the normalised text (offsets mode) -> host
@@ -204,7 +208,8 @@ constexpr ScalarRange kScalarLayout[] = {
     {kScalarFree18, 2},      {kScalarAlphaWord0, 1}, {kScalarRows, 1},            {kScalarRowsBad, 1},
     {kScalarRowsCut, 1},     {kScalarCand, 1},       {kScalarKept, 1},            {kScalarSrcRows, 1},
     {kScalarInCut, 1},       {kScalarInRows, 2},     {kScalarInWindowed, 1},      {kScalarFree31, 1},
-    {kScalarMask, 12},       {kScalarFree44, 4}};
+    {kScalarMask, 12},       {kScalarDetokLast, 2},  {kScalarDetokBad, 1},        {kScalarFree47, 1},
+    {kScalarDetok, 8}};
 // one past the last word of the range `slot` lies in: where a download or a clear "through" that slot ends
 constexpr int scalar_end(int slot) {
   for (const ScalarRange &r : kScalarLayout) {
@@ -269,6 +274,10 @@ struct Context {
            *d_lt_child_node = nullptr, *d_elig_node = nullptr, *d_elig_subtree = nullptr;  // the token trie (vocab.h, trie.h)
   int32_t *d_elig_id = nullptr, *d_tok_len = nullptr;
   uint8_t *d_tok_class = nullptr;  // wp_vocab_token_flags of every id, one byte each: uploaded by the first mask call (mask.h)
+  // the pieces of every id, uploaded by the first detokenize call (detok.h): records [cleanup][form][id] and their bytes
+  DetokRec *d_detok_rec = nullptr;
+  uint8_t *d_detok_pool = nullptr;
+  size_t detok_pool_bytes = 0;
   unsigned long long *d_trie_key = nullptr;  // the fast path's token trie (vocab.h)
   uint32_t *d_trie_child = nullptr;
   int32_t *d_trie_id = nullptr;
@@ -278,6 +287,8 @@ struct Context {
   // documents calls: explicit row starts of a host call, results of the per-document route, padded batch of a host call
   DeviceBuffer rows_in, rows_out, pad_buf;
   DeviceBuffer inputs_buf;  // model inputs: window counts and records per sample (inputs.h)
+  // detokenize (detok.h): ids and rows of a host call, tile records and offsets, the text and text_off of the last call
+  DeviceBuffer detok_in, detok_aux, detok_out;
   // WP_OPT_NORMALIZE (normalize.h): the tables (uploaded with the first normalising call), the normalised text, the
   // tile counts of the pre-pass, and the source of every normalised code point (offsets mode)
   uint16_t *d_norm_index = nullptr;
@@ -320,9 +331,9 @@ struct Context {
     size_t n = 0, n_text = 0;
   } dbg;
   // every DeviceBuffer above, for destroy_context, release_arenas and park_context: a new buffer is one more name here
-  std::array<DeviceBuffer *, 14> buffers() {
-    return {&text_buf, &a_buf,    &b_buf,   &fmt_buf,    &text_buf2, &ids_stage[0], &ids_stage[1],
-            &rows_in,  &rows_out, &pad_buf, &inputs_buf, &norm_buf,  &norm_aux,     &norm_map};
+  std::array<DeviceBuffer *, 17> buffers() {
+    return {&text_buf, &a_buf,    &b_buf,   &fmt_buf,    &text_buf2, &ids_stage[0], &ids_stage[1], &rows_in,   &rows_out,
+            &pad_buf,  &inputs_buf, &norm_buf, &norm_aux, &norm_map, &detok_in,     &detok_aux,    &detok_out};
   }
   Context() = default;
   Context(const Context &) = delete;
@@ -373,6 +384,8 @@ struct EncodeStats : wp_stats {
   int32_t inputs_call;
   wp_mask_stats mask;  // wp_get_mask_stats: filled by a mask or word-ids call (mask_call 1), zero otherwise
   int32_t mask_call;
+  wp_detok_stats detok;  // wp_get_detok_stats: filled by a detokenize call (detok_call 1), zero otherwise
+  int32_t detok_call;
 };
 
 struct wp_vocab {
@@ -403,7 +416,7 @@ static void free_dev(T *&...p) {
 // the tables of a vocabulary: they go when the handle is destroyed (a parked context gets the next handle's); a new
 // table is one more name here
 static void free_vocab_tables(Context *c) {
-  free_dev(c->d_stream, c->d_elig_start, c->d_elig_info, c->d_soft, c->d_elig_id, c->d_tok_len, c->d_tok_class, c->d_trie_key,
+  free_dev(c->d_stream, c->d_elig_start, c->d_elig_info, c->d_soft, c->d_elig_id, c->d_tok_len, c->d_tok_class, c->d_detok_rec, c->d_detok_pool, c->d_trie_key,
            c->d_trie_child, c->d_trie_id, c->d_vocab_word_idx, c->d_vocab_word_bits, c->d_cls_bmp, c->d_lt_chain_len,
            c->d_lt_chain_off, c->d_lt_child_begin, c->d_lt_child_cp, c->d_lt_child_node, c->d_elig_node, c->d_elig_subtree);
 }

@@ -20,6 +20,7 @@
 
 #include "../../include/wordpiece_amd.h"
 #include "context.h"
+#include "detok.h"
 #include "fast_path.h"
 #include "format.h"
 #include "inputs.h"
@@ -1229,6 +1230,237 @@ int wp_mlm_mask_device(wp_vocab *v, const int32_t *d_input_ids, const int32_t *d
       return;
     }
     mask_on_device(v, get_context(v), d_input_ids, d_lengths, n_rows, g, d_masked, d_labels, d_word_ids);
+  });
+}
+
+}  // extern "C"
+
+// ---- detokenize (include/wordpiece_amd.h, section "detokenize"; kernels: detok.h) -----------------------------------
+namespace {
+size_t up256(size_t bytes) { return (bytes + 255) & ~static_cast<size_t>(255); }
+
+// every argument rule that needs neither the ids nor a device; n_cells of a padded call, -1 of a ragged one
+DetokGeom check_detok_spec(const wp_vocab *v, const wp_detok_spec *spec, size_t n_rows) {
+  if (!spec) throw std::invalid_argument("detokenize: spec is NULL");
+  if (spec->cleanup != 0 && spec->cleanup != 1) throw std::invalid_argument("detokenize: cleanup must be 0 or 1");
+  if (spec->terminator < -1 || spec->terminator > 255) throw std::invalid_argument("detokenize: terminator must lie in [-1, 255]");
+  if (spec->n_skip < 0 || spec->n_skip > 8) throw std::invalid_argument("detokenize: n_skip must lie in [0, 8]");
+  if (spec->max_len < 0) throw std::invalid_argument("detokenize: max_len must be at least 0");
+  if (n_rows > static_cast<size_t>(INT32_MAX)) throw std::length_error("detokenize: more rows than INT32_MAX");
+  DetokGeom g{};
+  g.n_rows = static_cast<long long>(n_rows);
+  g.max_len = spec->max_len;
+  g.term = spec->terminator;
+  g.n_skip = spec->n_skip;
+  for (int k = 0; k < 8; k++) g.skip_ids[k] = k < spec->n_skip ? spec->skip_ids[k] : -1;
+  g.vocab_size = static_cast<long long>(v->hv.tokens.size());
+  g.n_cells = -1;
+  if (spec->max_len > 0) {  // (n_rows <= 2^31 - 1 and max_len <= 2^31 - 1: the product fits 64 bits)
+    g.n_cells = static_cast<long long>(n_rows) * spec->max_len;
+    if (g.n_cells > INT32_MAX) throw std::length_error("detokenize: more cells than INT32_MAX");
+  }
+  return g;
+}
+
+wp_detok_stats &begin_detok_stats(wp_vocab *v, size_t n_rows) {
+  v->stats.detok_call = 1;
+  v->stats.detok = wp_detok_stats{};
+  v->stats.detok.n_rows = static_cast<int64_t>(n_rows);
+  return v->stats.detok;
+}
+
+// the pieces of every id, both forms, both cleanup values: records [cleanup][form][id] and the pool of their bytes
+void ensure_detok_table(const wp_vocab *v, Context *c) {
+  if (c->d_detok_rec) return;
+  const size_t V = v->hv.tokens.size();
+  std::vector<DetokRec> rec(4 * V);
+  std::vector<uint8_t> pool;
+  for (int cleanup = 0; cleanup < 2; cleanup++) {
+    for (int form = 0; form < 2; form++) {
+      for (size_t i = 0; i < V; i++) {
+        const HostToken &t = v->hv.tokens[i];
+        DetokRec &r = rec[(static_cast<size_t>(cleanup) * 2 + static_cast<size_t>(form)) * V + i];
+        if (t.is_malformed) {
+          r = DetokRec{kDetokNoPiece, 0};
+          continue;
+        }
+        const std::string piece = detok_piece_bytes(t, form, cleanup);
+        if (cleanup == 1 && piece == detok_piece_bytes(t, form, 0)) {  // the clean-up changes few pieces: the bytes are shared
+          r = rec[static_cast<size_t>(form) * V + i];
+          continue;
+        }
+        if (pool.size() + piece.size() >= static_cast<size_t>(kDetokNoPiece)) throw std::length_error("detokenize: the pieces of the vocabulary exceed 4 GB");
+        r = DetokRec{static_cast<uint32_t>(pool.size()), static_cast<uint32_t>(piece.size())};
+        pool.insert(pool.end(), piece.begin(), piece.end());
+      }
+    }
+  }
+  c->d_detok_rec = upload(rec, c->stream);
+  c->d_detok_pool = upload(pool, c->stream);
+  c->detok_pool_bytes = pool.size();
+  WP_HIP(hipStreamSynchronize(c->stream));  // rec and pool are locals
+}
+
+// The three passes over device buffers on c's stream.  g.n_cells < 0: a ragged call whose row_splits have not been
+// checked (the device entry point).  The result lies in c->detok_out until the handle's next call.
+void detok_on_device(wp_vocab *v, Context *c, const int32_t *d_ids, const long long *d_splits, const int32_t *d_lengths, DetokGeom g,
+                     int cleanup, const void **d_text, const long long **d_text_off, size_t *n_bytes) {
+  wp_detok_stats &ds = begin_detok_stats(v, static_cast<size_t>(g.n_rows));
+  hipStream_t st = c->stream;
+  const size_t n_rows = static_cast<size_t>(g.n_rows);
+  if (g.n_cells < 0) {
+    clear_scalars(c, kScalarDetokLast, kScalarDetokBad, st);
+    hipLaunchKernelGGL(detok_check_splits_kernel, dim3(std::min<unsigned>(cdiv(n_rows + 1, kBlock), 1024u)), dim3(kBlock), 0, st, d_splits,
+                       n_rows, c->d_scalars + kScalarDetokBad, reinterpret_cast<long long *>(c->d_scalars + kScalarDetokLast));
+    WP_LAUNCH_CHECK();
+    WP_HIP(hipMemcpyAsync(c->h_scalars + kScalarDetokLast, c->d_scalars + kScalarDetokLast,
+                          sizeof(uint32_t) * (scalar_end(kScalarDetokBad) - kScalarDetokLast), hipMemcpyDeviceToHost, st));
+    WP_HIP(hipStreamSynchronize(st));
+    if (c->h_scalars[kScalarDetokBad] != 0) throw std::invalid_argument("detokenize: row_splits must start at 0 and never descend");
+    long long last;
+    std::memcpy(&last, c->h_scalars + kScalarDetokLast, sizeof(last));
+    if (last > INT32_MAX) throw std::length_error("detokenize: more cells than INT32_MAX");
+    g.n_cells = last;
+  }
+  if (g.n_cells > 0 && !d_ids) throw std::invalid_argument("detokenize: ids is NULL");
+  ensure_detok_table(v, c);
+  g.pool_bytes = c->detok_pool_bytes;
+  const size_t n_tiles = static_cast<size_t>(g.n_cells) / kDetokTile + 1;
+  // tile records | tile offsets | tile carries
+  const size_t off_rec = 0, off_off = up256(n_tiles * sizeof(DetokTile)), off_carry = off_off + up256(n_tiles * sizeof(unsigned long long));
+  c->detok_aux.ensure(off_carry + up256(n_tiles * sizeof(uint32_t)));
+  char *aux = static_cast<char *>(c->detok_aux.p);
+  DetokTile *d_tiles = reinterpret_cast<DetokTile *>(aux + off_rec);
+  unsigned long long *d_tile_off = reinterpret_cast<unsigned long long *>(aux + off_off);
+  uint32_t *d_tile_carry = reinterpret_cast<uint32_t *>(aux + off_carry);
+  const DetokRec *d_rec = c->d_detok_rec + static_cast<size_t>(cleanup) * 2 * static_cast<size_t>(g.vocab_size);
+  unsigned long long *d_tot = reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarDetok);
+  const dim3 grid(static_cast<unsigned>(n_tiles)), block(kBlock);
+  hipLaunchKernelGGL((detok_tile_kernel<false>), grid, block, 0, st, d_ids, d_splits, d_lengths, g, d_rec, c->d_detok_pool, d_tiles,
+                     static_cast<const unsigned long long *>(nullptr), static_cast<const uint32_t *>(nullptr),
+                     static_cast<uint8_t *>(nullptr), static_cast<long long *>(nullptr));
+  hipLaunchKernelGGL(detok_spine_kernel, dim3(1), block, 0, st, d_tiles, n_tiles, d_tile_off, d_tile_carry, d_tot);
+  WP_LAUNCH_CHECK();
+  unsigned long long *h_tot = reinterpret_cast<unsigned long long *>(c->h_scalars + kScalarDetok);
+  WP_HIP(hipMemcpyAsync(h_tot, d_tot, kDetokCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  WP_HIP(hipStreamSynchronize(st));
+  const unsigned long long total = h_tot[kDetokBytes] + (g.term >= 0 ? static_cast<unsigned long long>(n_rows) : 0ull);
+  if (total >= (1ull << 32)) throw std::length_error("detokenize: the text has 2^32 bytes or more");
+  g.n_bytes = total;
+  // text_off | text (a whole number of words)
+  const size_t off_text = up256((n_rows + 1) * sizeof(long long));
+  c->detok_out.ensure(off_text + up256(static_cast<size_t>(total) + 4));
+  long long *d_off = static_cast<long long *>(c->detok_out.p);
+  uint8_t *d_txt = static_cast<uint8_t *>(c->detok_out.p) + off_text;
+  hipLaunchKernelGGL((detok_tile_kernel<true>), grid, block, 0, st, d_ids, d_splits, d_lengths, g, d_rec, c->d_detok_pool,
+                     static_cast<DetokTile *>(nullptr), d_tile_off, d_tile_carry, d_txt, d_off);
+  WP_LAUNCH_CHECK();
+  WP_HIP(hipStreamSynchronize(st));
+#ifdef WP_DEBUG_BOUNDS
+  {
+    unsigned int oob = 0;
+    take_oob(kSiteDetok, 1, &oob);
+    if (oob != 0) throw HipError("debug bounds: detokenize: " + std::to_string(oob) + " gathers or stores outside their buffers skipped");
+  }
+#endif
+  ds.n_kept = static_cast<int64_t>(h_tot[kDetokKept]);
+  ds.n_skipped = static_cast<int64_t>(h_tot[kDetokSkipped]);
+  ds.n_dropped = static_cast<int64_t>(h_tot[kDetokDropped]);
+  ds.n_cells = ds.n_kept + ds.n_skipped + ds.n_dropped;
+  ds.n_bytes = static_cast<int64_t>(total);
+  *d_text = total ? d_txt : nullptr;
+  *d_text_off = d_off;
+  *n_bytes = static_cast<size_t>(total);
+}
+}  // namespace
+
+extern "C" {
+
+int wp_get_detok_stats(const wp_vocab *v, wp_detok_stats *out) {
+  *out = v->stats.detok;
+  if (!v->stats.detok_call) out->n_rows = -1;
+  return WP_OK;
+}
+
+int64_t wp_detok_piece(const wp_vocab *v, int64_t id, int form, int cleanup, char *buf, size_t cap) {
+  if (id < 0 || static_cast<size_t>(id) >= v->hv.tokens.size() || (form != 0 && form != 1) || (cleanup != 0 && cleanup != 1)) return -1;
+  const HostToken &t = v->hv.tokens[static_cast<size_t>(id)];
+  if (t.is_malformed) return -1;
+  const std::string piece = detok_piece_bytes(t, form, cleanup);
+  if (buf && cap) std::memcpy(buf, piece.data(), std::min(cap, piece.size()));
+  return static_cast<int64_t>(piece.size());
+}
+
+int wp_detokenize(wp_vocab *v, const int32_t *ids, const int64_t *row_splits, const int32_t *lengths, size_t n_rows,
+                  const wp_detok_spec *spec, char **text, int64_t **text_off, size_t *n_bytes) {
+  return guarded([&] {
+    if (!text || !text_off || !n_bytes) throw std::invalid_argument("detokenize: an out-pointer is NULL");
+    *text = nullptr;
+    *text_off = nullptr;
+    *n_bytes = 0;
+    DetokGeom g = check_detok_spec(v, spec, n_rows);
+    if (g.max_len == 0) {
+      if (!row_splits) throw std::invalid_argument("detokenize: a ragged call needs row_splits");
+      if (row_splits[0] != 0) throw std::invalid_argument("detokenize: row_splits must start at 0");
+      for (size_t r = 0; r < n_rows; r++) {
+        if (row_splits[r + 1] < row_splits[r]) throw std::invalid_argument("detokenize: row_splits must never descend");
+      }
+      if (row_splits[n_rows] > INT32_MAX) throw std::length_error("detokenize: more cells than INT32_MAX");
+      g.n_cells = row_splits[n_rows];
+    }
+    if (g.n_cells > 0 && !ids) throw std::invalid_argument("detokenize: ids is NULL");
+    if (n_rows == 0) {
+      int64_t *off = static_cast<int64_t *>(std::calloc(1, sizeof(int64_t)));
+      if (!off) throw std::bad_alloc();
+      *text_off = off;
+      begin_detok_stats(v, 0);
+      return;
+    }
+    Context *c = get_context(v);
+    const size_t n_cells = static_cast<size_t>(g.n_cells);
+    const bool ragged = g.max_len == 0;
+    // ids | row_splits or lengths
+    const size_t off_rows = up256(n_cells * sizeof(int32_t));
+    c->detok_in.ensure(off_rows + up256((n_rows + 1) * sizeof(int64_t)));
+    int32_t *d_ids = static_cast<int32_t *>(c->detok_in.p);
+    void *d_rows = static_cast<char *>(c->detok_in.p) + off_rows;
+    if (n_cells) WP_HIP(hipMemcpyAsync(d_ids, ids, n_cells * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if (ragged) {
+      WP_HIP(hipMemcpyAsync(d_rows, row_splits, (n_rows + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    } else if (lengths) {
+      WP_HIP(hipMemcpyAsync(d_rows, lengths, n_rows * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    }
+    const void *d_text = nullptr;
+    const long long *d_off = nullptr;
+    size_t nb = 0;
+    detok_on_device(v, c, d_ids, ragged ? static_cast<const long long *>(d_rows) : nullptr,
+                    !ragged && lengths ? static_cast<const int32_t *>(d_rows) : nullptr, g, spec->cleanup, &d_text, &d_off, &nb);
+    Downloads down(c->stream);
+    if (nb) down.add(text, d_text, nb);
+    down.add(text_off, d_off, (n_rows + 1) * sizeof(int64_t));
+    down.finish();
+    *n_bytes = nb;
+  });
+}
+
+int wp_detokenize_device(wp_vocab *v, const int32_t *d_ids, const int64_t *d_row_splits, const int32_t *d_lengths,
+                         size_t n_rows, const wp_detok_spec *spec, const void **d_text, const int64_t **d_text_off,
+                         size_t *n_bytes) {
+  return guarded([&] {
+    if (!d_text || !d_text_off || !n_bytes) throw std::invalid_argument("detokenize: an out-pointer is NULL");
+    *d_text = nullptr;
+    *d_text_off = nullptr;
+    *n_bytes = 0;
+    DetokGeom g = check_detok_spec(v, spec, n_rows);
+    if (g.max_len == 0 && !d_row_splits) throw std::invalid_argument("detokenize: a ragged call needs row_splits");
+    if ((reinterpret_cast<uintptr_t>(d_ids) & 3u) != 0 || (reinterpret_cast<uintptr_t>(d_lengths) & 3u) != 0 ||
+        (reinterpret_cast<uintptr_t>(d_row_splits) & 7u) != 0) {
+      throw std::invalid_argument("detokenize: device ids and lengths must be 4-byte aligned, row_splits 8-byte aligned");
+    }
+    const long long *d_off = nullptr;
+    detok_on_device(v, get_context(v), d_ids, g.max_len == 0 ? reinterpret_cast<const long long *>(d_row_splits) : nullptr,
+                    g.max_len == 0 ? nullptr : d_lengths, g, spec->cleanup, d_text, &d_off, n_bytes);
+    *d_text_off = reinterpret_cast<const int64_t *>(d_off);
   });
 }
 

@@ -434,6 +434,11 @@ int64_t wp_vocab_token_utf8(const wp_vocab *v, int64_t i, char *buf, size_t cap)
 #define WP_NORM_LOWER 2
 #define WP_NORM_STRIP_ACCENTS 4
 #define WP_NORM_BERT_UNCASED 7
+#define WP_OPT_LATE_REFINE 15 /* 1: the keys-only round 0 starts the refinement of the needed groups behind its last
+                                 pass, as it did before the early start.  Default 0: the groups are taken from the runs
+                                 of the sorted candidate list and refined on a side stream beside the remaining passes;
+                                 only the searches in the sorted keys and the rank scatter wait for the sort
+                                 (wp_refine_sched).  Same token ids, same wp_refine_stats; for same-build A/B runs. */
 int wp_set_option(wp_vocab *v, int option, int64_t value);
 
 /* ---- the normalisation stage on its own (WP_OPT_NORMALIZE's pre-pass; `flags` as there, 0 copies the valid UTF-8) ----
@@ -542,6 +547,15 @@ typedef struct {
   int32_t reserved;
 } wp_refine_stats;
 int wp_get_refine_stats(const wp_vocab *v, wp_refine_stats *out);
+/* Where the refinement of the last encode was queued, in a struct of its own for the same reason. */
+typedef struct {
+  int32_t early;            /* 1: the needed groups were built and refined beside the round-0 passes (keys-only round 0
+                               without WP_OPT_LATE_REFINE); 0: behind the sort, or no refinement ran                      */
+  int32_t reserved;
+  double ms_sort_to_scan;   /* WP_OPT_STAGE_TIMING: device time from the end of the last round-0 pass to the first kernel
+                               of the scanline stage (HIP events), else 0                                                */
+} wp_refine_sched;
+int wp_get_refine_sched(const wp_vocab *v, wp_refine_sched *out);
 /* The model-inputs part of the statistics of the last call, in a struct of its own for the same reason.  After an
  * inputs call wp_stats.n_rows, rows_route, offsets_unit and n_ids mean what they mean after a rows call and
  * rows_truncated is 0. */

@@ -26,6 +26,7 @@ WP_OPT_SPARSE_EMIT = 11
 WP_OPT_INDEXED_ROUND0 = 12
 WP_OPT_SORT_BLANKS = 13
 WP_OPT_NORMALIZE = 14
+WP_OPT_LATE_REFINE = 15
 WP_NORM_CLEAN, WP_NORM_LOWER, WP_NORM_STRIP_ACCENTS, WP_NORM_BERT_UNCASED = 1, 2, 4, 7
 WP_OFFSETS_BYTES, WP_OFFSETS_CODE_POINTS = 0, 1
 _OFFSET_UNITS = {"byte": WP_OFFSETS_BYTES, "char": WP_OFFSETS_CODE_POINTS}
@@ -44,7 +45,7 @@ ABI_SYMBOLS = [
     "wp_linear_encode_offsets", "wp_linear_encode_offsets_device",
     "wp_linear_encode_rows", "wp_linear_encode_rows_device", "wp_linear_encode_padded", "wp_linear_encode_padded_device",
     "wp_normalize_cp", "wp_normalize_device", "wp_normalize", "wp_get_norm_stats", "wp_get_walk_stats",
-    "wp_get_refine_stats",
+    "wp_get_refine_stats", "wp_get_refine_sched",
     "wp_linear_encode_inputs", "wp_linear_encode_inputs_device", "wp_get_inputs_stats",
     "wp_word_ids", "wp_word_ids_device", "wp_mlm_mask", "wp_mlm_mask_device", "wp_get_mask_stats",
     "wp_detokenize", "wp_detokenize_device", "wp_detok_piece", "wp_get_detok_stats",
@@ -96,6 +97,11 @@ class RefineStats(C.Structure):
     _fields_ = [("n_groups", C.c_int64), ("n_entries", C.c_int64), ("n_large_groups", C.c_int64),
                 ("n_large_entries", C.c_int64), ("trie_nodes", C.c_int64), ("sort_bits", C.c_int32),
                 ("key_lookup", C.c_int32), ("symbol_bytes", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RefineSched(C.Structure):
+    """wp_refine_sched: where the refinement of the last encode was queued (Vocab.refine_sched())."""
+    _fields_ = [("early", C.c_int32), ("reserved", C.c_int32), ("ms_sort_to_scan", C.c_double)]
 
 
 class InputsSpec(C.Structure):
@@ -228,6 +234,8 @@ def lib():
         L.wp_get_norm_stats.argtypes = [vp, C.POINTER(NormStats)]
         L.wp_get_walk_stats.argtypes = [vp, C.POINTER(WalkStats)]
         L.wp_get_refine_stats.argtypes = [vp, C.POINTER(RefineStats)]
+        if hasattr(L, "wp_get_refine_sched"):  # (WP_LIB may name a build from before the struct: A/B runs against a parent)
+            L.wp_get_refine_sched.argtypes = [vp, C.POINTER(RefineSched)]
         L.wp_linear_debug_fetch.argtypes = [vp, C.c_int, i32p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.wp_free.argtypes = [vp]
         L.wp_free.restype = None
@@ -349,6 +357,13 @@ class Vocab:
         rs = RefineStats()
         _check(lib().wp_get_refine_stats(self._h, C.byref(rs)))
         return {k: int(getattr(rs, k)) for k, _ in rs._fields_ if k != "reserved"}
+
+    def refine_sched(self):
+        """wp_refine_sched of the last encode as a dict: early (1: the refinement ran beside the round-0 passes),
+        ms_sort_to_scan (WP_OPT_STAGE_TIMING: last round-0 pass to the scanline stage, in ms)."""
+        rs = RefineSched()
+        _check(lib().wp_get_refine_sched(self._h, C.byref(rs)))
+        return {"early": int(rs.early), "ms_sort_to_scan": float(rs.ms_sort_to_scan)}
 
     def encode(self, text):
         """Host UTF-8 bytes/str -> numpy int32 ids (wp_linear_encode)."""

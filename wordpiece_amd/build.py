@@ -1,6 +1,11 @@
 """Builds wordpiece_amd/libwordpiece_amd.so (HIP kernels + C ABI + C++ API) for gfx950 with hipcc.
 
-In-tree on purpose: the built .so travels to the GPU box with the repo snapshot."""
+In-tree on purpose: the built .so travels to the GPU box with the repo snapshot.
+
+WP_HIPCC_FLAGS adds compiler flags to the main library's line, for tuning and A/B builds (a build under another name is
+loaded through WP_LIB).  -DWP_LATE_REFINE_DEFAULT=1 (csrc/context.h) makes every handle start with WP_OPT_LATE_REFINE set:
+the way to time the refinement behind the sort with a program that sets no options, such as bench.py.  No other macro
+changes a default."""
 import os
 import subprocess
 import sys

@@ -174,7 +174,8 @@ constexpr int kScalarCps64 = 14;      // code points of the text, 64 bits (words
 constexpr int kScalarGuard = 16;      // arena guard (guard_check_kernel gets + kScalarGuard, host writes {0, ~0} first):
 constexpr int kScalarGuardBad = kScalarGuard + 0;    //   damaged zones -> host
 constexpr int kScalarGuardFirst = kScalarGuard + 1;  //   1 + index of the first one -> host
-constexpr int kScalarFree18 = 18;      // words 18, 19: free (still inside the download behind the walk)
+constexpr int kScalarSplitTotals = 18; // words 18, 19: the totals of the trie round's split where it runs early (refine_early: the
+                                       // list sizes in kScalarList are still read then); not read by the host, inside the download behind the walk
 constexpr int kScalarAlphaWord0 = 20;  // first word of the text's alphabet bitmap before the vocabulary marks it: copy -> host
 // documents calls (rows.h): lines of the text / boundaries of explicit rows that fail the check / rows a padded call cut
 constexpr int kScalarRows = 21, kScalarRowsBad = 22, kScalarRowsCut = 23;
@@ -205,7 +206,7 @@ constexpr ScalarRange kScalarLayout[] = {
     {kScalarListGroups, 1},  {kScalarListLargeGroups, 1}, {kScalarListLargeEntries, 1}, {kScalarListWanted, 1},
     {kScalarIds, 1},         {kScalarAnchors, 1},    {kScalarAnchorGap, 1},       {kScalarLongWords, 1},
     {kScalarWideWords, 1},   {kScalarCps64, 2},      {kScalarGuardBad, 1},        {kScalarGuardFirst, 1},
-    {kScalarFree18, 2},      {kScalarAlphaWord0, 1}, {kScalarRows, 1},            {kScalarRowsBad, 1},
+    {kScalarSplitTotals, 2},      {kScalarAlphaWord0, 1}, {kScalarRows, 1},            {kScalarRowsBad, 1},
     {kScalarRowsCut, 1},     {kScalarCand, 1},       {kScalarKept, 1},            {kScalarSrcRows, 1},
     {kScalarInCut, 1},       {kScalarInRows, 2},     {kScalarInWindowed, 1},      {kScalarFree31, 1},
     {kScalarMask, 12},       {kScalarDetokLast, 2},  {kScalarDetokBad, 1},        {kScalarFree47, 1},
@@ -252,13 +253,18 @@ struct RowsCall {
 //   kEvKeysBuilt               the key builder is done
 //   kEvCandCount               the candidate count is in the pinned mirror
 //   kEvSpine / kEvKept         the spine of round 0's first pass is done / its kept count is in the pinned mirror
+//   kEvSorted                  the last pass of round 0 is done (early refinement: the side stream's anchor list waits for it)
+//   kEvListBuilt               early refinement: the needed list is built (the late half may overwrite the tokens' cells)
+//   kEvRoundDone               early refinement: the trie round's split is done (the rank scatter may start; the side
+//                              stream goes on with the anchor list, which kEvJoin covers at the walk)
 enum SideEvent { kEvFork, kEvJoin, kEvScalars, kEvKeysFree, kEvPartition, kEvTrieNodes, kEvLargeSorted, kEvKeysBuilt, kEvCandCount,
-                 kEvSpine, kEvKept, kSideEvents };
+                 kEvSpine, kEvKept, kEvSorted, kEvListBuilt, kEvRoundDone, kSideEvents };
 // c->ev: the marks of WP_OPT_STAGE_TIMING in the order an encode passes them: its start / code points counted / symbols,
 // classes and keys written / suffix array refined / LCP / scanlines / walk (the fast path: start, counted, symbols,
 // walked).  normalize_on_device: its start, and its end in the mark the encode behind it records next.
+// kMarkRound0: behind the last pass of the round-0 sort (wp_refine_sched.ms_sort_to_scan runs from there to kMarkLcp).
 enum TimingMark { kMarkStart, kMarkCounted, kMarkSymbols, kMarkSorted, kMarkLcp, kMarkScanned, kMarkWalked, kMarkNormStart,
-                  kTimingMarks, kMarkNormEnd = kMarkStart };
+                  kMarkRound0, kTimingMarks, kMarkNormEnd = kMarkStart };
 
 struct Context {
   int device = 0;
@@ -380,6 +386,7 @@ struct EncodeStats : wp_stats {
   double ms_normalize;
   wp_walk_stats walk;
   wp_refine_stats refine;  // which refinement ran (linear_path.h: trie_round_finish / doubling_rounds)
+  wp_refine_sched sched;   // ... and where it was queued (linear_path.h: ranks_round0)
   wp_inputs_stats inputs;  // wp_get_inputs_stats: filled by an inputs call (inputs_call 1), zero otherwise
   int32_t inputs_call;
   wp_mask_stats mask;  // wp_get_mask_stats: filled by a mask or word-ids call (mask_call 1), zero otherwise
@@ -387,6 +394,10 @@ struct EncodeStats : wp_stats {
   wp_detok_stats detok;  // wp_get_detok_stats: filled by a detokenize call (detok_call 1), zero otherwise
   int32_t detok_call;
 };
+
+#ifndef WP_LATE_REFINE_DEFAULT
+#define WP_LATE_REFINE_DEFAULT 0
+#endif
 
 struct wp_vocab {
   HostVocab hv;
@@ -399,6 +410,9 @@ struct wp_vocab {
   bool vocab_in_s = false;  // WP_OPT_VOCAB_IN_S: always the reference's S = text . 1 . vocab layout
   bool indexed_round0 = false;  // WP_OPT_INDEXED_ROUND0: the (key, index) round-0 sort also where keys alone would do
   bool sort_blanks = false;     // WP_OPT_SORT_BLANKS: the keys-only round 0 sorts the blank-start suffixes too
+  // WP_OPT_LATE_REFINE: the keys-only round 0 starts the refinement behind the sort, not beside it
+  // (-DWP_LATE_REFINE_DEFAULT=1: a build whose handles start with it, for A/B runs of programs that set no options)
+  bool late_refine = WP_LATE_REFINE_DEFAULT != 0;
   int normalize = 0;  // WP_OPT_NORMALIZE: WP_NORM_* flags of the pre-pass in front of every encode (normalize.h); 0: none
   int n_devices = 1;  // WP_OPT_DEVICES: GPUs wp_linear_encode shards a host buffer over (-1: all visible)
   EncodeStats stats{};

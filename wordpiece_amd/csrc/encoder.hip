@@ -168,6 +168,7 @@ int wp_set_option(wp_vocab *v, int option, int64_t value) {
     case WP_OPT_SPARSE_EMIT: v->sparse_emit = value != 0; return WP_OK;
     case WP_OPT_INDEXED_ROUND0: v->indexed_round0 = value != 0; return WP_OK;
     case WP_OPT_SORT_BLANKS: v->sort_blanks = value != 0; return WP_OK;
+    case WP_OPT_LATE_REFINE: v->late_refine = value != 0; return WP_OK;
     case WP_OPT_NORMALIZE:
       if (!known_norm_flags(value)) {
         g_last_error = "WP_OPT_NORMALIZE: unknown flag bits (WP_NORM_CLEAN | WP_NORM_LOWER | WP_NORM_STRIP_ACCENTS)";
@@ -224,6 +225,15 @@ int wp_get_walk_stats(const wp_vocab *v, wp_walk_stats *out) {
 
 int wp_get_refine_stats(const wp_vocab *v, wp_refine_stats *out) {
   *out = v->stats.refine;
+  return WP_OK;
+}
+
+int wp_get_refine_sched(const wp_vocab *v, wp_refine_sched *out) {
+  if (!v || !out) {
+    g_last_error = "wp_get_refine_sched: NULL handle or out pointer";
+    return WP_ERR_ARG;
+  }
+  *out = v->stats.sched;
   return WP_OK;
 }
 
@@ -1814,6 +1824,7 @@ void encode_pipeline(wp_vocab *v, Next &&next, Deliver &&deliver) {
       total.refine.n_large_groups = sum.n_large_groups + st.refine.n_large_groups;
       total.refine.n_large_entries = sum.n_large_entries + st.refine.n_large_entries;
     }
+    if (i == 0) total.sched = st.sched;  // (the first text's placement)
     total.rounds = std::max(total.rounds, st.rounds);
     if (next_up.valid()) {
       const std::string err = next_up.get();

@@ -124,6 +124,9 @@ struct LinearPath {
   hipStream_t st, st2;
   const HostVocab &hv;
   bool full, prune, use_trie, key_lookup, keys_only, window_store, use_digit_bytes, staged_possible, sparse_emit;
+  // keys_only: the needed groups are built from the candidate runs and refined beside the round-0 passes (ranks_round0,
+  // "the early refinement"; WP_OPT_LATE_REFINE: behind the sort as before)
+  bool early_refine;
   bool wide_ran = false;  // the walk took the wide branch: scalar 13 holds its count of words (wp_walk_stats)
   uint32_t need_depth;
   int M, P, P_cap, bucket_shift, bucket_shift_all, key_shift, key_shift_all, hb_n, win_mid;
@@ -169,6 +172,7 @@ struct LinearPath {
   // and per needed group the start of its run
   unsigned long long *d_cand_table = nullptr;
   uint32_t *d_cand_filter = nullptr, *d_cand_lo = nullptr, *d_cand_hi = nullptr, *d_gcand = nullptr;
+  uint32_t *d_tok_group = nullptr;  // early refinement: per eligible token, the needed group that carries its key (prune.h)
   uint32_t *d_cand_bcnt = nullptr, *d_cand_boff = nullptr, *d_cand_scan = nullptr;  // per key-builder workgroup
   int cand_bits = 0;
   uint32_t *d_blank_bits = nullptr;  // keys-only round 0: which keys start with a blank (radix_sort.h, key_is_blank)
@@ -225,6 +229,7 @@ struct LinearPath {
     // 8-bit symbols only: with 32-bit symbols (config 3: 1 GB of mixed scripts, 120 k tokens) the list holds a third of
     // the suffixes and its test, packing and sort cost more than the value column (33.1 against 31.1 ms per step)
     keys_only = key_lookup && !v->indexed_round0 && sizeof(SymT) == 1;
+    early_refine = keys_only && !v->late_refine;
     sl_tiles = cdiv(n, kSlTile);
     sl_groups = cdiv(sl_tiles, kSlGroup);
     P = kStepsPerMark * M + 1;  // steps of the scanline result (scanline.h)
@@ -362,7 +367,14 @@ struct LinearPath {
                               : nullptr;
       // vocabulary-sized
       d_claim = ar.take<uint32_t>(claim_size);
-      d_claim_need = ar.take<uint32_t>(claim_size);
+      if (keys_only) {  // the three tables that sort_candidates clears to 0, in one block: one memset
+        uint32_t *zeroed = ar.take<uint32_t>(3 * claim_size);
+        d_cand_lo = zeroed;
+        d_cand_hi = zeroed ? zeroed + claim_size : nullptr;
+        d_claim_need = zeroed ? zeroed + 2 * claim_size : nullptr;
+      } else {
+        d_claim_need = ar.take<uint32_t>(claim_size);
+      }
       d_gclaim = ar.take<uint32_t>(M + 4);
       d_gfirst = ar.take<uint32_t>(M + 4);  // per needed group (at most one per long token): first slot,
       d_gdep = ar.take<uint32_t>(M + 4);    // depth (whole codewords of the key),
@@ -408,9 +420,8 @@ struct LinearPath {
       d_kbfast_all = (key_lookup && key_shift_all != key_shift) ? ar.take<int2>(static_cast<size_t>(nkbuckets_all) + 1) : nullptr;
       d_cand_table = keys_only ? ar.take<unsigned long long>(claim_size) : nullptr;
       d_cand_filter = keys_only ? ar.take<uint32_t>(kCandFilterWords) : nullptr;
-      d_cand_lo = keys_only ? ar.take<uint32_t>(claim_size) : nullptr;
-      d_cand_hi = keys_only ? ar.take<uint32_t>(claim_size) : nullptr;
       d_gcand = keys_only ? ar.take<uint32_t>(M + 4) : nullptr;
+      d_tok_group = keys_only ? ar.take<uint32_t>(M + 1) : nullptr;
       d_cand_bcnt = keys_only ? ar.take<uint32_t>(cdiv(n, kKeyTile) + 2) : nullptr;  // (the generic builder's tiles: the smaller)
       d_cand_boff = keys_only ? ar.take<uint32_t>(cdiv(n, kKeyTile) + 2) : nullptr;
       d_cand_scan = keys_only ? ar.take<uint32_t>(cdiv(cdiv(n, kKeyTile), kScanTile) + 8) : nullptr;
@@ -645,8 +656,7 @@ struct LinearPath {
     WP_HIP(hipEventSynchronize(c->evs[kEvCandCount]));
     n_cand = c->h_scalars[kScalarCand];
     S.round0_candidates = static_cast<int64_t>(n_cand);
-    WP_HIP(hipMemsetAsync(d_cand_lo, 0, claim_size * sizeof(uint32_t), st2));
-    WP_HIP(hipMemsetAsync(d_cand_hi, 0, claim_size * sizeof(uint32_t), st2));
+    WP_HIP(hipMemsetAsync(d_cand_lo, 0, 3 * claim_size * sizeof(uint32_t), st2));  // (and d_cand_hi, d_claim_need: plan())
     const uint32_t *sorted_slot = X1, *sorted_pos = d_node_of_slot;
     if (n_cand > 1) {
       const int cc = radix_sort_pairs<uint32_t>(X1, d_node_of_slot, VA, VB, n_cand, 0, cand_bits, d_radix_tmp2,
@@ -748,7 +758,7 @@ struct LinearPath {
     auto enqueue_needed_groups = [&](hipEvent_t start_after) {
       if (start_after) WP_HIP(hipStreamWaitEvent(st2, start_after, 0));
       WP_HIP(hipMemsetAsync(d_claim, 0xff, claim_size * sizeof(uint32_t), st2));
-      WP_HIP(hipMemsetAsync(d_claim_need, 0, claim_size * sizeof(uint32_t), st2));
+      if (!keys_only) WP_HIP(hipMemsetAsync(d_claim_need, 0, claim_size * sizeof(uint32_t), st2));  // (else: sort_candidates)
       NeededList nl{slots, avals, AG, adep, d_ghead, d_gfirst, d_gdep, reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarList),
                     static_cast<uint32_t *>(nullptr), need_depth, d_claim_need, d_gclaim, d_gneed0,
                     keys_only ? d_gcand : nullptr, keys_only ? cand_runs.pos : nullptr, keys_only ? n_cand : 0};
@@ -786,6 +796,10 @@ struct LinearPath {
     };
     // (they start when the sort ends, beside the first partition pass's histogram: started beside its scatter instead,
     // which is bandwidth-bound, they cost the scatter more than they cost the histogram now — measured)
+    if (early_refine) {
+      refine_early();
+      return;
+    }
     if (key_lookup) {
       // No rank store: the needed-group searches and the trie round (side stream) are the critical path now, and the
       // anchor list (main stream: class bytes only) runs beside them.  The trie round stores a rank for every entry
@@ -847,6 +861,54 @@ struct LinearPath {
       classified = classify_groups(std::min(n, list_cap));
       join();
     }
+  }
+
+  // ---- keys-only round 0: the refinement beside the sort ("early refinement") -------------------------------------------
+  // The members of every needed group are known when the candidate list is sorted by slot (sort_candidates), while the
+  // second of the four passes over the keys still runs: a group is the run of its key's slot, its size the run length,
+  // its members' positions cand_pos.  The sorted keys add one number per group, its first slot — an additive base.  So
+  // the side stream builds the list, sends its sizes to the host and runs the whole trie round (which reads neither a
+  // rank nor a sorted key) in LIST SPACE beside the remaining passes: an entry's provisional slot is its list position,
+  // and whatever the round indexes by slot (slots, the trie nodes by slot, the rank entries) is indexed by list position.
+  // Behind the last pass only the slot-dependent tail is left, on the main stream: the searches in the sorted keys
+  // (every token's range, every group's first slot), the group starts of the step table, and the rank scatter, which
+  // adds gfirst[g] - ghead[g] to every entry while it reads (trie_token_range_list_kernel does the same for the ranges).
+  // The streams are ordered by events alone.  The anchor list goes to the side stream behind the round and behind the
+  // sort (kEvSorted): beside the tail and the scanline stage, not beside the passes.
+  void refine_early() {
+    WP_HIP(hipMemsetAsync(d_claim, 0xff, claim_size * sizeof(uint32_t), st2));  // (d_claim_need: cleared by sort_candidates)
+    NeededList nl{slots, avals, AG, adep, d_ghead, static_cast<uint32_t *>(nullptr), d_gdep,
+                  reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarList), static_cast<uint32_t *>(nullptr), need_depth,
+                  d_claim_need, d_gclaim, d_gneed0, d_gcand, cand_runs.pos, n_cand};
+    const TokenTrie trie{c->d_lt_chain_len, c->d_lt_chain_off, c->d_lt_child_begin, c->d_lt_child_node, d_child_sym};
+    const size_t ns = hv.stream.size(), nc = hv.lt_child_cp.size();
+    const unsigned tok_blocks = cdiv(static_cast<size_t>(M) * kWave, kBlock);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(trie_map_symbols_kernel<SymT>), dim3(cdiv(std::max<size_t>(std::max(ns, nc), 1), kBlock)),
+                       dim3(kBlock), 0, st2, c->d_stream, ns, c->d_lt_child_cp, nc, c->d_lut, d_vsym, d_child_sym);
+    // (a long token's table slot, run length and state wait in its cells of rng_lo / rng_hi / rng_long for the late half)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(need_groups_early_kernel<SymT>), dim3(tok_blocks), dim3(kBlock), 0, st2, n, d_sym, c->d_stream,
+                       c->d_elig_start, c->d_elig_info, M, c->d_lut, dcode, d_claim, nl, d_rng_lo, d_rng_hi, d_rng_long, cand_runs);
+    hipLaunchKernelGGL(needed_list_clamp_kernel, dim3(1), dim3(1), 0, st2, c->d_scalars + kScalarList, static_cast<uint32_t>(list_cap),
+                       c->d_scalars + kScalarListWanted);
+    hipLaunchKernelGGL(needed_list_close_kernel, dim3(1), dim3(1), 0, st2, c->d_scalars + kScalarList, d_ghead);
+    hipLaunchKernelGGL(needed_fill_kernel, dim3(1024), dim3(kBlock), 0, st2, nl, static_cast<const uint32_t *>(nullptr), n_sorted);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(trie_group_start_kernel<SymT>), dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st2,
+                       static_cast<const uint32_t *>(nullptr), cand_runs.pos, d_gcand, static_cast<const uint32_t *>(nullptr), d_gdep,
+                       c->d_scalars + kScalarList, d_sym, n, d_vsym, trie, d_gnode, d_gdone);
+    WP_HIP(hipEventRecord(c->evs[kEvListBuilt], st2));  // (the late half may overwrite the tokens' cells from here on)
+    trie_round_sizes();
+    trie_round_sort();
+    S.sched.early = 1;
+    // main stream, behind the last pass: the late half of the searches, and the group starts (they read the group table
+    // and its sizes, which nothing writes after the list is built: the round's own totals go elsewhere, trie_round_finish)
+    WP_HIP(hipEventRecord(c->evs[kEvSorted], st));
+    WP_HIP(hipStreamWaitEvent(st, c->evs[kEvListBuilt], 0));
+    hipLaunchKernelGGL(need_ranges_kernel, dim3(tok_blocks), dim3(kBlock), 0, st, keys, n_sorted, c->d_stream, c->d_elig_start,
+                       c->d_elig_info, M, c->d_lut, dcode, d_claim, d_gfirst, d_rng_lo, d_rng_hi, d_rng_long, d_tok_group);
+    hipLaunchKernelGGL(group_starts_kernel, dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st, d_gfirst, d_ghead, c->d_scalars + kScalarList,
+                       n_sorted, d_ps0 + P, d_gend);
+    WP_LAUNCH_CHECK();
+    trie_round_finish();
   }
 
   // ---- trie refinement of the needed groups (trie.h), on the side stream BESIDE the window store of the rank store ----
@@ -916,7 +978,28 @@ struct LinearPath {
       hipLaunchKernelGGL(rerank_prefix_kernel, dim3(cdiv(tiles, kRrChunk)), dim3(kBlock), 0, st2, d_agg, d_chunk_agg, tiles);
       hipLaunchKernelGGL(HIP_KERNEL_NAME(rerank_apply_kernel<SymT, false>), dim3(tiles), dim3(kBlock), 0, st2, skeys, spare_vals, slots,
                          adep, d_tdep, n_act, d_agg, d_sym, n, dcode.first_len, dcode.uniform_bits, rrule, d_sa, hd, d_lcp,
-                         other_slots, avals, AG, other_dep, d_ghead, d_gdepth, c->d_scalars + kScalarList);
+                         other_slots, avals, AG, other_dep, d_ghead, d_gdepth,
+                         c->d_scalars + (early_refine ? kScalarSplitTotals : kScalarList));  // (early: group_starts_kernel still reads the sizes)
+    }
+    if (early_refine) {  // the main stream goes on behind the round; the anchor list follows it on the side stream, behind the sort
+      WP_HIP(hipEventRecord(c->evs[kEvRoundDone], st2));
+      if (n_text > 0) {
+        WP_HIP(hipStreamWaitEvent(st2, c->evs[kEvSorted], 0));
+        launch_anchors(st2);
+      }
+      WP_HIP(hipStreamWaitEvent(st, c->evs[kEvRoundDone], 0));
+      if (n_act > 0) {  // hd: list positions of the subgroup heads; the scatter moves them to the group's slots
+        if (n_act >= (1u << 22)) {
+          hipLaunchKernelGGL(list_rank_base_kernel, dim3(cdiv(n_act, kBlock)), dim3(kBlock), 0, st, hd, AG, d_gfirst, d_ghead, n_act);
+          store_ranks(spare_vals, hd, reinterpret_cast<uint32_t *>(hd) + list_cap + 2, reinterpret_cast<uint32_t *>(skeys), n_act);
+        } else {
+          hipLaunchKernelGGL(scatter_list_ranks_kernel, dim3(cdiv(n_act, kBlock)), dim3(kBlock), 0, st, spare_vals, hd, AG, d_gfirst,
+                             d_ghead, n_act, d_rank, n);
+        }
+        rounds = 2;
+      }
+      WP_LAUNCH_CHECK();
+      return;
     }
     join();  // the rank table is complete (main stream) and the new ranks are known (side stream)
     if (n_act > 0) {
@@ -1039,8 +1122,13 @@ struct LinearPath {
       // S = text . 1: the reach of every token is its range in the sorted keys (prune.h); a long token's is the run of
       // the trie nodes below its own inside its group (trie.h).  The marks arrive sorted (tokens in lexicographic order).
       if (M > 0) {
-        hipLaunchKernelGGL(trie_token_range_kernel, dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st, d_node_of_slot, c->d_elig_node,
-                           c->d_elig_subtree, M, d_rng_lo, d_rng_hi, d_rng_long);
+        if (early_refine) {  // (the trie nodes are indexed by list position: refine_early)
+          hipLaunchKernelGGL(trie_token_range_list_kernel, dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st, d_node_of_slot, c->d_elig_node,
+                             c->d_elig_subtree, M, d_rng_lo, d_rng_hi, d_rng_long, d_tok_group, d_ghead);
+        } else {
+          hipLaunchKernelGGL(trie_token_range_kernel, dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st, d_node_of_slot, c->d_elig_node,
+                             c->d_elig_subtree, M, d_rng_lo, d_rng_hi, d_rng_long);
+        }
         hipLaunchKernelGGL(virtual_marks_kernel, dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st, d_rng_lo, d_rng_hi, M, c->d_elig_id,
                            c->d_elig_info, d_mslot0, d_mid, d_minfo, d_rf, d_rb);
       }
@@ -1410,7 +1498,7 @@ struct LinearPath {
       S.reserved0 = 1;  // this is the bounds-checking build
     }
 #endif
-    fetch_scalars(c, kScalarFree18);
+    fetch_scalars(c, kScalarSplitTotals);
     const size_t n_ids = n_text > 0 ? c->h_scalars[kScalarIds] : 0;
     S.n_ids = static_cast<int64_t>(n_ids);
     S.walk.n_wide_words = wide_ran ? static_cast<int64_t>(c->h_scalars[kScalarWideWords]) : 0;  // (cleared only when that branch runs)
@@ -1432,6 +1520,7 @@ struct LinearPath {
       S.ms_walk = span(kMarkScanned, kMarkWalked);
       S.ms_total = span(kMarkStart, kMarkWalked) + S.ms_normalize;
       S.ms_radix_scatter = c->rstats.spans.resolve();
+      S.sched.ms_sort_to_scan = span(kMarkRound0, kMarkLcp);
     }
     c->d_ids = d_ids;
     c->dbg.sym = d_sym;
@@ -1453,6 +1542,7 @@ struct LinearPath {
     symbols_and_keys();
     if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[kMarkSymbols], st));
     sort_round0();
+    if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[kMarkRound0], st));
     ranks_round0();
     refine();
     if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[kMarkSorted], st));

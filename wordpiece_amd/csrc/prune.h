@@ -133,6 +133,7 @@ __device__ __forceinline__ int suffix_vs_token(const SymT *__restrict__ sym, siz
 struct NeededList {
   uint32_t *slots, *vals, *gid, *dep, *ghead;
   uint32_t *gfirst, *gdepth;   // per group: its first slot and its depth (the entries are written by needed_fill_kernel)
+                               // (gfirst == nullptr: list space, see needed_fill_kernel)
   unsigned long long *totals;  // low word: list entries, high word: groups (one atomic allocates both)
   uint32_t *sa;                // != nullptr: slot -> suffix for the slots of needed groups (text-only layout)
   uint32_t need_depth;         // a group whose depth reaches this needs no refinement (depth cap)
@@ -246,6 +247,131 @@ __global__ __launch_bounds__(kBlock) void need_groups_kernel(const Key0 *__restr
   }
 }
 
+// ---- need_groups_kernel in two halves (keys-only round 0, linear_path.h: the early refinement) ------------------------
+// On the keys-only path the members of a needed group are the run of the key's slot in the sorted candidate list, known
+// long before the sort of the keys ends: the early half appends the groups from the runs alone (beside the radix
+// passes), the late half searches the sorted keys for what they alone can give — every token's range and the first slot
+// of every appended group.  Between the two, a long token's state waits in its own cells of rng_lo (table slot),
+// rng_hi (run length) and rng_long (one of the codes below); the claim table is indexed by table slot (one slot per
+// key: no probing) and ends up holding the group number.
+constexpr uint8_t kEarlyShort = 0;   // the stream fits the key: the late half searches its range
+constexpr uint8_t kEarlyGroup = 1;   // long, run of >= 2: a member of the group claim[slot]
+constexpr uint8_t kEarlyWinner = 2;  // ... and the token that appended it: it writes the group's first slot
+constexpr uint8_t kEarlyNone = 3;    // long, no suffix carries the key
+constexpr uint8_t kEarlySingle = 5;  // long, one suffix: kEarlySingle + suffix_vs_token (-1, 0, +1) = 4, 5, 6
+constexpr uint32_t kClaimNoGroup = 0xfffffffeu;  // claimed, but the group was deep enough already: not on the list
+
+template <typename SymT>
+__global__ __launch_bounds__(kBlock) void need_groups_early_kernel(size_t n, const SymT *__restrict__ sym,
+                                                                   const uint32_t *__restrict__ vocab_cps,
+                                                                   const uint32_t *__restrict__ tok_start,
+                                                                   const uint32_t *__restrict__ tok_info, int M,
+                                                                   const uint32_t *__restrict__ lut_excl, DevCode code,
+                                                                   uint32_t *__restrict__ claim, NeededList out,
+                                                                   uint32_t *__restrict__ tok_slot,
+                                                                   uint32_t *__restrict__ tok_run,
+                                                                   uint8_t *__restrict__ tok_state, CandRuns cr) {
+  const int m = static_cast<int>((static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x) >> 6);
+  if (m >= M) return;
+  uint64_t key = 0;
+  int bits = 0;
+  const uint32_t len = tok_info[m] & 0x0fffffffu;
+  const uint32_t *cps = vocab_cps + tok_start[m];
+  uint32_t whole = 0;
+  const bool is_long = wave_token_key(cps, len, lut_excl, code, key, bits, whole);  // wave-uniform
+  if (lane_id() != 0) return;
+  if (!is_long) {
+    tok_state[m] = kEarlyShort;
+    return;
+  }
+  // (long_key_set_kernel put the key of every long token into the table: the slot exists)
+  const uint32_t s = cand_find(cr.table, cr.bits, static_cast<uint32_t>(key));
+  const bool found = wp_in_bounds(s != ~0u, kSiteCandRun) && s != ~0u;
+  const uint32_t lo = found ? cr.lo[s] : 0u, run = found ? cr.hi[s] - lo : 0u;
+  tok_slot[m] = s;
+  tok_run[m] = run;
+  if (run < 2) {  // no such suffix, or a single one: nothing to refine
+    tok_state[m] = run ? static_cast<uint8_t>(kEarlySingle + suffix_vs_token(sym, n, cr.pos[lo], cps, len, lut_excl)) : kEarlyNone;
+    return;
+  }
+  // several tokens share a key (all long prefixes of one word): the first to claim the slot appends the group
+  const bool won = atomicCAS(&claim[s], kClaimEmpty, static_cast<uint32_t>(m)) == kClaimEmpty;
+  atomicMax(&out.claim_need[s], min(len, out.need_depth - 1u) + 1u);
+  if (!won) {
+    tok_state[m] = kEarlyGroup;
+    return;
+  }
+  uint32_t g = kClaimNoGroup;
+  if (whole < out.need_depth) {  // (whole: the codewords that lie in the key completely, the group's depth)
+    const unsigned long long got = atomicAdd(out.totals, (1ull << 32) | static_cast<unsigned long long>(run));
+    g = static_cast<uint32_t>(got >> 32);
+    out.ghead[g] = static_cast<uint32_t>(got);  // (the entries themselves: needed_fill_kernel, one thread per entry)
+    out.gdepth[g] = whole;
+    out.gclaim[g] = s;
+    out.gcand[g] = lo;
+  }
+  claim[s] = g;  // (the other tokens of the key only compare with kClaimEmpty; the late half reads the group from here)
+  tok_state[m] = kEarlyWinner;
+}
+
+// (ns: the sorted keys — slot space)
+__global__ __launch_bounds__(kBlock) void need_ranges_kernel(const Key0 *__restrict__ keys, size_t ns,
+                                                             const uint32_t *__restrict__ vocab_cps,
+                                                             const uint32_t *__restrict__ tok_start,
+                                                             const uint32_t *__restrict__ tok_info, int M,
+                                                             const uint32_t *__restrict__ lut_excl, DevCode code,
+                                                             const uint32_t *__restrict__ claim,
+                                                             uint32_t *__restrict__ gfirst, uint32_t *__restrict__ rng_lo,
+                                                             uint32_t *__restrict__ rng_hi, uint8_t *__restrict__ rng_long,
+                                                             uint32_t *__restrict__ tok_group) {
+  const int m = static_cast<int>((static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x) >> 6);
+  const int lane = lane_id();
+  if (m >= M) return;
+  uint64_t key = 0;
+  int bits = 0;
+  const uint32_t len = tok_info[m] & 0x0fffffffu;
+  uint32_t whole = 0;
+  const bool is_long = wave_token_key(vocab_cps + tok_start[m], len, lut_excl, code, key, bits, whole);  // wave-uniform
+  // (the whole wave searches: wave_key_lower_bound)
+  const size_t first = wave_key_lower_bound(keys, 0, ns, key, 2);
+  if (!is_long) {
+    const uint64_t step = 1ull << (kKeyBits - bits);
+    const uint64_t above = key + step;  // first key that no longer starts with the stream
+    const size_t ubd = (bits == 0 || (above >> kKeyBits) != 0) ? ns : wave_key_gallop(keys, first, ns, above);
+    if (lane == 0) {
+      rng_lo[m] = static_cast<uint32_t>(first);
+      rng_hi[m] = static_cast<uint32_t>(ubd);
+      rng_long[m] = 0;
+      tok_group[m] = kClaimNoGroup;
+    }
+    return;
+  }
+#ifdef WP_DEBUG_BOUNDS
+  const size_t last = wave_key_gallop(keys, first, ns, key + 1);
+#endif
+  if (lane != 0) return;
+  const uint32_t state = rng_long[m], s = rng_lo[m], run = rng_hi[m];
+#ifdef WP_DEBUG_BOUNDS
+  wp_in_bounds(run == last - first, kSiteCandRun);  // the run of the key's slot is its equal range in the sorted keys
+#endif
+  uint32_t lb = static_cast<uint32_t>(first), ubd = lb, g = kClaimNoGroup;
+  uint8_t lng = 0;
+  if (state == kEarlyGroup || state == kEarlyWinner) {
+    ubd = lb + run;
+    lng = 1;
+    g = claim[s];
+    if (state == kEarlyWinner && g != kClaimNoGroup) gfirst[g] = lb;
+  } else if (state != kEarlyNone) {  // a single suffix: before / a prefix of / behind the token
+    const int cmp = static_cast<int>(state) - static_cast<int>(kEarlySingle);
+    lb = cmp < 0 ? lb + 1u : lb;
+    ubd = static_cast<uint32_t>(first) + (cmp <= 0 ? 1u : 0u);
+  }
+  rng_lo[m] = lb;
+  rng_hi[m] = ubd;
+  rng_long[m] = lng;
+  tok_group[m] = g;
+}
+
 __global__ __launch_bounds__(kBlock) void needed_need_kernel(NeededList out) {
   const uint32_t g = blockIdx.x * kBlock + threadIdx.x;
   if (g < reinterpret_cast<const uint32_t *>(out.totals)[1]) out.gneed[g] = out.claim_need[out.gclaim[g]];
@@ -287,7 +413,9 @@ __global__ __launch_bounds__(kBlock) void needed_fill_kernel(NeededList out, con
       const uint32_t md = (lo + hi) >> 1;
       if (out.ghead[md] <= p) lo = md; else hi = md;
     }
-    const uint32_t k = out.gfirst[lo] + static_cast<uint32_t>(p - out.ghead[lo]);
+    // (gfirst == nullptr, the early refinement: the first slots are not known yet and the round runs in list space —
+    // an entry's provisional slot is its list position, the group's base is added behind the sort)
+    const uint32_t k = out.gfirst ? out.gfirst[lo] + static_cast<uint32_t>(p - out.ghead[lo]) : static_cast<uint32_t>(p);
     if (!wp_in_bounds(k < n, kSiteListSlot)) continue;
     // (keys-only round 0: the member at the same offset of the group's candidate run — the order inside a group is
     // free, the trie round's segmented sort puts it in place)

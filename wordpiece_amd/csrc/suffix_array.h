@@ -287,6 +287,31 @@ __global__ __launch_bounds__(kBlock) void scatter_pairs_kernel(const uint32_t *_
   }
 }
 
+// The same scatter behind a round that ran in list space (the early refinement, linear_path.h): val[k] is the list
+// position of the head of entry k's subgroup, and its rank is that position moved from the group's place in the list
+// (ghead) to its place in the sorted array (gfirst, known only behind the round-0 sort): one pass over the list.
+__global__ __launch_bounds__(kBlock) void scatter_list_ranks_kernel(const uint32_t *__restrict__ dst,
+                                                                    const RankEntry *__restrict__ val,
+                                                                    const uint32_t *__restrict__ gid,
+                                                                    const uint32_t *__restrict__ gfirst,
+                                                                    const uint32_t *__restrict__ ghead, size_t m,
+                                                                    RankEntry *__restrict__ out, size_t out_n) {
+  const size_t k = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (k >= m) return;
+  const uint32_t g = gid[k], d = dst[k];
+  const RankEntry v = val[k] + (gfirst[g] - ghead[g]);
+  if (wp_in_bounds(d < out_n && v < out_n, kSiteRankStore)) out[d] = v;
+}
+// ... and for a list long enough for the partitioned store (store_ranks): the base is added in place first
+__global__ __launch_bounds__(kBlock) void list_rank_base_kernel(RankEntry *__restrict__ val, const uint32_t *__restrict__ gid,
+                                                                const uint32_t *__restrict__ gfirst,
+                                                                const uint32_t *__restrict__ ghead, size_t m) {
+  const size_t k = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (k >= m) return;
+  const uint32_t g = gid[k];
+  val[k] += gfirst[g] - ghead[g];
+}
+
 // The rank store of round 0 is a permutation (every slot of the rank table is written exactly once).  After
 // the list has been partitioned by the destination bits above kWinBits, the entries of window w are exactly
 // list[w << kWinBits, (w + 1) << kWinBits): one workgroup places them in an LDS image of the window and

@@ -16,6 +16,7 @@
 #pragma once
 #include "decode.h"
 #include "primitives.h"
+#include "prune.h"
 
 namespace wp {
 
@@ -168,6 +169,37 @@ __global__ __launch_bounds__(kBlock) void trie_token_range_kernel(const uint32_t
   }
   rng_lo[m] = first;
   rng_hi[m] = lo;
+}
+
+// The same where the round ran in list space (the early refinement, linear_path.h): node_of_entry[] is indexed by list
+// position, group g of the list is [ghead[g], ghead[g + 1]) and its first slot is the rng_lo the searches in the sorted
+// keys left for its tokens; tok_group: the group of a long token (kClaimNoGroup: none on the list, the range stays)
+__global__ __launch_bounds__(kBlock) void trie_token_range_list_kernel(const uint32_t *__restrict__ node_of_entry,
+                                                                       const uint32_t *__restrict__ tok_node,
+                                                                       const uint32_t *__restrict__ tok_subtree, int M,
+                                                                       uint32_t *__restrict__ rng_lo, uint32_t *__restrict__ rng_hi,
+                                                                       const uint8_t *__restrict__ rng_long,
+                                                                       const uint32_t *__restrict__ tok_group,
+                                                                       const uint32_t *__restrict__ ghead) {
+  const int m = blockIdx.x * kBlock + threadIdx.x;
+  if (m >= M || !rng_long[m]) return;
+  const uint32_t g = tok_group[m];
+  if (g == kClaimNoGroup) return;
+  const uint32_t base = rng_lo[m], glo = ghead[g], ghi = glo + (rng_hi[m] - base);
+  const uint32_t a = tok_node[m], b = a + tok_subtree[m];
+  uint32_t lo = glo, hi = ghi;
+  while (lo < hi) {
+    const uint32_t md = lo + ((hi - lo) >> 1);
+    if (node_of_entry[md] < a) lo = md + 1; else hi = md;
+  }
+  const uint32_t first = lo;
+  hi = ghi;
+  while (lo < hi) {
+    const uint32_t md = lo + ((hi - lo) >> 1);
+    if (node_of_entry[md] < b) lo = md + 1; else hi = md;
+  }
+  rng_lo[m] = base + (first - glo);
+  rng_hi[m] = base + (lo - glo);
 }
 
 }  // namespace wp

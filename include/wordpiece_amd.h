@@ -373,7 +373,10 @@ int64_t wp_vocab_token_utf8(const wp_vocab *v, int64_t i, char *buf, size_t cap)
                                  vocab token — token ids are identical for duplicate-free vocabs;
                                  vocabs with duplicate lines force full depth automatically. */
 #define WP_OPT_DEVICE 2       /* HIP device ordinal used by this handle (default: current) */
-#define WP_OPT_KEEP_DEBUG 3   /* 1: keep SA/rank/LCP/best arrays for wp_linear_debug_fetch */
+#define WP_OPT_KEEP_DEBUG 3   /* 1: keep SA/rank/LCP/best arrays for wp_linear_debug_fetch (full rank table: the
+                                 key-space step lookup is off).  2: keep the step views by text position only
+                                 (wp_linear_debug_fetch 8..11): layout, key-space lookup, keys-only round 0 and the
+                                 early refinement stay as without the option; one more kernel in front of the walk. */
 #define WP_OPT_STAGE_TIMING 4 /* 1: record per-stage device times with HIP events */
 #define WP_OPT_LCP_KASAI 5    /* 1: build LCP with the chunked Kasai kernel (linear.cpp:18-70)
                                  instead of deriving it inside the doubling rounds */
@@ -556,6 +559,22 @@ typedef struct {
                                of the scanline stage (HIP events), else 0                                                */
 } wp_refine_sched;
 int wp_get_refine_sched(const wp_vocab *v, wp_refine_sched *out);
+/* The step tables of the last Linear encode (csrc/scanline.h: what the walk looks its longest matches up in), in a
+ * struct of its own for the same reason; from values the host holds anyway.  All zero when the stage was not reached.
+ * Sharded and pipelined calls report the first text's. */
+typedef struct {
+  int64_t n_marks;          /* eligible tokens M: the marks of the scanlines                                             */
+  int64_t n_steps;          /* steps of the table: 4 M + 1, and with key_lookup two more per needed group                */
+  int64_t n_tiles;          /* tiles of 4096 slots of the total length (the scanlines of the reference layout)           */
+  int64_t n_groups_of_tiles; /* groups of 64 tiles                                                                       */
+  int32_t bucket_shift;     /* slot >> bucket_shift indexes the slot-space table                                         */
+  int32_t bucket_shift_all; /* ... its small index, for the kernels that look up every position of a long word           */
+  int32_t key_shift;        /* round-0 key >> key_shift indexes the key-space table (key_lookup; else as computed)       */
+  int32_t key_shift_all;    /* ... its small index                                                                       */
+  int32_t packed;           /* 1: a step value carries the token's length above its id (ids < 2^20, lengths < 2^11)      */
+  int32_t key_lookup;       /* 1: the walk looked its steps up by round-0 key (wp_refine_stats.key_lookup)               */
+} wp_step_stats;
+int wp_get_step_stats(const wp_vocab *v, wp_step_stats *out);
 /* The model-inputs part of the statistics of the last call, in a struct of its own for the same reason.  After an
  * inputs call wp_stats.n_rows, rows_route, offsets_unit and n_ids mean what they mean after a rows call and
  * rows_truncated is 0. */
@@ -572,7 +591,12 @@ int wp_get_inputs_stats(const wp_vocab *v, wp_inputs_stats *out);
  * the default layout otherwise stores ranks for the suffixes of needed groups alone), 3 lcp (n-1; -1 = "at least
  * sorted_depth"), 4 best_prefix (n), 5 best_suffix (n), 6 code points (n_text), 7 class bytes (n_text, as int32:
  * 1 is_space, 2 is_spacing_char, 4 soft spacing char, 8 is_punctuation; the Linear path's anchor kernels add 16 at a
- * word-prefix position and 32 at an anchor of the walk) */
+ * word-prefix position and 32 at an anchor of the walk).
+ * WP_OPT_KEEP_DEBUG = 2 keeps four views by text position instead (n_text each; the others fail), written by one kernel
+ * in front of the walk through the walk's own lookup (key-space table, then rank and slot-space table for the key of a
+ * needed group): 8 / 9 the id of the longest prefix-class / ##-class token that matches at the position, -1 for none
+ * and at blank positions (the walk never looks them up); 10 / 11 that token's length in code points, 0 where the id
+ * is -1. */
 int wp_linear_debug_fetch(const wp_vocab *v, int which, int32_t *out, size_t capacity,
                           size_t *n_out);
 

@@ -174,3 +174,39 @@ def test_refine_stats_struct_matches_header(tmp_path):
     rs = W.Vocab(["a"]).refine_stats()
     assert rs == dict(n_groups=0, n_entries=0, n_large_groups=0, n_large_entries=0, trie_nodes=0, sort_bits=0, key_lookup=0,
                       symbol_bytes=0)
+
+
+def test_step_stats_struct_matches_header(tmp_path):
+    """wp_step_stats is a struct of its own (the other statistics structs keep their sizes): the ctypes mirror follows the
+    header's fields, and has the size and offsets a C compiler gives the header's struct; NULL arguments are argument errors."""
+    import ctypes as C
+    import subprocess
+    hdr = open(os.path.join(ROOT, "include", "wordpiece_amd.h")).read()
+    end = hdr.index("} wp_step_stats;")
+    body = hdr[hdr.rindex("typedef struct {", 0, end):end]
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S).replace("typedef struct {", "")
+    fields = [tuple(decl.split()) for decl in body.split(";") if decl.strip()]
+    widths = {"int64_t": C.c_int64, "int32_t": C.c_int32}
+    assert [(name, widths[ctype]) for ctype, name in fields] == list(W.StepStats._fields_)
+    assert [name for _, name in fields] == ["n_marks", "n_steps", "n_tiles", "n_groups_of_tiles", "bucket_shift", "bucket_shift_all",
+                                            "key_shift", "key_shift_all", "packed", "key_lookup"]
+    probe = ["sizeof(wp_step_stats)"] + ["offsetof(wp_step_stats, %s)" % name for _, name in fields] + \
+            ["sizeof(wp_stats)", "sizeof(wp_walk_stats)", "sizeof(wp_refine_stats)", "sizeof(wp_refine_sched)"]
+    src = tmp_path / "sz.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "wordpiece_amd.h"\nint main(void) {\n' +
+                   "".join('  printf("%%zu ", (size_t)%s);\n' % p for p in probe) + "  return 0;\n}\n")
+    exe = tmp_path / "sz"
+    subprocess.run([os.environ.get("CC", "gcc"), "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)], check=True)
+    got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
+    assert got == [C.sizeof(W.StepStats)] + [getattr(W.StepStats, name).offset for _, name in fields] + \
+                  [C.sizeof(W.Stats), C.sizeof(W.WalkStats), C.sizeof(W.RefineStats), C.sizeof(W.RefineSched)]
+    assert C.sizeof(W.StepStats) == 56 and C.sizeof(W.RefineStats) == 56 and C.sizeof(W.RefineSched) == 16
+    # without a device the statistics of a handle that never encoded are zero; WP_OPT_KEEP_DEBUG takes 0, 1 and 2
+    gv = W.Vocab(["a"])
+    assert gv.step_stats() == {name: 0 for _, name in fields}
+    for value in (2, 1, 0):
+        gv.set_option(W.WP_OPT_KEEP_DEBUG, value)
+    L = W.lib()
+    out = W.StepStats()
+    assert L.wp_get_step_stats(None, C.byref(out)) == 6 and b"wp_get_step_stats" in L.wp_last_error()
+    assert L.wp_get_step_stats(gv._h, None) == 6 and L.wp_get_step_stats(gv._h, C.byref(out)) == 0

@@ -45,7 +45,7 @@ ABI_SYMBOLS = [
     "wp_linear_encode_offsets", "wp_linear_encode_offsets_device",
     "wp_linear_encode_rows", "wp_linear_encode_rows_device", "wp_linear_encode_padded", "wp_linear_encode_padded_device",
     "wp_normalize_cp", "wp_normalize_device", "wp_normalize", "wp_get_norm_stats", "wp_get_walk_stats",
-    "wp_get_refine_stats", "wp_get_refine_sched",
+    "wp_get_refine_stats", "wp_get_refine_sched", "wp_get_step_stats",
     "wp_linear_encode_inputs", "wp_linear_encode_inputs_device", "wp_get_inputs_stats",
     "wp_word_ids", "wp_word_ids_device", "wp_mlm_mask", "wp_mlm_mask_device", "wp_get_mask_stats",
     "wp_detokenize", "wp_detokenize_device", "wp_detok_piece", "wp_get_detok_stats",
@@ -102,6 +102,13 @@ class RefineStats(C.Structure):
 class RefineSched(C.Structure):
     """wp_refine_sched: where the refinement of the last encode was queued (Vocab.refine_sched())."""
     _fields_ = [("early", C.c_int32), ("reserved", C.c_int32), ("ms_sort_to_scan", C.c_double)]
+
+
+class StepStats(C.Structure):
+    """wp_step_stats: the step tables the walk of the last encode read (Vocab.step_stats())."""
+    _fields_ = [("n_marks", C.c_int64), ("n_steps", C.c_int64), ("n_tiles", C.c_int64), ("n_groups_of_tiles", C.c_int64),
+                ("bucket_shift", C.c_int32), ("bucket_shift_all", C.c_int32), ("key_shift", C.c_int32),
+                ("key_shift_all", C.c_int32), ("packed", C.c_int32), ("key_lookup", C.c_int32)]
 
 
 class InputsSpec(C.Structure):
@@ -236,6 +243,8 @@ def lib():
         L.wp_get_refine_stats.argtypes = [vp, C.POINTER(RefineStats)]
         if hasattr(L, "wp_get_refine_sched"):  # (WP_LIB may name a build from before the struct: A/B runs against a parent)
             L.wp_get_refine_sched.argtypes = [vp, C.POINTER(RefineSched)]
+        if hasattr(L, "wp_get_step_stats"):
+            L.wp_get_step_stats.argtypes = [vp, C.POINTER(StepStats)]
         L.wp_linear_debug_fetch.argtypes = [vp, C.c_int, i32p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.wp_free.argtypes = [vp]
         L.wp_free.restype = None
@@ -364,6 +373,13 @@ class Vocab:
         rs = RefineSched()
         _check(lib().wp_get_refine_sched(self._h, C.byref(rs)))
         return {"early": int(rs.early), "ms_sort_to_scan": float(rs.ms_sort_to_scan)}
+
+    def step_stats(self):
+        """wp_step_stats of the last encode as a dict: n_marks, n_steps, n_tiles, n_groups_of_tiles, bucket_shift,
+        bucket_shift_all, key_shift, key_shift_all, packed, key_lookup."""
+        ss = StepStats()
+        _check(lib().wp_get_step_stats(self._h, C.byref(ss)))
+        return {k: int(getattr(ss, k)) for k, _ in ss._fields_}
 
     def encode(self, text):
         """Host UTF-8 bytes/str -> numpy int32 ids (wp_linear_encode)."""

@@ -334,6 +334,7 @@ struct Context {
     const uint8_t *cls = nullptr;  // class byte per text position (n_text; kept only with WP_OPT_KEEP_DEBUG)
     StepTable steps{};
     int32_t *best_scratch = nullptr;  // room for 2n int32 (debug expansion of the step functions)
+    const int32_t *step_views = nullptr;  // WP_OPT_KEEP_DEBUG = 2: 4 x n_text (ids prefix / ##, lengths prefix / ##) by text position
     size_t n = 0, n_text = 0;
   } dbg;
   // every DeviceBuffer above, for destroy_context, release_arenas and park_context: a new buffer is one more name here
@@ -387,6 +388,7 @@ struct EncodeStats : wp_stats {
   wp_walk_stats walk;
   wp_refine_stats refine;  // which refinement ran (linear_path.h: trie_round_finish / doubling_rounds)
   wp_refine_sched sched;   // ... and where it was queued (linear_path.h: ranks_round0)
+  wp_step_stats step;      // the step tables the walk read (linear_path.h: scanlines)
   wp_inputs_stats inputs;  // wp_get_inputs_stats: filled by an inputs call (inputs_call 1), zero otherwise
   int32_t inputs_call;
   wp_mask_stats mask;  // wp_get_mask_stats: filled by a mask or word-ids call (mask_call 1), zero otherwise
@@ -405,6 +407,7 @@ struct wp_vocab {
   std::vector<std::unique_ptr<Context>> multi;  // one per entry of the device list of wp_linear_encode_multi
   int device = -1;
   bool full_depth = false, keep_debug = false, stage_timing = false, lcp_kasai = false, cover_anchors = false;
+  bool keep_step_views = false;  // WP_OPT_KEEP_DEBUG = 2: the step views by position, nothing else changes
   bool arena_guard = false;
   bool sparse_emit = false;  // WP_OPT_SPARSE_EMIT: ids through the per-position emit array even where per-workgroup lists would do
   bool vocab_in_s = false;  // WP_OPT_VOCAB_IN_S: always the reference's S = text . 1 . vocab layout

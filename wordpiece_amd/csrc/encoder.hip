@@ -159,7 +159,10 @@ int wp_set_option(wp_vocab *v, int option, int64_t value) {
       }
       v->device = static_cast<int>(value);
       return WP_OK;
-    case WP_OPT_KEEP_DEBUG: v->keep_debug = value != 0; return WP_OK;
+    case WP_OPT_KEEP_DEBUG:  // (2: the step views by position alone; the layout stays the default one)
+      v->keep_debug = value != 0 && value != 2;
+      v->keep_step_views = value == 2;
+      return WP_OK;
     case WP_OPT_STAGE_TIMING: v->stage_timing = value != 0; return WP_OK;
     case WP_OPT_LCP_KASAI: v->lcp_kasai = value != 0; return WP_OK;
     case WP_OPT_COVER_ANCHORS: v->cover_anchors = value != 0; return WP_OK;
@@ -225,6 +228,15 @@ int wp_get_walk_stats(const wp_vocab *v, wp_walk_stats *out) {
 
 int wp_get_refine_stats(const wp_vocab *v, wp_refine_stats *out) {
   *out = v->stats.refine;
+  return WP_OK;
+}
+
+int wp_get_step_stats(const wp_vocab *v, wp_step_stats *out) {
+  if (!v || !out) {
+    g_last_error = "wp_get_step_stats: NULL handle or out pointer";
+    return WP_ERR_ARG;
+  }
+  *out = v->stats.step;
   return WP_OK;
 }
 
@@ -1715,7 +1727,7 @@ int wp_reserve(wp_vocab *v, size_t nbytes) {
     const size_t per_symbol = (v->keep_debug || v->vocab_in_s || v->full_depth) ? 108 : 56;
     c->text_buf.ensure(text_room(nbytes), false);
     c->a_buf.ensure(nbytes + nbytes / 512 + (size_t(1) << 20) + (v->keep_debug ? 4 * nbytes : 0), false);
-    c->b_buf.ensure(per_symbol * n + (v->keep_debug ? 4 * n : 0) + (size_t(64) << 20), false);
+    c->b_buf.ensure(per_symbol * n + (v->keep_debug ? 4 * n : 0) + (v->keep_step_views ? 16 * n : 0) + (size_t(64) << 20), false);
     PinnedBlock warm(nbytes + (size_t(1) << 20));  // about a quarter of an id per byte, 4 bytes each
   });
 }
@@ -1825,6 +1837,7 @@ void encode_pipeline(wp_vocab *v, Next &&next, Deliver &&deliver) {
       total.refine.n_large_entries = sum.n_large_entries + st.refine.n_large_entries;
     }
     if (i == 0) total.sched = st.sched;  // (the first text's placement)
+    if (i == 0) total.step = st.step;
     total.rounds = std::max(total.rounds, st.rounds);
     if (next_up.valid()) {
       const std::string err = next_up.get();
@@ -2183,6 +2196,14 @@ int wp_linear_debug_fetch(const wp_vocab *v, int which, int32_t *out, size_t cap
       case 7:
         if (!d.cls) throw std::invalid_argument("class bytes are kept only with WP_OPT_KEEP_DEBUG");
         src = d.cls;
+        cnt = d.n_text;
+        break;
+      case 8:
+      case 9:
+      case 10:
+      case 11:
+        if (!d.step_views) throw std::invalid_argument("the step views are kept only with WP_OPT_KEEP_DEBUG = 2");
+        src = d.step_views + static_cast<size_t>(which - 8) * d.n_text;
         cnt = d.n_text;
         break;
       default: throw std::invalid_argument("unknown debug array");

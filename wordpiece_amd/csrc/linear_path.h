@@ -145,6 +145,7 @@ struct LinearPath {
   uint32_t *d_sa = nullptr, *d_gdepth = nullptr;
   RankEntry *d_hd_n = nullptr;                 // reference layout: round 0's rank entries in suffix order
   int32_t *d_emit = nullptr, *d_dbg_best = nullptr;
+  int32_t *d_step_views = nullptr;  // WP_OPT_KEEP_DEBUG = 2: ids and lengths of the two classes by text position (walk.h, step_views_kernel)
   uint32_t *d_anchors = nullptr, *d_anchor_cnt = nullptr, *d_anchor_tmp = nullptr, *d_emit_cnt = nullptr, *d_emit_tmp = nullptr,
            *d_blk_cnt = nullptr, *d_blk_off = nullptr, *d_tile_scratch = nullptr;
   // list-sized (list_cap entries): the active list of the rounds and the large-group path
@@ -438,6 +439,7 @@ struct LinearPath {
       d_line_starts = (rows && (!rows->d_doc_off || nmap)) ? ar.take<long long>(rows->n_rows + 1) : nullptr;
       d_row_splits = rows ? ar.take<long long>(rows->n_rows + 1) : nullptr;
       d_row_base = (rows && rows->unit >= 0) ? ar.take<uint32_t>(rows->n_rows + 1) : nullptr;
+      d_step_views = v->keep_step_views ? ar.take<int32_t>(4 * n_text + 4) : nullptr;
       if (pass == 0) ar.commit();
     }
     ar.arm(st);
@@ -1186,6 +1188,17 @@ struct LinearPath {
       steps_all = StepTable{pstart, d_pval_p, d_pval_s, d_bidx_all, bucket_shift_all, pack_steps, d_bfast_all};
     }
     if (key_lookup) key_steps(pstart, P, pack_steps);
+    // wp_step_stats: the tables as the walk gets them
+    S.step.n_marks = M;
+    S.step.n_steps = P;
+    S.step.n_tiles = sl_tiles;
+    S.step.n_groups_of_tiles = sl_groups;
+    S.step.bucket_shift = bucket_shift;
+    S.step.bucket_shift_all = bucket_shift_all;
+    S.step.key_shift = key_shift;
+    S.step.key_shift_all = key_shift_all;
+    S.step.packed = pack_steps;
+    S.step.key_lookup = key_lookup ? 1 : 0;
   }
 
   // the step table in key space (scanline.h) from the slot-space one: starts by the sorted keys, the entries inside
@@ -1307,13 +1320,26 @@ struct LinearPath {
 
   // ---- greedy walk + id stream (linear.cpp:215-316).  Slabs: round-0 keys KA (key_lookup), ids VB, id lists X0, wide
   // list / counts KB VA (VA / X1 hold the coverage rule's reach / flags; VA X1 X0 KB the long words' scratch) ----------
+  WalkArgs walk_args() const {
+    return WalkArgs{d_cls, n_text, d_rank, steps, c->d_tok_len, hv.unk_id, d_emit, nullptr, nullptr, nullptr,
+                    hv.soft.empty() ? 1 : 0, static_cast<int32_t>(hv.tokens.size()),
+                    key_lookup ? reinterpret_cast<const uint32_t *>(KA) : nullptr, ksteps, drop_blanks ? 1 : 0};
+  }
+
+  // WP_OPT_KEEP_DEBUG = 2: what the walk's own lookup answers at every text position, behind the scanline stage and the
+  // rank scatter (both on the main stream) and in front of the walk, which reuses the slabs of the sort but none the
+  // lookup reads
+  void step_views() {
+    if (!d_step_views || n_text == 0) return;
+    hipLaunchKernelGGL(step_views_kernel, dim3(cdiv(n_text, kBlock)), dim3(kBlock), 0, st, walk_args(), d_step_views);
+    WP_LAUNCH_CHECK();
+  }
+
   int32_t *walk(size_t *n_ids_out) {
     int32_t *d_ids = reinterpret_cast<int32_t *>(VB);
     *n_ids_out = 0;
     if (n_text == 0) return d_ids;
-    WalkArgs wa{d_cls, n_text, d_rank, steps, c->d_tok_len, hv.unk_id, d_emit, nullptr, nullptr, nullptr,
-                hv.soft.empty() ? 1 : 0, static_cast<int32_t>(hv.tokens.size()),
-                key_lookup ? reinterpret_cast<const uint32_t *>(KA) : nullptr, ksteps, drop_blanks ? 1 : 0};
+    WalkArgs wa = walk_args();
     S.anchor_mode = 0;
     join();  // (the anchor list of the side stream)
     fetch_scalars(c, kScalarAnchorGap);
@@ -1530,6 +1556,7 @@ struct LinearPath {
     c->dbg.lcp = d_lcp;
     c->dbg.steps = steps;
     c->dbg.best_scratch = d_dbg_best;
+    c->dbg.step_views = n_text > 0 ? d_step_views : nullptr;
     c->dbg.cps = d_cps;
     c->dbg.cls = v->keep_debug ? d_cls : nullptr;
     c->dbg.n = n;
@@ -1555,6 +1582,7 @@ struct LinearPath {
     if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[kMarkLcp], st));
     scanlines();
     if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[kMarkScanned], st));
+    if (v->keep_step_views) step_views();  // (behind the mark: ms_scan stays the stage's own time, ms_walk carries the debug kernel)
     size_t n_ids = 0;
     int32_t *d_ids = walk(&n_ids);
     if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[kMarkWalked], st));

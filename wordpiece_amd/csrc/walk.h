@@ -71,6 +71,28 @@ __device__ __forceinline__ int32_t step_value(const WalkArgs &a, size_t q, bool 
   return step_value_of(a, key, r, prefix);
 }
 
+// WP_OPT_KEEP_DEBUG = 2 (wp_linear_debug_fetch 8..11): the lookup of the walk at every text position, for both classes —
+// out[0 .. n_text) the prefix-class id, then the ##-class id, then the two lengths (0 where the id is -1).  Blank
+// positions get -1: the walk never looks them up, and the key-space table has no answer for them.
+__global__ __launch_bounds__(kBlock) void step_views_kernel(WalkArgs a, int32_t *__restrict__ out) {
+  const size_t q = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (q >= a.n_text) return;
+  int32_t id[2] = {-1, -1}, len[2] = {0, 0};
+  if (!(a.cls[q] & kClsSpace)) {
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+      const int32_t raw = step_value(a, q, c == 0);
+      id[c] = step_id(a.steps, raw);
+      if (!wp_in_bounds(id[c] >= -1 && id[c] < a.n_tokens, kSiteTokenId)) id[c] = -1;
+      if (id[c] != -1) len[c] = step_len(a.steps, raw, a.tok_len);
+    }
+  }
+  out[q] = id[0];
+  out[a.n_text + q] = id[1];
+  out[2 * a.n_text + q] = len[0];
+  out[3 * a.n_text + q] = len[1];
+}
+
 __device__ __forceinline__ bool w_space(const WalkArgs &a, size_t p) { return a.cls[p] & kClsSpace; }
 __device__ __forceinline__ bool w_word_prefix(const WalkArgs &a, size_t p) {  // linear.cpp:215-219
   return p == 0 || (a.cls[p] & kClsSpacing) || (a.cls[p - 1] & kClsSpacing);

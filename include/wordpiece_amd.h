@@ -108,7 +108,11 @@ int wp_linear_encode_offsets_device(wp_vocab *v, const void *d_utf8, size_t nbyt
  * — row i is ids[row_splits[i] .. row_splits[i + 1]) — and, with unit WP_OFFSETS_* (-1: none, offsets NULL), offsets
  * as wp_linear_encode_offsets gives them but relative to the start of the id's own document.  Row i and its offsets
  * are exactly what wp_linear_encode_offsets(document i) returns (an empty document, or one of blanks or invalid bytes
- * only, is an empty row); the rows concatenated are wp_linear_encode of the joined text.
+ * only, is an empty row); the rows concatenated are wp_linear_encode of the joined text.  The span of a word that
+ * fails ([UNK]) begins at the word's first code point, so a failing first word belongs to its own document, with
+ * offset 0 or the number of blanks in front of it.  With WP_OPT_NORMALIZE the rows are those of the text the caller
+ * passed: a line of code points that the rule drops is still a row, an empty one — also the last line of a text that
+ * does not end in '\n', and the only line of a text that normalises to nothing.
  * Normally that is one encode of the joined text plus a few kernels over the spans (wp_stats.rows_route == 1).  Three
  * kinds of vocabulary could match differently in the joined text than in a document of its own and are encoded
  * document by document instead (rows_route == 0, same results, one encode per document): an eligible token that holds

@@ -257,8 +257,15 @@ struct RowsCall {
 //   kEvListBuilt               early refinement: the needed list is built (the late half may overwrite the tokens' cells)
 //   kEvRoundDone               early refinement: the trie round's split is done (the rank scatter may start; the side
 //                              stream goes on with the anchor list, which kEvJoin covers at the walk)
+//   kEvAnchorScalars           the anchor count and the largest anchor gap are in the pinned mirror (side stream, directly
+//                              behind the anchor list: the host waits for it alone before it queues the walk)
+//   kEvMarks / kEvCovered      scanline stage, key lookup: the marks are written (main stream) / their cover scan is done
+//                              (second side stream, beside the step starts and their sort)
+//   kEvStartsSorted / kEvTablesIndexed  the step starts are sorted (main stream) / the bucket indices, kstart and the flags
+//                              of the needed groups are built (second side stream, beside the step values)
 enum SideEvent { kEvFork, kEvJoin, kEvScalars, kEvKeysFree, kEvPartition, kEvTrieNodes, kEvLargeSorted, kEvKeysBuilt, kEvCandCount,
-                 kEvSpine, kEvKept, kEvSorted, kEvListBuilt, kEvRoundDone, kSideEvents };
+                 kEvSpine, kEvKept, kEvSorted, kEvListBuilt, kEvRoundDone, kEvAnchorScalars,
+                 kEvMarks, kEvCovered, kEvStartsSorted, kEvTablesIndexed, kSideEvents };
 // c->ev: the marks of WP_OPT_STAGE_TIMING in the order an encode passes them: its start / code points counted / symbols,
 // classes and keys written / suffix array refined / LCP / scanlines / walk (the fast path: start, counted, symbols,
 // walked).  normalize_on_device: its start, and its end in the mark the encode behind it records next.
@@ -399,6 +406,11 @@ struct EncodeStats : wp_stats {
 
 #ifndef WP_LATE_REFINE_DEFAULT
 #define WP_LATE_REFINE_DEFAULT 0
+#endif
+// -DWP_SERIAL_TAIL=1: a build that keeps the stretch between the round-0 sort and the walk on the main stream as it was
+// (the anchor scalars fetched behind the scanline stage, the cover scan and every table of the stage in a row), for A/B runs
+#ifndef WP_SERIAL_TAIL
+#define WP_SERIAL_TAIL 0
 #endif
 
 struct wp_vocab {
@@ -621,6 +633,10 @@ static void queue_scalars(Context *c, int last, hipStream_t st) {
 static void fetch_scalars(Context *c, int last) {
   queue_scalars(c, last, c->stream);
   WP_HIP(hipStreamSynchronize(c->stream));
+}
+// queues the copy of the slots `first` through `last` alone (other streams may be copying the words around them)
+static void queue_scalar_slots(Context *c, int first, int last, hipStream_t st) {
+  WP_HIP(hipMemcpyAsync(c->h_scalars + first, c->d_scalars + first, sizeof(uint32_t) * (scalar_end(last) - first), hipMemcpyDeviceToHost, st));
 }
 // queues the clearing of the device scalars from slot `first` through slot `last`
 static void clear_scalars(Context *c, int first, int last, hipStream_t st) {

@@ -37,6 +37,51 @@ __global__ void needed_list_clamp_kernel(uint32_t *__restrict__ totals, uint32_t
   }
 }
 
+// The per-token and per-group kernels between the late searches and the sort of the step starts in one launch (early
+// refinement, key lookup): thread i does what group_starts_kernel does for group i, and what
+// trie_token_range_list_kernel, virtual_marks_kernel and piece_starts_kernel do for token i, one after the other in
+// registers — four launches of one thread per token each were four links of a chain that is bound by launch latency.
+// No thread reads what another writes: a group's starts come from gfirst / ghead, a token's from its own range.
+__global__ __launch_bounds__(kBlock) void token_marks_kernel(const uint32_t *__restrict__ node_of_entry, const uint32_t *__restrict__ tok_node,
+                                                             const uint32_t *__restrict__ tok_subtree, int M, uint32_t *__restrict__ rng_lo,
+                                                             uint32_t *__restrict__ rng_hi, const uint8_t *__restrict__ rng_long,
+                                                             const uint32_t *__restrict__ tok_group, const uint32_t *__restrict__ ghead,
+                                                             const uint32_t *__restrict__ gfirst, const uint32_t *__restrict__ totals, size_t n,
+                                                             const int32_t *__restrict__ tok_id, const uint32_t *__restrict__ tok_info,
+                                                             uint32_t *__restrict__ mslot, int32_t *__restrict__ mid, uint32_t *__restrict__ minfo,
+                                                             int32_t *__restrict__ reach_fwd, int32_t *__restrict__ reach_bwd,
+                                                             uint32_t *__restrict__ pstart, uint32_t *__restrict__ gend) {
+  const int m = blockIdx.x * kBlock + threadIdx.x;
+  const uint32_t last = static_cast<uint32_t>(n - 1);
+  if (static_cast<uint32_t>(m) < totals[1]) {  // group m (at most one group per token): group_starts_kernel
+    const uint32_t f = gfirst[m], e = f + (ghead[m + 1] - ghead[m]);
+    uint32_t *tail = pstart + kStepsPerMark * static_cast<size_t>(M) + 1;
+    tail[2 * static_cast<size_t>(m)] = f;
+    tail[2 * static_cast<size_t>(m) + 1] = min(e, last);
+    gend[m] = e;
+  }
+  if (m == 0) pstart[kStepsPerMark * static_cast<size_t>(M)] = 0;
+  if (m >= M) return;
+  uint32_t lo = rng_lo[m], hi = rng_hi[m];
+  const uint32_t g = rng_long[m] ? tok_group[m] : kClaimNoGroup;
+  if (g != kClaimNoGroup) {  // a long token with a group on the list: trie_token_range_list_kernel
+    trie_token_range_in_list(node_of_entry, tok_node[m], tok_subtree[m], ghead[g], lo, hi);
+    rng_lo[m] = lo;
+    rng_hi[m] = hi;
+  }
+  const uint32_t reach = max(hi, lo);  // virtual_marks_kernel
+  mslot[m] = lo;
+  mid[m] = tok_id[m];
+  minfo[m] = tok_info[m];
+  reach_fwd[m] = static_cast<int32_t>(reach);
+  reach_bwd[m] = static_cast<int32_t>(lo);
+  uint32_t *o = pstart + kStepsPerMark * static_cast<size_t>(m);  // piece_starts_kernel
+  o[0] = min(lo + 1u, last);
+  o[1] = min(lo, last);
+  o[2] = min(lo + 1u, last);
+  o[3] = min(reach, last);
+}
+
 // The keys-only round 0 leaves the blank-start suffixes out only where the code's symbol histogram shows at least this
 // share of blanks: the test of every key (builder and first pass) costs about as much as sorting a few percent fewer
 // keys saves (config 2, 14.9 % blanks: 0.15 ms per step gained; config 5, 0.2 %: 1.5 % slower with the drop on).
@@ -122,6 +167,7 @@ struct LinearPath {
 
   // ---- derived
   hipStream_t st, st2;
+  static constexpr bool kSerialTail = WP_SERIAL_TAIL != 0;
   const HostVocab &hv;
   bool full, prune, use_trie, key_lookup, keys_only, window_store, use_digit_bytes, staged_possible, sparse_emit;
   // keys_only: the needed groups are built from the candidate runs and refined beside the round-0 passes (ranks_round0,
@@ -162,12 +208,13 @@ struct LinearPath {
   uint32_t *d_mslot0 = nullptr, *d_mslot1 = nullptr, *d_midx0 = nullptr, *d_midx1 = nullptr, *d_minfo = nullptr, *d_tile_mlo = nullptr;
   int32_t *d_mid = nullptr, *d_rf = nullptr, *d_rb = nullptr, *d_cover_f = nullptr, *d_cover_b = nullptr;
   int32_t *d_tmin_f = nullptr, *d_tmin_b = nullptr, *d_gmin_f = nullptr, *d_gmin_b = nullptr, *d_pval_p = nullptr, *d_pval_s = nullptr;
-  uint32_t *d_ps0 = nullptr, *d_ps1 = nullptr, *d_pv0 = nullptr, *d_pv1 = nullptr, *d_bidx = nullptr;
+  uint32_t *d_ps0 = nullptr, *d_ps1 = nullptr, *d_bidx = nullptr;
   int2 *d_bfast = nullptr, *d_bfast_all = nullptr;
   uint32_t *d_bidx_all = nullptr;
   // the step table in key space (scanline.h): starts, values, indices; the ends of the needed groups
   uint32_t *d_gend = nullptr, *d_kstart = nullptr, *d_kbidx = nullptr, *d_kbidx_all = nullptr;
-  int32_t *d_kval_p = nullptr, *d_kval_s = nullptr;
+  int32_t *d_kval_p = nullptr, *d_kval_s = nullptr, *d_cover_tot = nullptr;
+  uint8_t *d_kneed = nullptr;  // per step: its start lies inside a needed group (scanline.h, step_tables_kernel)
   int2 *d_kbfast = nullptr, *d_kbfast_all = nullptr;
   // keys-only round 0 (decode.h, CandSet): the long-token key set, the runs of its slots in the sorted candidate list,
   // and per needed group the start of its run
@@ -200,6 +247,7 @@ struct LinearPath {
   uint32_t *vals = nullptr, *other_vals = nullptr, *slots = nullptr, *other_slots = nullptr, *adep = nullptr, *other_dep = nullptr;
   uint32_t *avals = nullptr, *spare_vals = nullptr;
   bool classified = false, anchors_queued = false;
+  bool anchor_scalars_queued = false;  // the anchor scalars reach the host from the side stream, behind kEvAnchorScalars
   size_t n_act = 0, n_large = 0, n_large_groups = 0, n_groups = 0;
   StepTable steps{}, steps_all{};  // (steps_all: for the kernels that look up EVERY position of a stretch, scanlines())
   StepTable ksteps{}, ksteps_all{};  // the same in key space (key_lookup)
@@ -289,6 +337,9 @@ struct LinearPath {
     n_sorted = n;
     S.round0_sorted = static_cast<int64_t>(n);
   }
+
+  // early refinement: the group starts, the token ranges, the marks and their step starts in one launch (token_marks_kernel)
+  bool fused_marks() const { return early_refine && !kSerialTail; }
 
   // st2 starts after everything queued on st so far / st continues after everything queued on st2
   void fork() {
@@ -396,6 +447,7 @@ struct LinearPath {
       d_cover_f = ar.take<int32_t>(2 * static_cast<size_t>(M) + 2);
       d_cover_b = ar.take<int32_t>(2 * static_cast<size_t>(M) + 2);
       d_rb = ar.take<int32_t>(M + 1);
+      d_cover_tot = ar.take<int32_t>(4 * cdiv(static_cast<size_t>(std::max(M, 1)), kCoverChunk));
       d_tile_mlo = ref ? ar.take<uint32_t>(sl_tiles + 2) : nullptr;
       d_tmin_f = ref ? ar.take<int32_t>(sl_tiles + 1) : nullptr;
       d_tmin_b = ref ? ar.take<int32_t>(sl_tiles + 1) : nullptr;
@@ -403,8 +455,6 @@ struct LinearPath {
       d_gmin_b = ref ? ar.take<int32_t>(sl_groups + 1) : nullptr;
       d_ps0 = ar.take<uint32_t>(P_cap + 1);
       d_ps1 = ar.take<uint32_t>(P_cap + 1);
-      d_pv0 = ar.take<uint32_t>(P_cap + 1);
-      d_pv1 = ar.take<uint32_t>(P_cap + 1);
       d_pval_p = ar.take<int32_t>(P_cap + 1);
       d_pval_s = ar.take<int32_t>(P_cap + 1);
       d_bidx = ar.take<uint32_t>(static_cast<size_t>(nbuckets) + 2);
@@ -415,6 +465,7 @@ struct LinearPath {
       d_kstart = key_lookup ? ar.take<uint32_t>(P_cap + 1) : nullptr;
       d_kval_p = key_lookup ? ar.take<int32_t>(P_cap + 1) : nullptr;
       d_kval_s = key_lookup ? ar.take<int32_t>(P_cap + 1) : nullptr;
+      d_kneed = key_lookup ? ar.take<uint8_t>(P_cap + 1) : nullptr;
       d_kbidx = key_lookup ? ar.take<uint32_t>(static_cast<size_t>(nkbuckets) + 2) : nullptr;
       d_kbfast = key_lookup ? ar.take<int2>(static_cast<size_t>(nkbuckets) + 1) : nullptr;
       d_kbidx_all = (key_lookup && key_shift_all != key_shift) ? ar.take<uint32_t>(static_cast<size_t>(nkbuckets_all) + 2) : nullptr;
@@ -459,6 +510,16 @@ struct LinearPath {
                        n_text, d_anchor_cnt, d_anchors);
     hipLaunchKernelGGL(anchor_gap_kernel, dim3(std::min<size_t>(atiles, 1024)), dim3(kBlock), 0, as, d_anchors,
                        c->d_scalars + kScalarAnchors, n_text, d_cls, hv.soft.empty() ? 1 : 0, c->d_scalars + kScalarAnchorGap);
+    // The two scalars the host needs to queue the walk are final here.  On the side stream they travel at once, two words
+    // alone (every earlier copy into the mirror has been waited for; the main stream queues none before the walk), so
+    // that the walk is queued while the scanline kernels still wait in the main stream.  (On the main stream — the late
+    // refinement of the key lookup — the side stream's copy of the list sizes may still be under way: walk() fetches.)
+    if (as == st2 && !kSerialTail) {
+      static_assert(kScalarAnchorGap == kScalarAnchors + 1, "one copy takes both anchor scalars");
+      queue_scalar_slots(c, kScalarAnchors, kScalarAnchorGap, as);
+      WP_HIP(hipEventRecord(c->evs[kEvAnchorScalars], as));
+      anchor_scalars_queued = true;
+    }
   }
 
   // ---- S build: dense symbols, symbol code, round-0 keys (linear.cpp:77-103) -----------------------------------------
@@ -907,8 +968,10 @@ struct LinearPath {
     WP_HIP(hipStreamWaitEvent(st, c->evs[kEvListBuilt], 0));
     hipLaunchKernelGGL(need_ranges_kernel, dim3(tok_blocks), dim3(kBlock), 0, st, keys, n_sorted, c->d_stream, c->d_elig_start,
                        c->d_elig_info, M, c->d_lut, dcode, d_claim, d_gfirst, d_rng_lo, d_rng_hi, d_rng_long, d_tok_group);
-    hipLaunchKernelGGL(group_starts_kernel, dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st, d_gfirst, d_ghead, c->d_scalars + kScalarList,
-                       n_sorted, d_ps0 + P, d_gend);
+    if (!fused_marks()) {  // (else: token_marks_kernel, scanlines())
+      hipLaunchKernelGGL(group_starts_kernel, dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st, d_gfirst, d_ghead, c->d_scalars + kScalarList,
+                         n_sorted, d_ps0 + P, d_gend);
+    }
     WP_LAUNCH_CHECK();
     trie_round_finish();
   }
@@ -1124,15 +1187,22 @@ struct LinearPath {
       // S = text . 1: the reach of every token is its range in the sorted keys (prune.h); a long token's is the run of
       // the trie nodes below its own inside its group (trie.h).  The marks arrive sorted (tokens in lexicographic order).
       if (M > 0) {
-        if (early_refine) {  // (the trie nodes are indexed by list position: refine_early)
+        if (fused_marks()) {
+          hipLaunchKernelGGL(token_marks_kernel, dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st, d_node_of_slot, c->d_elig_node,
+                             c->d_elig_subtree, M, d_rng_lo, d_rng_hi, d_rng_long, d_tok_group, d_ghead, d_gfirst,
+                             c->d_scalars + kScalarList, n_sorted, c->d_elig_id, c->d_elig_info, d_mslot0, d_mid, d_minfo, d_rf, d_rb,
+                             d_ps0, d_gend);
+        } else if (early_refine) {  // (the trie nodes are indexed by list position: refine_early)
           hipLaunchKernelGGL(trie_token_range_list_kernel, dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st, d_node_of_slot, c->d_elig_node,
                              c->d_elig_subtree, M, d_rng_lo, d_rng_hi, d_rng_long, d_tok_group, d_ghead);
         } else {
           hipLaunchKernelGGL(trie_token_range_kernel, dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st, d_node_of_slot, c->d_elig_node,
                              c->d_elig_subtree, M, d_rng_lo, d_rng_hi, d_rng_long);
         }
-        hipLaunchKernelGGL(virtual_marks_kernel, dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st, d_rng_lo, d_rng_hi, M, c->d_elig_id,
-                           c->d_elig_info, d_mslot0, d_mid, d_minfo, d_rf, d_rb);
+        if (!fused_marks()) {
+          hipLaunchKernelGGL(virtual_marks_kernel, dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st, d_rng_lo, d_rng_hi, M, c->d_elig_id,
+                             c->d_elig_info, d_mslot0, d_mid, d_minfo, d_rf, d_rb);
+        }
       }
       mv = MarkView{mslot, d_mid, d_minfo, d_rf, d_rb, M, d_cover_f, d_cover_b};
     } else {
@@ -1157,37 +1227,75 @@ struct LinearPath {
                            sl_tiles, sl_groups, mslot, d_minfo, M, d_tmin_f, d_tmin_b, d_gmin_f, d_gmin_b, d_rf, d_rb);
       }
     }
+    // The tail of the stage on two streams (key lookup): the cover scan runs on the second side stream beside the step
+    // starts and their sort, and so does, beside the step values, everything behind the sort that reads no value
+    // (side_tables).  The main stream waits for the scan in front of piece_values_kernel and for the tables behind it.
+    const bool side_tail = key_lookup && !kSerialTail;
+    hipStream_t st3 = side_tail ? c->stream3 : st;
     if (M > 0) {
-      hipLaunchKernelGGL(mark_cover_kernel, dim3(4), dim3(kCoverThreads), 0, st, d_minfo, d_rf, d_rb, M, d_cover_f, d_cover_b);
+      if (side_tail) {
+        WP_HIP(hipEventRecord(c->evs[kEvMarks], st));
+        WP_HIP(hipStreamWaitEvent(st3, c->evs[kEvMarks], 0));
+      }
+      const unsigned chunks = cdiv(M, kCoverChunk);
+      if (chunks > 1) {
+        hipLaunchKernelGGL(mark_cover_totals_kernel, dim3(chunks, 4), dim3(kCoverThreads), 0, st3, d_minfo, d_rf, d_rb, M, d_cover_tot);
+      }
+      hipLaunchKernelGGL(mark_cover_kernel, dim3(chunks, 4), dim3(kCoverThreads), 0, st3, d_minfo, d_rf, d_rb, M,
+                         chunks > 1 ? d_cover_tot : static_cast<const int32_t *>(nullptr), d_cover_f, d_cover_b);
+      if (side_tail) WP_HIP(hipEventRecord(c->evs[kEvCovered], st3));
     }
     if (n_text > 0 && !anchors_queued) launch_anchors(st2);
-    hipLaunchKernelGGL(piece_starts_kernel, dim3(cdiv(std::max(M, 1), kBlock)), dim3(kBlock), 0, st, mv, n_sorted, d_ps0);
+    if (!fused_marks()) {
+      hipLaunchKernelGGL(piece_starts_kernel, dim3(cdiv(std::max(M, 1), kBlock)), dim3(kBlock), 0, st, mv, n_sorted, d_ps0);
+    }
     // (key_lookup: the starts of the needed groups wait behind the marks' starts, group_starts_kernel; extra starts
     // leave the slot-space step function as it is — every value is evaluated at its own start)
     const int P = this->P + (key_lookup ? 2 * static_cast<int>(n_groups) : 0);
-    const int pc = radix_sort_pairs<uint32_t>(d_ps0, d_pv0, d_ps1, d_pv1, P, 0, bit_length(n), d_radix_tmp, radix_words, st, nullptr);
+    // (keys alone: only the sorted starts go on)
+    const int pc = radix_sort_pairs<uint32_t>(d_ps0, nullptr, d_ps1, nullptr, P, 0, bit_length(n), d_radix_tmp, radix_words, st, nullptr);
     // (slot space holds n_sorted slots: the indices need no bucket behind them; the arena was planned for n)
     nbuckets = static_cast<unsigned>(((n_sorted - 1) >> bucket_shift) + 1);
     nbuckets_all = static_cast<unsigned>(((n_sorted - 1) >> bucket_shift_all) + 1);
     uint32_t *pstart = pc ? d_ps1 : d_ps0;
+    if (side_tail) {
+      WP_HIP(hipEventRecord(c->evs[kEvStartsSorted], st));
+      if (M > 0) WP_HIP(hipStreamWaitEvent(st, c->evs[kEvCovered], 0));
+    }
     hipLaunchKernelGGL(piece_values_kernel, dim3(cdiv(static_cast<size_t>(P) * kWave, kBlock)), dim3(kBlock), 0, st, mv, pstart, P,
                        d_pval_p, d_pval_s, pack_steps);
-    hipLaunchKernelGGL(piece_bucket_kernel, dim3(cdiv(nbuckets + 1, kBlock)), dim3(kBlock), 0, st, pstart, P, bucket_shift, nbuckets,
-                       d_bidx);
-    hipLaunchKernelGGL(piece_bucket_fast_kernel, dim3(cdiv(nbuckets, kBlock)), dim3(kBlock), 0, st, d_bidx, d_pval_p, d_pval_s, nbuckets,
-                       d_bfast);
+    if (side_tail) {  // (queued behind the values, which take longer than these six launches: the host keeps neither stream waiting)
+      WP_HIP(hipStreamWaitEvent(st3, c->evs[kEvStartsSorted], 0));
+      side_tables(pstart, P, st3);
+      WP_HIP(hipEventRecord(c->evs[kEvTablesIndexed], st3));
+      WP_HIP(hipStreamWaitEvent(st, c->evs[kEvTablesIndexed], 0));
+      fill_tables(pstart, P);
+    } else {
+      hipLaunchKernelGGL(piece_bucket_kernel, dim3(cdiv(nbuckets + 1, kBlock)), dim3(kBlock), 0, st, pstart, P, bucket_shift, nbuckets,
+                         d_bidx);
+      hipLaunchKernelGGL(piece_bucket_fast_kernel, dim3(cdiv(nbuckets, kBlock)), dim3(kBlock), 0, st, d_bidx, d_pval_p, d_pval_s, nbuckets,
+                         d_bfast);
+      if (bucket_shift_all != bucket_shift) {
+        hipLaunchKernelGGL(piece_bucket_kernel, dim3(cdiv(nbuckets_all + 1, kBlock)), dim3(kBlock), 0, st, pstart, P, bucket_shift_all,
+                           nbuckets_all, d_bidx_all);
+        hipLaunchKernelGGL(piece_bucket_fast_kernel, dim3(cdiv(nbuckets_all, kBlock)), dim3(kBlock), 0, st, d_bidx_all, d_pval_p, d_pval_s,
+                           nbuckets_all, d_bfast_all);
+      }
+    }
     WP_LAUNCH_CHECK();
     steps = StepTable{pstart, d_pval_p, d_pval_s, d_bidx, bucket_shift, pack_steps, d_bfast};
     steps_all = steps;
     if (bucket_shift_all != bucket_shift) {
-      hipLaunchKernelGGL(piece_bucket_kernel, dim3(cdiv(nbuckets_all + 1, kBlock)), dim3(kBlock), 0, st, pstart, P, bucket_shift_all,
-                         nbuckets_all, d_bidx_all);
-      hipLaunchKernelGGL(piece_bucket_fast_kernel, dim3(cdiv(nbuckets_all, kBlock)), dim3(kBlock), 0, st, d_bidx_all, d_pval_p, d_pval_s,
-                         nbuckets_all, d_bfast_all);
-      WP_LAUNCH_CHECK();
       steps_all = StepTable{pstart, d_pval_p, d_pval_s, d_bidx_all, bucket_shift_all, pack_steps, d_bfast_all};
     }
-    if (key_lookup) key_steps(pstart, P, pack_steps);
+    if (key_lookup) {
+      if (!side_tail) key_steps(pstart, P);
+      ksteps = StepTable{d_kstart, d_kval_p, d_kval_s, d_kbidx, key_shift, pack_steps, d_kbfast};
+      ksteps_all = ksteps;
+      if (key_shift_all != key_shift) {
+        ksteps_all = StepTable{d_kstart, d_kval_p, d_kval_s, d_kbidx_all, key_shift_all, pack_steps, d_kbfast_all};
+      }
+    }
     // wp_step_stats: the tables as the walk gets them
     S.step.n_marks = M;
     S.step.n_steps = P;
@@ -1203,7 +1311,7 @@ struct LinearPath {
 
   // the step table in key space (scanline.h) from the slot-space one: starts by the sorted keys, the entries inside
   // needed groups answer kStepNeeded, two bucket indices on the top bits of the key
-  void key_steps(const uint32_t *pstart, int P, int pack_steps) {
+  void key_steps(const uint32_t *pstart, int P) {
     const uint32_t *skeys = reinterpret_cast<const uint32_t *>(keys);
     hipLaunchKernelGGL(key_steps_kernel, dim3(cdiv(P, kBlock)), dim3(kBlock), 0, st, pstart, d_pval_p, d_pval_s, P, skeys, d_kstart,
                        d_kval_p, d_kval_s);
@@ -1218,15 +1326,55 @@ struct LinearPath {
                        d_kbidx);
     hipLaunchKernelGGL(piece_bucket_fast_kernel, dim3(cdiv(nkbuckets, kBlock)), dim3(kBlock), 0, st, d_kbidx, d_kval_p, d_kval_s,
                        nkbuckets, d_kbfast);
-    ksteps = StepTable{d_kstart, d_kval_p, d_kval_s, d_kbidx, key_shift, pack_steps, d_kbfast};
-    ksteps_all = ksteps;
     if (key_shift_all != key_shift) {
       hipLaunchKernelGGL(piece_bucket_kernel, dim3(cdiv(nkbuckets_all + 1, kBlock)), dim3(kBlock), 0, st, d_kstart, P, key_shift_all,
                          nkbuckets_all, d_kbidx_all);
       hipLaunchKernelGGL(piece_bucket_fast_kernel, dim3(cdiv(nkbuckets_all, kBlock)), dim3(kBlock), 0, st, d_kbidx_all, d_kval_p,
                          d_kval_s, nkbuckets_all, d_kbfast_all);
-      ksteps_all = StepTable{d_kstart, d_kval_p, d_kval_s, d_kbidx_all, key_shift_all, pack_steps, d_kbfast_all};
     }
+    WP_LAUNCH_CHECK();
+  }
+
+  // The same tables in two halves (scanlines(), key lookup).  side_tables: what needs the sorted starts, the sorted keys
+  // and the group table only — the bucket indices of both spaces, kstart and the steps inside needed groups — on stream
+  // s, beside piece_values_kernel.  fill_tables: behind the values, one launch for kval and every fast entry.
+  void side_tables(const uint32_t *pstart, int P, hipStream_t s) {
+    const uint32_t *skeys = reinterpret_cast<const uint32_t *>(keys);
+    hipLaunchKernelGGL(key_starts_kernel, dim3(cdiv(P, kBlock)), dim3(kBlock), 0, s, pstart, P, skeys, d_kstart, d_kneed);
+    if (n_groups > 0) {
+      hipLaunchKernelGGL(key_steps_flag_kernel, dim3(cdiv(n_groups, kBlock)), dim3(kBlock), 0, s, d_gfirst, d_gend,
+                         static_cast<uint32_t>(n_groups), pstart, P, d_kneed);
+    }
+    hipLaunchKernelGGL(piece_bucket_kernel, dim3(cdiv(nbuckets + 1, kBlock)), dim3(kBlock), 0, s, pstart, P, bucket_shift, nbuckets, d_bidx);
+    hipLaunchKernelGGL(piece_bucket_kernel, dim3(cdiv(nkbuckets + 1, kBlock)), dim3(kBlock), 0, s, d_kstart, P, key_shift, nkbuckets,
+                       d_kbidx);
+    if (bucket_shift_all != bucket_shift) {
+      hipLaunchKernelGGL(piece_bucket_kernel, dim3(cdiv(nbuckets_all + 1, kBlock)), dim3(kBlock), 0, s, pstart, P, bucket_shift_all,
+                         nbuckets_all, d_bidx_all);
+    }
+    if (key_shift_all != key_shift) {
+      hipLaunchKernelGGL(piece_bucket_kernel, dim3(cdiv(nkbuckets_all + 1, kBlock)), dim3(kBlock), 0, s, d_kstart, P, key_shift_all,
+                         nkbuckets_all, d_kbidx_all);
+    }
+    WP_LAUNCH_CHECK();
+  }
+  void fill_tables(const uint32_t *pstart, int P) {
+    StepFill fill{};
+    unsigned most = static_cast<unsigned>(P);
+    auto add = [&](const uint32_t *bidx, int2 *bfast, unsigned nb, int keyed) {
+      fill.t[fill.count++] = StepFillTable{bidx, bfast, nb, keyed};
+      most = std::max(most, nb);
+    };
+    add(d_bidx, d_bfast, nbuckets, 0);
+    add(d_kbidx, d_kbfast, nkbuckets, 1);
+    if (bucket_shift_all != bucket_shift) add(d_bidx_all, d_bfast_all, nbuckets_all, 0);
+    if (key_shift_all != key_shift) add(d_kbidx_all, d_kbfast_all, nkbuckets_all, 1);
+    hipLaunchKernelGGL(step_tables_kernel, dim3(cdiv(most, kBlock)), dim3(kBlock), 0, st, d_pval_p, d_pval_s, P, d_kneed, d_kval_p, d_kval_s,
+                       fill);
+#ifdef WP_DEBUG_BOUNDS
+    hipLaunchKernelGGL(key_steps_check_kernel, dim3(cdiv(P, kBlock)), dim3(kBlock), 0, st, pstart, P,
+                       reinterpret_cast<const uint32_t *>(keys), d_kval_p, d_kval_s);
+#endif
     WP_LAUNCH_CHECK();
   }
 
@@ -1342,7 +1490,11 @@ struct LinearPath {
     WalkArgs wa = walk_args();
     S.anchor_mode = 0;
     join();  // (the anchor list of the side stream)
-    fetch_scalars(c, kScalarAnchorGap);
+    if (anchor_scalars_queued) {  // (their own copy, queued behind the anchor list: no wait for the main stream)
+      WP_HIP(hipEventSynchronize(c->evs[kEvAnchorScalars]));
+    } else {
+      fetch_scalars(c, kScalarAnchorGap);
+    }
     size_t n_anchors = c->h_scalars[kScalarAnchors];
     const size_t max_anchor_gap = c->h_scalars[kScalarAnchorGap];
     S.walk.max_anchor_gap = static_cast<int32_t>(max_anchor_gap);

@@ -263,69 +263,110 @@ struct MarkView {
   const int32_t *cover_f, *cover_b;
 };
 
-// grid = 4 workgroups (class x direction): running max / min per class over the (sorted) marks.
-// 1024 threads x kCoverItems consecutive marks per step, so a step of the serial carry chain covers
-// 8192 marks (the 256-thread, one-mark version took 0.1 ms for 29 k marks and 3.5 ms for 1 M).
+// Running max / min per class over the (sorted) marks: one workgroup per (class x direction, chunk of kCoverThreads *
+// kCoverItems = 8192 marks) — 1024 threads x kCoverItems consecutive marks (the 256-thread, one-mark version took 0.1 ms
+// for 29 k marks and 3.5 ms for 1 M; four workgroups that walked the chunks one after the other 63 us for 29 k).  The
+// carry into a chunk is the max of the totals of the chunks in front of it, which mark_cover_totals_kernel leaves per
+// (class x direction, chunk) when there is more than one chunk: M <= 2^20 is at most 128 totals, one load per thread.
+// forward: running max of reach_fwd; backward: running min of reach_bwd as a max of negated values, taken over the marks
+// in reverse order (scan index i <-> mark M-1-i).
 constexpr int kCoverThreads = 1024;
 constexpr int kCoverItems = 8;
-__global__ __launch_bounds__(kCoverThreads) void mark_cover_kernel(const uint32_t *__restrict__ minfo,
-                                                                   const int32_t *__restrict__ reach_fwd,
-                                                                   const int32_t *__restrict__ reach_bwd, int M,
-                                                                   int32_t *__restrict__ cover_f,
-                                                                   int32_t *__restrict__ cover_b) {
+constexpr int kCoverChunk = kCoverThreads * kCoverItems;
+constexpr int32_t kCoverNone = -2147483647 - 1;
+
+// the values of this thread's kCoverItems marks of chunk `chunk` for class c (kCoverNone: past the end or the other class)
+// (all loads issued before the first use, none behind a branch: eight marks per thread were eight chains of info -> reach
+// in a row, 62 us for 29 k marks)
+__device__ __forceinline__ void cover_values(const uint32_t *__restrict__ minfo, const int32_t *__restrict__ reach, int M, int chunk,
+                                             int c, int back, int32_t (&v)[kCoverItems]) {
+  const int first = chunk * kCoverChunk + static_cast<int>(threadIdx.x) * kCoverItems;
+  uint32_t info[kCoverItems];
+  int32_t rv[kCoverItems];
+#pragma unroll
+  for (int j = 0; j < kCoverItems; j++) {
+    const int i = first + j;
+    const int q = i < M ? (back ? M - 1 - i : i) : 0;
+    info[j] = minfo[q];
+    rv[j] = reach[q];
+  }
+#pragma unroll
+  for (int j = 0; j < kCoverItems; j++) {
+    v[j] = kCoverNone;
+    if (first + j < M && static_cast<int>(info[j] >> kMarkClsShift) == c) v[j] = back ? -rv[j] - 1 : rv[j];
+  }
+}
+
+// grid = (chunks, 4): tot[cd * chunks + chunk] = max of the chunk's values for cd = (class, direction)
+__global__ __launch_bounds__(kCoverThreads) void mark_cover_totals_kernel(const uint32_t *__restrict__ minfo,
+                                                                          const int32_t *__restrict__ reach_fwd,
+                                                                          const int32_t *__restrict__ reach_bwd, int M,
+                                                                          int32_t *__restrict__ tot) {
   constexpr int WAVES = kCoverThreads / kWave;
   __shared__ int32_t wm[WAVES];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int c = blockIdx.x >> 1, back = blockIdx.x & 1;
-  constexpr int32_t kNone = -2147483647 - 1;
-  int32_t carry = kNone;
-  for (int base = 0; base < M; base += kCoverThreads * kCoverItems) {
-    // forward: running max of reach_fwd; backward: running min of reach_bwd as a max of negated values,
-    // taken over the marks in reverse order (scan index i <-> mark M-1-i)
-    // (all loads of a step issued before the first use, none behind a branch: eight marks per thread were eight
-    // chains of info -> reach in a row, 62 us for 29 k marks)
-    int32_t v[kCoverItems], mx = kNone;
-    uint32_t info[kCoverItems];
-    int32_t rv[kCoverItems];
-    const int32_t *__restrict__ reach = back ? reach_bwd : reach_fwd;
+  const int c = blockIdx.y >> 1, back = blockIdx.y & 1;
+  int32_t v[kCoverItems], mx = kCoverNone;
+  cover_values(minfo, back ? reach_bwd : reach_fwd, M, blockIdx.x, c, back, v);
 #pragma unroll
-    for (int j = 0; j < kCoverItems; j++) {
-      const int i = base + tid * kCoverItems + j;
-      const int q = i < M ? (back ? M - 1 - i : i) : 0;
-      info[j] = minfo[q];
-      rv[j] = reach[q];
-    }
+  for (int j = 0; j < kCoverItems; j++) mx = max(mx, v[j]);
+  const int32_t inc = wave_incl_max(mx);
+  if (lane == kWave - 1) wm[w] = inc;
+  __syncthreads();
+  if (tid == 0) {
+    int32_t all = kCoverNone;
 #pragma unroll
-    for (int j = 0; j < kCoverItems; j++) {
-      const int i = base + tid * kCoverItems + j;
-      v[j] = kNone;
-      if (i < M && static_cast<int>(info[j] >> kMarkClsShift) == c) v[j] = back ? -rv[j] - 1 : rv[j];
-      mx = max(mx, v[j]);
-      v[j] = mx;  // inclusive within the thread
-    }
-    const int32_t inc = wave_incl_max(mx);
-    if (lane == kWave - 1) wm[w] = inc;
-    __syncthreads();
-    int32_t before = carry, all = carry;
+    for (int q = 0; q < WAVES; q++) all = max(all, wm[q]);
+    tot[static_cast<size_t>(blockIdx.y) * gridDim.x + blockIdx.x] = all;
+  }
+}
+
+// grid = (chunks, 4).  tot: the chunk totals (nullptr with a single chunk: nothing is carried in)
+__global__ __launch_bounds__(kCoverThreads) void mark_cover_kernel(const uint32_t *__restrict__ minfo,
+                                                                   const int32_t *__restrict__ reach_fwd,
+                                                                   const int32_t *__restrict__ reach_bwd, int M,
+                                                                   const int32_t *__restrict__ tot,
+                                                                   int32_t *__restrict__ cover_f,
+                                                                   int32_t *__restrict__ cover_b) {
+  constexpr int WAVES = kCoverThreads / kWave;
+  __shared__ int32_t wm[WAVES], cm[WAVES];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int c = blockIdx.y >> 1, back = blockIdx.y & 1, chunk = blockIdx.x;
+  int32_t v[kCoverItems], mx = kCoverNone;
+  cover_values(minfo, back ? reach_bwd : reach_fwd, M, chunk, c, back, v);
+  // the carry: the totals of the chunks in front of this one (issued beside the loads of the chunk itself)
+  int32_t before_chunk = kCoverNone;
+  if (tot) {
+    for (int t = tid; t < chunk; t += kCoverThreads) before_chunk = max(before_chunk, tot[static_cast<size_t>(blockIdx.y) * gridDim.x + t]);
+  }
 #pragma unroll
-    for (int q = 0; q < WAVES; q++) {
-      if (q < w) before = max(before, wm[q]);
-      all = max(all, wm[q]);
-    }
-    const int32_t up = __shfl_up(inc, 1, kWave);
-    if (lane > 0) before = max(before, up);
+  for (int j = 0; j < kCoverItems; j++) {
+    mx = max(mx, v[j]);
+    v[j] = mx;  // inclusive within the thread
+  }
+  const int32_t inc = wave_incl_max(mx), cinc = wave_incl_max(before_chunk);
+  if (lane == kWave - 1) {
+    wm[w] = inc;
+    cm[w] = cinc;
+  }
+  __syncthreads();
+  int32_t before = kCoverNone;
 #pragma unroll
-    for (int j = 0; j < kCoverItems; j++) {
-      const int i = base + tid * kCoverItems + j;
-      if (i < M) {
-        const int q = back ? M - 1 - i : i;
-        const int32_t r = max(before, v[j]);
-        if (back) cover_b[static_cast<size_t>(c) * M + q] = r == kNone ? 2147483647 : -(r + 1);
-        else cover_f[static_cast<size_t>(c) * M + q] = r;
-      }
+  for (int q = 0; q < WAVES; q++) {
+    before = max(before, cm[q]);
+    if (q < w) before = max(before, wm[q]);
+  }
+  const int32_t up = __shfl_up(inc, 1, kWave);
+  if (lane > 0) before = max(before, up);
+#pragma unroll
+  for (int j = 0; j < kCoverItems; j++) {
+    const int i = chunk * kCoverChunk + tid * kCoverItems + j;
+    if (i < M) {
+      const int q = back ? M - 1 - i : i;
+      const int32_t r = max(before, v[j]);
+      if (back) cover_b[static_cast<size_t>(c) * M + q] = r == kCoverNone ? 2147483647 : -(r + 1);
+      else cover_f[static_cast<size_t>(c) * M + q] = r;
     }
-    carry = all;
-    __syncthreads();
   }
 }
 
@@ -358,6 +399,12 @@ __global__ __launch_bounds__(kBlock) void piece_values_kernel(MarkView mv, const
   const int lane = lane_id();
   if (k >= P) return;
   const uint32_t slot = pstart[k];
+  // Equal starts stand side by side in the sorted list and get equal values (a mark's first covered slot is the slot
+  // behind its own in the text-only layout; tokens that never occur bring rows of equal starts): the wave of the first
+  // of them evaluates the slot and writes the values of the run, the waves of the others have nothing to do.  A run is
+  // cut at every multiple of kWave steps (the step there evaluates the slot again): one wave writes at most 64 entries
+  // with one probe, however many starts fall onto one slot (a vocabulary of 2^20 lines on a short text).
+  if (k > 0 && (k & (kWave - 1)) != 0 && pstart[k - 1] == slot) return;
   int lo = 0, hi = mv.M;  // first mark with slot > `slot`: 64 probes per step while the range is wide (decode.h)
   while (hi - lo > 64) {
     const int st = (hi - lo) / kWave + 1;
@@ -374,9 +421,10 @@ __global__ __launch_bounds__(kBlock) void piece_values_kernel(MarkView mv, const
     hi = first_gt < hi ? first_gt : hi;
     if (!t) hi = lo;
   }
-  while (lo < hi) {
-    const int md = (lo + hi) >> 1;
-    if (mv.mslot[md] <= slot) lo = md + 1; else hi = md;
+  {  // at most 64 marks are left: one load per lane, the first lane whose mark lies behind the slot (lanes past hi: "behind")
+    const int idx = lo + lane;
+    const uint64_t m = __ballot(idx < hi ? mv.mslot[idx] > slot : true);
+    lo = m ? min(hi, lo + __ffsll(static_cast<long long>(m)) - 1) : hi;
   }
   const int ub = lo;
   int xq[2] = {-1, -1}, yq[2] = {-1, -1};  // mark index of the stack tops per class
@@ -423,9 +471,10 @@ __global__ __launch_bounds__(kBlock) void piece_values_kernel(MarkView mv, const
       if (yq[c] < 0 && b) yq[c] = base + __ffsll(static_cast<long long>(b)) - 1;
     }
   }
-  if (lane < 2) {
-    const int c = lane;
-    const int x = c ? xq[1] : xq[0], y = c ? yq[1] : yq[0];
+  int32_t val[2];  // (the stack tops are wave-uniform: every lane ends with both values)
+#pragma unroll
+  for (int c = 0; c < 2; c++) {
+    const int x = xq[c], y = yq[c];
     int wq = -1;  // the winning mark
     if (x >= 0 && y >= 0) {  // linear.cpp:243-250: both -> x iff strictly longer, else y
       const int32_t xl = static_cast<int32_t>(mv.minfo[x] & kMarkLenMask), yl = static_cast<int32_t>(mv.minfo[y] & kMarkLenMask);
@@ -439,7 +488,15 @@ __global__ __launch_bounds__(kBlock) void piece_values_kernel(MarkView mv, const
     // packed: the token's length rides in the bits above its id (step_id / step_len below): the walk gets both
     // with one load instead of id -> tok_len[id], one link less in its chain of dependent loads
     if (packed && r >= 0) r |= static_cast<int32_t>(mv.minfo[wq] & kMarkLenMask) << kStepIdBits;
-    (c ? pval_suffix : pval_prefix)[k] = r;
+    val[c] = r;
+  }
+  // the run of equal starts that begins at step k, up to the next multiple of kWave: one probe
+  const int idx = k + 1 + lane, stop = (k | (kWave - 1)) + 1;
+  const uint64_t same = __ballot(idx < P && idx < stop && pstart[idx] == slot);
+  const int run = 1 + (~same ? __ffsll(static_cast<long long>(~same)) - 1 : kWave);
+  if (lane < run) {
+    pval_prefix[k + lane] = val[0];
+    pval_suffix[k + lane] = val[1];
   }
 }
 
@@ -555,6 +612,58 @@ __global__ __launch_bounds__(kBlock) void key_steps_kernel(const uint32_t *__res
   kval_suffix[k] = pval_suffix[k];
 }
 
+// The tables behind the step values in one launch (key lookup).  Everything that does not read the values — the bucket
+// indices of both spaces, kstart, and which steps lie inside a needed group (key_starts_kernel, key_steps_flag_kernel) —
+// is built beside piece_values_kernel; this kernel then writes kval (the slot-space value, or kStepNeeded by the flag)
+// and the fast entries of up to four indices (slot space and key space, each with its "_all" twin where the shifts
+// differ).  A key-space entry takes its values as kval would give them, from pval and the flag: no thread reads what
+// another writes here.
+struct StepFillTable {
+  const uint32_t *bidx;
+  int2 *bfast;
+  unsigned nbuckets;
+  int keyed;  // key space: a step inside a needed group answers kStepNeeded
+};
+struct StepFill {
+  StepFillTable t[4];
+  int count;
+};
+__global__ __launch_bounds__(kBlock) void step_tables_kernel(const int32_t *__restrict__ pval_prefix,
+                                                             const int32_t *__restrict__ pval_suffix, int P,
+                                                             const uint8_t *__restrict__ kneed, int32_t *__restrict__ kval_prefix,
+                                                             int32_t *__restrict__ kval_suffix, StepFill fill) {
+  const unsigned i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < static_cast<unsigned>(P)) {
+    const bool nd = kneed[i] != 0;
+    kval_prefix[i] = nd ? kStepNeeded : pval_prefix[i];
+    kval_suffix[i] = nd ? kStepNeeded : pval_suffix[i];
+  }
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    if (q >= fill.count || i >= fill.t[q].nbuckets) continue;
+    const uint32_t lo = fill.t[q].bidx[i], hi = fill.t[q].bidx[i + 1];
+    int2 e;
+    if (lo != hi) {
+      e = int2{kStepSlow | static_cast<int32_t>(hi - lo), static_cast<int32_t>(lo)};
+    } else if (fill.t[q].keyed && kneed[lo - 1]) {  // (bucket 0 holds step 0: lo == hi implies lo > 0)
+      e = int2{kStepNeeded, kStepNeeded};
+    } else {
+      e = int2{pval_prefix[lo - 1], pval_suffix[lo - 1]};
+    }
+    fill.t[q].bfast[i] = e;
+  }
+}
+
+// kstart of every step, and its flag cleared (key_steps_flag_kernel sets it inside the needed groups)
+__global__ __launch_bounds__(kBlock) void key_starts_kernel(const uint32_t *__restrict__ pstart, int P,
+                                                            const uint32_t *__restrict__ sorted_keys, uint32_t *__restrict__ kstart,
+                                                            uint8_t *__restrict__ kneed) {
+  const int k = blockIdx.x * kBlock + threadIdx.x;
+  if (k >= P) return;
+  kstart[k] = k == 0 ? 0u : sorted_keys[pstart[k]];
+  kneed[k] = 0;
+}
+
 // first index in [0, P) with pstart >= x
 __device__ __forceinline__ int starts_lower_bound(const uint32_t *__restrict__ pstart, int P, uint32_t x) {
   int lo = 0, hi = P;
@@ -577,6 +686,16 @@ __global__ __launch_bounds__(kBlock) void key_steps_needed_kernel(const uint32_t
     kval_prefix[k] = kStepNeeded;
     kval_suffix[k] = kStepNeeded;
   }
+}
+
+// the same as a flag per step, for step_tables_kernel
+__global__ __launch_bounds__(kBlock) void key_steps_flag_kernel(const uint32_t *__restrict__ gfirst, const uint32_t *__restrict__ gend,
+                                                                uint32_t n_groups, const uint32_t *__restrict__ pstart, int P,
+                                                                uint8_t *__restrict__ kneed) {
+  const uint32_t g = blockIdx.x * kBlock + threadIdx.x;
+  if (g >= n_groups) return;
+  const int k0 = starts_lower_bound(pstart, P, gfirst[g]), k1 = starts_lower_bound(pstart, P, gend[g]);
+  for (int k = k0; k < k1; k++) kneed[k] = 1;
 }
 
 // bounds-checking build: a step that starts strictly inside a run of equal keys that is not a needed group must carry

@@ -171,6 +171,27 @@ __global__ __launch_bounds__(kBlock) void trie_token_range_kernel(const uint32_t
   rng_hi[m] = lo;
 }
 
+// [rng_lo, rng_hi): the slots of the token's group on entry, the token's own reach inside it on return; glo: the list
+// position of the group's first entry
+__device__ __forceinline__ void trie_token_range_in_list(const uint32_t *__restrict__ node_of_entry, uint32_t tok_node,
+                                                         uint32_t tok_subtree, uint32_t glo, uint32_t &rng_lo, uint32_t &rng_hi) {
+  const uint32_t base = rng_lo, ghi = glo + (rng_hi - base);
+  const uint32_t a = tok_node, b = a + tok_subtree;
+  uint32_t lo = glo, hi = ghi;
+  while (lo < hi) {
+    const uint32_t md = lo + ((hi - lo) >> 1);
+    if (node_of_entry[md] < a) lo = md + 1; else hi = md;
+  }
+  const uint32_t first = lo;
+  hi = ghi;
+  while (lo < hi) {
+    const uint32_t md = lo + ((hi - lo) >> 1);
+    if (node_of_entry[md] < b) lo = md + 1; else hi = md;
+  }
+  rng_lo = base + (first - glo);
+  rng_hi = base + (lo - glo);
+}
+
 // The same where the round ran in list space (the early refinement, linear_path.h): node_of_entry[] is indexed by list
 // position, group g of the list is [ghead[g], ghead[g + 1]) and its first slot is the rng_lo the searches in the sorted
 // keys left for its tokens; tok_group: the group of a long token (kClaimNoGroup: none on the list, the range stays)
@@ -185,21 +206,10 @@ __global__ __launch_bounds__(kBlock) void trie_token_range_list_kernel(const uin
   if (m >= M || !rng_long[m]) return;
   const uint32_t g = tok_group[m];
   if (g == kClaimNoGroup) return;
-  const uint32_t base = rng_lo[m], glo = ghead[g], ghi = glo + (rng_hi[m] - base);
-  const uint32_t a = tok_node[m], b = a + tok_subtree[m];
-  uint32_t lo = glo, hi = ghi;
-  while (lo < hi) {
-    const uint32_t md = lo + ((hi - lo) >> 1);
-    if (node_of_entry[md] < a) lo = md + 1; else hi = md;
-  }
-  const uint32_t first = lo;
-  hi = ghi;
-  while (lo < hi) {
-    const uint32_t md = lo + ((hi - lo) >> 1);
-    if (node_of_entry[md] < b) lo = md + 1; else hi = md;
-  }
-  rng_lo[m] = base + (first - glo);
-  rng_hi[m] = base + (lo - glo);
+  uint32_t lo = rng_lo[m], hi = rng_hi[m];
+  trie_token_range_in_list(node_of_entry, tok_node[m], tok_subtree[m], ghead[g], lo, hi);
+  rng_lo[m] = lo;
+  rng_hi[m] = hi;
 }
 
 }  // namespace wp

@@ -300,6 +300,67 @@ int64_t wp_detok_piece(const wp_vocab *v, int64_t id, int form, int cleanup, cha
 typedef struct { int64_t n_rows, n_cells, n_kept, n_skipped, n_dropped, n_bytes; } wp_detok_stats;
 int wp_get_detok_stats(const wp_vocab *v, wp_detok_stats *out); /* n_rows == -1: no such call yet */
 
+/* ---- pack (an addition: several encoded documents per fixed-length row; seqio / T5 trim_and_pack_dataset with its
+ * segment ids and positions, HF run_mlm.py group_texts) ----
+ * Ragged ids in — ids[n_ids] with row_splits[0 .. n_docs], the layout the rows call returns and the detokenize call
+ * takes — a packed batch of n_out rows of max_len cells out.  No encode runs and no vocabulary is read; the ids are not
+ * range-checked.  Document i is T_i of l_i ids.  L = max_len, s = (bos_id >= 0) + (eos_id >= 0), B = L - s.
+ * Pieces, in document order, numbered k = 0 .. n_p - 1: a document with l_i == 0 gives none;
+ *   WP_PACK_STREAM:                            one piece (i, 0, l_i); long_docs is not read
+ *   WP_PACK_NEXT_FIT + WP_PACK_LONG_TRUNCATE:  one piece (i, 0, min(l_i, B)); a document that loses ids counts in n_cut,
+ *                                              its lost ids in n_ids_cut
+ *   WP_PACK_NEXT_FIT + WP_PACK_LONG_SPLIT:     ceil(l_i / B) pieces (i, j B, min(B, l_i - j B))
+ * The unit of a piece (i, f, n) is [bos] T_i[f : f + n] [eos], each special only where its id is >= 0: u = n + s cells.
+ * P[k]: the sum of the unit lengths in front of piece k;  N = P[n_p].
+ * Rows.  WP_PACK_STREAM: the units back to back are one stream of N cells, row r is its cells [r L, min(N, (r + 1) L)),
+ *   n_out = ceil(N / L); a unit may straddle rows (group_texts with the remainder kept and padded).
+ *   WP_PACK_NEXT_FIT: no unit is longer than L and none is split; row j holds the units [k_j, k_{j+1}), k_0 = 0, k_{j+1}
+ *   the first k > k_j with P[k + 1] - P[k_j] > L, or n_p: order is kept, and a unit opens a new row exactly when it does
+ *   not fit behind the ones before it (with WP_PACK_LONG_TRUNCATE: trim_and_pack_dataset for one feature).
+ * Cells.  Every cell of the n_out rows is written, padding included; nothing behind row n_out is.
+ *   input_ids:    the unit's cell; pad_id in a padding cell
+ *   lengths[r]:   the cells of row r that are no padding, in [1, L]
+ *   segment_ids:  1 + the number of columns c' in (0, c] at which a unit begins; 0 in a padding cell (the unit that goes on
+ *                 from the row before in stream mode is segment 1: the T5 *_segment_ids convention)
+ *   position_ids: c minus the column of the last such beginning at or before c (column 0 if there is none); 0 in a padding
+ *                 cell.  Positions stay below L whatever a document's length
+ *   source:       the index into ids of an id cell; -1 for specials and padding.  One gather x[source] carries per-token
+ *                 data (the offsets of the rows call) into the batch.  Outside NEXT_FIT + LONG_TRUNCATE the entries >= 0
+ *                 are 0 .. n_ids - 1 in row-major order
+ * want (WP_PACK_WANT_*) names the optional outputs that are produced: the host entry point returns NULL for the others,
+ * the device entry point reads only the pointers of the wanted ones.  input_ids and lengths are always produced.
+ * WP_ERR_ARG (host entry point: before a device is touched): spec NULL, an unknown mode, an unknown long_docs under
+ * NEXT_FIT, want with bits outside 7, max_len < 1 or B < 1, a required pointer NULL (row_splits, ids where there are
+ * ids, an out-pointer, a wanted output of the device call), bad row_splits (row_splits[0] != 0 or a descent: checked on
+ * the host by the host entry point, in a kernel by the device entry point, before anything is written), a device pointer
+ * that is not aligned to its element; in the device call capacity_rows < n_out, with the needed count in *n_out and
+ * nothing written.  WP_ERR_TOO_LARGE, from 64-bit totals before the write pass runs: n_docs, n_ids, N or n_out *
+ * max_len above INT32_MAX.  The size rules are checked before the pointers.  n_docs == 0 or only empty documents:
+ * n_out == 0, every block NULL, and the host entry point needs no device.  The device call runs on the handle's device
+ * and stream, uses buffers of its own (a rows result of the same handle may be fed straight in) and returns when the
+ * batch is complete. */
+#define WP_PACK_NEXT_FIT 0
+#define WP_PACK_STREAM   1
+#define WP_PACK_LONG_TRUNCATE 0
+#define WP_PACK_LONG_SPLIT    1
+#define WP_PACK_WANT_SEGMENTS  1
+#define WP_PACK_WANT_POSITIONS 2
+#define WP_PACK_WANT_SOURCE    4
+typedef struct { int32_t max_len, mode, bos_id, eos_id, pad_id, long_docs, want, reserved; } wp_pack_spec;
+/* the blocks of a packed batch: input_ids, segment_ids, position_ids, source int32 [n_out, max_len], lengths int32 [n_out] */
+typedef struct { int32_t *input_ids, *segment_ids, *position_ids, *source, *lengths; } wp_packed;
+/* host ids in; the blocks out (free each with wp_free) */
+int wp_pack_sequences(wp_vocab *v, const int32_t *ids, const int64_t *row_splits, size_t n_docs,
+                      const wp_pack_spec *spec, wp_packed *out, size_t *n_out);
+/* device ids in, caller-owned device buffers of capacity_rows rows out */
+int wp_pack_sequences_device(wp_vocab *v, const int32_t *d_ids, const int64_t *d_row_splits, size_t n_docs,
+                             const wp_pack_spec *spec, const wp_packed *d_out, size_t capacity_rows, size_t *n_out);
+/* The statistics of the last pack call, in a struct of its own (wp_stats keeps its size); every other statistic keeps
+ * what the last encode left.  n_cells: the sum of lengths (N); n_segments: the sum over the rows of the row's largest
+ * segment id. */
+typedef struct { int64_t n_docs, n_empty, n_cut, n_ids_cut, n_pieces, n_out, n_cells, n_segments; } wp_pack_stats;
+int wp_get_pack_stats(const wp_vocab *v, wp_pack_stats *out); /* n_docs == -1: no such call yet */
+
 /* The same call sharded over several GPUs of the node, behind the boundary: the reference's own
  * precedent is the in-library chunking at whitespace of linear.cpp:283-299 (thread chunks) and
  * linear.cpp:355-367 (encodeExternal batches).  The text is cut at ASCII whitespace into one shard

@@ -31,6 +31,12 @@ WP_NORM_CLEAN, WP_NORM_LOWER, WP_NORM_STRIP_ACCENTS, WP_NORM_BERT_UNCASED = 1, 2
 WP_OFFSETS_BYTES, WP_OFFSETS_CODE_POINTS = 0, 1
 _OFFSET_UNITS = {"byte": WP_OFFSETS_BYTES, "char": WP_OFFSETS_CODE_POINTS}
 WP_TRUNC_LONGEST_FIRST, WP_TRUNC_ONLY_FIRST, WP_TRUNC_ONLY_SECOND = 0, 1, 2
+WP_PACK_NEXT_FIT, WP_PACK_STREAM = 0, 1
+WP_PACK_LONG_TRUNCATE, WP_PACK_LONG_SPLIT = 0, 1
+WP_PACK_WANT_SEGMENTS, WP_PACK_WANT_POSITIONS, WP_PACK_WANT_SOURCE = 1, 2, 4
+_PACK_MODES = {"next_fit": WP_PACK_NEXT_FIT, "stream": WP_PACK_STREAM}
+_PACK_LONG_DOCS = {"truncate": WP_PACK_LONG_TRUNCATE, "split": WP_PACK_LONG_SPLIT}
+_PACK_WANT = {"segment_ids": WP_PACK_WANT_SEGMENTS, "position_ids": WP_PACK_WANT_POSITIONS, "source": WP_PACK_WANT_SOURCE}
 _TRUNCATIONS = {"longest_first": WP_TRUNC_LONGEST_FIRST, "only_first": WP_TRUNC_ONLY_FIRST,
                 "only_second": WP_TRUNC_ONLY_SECOND}
 
@@ -49,6 +55,7 @@ ABI_SYMBOLS = [
     "wp_linear_encode_inputs", "wp_linear_encode_inputs_device", "wp_get_inputs_stats",
     "wp_word_ids", "wp_word_ids_device", "wp_mlm_mask", "wp_mlm_mask_device", "wp_get_mask_stats",
     "wp_detokenize", "wp_detokenize_device", "wp_detok_piece", "wp_get_detok_stats",
+    "wp_pack_sequences", "wp_pack_sequences_device", "wp_get_pack_stats",
 ]
 
 
@@ -156,6 +163,24 @@ class DetokStats(C.Structure):
                 ("n_dropped", C.c_int64), ("n_bytes", C.c_int64)]
 
 
+class PackSpec(C.Structure):
+    """wp_pack_spec: the arguments of a pack call (bos_id / eos_id -1: none)."""
+    _fields_ = [("max_len", C.c_int32), ("mode", C.c_int32), ("bos_id", C.c_int32), ("eos_id", C.c_int32),
+                ("pad_id", C.c_int32), ("long_docs", C.c_int32), ("want", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Packed(C.Structure):
+    """wp_packed: the five blocks of a packed batch (host blocks out, or caller-owned device buffers in)."""
+    _fields_ = [("input_ids", C.c_void_p), ("segment_ids", C.c_void_p), ("position_ids", C.c_void_p), ("source", C.c_void_p),
+                ("lengths", C.c_void_p)]
+
+
+class PackStats(C.Structure):
+    """wp_pack_stats: the statistics of the last pack call (Vocab.pack_stats())."""
+    _fields_ = [("n_docs", C.c_int64), ("n_empty", C.c_int64), ("n_cut", C.c_int64), ("n_ids_cut", C.c_int64),
+                ("n_pieces", C.c_int64), ("n_out", C.c_int64), ("n_cells", C.c_int64), ("n_segments", C.c_int64)]
+
+
 _TEXT_SOURCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t))
 _IDS_SINK = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.c_size_t)
 
@@ -218,6 +243,12 @@ def lib():
         L.wp_detok_piece.argtypes = [vp, C.c_int64, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
         L.wp_detok_piece.restype = C.c_int64
         L.wp_get_detok_stats.argtypes = [vp, C.POINTER(DetokStats)]
+        if hasattr(L, "wp_pack_sequences"):  # (WP_LIB may name a build from before the call: A/B runs against a parent)
+            L.wp_pack_sequences.argtypes = [vp, i32p, i64p, C.c_size_t, C.POINTER(PackSpec), C.POINTER(Packed),
+                                            C.POINTER(C.c_size_t)]
+            L.wp_pack_sequences_device.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(PackSpec), C.POINTER(Packed), C.c_size_t,
+                                                   C.POINTER(C.c_size_t)]
+            L.wp_get_pack_stats.argtypes = [vp, C.POINTER(PackStats)]
         L.wp_linear_encode_multi.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.POINTER(i32p),
                                              C.POINTER(C.c_size_t)]
         L.wp_reserve.argtypes = [vp, C.c_size_t]
@@ -819,6 +850,106 @@ class Vocab:
         off = torch.as_tensor(DeviceIds(d_off.value, n_rows + 1, typestr="<i8"), device=dev)
         return (text.clone(), off.clone()) if copy else (text, off)
 
+    def pack_stats(self):
+        """wp_pack_stats of the last pack call as a dict (n_docs -1: no such call yet)."""
+        s = PackStats()
+        _check(lib().wp_get_pack_stats(self._h, C.byref(s)))
+        return {k: int(getattr(s, k)) for k, _ in s._fields_}
+
+    def pack_sequences(self, ids, row_splits, max_len=128, mode="next_fit", bos_id=None, eos_id=None, pad_id=0,
+                       long_docs="truncate", want=("segment_ids", "position_ids", "source")):
+        """Several encoded documents per row (wp_pack_sequences): ids int32 [n] with row_splits int64 [n_docs + 1] (what
+        encode_rows returns) -> a dict of numpy int32 arrays: input_ids [n_out, max_len], lengths [n_out] and the wanted
+        ones of segment_ids, position_ids, source [n_out, max_len].  Every document becomes [bos] ids [eos]; mode
+        "next_fit": a unit opens a new row when it does not fit behind the ones before it (long_docs: "truncate" cuts a
+        document to one row, "split" cuts it into several units); "stream": the units back to back, cut every max_len
+        cells.  segment_ids count the units of a row from 1 (0: padding), position_ids restart with every unit, source
+        is the index into ids of an id cell (-1: specials, padding)."""
+        a = np.ascontiguousarray(ids, dtype=np.int32)
+        splits = np.ascontiguousarray(row_splits, dtype=np.int64)
+        if a.ndim != 1 or splits.ndim != 1 or len(splits) < 1:
+            raise WordPieceError("ids must be a 1-d array and row_splits a 1-d array of n_docs + 1 entries")
+        if splits[-1] > len(a):
+            raise WordPieceError("row_splits end behind the ids")
+        spec = _pack_spec(max_len, mode, bos_id, eos_id, pad_id, long_docs, want)
+        out, n = Packed(), C.c_size_t()
+        _check(lib().wp_pack_sequences(self._h, _i32_ptr(a), _i64_ptr(splits), len(splits) - 1, C.byref(spec), C.byref(out),
+                                       C.byref(n)))
+        rows, L = n.value, int(max_len)
+        keys = ["input_ids"] + [k for k, bit in _PACK_WANT.items() if spec.want & bit]
+        if rows == 0:
+            res = {k: np.zeros((0, L), np.int32) for k in keys}
+            res["lengths"] = np.zeros(0, np.int32)
+            return res
+        i32p = C.POINTER(C.c_int32)
+        res = {k: _adopt_block(C.cast(getattr(out, k), i32p), (rows, L)) for k in keys}
+        res["lengths"] = _adopt_block(C.cast(out.lengths, i32p), (rows,))
+        return res
+
+    def pack_sequences_tensor(self, ids, row_splits, max_len=128, mode="next_fit", bos_id=None, eos_id=None, pad_id=0,
+                              long_docs="truncate", want=("segment_ids", "position_ids", "source"), n_out=None, out=None):
+        """pack_sequences for tensors on this handle's GPU (wp_pack_sequences_device): ids int32 [n] and row_splits int64
+        [n_docs + 1] (what encode_rows_tensor returns, views included) -> a dict of int32 tensors written by the library
+        into torch.empty tensors (no copy); nothing leaves the device.  n_out: the row count if it is known (an upper
+        bound will do); without it the rows are sized by the stream bound ceil((n + 2 n_docs) / max_len) in stream mode
+        and by min(n_docs, twice that bound + 1) otherwise, and the call runs twice when that was too small (split mode).  out=dict of caller-owned
+        tensors (the same keys) to write into: views of the first n_out rows are returned."""
+        import torch
+        if ids.dtype != torch.int32 or not ids.is_cuda or not ids.is_contiguous() or ids.dim() != 1:
+            raise WordPieceError("pack on tensors needs a contiguous 1-d int32 CUDA/HIP tensor of ids")
+        dev = ids.device
+        if self._device is not None and dev.index != self._device:  # (raw pointers go to the handle's device)
+            raise WordPieceError("the tensors lie on %s, the handle on device %d" % (dev, self._device))
+        if row_splits.dtype != torch.int64 or row_splits.device != dev or row_splits.dim() != 1 or row_splits.numel() < 1 or \
+                not row_splits.is_contiguous():
+            raise WordPieceError("row_splits must be a contiguous 1-d int64 tensor on the device of ids")
+        for t in (ids, row_splits):  # (a view of a tensor may start anywhere)
+            if t.data_ptr() % t.element_size() != 0:
+                raise WordPieceError("the tensors must be aligned to their element size")
+        L = int(max_len)
+        spec = _pack_spec(L, mode, bos_id, eos_id, pad_id, long_docs, want)
+        n_docs = row_splits.numel() - 1
+        keys = ["input_ids"] + [k for k, bit in _PACK_WANT.items() if spec.want & bit] + ["lengths"]
+        if n_out is not None:
+            cap = int(n_out)
+        elif spec.mode == WP_PACK_STREAM:
+            cap = (ids.numel() + 2 * n_docs + L - 1) // L
+        else:  # (two neighbouring rows hold more than max_len cells between them, and a document gives a row at most)
+            cap = min(n_docs, 2 * (ids.numel() + 2 * n_docs) // L + 1)
+        rows = C.c_size_t()
+        for _ in range(2):
+            if out is not None:
+                t = {k: out[k] for k in keys}
+                for k, x in t.items():
+                    if x.dtype != torch.int32 or not x.is_contiguous() or x.device != dev or \
+                            not (x.dim() == 1 if k == "lengths" else x.dim() == 2 and x.shape[1] == L):
+                        raise WordPieceError("out must hold contiguous int32 tensors [rows, max_len] and lengths [rows] on the "
+                                             "device of ids")
+                cap = min(x.shape[0] for x in t.values())
+            else:
+                t = {k: torch.empty(cap if k == "lengths" else (cap, L), dtype=torch.int32, device=dev) for k in keys}
+            bufs = Packed(*[t[k].data_ptr() if k in t and cap else None
+                            for k in ("input_ids", "segment_ids", "position_ids", "source", "lengths")])
+            torch.cuda.current_stream(dev).synchronize()  # the library runs on its own HIP streams
+            rc = lib().wp_pack_sequences_device(
+                self._h, C.c_void_p(ids.data_ptr()) if ids.numel() else None, C.c_void_p(row_splits.data_ptr()), n_docs,
+                C.byref(spec), C.byref(bufs), cap, C.byref(rows))
+            if rc != 0 and out is None and rows.value > cap:  # (guess too small: the call said how many)
+                cap = rows.value
+                continue
+            _check(rc)
+            break
+        return {k: t[k][:rows.value] for k in keys}
+
+    def encode_packed_tensor(self, text, doc_offsets=None, max_len=128, mode="next_fit", bos_id=None, eos_id=None, pad_id=0,
+                             long_docs="truncate", want=("segment_ids", "position_ids", "source"), n_out=None):
+        """Text to a packed batch without leaving the device: encode_rows_tensor without a copy (the rows stay in the
+        library's buffers), then pack_sequences_tensor, which has buffers of its own.  text, doc_offsets as in
+        encode_rows_tensor; the rest as in pack_sequences_tensor."""
+        ids, splits = self.encode_rows_tensor(text, doc_offsets, copy=False)
+        return self.pack_sequences_tensor(ids, splits, max_len=max_len, mode=mode, bos_id=bos_id, eos_id=eos_id, pad_id=pad_id,
+                                          long_docs=long_docs, want=want, n_out=n_out)
+
     def fast_encode(self, text):
         """word_piece::fast::encode on the GPU (wp_fast_encode): host bytes/str -> numpy int32 ids."""
         b = _bytes(text)
@@ -1030,6 +1161,22 @@ def _mask_spec(max_len, mask_id, prob, mask_share, random_share, whole_word, see
     return MaskSpec(int(max_len), _special(cls_id), _special(sep_id), _special(pad_id), int(mask_id), int(ignore_id),
                     int(whole_word), 0, q32(prob), q32(mask_share), q32(random_share), int(seed) & (2 ** 64 - 1),
                     int(row_base) & (2 ** 64 - 1))
+
+
+def _pack_spec(max_len, mode, bos_id, eos_id, pad_id, long_docs, want):
+    if mode not in _PACK_MODES:
+        raise WordPieceError("mode must be one of %s" % ", ".join(sorted(_PACK_MODES)))
+    if long_docs not in _PACK_LONG_DOCS:
+        raise WordPieceError("long_docs must be one of %s" % ", ".join(sorted(_PACK_LONG_DOCS)))
+    if isinstance(want, int):
+        bits = want
+    else:
+        unknown = [k for k in want if k not in _PACK_WANT]
+        if unknown:
+            raise WordPieceError("want names %s; known: %s" % (", ".join(map(str, unknown)), ", ".join(_PACK_WANT)))
+        bits = sum(_PACK_WANT[k] for k in set(want))
+    return PackSpec(int(max_len), _PACK_MODES[mode], _special(bos_id), _special(eos_id), int(pad_id), _PACK_LONG_DOCS[long_docs],
+                    int(bits), 0)
 
 
 def _detok_spec(max_len, skip_ids, cleanup, terminator):

@@ -49,7 +49,8 @@ enum BoundSite {
   kSiteInputs = 9,  // model inputs: the gathers of the packer from the ids and their spans (inputs.h)
   kSiteMask = 10,   // masking: the lookup of an id's class byte (mask.h)
   kSiteDetok = 11,  // detokenize: the record gather, the pool gather and the store of the text (detok.h)
-  kBoundSites = 12
+  kSitePack = 12,   // packing: the gather from the ids, the stores of the batch and of the row starts (packing.h)
+  kBoundSites = 13
 };
 #ifdef WP_DEBUG_BOUNDS
 __device__ unsigned int g_wp_oob[kBoundSites];

@@ -12,6 +12,7 @@
 #include "code.h"
 #include "decode.h"
 #include "detok.h"
+#include "packing.h"
 #include "radix_sort.h"
 #include "scanline.h"
 #include "suffix_array.h"
@@ -152,7 +153,7 @@ static int bit_length(uint64_t v) {
 // c->d_scalars: kScalars 32-bit words that kernels and scans leave their totals in; c->h_scalars: the pinned mirror the
 // host reads them from.  Every word has a name here and nowhere else; no call site names a number.  An encode clears
 // the whole block when it starts (and the pre-pass of WP_OPT_NORMALIZE in front of it does the same, see below).
-constexpr int kScalars = 56;
+constexpr int kScalars = 76;
 constexpr int kScalarCps = 0;       // code points of the text, 32 bits: the decode scan (linear, fast) -> host
 constexpr int kScalarAlphabet = 1;  // alphabet size: alphabet_prefix_kernel -> host
 constexpr int kScalarInvalid = 2;   // invalid sequences, 64 bits (words 2, 3): decode_count_kernel / norm_count_kernel -> host
@@ -190,6 +191,10 @@ constexpr int kScalarMask = 32;    // d_scalars words 32..43: the six 64-bit cou
 constexpr int kScalarDetokLast = 44, kScalarDetokBad = 46;
 constexpr int kScalarFree47 = 47;  // free
 constexpr int kScalarDetok = 48;   // d_scalars words 48..55: the four 64-bit totals of a detokenize call (detok.h, DetokCounter)
+// packing (packing.h): the last entry of row_splits as the check kernel read it, 64 bits (words 56, 57) / its violations
+constexpr int kScalarPackLast = 56, kScalarPackBad = 58;
+constexpr int kScalarFree59 = 59;  // free
+constexpr int kScalarPack = 60;    // d_scalars words 60..75: the eight 64-bit totals of a pack call (packing.h, PackCounter)
 // normalize_on_device runs in front of the encode, which clears the block again: while it runs, four slots mean
 constexpr int kScalarNormBytes = kScalarCps;           // bytes of the normalised text, 32 bits: its scan
 constexpr int kScalarNormCps = kScalarAlphabet;        // code points of the normalised text (offsets mode) -> host
@@ -210,7 +215,8 @@ constexpr ScalarRange kScalarLayout[] = {
     {kScalarRowsCut, 1},     {kScalarCand, 1},       {kScalarKept, 1},            {kScalarSrcRows, 1},
     {kScalarInCut, 1},       {kScalarInRows, 2},     {kScalarInWindowed, 1},      {kScalarFree31, 1},
     {kScalarMask, 12},       {kScalarDetokLast, 2},  {kScalarDetokBad, 1},        {kScalarFree47, 1},
-    {kScalarDetok, 8}};
+    {kScalarDetok, 8},       {kScalarPackLast, 2},   {kScalarPackBad, 1},         {kScalarFree59, 1},
+    {kScalarPack, 16}};
 // one past the last word of the range `slot` lies in: where a download or a clear "through" that slot ends
 constexpr int scalar_end(int slot) {
   for (const ScalarRange &r : kScalarLayout) {
@@ -302,6 +308,9 @@ struct Context {
   DeviceBuffer inputs_buf;  // model inputs: window counts and records per sample (inputs.h)
   // detokenize (detok.h): ids and rows of a host call, tile records and offsets, the text and text_off of the last call
   DeviceBuffer detok_in, detok_aux, detok_out;
+  // packing (packing.h): ids and row_splits of a host call, the per-document plan, the per-piece tables and row starts,
+  // the batch of a host call
+  DeviceBuffer pack_in, pack_plan, pack_tab, pack_out;
   // WP_OPT_NORMALIZE (normalize.h): the tables (uploaded with the first normalising call), the normalised text, the
   // tile counts of the pre-pass, and the source of every normalised code point (offsets mode)
   uint16_t *d_norm_index = nullptr;
@@ -345,9 +354,10 @@ struct Context {
     size_t n = 0, n_text = 0;
   } dbg;
   // every DeviceBuffer above, for destroy_context, release_arenas and park_context: a new buffer is one more name here
-  std::array<DeviceBuffer *, 17> buffers() {
+  std::array<DeviceBuffer *, 21> buffers() {
     return {&text_buf, &a_buf,    &b_buf,   &fmt_buf,    &text_buf2, &ids_stage[0], &ids_stage[1], &rows_in,   &rows_out,
-            &pad_buf,  &inputs_buf, &norm_buf, &norm_aux, &norm_map, &detok_in,     &detok_aux,    &detok_out};
+            &pad_buf,  &inputs_buf, &norm_buf, &norm_aux, &norm_map, &detok_in,     &detok_aux,    &detok_out,
+            &pack_in,  &pack_plan,  &pack_tab, &pack_out};
   }
   Context() = default;
   Context(const Context &) = delete;
@@ -402,6 +412,8 @@ struct EncodeStats : wp_stats {
   int32_t mask_call;
   wp_detok_stats detok;  // wp_get_detok_stats: filled by a detokenize call (detok_call 1), zero otherwise
   int32_t detok_call;
+  wp_pack_stats pack;  // wp_get_pack_stats: filled by a pack call (pack_call 1), zero otherwise
+  int32_t pack_call;
 };
 
 #ifndef WP_LATE_REFINE_DEFAULT

@@ -26,6 +26,7 @@
 #include "inputs.h"
 #include "linear_path.h"
 #include "mask.h"
+#include "packing.h"
 
 
 wp_vocab::~wp_vocab() {
@@ -1483,6 +1484,249 @@ int wp_detokenize_device(wp_vocab *v, const int32_t *d_ids, const int64_t *d_row
     detok_on_device(v, get_context(v), d_ids, g.max_len == 0 ? reinterpret_cast<const long long *>(d_row_splits) : nullptr,
                     g.max_len == 0 ? nullptr : d_lengths, g, spec->cleanup, d_text, &d_off, n_bytes);
     *d_text_off = reinterpret_cast<const int64_t *>(d_off);
+  });
+}
+
+}  // extern "C"
+
+// ---- pack (include/wordpiece_amd.h, section "pack"; kernels: packing.h) ---------------------------------------------
+namespace {
+// every argument rule that needs neither the rows nor a device
+PackGeom check_pack_spec(const wp_pack_spec *spec, size_t n_docs) {
+  if (!spec) throw std::invalid_argument("pack: spec is NULL");
+  if (spec->mode != WP_PACK_NEXT_FIT && spec->mode != WP_PACK_STREAM) throw std::invalid_argument("pack: unknown mode");
+  if (spec->mode == WP_PACK_NEXT_FIT && spec->long_docs != WP_PACK_LONG_TRUNCATE && spec->long_docs != WP_PACK_LONG_SPLIT) {
+    throw std::invalid_argument("pack: unknown long_docs");
+  }
+  if ((spec->want & ~7) != 0) throw std::invalid_argument("pack: want has bits outside 7");
+  if (spec->max_len < 1) throw std::invalid_argument("pack: max_len must be at least 1");
+  const int specials = (spec->bos_id >= 0 ? 1 : 0) + (spec->eos_id >= 0 ? 1 : 0);
+  if (spec->max_len - specials < 1) throw std::invalid_argument("pack: max_len leaves no room for an id beside the specials");
+  if (n_docs > static_cast<size_t>(INT32_MAX)) throw std::length_error("pack: more documents than INT32_MAX");
+  PackGeom g{};
+  g.max_len = spec->max_len;
+  g.budget = spec->max_len - specials;
+  g.stream = spec->mode == WP_PACK_STREAM;
+  g.split = !g.stream && spec->long_docs == WP_PACK_LONG_SPLIT;
+  g.bos_id = spec->bos_id;
+  g.eos_id = spec->eos_id;
+  g.pad_id = spec->pad_id;
+  g.want = spec->want;
+  return g;
+}
+
+wp_pack_stats &begin_pack_stats(wp_vocab *v, size_t n_docs) {
+  v->stats.pack_call = 1;
+  v->stats.pack = wp_pack_stats{};
+  v->stats.pack.n_docs = static_cast<int64_t>(n_docs);
+  return v->stats.pack;
+}
+
+void check_pack_totals(unsigned long long n_ids, unsigned long long n_cells) {
+  if (n_ids > static_cast<unsigned long long>(INT32_MAX)) throw std::length_error("pack: more ids than INT32_MAX");
+  if (n_cells > static_cast<unsigned long long>(INT32_MAX)) throw std::length_error("pack: more cells in the units than INT32_MAX");
+}
+void check_pack_rows(unsigned long long n_out, int max_len) {
+  if (n_out * static_cast<unsigned long long>(max_len) > static_cast<unsigned long long>(INT32_MAX)) {
+    throw std::length_error("pack: n_out * max_len exceeds INT32_MAX");
+  }
+}
+
+// The passes over device buffers on c's stream; the row_splits are checked here in a kernel.  out_for(n_out): the
+// buffers of the batch once the number of rows is known (throws where there is no room); not called for n_out == 0.
+// Returns n_out.  Nothing is written through the caller's pointers before every check has passed.
+template <typename OutFor>
+size_t pack_on_device(wp_vocab *v, Context *c, const int32_t *d_ids, const long long *d_splits, size_t n_docs, PackGeom g, OutFor &&out_for) {
+  wp_pack_stats &ps = begin_pack_stats(v, n_docs);
+  if (n_docs == 0) return 0;
+  hipStream_t st = c->stream;
+  const dim3 block(kBlock);
+  // pieces | cells per document, scanned in place | the scans' tile sums
+  const size_t scan_tmp = up256((cdiv(n_docs, kScanTile) + 1) * sizeof(uint32_t));
+  const size_t off_cells = up256(n_docs * sizeof(uint32_t)), off_tmp = 2 * off_cells;
+  c->pack_plan.ensure(off_tmp + scan_tmp);
+  char *plan = static_cast<char *>(c->pack_plan.p);
+  uint32_t *d_piece_base = reinterpret_cast<uint32_t *>(plan), *d_cell_base = reinterpret_cast<uint32_t *>(plan + off_cells);
+  uint32_t *d_scan_tmp = reinterpret_cast<uint32_t *>(plan + off_tmp);
+  unsigned long long *d_tot = reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarPack);
+  const unsigned long long *h_tot = reinterpret_cast<const unsigned long long *>(c->h_scalars + kScalarPack);
+  clear_scalars(c, kScalarPackLast, kScalarPack, st);
+  hipLaunchKernelGGL(detok_check_splits_kernel, dim3(std::min<unsigned>(cdiv(n_docs + 1, kBlock), 1024u)), block, 0, st, d_splits, n_docs,
+                     c->d_scalars + kScalarPackBad, reinterpret_cast<long long *>(c->d_scalars + kScalarPackLast));
+  hipLaunchKernelGGL(seqpack_plan_kernel, dim3(std::min<unsigned>(cdiv(n_docs, kBlock), kPackMaxGrid)), block, 0, st, d_splits, n_docs, g,
+                     d_piece_base, d_cell_base, d_tot);
+  WP_LAUNCH_CHECK();
+  queue_scalar_slots(c, kScalarPackLast, kScalarPack, st);
+  WP_HIP(hipStreamSynchronize(st));
+  if (c->h_scalars[kScalarPackBad] != 0) throw std::invalid_argument("pack: row_splits must start at 0 and never descend");
+  long long last;
+  std::memcpy(&last, c->h_scalars + kScalarPackLast, sizeof(last));
+  check_pack_totals(static_cast<unsigned long long>(last), h_tot[kPackStream]);
+  if (last > 0 && !d_ids) throw std::invalid_argument("pack: ids is NULL");
+  ps.n_empty = static_cast<int64_t>(h_tot[kPackEmpty]);
+  ps.n_cut = static_cast<int64_t>(h_tot[kPackCut]);
+  ps.n_ids_cut = static_cast<int64_t>(h_tot[kPackIdsCut]);
+  ps.n_pieces = static_cast<int64_t>(h_tot[kPackPieces]);
+  g.n_ids = static_cast<uint32_t>(last);
+  g.n_cells = static_cast<uint32_t>(h_tot[kPackStream]);
+  g.n_pieces = static_cast<uint32_t>(h_tot[kPackPieces]);  // (every unit holds a cell: n_pieces <= n_cells)
+  if (g.n_pieces == 0) return 0;
+  const size_t n_p = g.n_pieces, n_tiles = cdiv(n_p, kPackPieceTile);
+  // P | src0 | nx | row_first | tile_entry | tile_row | records
+  const size_t per_piece = up256((n_p + 1) * sizeof(uint32_t)), per_tile = up256(n_tiles * sizeof(uint32_t));
+  const size_t off_entry = 4 * per_piece, off_rec = off_entry + 2 * per_tile;
+  c->pack_tab.ensure(off_rec + up256(n_p * sizeof(unsigned long long)));
+  char *tab = static_cast<char *>(c->pack_tab.p);
+  uint32_t *d_P = reinterpret_cast<uint32_t *>(tab), *d_nx = reinterpret_cast<uint32_t *>(tab + 2 * per_piece);
+  int32_t *d_src0 = reinterpret_cast<int32_t *>(tab + per_piece);
+  uint32_t *d_row_first = reinterpret_cast<uint32_t *>(tab + 3 * per_piece);
+  uint32_t *d_tile_entry = reinterpret_cast<uint32_t *>(tab + off_entry), *d_tile_row = reinterpret_cast<uint32_t *>(tab + off_entry + per_tile);
+  unsigned long long *d_rec = reinterpret_cast<unsigned long long *>(tab + off_rec);
+  device_exclusive_scan(d_piece_base, d_piece_base, n_docs, d_scan_tmp, nullptr, st);
+  device_exclusive_scan(d_cell_base, d_cell_base, n_docs, d_scan_tmp, nullptr, st);
+  hipLaunchKernelGGL(seqpack_pieces_kernel, dim3(cdiv(n_p, kBlock)), block, 0, st, d_splits, static_cast<uint32_t>(n_docs), d_piece_base,
+                     d_cell_base, g, d_P, d_src0);
+  WP_LAUNCH_CHECK();
+  unsigned long long n_out = (static_cast<unsigned long long>(g.n_cells) + g.max_len - 1) / static_cast<unsigned long long>(g.max_len);
+  if (!g.stream) {
+    WP_HIP(hipMemsetAsync(d_tile_entry, 0xFF, n_tiles * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(seqpack_tile_kernel, dim3(static_cast<unsigned>(n_tiles)), block, 0, st, d_P, g.n_pieces, static_cast<uint32_t>(g.max_len),
+                       d_nx, d_rec);
+    hipLaunchKernelGGL(seqpack_spine_kernel, dim3(1), dim3(kWave), 0, st, d_rec, g.n_pieces, d_tile_entry, d_tile_row, d_row_first, d_tot);
+    WP_LAUNCH_CHECK();
+    queue_scalar_slots(c, kScalarPack, kScalarPack, st);
+    WP_HIP(hipStreamSynchronize(st));
+    n_out = h_tot[kPackRows];
+  }
+  ps.n_out = static_cast<int64_t>(n_out);
+  check_pack_rows(n_out, g.max_len);
+  g.n_out = static_cast<uint32_t>(n_out);
+  const PackOut o = out_for(static_cast<size_t>(n_out));
+  if (!g.stream) {
+    hipLaunchKernelGGL(seqpack_apply_kernel, dim3(static_cast<unsigned>(n_tiles)), block, 0, st, d_nx, g.n_pieces, static_cast<uint32_t>(g.max_len),
+                       d_tile_entry, d_tile_row, d_row_first);
+  }
+  const size_t cell_tiles = cdiv(static_cast<size_t>(n_out) * static_cast<size_t>(g.max_len), kPackCellTile);
+  hipLaunchKernelGGL(seqpack_write_kernel, dim3(static_cast<unsigned>(std::min<size_t>(cell_tiles, kPackMaxGrid))), block, 0, st, d_ids, d_P,
+                     d_src0, d_row_first, g, o, d_tot);
+  WP_LAUNCH_CHECK();
+  queue_scalar_slots(c, kScalarPack, kScalarPack, st);
+  WP_HIP(hipStreamSynchronize(st));
+#ifdef WP_DEBUG_BOUNDS
+  {
+    unsigned int oob = 0;
+    take_oob(kSitePack, 1, &oob);
+    if (oob != 0) throw HipError("debug bounds: pack: " + std::to_string(oob) + " gathers or stores outside their buffers skipped");
+  }
+#endif
+  ps.n_cells = static_cast<int64_t>(h_tot[kPackCells]);
+  ps.n_segments = static_cast<int64_t>(h_tot[kPackSegments]);
+  return static_cast<size_t>(n_out);
+}
+}  // namespace
+
+extern "C" {
+
+int wp_get_pack_stats(const wp_vocab *v, wp_pack_stats *out) {
+  *out = v->stats.pack;
+  if (!v->stats.pack_call) out->n_docs = -1;
+  return WP_OK;
+}
+
+int wp_pack_sequences(wp_vocab *v, const int32_t *ids, const int64_t *row_splits, size_t n_docs, const wp_pack_spec *spec,
+                      wp_packed *out, size_t *n_out) {
+  return guarded([&] {
+    if (!out || !n_out) throw std::invalid_argument("pack: an out-pointer is NULL");
+    *out = wp_packed{};
+    *n_out = 0;
+    const PackGeom g = check_pack_spec(spec, n_docs);
+    if (!row_splits) throw std::invalid_argument("pack: row_splits is NULL");
+    if (row_splits[0] != 0) throw std::invalid_argument("pack: row_splits must start at 0");
+    const unsigned long long s = static_cast<unsigned long long>(g.max_len - g.budget), B = static_cast<unsigned long long>(g.budget);
+    unsigned long long n_cells = 0, n_pieces = 0, n_empty = 0;
+    for (size_t r = 0; r < n_docs; r++) {
+      if (row_splits[r + 1] < row_splits[r]) throw std::invalid_argument("pack: row_splits must never descend");
+      const unsigned long long l = static_cast<unsigned long long>(row_splits[r + 1] - row_splits[r]);
+      if (l == 0) {
+        n_empty++;
+        continue;
+      }
+      const unsigned long long np = g.split ? (l - 1) / B + 1 : 1ull;
+      n_pieces += np;
+      n_cells += (g.stream || g.split ? l : std::min(l, B)) + np * s;  // (l < 2^63, np * s <= 2 l: no wrap before the check of n_ids)
+      if (n_cells > (1ull << 62)) n_cells = 1ull << 62;
+    }
+    const size_t n_ids = static_cast<size_t>(row_splits[n_docs]);
+    check_pack_totals(n_ids, n_cells);
+    if (g.stream) check_pack_rows((n_cells + g.max_len - 1) / static_cast<unsigned long long>(g.max_len), g.max_len);
+    if (n_ids > 0 && !ids) throw std::invalid_argument("pack: ids is NULL");
+    if (n_pieces == 0) {  // no document, or empty ones only: no device
+      begin_pack_stats(v, n_docs).n_empty = static_cast<int64_t>(n_empty);
+      return;
+    }
+    Context *c = get_context(v);
+    // ids | row_splits
+    const size_t off_rows = up256(n_ids * sizeof(int32_t));
+    c->pack_in.ensure(off_rows + up256((n_docs + 1) * sizeof(int64_t)));
+    int32_t *d_ids = static_cast<int32_t *>(c->pack_in.p);
+    long long *d_rows = reinterpret_cast<long long *>(static_cast<char *>(c->pack_in.p) + off_rows);
+    WP_HIP(hipMemcpyAsync(d_ids, ids, n_ids * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    WP_HIP(hipMemcpyAsync(d_rows, row_splits, (n_docs + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    PackOut o{};
+    const size_t rows = pack_on_device(v, c, d_ids, d_rows, n_docs, g, [&](size_t n) {
+      // input_ids | segment_ids | position_ids | source | lengths
+      const size_t block = up256(n * static_cast<size_t>(g.max_len) * sizeof(int32_t));
+      c->pack_out.ensure(4 * block + up256(n * sizeof(int32_t)));
+      char *p = static_cast<char *>(c->pack_out.p);
+      o = PackOut{reinterpret_cast<int32_t *>(p), reinterpret_cast<int32_t *>(p + block), reinterpret_cast<int32_t *>(p + 2 * block),
+                  reinterpret_cast<int32_t *>(p + 3 * block), reinterpret_cast<int32_t *>(p + 4 * block)};
+      return o;
+    });
+    if (rows == 0) return;
+    const size_t cells = rows * static_cast<size_t>(g.max_len) * sizeof(int32_t);
+    Downloads down(c->stream);
+    down.add(&out->input_ids, o.input_ids, cells);
+    if (g.want & WP_PACK_WANT_SEGMENTS) down.add(&out->segment_ids, o.segment_ids, cells);
+    if (g.want & WP_PACK_WANT_POSITIONS) down.add(&out->position_ids, o.position_ids, cells);
+    if (g.want & WP_PACK_WANT_SOURCE) down.add(&out->source, o.source, cells);
+    down.add(&out->lengths, o.lengths, rows * sizeof(int32_t));
+    down.finish();
+    *n_out = rows;
+  });
+}
+
+int wp_pack_sequences_device(wp_vocab *v, const int32_t *d_ids, const int64_t *d_row_splits, size_t n_docs, const wp_pack_spec *spec,
+                             const wp_packed *d_out, size_t capacity_rows, size_t *n_out) {
+  return guarded([&] {
+    if (!n_out) throw std::invalid_argument("pack: an out-pointer is NULL");
+    *n_out = 0;
+    const PackGeom g = check_pack_spec(spec, n_docs);
+    if (!d_row_splits) throw std::invalid_argument("pack: row_splits is NULL");
+    if (!d_out) throw std::invalid_argument("pack: an out-pointer is NULL");
+    // (buffers of no rows may be NULL: any row at all then fails the capacity rule, with the count)
+    if (capacity_rows > 0 && (!d_out->input_ids || !d_out->lengths || ((g.want & WP_PACK_WANT_SEGMENTS) && !d_out->segment_ids) ||
+                              ((g.want & WP_PACK_WANT_POSITIONS) && !d_out->position_ids) || ((g.want & WP_PACK_WANT_SOURCE) && !d_out->source))) {
+      throw std::invalid_argument("pack: an output buffer is NULL");
+    }
+    PackOut o{d_out->input_ids, (g.want & WP_PACK_WANT_SEGMENTS) ? d_out->segment_ids : nullptr,
+              (g.want & WP_PACK_WANT_POSITIONS) ? d_out->position_ids : nullptr, (g.want & WP_PACK_WANT_SOURCE) ? d_out->source : nullptr,
+              d_out->lengths};
+    for (const void *p : {static_cast<const void *>(d_ids), static_cast<const void *>(o.input_ids), static_cast<const void *>(o.segment_ids),
+                          static_cast<const void *>(o.position_ids), static_cast<const void *>(o.source), static_cast<const void *>(o.lengths)}) {
+      if ((reinterpret_cast<uintptr_t>(p) & 3u) != 0) throw std::invalid_argument("pack: device ids and outputs must be 4-byte aligned");
+    }
+    if ((reinterpret_cast<uintptr_t>(d_row_splits) & 7u) != 0) throw std::invalid_argument("pack: device row_splits must be 8-byte aligned");
+    if (n_docs == 0) {
+      begin_pack_stats(v, 0);
+      return;
+    }
+    *n_out = pack_on_device(v, get_context(v), d_ids, reinterpret_cast<const long long *>(d_row_splits), n_docs, g, [&](size_t n) {
+      if (n > capacity_rows) {
+        *n_out = n;
+        throw std::invalid_argument("pack: capacity_rows is smaller than the number of output rows");
+      }
+      return o;
+    });
   });
 }
 

@@ -336,7 +336,7 @@ MAX_LENS = (1, 2, 3, 4, 5, 8, 9, 16, 17, 32, 33, 63, 64, 65, 129, 200)
 
 
 def lanes_for(max_len):
-    """encoder.hip, lanes_for: lanes of a wave that share a row"""
+    """rows.h, lanes_for: lanes of a wave that share a row"""
     lanes = 4
     while lanes < WAVE and lanes < max_len:
         lanes *= 2

@@ -1,5 +1,6 @@
 // context.h — what a vocabulary handle owns on a device: streams, vocabulary tables, bump arenas, the pool of parked
-// contexts (the C ABI itself is in encoder.hip; the device path in linear_path.h and fast_path.h).
+// contexts (the C ABI itself is in encoder.hip; the device path in linear_path.h and fast_path.h, the layers on top of
+// it in rows_path.h, inputs_path.h, mask_path.h, detok_path.h and pack_path.h).
 #pragma once
 #include <array>
 #include <cstring>
@@ -391,6 +392,15 @@ static void take_oob(int first, int count, unsigned int *oob) {
   WP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_wp_oob), zero, count * sizeof(unsigned int), first * sizeof(unsigned int)));
 }
 #endif
+// behind the last kernel of a layer's call: the bounds-checking build fails the call where the kernels skipped an access
+// at `site` (the release build counts nothing)
+static void throw_if_oob(int site, const char *layer, const char *skipped) {
+#ifdef WP_DEBUG_BOUNDS
+  unsigned int oob = 0;
+  take_oob(site, 1, &oob);
+  if (oob != 0) throw HipError(std::string("debug bounds: ") + layer + ": " + std::to_string(oob) + " " + skipped);
+#endif
+}
 
 }  // namespace wp
 
@@ -635,6 +645,34 @@ static Context *get_context(wp_vocab *v) {
   if (!v->ctx) v->ctx = make_context(v, v->device);
   WP_HIP(hipSetDevice(v->ctx->device));
   return v->ctx.get();
+}
+
+// uploads [utf8, utf8 + nbytes) into a text buffer (grown and padded as the decoder expects: text_room) on stream st
+static void upload_text(DeviceBuffer &buf, hipStream_t st, const char *utf8, size_t nbytes) {
+  buf.ensure(text_room(nbytes));
+  zero_text_tail(buf.p, nbytes, st);
+  WP_HIP(hipMemcpyAsync(buf.p, utf8, nbytes, hipMemcpyHostToDevice, st));
+}
+static void upload_text(Context *c, const char *utf8, size_t nbytes) { upload_text(c->text_buf, c->stream, utf8, nbytes); }
+
+// The ids and the rows of a host call (detokenize, pack) in `buf`, ids | rows: n_ids int32 go up on st, and row_bytes of
+// `rows` (nullptr: none) into room for the n_rows + 1 entries of row_splits.
+struct StagedRows {
+  int32_t *d_ids = nullptr;
+  long long *d_rows = nullptr;
+};
+static StagedRows stage_ids_and_rows(DeviceBuffer &buf, hipStream_t st, const int32_t *ids, size_t n_ids, const void *rows, size_t row_bytes,
+                                     size_t n_rows) {
+  Arena in(&buf);
+  StagedRows s;
+  for (int pass = 0; pass < 2; pass++) {
+    s.d_ids = in.take<int32_t>(n_ids);
+    s.d_rows = in.take<long long>(n_rows + 1);
+    if (pass == 0) in.commit();
+  }
+  if (n_ids) WP_HIP(hipMemcpyAsync(s.d_ids, ids, n_ids * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  if (rows) WP_HIP(hipMemcpyAsync(s.d_rows, rows, row_bytes, hipMemcpyHostToDevice, st));
+  return s;
 }
 
 // queues the copy of the device scalars from word 0 through slot `last` to the pinned mirror

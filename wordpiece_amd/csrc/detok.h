@@ -32,7 +32,6 @@
 #include <string>
 
 #include "common.h"
-#include "mask.h"  // bits_up_to, top_bit
 #include "primitives.h"
 #include "vocab.h"
 
@@ -126,41 +125,6 @@ constexpr uint32_t kDetokTailKept = 4;  // a kept cell follows the last row star
 // the totals of a call, 64 bits each, in this order behind d_scalars + kScalarDetok
 enum DetokCounter { kDetokBytes = 0, kDetokKept, kDetokSkipped, kDetokDropped, kDetokCounters };
 
-__device__ __forceinline__ unsigned long long wave_incl_sum64(unsigned long long v) {
-  const int lane = lane_id();
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) {
-    unsigned long long t = __shfl_up(v, d, kWave);
-    if (lane >= d) v += t;
-  }
-  return v;
-}
-__device__ __forceinline__ unsigned long long wave_reduce_sum64(unsigned long long v) {
-#pragma unroll
-  for (int d = kWave / 2; d > 0; d >>= 1) v += __shfl_xor(v, d, kWave);
-  return v;
-}
-// The running maximum of the threads in front of this one (-1 in front of thread 0; all values >= -1); total: the
-// block's maximum.  smem: >= 4 int32.
-__device__ __forceinline__ int32_t block_excl_max(int32_t v, int32_t *smem, int32_t &total) {
-  const int lane = lane_id(), w = wave_id();
-  const int32_t inc = wave_incl_max(v);
-  __syncthreads();  // protect smem reuse across calls
-  if (lane == kWave - 1) smem[w] = inc;
-  __syncthreads();
-  int32_t ex = __shfl_up(inc, 1, kWave);
-  if (lane == 0) ex = -1;
-  int32_t tot = -1;
-#pragma unroll
-  for (int i = 0; i < kBlock / kWave; i++) {
-    const int32_t s = smem[i];
-    if (i < w) ex = max(ex, s);
-    tot = max(tot, s);
-  }
-  total = tot;
-  return ex;
-}
-
 // the first slot of row r, for 0 <= r <= n_rows (n_rows: the end slot)
 __device__ __forceinline__ long long detok_first_cell(const long long *__restrict__ row_splits, const DetokGeom &g, long long r) {
   return g.max_len > 0 ? r * g.max_len : row_splits[r];
@@ -179,16 +143,6 @@ __device__ inline long long detok_rows_below(const long long *__restrict__ row_s
     }
   }
   return lo;
-}
-
-// ragged rows given in device memory: splits[0] == 0, no descent.  bad: violations; last: splits[n_rows].
-__global__ __launch_bounds__(kBlock) void detok_check_splits_kernel(const long long *__restrict__ splits, size_t n_rows,
-                                                                    uint32_t *__restrict__ bad, long long *__restrict__ last) {
-  for (size_t r = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x; r <= n_rows; r += static_cast<size_t>(gridDim.x) * kBlock) {
-    const long long s = splits[r];
-    if (s < 0 || (r == 0 && s != 0) || (r < n_rows && splits[r + 1] < s)) atomicAdd(bad, 1u);
-    if (r == n_rows) *last = s;
-  }
 }
 
 // One tile of kDetokTile slots.  rec: the records of the call's cleanup value, [2][vocab_size] (form, id).

@@ -1,6 +1,8 @@
 // encoder.hip — the C ABI of the HIP Linear-WordPiece path (include/wordpiece_amd.h) and the one translation unit the
-// device code is compiled in.  The device path itself: linear_path.h (word_piece::linear, stage by stage) and
-// fast_path.h (word_piece::fast); what a handle owns on a device: context.h.
+// device code is compiled in: the entry points (out-pointers, the answers that need no device, uploads and downloads),
+// the pinned pool, the multi-GPU, batch, stream, file and external calls.  The device path itself: linear_path.h
+// (word_piece::linear, stage by stage) and fast_path.h (word_piece::fast); the layers on top of it, one host header
+// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h; what a handle owns on a device: context.h.
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -10,7 +12,6 @@
 #include <chrono>
 #include <cstring>
 #include <fstream>
-#include <functional>
 #include <future>
 #include <memory>
 #include <mutex>
@@ -20,13 +21,14 @@
 
 #include "../../include/wordpiece_amd.h"
 #include "context.h"
-#include "detok.h"
+#include "detok_path.h"
 #include "fast_path.h"
 #include "format.h"
-#include "inputs.h"
+#include "inputs_path.h"
 #include "linear_path.h"
-#include "mask.h"
-#include "packing.h"
+#include "mask_path.h"
+#include "pack_path.h"
+#include "rows_path.h"
 
 
 wp_vocab::~wp_vocab() {
@@ -66,20 +68,26 @@ static int guarded(F &&f) {
 }
 
 // ---- argument rules that several entry points share -----------------------------------------------------------------
-static void check_device_text(const void *d_utf8) {
-  if ((reinterpret_cast<uintptr_t>(d_utf8) & 3u) != 0) throw std::invalid_argument("device text must be 4-byte aligned");
+// a pointer the kernels load or store `bytes` (4 or 8) at a time through
+static void check_aligned(const void *p, size_t bytes, const char *message) {
+  if ((reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0) throw std::invalid_argument(message);
 }
-static void check_device_doc_off(const void *d_doc_off) {
-  if ((reinterpret_cast<uintptr_t>(d_doc_off) & 7u) != 0) throw std::invalid_argument("device document offsets must be 8-byte aligned");
-}
+static void check_device_text(const void *d_utf8) { check_aligned(d_utf8, 4, "device text must be 4-byte aligned"); }
+static void check_device_doc_off(const void *d_doc_off) { check_aligned(d_doc_off, 8, "device document offsets must be 8-byte aligned"); }
 // a device documents call without text has no rows: explicit rows cannot end at 0 unless there are none
 static void check_doc_off_without_text(const void *d_doc_off, size_t n_docs) {
   if (d_doc_off && n_docs != 0) throw std::invalid_argument("document offsets must increase from 0 to nbytes");
 }
 static bool known_norm_flags(int64_t flags) { return flags >= 0 && (flags & ~static_cast<int64_t>(kNormKnownFlags)) == 0; }
 
-// wp_vocab_token_flags, and the class byte of an id on the device (mask.h)
-static int32_t token_flags(const HostToken &t) { return (t.is_prefix ? 1 : 0) | (t.is_special ? 2 : 0) | (t.is_malformed ? 4 : 0); }
+// row_splits of a host call: start at 0, never descend; returns the last entry (its bound is the caller's, in its own words)
+static int64_t check_row_splits(const char *prefix, const int64_t *row_splits, size_t n) {
+  if (row_splits[0] != 0) throw std::invalid_argument(std::string(prefix) + ": row_splits must start at 0");
+  for (size_t r = 0; r < n; r++) {
+    if (row_splits[r + 1] < row_splits[r]) throw std::invalid_argument(std::string(prefix) + ": row_splits must never descend");
+  }
+  return row_splits[n];
+}
 
 static int vocab_from_lines(const std::vector<std::pair<const char *, size_t>> &lines, wp_vocab **out) {
   if (!out) {
@@ -375,21 +383,6 @@ class Downloads {
 using wp_clock = std::chrono::steady_clock;
 double ms_since(wp_clock::time_point t0) { return std::chrono::duration<double, std::milli>(wp_clock::now() - t0).count(); }
 
-// uploads [utf8, utf8 + nbytes) into a text buffer (grown and padded as the decoder expects: context.h) on stream st
-void upload_text(DeviceBuffer &buf, hipStream_t st, const char *utf8, size_t nbytes) {
-  buf.ensure(text_room(nbytes));
-  zero_text_tail(buf.p, nbytes, st);
-  WP_HIP(hipMemcpyAsync(buf.p, utf8, nbytes, hipMemcpyHostToDevice, st));
-}
-void upload_text(Context *c, const char *utf8, size_t nbytes) { upload_text(c->text_buf, c->stream, utf8, nbytes); }
-
-// lanes of a wave that share a row of max_len cells (pack_rows_kernel, inputs_pack_kernel, mask_kernel)
-int lanes_for(int max_len) {
-  int lanes = 4;
-  while (lanes < kWave && lanes < max_len) lanes *= 2;
-  return lanes;
-}
-
 // The batch of a call whose documents are all empty, on the host: n rows of specials and padding, and their lengths.
 // token_types / sample: the two further arrays of an inputs call (nullptr: a padded call); second_sep: its pair form.
 void fill_empty_rows(size_t n, int max_len, int32_t cls_id, int32_t sep_id, int32_t pad_id, bool second_sep, int32_t *ids,
@@ -407,6 +400,12 @@ void fill_empty_rows(size_t n, int max_len, int32_t cls_id, int32_t sep_id, int3
     while (col < max_len) row[col++] = pad_id;
     if (sample) sample[r] = static_cast<int32_t>(r);
   }
+}
+
+void *zeroed(size_t bytes) {
+  void *p = std::calloc(std::max<size_t>(bytes, 1), 1);
+  if (!p) throw std::bad_alloc();
+  return p;
 }
 
 bool ascii_space(uint8_t b) { return (b >= 0x09 && b <= 0x0d) || b == 0x20; }
@@ -729,207 +728,7 @@ int wp_linear_encode_offsets_device(wp_vocab *v, const void *d_utf8, size_t nbyt
 
 }  // extern "C"
 
-// ---- documents (include/wordpiece_amd.h, section "documents"; kernels: rows.h) --------------------------------------
-namespace {
-struct RowsResult {  // device pointers, valid until the handle's next call
-  const int32_t *d_ids = nullptr;
-  const long long *d_row_splits = nullptr;
-  const uint32_t *d_offs = nullptr;
-  size_t n_ids = 0, n_rows = 0;
-};
-
-// A vocabulary that can match differently inside a joined text than in a document of its own: an eligible token with
-// U+000A matches across the separator; a token with U+0000 / U+0001 can match into the 1 . vocab tail of S, which only
-// the end of a text has; with duplicate eligible lines the copy a match at the end of a text names depends on what
-// follows it.  Such batches are encoded document by document.
-bool rows_per_document(const wp_vocab *v) { return v->hv.newline_in_token || v->hv.low_cp || v->hv.n_dup_eligible > 0; }
-
-void check_rows_call(int unit, size_t nbytes) {
-  if (unit != -1 && unit != WP_OFFSETS_BYTES && unit != WP_OFFSETS_CODE_POINTS) {
-    throw std::invalid_argument("offsets unit must be -1 (none), 0 (bytes) or 1 (code points)");
-  }
-  // (row membership goes through the 32-bit first-byte table of the code points in every unit)
-  if (nbytes > static_cast<size_t>(UINT32_MAX)) throw std::length_error("a documents call needs nbytes <= UINT32_MAX");
-}
-
-int padded_specials(int max_len, int32_t cls_id, int32_t sep_id) {
-  const int specials = (cls_id >= 0 ? 1 : 0) + (sep_id >= 0 ? 1 : 0);
-  if (max_len < 1 || max_len < specials) throw std::invalid_argument("max_len must be at least 1 and at least the number of specials");
-  return specials;
-}
-
-void check_doc_off_host(const char *utf8, size_t nbytes, const int64_t *doc_off, size_t n_docs) {
-  bool ok = doc_off[0] == 0 && static_cast<uint64_t>(doc_off[n_docs]) == nbytes && doc_off[n_docs] >= 0;
-  for (size_t i = 1; ok && i <= n_docs; i++) {
-    ok = doc_off[i] > doc_off[i - 1] && static_cast<uint64_t>(doc_off[i]) <= nbytes && utf8[doc_off[i] - 1] == '\n';
-  }
-  if (!ok) throw std::invalid_argument("document offsets must increase from 0 to nbytes with a '\\n' in front of each");
-}
-
-// The per-document route: the rows' starts come to the host (explicit: checked and copied; lines: found by the kernels
-// of the joined route), every document is copied into the context's second text buffer (a document starts at any byte,
-// the decoder wants 4-byte alignment) and encoded through the existing ids-only / offsets path, and the assembled result
-// goes back into c->rows_out.  A correctness route: it syncs per document.
-void rows_by_document(wp_vocab *v, Context *c, const uint8_t *d_text, size_t nbytes, const long long *d_doc_off, size_t n_docs,
-                      int unit, size_t capacity, RowsResult &out) {
-  hipStream_t st = c->stream;
-  clear_scalars(c, kScalarRows, kScalarRowsCut, st);
-  size_t n_rows = n_docs;
-  const void *d_starts = d_doc_off;
-  auto check_capacity = [&] {
-    out.n_rows = n_rows;
-    if (n_rows > capacity) throw std::invalid_argument("capacity_rows is smaller than the number of rows");
-  };
-  if (d_doc_off) {
-    hipLaunchKernelGGL(rows_check_kernel, dim3(cdiv(n_docs + 1, kBlock)), dim3(kBlock), 0, st, d_text, nbytes, d_doc_off, n_docs,
-                       c->d_scalars + kScalarRowsBad);
-    WP_LAUNCH_CHECK();
-    fetch_scalars(c, kScalarRowsCut);
-    if (c->h_scalars[kScalarRowsBad] != 0) {
-      throw std::invalid_argument("document offsets must increase from 0 to nbytes with a '\\n' in front of each");
-    }
-    check_capacity();
-  } else {
-    const unsigned tiles = cdiv(nbytes, kLineTile);
-    const size_t tmp_words = cdiv(tiles, kScanTile) + 8;
-    c->rows_in.ensure((tiles + 1 + tmp_words) * sizeof(uint32_t));
-    uint32_t *d_cnt = static_cast<uint32_t *>(c->rows_in.p);
-    hipLaunchKernelGGL(line_count_kernel, dim3(tiles), dim3(kBlock), 0, st, d_text, nbytes, d_cnt);
-    device_exclusive_scan(d_cnt, d_cnt, tiles, d_cnt + tiles + 1, c->d_scalars + kScalarRows, st);
-    fetch_scalars(c, kScalarRowsCut);
-    n_rows = c->h_scalars[kScalarRows];
-    check_capacity();
-    c->rows_out.ensure((n_rows + 1) * sizeof(long long));
-    hipLaunchKernelGGL(line_write_kernel, dim3(tiles), dim3(kBlock), 0, st, d_text, nbytes, static_cast<const uint32_t *>(d_cnt), n_rows,
-                       static_cast<long long *>(c->rows_out.p));
-    WP_LAUNCH_CHECK();
-    d_starts = c->rows_out.p;
-  }
-  std::vector<long long> starts(n_rows + 1);
-  WP_HIP(hipMemcpyAsync(starts.data(), d_starts, (n_rows + 1) * sizeof(long long), hipMemcpyDeviceToHost, st));
-  WP_HIP(hipStreamSynchronize(st));
-  uint8_t last = '\n';
-  WP_HIP(hipMemcpyAsync(&last, d_text + nbytes - 1, 1, hipMemcpyDeviceToHost, st));
-  WP_HIP(hipStreamSynchronize(st));
-  auto doc_end = [&](size_t i) {  // (a last line without a separator runs to the end of the text)
-    return static_cast<size_t>(starts[i + 1]) - ((i + 1 == n_rows && last != '\n') ? 0 : 1);
-  };
-  size_t longest = 0;
-  for (size_t i = 0; i < n_rows; i++) longest = std::max(longest, doc_end(i) - static_cast<size_t>(starts[i]));
-  c->text_buf2.ensure(text_room(longest));
-  std::vector<int32_t> h_ids;
-  std::vector<uint32_t> h_offs;
-  std::vector<long long> splits(n_rows + 1, 0);
-  EncodeStats last_stats;
-  std::memset(&last_stats, 0, sizeof(last_stats));
-  int32_t guard_zones = 0;
-  int64_t norm_bytes = 0;  // (WP_OPT_NORMALIZE: every document is normalised by its own encode)
-  for (size_t i = 0; i < n_rows; i++) {
-    splits[i] = static_cast<long long>(h_ids.size());
-    const size_t a = static_cast<size_t>(starts[i]), len = doc_end(i) - a;
-    if (len == 0) continue;
-    char *dst = static_cast<char *>(c->text_buf2.p);
-    zero_text_tail(dst, len, st);
-    WP_HIP(hipMemcpyAsync(dst, d_text + a, len, hipMemcpyDeviceToDevice, st));
-    size_t n = 0;
-    encode_on_device(v, c, reinterpret_cast<const uint8_t *>(dst), len, &n, last_stats, unit);
-    guard_zones = std::max(guard_zones, last_stats.guard_zones);
-    norm_bytes += last_stats.norm_bytes;
-    if (n == 0) continue;
-    const size_t at = h_ids.size();
-    h_ids.resize(at + n);
-    WP_HIP(hipMemcpyAsync(h_ids.data() + at, c->d_ids, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (unit >= 0) {
-      h_offs.resize(2 * (at + n));
-      WP_HIP(hipMemcpyAsync(h_offs.data() + 2 * at, c->d_offs, 2 * n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    }
-    WP_HIP(hipStreamSynchronize(st));
-  }
-  const size_t n_ids = h_ids.size();
-  splits[n_rows] = static_cast<long long>(n_ids);
-  // result block: row_splits | offsets | ids
-  const size_t split_bytes = (n_rows + 1) * sizeof(long long), offs_bytes = unit >= 0 ? n_ids * 2 * sizeof(uint32_t) : 0;
-  c->rows_out.ensure(split_bytes + offs_bytes + n_ids * sizeof(int32_t) + 16);
-  char *base = static_cast<char *>(c->rows_out.p);
-  WP_HIP(hipMemcpyAsync(base, splits.data(), split_bytes, hipMemcpyHostToDevice, st));
-  if (offs_bytes) WP_HIP(hipMemcpyAsync(base + split_bytes, h_offs.data(), offs_bytes, hipMemcpyHostToDevice, st));
-  if (n_ids) WP_HIP(hipMemcpyAsync(base + split_bytes + offs_bytes, h_ids.data(), n_ids * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  WP_HIP(hipStreamSynchronize(st));
-  c->d_ids = nullptr;  // (the arenas hold the last document only)
-  c->d_offs = nullptr;
-  out.d_row_splits = reinterpret_cast<const long long *>(base);
-  out.d_offs = (offs_bytes && n_ids) ? reinterpret_cast<const uint32_t *>(base + split_bytes) : nullptr;
-  out.d_ids = n_ids ? reinterpret_cast<const int32_t *>(base + split_bytes + offs_bytes) : nullptr;
-  out.n_ids = n_ids;
-  v->stats = last_stats;  // (of the last non-empty document; the sums of the call below)
-  v->stats.guard_zones = guard_zones;
-  v->stats.normalize = v->normalize;
-  v->stats.norm_bytes = norm_bytes;
-  v->stats.n_bytes = static_cast<int64_t>(nbytes);
-  v->stats.n_ids = static_cast<int64_t>(n_ids);
-  v->stats.n_rows = static_cast<int64_t>(n_rows);
-  v->stats.rows_route = 0;
-}
-
-// both routes: d_text as wp_linear_encode_device wants it, nbytes > 0; d_doc_off in device memory or nullptr (lines)
-void rows_on_device(wp_vocab *v, Context *c, const uint8_t *d_text, size_t nbytes, const long long *d_doc_off, size_t n_docs, int unit,
-                    size_t capacity, RowsResult &out) {
-  if (rows_per_document(v)) {
-    rows_by_document(v, c, d_text, nbytes, d_doc_off, n_docs, unit, capacity, out);
-  } else {
-    RowsCall rc{d_doc_off, n_docs, unit, capacity};
-    size_t n = 0;
-    try {  // (row membership comes from the spans: without a unit they stay in code points, which need no second pass)
-      encode_on_device(v, c, d_text, nbytes, &n, v->stats, unit >= 0 ? unit : WP_OFFSETS_CODE_POINTS, &rc);
-    } catch (...) {
-      out.n_rows = rc.n_rows;
-      throw;
-    }
-    out.d_ids = n ? c->d_ids : nullptr;
-    out.d_row_splits = rc.d_row_splits;
-    out.d_offs = (n && unit >= 0) ? c->d_offs : nullptr;
-    out.n_ids = n;
-    out.n_rows = rc.n_rows;
-  }
-  v->stats.offsets_unit = unit;
-  v->stats.n_devices = 1;
-}
-
-// the padded batch of a rows result, into device buffers of n_rows * max_len and n_rows int32; waits for it
-void pack_on_device(wp_vocab *v, Context *c, const RowsResult &r, int max_len, int32_t cls_id, int32_t sep_id, int32_t pad_id,
-                    int32_t *d_input_ids, int32_t *d_lengths) {
-  v->stats.rows_truncated = 0;
-  if (r.n_rows == 0) return;
-  const int lanes = lanes_for(max_len);
-  clear_scalars(c, kScalarRowsCut, kScalarRowsCut, c->stream);
-  hipLaunchKernelGGL(pack_rows_kernel, dim3(cdiv(r.n_rows, static_cast<size_t>(kBlock / lanes))), dim3(kBlock), 0, c->stream, r.d_ids,
-                     r.d_row_splits, r.n_rows, max_len, cls_id, sep_id, pad_id, lanes, d_input_ids, d_lengths,
-                     c->d_scalars + kScalarRowsCut);
-  WP_LAUNCH_CHECK();
-  fetch_scalars(c, kScalarRowsCut);
-  v->stats.rows_truncated = c->h_scalars[kScalarRowsCut];
-}
-
-// the host form of a documents call as far as its rows: the text and the explicit row starts go up, then rows_on_device
-Context *rows_from_host(wp_vocab *v, const char *utf8, size_t nbytes, const int64_t *doc_off, size_t n_docs, int unit, RowsResult &r) {
-  Context *c = get_context(v);
-  upload_text(c, utf8, nbytes);
-  if (doc_off) {
-    c->rows_in.ensure((n_docs + 1) * sizeof(int64_t));
-    WP_HIP(hipMemcpyAsync(c->rows_in.p, doc_off, (n_docs + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-  }
-  rows_on_device(v, c, static_cast<const uint8_t *>(c->text_buf.p), nbytes, doc_off ? static_cast<const long long *>(c->rows_in.p) : nullptr,
-                 n_docs, unit, SIZE_MAX, r);
-  return c;
-}
-
-void *zeroed(size_t bytes) {
-  void *p = std::calloc(std::max<size_t>(bytes, 1), 1);
-  if (!p) throw std::bad_alloc();
-  return p;
-}
-}  // namespace
-
+// ---- documents (include/wordpiece_amd.h, section "documents"; host path: rows_path.h) -------------------------------
 extern "C" {
 
 int wp_linear_encode_rows(wp_vocab *v, const char *utf8, size_t nbytes, const int64_t *doc_off, size_t n_docs, int unit,
@@ -1021,13 +820,11 @@ int wp_linear_encode_padded(wp_vocab *v, const char *utf8, size_t nbytes, const 
     const auto t_all = wp_clock::now();
     RowsResult r;
     Context *c = rows_from_host(v, utf8, nbytes, doc_off, n_docs, -1, r);
-    const size_t cells = r.n_rows * static_cast<size_t>(max_len);
-    c->pad_buf.ensure((cells + r.n_rows) * sizeof(int32_t));
-    int32_t *d_out = static_cast<int32_t *>(c->pad_buf.p), *d_len = d_out + cells;
-    pack_on_device(v, c, r, max_len, cls_id, sep_id, pad_id, d_out, d_len);
+    const PaddedBatch b = padded_batch(c, r.n_rows, max_len);
+    pad_rows_on_device(v, c, r, max_len, cls_id, sep_id, pad_id, b.d_input_ids, b.d_lengths);
     Downloads down(c->stream);
-    down.add(input_ids, d_out, cells * sizeof(int32_t));
-    down.add(lengths, d_len, r.n_rows * sizeof(int32_t));
+    down.add(input_ids, b.d_input_ids, r.n_rows * static_cast<size_t>(max_len) * sizeof(int32_t));
+    down.add(lengths, b.d_lengths, r.n_rows * sizeof(int32_t));
     down.finish();
     *n_rows = r.n_rows;
     v->stats.ms_host_total = ms_since(t_all);
@@ -1057,134 +854,28 @@ int wp_linear_encode_padded_device(wp_vocab *v, const void *d_utf8, size_t nbyte
       *n_rows = r.n_rows;  // (too many rows for the caller's buffers: the count it needs)
       throw;
     }
-    pack_on_device(v, c, r, max_len, cls_id, sep_id, pad_id, d_input_ids, d_lengths);
+    pad_rows_on_device(v, c, r, max_len, cls_id, sep_id, pad_id, d_input_ids, d_lengths);
     *n_rows = r.n_rows;
   });
 }
 
 }  // extern "C"
 
-// ---- masking (include/wordpiece_amd.h, section "masking"; kernel: mask.h) --------------------------------------------
-namespace {
-constexpr unsigned long long kQ32One = 1ull << 32;
-
-// every argument rule of a mask (mask_call) or word-ids call that needs no device
-MaskGeom check_mask_spec(const wp_vocab *v, const wp_mask_spec *spec, size_t n_rows, bool mask_call) {
-  if (!spec) throw std::invalid_argument("mask: spec is NULL");
-  if (spec->max_len < 1) throw std::invalid_argument("mask: max_len must be at least 1");
-  MaskGeom g{};
-  g.max_len = spec->max_len;
-  g.cls_id = spec->cls_id;
-  g.sep_id = spec->sep_id;
-  g.pad_id = spec->pad_id;
-  g.vocab_size = static_cast<long long>(v->hv.tokens.size());
-  if (mask_call) {
-    if (spec->whole_word != 0 && spec->whole_word != 1) throw std::invalid_argument("mask: whole_word must be 0 or 1");
-    if (spec->select_q32 > kQ32One) throw std::invalid_argument("mask: select_q32 must be at most 2^32");
-    if (spec->mask_q32 > kQ32One) throw std::invalid_argument("mask: mask_q32 must be at most 2^32");
-    if (spec->random_q32 > kQ32One) throw std::invalid_argument("mask: random_q32 must be at most 2^32");
-    if (spec->mask_q32 + spec->random_q32 > kQ32One) throw std::invalid_argument("mask: mask_q32 + random_q32 must be at most 2^32");
-    if (spec->mask_id < 0) throw std::invalid_argument("mask: mask_id must be at least 0");
-    g.mask_id = spec->mask_id;
-    g.ignore_id = spec->ignore_id;
-    g.whole_word = spec->whole_word;
-    g.select_q32 = spec->select_q32;
-    g.mask_q32 = spec->mask_q32;
-    g.random_q32 = spec->random_q32;
-    g.seed = spec->seed;
-    g.row_base = spec->row_base;
-  }
-  if (n_rows > static_cast<size_t>(INT32_MAX)) throw std::length_error("mask: more rows than INT32_MAX");
-  if (n_rows > SIZE_MAX / sizeof(int32_t) / static_cast<size_t>(spec->max_len)) {
-    throw std::length_error("mask: n_rows * max_len is too large");
-  }
-  return g;
-}
-
-// the statistics of a mask or word-ids call before its counters are known (all there is to say of a call without rows)
-wp_mask_stats &begin_mask_stats(wp_vocab *v, size_t n_rows, int whole_word) {
-  v->stats.mask_call = 1;
-  v->stats.mask = wp_mask_stats{};
-  v->stats.mask.n_rows = static_cast<int64_t>(n_rows);
-  v->stats.mask.whole_word = whole_word;
-  return v->stats.mask;
-}
-
-// One launch of mask_kernel over device buffers on c's stream, one wait (for the counters), the statistics of the call.
-// d_masked == nullptr: the word-ids form.
-void mask_on_device(wp_vocab *v, Context *c, const int32_t *d_in, const int32_t *d_lengths, size_t n_rows, const MaskGeom &g,
-                    int32_t *d_masked, int32_t *d_labels, int32_t *d_word_ids) {
-  const bool mask_call = d_masked != nullptr;
-  wp_mask_stats &ms = begin_mask_stats(v, n_rows, mask_call ? g.whole_word : 0);
-  if (n_rows == 0) return;
-  hipStream_t st = c->stream;
-  if (!c->d_tok_class) {  // one byte per id: wp_vocab_token_flags
-    std::vector<uint8_t> cls(v->hv.tokens.size());
-    for (size_t i = 0; i < cls.size(); i++) cls[i] = static_cast<uint8_t>(token_flags(v->hv.tokens[i]));
-    c->d_tok_class = upload(cls, st);
-    WP_HIP(hipStreamSynchronize(st));  // cls is a local
-  }
-  unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarMask);
-  WP_HIP(hipMemsetAsync(d_cnt, 0, kMaskCounters * sizeof(unsigned long long), st));
-  const int lanes = lanes_for(g.max_len);
-  const size_t n_blocks = (n_rows + static_cast<size_t>(kBlock / lanes) - 1) / static_cast<size_t>(kBlock / lanes);
-  const dim3 grid(static_cast<unsigned>(std::min<size_t>(n_blocks, kMaskMaxGrid))), block(kBlock);
-  if (!mask_call) {
-    hipLaunchKernelGGL((mask_kernel<false, true>), grid, block, 0, st, d_in, d_lengths, n_rows, n_blocks, g, lanes,
-                       c->d_tok_class, d_masked, d_labels,
-                       d_word_ids, d_cnt);
-  } else if (d_word_ids) {
-    hipLaunchKernelGGL((mask_kernel<true, true>), grid, block, 0, st, d_in, d_lengths, n_rows, n_blocks, g, lanes,
-                       c->d_tok_class, d_masked, d_labels,
-                       d_word_ids, d_cnt);
-  } else {
-    hipLaunchKernelGGL((mask_kernel<true, false>), grid, block, 0, st, d_in, d_lengths, n_rows, n_blocks, g, lanes,
-                       c->d_tok_class, d_masked, d_labels,
-                       d_word_ids, d_cnt);
-  }
-  WP_LAUNCH_CHECK();
-  unsigned long long *h_cnt = reinterpret_cast<unsigned long long *>(c->h_scalars + kScalarMask);
-  WP_HIP(hipMemcpyAsync(h_cnt, d_cnt, kMaskCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  WP_HIP(hipStreamSynchronize(st));
-#ifdef WP_DEBUG_BOUNDS
-  {
-    unsigned int oob = 0;
-    take_oob(kSiteMask, 1, &oob);
-    if (oob != 0) throw HipError("debug bounds: masking: " + std::to_string(oob) + " class lookups outside the vocabulary skipped");
-  }
-#endif
-  ms.n_words = static_cast<int64_t>(h_cnt[kMaskWords]);
-  ms.n_selected = static_cast<int64_t>(h_cnt[kMaskSelected]);
-  ms.n_selected_units = static_cast<int64_t>(h_cnt[kMaskUnits]);
-  ms.n_masked = static_cast<int64_t>(h_cnt[kMaskMasked]);
-  ms.n_random = static_cast<int64_t>(h_cnt[kMaskRandom]);
-  ms.n_kept = static_cast<int64_t>(h_cnt[kMaskKept]);
-}
-
-// the host entry points: ids (and lengths) up, one launch, 1..3 blocks of n_rows * max_len int32 down
-void mask_from_host(wp_vocab *v, const int32_t *input_ids, const int32_t *lengths, size_t n_rows, const MaskGeom &g, int32_t **masked,
-                    int32_t **labels, int32_t **word_ids) {
-  const size_t cells = n_rows * static_cast<size_t>(g.max_len);
+// ---- masking (include/wordpiece_amd.h, section "masking"; host path: mask_path.h) ------------------------------------
+// the host entry points behind their argument rules: mask_from_host, then the 1..3 blocks the caller asked for come down
+static void mask_host_call(wp_vocab *v, const int32_t *input_ids, const int32_t *lengths, size_t n_rows, const MaskGeom &g, int32_t **masked,
+                           int32_t **labels, int32_t **word_ids) {
   Context *c = get_context(v);
-  const int n_out = (masked ? 2 : 0) + (word_ids ? 1 : 0);
-  // ids | outputs | lengths
-  c->pad_buf.ensure((cells * (1 + static_cast<size_t>(n_out)) + n_rows) * sizeof(int32_t) + 16);
-  int32_t *d_in = static_cast<int32_t *>(c->pad_buf.p);
-  int32_t *d_masked = masked ? d_in + cells : nullptr, *d_labels = masked ? d_in + 2 * cells : nullptr;
-  int32_t *d_wid = word_ids ? d_in + (masked ? 3 : 1) * cells : nullptr;
-  int32_t *d_len = lengths ? d_in + (1 + static_cast<size_t>(n_out)) * cells : nullptr;
-  WP_HIP(hipMemcpyAsync(d_in, input_ids, cells * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-  if (lengths) WP_HIP(hipMemcpyAsync(d_len, lengths, n_rows * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-  mask_on_device(v, c, d_in, d_len, n_rows, g, d_masked, d_labels, d_wid);
+  const MaskBatch b = mask_from_host(v, c, input_ids, lengths, n_rows, g, masked != nullptr, word_ids != nullptr);
+  const size_t bytes = n_rows * static_cast<size_t>(g.max_len) * sizeof(int32_t);
   Downloads down(c->stream);
   if (masked) {
-    down.add(masked, d_masked, cells * sizeof(int32_t));
-    down.add(labels, d_labels, cells * sizeof(int32_t));
+    down.add(masked, b.d_masked, bytes);
+    down.add(labels, b.d_labels, bytes);
   }
-  if (word_ids) down.add(word_ids, d_wid, cells * sizeof(int32_t));
+  if (word_ids) down.add(word_ids, b.d_word_ids, bytes);
   down.finish();
 }
-}  // namespace
 
 extern "C" {
 
@@ -1205,7 +896,7 @@ int wp_word_ids(wp_vocab *v, const int32_t *input_ids, const int32_t *lengths, s
       begin_mask_stats(v, 0, 0);
       return;
     }
-    mask_from_host(v, input_ids, lengths, n_rows, g, nullptr, nullptr, word_ids);
+    mask_host_call(v, input_ids, lengths, n_rows, g, nullptr, nullptr, word_ids);
   });
 }
 
@@ -1237,7 +928,7 @@ int wp_mlm_mask(wp_vocab *v, const int32_t *input_ids, const int32_t *lengths, s
       begin_mask_stats(v, 0, g.whole_word);
       return;
     }
-    mask_from_host(v, input_ids, lengths, n_rows, g, masked, labels, word_ids);
+    mask_host_call(v, input_ids, lengths, n_rows, g, masked, labels, word_ids);
   });
 }
 
@@ -1258,145 +949,7 @@ int wp_mlm_mask_device(wp_vocab *v, const int32_t *d_input_ids, const int32_t *d
 
 }  // extern "C"
 
-// ---- detokenize (include/wordpiece_amd.h, section "detokenize"; kernels: detok.h) -----------------------------------
-namespace {
-size_t up256(size_t bytes) { return (bytes + 255) & ~static_cast<size_t>(255); }
-
-// every argument rule that needs neither the ids nor a device; n_cells of a padded call, -1 of a ragged one
-DetokGeom check_detok_spec(const wp_vocab *v, const wp_detok_spec *spec, size_t n_rows) {
-  if (!spec) throw std::invalid_argument("detokenize: spec is NULL");
-  if (spec->cleanup != 0 && spec->cleanup != 1) throw std::invalid_argument("detokenize: cleanup must be 0 or 1");
-  if (spec->terminator < -1 || spec->terminator > 255) throw std::invalid_argument("detokenize: terminator must lie in [-1, 255]");
-  if (spec->n_skip < 0 || spec->n_skip > 8) throw std::invalid_argument("detokenize: n_skip must lie in [0, 8]");
-  if (spec->max_len < 0) throw std::invalid_argument("detokenize: max_len must be at least 0");
-  if (n_rows > static_cast<size_t>(INT32_MAX)) throw std::length_error("detokenize: more rows than INT32_MAX");
-  DetokGeom g{};
-  g.n_rows = static_cast<long long>(n_rows);
-  g.max_len = spec->max_len;
-  g.term = spec->terminator;
-  g.n_skip = spec->n_skip;
-  for (int k = 0; k < 8; k++) g.skip_ids[k] = k < spec->n_skip ? spec->skip_ids[k] : -1;
-  g.vocab_size = static_cast<long long>(v->hv.tokens.size());
-  g.n_cells = -1;
-  if (spec->max_len > 0) {  // (n_rows <= 2^31 - 1 and max_len <= 2^31 - 1: the product fits 64 bits)
-    g.n_cells = static_cast<long long>(n_rows) * spec->max_len;
-    if (g.n_cells > INT32_MAX) throw std::length_error("detokenize: more cells than INT32_MAX");
-  }
-  return g;
-}
-
-wp_detok_stats &begin_detok_stats(wp_vocab *v, size_t n_rows) {
-  v->stats.detok_call = 1;
-  v->stats.detok = wp_detok_stats{};
-  v->stats.detok.n_rows = static_cast<int64_t>(n_rows);
-  return v->stats.detok;
-}
-
-// the pieces of every id, both forms, both cleanup values: records [cleanup][form][id] and the pool of their bytes
-void ensure_detok_table(const wp_vocab *v, Context *c) {
-  if (c->d_detok_rec) return;
-  const size_t V = v->hv.tokens.size();
-  std::vector<DetokRec> rec(4 * V);
-  std::vector<uint8_t> pool;
-  for (int cleanup = 0; cleanup < 2; cleanup++) {
-    for (int form = 0; form < 2; form++) {
-      for (size_t i = 0; i < V; i++) {
-        const HostToken &t = v->hv.tokens[i];
-        DetokRec &r = rec[(static_cast<size_t>(cleanup) * 2 + static_cast<size_t>(form)) * V + i];
-        if (t.is_malformed) {
-          r = DetokRec{kDetokNoPiece, 0};
-          continue;
-        }
-        const std::string piece = detok_piece_bytes(t, form, cleanup);
-        if (cleanup == 1 && piece == detok_piece_bytes(t, form, 0)) {  // the clean-up changes few pieces: the bytes are shared
-          r = rec[static_cast<size_t>(form) * V + i];
-          continue;
-        }
-        if (pool.size() + piece.size() >= static_cast<size_t>(kDetokNoPiece)) throw std::length_error("detokenize: the pieces of the vocabulary exceed 4 GB");
-        r = DetokRec{static_cast<uint32_t>(pool.size()), static_cast<uint32_t>(piece.size())};
-        pool.insert(pool.end(), piece.begin(), piece.end());
-      }
-    }
-  }
-  c->d_detok_rec = upload(rec, c->stream);
-  c->d_detok_pool = upload(pool, c->stream);
-  c->detok_pool_bytes = pool.size();
-  WP_HIP(hipStreamSynchronize(c->stream));  // rec and pool are locals
-}
-
-// The three passes over device buffers on c's stream.  g.n_cells < 0: a ragged call whose row_splits have not been
-// checked (the device entry point).  The result lies in c->detok_out until the handle's next call.
-void detok_on_device(wp_vocab *v, Context *c, const int32_t *d_ids, const long long *d_splits, const int32_t *d_lengths, DetokGeom g,
-                     int cleanup, const void **d_text, const long long **d_text_off, size_t *n_bytes) {
-  wp_detok_stats &ds = begin_detok_stats(v, static_cast<size_t>(g.n_rows));
-  hipStream_t st = c->stream;
-  const size_t n_rows = static_cast<size_t>(g.n_rows);
-  if (g.n_cells < 0) {
-    clear_scalars(c, kScalarDetokLast, kScalarDetokBad, st);
-    hipLaunchKernelGGL(detok_check_splits_kernel, dim3(std::min<unsigned>(cdiv(n_rows + 1, kBlock), 1024u)), dim3(kBlock), 0, st, d_splits,
-                       n_rows, c->d_scalars + kScalarDetokBad, reinterpret_cast<long long *>(c->d_scalars + kScalarDetokLast));
-    WP_LAUNCH_CHECK();
-    WP_HIP(hipMemcpyAsync(c->h_scalars + kScalarDetokLast, c->d_scalars + kScalarDetokLast,
-                          sizeof(uint32_t) * (scalar_end(kScalarDetokBad) - kScalarDetokLast), hipMemcpyDeviceToHost, st));
-    WP_HIP(hipStreamSynchronize(st));
-    if (c->h_scalars[kScalarDetokBad] != 0) throw std::invalid_argument("detokenize: row_splits must start at 0 and never descend");
-    long long last;
-    std::memcpy(&last, c->h_scalars + kScalarDetokLast, sizeof(last));
-    if (last > INT32_MAX) throw std::length_error("detokenize: more cells than INT32_MAX");
-    g.n_cells = last;
-  }
-  if (g.n_cells > 0 && !d_ids) throw std::invalid_argument("detokenize: ids is NULL");
-  ensure_detok_table(v, c);
-  g.pool_bytes = c->detok_pool_bytes;
-  const size_t n_tiles = static_cast<size_t>(g.n_cells) / kDetokTile + 1;
-  // tile records | tile offsets | tile carries
-  const size_t off_rec = 0, off_off = up256(n_tiles * sizeof(DetokTile)), off_carry = off_off + up256(n_tiles * sizeof(unsigned long long));
-  c->detok_aux.ensure(off_carry + up256(n_tiles * sizeof(uint32_t)));
-  char *aux = static_cast<char *>(c->detok_aux.p);
-  DetokTile *d_tiles = reinterpret_cast<DetokTile *>(aux + off_rec);
-  unsigned long long *d_tile_off = reinterpret_cast<unsigned long long *>(aux + off_off);
-  uint32_t *d_tile_carry = reinterpret_cast<uint32_t *>(aux + off_carry);
-  const DetokRec *d_rec = c->d_detok_rec + static_cast<size_t>(cleanup) * 2 * static_cast<size_t>(g.vocab_size);
-  unsigned long long *d_tot = reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarDetok);
-  const dim3 grid(static_cast<unsigned>(n_tiles)), block(kBlock);
-  hipLaunchKernelGGL((detok_tile_kernel<false>), grid, block, 0, st, d_ids, d_splits, d_lengths, g, d_rec, c->d_detok_pool, d_tiles,
-                     static_cast<const unsigned long long *>(nullptr), static_cast<const uint32_t *>(nullptr),
-                     static_cast<uint8_t *>(nullptr), static_cast<long long *>(nullptr));
-  hipLaunchKernelGGL(detok_spine_kernel, dim3(1), block, 0, st, d_tiles, n_tiles, d_tile_off, d_tile_carry, d_tot);
-  WP_LAUNCH_CHECK();
-  unsigned long long *h_tot = reinterpret_cast<unsigned long long *>(c->h_scalars + kScalarDetok);
-  WP_HIP(hipMemcpyAsync(h_tot, d_tot, kDetokCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  WP_HIP(hipStreamSynchronize(st));
-  const unsigned long long total = h_tot[kDetokBytes] + (g.term >= 0 ? static_cast<unsigned long long>(n_rows) : 0ull);
-  if (total >= (1ull << 32)) throw std::length_error("detokenize: the text has 2^32 bytes or more");
-  g.n_bytes = total;
-  // text_off | text (a whole number of words)
-  const size_t off_text = up256((n_rows + 1) * sizeof(long long));
-  c->detok_out.ensure(off_text + up256(static_cast<size_t>(total) + 4));
-  long long *d_off = static_cast<long long *>(c->detok_out.p);
-  uint8_t *d_txt = static_cast<uint8_t *>(c->detok_out.p) + off_text;
-  hipLaunchKernelGGL((detok_tile_kernel<true>), grid, block, 0, st, d_ids, d_splits, d_lengths, g, d_rec, c->d_detok_pool,
-                     static_cast<DetokTile *>(nullptr), d_tile_off, d_tile_carry, d_txt, d_off);
-  WP_LAUNCH_CHECK();
-  WP_HIP(hipStreamSynchronize(st));
-#ifdef WP_DEBUG_BOUNDS
-  {
-    unsigned int oob = 0;
-    take_oob(kSiteDetok, 1, &oob);
-    if (oob != 0) throw HipError("debug bounds: detokenize: " + std::to_string(oob) + " gathers or stores outside their buffers skipped");
-  }
-#endif
-  ds.n_kept = static_cast<int64_t>(h_tot[kDetokKept]);
-  ds.n_skipped = static_cast<int64_t>(h_tot[kDetokSkipped]);
-  ds.n_dropped = static_cast<int64_t>(h_tot[kDetokDropped]);
-  ds.n_cells = ds.n_kept + ds.n_skipped + ds.n_dropped;
-  ds.n_bytes = static_cast<int64_t>(total);
-  *d_text = total ? d_txt : nullptr;
-  *d_text_off = d_off;
-  *n_bytes = static_cast<size_t>(total);
-}
-}  // namespace
-
+// ---- detokenize (include/wordpiece_amd.h, section "detokenize"; host path: detok_path.h) -----------------------------
 extern "C" {
 
 int wp_get_detok_stats(const wp_vocab *v, wp_detok_stats *out) {
@@ -1424,40 +977,25 @@ int wp_detokenize(wp_vocab *v, const int32_t *ids, const int64_t *row_splits, co
     DetokGeom g = check_detok_spec(v, spec, n_rows);
     if (g.max_len == 0) {
       if (!row_splits) throw std::invalid_argument("detokenize: a ragged call needs row_splits");
-      if (row_splits[0] != 0) throw std::invalid_argument("detokenize: row_splits must start at 0");
-      for (size_t r = 0; r < n_rows; r++) {
-        if (row_splits[r + 1] < row_splits[r]) throw std::invalid_argument("detokenize: row_splits must never descend");
-      }
-      if (row_splits[n_rows] > INT32_MAX) throw std::length_error("detokenize: more cells than INT32_MAX");
-      g.n_cells = row_splits[n_rows];
+      g.n_cells = check_row_splits("detokenize", row_splits, n_rows);
+      if (g.n_cells > INT32_MAX) throw std::length_error("detokenize: more cells than INT32_MAX");
     }
     if (g.n_cells > 0 && !ids) throw std::invalid_argument("detokenize: ids is NULL");
     if (n_rows == 0) {
-      int64_t *off = static_cast<int64_t *>(std::calloc(1, sizeof(int64_t)));
-      if (!off) throw std::bad_alloc();
-      *text_off = off;
+      *text_off = static_cast<int64_t *>(zeroed(sizeof(int64_t)));
       begin_detok_stats(v, 0);
       return;
     }
     Context *c = get_context(v);
-    const size_t n_cells = static_cast<size_t>(g.n_cells);
     const bool ragged = g.max_len == 0;
-    // ids | row_splits or lengths
-    const size_t off_rows = up256(n_cells * sizeof(int32_t));
-    c->detok_in.ensure(off_rows + up256((n_rows + 1) * sizeof(int64_t)));
-    int32_t *d_ids = static_cast<int32_t *>(c->detok_in.p);
-    void *d_rows = static_cast<char *>(c->detok_in.p) + off_rows;
-    if (n_cells) WP_HIP(hipMemcpyAsync(d_ids, ids, n_cells * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    if (ragged) {
-      WP_HIP(hipMemcpyAsync(d_rows, row_splits, (n_rows + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    } else if (lengths) {
-      WP_HIP(hipMemcpyAsync(d_rows, lengths, n_rows * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    }
+    const void *rows = ragged ? static_cast<const void *>(row_splits) : static_cast<const void *>(lengths);
+    const StagedRows in = stage_ids_and_rows(c->detok_in, c->stream, ids, static_cast<size_t>(g.n_cells), rows,
+                                             ragged ? (n_rows + 1) * sizeof(int64_t) : n_rows * sizeof(int32_t), n_rows);
     const void *d_text = nullptr;
     const long long *d_off = nullptr;
     size_t nb = 0;
-    detok_on_device(v, c, d_ids, ragged ? static_cast<const long long *>(d_rows) : nullptr,
-                    !ragged && lengths ? static_cast<const int32_t *>(d_rows) : nullptr, g, spec->cleanup, &d_text, &d_off, &nb);
+    detok_on_device(v, c, in.d_ids, ragged ? in.d_rows : nullptr, !ragged && lengths ? reinterpret_cast<const int32_t *>(in.d_rows) : nullptr,
+                    g, spec->cleanup, &d_text, &d_off, &nb);
     Downloads down(c->stream);
     if (nb) down.add(text, d_text, nb);
     down.add(text_off, d_off, (n_rows + 1) * sizeof(int64_t));
@@ -1476,10 +1014,10 @@ int wp_detokenize_device(wp_vocab *v, const int32_t *d_ids, const int64_t *d_row
     *n_bytes = 0;
     DetokGeom g = check_detok_spec(v, spec, n_rows);
     if (g.max_len == 0 && !d_row_splits) throw std::invalid_argument("detokenize: a ragged call needs row_splits");
-    if ((reinterpret_cast<uintptr_t>(d_ids) & 3u) != 0 || (reinterpret_cast<uintptr_t>(d_lengths) & 3u) != 0 ||
-        (reinterpret_cast<uintptr_t>(d_row_splits) & 7u) != 0) {
-      throw std::invalid_argument("detokenize: device ids and lengths must be 4-byte aligned, row_splits 8-byte aligned");
-    }
+    const char *aligned = "detokenize: device ids and lengths must be 4-byte aligned, row_splits 8-byte aligned";
+    check_aligned(d_ids, 4, aligned);
+    check_aligned(d_lengths, 4, aligned);
+    check_aligned(d_row_splits, 8, aligned);
     const long long *d_off = nullptr;
     detok_on_device(v, get_context(v), d_ids, g.max_len == 0 ? reinterpret_cast<const long long *>(d_row_splits) : nullptr,
                     g.max_len == 0 ? nullptr : d_lengths, g, spec->cleanup, d_text, &d_off, n_bytes);
@@ -1489,142 +1027,7 @@ int wp_detokenize_device(wp_vocab *v, const int32_t *d_ids, const int64_t *d_row
 
 }  // extern "C"
 
-// ---- pack (include/wordpiece_amd.h, section "pack"; kernels: packing.h) ---------------------------------------------
-namespace {
-// every argument rule that needs neither the rows nor a device
-PackGeom check_pack_spec(const wp_pack_spec *spec, size_t n_docs) {
-  if (!spec) throw std::invalid_argument("pack: spec is NULL");
-  if (spec->mode != WP_PACK_NEXT_FIT && spec->mode != WP_PACK_STREAM) throw std::invalid_argument("pack: unknown mode");
-  if (spec->mode == WP_PACK_NEXT_FIT && spec->long_docs != WP_PACK_LONG_TRUNCATE && spec->long_docs != WP_PACK_LONG_SPLIT) {
-    throw std::invalid_argument("pack: unknown long_docs");
-  }
-  if ((spec->want & ~7) != 0) throw std::invalid_argument("pack: want has bits outside 7");
-  if (spec->max_len < 1) throw std::invalid_argument("pack: max_len must be at least 1");
-  const int specials = (spec->bos_id >= 0 ? 1 : 0) + (spec->eos_id >= 0 ? 1 : 0);
-  if (spec->max_len - specials < 1) throw std::invalid_argument("pack: max_len leaves no room for an id beside the specials");
-  if (n_docs > static_cast<size_t>(INT32_MAX)) throw std::length_error("pack: more documents than INT32_MAX");
-  PackGeom g{};
-  g.max_len = spec->max_len;
-  g.budget = spec->max_len - specials;
-  g.stream = spec->mode == WP_PACK_STREAM;
-  g.split = !g.stream && spec->long_docs == WP_PACK_LONG_SPLIT;
-  g.bos_id = spec->bos_id;
-  g.eos_id = spec->eos_id;
-  g.pad_id = spec->pad_id;
-  g.want = spec->want;
-  return g;
-}
-
-wp_pack_stats &begin_pack_stats(wp_vocab *v, size_t n_docs) {
-  v->stats.pack_call = 1;
-  v->stats.pack = wp_pack_stats{};
-  v->stats.pack.n_docs = static_cast<int64_t>(n_docs);
-  return v->stats.pack;
-}
-
-void check_pack_totals(unsigned long long n_ids, unsigned long long n_cells) {
-  if (n_ids > static_cast<unsigned long long>(INT32_MAX)) throw std::length_error("pack: more ids than INT32_MAX");
-  if (n_cells > static_cast<unsigned long long>(INT32_MAX)) throw std::length_error("pack: more cells in the units than INT32_MAX");
-}
-void check_pack_rows(unsigned long long n_out, int max_len) {
-  if (n_out * static_cast<unsigned long long>(max_len) > static_cast<unsigned long long>(INT32_MAX)) {
-    throw std::length_error("pack: n_out * max_len exceeds INT32_MAX");
-  }
-}
-
-// The passes over device buffers on c's stream; the row_splits are checked here in a kernel.  out_for(n_out): the
-// buffers of the batch once the number of rows is known (throws where there is no room); not called for n_out == 0.
-// Returns n_out.  Nothing is written through the caller's pointers before every check has passed.
-template <typename OutFor>
-size_t pack_on_device(wp_vocab *v, Context *c, const int32_t *d_ids, const long long *d_splits, size_t n_docs, PackGeom g, OutFor &&out_for) {
-  wp_pack_stats &ps = begin_pack_stats(v, n_docs);
-  if (n_docs == 0) return 0;
-  hipStream_t st = c->stream;
-  const dim3 block(kBlock);
-  // pieces | cells per document, scanned in place | the scans' tile sums
-  const size_t scan_tmp = up256((cdiv(n_docs, kScanTile) + 1) * sizeof(uint32_t));
-  const size_t off_cells = up256(n_docs * sizeof(uint32_t)), off_tmp = 2 * off_cells;
-  c->pack_plan.ensure(off_tmp + scan_tmp);
-  char *plan = static_cast<char *>(c->pack_plan.p);
-  uint32_t *d_piece_base = reinterpret_cast<uint32_t *>(plan), *d_cell_base = reinterpret_cast<uint32_t *>(plan + off_cells);
-  uint32_t *d_scan_tmp = reinterpret_cast<uint32_t *>(plan + off_tmp);
-  unsigned long long *d_tot = reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarPack);
-  const unsigned long long *h_tot = reinterpret_cast<const unsigned long long *>(c->h_scalars + kScalarPack);
-  clear_scalars(c, kScalarPackLast, kScalarPack, st);
-  hipLaunchKernelGGL(detok_check_splits_kernel, dim3(std::min<unsigned>(cdiv(n_docs + 1, kBlock), 1024u)), block, 0, st, d_splits, n_docs,
-                     c->d_scalars + kScalarPackBad, reinterpret_cast<long long *>(c->d_scalars + kScalarPackLast));
-  hipLaunchKernelGGL(seqpack_plan_kernel, dim3(std::min<unsigned>(cdiv(n_docs, kBlock), kPackMaxGrid)), block, 0, st, d_splits, n_docs, g,
-                     d_piece_base, d_cell_base, d_tot);
-  WP_LAUNCH_CHECK();
-  queue_scalar_slots(c, kScalarPackLast, kScalarPack, st);
-  WP_HIP(hipStreamSynchronize(st));
-  if (c->h_scalars[kScalarPackBad] != 0) throw std::invalid_argument("pack: row_splits must start at 0 and never descend");
-  long long last;
-  std::memcpy(&last, c->h_scalars + kScalarPackLast, sizeof(last));
-  check_pack_totals(static_cast<unsigned long long>(last), h_tot[kPackStream]);
-  if (last > 0 && !d_ids) throw std::invalid_argument("pack: ids is NULL");
-  ps.n_empty = static_cast<int64_t>(h_tot[kPackEmpty]);
-  ps.n_cut = static_cast<int64_t>(h_tot[kPackCut]);
-  ps.n_ids_cut = static_cast<int64_t>(h_tot[kPackIdsCut]);
-  ps.n_pieces = static_cast<int64_t>(h_tot[kPackPieces]);
-  g.n_ids = static_cast<uint32_t>(last);
-  g.n_cells = static_cast<uint32_t>(h_tot[kPackStream]);
-  g.n_pieces = static_cast<uint32_t>(h_tot[kPackPieces]);  // (every unit holds a cell: n_pieces <= n_cells)
-  if (g.n_pieces == 0) return 0;
-  const size_t n_p = g.n_pieces, n_tiles = cdiv(n_p, kPackPieceTile);
-  // P | src0 | nx | row_first | tile_entry | tile_row | records
-  const size_t per_piece = up256((n_p + 1) * sizeof(uint32_t)), per_tile = up256(n_tiles * sizeof(uint32_t));
-  const size_t off_entry = 4 * per_piece, off_rec = off_entry + 2 * per_tile;
-  c->pack_tab.ensure(off_rec + up256(n_p * sizeof(unsigned long long)));
-  char *tab = static_cast<char *>(c->pack_tab.p);
-  uint32_t *d_P = reinterpret_cast<uint32_t *>(tab), *d_nx = reinterpret_cast<uint32_t *>(tab + 2 * per_piece);
-  int32_t *d_src0 = reinterpret_cast<int32_t *>(tab + per_piece);
-  uint32_t *d_row_first = reinterpret_cast<uint32_t *>(tab + 3 * per_piece);
-  uint32_t *d_tile_entry = reinterpret_cast<uint32_t *>(tab + off_entry), *d_tile_row = reinterpret_cast<uint32_t *>(tab + off_entry + per_tile);
-  unsigned long long *d_rec = reinterpret_cast<unsigned long long *>(tab + off_rec);
-  device_exclusive_scan(d_piece_base, d_piece_base, n_docs, d_scan_tmp, nullptr, st);
-  device_exclusive_scan(d_cell_base, d_cell_base, n_docs, d_scan_tmp, nullptr, st);
-  hipLaunchKernelGGL(seqpack_pieces_kernel, dim3(cdiv(n_p, kBlock)), block, 0, st, d_splits, static_cast<uint32_t>(n_docs), d_piece_base,
-                     d_cell_base, g, d_P, d_src0);
-  WP_LAUNCH_CHECK();
-  unsigned long long n_out = (static_cast<unsigned long long>(g.n_cells) + g.max_len - 1) / static_cast<unsigned long long>(g.max_len);
-  if (!g.stream) {
-    WP_HIP(hipMemsetAsync(d_tile_entry, 0xFF, n_tiles * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(seqpack_tile_kernel, dim3(static_cast<unsigned>(n_tiles)), block, 0, st, d_P, g.n_pieces, static_cast<uint32_t>(g.max_len),
-                       d_nx, d_rec);
-    hipLaunchKernelGGL(seqpack_spine_kernel, dim3(1), dim3(kWave), 0, st, d_rec, g.n_pieces, d_tile_entry, d_tile_row, d_row_first, d_tot);
-    WP_LAUNCH_CHECK();
-    queue_scalar_slots(c, kScalarPack, kScalarPack, st);
-    WP_HIP(hipStreamSynchronize(st));
-    n_out = h_tot[kPackRows];
-  }
-  ps.n_out = static_cast<int64_t>(n_out);
-  check_pack_rows(n_out, g.max_len);
-  g.n_out = static_cast<uint32_t>(n_out);
-  const PackOut o = out_for(static_cast<size_t>(n_out));
-  if (!g.stream) {
-    hipLaunchKernelGGL(seqpack_apply_kernel, dim3(static_cast<unsigned>(n_tiles)), block, 0, st, d_nx, g.n_pieces, static_cast<uint32_t>(g.max_len),
-                       d_tile_entry, d_tile_row, d_row_first);
-  }
-  const size_t cell_tiles = cdiv(static_cast<size_t>(n_out) * static_cast<size_t>(g.max_len), kPackCellTile);
-  hipLaunchKernelGGL(seqpack_write_kernel, dim3(static_cast<unsigned>(std::min<size_t>(cell_tiles, kPackMaxGrid))), block, 0, st, d_ids, d_P,
-                     d_src0, d_row_first, g, o, d_tot);
-  WP_LAUNCH_CHECK();
-  queue_scalar_slots(c, kScalarPack, kScalarPack, st);
-  WP_HIP(hipStreamSynchronize(st));
-#ifdef WP_DEBUG_BOUNDS
-  {
-    unsigned int oob = 0;
-    take_oob(kSitePack, 1, &oob);
-    if (oob != 0) throw HipError("debug bounds: pack: " + std::to_string(oob) + " gathers or stores outside their buffers skipped");
-  }
-#endif
-  ps.n_cells = static_cast<int64_t>(h_tot[kPackCells]);
-  ps.n_segments = static_cast<int64_t>(h_tot[kPackSegments]);
-  return static_cast<size_t>(n_out);
-}
-}  // namespace
-
+// ---- pack (include/wordpiece_amd.h, section "pack"; host path: pack_path.h) ------------------------------------------
 extern "C" {
 
 int wp_get_pack_stats(const wp_vocab *v, wp_pack_stats *out) {
@@ -1641,11 +1044,10 @@ int wp_pack_sequences(wp_vocab *v, const int32_t *ids, const int64_t *row_splits
     *n_out = 0;
     const PackGeom g = check_pack_spec(spec, n_docs);
     if (!row_splits) throw std::invalid_argument("pack: row_splits is NULL");
-    if (row_splits[0] != 0) throw std::invalid_argument("pack: row_splits must start at 0");
+    const size_t n_ids = static_cast<size_t>(check_row_splits("pack", row_splits, n_docs));
     const unsigned long long s = static_cast<unsigned long long>(g.max_len - g.budget), B = static_cast<unsigned long long>(g.budget);
     unsigned long long n_cells = 0, n_pieces = 0, n_empty = 0;
     for (size_t r = 0; r < n_docs; r++) {
-      if (row_splits[r + 1] < row_splits[r]) throw std::invalid_argument("pack: row_splits must never descend");
       const unsigned long long l = static_cast<unsigned long long>(row_splits[r + 1] - row_splits[r]);
       if (l == 0) {
         n_empty++;
@@ -1656,7 +1058,6 @@ int wp_pack_sequences(wp_vocab *v, const int32_t *ids, const int64_t *row_splits
       n_cells += (g.stream || g.split ? l : std::min(l, B)) + np * s;  // (l < 2^63, np * s <= 2 l: no wrap before the check of n_ids)
       if (n_cells > (1ull << 62)) n_cells = 1ull << 62;
     }
-    const size_t n_ids = static_cast<size_t>(row_splits[n_docs]);
     check_pack_totals(n_ids, n_cells);
     if (g.stream) check_pack_rows((n_cells + g.max_len - 1) / static_cast<unsigned long long>(g.max_len), g.max_len);
     if (n_ids > 0 && !ids) throw std::invalid_argument("pack: ids is NULL");
@@ -1665,23 +1066,9 @@ int wp_pack_sequences(wp_vocab *v, const int32_t *ids, const int64_t *row_splits
       return;
     }
     Context *c = get_context(v);
-    // ids | row_splits
-    const size_t off_rows = up256(n_ids * sizeof(int32_t));
-    c->pack_in.ensure(off_rows + up256((n_docs + 1) * sizeof(int64_t)));
-    int32_t *d_ids = static_cast<int32_t *>(c->pack_in.p);
-    long long *d_rows = reinterpret_cast<long long *>(static_cast<char *>(c->pack_in.p) + off_rows);
-    WP_HIP(hipMemcpyAsync(d_ids, ids, n_ids * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    WP_HIP(hipMemcpyAsync(d_rows, row_splits, (n_docs + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    const StagedRows in = stage_ids_and_rows(c->pack_in, c->stream, ids, n_ids, row_splits, (n_docs + 1) * sizeof(int64_t), n_docs);
     PackOut o{};
-    const size_t rows = pack_on_device(v, c, d_ids, d_rows, n_docs, g, [&](size_t n) {
-      // input_ids | segment_ids | position_ids | source | lengths
-      const size_t block = up256(n * static_cast<size_t>(g.max_len) * sizeof(int32_t));
-      c->pack_out.ensure(4 * block + up256(n * sizeof(int32_t)));
-      char *p = static_cast<char *>(c->pack_out.p);
-      o = PackOut{reinterpret_cast<int32_t *>(p), reinterpret_cast<int32_t *>(p + block), reinterpret_cast<int32_t *>(p + 2 * block),
-                  reinterpret_cast<int32_t *>(p + 3 * block), reinterpret_cast<int32_t *>(p + 4 * block)};
-      return o;
-    });
+    const size_t rows = pack_on_device(v, c, in.d_ids, in.d_rows, n_docs, g, [&](size_t n) { return o = pack_batch(c, n, g.max_len); });
     if (rows == 0) return;
     const size_t cells = rows * static_cast<size_t>(g.max_len) * sizeof(int32_t);
     Downloads down(c->stream);
@@ -1711,11 +1098,12 @@ int wp_pack_sequences_device(wp_vocab *v, const int32_t *d_ids, const int64_t *d
     PackOut o{d_out->input_ids, (g.want & WP_PACK_WANT_SEGMENTS) ? d_out->segment_ids : nullptr,
               (g.want & WP_PACK_WANT_POSITIONS) ? d_out->position_ids : nullptr, (g.want & WP_PACK_WANT_SOURCE) ? d_out->source : nullptr,
               d_out->lengths};
-    for (const void *p : {static_cast<const void *>(d_ids), static_cast<const void *>(o.input_ids), static_cast<const void *>(o.segment_ids),
-                          static_cast<const void *>(o.position_ids), static_cast<const void *>(o.source), static_cast<const void *>(o.lengths)}) {
-      if ((reinterpret_cast<uintptr_t>(p) & 3u) != 0) throw std::invalid_argument("pack: device ids and outputs must be 4-byte aligned");
+    for (const int32_t *p : {d_ids, static_cast<const int32_t *>(o.input_ids), static_cast<const int32_t *>(o.segment_ids),
+                             static_cast<const int32_t *>(o.position_ids), static_cast<const int32_t *>(o.source),
+                             static_cast<const int32_t *>(o.lengths)}) {
+      check_aligned(p, 4, "pack: device ids and outputs must be 4-byte aligned");
     }
-    if ((reinterpret_cast<uintptr_t>(d_row_splits) & 7u) != 0) throw std::invalid_argument("pack: device row_splits must be 8-byte aligned");
+    check_aligned(d_row_splits, 8, "pack: device row_splits must be 8-byte aligned");
     if (n_docs == 0) {
       begin_pack_stats(v, 0);
       return;
@@ -1732,128 +1120,7 @@ int wp_pack_sequences_device(wp_vocab *v, const int32_t *d_ids, const int64_t *d
 
 }  // extern "C"
 
-// ---- model inputs (include/wordpiece_amd.h, section "model inputs"; kernels: inputs.h) -------------------------------
-namespace {
-// every argument rule that needs neither the text nor a device
-InputsGeom check_inputs_spec(const wp_inputs_spec *spec, size_t nbytes) {
-  if (!spec) throw std::invalid_argument("inputs: spec is NULL");
-  check_rows_call(spec->unit, nbytes);
-  if (spec->truncation != WP_TRUNC_LONGEST_FIRST && spec->truncation != WP_TRUNC_ONLY_FIRST && spec->truncation != WP_TRUNC_ONLY_SECOND) {
-    throw std::invalid_argument("inputs: unknown truncation strategy");
-  }
-  if (spec->stride < -1) throw std::invalid_argument("inputs: stride must be -1 (no windows) or at least 0");
-  if (spec->pairs != 0 && spec->pairs != 1) throw std::invalid_argument("inputs: pairs must be 0 or 1");
-  InputsGeom g;
-  g.max_len = spec->max_len;
-  g.head = spec->cls_id >= 0 ? 1 : 0;
-  g.nsep = spec->sep_id >= 0 ? 1 : 0;
-  const int specials = g.head + g.nsep * (spec->pairs ? 2 : 1);
-  if (spec->max_len < 1 || spec->max_len < specials) {
-    throw std::invalid_argument("max_len must be at least 1 and at least the number of specials");
-  }
-  g.budget = spec->max_len - specials;
-  g.pairs = spec->pairs;
-  g.truncation = spec->truncation;
-  g.stride = spec->stride;
-  g.cls_id = spec->cls_id;
-  g.sep_id = spec->sep_id;
-  g.pad_id = spec->pad_id;
-  if (spec->truncation == WP_TRUNC_LONGEST_FIRST) {
-    if (spec->stride >= 0) throw std::invalid_argument("inputs: windows (stride >= 0) need the truncation only_first or only_second");
-  } else {
-    if (spec->truncation == WP_TRUNC_ONLY_SECOND && !spec->pairs) throw std::invalid_argument("inputs: only_second needs pairs");
-    if (static_cast<long long>(g.budget) < static_cast<long long>(std::max(spec->stride, 0)) + 1) {
-      throw std::invalid_argument("inputs: max_len leaves no room for a window");
-    }
-  }
-  return g;
-}
-
-void check_inputs_rows(const InputsGeom &g, size_t n_rows) {
-  if (g.pairs && (n_rows & 1) != 0) throw std::invalid_argument("inputs: pairs need an even number of rows");
-}
-
-// n_out * max_len cells of 8 bytes must be addressable
-void check_inputs_size(size_t n_out, int max_len) {
-  if (n_out > static_cast<size_t>(UINT32_MAX) || n_out > SIZE_MAX / 8 / static_cast<size_t>(max_len)) {
-    throw std::length_error("inputs: too many output rows");
-  }
-}
-
-// The model inputs of a rows result.  place(n_out) names the buffers of the batch once the number of output rows is
-// known (and throws where they do not fit); returns n_out.  Waits for the batch.  Without windows the host waits once,
-// behind the packer (as pack_on_device does); with windows once more, for the row count.
-size_t inputs_on_device(wp_vocab *v, Context *c, const RowsResult &r, const InputsGeom &g, int unit,
-                        const std::function<wp_inputs(size_t)> &place) {
-  hipStream_t st = c->stream;
-  const size_t n_samples = r.n_rows / (g.pairs ? 2 : 1);
-  v->stats.rows_truncated = 0;
-  v->stats.inputs_call = 1;
-  wp_inputs_stats &is = v->stats.inputs;
-  is = wp_inputs_stats{};
-  is.n_samples = static_cast<int64_t>(n_samples);
-  is.pairs = g.pairs;
-  is.truncation = g.truncation;
-  is.stride = g.stride;
-  if (n_samples > static_cast<size_t>(INT32_MAX)) throw std::length_error("inputs: too many samples");
-  if (n_samples == 0) {
-    (void)place(0);
-    return 0;
-  }
-  const bool windows = g.stride >= 0;
-  // scratch: a record per sample | window counts (scanned in place) | the scan's tile sums
-  const size_t scan_words = cdiv(n_samples, kScanTile) + 8;
-  c->inputs_buf.ensure(n_samples * sizeof(InputsRec) + (n_samples + scan_words) * sizeof(uint32_t));
-  InputsRec *d_rec = static_cast<InputsRec *>(c->inputs_buf.p);
-  uint32_t *d_win = reinterpret_cast<uint32_t *>(d_rec + n_samples), *d_tmp = d_win + n_samples;
-  clear_scalars(c, kScalarInCut, kScalarInWindowed, st);
-  hipLaunchKernelGGL(inputs_plan_kernel, dim3(cdiv(n_samples, kBlock)), dim3(kBlock), 0, st, r.d_row_splits, n_samples, g, d_win, d_rec,
-                     c->d_scalars + kScalarInCut, c->d_scalars + kScalarInWindowed);
-  WP_LAUNCH_CHECK();
-  size_t n_out = n_samples;
-  if (windows) {
-    device_exclusive_scan(d_win, d_win, n_samples, d_tmp, nullptr, st, nullptr,
-                          reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarInRows));
-    fetch_scalars(c, kScalarInWindowed);
-    unsigned long long total;
-    std::memcpy(&total, c->h_scalars + kScalarInRows, sizeof(total));
-    if (total > static_cast<unsigned long long>(UINT32_MAX)) throw std::length_error("inputs: too many output rows");
-    n_out = static_cast<size_t>(total);
-  }
-  check_inputs_size(n_out, g.max_len);
-  is.n_out = static_cast<int64_t>(n_out);
-  const wp_inputs o = place(n_out);
-  const int lanes = lanes_for(g.max_len);
-  hipLaunchKernelGGL(inputs_pack_kernel, dim3(cdiv(n_out, static_cast<size_t>(kBlock / lanes))), dim3(kBlock), 0, st, r.d_ids,
-                     reinterpret_cast<const uint2 *>(r.d_offs), r.n_ids, r.d_row_splits, static_cast<const InputsRec *>(d_rec),
-                     windows ? static_cast<const uint32_t *>(d_win) : nullptr, n_samples, n_out, g, lanes, o.input_ids, o.token_type_ids,
-                     unit >= 0 ? reinterpret_cast<uint2 *>(o.offsets) : nullptr, o.lengths, o.sample);
-  WP_LAUNCH_CHECK();
-  if (windows) {
-    WP_HIP(hipStreamSynchronize(st));
-  } else {
-    fetch_scalars(c, kScalarInWindowed);
-  }
-#ifdef WP_DEBUG_BOUNDS
-  {
-    unsigned int oob = 0;
-    take_oob(kSiteInputs, 1, &oob);
-    if (oob != 0) throw HipError("debug bounds: model inputs: " + std::to_string(oob) + " gathers outside the id list skipped");
-  }
-#endif
-  is.n_cut = c->h_scalars[kScalarInCut];
-  is.n_windowed = c->h_scalars[kScalarInWindowed];
-  return n_out;
-}
-
-size_t count_lines_host(const char *utf8, size_t nbytes) {
-  if (nbytes == 0) return 0;
-  size_t n = utf8[nbytes - 1] != '\n' ? 1 : 0;
-  for (const char *p = utf8, *end = utf8 + nbytes; (p = static_cast<const char *>(std::memchr(p, '\n', end - p))) != nullptr; p++) n++;
-  return n;
-}
-}  // namespace
-
+// ---- model inputs (include/wordpiece_amd.h, section "model inputs"; host path: inputs_path.h) -------------------------
 extern "C" {
 
 int wp_linear_encode_inputs(wp_vocab *v, const char *utf8, size_t nbytes, const int64_t *doc_off, size_t n_docs,
@@ -1888,20 +1155,9 @@ int wp_linear_encode_inputs(wp_vocab *v, const char *utf8, size_t nbytes, const 
     RowsResult r;
     Context *c = rows_from_host(v, utf8, nbytes, doc_off, n_docs, unit, r);
     check_inputs_rows(g, r.n_rows);
-    size_t cells = 0;
     wp_inputs o{};  // the batch in c->pad_buf
-    const size_t n = inputs_on_device(v, c, r, g, unit, [&](size_t rows_out) {
-      cells = rows_out * max_len;  // offsets | input_ids | token_type_ids | lengths | sample
-      const size_t offs_bytes = unit >= 0 ? cells * 2 * sizeof(uint32_t) : 0;
-      c->pad_buf.ensure(offs_bytes + (2 * cells + 2 * rows_out) * sizeof(int32_t) + 16);
-      char *base = static_cast<char *>(c->pad_buf.p);
-      o.offsets = unit >= 0 ? reinterpret_cast<uint32_t *>(base) : nullptr;
-      o.input_ids = reinterpret_cast<int32_t *>(base + offs_bytes);
-      o.token_type_ids = o.input_ids + cells;
-      o.lengths = o.token_type_ids + cells;
-      o.sample = o.lengths + rows_out;
-      return o;
-    });
+    const size_t n = inputs_on_device(v, c, r, g, unit, [&](size_t rows_out) { return o = inputs_batch(c, unit, rows_out, g.max_len); });
+    const size_t cells = n * max_len;
     *n_samples = r.n_rows / (g.pairs ? 2 : 1);
     *n_out = n;
     if (n == 0) return;
@@ -1935,7 +1191,7 @@ int wp_linear_encode_inputs_device(wp_vocab *v, const void *d_utf8, size_t nbyte
     if (!d_out || !d_out->input_ids || !d_out->token_type_ids || !d_out->lengths || !d_out->sample || (unit >= 0 && !d_out->offsets)) {
       throw std::invalid_argument("null output buffer");
     }
-    if ((reinterpret_cast<uintptr_t>(d_out->offsets) & 7u) != 0) throw std::invalid_argument("the offsets buffer must be 8-byte aligned");
+    check_aligned(d_out->offsets, 8, "the offsets buffer must be 8-byte aligned");
     const size_t mult = g.pairs ? 2 : 1;
     // without windows the rows say how many output rows there are: too little room is found before the encode
     const size_t rows_cap = (g.stride >= 0 || capacity_rows > (SIZE_MAX - 1) / 2) ? SIZE_MAX : capacity_rows * mult + (mult - 1);

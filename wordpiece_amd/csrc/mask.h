@@ -11,7 +11,7 @@
 // A cell is one 4-byte coalesced load, one byte of the per-id class table (an L2-resident gather) and up to three
 // 4-byte coalesced stores; the random draws are integer arithmetic in registers.
 #pragma once
-#include "common.h"
+#include "primitives.h"  // bits_up_to, top_bit
 
 namespace wp {
 
@@ -48,10 +48,6 @@ __host__ __device__ inline unsigned long long mask_draw(unsigned long long row_k
 // 8, 12 or 16 B per cell (profiles/mask_probe.jsonl, line 1): not the bytes — the reading that
 // fits is those atomics, serialised.  A capped grid bounds them by the machine, not by the batch.
 constexpr unsigned kMaskMaxGrid = 2048;
-
-// bits [0, k] of a 64-bit word
-__device__ __forceinline__ unsigned long long bits_up_to(int k) { return k >= 63 ? ~0ull : (1ull << (k + 1)) - 1ull; }
-__device__ __forceinline__ int top_bit(unsigned long long x) { return 63 - __clzll(static_cast<long long>(x)); }
 
 // MASK: `out` and `labels` are written; WORD_IDS: `word_ids` is.  `in` and `out` may be the same buffer: a lane reads
 // its own cell only, before it stores there.  tok_class[x] = wp_vocab_token_flags(x) for 0 <= x < g.vocab_size.

@@ -37,7 +37,6 @@
 // Per cell: 4 B of ids gathered, 4 B per wanted output written; per piece 20 B of tables (P, src0, nx, the record).
 #pragma once
 #include "common.h"
-#include "detok.h"  // wave_reduce_sum64
 #include "primitives.h"
 
 namespace wp {

@@ -45,6 +45,24 @@ __device__ __forceinline__ uint32_t wave_reduce_sum(uint32_t v) {
   for (int d = kWave / 2; d > 0; d >>= 1) v += __shfl_xor(v, d, kWave);
   return v;
 }
+__device__ __forceinline__ unsigned long long wave_incl_sum64(unsigned long long v) {
+  const int lane = lane_id();
+#pragma unroll
+  for (int d = 1; d < kWave; d <<= 1) {
+    unsigned long long t = __shfl_up(v, d, kWave);
+    if (lane >= d) v += t;
+  }
+  return v;
+}
+__device__ __forceinline__ unsigned long long wave_reduce_sum64(unsigned long long v) {
+#pragma unroll
+  for (int d = kWave / 2; d > 0; d >>= 1) v += __shfl_xor(v, d, kWave);
+  return v;
+}
+
+// bits [0, k] of a 64-bit word (a ballot), and the highest bit set in one (x != 0)
+__device__ __forceinline__ unsigned long long bits_up_to(int k) { return k >= 63 ? ~0ull : (1ull << (k + 1)) - 1ull; }
+__device__ __forceinline__ int top_bit(unsigned long long x) { return 63 - __clzll(static_cast<long long>(x)); }
 
 // Workgroup barrier that only orders LDS traffic.  __syncthreads() also waits for the wave's
 // outstanding global stores (vmcnt(0)), which costs a memory round trip per loop iteration in the
@@ -85,6 +103,26 @@ __device__ __forceinline__ int32_t block_incl_max(int32_t v, int32_t *smem) {
     if (i < w) r = max(r, smem[i]);
   }
   return r;
+}
+// The running maximum of the threads in front of this one (-1 in front of thread 0; all values >= -1); total: the
+// block's maximum.  smem: >= 4 int32.
+__device__ __forceinline__ int32_t block_excl_max(int32_t v, int32_t *smem, int32_t &total) {
+  const int lane = lane_id(), w = wave_id();
+  const int32_t inc = wave_incl_max(v);
+  __syncthreads();  // protect smem reuse across calls
+  if (lane == kWave - 1) smem[w] = inc;
+  __syncthreads();
+  int32_t ex = __shfl_up(inc, 1, kWave);
+  if (lane == 0) ex = -1;
+  int32_t tot = -1;
+#pragma unroll
+  for (int i = 0; i < kBlock / kWave; i++) {
+    const int32_t s = smem[i];
+    if (i < w) ex = max(ex, s);
+    tot = max(tot, s);
+  }
+  total = tot;
+  return ex;
 }
 __device__ __forceinline__ int32_t block_reduce_min(int32_t v, int32_t *smem) {
   v = wave_reduce_min(v);

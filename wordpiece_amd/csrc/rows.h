@@ -192,6 +192,23 @@ __global__ __launch_bounds__(kBlock) void rebase_kernel(uint2 *__restrict__ offs
   }
 }
 
+// Ragged rows given in device memory (detokenize, pack): splits[0] == 0, no descent.  bad: violations; last: splits[n_rows].
+__global__ __launch_bounds__(kBlock) void check_splits_kernel(const long long *__restrict__ splits, size_t n_rows,
+                                                              uint32_t *__restrict__ bad, long long *__restrict__ last) {
+  for (size_t r = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x; r <= n_rows; r += static_cast<size_t>(gridDim.x) * kBlock) {
+    const long long s = splits[r];
+    if (s < 0 || (r == 0 && s != 0) || (r < n_rows && splits[r + 1] < s)) atomicAdd(bad, 1u);
+    if (r == n_rows) *last = s;
+  }
+}
+
+// lanes of a wave that share a row of max_len cells (pack_rows_kernel, inputs_pack_kernel, mask_kernel)
+static int lanes_for(int max_len) {
+  int lanes = 4;
+  while (lanes < kWave && lanes < max_len) lanes *= 2;
+  return lanes;
+}
+
 // Padded batch: row r of input_ids[n_rows, max_len] = [cls] + T[:keep] + [sep] + pad..., T = ids[row_splits[r] :
 // row_splits[r + 1]], keep = min(len(T), max_len - specials); lengths[r] = keep + specials.  cls_id / sep_id < 0: none.
 // `lanes` (a power of two, 4..64, >= max_len where that is <= 64) lanes share a row, so a wave holds 64 / lanes short

@@ -10,7 +10,8 @@ symbols) and M (alphabet marking), on fresh handles:
     positions, fetch 7 the class bits (space, spacing, punctuation from the oracle's predicates, soft from the vocabulary);
   - encode_with_offsets in both units equals offsets_model (the byte unit is what checks cp_byte_kernel's lead positions);
   - fast_encode equals the oracle's fast ids where the fast entry point applies;
-  - normalize(flags=0) equals the UTF-8 of the model's code points, and WP_NORM_BERT_UNCASED equals normalize_model (B, E);
+  - normalize(flags=0) equals the UTF-8 of the model's code points, and WP_NORM_BERT_UNCASED equals normalize_model (B, E, and
+    M_ascii_flags: all 128 ASCII values x 9);
   - the same text again on the same handle behind a text of another group: same ids, same n_text.
 
 Group P runs the _device entry points (Linear, offsets, fast, normalise, the lines mode of the rows call) directly on a
@@ -78,7 +79,7 @@ def reference(name, light=False):
     ref["sym"] = np.array(m.symbols(), dtype=np.int32)
     ref["cls"] = class_bits(m.cps, D.soft_set(vocab))
     ref["norm0"] = "".join(map(chr, m.cps)).encode("utf8")
-    ref["norm7"] = NM.normalize(text, W.WP_NORM_BERT_UNCASED)[0] if name[0] in "BE" else None
+    ref["norm7"] = NM.normalize(text, W.WP_NORM_BERT_UNCASED)[0] if name[0] in "BE" or name == "M_ascii_flags" else None
     return ref
 
 

@@ -71,4 +71,33 @@ WP_HD uint32_t byte_mask4(uint32_t m) {
   return (x | (x >> 7) | (x >> 14) | (x >> 21)) & 0xfu;
 }
 
+// ---- the word-wide ASCII tests of the normalise pre-pass (normalize.h), on a lane's chunk: w[0..3], w[4] the word behind it.
+// Checked on the host against the per-byte rules by tests/test_norm_swar.py.
+//
+// Which bytes of the lane's chunk WP_NORM_CLEAN drops if they are ASCII (bit j: byte j): the controls but U+0009, U+000A,
+// U+000D, and U+007F.  Bytes with the high bit set give bits without meaning: the caller looks at ASCII leads only.
+WP_HD uint32_t norm_ascii_dropped16(const uint32_t (&w)[5]) {
+  uint32_t bad16 = 0;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const uint32_t x = w[k] & 0x7f7f7f7fu;
+    auto is = [&](uint32_t c) { return ~((x ^ (c * 0x01010101u)) + 0x7f7f7f7fu) & kHi; };  // (bytes <= 0x7f: no carries)
+    const uint32_t lt20 = ~(x + 0x60606060u) & kHi;
+    bad16 |= byte_mask4((lt20 & ~(is(0x09u) | is(0x0au) | is(0x0du))) | is(0x7fu)) << (4 * k);
+  }
+  return bad16;
+}
+// the bytes of the lane's chunk below 0x80 (bit j: byte j)
+WP_HD uint32_t norm_ascii16(const uint32_t (&w)[5]) {
+  uint32_t hb = 0;
+#pragma unroll
+  for (int k = 0; k < 4; k++) hb |= byte_mask4(w[k] & kHi) << (4 * k);
+  return ~hb & 0xffffu;
+}
+// A..Z of an ASCII word -> a..z
+WP_HD uint32_t norm_ascii_lower(uint32_t x) {
+  const uint32_t up = (x + 0x3f3f3f3fu) & ~(x + 0x25252525u) & kHi;
+  return x | (up >> 2);
+}
+
 }  // namespace wp

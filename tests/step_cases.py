@@ -1,5 +1,5 @@
 """Constructed inputs for the stage between the sort and the walk — the scanlines of csrc/scanline.h, virtual_marks_kernel
-of csrc/prune.h and linear_path.h::scanlines / key_steps, which turn "which token is the longest match at this suffix" into
+of csrc/prune.h and linear_path.h::scanlines / side_tables / fill_tables, which turn "which token is the longest match at this suffix" into
 the step tables the walk reads — a plain model of what the stage has to find (refine_cases.longest_matches, unchanged), and
 what every case claims.  Shared by test_step_cases.py (CPU) and test_gpu_step_edges.py.  Importing this module loads no
 library.

@@ -1,5 +1,6 @@
 """GPU tests (-m gpu) of the early refinement of the keys-only round 0 (linear_path.h::refine_early; csrc/prune.h,
-need_groups_early_kernel / need_ranges_kernel; csrc/trie.h, trie_token_range_list_kernel; csrc/suffix_array.h,
+need_groups_early_kernel / need_ranges_kernel; csrc/trie.h, trie_token_range_in_list as linear_path.h::token_marks_kernel
+calls it; csrc/suffix_array.h,
 scatter_list_ranks_kernel): the needed groups are built from the runs of the sorted candidate list and refined in list
 space beside the radix passes; only the searches in the sorted keys and the rank scatter wait for the sort.
 
@@ -25,7 +26,8 @@ Proof that the file can fail — two scratch builds, never committed, run on an 
   - gfirst - ghead left out of the ranks alone (scatter_list_ranks_kernel, list_rank_base_kernel): 21 fail.  The two that
     pass have to: R_all_once puts nothing on the list, so no rank is stored, and test_early_refine_bounds_build loads
     libwordpiece_amd_dbg.so by its path, not the scratch build.
-  - the base left out of the ranks AND of trie_token_range_list_kernel: 19 fail.  Besides those two, R_inword_family and
+  - the base left out of the ranks AND of trie_token_range_list_kernel (the kernel that called trie_token_range_in_list
+    then; token_marks_kernel does now): 19 fail.  Besides those two, R_inword_family and
     the 2^22-entry list pass: ranks and token ranges are then both in list space and agree with each other, and the ids
     are right wherever the list positions of a group collide with no other step of the slot-space table.  The first
     build is the sharper one."""

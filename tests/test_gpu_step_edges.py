@@ -1,5 +1,5 @@
 """GPU tests (-m gpu) of the stage between the sort and the walk — csrc/scanline.h, virtual_marks_kernel of csrc/prune.h,
-linear_path.h::scanlines / key_steps — on the inputs of step_cases.py.  For every named case of families S (slot space: tiles,
+linear_path.h::scanlines / side_tables / fill_tables — on the inputs of step_cases.py.  For every named case of families S (slot space: tiles,
 groups of tiles, ballots, two marks, duplicates) and K (key space: the 64-ary search, the carry of the cover scan, the walk
 away from a slot, empty ranges, nested prefixes, the ends of slot space, the index shifts, a needed group, wide symbols):
 

@@ -4,9 +4,8 @@ In-tree on purpose: the built .so travels to the GPU box with the repo snapshot.
 
 WP_HIPCC_FLAGS adds compiler flags to the main library's line, for tuning and A/B builds (a build under another name is
 loaded through WP_LIB).  -DWP_LATE_REFINE_DEFAULT=1 (csrc/context.h) makes every handle start with WP_OPT_LATE_REFINE set:
-the way to time the refinement behind the sort with a program that sets no options, such as bench.py.
--DWP_SERIAL_TAIL=1 (csrc/context.h) keeps the stretch between the round-0 sort and the walk on the main stream in its old
-launch order, for the same kind of A/B run.  No other macro changes a default."""
+the way to time the refinement behind the sort with a program that sets no options, such as bench.py.  No other macro
+changes a default."""
 import os
 import subprocess
 import sys

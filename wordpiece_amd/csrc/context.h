@@ -429,11 +429,6 @@ struct EncodeStats : wp_stats {
 #ifndef WP_LATE_REFINE_DEFAULT
 #define WP_LATE_REFINE_DEFAULT 0
 #endif
-// -DWP_SERIAL_TAIL=1: a build that keeps the stretch between the round-0 sort and the walk on the main stream as it was
-// (the anchor scalars fetched behind the scanline stage, the cover scan and every table of the stage in a row), for A/B runs
-#ifndef WP_SERIAL_TAIL
-#define WP_SERIAL_TAIL 0
-#endif
 
 struct wp_vocab {
   HostVocab hv;

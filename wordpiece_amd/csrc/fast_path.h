@@ -3,6 +3,7 @@
 #pragma once
 #include "context.h"
 #include "fast.h"
+#include "long_word_path.h"
 #include "normalize.h"
 #include "walk.h"
 
@@ -118,38 +119,14 @@ static void encode_fast_on_device(const wp_vocab *v, Context *c, const uint8_t *
     hipLaunchKernelGGL(fast_long_word_collect_kernel, dim3(std::min<size_t>(cdiv(std::max<size_t>(n_anchors, 1), kBlock), 2048)),
                        dim3(kBlock), 0, st, d_anchors, c->d_scalars + kScalarAnchors, n_text, d_cls, d_lw, lw_cap, c->d_scalars + kScalarLongWords);
     WP_LAUNCH_CHECK();
-    fetch_scalars(c, kScalarLongWords);
-    const uint32_t nw = std::min(c->h_scalars[kScalarLongWords], lw_cap);
-    if (nw > 0) {
-      S.walk.n_long_words = static_cast<int64_t>(nw);
-      std::vector<LongWord> h_lw(nw);
-      WP_HIP(hipMemcpyAsync(h_lw.data(), d_lw, sizeof(LongWord) * nw, hipMemcpyDeviceToHost, st));
-      WP_HIP(hipStreamSynchronize(st));
-      std::vector<uint32_t> h_off(nw + 1);
-      uint64_t total64 = 0;
-      uint32_t longest = 0;
-      for (uint32_t i = 0; i < nw; i++) {
-        h_off[i] = static_cast<uint32_t>(total64);
-        total64 += h_lw[i].end - h_lw[i].begin;
-        longest = std::max(longest, h_lw[i].end - h_lw[i].begin);
-      }
-      h_off[nw] = static_cast<uint32_t>(total64);
-      const uint32_t total = static_cast<uint32_t>(total64);  // <= n_text
-      WP_HIP(hipMemcpyAsync(d_lw_off, h_off.data(), sizeof(uint32_t) * (nw + 1), hipMemcpyHostToDevice, st));
-      WP_HIP(hipMemsetAsync(d_lw_fail, 0, sizeof(uint32_t) * nw, st));
-      const dim3 grid(cdiv(total, kBlock));
-      hipLaunchKernelGGL(fast_long_word_next_kernel, grid, dim3(kBlock), 0, st, fa, d_lw, d_lw_off, nw, total, d_lid, jump_a,
+    const LongWordList lw = long_word_offsets(c, d_lw, lw_cap, d_lw_off, d_lw_fail, st);
+    if (lw.nw > 0) {
+      S.walk.n_long_words = static_cast<int64_t>(lw.nw);
+      hipLaunchKernelGGL(fast_long_word_next_kernel, lw.grid(), dim3(kBlock), 0, st, fa, d_lw, d_lw_off, lw.nw, lw.total, d_lid, jump_a,
                          d_mark);
-      WP_HIP(hipStreamSynchronize(st));  // h_off is a stack-owned upload source
-      uint32_t *ja = jump_a, *jb = jump_b;
-      for (uint32_t reach = 1; reach < longest; reach *= 2) {
-        hipLaunchKernelGGL(long_word_mark_kernel, grid, dim3(kBlock), 0, st, ja, total, d_mark);
-        hipLaunchKernelGGL(long_word_double_kernel, grid, dim3(kBlock), 0, st, ja, total, jb);
-        std::swap(ja, jb);
-      }
-      hipLaunchKernelGGL(long_word_mark_kernel, grid, dim3(kBlock), 0, st, ja, total, d_mark);
-      hipLaunchKernelGGL(long_word_fail_kernel, grid, dim3(kBlock), 0, st, d_lid, d_mark, d_lw_off, nw, total, d_lw_fail);
-      hipLaunchKernelGGL(fast_long_word_emit_kernel, grid, dim3(kBlock), 0, st, fa, d_lw, d_lw_off, nw, total, d_lid, d_mark,
+      WP_HIP(hipStreamSynchronize(st));  // lw.h_off is an upload source
+      long_word_chains(lw, jump_a, jump_b, d_lid, d_mark, d_lw_off, d_lw_fail, st);
+      hipLaunchKernelGGL(fast_long_word_emit_kernel, lw.grid(), dim3(kBlock), 0, st, fa, d_lw, d_lw_off, lw.nw, lw.total, d_lid, d_mark,
                          d_lw_fail);
       WP_LAUNCH_CHECK();
       S.anchor_mode = 2;

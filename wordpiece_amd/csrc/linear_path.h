@@ -9,10 +9,9 @@
 //   who marks + 4 scanlines       linear.cpp:153-213                                         scanline.h    scanlines
 //   greedy walk + id stream       linear.cpp:215-316                                         walk.h        walk
 #pragma once
-#include <functional>
-
 #include "context.h"
 #include "local_sort.h"
+#include "long_word_path.h"
 #include "prune.h"
 #include "trie.h"
 #include "offsets.h"
@@ -28,20 +27,13 @@ struct ListOverflow {
   size_t wanted;
 };
 
-// needed list longer than the room it was given: empty it (every later kernel reads its sizes on the device) and report
-__global__ void needed_list_clamp_kernel(uint32_t *__restrict__ totals, uint32_t cap, uint32_t *__restrict__ wanted) {
-  if (totals[0] > cap) {
-    *wanted = totals[0];
-    totals[0] = 0;
-    totals[1] = 0;
-  }
-}
-
+// The one kernel of this file, which is host code otherwise: it fuses kernels of scanline.h, trie.h and prune.h, and only
+// here are all three in view.
 // The per-token and per-group kernels between the late searches and the sort of the step starts in one launch (early
-// refinement, key lookup): thread i does what group_starts_kernel does for group i, and what
-// trie_token_range_list_kernel, virtual_marks_kernel and piece_starts_kernel do for token i, one after the other in
-// registers — four launches of one thread per token each were four links of a chain that is bound by launch latency.
-// No thread reads what another writes: a group's starts come from gfirst / ghead, a token's from its own range.
+// refinement, key lookup): thread i does what group_starts_kernel does for group i, and what trie_token_range_kernel
+// (in list space: trie_token_range_in_list), virtual_marks_kernel and piece_starts_kernel do for token i, one after the
+// other in registers — four launches of one thread per token each were four links of a chain that is bound by launch
+// latency.  No thread reads what another writes: a group's starts come from gfirst / ghead, a token's from its own range.
 __global__ __launch_bounds__(kBlock) void token_marks_kernel(const uint32_t *__restrict__ node_of_entry, const uint32_t *__restrict__ tok_node,
                                                              const uint32_t *__restrict__ tok_subtree, int M, uint32_t *__restrict__ rng_lo,
                                                              uint32_t *__restrict__ rng_hi, const uint8_t *__restrict__ rng_long,
@@ -64,7 +56,7 @@ __global__ __launch_bounds__(kBlock) void token_marks_kernel(const uint32_t *__r
   if (m >= M) return;
   uint32_t lo = rng_lo[m], hi = rng_hi[m];
   const uint32_t g = rng_long[m] ? tok_group[m] : kClaimNoGroup;
-  if (g != kClaimNoGroup) {  // a long token with a group on the list: trie_token_range_list_kernel
+  if (g != kClaimNoGroup) {  // a long token with a group on the list: trie_token_range_kernel, in list space
     trie_token_range_in_list(node_of_entry, tok_node[m], tok_subtree[m], ghead[g], lo, hi);
     rng_lo[m] = lo;
     rng_hi[m] = hi;
@@ -87,87 +79,44 @@ __global__ __launch_bounds__(kBlock) void token_marks_kernel(const uint32_t *__r
 // keys saves (config 2, 14.9 % blanks: 0.15 ms per step gained; config 5, 0.2 %: 1.5 % slower with the drop on).
 constexpr double kBlankDropMinShare = 1.0 / 16;
 
-#ifdef WP_DEBUG_BOUNDS
-// The sorted array of round 0 in the default layout (no debug view shows it, and the walk finds its steps by key value,
-// so the ids can be right over a wrong array), counted under kSiteSortOrder:
-//   descents sorted[i] > sorted[i + 1];
-//   keys the blank table marks (blanks dropped: none may be left);
-//   the sorted array against the keys the sort had to keep of the unsorted array (which survives the sort), as multisets:
-//   count, wrapping sum and xor of each side.  Kept: every key where no blanks were dropped, else the positions whose
-//   class byte (written by the decode, not derived from the code) is no blank, and the terminal one.
-__device__ unsigned int g_wp_sorted_sig[6];  // count, sum, xor: the sorted array | the kept keys of the unsorted one
-__global__ __launch_bounds__(kBlock) void sorted_check_kernel(const uint32_t *__restrict__ sorted, size_t n_sorted,
-                                                              const uint32_t *__restrict__ unsorted, size_t n,
-                                                              const uint8_t *__restrict__ cls, size_t n_text,
-                                                              const uint32_t *__restrict__ blank_bits) {
-  __shared__ uint32_t acc[7];
-  if (threadIdx.x < 7) acc[threadIdx.x] = 0u;
-  __syncthreads();
-  uint32_t bad = 0, cnt[2] = {0, 0}, sum[2] = {0, 0}, x[2] = {0, 0};
-  const size_t first = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x, stride = static_cast<size_t>(gridDim.x) * kBlock;
-  for (size_t i = first; i < n_sorted; i += stride) {
-    const uint32_t k = sorted[i];
-    if (i + 1 < n_sorted && k > sorted[i + 1]) bad++;
-    if (blank_bits && key_is_blank(blank_bits, k)) bad++;
-    cnt[0]++;
-    sum[0] += k;
-    x[0] ^= k;
-  }
-  for (size_t i = first; i < n; i += stride) {
-    if (blank_bits && i < n_text && (cls[i] & kClsSpace)) continue;
-    const uint32_t k = unsorted[i];
-    cnt[1]++;
-    sum[1] += k;
-    x[1] ^= k;
-  }
-  if (bad) atomicAdd(&acc[6], bad);
-  for (int s = 0; s < 2; s++) {
-    if (cnt[s]) {
-      atomicAdd(&acc[3 * s], cnt[s]);
-      atomicAdd(&acc[3 * s + 1], sum[s]);
-      atomicXor(&acc[3 * s + 2], x[s]);
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < 6 && acc[threadIdx.x]) {
-    if (threadIdx.x % 3 == 2) {
-      atomicXor(&g_wp_sorted_sig[threadIdx.x], acc[threadIdx.x]);
-    } else {
-      atomicAdd(&g_wp_sorted_sig[threadIdx.x], acc[threadIdx.x]);
-    }
-  }
-  if (threadIdx.x == 6 && acc[6]) atomicAdd(&g_wp_oob[kSiteSortOrder], acc[6]);
-}
-__global__ void sorted_check_close_kernel() {
-  bool same = true;
-  for (int j = 0; j < 3; j++) same = same && g_wp_sorted_sig[j] == g_wp_sorted_sig[3 + j];
-  wp_in_bounds(same, kSiteSortOrder);
-  for (int j = 0; j < 6; j++) g_wp_sorted_sig[j] = 0u;
-}
-#endif
-
-template <typename SymT>
-struct LinearPath {
-  // ---- what the decode phase hands over
-  const wp_vocab *v;
-  Context *c;
-  EncodeStats &S;
-  Arena &ar, &aa;
+// What the decode phase of encode_on_device hands to LinearPath.
+struct DecodedText {
   const uint8_t *d_text;
   size_t nbytes;
   const uint32_t *d_tile_prefix;
-  size_t n_text, n;
+  size_t n_text, n;  // code points of the text | symbols of S (the separator and, in the reference layout, the vocabulary behind them)
   uint32_t *d_cps;
   uint8_t *d_cls;
   int bits;
   bool text_only;
+};
+
+// One bucket index of a step table (scanline.h: StepTable bidx / bfast / shift).  A table has up to four, in this order:
+// slot space and key space (key lookup), and for each an "_all" twin with fewer buckets where that makes another shift.
+enum { kIxSlot = 0, kIxKey = 1, kIxSlotAll = 2, kIxKeyAll = 3, kStepIndexes = 4 };
+struct BucketIndex {
+  uint32_t *idx = nullptr;
+  int2 *fast = nullptr;
+  int shift = 0;         // (set for an absent index too: wp_step_stats reports all four)
+  unsigned used = 0;     // buckets in use: slot space holds n_sorted <= n slots (scanlines())
+  unsigned planned = 0;  // buckets the arena was planned for, from n; 0: absent (no key lookup, or a twin with the same shift)
+  bool keyed = false;    // key space: a step inside a needed group answers kStepNeeded
+  const uint32_t *starts = nullptr;  // the sorted step starts it indexes: slots, or their keys (scanlines())
+};
+
+template <typename SymT>
+struct LinearPath : DecodedText {
+  // ---- what the decode phase hands over (and DecodedText)
+  const wp_vocab *v;
+  Context *c;
+  EncodeStats &S;
+  Arena &ar, &aa;
   int offs_unit;  // offsets mode (wp_linear_encode_offsets): WP_OFFSETS_BYTES / WP_OFFSETS_CODE_POINTS; -1: ids only
   RowsCall *rows;  // a documents call (rows.h; offsets mode is on): the row structure is built behind the spans; else nullptr
   const NormMap *nmap;  // offsets mode on normalised text (normalize.h): d_text is the normalised copy, spans go back through this
 
   // ---- derived
   hipStream_t st, st2;
-  static constexpr bool kSerialTail = WP_SERIAL_TAIL != 0;
   const HostVocab &hv;
   bool full, prune, use_trie, key_lookup, keys_only, window_store, use_digit_bytes, staged_possible, sparse_emit;
   // keys_only: the needed groups are built from the candidate runs and refined beside the round-0 passes (ranks_round0,
@@ -175,8 +124,9 @@ struct LinearPath {
   bool early_refine;
   bool wide_ran = false;  // the walk took the wide branch: scalar 13 holds its count of words (wp_walk_stats)
   uint32_t need_depth;
-  int M, P, P_cap, bucket_shift, bucket_shift_all, key_shift, key_shift_all, hb_n, win_mid;
-  unsigned sl_tiles, sl_groups, nbuckets, nbuckets_all, nkbuckets, nkbuckets_all;
+  int M, P, P_cap, hb_n, win_mid;
+  unsigned sl_tiles, sl_groups;
+  BucketIndex bix[kStepIndexes];
   size_t radix_words, emit_tiles, walk_blocks, claim_size, list_cap;
 
   // ---- device buffers.  n-sized "slabs" of 4 bytes per symbol change roles from stage to stage (see plan()).
@@ -208,14 +158,11 @@ struct LinearPath {
   uint32_t *d_mslot0 = nullptr, *d_mslot1 = nullptr, *d_midx0 = nullptr, *d_midx1 = nullptr, *d_minfo = nullptr, *d_tile_mlo = nullptr;
   int32_t *d_mid = nullptr, *d_rf = nullptr, *d_rb = nullptr, *d_cover_f = nullptr, *d_cover_b = nullptr;
   int32_t *d_tmin_f = nullptr, *d_tmin_b = nullptr, *d_gmin_f = nullptr, *d_gmin_b = nullptr, *d_pval_p = nullptr, *d_pval_s = nullptr;
-  uint32_t *d_ps0 = nullptr, *d_ps1 = nullptr, *d_bidx = nullptr;
-  int2 *d_bfast = nullptr, *d_bfast_all = nullptr;
-  uint32_t *d_bidx_all = nullptr;
-  // the step table in key space (scanline.h): starts, values, indices; the ends of the needed groups
-  uint32_t *d_gend = nullptr, *d_kstart = nullptr, *d_kbidx = nullptr, *d_kbidx_all = nullptr;
+  uint32_t *d_ps0 = nullptr, *d_ps1 = nullptr;
+  // the step table in key space (scanline.h): starts, values (indices: bix); the ends of the needed groups
+  uint32_t *d_gend = nullptr, *d_kstart = nullptr;
   int32_t *d_kval_p = nullptr, *d_kval_s = nullptr, *d_cover_tot = nullptr;
   uint8_t *d_kneed = nullptr;  // per step: its start lies inside a needed group (scanline.h, step_tables_kernel)
-  int2 *d_kbfast = nullptr, *d_kbfast_all = nullptr;
   // keys-only round 0 (decode.h, CandSet): the long-token key set, the runs of its slots in the sorted candidate list,
   // and per needed group the start of its run
   unsigned long long *d_cand_table = nullptr;
@@ -249,18 +196,17 @@ struct LinearPath {
   bool classified = false, anchors_queued = false;
   bool anchor_scalars_queued = false;  // the anchor scalars reach the host from the side stream, behind kEvAnchorScalars
   size_t n_act = 0, n_large = 0, n_large_groups = 0, n_groups = 0;
-  StepTable steps{}, steps_all{};  // (steps_all: for the kernels that look up EVERY position of a stretch, scanlines())
-  StepTable ksteps{}, ksteps_all{};  // the same in key space (key_lookup)
+  // one per bucket index (an absent twin: its table again; no key lookup: empty).  The "_all" ones are for the kernels
+  // that look up EVERY position of a stretch (scanlines())
+  StepTable tables[kStepIndexes] = {};
   CandSet cand{};                    // keys_only: the set and the list the key builder appends to
   CandRuns cand_runs{};              // keys_only: the sorted list as the needed-group kernels read it
   size_t n_cand = 0;
 
-  LinearPath(const wp_vocab *v_, Context *c_, EncodeStats &S_, Arena &ar_, Arena &aa_, const uint8_t *text, size_t nb,
-             const uint32_t *tile_prefix, size_t n_text_, size_t n_, uint32_t *cps, uint8_t *cls, int bits_, bool text_only_,
-             int offs_unit_, RowsCall *rows_ = nullptr, const NormMap *nmap_ = nullptr)
-      : v(v_), c(c_), S(S_), ar(ar_), aa(aa_), d_text(text), nbytes(nb), d_tile_prefix(tile_prefix), n_text(n_text_), n(n_),
-        d_cps(cps), d_cls(cls), bits(bits_), text_only(text_only_), offs_unit(offs_unit_), rows(rows_), nmap(nmap_), st(c_->stream), st2(c_->stream2),
-        hv(v_->hv) {
+  LinearPath(const wp_vocab *v_, Context *c_, EncodeStats &S_, Arena &ar_, Arena &aa_, const DecodedText &text, int offs_unit_,
+             RowsCall *rows_ = nullptr, const NormMap *nmap_ = nullptr)
+      : DecodedText(text), v(v_), c(c_), S(S_), ar(ar_), aa(aa_), offs_unit(offs_unit_), rows(rows_), nmap(nmap_), st(c_->stream),
+        st2(c_->stream2), hv(v_->hv) {
     full = v->full_depth || hv.n_dup_eligible > 0 || v->lcp_kasai;
     need_depth = static_cast<uint32_t>(std::min<int64_t>(hv.longest + 1, 0x7fffffff));
     M = static_cast<int>(hv.elig_id.size());
@@ -285,21 +231,22 @@ struct LinearPath {
     P_cap = P + 2 * M + 2;      // ... and two per needed group (at most one group per eligible token) with key_lookup
     // buckets of the step table's index: about four per step (most lookups then end at the bucket entry, scanline.h)
     const int bucket_bits = std::min(kStepBucketBitsMax, std::max(kStepBucketBits, bit_length(4 * static_cast<size_t>(P))));
-    bucket_shift = std::max(0, bit_length(n) - bucket_bits);
-    nbuckets = static_cast<unsigned>(((n - 1) >> bucket_shift) + 1);
+    const int bucket_shift = std::max(0, bit_length(n) - bucket_bits);
     // ... and a second index of 2^18 buckets (2 MB: stays in the L2) for the kernels that look up every position of a
     // long word, on the chain or not — their ranks spread over all slots, and 16 MB of entries miss the L2 (config 5:
     // 13.0 against 11.0 ms; the coverage rule's reach kernel, whose positions nearly all ARE visited, is faster on the
     // fine index: config 3, 9.3 against 9.8 ms)
-    bucket_shift_all = std::max(0, bit_length(n) - kStepBucketBits);
-    nbuckets_all = static_cast<unsigned>(((n - 1) >> bucket_shift_all) + 1);
+    const int bucket_shift_all = std::max(0, bit_length(n) - kStepBucketBits);
     // the key-space indices: as many buckets, on the top bits of the key (entropy-coded: near-uniform)
-    const int kb = std::min(kKeyBits, std::max(1, bit_length(n - 1) - bucket_shift));
-    const int kb_all = std::min(kKeyBits, std::max(1, bit_length(n - 1) - bucket_shift_all));
-    key_shift = kKeyBits - kb;
-    key_shift_all = kKeyBits - kb_all;
-    nkbuckets = 1u << kb;
-    nkbuckets_all = 1u << kb_all;
+    for (int i = 0; i < kStepIndexes; i++) {
+      BucketIndex &b = bix[i];
+      const int slot_shift = i >= kIxSlotAll ? bucket_shift_all : bucket_shift;
+      const int kb = std::min(kKeyBits, std::max(1, bit_length(n - 1) - slot_shift));
+      b.keyed = i == kIxKey || i == kIxKeyAll;
+      b.shift = b.keyed ? kKeyBits - kb : slot_shift;
+      const bool present = (!b.keyed || key_lookup) && (i < kIxSlotAll || b.shift != bix[i - 2].shift);
+      if (present) b.planned = b.used = b.keyed ? 1u << kb : static_cast<unsigned>(((n - 1) >> slot_shift) + 1);
+    }
     radix_words = std::max(radix_tmp_words<uint64_t>(n), radix_tmp_words<uint32_t>(std::max<size_t>(n, static_cast<size_t>(P_cap))));
     emit_tiles = cdiv(std::max<size_t>(n_text, 1), kScanTile);
     walk_blocks = cdiv(std::max<size_t>(n_text, 1), kBlock);  // (at most one anchor per position)
@@ -337,9 +284,6 @@ struct LinearPath {
     n_sorted = n;
     S.round0_sorted = static_cast<int64_t>(n);
   }
-
-  // early refinement: the group starts, the token ranges, the marks and their step starts in one launch (token_marks_kernel)
-  bool fused_marks() const { return early_refine && !kSerialTail; }
 
   // st2 starts after everything queued on st so far / st continues after everything queued on st2
   void fork() {
@@ -457,19 +401,15 @@ struct LinearPath {
       d_ps1 = ar.take<uint32_t>(P_cap + 1);
       d_pval_p = ar.take<int32_t>(P_cap + 1);
       d_pval_s = ar.take<int32_t>(P_cap + 1);
-      d_bidx = ar.take<uint32_t>(static_cast<size_t>(nbuckets) + 2);
-      d_bfast = ar.take<int2>(static_cast<size_t>(nbuckets) + 1);
-      d_bidx_all = bucket_shift_all != bucket_shift ? ar.take<uint32_t>(static_cast<size_t>(nbuckets_all) + 2) : nullptr;
-      d_bfast_all = bucket_shift_all != bucket_shift ? ar.take<int2>(static_cast<size_t>(nbuckets_all) + 1) : nullptr;
+      for (BucketIndex &b : bix) {
+        b.idx = b.planned ? ar.take<uint32_t>(static_cast<size_t>(b.planned) + 2) : nullptr;
+        b.fast = b.planned ? ar.take<int2>(static_cast<size_t>(b.planned) + 1) : nullptr;
+      }
       d_gend = key_lookup ? ar.take<uint32_t>(M + 4) : nullptr;
       d_kstart = key_lookup ? ar.take<uint32_t>(P_cap + 1) : nullptr;
       d_kval_p = key_lookup ? ar.take<int32_t>(P_cap + 1) : nullptr;
       d_kval_s = key_lookup ? ar.take<int32_t>(P_cap + 1) : nullptr;
       d_kneed = key_lookup ? ar.take<uint8_t>(P_cap + 1) : nullptr;
-      d_kbidx = key_lookup ? ar.take<uint32_t>(static_cast<size_t>(nkbuckets) + 2) : nullptr;
-      d_kbfast = key_lookup ? ar.take<int2>(static_cast<size_t>(nkbuckets) + 1) : nullptr;
-      d_kbidx_all = (key_lookup && key_shift_all != key_shift) ? ar.take<uint32_t>(static_cast<size_t>(nkbuckets_all) + 2) : nullptr;
-      d_kbfast_all = (key_lookup && key_shift_all != key_shift) ? ar.take<int2>(static_cast<size_t>(nkbuckets_all) + 1) : nullptr;
       d_cand_table = keys_only ? ar.take<unsigned long long>(claim_size) : nullptr;
       d_cand_filter = keys_only ? ar.take<uint32_t>(kCandFilterWords) : nullptr;
       d_gcand = keys_only ? ar.take<uint32_t>(M + 4) : nullptr;
@@ -514,7 +454,7 @@ struct LinearPath {
     // alone (every earlier copy into the mirror has been waited for; the main stream queues none before the walk), so
     // that the walk is queued while the scanline kernels still wait in the main stream.  (On the main stream — the late
     // refinement of the key lookup — the side stream's copy of the list sizes may still be under way: walk() fetches.)
-    if (as == st2 && !kSerialTail) {
+    if (as == st2) {
       static_assert(kScalarAnchorGap == kScalarAnchors + 1, "one copy takes both anchor scalars");
       queue_scalar_slots(c, kScalarAnchors, kScalarAnchorGap, as);
       WP_HIP(hipEventRecord(c->evs[kEvAnchorScalars], as));
@@ -683,27 +623,21 @@ struct LinearPath {
       vals = keys_only ? nullptr : (cur ? VB : VA);
       other_vals = keys_only ? nullptr : (cur ? VA : VB);
       if (keys_only) sort_candidates();
-      slots = AS0;
-      other_slots = AS1;
-      adep = AD0;
-      other_dep = AD1;
-      avals = LA;
-      spare_vals = LB;
-      return;
+    } else {
+      if (window_store) {  // the last pass leaves the first digit of the rank store's destination partition
+        db.tail_bit = kWinBits;
+        db.tail_mask = (1u << (win_mid - kWinBits)) - 1u;
+        db.tail_from_val = true;
+      }
+      // histogram: one per-wave LDS counter per digit for the lowest digit (near-uniform), interleaved copies above it
+      cur = radix_sort_pairs<Key0>(KA, VA, KB, VB, n, 0, kKeyBits, d_radix_tmp, radix_words, st, &c->rstats, true,
+                                   code.uniform_bits ? 0 : 8, db, true, hist_in_keys ? &sort_plan : nullptr);
+      S.hist_in_keys = hist_in_keys ? 1 : 0;
+      keys = cur ? KB : KA;
+      other_keys = cur ? KA : KB;
+      vals = cur ? VB : VA;
+      other_vals = cur ? VA : VB;
     }
-    if (window_store) {  // the last pass leaves the first digit of the rank store's destination partition
-      db.tail_bit = kWinBits;
-      db.tail_mask = (1u << (win_mid - kWinBits)) - 1u;
-      db.tail_from_val = true;
-    }
-    // histogram: one per-wave LDS counter per digit for the lowest digit (near-uniform), interleaved copies above it
-    cur = radix_sort_pairs<Key0>(KA, VA, KB, VB, n, 0, kKeyBits, d_radix_tmp, radix_words, st, &c->rstats, true,
-                                 code.uniform_bits ? 0 : 8, db, true, hist_in_keys ? &sort_plan : nullptr);
-    S.hist_in_keys = hist_in_keys ? 1 : 0;
-    keys = cur ? KB : KA;
-    other_keys = cur ? KA : KB;
-    vals = cur ? VB : VA;
-    other_vals = cur ? VA : VB;
     slots = AS0;
     other_slots = AS1;
     adep = AD0;
@@ -770,10 +704,9 @@ struct LinearPath {
 
   // The rank store of round 0 at full size.  val == nullptr: the values are the slots themselves, made up by the first
   // pass.  The passes go through the scratch pairs a = (X0, X1) and b = (the value buffer the sort did not end in, the
-  // sorted keys — free once the side stream's searches in them are over: before_second).
+  // sorted keys — free once the side stream's searches in them are over: keys_free).
   // dig: digit bytes of dst bits [kWinBits, ...), left by the last pass of the sort; other: the second byte buffer.
-  void store_ranks_round0(uint32_t *dst, uint32_t *val, uint8_t *dig, uint8_t *other, const std::function<void()> &before_second,
-                          const std::function<void()> &before_window) {
+  void store_ranks_round0(uint32_t *dst, uint32_t *val, uint8_t *dig, uint8_t *other) {
     // (a per-device attribute: set on every call, the context may live on any device)
     WP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(window_store_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                static_cast<int>(kWinLdsBytes)));
@@ -789,7 +722,7 @@ struct LinearPath {
     // (the digits of both passes are position bits, uniform over 64..128 values: LDS atomics into interleaved copies)
     radix_sort_pairs<uint32_t>(dst, val, a_dst, a_val, n, kWinBits, win_mid, d_radix_tmp, radix_words, st, &c->rstats,
                                val == nullptr, 0, d1, true);
-    if (before_second) before_second();
+    keys_free();
     const uint32_t *f_dst = a_dst, *f_val = a_val;
     if (win_mid < hb_n) {
       DigitBytes d2;
@@ -801,83 +734,117 @@ struct LinearPath {
       f_dst = b_dst;
       f_val = b_val;
     }
-    if (before_window) before_window();
+    start_trie_round();
     hipLaunchKernelGGL(window_store_kernel, dim3(cdiv(n, size_t(1) << kWinBits)), dim3(kWinThreads), kWinLdsBytes, st, f_dst, f_val,
                        n, d_rank);
   }
 
+  // ---- the needed groups of a pruned round 0 (prune.h, trie.h): what the late and the early path share ----------------
+  TokenTrie token_trie() const {
+    return TokenTrie{c->d_lt_chain_len, c->d_lt_chain_off, c->d_lt_child_begin, c->d_lt_child_node, d_child_sym};
+  }
+  // early: the list is built before the sort ends, the groups' first slots are not known yet (refine_early)
+  NeededList needed_list(bool early) const {
+    return NeededList{slots, avals, AG, adep, d_ghead, early ? nullptr : d_gfirst, d_gdep,
+                      reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarList), static_cast<uint32_t *>(nullptr), need_depth,
+                      d_claim_need, d_gclaim, d_gneed0, keys_only ? d_gcand : nullptr, keys_only ? cand_runs.pos : nullptr,
+                      keys_only ? n_cand : 0};
+  }
+  void clear_claims() {
+    WP_HIP(hipMemsetAsync(d_claim, 0xff, claim_size * sizeof(uint32_t), st2));
+    if (!keys_only) WP_HIP(hipMemsetAsync(d_claim_need, 0, claim_size * sizeof(uint32_t), st2));  // (else: sort_candidates)
+  }
+  // the vocabulary stream and the trie's child labels as dense symbols of this encode's alphabet
+  void map_trie_symbols() {
+    const size_t ns = hv.stream.size(), nc = hv.lt_child_cp.size();
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(trie_map_symbols_kernel<SymT>), dim3(cdiv(std::max<size_t>(std::max(ns, nc), 1), kBlock)),
+                       dim3(kBlock), 0, st2, c->d_stream, ns, c->d_lt_child_cp, nc, c->d_lut, d_vsym, d_child_sym);
+  }
+  // a list longer than its room is emptied and reported (ListOverflow); the closing entry of the group heads
+  void close_needed_list() {
+    hipLaunchKernelGGL(needed_list_clamp_kernel, dim3(1), dim3(1), 0, st2, c->d_scalars + kScalarList, static_cast<uint32_t>(list_cap),
+                       c->d_scalars + kScalarListWanted);
+    hipLaunchKernelGGL(needed_list_close_kernel, dim3(1), dim3(1), 0, st2, c->d_scalars + kScalarList, d_ghead);
+  }
+
+  // Depth-capped mode, behind the sort: the groups that have to go on are found from the vocabulary (prune.h) and
+  // appended to the active list by the kernel that finds them — on the side stream (a few thousand waves of searches).
+  void enqueue_needed_groups() {
+    clear_claims();
+    const NeededList nl = needed_list(false);
+    if (use_trie) map_trie_symbols();
+    if (M > 0) {  // (no eligible token at all: every tied group retires)
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(need_groups_kernel<SymT>), dim3(cdiv(static_cast<size_t>(M) * kWave, kBlock)),
+                         dim3(kBlock), 0, st2, keys, vals, n_sorted, n, d_sym, c->d_stream, c->d_elig_start, c->d_elig_info, M, c->d_lut, dcode,
+                         d_claim, static_cast<uint32_t>(claim_size - 1), nl, text_only ? d_rng_lo : nullptr, d_rng_hi, d_rng_long,
+                         cand_runs);
+    }
+    close_needed_list();
+    if (key_lookup) {  // (the group heads are overwritten by the trie round: the group ends are taken now)
+      hipLaunchKernelGGL(group_starts_kernel, dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st2, d_gfirst, d_ghead, c->d_scalars + kScalarList,
+                         n_sorted, d_ps0 + P, d_gend);
+    }
+    if (M > 0) {
+      if (!use_trie) hipLaunchKernelGGL(needed_need_kernel, dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st2, nl);
+      hipLaunchKernelGGL(needed_fill_kernel, dim3(1024), dim3(kBlock), 0, st2, nl, vals, n_sorted);
+      if (use_trie) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(trie_group_start_kernel<SymT>), dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st2, vals,
+                           keys_only ? cand_runs.pos : nullptr, d_gcand, d_gfirst,
+                           d_gdep, c->d_scalars + kScalarList, d_sym, n, d_vsym, token_trie(), d_gnode, d_gdone);
+      }
+    }
+    // (from here on the side stream no longer reads the sorted keys and suffixes: the rank store may reuse them)
+    WP_HIP(hipEventRecord(c->evs[kEvKeysFree], st2));
+    if (use_trie) trie_round_sizes();
+  }
+  // pair b of the rank store holds the sorted keys: the side stream's searches in them must be over
+  void keys_free() {
+    if (prune) WP_HIP(hipStreamWaitEvent(st, c->evs[kEvKeysFree], 0));
+  }
+  // The trie round (side stream) starts when the partition passes are through: its small latency-bound kernels run
+  // beside the window store — beside the radix passes they took a quarter of the passes' bandwidth for the same gain.
+  void start_trie_round() {
+    if (!use_trie) return;
+    WP_HIP(hipEventRecord(c->evs[kEvPartition], st));
+    WP_HIP(hipStreamWaitEvent(st2, c->evs[kEvPartition], 0));
+    trie_round_sort();
+  }
+
   // ---- behind the sort: which tied groups go on (side stream), and the inverse suffix array (linear.cpp:144-147) ----
   void ranks_round0() {
-    const DepthRule rule{need_depth, full ? 1 : 0, nullptr, nullptr, 0, nullptr};
-    const unsigned tiles = cdiv(n, kRrTile);
+    if (early_refine) {
+      refine_early();
+    } else if (key_lookup) {
+      refine_late_by_key();
+    } else {
+      rank_all_round0();
+    }
+  }
+
+  // No rank store: the needed-group searches and the trie round (side stream) are the critical path now, and the
+  // anchor list (main stream: class bytes only) runs beside them.  The trie round stores a rank for every entry
+  // of the needed list — the only ranks anything reads (walk.h, step_value).
+  void refine_late_by_key() {
+    fork();
+    enqueue_needed_groups();
+    trie_round_sort();
+    if (n_text > 0) launch_anchors(st);
+    WP_LAUNCH_CHECK();
+    trie_round_finish();
+  }
+
+  // The rank store: a rank for every suffix, beside the needed groups of a pruned round 0 or with every tied group on the list.
+  void rank_all_round0() {
     // Default layout: nobody asks for a group's head or depth — the step functions change at boundaries between
     // distinct keys only (short tokens) or inside needed groups (long tokens, resolved by the trie round, which stores
     // every rank it touches) — so a suffix's own slot serves as its rank and no kernel derives group heads.
     const bool slot_ranks = text_only && !d_lcp;
     uint8_t *dig = DG0 ? db.tail_out(cur) : nullptr, *dig_other = DG0 ? db.tail_out(cur ^ 1) : nullptr;
-    // Depth-capped mode: the groups that have to go on are found from the vocabulary (prune.h) and appended to the
-    // active list by the kernel that finds them — on the side stream (a few thousand waves of searches).
-    // start_after != nullptr: the side stream starts there (an event of the main stream).
-    auto enqueue_needed_groups = [&](hipEvent_t start_after) {
-      if (start_after) WP_HIP(hipStreamWaitEvent(st2, start_after, 0));
-      WP_HIP(hipMemsetAsync(d_claim, 0xff, claim_size * sizeof(uint32_t), st2));
-      if (!keys_only) WP_HIP(hipMemsetAsync(d_claim_need, 0, claim_size * sizeof(uint32_t), st2));  // (else: sort_candidates)
-      NeededList nl{slots, avals, AG, adep, d_ghead, d_gfirst, d_gdep, reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarList),
-                    static_cast<uint32_t *>(nullptr), need_depth, d_claim_need, d_gclaim, d_gneed0,
-                    keys_only ? d_gcand : nullptr, keys_only ? cand_runs.pos : nullptr, keys_only ? n_cand : 0};
-      const TokenTrie trie{c->d_lt_chain_len, c->d_lt_chain_off, c->d_lt_child_begin, c->d_lt_child_node, d_child_sym};
-      if (use_trie) {  // the vocabulary stream and the trie's child labels as dense symbols of this encode's alphabet
-        const size_t ns = hv.stream.size(), nc = hv.lt_child_cp.size();
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(trie_map_symbols_kernel<SymT>), dim3(cdiv(std::max<size_t>(std::max(ns, nc), 1), kBlock)),
-                           dim3(kBlock), 0, st2, c->d_stream, ns, c->d_lt_child_cp, nc, c->d_lut, d_vsym, d_child_sym);
-      }
-      if (M > 0) {  // (no eligible token at all: every tied group retires)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(need_groups_kernel<SymT>), dim3(cdiv(static_cast<size_t>(M) * kWave, kBlock)),
-                           dim3(kBlock), 0, st2, keys, vals, n_sorted, n, d_sym, c->d_stream, c->d_elig_start, c->d_elig_info, M, c->d_lut, dcode,
-                           d_claim, static_cast<uint32_t>(claim_size - 1), nl, text_only ? d_rng_lo : nullptr, d_rng_hi, d_rng_long,
-                           cand_runs);
-      }
-      hipLaunchKernelGGL(needed_list_clamp_kernel, dim3(1), dim3(1), 0, st2, c->d_scalars + kScalarList, static_cast<uint32_t>(list_cap),
-                         c->d_scalars + kScalarListWanted);
-      hipLaunchKernelGGL(needed_list_close_kernel, dim3(1), dim3(1), 0, st2, c->d_scalars + kScalarList, d_ghead);
-      if (key_lookup) {  // (the group heads are overwritten by the trie round: the group ends are taken now)
-        hipLaunchKernelGGL(group_starts_kernel, dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st2, d_gfirst, d_ghead, c->d_scalars + kScalarList,
-                           n_sorted, d_ps0 + P, d_gend);
-      }
-      if (M > 0) {
-        if (!use_trie) hipLaunchKernelGGL(needed_need_kernel, dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st2, nl);
-        hipLaunchKernelGGL(needed_fill_kernel, dim3(1024), dim3(kBlock), 0, st2, nl, vals, n_sorted);
-        if (use_trie) {
-          hipLaunchKernelGGL(HIP_KERNEL_NAME(trie_group_start_kernel<SymT>), dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st2, vals,
-                             keys_only ? cand_runs.pos : nullptr, d_gcand, d_gfirst,
-                             d_gdep, c->d_scalars + kScalarList, d_sym, n, d_vsym, trie, d_gnode, d_gdone);
-        }
-      }
-      // (from here on the side stream no longer reads the sorted keys and suffixes: the rank store may reuse them)
-      WP_HIP(hipEventRecord(c->evs[kEvKeysFree], st2));
-      if (use_trie) trie_round_sizes();
-    };
-    // (they start when the sort ends, beside the first partition pass's histogram: started beside its scatter instead,
-    // which is bandwidth-bound, they cost the scatter more than they cost the histogram now — measured)
-    if (early_refine) {
-      refine_early();
-      return;
-    }
-    if (key_lookup) {
-      // No rank store: the needed-group searches and the trie round (side stream) are the critical path now, and the
-      // anchor list (main stream: class bytes only) runs beside them.  The trie round stores a rank for every entry
-      // of the needed list — the only ranks anything reads (walk.h, step_value).
-      fork();
-      enqueue_needed_groups(nullptr);
-      trie_round_sort();
-      if (n_text > 0) launch_anchors(st);
-      WP_LAUNCH_CHECK();
-      trie_round_finish();
-      return;
-    }
     if (prune) {
+      // (the searches start when the sort ends, beside the first partition pass's histogram: started beside its scatter
+      // instead, which is bandwidth-bound, they cost the scatter more than they cost the histogram now — measured)
       fork();
-      enqueue_needed_groups(nullptr);
+      enqueue_needed_groups();
       if (!slot_ranks) {  // reference layout: rank entries, LCPs and group depths from the sorted keys
         hipLaunchKernelGGL(round0_rank_kernel<true>, dim3(cdiv(n, kR0Tile)), dim3(kBlock), 0, st, keys, vals, n, dcode.first_len,
                            dcode.uniform_bits, d_sa, d_hd_n, d_lcp, d_gdepth);
@@ -885,6 +852,8 @@ struct LinearPath {
     } else {
       // every tied group goes on (true suffix array, or no pruning possible): the count / prefix / apply kernels take
       // 64-bit keys, the 32-bit round-0 keys are widened into the large-list key buffer (free during round 0)
+      const DepthRule rule{need_depth, full ? 1 : 0, nullptr, nullptr, 0, nullptr};
+      const unsigned tiles = cdiv(n, kRrTile);
       hipLaunchKernelGGL(widen_keys_kernel, dim3(std::min<size_t>(cdiv(n, kBlock), 8192)), dim3(kBlock), 0, st, keys, LK2, n);
       hipLaunchKernelGGL(HIP_KERNEL_NAME(rerank_agg_kernel<true>), dim3(tiles), dim3(kBlock), 0, st, LK2, vals, n,
                          static_cast<const uint32_t *>(nullptr), static_cast<const RankEntry *>(nullptr),
@@ -897,19 +866,8 @@ struct LinearPath {
                          c->d_scalars + kScalarList);
     }
     uint32_t *rank_vals = slot_ranks ? nullptr : reinterpret_cast<uint32_t *>(d_hd_n);
-    auto keys_free = [&] {  // pair b of the rank store holds the sorted keys: the side stream's searches in them must be over
-      if (prune) WP_HIP(hipStreamWaitEvent(st, c->evs[kEvKeysFree], 0));
-    };
-    // The trie round (side stream) starts when the partition passes are through: its small latency-bound kernels run
-    // beside the window store — beside the radix passes they took a quarter of the passes' bandwidth for the same gain.
-    auto start_trie_round = [&] {
-      if (!use_trie) return;
-      WP_HIP(hipEventRecord(c->evs[kEvPartition], st));
-      WP_HIP(hipStreamWaitEvent(st2, c->evs[kEvPartition], 0));
-      trie_round_sort();
-    };
     if (window_store) {
-      store_ranks_round0(vals, rank_vals, dig, dig_other, keys_free, start_trie_round);
+      store_ranks_round0(vals, rank_vals, dig, dig_other);
     } else {
       keys_free();
       start_trie_round();
@@ -935,43 +893,33 @@ struct LinearPath {
   // and whatever the round indexes by slot (slots, the trie nodes by slot, the rank entries) is indexed by list position.
   // Behind the last pass only the slot-dependent tail is left, on the main stream: the searches in the sorted keys
   // (every token's range, every group's first slot), the group starts of the step table, and the rank scatter, which
-  // adds gfirst[g] - ghead[g] to every entry while it reads (trie_token_range_list_kernel does the same for the ranges).
+  // adds gfirst[g] - ghead[g] to every entry while it reads (token_marks_kernel does the same for the ranges).
   // The streams are ordered by events alone.  The anchor list goes to the side stream behind the round and behind the
   // sort (kEvSorted): beside the tail and the scanline stage, not beside the passes.
   void refine_early() {
-    WP_HIP(hipMemsetAsync(d_claim, 0xff, claim_size * sizeof(uint32_t), st2));  // (d_claim_need: cleared by sort_candidates)
-    NeededList nl{slots, avals, AG, adep, d_ghead, static_cast<uint32_t *>(nullptr), d_gdep,
-                  reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarList), static_cast<uint32_t *>(nullptr), need_depth,
-                  d_claim_need, d_gclaim, d_gneed0, d_gcand, cand_runs.pos, n_cand};
-    const TokenTrie trie{c->d_lt_chain_len, c->d_lt_chain_off, c->d_lt_child_begin, c->d_lt_child_node, d_child_sym};
-    const size_t ns = hv.stream.size(), nc = hv.lt_child_cp.size();
+    clear_claims();
+    const NeededList nl = needed_list(true);
     const unsigned tok_blocks = cdiv(static_cast<size_t>(M) * kWave, kBlock);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(trie_map_symbols_kernel<SymT>), dim3(cdiv(std::max<size_t>(std::max(ns, nc), 1), kBlock)),
-                       dim3(kBlock), 0, st2, c->d_stream, ns, c->d_lt_child_cp, nc, c->d_lut, d_vsym, d_child_sym);
+    map_trie_symbols();
     // (a long token's table slot, run length and state wait in its cells of rng_lo / rng_hi / rng_long for the late half)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(need_groups_early_kernel<SymT>), dim3(tok_blocks), dim3(kBlock), 0, st2, n, d_sym, c->d_stream,
                        c->d_elig_start, c->d_elig_info, M, c->d_lut, dcode, d_claim, nl, d_rng_lo, d_rng_hi, d_rng_long, cand_runs);
-    hipLaunchKernelGGL(needed_list_clamp_kernel, dim3(1), dim3(1), 0, st2, c->d_scalars + kScalarList, static_cast<uint32_t>(list_cap),
-                       c->d_scalars + kScalarListWanted);
-    hipLaunchKernelGGL(needed_list_close_kernel, dim3(1), dim3(1), 0, st2, c->d_scalars + kScalarList, d_ghead);
+    close_needed_list();
     hipLaunchKernelGGL(needed_fill_kernel, dim3(1024), dim3(kBlock), 0, st2, nl, static_cast<const uint32_t *>(nullptr), n_sorted);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(trie_group_start_kernel<SymT>), dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st2,
                        static_cast<const uint32_t *>(nullptr), cand_runs.pos, d_gcand, static_cast<const uint32_t *>(nullptr), d_gdep,
-                       c->d_scalars + kScalarList, d_sym, n, d_vsym, trie, d_gnode, d_gdone);
+                       c->d_scalars + kScalarList, d_sym, n, d_vsym, token_trie(), d_gnode, d_gdone);
     WP_HIP(hipEventRecord(c->evs[kEvListBuilt], st2));  // (the late half may overwrite the tokens' cells from here on)
     trie_round_sizes();
     trie_round_sort();
     S.sched.early = 1;
-    // main stream, behind the last pass: the late half of the searches, and the group starts (they read the group table
-    // and its sizes, which nothing writes after the list is built: the round's own totals go elsewhere, trie_round_finish)
+    // main stream, behind the last pass: the late half of the searches (the group starts follow in token_marks_kernel,
+    // scanlines(): they read the group table and its sizes, which nothing writes after the list is built — the round's
+    // own totals go elsewhere, trie_round_finish)
     WP_HIP(hipEventRecord(c->evs[kEvSorted], st));
     WP_HIP(hipStreamWaitEvent(st, c->evs[kEvListBuilt], 0));
     hipLaunchKernelGGL(need_ranges_kernel, dim3(tok_blocks), dim3(kBlock), 0, st, keys, n_sorted, c->d_stream, c->d_elig_start,
                        c->d_elig_info, M, c->d_lut, dcode, d_claim, d_gfirst, d_rng_lo, d_rng_hi, d_rng_long, d_tok_group);
-    if (!fused_marks()) {  // (else: token_marks_kernel, scanlines())
-      hipLaunchKernelGGL(group_starts_kernel, dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st, d_gfirst, d_ghead, c->d_scalars + kScalarList,
-                         n_sorted, d_ps0 + P, d_gend);
-    }
     WP_LAUNCH_CHECK();
     trie_round_finish();
   }
@@ -988,10 +936,9 @@ struct LinearPath {
     WP_HIP(hipEventRecord(c->evs[kEvScalars], st2));
   }
   void trie_round_sort() {
-    const TokenTrie trie{c->d_lt_chain_len, c->d_lt_chain_off, c->d_lt_child_begin, c->d_lt_child_node, d_child_sym};
     // (sizes are read on the device: the launches do not wait for the host to learn them)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(trie_walk_kernel<SymT>), dim3(std::min<size_t>(cdiv(list_cap, kBlock), 16384)), dim3(kBlock), 0,
-                       st2, avals, AG, d_gnode, d_gdone, c->d_scalars + kScalarList, d_sym, n, d_vsym, trie, adep);
+                       st2, avals, AG, d_gnode, d_gdone, c->d_scalars + kScalarList, d_sym, n, d_vsym, token_trie(), adep);
     WP_HIP(hipEventRecord(c->evs[kEvTrieNodes], st2));  // (the large-group path starts from here, beside the LDS sort: trie_round_finish)
     hipLaunchKernelGGL(local_sort_kernel, dim3(cdiv(list_cap, kLsT)), dim3(kBlock), 0, st2, avals, AG, adep, c->d_scalars + kScalarList,
                        d_ghead, d_rank, n, trie_rb(), LK0, spare_vals, adep);
@@ -1044,7 +991,7 @@ struct LinearPath {
       hipLaunchKernelGGL(HIP_KERNEL_NAME(rerank_apply_kernel<SymT, false>), dim3(tiles), dim3(kBlock), 0, st2, skeys, spare_vals, slots,
                          adep, d_tdep, n_act, d_agg, d_sym, n, dcode.first_len, dcode.uniform_bits, rrule, d_sa, hd, d_lcp,
                          other_slots, avals, AG, other_dep, d_ghead, d_gdepth,
-                         c->d_scalars + (early_refine ? kScalarSplitTotals : kScalarList));  // (early: group_starts_kernel still reads the sizes)
+                         c->d_scalars + (early_refine ? kScalarSplitTotals : kScalarList));  // (early: token_marks_kernel still reads the sizes)
     }
     if (early_refine) {  // the main stream goes on behind the round; the anchor list follows it on the side stream, behind the sort
       WP_HIP(hipEventRecord(c->evs[kEvRoundDone], st2));
@@ -1187,19 +1134,14 @@ struct LinearPath {
       // S = text . 1: the reach of every token is its range in the sorted keys (prune.h); a long token's is the run of
       // the trie nodes below its own inside its group (trie.h).  The marks arrive sorted (tokens in lexicographic order).
       if (M > 0) {
-        if (fused_marks()) {
+        if (early_refine) {  // the group starts, the token ranges, the marks and their step starts in one launch
           hipLaunchKernelGGL(token_marks_kernel, dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st, d_node_of_slot, c->d_elig_node,
                              c->d_elig_subtree, M, d_rng_lo, d_rng_hi, d_rng_long, d_tok_group, d_ghead, d_gfirst,
                              c->d_scalars + kScalarList, n_sorted, c->d_elig_id, c->d_elig_info, d_mslot0, d_mid, d_minfo, d_rf, d_rb,
                              d_ps0, d_gend);
-        } else if (early_refine) {  // (the trie nodes are indexed by list position: refine_early)
-          hipLaunchKernelGGL(trie_token_range_list_kernel, dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st, d_node_of_slot, c->d_elig_node,
-                             c->d_elig_subtree, M, d_rng_lo, d_rng_hi, d_rng_long, d_tok_group, d_ghead);
         } else {
           hipLaunchKernelGGL(trie_token_range_kernel, dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st, d_node_of_slot, c->d_elig_node,
                              c->d_elig_subtree, M, d_rng_lo, d_rng_hi, d_rng_long);
-        }
-        if (!fused_marks()) {
           hipLaunchKernelGGL(virtual_marks_kernel, dim3(cdiv(M, kBlock)), dim3(kBlock), 0, st, d_rng_lo, d_rng_hi, M, c->d_elig_id,
                              c->d_elig_info, d_mslot0, d_mid, d_minfo, d_rf, d_rb);
         }
@@ -1230,10 +1172,9 @@ struct LinearPath {
     // The tail of the stage on two streams (key lookup): the cover scan runs on the second side stream beside the step
     // starts and their sort, and so does, beside the step values, everything behind the sort that reads no value
     // (side_tables).  The main stream waits for the scan in front of piece_values_kernel and for the tables behind it.
-    const bool side_tail = key_lookup && !kSerialTail;
-    hipStream_t st3 = side_tail ? c->stream3 : st;
+    hipStream_t st3 = key_lookup ? c->stream3 : st;
     if (M > 0) {
-      if (side_tail) {
+      if (key_lookup) {
         WP_HIP(hipEventRecord(c->evs[kEvMarks], st));
         WP_HIP(hipStreamWaitEvent(st3, c->evs[kEvMarks], 0));
       }
@@ -1243,10 +1184,10 @@ struct LinearPath {
       }
       hipLaunchKernelGGL(mark_cover_kernel, dim3(chunks, 4), dim3(kCoverThreads), 0, st3, d_minfo, d_rf, d_rb, M,
                          chunks > 1 ? d_cover_tot : static_cast<const int32_t *>(nullptr), d_cover_f, d_cover_b);
-      if (side_tail) WP_HIP(hipEventRecord(c->evs[kEvCovered], st3));
+      if (key_lookup) WP_HIP(hipEventRecord(c->evs[kEvCovered], st3));
     }
     if (n_text > 0 && !anchors_queued) launch_anchors(st2);
-    if (!fused_marks()) {
+    if (!early_refine) {  // (else: token_marks_kernel)
       hipLaunchKernelGGL(piece_starts_kernel, dim3(cdiv(std::max(M, 1), kBlock)), dim3(kBlock), 0, st, mv, n_sorted, d_ps0);
     }
     // (key_lookup: the starts of the needed groups wait behind the marks' starts, group_starts_kernel; extra starts
@@ -1254,90 +1195,60 @@ struct LinearPath {
     const int P = this->P + (key_lookup ? 2 * static_cast<int>(n_groups) : 0);
     // (keys alone: only the sorted starts go on)
     const int pc = radix_sort_pairs<uint32_t>(d_ps0, nullptr, d_ps1, nullptr, P, 0, bit_length(n), d_radix_tmp, radix_words, st, nullptr);
-    // (slot space holds n_sorted slots: the indices need no bucket behind them; the arena was planned for n)
-    nbuckets = static_cast<unsigned>(((n_sorted - 1) >> bucket_shift) + 1);
-    nbuckets_all = static_cast<unsigned>(((n_sorted - 1) >> bucket_shift_all) + 1);
     uint32_t *pstart = pc ? d_ps1 : d_ps0;
-    if (side_tail) {
+    for (BucketIndex &b : bix) {  // (slot space holds n_sorted slots: the indices need no bucket behind them)
+      if (b.planned && !b.keyed) b.used = static_cast<unsigned>(((n_sorted - 1) >> b.shift) + 1);
+      b.starts = b.keyed ? d_kstart : pstart;
+    }
+    if (key_lookup) {
       WP_HIP(hipEventRecord(c->evs[kEvStartsSorted], st));
       if (M > 0) WP_HIP(hipStreamWaitEvent(st, c->evs[kEvCovered], 0));
     }
     hipLaunchKernelGGL(piece_values_kernel, dim3(cdiv(static_cast<size_t>(P) * kWave, kBlock)), dim3(kBlock), 0, st, mv, pstart, P,
                        d_pval_p, d_pval_s, pack_steps);
-    if (side_tail) {  // (queued behind the values, which take longer than these six launches: the host keeps neither stream waiting)
+    if (key_lookup) {  // (queued behind the values, which take longer than these six launches: the host keeps neither stream waiting)
       WP_HIP(hipStreamWaitEvent(st3, c->evs[kEvStartsSorted], 0));
       side_tables(pstart, P, st3);
       WP_HIP(hipEventRecord(c->evs[kEvTablesIndexed], st3));
       WP_HIP(hipStreamWaitEvent(st, c->evs[kEvTablesIndexed], 0));
       fill_tables(pstart, P);
     } else {
-      hipLaunchKernelGGL(piece_bucket_kernel, dim3(cdiv(nbuckets + 1, kBlock)), dim3(kBlock), 0, st, pstart, P, bucket_shift, nbuckets,
-                         d_bidx);
-      hipLaunchKernelGGL(piece_bucket_fast_kernel, dim3(cdiv(nbuckets, kBlock)), dim3(kBlock), 0, st, d_bidx, d_pval_p, d_pval_s, nbuckets,
-                         d_bfast);
-      if (bucket_shift_all != bucket_shift) {
-        hipLaunchKernelGGL(piece_bucket_kernel, dim3(cdiv(nbuckets_all + 1, kBlock)), dim3(kBlock), 0, st, pstart, P, bucket_shift_all,
-                           nbuckets_all, d_bidx_all);
-        hipLaunchKernelGGL(piece_bucket_fast_kernel, dim3(cdiv(nbuckets_all, kBlock)), dim3(kBlock), 0, st, d_bidx_all, d_pval_p, d_pval_s,
-                           nbuckets_all, d_bfast_all);
+      for (const BucketIndex &b : bix) {
+        if (!b.planned) continue;
+        bucket_index(b, P, st);
+        hipLaunchKernelGGL(piece_bucket_fast_kernel, dim3(cdiv(b.used, kBlock)), dim3(kBlock), 0, st, b.idx, d_pval_p, d_pval_s, b.used,
+                           b.fast);
       }
     }
     WP_LAUNCH_CHECK();
-    steps = StepTable{pstart, d_pval_p, d_pval_s, d_bidx, bucket_shift, pack_steps, d_bfast};
-    steps_all = steps;
-    if (bucket_shift_all != bucket_shift) {
-      steps_all = StepTable{pstart, d_pval_p, d_pval_s, d_bidx_all, bucket_shift_all, pack_steps, d_bfast_all};
-    }
-    if (key_lookup) {
-      if (!side_tail) key_steps(pstart, P);
-      ksteps = StepTable{d_kstart, d_kval_p, d_kval_s, d_kbidx, key_shift, pack_steps, d_kbfast};
-      ksteps_all = ksteps;
-      if (key_shift_all != key_shift) {
-        ksteps_all = StepTable{d_kstart, d_kval_p, d_kval_s, d_kbidx_all, key_shift_all, pack_steps, d_kbfast_all};
-      }
+    for (int i = 0; i < kStepIndexes; i++) {  // (an absent twin: the table of the index it would repeat)
+      const BucketIndex &b = bix[i].planned || i < kIxSlotAll ? bix[i] : bix[i - 2];
+      if (!b.planned) continue;
+      tables[i] = StepTable{b.starts, b.keyed ? d_kval_p : d_pval_p, b.keyed ? d_kval_s : d_pval_s, b.idx, b.shift, pack_steps, b.fast};
     }
     // wp_step_stats: the tables as the walk gets them
     S.step.n_marks = M;
     S.step.n_steps = P;
     S.step.n_tiles = sl_tiles;
     S.step.n_groups_of_tiles = sl_groups;
-    S.step.bucket_shift = bucket_shift;
-    S.step.bucket_shift_all = bucket_shift_all;
-    S.step.key_shift = key_shift;
-    S.step.key_shift_all = key_shift_all;
+    S.step.bucket_shift = bix[kIxSlot].shift;
+    S.step.bucket_shift_all = bix[kIxSlotAll].shift;
+    S.step.key_shift = bix[kIxKey].shift;
+    S.step.key_shift_all = bix[kIxKeyAll].shift;
     S.step.packed = pack_steps;
     S.step.key_lookup = key_lookup ? 1 : 0;
   }
 
-  // the step table in key space (scanline.h) from the slot-space one: starts by the sorted keys, the entries inside
-  // needed groups answer kStepNeeded, two bucket indices on the top bits of the key
-  void key_steps(const uint32_t *pstart, int P) {
-    const uint32_t *skeys = reinterpret_cast<const uint32_t *>(keys);
-    hipLaunchKernelGGL(key_steps_kernel, dim3(cdiv(P, kBlock)), dim3(kBlock), 0, st, pstart, d_pval_p, d_pval_s, P, skeys, d_kstart,
-                       d_kval_p, d_kval_s);
-    if (n_groups > 0) {
-      hipLaunchKernelGGL(key_steps_needed_kernel, dim3(cdiv(n_groups, kBlock)), dim3(kBlock), 0, st, d_gfirst, d_gend,
-                         static_cast<uint32_t>(n_groups), pstart, P, d_kval_p, d_kval_s);
-    }
-#ifdef WP_DEBUG_BOUNDS
-    hipLaunchKernelGGL(key_steps_check_kernel, dim3(cdiv(P, kBlock)), dim3(kBlock), 0, st, pstart, P, skeys, d_kval_p, d_kval_s);
-#endif
-    hipLaunchKernelGGL(piece_bucket_kernel, dim3(cdiv(nkbuckets + 1, kBlock)), dim3(kBlock), 0, st, d_kstart, P, key_shift, nkbuckets,
-                       d_kbidx);
-    hipLaunchKernelGGL(piece_bucket_fast_kernel, dim3(cdiv(nkbuckets, kBlock)), dim3(kBlock), 0, st, d_kbidx, d_kval_p, d_kval_s,
-                       nkbuckets, d_kbfast);
-    if (key_shift_all != key_shift) {
-      hipLaunchKernelGGL(piece_bucket_kernel, dim3(cdiv(nkbuckets_all + 1, kBlock)), dim3(kBlock), 0, st, d_kstart, P, key_shift_all,
-                         nkbuckets_all, d_kbidx_all);
-      hipLaunchKernelGGL(piece_bucket_fast_kernel, dim3(cdiv(nkbuckets_all, kBlock)), dim3(kBlock), 0, st, d_kbidx_all, d_kval_p,
-                         d_kval_s, nkbuckets_all, d_kbfast_all);
-    }
-    WP_LAUNCH_CHECK();
+  // bidx of one index: the first step of every bucket
+  void bucket_index(const BucketIndex &b, int P, hipStream_t s) {
+    hipLaunchKernelGGL(piece_bucket_kernel, dim3(cdiv(b.used + 1, kBlock)), dim3(kBlock), 0, s, b.starts, P, b.shift, b.used, b.idx);
   }
 
-  // The same tables in two halves (scanlines(), key lookup).  side_tables: what needs the sorted starts, the sorted keys
-  // and the group table only — the bucket indices of both spaces, kstart and the steps inside needed groups — on stream
-  // s, beside piece_values_kernel.  fill_tables: behind the values, one launch for kval and every fast entry.
+  // The tables of the key lookup in two halves (scanlines()): the step table in key space (scanline.h) has its starts by
+  // the sorted keys, and its entries inside needed groups answer kStepNeeded.  side_tables: what needs the sorted starts,
+  // the sorted keys and the group table only — the bucket indices of both spaces, kstart and the steps inside needed
+  // groups — on stream s, beside piece_values_kernel.  fill_tables: behind the values, one launch for kval and every fast
+  // entry.
   void side_tables(const uint32_t *pstart, int P, hipStream_t s) {
     const uint32_t *skeys = reinterpret_cast<const uint32_t *>(keys);
     hipLaunchKernelGGL(key_starts_kernel, dim3(cdiv(P, kBlock)), dim3(kBlock), 0, s, pstart, P, skeys, d_kstart, d_kneed);
@@ -1345,30 +1256,19 @@ struct LinearPath {
       hipLaunchKernelGGL(key_steps_flag_kernel, dim3(cdiv(n_groups, kBlock)), dim3(kBlock), 0, s, d_gfirst, d_gend,
                          static_cast<uint32_t>(n_groups), pstart, P, d_kneed);
     }
-    hipLaunchKernelGGL(piece_bucket_kernel, dim3(cdiv(nbuckets + 1, kBlock)), dim3(kBlock), 0, s, pstart, P, bucket_shift, nbuckets, d_bidx);
-    hipLaunchKernelGGL(piece_bucket_kernel, dim3(cdiv(nkbuckets + 1, kBlock)), dim3(kBlock), 0, s, d_kstart, P, key_shift, nkbuckets,
-                       d_kbidx);
-    if (bucket_shift_all != bucket_shift) {
-      hipLaunchKernelGGL(piece_bucket_kernel, dim3(cdiv(nbuckets_all + 1, kBlock)), dim3(kBlock), 0, s, pstart, P, bucket_shift_all,
-                         nbuckets_all, d_bidx_all);
-    }
-    if (key_shift_all != key_shift) {
-      hipLaunchKernelGGL(piece_bucket_kernel, dim3(cdiv(nkbuckets_all + 1, kBlock)), dim3(kBlock), 0, s, d_kstart, P, key_shift_all,
-                         nkbuckets_all, d_kbidx_all);
+    for (const BucketIndex &b : bix) {
+      if (b.planned) bucket_index(b, P, s);
     }
     WP_LAUNCH_CHECK();
   }
   void fill_tables(const uint32_t *pstart, int P) {
     StepFill fill{};
     unsigned most = static_cast<unsigned>(P);
-    auto add = [&](const uint32_t *bidx, int2 *bfast, unsigned nb, int keyed) {
-      fill.t[fill.count++] = StepFillTable{bidx, bfast, nb, keyed};
-      most = std::max(most, nb);
-    };
-    add(d_bidx, d_bfast, nbuckets, 0);
-    add(d_kbidx, d_kbfast, nkbuckets, 1);
-    if (bucket_shift_all != bucket_shift) add(d_bidx_all, d_bfast_all, nbuckets_all, 0);
-    if (key_shift_all != key_shift) add(d_kbidx_all, d_kbfast_all, nkbuckets_all, 1);
+    for (const BucketIndex &b : bix) {
+      if (!b.planned) continue;
+      fill.t[fill.count++] = StepFillTable{b.idx, b.fast, b.used, b.keyed ? 1 : 0};
+      most = std::max(most, b.used);
+    }
     hipLaunchKernelGGL(step_tables_kernel, dim3(cdiv(most, kBlock)), dim3(kBlock), 0, st, d_pval_p, d_pval_s, P, d_kneed, d_kval_p, d_kval_s,
                        fill);
 #ifdef WP_DEBUG_BOUNDS
@@ -1388,51 +1288,25 @@ struct LinearPath {
     hipLaunchKernelGGL(long_word_collect_kernel, dim3(std::min<size_t>(cdiv(std::max<size_t>(n_anchors, 1), kBlock), 2048)),
                        dim3(kBlock), 0, st, d_anchors, c->d_scalars + kScalarAnchors, n_text, d_cls, d_lw, lw_cap, c->d_scalars + kScalarLongWords);
     WP_LAUNCH_CHECK();
-    fetch_scalars(c, kScalarLongWords);
-    const uint32_t nw = std::min(c->h_scalars[kScalarLongWords], lw_cap);
-    if (nw == 0) return;
-    S.walk.n_long_words = static_cast<int64_t>(nw);
-    std::vector<LongWord> h_lw(nw);
-    WP_HIP(hipMemcpyAsync(h_lw.data(), d_lw, sizeof(LongWord) * nw, hipMemcpyDeviceToHost, st));
-    WP_HIP(hipStreamSynchronize(st));
-    std::vector<uint32_t> h_off(nw + 1);
-    uint64_t total64 = 0;
-    uint32_t longest = 0;
-    for (uint32_t i = 0; i < nw; i++) {
-      h_off[i] = static_cast<uint32_t>(total64);
-      total64 += h_lw[i].end - h_lw[i].begin;
-      longest = std::max(longest, h_lw[i].end - h_lw[i].begin);
-    }
-    h_off[nw] = static_cast<uint32_t>(total64);
-    const uint32_t total = static_cast<uint32_t>(total64);  // <= n_text < 2^31
-    WP_HIP(hipMemcpyAsync(d_lw_off, h_off.data(), sizeof(uint32_t) * (nw + 1), hipMemcpyHostToDevice, st));
-    WP_HIP(hipMemsetAsync(d_lw_fail, 0, sizeof(uint32_t) * nw, st));
+    const LongWordList lw = long_word_offsets(c, d_lw, lw_cap, d_lw_off, d_lw_fail, st);
+    if (lw.nw == 0) return;
+    S.walk.n_long_words = static_cast<int64_t>(lw.nw);
     int32_t *d_lid = reinterpret_cast<int32_t *>(VA);
     uint32_t *jump_a = X1, *jump_b = X0;
     uint8_t *d_mark = reinterpret_cast<uint8_t *>(KB);
-    const dim3 grid(cdiv(total, kBlock));
-    WalkArgs wa_all = wa;  // (every position of the long words is looked up: the small index)
-    wa_all.steps = steps_all;
-    wa_all.ksteps = ksteps_all;
-    hipLaunchKernelGGL(long_word_next_kernel, grid, dim3(kBlock), 0, st, wa_all, d_lw, d_lw_off, nw, total, d_lid, jump_a, d_mark);
-    WP_HIP(hipStreamSynchronize(st));  // h_off is a stack-owned upload source
-    for (uint32_t reach = 1; reach < longest; reach *= 2) {  // after r rounds: chain prefixes of length 2^r
-      hipLaunchKernelGGL(long_word_mark_kernel, grid, dim3(kBlock), 0, st, jump_a, total, d_mark);
-      hipLaunchKernelGGL(long_word_double_kernel, grid, dim3(kBlock), 0, st, jump_a, total, jump_b);
-      std::swap(jump_a, jump_b);
+    // (every position of the long words is looked up: the small index)
+    hipLaunchKernelGGL(long_word_next_kernel, lw.grid(), dim3(kBlock), 0, st, walk_args(true), d_lw, d_lw_off, lw.nw, lw.total, d_lid,
+                       jump_a, d_mark);
+    WP_HIP(hipStreamSynchronize(st));  // lw.h_off is an upload source
+    long_word_chains(lw, jump_a, jump_b, d_lid, d_mark, d_lw_off, d_lw_fail, st);
+    const bool offs = offs_unit >= 0;
+    uint32_t *d_lw_end = offs ? d_lw_fail + lw_cap : nullptr;
+    if (offs) {  // (the [UNK] of a failed word spans the word: up to its first blank)
+      WP_HIP(hipMemsetAsync(d_lw_end, 0xff, sizeof(uint32_t) * lw.nw, st));
+      hipLaunchKernelGGL(long_word_end_kernel, lw.grid(), dim3(kBlock), 0, st, d_lw, d_lw_off, lw.nw, lw.total, d_lid, d_lw_end);
     }
-    hipLaunchKernelGGL(long_word_mark_kernel, grid, dim3(kBlock), 0, st, jump_a, total, d_mark);
-    hipLaunchKernelGGL(long_word_fail_kernel, grid, dim3(kBlock), 0, st, d_lid, d_mark, d_lw_off, nw, total, d_lw_fail);
-    if (offs_unit >= 0) {  // (the [UNK] of a failed word spans the word: up to its first blank)
-      uint32_t *d_lw_end = d_lw_fail + lw_cap;
-      WP_HIP(hipMemsetAsync(d_lw_end, 0xff, sizeof(uint32_t) * nw, st));
-      hipLaunchKernelGGL(long_word_end_kernel, grid, dim3(kBlock), 0, st, d_lw, d_lw_off, nw, total, d_lid, d_lw_end);
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(long_word_emit_kernel<true>), grid, dim3(kBlock), 0, st, wa, d_lw, d_lw_off, nw, total, d_lid,
-                         d_mark, d_lw_fail, d_ospill, static_cast<const uint32_t *>(d_lw_end));
-    } else {
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(long_word_emit_kernel<false>), grid, dim3(kBlock), 0, st, wa, d_lw, d_lw_off, nw, total, d_lid,
-                         d_mark, d_lw_fail, static_cast<uint2 *>(nullptr), static_cast<const uint32_t *>(nullptr));
-    }
+    hipLaunchKernelGGL(offs ? long_word_emit_kernel<true> : long_word_emit_kernel<false>, lw.grid(), dim3(kBlock), 0, st, wa, d_lw,
+                       d_lw_off, lw.nw, lw.total, d_lid, d_mark, d_lw_fail, d_ospill, static_cast<const uint32_t *>(d_lw_end));
     WP_LAUNCH_CHECK();
     S.anchor_mode = 2;
   }
@@ -1468,10 +1342,11 @@ struct LinearPath {
 
   // ---- greedy walk + id stream (linear.cpp:215-316).  Slabs: round-0 keys KA (key_lookup), ids VB, id lists X0, wide
   // list / counts KB VA (VA / X1 hold the coverage rule's reach / flags; VA X1 X0 KB the long words' scratch) ----------
-  WalkArgs walk_args() const {
-    return WalkArgs{d_cls, n_text, d_rank, steps, c->d_tok_len, hv.unk_id, d_emit, nullptr, nullptr, nullptr,
+  // all: with the "_all" indexes, for a kernel that looks up every position of a stretch
+  WalkArgs walk_args(bool all = false) const {
+    return WalkArgs{d_cls, n_text, d_rank, tables[all ? kIxSlotAll : kIxSlot], c->d_tok_len, hv.unk_id, d_emit, nullptr, nullptr, nullptr,
                     hv.soft.empty() ? 1 : 0, static_cast<int32_t>(hv.tokens.size()),
-                    key_lookup ? reinterpret_cast<const uint32_t *>(KA) : nullptr, ksteps, drop_blanks ? 1 : 0};
+                    key_lookup ? reinterpret_cast<const uint32_t *>(KA) : nullptr, tables[all ? kIxKeyAll : kIxKey], drop_blanks ? 1 : 0};
   }
 
   // WP_OPT_KEEP_DEBUG = 2: what the walk's own lookup answers at every text position, behind the scanline stage and the
@@ -1524,57 +1399,29 @@ struct LinearPath {
         clear_scalars(c, kScalarWideWords, kScalarWideWords, st);
         hipLaunchKernelGGL(wide_collect_kernel, dim3(std::min<size_t>(cdiv(acap, kBlock), 2048)), dim3(kBlock), 0, st, d_anchors,
                            c->d_scalars + kScalarAnchors, n_text, d_wide_list, c->d_scalars + kScalarWideWords);
-        WalkArgs wa_all = wa;  // (every position of the wide words is looked up: the small index)
-        wa_all.steps = steps_all;
-        wa_all.ksteps = ksteps_all;
-        const dim3 wgrid(std::min<size_t>(cdiv(acap, kBlock / kWave), 8192));
-        if (offs) {
-          hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_wide_kernel<true>), wgrid, dim3(kBlock), 0, st, wa_all, d_anchors, c->d_scalars + kScalarAnchors,
-                             d_wide_list, c->d_scalars + kScalarWideWords, d_wide_cnt, d_ospill);
-          hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_lean_kernel<true, true>), dim3(sblocks), dim3(kBlock), 0, st, wa, d_anchors,
-                             c->d_scalars + kScalarAnchors, acap, d_ctmp, d_blk_cnt, d_wide_cnt, d_ospill, d_cspan);
-        } else {
-          hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_wide_kernel<false>), wgrid, dim3(kBlock), 0, st, wa_all, d_anchors, c->d_scalars + kScalarAnchors,
-                             d_wide_list, c->d_scalars + kScalarWideWords, d_wide_cnt, static_cast<uint2 *>(nullptr));
-          hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_lean_kernel<true, false>), dim3(sblocks), dim3(kBlock), 0, st, wa, d_anchors,
-                             c->d_scalars + kScalarAnchors, acap, d_ctmp, d_blk_cnt, d_wide_cnt, static_cast<uint2 *>(nullptr),
-                             static_cast<uint2 *>(nullptr));
-        }
-      } else if (offs) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_lean_kernel<false, true>), dim3(sblocks), dim3(kBlock), 0, st, wa, d_anchors,
-                           c->d_scalars + kScalarAnchors, acap, d_ctmp, d_blk_cnt, static_cast<const uint32_t *>(nullptr), d_ospill, d_cspan);
+        // (every position of the wide words is looked up: the small index)
+        hipLaunchKernelGGL(offs ? walk_wide_kernel<true> : walk_wide_kernel<false>, dim3(std::min<size_t>(cdiv(acap, kBlock / kWave), 8192)),
+                           dim3(kBlock), 0, st, walk_args(true), d_anchors, c->d_scalars + kScalarAnchors, d_wide_list,
+                           c->d_scalars + kScalarWideWords, d_wide_cnt, d_ospill);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(offs ? walk_lean_kernel<true, true> : walk_lean_kernel<true, false>), dim3(sblocks), dim3(kBlock),
+                           0, st, wa, d_anchors, c->d_scalars + kScalarAnchors, acap, d_ctmp, d_blk_cnt, d_wide_cnt, d_ospill, d_cspan);
       } else {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_lean_kernel<false, false>), dim3(sblocks), dim3(kBlock), 0, st, wa, d_anchors,
-                           c->d_scalars + kScalarAnchors, acap, d_ctmp, d_blk_cnt, static_cast<const uint32_t *>(nullptr),
-                           static_cast<uint2 *>(nullptr), static_cast<uint2 *>(nullptr));
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(offs ? walk_lean_kernel<false, true> : walk_lean_kernel<false, false>), dim3(sblocks),
+                           dim3(kBlock), 0, st, wa, d_anchors, c->d_scalars + kScalarAnchors, acap, d_ctmp, d_blk_cnt,
+                           static_cast<const uint32_t *>(nullptr), d_ospill, d_cspan);
       }
       device_exclusive_scan(d_blk_cnt, d_blk_off, sblocks, d_emit_tmp, c->d_scalars + kScalarIds, st);
-      if (offs) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(emit_gather_kernel<true>), dim3(sblocks), dim3(kBlock), 0, st, d_anchors, c->d_scalars + kScalarAnchors,
-                           acap, d_ctmp, d_blk_cnt, d_blk_off, d_ids, kWbWords, static_cast<const uint2 *>(d_cspan), d_offs);
-      } else {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(emit_gather_kernel<false>), dim3(sblocks), dim3(kBlock), 0, st, d_anchors, c->d_scalars + kScalarAnchors,
-                           acap, d_ctmp, d_blk_cnt, d_blk_off, d_ids, kWbWords, static_cast<const uint2 *>(nullptr),
-                           static_cast<uint2 *>(nullptr));
-      }
+      hipLaunchKernelGGL(offs ? emit_gather_kernel<true> : emit_gather_kernel<false>, dim3(sblocks), dim3(kBlock), 0, st, d_anchors,
+                         c->d_scalars + kScalarAnchors, acap, d_ctmp, d_blk_cnt, d_blk_off, d_ids, kWbWords,
+                         static_cast<const uint2 *>(d_cspan), d_offs);
     } else {
-      if (offs) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_kernel<true>), dim3(cdiv(acap, kBlock)), dim3(kBlock), 0, st, wa, d_anchors,
-                           c->d_scalars + kScalarAnchors, acap, d_ospill);
-      } else {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(walk_kernel<false>), dim3(cdiv(acap, kBlock)), dim3(kBlock), 0, st, wa, d_anchors,
-                           c->d_scalars + kScalarAnchors, acap, static_cast<uint2 *>(nullptr));
-      }
+      hipLaunchKernelGGL(offs ? walk_kernel<true> : walk_kernel<false>, dim3(cdiv(acap, kBlock)), dim3(kBlock), 0, st, wa, d_anchors,
+                         c->d_scalars + kScalarAnchors, acap, d_ospill);
       const unsigned tiles = cdiv(n_text, kScanTile);
       hipLaunchKernelGGL(emit_count_kernel, dim3(tiles), dim3(kBlock), 0, st, d_emit, n_text, d_emit_cnt);
       device_exclusive_scan(d_emit_cnt, d_emit_cnt, tiles, d_emit_tmp, c->d_scalars + kScalarIds, st);
-      if (offs) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(emit_write_kernel<true>), dim3(tiles), dim3(kBlock), 0, st, d_emit, n_text, d_emit_cnt, d_ids,
-                           static_cast<const uint2 *>(d_ospill), d_offs);
-      } else {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(emit_write_kernel<false>), dim3(tiles), dim3(kBlock), 0, st, d_emit, n_text, d_emit_cnt, d_ids,
-                           static_cast<const uint2 *>(nullptr), static_cast<uint2 *>(nullptr));
-      }
+      hipLaunchKernelGGL(offs ? emit_write_kernel<true> : emit_write_kernel<false>, dim3(tiles), dim3(kBlock), 0, st, d_emit, n_text,
+                         d_emit_cnt, d_ids, static_cast<const uint2 *>(d_ospill), d_offs);
     }
     S.staged_emit = staged ? 1 : 0;
     S.walk.lean = staged ? 1 : 0;  // (every list-building walk of this path is walk_lean_kernel)
@@ -1706,7 +1553,7 @@ struct LinearPath {
     c->dbg.sa = d_sa;
     c->dbg.rank = d_rank;
     c->dbg.lcp = d_lcp;
-    c->dbg.steps = steps;
+    c->dbg.steps = tables[kIxSlot];
     c->dbg.best_scratch = d_dbg_best;
     c->dbg.step_views = n_text > 0 ? d_step_views : nullptr;
     c->dbg.cps = d_cps;
@@ -1741,6 +1588,15 @@ struct LinearPath {
     finish(d_ids, n_ids_out);
   }
 };
+
+// the radix statistics of an encode start from zero, and again when the encode starts over (ListOverflow)
+static void reset_radix_stats(Context *c) {
+  c->rstats.passes = 0;
+  c->rstats.elems = 0;
+  c->rstats.digit_bytes = 0;
+  c->rstats.bytes = 0;
+  c->rstats.spans.used = 0;
+}
 
 // The whole device path on context c (the calling thread has c's device current).  d_text must be
 // 4-byte aligned and readable up to the next multiple of 16.  S: statistics of this call.
@@ -1788,12 +1644,8 @@ static void encode_on_device(const wp_vocab *v, Context *c, const uint8_t *d_tex
     if (offs_unit >= 0) nmap = &norm.map;
   }
 
-  c->rstats.passes = 0;
-  c->rstats.elems = 0;
-  c->rstats.digit_bytes = 0;
-  c->rstats.bytes = 0;
+  reset_radix_stats(c);
   c->rstats.spans.on = v->stage_timing;
-  c->rstats.spans.used = 0;
   if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[kMarkStart], st));
 
   // ---------------- phase A: decode ----------------
@@ -1881,15 +1733,14 @@ static void encode_on_device(const wp_vocab *v, Context *c, const uint8_t *d_tex
   if (v->stage_timing) WP_HIP(hipEventRecord(c->ev[kMarkCounted], st));
 
   const int bits = std::max(1, bit_length(sigma));  // symbols are 1..sigma, 0 = past the end
+  const DecodedText decoded{d_text, nbytes, d_tile_cnt, n_text, n, d_cps, d_cls, bits, text_only};
   for (int attempt = 0;; attempt++) {
     Arena ab(&c->b_buf, guard);
     try {
       if (sigma <= 255) {
-        LinearPath<uint8_t>(v, c, S, ab, aa, d_text, nbytes, d_tile_cnt, n_text, n, d_cps, d_cls, bits, text_only,
-                                 offs_unit, rows, nmap).run(n_ids_out);
+        LinearPath<uint8_t>(v, c, S, ab, aa, decoded, offs_unit, rows, nmap).run(n_ids_out);
       } else {
-        LinearPath<uint32_t>(v, c, S, ab, aa, d_text, nbytes, d_tile_cnt, n_text, n, d_cps, d_cls, bits, text_only,
-                                 offs_unit, rows, nmap).run(n_ids_out);
+        LinearPath<uint32_t>(v, c, S, ab, aa, decoded, offs_unit, rows, nmap).run(n_ids_out);
       }
       S.list_retries = attempt;
       return;
@@ -1900,16 +1751,10 @@ static void encode_on_device(const wp_vocab *v, Context *c, const uint8_t *d_tex
       WP_HIP(hipStreamSynchronize(c->stream));
       WP_HIP(hipStreamSynchronize(c->stream2));
       c->list_hint = o.wanted;
-      c->rstats.passes = 0;
-      c->rstats.elems = 0;
-      c->rstats.digit_bytes = 0;
-      c->rstats.bytes = 0;
-      c->rstats.spans.used = 0;
+      reset_radix_stats(c);
       clear_scalars(c, kScalarListEntries, kScalarWideWords, st);  // (list sizes, overflow flag, walk counters)
     }
   }
 }
 
 }  // namespace wp
-
-

@@ -435,6 +435,15 @@ __global__ __launch_bounds__(kBlock) void needed_fill_kernel(NeededList out, con
   }
 }
 
+// needed list longer than the room it was given: empty it (every later kernel reads its sizes on the device) and report
+__global__ void needed_list_clamp_kernel(uint32_t *__restrict__ totals, uint32_t cap, uint32_t *__restrict__ wanted) {
+  if (totals[0] > cap) {
+    *wanted = totals[0];
+    totals[0] = 0;
+    totals[1] = 0;
+  }
+}
+
 // group g of the list is [ghead[g], ghead[g+1]): the closing entry
 __global__ void needed_list_close_kernel(const uint32_t *__restrict__ totals, uint32_t *__restrict__ ghead) {
   ghead[totals[1]] = totals[0];

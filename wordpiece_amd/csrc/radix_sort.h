@@ -55,6 +55,65 @@ __device__ __forceinline__ bool key_is_blank(const uint32_t *tab, uint32_t key) 
   return ((tab[t >> 5] >> (t & 31u)) & 1u) != 0u;
 }
 
+#ifdef WP_DEBUG_BOUNDS
+// The sorted array of round 0 in the default layout (no debug view shows it, and the walk finds its steps by key value,
+// so the ids can be right over a wrong array), counted under kSiteSortOrder (linear_path.h, sort_round0):
+//   descents sorted[i] > sorted[i + 1];
+//   keys the blank table marks (blanks dropped: none may be left);
+//   the sorted array against the keys the sort had to keep of the unsorted array (which survives the sort), as multisets:
+//   count, wrapping sum and xor of each side.  Kept: every key where no blanks were dropped, else the positions whose
+//   class byte (written by the decode, not derived from the code) is no blank, and the terminal one.
+__device__ unsigned int g_wp_sorted_sig[6];  // count, sum, xor: the sorted array | the kept keys of the unsorted one
+__global__ __launch_bounds__(kBlock) void sorted_check_kernel(const uint32_t *__restrict__ sorted, size_t n_sorted,
+                                                              const uint32_t *__restrict__ unsorted, size_t n,
+                                                              const uint8_t *__restrict__ cls, size_t n_text,
+                                                              const uint32_t *__restrict__ blank_bits) {
+  __shared__ uint32_t acc[7];
+  if (threadIdx.x < 7) acc[threadIdx.x] = 0u;
+  __syncthreads();
+  uint32_t bad = 0, cnt[2] = {0, 0}, sum[2] = {0, 0}, x[2] = {0, 0};
+  const size_t first = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x, stride = static_cast<size_t>(gridDim.x) * kBlock;
+  for (size_t i = first; i < n_sorted; i += stride) {
+    const uint32_t k = sorted[i];
+    if (i + 1 < n_sorted && k > sorted[i + 1]) bad++;
+    if (blank_bits && key_is_blank(blank_bits, k)) bad++;
+    cnt[0]++;
+    sum[0] += k;
+    x[0] ^= k;
+  }
+  for (size_t i = first; i < n; i += stride) {
+    if (blank_bits && i < n_text && (cls[i] & kClsSpace)) continue;
+    const uint32_t k = unsorted[i];
+    cnt[1]++;
+    sum[1] += k;
+    x[1] ^= k;
+  }
+  if (bad) atomicAdd(&acc[6], bad);
+  for (int s = 0; s < 2; s++) {
+    if (cnt[s]) {
+      atomicAdd(&acc[3 * s], cnt[s]);
+      atomicAdd(&acc[3 * s + 1], sum[s]);
+      atomicXor(&acc[3 * s + 2], x[s]);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 6 && acc[threadIdx.x]) {
+    if (threadIdx.x % 3 == 2) {
+      atomicXor(&g_wp_sorted_sig[threadIdx.x], acc[threadIdx.x]);
+    } else {
+      atomicAdd(&g_wp_sorted_sig[threadIdx.x], acc[threadIdx.x]);
+    }
+  }
+  if (threadIdx.x == 6 && acc[6]) atomicAdd(&g_wp_oob[kSiteSortOrder], acc[6]);
+}
+__global__ void sorted_check_close_kernel() {
+  bool same = true;
+  for (int j = 0; j < 3; j++) same = same && g_wp_sorted_sig[j] == g_wp_sorted_sig[3 + j];
+  wp_in_bounds(same, kSiteSortOrder);
+  for (int j = 0; j < 6; j++) g_wp_sorted_sig[j] = 0u;
+}
+#endif
+
 // Lanes of the wave holding the same digit, as (mismatch_lo, mismatch_hi) complemented.  Per digit
 // bit: one ballot, and "my bit differs from lane l's bit" = ballot ^ sign-extended(my bit), OR-ed
 // into a per-lane mismatch mask (6 vector ops per bit).

@@ -601,17 +601,6 @@ __global__ __launch_bounds__(kBlock) void group_starts_kernel(const uint32_t *__
   gend[g] = e;
 }
 
-__global__ __launch_bounds__(kBlock) void key_steps_kernel(const uint32_t *__restrict__ pstart, const int32_t *__restrict__ pval_prefix,
-                                                           const int32_t *__restrict__ pval_suffix, int P,
-                                                           const uint32_t *__restrict__ sorted_keys, uint32_t *__restrict__ kstart,
-                                                           int32_t *__restrict__ kval_prefix, int32_t *__restrict__ kval_suffix) {
-  const int k = blockIdx.x * kBlock + threadIdx.x;
-  if (k >= P) return;
-  kstart[k] = k == 0 ? 0u : sorted_keys[pstart[k]];
-  kval_prefix[k] = pval_prefix[k];
-  kval_suffix[k] = pval_suffix[k];
-}
-
 // The tables behind the step values in one launch (key lookup).  Everything that does not read the values — the bucket
 // indices of both spaces, kstart, and which steps lie inside a needed group (key_starts_kernel, key_steps_flag_kernel) —
 // is built beside piece_values_kernel; this kernel then writes kval (the slot-space value, or kStepNeeded by the flag)
@@ -674,21 +663,8 @@ __device__ __forceinline__ int starts_lower_bound(const uint32_t *__restrict__ p
   return lo;
 }
 
-// the entries whose start lies inside a needed group answer kStepNeeded (one thread per group)
-__global__ __launch_bounds__(kBlock) void key_steps_needed_kernel(const uint32_t *__restrict__ gfirst,
-                                                                  const uint32_t *__restrict__ gend, uint32_t n_groups,
-                                                                  const uint32_t *__restrict__ pstart, int P,
-                                                                  int32_t *__restrict__ kval_prefix, int32_t *__restrict__ kval_suffix) {
-  const uint32_t g = blockIdx.x * kBlock + threadIdx.x;
-  if (g >= n_groups) return;
-  const int k0 = starts_lower_bound(pstart, P, gfirst[g]), k1 = starts_lower_bound(pstart, P, gend[g]);
-  for (int k = k0; k < k1; k++) {
-    kval_prefix[k] = kStepNeeded;
-    kval_suffix[k] = kStepNeeded;
-  }
-}
-
-// the same as a flag per step, for step_tables_kernel
+// the entries whose start lies inside a needed group answer kStepNeeded (one thread per group): a flag per step, for
+// step_tables_kernel
 __global__ __launch_bounds__(kBlock) void key_steps_flag_kernel(const uint32_t *__restrict__ gfirst, const uint32_t *__restrict__ gend,
                                                                 uint32_t n_groups, const uint32_t *__restrict__ pstart, int P,
                                                                 uint8_t *__restrict__ kneed) {

@@ -171,6 +171,9 @@ __global__ __launch_bounds__(kBlock) void trie_token_range_kernel(const uint32_t
   rng_hi[m] = lo;
 }
 
+// The same where the round ran in list space (the early refinement, linear_path.h: token_marks_kernel): node_of_entry[]
+// is indexed by list position, the token's group is [glo, glo + its size) of the list and its first slot is the rng_lo
+// the searches in the sorted keys left for its tokens.
 // [rng_lo, rng_hi): the slots of the token's group on entry, the token's own reach inside it on return; glo: the list
 // position of the group's first entry
 __device__ __forceinline__ void trie_token_range_in_list(const uint32_t *__restrict__ node_of_entry, uint32_t tok_node,
@@ -190,26 +193,6 @@ __device__ __forceinline__ void trie_token_range_in_list(const uint32_t *__restr
   }
   rng_lo = base + (first - glo);
   rng_hi = base + (lo - glo);
-}
-
-// The same where the round ran in list space (the early refinement, linear_path.h): node_of_entry[] is indexed by list
-// position, group g of the list is [ghead[g], ghead[g + 1]) and its first slot is the rng_lo the searches in the sorted
-// keys left for its tokens; tok_group: the group of a long token (kClaimNoGroup: none on the list, the range stays)
-__global__ __launch_bounds__(kBlock) void trie_token_range_list_kernel(const uint32_t *__restrict__ node_of_entry,
-                                                                       const uint32_t *__restrict__ tok_node,
-                                                                       const uint32_t *__restrict__ tok_subtree, int M,
-                                                                       uint32_t *__restrict__ rng_lo, uint32_t *__restrict__ rng_hi,
-                                                                       const uint8_t *__restrict__ rng_long,
-                                                                       const uint32_t *__restrict__ tok_group,
-                                                                       const uint32_t *__restrict__ ghead) {
-  const int m = blockIdx.x * kBlock + threadIdx.x;
-  if (m >= M || !rng_long[m]) return;
-  const uint32_t g = tok_group[m];
-  if (g == kClaimNoGroup) return;
-  uint32_t lo = rng_lo[m], hi = rng_hi[m];
-  trie_token_range_in_list(node_of_entry, tok_node[m], tok_subtree[m], ghead[g], lo, hi);
-  rng_lo[m] = lo;
-  rng_hi[m] = hi;
 }
 
 }  // namespace wp

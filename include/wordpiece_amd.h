@@ -361,6 +361,56 @@ int wp_pack_sequences_device(wp_vocab *v, const int32_t *d_ids, const int64_t *d
 typedef struct { int64_t n_docs, n_empty, n_cut, n_ids_cut, n_pieces, n_out, n_cells, n_segments; } wp_pack_stats;
 int wp_get_pack_stats(const wp_vocab *v, wp_pack_stats *out); /* n_docs == -1: no such call yet */
 
+/* ---- special tokens (an addition: HF tokenizer.add_special_tokens / all_special_ids — BertTokenizer with
+ * split_special_tokens=False keeps "[MASK]", "[SEP]" ... in a text whole) ----
+ * The encoder itself never matches a vocabulary line of the form "[...]" (utils.cpp:143-146): "[CLS] a" gives "[", "CLS",
+ * "]", "a".  These calls take a list of such lines' ids and keep every listed line that stands in the text as its id, the
+ * way that tokenizer does: the text is cut at them before anything else (before WP_OPT_NORMALIZE too: "[mask]" is
+ * ordinary text), so "foo[MASK]bar" gives foo, [MASK], bar.
+ * Eligible ids.  An id may be listed when it is in range, bit 1 of wp_vocab_token_flags is set (special) and bit 2 is
+ * clear (malformed), its line has at most 64 bytes, every byte of it is in 0x21..0x7E, and '[' is its first byte only
+ * and ']' its last byte only.  Any other id, and two listed ids with the same line, fail with WP_ERR_ARG and a message
+ * that names the id; the same id twice is fine.  n_ids is in [0, 4096]; ids is host memory in every entry point.
+ * Literals.  At a byte '[' of the caller's text take the bytes up to and including the next ']'.  They are a literal when
+ * they lie inside nbytes, number at most 64, hold only bytes 0x21..0x7E with no further '[', and equal a listed line.  So
+ * the candidate at a '[' is decided by the text alone, and two literals never overlap ("[[MASK]]" holds one, at byte 1).
+ * Result.  That of wp_linear_encode_offsets on the text with every literal's bytes set to 0x20, with (id, [start, end))
+ * of every literal merged in by position; start and end in `unit` — bytes, or code points, of the caller's text.  unit
+ * -1: only the ids come back (offsets may be NULL).  No span of the inner encode covers a blanked byte, so positions are
+ * distinct and offsets keep referring to the caller's text.  WP_OPT_NORMALIZE applies to the blanked text only.
+ * Documents form.  Rows as wp_linear_encode_rows takes them (explicit rows or lines; both routes; empty rows; the row
+ * rules under WP_OPT_NORMALIZE).  Row i and its document-relative offsets are the flat call on document i.
+ * A text without a literal gives exactly the plain call's result (wp_linear_encode_offsets / wp_linear_encode_rows), and
+ * so does n_ids == 0 in the spec.  Buffers, ownership and the order of errors are those of the offsets and rows calls:
+ * the host forms report every argument error before a device is touched, and need no device for an empty text; without
+ * a device the result is WP_ERR_NO_DEVICE.  nbytes > UINT32_MAX fails with WP_ERR_TOO_LARGE in every unit.
+ * On the device (csrc/special.h): one pass over the text finds the literals (one table lookup per '[', a bisection over
+ * the sorted lines), the count comes to the host, and with none the plain path runs on the caller's buffer.  Else the
+ * text is copied and blanked, encoded through the offsets or rows path as it stands, and one pass per literal and one
+ * over the ids put the literals in. */
+typedef struct { const int32_t *ids; int32_t n_ids; } wp_special_spec;   /* host memory, n_ids in [0, 4096] */
+/* host text in; ids and offsets out as blocks (free each with wp_free; NULL when n_ids == 0, offsets NULL when unit == -1) */
+int wp_linear_encode_special(wp_vocab *v, const char *utf8, size_t nbytes, const wp_special_spec *spec, int unit,
+                             int32_t **ids, uint32_t **offsets, size_t *n_ids);
+/* device text (buffer contract of wp_linear_encode_device); the results stay there, owned by the handle until its next call */
+int wp_linear_encode_special_device(wp_vocab *v, const void *d_utf8, size_t nbytes, const wp_special_spec *spec, int unit,
+                                    const int32_t **d_ids, const uint32_t **d_offsets, size_t *n_ids);
+/* the documents form: arguments and blocks of wp_linear_encode_rows, plus the spec */
+int wp_linear_encode_special_rows(wp_vocab *v, const char *utf8, size_t nbytes, const int64_t *doc_off, size_t n_docs,
+                                  const wp_special_spec *spec, int unit, int32_t **ids, int64_t **row_splits,
+                                  uint32_t **offsets, size_t *n_ids, size_t *n_rows);
+/* ... of wp_linear_encode_rows_device, plus the spec */
+int wp_linear_encode_special_rows_device(wp_vocab *v, const void *d_utf8, size_t nbytes, const int64_t *d_doc_off,
+                                         size_t n_docs, const wp_special_spec *spec, int unit, const int32_t **d_ids,
+                                         const int64_t **d_row_splits, const uint32_t **d_offsets, size_t *n_ids,
+                                         size_t *n_rows);
+/* The statistics of the last special-tokens call, in a struct of its own (wp_stats keeps its size): the literals found,
+ * the ids of the result (literals included), its rows (-1: the flat form) and the entries of the spec.  wp_stats and its
+ * kin hold what the inner encode left, with n_ids and offsets_unit those of the call.  Any other encode on the handle
+ * starts these statistics over. */
+typedef struct { int64_t n_literals, n_ids, n_rows, n_listed; } wp_special_stats;
+int wp_get_special_stats(const wp_vocab *v, wp_special_stats *out); /* n_literals == -1: no such call yet, or another encode since */
+
 /* The same call sharded over several GPUs of the node, behind the boundary: the reference's own
  * precedent is the in-library chunking at whitespace of linear.cpp:283-299 (thread chunks) and
  * linear.cpp:355-367 (encodeExternal batches).  The text is cut at ASCII whitespace into one shard

@@ -56,6 +56,8 @@ ABI_SYMBOLS = [
     "wp_word_ids", "wp_word_ids_device", "wp_mlm_mask", "wp_mlm_mask_device", "wp_get_mask_stats",
     "wp_detokenize", "wp_detokenize_device", "wp_detok_piece", "wp_get_detok_stats",
     "wp_pack_sequences", "wp_pack_sequences_device", "wp_get_pack_stats",
+    "wp_linear_encode_special", "wp_linear_encode_special_device", "wp_linear_encode_special_rows",
+    "wp_linear_encode_special_rows_device", "wp_get_special_stats",
 ]
 
 
@@ -181,6 +183,16 @@ class PackStats(C.Structure):
                 ("n_pieces", C.c_int64), ("n_out", C.c_int64), ("n_cells", C.c_int64), ("n_segments", C.c_int64)]
 
 
+class SpecialSpec(C.Structure):
+    """wp_special_spec: the listed ids of a special-tokens call (host memory)."""
+    _fields_ = [("ids", C.POINTER(C.c_int32)), ("n_ids", C.c_int32)]
+
+
+class SpecialStats(C.Structure):
+    """wp_special_stats: the statistics of the last special-tokens call (Vocab.special_stats())."""
+    _fields_ = [("n_literals", C.c_int64), ("n_ids", C.c_int64), ("n_rows", C.c_int64), ("n_listed", C.c_int64)]
+
+
 _TEXT_SOURCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t))
 _IDS_SINK = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.c_size_t)
 
@@ -249,6 +261,19 @@ def lib():
             L.wp_pack_sequences_device.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(PackSpec), C.POINTER(Packed), C.c_size_t,
                                                    C.POINTER(C.c_size_t)]
             L.wp_get_pack_stats.argtypes = [vp, C.POINTER(PackStats)]
+        if hasattr(L, "wp_linear_encode_special"):  # (WP_LIB, as above)
+            sp = C.POINTER(SpecialSpec)
+            L.wp_linear_encode_special.argtypes = [vp, C.c_char_p, C.c_size_t, sp, C.c_int, C.POINTER(i32p), C.POINTER(u32p),
+                                                   C.POINTER(C.c_size_t)]
+            L.wp_linear_encode_special_device.argtypes = [vp, vp, C.c_size_t, sp, C.c_int, C.POINTER(vp), C.POINTER(vp),
+                                                          C.POINTER(C.c_size_t)]
+            L.wp_linear_encode_special_rows.argtypes = [vp, C.c_char_p, C.c_size_t, i64p, C.c_size_t, sp, C.c_int, C.POINTER(i32p),
+                                                        C.POINTER(i64p), C.POINTER(u32p), C.POINTER(C.c_size_t),
+                                                        C.POINTER(C.c_size_t)]
+            L.wp_linear_encode_special_rows_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, sp, C.c_int, C.POINTER(vp),
+                                                               C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t),
+                                                               C.POINTER(C.c_size_t)]
+            L.wp_get_special_stats.argtypes = [vp, C.POINTER(SpecialStats)]
         L.wp_linear_encode_multi.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.POINTER(i32p),
                                              C.POINTER(C.c_size_t)]
         L.wp_reserve.argtypes = [vp, C.c_size_t]
@@ -949,6 +974,113 @@ class Vocab:
         ids, splits = self.encode_rows_tensor(text, doc_offsets, copy=False)
         return self.pack_sequences_tensor(ids, splits, max_len=max_len, mode=mode, bos_id=bos_id, eos_id=eos_id, pad_id=pad_id,
                                           long_docs=long_docs, want=want, n_out=n_out)
+
+    def special_stats(self):
+        """wp_special_stats of the last special-tokens call as a dict (n_literals -1: no such call yet)."""
+        s = SpecialStats()
+        _check(lib().wp_get_special_stats(self._h, C.byref(s)))
+        return {k: int(getattr(s, k)) for k, _ in s._fields_}
+
+    def special_ids(self, tokens=None):
+        """Strings -> ids for the special_ids= of the encode_special calls.  tokens=None: every line that may be listed
+        (a "[...]" line the vocabulary flags as special, at most 64 bytes of 0x21..0x7E, no further bracket), the first
+        copy of a line that repeats.  A string that is no such line raises."""
+        table = getattr(self, "_special_lines", None)
+        if table is None:
+            table = {}
+            for i in range(len(self)):
+                if (self.token_flags(i) & 6) == 2:
+                    w = self.token_utf8(i)
+                    if len(w) <= 64 and all(0x21 <= c <= 0x7E for c in w) and b"[" not in w[1:] and b"]" not in w[:-1]:
+                        table.setdefault(w, i)
+            self._special_lines = table
+        if tokens is None:
+            return sorted(table.values())
+        out = []
+        for t in tokens:
+            if _bytes(t) not in table:
+                raise WordPieceError("%r is no special token of the vocabulary that can be listed" % (t,))
+            out.append(table[_bytes(t)])
+        return out
+
+    def _special_spec(self, special_ids):
+        """-> (wp_special_spec, the array it points into)"""
+        a = np.ascontiguousarray(self.special_ids() if special_ids is None else special_ids, dtype=np.int32)
+        if a.ndim != 1:
+            raise WordPieceError("special_ids must be a 1-d sequence of ids")
+        return SpecialSpec(_i32_ptr(a) if len(a) else None, len(a)), a
+
+    def encode_special(self, text, special_ids=None, offsets=None):
+        """encode / encode_with_offsets that keeps special-token literals whole (wp_linear_encode_special): every listed
+        line ("[MASK]", "[SEP]" ...) that stands in the text becomes its id, as HF's BertTokenizer does it; everything
+        else is encoded as if the literal were blanks.  special_ids: ids (Vocab.special_ids(["[MASK]"])); None: every
+        line that may be listed.  -> ids int32 [n], or with offsets="byte" / "char" (ids, offsets uint32 [n, 2])."""
+        b = _bytes(text)
+        spec, keep = self._special_spec(special_ids)
+        unit = -1 if offsets is None else _offset_unit(offsets)
+        ids, offs, n = C.POINTER(C.c_int32)(), C.POINTER(C.c_uint32)(), C.c_size_t()
+        _check(lib().wp_linear_encode_special(self._h, b, len(b), C.byref(spec), unit, C.byref(ids), C.byref(offs), C.byref(n)))
+        if offsets is None:
+            return _adopt_ids(ids, n.value)
+        return _adopt_ids(ids, n.value), (_adopt_block(offs, (n.value, 2)) if n.value else np.zeros((0, 2), dtype=np.uint32))
+
+    def encode_special_rows(self, docs=None, text=None, doc_offsets=None, special_ids=None, offsets=None):
+        """encode_rows that keeps special-token literals whole (wp_linear_encode_special_rows): row i is
+        encode_special(document i).  Documents and results as in encode_rows, special_ids as in encode_special."""
+        b, off = _docs_arg(docs, text, doc_offsets)
+        spec, keep = self._special_spec(special_ids)
+        unit = -1 if offsets is None else _offset_unit(offsets)
+        ids, splits, offs = C.POINTER(C.c_int32)(), C.POINTER(C.c_int64)(), C.POINTER(C.c_uint32)()
+        n, rows = C.c_size_t(), C.c_size_t()
+        _check(lib().wp_linear_encode_special_rows(self._h, b, len(b), _i64_ptr(off), 0 if off is None else len(off) - 1,
+                                                   C.byref(spec), unit, C.byref(ids), C.byref(splits), C.byref(offs), C.byref(n),
+                                                   C.byref(rows)))
+        out = (_adopt_ids(ids, n.value), _adopt_block(splits, (rows.value + 1,)))
+        if offsets is None:
+            return out
+        return out + (_adopt_block(offs, (n.value, 2)) if n.value else np.zeros((0, 2), dtype=np.uint32),)
+
+    def encode_special_tensor(self, text, special_ids=None, offsets=None, copy=True):
+        """encode_special for a uint8 text tensor on this handle's GPU (wp_linear_encode_special_device) -> ids int32 [n]
+        there, or (ids, offsets uint32 [n, 2]).  copy=False: views of the library's buffers, valid until the next call."""
+        import torch
+        text, nbytes, _ = self._rows_tensor_args(text, None)
+        spec, keep = self._special_spec(special_ids)
+        unit = -1 if offsets is None else _offset_unit(offsets)
+        d_ids, d_offs, n = C.c_void_p(), C.c_void_p(), C.c_size_t()
+        _check(lib().wp_linear_encode_special_device(self._h, C.c_void_p(text.data_ptr()), nbytes, C.byref(spec), unit,
+                                                     C.byref(d_ids), C.byref(d_offs), C.byref(n)))
+        dev = text.device
+        ids = torch.as_tensor(DeviceIds(d_ids.value, n.value), device=dev) if n.value else torch.zeros(0, dtype=torch.int32, device=dev)
+        if offsets is None:
+            return ids.clone() if copy else ids
+        offs = torch.as_tensor(DeviceIds(d_offs.value, n.value, cols=2), device=dev).view(torch.uint32) if n.value else \
+            torch.zeros((0, 2), dtype=torch.uint32, device=dev)
+        return (ids.clone(), offs.clone()) if copy else (ids, offs)
+
+    def encode_special_rows_tensor(self, text, doc_offsets=None, special_ids=None, offsets=None, copy=True):
+        """encode_special_rows for tensors on this handle's GPU (wp_linear_encode_special_rows_device): arguments and
+        results of encode_rows_tensor, special_ids as in encode_special.  The result feeds pack_sequences_tensor,
+        detokenize_tensor and, once padded, mask_inputs_tensor without leaving the device."""
+        import torch
+        text, nbytes, doc_offsets = self._rows_tensor_args(text, doc_offsets)
+        spec, keep = self._special_spec(special_ids)
+        unit = -1 if offsets is None else _offset_unit(offsets)
+        d_ids, d_splits, d_offs = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        n, rows = C.c_size_t(), C.c_size_t()
+        _check(lib().wp_linear_encode_special_rows_device(
+            self._h, C.c_void_p(text.data_ptr()), nbytes, None if doc_offsets is None else C.c_void_p(doc_offsets.data_ptr()),
+            0 if doc_offsets is None else doc_offsets.numel() - 1, C.byref(spec), unit, C.byref(d_ids), C.byref(d_splits),
+            C.byref(d_offs), C.byref(n), C.byref(rows)))
+        dev = text.device
+        ids = torch.as_tensor(DeviceIds(d_ids.value, n.value), device=dev) if n.value else \
+            torch.zeros(0, dtype=torch.int32, device=dev)
+        splits = torch.as_tensor(DeviceIds(d_splits.value, rows.value + 1, typestr="<i8"), device=dev)
+        out = (ids, splits)
+        if offsets is not None:
+            out += (torch.as_tensor(DeviceIds(d_offs.value, n.value, cols=2), device=dev).view(torch.uint32) if n.value else
+                    torch.zeros((0, 2), dtype=torch.uint32, device=dev),)
+        return tuple(t.clone() for t in out) if copy else out
 
     def fast_encode(self, text):
         """word_piece::fast::encode on the GPU (wp_fast_encode): host bytes/str -> numpy int32 ids."""

@@ -50,7 +50,8 @@ enum BoundSite {
   kSiteMask = 10,   // masking: the lookup of an id's class byte (mask.h)
   kSiteDetok = 11,  // detokenize: the record gather, the pool gather and the store of the text (detok.h)
   kSitePack = 12,   // packing: the gather from the ids, the stores of the batch and of the row starts (packing.h)
-  kBoundSites = 13
+  kSiteSpecial = 13,  // special tokens: the stores of the literal list and of the blanks, the rows and the gather of the merge (special.h)
+  kBoundSites = 14
 };
 #ifdef WP_DEBUG_BOUNDS
 __device__ unsigned int g_wp_oob[kBoundSites];

@@ -1,6 +1,6 @@
 // context.h — what a vocabulary handle owns on a device: streams, vocabulary tables, bump arenas, the pool of parked
 // contexts (the C ABI itself is in encoder.hip; the device path in linear_path.h and fast_path.h, the layers on top of
-// it in rows_path.h, inputs_path.h, mask_path.h, detok_path.h and pack_path.h).
+// it in rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h and special_path.h).
 #pragma once
 #include <array>
 #include <cstring>
@@ -15,6 +15,7 @@
 #include "detok.h"
 #include "packing.h"
 #include "radix_sort.h"
+#include "special.h"
 #include "scanline.h"
 #include "suffix_array.h"
 #include "vocab.h"
@@ -186,7 +187,7 @@ constexpr int kScalarKept = 25;  // d_scalars word: suffixes the keys-only round
 constexpr int kScalarSrcRows = 26;  // lines of the caller's text in a documents call on normalised text (normalize.h)
 // model inputs (inputs.h): samples that lost ids / the number of output rows, 64 bits (words 28, 29) / samples with windows
 constexpr int kScalarInCut = 27, kScalarInRows = 28, kScalarInWindowed = 30;
-constexpr int kScalarFree31 = 31;  // free
+constexpr int kScalarSpecial = 31;  // special tokens (special.h): the literals of the text, the total of their scan -> host
 constexpr int kScalarMask = 32;    // d_scalars words 32..43: the six 64-bit counters of a mask call (mask.h, MaskCounter)
 // detokenize (detok.h): the last entry of row_splits given in device memory, 64 bits (words 44, 45) / its violations
 constexpr int kScalarDetokLast = 44, kScalarDetokBad = 46;
@@ -214,7 +215,7 @@ constexpr ScalarRange kScalarLayout[] = {
     {kScalarWideWords, 1},   {kScalarCps64, 2},      {kScalarGuardBad, 1},        {kScalarGuardFirst, 1},
     {kScalarSplitTotals, 2},      {kScalarAlphaWord0, 1}, {kScalarRows, 1},            {kScalarRowsBad, 1},
     {kScalarRowsCut, 1},     {kScalarCand, 1},       {kScalarKept, 1},            {kScalarSrcRows, 1},
-    {kScalarInCut, 1},       {kScalarInRows, 2},     {kScalarInWindowed, 1},      {kScalarFree31, 1},
+    {kScalarInCut, 1},       {kScalarInRows, 2},     {kScalarInWindowed, 1},      {kScalarSpecial, 1},
     {kScalarMask, 12},       {kScalarDetokLast, 2},  {kScalarDetokBad, 1},        {kScalarFree47, 1},
     {kScalarDetok, 8},       {kScalarPackLast, 2},   {kScalarPackBad, 1},         {kScalarFree59, 1},
     {kScalarPack, 16}};
@@ -312,6 +313,9 @@ struct Context {
   // packing (packing.h): ids and row_splits of a host call, the per-document plan, the per-piece tables and row starts,
   // the batch of a host call
   DeviceBuffer pack_in, pack_plan, pack_tab, pack_out;
+  // special tokens (special.h): the blanked copy of the text, the listed lines and the tile counts of the match, the
+  // literal list, and the merged result with the tables its placement needs
+  DeviceBuffer special_text, special_in, special_lit, special_out;
   // WP_OPT_NORMALIZE (normalize.h): the tables (uploaded with the first normalising call), the normalised text, the
   // tile counts of the pre-pass, and the source of every normalised code point (offsets mode)
   uint16_t *d_norm_index = nullptr;
@@ -355,10 +359,10 @@ struct Context {
     size_t n = 0, n_text = 0;
   } dbg;
   // every DeviceBuffer above, for destroy_context, release_arenas and park_context: a new buffer is one more name here
-  std::array<DeviceBuffer *, 21> buffers() {
+  std::array<DeviceBuffer *, 25> buffers() {
     return {&text_buf, &a_buf,    &b_buf,   &fmt_buf,    &text_buf2, &ids_stage[0], &ids_stage[1], &rows_in,   &rows_out,
             &pad_buf,  &inputs_buf, &norm_buf, &norm_aux, &norm_map, &detok_in,     &detok_aux,    &detok_out,
-            &pack_in,  &pack_plan,  &pack_tab, &pack_out};
+            &pack_in,  &pack_plan,  &pack_tab, &pack_out, &special_text, &special_in, &special_lit, &special_out};
   }
   Context() = default;
   Context(const Context &) = delete;
@@ -424,6 +428,8 @@ struct EncodeStats : wp_stats {
   int32_t detok_call;
   wp_pack_stats pack;  // wp_get_pack_stats: filled by a pack call (pack_call 1), zero otherwise
   int32_t pack_call;
+  wp_special_stats special;  // wp_get_special_stats: filled by a special-tokens call (special_call 1), zero otherwise
+  int32_t special_call;
 };
 
 #ifndef WP_LATE_REFINE_DEFAULT

@@ -29,6 +29,7 @@
 #include "mask_path.h"
 #include "pack_path.h"
 #include "rows_path.h"
+#include "special_path.h"
 
 
 wp_vocab::~wp_vocab() {
@@ -1115,6 +1116,148 @@ int wp_pack_sequences_device(wp_vocab *v, const int32_t *d_ids, const int64_t *d
       }
       return o;
     });
+  });
+}
+
+}  // extern "C"
+
+// ---- special tokens (include/wordpiece_amd.h, section "special tokens"; host path: special_path.h) -------------------
+extern "C" {
+
+int wp_get_special_stats(const wp_vocab *v, wp_special_stats *out) {
+  *out = v->stats.special;
+  if (!v->stats.special_call) out->n_literals = -1;
+  return WP_OK;
+}
+
+int wp_linear_encode_special(wp_vocab *v, const char *utf8, size_t nbytes, const wp_special_spec *spec, int unit, int32_t **ids,
+                             uint32_t **offsets, size_t *n_ids) {
+  return guarded([&] {
+    *ids = nullptr;
+    if (offsets) *offsets = nullptr;
+    *n_ids = 0;
+    check_special_call(unit, nbytes);
+    if (unit >= 0 && !offsets) throw std::invalid_argument("offsets asked for without a place to return them");
+    const SpecialList list = check_special_spec(v, spec);
+    if (nbytes == 0) {  // (no device needed, as wp_linear_encode_offsets)
+      set_special_stats(v, list, 0, 0, false, 0);
+      return;
+    }
+    const auto t_all = wp_clock::now();
+    Context *c = get_context(v);
+    upload_text(c, utf8, nbytes);
+    RowsResult r;
+    special_on_device(v, c, static_cast<const uint8_t *>(c->text_buf.p), nbytes, false, nullptr, 0, unit, SIZE_MAX, list, r);
+    const auto t0 = wp_clock::now();
+    if (r.n_ids) {
+      Downloads down(c->stream);
+      down.add(ids, r.d_ids, r.n_ids * sizeof(int32_t));
+      if (unit >= 0) down.add(offsets, r.d_offs, r.n_ids * 2 * sizeof(uint32_t));
+      down.finish();
+      *n_ids = r.n_ids;
+    }
+    v->stats.ms_d2h = ms_since(t0);
+    v->stats.ms_host_total = ms_since(t_all);
+  });
+}
+
+int wp_linear_encode_special_device(wp_vocab *v, const void *d_utf8, size_t nbytes, const wp_special_spec *spec, int unit,
+                                    const int32_t **d_ids, const uint32_t **d_offsets, size_t *n_ids) {
+  return guarded([&] {
+    *d_ids = nullptr;
+    if (d_offsets) *d_offsets = nullptr;
+    *n_ids = 0;
+    check_special_call(unit, nbytes);
+    if (unit >= 0 && !d_offsets) throw std::invalid_argument("offsets asked for without a place to return them");
+    const SpecialList list = check_special_spec(v, spec);
+    if (nbytes == 0) {
+      set_special_stats(v, list, 0, 0, false, 0);
+      return;
+    }
+    check_device_text(d_utf8);
+    RowsResult r;
+    special_on_device(v, get_context(v), static_cast<const uint8_t *>(d_utf8), nbytes, false, nullptr, 0, unit, SIZE_MAX, list, r);
+    *d_ids = r.d_ids;
+    if (d_offsets) *d_offsets = r.d_offs;
+    *n_ids = r.n_ids;
+  });
+}
+
+int wp_linear_encode_special_rows(wp_vocab *v, const char *utf8, size_t nbytes, const int64_t *doc_off, size_t n_docs,
+                                  const wp_special_spec *spec, int unit, int32_t **ids, int64_t **row_splits, uint32_t **offsets,
+                                  size_t *n_ids, size_t *n_rows) {
+  return guarded([&] {
+    *ids = nullptr;
+    *row_splits = nullptr;
+    if (offsets) *offsets = nullptr;
+    *n_ids = 0;
+    *n_rows = 0;
+    check_special_call(unit, nbytes);
+    if (unit >= 0 && !offsets) throw std::invalid_argument("offsets asked for without a place to return them");
+    if (doc_off) check_doc_off_host(utf8, nbytes, doc_off, n_docs);
+    const SpecialList list = check_special_spec(v, spec);
+    if (nbytes == 0 || (doc_off && nbytes == n_docs)) {  // no text, or empty documents only: no device needed
+      const size_t rows = doc_off ? n_docs : 0;
+      *row_splits = static_cast<int64_t *>(zeroed((rows + 1) * sizeof(int64_t)));
+      *n_rows = rows;
+      set_special_stats(v, list, 0, 0, true, rows);
+      return;
+    }
+    const auto t_all = wp_clock::now();
+    Context *c = get_context(v);
+    upload_text(c, utf8, nbytes);
+    if (doc_off) {
+      c->rows_in.ensure((n_docs + 1) * sizeof(int64_t));
+      WP_HIP(hipMemcpyAsync(c->rows_in.p, doc_off, (n_docs + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    }
+    RowsResult r;
+    special_rows_on_device(v, c, static_cast<const uint8_t *>(c->text_buf.p), nbytes,
+                           doc_off ? static_cast<const long long *>(c->rows_in.p) : nullptr, n_docs, unit, SIZE_MAX, list, r);
+    const auto t0 = wp_clock::now();
+    Downloads down(c->stream);
+    down.add(row_splits, r.d_row_splits, (r.n_rows + 1) * sizeof(int64_t));
+    if (r.n_ids) down.add(ids, r.d_ids, r.n_ids * sizeof(int32_t));
+    if (r.n_ids && unit >= 0) down.add(offsets, r.d_offs, r.n_ids * 2 * sizeof(uint32_t));
+    down.finish();
+    *n_ids = r.n_ids;
+    *n_rows = r.n_rows;
+    v->stats.ms_d2h = ms_since(t0);
+    v->stats.ms_host_total = ms_since(t_all);
+  });
+}
+
+int wp_linear_encode_special_rows_device(wp_vocab *v, const void *d_utf8, size_t nbytes, const int64_t *d_doc_off, size_t n_docs,
+                                         const wp_special_spec *spec, int unit, const int32_t **d_ids, const int64_t **d_row_splits,
+                                         const uint32_t **d_offsets, size_t *n_ids, size_t *n_rows) {
+  return guarded([&] {
+    *d_ids = nullptr;
+    *d_row_splits = nullptr;
+    if (d_offsets) *d_offsets = nullptr;
+    *n_ids = 0;
+    *n_rows = 0;
+    check_special_call(unit, nbytes);
+    if (unit >= 0 && !d_offsets) throw std::invalid_argument("offsets asked for without a place to return them");
+    const SpecialList list = check_special_spec(v, spec);
+    check_device_text(d_utf8);
+    check_device_doc_off(d_doc_off);
+    Context *c = get_context(v);
+    if (nbytes == 0) {  // no text: no rows (explicit rows cannot end at 0 unless there are none)
+      check_doc_off_without_text(d_doc_off, n_docs);
+      c->special_out.ensure(sizeof(int64_t));
+      WP_HIP(hipMemsetAsync(c->special_out.p, 0, sizeof(int64_t), c->stream));
+      WP_HIP(hipStreamSynchronize(c->stream));
+      *d_row_splits = static_cast<const int64_t *>(c->special_out.p);
+      set_special_stats(v, list, 0, 0, true, 0);
+      return;
+    }
+    RowsResult r;
+    special_rows_on_device(v, c, static_cast<const uint8_t *>(d_utf8), nbytes, reinterpret_cast<const long long *>(d_doc_off), n_docs, unit,
+                           SIZE_MAX, list, r);
+    *d_ids = r.d_ids;
+    *d_row_splits = reinterpret_cast<const int64_t *>(r.d_row_splits);
+    if (d_offsets) *d_offsets = r.d_offs;
+    *n_ids = r.n_ids;
+    *n_rows = r.n_rows;
   });
 }
 

@@ -411,6 +411,78 @@ int wp_linear_encode_special_rows_device(wp_vocab *v, const void *d_utf8, size_t
 typedef struct { int64_t n_literals, n_ids, n_rows, n_listed; } wp_special_stats;
 int wp_get_special_stats(const wp_vocab *v, wp_special_stats *out); /* n_literals == -1: no such call yet, or another encode since */
 
+/* ---- span alignment (an addition: the label side of a fine-tuning batch — HF course preprocess_training_examples for
+ * extractive QA, align_labels_with_tokens / Encoding.char_to_token for token classification) ----
+ * Labelled character spans in, per-cell labels and per-row answer positions out, for a batch whose offsets are already
+ * there: no encode runs and no vocabulary is read.
+ * Spans, ragged per sample: span_splits[0 .. n_samples] (int64; [0] == 0, never descends, [n_samples] == n_spans),
+ * spans[n_spans][2] (uint32, [begin, end)) and span_labels[n_spans] (int32).  Spans are in the unit and frame of the
+ * batch's offsets (relative to the document they label; bytes or code points: the call does not know which).  Within a
+ * sample they are non-empty, sorted and disjoint: begin < end, and end[j] <= begin[j + 1].
+ * Padded form.  offsets[n_rows][max_len][2], token_type_ids[n_rows][max_len] (NULL: all 0), lengths[n_rows] (NULL:
+ * max_len; a given length is clamped to [0, max_len]) and sample[n_rows] (NULL: sample[r] = r) as the inputs call hands
+ * them out.  side: the sequence the spans label, 0 (A) or 1 (B, the context of a question-first pair).
+ * For row r and column c, (b, e) the cell's offsets, s the row's sample and J = [span_splits[s], span_splits[s + 1]):
+ *   token(c):   c < len_r, e > b and type(r, c) == side   (specials and padding carry (0, 0): never tokens)
+ *   j(c):       the smallest j in J with end[j] > b
+ *   covered(c): token(c), j(c) exists, and begin[j] < e   (overlap; a token over two spans takes the first)
+ *   span_index[r][c] = j(c), an index into the flat span list, if covered, else -1
+ *   labels[r][c] = ignore_id if !token(c);  outside_label if token(c) and not covered;
+ *                  else span_labels[j] + (b > begin[j] ? inside_add : 0)
+ * The begin cell of a span is the one that starts at or before the span's begin: the cell alone decides, so a token has
+ * the same label in every window that holds it, and a window that opens inside an entity opens with an inside label.  A
+ * span that begins in a gap in front of a token has no begin cell.
+ *   start_positions[r], end_positions[r]: a = the first span of s.  no_answer in both when s has no span, when the row
+ *   has no token cell, or when begin[a] < lo or end[a] > hi, lo / hi the smallest b / the largest e of the row's token
+ *   cells (the window does not hold the whole answer).  Else start = the largest token column with b <= begin[a], end =
+ *   the smallest token column with e >= end[a].  This is the loop of preprocess_training_examples on the context cells
+ *   alone; it never walks into [SEP] or the padding.  Where several cells share one source span (WP_OPT_NORMALIZE),
+ *   start may lie behind end: the rule is literal.
+ * Ragged form.  offsets[n_ids][2] with row_splits[0 .. n_rows] as the rows call returns them: row i is sample i
+ * (n_samples == n_rows), every cell is a token, the same cell rule; labels[n_ids] and span_index[n_ids], no positions,
+ * and max_len and side of the spec are not read.  One gather through `source` of a packed batch carries them into it.
+ * Outputs.  want (WP_ALIGN_*) names the blocks a host entry point produces (NULL for the others; each freed with
+ * wp_free; all NULL without rows); a device entry point takes caller-owned buffers, NULL for an output that is not
+ * wanted (start and end positions: both or neither), writes every cell of the n_rows rows and nothing behind them, and
+ * does not read want.  At least one output must be wanted.
+ * WP_ERR_ARG: spec NULL, max_len < 1 (padded form), side not 0 / 1, side 1 without token_type_ids, want without a
+ * known bit or with an unknown one (WP_ALIGN_POSITIONS in the ragged form), labels wanted without span_labels, a
+ * required pointer NULL, a device pointer that is not aligned (offsets, spans and splits to 8 bytes, everything else to
+ * 4); and, with the first offender named: row_splits or span_splits that do not start at 0, descend or end elsewhere
+ * than at n_ids / n_spans, a span that is empty or begins before the one in front of it in its sample ends, a row whose
+ * sample is outside [0, n_samples).  The host entry points check all of this before a device is touched; the device entry
+ * points check the arrays in a kernel with one word of result, and the kernels behind it write nothing where it
+ * failed.  WP_ERR_TOO_LARGE: n_rows, n_samples, n_spans or n_ids above INT32_MAX, n_rows * max_len too large.
+ * The device calls run on the handle's device and stream and return after one wait, for the counters. */
+#define WP_ALIGN_LABELS     1
+#define WP_ALIGN_SPAN_INDEX 2
+#define WP_ALIGN_POSITIONS  4
+typedef struct { int32_t max_len, side, outside_label, inside_add, ignore_id, no_answer, want, reserved; } wp_align_spec;
+/* host arrays in; labels, span_index int32 [n_rows, max_len] and start_positions, end_positions int32 [n_rows] out as blocks */
+int wp_align(wp_vocab *v, const uint32_t *offsets, const int32_t *token_type_ids, const int32_t *lengths,
+             const int32_t *sample, size_t n_rows, const int64_t *span_splits, size_t n_samples, const uint32_t *spans,
+             const int32_t *span_labels, size_t n_spans, const wp_align_spec *spec, int32_t **labels,
+             int32_t **span_index, int32_t **start_positions, int32_t **end_positions);
+/* device arrays in, caller-owned device buffers out */
+int wp_align_device(wp_vocab *v, const uint32_t *d_offsets, const int32_t *d_token_type_ids, const int32_t *d_lengths,
+                    const int32_t *d_sample, size_t n_rows, const int64_t *d_span_splits, size_t n_samples,
+                    const uint32_t *d_spans, const int32_t *d_span_labels, size_t n_spans, const wp_align_spec *spec,
+                    int32_t *d_labels, int32_t *d_span_index, int32_t *d_start_positions, int32_t *d_end_positions);
+/* the ragged form: host arrays in; labels, span_index int32 [n_ids] out as blocks (n_ids = row_splits[n_rows]) */
+int wp_align_rows(wp_vocab *v, const uint32_t *offsets, const int64_t *row_splits, size_t n_rows,
+                  const int64_t *span_splits, const uint32_t *spans, const int32_t *span_labels, size_t n_spans,
+                  const wp_align_spec *spec, int32_t **labels, int32_t **span_index);
+/* ... device arrays in (n_ids given: it must be the last entry of d_row_splits), caller-owned device buffers out */
+int wp_align_rows_device(wp_vocab *v, const uint32_t *d_offsets, const int64_t *d_row_splits, size_t n_rows, size_t n_ids,
+                         const int64_t *d_span_splits, const uint32_t *d_spans, const int32_t *d_span_labels,
+                         size_t n_spans, const wp_align_spec *spec, int32_t *d_labels, int32_t *d_span_index);
+/* The statistics of the last align call, in a struct of its own (the other statistics structs keep their sizes); every
+ * other statistic keeps what the last encode left.  n_tokens: token cells; n_covered, n_begin: covered cells and, of
+ * those, begin cells (0 when neither labels nor span_index were wanted: no span is looked up then); n_spans: of the
+ * call; n_answer_rows + n_no_answer_rows == n_rows when positions were wanted, both 0 otherwise. */
+typedef struct { int64_t n_rows, n_tokens, n_covered, n_begin, n_spans, n_answer_rows, n_no_answer_rows; } wp_align_stats;
+int wp_get_align_stats(const wp_vocab *v, wp_align_stats *out); /* n_rows == -1: the last call was no align call */
+
 /* The same call sharded over several GPUs of the node, behind the boundary: the reference's own
  * precedent is the in-library chunking at whitespace of linear.cpp:283-299 (thread chunks) and
  * linear.cpp:355-367 (encodeExternal batches).  The text is cut at ASCII whitespace into one shard

@@ -34,6 +34,7 @@ WP_TRUNC_LONGEST_FIRST, WP_TRUNC_ONLY_FIRST, WP_TRUNC_ONLY_SECOND = 0, 1, 2
 WP_PACK_NEXT_FIT, WP_PACK_STREAM = 0, 1
 WP_PACK_LONG_TRUNCATE, WP_PACK_LONG_SPLIT = 0, 1
 WP_PACK_WANT_SEGMENTS, WP_PACK_WANT_POSITIONS, WP_PACK_WANT_SOURCE = 1, 2, 4
+WP_ALIGN_LABELS, WP_ALIGN_SPAN_INDEX, WP_ALIGN_POSITIONS = 1, 2, 4
 _PACK_MODES = {"next_fit": WP_PACK_NEXT_FIT, "stream": WP_PACK_STREAM}
 _PACK_LONG_DOCS = {"truncate": WP_PACK_LONG_TRUNCATE, "split": WP_PACK_LONG_SPLIT}
 _PACK_WANT = {"segment_ids": WP_PACK_WANT_SEGMENTS, "position_ids": WP_PACK_WANT_POSITIONS, "source": WP_PACK_WANT_SOURCE}
@@ -58,6 +59,7 @@ ABI_SYMBOLS = [
     "wp_pack_sequences", "wp_pack_sequences_device", "wp_get_pack_stats",
     "wp_linear_encode_special", "wp_linear_encode_special_device", "wp_linear_encode_special_rows",
     "wp_linear_encode_special_rows_device", "wp_get_special_stats",
+    "wp_align", "wp_align_device", "wp_align_rows", "wp_align_rows_device", "wp_get_align_stats",
 ]
 
 
@@ -193,6 +195,18 @@ class SpecialStats(C.Structure):
     _fields_ = [("n_literals", C.c_int64), ("n_ids", C.c_int64), ("n_rows", C.c_int64), ("n_listed", C.c_int64)]
 
 
+class AlignSpec(C.Structure):
+    """wp_align_spec: the arguments of an align call (want: WP_ALIGN_* bits, read by the host entry points)."""
+    _fields_ = [("max_len", C.c_int32), ("side", C.c_int32), ("outside_label", C.c_int32), ("inside_add", C.c_int32),
+                ("ignore_id", C.c_int32), ("no_answer", C.c_int32), ("want", C.c_int32), ("reserved", C.c_int32)]
+
+
+class AlignStats(C.Structure):
+    """wp_align_stats: the statistics of the last align call (Vocab.align_stats())."""
+    _fields_ = [("n_rows", C.c_int64), ("n_tokens", C.c_int64), ("n_covered", C.c_int64), ("n_begin", C.c_int64),
+                ("n_spans", C.c_int64), ("n_answer_rows", C.c_int64), ("n_no_answer_rows", C.c_int64)]
+
+
 _TEXT_SOURCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t))
 _IDS_SINK = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.c_size_t)
 
@@ -274,6 +288,15 @@ def lib():
                                                                C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t),
                                                                C.POINTER(C.c_size_t)]
             L.wp_get_special_stats.argtypes = [vp, C.POINTER(SpecialStats)]
+        if hasattr(L, "wp_align"):  # (WP_LIB, as above)
+            ap = C.POINTER(AlignSpec)
+            L.wp_align.argtypes = [vp, u32p, i32p, i32p, i32p, C.c_size_t, i64p, C.c_size_t, u32p, i32p, C.c_size_t, ap,
+                                   C.POINTER(i32p), C.POINTER(i32p), C.POINTER(i32p), C.POINTER(i32p)]
+            L.wp_align_device.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp, C.c_size_t, ap, vp, vp, vp, vp]
+            L.wp_align_rows.argtypes = [vp, u32p, i64p, C.c_size_t, i64p, u32p, i32p, C.c_size_t, ap, C.POINTER(i32p),
+                                        C.POINTER(i32p)]
+            L.wp_align_rows_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, vp, C.c_size_t, ap, vp, vp]
+            L.wp_get_align_stats.argtypes = [vp, C.POINTER(AlignStats)]
         L.wp_linear_encode_multi.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.POINTER(i32p),
                                              C.POINTER(C.c_size_t)]
         L.wp_reserve.argtypes = [vp, C.c_size_t]
@@ -975,6 +998,159 @@ class Vocab:
         return self.pack_sequences_tensor(ids, splits, max_len=max_len, mode=mode, bos_id=bos_id, eos_id=eos_id, pad_id=pad_id,
                                           long_docs=long_docs, want=want, n_out=n_out)
 
+    def align_stats(self):
+        """wp_align_stats of the last call as a dict (n_rows -1: it was no align call)."""
+        s = AlignStats()
+        _check(lib().wp_get_align_stats(self._h, C.byref(s)))
+        return {k: int(getattr(s, k)) for k, _ in s._fields_}
+
+    def align_spans(self, batch=None, spans=None, side=0, outside_label=0, inside_add=0, ignore_id=-100, no_answer=0,
+                    labels=True, span_index=False, positions=False, offsets=None, token_type_ids=None, lengths=None,
+                    sample=None):
+        """Labelled character spans against a batch of model inputs (wp_align).  batch: the dict encode_inputs returns
+        (its offsets, token_type_ids, lengths and sample are used unless others are given), or None with the arrays one
+        by one: offsets uint32 [n_rows, max_len, 2], and optionally token_type_ids, lengths, sample.  spans: a list, per
+        sample, of (begin, end[, label]) in the unit of the offsets — sorted, disjoint, non-empty — or what join_spans
+        returns.  side: the sequence the spans label (1: B, the context of a question-first pair).
+        -> a dict of numpy int32 arrays: labels [n_rows, max_len] (ignore_id where there is no token of that side,
+        outside_label on a token no span overlaps, else the span's label, + inside_add unless the token starts at or
+        before the span's begin), span_index (the flat index of the span, -1) and, with positions=True,
+        start_positions / end_positions [n_rows] of the sample's first span (no_answer where the row does not hold it
+        whole)."""
+        offs, types, lens, samp = _align_batch(batch, offsets, token_type_ids, lengths, sample, np.asarray)
+        offs = np.ascontiguousarray(offs, dtype=np.uint32)
+        if offs.ndim != 3 or offs.shape[2] != 2:
+            raise WordPieceError("offsets must be a 3-d array [n_rows, max_len, 2]")
+        n_rows, L = offs.shape[0], offs.shape[1]
+        types = None if types is None else np.ascontiguousarray(types, dtype=np.int32)
+        lens = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
+        samp = None if samp is None else np.ascontiguousarray(samp, dtype=np.int32)
+        if (types is not None and types.shape != (n_rows, L)) or any(x is not None and x.shape != (n_rows,) for x in (lens, samp)):
+            raise WordPieceError("token_type_ids must be [n_rows, max_len], lengths and sample [n_rows]")
+        splits, sp, sl = _spans_arg(spans)
+        spec = AlignSpec(max_len=L, side=side, outside_label=outside_label, inside_add=inside_add, ignore_id=ignore_id,
+                         no_answer=no_answer, want=_align_want(labels, span_index, positions))
+        i32p = C.POINTER(C.c_int32)
+        o_lab, o_idx, o_start, o_end = i32p(), i32p(), i32p(), i32p()
+        _check(lib().wp_align(self._h, offs.ctypes.data_as(C.POINTER(C.c_uint32)), _i32_ptr(types), _i32_ptr(lens), _i32_ptr(samp),
+                              n_rows, _i64_ptr(splits), len(splits) - 1, sp.ctypes.data_as(C.POINTER(C.c_uint32)), _i32_ptr(sl),
+                              len(sp), C.byref(spec), C.byref(o_lab), C.byref(o_idx), C.byref(o_start), C.byref(o_end)))
+        res = {}
+        for want, key, ptr, shape in ((labels, "labels", o_lab, (n_rows, L)), (span_index, "span_index", o_idx, (n_rows, L)),
+                                      (positions, "start_positions", o_start, (n_rows,)),
+                                      (positions, "end_positions", o_end, (n_rows,))):
+            if want:
+                res[key] = _adopt_block(ptr, shape) if n_rows else np.zeros(shape, np.int32)
+        return res
+
+    def align_rows(self, offsets, row_splits, spans, outside_label=0, inside_add=0, labels=True, span_index=False):
+        """The same cell rule over the ragged result of encode_rows (wp_align_rows): offsets uint32 [n_ids, 2], row_splits
+        [n_rows + 1]; row i is sample i and every cell is a token -> a dict of numpy int32 arrays [n_ids]: labels,
+        span_index.  x[source] of a packed batch carries them into it."""
+        offs = np.ascontiguousarray(offsets, dtype=np.uint32).reshape(-1, 2)
+        rows = np.ascontiguousarray(row_splits, dtype=np.int64)
+        if rows.ndim != 1 or len(rows) < 1:
+            raise WordPieceError("row_splits must be a 1-d array of n_rows + 1 entries")
+        if rows[-1] > len(offs):
+            raise WordPieceError("row_splits end behind the offsets")
+        splits, sp, sl = _spans_arg(spans)
+        if len(splits) != len(rows):
+            raise WordPieceError("the ragged form needs one list of spans per row")
+        spec = AlignSpec(outside_label=outside_label, inside_add=inside_add, want=_align_want(labels, span_index, False))
+        i32p = C.POINTER(C.c_int32)
+        o_lab, o_idx = i32p(), i32p()
+        _check(lib().wp_align_rows(self._h, offs.ctypes.data_as(C.POINTER(C.c_uint32)), _i64_ptr(rows), len(rows) - 1, _i64_ptr(splits),
+                                   sp.ctypes.data_as(C.POINTER(C.c_uint32)), _i32_ptr(sl), len(sp), C.byref(spec), C.byref(o_lab),
+                                   C.byref(o_idx)))
+        n = int(rows[-1])
+        res = {}
+        for want, key, ptr in ((labels, "labels", o_lab), (span_index, "span_index", o_idx)):
+            if want:
+                res[key] = _adopt_block(ptr, (n,)) if n else np.zeros(0, np.int32)
+        return res
+
+    def _align_tensor_spans(self, spans, dev):
+        """(span_splits int64, spans uint32-as-int32 [n, 2], span_labels int32) as contiguous tensors on dev"""
+        import torch
+        if not (isinstance(spans, tuple) and len(spans) == 3 and all(isinstance(x, torch.Tensor) for x in spans)):
+            splits, sp, sl = _spans_arg(spans)
+            spans = (torch.from_numpy(splits), torch.from_numpy(sp.view(np.int32)), torch.from_numpy(sl))
+        splits, sp, sl = (x.to(dev) for x in spans)
+        if sp.dtype == torch.uint32:
+            sp = sp.view(torch.int32)
+        if splits.dtype != torch.int64 or sp.dtype != torch.int32 or sl.dtype != torch.int32 or splits.dim() != 1 or \
+                splits.numel() < 1 or sp.shape != (sl.numel(), 2) or sl.dim() != 1:
+            raise WordPieceError("spans on tensors: span_splits int64 [n_samples + 1], spans int32 / uint32 [n_spans, 2], "
+                                 "span_labels int32 [n_spans]")
+        return splits.contiguous(), sp.contiguous(), sl.contiguous()
+
+    def align_spans_tensor(self, batch=None, spans=None, side=0, outside_label=0, inside_add=0, ignore_id=-100, no_answer=0,
+                           labels=True, span_index=False, positions=False, offsets=None, token_type_ids=None, lengths=None,
+                           sample=None):
+        """align_spans for tensors on this handle's GPU (wp_align_device): batch is the dict encode_inputs_tensor returns
+        (or the tensors one by one: offsets int32 / uint32 [n_rows, max_len, 2], ...), spans what join_spans returns — as
+        tensors, or as numpy arrays / a list of lists, which are uploaded -> a dict of int32 tensors there.  Nothing
+        leaves the device."""
+        import torch
+        offs, types, lens, samp = _align_batch(batch, offsets, token_type_ids, lengths, sample, lambda x: x)
+        if offs.dtype == torch.uint32:
+            offs = offs.view(torch.int32)
+        if offs.dtype != torch.int32 or not offs.is_cuda or not offs.is_contiguous() or offs.dim() != 3 or offs.shape[2] != 2:
+            raise WordPieceError("align on tensors needs contiguous int32 / uint32 CUDA/HIP offsets [n_rows, max_len, 2]")
+        dev, (n_rows, L) = offs.device, offs.shape[:2]
+        if self._device is not None and dev.index != self._device:  # (raw pointers go to the handle's device)
+            raise WordPieceError("the tensors lie on %s, the handle on device %d" % (dev, self._device))
+        for x, shape, name in ((types, (n_rows, L), "token_type_ids"), (lens, (n_rows,), "lengths"), (samp, (n_rows,), "sample")):
+            if x is not None and (x.dtype != torch.int32 or x.device != dev or not x.is_contiguous() or tuple(x.shape) != shape):
+                raise WordPieceError("%s must be a contiguous int32 tensor %s on the device of the offsets" % (name, list(shape)))
+        splits, sp, sl = self._align_tensor_spans(spans, dev)
+        spec = AlignSpec(max_len=L, side=side, outside_label=outside_label, inside_add=inside_add, ignore_id=ignore_id,
+                         no_answer=no_answer, want=_align_want(labels, span_index, positions))
+        res = {}
+        if labels:
+            res["labels"] = torch.empty((n_rows, L), dtype=torch.int32, device=dev)
+        if span_index:
+            res["span_index"] = torch.empty((n_rows, L), dtype=torch.int32, device=dev)
+        if positions:
+            res["start_positions"] = torch.empty(n_rows, dtype=torch.int32, device=dev)
+            res["end_positions"] = torch.empty(n_rows, dtype=torch.int32, device=dev)
+        if n_rows == 0:  # (nothing to write, and an empty tensor has no address to name an output by)
+            return res
+        torch.cuda.current_stream(dev).synchronize()  # the library runs on its own HIP streams
+        _check(lib().wp_align_device(self._h, _tensor_ptr(offs), _tensor_ptr(types), _tensor_ptr(lens), _tensor_ptr(samp), n_rows,
+                                     _tensor_ptr(splits), splits.numel() - 1, _tensor_ptr(sp), _tensor_ptr(sl), sl.numel(),
+                                     C.byref(spec), *[_tensor_ptr(res.get(k)) for k in ("labels", "span_index", "start_positions",
+                                                                                        "end_positions")]))
+        return res
+
+    def align_rows_tensor(self, offsets, row_splits, spans, outside_label=0, inside_add=0, labels=True, span_index=False):
+        """align_rows for tensors on this handle's GPU (wp_align_rows_device): offsets int32 / uint32 [n_ids, 2] and
+        row_splits int64 [n_rows + 1] as encode_rows_tensor returns them -> a dict of int32 tensors [n_ids] there."""
+        import torch
+        offs = offsets.view(torch.int32) if offsets.dtype == torch.uint32 else offsets
+        if offs.dtype != torch.int32 or not offs.is_cuda or not offs.is_contiguous() or offs.dim() != 2 or offs.shape[1] != 2:
+            raise WordPieceError("align on tensors needs contiguous int32 / uint32 CUDA/HIP offsets [n_ids, 2]")
+        dev, n = offs.device, offs.shape[0]
+        if self._device is not None and dev.index != self._device:
+            raise WordPieceError("the tensors lie on %s, the handle on device %d" % (dev, self._device))
+        if row_splits.dtype != torch.int64 or row_splits.device != dev or row_splits.dim() != 1 or row_splits.numel() < 1 or \
+                not row_splits.is_contiguous():
+            raise WordPieceError("row_splits must be a contiguous 1-d int64 tensor on the device of the offsets")
+        splits, sp, sl = self._align_tensor_spans(spans, dev)
+        spec = AlignSpec(outside_label=outside_label, inside_add=inside_add, want=_align_want(labels, span_index, False))
+        res = {}
+        if labels:
+            res["labels"] = torch.empty(n, dtype=torch.int32, device=dev)
+        if span_index:
+            res["span_index"] = torch.empty(n, dtype=torch.int32, device=dev)
+        if n == 0:
+            return res
+        torch.cuda.current_stream(dev).synchronize()  # the library runs on its own HIP streams
+        _check(lib().wp_align_rows_device(self._h, _tensor_ptr(offs), _tensor_ptr(row_splits), row_splits.numel() - 1, n,
+                                          _tensor_ptr(splits), _tensor_ptr(sp), _tensor_ptr(sl), sl.numel(), C.byref(spec),
+                                          _tensor_ptr(res.get("labels")), _tensor_ptr(res.get("span_index"))))
+        return res
+
     def special_stats(self):
         """wp_special_stats of the last special-tokens call as a dict (n_literals -1: no such call yet)."""
         s = SpecialStats()
@@ -1242,6 +1418,59 @@ def join_docs(docs):
     if bs:
         off[1:] = np.cumsum([len(b) + 1 for b in bs])
     return b"".join(b + b"\n" for b in bs), off
+
+
+def join_spans(spans):
+    """The flat form of labelled spans given per sample: a list, per sample, of (begin, end) or (begin, end, label)
+    (label 0 where there is none) -> (span_splits int64 [n_samples + 1], spans uint32 [n_spans, 2], span_labels int32
+    [n_spans]), what the align calls take.  The rules — non-empty, sorted, disjoint — are the library's to check."""
+    splits = np.zeros(len(spans) + 1, dtype=np.int64)
+    if len(spans):
+        splits[1:] = np.cumsum([len(s) for s in spans])
+    flat = [t for s in spans for t in s]
+    sp = np.array([(t[0], t[1]) for t in flat], dtype=np.uint32).reshape(-1, 2)
+    sl = np.array([t[2] if len(t) > 2 else 0 for t in flat], dtype=np.int32)
+    return splits, sp, sl
+
+
+def _spans_arg(spans):
+    """what join_spans returns, from that or from the list of lists"""
+    if spans is None:
+        raise WordPieceError("spans is required")
+    if isinstance(spans, tuple) and len(spans) == 3 and all(isinstance(x, np.ndarray) for x in spans):
+        splits = np.ascontiguousarray(spans[0], dtype=np.int64)
+        sp = np.ascontiguousarray(spans[1], dtype=np.uint32).reshape(-1, 2)
+        sl = np.ascontiguousarray(spans[2], dtype=np.int32)
+    else:
+        splits, sp, sl = join_spans(spans)
+    if splits.ndim != 1 or len(splits) < 1 or sl.shape != (len(sp),):
+        raise WordPieceError("spans: span_splits [n_samples + 1], spans [n_spans, 2] and span_labels [n_spans]")
+    return splits, sp, sl
+
+
+def _align_batch(batch, offsets, token_type_ids, lengths, sample, conv):
+    """the four arrays of an align call from the dict of an inputs call and / or one by one (given ones win)"""
+    if batch is not None:
+        if not isinstance(batch, dict):
+            raise WordPieceError("batch is the dict an inputs call returns; pass single arrays by name")
+        offsets = batch.get("offsets") if offsets is None else offsets
+        token_type_ids = batch.get("token_type_ids") if token_type_ids is None else token_type_ids
+        lengths = batch.get("lengths") if lengths is None else lengths
+        sample = batch.get("sample") if sample is None else sample
+    if offsets is None:
+        raise WordPieceError("an align call needs the offsets of the batch (encode_inputs(..., offsets=...))")
+    return tuple(None if x is None else conv(x) for x in (offsets, token_type_ids, lengths, sample))
+
+
+def _align_want(labels, span_index, positions):
+    want = (WP_ALIGN_LABELS if labels else 0) | (WP_ALIGN_SPAN_INDEX if span_index else 0) | (WP_ALIGN_POSITIONS if positions else 0)
+    if want == 0:
+        raise WordPieceError("an align call needs an output: labels, span_index or positions")
+    return want
+
+
+def _tensor_ptr(t):
+    return None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
 
 
 def _docs_arg(docs, text, doc_offsets):

@@ -51,7 +51,8 @@ enum BoundSite {
   kSiteDetok = 11,  // detokenize: the record gather, the pool gather and the store of the text (detok.h)
   kSitePack = 12,   // packing: the gather from the ids, the stores of the batch and of the row starts (packing.h)
   kSiteSpecial = 13,  // special tokens: the stores of the literal list and of the blanks, the rows and the gather of the merge (special.h)
-  kBoundSites = 14
+  kSiteAlign = 14,    // span alignment: the sample of a row and the gathers from the span list (align.h)
+  kBoundSites = 15
 };
 #ifdef WP_DEBUG_BOUNDS
 __device__ unsigned int g_wp_oob[kBoundSites];

@@ -1,6 +1,6 @@
 // context.h — what a vocabulary handle owns on a device: streams, vocabulary tables, bump arenas, the pool of parked
 // contexts (the C ABI itself is in encoder.hip; the device path in linear_path.h and fast_path.h, the layers on top of
-// it in rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h and special_path.h).
+// it in rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h and align_path.h).
 #pragma once
 #include <array>
 #include <cstring>
@@ -155,7 +155,7 @@ static int bit_length(uint64_t v) {
 // c->d_scalars: kScalars 32-bit words that kernels and scans leave their totals in; c->h_scalars: the pinned mirror the
 // host reads them from.  Every word has a name here and nowhere else; no call site names a number.  An encode clears
 // the whole block when it starts (and the pre-pass of WP_OPT_NORMALIZE in front of it does the same, see below).
-constexpr int kScalars = 76;
+constexpr int kScalars = 88;
 constexpr int kScalarCps = 0;       // code points of the text, 32 bits: the decode scan (linear, fast) -> host
 constexpr int kScalarAlphabet = 1;  // alphabet size: alphabet_prefix_kernel -> host
 constexpr int kScalarInvalid = 2;   // invalid sequences, 64 bits (words 2, 3): decode_count_kernel / norm_count_kernel -> host
@@ -197,6 +197,9 @@ constexpr int kScalarDetok = 48;   // d_scalars words 48..55: the four 64-bit to
 constexpr int kScalarPackLast = 56, kScalarPackBad = 58;
 constexpr int kScalarFree59 = 59;  // free
 constexpr int kScalarPack = 60;    // d_scalars words 60..75: the eight 64-bit totals of a pack call (packing.h, PackCounter)
+// span alignment (align.h): what the argument check found, one 64-bit word (words 76, 77; align_bad_key) / the five 64-bit
+// counters of a call (words 78..87, AlignCounter)
+constexpr int kScalarAlignBad = 76, kScalarAlign = 78;
 // normalize_on_device runs in front of the encode, which clears the block again: while it runs, four slots mean
 constexpr int kScalarNormBytes = kScalarCps;           // bytes of the normalised text, 32 bits: its scan
 constexpr int kScalarNormCps = kScalarAlphabet;        // code points of the normalised text (offsets mode) -> host
@@ -218,7 +221,7 @@ constexpr ScalarRange kScalarLayout[] = {
     {kScalarInCut, 1},       {kScalarInRows, 2},     {kScalarInWindowed, 1},      {kScalarSpecial, 1},
     {kScalarMask, 12},       {kScalarDetokLast, 2},  {kScalarDetokBad, 1},        {kScalarFree47, 1},
     {kScalarDetok, 8},       {kScalarPackLast, 2},   {kScalarPackBad, 1},         {kScalarFree59, 1},
-    {kScalarPack, 16}};
+    {kScalarPack, 16},       {kScalarAlignBad, 2},   {kScalarAlign, 10}};
 // one past the last word of the range `slot` lies in: where a download or a clear "through" that slot ends
 constexpr int scalar_end(int slot) {
   for (const ScalarRange &r : kScalarLayout) {
@@ -430,6 +433,8 @@ struct EncodeStats : wp_stats {
   int32_t pack_call;
   wp_special_stats special;  // wp_get_special_stats: filled by a special-tokens call (special_call 1), zero otherwise
   int32_t special_call;
+  wp_align_stats align;  // wp_get_align_stats: filled by an align call (align_call 1), zero otherwise
+  int32_t align_call;
 };
 
 #ifndef WP_LATE_REFINE_DEFAULT

@@ -2,7 +2,8 @@
 // device code is compiled in: the entry points (out-pointers, the answers that need no device, uploads and downloads),
 // the pinned pool, the multi-GPU, batch, stream, file and external calls.  The device path itself: linear_path.h
 // (word_piece::linear, stage by stage) and fast_path.h (word_piece::fast); the layers on top of it, one host header
-// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h; what a handle owns on a device: context.h.
+// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h; what a handle owns
+// on a device: context.h.
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -20,6 +21,7 @@
 #include <vector>
 
 #include "../../include/wordpiece_amd.h"
+#include "align_path.h"
 #include "context.h"
 #include "detok_path.h"
 #include "fast_path.h"
@@ -1116,6 +1118,169 @@ int wp_pack_sequences_device(wp_vocab *v, const int32_t *d_ids, const int64_t *d
       }
       return o;
     });
+  });
+}
+
+}  // extern "C"
+
+// ---- span alignment (include/wordpiece_amd.h, section "span alignment"; host path: align_path.h) ---------------------
+// the host entry points behind their argument rules: align_from_host, then the blocks the caller asked for come down
+static void align_host_call(wp_vocab *v, const AlignIn &in, const AlignGeom &g, bool ragged, int want, int32_t **labels, int32_t **span_index,
+                            int32_t **start, int32_t **end) {
+  Context *c = get_context(v);
+  const AlignOut o = align_from_host(v, c, in, g, ragged, want);
+  const size_t cells = (ragged ? in.n_ids : in.n_rows * static_cast<size_t>(g.max_len)) * sizeof(int32_t);
+  Downloads down(c->stream);
+  if (want & WP_ALIGN_LABELS) down.add(labels, o.labels, cells);
+  if (want & WP_ALIGN_SPAN_INDEX) down.add(span_index, o.span_index, cells);
+  if (want & WP_ALIGN_POSITIONS) {
+    down.add(start, o.start, in.n_rows * sizeof(int32_t));
+    down.add(end, o.end, in.n_rows * sizeof(int32_t));
+  }
+  down.finish();
+}
+
+// the alignment rule of the device entry points
+static void check_align_pointers(const AlignIn &in, const AlignOut &out) {
+  const char *aligned = "align: device offsets, spans and splits must be 8-byte aligned, everything else 4-byte aligned";
+  for (const void *p : {static_cast<const void *>(in.offsets), static_cast<const void *>(in.spans), static_cast<const void *>(in.span_splits),
+                        static_cast<const void *>(in.row_splits)}) {
+    check_aligned(p, 8, aligned);
+  }
+  for (const int32_t *p : {in.types, in.lengths, in.sample, in.span_labels, static_cast<const int32_t *>(out.labels),
+                           static_cast<const int32_t *>(out.span_index), static_cast<const int32_t *>(out.start),
+                           static_cast<const int32_t *>(out.end)}) {
+    check_aligned(p, 4, aligned);
+  }
+}
+
+extern "C" {
+
+int wp_get_align_stats(const wp_vocab *v, wp_align_stats *out) {
+  *out = v->stats.align;
+  if (!v->stats.align_call) out->n_rows = -1;
+  return WP_OK;
+}
+
+int wp_align(wp_vocab *v, const uint32_t *offsets, const int32_t *token_type_ids, const int32_t *lengths, const int32_t *sample,
+             size_t n_rows, const int64_t *span_splits, size_t n_samples, const uint32_t *spans, const int32_t *span_labels, size_t n_spans,
+             const wp_align_spec *spec, int32_t **labels, int32_t **span_index, int32_t **start_positions, int32_t **end_positions) {
+  return guarded([&] {
+    for (int32_t **p : {labels, span_index, start_positions, end_positions}) {
+      if (p) *p = nullptr;
+    }
+    AlignIn in;
+    in.offsets = offsets;
+    in.types = token_type_ids;
+    in.lengths = lengths;
+    in.sample = sample;
+    in.span_splits = span_splits;
+    in.spans = spans;
+    in.span_labels = span_labels;
+    in.n_rows = n_rows;
+    in.n_samples = n_samples;
+    in.n_spans = n_spans;
+    const int want = spec ? spec->want : 0;
+    const AlignGeom g = check_align_spec(spec, in, false, want, true);
+    if (((want & WP_ALIGN_LABELS) && !labels) || ((want & WP_ALIGN_SPAN_INDEX) && !span_index) ||
+        ((want & WP_ALIGN_POSITIONS) && (!start_positions || !end_positions))) {
+      throw std::invalid_argument("align: the out-pointer of a wanted output is NULL");
+    }
+    if (n_rows != 0 && !offsets) throw std::invalid_argument("align: offsets is NULL");
+    check_align_arrays(in, false);
+    if (n_rows == 0) {
+      begin_align_stats(v, 0, n_spans);
+      return;
+    }
+    align_host_call(v, in, g, false, want, labels, span_index, start_positions, end_positions);
+  });
+}
+
+int wp_align_device(wp_vocab *v, const uint32_t *d_offsets, const int32_t *d_token_type_ids, const int32_t *d_lengths, const int32_t *d_sample,
+                    size_t n_rows, const int64_t *d_span_splits, size_t n_samples, const uint32_t *d_spans, const int32_t *d_span_labels,
+                    size_t n_spans, const wp_align_spec *spec, int32_t *d_labels, int32_t *d_span_index, int32_t *d_start_positions,
+                    int32_t *d_end_positions) {
+  return guarded([&] {
+    AlignIn in;
+    in.offsets = d_offsets;
+    in.types = d_token_type_ids;
+    in.lengths = d_lengths;
+    in.sample = d_sample;
+    in.span_splits = d_span_splits;
+    in.spans = d_spans;
+    in.span_labels = d_span_labels;
+    in.n_rows = n_rows;
+    in.n_samples = n_samples;
+    in.n_spans = n_spans;
+    const AlignOut out{d_labels, d_span_index, d_start_positions, d_end_positions};
+    if ((d_start_positions == nullptr) != (d_end_positions == nullptr)) {
+      throw std::invalid_argument("align: start_positions and end_positions go together");
+    }
+    const int want = (d_labels ? WP_ALIGN_LABELS : 0) | (d_span_index ? WP_ALIGN_SPAN_INDEX : 0) | (d_start_positions ? WP_ALIGN_POSITIONS : 0);
+    const AlignGeom g = check_align_spec(spec, in, false, want, false);
+    if (n_rows != 0 && !d_offsets) throw std::invalid_argument("align: offsets is NULL");
+    check_align_pointers(in, out);
+    align_on_device(v, get_context(v), in, g, false, out, true);
+  });
+}
+
+int wp_align_rows(wp_vocab *v, const uint32_t *offsets, const int64_t *row_splits, size_t n_rows, const int64_t *span_splits,
+                  const uint32_t *spans, const int32_t *span_labels, size_t n_spans, const wp_align_spec *spec, int32_t **labels,
+                  int32_t **span_index) {
+  return guarded([&] {
+    for (int32_t **p : {labels, span_index}) {
+      if (p) *p = nullptr;
+    }
+    AlignIn in;
+    in.offsets = offsets;
+    in.row_splits = row_splits;
+    in.span_splits = span_splits;
+    in.spans = spans;
+    in.span_labels = span_labels;
+    in.n_rows = n_rows;
+    in.n_samples = n_rows;
+    in.n_spans = n_spans;
+    if (!row_splits) throw std::invalid_argument("align: row_splits is NULL");
+    if (n_rows > static_cast<size_t>(INT32_MAX)) throw std::length_error("align: more rows than INT32_MAX");
+    // (the last entry is taken on trust only as far as the size rule; check_align_arrays holds it against the others)
+    if (row_splits[n_rows] < 0) throw_align_bad(align_bad_key(kAlignBadRowSplits, n_rows));
+    in.n_ids = static_cast<size_t>(row_splits[n_rows]);
+    const int want = spec ? spec->want : 0;
+    const AlignGeom g = check_align_spec(spec, in, true, want, true);
+    if (((want & WP_ALIGN_LABELS) && !labels) || ((want & WP_ALIGN_SPAN_INDEX) && !span_index)) {
+      throw std::invalid_argument("align: the out-pointer of a wanted output is NULL");
+    }
+    if (in.n_ids != 0 && !offsets) throw std::invalid_argument("align: offsets is NULL");
+    check_align_arrays(in, true);
+    if (in.n_ids == 0) {
+      begin_align_stats(v, n_rows, n_spans);
+      return;
+    }
+    align_host_call(v, in, g, true, want, labels, span_index, nullptr, nullptr);
+  });
+}
+
+int wp_align_rows_device(wp_vocab *v, const uint32_t *d_offsets, const int64_t *d_row_splits, size_t n_rows, size_t n_ids,
+                         const int64_t *d_span_splits, const uint32_t *d_spans, const int32_t *d_span_labels, size_t n_spans,
+                         const wp_align_spec *spec, int32_t *d_labels, int32_t *d_span_index) {
+  return guarded([&] {
+    AlignIn in;
+    in.offsets = d_offsets;
+    in.row_splits = d_row_splits;
+    in.span_splits = d_span_splits;
+    in.spans = d_spans;
+    in.span_labels = d_span_labels;
+    in.n_rows = n_rows;
+    in.n_samples = n_rows;
+    in.n_spans = n_spans;
+    in.n_ids = n_ids;
+    const AlignOut out{d_labels, d_span_index, nullptr, nullptr};
+    const int want = (d_labels ? WP_ALIGN_LABELS : 0) | (d_span_index ? WP_ALIGN_SPAN_INDEX : 0);
+    if (!d_row_splits) throw std::invalid_argument("align: row_splits is NULL");
+    const AlignGeom g = check_align_spec(spec, in, true, want, false);
+    if (n_ids != 0 && !d_offsets) throw std::invalid_argument("align: offsets is NULL");
+    check_align_pointers(in, out);
+    align_on_device(v, get_context(v), in, g, true, out, true);
   });
 }
 

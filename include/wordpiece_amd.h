@@ -483,6 +483,62 @@ int wp_align_rows_device(wp_vocab *v, const uint32_t *d_offsets, const int64_t *
 typedef struct { int64_t n_rows, n_tokens, n_covered, n_begin, n_spans, n_answer_rows, n_no_answer_rows; } wp_align_stats;
 int wp_get_align_stats(const wp_vocab *v, wp_align_stats *out); /* n_rows == -1: the last call was no align call */
 
+/* ---- word counts (an addition: the "word -> count" table a vocabulary learner starts from — HF WordPieceTrainer, TF
+ * Text wordpiece_vocab —, collections.Counter over the split text) ----
+ * The distinct words of a text with their counts, and per occurrence the word's index in that table, computed on the
+ * device.  No vocabulary is read: two handles with different vocabularies give the same table.
+ * Text.  What is counted is the text wp_normalize[_device] gives for the handle's WP_OPT_NORMALIZE flags (flags 0: the
+ * valid UTF-8 of the input, invalid sequences dropped).
+ * Words.  c[p] the code points of that text: p starts a word iff !is_space(c[p]) and (p == 0 or spacing(c[p]) or
+ * spacing(c[p - 1])), and the word runs to the next word start or the next space (the classes of utf8.cpp:10-29:
+ * spacing = space, punctuation or is_chinese).  So a maximal run of non-spacing characters is a word, every punctuation
+ * character and every is_chinese character is a word of its own, and blanks belong to no word: the units the walk of the
+ * encoder tokenises.  Only the vocabulary-independent classes count; the handle's soft list and the special-token list
+ * play no part, so a literal "[MASK]" in the text counts as "[", "MASK", "]".
+ * Long words.  A word of more than max_word_bytes UTF-8 bytes (0: 256; else 1..1024) is not listed: it counts in
+ * wp_count_stats.n_long and in n_words, and takes a slot of word_index with value -1.
+ * Result.  The distinct listed words whose count is at least min_count (0: 1), n_distinct of them:
+ *   words       their UTF-8 bytes back to back, each followed by the byte `terminator` when that is in 0..255 (-1: nothing
+ *               is added); n_bytes bytes.  With terminator '\n' this is the joined-documents text of
+ *               wp_linear_encode_rows, one word per row, and word_off is its doc_off.
+ *   word_off    int64 [n_distinct + 1]: word k lies at [word_off[k], word_off[k + 1]), its terminator, if any, last
+ *   counts      int64 [n_distinct]
+ *   word_index  int32 [n_words], with WP_COUNT_WANT_INDEX: for every word occurrence in text order the index of its
+ *               word in the table, -1 where the word is long or was dropped by min_count
+ * Order.  WP_COUNT_ORDER_FIRST: by first occurrence in the text (iterating collections.Counter(words));
+ * WP_COUNT_ORDER_COUNT: count descending, ties by first occurrence (Counter(words).most_common()).  Neither depends on a
+ * hash.
+ * Exactness.  Two words are the same iff their bytes are equal.  Words are grouped by a 64-bit hash of their bytes, and
+ * every member of a group is then compared byte by byte with the group's first occurrence; what differs is grouped again
+ * under another seed (wp_count_stats.n_rounds, n_collided).  hash_bits (0: 64; else 8..64) narrows the hash so that a
+ * test reaches those rounds with few words; it never changes a result.  reserved must be 0.
+ * Host form: the blocks of *out are malloc'd, each freed with wp_free; a block is NULL where it is empty or was not asked
+ * for (word_off always holds at least {0}).  The empty text is answered without a device.  Device form: d_utf8 under the
+ * buffer contract of wp_linear_encode_device; the arrays of *d_out are device memory owned by the handle until its next
+ * call.  Both return when the table is complete (one wait per size the host needs, one per round).
+ * WP_ERR_ARG, before a device is touched and with the field named: spec or out NULL, order not 0 / 1, max_word_bytes
+ * outside [0, 1024], terminator outside [-1, 255], want with an unknown bit, hash_bits not 0 and outside [8, 64],
+ * reserved not 0, min_count negative.  WP_ERR_TOO_LARGE: a normalised text of more than UINT32_MAX bytes, 2^31 words or
+ * more. */
+#define WP_COUNT_ORDER_FIRST 0
+#define WP_COUNT_ORDER_COUNT 1
+#define WP_COUNT_WANT_INDEX  1
+typedef struct { int32_t order, max_word_bytes, terminator, want, hash_bits, reserved; int64_t min_count; } wp_count_spec;
+typedef struct { uint8_t *words; int64_t *word_off, *counts; int32_t *word_index; int64_t n_distinct, n_words, n_bytes; } wp_word_counts;
+int wp_count_words(wp_vocab *v, const char *utf8, size_t nbytes, const wp_count_spec *spec, wp_word_counts *out);
+int wp_count_words_device(wp_vocab *v, const void *d_utf8, size_t nbytes, const wp_count_spec *spec, wp_word_counts *d_out);
+/* The statistics of the last count call, in a struct of its own (the other statistics structs keep their sizes); every
+ * other statistic keeps what the last encode left, and an encode clears these as it clears every layer's.
+ * n_words: every word, long ones included; n_distinct: the entries of the table; n_long: occurrences of long words;
+ * n_below_min: distinct listed words that min_count dropped; n_text_bytes: bytes of the counted (normalised) text;
+ * n_rounds: grouping rounds (0 without listed words, 1 unless hashes collided); n_collided: the word occurrences that
+ * round 0 left for later rounds.  With WP_OPT_STAGE_TIMING a count call also leaves its device times (HIP events) in the
+ * fields of wp_stats an encode times itself in: ms_normalize (the pre-pass), ms_decode (word starts, ends and the list),
+ * ms_sa (the grouping rounds: keys, sort, comparison), ms_walk (filter, order, gather, index), ms_total (their sum),
+ * and ms_radix_scatter, radix_passes, radix_pass_elems, radix_pass_bytes of its full-size sorts. */
+typedef struct { int64_t n_words, n_distinct, n_long, n_below_min, n_text_bytes, n_rounds, n_collided; } wp_count_stats;
+int wp_get_count_stats(const wp_vocab *v, wp_count_stats *out);   /* n_words == -1: no such call yet, or an encode since */
+
 /* The same call sharded over several GPUs of the node, behind the boundary: the reference's own
  * precedent is the in-library chunking at whitespace of linear.cpp:283-299 (thread chunks) and
  * linear.cpp:355-367 (encodeExternal batches).  The text is cut at ASCII whitespace into one shard

@@ -60,6 +60,7 @@ ABI_SYMBOLS = [
     "wp_linear_encode_special", "wp_linear_encode_special_device", "wp_linear_encode_special_rows",
     "wp_linear_encode_special_rows_device", "wp_get_special_stats",
     "wp_align", "wp_align_device", "wp_align_rows", "wp_align_rows_device", "wp_get_align_stats",
+    "wp_count_words", "wp_count_words_device", "wp_get_count_stats",
 ]
 
 
@@ -207,6 +208,29 @@ class AlignStats(C.Structure):
                 ("n_spans", C.c_int64), ("n_answer_rows", C.c_int64), ("n_no_answer_rows", C.c_int64)]
 
 
+WP_COUNT_ORDER_FIRST, WP_COUNT_ORDER_COUNT = 0, 1
+WP_COUNT_WANT_INDEX = 1
+_COUNT_ORDERS = {"first": WP_COUNT_ORDER_FIRST, "count": WP_COUNT_ORDER_COUNT}
+
+
+class CountSpec(C.Structure):
+    """wp_count_spec: the arguments of a count call (want: WP_COUNT_WANT_* bits; hash_bits 0: 64)."""
+    _fields_ = [("order", C.c_int32), ("max_word_bytes", C.c_int32), ("terminator", C.c_int32), ("want", C.c_int32),
+                ("hash_bits", C.c_int32), ("reserved", C.c_int32), ("min_count", C.c_int64)]
+
+
+class WordCounts(C.Structure):
+    """wp_word_counts: the table of a count call (host blocks, or device memory owned by the handle)."""
+    _fields_ = [("words", C.c_void_p), ("word_off", C.c_void_p), ("counts", C.c_void_p), ("word_index", C.c_void_p),
+                ("n_distinct", C.c_int64), ("n_words", C.c_int64), ("n_bytes", C.c_int64)]
+
+
+class CountStats(C.Structure):
+    """wp_count_stats: the statistics of the last count call (Vocab.count_stats())."""
+    _fields_ = [("n_words", C.c_int64), ("n_distinct", C.c_int64), ("n_long", C.c_int64), ("n_below_min", C.c_int64),
+                ("n_text_bytes", C.c_int64), ("n_rounds", C.c_int64), ("n_collided", C.c_int64)]
+
+
 _TEXT_SOURCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t))
 _IDS_SINK = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.c_size_t)
 
@@ -297,6 +321,10 @@ def lib():
                                         C.POINTER(i32p)]
             L.wp_align_rows_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, vp, C.c_size_t, ap, vp, vp]
             L.wp_get_align_stats.argtypes = [vp, C.POINTER(AlignStats)]
+        if hasattr(L, "wp_count_words"):  # (WP_LIB, as above)
+            L.wp_count_words.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(CountSpec), C.POINTER(WordCounts)]
+            L.wp_count_words_device.argtypes = [vp, vp, C.c_size_t, C.POINTER(CountSpec), C.POINTER(WordCounts)]
+            L.wp_get_count_stats.argtypes = [vp, C.POINTER(CountStats)]
         L.wp_linear_encode_multi.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.POINTER(i32p),
                                              C.POINTER(C.c_size_t)]
         L.wp_reserve.argtypes = [vp, C.c_size_t]
@@ -997,6 +1025,93 @@ class Vocab:
         ids, splits = self.encode_rows_tensor(text, doc_offsets, copy=False)
         return self.pack_sequences_tensor(ids, splits, max_len=max_len, mode=mode, bos_id=bos_id, eos_id=eos_id, pad_id=pad_id,
                                           long_docs=long_docs, want=want, n_out=n_out)
+
+    def count_stats(self):
+        """wp_count_stats of the last count call as a dict (n_words -1: no such call yet)."""
+        s = CountStats()
+        _check(lib().wp_get_count_stats(self._h, C.byref(s)))
+        return {k: int(getattr(s, k)) for k, _ in s._fields_}
+
+    @staticmethod
+    def _count_spec(order, min_count, max_word_bytes, terminator, index, hash_bits):
+        if order not in _COUNT_ORDERS:
+            raise WordPieceError("count: order must be 'first' or 'count'")
+        if terminator is None:
+            term = -1
+        elif isinstance(terminator, int):
+            term = terminator
+        else:
+            t = _bytes(terminator)
+            if len(t) != 1:
+                raise WordPieceError("count: terminator must be one byte")
+            term = t[0]
+        return CountSpec(_COUNT_ORDERS[order], int(max_word_bytes), term, WP_COUNT_WANT_INDEX if index else 0, int(hash_bits), 0,
+                         int(min_count))
+
+    def count_words(self, text, order="first", min_count=1, max_word_bytes=256, terminator=None, index=False, raw=False,
+                    hash_bits=0):
+        """The distinct words of a text with their counts (wp_count_words): the words of the handle's normalised text by
+        the encoder's own word rule, in order of first occurrence ("first") or of Counter.most_common() ("count").
+        -> {"words": [str...], "counts": np.int64[...]} and, with index, "word_index": np.int32 per word occurrence (-1:
+        long or below min_count).  raw: "words" is the byte pool (np.uint8; each word followed by `terminator`, a byte or
+        one-byte str, if given) and "word_off" (np.int64) comes along.  hash_bits: for tests of the collision rounds."""
+        b = _bytes(text)
+        spec = self._count_spec(order, min_count, max_word_bytes, terminator, index, hash_bits)
+        out = WordCounts()
+        _check(lib().wp_count_words(self._h, b, len(b), C.byref(spec), C.byref(out)))
+        try:
+            n = out.n_distinct
+            pool = np.ctypeslib.as_array(C.cast(out.words, C.POINTER(C.c_uint8)), (out.n_bytes,)).copy() if out.n_bytes else \
+                np.zeros(0, dtype=np.uint8)
+            off = np.ctypeslib.as_array(C.cast(out.word_off, C.POINTER(C.c_int64)), (n + 1,)).copy()
+            counts = np.ctypeslib.as_array(C.cast(out.counts, C.POINTER(C.c_int64)), (n,)).copy() if n else np.zeros(0, dtype=np.int64)
+            widx = None
+            if index:
+                widx = np.ctypeslib.as_array(C.cast(out.word_index, C.POINTER(C.c_int32)), (out.n_words,)).copy() if out.n_words else \
+                    np.zeros(0, dtype=np.int32)
+        finally:
+            for blk in (out.words, out.word_off, out.counts, out.word_index):
+                if blk:
+                    lib().wp_free(blk)
+        if raw:
+            res = {"words": pool, "word_off": off, "counts": counts}
+        else:
+            data, cut = pool.tobytes(), 1 if spec.terminator >= 0 else 0
+            res = {"words": [data[off[k]:off[k + 1] - cut].decode("utf8") for k in range(n)], "counts": counts}
+        if index:
+            res["word_index"] = widx
+        return res
+
+    def count_words_tensor(self, text, order="first", min_count=1, max_word_bytes=256, terminator=None, index=False, copy=True,
+                           hash_bits=0):
+        """count_words for a uint8 text tensor on this handle's GPU (wp_count_words_device) -> {"words": uint8 pool,
+        "word_off": int64 [n + 1], "counts": int64 [n]} and, with index, "word_index": int32 per word occurrence, tensors
+        on that device.  copy=False: views of the library's buffers, valid until the next call on this handle."""
+        import torch
+        if text.dtype != torch.uint8 or not text.is_cuda or not text.is_contiguous():
+            raise WordPieceError("count_words_tensor needs a contiguous uint8 CUDA/HIP tensor")
+        spec = self._count_spec(order, min_count, max_word_bytes, terminator, index, hash_bits)
+        nbytes = text.numel()
+        if text.data_ptr() % 4 != 0 or nbytes % 4 != 0:  # (as encode_tensor: the decoder reads whole aligned words)
+            padded = torch.zeros((nbytes + 19) // 16 * 16, dtype=torch.uint8, device=text.device)
+            padded[:nbytes] = text
+            text = padded
+        dev = text.device
+        torch.cuda.current_stream(dev).synchronize()  # the library runs on its own HIP streams
+        out = WordCounts()
+        _check(lib().wp_count_words_device(self._h, C.c_void_p(text.data_ptr()), nbytes, C.byref(spec), C.byref(out)))
+
+        def view(ptr, n, typestr, dtype):
+            if not n:
+                return torch.zeros(0, dtype=dtype, device=dev)
+            t = torch.as_tensor(DeviceIds(ptr, n, typestr=typestr), device=dev)
+            return t.clone() if copy else t
+        res = {"words": view(out.words, out.n_bytes, "|u1", torch.uint8),
+               "word_off": view(out.word_off, out.n_distinct + 1, "<i8", torch.int64),
+               "counts": view(out.counts, out.n_distinct, "<i8", torch.int64)}
+        if index:
+            res["word_index"] = view(out.word_index, out.n_words, "<i4", torch.int32)
+        return res
 
     def align_stats(self):
         """wp_align_stats of the last call as a dict (n_rows -1: it was no align call)."""

@@ -52,7 +52,8 @@ enum BoundSite {
   kSitePack = 12,   // packing: the gather from the ids, the stores of the batch and of the row starts (packing.h)
   kSiteSpecial = 13,  // special tokens: the stores of the literal list and of the blanks, the rows and the gather of the merge (special.h)
   kSiteAlign = 14,    // span alignment: the sample of a row and the gathers from the span list (align.h)
-  kBoundSites = 15
+  kSiteCount = 15,    // word counts: the stores of the word list, the groups and the table, the gathers behind them (count.h)
+  kBoundSites = 16
 };
 #ifdef WP_DEBUG_BOUNDS
 __device__ unsigned int g_wp_oob[kBoundSites];

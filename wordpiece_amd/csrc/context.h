@@ -1,6 +1,6 @@
 // context.h — what a vocabulary handle owns on a device: streams, vocabulary tables, bump arenas, the pool of parked
 // contexts (the C ABI itself is in encoder.hip; the device path in linear_path.h and fast_path.h, the layers on top of
-// it in rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h and align_path.h).
+// it in rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h and count_path.h).
 #pragma once
 #include <array>
 #include <cstring>
@@ -155,7 +155,7 @@ static int bit_length(uint64_t v) {
 // c->d_scalars: kScalars 32-bit words that kernels and scans leave their totals in; c->h_scalars: the pinned mirror the
 // host reads them from.  Every word has a name here and nowhere else; no call site names a number.  An encode clears
 // the whole block when it starts (and the pre-pass of WP_OPT_NORMALIZE in front of it does the same, see below).
-constexpr int kScalars = 88;
+constexpr int kScalars = 96;
 constexpr int kScalarCps = 0;       // code points of the text, 32 bits: the decode scan (linear, fast) -> host
 constexpr int kScalarAlphabet = 1;  // alphabet size: alphabet_prefix_kernel -> host
 constexpr int kScalarInvalid = 2;   // invalid sequences, 64 bits (words 2, 3): decode_count_kernel / norm_count_kernel -> host
@@ -200,6 +200,10 @@ constexpr int kScalarPack = 60;    // d_scalars words 60..75: the eight 64-bit t
 // span alignment (align.h): what the argument check found, one 64-bit word (words 76, 77; align_bad_key) / the five 64-bit
 // counters of a call (words 78..87, AlignCounter)
 constexpr int kScalarAlignBad = 76, kScalarAlign = 78;
+// word counts (count.h): the words of the text, 64 bits (words 88, 89) / the listed ones / the runs and the leftovers of
+// a round / the kept groups / the 64-bit counters of a call (words 94, 95, CountCounter)
+constexpr int kScalarCountWords = 88, kScalarCountListed = 90, kScalarCountRuns = 91, kScalarCountLeft = 92, kScalarCountKept = 93;
+constexpr int kScalarCount = 94;
 // normalize_on_device runs in front of the encode, which clears the block again: while it runs, four slots mean
 constexpr int kScalarNormBytes = kScalarCps;           // bytes of the normalised text, 32 bits: its scan
 constexpr int kScalarNormCps = kScalarAlphabet;        // code points of the normalised text (offsets mode) -> host
@@ -221,7 +225,9 @@ constexpr ScalarRange kScalarLayout[] = {
     {kScalarInCut, 1},       {kScalarInRows, 2},     {kScalarInWindowed, 1},      {kScalarSpecial, 1},
     {kScalarMask, 12},       {kScalarDetokLast, 2},  {kScalarDetokBad, 1},        {kScalarFree47, 1},
     {kScalarDetok, 8},       {kScalarPackLast, 2},   {kScalarPackBad, 1},         {kScalarFree59, 1},
-    {kScalarPack, 16},       {kScalarAlignBad, 2},   {kScalarAlign, 10}};
+    {kScalarPack, 16},       {kScalarAlignBad, 2},   {kScalarAlign, 10},
+    {kScalarCountWords, 2},  {kScalarCountListed, 1}, {kScalarCountRuns, 1},      {kScalarCountLeft, 1},
+    {kScalarCountKept, 1},   {kScalarCount, 2}};
 // one past the last word of the range `slot` lies in: where a download or a clear "through" that slot ends
 constexpr int scalar_end(int slot) {
   for (const ScalarRange &r : kScalarLayout) {
@@ -319,6 +325,9 @@ struct Context {
   // special tokens (special.h): the blanked copy of the text, the listed lines and the tile counts of the match, the
   // literal list, and the merged result with the tables its placement needs
   DeviceBuffer special_text, special_in, special_lit, special_out;
+  // word counts (count.h): the tile counts of the word-start pass, the per-word and per-group arrays of the rounds, and
+  // the table of the last call (the counted text itself is in norm_buf)
+  DeviceBuffer count_aux, count_words, count_out;
   // WP_OPT_NORMALIZE (normalize.h): the tables (uploaded with the first normalising call), the normalised text, the
   // tile counts of the pre-pass, and the source of every normalised code point (offsets mode)
   uint16_t *d_norm_index = nullptr;
@@ -362,10 +371,11 @@ struct Context {
     size_t n = 0, n_text = 0;
   } dbg;
   // every DeviceBuffer above, for destroy_context, release_arenas and park_context: a new buffer is one more name here
-  std::array<DeviceBuffer *, 25> buffers() {
+  std::array<DeviceBuffer *, 28> buffers() {
     return {&text_buf, &a_buf,    &b_buf,   &fmt_buf,    &text_buf2, &ids_stage[0], &ids_stage[1], &rows_in,   &rows_out,
             &pad_buf,  &inputs_buf, &norm_buf, &norm_aux, &norm_map, &detok_in,     &detok_aux,    &detok_out,
-            &pack_in,  &pack_plan,  &pack_tab, &pack_out, &special_text, &special_in, &special_lit, &special_out};
+            &pack_in,  &pack_plan,  &pack_tab, &pack_out, &special_text, &special_in, &special_lit, &special_out,
+            &count_aux, &count_words, &count_out};
   }
   Context() = default;
   Context(const Context &) = delete;
@@ -435,6 +445,8 @@ struct EncodeStats : wp_stats {
   int32_t special_call;
   wp_align_stats align;  // wp_get_align_stats: filled by an align call (align_call 1), zero otherwise
   int32_t align_call;
+  wp_count_stats count;  // wp_get_count_stats: filled by a count call (count_call 1), zero otherwise
+  int32_t count_call;
 };
 
 #ifndef WP_LATE_REFINE_DEFAULT

@@ -2,7 +2,7 @@
 // device code is compiled in: the entry points (out-pointers, the answers that need no device, uploads and downloads),
 // the pinned pool, the multi-GPU, batch, stream, file and external calls.  The device path itself: linear_path.h
 // (word_piece::linear, stage by stage) and fast_path.h (word_piece::fast); the layers on top of it, one host header
-// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h; what a handle owns
+// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h, count_path.h; what a handle owns
 // on a device: context.h.
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -23,6 +23,7 @@
 #include "../../include/wordpiece_amd.h"
 #include "align_path.h"
 #include "context.h"
+#include "count_path.h"
 #include "detok_path.h"
 #include "fast_path.h"
 #include "format.h"
@@ -1281,6 +1282,59 @@ int wp_align_rows_device(wp_vocab *v, const uint32_t *d_offsets, const int64_t *
     if (n_ids != 0 && !d_offsets) throw std::invalid_argument("align: offsets is NULL");
     check_align_pointers(in, out);
     align_on_device(v, get_context(v), in, g, true, out, true);
+  });
+}
+
+}  // extern "C"
+
+// ---- word counts (include/wordpiece_amd.h, section "word counts"; host path: count_path.h) ----------------------------
+extern "C" {
+
+int wp_get_count_stats(const wp_vocab *v, wp_count_stats *out) {
+  *out = v->stats.count;
+  if (!v->stats.count_call) out->n_words = -1;
+  return WP_OK;
+}
+
+int wp_count_words(wp_vocab *v, const char *utf8, size_t nbytes, const wp_count_spec *spec, wp_word_counts *out) {
+  return guarded([&] {
+    if (out) *out = wp_word_counts{};
+    const CountPlan plan = check_count_spec(spec, out);
+    if (nbytes > static_cast<size_t>(UINT32_MAX)) throw std::length_error("count: nbytes above UINT32_MAX");
+    if (nbytes == 0) {  // (no device needed)
+      begin_count_stats(v);
+      out->word_off = static_cast<int64_t *>(zeroed(sizeof(int64_t)));
+      return;
+    }
+    if (!utf8) throw std::invalid_argument("count: utf8 is NULL");
+    Context *c = get_context(v);
+    upload_text(c, utf8, nbytes);
+    wp_word_counts d;
+    count_on_device(v, c, static_cast<const uint8_t *>(c->text_buf.p), nbytes, plan, &d);
+    wp_word_counts h = d;
+    h.words = nullptr;
+    h.word_off = h.counts = nullptr;
+    h.word_index = nullptr;
+    Downloads down(c->stream);
+    if (d.n_bytes) down.add(&h.words, d.words, static_cast<size_t>(d.n_bytes));
+    down.add(&h.word_off, d.word_off, static_cast<size_t>(d.n_distinct + 1) * sizeof(int64_t));
+    if (d.n_distinct) down.add(&h.counts, d.counts, static_cast<size_t>(d.n_distinct) * sizeof(int64_t));
+    if (d.word_index) down.add(&h.word_index, d.word_index, static_cast<size_t>(d.n_words) * sizeof(int32_t));
+    down.finish();
+    *out = h;
+  });
+}
+
+int wp_count_words_device(wp_vocab *v, const void *d_utf8, size_t nbytes, const wp_count_spec *spec, wp_word_counts *d_out) {
+  return guarded([&] {
+    if (d_out) *d_out = wp_word_counts{};
+    const CountPlan plan = check_count_spec(spec, d_out);
+    if (nbytes > static_cast<size_t>(UINT32_MAX)) throw std::length_error("count: nbytes above UINT32_MAX");
+    if (nbytes != 0) {
+      if (!d_utf8) throw std::invalid_argument("count: utf8 is NULL");
+      check_device_text(d_utf8);
+    }
+    count_on_device(v, get_context(v), static_cast<const uint8_t *>(d_utf8), nbytes, plan, d_out);
   });
 }
 

@@ -539,6 +539,68 @@ int wp_count_words_device(wp_vocab *v, const void *d_utf8, size_t nbytes, const 
 typedef struct { int64_t n_words, n_distinct, n_long, n_below_min, n_text_bytes, n_rounds, n_collided; } wp_count_stats;
 int wp_get_count_stats(const wp_vocab *v, wp_count_stats *out);   /* n_words == -1: no such call yet, or an encode since */
 
+/* ---- vocabulary learner (an addition: a WordPiece vocabulary from the word table above, computed on the device; the
+ * top-down scheme of TF Text's wordpiece_vocab learner — no bit parity with that package is claimed: the contract is the
+ * one stated here, and tests/learn_model.py is its executable form) ----
+ * Input.  A word table as wp_count_words[_device] gives it: words (a byte pool of n_bytes bytes), word_off int64
+ * [n_words + 1], counts int64 [n_words], and spec->terminator, the byte behind every word in the pool (-1: none).  Any
+ * table is taken: duplicate words add their counts up, a word of 0 bytes is skipped.  A check on the device answers
+ * WP_ERR_ARG, naming the first word it concerns, where word_off descends or leaves the pool, a count is negative, or a
+ * word is not valid UTF-8.  Lengths below are in code points.
+ * Filters, in this order: (1) a word equal to a reserved token, and a word whose bytes begin with "##", is dropped;
+ * (2) a word of more than max_token_chars is dropped; (3) with max_unique_chars = K > 0 the characters of the remaining
+ * words are ranked by their occurrences weighted by the word counts, descending, ties by code point ascending: the first
+ * K are allowed, and a word that holds any other character is dropped.  The characters of the call are those of the words
+ * that remain.
+ * Tokens.  A token is a pair (joined, text): the substring [s, e) of a word is the token (s > 0, those characters), and
+ * two tokens are the same iff flag and bytes are equal.  The universe is every substring of every remaining word in the
+ * order (word, s, e); a token's first occurrence is its first place in that order.
+ * One threshold t runs num_iterations iterations.  In iteration 0 every start of every word is active; in iteration
+ * k > 0 the active starts of a word are the piece starts of its greedy longest-match split over the tokens iteration
+ * k - 1 ended with.  count[T] is the sum of the word counts over the occurrences of T whose start is active (int64).
+ * Then for L = max_token_chars down to 1 every token of length L with count >= t is kept with that count as its score,
+ * and its count is taken from each of its proper prefixes with the same flag (counts may go negative).  Behind the level
+ * pass every character is added bare and joined, with score 1 where it was not kept.
+ * The list: the reserved tokens in the order given (score 0), then for every character in code point order c, then ##c,
+ * then the other kept tokens of the last iteration by score descending, ties by first occurrence; joined tokens are
+ * written with "##".  Its length is the size.
+ * Search.  lower = lower_thresh, upper = upper_thresh; a step takes t = (lower + upper) / 2 and is accepted if
+ * size <= vocab_size and vocab_size - size <= slack (a number of entries), or lower >= upper, or t <= 1; otherwise
+ * lower = t + 1 where size > vocab_size, else upper = t - 1.
+ * Result.  tokens: the list as text, each token followed by '\n' (the content of a vocab.txt), n_bytes bytes; token_off
+ * int64 [n_tokens + 1]; scores int64 [n_tokens]; thresh: the accepted threshold (0: no word remained, the list is the
+ * reserved tokens alone).
+ * Exactness.  Occurrences are grouped into tokens by a 64-bit hash of flag and bytes, and every member of a group is
+ * compared with the group's first occurrence; what differs is grouped again under another seed (wp_learn_stats.n_rounds,
+ * n_collided).  hash_bits (0: 64; else 8..64) narrows the hash for tests and never changes a result.  The sums are
+ * integer sums: no result depends on an order of execution.
+ * The handle lends its device context only: its vocabulary and its options are not read (WP_OPT_STAGE_TIMING and
+ * WP_OPT_ARENA_GUARD excepted).  Host form: the table in host memory, the blocks of *out malloc'd, each freed with
+ * wp_free; the empty table is answered without a device.  Device form: device arrays in (word_off, counts 8-byte
+ * aligned), the arrays of *d_out device memory owned by the handle until its next learn call.
+ * WP_ERR_ARG, before a device is touched and with the field named: spec or out NULL, words, word_off or counts NULL with
+ * n_words > 0, vocab_size < 1, max_token_chars outside [1, 64], num_iterations < 1, lower_thresh or upper_thresh below
+ * 1 or lower_thresh > upper_thresh, slack negative, max_unique_chars negative, terminator outside [-1, 255], hash_bits
+ * not 0 and outside [8, 64], n_reserved negative or reserved_tokens / reserved_off NULL with n_reserved > 0, a reserved
+ * token that is empty or holds '\n', reserved not 0.  WP_ERR_TOO_LARGE: a pool of more than UINT32_MAX bytes, 2^31
+ * words, or 2^31 substring occurrences or more. */
+typedef struct { const uint8_t *reserved_tokens; const int64_t *reserved_off; int64_t n_reserved, vocab_size, lower_thresh, upper_thresh, slack; int32_t num_iterations, max_token_chars, max_unique_chars, terminator, hash_bits, reserved; } wp_learn_spec;
+typedef struct { uint8_t *tokens; int64_t *token_off, *scores; int64_t n_tokens, n_bytes, thresh; } wp_learned_vocab;
+int wp_learn_vocab(wp_vocab *v, const uint8_t *words, const int64_t *word_off, const int64_t *counts, size_t n_words,
+                   const wp_learn_spec *spec, wp_learned_vocab *out);
+int wp_learn_vocab_device(wp_vocab *v, const void *d_words, size_t n_bytes, const int64_t *d_word_off, const int64_t *d_counts,
+                          size_t n_words, const wp_learn_spec *spec, wp_learned_vocab *d_out);
+/* The statistics of the last learn call, in a struct of its own.  n_words: the entries of the table; n_reserved, n_long,
+ * n_char_dropped: the words filters 1, 2 and 3 dropped; n_chars: the characters; n_occurrences: the substring
+ * occurrences; n_tokens: the distinct tokens among them; n_steps: the steps of the search; thresh: the accepted
+ * threshold; n_rounds, n_collided: the grouping rounds and the occurrences round 0 left for later ones.  With
+ * WP_OPT_STAGE_TIMING a learn call leaves its device times (HIP events) in the fields of wp_stats an encode times itself
+ * in: ms_decode (table check, filters, characters, enumeration), ms_sa (the grouping: keys, sorts, comparison, parents,
+ * the order by group), ms_scan (the search: every step's splits, sums and levels), ms_walk (order, list, gather),
+ * ms_total (their sum). */
+typedef struct { int64_t n_words, n_reserved, n_long, n_char_dropped, n_chars, n_occurrences, n_tokens, n_steps, thresh, n_rounds, n_collided; } wp_learn_stats;
+int wp_get_learn_stats(const wp_vocab *v, wp_learn_stats *out);   /* n_words == -1: no such call yet, or an encode since */
+
 /* The same call sharded over several GPUs of the node, behind the boundary: the reference's own
  * precedent is the in-library chunking at whitespace of linear.cpp:283-299 (thread chunks) and
  * linear.cpp:355-367 (encodeExternal batches).  The text is cut at ASCII whitespace into one shard

@@ -61,6 +61,7 @@ ABI_SYMBOLS = [
     "wp_linear_encode_special_rows_device", "wp_get_special_stats",
     "wp_align", "wp_align_device", "wp_align_rows", "wp_align_rows_device", "wp_get_align_stats",
     "wp_count_words", "wp_count_words_device", "wp_get_count_stats",
+    "wp_learn_vocab", "wp_learn_vocab_device", "wp_get_learn_stats",
 ]
 
 
@@ -231,6 +232,30 @@ class CountStats(C.Structure):
                 ("n_text_bytes", C.c_int64), ("n_rounds", C.c_int64), ("n_collided", C.c_int64)]
 
 
+DEFAULT_RESERVED = ("[PAD]", "[UNK]", "[CLS]", "[SEP]", "[MASK]")
+
+
+class LearnSpec(C.Structure):
+    """wp_learn_spec: the arguments of a learn call (slack: a number of entries; hash_bits 0: 64)."""
+    _fields_ = [("reserved_tokens", C.c_char_p), ("reserved_off", C.POINTER(C.c_int64)), ("n_reserved", C.c_int64),
+                ("vocab_size", C.c_int64), ("lower_thresh", C.c_int64), ("upper_thresh", C.c_int64), ("slack", C.c_int64),
+                ("num_iterations", C.c_int32), ("max_token_chars", C.c_int32), ("max_unique_chars", C.c_int32),
+                ("terminator", C.c_int32), ("hash_bits", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LearnedVocab(C.Structure):
+    """wp_learned_vocab: the list of a learn call (host blocks, or device memory owned by the handle)."""
+    _fields_ = [("tokens", C.c_void_p), ("token_off", C.c_void_p), ("scores", C.c_void_p), ("n_tokens", C.c_int64),
+                ("n_bytes", C.c_int64), ("thresh", C.c_int64)]
+
+
+class LearnStats(C.Structure):
+    """wp_learn_stats: the statistics of the last learn call (Vocab.learn_stats())."""
+    _fields_ = [("n_words", C.c_int64), ("n_reserved", C.c_int64), ("n_long", C.c_int64), ("n_char_dropped", C.c_int64),
+                ("n_chars", C.c_int64), ("n_occurrences", C.c_int64), ("n_tokens", C.c_int64), ("n_steps", C.c_int64),
+                ("thresh", C.c_int64), ("n_rounds", C.c_int64), ("n_collided", C.c_int64)]
+
+
 _TEXT_SOURCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t))
 _IDS_SINK = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.c_size_t)
 
@@ -325,6 +350,10 @@ def lib():
             L.wp_count_words.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(CountSpec), C.POINTER(WordCounts)]
             L.wp_count_words_device.argtypes = [vp, vp, C.c_size_t, C.POINTER(CountSpec), C.POINTER(WordCounts)]
             L.wp_get_count_stats.argtypes = [vp, C.POINTER(CountStats)]
+        if hasattr(L, "wp_learn_vocab"):  # (WP_LIB, as above)
+            L.wp_learn_vocab.argtypes = [vp, vp, vp, vp, C.c_size_t, C.POINTER(LearnSpec), C.POINTER(LearnedVocab)]
+            L.wp_learn_vocab_device.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(LearnSpec), C.POINTER(LearnedVocab)]
+            L.wp_get_learn_stats.argtypes = [vp, C.POINTER(LearnStats)]
         L.wp_linear_encode_multi.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.POINTER(i32p),
                                              C.POINTER(C.c_size_t)]
         L.wp_reserve.argtypes = [vp, C.c_size_t]
@@ -1113,6 +1142,111 @@ class Vocab:
             res["word_index"] = view(out.word_index, out.n_words, "<i4", torch.int32)
         return res
 
+    def learn_stats(self):
+        """wp_learn_stats of the last learn call as a dict (n_words -1: no such call yet)."""
+        s = LearnStats()
+        _check(lib().wp_get_learn_stats(self._h, C.byref(s)))
+        return {k: int(getattr(s, k)) for k, _ in s._fields_}
+
+    @staticmethod
+    def _learn_spec(vocab_size, reserved, lower_thresh, upper_thresh, num_iterations, max_token_chars, max_unique_chars, slack_ratio,
+                    slack, terminator, hash_bits):
+        """-> (LearnSpec, what it points into: keep both alive over the call)"""
+        res = [_bytes(r) for r in reserved]
+        off = np.zeros(len(res) + 1, dtype=np.int64)
+        if res:
+            off[1:] = np.cumsum([len(r) for r in res])
+        pool = b"".join(res)
+        if terminator is None:
+            term = -1
+        elif isinstance(terminator, int):
+            term = terminator
+        else:
+            t = _bytes(terminator)
+            if len(t) != 1:
+                raise WordPieceError("learn: terminator must be one byte")
+            term = t[0]
+        if slack is None:
+            slack = int(slack_ratio * vocab_size)
+        spec = LearnSpec(pool, off.ctypes.data_as(C.POINTER(C.c_int64)), len(res), int(vocab_size), int(lower_thresh), int(upper_thresh),
+                         int(slack), int(num_iterations), int(max_token_chars), int(max_unique_chars), term, int(hash_bits), 0)
+        return spec, (pool, off)
+
+    def learn_vocab(self, table, vocab_size, reserved=DEFAULT_RESERVED, lower_thresh=10, upper_thresh=10_000_000, num_iterations=4,
+                    max_token_chars=50, max_unique_chars=1000, slack_ratio=0.05, slack=None, hash_bits=0):
+        """A WordPiece vocabulary learned from a word table on the device (wp_learn_vocab).  table: the dict count_words
+        returns ("words": strs or bytes, "counts"), or its raw form ("words": the byte pool, "word_off", "counts", and
+        "terminator" if the pool has one).  -> {"tokens": [str...], "scores": np.int64[...], "thresh": int}; the tokens
+        are the lines of a vocab.txt.  slack: entries the list may stay below vocab_size (default: slack_ratio * vocab_size)."""
+        counts = np.ascontiguousarray(table["counts"], dtype=np.int64)
+        if "word_off" in table:
+            pool = np.ascontiguousarray(table["words"], dtype=np.uint8)
+            off = np.ascontiguousarray(table["word_off"], dtype=np.int64)
+            terminator = table.get("terminator")
+        else:
+            ws = [_bytes(w) for w in table["words"]]
+            pool = np.frombuffer(b"".join(ws), dtype=np.uint8)
+            off = np.zeros(len(ws) + 1, dtype=np.int64)
+            if ws:
+                off[1:] = np.cumsum([len(w) for w in ws])
+            terminator = None
+        n = len(off) - 1
+        if n < 0 or len(counts) != n:
+            raise WordPieceError("learn: word_off needs one entry more than counts")
+        if n and off[n] > pool.size:  # (the library reads word_off[n] bytes of the pool)
+            raise WordPieceError("learn: word_off ends behind the pool")
+        spec, keep = self._learn_spec(vocab_size, reserved, lower_thresh, upper_thresh, num_iterations, max_token_chars, max_unique_chars,
+                                      slack_ratio, slack, terminator, hash_bits)
+        out = LearnedVocab()
+        _check(lib().wp_learn_vocab(self._h, pool.ctypes.data if pool.size else None, off.ctypes.data if n else None,
+                                    counts.ctypes.data if n else None, n, C.byref(spec), C.byref(out)))
+        del keep
+        try:
+            k = out.n_tokens
+            data = C.string_at(out.tokens, out.n_bytes) if out.n_bytes else b""
+            toff = np.ctypeslib.as_array(C.cast(out.token_off, C.POINTER(C.c_int64)), (k + 1,)).copy()
+            scores = np.ctypeslib.as_array(C.cast(out.scores, C.POINTER(C.c_int64)), (k,)).copy() if k else np.zeros(0, dtype=np.int64)
+        finally:
+            for blk in (out.tokens, out.token_off, out.scores):
+                if blk:
+                    lib().wp_free(blk)
+        return {"tokens": [data[toff[j]:toff[j + 1] - 1].decode("utf8") for j in range(k)], "scores": scores, "thresh": int(out.thresh)}
+
+    def learn_vocab_tensor(self, words, word_off, counts, vocab_size, reserved=DEFAULT_RESERVED, lower_thresh=10, upper_thresh=10_000_000,
+                           num_iterations=4, max_token_chars=50, max_unique_chars=1000, slack_ratio=0.05, slack=None, terminator=None,
+                           hash_bits=0, copy=True):
+        """learn_vocab for a table in tensors on this handle's GPU, as count_words_tensor gives it (wp_learn_vocab_device)
+        -> {"tokens": uint8 text of the list, every token followed by a line feed, "token_off": int64 [n + 1], "scores":
+        int64 [n], "thresh": int}, tensors on that device.  copy=False: views of the library's buffers, valid until the
+        next learn call on this handle."""
+        import torch
+        if words.dtype != torch.uint8 or word_off.dtype != torch.int64 or counts.dtype != torch.int64:
+            raise WordPieceError("learn_vocab_tensor needs uint8 words and int64 word_off and counts")
+        for t in (words, word_off, counts):
+            if not t.is_cuda or not t.is_contiguous():
+                raise WordPieceError("learn_vocab_tensor needs contiguous CUDA/HIP tensors")
+        n = word_off.numel() - 1
+        if n < 0 or counts.numel() != n:
+            raise WordPieceError("learn: word_off needs one entry more than counts")
+        spec, keep = self._learn_spec(vocab_size, reserved, lower_thresh, upper_thresh, num_iterations, max_token_chars, max_unique_chars,
+                                      slack_ratio, slack, terminator, hash_bits)
+        dev = words.device
+        torch.cuda.current_stream(dev).synchronize()  # the library runs on its own HIP streams
+        out = LearnedVocab()
+        _check(lib().wp_learn_vocab_device(self._h, C.c_void_p(words.data_ptr()) if words.numel() else None, words.numel(),
+                                           C.c_void_p(word_off.data_ptr()), C.c_void_p(counts.data_ptr()) if n else None, n,
+                                           C.byref(spec), C.byref(out)))
+        del keep
+
+        def view(ptr, k, typestr, dtype):
+            if not k:
+                return torch.zeros(0, dtype=dtype, device=dev)
+            t = torch.as_tensor(DeviceIds(ptr, k, typestr=typestr), device=dev)
+            return t.clone() if copy else t
+        return {"tokens": view(out.tokens, out.n_bytes, "|u1", torch.uint8),
+                "token_off": view(out.token_off, out.n_tokens + 1, "<i8", torch.int64),
+                "scores": view(out.scores, out.n_tokens, "<i8", torch.int64), "thresh": int(out.thresh)}
+
     def align_stats(self):
         """wp_align_stats of the last call as a dict (n_rows -1: it was no align call)."""
         s = AlignStats()
@@ -1750,6 +1884,27 @@ class _Fast:
 
 
 fast = _Fast()
+
+
+def learn_vocab(text_or_docs, vocab_size, normalize=0, device=None, min_count=1, max_word_bytes=256, **kw):
+    """Text to the handle of a vocabulary learned from it: a bootstrap handle counts the words of the text (normalised
+    with the WP_NORM_* flags `normalize`) and learns the list from that table, both on the device; only the token list
+    comes to the host, where the returned Vocab (same `normalize`) is built from it.  text_or_docs: str, bytes, or a list
+    of documents; kw: the arguments of Vocab.learn_vocab_tensor (reserved, lower_thresh, ..., slack)."""
+    import torch
+    if isinstance(text_or_docs, (str, bytes, bytearray, memoryview)):
+        data = _bytes(text_or_docs)
+    else:
+        data = b"\n".join(_bytes(d) for d in text_or_docs)
+    boot = Vocab(["[UNK]"], device=device, normalize=normalize)
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
+    text = torch.zeros((len(data) + 19) // 16 * 16, dtype=torch.uint8, device=dev)
+    if data:
+        text[:len(data)] = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev)
+    table = boot.count_words_tensor(text[:len(data)], order="count", min_count=min_count, max_word_bytes=max_word_bytes, copy=False)
+    r = boot.learn_vocab_tensor(table["words"], table["word_off"], table["counts"], vocab_size, copy=False, **kw)
+    lines = bytes(r["tokens"].cpu().numpy()).split(b"\n")[:-1]
+    return Vocab(lines, device=device, normalize=normalize)
 
 
 def shard_bounds(data, world_size):

@@ -53,7 +53,8 @@ enum BoundSite {
   kSiteSpecial = 13,  // special tokens: the stores of the literal list and of the blanks, the rows and the gather of the merge (special.h)
   kSiteAlign = 14,    // span alignment: the sample of a row and the gathers from the span list (align.h)
   kSiteCount = 15,    // word counts: the stores of the word list, the groups and the table, the gathers behind them (count.h)
-  kBoundSites = 16
+  kSiteLearn = 16,    // vocabulary learner: the stores of the items, the groups and the list, the gathers behind them (learn.h)
+  kBoundSites = 17
 };
 #ifdef WP_DEBUG_BOUNDS
 __device__ unsigned int g_wp_oob[kBoundSites];

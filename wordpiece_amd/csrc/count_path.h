@@ -46,7 +46,7 @@ static wp_count_stats &begin_count_stats(wp_vocab *v) {
 }
 
 // the guard zones of one arena of the call, checked behind the kernels that wrote into it
-static void check_count_guard(Context *c, const Arena &a, hipStream_t st) {
+static void check_count_guard(Context *c, const Arena &a, hipStream_t st, const char *layer = "count") {
   if (!a.guard || a.zones.empty()) return;
   const uint32_t init[2] = {0u, 0xffffffffu};
   WP_HIP(hipMemcpyAsync(c->d_scalars + kScalarGuard, init, sizeof(init), hipMemcpyHostToDevice, st));
@@ -54,7 +54,7 @@ static void check_count_guard(Context *c, const Arena &a, hipStream_t st) {
   queue_scalar_slots(c, kScalarGuardBad, kScalarGuardFirst, st);
   WP_HIP(hipStreamSynchronize(st));
   if (c->h_scalars[kScalarGuardBad] != 0) {
-    throw HipError("arena guard: count: " + std::to_string(c->h_scalars[kScalarGuardBad]) + " guard zone(s) overwritten, first behind allocation #" +
+    throw HipError(std::string("arena guard: ") + layer + ": " + std::to_string(c->h_scalars[kScalarGuardBad]) + " guard zone(s) overwritten, first behind allocation #" +
                    std::to_string(c->h_scalars[kScalarGuardFirst] - 1));
   }
 }

@@ -2,7 +2,7 @@
 // device code is compiled in: the entry points (out-pointers, the answers that need no device, uploads and downloads),
 // the pinned pool, the multi-GPU, batch, stream, file and external calls.  The device path itself: linear_path.h
 // (word_piece::linear, stage by stage) and fast_path.h (word_piece::fast); the layers on top of it, one host header
-// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h, count_path.h; what a handle owns
+// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h; what a handle owns
 // on a device: context.h.
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -28,6 +28,7 @@
 #include "fast_path.h"
 #include "format.h"
 #include "inputs_path.h"
+#include "learn_path.h"
 #include "linear_path.h"
 #include "mask_path.h"
 #include "pack_path.h"
@@ -1335,6 +1336,104 @@ int wp_count_words_device(wp_vocab *v, const void *d_utf8, size_t nbytes, const 
       check_device_text(d_utf8);
     }
     count_on_device(v, get_context(v), static_cast<const uint8_t *>(d_utf8), nbytes, plan, d_out);
+  });
+}
+
+}  // extern "C"
+
+// ---- vocabulary learner (include/wordpiece_amd.h, section "vocabulary learner"; host path: learn_path.h) -------------
+extern "C" {
+
+int wp_get_learn_stats(const wp_vocab *v, wp_learn_stats *out) {
+  *out = v->stats.learn;
+  if (!v->stats.learn_call) out->n_words = -1;
+  return WP_OK;
+}
+
+int wp_learn_vocab(wp_vocab *v, const uint8_t *words, const int64_t *word_off, const int64_t *counts, size_t n_words, const wp_learn_spec *spec,
+                   wp_learned_vocab *out) {
+  return guarded([&] {
+    if (out) *out = wp_learned_vocab{};
+    const LearnPlan plan = check_learn_spec(spec, out);
+    if (n_words != 0 && !word_off) throw std::invalid_argument("learn: word_off is NULL");
+    if (n_words != 0 && !counts) throw std::invalid_argument("learn: counts is NULL");
+    const int64_t n_bytes = n_words ? word_off[n_words] : 0;
+    if (n_bytes < 0) throw std::invalid_argument("learn: word_off ends below 0");
+    check_learn_sizes(static_cast<size_t>(n_bytes), n_words);
+    if (n_bytes != 0 && !words) throw std::invalid_argument("learn: words is NULL");
+    if (n_words == 0) {  // (no device needed: the reserved tokens alone)
+      begin_learn_stats(v, 0);
+      const size_t n_res = plan.res_off.size() - 1;
+      wp_learned_vocab h{};
+      h.n_tokens = static_cast<int64_t>(n_res);
+      h.n_bytes = static_cast<int64_t>(plan.res.size() + n_res);
+      h.token_off = static_cast<int64_t *>(zeroed((n_res + 1) * sizeof(int64_t)));
+      if (n_res) {
+        h.scores = static_cast<int64_t *>(zeroed(n_res * sizeof(int64_t)));
+        h.tokens = static_cast<uint8_t *>(zeroed(static_cast<size_t>(h.n_bytes)));
+        size_t at = 0;
+        for (size_t r = 0; r < n_res; r++) {
+          const size_t len = plan.res_off[r + 1] - plan.res_off[r];
+          std::memcpy(h.tokens + at, plan.res.data() + plan.res_off[r], len);
+          h.tokens[at + len] = '\n';
+          at += len + 1;
+          h.token_off[r + 1] = static_cast<int64_t>(at);
+        }
+      }
+      *out = h;
+      return;
+    }
+    Context *c = get_context(v);
+    Arena in(&c->learn_in);
+    LearnIn t;
+    uint8_t *d_pool = nullptr;
+    long long *d_off = nullptr, *d_cnt = nullptr;
+    for (int pass = 0; pass < 2; pass++) {
+      d_pool = in.take<uint8_t>(static_cast<size_t>(n_bytes) + 8);
+      d_off = in.take<long long>(n_words + 1);
+      d_cnt = in.take<long long>(n_words);
+      if (pass == 0) in.commit();
+    }
+    if (n_bytes) WP_HIP(hipMemcpyAsync(d_pool, words, static_cast<size_t>(n_bytes), hipMemcpyHostToDevice, c->stream));
+    WP_HIP(hipMemcpyAsync(d_off, word_off, (n_words + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    WP_HIP(hipMemcpyAsync(d_cnt, counts, n_words * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    t.d_pool = d_pool;
+    t.n_bytes = static_cast<size_t>(n_bytes);
+    t.d_word_off = d_off;
+    t.d_counts = d_cnt;
+    t.n_words = n_words;
+    wp_learned_vocab d;
+    learn_on_device(v, c, t, plan, &d);
+    wp_learned_vocab h = d;
+    h.tokens = nullptr;
+    h.token_off = h.scores = nullptr;
+    Downloads down(c->stream);
+    if (d.n_bytes) down.add(&h.tokens, d.tokens, static_cast<size_t>(d.n_bytes));
+    down.add(&h.token_off, d.token_off, static_cast<size_t>(d.n_tokens + 1) * sizeof(int64_t));
+    if (d.n_tokens) down.add(&h.scores, d.scores, static_cast<size_t>(d.n_tokens) * sizeof(int64_t));
+    down.finish();
+    *out = h;
+  });
+}
+
+int wp_learn_vocab_device(wp_vocab *v, const void *d_words, size_t n_bytes, const int64_t *d_word_off, const int64_t *d_counts, size_t n_words,
+                          const wp_learn_spec *spec, wp_learned_vocab *d_out) {
+  return guarded([&] {
+    if (d_out) *d_out = wp_learned_vocab{};
+    const LearnPlan plan = check_learn_spec(spec, d_out);
+    check_learn_sizes(n_bytes, n_words);
+    if (n_words != 0 && !d_word_off) throw std::invalid_argument("learn: word_off is NULL");
+    if (n_words != 0 && !d_counts) throw std::invalid_argument("learn: counts is NULL");
+    if (n_bytes != 0 && !d_words) throw std::invalid_argument("learn: words is NULL");
+    check_aligned(d_word_off, 8, "learn: word_off must be 8-byte aligned");
+    check_aligned(d_counts, 8, "learn: counts must be 8-byte aligned");
+    LearnIn t;
+    t.d_pool = static_cast<const uint8_t *>(d_words);
+    t.n_bytes = n_bytes;
+    t.d_word_off = reinterpret_cast<const long long *>(d_word_off);
+    t.d_counts = reinterpret_cast<const long long *>(d_counts);
+    t.n_words = n_words;
+    learn_on_device(v, get_context(v), t, plan, d_out);
   });
 }
 

@@ -601,6 +601,56 @@ int wp_learn_vocab_device(wp_vocab *v, const void *d_words, size_t n_bytes, cons
 typedef struct { int64_t n_words, n_reserved, n_long, n_char_dropped, n_chars, n_occurrences, n_tokens, n_steps, thresh, n_rounds, n_collided; } wp_learn_stats;
 int wp_get_learn_stats(const wp_vocab *v, wp_learn_stats *out);   /* n_words == -1: no such call yet, or an encode since */
 
+/* ---- duplicate rows (an addition: the duplicate rows of a ragged batch dropped on the device, exactly; the contract is
+ * the one stated here, and tests/dedup_model.py is its executable form) ----
+ * Input.  data: a flat stream of elements of spec->elem_bytes bytes (1: text, 4: ids); row_off int64 [n_rows + 1],
+ * ascending from row_off[0] == 0, in elements: row i is the elements [row_off[i], row_off[i + 1]), and n_elems =
+ * row_off[n_rows].  These are the doc_off of the joined-documents form (the '\n' belongs to the row), the row_splits of
+ * the rows calls, or the word_off of the count call.  A row may start at any byte.  No vocabulary is read: the handle
+ * lends its device context, as it does to the learner (WP_OPT_STAGE_TIMING and WP_OPT_ARENA_GUARD are its only options
+ * that matter).
+ * Equality.  Two rows are the same iff they have the same number of elements and the same bytes; empty rows equal each
+ * other.
+ * Result, always: first int32 [n_rows], the smallest index of a row equal to row i (first[i] == i iff row i is kept);
+ * kept int32 [n_unique], the kept rows ascending, i.e. in order of first occurrence; counts int64 [n_unique], how many
+ * rows equal kept[k].  With WP_DEDUP_WANT_INVERSE: inverse int32 [n_rows] with first[i] == kept[inverse[i]] (numpy's
+ * return_inverse).  With WP_DEDUP_WANT_COMPACT: data and row_off int64 [n_unique + 1], the kept rows back to back in
+ * that order, n_elems elements — for text again a joined-documents text with its doc_off, for ids again ids and
+ * row_splits.  (n_elems of the result is 0 without WP_DEDUP_WANT_COMPACT; wp_dedup_stats.n_elems is the input's.)
+ * Exactness.  Rows are cut into chunks of 256 bytes; a row's key is the sum mod 2^64 of the seeded 64-bit hashes of its
+ * chunks, each mixed with its index in the row, plus a mix of the length.  Rows are grouped by key (a stable sort, so a
+ * group's head is its first row), every member is compared with the head chunk by chunk, and what differs is grouped
+ * again under another seed (wp_dedup_stats.n_rounds, n_collided).  No part of the result depends on a hash, on a seed
+ * or on an order of execution; hash_bits (0: 64; else 8..64) narrows the key for tests and never changes a result.  All
+ * work on bytes is flat over the chunks: its cost follows n_elems, never the longest row.
+ * WP_ERR_ARG, before a device is touched and with the field named: spec or out NULL, elem_bytes not 1 or 4, want with a
+ * bit outside 3, hash_bits not 0 and outside [8, 64], reserved not 0, row_off NULL with n_rows > 0; data NULL with
+ * n_elems > 0.  Offsets that do not start at 0 or descend give WP_ERR_ARG and name the first row i with
+ * row_off[i + 1] < row_off[i] (row 0 also where row_off[0] != 0): the host form checks on the host, the device form by
+ * a kernel.  (The host form has no length of data to check row_off[n_rows] against: that is the caller's.)
+ * WP_ERR_TOO_LARGE: n_rows >= 2^31, or n_elems * elem_bytes > UINT32_MAX.
+ * Host form: the blocks of *out are malloc'd, each freed with wp_free; a block is NULL where it is empty or was not asked
+ * for.  n_rows == 0, and a batch whose rows are all empty, are answered without a device.  Device form: d_data under
+ * the buffer contract of wp_linear_encode_device for text (4-byte aligned, readable to the next multiple of 16), 4-byte
+ * aligned for ids; d_row_off 8-byte aligned; the arrays of *d_out are device memory owned by the handle until its next
+ * call (n_rows == 0: all NULL).  Nothing behind n_elems * elem_bytes influences the result.
+ * Waits of a call: one for the sizes (the offset check, n_elems, the chunks), one per round, one that ends the call and
+ * brings the size of the compact form.  With WP_OPT_STAGE_TIMING a dedup call leaves its device times (HIP events) in
+ * the fields of wp_stats a count call uses: ms_decode (offset check and chunk list), ms_sa (the rounds: keys, sort,
+ * comparison), ms_walk (table, compact form), ms_total (their sum); ms_normalize is 0. */
+#define WP_DEDUP_WANT_INVERSE 1
+#define WP_DEDUP_WANT_COMPACT 2
+typedef struct { int32_t elem_bytes, want, hash_bits, reserved; } wp_dedup_spec;
+typedef struct { int32_t *first, *kept, *inverse; int64_t *counts, *row_off; void *data; int64_t n_rows, n_unique, n_elems; } wp_dedup_result;
+int wp_dedup_rows(wp_vocab *v, const void *data, const int64_t *row_off, size_t n_rows, const wp_dedup_spec *spec, wp_dedup_result *out);
+int wp_dedup_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row_off, size_t n_rows, const wp_dedup_spec *spec, wp_dedup_result *d_out);
+/* The statistics of the last dedup call, in a struct of its own.  n_rows, n_unique, n_empty (rows of no element), n_elems
+ * (of the input): these depend on no hash.  n_chunks: the chunks of the batch; n_compared: the elements of the chunks
+ * that were compared with their head's; n_rounds, n_collided: the grouping rounds and the rows round 0 left for later
+ * ones. */
+typedef struct { int64_t n_rows, n_unique, n_empty, n_elems, n_chunks, n_compared, n_rounds, n_collided; } wp_dedup_stats;
+int wp_get_dedup_stats(const wp_vocab *v, wp_dedup_stats *out);   /* n_rows == -1: no such call yet, or an encode since */
+
 /* The same call sharded over several GPUs of the node, behind the boundary: the reference's own
  * precedent is the in-library chunking at whitespace of linear.cpp:283-299 (thread chunks) and
  * linear.cpp:355-367 (encodeExternal batches).  The text is cut at ASCII whitespace into one shard

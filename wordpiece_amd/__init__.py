@@ -62,6 +62,7 @@ ABI_SYMBOLS = [
     "wp_align", "wp_align_device", "wp_align_rows", "wp_align_rows_device", "wp_get_align_stats",
     "wp_count_words", "wp_count_words_device", "wp_get_count_stats",
     "wp_learn_vocab", "wp_learn_vocab_device", "wp_get_learn_stats",
+    "wp_dedup_rows", "wp_dedup_rows_device", "wp_get_dedup_stats",
 ]
 
 
@@ -256,6 +257,27 @@ class LearnStats(C.Structure):
                 ("thresh", C.c_int64), ("n_rounds", C.c_int64), ("n_collided", C.c_int64)]
 
 
+WP_DEDUP_WANT_INVERSE = 1
+WP_DEDUP_WANT_COMPACT = 2
+
+
+class DedupSpec(C.Structure):
+    """wp_dedup_spec: the arguments of a dedup call (elem_bytes 1: text, 4: ids; hash_bits 0: 64)."""
+    _fields_ = [("elem_bytes", C.c_int32), ("want", C.c_int32), ("hash_bits", C.c_int32), ("reserved", C.c_int32)]
+
+
+class DedupResult(C.Structure):
+    """wp_dedup_result: the arrays of a dedup call (host blocks, or device memory owned by the handle)."""
+    _fields_ = [("first", C.c_void_p), ("kept", C.c_void_p), ("inverse", C.c_void_p), ("counts", C.c_void_p), ("row_off", C.c_void_p),
+                ("data", C.c_void_p), ("n_rows", C.c_int64), ("n_unique", C.c_int64), ("n_elems", C.c_int64)]
+
+
+class DedupStats(C.Structure):
+    """wp_dedup_stats: the statistics of the last dedup call (Vocab.dedup_stats())."""
+    _fields_ = [("n_rows", C.c_int64), ("n_unique", C.c_int64), ("n_empty", C.c_int64), ("n_elems", C.c_int64), ("n_chunks", C.c_int64),
+                ("n_compared", C.c_int64), ("n_rounds", C.c_int64), ("n_collided", C.c_int64)]
+
+
 _TEXT_SOURCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t))
 _IDS_SINK = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.c_size_t)
 
@@ -354,6 +376,10 @@ def lib():
             L.wp_learn_vocab.argtypes = [vp, vp, vp, vp, C.c_size_t, C.POINTER(LearnSpec), C.POINTER(LearnedVocab)]
             L.wp_learn_vocab_device.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(LearnSpec), C.POINTER(LearnedVocab)]
             L.wp_get_learn_stats.argtypes = [vp, C.POINTER(LearnStats)]
+        if hasattr(L, "wp_dedup_rows"):  # (WP_LIB, as above)
+            L.wp_dedup_rows.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(DedupSpec), C.POINTER(DedupResult)]
+            L.wp_dedup_rows_device.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(DedupSpec), C.POINTER(DedupResult)]
+            L.wp_get_dedup_stats.argtypes = [vp, C.POINTER(DedupStats)]
         L.wp_linear_encode_multi.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.POINTER(i32p),
                                              C.POINTER(C.c_size_t)]
         L.wp_reserve.argtypes = [vp, C.c_size_t]
@@ -1247,6 +1273,113 @@ class Vocab:
                 "token_off": view(out.token_off, out.n_tokens + 1, "<i8", torch.int64),
                 "scores": view(out.scores, out.n_tokens, "<i8", torch.int64), "thresh": int(out.thresh)}
 
+    def dedup_stats(self):
+        """wp_dedup_stats of the last dedup call as a dict (n_rows -1: no such call yet)."""
+        s = DedupStats()
+        _check(lib().wp_get_dedup_stats(self._h, C.byref(s)))
+        return {k: int(getattr(s, k)) for k, _ in s._fields_}
+
+    def dedup_rows(self, data, row_off=None, inverse=False, compact=False, hash_bits=0, raw=False):
+        """The duplicate rows of a ragged batch dropped on the device, exactly (wp_dedup_rows).  data: bytes / str / a
+        uint8 array (text, one byte per element) or an int32 array (ids); row_off: int64 [n_rows + 1] in elements,
+        ascending from 0 — or None for the lines form of a text: a row per line, its line feed included, one appended
+        where the text does not end in one.  -> {"first": np.int32 [n_rows], "kept": np.int32 [n_unique], "counts":
+        np.int64 [n_unique]}, with inverse "inverse": np.int32 [n_rows] (first[i] == kept[inverse[i]]), with compact
+        "data" and "row_off" of the kept rows back to back.  raw: text data comes back as np.uint8 rather than bytes.
+        hash_bits: for tests of the collision rounds."""
+        if isinstance(data, (str, bytes, bytearray, memoryview)):
+            data = np.frombuffer(_bytes(data), dtype=np.uint8)
+        else:
+            data = np.ascontiguousarray(data)
+        if data.dtype not in (np.uint8, np.int32) or data.ndim != 1:
+            raise WordPieceError("dedup: data must be text (bytes, uint8) or a flat int32 array")
+        if row_off is None:
+            if data.dtype != np.uint8:
+                raise WordPieceError("dedup: the lines form takes text")
+            data, row_off = line_rows(data)
+        off = np.ascontiguousarray(row_off, dtype=np.int64)
+        n = off.size - 1
+        if off.ndim != 1 or n < 0:
+            raise WordPieceError("dedup: row_off needs n_rows + 1 entries")
+        if n and off[n] > data.size:  # (the library reads row_off[n_rows] elements of data)
+            raise WordPieceError("dedup: row_off ends behind the data")
+        want = (WP_DEDUP_WANT_INVERSE if inverse else 0) | (WP_DEDUP_WANT_COMPACT if compact else 0)
+        spec = DedupSpec(data.dtype.itemsize, want, int(hash_bits), 0)
+        out = DedupResult()
+        _check(lib().wp_dedup_rows(self._h, data.ctypes.data if data.size else None, off.ctypes.data if n else None, n, C.byref(spec),
+                                   C.byref(out)))
+
+        def block(ptr, k, dtype):
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(np.ctypeslib.as_ctypes_type(dtype))), (k,)).copy() if k and ptr else \
+                np.zeros(0, dtype=dtype)
+        try:
+            u = out.n_unique
+            res = {"first": block(out.first, n, np.int32), "kept": block(out.kept, u, np.int32), "counts": block(out.counts, u, np.int64)}
+            if inverse:
+                res["inverse"] = block(out.inverse, n, np.int32)
+            if compact:
+                kept_data = block(out.data, out.n_elems, data.dtype)
+                res["data"] = kept_data if raw or data.dtype != np.uint8 else kept_data.tobytes()
+                res["row_off"] = block(out.row_off, u + 1, np.int64)
+        finally:
+            for blk in (out.first, out.kept, out.inverse, out.counts, out.row_off, out.data):
+                if blk:
+                    lib().wp_free(blk)
+        return res
+
+    def dedup_rows_tensor(self, data, row_off, inverse=False, compact=False, copy=True, hash_bits=0):
+        """dedup_rows for a batch in tensors on this handle's GPU (wp_dedup_rows_device): data uint8 (text) or int32
+        (ids), row_off int64 [n_rows + 1] — the ids and row_splits of encode_rows_tensor, a joined text and its doc_off,
+        the words and word_off of count_words_tensor.  -> a dict of tensors on that device: "first", "kept", "counts",
+        with inverse "inverse", with compact "data" and "row_off" (what encode_rows_tensor and pack_sequences_tensor
+        take).  copy=False: views of the library's buffers, valid until the next call on this handle."""
+        import torch
+        if data.dtype not in (torch.uint8, torch.int32) or row_off.dtype != torch.int64:
+            raise WordPieceError("dedup_rows_tensor needs uint8 or int32 data and int64 row_off")
+        for t in (data, row_off):
+            if not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
+                raise WordPieceError("dedup_rows_tensor needs flat contiguous CUDA/HIP tensors")
+        if self._device is not None and data.device.index != self._device:  # (raw pointers go to the handle's device)
+            raise WordPieceError("the tensors lie on %s, the handle on device %d" % (data.device, self._device))
+        n = row_off.numel() - 1
+        if n < 0:
+            raise WordPieceError("dedup: row_off needs n_rows + 1 entries")
+        nbytes = data.numel() * data.element_size()
+        if data.dtype == torch.uint8 and (data.data_ptr() % 4 != 0 or nbytes % 4 != 0):  # (the kernels read whole aligned words)
+            padded = torch.zeros((nbytes + 19) // 16 * 16, dtype=torch.uint8, device=data.device)
+            padded[:nbytes] = data
+            data = padded
+        want = (WP_DEDUP_WANT_INVERSE if inverse else 0) | (WP_DEDUP_WANT_COMPACT if compact else 0)
+        spec = DedupSpec(data.element_size(), want, int(hash_bits), 0)
+        dev = data.device
+        torch.cuda.current_stream(dev).synchronize()  # the library runs on its own HIP streams
+        out = DedupResult()
+        _check(lib().wp_dedup_rows_device(self._h, C.c_void_p(data.data_ptr()) if nbytes else None, C.c_void_p(row_off.data_ptr()), n,
+                                          C.byref(spec), C.byref(out)))
+
+        def view(ptr, k, typestr, dtype):
+            if not k or not ptr:
+                return torch.zeros(0, dtype=dtype, device=dev)
+            t = torch.as_tensor(DeviceIds(ptr, k, typestr=typestr), device=dev)
+            return t.clone() if copy else t
+        u = out.n_unique
+        res = {"first": view(out.first, n, "<i4", torch.int32), "kept": view(out.kept, u, "<i4", torch.int32),
+               "counts": view(out.counts, u, "<i8", torch.int64)}
+        if inverse:
+            res["inverse"] = view(out.inverse, n, "<i4", torch.int32)
+        if compact:
+            res["data"] = view(out.data, out.n_elems, "|u1" if data.dtype == torch.uint8 else "<i4", data.dtype)
+            res["row_off"] = view(out.row_off, u + 1, "<i8", torch.int64) if n else torch.zeros(1, dtype=torch.int64, device=dev)
+        return res
+
+    def dedup_docs(self, docs):
+        """The documents of a list (str / bytes) without their repeats, in order of first occurrence, and how often each
+        occurred -> ([documents as given: str or bytes], np.int64 counts); through join_docs and dedup_rows."""
+        docs = list(docs)
+        text, off = join_docs(docs)
+        r = self.dedup_rows(text, off)
+        return [docs[k] for k in r["kept"]], r["counts"]
+
     def align_stats(self):
         """wp_align_stats of the last call as a dict (n_rows -1: it was no align call)."""
         s = AlignStats()
@@ -1667,6 +1800,16 @@ def join_docs(docs):
     if bs:
         off[1:] = np.cumsum([len(b) + 1 for b in bs])
     return b"".join(b + b"\n" for b in bs), off
+
+
+def line_rows(text):
+    """The lines form of a text for the dedup calls: a row per line with its line feed, one appended where the text does
+    not end in one -> (np.uint8 text, int64 row_off [n_lines + 1]).  The empty text has no line."""
+    t = np.frombuffer(_bytes(text), dtype=np.uint8) if isinstance(text, (str, bytes, bytearray, memoryview)) else np.ascontiguousarray(text, dtype=np.uint8)
+    if t.size and t[-1] != 10:
+        t = np.concatenate((t, np.array([10], dtype=np.uint8)))
+    ends = np.flatnonzero(t == 10).astype(np.int64) + 1
+    return t, np.concatenate((np.zeros(1, dtype=np.int64), ends))
 
 
 def join_spans(spans):

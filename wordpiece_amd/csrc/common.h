@@ -54,7 +54,8 @@ enum BoundSite {
   kSiteAlign = 14,    // span alignment: the sample of a row and the gathers from the span list (align.h)
   kSiteCount = 15,    // word counts: the stores of the word list, the groups and the table, the gathers behind them (count.h)
   kSiteLearn = 16,    // vocabulary learner: the stores of the items, the groups and the list, the gathers behind them (learn.h)
-  kBoundSites = 17
+  kSiteDedup = 17,    // duplicate rows: the stores of the chunk list, the runs and the table, the gathers behind them (dedup.h)
+  kBoundSites = 18
 };
 #ifdef WP_DEBUG_BOUNDS
 __device__ unsigned int g_wp_oob[kBoundSites];

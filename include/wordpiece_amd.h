@@ -651,6 +651,72 @@ int wp_dedup_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row_o
 typedef struct { int64_t n_rows, n_unique, n_empty, n_elems, n_chunks, n_compared, n_rounds, n_collided; } wp_dedup_stats;
 int wp_get_dedup_stats(const wp_vocab *v, wp_dedup_stats *out);   /* n_rows == -1: no such call yet, or an encode since */
 
+/* ---- near-duplicate rows (an addition: the rows of a ragged batch clustered by MinHash signatures over shingles and LSH
+ * bands, on the device; every hash is a fixed integer function stated here, so the result is bit-exact against
+ * tests/neardup_model.py, the contract's executable form) ----
+ * Input.  As wp_dedup_rows: data, a flat stream of elements of spec->elem_bytes bytes (1: text, 4: ids), and row_off int64
+ * [n_rows + 1], ascending from 0, in elements.  No vocabulary is read: the handle lends its device context
+ * (WP_OPT_STAGE_TIMING and WP_OPT_ARENA_GUARD are its only options that matter).  Ids are the better view of text: the
+ * shingles of the tokens of an uncased handle ignore case, accents and spacing.
+ * Spec.  shingle = k in [1, 64] elements; n_perm in [1, 256]; bands >= 1 and a divisor of n_perm, r = n_perm / bands;
+ * min_agree in [0, n_perm]; want: a bit set of WP_NEARDUP_WANT_*; seed: any; reserved: 0.
+ * Functions.  M = the 64-bit finaliser (h ^= h >> 33; h *= 0xff51afd7ed558ccd; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53;
+ * h ^= h >> 33), G = 0x9e3779b97f4a7c15, all arithmetic mod 2^64.
+ *   Shingles of a row of L elements: none for L = 0; the whole row for 0 < L < k; else the L - k + 1 windows of k elements.
+ *   Shingle hash over the B bytes of the shingle: h = M(M(seed ^ G) ^ (B | 1 << 41)); for every full little-endian 64-bit
+ *   word x: h = M(h ^ x) + G; then with the rest zero-extended, or 0: h = M(h ^ x); x32 = (h ^ h >> 32) & 0xffffffff.
+ *   Permutation j: a_j = M(seed + (2j + 1) G), b_j = M(seed + (2j + 2) G), P_j(x32) = (a_j x32 + b_j) >> 32
+ *   (multiply-add-shift: strongly universal for a 32-bit x with 64-bit a and b).
+ *   Signature: sig[i][j] = the minimum over row i's shingles of P_j, as uint32; 0xffffffff for a row without shingles.
+ *   Band key of row i, band b: h = M(M(seed ^ G) ^ (b + (1 << 42))); for t < r: h = M(h ^ sig[i][b r + t]) + G.  The band
+ *   index is in the key, so the keys of all bands share one sort.
+ * Buckets.  A bucket is the set of (row, band) pairs with equal 64-bit band key; rows without shingles are in no
+ * bucket; a bucket's head is its smallest row.  The contract defines buckets by the 64-bit key: a key collision joins
+ * rows in the model exactly as on the device, and min_agree is what filters it.
+ * Edges.  Every member of a bucket whose row is not the head is compared with the head only: agree = the number of j
+ * with sig[m][j] == sig[head][j], and (m, head) is an edge iff agree >= min_agree (min_agree == 0: no signature is read).
+ * Clusters.  cluster[i] = the smallest row index in the connected component of i in the edge graph.  Equal rows with
+ * elements always share a cluster (equal signatures, equal keys).  Empty rows are each their own cluster — unlike
+ * wp_dedup_rows, which joins them: there is no shingle to compare.
+ * Result, always: cluster int32 [n_rows]; kept int32 [n_unique], the rows with cluster[i] == i, ascending; counts int64
+ * [n_unique], the component sizes.  With WP_NEARDUP_WANT_INVERSE: inverse int32 [n_rows], cluster[i] ==
+ * kept[inverse[i]].  With WP_NEARDUP_WANT_COMPACT: data and row_off int64 [n_unique + 1], the kept rows back to back,
+ * n_elems elements, as in wp_dedup_rows.  With WP_NEARDUP_WANT_SIGNATURES: signatures uint32 [n_rows, n_perm],
+ * row-major (n_perm of the result repeats the spec's).  Nothing depends on an order of execution: every combination
+ * across lanes is an integer minimum or an integer sum.
+ * WP_ERR_ARG, before a device is touched and with the field named: spec or out NULL, elem_bytes not 1 or 4, want with a
+ * bit outside 7, shingle outside [1, 64], n_perm outside [1, 256], bands below 1 or no divisor of n_perm, min_agree
+ * outside [0, n_perm], reserved not 0, row_off NULL with n_rows > 0; data NULL with n_elems > 0.  Offsets are checked as
+ * wp_dedup_rows checks them, with the first bad row named: on the host in the host form, by a kernel in the device form.
+ * WP_ERR_TOO_LARGE: n_rows >= 2^31, n_elems * elem_bytes > UINT32_MAX, n_rows * n_perm or n_rows * bands >= 2^32.
+ * WP_ERR_INTERNAL: the component rounds did not end within n_rows + 1 rounds (every round that changes a label leaves at
+ * least one root label fewer, so this cannot happen; the loop is capped all the same).
+ * Host form: the blocks of *out are malloc'd, each freed with wp_free; a block is NULL where it is empty or was not asked
+ * for.  n_rows == 0, and a batch whose rows are all empty, are answered without a device.  Device form: the buffer
+ * contract of wp_dedup_rows_device; the arrays of *d_out are device memory owned by the handle until its next call
+ * (n_rows == 0: all NULL).  Nothing behind n_elems * elem_bytes influences the result.
+ * Cost.  All work on the data is flat over the shingle positions of the batch, n_shingles * n_perm multiply-add-min
+ * steps: it follows n_elems, never the longest row.
+ * Waits of a call: one for the sizes (the offset check, n_elems, the positions), one behind the grouping (the candidate
+ * count), with min_agree > 0 one behind the comparison (the edge count), one per component round, one for the kept
+ * count, one that ends the call.  With WP_OPT_STAGE_TIMING a call
+ * leaves its device times (HIP events) in wp_stats: ms_decode (offset check and position list), ms_scan (signatures),
+ * ms_sa (band keys, sort, heads, edges), ms_walk (components, table, compact form), ms_total (their sum). */
+#define WP_ERR_INTERNAL 7
+#define WP_NEARDUP_WANT_INVERSE    1
+#define WP_NEARDUP_WANT_COMPACT    2
+#define WP_NEARDUP_WANT_SIGNATURES 4
+typedef struct { int32_t elem_bytes, want, shingle, n_perm, bands, min_agree; uint64_t seed; int32_t reserved[2]; } wp_neardup_spec;
+typedef struct { int32_t *cluster, *kept, *inverse; int64_t *counts, *row_off; void *data; uint32_t *signatures; int64_t n_rows, n_unique, n_elems, n_perm; } wp_neardup_result;
+int wp_neardup_rows(wp_vocab *v, const void *data, const int64_t *row_off, size_t n_rows, const wp_neardup_spec *spec, wp_neardup_result *out);
+int wp_neardup_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row_off, size_t n_rows, const wp_neardup_spec *spec, wp_neardup_result *d_out);
+/* The statistics of the last neardup call, in a struct of its own.  n_rows, n_unique, n_empty, n_elems (of the input),
+ * n_shingles (the shingle positions), n_buckets (buckets of more than one member), n_candidates (members compared with
+ * their head, one per (row, band) pair whose row is not the head), n_edges (the candidates that passed min_agree):
+ * functions of the contract.  n_rounds: the component rounds, which depends on the scheme and is only reported. */
+typedef struct { int64_t n_rows, n_unique, n_empty, n_elems, n_shingles, n_buckets, n_candidates, n_edges, n_rounds; } wp_neardup_stats;
+int wp_get_neardup_stats(const wp_vocab *v, wp_neardup_stats *out);   /* n_rows == -1: no such call yet, or an encode since */
+
 /* The same call sharded over several GPUs of the node, behind the boundary: the reference's own
  * precedent is the in-library chunking at whitespace of linear.cpp:283-299 (thread chunks) and
  * linear.cpp:355-367 (encodeExternal batches).  The text is cut at ASCII whitespace into one shard

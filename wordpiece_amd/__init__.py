@@ -11,6 +11,7 @@ include/wordpiece_amd.h (libwordpiece_amd.so, hand-written HIP for gfx950):
 There is no CPU fallback: without the built extension or without a GPU every call raises.
 """
 import ctypes as C
+import math
 import os
 import weakref
 
@@ -63,6 +64,7 @@ ABI_SYMBOLS = [
     "wp_count_words", "wp_count_words_device", "wp_get_count_stats",
     "wp_learn_vocab", "wp_learn_vocab_device", "wp_get_learn_stats",
     "wp_dedup_rows", "wp_dedup_rows_device", "wp_get_dedup_stats",
+    "wp_neardup_rows", "wp_neardup_rows_device", "wp_get_neardup_stats",
 ]
 
 
@@ -278,6 +280,35 @@ class DedupStats(C.Structure):
                 ("n_compared", C.c_int64), ("n_rounds", C.c_int64), ("n_collided", C.c_int64)]
 
 
+WP_NEARDUP_WANT_INVERSE = 1
+WP_NEARDUP_WANT_COMPACT = 2
+WP_NEARDUP_WANT_SIGNATURES = 4
+
+
+class NearDupSpec(C.Structure):
+    """wp_neardup_spec: the arguments of a neardup call (elem_bytes 1: text, 4: ids; shingle: elements per shingle)."""
+    _fields_ = [("elem_bytes", C.c_int32), ("want", C.c_int32), ("shingle", C.c_int32), ("n_perm", C.c_int32), ("bands", C.c_int32),
+                ("min_agree", C.c_int32), ("seed", C.c_uint64), ("reserved", C.c_int32 * 2)]
+
+
+class NearDupResult(C.Structure):
+    """wp_neardup_result: the arrays of a neardup call (host blocks, or device memory owned by the handle)."""
+    _fields_ = [("cluster", C.c_void_p), ("kept", C.c_void_p), ("inverse", C.c_void_p), ("counts", C.c_void_p), ("row_off", C.c_void_p),
+                ("data", C.c_void_p), ("signatures", C.c_void_p), ("n_rows", C.c_int64), ("n_unique", C.c_int64), ("n_elems", C.c_int64),
+                ("n_perm", C.c_int64)]
+
+
+class NearDupStats(C.Structure):
+    """wp_neardup_stats: the statistics of the last neardup call (Vocab.neardup_stats())."""
+    _fields_ = [("n_rows", C.c_int64), ("n_unique", C.c_int64), ("n_empty", C.c_int64), ("n_elems", C.c_int64), ("n_shingles", C.c_int64),
+                ("n_buckets", C.c_int64), ("n_candidates", C.c_int64), ("n_edges", C.c_int64), ("n_rounds", C.c_int64)]
+
+
+def lsh_min_agree(threshold, n_perm):
+    """The min_agree that stands for a Jaccard threshold: ceil(threshold * n_perm) signature slots."""
+    return int(math.ceil(threshold * n_perm))
+
+
 _TEXT_SOURCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t))
 _IDS_SINK = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.c_size_t)
 
@@ -380,6 +411,10 @@ def lib():
             L.wp_dedup_rows.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(DedupSpec), C.POINTER(DedupResult)]
             L.wp_dedup_rows_device.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(DedupSpec), C.POINTER(DedupResult)]
             L.wp_get_dedup_stats.argtypes = [vp, C.POINTER(DedupStats)]
+        if hasattr(L, "wp_neardup_rows"):  # (WP_LIB, as above)
+            L.wp_neardup_rows.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(NearDupSpec), C.POINTER(NearDupResult)]
+            L.wp_neardup_rows_device.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(NearDupSpec), C.POINTER(NearDupResult)]
+            L.wp_get_neardup_stats.argtypes = [vp, C.POINTER(NearDupStats)]
         L.wp_linear_encode_multi.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.POINTER(i32p),
                                              C.POINTER(C.c_size_t)]
         L.wp_reserve.argtypes = [vp, C.c_size_t]
@@ -1378,6 +1413,127 @@ class Vocab:
         docs = list(docs)
         text, off = join_docs(docs)
         r = self.dedup_rows(text, off)
+        return [docs[k] for k in r["kept"]], r["counts"]
+
+    def neardup_stats(self):
+        """wp_neardup_stats of the last neardup call as a dict (n_rows -1: no such call yet)."""
+        s = NearDupStats()
+        _check(lib().wp_get_neardup_stats(self._h, C.byref(s)))
+        return {k: int(getattr(s, k)) for k, _ in s._fields_}
+
+    @staticmethod
+    def _neardup_spec(elem_bytes, shingle, n_perm, bands, min_agree, seed, inverse, compact, signatures):
+        want = (WP_NEARDUP_WANT_INVERSE if inverse else 0) | (WP_NEARDUP_WANT_COMPACT if compact else 0) | \
+            (WP_NEARDUP_WANT_SIGNATURES if signatures else 0)
+        return NearDupSpec(elem_bytes, want, int(shingle), int(n_perm), int(bands), int(min_agree), int(seed) & (2 ** 64 - 1), (C.c_int32 * 2)(0, 0))
+
+    def neardup_rows(self, data, row_off=None, shingle=5, n_perm=128, bands=16, min_agree=0, seed=0, inverse=False, compact=False,
+                     signatures=False, raw=False):
+        """The rows of a ragged batch clustered into near-duplicates on the device (wp_neardup_rows): MinHash signatures
+        of n_perm permutations over shingles of `shingle` elements, LSH over `bands` bands, a member of a bucket joined to
+        the bucket's first row where at least min_agree signature slots agree (lsh_min_agree turns a Jaccard threshold
+        into that number), clusters = connected components.  data and row_off as dedup_rows takes them (row_off None:
+        the lines of a text).  -> {"cluster": np.int32 [n_rows] (the smallest row of the cluster), "kept": np.int32
+        [n_unique], "counts": np.int64 [n_unique]}, with inverse "inverse", with compact "data" and "row_off" of the kept
+        rows back to back, with signatures "signatures": np.uint32 [n_rows, n_perm].  raw: text data comes back as
+        np.uint8 rather than bytes."""
+        if isinstance(data, (str, bytes, bytearray, memoryview)):
+            data = np.frombuffer(_bytes(data), dtype=np.uint8)
+        else:
+            data = np.ascontiguousarray(data)
+        if data.dtype not in (np.uint8, np.int32) or data.ndim != 1:
+            raise WordPieceError("neardup: data must be text (bytes, uint8) or a flat int32 array")
+        if row_off is None:
+            if data.dtype != np.uint8:
+                raise WordPieceError("neardup: the lines form takes text")
+            data, row_off = line_rows(data)
+        off = np.ascontiguousarray(row_off, dtype=np.int64)
+        n = off.size - 1
+        if off.ndim != 1 or n < 0:
+            raise WordPieceError("neardup: row_off needs n_rows + 1 entries")
+        if n and off[n] > data.size:  # (the library reads row_off[n_rows] elements of data)
+            raise WordPieceError("neardup: row_off ends behind the data")
+        spec = self._neardup_spec(data.dtype.itemsize, shingle, n_perm, bands, min_agree, seed, inverse, compact, signatures)
+        out = NearDupResult()
+        _check(lib().wp_neardup_rows(self._h, data.ctypes.data if data.size else None, off.ctypes.data if n else None, n, C.byref(spec),
+                                     C.byref(out)))
+
+        def block(ptr, k, dtype):
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(np.ctypeslib.as_ctypes_type(dtype))), (k,)).copy() if k and ptr else \
+                np.zeros(0, dtype=dtype)
+        try:
+            u = out.n_unique
+            res = {"cluster": block(out.cluster, n, np.int32), "kept": block(out.kept, u, np.int32), "counts": block(out.counts, u, np.int64)}
+            if inverse:
+                res["inverse"] = block(out.inverse, n, np.int32)
+            if compact:
+                kept_data = block(out.data, out.n_elems, data.dtype)
+                res["data"] = kept_data if raw or data.dtype != np.uint8 else kept_data.tobytes()
+                res["row_off"] = block(out.row_off, u + 1, np.int64)
+            if signatures:
+                res["signatures"] = block(out.signatures, n * int(n_perm), np.uint32).reshape(n, int(n_perm))
+        finally:
+            for blk in (out.cluster, out.kept, out.inverse, out.counts, out.row_off, out.data, out.signatures):
+                if blk:
+                    lib().wp_free(blk)
+        return res
+
+    def neardup_rows_tensor(self, data, row_off, shingle=5, n_perm=128, bands=16, min_agree=0, seed=0, inverse=False, compact=False,
+                            signatures=False, copy=True):
+        """neardup_rows for a batch in tensors on this handle's GPU (wp_neardup_rows_device): data uint8 (text) or int32
+        (ids), row_off int64 [n_rows + 1] — the ids and row_splits of encode_rows_tensor, the compact form of
+        dedup_rows_tensor, a joined text and its doc_off.  -> a dict of tensors on that device: "cluster", "kept",
+        "counts", with inverse "inverse", with compact "data" and "row_off" (what pack_sequences_tensor takes), with
+        signatures "signatures" (int32 bit patterns of the uint32 values, [n_rows, n_perm]: torch has no uint32
+        arithmetic; .cpu().numpy().view(np.uint32) reads them).  copy=False: views of the library's buffers, valid until
+        the next call on this handle."""
+        import torch
+        if data.dtype not in (torch.uint8, torch.int32) or row_off.dtype != torch.int64:
+            raise WordPieceError("neardup_rows_tensor needs uint8 or int32 data and int64 row_off")
+        for t in (data, row_off):
+            if not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
+                raise WordPieceError("neardup_rows_tensor needs flat contiguous CUDA/HIP tensors")
+        if self._device is not None and data.device.index != self._device:  # (raw pointers go to the handle's device)
+            raise WordPieceError("the tensors lie on %s, the handle on device %d" % (data.device, self._device))
+        n = row_off.numel() - 1
+        if n < 0:
+            raise WordPieceError("neardup: row_off needs n_rows + 1 entries")
+        nbytes = data.numel() * data.element_size()
+        if data.dtype == torch.uint8 and (data.data_ptr() % 4 != 0 or nbytes % 4 != 0):  # (the kernels read whole aligned words)
+            padded = torch.zeros((nbytes + 19) // 16 * 16, dtype=torch.uint8, device=data.device)
+            padded[:nbytes] = data
+            data = padded
+        spec = self._neardup_spec(data.element_size(), shingle, n_perm, bands, min_agree, seed, inverse, compact, signatures)
+        dev = data.device
+        torch.cuda.current_stream(dev).synchronize()  # the library runs on its own HIP streams
+        out = NearDupResult()
+        _check(lib().wp_neardup_rows_device(self._h, C.c_void_p(data.data_ptr()) if nbytes else None, C.c_void_p(row_off.data_ptr()), n,
+                                            C.byref(spec), C.byref(out)))
+
+        def view(ptr, k, typestr, dtype):
+            if not k or not ptr:
+                return torch.zeros(0, dtype=dtype, device=dev)
+            t = torch.as_tensor(DeviceIds(ptr, k, typestr=typestr), device=dev)
+            return t.clone() if copy else t
+        u = out.n_unique
+        res = {"cluster": view(out.cluster, n, "<i4", torch.int32), "kept": view(out.kept, u, "<i4", torch.int32),
+               "counts": view(out.counts, u, "<i8", torch.int64)}
+        if inverse:
+            res["inverse"] = view(out.inverse, n, "<i4", torch.int32)
+        if compact:
+            res["data"] = view(out.data, out.n_elems, "|u1" if data.dtype == torch.uint8 else "<i4", data.dtype)
+            res["row_off"] = view(out.row_off, u + 1, "<i8", torch.int64) if n else torch.zeros(1, dtype=torch.int64, device=dev)
+        if signatures:
+            res["signatures"] = view(out.signatures, n * int(n_perm), "<i4", torch.int32).reshape(n, int(n_perm))
+        return res
+
+    def neardup_docs(self, docs, **kw):
+        """The documents of a list (str / bytes) without their near-duplicates: the first document of every cluster, in
+        order, and the sizes of the clusters -> ([documents as given], np.int64 counts); through join_docs and
+        neardup_rows, whose keyword arguments (shingle, n_perm, bands, min_agree, seed) pass through."""
+        docs = list(docs)
+        text, off = join_docs(docs)
+        r = self.neardup_rows(text, off, **kw)
         return [docs[k] for k in r["kept"]], r["counts"]
 
     def align_stats(self):

@@ -55,7 +55,8 @@ enum BoundSite {
   kSiteCount = 15,    // word counts: the stores of the word list, the groups and the table, the gathers behind them (count.h)
   kSiteLearn = 16,    // vocabulary learner: the stores of the items, the groups and the list, the gathers behind them (learn.h)
   kSiteDedup = 17,    // duplicate rows: the stores of the chunk list, the runs and the table, the gathers behind them (dedup.h)
-  kBoundSites = 18
+  kSiteNearDup = 18,  // near-duplicate rows: the gathers of the shingles and signatures, the stores of the edges and labels (neardup.h)
+  kBoundSites = 19
 };
 #ifdef WP_DEBUG_BOUNDS
 __device__ unsigned int g_wp_oob[kBoundSites];

@@ -1,6 +1,6 @@
 // context.h — what a vocabulary handle owns on a device: streams, vocabulary tables, bump arenas, the pool of parked
 // contexts (the C ABI itself is in encoder.hip; the device path in linear_path.h and fast_path.h, the layers on top of
-// it in rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h and dedup_path.h).
+// it in rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h and neardup_path.h).
 #pragma once
 #include <array>
 #include <cstring>
@@ -155,7 +155,7 @@ static int bit_length(uint64_t v) {
 // c->d_scalars: kScalars 32-bit words that kernels and scans leave their totals in; c->h_scalars: the pinned mirror the
 // host reads them from.  Every word has a name here and nowhere else; no call site names a number.  An encode clears
 // the whole block when it starts (and the pre-pass of WP_OPT_NORMALIZE in front of it does the same, see below).
-constexpr int kScalars = 130;
+constexpr int kScalars = 148;
 constexpr int kScalarCps = 0;       // code points of the text, 32 bits: the decode scan (linear, fast) -> host
 constexpr int kScalarAlphabet = 1;  // alphabet size: alphabet_prefix_kernel -> host
 constexpr int kScalarInvalid = 2;   // invalid sequences, 64 bits (words 2, 3): decode_count_kernel / norm_count_kernel -> host
@@ -215,6 +215,12 @@ constexpr int kScalarLearnLeft = 103, kScalarLearnKept = 104, kScalarLearnOutByt
 // 122..129, DedupCounter)
 constexpr int kScalarDedupBad = 114, kScalarDedupRuns = 115, kScalarDedupElems = 116, kScalarDedupChunks = 118, kScalarDedupLeft = 120;
 constexpr int kScalarDedupUnique = 121, kScalarDedup = 122;
+// near-duplicate rows (neardup.h): the first row whose offsets fail the check (~0: none) / the runs of the grouping /
+// row_off[n_rows], 64 bits (words 132, 133) / the shingle positions, 64 bits (words 134, 135) / the edges / whether a
+// component round lowered a label / the kept rows / the bytes of the compact form / the 64-bit counters of a call (words
+// 140..147, NearCounter)
+constexpr int kScalarNearBad = 130, kScalarNearRuns = 131, kScalarNearElems = 132, kScalarNearPositions = 134, kScalarNearEdges = 136;
+constexpr int kScalarNearChanged = 137, kScalarNearUnique = 138, kScalarNearOutBytes = 139, kScalarNear = 140;
 // normalize_on_device runs in front of the encode, which clears the block again: while it runs, four slots mean
 constexpr int kScalarNormBytes = kScalarCps;           // bytes of the normalised text, 32 bits: its scan
 constexpr int kScalarNormCps = kScalarAlphabet;        // code points of the normalised text (offsets mode) -> host
@@ -243,7 +249,10 @@ constexpr ScalarRange kScalarLayout[] = {
     {kScalarLearnRuns, 1},   {kScalarLearnLeft, 1},   {kScalarLearnKept, 1},      {kScalarLearnOutBytes, 1},
     {kScalarLearn, 8},
     {kScalarDedupBad, 1},    {kScalarDedupRuns, 1},   {kScalarDedupElems, 2},     {kScalarDedupChunks, 2},
-    {kScalarDedupLeft, 1},   {kScalarDedupUnique, 1}, {kScalarDedup, 8}};
+    {kScalarDedupLeft, 1},   {kScalarDedupUnique, 1}, {kScalarDedup, 8},
+    {kScalarNearBad, 1},     {kScalarNearRuns, 1},    {kScalarNearElems, 2},      {kScalarNearPositions, 2},
+    {kScalarNearEdges, 1},   {kScalarNearChanged, 1}, {kScalarNearUnique, 1},     {kScalarNearOutBytes, 1},
+    {kScalarNear, 8}};
 // one past the last word of the range `slot` lies in: where a download or a clear "through" that slot ends
 constexpr int scalar_end(int slot) {
   for (const ScalarRange &r : kScalarLayout) {
@@ -350,6 +359,10 @@ struct Context {
   // duplicate rows (dedup.h): the data and the offsets of a host call, the per-row arrays of the rounds (with `first`
   // of the last call), and the table and the compact form of the last call
   DeviceBuffer dedup_in, dedup_rows, dedup_out;
+  // near-duplicate rows (neardup.h): the data and the offsets of a host call, the per-row arrays (with the signatures
+  // and `cluster` of the last call), the per-item arrays of the grouping and the edge list, and the table and the
+  // compact form of the last call
+  DeviceBuffer neardup_in, neardup_rows, neardup_items, neardup_out;
   // WP_OPT_NORMALIZE (normalize.h): the tables (uploaded with the first normalising call), the normalised text, the
   // tile counts of the pre-pass, and the source of every normalised code point (offsets mode)
   uint16_t *d_norm_index = nullptr;
@@ -393,12 +406,12 @@ struct Context {
     size_t n = 0, n_text = 0;
   } dbg;
   // every DeviceBuffer above, for destroy_context, release_arenas and park_context: a new buffer is one more name here
-  std::array<DeviceBuffer *, 36> buffers() {
+  std::array<DeviceBuffer *, 40> buffers() {
     return {&text_buf, &a_buf,    &b_buf,   &fmt_buf,    &text_buf2, &ids_stage[0], &ids_stage[1], &rows_in,   &rows_out,
             &pad_buf,  &inputs_buf, &norm_buf, &norm_aux, &norm_map, &detok_in,     &detok_aux,    &detok_out,
             &pack_in,  &pack_plan,  &pack_tab, &pack_out, &special_text, &special_in, &special_lit, &special_out,
             &count_aux, &count_words, &count_out, &learn_in, &learn_aux, &learn_items, &learn_groups, &learn_out,
-            &dedup_in, &dedup_rows, &dedup_out};
+            &dedup_in, &dedup_rows, &dedup_out, &neardup_in, &neardup_rows, &neardup_items, &neardup_out};
   }
   Context() = default;
   Context(const Context &) = delete;
@@ -474,6 +487,8 @@ struct EncodeStats : wp_stats {
   int32_t learn_call;
   wp_dedup_stats dedup;  // wp_get_dedup_stats: filled by a dedup call (dedup_call 1), zero otherwise
   int32_t dedup_call;
+  wp_neardup_stats neardup;  // wp_get_neardup_stats: filled by a neardup call (neardup_call 1), zero otherwise
+  int32_t neardup_call;
 };
 
 #ifndef WP_LATE_REFINE_DEFAULT

@@ -2,7 +2,7 @@
 // device code is compiled in: the entry points (out-pointers, the answers that need no device, uploads and downloads),
 // the pinned pool, the multi-GPU, batch, stream, file and external calls.  The device path itself: linear_path.h
 // (word_piece::linear, stage by stage) and fast_path.h (word_piece::fast); the layers on top of it, one host header
-// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h; what a handle owns
+// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h; what a handle owns
 // on a device: context.h.
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -32,6 +32,7 @@
 #include "learn_path.h"
 #include "linear_path.h"
 #include "mask_path.h"
+#include "neardup_path.h"
 #include "pack_path.h"
 #include "rows_path.h"
 #include "special_path.h"
@@ -64,6 +65,9 @@ static int guarded(F &&f) {
   } catch (const std::ios_base::failure &e) {
     g_last_error = e.what();
     return WP_ERR_IO;
+  } catch (const InternalError &e) {
+    g_last_error = e.what();
+    return WP_ERR_INTERNAL;
   } catch (const std::exception &e) {
     g_last_error = e.what();
     return WP_ERR_HIP;
@@ -1524,6 +1528,106 @@ int wp_dedup_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row_o
       return;
     }
     dedup_on_device(v, get_context(v), d_data, reinterpret_cast<const long long *>(d_row_off), n_rows, plan, d_out);
+  });
+}
+
+}  // extern "C"
+
+// ---- near-duplicate rows (include/wordpiece_amd.h, section "near-duplicate rows"; host path: neardup_path.h) -----------
+extern "C" {
+
+int wp_get_neardup_stats(const wp_vocab *v, wp_neardup_stats *out) {
+  *out = v->stats.neardup;
+  if (!v->stats.neardup_call) out->n_rows = -1;
+  return WP_OK;
+}
+
+int wp_neardup_rows(wp_vocab *v, const void *data, const int64_t *row_off, size_t n_rows, const wp_neardup_spec *spec, wp_neardup_result *out) {
+  return guarded([&] {
+    if (out) *out = wp_neardup_result{};
+    const NearDupPlan plan = check_neardup_spec(spec, out);
+    if (n_rows != 0 && !row_off) throw std::invalid_argument("neardup: row_off is NULL");
+    check_neardup_rows(n_rows, plan);
+    if (n_rows != 0 && row_off[0] != 0) throw std::invalid_argument("neardup: row_off must start at 0 and never descend: row 0");
+    for (size_t r = 0; r < n_rows; r++) {
+      if (row_off[r + 1] < row_off[r]) throw std::invalid_argument("neardup: row_off must never descend: row " + std::to_string(r));
+    }
+    const unsigned long long n_elems = n_rows ? static_cast<unsigned long long>(row_off[n_rows]) : 0ull;
+    check_neardup_bytes(n_elems, plan.elem_bytes);
+    if (n_elems != 0 && !data) throw std::invalid_argument("neardup: data is NULL");
+    if (n_elems == 0) {  // (no device needed: no row, or rows that are all empty and so each a cluster of its own)
+      wp_neardup_stats &ns = begin_neardup_stats(v, n_rows);
+      wp_neardup_result h{};
+      h.n_rows = static_cast<int64_t>(n_rows);
+      h.n_perm = static_cast<int64_t>(plan.n_perm);
+      if (plan.want_compact) h.row_off = static_cast<int64_t *>(zeroed((n_rows + 1) * sizeof(int64_t)));
+      if (n_rows != 0) {
+        ns.n_unique = ns.n_empty = static_cast<int64_t>(n_rows);
+        h.n_unique = static_cast<int64_t>(n_rows);
+        h.cluster = static_cast<int32_t *>(zeroed(n_rows * sizeof(int32_t)));
+        h.kept = static_cast<int32_t *>(zeroed(n_rows * sizeof(int32_t)));
+        h.counts = static_cast<int64_t *>(zeroed(n_rows * sizeof(int64_t)));
+        if (plan.want_inverse) h.inverse = static_cast<int32_t *>(zeroed(n_rows * sizeof(int32_t)));
+        for (size_t r = 0; r < n_rows; r++) {
+          h.cluster[r] = h.kept[r] = static_cast<int32_t>(r);
+          h.counts[r] = 1;
+          if (h.inverse) h.inverse[r] = static_cast<int32_t>(r);
+        }
+        if (plan.want_signatures) {
+          const size_t bytes = n_rows * plan.n_perm * sizeof(uint32_t);
+          h.signatures = static_cast<uint32_t *>(zeroed(bytes));
+          std::memset(h.signatures, 0xff, bytes);
+        }
+      }
+      *out = h;
+      return;
+    }
+    Context *c = get_context(v);
+    const size_t n_bytes = static_cast<size_t>(n_elems) * plan.elem_bytes;
+    Arena in(&c->neardup_in);
+    uint8_t *d_data = nullptr;
+    long long *d_off = nullptr;
+    for (int pass = 0; pass < 2; pass++) {
+      d_data = in.take<uint8_t>(text_room(n_bytes));
+      d_off = in.take<long long>(n_rows + 1);
+      if (pass == 0) in.commit();
+    }
+    WP_HIP(hipMemcpyAsync(d_data, data, n_bytes, hipMemcpyHostToDevice, c->stream));
+    WP_HIP(hipMemcpyAsync(d_off, row_off, (n_rows + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    wp_neardup_result d;
+    neardup_on_device(v, c, d_data, d_off, n_rows, plan, &d);
+    wp_neardup_result h = d;
+    h.cluster = h.kept = h.inverse = nullptr;
+    h.counts = h.row_off = nullptr;
+    h.data = nullptr;
+    h.signatures = nullptr;
+    Downloads down(c->stream);
+    down.add(&h.cluster, d.cluster, n_rows * sizeof(int32_t));
+    down.add(&h.kept, d.kept, static_cast<size_t>(d.n_unique) * sizeof(int32_t));
+    down.add(&h.counts, d.counts, static_cast<size_t>(d.n_unique) * sizeof(int64_t));
+    if (d.inverse) down.add(&h.inverse, d.inverse, n_rows * sizeof(int32_t));
+    if (d.row_off) down.add(&h.row_off, d.row_off, static_cast<size_t>(d.n_unique + 1) * sizeof(int64_t));
+    if (d.data) down.add(&h.data, d.data, static_cast<size_t>(d.n_elems) * plan.elem_bytes);
+    if (d.signatures) down.add(&h.signatures, d.signatures, n_rows * plan.n_perm * sizeof(uint32_t));
+    down.finish();
+    *out = h;
+  });
+}
+
+int wp_neardup_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row_off, size_t n_rows, const wp_neardup_spec *spec,
+                           wp_neardup_result *d_out) {
+  return guarded([&] {
+    if (d_out) *d_out = wp_neardup_result{};
+    const NearDupPlan plan = check_neardup_spec(spec, d_out);
+    if (n_rows != 0 && !d_row_off) throw std::invalid_argument("neardup: row_off is NULL");
+    check_neardup_rows(n_rows, plan);
+    check_aligned(d_row_off, 8, "neardup: row_off must be 8-byte aligned");
+    check_aligned(d_data, 4, "neardup: data must be 4-byte aligned");
+    if (n_rows == 0) {  // (nothing to read and nothing to hand out: every pointer of the result stays NULL)
+      begin_neardup_stats(v, 0);
+      return;
+    }
+    neardup_on_device(v, get_context(v), d_data, reinterpret_cast<const long long *>(d_row_off), n_rows, plan, d_out);
   });
 }
 

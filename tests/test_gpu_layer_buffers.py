@@ -1,5 +1,6 @@
 """GPU tests (-m gpu) of the device buffers of the layers on top of the encoder (csrc/rows_path.h, inputs_path.h,
-mask_path.h, detok_path.h, pack_path.h, the pre-pass of csrc/normalize.h) across the calls of one handle.  Every layer
+mask_path.h, detok_path.h, pack_path.h, the pre-pass of csrc/normalize.h, and the grouping layers: count_path.h,
+learn_path.h, dedup_path.h, neardup_path.h over group_path.h) across the calls of one handle.  Every layer
 lays its buffers out with an Arena over a DeviceBuffer that grows when a call needs more than it holds, and two mistakes
 show only from one call to the next: a sequence of allocations that differs between the planning pass and the real one,
 and a pointer kept across a regrowth.  So every layer is called small, then large enough to make its buffers grow, then
@@ -15,9 +16,13 @@ import random
 import numpy as np
 import pytest
 
+import count_model as CM
+import dedup_model as DDM
 import detok_model as DM
 import inputs_model as I
+import learn_model as LM
 import mask_model as MM
+import neardup_model as NDM
 import normalize_model as NM
 import pack_model as PM
 import rows_model as R
@@ -315,3 +320,139 @@ def test_normalising_handle_offsets(gv):
         small_then_large(gv, run, 64, n_large, 8)
     finally:
         gv.set_option(W.WP_OPT_NORMALIZE, 0)
+
+
+# ---- the grouping layers ----------------------------------------------------------------------------------------------
+
+
+def _words_text(n_words, seed):
+    """n_words words of 1 to 4 letters"""
+    rng = random.Random(seed)
+    return " ".join("".join(rng.choice(LETTERS) for _ in range(rng.randint(1, 4))) for _ in range(n_words)).encode()
+
+
+@pytest.mark.gpu
+def test_count_words(gv):
+    def run(text):
+        exp = known.get(id(text)) or CM.count_words(text, order="count")
+        got = gv.count_words(text, order="count", index=True, raw=True)
+        assert got["words"].tobytes() == exp["pool"]
+        for k in ("word_off", "counts", "word_index"):
+            assert got[k].tolist() == exp[k], k
+        st = gv.count_stats()
+        assert {k: st[k] for k in exp["stats"]} == exp["stats"]
+
+    n_large = 325000
+    large = _words_text(n_large, 91)
+    exp = CM.count_words(large, order="count")  # (the model takes 2.9 s at this size)
+    known = {id(large): exp}
+    # the text in text_buf and its valid UTF-8 in norm_buf; 17 words of 32 bits and 2 of 64 per word in count_words; the
+    # pool, an offset and a count per kept word and the index in count_out.  count_aux holds three words per 2048 bytes
+    # of text: no text a test can afford makes it grow.
+    assert len(large) + 64 > GROW and (17 * 4 + 2 * 8) * n_large > GROW
+    assert len(exp["pool"]) + 16 * len(exp["counts"]) + 4 * n_large > GROW
+    small_then_large(gv, run, _words_text(64, 90), large, _words_text(8, 89))
+
+
+def _table(n_words, alphabet, max_len, seed):
+    """n_words distinct words in random order, with counts: (words as bytes, counts, pool, word_off)"""
+    rng = random.Random(seed)
+    words = set()
+    while len(words) < n_words:
+        words.add("".join(rng.choice(alphabet) for _ in range(rng.randint(1, max_len))))
+    words = sorted(words)
+    rng.shuffle(words)
+    words = [w.encode() for w in words]
+    off = np.zeros(n_words + 1, dtype=np.int64)
+    np.cumsum([len(w) for w in words], out=off[1:])
+    return words, [rng.randint(1, 40) for _ in words], np.frombuffer(b"".join(words), dtype=np.uint8), off
+
+
+@pytest.mark.gpu
+def test_learn_vocab(gv):
+    kw = dict(lower_thresh=2, upper_thresh=2, num_iterations=2, max_token_chars=8, max_unique_chars=0, slack=1 << 20)
+
+    def run(case):
+        words, counts, pool, off = case
+        exp = known.get(id(case)) or LM.learn(words, counts, 1 << 20, reserved=[b"[PAD]", b"[UNK]"], **kw)
+        got = gv.learn_vocab({"words": pool, "word_off": off, "counts": counts, "terminator": None}, 1 << 20, reserved=("[PAD]", "[UNK]"), **kw)
+        assert got["tokens"] == exp["tokens"] and got["scores"].tolist() == exp["scores"] and got["thresh"] == exp["thresh"] == 2
+        st = gv.learn_stats()
+        assert {k: st[k] for k in exp["stats"]} == exp["stats"]
+
+    large = _table(60000, LETTERS[:16], 5, 92)  # (the model takes 1.8 s on this table)
+    n, n_bytes = len(large[0]), large[2].size
+    exp = LM.learn(large[0], large[1], 1 << 20, reserved=[b"[PAD]", b"[UNK]"], **kw)
+    known = {id(large): exp}
+    n_listed = len(exp["tokens"]) - 2 - 2 * exp["stats"]["n_chars"]
+    # the pool, the offsets and the counts in learn_in; 66 bytes per occurrence in learn_items; 32 per token in
+    # learn_groups; room for the longest possible text of every listed token in learn_out
+    assert n_bytes + 16 * n > GROW and 66 * exp["stats"]["n_occurrences"] > GROW and 32 * exp["stats"]["n_tokens"] > GROW
+    assert (4 * 64 + 3) * n_listed > GROW
+    # learn_aux holds two tables of 0x110000 words from the small call on; 36 bytes per byte of the pool come on top
+    assert 36 * n_bytes > GROW + 2 * 4 * 0x110000 // 16
+    small_then_large(gv, run, _table(31, "ab", 6, 93), large, _table(8, "abc", 3, 94))
+
+
+def _ragged_rows(n_rows, seed):
+    """n_rows text rows of 0 to 9 bytes drawn from a pool of 200: (data uint8, row_off)"""
+    rng = random.Random(seed)
+    pool = [bytes(rng.randrange(97, 101) for _ in range(rng.randint(0, 9))) for _ in range(200)]
+    rows = [rng.choice(pool) for _ in range(n_rows)]
+    off = np.zeros(n_rows + 1, dtype=np.int64)
+    np.cumsum([len(r) for r in rows], out=off[1:])
+    return np.frombuffer(b"".join(rows), dtype=np.uint8), off
+
+
+def _table_equal(got, exp, keys, want, dtype):
+    """the arrays of a dedup or neardup result against the model's; the keys of the two forms of the output arena"""
+    assert sorted(got) == sorted(keys + (("inverse", "data", "row_off") if want else ()))
+    for k in got:
+        if k == "data":
+            assert got[k].dtype == dtype and got[k].tobytes() == exp[k]
+        elif k != "signatures":
+            assert got[k].tolist() == exp[k], k
+
+
+N_RAGGED = 280000  # rows of the large batch of dedup and neardup: 4 bytes of `inverse` per row are all that grows their output arenas
+
+
+@pytest.mark.gpu
+def test_dedup_rows(gv):
+    def run(case):
+        data, off = case
+        exp = DDM.dedup_rows(data.tobytes(), off, data.dtype.itemsize)
+        for want in (True, False):  # (the two layouts of dedup_out alternate)
+            got = gv.dedup_rows(data, off, inverse=want, compact=want, raw=True)
+            _table_equal(got, exp, ("first", "kept", "counts"), want, data.dtype)
+            st = gv.dedup_stats()
+            assert {k: st[k] for k in exp["stats"]} == exp["stats"]
+
+    large = _ragged_rows(N_RAGGED, 95)
+    # the offsets in dedup_in; 23 words per row in dedup_rows; the inverse alone in dedup_out (the model takes 0.25 s)
+    assert 8 * (N_RAGGED + 1) > GROW and 23 * 4 * N_RAGGED > GROW and 4 * N_RAGGED > GROW
+    small_then_large(gv, run, _cells(31, 0, 96), large, _cells(8, 4, 97))
+
+
+@pytest.mark.gpu
+def test_neardup_rows(gv):
+    spec = dict(shingle=2, n_perm=4, bands=2)
+
+    def run(case):
+        data, off = case
+        exp = known.get(id(case)) or NDM.neardup_rows(data.tobytes(), off, data.dtype.itemsize, **spec)
+        for want in (True, False):  # (the two layouts of neardup_out alternate)
+            got = gv.neardup_rows(data, off, inverse=want, compact=want, signatures=want, raw=True, **spec)
+            _table_equal(got, exp, ("cluster", "kept", "counts") + (("signatures",) if want else ()), want, data.dtype)
+            if want:
+                assert np.array_equal(got["signatures"], exp["signatures"])
+            st = gv.neardup_stats()
+            assert {k: st[k] for k in exp["stats"]} == exp["stats"]
+
+    large = _ragged_rows(N_RAGGED, 95)
+    known = {id(large): NDM.neardup_rows(large[0].tobytes(), large[1], 1, **spec)}  # (the model takes 1.1 s)
+    n_live = N_RAGGED - known[id(large)]["stats"]["n_empty"]
+    # the offsets in neardup_in; 12 words and 4 signature slots per row in neardup_rows; 60 bytes per band of a row with
+    # elements in neardup_items; the inverse alone in neardup_out
+    assert 8 * (N_RAGGED + 1) > GROW and (12 + 4) * 4 * N_RAGGED > GROW and 60 * 2 * n_live > GROW and 4 * N_RAGGED > GROW
+    small_then_large(gv, run, _cells(31, 0, 98), large, _cells(8, 4, 99))

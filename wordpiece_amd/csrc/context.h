@@ -707,6 +707,13 @@ static Context *get_context(wp_vocab *v) {
   return v->ctx.get();
 }
 
+// `bytes` zero bytes for the caller to wp_free(): the arrays of a result that no device call made
+static void *zeroed(size_t bytes) {
+  void *p = std::calloc(std::max<size_t>(bytes, 1), 1);
+  if (!p) throw std::bad_alloc();
+  return p;
+}
+
 // uploads [utf8, utf8 + nbytes) into a text buffer (grown and padded as the decoder expects: text_room) on stream st
 static void upload_text(DeviceBuffer &buf, hipStream_t st, const char *utf8, size_t nbytes) {
   buf.ensure(text_room(nbytes));

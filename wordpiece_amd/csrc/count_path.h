@@ -3,6 +3,7 @@
 #pragma once
 #include "context.h"
 #include "count.h"
+#include "group_path.h"
 #include "normalize.h"
 
 namespace wp {
@@ -45,21 +46,13 @@ static wp_count_stats &begin_count_stats(wp_vocab *v) {
   return v->stats.count;
 }
 
-// the guard zones of one arena of the call, checked behind the kernels that wrote into it
-static void check_count_guard(Context *c, const Arena &a, hipStream_t st, const char *layer = "count") {
-  if (!a.guard || a.zones.empty()) return;
-  const uint32_t init[2] = {0u, 0xffffffffu};
-  WP_HIP(hipMemcpyAsync(c->d_scalars + kScalarGuard, init, sizeof(init), hipMemcpyHostToDevice, st));
-  a.check(st, c->d_scalars + kScalarGuard);
-  queue_scalar_slots(c, kScalarGuardBad, kScalarGuardFirst, st);
-  WP_HIP(hipStreamSynchronize(st));
-  if (c->h_scalars[kScalarGuardBad] != 0) {
-    throw HipError(std::string("arena guard: ") + layer + ": " + std::to_string(c->h_scalars[kScalarGuardBad]) + " guard zone(s) overwritten, first behind allocation #" +
-                   std::to_string(c->h_scalars[kScalarGuardFirst] - 1));
-  }
+// the table of an empty text: no word, one offset; no device needed
+static wp_word_counts count_of_nothing(wp_vocab *v) {
+  begin_count_stats(v);
+  wp_word_counts h{};
+  h.word_off = static_cast<int64_t *>(zeroed(sizeof(int64_t)));
+  return h;
 }
-
-static dim3 count_grid(size_t n) { return dim3(std::max(1u, cdiv(n, kBlock))); }
 
 // The table of the text at d_text (buffer contract of the device encode), on c's stream.  The results are device
 // pointers into c->count_out (R->words, word_off, counts, word_index), valid until the handle's next call; the counted
@@ -75,16 +68,7 @@ static void count_on_device(wp_vocab *v, Context *c, const uint8_t *d_text, size
   // kMarkSorted (the rounds are over) and kMarkWalked (the table is written)
   const bool timing = v->stage_timing && nbytes != 0;
   if (nbytes != 0) normalize_on_device(c, d_text, nbytes, v->normalize, false, timing, norm);  // (flags 0: the valid UTF-8 of the text)
-  RadixStats *rs = timing ? &c->rstats : nullptr;
-  if (timing) {
-    c->rstats.passes = 0;
-    c->rstats.elems = 0;
-    c->rstats.digit_bytes = 0;
-    c->rstats.bytes = 0;
-    c->rstats.spans.used = 0;
-    c->rstats.spans.on = true;
-    WP_HIP(hipEventRecord(c->ev[kMarkStart], st));
-  }
+  RadixStats *rs = begin_stage_timing(c, timing, st);
   const size_t nb = norm.nbytes;  // (at most UINT32_MAX: the pre-pass throws std::length_error beyond)
   cs.n_text_bytes = static_cast<int64_t>(nb);
   const uint8_t *text = norm.text;
@@ -157,8 +141,7 @@ static void count_on_device(wp_vocab *v, Context *c, const uint8_t *d_text, size
     // the listed words (not long), in text order: the items of round 0
     hipLaunchKernelGGL(count_listed_kernel, count_grid(n_words), dim3(kBlock), 0, st, d_start, d_end, n_words, plan.max_bytes, d_head, d_wgroup);
     device_exclusive_scan(d_head, d_run, n_words, d_stmp, c->d_scalars + kScalarCountListed, st);
-    hipLaunchKernelGGL(count_compact_kernel, count_grid(n_words), dim3(kBlock), 0, st, d_head, d_run, n_words, static_cast<const uint32_t *>(nullptr),
-                       d_items0, n_words);
+    compact_flagged(d_head, d_run, n_words, nullptr, d_items0, st);
     WP_LAUNCH_CHECK();
     if (timing) WP_HIP(hipEventRecord(c->ev[kMarkCounted], st));
     queue_scalar_slots(c, kScalarCountListed, kScalarCountListed, st);
@@ -178,26 +161,15 @@ static void count_on_device(wp_vocab *v, Context *c, const uint8_t *d_text, size
     const int cur = radix_sort_pairs<uint64_t>(d_k0, d_v0, d_k1, d_v1, m, 0, plan.hash_bits, d_rtmp, tmp_words, st, rs, true);
     const uint64_t *keys = cur ? d_k1 : d_k0;
     const uint32_t *vals = cur ? d_v1 : d_v0;
-    const uint32_t *d_runs = c->d_scalars + kScalarCountRuns;
-    hipLaunchKernelGGL(count_heads_kernel, count_grid(m), dim3(kBlock), 0, st, keys, m, d_head);
-    device_exclusive_scan(d_head, d_run, m, d_stmp, c->d_scalars + kScalarCountRuns, st);
-    hipLaunchKernelGGL(count_head_pos_kernel, count_grid(m), dim3(kBlock), 0, st, d_head, d_run, m, d_runs, d_head_pos);
+    uint32_t *d_runs = c->d_scalars + kScalarCountRuns;
+    group_runs(keys, m, d_head, d_run, d_head_pos, d_stmp, d_runs, st);
     hipLaunchKernelGGL(count_verify_kernel, count_grid(m), dim3(kBlock), 0, st, text, d_start, d_end, items, vals, d_head, d_run, d_head_pos, m, n_words,
                        plan.max_bytes, static_cast<uint32_t>(n_groups), d_agree, d_left, d_wgroup);
     device_exclusive_scan(d_agree, d_agree_pos, m + 1, d_stmp, nullptr, st);
-    device_exclusive_scan(d_left, d_left_pos, m, d_stmp, c->d_scalars + kScalarCountLeft, st);
     hipLaunchKernelGGL(count_groups_kernel, count_grid(m), dim3(kBlock), 0, st, items, vals, d_head_pos, d_agree_pos, d_runs, m, d_gfirst + n_groups,
                        d_gcount + n_groups);
-    hipLaunchKernelGGL(count_compact_kernel, count_grid(m), dim3(kBlock), 0, st, d_left, d_left_pos, m, static_cast<const uint32_t *>(items), next, m);
-    WP_LAUNCH_CHECK();
-    queue_scalar_slots(c, kScalarCountRuns, kScalarCountLeft, st);
-    WP_HIP(hipStreamSynchronize(st));
-    const size_t runs = c->h_scalars[kScalarCountRuns], left = c->h_scalars[kScalarCountLeft];
-    if (runs == 0 || left >= m) throw HipError("count: a round settled no word");  // (every run settles its head)
-    n_groups += runs;
-    if (cs.n_rounds == 0) cs.n_collided = static_cast<int64_t>(left);
-    cs.n_rounds++;
-    m = left;
+    carry_leftovers(d_left, d_left_pos, m, items, next, d_stmp, c->d_scalars + kScalarCountLeft, st);
+    n_groups += end_round(c, kScalarCountRuns, kScalarCountLeft, "count", "word", &m, &cs, st);
     std::swap(items, next);
   }
 
@@ -255,25 +227,18 @@ static void count_on_device(wp_vocab *v, Context *c, const uint8_t *d_text, size
   if (timing) WP_HIP(hipEventRecord(c->ev[kMarkWalked], st));
   WP_HIP(hipStreamSynchronize(st));
   if (timing) {  // wp_stats, as the header's section says: the stage times of this call in the fields an encode times itself in
-    float words = 0, rounds = 0, table = 0;
-    WP_HIP(hipEventElapsedTime(&words, c->ev[kMarkStart], c->ev[kMarkCounted]));
-    WP_HIP(hipEventElapsedTime(&rounds, c->ev[kMarkCounted], c->ev[kMarkSorted]));
-    WP_HIP(hipEventElapsedTime(&table, c->ev[kMarkSorted], c->ev[kMarkWalked]));
+    const float words = mark_ms(c, kMarkStart, kMarkCounted), rounds = mark_ms(c, kMarkCounted, kMarkSorted), table = mark_ms(c, kMarkSorted, kMarkWalked);
     v->stats.ms_normalize = norm.ms;
     v->stats.ms_decode = words;
     v->stats.ms_sa = rounds;
     v->stats.ms_walk = table;
     v->stats.ms_total = norm.ms + words + rounds + table;
-    v->stats.ms_radix_scatter = c->rstats.spans.resolve();
-    v->stats.radix_passes = c->rstats.passes;
-    v->stats.radix_pass_elems = c->rstats.elems;
-    v->stats.radix_pass_bytes = c->rstats.bytes;
-    c->rstats.spans.on = false;
+    end_stage_timing(v, c);
   }
   throw_if_oob(kSiteCount, "word counts", "stores or gathers outside the word, group or table arrays skipped");
-  check_count_guard(c, aux, st);
-  check_count_guard(c, wa, st);
-  check_count_guard(c, oa, st);
+  check_arena_guard(c, aux, st, "count");
+  check_arena_guard(c, wa, st, "count");
+  check_arena_guard(c, oa, st, "count");
   R->words = pool_bytes ? d_pool : nullptr;
   R->word_off = reinterpret_cast<int64_t *>(d_word_off);
   R->counts = n_kept ? reinterpret_cast<int64_t *>(d_counts) : nullptr;

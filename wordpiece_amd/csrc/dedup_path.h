@@ -2,8 +2,8 @@
 // argument rules, the launches over a device batch, the rounds of the grouping and the buffers of a call.
 #pragma once
 #include "context.h"
-#include "count_path.h"  // count_grid, check_count_guard
 #include "dedup.h"
+#include "group_path.h"
 
 namespace wp {
 
@@ -33,9 +33,6 @@ static DedupPlan check_dedup_spec(const wp_dedup_spec *spec, const wp_dedup_resu
 static void check_dedup_rows(size_t n_rows) {
   if (n_rows >= (size_t(1) << 31)) throw std::length_error("dedup: 2^31 rows or more");
 }
-static void check_dedup_bytes(unsigned long long n_elems, uint32_t elem_bytes) {
-  if (n_elems > static_cast<unsigned long long>(UINT32_MAX) / elem_bytes) throw std::length_error("dedup: the data has more than UINT32_MAX bytes");
-}
 
 // the statistics of a dedup call before anything is known of its rows
 static wp_dedup_stats &begin_dedup_stats(wp_vocab *v, size_t n_rows) {
@@ -45,31 +42,40 @@ static wp_dedup_stats &begin_dedup_stats(wp_vocab *v, size_t n_rows) {
   return v->stats.dedup;
 }
 
-// The rows of the batch at d_data / d_row_off (n_rows >= 1), on c's stream.  The results are device pointers into
+// no row, or rows that are all empty and so all equal to row 0: no device needed
+static wp_dedup_result dedup_all_empty(wp_vocab *v, size_t n_rows, const DedupPlan &plan) {
+  wp_dedup_stats &ds = begin_dedup_stats(v, n_rows);
+  wp_dedup_result h{};
+  h.n_rows = static_cast<int64_t>(n_rows);
+  if (plan.want_compact) h.row_off = static_cast<int64_t *>(zeroed((n_rows ? 2 : 1) * sizeof(int64_t)));
+  if (n_rows == 0) return h;
+  ds.n_unique = 1;
+  ds.n_empty = static_cast<int64_t>(n_rows);
+  h.n_unique = 1;
+  h.first = static_cast<int32_t *>(zeroed(n_rows * sizeof(int32_t)));
+  h.kept = static_cast<int32_t *>(zeroed(sizeof(int32_t)));
+  h.counts = static_cast<int64_t *>(zeroed(sizeof(int64_t)));
+  h.counts[0] = static_cast<int64_t>(n_rows);
+  if (plan.want_inverse) h.inverse = static_cast<int32_t *>(zeroed(n_rows * sizeof(int32_t)));
+  return h;
+}
+
+// The rows of the batch `in` (n_rows >= 1), on c's stream.  The results are device pointers into
 // c->dedup_rows (first) and c->dedup_out (everything else), valid until the handle's next call.  Waits: the sizes (the
 // offset check, the elements, the chunks), one per round, and the one that ends the call (it brings the size of the
 // compact form, whose room was the size of the input).
-static void dedup_on_device(wp_vocab *v, Context *c, const void *d_data, const long long *d_row_off, size_t n, const DedupPlan &plan,
-                            wp_dedup_result *R) {
+static void dedup_on_device(wp_vocab *v, Context *c, const RaggedIn &in, const DedupPlan &plan, wp_dedup_result *R) {
+  const size_t n = in.n_rows;
   wp_dedup_stats &ds = begin_dedup_stats(v, n);
   *R = wp_dedup_result{};
   R->n_rows = static_cast<int64_t>(n);
   hipStream_t st = c->stream;
   const bool guard = v->arena_guard || EnvOptions::get().arena_guard;
-  const uint32_t eb = plan.elem_bytes;
+  const uint32_t eb = in.elem_bytes;
   // WP_OPT_STAGE_TIMING: the marks of a dedup call are kMarkStart, kMarkCounted (offsets checked, chunks listed),
   // kMarkSorted (the rounds are over) and kMarkWalked (the table and the compact form are written)
   const bool timing = v->stage_timing;
-  RadixStats *rs = timing ? &c->rstats : nullptr;
-  if (timing) {
-    c->rstats.passes = 0;
-    c->rstats.elems = 0;
-    c->rstats.digit_bytes = 0;
-    c->rstats.bytes = 0;
-    c->rstats.spans.used = 0;
-    c->rstats.spans.on = true;
-    WP_HIP(hipEventRecord(c->ev[kMarkStart], st));
-  }
+  RadixStats *rs = begin_stage_timing(c, timing, st);
 
   // ---- the per-row arrays, the offset check, the chunk list -------------------------------------------------------
   const size_t n1 = n + 1;
@@ -112,29 +118,22 @@ static void dedup_on_device(wp_vocab *v, Context *c, const void *d_data, const l
   unsigned long long *d_chunks = reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarDedupChunks);
   clear_scalars(c, kScalarDedupBad, kScalarDedup, st);
   WP_HIP(hipMemsetAsync(c->d_scalars + kScalarDedupBad, 0xff, sizeof(uint32_t), st));
-  hipLaunchKernelGGL(dedup_rows_kernel, count_grid(n1), dim3(kBlock), 0, st, d_row_off, n, eb, d_boff, d_nch, d_items0, d_first,
+  hipLaunchKernelGGL(dedup_rows_kernel, count_grid(n1), dim3(kBlock), 0, st, in.d_row_off, n, eb, d_boff, d_nch, d_items0, d_first,
                      c->d_scalars + kScalarDedupBad, d_elems, d_counters);
   device_exclusive_scan(d_nch, d_choff0, n1, d_stmp, nullptr, st, nullptr, d_chunks);
   WP_LAUNCH_CHECK();
   if (timing) WP_HIP(hipEventRecord(c->ev[kMarkCounted], st));
   queue_scalar_slots(c, kScalarDedupBad, kScalarDedup, st);
   WP_HIP(hipStreamSynchronize(st));
-  const uint32_t bad = c->h_scalars[kScalarDedupBad];
-  if (bad != kDedupNoBad) {
-    throw std::invalid_argument(bad == 0 ? "dedup: row_off must start at 0 and never descend: row 0"
-                                         : "dedup: row_off must never descend: row " + std::to_string(bad));
-  }
   unsigned long long elems64, chunks64, counters[kDedupCounters];
   std::memcpy(&elems64, c->h_scalars + kScalarDedupElems, sizeof(elems64));
   std::memcpy(&chunks64, c->h_scalars + kScalarDedupChunks, sizeof(chunks64));
   std::memcpy(counters, c->h_scalars + kScalarDedup, sizeof(counters));
-  check_dedup_bytes(elems64, eb);
-  const size_t n_bytes = static_cast<size_t>(elems64) * eb;
-  if (n_bytes != 0 && !d_data) throw std::invalid_argument("dedup: data is NULL");
+  const size_t n_bytes = check_ragged_device("dedup", in, c->h_scalars[kScalarDedupBad], elems64);
   ds.n_elems = static_cast<int64_t>(elems64);
   ds.n_empty = static_cast<int64_t>(counters[kDedupEmpty]);
   ds.n_chunks = static_cast<int64_t>(chunks64);
-  const uint32_t *d32 = static_cast<const uint32_t *>(d_data);
+  const uint32_t *d32 = static_cast<const uint32_t *>(in.d_data);
 
   // ---- the rounds: chunk hashes summed per row, sort, compare with the head of the run, leftovers on ------------------
   const uint64_t mask = plan.hash_bits >= 64 ? ~0ull : (1ull << plan.hash_bits) - 1ull;
@@ -152,9 +151,7 @@ static void dedup_on_device(wp_vocab *v, Context *c, const void *d_data, const l
     const uint64_t *keys = cur ? d_k1 : d_k0;
     const uint32_t *vals = cur ? d_v1 : d_v0;
     uint32_t *d_runs = c->d_scalars + kScalarDedupRuns, *d_nleft = c->d_scalars + kScalarDedupLeft;
-    hipLaunchKernelGGL(count_heads_kernel, count_grid(m), dim3(kBlock), 0, st, keys, m, d_head);
-    device_exclusive_scan(d_head, d_run, m, d_stmp, d_runs, st);
-    hipLaunchKernelGGL(count_head_pos_kernel, count_grid(m), dim3(kBlock), 0, st, d_head, d_run, m, d_runs, d_head_pos);
+    group_runs(keys, m, d_head, d_run, d_head_pos, d_stmp, d_runs, st);
     hipLaunchKernelGGL(dedup_match_kernel, count_grid(m), dim3(kBlock), 0, st, items, vals, d_head, d_run, d_head_pos, m, n, d_boff, d_head_row, d_left);
     if (mc != 0) {
       hipLaunchKernelGGL(dedup_compare_kernel, count_grid(mc), dim3(kBlock), 0, st, d32, n_bytes, d_boff, items, choff, d_head_row, m, mc, n, d_left,
@@ -163,21 +160,13 @@ static void dedup_on_device(wp_vocab *v, Context *c, const void *d_data, const l
     hipLaunchKernelGGL(dedup_settle_kernel, count_grid(m), dim3(kBlock), 0, st, items, vals, d_head_row, d_left, m, n, d_agree, d_first);
     device_exclusive_scan(d_agree, d_agree_pos, m + 1, d_stmp, nullptr, st);
     hipLaunchKernelGGL(dedup_run_counts_kernel, count_grid(m), dim3(kBlock), 0, st, items, vals, d_head_pos, d_agree_pos, d_runs, m, n, d_rcount);
-    device_exclusive_scan(d_left, d_left_pos, m, d_stmp, d_nleft, st);
-    hipLaunchKernelGGL(count_compact_kernel, count_grid(m), dim3(kBlock), 0, st, d_left, d_left_pos, m, static_cast<const uint32_t *>(items), next, m);
+    carry_leftovers(d_left, d_left_pos, m, items, next, d_stmp, d_nleft, st);
     // the chunk list of the next round: the chunks of its items, scanned
     hipLaunchKernelGGL(dedup_item_chunks_kernel, count_grid(m + 1), dim3(kBlock), 0, st, next, d_nleft, m, d_nch, n, d_icnt);
     device_exclusive_scan(d_icnt, choff_next, m + 1, d_stmp, nullptr, st, nullptr, d_chunks);
-    WP_LAUNCH_CHECK();
-    queue_scalar_slots(c, kScalarDedupRuns, kScalarDedupLeft, st);
-    WP_HIP(hipStreamSynchronize(st));
-    const size_t runs = c->h_scalars[kScalarDedupRuns], left = c->h_scalars[kScalarDedupLeft];
-    if (runs == 0 || left >= m) throw HipError("dedup: a round settled no row");  // (every run settles its head)
+    // (the slots from the runs through the leftovers hold the chunks as well: one wait)
+    n_unique += end_round(c, kScalarDedupRuns, kScalarDedupLeft, "dedup", "row", &m, &ds, st);
     std::memcpy(&chunks64, c->h_scalars + kScalarDedupChunks, sizeof(chunks64));
-    n_unique += runs;
-    if (ds.n_rounds == 0) ds.n_collided = static_cast<int64_t>(left);
-    ds.n_rounds++;
-    m = left;
     mc = static_cast<size_t>(chunks64);
     std::swap(items, next);
     std::swap(choff, choff_next);
@@ -186,36 +175,12 @@ static void dedup_on_device(wp_vocab *v, Context *c, const void *d_data, const l
   ds.n_unique = static_cast<int64_t>(n_unique);
 
   // ---- the table and the compact form ----------------------------------------------------------------------------------
-  Arena oa(&c->dedup_out, guard);
-  int32_t *d_kept = nullptr, *d_inverse = nullptr;
-  long long *d_counts = nullptr, *d_out_off = nullptr;
-  uint32_t *d_out = nullptr;
-  for (int pass = 0; pass < 2; pass++) {
-    d_kept = oa.take<int32_t>(n_unique);
-    d_counts = oa.take<long long>(n_unique);
-    if (plan.want_inverse) d_inverse = oa.take<int32_t>(n);
-    if (plan.want_compact) {
-      d_out_off = oa.take<long long>(n_unique + 1);
-      d_out = oa.take<uint32_t>(n_bytes / 4 + 1);
-    }
-    if (pass == 0) oa.commit();
-  }
-  oa.arm(st);
   uint32_t *d_keep = d_head, *d_keep_pos = d_run, *d_out_len = d_agree, *d_out_pos = d_agree_pos;  // (the rounds are over)
   hipLaunchKernelGGL(dedup_keep_kernel, count_grid(n1), dim3(kBlock), 0, st, d_first, n, d_keep);
   device_exclusive_scan(d_keep, d_keep_pos, n1, d_stmp, c->d_scalars + kScalarDedupUnique, st);
-  hipLaunchKernelGGL(dedup_table_kernel, count_grid(n), dim3(kBlock), 0, st, d_first, d_keep_pos, d_rcount, d_boff, n, n_unique, d_kept, d_counts,
-                     d_inverse, plan.want_compact ? d_out_len : static_cast<uint32_t *>(nullptr));
-  if (plan.want_compact) {
-    device_exclusive_scan(d_out_len, d_out_pos, n_unique + 1, d_stmp, nullptr, st);
-    hipLaunchKernelGGL(dedup_out_off_kernel, count_grid(n_unique + 1), dim3(kBlock), 0, st, d_out_pos, n_unique, eb, d_out_off);
-    if (n_bytes != 0) {
-      hipLaunchKernelGGL(dedup_gather_kernel, count_grid((n_bytes + 3) / 4), dim3(kBlock), 0, st, static_cast<const uint8_t *>(d_data), n_bytes, d_boff,
-                         d_kept, d_out_pos, n_unique, n, n_bytes, d_out);
-    }
-    // (the size of the compact form: the last entry of its offsets, through the word the round totals came in)
-    WP_HIP(hipMemcpyAsync(c->d_scalars + kScalarDedupLeft, d_out_pos + n_unique, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-  }
+  // (the size of the compact form comes through the word the round totals came in)
+  const GroupTable t = group_table(c, in, d_first, d_keep_pos, d_rcount, d_boff, n_unique, n_bytes, plan.want_inverse, plan.want_compact, &c->dedup_out, guard,
+                                   d_out_len, d_out_pos, d_stmp, kScalarDedupLeft, st);
   WP_LAUNCH_CHECK();
   if (timing) WP_HIP(hipEventRecord(c->ev[kMarkWalked], st));
   queue_scalar_slots(c, kScalarDedupLeft, kScalarDedup, st);
@@ -224,35 +189,19 @@ static void dedup_on_device(wp_vocab *v, Context *c, const void *d_data, const l
   ds.n_compared = static_cast<int64_t>(counters[kDedupCompared] / eb);
   if (c->h_scalars[kScalarDedupUnique] != n_unique) throw HipError("dedup: the kept rows are not the heads of the rounds");
   if (timing) {  // wp_stats, as the header's section says: the stage times of this call in the fields a count call uses
-    float list = 0, rounds = 0, table = 0;
-    WP_HIP(hipEventElapsedTime(&list, c->ev[kMarkStart], c->ev[kMarkCounted]));
-    WP_HIP(hipEventElapsedTime(&rounds, c->ev[kMarkCounted], c->ev[kMarkSorted]));
-    WP_HIP(hipEventElapsedTime(&table, c->ev[kMarkSorted], c->ev[kMarkWalked]));
+    const float list = mark_ms(c, kMarkStart, kMarkCounted), rounds = mark_ms(c, kMarkCounted, kMarkSorted), table = mark_ms(c, kMarkSorted, kMarkWalked);
     v->stats.ms_normalize = 0;
     v->stats.ms_decode = list;
     v->stats.ms_sa = rounds;
     v->stats.ms_walk = table;
     v->stats.ms_total = list + rounds + table;
-    v->stats.ms_radix_scatter = c->rstats.spans.resolve();
-    v->stats.radix_passes = c->rstats.passes;
-    v->stats.radix_pass_elems = c->rstats.elems;
-    v->stats.radix_pass_bytes = c->rstats.bytes;
-    c->rstats.spans.on = false;
+    end_stage_timing(v, c);
   }
   throw_if_oob(kSiteDedup, "duplicate rows", "stores or gathers outside the row, chunk or table arrays skipped");
-  check_count_guard(c, ra, st, "dedup");
-  check_count_guard(c, oa, st, "dedup");
+  check_arena_guard(c, ra, st, "dedup");
+  check_arena_guard(c, t.oa, st, "dedup");
   R->first = d_first;
-  R->kept = d_kept;
-  R->counts = reinterpret_cast<int64_t *>(d_counts);
-  R->inverse = d_inverse;
-  R->n_unique = static_cast<int64_t>(n_unique);
-  if (plan.want_compact) {
-    const size_t out_bytes = c->h_scalars[kScalarDedupLeft];
-    R->row_off = reinterpret_cast<int64_t *>(d_out_off);
-    R->data = out_bytes ? d_out : nullptr;
-    R->n_elems = static_cast<int64_t>(out_bytes / eb);
-  }
+  t.hand_out(R, n_unique, plan.want_compact, c->h_scalars[kScalarDedupLeft], eb);
 }
 
 }  // namespace wp

@@ -390,6 +390,19 @@ class Downloads {
   }
 };
 
+// the five fields that the results of dedup and neardup share: h's pointers cleared, d's ranges queued
+template <typename Result>
+void add_table_downloads(Downloads &down, Result &h, const Result &d, uint32_t elem_bytes) {
+  h.kept = h.inverse = nullptr;
+  h.counts = h.row_off = nullptr;
+  h.data = nullptr;
+  down.add(&h.kept, d.kept, static_cast<size_t>(d.n_unique) * sizeof(int32_t));
+  down.add(&h.counts, d.counts, static_cast<size_t>(d.n_unique) * sizeof(int64_t));
+  if (d.inverse) down.add(&h.inverse, d.inverse, static_cast<size_t>(d.n_rows) * sizeof(int32_t));
+  if (d.row_off) down.add(&h.row_off, d.row_off, static_cast<size_t>(d.n_unique + 1) * sizeof(int64_t));
+  if (d.data) down.add(&h.data, d.data, static_cast<size_t>(d.n_elems) * elem_bytes);
+}
+
 using wp_clock = std::chrono::steady_clock;
 double ms_since(wp_clock::time_point t0) { return std::chrono::duration<double, std::milli>(wp_clock::now() - t0).count(); }
 
@@ -410,12 +423,6 @@ void fill_empty_rows(size_t n, int max_len, int32_t cls_id, int32_t sep_id, int3
     while (col < max_len) row[col++] = pad_id;
     if (sample) sample[r] = static_cast<int32_t>(r);
   }
-}
-
-void *zeroed(size_t bytes) {
-  void *p = std::calloc(std::max<size_t>(bytes, 1), 1);
-  if (!p) throw std::bad_alloc();
-  return p;
 }
 
 bool ascii_space(uint8_t b) { return (b >= 0x09 && b <= 0x0d) || b == 0x20; }
@@ -1307,9 +1314,8 @@ int wp_count_words(wp_vocab *v, const char *utf8, size_t nbytes, const wp_count_
     if (out) *out = wp_word_counts{};
     const CountPlan plan = check_count_spec(spec, out);
     if (nbytes > static_cast<size_t>(UINT32_MAX)) throw std::length_error("count: nbytes above UINT32_MAX");
-    if (nbytes == 0) {  // (no device needed)
-      begin_count_stats(v);
-      out->word_off = static_cast<int64_t *>(zeroed(sizeof(int64_t)));
+    if (nbytes == 0) {
+      *out = count_of_nothing(v);
       return;
     }
     if (!utf8) throw std::invalid_argument("count: utf8 is NULL");
@@ -1366,31 +1372,12 @@ int wp_learn_vocab(wp_vocab *v, const uint8_t *words, const int64_t *word_off, c
     if (n_bytes < 0) throw std::invalid_argument("learn: word_off ends below 0");
     check_learn_sizes(static_cast<size_t>(n_bytes), n_words);
     if (n_bytes != 0 && !words) throw std::invalid_argument("learn: words is NULL");
-    if (n_words == 0) {  // (no device needed: the reserved tokens alone)
-      begin_learn_stats(v, 0);
-      const size_t n_res = plan.res_off.size() - 1;
-      wp_learned_vocab h{};
-      h.n_tokens = static_cast<int64_t>(n_res);
-      h.n_bytes = static_cast<int64_t>(plan.res.size() + n_res);
-      h.token_off = static_cast<int64_t *>(zeroed((n_res + 1) * sizeof(int64_t)));
-      if (n_res) {
-        h.scores = static_cast<int64_t *>(zeroed(n_res * sizeof(int64_t)));
-        h.tokens = static_cast<uint8_t *>(zeroed(static_cast<size_t>(h.n_bytes)));
-        size_t at = 0;
-        for (size_t r = 0; r < n_res; r++) {
-          const size_t len = plan.res_off[r + 1] - plan.res_off[r];
-          std::memcpy(h.tokens + at, plan.res.data() + plan.res_off[r], len);
-          h.tokens[at + len] = '\n';
-          at += len + 1;
-          h.token_off[r + 1] = static_cast<int64_t>(at);
-        }
-      }
-      *out = h;
+    if (n_words == 0) {
+      *out = learn_reserved_only(v, plan);
       return;
     }
     Context *c = get_context(v);
     Arena in(&c->learn_in);
-    LearnIn t;
     uint8_t *d_pool = nullptr;
     long long *d_off = nullptr, *d_cnt = nullptr;
     for (int pass = 0; pass < 2; pass++) {
@@ -1402,13 +1389,8 @@ int wp_learn_vocab(wp_vocab *v, const uint8_t *words, const int64_t *word_off, c
     if (n_bytes) WP_HIP(hipMemcpyAsync(d_pool, words, static_cast<size_t>(n_bytes), hipMemcpyHostToDevice, c->stream));
     WP_HIP(hipMemcpyAsync(d_off, word_off, (n_words + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
     WP_HIP(hipMemcpyAsync(d_cnt, counts, n_words * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    t.d_pool = d_pool;
-    t.n_bytes = static_cast<size_t>(n_bytes);
-    t.d_word_off = d_off;
-    t.d_counts = d_cnt;
-    t.n_words = n_words;
     wp_learned_vocab d;
-    learn_on_device(v, c, t, plan, &d);
+    learn_on_device(v, c, LearnIn{d_pool, static_cast<size_t>(n_bytes), d_off, d_cnt, n_words}, plan, &d);
     wp_learned_vocab h = d;
     h.tokens = nullptr;
     h.token_off = h.scores = nullptr;
@@ -1432,12 +1414,8 @@ int wp_learn_vocab_device(wp_vocab *v, const void *d_words, size_t n_bytes, cons
     if (n_bytes != 0 && !d_words) throw std::invalid_argument("learn: words is NULL");
     check_aligned(d_word_off, 8, "learn: word_off must be 8-byte aligned");
     check_aligned(d_counts, 8, "learn: counts must be 8-byte aligned");
-    LearnIn t;
-    t.d_pool = static_cast<const uint8_t *>(d_words);
-    t.n_bytes = n_bytes;
-    t.d_word_off = reinterpret_cast<const long long *>(d_word_off);
-    t.d_counts = reinterpret_cast<const long long *>(d_counts);
-    t.n_words = n_words;
+    const LearnIn t{static_cast<const uint8_t *>(d_words), n_bytes, reinterpret_cast<const long long *>(d_word_off),
+                    reinterpret_cast<const long long *>(d_counts), n_words};
     learn_on_device(v, get_context(v), t, plan, d_out);
   });
 }
@@ -1459,56 +1437,20 @@ int wp_dedup_rows(wp_vocab *v, const void *data, const int64_t *row_off, size_t 
     const DedupPlan plan = check_dedup_spec(spec, out);
     if (n_rows != 0 && !row_off) throw std::invalid_argument("dedup: row_off is NULL");
     check_dedup_rows(n_rows);
-    if (n_rows != 0 && row_off[0] != 0) throw std::invalid_argument("dedup: row_off must start at 0 and never descend: row 0");
-    for (size_t r = 0; r < n_rows; r++) {
-      if (row_off[r + 1] < row_off[r]) throw std::invalid_argument("dedup: row_off must never descend: row " + std::to_string(r));
-    }
-    const unsigned long long n_elems = n_rows ? static_cast<unsigned long long>(row_off[n_rows]) : 0ull;
-    check_dedup_bytes(n_elems, plan.elem_bytes);
-    if (n_elems != 0 && !data) throw std::invalid_argument("dedup: data is NULL");
-    if (n_elems == 0) {  // (no device needed: no row, or rows that are all empty and so all equal to row 0)
-      wp_dedup_stats &ds = begin_dedup_stats(v, n_rows);
-      wp_dedup_result h{};
-      h.n_rows = static_cast<int64_t>(n_rows);
-      if (plan.want_compact) h.row_off = static_cast<int64_t *>(zeroed((n_rows ? 2 : 1) * sizeof(int64_t)));
-      if (n_rows != 0) {
-        ds.n_unique = 1;
-        ds.n_empty = static_cast<int64_t>(n_rows);
-        h.n_unique = 1;
-        h.first = static_cast<int32_t *>(zeroed(n_rows * sizeof(int32_t)));
-        h.kept = static_cast<int32_t *>(zeroed(sizeof(int32_t)));
-        h.counts = static_cast<int64_t *>(zeroed(sizeof(int64_t)));
-        h.counts[0] = static_cast<int64_t>(n_rows);
-        if (plan.want_inverse) h.inverse = static_cast<int32_t *>(zeroed(n_rows * sizeof(int32_t)));
-      }
-      *out = h;
+    const unsigned long long n_elems = check_ragged_host("dedup", data, row_off, n_rows, plan.elem_bytes);
+    if (n_elems == 0) {
+      *out = dedup_all_empty(v, n_rows, plan);
       return;
     }
     Context *c = get_context(v);
-    const size_t n_bytes = static_cast<size_t>(n_elems) * plan.elem_bytes;
-    Arena in(&c->dedup_in);
-    uint8_t *d_data = nullptr;
-    long long *d_off = nullptr;
-    for (int pass = 0; pass < 2; pass++) {
-      d_data = in.take<uint8_t>(text_room(n_bytes));
-      d_off = in.take<long long>(n_rows + 1);
-      if (pass == 0) in.commit();
-    }
-    WP_HIP(hipMemcpyAsync(d_data, data, n_bytes, hipMemcpyHostToDevice, c->stream));
-    WP_HIP(hipMemcpyAsync(d_off, row_off, (n_rows + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    const RaggedIn in = upload_ragged(c->dedup_in, c->stream, data, row_off, n_rows, static_cast<size_t>(n_elems) * plan.elem_bytes, plan.elem_bytes);
     wp_dedup_result d;
-    dedup_on_device(v, c, d_data, d_off, n_rows, plan, &d);
+    dedup_on_device(v, c, in, plan, &d);
     wp_dedup_result h = d;
-    h.first = h.kept = h.inverse = nullptr;
-    h.counts = h.row_off = nullptr;
-    h.data = nullptr;
+    h.first = nullptr;
     Downloads down(c->stream);
     down.add(&h.first, d.first, n_rows * sizeof(int32_t));
-    down.add(&h.kept, d.kept, static_cast<size_t>(d.n_unique) * sizeof(int32_t));
-    down.add(&h.counts, d.counts, static_cast<size_t>(d.n_unique) * sizeof(int64_t));
-    if (d.inverse) down.add(&h.inverse, d.inverse, n_rows * sizeof(int32_t));
-    if (d.row_off) down.add(&h.row_off, d.row_off, static_cast<size_t>(d.n_unique + 1) * sizeof(int64_t));
-    if (d.data) down.add(&h.data, d.data, static_cast<size_t>(d.n_elems) * plan.elem_bytes);
+    add_table_downloads(down, h, d, plan.elem_bytes);
     down.finish();
     *out = h;
   });
@@ -1527,7 +1469,7 @@ int wp_dedup_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row_o
       begin_dedup_stats(v, 0);
       return;
     }
-    dedup_on_device(v, get_context(v), d_data, reinterpret_cast<const long long *>(d_row_off), n_rows, plan, d_out);
+    dedup_on_device(v, get_context(v), RaggedIn{d_data, reinterpret_cast<const long long *>(d_row_off), n_rows, plan.elem_bytes}, plan, d_out);
   });
 }
 
@@ -1548,66 +1490,21 @@ int wp_neardup_rows(wp_vocab *v, const void *data, const int64_t *row_off, size_
     const NearDupPlan plan = check_neardup_spec(spec, out);
     if (n_rows != 0 && !row_off) throw std::invalid_argument("neardup: row_off is NULL");
     check_neardup_rows(n_rows, plan);
-    if (n_rows != 0 && row_off[0] != 0) throw std::invalid_argument("neardup: row_off must start at 0 and never descend: row 0");
-    for (size_t r = 0; r < n_rows; r++) {
-      if (row_off[r + 1] < row_off[r]) throw std::invalid_argument("neardup: row_off must never descend: row " + std::to_string(r));
-    }
-    const unsigned long long n_elems = n_rows ? static_cast<unsigned long long>(row_off[n_rows]) : 0ull;
-    check_neardup_bytes(n_elems, plan.elem_bytes);
-    if (n_elems != 0 && !data) throw std::invalid_argument("neardup: data is NULL");
-    if (n_elems == 0) {  // (no device needed: no row, or rows that are all empty and so each a cluster of its own)
-      wp_neardup_stats &ns = begin_neardup_stats(v, n_rows);
-      wp_neardup_result h{};
-      h.n_rows = static_cast<int64_t>(n_rows);
-      h.n_perm = static_cast<int64_t>(plan.n_perm);
-      if (plan.want_compact) h.row_off = static_cast<int64_t *>(zeroed((n_rows + 1) * sizeof(int64_t)));
-      if (n_rows != 0) {
-        ns.n_unique = ns.n_empty = static_cast<int64_t>(n_rows);
-        h.n_unique = static_cast<int64_t>(n_rows);
-        h.cluster = static_cast<int32_t *>(zeroed(n_rows * sizeof(int32_t)));
-        h.kept = static_cast<int32_t *>(zeroed(n_rows * sizeof(int32_t)));
-        h.counts = static_cast<int64_t *>(zeroed(n_rows * sizeof(int64_t)));
-        if (plan.want_inverse) h.inverse = static_cast<int32_t *>(zeroed(n_rows * sizeof(int32_t)));
-        for (size_t r = 0; r < n_rows; r++) {
-          h.cluster[r] = h.kept[r] = static_cast<int32_t>(r);
-          h.counts[r] = 1;
-          if (h.inverse) h.inverse[r] = static_cast<int32_t>(r);
-        }
-        if (plan.want_signatures) {
-          const size_t bytes = n_rows * plan.n_perm * sizeof(uint32_t);
-          h.signatures = static_cast<uint32_t *>(zeroed(bytes));
-          std::memset(h.signatures, 0xff, bytes);
-        }
-      }
-      *out = h;
+    const unsigned long long n_elems = check_ragged_host("neardup", data, row_off, n_rows, plan.elem_bytes);
+    if (n_elems == 0) {
+      *out = neardup_all_empty(v, n_rows, plan);
       return;
     }
     Context *c = get_context(v);
-    const size_t n_bytes = static_cast<size_t>(n_elems) * plan.elem_bytes;
-    Arena in(&c->neardup_in);
-    uint8_t *d_data = nullptr;
-    long long *d_off = nullptr;
-    for (int pass = 0; pass < 2; pass++) {
-      d_data = in.take<uint8_t>(text_room(n_bytes));
-      d_off = in.take<long long>(n_rows + 1);
-      if (pass == 0) in.commit();
-    }
-    WP_HIP(hipMemcpyAsync(d_data, data, n_bytes, hipMemcpyHostToDevice, c->stream));
-    WP_HIP(hipMemcpyAsync(d_off, row_off, (n_rows + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    const RaggedIn in = upload_ragged(c->neardup_in, c->stream, data, row_off, n_rows, static_cast<size_t>(n_elems) * plan.elem_bytes, plan.elem_bytes);
     wp_neardup_result d;
-    neardup_on_device(v, c, d_data, d_off, n_rows, plan, &d);
+    neardup_on_device(v, c, in, plan, &d);
     wp_neardup_result h = d;
-    h.cluster = h.kept = h.inverse = nullptr;
-    h.counts = h.row_off = nullptr;
-    h.data = nullptr;
+    h.cluster = nullptr;
     h.signatures = nullptr;
     Downloads down(c->stream);
     down.add(&h.cluster, d.cluster, n_rows * sizeof(int32_t));
-    down.add(&h.kept, d.kept, static_cast<size_t>(d.n_unique) * sizeof(int32_t));
-    down.add(&h.counts, d.counts, static_cast<size_t>(d.n_unique) * sizeof(int64_t));
-    if (d.inverse) down.add(&h.inverse, d.inverse, n_rows * sizeof(int32_t));
-    if (d.row_off) down.add(&h.row_off, d.row_off, static_cast<size_t>(d.n_unique + 1) * sizeof(int64_t));
-    if (d.data) down.add(&h.data, d.data, static_cast<size_t>(d.n_elems) * plan.elem_bytes);
+    add_table_downloads(down, h, d, plan.elem_bytes);
     if (d.signatures) down.add(&h.signatures, d.signatures, n_rows * plan.n_perm * sizeof(uint32_t));
     down.finish();
     *out = h;
@@ -1627,7 +1524,7 @@ int wp_neardup_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row
       begin_neardup_stats(v, 0);
       return;
     }
-    neardup_on_device(v, get_context(v), d_data, reinterpret_cast<const long long *>(d_row_off), n_rows, plan, d_out);
+    neardup_on_device(v, get_context(v), RaggedIn{d_data, reinterpret_cast<const long long *>(d_row_off), n_rows, plan.elem_bytes}, plan, d_out);
   });
 }
 

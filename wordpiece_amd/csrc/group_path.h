@@ -1,0 +1,204 @@
+// group_path.h — what the layers that group items by a 64-bit key share on a context (word counts: count_path.h, the
+// vocabulary learner: learn_path.h, duplicate rows: dedup_path.h, near-duplicate rows: neardup_path.h; kernels: count.h,
+// and dedup.h for the table): the launch grid, the arena-guard check, the stage timing of a call, the run heads of a
+// sorted key list, the end of a collision round, a ragged batch on the device and the table with its compact form.
+#pragma once
+#include "context.h"
+#include "count.h"
+#include "dedup.h"  // the table kernels, kDedupNoBad
+
+namespace wp {
+
+static dim3 count_grid(size_t n) { return dim3(std::max(1u, cdiv(n, kBlock))); }
+
+// the guard zones of one arena of the call, checked behind the kernels that wrote into it
+static void check_arena_guard(Context *c, const Arena &a, hipStream_t st, const char *layer) {
+  if (!a.guard || a.zones.empty()) return;
+  const uint32_t init[2] = {0u, 0xffffffffu};
+  WP_HIP(hipMemcpyAsync(c->d_scalars + kScalarGuard, init, sizeof(init), hipMemcpyHostToDevice, st));
+  a.check(st, c->d_scalars + kScalarGuard);
+  queue_scalar_slots(c, kScalarGuardBad, kScalarGuardFirst, st);
+  WP_HIP(hipStreamSynchronize(st));
+  if (c->h_scalars[kScalarGuardBad] != 0) {
+    throw HipError(std::string("arena guard: ") + layer + ": " + std::to_string(c->h_scalars[kScalarGuardBad]) + " guard zone(s) overwritten, first behind allocation #" +
+                   std::to_string(c->h_scalars[kScalarGuardFirst] - 1));
+  }
+}
+
+// ---- WP_OPT_STAGE_TIMING ----------------------------------------------------------------------------------------------
+// A timed call starts here: the radix statistics from zero, their spans on, kMarkStart recorded.  Returns what the sorts
+// of the call report into (nullptr: the call is not timed).
+static RadixStats *begin_stage_timing(Context *c, bool timing, hipStream_t st) {
+  if (!timing) return nullptr;
+  c->rstats.passes = 0;
+  c->rstats.elems = 0;
+  c->rstats.digit_bytes = 0;
+  c->rstats.bytes = 0;
+  c->rstats.spans.used = 0;
+  c->rstats.spans.on = true;
+  WP_HIP(hipEventRecord(c->ev[kMarkStart], st));
+  return &c->rstats;
+}
+// ... and ends here, behind the last wait: the radix fields of wp_stats, the spans off
+static void end_stage_timing(wp_vocab *v, Context *c) {
+  v->stats.ms_radix_scatter = c->rstats.spans.resolve();
+  v->stats.radix_passes = c->rstats.passes;
+  v->stats.radix_pass_elems = c->rstats.elems;
+  v->stats.radix_pass_bytes = c->rstats.bytes;
+  c->rstats.spans.on = false;
+}
+static float mark_ms(Context *c, int from, int to) {
+  float ms = 0;
+  WP_HIP(hipEventElapsedTime(&ms, c->ev[from], c->ev[to]));
+  return ms;
+}
+
+// ---- the round protocol ----------------------------------------------------------------------------------
+// The runs of m sorted keys: d_head[s] marks the first item of a run, d_run is the exclusive scan of the marks,
+// d_head_pos[r] the position of the head of run r (and m behind the last), *d_runs the number of runs.
+static void group_runs(const uint64_t *keys, size_t m, uint32_t *d_head, uint32_t *d_run, uint32_t *d_head_pos, uint32_t *d_stmp, uint32_t *d_runs,
+                       hipStream_t st) {
+  hipLaunchKernelGGL(count_heads_kernel, count_grid(m), dim3(kBlock), 0, st, keys, m, d_head);
+  device_exclusive_scan(d_head, d_run, m, d_stmp, d_runs, st);
+  hipLaunchKernelGGL(count_head_pos_kernel, count_grid(m), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_head), static_cast<const uint32_t *>(d_run),
+                     m, static_cast<const uint32_t *>(d_runs), d_head_pos);
+}
+
+// out[pos[i]] = src ? src[i] : i for the flagged i < n, in order (out has room for n)
+static void compact_flagged(const uint32_t *flag, const uint32_t *pos, size_t n, const uint32_t *src, uint32_t *out, hipStream_t st) {
+  hipLaunchKernelGGL(count_compact_kernel, count_grid(n), dim3(kBlock), 0, st, flag, pos, n, src, out, n);
+}
+
+// The end of a collision round, in two steps so that a layer can queue work on `next` in front of the round's one wait.
+// First the items the round's head comparison flagged in d_left go to `next`, in order, and their number to *d_nleft.
+static void carry_leftovers(const uint32_t *d_left, uint32_t *d_left_pos, size_t m, const uint32_t *items, uint32_t *next, uint32_t *d_stmp,
+                            uint32_t *d_nleft, hipStream_t st) {
+  device_exclusive_scan(d_left, d_left_pos, m, d_stmp, d_nleft, st);
+  compact_flagged(d_left, d_left_pos, m, items, next, st);
+}
+// Then the wait: it brings the scalar slots from slot_runs through slot_left.  Every run settles at least its head, so
+// a round with no run or with nothing settled is an error.  Counts the round in the layer's statistics, leaves the
+// leftovers in *m and returns the number of runs, each a new group.
+template <typename Stats>
+static size_t end_round(Context *c, int slot_runs, int slot_left, const char *layer, const char *noun, size_t *m, Stats *stats, hipStream_t st) {
+  WP_LAUNCH_CHECK();
+  queue_scalar_slots(c, slot_runs, slot_left, st);
+  WP_HIP(hipStreamSynchronize(st));
+  const size_t runs = c->h_scalars[slot_runs], left = c->h_scalars[slot_left];
+  if (runs == 0 || left >= *m) throw HipError(std::string(layer) + ": a round settled no " + noun);
+  if (stats->n_rounds == 0) stats->n_collided = static_cast<int64_t>(left);
+  stats->n_rounds++;
+  *m = left;
+  return runs;
+}
+
+// ---- a ragged batch ---------------------------------------------------------------------------------------------------
+// rows of elem_bytes-wide elements back to back at d_data, row r from d_row_off[r] to d_row_off[r + 1] (in elements)
+struct RaggedIn {
+  const void *d_data = nullptr;
+  const long long *d_row_off = nullptr;
+  size_t n_rows = 0;
+  uint32_t elem_bytes = 1;
+};
+
+static void check_ragged_bytes(const char *layer, unsigned long long n_elems, uint32_t elem_bytes) {
+  if (n_elems > static_cast<unsigned long long>(UINT32_MAX) / elem_bytes) throw std::length_error(std::string(layer) + ": the data has more than UINT32_MAX bytes");
+}
+static void throw_bad_row(const char *layer, size_t row) {
+  throw std::invalid_argument(std::string(layer) + (row == 0 ? ": row_off must start at 0 and never descend: row 0" : ": row_off must never descend: row " + std::to_string(row)));
+}
+
+// the offsets of a batch in host memory, walked: returns the number of elements
+static unsigned long long check_ragged_host(const char *layer, const void *data, const int64_t *row_off, size_t n_rows, uint32_t elem_bytes) {
+  if (n_rows != 0 && row_off[0] != 0) throw_bad_row(layer, 0);
+  for (size_t r = 0; r < n_rows; r++) {
+    if (row_off[r + 1] < row_off[r]) throw_bad_row(layer, r);
+  }
+  const unsigned long long n_elems = n_rows ? static_cast<unsigned long long>(row_off[n_rows]) : 0ull;
+  check_ragged_bytes(layer, n_elems, elem_bytes);
+  if (n_elems != 0 && !data) throw std::invalid_argument(std::string(layer) + ": data is NULL");
+  return n_elems;
+}
+
+// the batch of a host call into `buf`, data | row_off, on st (the data with the room of a text: the kernels read whole aligned words)
+static RaggedIn upload_ragged(DeviceBuffer &buf, hipStream_t st, const void *data, const int64_t *row_off, size_t n_rows, size_t n_bytes, uint32_t elem_bytes) {
+  Arena in(&buf);
+  uint8_t *d_data = nullptr;
+  long long *d_off = nullptr;
+  for (int pass = 0; pass < 2; pass++) {
+    d_data = in.take<uint8_t>(text_room(n_bytes));
+    d_off = in.take<long long>(n_rows + 1);
+    if (pass == 0) in.commit();
+  }
+  WP_HIP(hipMemcpyAsync(d_data, data, n_bytes, hipMemcpyHostToDevice, st));
+  WP_HIP(hipMemcpyAsync(d_off, row_off, (n_rows + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+  return RaggedIn{d_data, d_off, n_rows, elem_bytes};
+}
+
+// what the layer's row kernel found, behind the wait that brought it: `bad` the first row whose offsets fail the check
+// (kDedupNoBad: none), n_elems the last offset.  Returns the bytes of the data.
+static size_t check_ragged_device(const char *layer, const RaggedIn &in, uint32_t bad, unsigned long long n_elems) {
+  if (bad != kDedupNoBad) throw_bad_row(layer, bad);
+  check_ragged_bytes(layer, n_elems, in.elem_bytes);
+  if (n_elems != 0 && !in.d_data) throw std::invalid_argument(std::string(layer) + ": data is NULL");
+  return static_cast<size_t>(n_elems) * in.elem_bytes;
+}
+
+// ---- the table and the compact form ----------------------------------------------------------------------
+// device pointers into the output buffer of the call, with the arena that laid them out (for the caller's guard check)
+struct GroupTable {
+  Arena oa;
+  int32_t *d_kept = nullptr, *d_inverse = nullptr;
+  long long *d_counts = nullptr, *d_out_off = nullptr;
+  uint32_t *d_out = nullptr;
+  // into a layer's result, behind the caller's last wait (out_bytes: the word that wait brought from the out-bytes slot)
+  template <typename Result>
+  void hand_out(Result *R, size_t n_unique, bool want_compact, size_t out_bytes, uint32_t elem_bytes) const {
+    R->kept = d_kept;
+    R->counts = reinterpret_cast<int64_t *>(d_counts);
+    R->inverse = d_inverse;
+    R->n_unique = static_cast<int64_t>(n_unique);
+    if (!want_compact) return;
+    R->row_off = reinterpret_cast<int64_t *>(d_out_off);
+    R->data = out_bytes ? d_out : nullptr;
+    R->n_elems = static_cast<int64_t>(out_bytes / elem_bytes);
+  }
+};
+
+// d_rep[i]: the representative of row i (itself where the row is kept); d_keep_pos: the scan of the kept flags;
+// d_rcount: the rows each kept row stands for; d_boff: the byte offsets of the rows of `in`.  Lays `out` out, queues the
+// table, with want_compact the kept rows back to back (room: the n_bytes of the input) and the copy of their size into
+// slot_out_bytes.  No wait: the caller's last one brings that slot.  d_out_len, d_out_pos: n_rows + 1 words of scratch.
+static GroupTable group_table(Context *c, const RaggedIn &in, const int32_t *d_rep, const uint32_t *d_keep_pos, const uint32_t *d_rcount, const uint32_t *d_boff,
+                              size_t n_unique, size_t n_bytes, bool want_inverse, bool want_compact, DeviceBuffer *out, bool guard, uint32_t *d_out_len,
+                              uint32_t *d_out_pos, uint32_t *d_stmp, int slot_out_bytes, hipStream_t st) {
+  const size_t n = in.n_rows;
+  GroupTable t{Arena(out, guard)};
+  for (int pass = 0; pass < 2; pass++) {
+    t.d_kept = t.oa.take<int32_t>(n_unique);
+    t.d_counts = t.oa.take<long long>(n_unique);
+    if (want_inverse) t.d_inverse = t.oa.take<int32_t>(n);
+    if (want_compact) {
+      t.d_out_off = t.oa.take<long long>(n_unique + 1);
+      t.d_out = t.oa.take<uint32_t>(n_bytes / 4 + 1);
+    }
+    if (pass == 0) t.oa.commit();
+  }
+  t.oa.arm(st);
+  hipLaunchKernelGGL(dedup_table_kernel, count_grid(n), dim3(kBlock), 0, st, d_rep, d_keep_pos, d_rcount, d_boff, n, n_unique, t.d_kept, t.d_counts,
+                     t.d_inverse, want_compact ? d_out_len : static_cast<uint32_t *>(nullptr));
+  if (want_compact) {
+    device_exclusive_scan(d_out_len, d_out_pos, n_unique + 1, d_stmp, nullptr, st);
+    hipLaunchKernelGGL(dedup_out_off_kernel, count_grid(n_unique + 1), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_out_pos), n_unique,
+                       in.elem_bytes, t.d_out_off);
+    if (n_bytes != 0) {
+      hipLaunchKernelGGL(dedup_gather_kernel, count_grid((n_bytes + 3) / 4), dim3(kBlock), 0, st, static_cast<const uint8_t *>(in.d_data), n_bytes, d_boff,
+                         static_cast<const int32_t *>(t.d_kept), static_cast<const uint32_t *>(d_out_pos), n_unique, n, n_bytes, t.d_out);
+    }
+    // (the size of the compact form: the last entry of its offsets)
+    WP_HIP(hipMemcpyAsync(c->d_scalars + slot_out_bytes, d_out_pos + n_unique, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+  }
+  return t;
+}
+
+}  // namespace wp

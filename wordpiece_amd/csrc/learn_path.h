@@ -6,7 +6,7 @@
 #include <array>
 
 #include "context.h"
-#include "count_path.h"  // check_count_guard, count_grid
+#include "group_path.h"
 #include "learn.h"
 
 namespace wp {
@@ -78,6 +78,28 @@ struct LearnIn {
 static void check_learn_sizes(size_t n_bytes, size_t n_words) {
   if (n_bytes > static_cast<size_t>(UINT32_MAX)) throw std::length_error("learn: a pool of more than UINT32_MAX bytes");
   if (n_words >= (size_t(1) << 31)) throw std::length_error("learn: the table has 2^31 words or more");
+}
+
+// the list of a table without words, the reserved tokens alone: no device needed
+static wp_learned_vocab learn_reserved_only(wp_vocab *v, const LearnPlan &plan) {
+  begin_learn_stats(v, 0);
+  const size_t n_res = plan.res_off.size() - 1;
+  wp_learned_vocab h{};
+  h.n_tokens = static_cast<int64_t>(n_res);
+  h.n_bytes = static_cast<int64_t>(plan.res.size() + n_res);
+  h.token_off = static_cast<int64_t *>(zeroed((n_res + 1) * sizeof(int64_t)));
+  if (n_res == 0) return h;
+  h.scores = static_cast<int64_t *>(zeroed(n_res * sizeof(int64_t)));
+  h.tokens = static_cast<uint8_t *>(zeroed(static_cast<size_t>(h.n_bytes)));
+  size_t at = 0;
+  for (size_t r = 0; r < n_res; r++) {
+    const size_t len = plan.res_off[r + 1] - plan.res_off[r];
+    std::memcpy(h.tokens + at, plan.res.data() + plan.res_off[r], len);
+    h.tokens[at + len] = '\n';
+    at += len + 1;
+    h.token_off[r + 1] = static_cast<int64_t>(at);
+  }
+  return h;
 }
 
 // The list learned from the table `in`, on c's stream.  The results are device pointers into c->learn_out, valid until
@@ -239,24 +261,13 @@ static void learn_on_device(wp_vocab *v, Context *c, const LearnIn &in, const Le
       const int cur = radix_sort_pairs<uint64_t>(d_k0, d_v0, d_k1, d_v1, m, 0, plan.hash_bits, d_rtmp, tmp_words, st, rs, true);
       const uint64_t *keys = cur ? d_k1 : d_k0;
       const uint32_t *vals = cur ? d_v1 : d_v0;
-      const uint32_t *d_runs = c->d_scalars + kScalarLearnRuns;
-      hipLaunchKernelGGL(count_heads_kernel, count_grid(m), dim3(kBlock), 0, st, keys, m, d_head);
-      device_exclusive_scan(d_head, d_run, m, d_istmp, c->d_scalars + kScalarLearnRuns, st);
-      hipLaunchKernelGGL(count_head_pos_kernel, count_grid(m), dim3(kBlock), 0, st, d_head, d_run, m, d_runs, d_head_pos);
+      uint32_t *d_runs = c->d_scalars + kScalarLearnRuns;
+      group_runs(keys, m, d_head, d_run, d_head_pos, d_istmp, d_runs, st);
       hipLaunchKernelGGL(learn_verify_kernel, count_grid(m), dim3(kBlock), 0, st, in.d_pool, d_item_word, d_item_se, d_cell_off, d_cell, list, vals, d_head,
                          d_run, d_head_pos, m, M, static_cast<uint32_t>(n_groups), d_left, d_item_group);
-      device_exclusive_scan(d_left, d_left_pos, m, d_istmp, c->d_scalars + kScalarLearnLeft, st);
       hipLaunchKernelGGL(learn_group_first_kernel, count_grid(m), dim3(kBlock), 0, st, list, vals, d_head_pos, d_runs, m, d_gfirst + n_groups);
-      hipLaunchKernelGGL(count_compact_kernel, count_grid(m), dim3(kBlock), 0, st, d_left, d_left_pos, m, static_cast<const uint32_t *>(list), next, m);
-      WP_LAUNCH_CHECK();
-      queue_scalar_slots(c, kScalarLearnRuns, kScalarLearnLeft, st);
-      WP_HIP(hipStreamSynchronize(st));
-      const size_t runs = c->h_scalars[kScalarLearnRuns], left = c->h_scalars[kScalarLearnLeft];
-      if (runs == 0 || left >= m) throw HipError("learn: a round settled no occurrence");  // (every run settles its head)
-      n_groups += runs;
-      if (ls.n_rounds == 0) ls.n_collided = static_cast<int64_t>(left);
-      ls.n_rounds++;
-      m = left;
+      carry_leftovers(d_left, d_left_pos, m, list, next, d_istmp, c->d_scalars + kScalarLearnLeft, st);
+      n_groups += end_round(c, kScalarLearnRuns, kScalarLearnLeft, "learn", "occurrence", &m, &ls, st);
       std::swap(list, next);
     }
   }
@@ -384,11 +395,8 @@ static void learn_on_device(wp_vocab *v, Context *c, const LearnIn &in, const Le
   const size_t out_bytes = c->h_scalars[kScalarLearnOutBytes];
   if (out_bytes > text_cap) throw HipError("learn: the list is longer than its bound");
   if (timing) {  // wp_stats, as the header's section says: the stage times of this call in the fields an encode times itself in
-    float table = 0, groups = 0, search = 0, list = 0;
-    WP_HIP(hipEventElapsedTime(&table, c->ev[kMarkStart], c->ev[kMarkCounted]));
-    WP_HIP(hipEventElapsedTime(&groups, c->ev[kMarkCounted], c->ev[kMarkSorted]));
-    WP_HIP(hipEventElapsedTime(&search, c->ev[kMarkSorted], c->ev[kMarkScanned]));
-    WP_HIP(hipEventElapsedTime(&list, c->ev[kMarkScanned], c->ev[kMarkWalked]));
+    const float table = mark_ms(c, kMarkStart, kMarkCounted), groups = mark_ms(c, kMarkCounted, kMarkSorted), search = mark_ms(c, kMarkSorted, kMarkScanned),
+                list = mark_ms(c, kMarkScanned, kMarkWalked);
     v->stats.ms_decode = table;
     v->stats.ms_sa = groups;
     v->stats.ms_scan = search;
@@ -397,10 +405,10 @@ static void learn_on_device(wp_vocab *v, Context *c, const LearnIn &in, const Le
   }
   throw_if_oob(kSiteLearn, "vocabulary learner", "stores or gathers outside the item, group or list arrays skipped");
   throw_if_oob(kSiteCount, "vocabulary learner", "stores outside the run arrays of a grouping round skipped");
-  check_count_guard(c, aux, st, "learn");
-  check_count_guard(c, ia, st, "learn");
-  check_count_guard(c, ga, st, "learn");
-  check_count_guard(c, oa, st, "learn");
+  check_arena_guard(c, aux, st, "learn");
+  check_arena_guard(c, ia, st, "learn");
+  check_arena_guard(c, ga, st, "learn");
+  check_arena_guard(c, oa, st, "learn");
   R->tokens = out_bytes ? d_text : nullptr;
   R->token_off = reinterpret_cast<int64_t *>(d_token_off);
   R->scores = E ? reinterpret_cast<int64_t *>(d_scores) : nullptr;

@@ -2,7 +2,7 @@
 // neardup.h): the argument rules, the launches over a device batch, the component rounds and the buffers of a call.
 #pragma once
 #include "context.h"
-#include "count_path.h"  // count_grid, check_count_guard
+#include "group_path.h"
 #include "neardup.h"
 
 namespace wp {
@@ -50,9 +50,6 @@ static void check_neardup_rows(size_t n_rows, const NearDupPlan &plan) {
   if (static_cast<unsigned long long>(n_rows) * plan.n_perm >= (1ull << 32)) throw std::length_error("neardup: n_rows * n_perm reaches 2^32");
   if (static_cast<unsigned long long>(n_rows) * plan.bands >= (1ull << 32)) throw std::length_error("neardup: n_rows * bands reaches 2^32");
 }
-static void check_neardup_bytes(unsigned long long n_elems, uint32_t elem_bytes) {
-  if (n_elems > static_cast<unsigned long long>(UINT32_MAX) / elem_bytes) throw std::length_error("neardup: the data has more than UINT32_MAX bytes");
-}
 
 // the statistics of a neardup call before anything is known of its rows
 static wp_neardup_stats &begin_neardup_stats(wp_vocab *v, size_t n_rows) {
@@ -62,6 +59,33 @@ static wp_neardup_stats &begin_neardup_stats(wp_vocab *v, size_t n_rows) {
   return v->stats.neardup;
 }
 
+// no row, or rows that are all empty and so each a cluster of its own: no device needed
+static wp_neardup_result neardup_all_empty(wp_vocab *v, size_t n_rows, const NearDupPlan &plan) {
+  wp_neardup_stats &ns = begin_neardup_stats(v, n_rows);
+  wp_neardup_result h{};
+  h.n_rows = static_cast<int64_t>(n_rows);
+  h.n_perm = static_cast<int64_t>(plan.n_perm);
+  if (plan.want_compact) h.row_off = static_cast<int64_t *>(zeroed((n_rows + 1) * sizeof(int64_t)));
+  if (n_rows == 0) return h;
+  ns.n_unique = ns.n_empty = static_cast<int64_t>(n_rows);
+  h.n_unique = static_cast<int64_t>(n_rows);
+  h.cluster = static_cast<int32_t *>(zeroed(n_rows * sizeof(int32_t)));
+  h.kept = static_cast<int32_t *>(zeroed(n_rows * sizeof(int32_t)));
+  h.counts = static_cast<int64_t *>(zeroed(n_rows * sizeof(int64_t)));
+  if (plan.want_inverse) h.inverse = static_cast<int32_t *>(zeroed(n_rows * sizeof(int32_t)));
+  for (size_t r = 0; r < n_rows; r++) {
+    h.cluster[r] = h.kept[r] = static_cast<int32_t>(r);
+    h.counts[r] = 1;
+    if (h.inverse) h.inverse[r] = static_cast<int32_t>(r);
+  }
+  if (plan.want_signatures) {
+    const size_t bytes = n_rows * plan.n_perm * sizeof(uint32_t);
+    h.signatures = static_cast<uint32_t *>(zeroed(bytes));
+    std::memset(h.signatures, 0xff, bytes);
+  }
+  return h;
+}
+
 template <int SLOTS>
 static void launch_near_sig(unsigned tiles, hipStream_t st, const uint32_t *d32, size_t n_bytes, const uint32_t *d_boff, const uint32_t *d_pos_off,
                             size_t n, size_t n_positions, const NearDupPlan &plan, uint32_t *d_sig) {
@@ -69,7 +93,7 @@ static void launch_near_sig(unsigned tiles, hipStream_t st, const uint32_t *d32,
                      plan.shingle, plan.n_perm, plan.seed, d_sig);
 }
 
-// The rows of the batch at d_data / d_row_off (n_rows >= 1), on c's stream.  The results are device pointers into
+// The rows of the batch `in` (n_rows >= 1), on c's stream.  The results are device pointers into
 // c->neardup_rows (cluster, signatures) and c->neardup_out (everything else), valid until the handle's next call.
 // Waits: the sizes (the offset check, the elements, the positions, the empty rows), one behind the grouping (it brings
 // the candidate count), with min_agree > 0 one behind the comparison (the edge count), one per component round (its
@@ -78,28 +102,19 @@ static void launch_near_sig(unsigned tiles, hipStream_t st, const uint32_t *d32,
 // of the round before, or the first labels).  A round that lowers any label lowers a root's first, and that row is no
 // root afterwards, so every round that reports a change leaves at least one root fewer; there are at most n_rows roots.
 // The loop therefore ends within n_rows + 1 rounds, and throws where it does not.
-static void neardup_on_device(wp_vocab *v, Context *c, const void *d_data, const long long *d_row_off, size_t n, const NearDupPlan &plan,
-                              wp_neardup_result *R) {
+static void neardup_on_device(wp_vocab *v, Context *c, const RaggedIn &in, const NearDupPlan &plan, wp_neardup_result *R) {
+  const size_t n = in.n_rows;
   wp_neardup_stats &ns = begin_neardup_stats(v, n);
   *R = wp_neardup_result{};
   R->n_rows = static_cast<int64_t>(n);
   R->n_perm = static_cast<int64_t>(plan.n_perm);
   hipStream_t st = c->stream;
   const bool guard = v->arena_guard || EnvOptions::get().arena_guard;
-  const uint32_t eb = plan.elem_bytes;
+  const uint32_t eb = in.elem_bytes;
   // WP_OPT_STAGE_TIMING: kMarkStart, kMarkCounted (offsets checked, positions listed), kMarkSymbols (signatures),
   // kMarkSorted (band keys, sort, heads, edges), kMarkWalked (components, table, compact form)
   const bool timing = v->stage_timing;
-  RadixStats *rs = timing ? &c->rstats : nullptr;
-  if (timing) {
-    c->rstats.passes = 0;
-    c->rstats.elems = 0;
-    c->rstats.digit_bytes = 0;
-    c->rstats.bytes = 0;
-    c->rstats.spans.used = 0;
-    c->rstats.spans.on = true;
-    WP_HIP(hipEventRecord(c->ev[kMarkStart], st));
-  }
+  RadixStats *rs = begin_stage_timing(c, timing, st);
 
   // ---- the per-row arrays, the offset check, the position list ---------------------------------------------------------
   const size_t n1 = n + 1;
@@ -131,36 +146,28 @@ static void neardup_on_device(wp_vocab *v, Context *c, const void *d_data, const
   unsigned long long *d_positions = reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarNearPositions);
   clear_scalars(c, kScalarNearBad, kScalarNear, st);
   WP_HIP(hipMemsetAsync(c->d_scalars + kScalarNearBad, 0xff, sizeof(uint32_t), st));
-  hipLaunchKernelGGL(near_rows_kernel, count_grid(n1), dim3(kBlock), 0, st, d_row_off, n, eb, plan.shingle, d_boff, d_npos, d_has, d_cluster,
+  hipLaunchKernelGGL(near_rows_kernel, count_grid(n1), dim3(kBlock), 0, st, in.d_row_off, n, eb, plan.shingle, d_boff, d_npos, d_has, d_cluster,
                      c->d_scalars + kScalarNearBad, d_elems, d_counters);
   device_exclusive_scan(d_npos, d_pos_off, n1, d_stmp, nullptr, st, nullptr, d_positions);
   device_exclusive_scan(d_has, d_has_pos, n1, d_stmp, nullptr, st);
-  hipLaunchKernelGGL(count_compact_kernel, count_grid(n), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_has),
-                     static_cast<const uint32_t *>(d_has_pos), n, static_cast<const uint32_t *>(nullptr), d_rows, n);
+  compact_flagged(d_has, d_has_pos, n, nullptr, d_rows, st);
   WP_HIP(hipMemsetAsync(d_sig, 0xff, sig_words * sizeof(uint32_t), st));  // (a row without shingles keeps this; atomicMin starts from it)
   WP_HIP(hipMemsetAsync(d_rcount, 0, n * sizeof(uint32_t), st));
   WP_LAUNCH_CHECK();
   if (timing) WP_HIP(hipEventRecord(c->ev[kMarkCounted], st));
   queue_scalar_slots(c, kScalarNearBad, kScalarNear, st);
   WP_HIP(hipStreamSynchronize(st));
-  const uint32_t bad = c->h_scalars[kScalarNearBad];
-  if (bad != kDedupNoBad) {
-    throw std::invalid_argument(bad == 0 ? "neardup: row_off must start at 0 and never descend: row 0"
-                                         : "neardup: row_off must never descend: row " + std::to_string(bad));
-  }
   unsigned long long elems64, positions64, counters[kNearCounters];
   std::memcpy(&elems64, c->h_scalars + kScalarNearElems, sizeof(elems64));
   std::memcpy(&positions64, c->h_scalars + kScalarNearPositions, sizeof(positions64));
   std::memcpy(counters, c->h_scalars + kScalarNear, sizeof(counters));
-  check_neardup_bytes(elems64, eb);
-  const size_t n_bytes = static_cast<size_t>(elems64) * eb;
-  if (n_bytes != 0 && !d_data) throw std::invalid_argument("neardup: data is NULL");
+  const size_t n_bytes = check_ragged_device("neardup", in, c->h_scalars[kScalarNearBad], elems64);
   if (positions64 > elems64 || counters[kNearEmpty] > n) throw HipError("neardup: the position list does not fit the rows");
   const size_t n_positions = static_cast<size_t>(positions64), n_live = n - static_cast<size_t>(counters[kNearEmpty]);
   ns.n_elems = static_cast<int64_t>(elems64);
   ns.n_empty = static_cast<int64_t>(counters[kNearEmpty]);
   ns.n_shingles = static_cast<int64_t>(positions64);
-  const uint32_t *d32 = static_cast<const uint32_t *>(d_data);
+  const uint32_t *d32 = static_cast<const uint32_t *>(in.d_data);
 
   // ---- signatures: flat over the positions ------------------------------------------------------------------------------
   if (n_positions != 0) {
@@ -209,19 +216,14 @@ static void neardup_on_device(wp_vocab *v, Context *c, const void *d_data, const
     const uint64_t *keys = cur ? d_k1 : d_k0;
     const uint32_t *vals = cur ? d_v1 : d_v0;
     uint32_t *d_runs = c->d_scalars + kScalarNearRuns;
-    hipLaunchKernelGGL(count_heads_kernel, count_grid(m), dim3(kBlock), 0, st, keys, m, d_head);
-    device_exclusive_scan(d_head, d_run, m, d_itmp, d_runs, st);
-    hipLaunchKernelGGL(count_head_pos_kernel, count_grid(m), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_head),
-                       static_cast<const uint32_t *>(d_run), m, static_cast<const uint32_t *>(d_runs), d_head_pos);
+    group_runs(keys, m, d_head, d_run, d_head_pos, d_itmp, d_runs, st);
     hipLaunchKernelGGL(near_match_kernel, count_grid(m), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_rows), vals,
                        static_cast<const uint32_t *>(d_head), static_cast<const uint32_t *>(d_run), static_cast<const uint32_t *>(d_head_pos), m, n,
                        plan.bands, d_edge, d_mrow, d_hrow, d_counters);
     // the candidates, compacted in sorted order: (d_eu, d_ev)
     device_exclusive_scan(d_edge, d_edge_pos, m, d_itmp, c->d_scalars + kScalarNearEdges, st);
-    hipLaunchKernelGGL(count_compact_kernel, count_grid(m), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_edge),
-                       static_cast<const uint32_t *>(d_edge_pos), m, static_cast<const uint32_t *>(d_mrow), d_eu, m);
-    hipLaunchKernelGGL(count_compact_kernel, count_grid(m), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_edge),
-                       static_cast<const uint32_t *>(d_edge_pos), m, static_cast<const uint32_t *>(d_hrow), d_ev, m);
+    compact_flagged(d_edge, d_edge_pos, m, d_mrow, d_eu, st);
+    compact_flagged(d_edge, d_edge_pos, m, d_hrow, d_ev, st);
     WP_LAUNCH_CHECK();
     queue_scalar_slots(c, kScalarNearRuns, kScalarNearEdges, st);
     WP_HIP(hipStreamSynchronize(st));
@@ -233,10 +235,8 @@ static void neardup_on_device(wp_vocab *v, Context *c, const void *d_data, const
       hipLaunchKernelGGL(near_agree_kernel, count_grid(n_cand * kNearEdgeLanes), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_sig),
                          static_cast<const uint32_t *>(d_eu), static_cast<const uint32_t *>(d_ev), n_cand, n, plan.n_perm, plan.min_agree, d_edge);
       device_exclusive_scan(d_edge, d_edge_pos, n_cand, d_itmp, c->d_scalars + kScalarNearEdges, st);
-      hipLaunchKernelGGL(count_compact_kernel, count_grid(n_cand), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_edge),
-                         static_cast<const uint32_t *>(d_edge_pos), n_cand, static_cast<const uint32_t *>(d_eu), d_mrow, n_cand);
-      hipLaunchKernelGGL(count_compact_kernel, count_grid(n_cand), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_edge),
-                         static_cast<const uint32_t *>(d_edge_pos), n_cand, static_cast<const uint32_t *>(d_ev), d_hrow, n_cand);
+      compact_flagged(d_edge, d_edge_pos, n_cand, d_eu, d_mrow, st);
+      compact_flagged(d_edge, d_edge_pos, n_cand, d_ev, d_hrow, st);
       WP_LAUNCH_CHECK();
       if (timing) WP_HIP(hipEventRecord(c->ev[kMarkSorted], st));
       queue_scalar_slots(c, kScalarNearEdges, kScalarNearEdges, st);
@@ -282,35 +282,8 @@ static void neardup_on_device(wp_vocab *v, Context *c, const void *d_data, const
   ns.n_unique = static_cast<int64_t>(n_unique);
 
   // ---- the table and the compact form: dedup's kernels over `cluster` ------------------------------------------------------
-  Arena oa(&c->neardup_out, guard);
-  int32_t *d_kept = nullptr, *d_inverse = nullptr;
-  long long *d_counts = nullptr, *d_out_off = nullptr;
-  uint32_t *d_out = nullptr;
-  for (int pass = 0; pass < 2; pass++) {
-    d_kept = oa.take<int32_t>(n_unique);
-    d_counts = oa.take<long long>(n_unique);
-    if (plan.want_inverse) d_inverse = oa.take<int32_t>(n);
-    if (plan.want_compact) {
-      d_out_off = oa.take<long long>(n_unique + 1);
-      d_out = oa.take<uint32_t>(n_bytes / 4 + 1);
-    }
-    if (pass == 0) oa.commit();
-  }
-  oa.arm(st);
-  hipLaunchKernelGGL(dedup_table_kernel, count_grid(n), dim3(kBlock), 0, st, static_cast<const int32_t *>(d_cluster),
-                     static_cast<const uint32_t *>(d_keep_pos), static_cast<const uint32_t *>(d_rcount), static_cast<const uint32_t *>(d_boff), n,
-                     n_unique, d_kept, d_counts, d_inverse, plan.want_compact ? d_out_len : static_cast<uint32_t *>(nullptr));
-  if (plan.want_compact) {
-    device_exclusive_scan(d_out_len, d_out_pos, n_unique + 1, d_stmp, nullptr, st);
-    hipLaunchKernelGGL(dedup_out_off_kernel, count_grid(n_unique + 1), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_out_pos), n_unique, eb,
-                       d_out_off);
-    if (n_bytes != 0) {
-      hipLaunchKernelGGL(dedup_gather_kernel, count_grid((n_bytes + 3) / 4), dim3(kBlock), 0, st, static_cast<const uint8_t *>(d_data), n_bytes,
-                         static_cast<const uint32_t *>(d_boff), static_cast<const int32_t *>(d_kept), static_cast<const uint32_t *>(d_out_pos),
-                         n_unique, n, n_bytes, d_out);
-    }
-    WP_HIP(hipMemcpyAsync(c->d_scalars + kScalarNearOutBytes, d_out_pos + n_unique, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-  }
+  const GroupTable t = group_table(c, in, d_cluster, d_keep_pos, d_rcount, d_boff, n_unique, n_bytes, plan.want_inverse, plan.want_compact, &c->neardup_out,
+                                   guard, d_out_len, d_out_pos, d_stmp, kScalarNearOutBytes, st);
   WP_LAUNCH_CHECK();
   if (timing) WP_HIP(hipEventRecord(c->ev[kMarkWalked], st));
   queue_scalar_slots(c, kScalarNearOutBytes, kScalarNear, st);
@@ -318,41 +291,25 @@ static void neardup_on_device(wp_vocab *v, Context *c, const void *d_data, const
   std::memcpy(counters, c->h_scalars + kScalarNear, sizeof(counters));
   ns.n_buckets = static_cast<int64_t>(counters[kNearBuckets]);
   if (timing) {  // wp_stats, as the header's section says: the stage times of this call in the fields an encode times itself in
-    float list = 0, sigs = 0, group = 0, table = 0;
-    WP_HIP(hipEventElapsedTime(&list, c->ev[kMarkStart], c->ev[kMarkCounted]));
-    WP_HIP(hipEventElapsedTime(&sigs, c->ev[kMarkCounted], c->ev[kMarkSymbols]));
-    WP_HIP(hipEventElapsedTime(&group, c->ev[kMarkSymbols], c->ev[kMarkSorted]));
-    WP_HIP(hipEventElapsedTime(&table, c->ev[kMarkSorted], c->ev[kMarkWalked]));
+    const float list = mark_ms(c, kMarkStart, kMarkCounted), sigs = mark_ms(c, kMarkCounted, kMarkSymbols), group = mark_ms(c, kMarkSymbols, kMarkSorted),
+                table = mark_ms(c, kMarkSorted, kMarkWalked);
     v->stats.ms_normalize = 0;
     v->stats.ms_decode = list;
     v->stats.ms_scan = sigs;
     v->stats.ms_sa = group;
     v->stats.ms_walk = table;
     v->stats.ms_total = list + sigs + group + table;
-    v->stats.ms_radix_scatter = c->rstats.spans.resolve();
-    v->stats.radix_passes = c->rstats.passes;
-    v->stats.radix_pass_elems = c->rstats.elems;
-    v->stats.radix_pass_bytes = c->rstats.bytes;
-    c->rstats.spans.on = false;
+    end_stage_timing(v, c);
   }
   throw_if_oob(kSiteNearDup, "near-duplicate rows", "gathers or stores outside the row, item or edge arrays skipped");
   throw_if_oob(kSiteDedup, "near-duplicate rows", "stores or gathers outside the table arrays skipped");
   throw_if_oob(kSiteCount, "near-duplicate rows", "stores outside the compacted lists skipped");
-  check_count_guard(c, ra, st, "neardup");
-  check_count_guard(c, ia, st, "neardup");
-  check_count_guard(c, oa, st, "neardup");
+  check_arena_guard(c, ra, st, "neardup");
+  check_arena_guard(c, ia, st, "neardup");
+  check_arena_guard(c, t.oa, st, "neardup");
   R->cluster = d_cluster;
-  R->kept = d_kept;
-  R->counts = reinterpret_cast<int64_t *>(d_counts);
-  R->inverse = d_inverse;
-  R->n_unique = static_cast<int64_t>(n_unique);
   if (plan.want_signatures) R->signatures = d_sig;
-  if (plan.want_compact) {
-    const size_t out_bytes = c->h_scalars[kScalarNearOutBytes];
-    R->row_off = reinterpret_cast<int64_t *>(d_out_off);
-    R->data = out_bytes ? d_out : nullptr;
-    R->n_elems = static_cast<int64_t>(out_bytes / eb);
-  }
+  t.hand_out(R, n_unique, plan.want_compact, c->h_scalars[kScalarNearOutBytes], eb);
 }
 
 }  // namespace wp

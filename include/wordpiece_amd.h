@@ -717,6 +717,66 @@ int wp_neardup_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row
 typedef struct { int64_t n_rows, n_unique, n_empty, n_elems, n_shingles, n_buckets, n_candidates, n_edges, n_rounds; } wp_neardup_stats;
 int wp_get_neardup_stats(const wp_vocab *v, wp_neardup_stats *out);   /* n_rows == -1: no such call yet, or an encode since */
 
+/* ---- n-gram overlap (an addition: the rows of a ragged batch that share an n-gram with a reference set, found on the
+ * device, exactly — decontamination against evaluation data, a block list, licensed text; the contract is the one stated
+ * here, and tests/overlap_model.py is its executable form) ----
+ * Input.  Two batches as wp_dedup_rows takes one: the corpus, data and row_off int64 [n_rows + 1], and the reference
+ * set, ref_data and ref_off int64 [n_ref + 1]; offsets ascending from 0, in elements of spec->elem_bytes bytes (1: text,
+ * 4: ids), the same for both batches; a row may start at any byte.  No vocabulary is read: the handle lends its device
+ * context (WP_OPT_STAGE_TIMING and WP_OPT_ARENA_GUARD are its only options that matter).  Ids are the better view of
+ * text: the windows of the tokens of an uncased handle ignore case, accents and spacing.
+ * Windows.  k = spec->ngram in [1, 64].  A row of L >= k elements has the L - k + 1 windows at the positions p = 0 ..
+ * L - k; a row of L < k elements has none (unlike the shingles of wp_neardup_rows: a short row neither hits nor is hit).
+ * A window never crosses a row boundary.
+ * Hit.  Window p of corpus row i hits iff its k * elem_bytes bytes equal those of some window of some reference row.
+ * Result, always: hits int64 [n_rows], the hitting windows of row i; first_hit int64 [n_rows], the smallest hitting p or
+ * -1; first_ref int32 [n_rows], the smallest reference row that holds a window equal to the one at first_hit, or -1;
+ * covered int64 [n_rows], the elements of row i that lie in at least one hitting window (the size of the union of the
+ * [p, p + k)).  With WP_OVERLAP_WANT_MASK: mask uint8 [n_elems of the corpus], 1 where the element is covered — covered[i]
+ * is its sum over row i, data[mask == 0] the corpus with the leaked spans cut out.  With WP_OVERLAP_WANT_REF: ref_hits
+ * int64 [n_ref], the windows of reference row j that equal some corpus window (each window once, however often it is
+ * met).  With WP_OVERLAP_WANT_COMPACT: kept int32 [n_kept], the rows with hits[i] <= spec->max_hits ascending (max_hits
+ * >= 0; 0 keeps the clean rows), and those rows back to back as data and row_off int64 [n_kept + 1], n_elems elements,
+ * as the compact forms of wp_dedup_rows and wp_neardup_rows; without the bit kept, data and row_off are NULL and n_kept,
+ * n_elems are 0.
+ * Exactness.  No part of any result array depends on a hash, a seed or an order of execution: every window that a key
+ * lets through is compared byte by byte, and every combination across lanes is an integer sum, minimum or OR.
+ * hash_bits (0: 64; else 8..64) narrows the window key to its low bits, for tests, and never changes a result; the
+ * bucket index reads the top bits of the narrowed key.
+ * WP_ERR_ARG, before a device is touched and with the field named: spec or out NULL, elem_bytes not 1 or 4, want with a
+ * bit outside 7, ngram outside [1, 64], max_hits < 0, hash_bits not 0 and outside [8, 64], reserved not 0, row_off NULL
+ * with n_rows > 0, ref_off NULL with n_ref > 0; data or ref_data NULL with elements.  Offsets that do not start at 0 or
+ * descend give WP_ERR_ARG, naming the array (row_off or ref_off) and its first bad row: the host form checks on the
+ * host, the device form by a kernel.
+ * WP_ERR_TOO_LARGE: n_rows or n_ref >= 2^31, or either batch over UINT32_MAX bytes.
+ * Host form: the blocks of *out are malloc'd, each freed with wp_free; a block is NULL where it is empty or was not asked
+ * for.  n_rows == 0 returns all NULL; a corpus or a reference set without any window is answered without a device
+ * (hits and covered 0, first_hit and first_ref -1, every row kept).  Device form: both batches under the buffer contract
+ * of wp_dedup_rows_device; the arrays of *d_out are device memory owned by the handle until its next call (n_rows == 0:
+ * all NULL).  Nothing behind n_elems * elem_bytes of either batch influences a result.
+ * Cost.  All work is flat over the elements of the two batches, never over rows; a window key costs the same for every
+ * k (a polynomial hash from two prefix values of a tile in LDS).
+ * Waits of a call: one for the sizes of both batches (the offset checks, the elements, the windows), one for the
+ * candidate count (it brings the table size too), with WP_OVERLAP_WANT_COMPACT one for the kept count, one that ends the
+ * call: three or four by the spec, never by the data or by collisions.  With WP_OPT_STAGE_TIMING a call leaves its
+ * device times (HIP events) in wp_stats: ms_decode (the offset checks), ms_sa (the reference table: keys, sort,
+ * distinct windows, bucket index), ms_scan (the corpus windows, lookup and comparison), ms_walk (the per-row results and
+ * the compact form), ms_total (their sum); ms_normalize is 0. */
+#define WP_OVERLAP_WANT_MASK    1
+#define WP_OVERLAP_WANT_REF     2
+#define WP_OVERLAP_WANT_COMPACT 4
+typedef struct { int32_t elem_bytes, want, ngram, max_hits, hash_bits, reserved[3]; } wp_overlap_spec;
+typedef struct { int64_t *hits, *first_hit, *covered, *ref_hits, *row_off; int32_t *first_ref, *kept; uint8_t *mask; void *data; int64_t n_rows, n_ref, n_kept, n_elems; } wp_overlap_result;
+int wp_overlap_rows(wp_vocab *v, const void *data, const int64_t *row_off, size_t n_rows, const void *ref_data, const int64_t *ref_off, size_t n_ref, const wp_overlap_spec *spec, wp_overlap_result *out);
+int wp_overlap_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row_off, size_t n_rows, const void *d_ref_data, const int64_t *d_ref_off, size_t n_ref, const wp_overlap_spec *spec, wp_overlap_result *d_out);
+/* The statistics of the last overlap call, in a struct of its own.  n_rows, n_ref, n_elems, n_ref_elems, n_windows,
+ * n_ref_windows, n_ref_distinct (the distinct reference windows), n_hits (the sum of hits), n_hit_rows (the rows with a
+ * hit), n_covered (the sum of covered): functions of the contract.  n_candidates (the corpus windows whose key was in the
+ * table) and n_collided (the reference windows that differ from the first window of their key) depend on the hash and
+ * are only reported. */
+typedef struct { int64_t n_rows, n_ref, n_elems, n_ref_elems, n_windows, n_ref_windows, n_ref_distinct, n_hits, n_hit_rows, n_covered, n_candidates, n_collided; } wp_overlap_stats;
+int wp_get_overlap_stats(const wp_vocab *v, wp_overlap_stats *out);   /* n_rows == -1: no such call yet, or an encode since */
+
 /* The same call sharded over several GPUs of the node, behind the boundary: the reference's own
  * precedent is the in-library chunking at whitespace of linear.cpp:283-299 (thread chunks) and
  * linear.cpp:355-367 (encodeExternal batches).  The text is cut at ASCII whitespace into one shard

@@ -65,6 +65,7 @@ ABI_SYMBOLS = [
     "wp_learn_vocab", "wp_learn_vocab_device", "wp_get_learn_stats",
     "wp_dedup_rows", "wp_dedup_rows_device", "wp_get_dedup_stats",
     "wp_neardup_rows", "wp_neardup_rows_device", "wp_get_neardup_stats",
+    "wp_overlap_rows", "wp_overlap_rows_device", "wp_get_overlap_stats",
 ]
 
 
@@ -304,6 +305,31 @@ class NearDupStats(C.Structure):
                 ("n_buckets", C.c_int64), ("n_candidates", C.c_int64), ("n_edges", C.c_int64), ("n_rounds", C.c_int64)]
 
 
+WP_OVERLAP_WANT_MASK = 1
+WP_OVERLAP_WANT_REF = 2
+WP_OVERLAP_WANT_COMPACT = 4
+
+
+class OverlapSpec(C.Structure):
+    """wp_overlap_spec: the arguments of an overlap call (elem_bytes 1: text, 4: ids; ngram: elements per window)."""
+    _fields_ = [("elem_bytes", C.c_int32), ("want", C.c_int32), ("ngram", C.c_int32), ("max_hits", C.c_int32), ("hash_bits", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
+class OverlapResult(C.Structure):
+    """wp_overlap_result: the arrays of an overlap call (host blocks, or device memory owned by the handle)."""
+    _fields_ = [("hits", C.c_void_p), ("first_hit", C.c_void_p), ("covered", C.c_void_p), ("ref_hits", C.c_void_p), ("row_off", C.c_void_p),
+                ("first_ref", C.c_void_p), ("kept", C.c_void_p), ("mask", C.c_void_p), ("data", C.c_void_p), ("n_rows", C.c_int64),
+                ("n_ref", C.c_int64), ("n_kept", C.c_int64), ("n_elems", C.c_int64)]
+
+
+class OverlapStats(C.Structure):
+    """wp_overlap_stats: the statistics of the last overlap call (Vocab.overlap_stats())."""
+    _fields_ = [("n_rows", C.c_int64), ("n_ref", C.c_int64), ("n_elems", C.c_int64), ("n_ref_elems", C.c_int64), ("n_windows", C.c_int64),
+                ("n_ref_windows", C.c_int64), ("n_ref_distinct", C.c_int64), ("n_hits", C.c_int64), ("n_hit_rows", C.c_int64),
+                ("n_covered", C.c_int64), ("n_candidates", C.c_int64), ("n_collided", C.c_int64)]
+
+
 def lsh_min_agree(threshold, n_perm):
     """The min_agree that stands for a Jaccard threshold: ceil(threshold * n_perm) signature slots."""
     return int(math.ceil(threshold * n_perm))
@@ -415,6 +441,10 @@ def lib():
             L.wp_neardup_rows.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(NearDupSpec), C.POINTER(NearDupResult)]
             L.wp_neardup_rows_device.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(NearDupSpec), C.POINTER(NearDupResult)]
             L.wp_get_neardup_stats.argtypes = [vp, C.POINTER(NearDupStats)]
+        if hasattr(L, "wp_overlap_rows"):  # (WP_LIB, as above)
+            L.wp_overlap_rows.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(OverlapSpec), C.POINTER(OverlapResult)]
+            L.wp_overlap_rows_device.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(OverlapSpec), C.POINTER(OverlapResult)]
+            L.wp_get_overlap_stats.argtypes = [vp, C.POINTER(OverlapStats)]
         L.wp_linear_encode_multi.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.POINTER(i32p),
                                              C.POINTER(C.c_size_t)]
         L.wp_reserve.argtypes = [vp, C.c_size_t]
@@ -1535,6 +1565,144 @@ class Vocab:
         text, off = join_docs(docs)
         r = self.neardup_rows(text, off, **kw)
         return [docs[k] for k in r["kept"]], r["counts"]
+
+    def overlap_stats(self):
+        """wp_overlap_stats of the last overlap call as a dict (n_rows -1: no such call yet)."""
+        s = OverlapStats()
+        _check(lib().wp_get_overlap_stats(self._h, C.byref(s)))
+        return {k: int(getattr(s, k)) for k, _ in s._fields_}
+
+    @staticmethod
+    def _overlap_spec(elem_bytes, ngram, max_hits, mask, ref, compact, hash_bits):
+        want = (WP_OVERLAP_WANT_MASK if mask else 0) | (WP_OVERLAP_WANT_REF if ref else 0) | (WP_OVERLAP_WANT_COMPACT if compact else 0)
+        return OverlapSpec(elem_bytes, want, int(ngram), int(max_hits), int(hash_bits), (C.c_int32 * 3)(0, 0, 0))
+
+    @staticmethod
+    def _overlap_batch(data, row_off, name):
+        """one batch of a host overlap call -> (flat uint8 / int32 array, int64 offsets, n_rows)"""
+        if isinstance(data, (str, bytes, bytearray, memoryview)):
+            data = np.frombuffer(_bytes(data), dtype=np.uint8)
+        else:
+            data = np.ascontiguousarray(data)
+        if data.dtype not in (np.uint8, np.int32) or data.ndim != 1:
+            raise WordPieceError("overlap: %s must be text (bytes, uint8) or a flat int32 array" % name)
+        if row_off is None:
+            if data.dtype != np.uint8:
+                raise WordPieceError("overlap: the lines form takes text")
+            data, row_off = line_rows(data)
+        off = np.ascontiguousarray(row_off, dtype=np.int64)
+        n = off.size - 1
+        if off.ndim != 1 or n < 0:
+            raise WordPieceError("overlap: the offsets of %s need n_rows + 1 entries" % name)
+        if n and off[n] > data.size:  # (the library reads the last offset's elements of the data)
+            raise WordPieceError("overlap: the offsets of %s end behind the data" % name)
+        return data, off, n
+
+    def overlap_rows(self, data, row_off, ref_data, ref_off, ngram=13, max_hits=0, mask=False, ref=False, compact=False, hash_bits=0,
+                     raw=False):
+        """The rows of a ragged batch that share an n-gram with a reference set, found on the device, exactly
+        (wp_overlap_rows).  data / row_off: the corpus, ref_data / ref_off: the reference set, each as dedup_rows takes a
+        batch (text or int32 ids, the same kind for both; offsets None: the lines of a text).  A window is `ngram`
+        consecutive elements of a row.  -> {"hits": np.int64 [n_rows] (the windows of the row that equal a reference
+        window), "first_hit": np.int64 (the first such position, or -1), "first_ref": np.int32 (the smallest reference
+        row that holds it, or -1), "covered": np.int64 (the elements inside a hitting window)}, with mask "mask": np.uint8
+        per element, with ref "ref_hits": np.int64 [n_ref] (the windows of a reference row found in the corpus), with
+        compact "kept": np.int32 (the rows with hits <= max_hits) and their "data" and "row_off" back to back.  raw: text
+        data comes back as np.uint8 rather than bytes.  hash_bits: for tests of key collisions."""
+        data, off, n = self._overlap_batch(data, row_off, "data")
+        rdata, roff, nr = self._overlap_batch(ref_data, ref_off, "ref_data")
+        if data.dtype != rdata.dtype:
+            raise WordPieceError("overlap: data and ref_data must both be text or both be ids")
+        spec = self._overlap_spec(data.dtype.itemsize, ngram, max_hits, mask, ref, compact, hash_bits)
+        out = OverlapResult()
+        _check(lib().wp_overlap_rows(self._h, data.ctypes.data if data.size else None, off.ctypes.data if n else None, n,
+                                     rdata.ctypes.data if rdata.size else None, roff.ctypes.data if nr else None, nr, C.byref(spec), C.byref(out)))
+
+        def block(ptr, k, dtype):
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(np.ctypeslib.as_ctypes_type(dtype))), (k,)).copy() if k and ptr else \
+                np.zeros(0, dtype=dtype)
+        try:
+            res = {"hits": block(out.hits, n, np.int64), "first_hit": block(out.first_hit, n, np.int64),
+                   "first_ref": block(out.first_ref, n, np.int32), "covered": block(out.covered, n, np.int64)}
+            if mask:
+                res["mask"] = block(out.mask, int(off[n]) if n else 0, np.uint8)
+            if ref:
+                res["ref_hits"] = block(out.ref_hits, nr, np.int64)
+            if compact:
+                kept_data = block(out.data, out.n_elems, data.dtype)
+                res["kept"] = block(out.kept, out.n_kept, np.int32)
+                res["data"] = kept_data if raw or data.dtype != np.uint8 else kept_data.tobytes()
+                res["row_off"] = block(out.row_off, out.n_kept + 1, np.int64) if n else np.zeros(1, dtype=np.int64)
+        finally:
+            for blk in (out.hits, out.first_hit, out.covered, out.ref_hits, out.row_off, out.first_ref, out.kept, out.mask, out.data):
+                if blk:
+                    lib().wp_free(blk)
+        return res
+
+    def overlap_rows_tensor(self, data, row_off, ref_data, ref_off, ngram=13, max_hits=0, mask=False, ref=False, compact=False, copy=True,
+                            hash_bits=0):
+        """overlap_rows for batches in tensors on this handle's GPU (wp_overlap_rows_device): data and ref_data uint8
+        (text) or int32 (ids), row_off and ref_off int64 — the ids and row_splits of encode_rows_tensor, the compact
+        forms of dedup_rows_tensor and neardup_rows_tensor, a joined text and its doc_off.  -> a dict of tensors on that
+        device: "hits", "first_hit", "first_ref", "covered", with mask "mask" (torch.uint8), with ref "ref_hits", with
+        compact "kept", "data" and "row_off" (what pack_sequences_tensor takes).  copy=False: views of the library's
+        buffers, valid until the next call on this handle."""
+        import torch
+        if data.dtype not in (torch.uint8, torch.int32) or ref_data.dtype != data.dtype or row_off.dtype != torch.int64 or ref_off.dtype != torch.int64:
+            raise WordPieceError("overlap_rows_tensor needs uint8 or int32 data of one kind and int64 offsets")
+        for t in (data, row_off, ref_data, ref_off):
+            if not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
+                raise WordPieceError("overlap_rows_tensor needs flat contiguous CUDA/HIP tensors")
+            if self._device is not None and t.device.index != self._device:  # (raw pointers go to the handle's device)
+                raise WordPieceError("the tensors lie on %s, the handle on device %d" % (t.device, self._device))
+        n, nr = row_off.numel() - 1, ref_off.numel() - 1
+        if n < 0 or nr < 0:
+            raise WordPieceError("overlap: offsets need n_rows + 1 entries")
+
+        def aligned(t):
+            nbytes = t.numel() * t.element_size()
+            if t.dtype == torch.uint8 and (t.data_ptr() % 4 != 0 or nbytes % 4 != 0):  # (the kernels read whole aligned words)
+                padded = torch.zeros((nbytes + 19) // 16 * 16, dtype=torch.uint8, device=t.device)
+                padded[:nbytes] = t
+                return padded, nbytes
+            return t, nbytes
+        n_elems = data.numel()
+        data, nbytes = aligned(data)
+        ref_data, ref_nbytes = aligned(ref_data)
+        spec = self._overlap_spec(data.element_size(), ngram, max_hits, mask, ref, compact, hash_bits)
+        dev = data.device
+        torch.cuda.current_stream(dev).synchronize()  # the library runs on its own HIP streams
+        out = OverlapResult()
+        _check(lib().wp_overlap_rows_device(self._h, C.c_void_p(data.data_ptr()) if nbytes else None, C.c_void_p(row_off.data_ptr()), n,
+                                            C.c_void_p(ref_data.data_ptr()) if ref_nbytes else None, C.c_void_p(ref_off.data_ptr()), nr,
+                                            C.byref(spec), C.byref(out)))
+
+        def view(ptr, k, typestr, dtype):
+            if not k or not ptr:
+                return torch.zeros(0, dtype=dtype, device=dev)
+            t = torch.as_tensor(DeviceIds(ptr, k, typestr=typestr), device=dev)
+            return t.clone() if copy else t
+        res = {"hits": view(out.hits, n, "<i8", torch.int64), "first_hit": view(out.first_hit, n, "<i8", torch.int64),
+               "first_ref": view(out.first_ref, n, "<i4", torch.int32), "covered": view(out.covered, n, "<i8", torch.int64)}
+        if mask:
+            res["mask"] = view(out.mask, min(n_elems, int(row_off[n])) if n and out.mask else 0, "|u1", torch.uint8)
+        if ref:
+            res["ref_hits"] = view(out.ref_hits, nr, "<i8", torch.int64)
+        if compact:
+            res["kept"] = view(out.kept, out.n_kept, "<i4", torch.int32)
+            res["data"] = view(out.data, out.n_elems, "|u1" if data.dtype == torch.uint8 else "<i4", data.dtype)
+            res["row_off"] = view(out.row_off, out.n_kept + 1, "<i8", torch.int64) if n else torch.zeros(1, dtype=torch.int64, device=dev)
+        return res
+
+    def overlap_docs(self, docs, ref_docs, ngram=13, max_hits=0):
+        """The documents of a list (str / bytes) that share at most max_hits windows of `ngram` bytes with the documents
+        of ref_docs -> ([those documents as given], np.int64 hits of every document of docs); through join_docs and
+        overlap_rows."""
+        docs, ref_docs = list(docs), list(ref_docs)
+        text, off = join_docs(docs)
+        ref_text, ref_off = join_docs(ref_docs)
+        r = self.overlap_rows(text, off, ref_text, ref_off, ngram=ngram, max_hits=max_hits, compact=True)
+        return [docs[k] for k in r["kept"]], r["hits"]
 
     def align_stats(self):
         """wp_align_stats of the last call as a dict (n_rows -1: it was no align call)."""

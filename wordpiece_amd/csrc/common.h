@@ -56,7 +56,8 @@ enum BoundSite {
   kSiteLearn = 16,    // vocabulary learner: the stores of the items, the groups and the list, the gathers behind them (learn.h)
   kSiteDedup = 17,    // duplicate rows: the stores of the chunk list, the runs and the table, the gathers behind them (dedup.h)
   kSiteNearDup = 18,  // near-duplicate rows: the gathers of the shingles and signatures, the stores of the edges and labels (neardup.h)
-  kBoundSites = 19
+  kSiteOverlap = 19,  // n-gram overlap: the gathers of the windows and table entries, the stores of the table, the candidates and the results (overlap.h)
+  kBoundSites = 20
 };
 #ifdef WP_DEBUG_BOUNDS
 __device__ unsigned int g_wp_oob[kBoundSites];

@@ -1,6 +1,6 @@
 // context.h — what a vocabulary handle owns on a device: streams, vocabulary tables, bump arenas, the pool of parked
 // contexts (the C ABI itself is in encoder.hip; the device path in linear_path.h and fast_path.h, the layers on top of
-// it in rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h and neardup_path.h).
+// it in rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h and overlap_path.h).
 #pragma once
 #include <array>
 #include <cstring>
@@ -155,7 +155,7 @@ static int bit_length(uint64_t v) {
 // c->d_scalars: kScalars 32-bit words that kernels and scans leave their totals in; c->h_scalars: the pinned mirror the
 // host reads them from.  Every word has a name here and nowhere else; no call site names a number.  An encode clears
 // the whole block when it starts (and the pre-pass of WP_OPT_NORMALIZE in front of it does the same, see below).
-constexpr int kScalars = 148;
+constexpr int kScalars = 174;
 constexpr int kScalarCps = 0;       // code points of the text, 32 bits: the decode scan (linear, fast) -> host
 constexpr int kScalarAlphabet = 1;  // alphabet size: alphabet_prefix_kernel -> host
 constexpr int kScalarInvalid = 2;   // invalid sequences, 64 bits (words 2, 3): decode_count_kernel / norm_count_kernel -> host
@@ -221,6 +221,13 @@ constexpr int kScalarDedupUnique = 121, kScalarDedup = 122;
 // 140..147, NearCounter)
 constexpr int kScalarNearBad = 130, kScalarNearRuns = 131, kScalarNearElems = 132, kScalarNearPositions = 134, kScalarNearEdges = 136;
 constexpr int kScalarNearChanged = 137, kScalarNearUnique = 138, kScalarNearOutBytes = 139, kScalarNear = 140;
+// n-gram overlap (overlap.h): the first bad row of the corpus and of the reference set (~0: none) / row_off[n_rows] and
+// ref_off[n_ref], 64 bits each (words 150..153) / the windows of both, 64 bits each (words 154..157) / the runs of the
+// reference sort / the table entries / the candidates / the hits / the covered elements / the kept rows / the bytes of
+// the compact form / a free word / the 64-bit counters of a call (words 166..173, OvlCounter)
+constexpr int kScalarOvlBad = 148, kScalarOvlRefBad = 149, kScalarOvlElems = 150, kScalarOvlRefElems = 152, kScalarOvlWindows = 154;
+constexpr int kScalarOvlRefWindows = 156, kScalarOvlRuns = 158, kScalarOvlEntries = 159, kScalarOvlCands = 160, kScalarOvlHits = 161;
+constexpr int kScalarOvlCovered = 162, kScalarOvlKept = 163, kScalarOvlOutBytes = 164, kScalarFree165 = 165, kScalarOvl = 166;
 // normalize_on_device runs in front of the encode, which clears the block again: while it runs, four slots mean
 constexpr int kScalarNormBytes = kScalarCps;           // bytes of the normalised text, 32 bits: its scan
 constexpr int kScalarNormCps = kScalarAlphabet;        // code points of the normalised text (offsets mode) -> host
@@ -252,7 +259,11 @@ constexpr ScalarRange kScalarLayout[] = {
     {kScalarDedupLeft, 1},   {kScalarDedupUnique, 1}, {kScalarDedup, 8},
     {kScalarNearBad, 1},     {kScalarNearRuns, 1},    {kScalarNearElems, 2},      {kScalarNearPositions, 2},
     {kScalarNearEdges, 1},   {kScalarNearChanged, 1}, {kScalarNearUnique, 1},     {kScalarNearOutBytes, 1},
-    {kScalarNear, 8}};
+    {kScalarNear, 8},
+    {kScalarOvlBad, 1},      {kScalarOvlRefBad, 1},   {kScalarOvlElems, 2},       {kScalarOvlRefElems, 2},
+    {kScalarOvlWindows, 2},  {kScalarOvlRefWindows, 2}, {kScalarOvlRuns, 1},      {kScalarOvlEntries, 1},
+    {kScalarOvlCands, 1},    {kScalarOvlHits, 1},     {kScalarOvlCovered, 1},     {kScalarOvlKept, 1},
+    {kScalarOvlOutBytes, 1}, {kScalarFree165, 1},     {kScalarOvl, 8}};
 // one past the last word of the range `slot` lies in: where a download or a clear "through" that slot ends
 constexpr int scalar_end(int slot) {
   for (const ScalarRange &r : kScalarLayout) {
@@ -363,6 +374,10 @@ struct Context {
   // and `cluster` of the last call), the per-item arrays of the grouping and the edge list, and the table and the
   // compact form of the last call
   DeviceBuffer neardup_in, neardup_rows, neardup_items, neardup_out;
+  // n-gram overlap (overlap.h): the data and the offsets of both batches of a host call, the per-row arrays of both (with
+  // hits, first_hit, first_ref, covered and ref_hits of the last call), the per-element and per-window arrays of the
+  // table and the lookup (with mask), and the compact form of the last call
+  DeviceBuffer overlap_in, overlap_ref_in, overlap_rows, overlap_items, overlap_out;
   // WP_OPT_NORMALIZE (normalize.h): the tables (uploaded with the first normalising call), the normalised text, the
   // tile counts of the pre-pass, and the source of every normalised code point (offsets mode)
   uint16_t *d_norm_index = nullptr;
@@ -406,12 +421,13 @@ struct Context {
     size_t n = 0, n_text = 0;
   } dbg;
   // every DeviceBuffer above, for destroy_context, release_arenas and park_context: a new buffer is one more name here
-  std::array<DeviceBuffer *, 40> buffers() {
+  std::array<DeviceBuffer *, 45> buffers() {
     return {&text_buf, &a_buf,    &b_buf,   &fmt_buf,    &text_buf2, &ids_stage[0], &ids_stage[1], &rows_in,   &rows_out,
             &pad_buf,  &inputs_buf, &norm_buf, &norm_aux, &norm_map, &detok_in,     &detok_aux,    &detok_out,
             &pack_in,  &pack_plan,  &pack_tab, &pack_out, &special_text, &special_in, &special_lit, &special_out,
             &count_aux, &count_words, &count_out, &learn_in, &learn_aux, &learn_items, &learn_groups, &learn_out,
-            &dedup_in, &dedup_rows, &dedup_out, &neardup_in, &neardup_rows, &neardup_items, &neardup_out};
+            &dedup_in, &dedup_rows, &dedup_out, &neardup_in, &neardup_rows, &neardup_items, &neardup_out,
+            &overlap_in, &overlap_ref_in, &overlap_rows, &overlap_items, &overlap_out};
   }
   Context() = default;
   Context(const Context &) = delete;
@@ -489,6 +505,8 @@ struct EncodeStats : wp_stats {
   int32_t dedup_call;
   wp_neardup_stats neardup;  // wp_get_neardup_stats: filled by a neardup call (neardup_call 1), zero otherwise
   int32_t neardup_call;
+  wp_overlap_stats overlap;  // wp_get_overlap_stats: filled by an overlap call (overlap_call 1), zero otherwise
+  int32_t overlap_call;
 };
 
 #ifndef WP_LATE_REFINE_DEFAULT

@@ -2,7 +2,7 @@
 // device code is compiled in: the entry points (out-pointers, the answers that need no device, uploads and downloads),
 // the pinned pool, the multi-GPU, batch, stream, file and external calls.  The device path itself: linear_path.h
 // (word_piece::linear, stage by stage) and fast_path.h (word_piece::fast); the layers on top of it, one host header
-// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h; what a handle owns
+// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h; what a handle owns
 // on a device: context.h.
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -33,6 +33,7 @@
 #include "linear_path.h"
 #include "mask_path.h"
 #include "neardup_path.h"
+#include "overlap_path.h"
 #include "pack_path.h"
 #include "rows_path.h"
 #include "special_path.h"
@@ -1525,6 +1526,81 @@ int wp_neardup_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row
       return;
     }
     neardup_on_device(v, get_context(v), RaggedIn{d_data, reinterpret_cast<const long long *>(d_row_off), n_rows, plan.elem_bytes}, plan, d_out);
+  });
+}
+
+}  // extern "C"
+
+// ---- n-gram overlap (include/wordpiece_amd.h, section "n-gram overlap"; host path: overlap_path.h) ---------------------
+extern "C" {
+
+int wp_get_overlap_stats(const wp_vocab *v, wp_overlap_stats *out) {
+  *out = v->stats.overlap;
+  if (!v->stats.overlap_call) out->n_rows = -1;
+  return WP_OK;
+}
+
+int wp_overlap_rows(wp_vocab *v, const void *data, const int64_t *row_off, size_t n_rows, const void *ref_data, const int64_t *ref_off, size_t n_ref,
+                    const wp_overlap_spec *spec, wp_overlap_result *out) {
+  return guarded([&] {
+    if (out) *out = wp_overlap_result{};
+    const OverlapPlan plan = check_overlap_spec(spec, out);
+    check_overlap_rows(row_off, n_rows, ref_off, n_ref);
+    const unsigned long long n_elems = check_ragged_host("overlap", data, row_off, n_rows, plan.elem_bytes);
+    const unsigned long long n_ref_elems = check_ragged_host("overlap", ref_data, ref_off, n_ref, plan.elem_bytes, "ref_off", "ref_data");
+    if (n_rows == 0) {  // (nothing to hand out: every pointer of the result stays NULL)
+      begin_overlap_stats(v, 0, n_ref);
+      out->n_ref = static_cast<int64_t>(n_ref);
+      return;
+    }
+    const unsigned long long n_windows = host_windows(row_off, n_rows, plan.ngram), n_ref_windows = host_windows(ref_off, n_ref, plan.ngram);
+    if (n_windows == 0 || n_ref_windows == 0) {
+      *out = overlap_no_window(v, plan, data, row_off, n_rows, ref_data, ref_off, n_ref, n_windows, n_ref_windows);
+      return;
+    }
+    Context *c = get_context(v);
+    const uint32_t eb = plan.elem_bytes;
+    const RaggedIn in = upload_ragged(c->overlap_in, c->stream, data, row_off, n_rows, static_cast<size_t>(n_elems) * eb, eb);
+    const RaggedIn ref = upload_ragged(c->overlap_ref_in, c->stream, ref_data, ref_off, n_ref, static_cast<size_t>(n_ref_elems) * eb, eb);
+    wp_overlap_result d;
+    overlap_on_device(v, c, in, ref, plan, &d);
+    wp_overlap_result h = d;
+    h.hits = h.first_hit = h.covered = h.ref_hits = h.row_off = nullptr;
+    h.first_ref = h.kept = nullptr;
+    h.mask = nullptr;
+    h.data = nullptr;
+    Downloads down(c->stream);
+    down.add(&h.hits, d.hits, n_rows * sizeof(int64_t));
+    down.add(&h.first_hit, d.first_hit, n_rows * sizeof(int64_t));
+    down.add(&h.covered, d.covered, n_rows * sizeof(int64_t));
+    down.add(&h.first_ref, d.first_ref, n_rows * sizeof(int32_t));
+    if (d.mask) down.add(&h.mask, d.mask, static_cast<size_t>(n_elems));
+    if (d.ref_hits) down.add(&h.ref_hits, d.ref_hits, n_ref * sizeof(int64_t));
+    if (d.kept) down.add(&h.kept, d.kept, static_cast<size_t>(d.n_kept) * sizeof(int32_t));
+    if (d.row_off) down.add(&h.row_off, d.row_off, static_cast<size_t>(d.n_kept + 1) * sizeof(int64_t));
+    if (d.data) down.add(&h.data, d.data, static_cast<size_t>(d.n_elems) * eb);
+    down.finish();
+    *out = h;
+  });
+}
+
+int wp_overlap_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row_off, size_t n_rows, const void *d_ref_data, const int64_t *d_ref_off,
+                           size_t n_ref, const wp_overlap_spec *spec, wp_overlap_result *d_out) {
+  return guarded([&] {
+    if (d_out) *d_out = wp_overlap_result{};
+    const OverlapPlan plan = check_overlap_spec(spec, d_out);
+    check_overlap_rows(d_row_off, n_rows, d_ref_off, n_ref);
+    check_aligned(d_row_off, 8, "overlap: row_off must be 8-byte aligned");
+    check_aligned(d_ref_off, 8, "overlap: ref_off must be 8-byte aligned");
+    check_aligned(d_data, 4, "overlap: data must be 4-byte aligned");
+    check_aligned(d_ref_data, 4, "overlap: ref_data must be 4-byte aligned");
+    if (n_rows == 0) {  // (nothing to read and nothing to hand out: every pointer of the result stays NULL)
+      begin_overlap_stats(v, 0, n_ref);
+      d_out->n_ref = static_cast<int64_t>(n_ref);
+      return;
+    }
+    overlap_on_device(v, get_context(v), RaggedIn{d_data, reinterpret_cast<const long long *>(d_row_off), n_rows, plan.elem_bytes},
+                      RaggedIn{d_ref_data, reinterpret_cast<const long long *>(d_ref_off), n_ref, plan.elem_bytes}, plan, d_out);
   });
 }
 

@@ -1,5 +1,5 @@
 // group_path.h — what the layers that group items by a 64-bit key share on a context (word counts: count_path.h, the
-// vocabulary learner: learn_path.h, duplicate rows: dedup_path.h, near-duplicate rows: neardup_path.h; kernels: count.h,
+// vocabulary learner: learn_path.h, duplicate rows: dedup_path.h, near-duplicate rows: neardup_path.h, n-gram overlap: overlap_path.h; kernels: count.h,
 // and dedup.h for the table): the launch grid, the arena-guard check, the stage timing of a call, the run heads of a
 // sorted key list, the end of a collision round, a ragged batch on the device and the table with its compact form.
 #pragma once
@@ -104,19 +104,21 @@ struct RaggedIn {
 static void check_ragged_bytes(const char *layer, unsigned long long n_elems, uint32_t elem_bytes) {
   if (n_elems > static_cast<unsigned long long>(UINT32_MAX) / elem_bytes) throw std::length_error(std::string(layer) + ": the data has more than UINT32_MAX bytes");
 }
-static void throw_bad_row(const char *layer, size_t row) {
-  throw std::invalid_argument(std::string(layer) + (row == 0 ? ": row_off must start at 0 and never descend: row 0" : ": row_off must never descend: row " + std::to_string(row)));
+static void throw_bad_row(const char *layer, size_t row, const char *off_name = "row_off") {
+  throw std::invalid_argument(std::string(layer) + ": " + off_name + (row == 0 ? " must start at 0 and never descend: row 0" : " must never descend: row " + std::to_string(row)));
 }
 
-// the offsets of a batch in host memory, walked: returns the number of elements
-static unsigned long long check_ragged_host(const char *layer, const void *data, const int64_t *row_off, size_t n_rows, uint32_t elem_bytes) {
-  if (n_rows != 0 && row_off[0] != 0) throw_bad_row(layer, 0);
+// the offsets of a batch in host memory, walked: returns the number of elements (off_name, data_name: what a message
+// calls the two arrays of the batch)
+static unsigned long long check_ragged_host(const char *layer, const void *data, const int64_t *row_off, size_t n_rows, uint32_t elem_bytes,
+                                            const char *off_name = "row_off", const char *data_name = "data") {
+  if (n_rows != 0 && row_off[0] != 0) throw_bad_row(layer, 0, off_name);
   for (size_t r = 0; r < n_rows; r++) {
-    if (row_off[r + 1] < row_off[r]) throw_bad_row(layer, r);
+    if (row_off[r + 1] < row_off[r]) throw_bad_row(layer, r, off_name);
   }
   const unsigned long long n_elems = n_rows ? static_cast<unsigned long long>(row_off[n_rows]) : 0ull;
   check_ragged_bytes(layer, n_elems, elem_bytes);
-  if (n_elems != 0 && !data) throw std::invalid_argument(std::string(layer) + ": data is NULL");
+  if (n_elems != 0 && !data) throw std::invalid_argument(std::string(layer) + ": " + data_name + " is NULL");
   return n_elems;
 }
 
@@ -137,10 +139,11 @@ static RaggedIn upload_ragged(DeviceBuffer &buf, hipStream_t st, const void *dat
 
 // what the layer's row kernel found, behind the wait that brought it: `bad` the first row whose offsets fail the check
 // (kDedupNoBad: none), n_elems the last offset.  Returns the bytes of the data.
-static size_t check_ragged_device(const char *layer, const RaggedIn &in, uint32_t bad, unsigned long long n_elems) {
-  if (bad != kDedupNoBad) throw_bad_row(layer, bad);
+static size_t check_ragged_device(const char *layer, const RaggedIn &in, uint32_t bad, unsigned long long n_elems, const char *off_name = "row_off",
+                                  const char *data_name = "data") {
+  if (bad != kDedupNoBad) throw_bad_row(layer, bad, off_name);
   check_ragged_bytes(layer, n_elems, in.elem_bytes);
-  if (n_elems != 0 && !in.d_data) throw std::invalid_argument(std::string(layer) + ": data is NULL");
+  if (n_elems != 0 && !in.d_data) throw std::invalid_argument(std::string(layer) + ": " + data_name + " is NULL");
   return static_cast<size_t>(n_elems) * in.elem_bytes;
 }
 

@@ -777,6 +777,77 @@ int wp_overlap_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row
 typedef struct { int64_t n_rows, n_ref, n_elems, n_ref_elems, n_windows, n_ref_windows, n_ref_distinct, n_hits, n_hit_rows, n_covered, n_candidates, n_collided; } wp_overlap_stats;
 int wp_get_overlap_stats(const wp_vocab *v, wp_overlap_stats *out);   /* n_rows == -1: no such call yet, or an encode since */
 
+/* ---- repeated spans (an addition: the windows of a ragged batch that already occurred earlier in the same batch, found
+ * on the device, exactly, and cut out there — the exact-substring step of a corpus pipeline: licence headers, navigation
+ * bars, templated paragraphs inside rows that are otherwise different; the contract is the one stated here, and
+ * tests/repeat_model.py is its executable form) ----
+ * Input.  One batch as wp_dedup_rows takes it: data, a flat stream of elements of spec->elem_bytes bytes (1: text, 4:
+ * ids), and row_off int64 [n_rows + 1], ascending from 0, in elements; a row may start at any byte.  No vocabulary is
+ * read: the handle lends its device context (WP_OPT_STAGE_TIMING and WP_OPT_ARENA_GUARD are its only options that matter).
+ * Windows.  As in wp_overlap_rows: k = spec->ngram in [1, 64]; a row of L >= k elements has the windows at p = 0 .. L - k,
+ * a shorter row has none; no window crosses a row boundary.  The flat position of (row i, p) is row_off[i] + p.
+ * Repeat.  The first occurrence of a window is the smallest flat position that holds an equal window (the same
+ * k * elem_bytes bytes); it may lie in the same row and it may overlap the window itself.  spec->scope 0 (anywhere): a
+ * window is a repeat iff its first occurrence is not itself.  scope 1 (earlier rows only): iff its first occurrence lies
+ * in a row of smaller index — what a row repeats of itself stays; the smallest occurrence lies in the smallest row, so
+ * the same grouping answers both.
+ * Covered.  An element is covered iff it lies in [p, p + k) of some repeat window of its row: the union, so a stretch may
+ * be covered piecewise from several sources.  A first occurrence is never a repeat, but its elements may be covered by
+ * other repeat windows: with k = 2, "aaaa" keeps "a".
+ * spec->flags: WP_REPEAT_UTF8 (elem_bytes 1 only, WP_ERR_ARG otherwise): position p is a window only if byte p is no
+ * continuation byte (10xxxxxx) and byte p + k is past the row end or no continuation byte.  The other positions are
+ * windows neither as repeats nor as sources, so a cut never splits a sequence: valid UTF-8 stays valid.  The rule reads
+ * bytes only and is defined for invalid text too.
+ * Result, always, per row: repeats int64 [n_rows], the repeat windows of row i; first_repeat int64, the smallest
+ * repeating p or -1; first_src_row int32, the row of the first occurrence of the window at first_repeat, or -1;
+ * first_src_pos int64, the position of that first occurrence in its row, or -1; covered int64.  With
+ * WP_REPEAT_WANT_MASK: mask uint8 [n_elems], 1 where the element is covered.  With WP_REPEAT_WANT_SRC: src int64
+ * [n_elems], the flat position of the first occurrence where the window at that element is a repeat, else -1.  With
+ * WP_REPEAT_WANT_COMPACT: kept int32 [n_kept], the rows with repeats[i] <= spec->max_repeats ascending, and those rows
+ * whole and back to back as data and row_off int64 [n_kept + 1], n_elems elements, as the compact form of
+ * wp_overlap_rows.  With WP_REPEAT_WANT_CUT: cut_data and cut_off int64 [n_rows + 1], every row with its covered
+ * elements removed (data[mask == 0]) and its index unchanged — a row may become empty — and n_cut_elems, their number.
+ * Both forms may be asked for in one call.  Without a bit its arrays are NULL and its counts 0.
+ * Exactness.  No result array depends on a hash, a seed or an order of execution: every window a key groups is compared
+ * byte by byte, every position is written by one lane, and every combination across lanes is an integer sum.
+ * hash_bits (0: 64; else 8..64) narrows the window key to its low bits, for tests, and never changes a result.  The
+ * default is the full 64 bits whatever the window count: no narrower default was measured, so none is claimed.
+ * WP_ERR_ARG, before a device is touched and with the field named: spec or out NULL, elem_bytes not 1 or 4, want with a
+ * bit outside 15, ngram outside [1, 64], scope outside {0, 1}, max_repeats < 0, hash_bits not 0 and outside [8, 64],
+ * flags other than WP_REPEAT_UTF8 (and that one with elem_bytes 4), reserved not 0, row_off NULL with n_rows > 0; data
+ * NULL with elements.  Offsets that do not start at 0 or descend give WP_ERR_ARG with the first bad row: the host form
+ * checks on the host, the device form by a kernel, before anything reads through them.
+ * WP_ERR_TOO_LARGE: n_rows >= 2^31, or the batch over UINT32_MAX bytes.
+ * Host form: the blocks of *out are malloc'd, each freed with wp_free; a block is NULL where it is empty or was not asked
+ * for.  n_rows == 0 returns all NULL; a batch without any window is answered without a device (repeats and covered 0,
+ * the firsts -1, every row kept, the cut equal to the input).  Device form: the buffer contract of wp_dedup_rows_device;
+ * the arrays of *d_out are device memory owned by the handle until its next call (n_rows == 0: all NULL).  Nothing
+ * behind n_elems * elem_bytes influences a result.
+ * Cost.  All work is flat over the elements or the windows of the batch, never over rows: one row of 10^8 elements costs
+ * what 10^6 rows of 100 do.
+ * Waits of a call, set by the spec alone: one for the sizes (the offset check, the elements, the windows), with
+ * WP_REPEAT_UTF8 one for the number of eligible windows (without the flag every window is listed and the first wait
+ * brought their number), with WP_REPEAT_WANT_COMPACT one for the kept count, one that ends the call.  The cut is bounded
+ * by the input and needs none.  With WP_OPT_STAGE_TIMING a call leaves its device times (HIP events) in wp_stats:
+ * ms_decode (the offset check), ms_sa (keys, sort, distinct windows, first occurrences), ms_scan (the repeat flags, their
+ * scan, the cover pass), ms_walk (the per-row results, the cut, the compact form), ms_total (their sum); ms_normalize is 0. */
+#define WP_REPEAT_WANT_MASK    1
+#define WP_REPEAT_WANT_SRC     2
+#define WP_REPEAT_WANT_COMPACT 4
+#define WP_REPEAT_WANT_CUT     8
+#define WP_REPEAT_UTF8         1
+typedef struct { int32_t elem_bytes, want, ngram, scope, max_repeats, hash_bits, flags, reserved; } wp_repeat_spec;
+typedef struct { int64_t *repeats, *first_repeat, *first_src_pos, *covered, *src, *row_off, *cut_off; int32_t *first_src_row, *kept; uint8_t *mask; void *data, *cut_data; int64_t n_rows, n_kept, n_elems, n_cut_elems; } wp_repeat_result;
+int wp_repeat_rows(wp_vocab *v, const void *data, const int64_t *row_off, size_t n_rows, const wp_repeat_spec *spec, wp_repeat_result *out);
+int wp_repeat_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row_off, size_t n_rows, const wp_repeat_spec *spec, wp_repeat_result *d_out);
+/* The statistics of the last repeat call, in a struct of its own.  n_rows, n_elems, n_windows (with WP_REPEAT_UTF8: the
+ * eligible ones), n_distinct (the distinct windows), n_repeats (the sum of repeats; at scope 0 n_windows - n_distinct),
+ * n_repeat_rows (the rows with a repeat), n_covered (the sum of covered), n_cut_elems (with WP_REPEAT_WANT_CUT n_elems -
+ * n_covered, else 0): functions of the contract.  n_collided (the windows that differ from the first window of their
+ * key) depends on the hash and is only reported. */
+typedef struct { int64_t n_rows, n_elems, n_windows, n_distinct, n_repeats, n_repeat_rows, n_covered, n_cut_elems, n_collided; } wp_repeat_stats;
+int wp_get_repeat_stats(const wp_vocab *v, wp_repeat_stats *out);   /* n_rows == -1: no such call yet, or an encode since */
+
 /* The same call sharded over several GPUs of the node, behind the boundary: the reference's own
  * precedent is the in-library chunking at whitespace of linear.cpp:283-299 (thread chunks) and
  * linear.cpp:355-367 (encodeExternal batches).  The text is cut at ASCII whitespace into one shard

@@ -66,6 +66,7 @@ ABI_SYMBOLS = [
     "wp_dedup_rows", "wp_dedup_rows_device", "wp_get_dedup_stats",
     "wp_neardup_rows", "wp_neardup_rows_device", "wp_get_neardup_stats",
     "wp_overlap_rows", "wp_overlap_rows_device", "wp_get_overlap_stats",
+    "wp_repeat_rows", "wp_repeat_rows_device", "wp_get_repeat_stats",
 ]
 
 
@@ -330,6 +331,34 @@ class OverlapStats(C.Structure):
                 ("n_covered", C.c_int64), ("n_candidates", C.c_int64), ("n_collided", C.c_int64)]
 
 
+WP_REPEAT_WANT_MASK = 1
+WP_REPEAT_WANT_SRC = 2
+WP_REPEAT_WANT_COMPACT = 4
+WP_REPEAT_WANT_CUT = 8
+WP_REPEAT_UTF8 = 1
+
+
+class RepeatSpec(C.Structure):
+    """wp_repeat_spec: the arguments of a repeat call (elem_bytes 1: text, 4: ids; ngram: elements per window; scope 0:
+    anywhere, 1: earlier rows only; flags: WP_REPEAT_UTF8)."""
+    _fields_ = [("elem_bytes", C.c_int32), ("want", C.c_int32), ("ngram", C.c_int32), ("scope", C.c_int32), ("max_repeats", C.c_int32),
+                ("hash_bits", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RepeatResult(C.Structure):
+    """wp_repeat_result: the arrays of a repeat call (host blocks, or device memory owned by the handle)."""
+    _fields_ = [("repeats", C.c_void_p), ("first_repeat", C.c_void_p), ("first_src_pos", C.c_void_p), ("covered", C.c_void_p), ("src", C.c_void_p),
+                ("row_off", C.c_void_p), ("cut_off", C.c_void_p), ("first_src_row", C.c_void_p), ("kept", C.c_void_p), ("mask", C.c_void_p),
+                ("data", C.c_void_p), ("cut_data", C.c_void_p), ("n_rows", C.c_int64), ("n_kept", C.c_int64), ("n_elems", C.c_int64),
+                ("n_cut_elems", C.c_int64)]
+
+
+class RepeatStats(C.Structure):
+    """wp_repeat_stats: the statistics of the last repeat call (Vocab.repeat_stats())."""
+    _fields_ = [("n_rows", C.c_int64), ("n_elems", C.c_int64), ("n_windows", C.c_int64), ("n_distinct", C.c_int64), ("n_repeats", C.c_int64),
+                ("n_repeat_rows", C.c_int64), ("n_covered", C.c_int64), ("n_cut_elems", C.c_int64), ("n_collided", C.c_int64)]
+
+
 def lsh_min_agree(threshold, n_perm):
     """The min_agree that stands for a Jaccard threshold: ceil(threshold * n_perm) signature slots."""
     return int(math.ceil(threshold * n_perm))
@@ -445,6 +474,10 @@ def lib():
             L.wp_overlap_rows.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(OverlapSpec), C.POINTER(OverlapResult)]
             L.wp_overlap_rows_device.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(OverlapSpec), C.POINTER(OverlapResult)]
             L.wp_get_overlap_stats.argtypes = [vp, C.POINTER(OverlapStats)]
+        if hasattr(L, "wp_repeat_rows"):  # (WP_LIB, as above)
+            L.wp_repeat_rows.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(RepeatSpec), C.POINTER(RepeatResult)]
+            L.wp_repeat_rows_device.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(RepeatSpec), C.POINTER(RepeatResult)]
+            L.wp_get_repeat_stats.argtypes = [vp, C.POINTER(RepeatStats)]
         L.wp_linear_encode_multi.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.POINTER(i32p),
                                              C.POINTER(C.c_size_t)]
         L.wp_reserve.argtypes = [vp, C.c_size_t]
@@ -1703,6 +1736,142 @@ class Vocab:
         ref_text, ref_off = join_docs(ref_docs)
         r = self.overlap_rows(text, off, ref_text, ref_off, ngram=ngram, max_hits=max_hits, compact=True)
         return [docs[k] for k in r["kept"]], r["hits"]
+
+    def repeat_stats(self):
+        """wp_repeat_stats of the last repeat call as a dict (n_rows -1: no such call yet)."""
+        s = RepeatStats()
+        _check(lib().wp_get_repeat_stats(self._h, C.byref(s)))
+        return {k: int(getattr(s, k)) for k, _ in s._fields_}
+
+    @staticmethod
+    def _repeat_spec(elem_bytes, ngram, scope, max_repeats, mask, src, compact, cut, utf8, hash_bits):
+        want = (WP_REPEAT_WANT_MASK if mask else 0) | (WP_REPEAT_WANT_SRC if src else 0) | (WP_REPEAT_WANT_COMPACT if compact else 0) | \
+            (WP_REPEAT_WANT_CUT if cut else 0)
+        if utf8 is None:  # (on for text, off for ids)
+            utf8 = elem_bytes == 1
+        return RepeatSpec(elem_bytes, want, int(ngram), int(scope), int(max_repeats), int(hash_bits), WP_REPEAT_UTF8 if utf8 else 0, 0)
+
+    def repeat_rows(self, data, row_off, ngram=50, scope=0, max_repeats=0, mask=False, src=False, compact=False, cut=False, utf8=None,
+                    hash_bits=0, lines=False):
+        """The spans a ragged batch repeats, found on the device, exactly, and cut out there (wp_repeat_rows).  data /
+        row_off: the batch as dedup_rows takes it (text or int32 ids; lines=True, or offsets None: the lines of a text).
+        A window is `ngram` consecutive elements of a row; it is a repeat where an equal window begins at a smaller flat
+        position (scope 0) or in an earlier row (scope 1).  -> {"repeats": np.int64 [n_rows], "first_repeat": np.int64
+        (the first repeating position, or -1), "first_src_row": np.int32 and "first_src_pos": np.int64 (where that window
+        first occurred, or -1), "covered": np.int64 (the elements inside a repeat window)}, with mask "mask": np.uint8 per
+        element, with src "src": np.int64 per element (the flat position of the first occurrence of a repeat, else -1),
+        with compact "kept": np.int32 (the rows with repeats <= max_repeats) and their "data" and "row_off" back to
+        back, with cut "cut_data" and "cut_off": every row without its covered elements.  utf8 (None: on for text, off
+        for ids): windows begin and end at code point boundaries, so the cut of valid UTF-8 is valid.  Text comes back as
+        bytes.  hash_bits: for tests of key collisions."""
+        if lines and row_off is not None:
+            raise WordPieceError("repeat: the lines form takes no offsets")
+        data, off, n = self._overlap_batch(data, row_off, "data")
+        spec = self._repeat_spec(data.dtype.itemsize, ngram, scope, max_repeats, mask, src, compact, cut, utf8, hash_bits)
+        out = RepeatResult()
+        _check(lib().wp_repeat_rows(self._h, data.ctypes.data if data.size else None, off.ctypes.data if n else None, n, C.byref(spec), C.byref(out)))
+
+        def block(ptr, k, dtype):
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(np.ctypeslib.as_ctypes_type(dtype))), (k,)).copy() if k and ptr else \
+                np.zeros(0, dtype=dtype)
+
+        def elems(ptr, k):
+            a = block(ptr, k, data.dtype)
+            return a.tobytes() if data.dtype == np.uint8 else a
+        try:
+            n_elems = int(off[n]) if n else 0
+            res = {"repeats": block(out.repeats, n, np.int64), "first_repeat": block(out.first_repeat, n, np.int64),
+                   "first_src_row": block(out.first_src_row, n, np.int32), "first_src_pos": block(out.first_src_pos, n, np.int64),
+                   "covered": block(out.covered, n, np.int64)}
+            if mask:
+                res["mask"] = block(out.mask, n_elems, np.uint8)
+            if src:
+                res["src"] = block(out.src, n_elems, np.int64)
+            if compact:
+                res["kept"] = block(out.kept, out.n_kept, np.int32)
+                res["data"] = elems(out.data, out.n_elems)
+                res["row_off"] = block(out.row_off, out.n_kept + 1, np.int64) if n else np.zeros(1, dtype=np.int64)
+            if cut:
+                res["cut_data"] = elems(out.cut_data, out.n_cut_elems)
+                res["cut_off"] = block(out.cut_off, n + 1, np.int64) if n else np.zeros(1, dtype=np.int64)
+        finally:
+            for blk in (out.repeats, out.first_repeat, out.first_src_pos, out.covered, out.src, out.row_off, out.cut_off, out.first_src_row, out.kept,
+                        out.mask, out.data, out.cut_data):
+                if blk:
+                    lib().wp_free(blk)
+        return res
+
+    def repeat_rows_tensor(self, data, row_off, ngram=50, scope=0, max_repeats=0, mask=False, src=False, compact=False, cut=False, utf8=None,
+                           hash_bits=0, copy=True):
+        """repeat_rows for a batch in tensors on this handle's GPU (wp_repeat_rows_device): data uint8 (text) or int32
+        (ids), row_off int64 — the ids and row_splits of encode_rows_tensor, the compact form of dedup_rows_tensor, a
+        joined text and its doc_off.  -> a dict of tensors on that device with the keys of repeat_rows; "data" + "row_off"
+        and "cut_data" + "cut_off" are what pack_sequences_tensor takes.  copy=False: views of the library's buffers,
+        valid until the next call on this handle."""
+        import torch
+        if data.dtype not in (torch.uint8, torch.int32) or row_off.dtype != torch.int64:
+            raise WordPieceError("repeat_rows_tensor needs uint8 or int32 data and int64 offsets")
+        for t in (data, row_off):
+            if not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
+                raise WordPieceError("repeat_rows_tensor needs flat contiguous CUDA/HIP tensors")
+            if self._device is not None and t.device.index != self._device:  # (raw pointers go to the handle's device)
+                raise WordPieceError("the tensors lie on %s, the handle on device %d" % (t.device, self._device))
+        n = row_off.numel() - 1
+        if n < 0:
+            raise WordPieceError("repeat: offsets need n_rows + 1 entries")
+        n_elems = data.numel()
+        nbytes = n_elems * data.element_size()
+        if data.dtype == torch.uint8 and (data.data_ptr() % 4 != 0 or nbytes % 4 != 0):  # (the kernels read whole aligned words)
+            padded = torch.zeros((nbytes + 19) // 16 * 16, dtype=torch.uint8, device=data.device)
+            padded[:nbytes] = data
+            data = padded
+        spec = self._repeat_spec(data.element_size(), ngram, scope, max_repeats, mask, src, compact, cut, utf8, hash_bits)
+        dev = data.device
+        torch.cuda.current_stream(dev).synchronize()  # the library runs on its own HIP streams
+        out = RepeatResult()
+        _check(lib().wp_repeat_rows_device(self._h, C.c_void_p(data.data_ptr()) if nbytes else None, C.c_void_p(row_off.data_ptr()), n,
+                                           C.byref(spec), C.byref(out)))
+
+        def view(ptr, k, typestr, dtype):
+            if not k or not ptr:
+                return torch.zeros(0, dtype=dtype, device=dev)
+            t = torch.as_tensor(DeviceIds(ptr, k, typestr=typestr), device=dev)
+            return t.clone() if copy else t
+        etype = "|u1" if data.dtype == torch.uint8 else "<i4"
+        res = {"repeats": view(out.repeats, n, "<i8", torch.int64), "first_repeat": view(out.first_repeat, n, "<i8", torch.int64),
+               "first_src_row": view(out.first_src_row, n, "<i4", torch.int32), "first_src_pos": view(out.first_src_pos, n, "<i8", torch.int64),
+               "covered": view(out.covered, n, "<i8", torch.int64)}
+        if mask or src:
+            last = min(n_elems, int(row_off[n])) if n else 0
+            if mask:
+                res["mask"] = view(out.mask, last if out.mask else 0, "|u1", torch.uint8)
+            if src:
+                res["src"] = view(out.src, last if out.src else 0, "<i8", torch.int64)
+        if compact:
+            res["kept"] = view(out.kept, out.n_kept, "<i4", torch.int32)
+            res["data"] = view(out.data, out.n_elems, etype, data.dtype)
+            res["row_off"] = view(out.row_off, out.n_kept + 1, "<i8", torch.int64) if n else torch.zeros(1, dtype=torch.int64, device=dev)
+        if cut:
+            res["cut_data"] = view(out.cut_data, out.n_cut_elems, etype, data.dtype)
+            res["cut_off"] = view(out.cut_off, n + 1, "<i8", torch.int64) if n else torch.zeros(1, dtype=torch.int64, device=dev)
+        return res
+
+    def repeat_docs(self, docs, ngram=50, scope=0):
+        """The documents of a list (str / bytes) with the spans cut out that occurred before in the list (windows of
+        `ngram` bytes, at code point boundaries) -> ([the documents, each of the type it was given in], np.int64 covered
+        bytes of every document, the line feed of the join included where a span takes it along); through join_docs and
+        repeat_rows."""
+        docs = list(docs)
+        text, off = join_docs(docs)
+        r = self.repeat_rows(text, off, ngram=ngram, scope=scope, mask=True, cut=True)
+        co = r["cut_off"]
+        out = []
+        for i, d in enumerate(docs):
+            b = r["cut_data"][int(co[i]):int(co[i + 1])]
+            if not r["mask"][int(off[i + 1]) - 1]:  # (the line feed of the join is still there)
+                b = b[:-1]
+            out.append(b.decode("utf8") if isinstance(d, str) else b)
+        return out, r["covered"]
 
     def align_stats(self):
         """wp_align_stats of the last call as a dict (n_rows -1: it was no align call)."""

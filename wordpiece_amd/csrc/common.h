@@ -57,7 +57,8 @@ enum BoundSite {
   kSiteDedup = 17,    // duplicate rows: the stores of the chunk list, the runs and the table, the gathers behind them (dedup.h)
   kSiteNearDup = 18,  // near-duplicate rows: the gathers of the shingles and signatures, the stores of the edges and labels (neardup.h)
   kSiteOverlap = 19,  // n-gram overlap: the gathers of the windows and table entries, the stores of the table, the candidates and the results (overlap.h)
-  kBoundSites = 20
+  kSiteRepeat = 20,   // repeated spans: the stores of the first occurrences, the gathers of the flag and cover passes, the stores of the cut (repeat.h)
+  kBoundSites = 21
 };
 #ifdef WP_DEBUG_BOUNDS
 __device__ unsigned int g_wp_oob[kBoundSites];

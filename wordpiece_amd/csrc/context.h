@@ -1,6 +1,6 @@
 // context.h — what a vocabulary handle owns on a device: streams, vocabulary tables, bump arenas, the pool of parked
 // contexts (the C ABI itself is in encoder.hip; the device path in linear_path.h and fast_path.h, the layers on top of
-// it in rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h and overlap_path.h).
+// it in rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h and repeat_path.h).
 #pragma once
 #include <array>
 #include <cstring>
@@ -155,7 +155,7 @@ static int bit_length(uint64_t v) {
 // c->d_scalars: kScalars 32-bit words that kernels and scans leave their totals in; c->h_scalars: the pinned mirror the
 // host reads them from.  Every word has a name here and nowhere else; no call site names a number.  An encode clears
 // the whole block when it starts (and the pre-pass of WP_OPT_NORMALIZE in front of it does the same, see below).
-constexpr int kScalars = 174;
+constexpr int kScalars = 194;
 constexpr int kScalarCps = 0;       // code points of the text, 32 bits: the decode scan (linear, fast) -> host
 constexpr int kScalarAlphabet = 1;  // alphabet size: alphabet_prefix_kernel -> host
 constexpr int kScalarInvalid = 2;   // invalid sequences, 64 bits (words 2, 3): decode_count_kernel / norm_count_kernel -> host
@@ -228,6 +228,13 @@ constexpr int kScalarNearChanged = 137, kScalarNearUnique = 138, kScalarNearOutB
 constexpr int kScalarOvlBad = 148, kScalarOvlRefBad = 149, kScalarOvlElems = 150, kScalarOvlRefElems = 152, kScalarOvlWindows = 154;
 constexpr int kScalarOvlRefWindows = 156, kScalarOvlRuns = 158, kScalarOvlEntries = 159, kScalarOvlCands = 160, kScalarOvlHits = 161;
 constexpr int kScalarOvlCovered = 162, kScalarOvlKept = 163, kScalarOvlOutBytes = 164, kScalarFree165 = 165, kScalarOvl = 166;
+// repeated spans (repeat.h): the first bad row (~0: none) / the runs of the window sort / row_off[n_rows], 64 bits (words
+// 176, 177) / the windows, 64 bits (words 178, 179) / the listed (eligible) windows / the distinct windows / the repeats /
+// the covered elements / the kept rows / the bytes of the compact form / the 64-bit counters of a call (words 186..193,
+// RepCounter)
+constexpr int kScalarRepBad = 174, kScalarRepRuns = 175, kScalarRepElems = 176, kScalarRepWindows = 178, kScalarRepListed = 180;
+constexpr int kScalarRepDistinct = 181, kScalarRepRepeats = 182, kScalarRepCovered = 183, kScalarRepKept = 184, kScalarRepOutBytes = 185;
+constexpr int kScalarRep = 186;
 // normalize_on_device runs in front of the encode, which clears the block again: while it runs, four slots mean
 constexpr int kScalarNormBytes = kScalarCps;           // bytes of the normalised text, 32 bits: its scan
 constexpr int kScalarNormCps = kScalarAlphabet;        // code points of the normalised text (offsets mode) -> host
@@ -263,7 +270,10 @@ constexpr ScalarRange kScalarLayout[] = {
     {kScalarOvlBad, 1},      {kScalarOvlRefBad, 1},   {kScalarOvlElems, 2},       {kScalarOvlRefElems, 2},
     {kScalarOvlWindows, 2},  {kScalarOvlRefWindows, 2}, {kScalarOvlRuns, 1},      {kScalarOvlEntries, 1},
     {kScalarOvlCands, 1},    {kScalarOvlHits, 1},     {kScalarOvlCovered, 1},     {kScalarOvlKept, 1},
-    {kScalarOvlOutBytes, 1}, {kScalarFree165, 1},     {kScalarOvl, 8}};
+    {kScalarOvlOutBytes, 1}, {kScalarFree165, 1},     {kScalarOvl, 8},
+    {kScalarRepBad, 1},      {kScalarRepRuns, 1},     {kScalarRepElems, 2},       {kScalarRepWindows, 2},
+    {kScalarRepListed, 1},   {kScalarRepDistinct, 1}, {kScalarRepRepeats, 1},     {kScalarRepCovered, 1},
+    {kScalarRepKept, 1},     {kScalarRepOutBytes, 1}, {kScalarRep, 8}};
 // one past the last word of the range `slot` lies in: where a download or a clear "through" that slot ends
 constexpr int scalar_end(int slot) {
   for (const ScalarRange &r : kScalarLayout) {
@@ -378,6 +388,10 @@ struct Context {
   // hits, first_hit, first_ref, covered and ref_hits of the last call), the per-element and per-window arrays of the
   // table and the lookup (with mask), and the compact form of the last call
   DeviceBuffer overlap_in, overlap_ref_in, overlap_rows, overlap_items, overlap_out;
+  // repeated spans (repeat.h): the data and the offsets of a host call, the per-row arrays (with repeats, first_repeat,
+  // first_src_row, first_src_pos and covered of the last call), the per-element and per-window arrays (with mask and
+  // src), and the cut and the compact form of the last call
+  DeviceBuffer repeat_in, repeat_rows, repeat_items, repeat_out;
   // WP_OPT_NORMALIZE (normalize.h): the tables (uploaded with the first normalising call), the normalised text, the
   // tile counts of the pre-pass, and the source of every normalised code point (offsets mode)
   uint16_t *d_norm_index = nullptr;
@@ -421,13 +435,14 @@ struct Context {
     size_t n = 0, n_text = 0;
   } dbg;
   // every DeviceBuffer above, for destroy_context, release_arenas and park_context: a new buffer is one more name here
-  std::array<DeviceBuffer *, 45> buffers() {
+  std::array<DeviceBuffer *, 49> buffers() {
     return {&text_buf, &a_buf,    &b_buf,   &fmt_buf,    &text_buf2, &ids_stage[0], &ids_stage[1], &rows_in,   &rows_out,
             &pad_buf,  &inputs_buf, &norm_buf, &norm_aux, &norm_map, &detok_in,     &detok_aux,    &detok_out,
             &pack_in,  &pack_plan,  &pack_tab, &pack_out, &special_text, &special_in, &special_lit, &special_out,
             &count_aux, &count_words, &count_out, &learn_in, &learn_aux, &learn_items, &learn_groups, &learn_out,
             &dedup_in, &dedup_rows, &dedup_out, &neardup_in, &neardup_rows, &neardup_items, &neardup_out,
-            &overlap_in, &overlap_ref_in, &overlap_rows, &overlap_items, &overlap_out};
+            &overlap_in, &overlap_ref_in, &overlap_rows, &overlap_items, &overlap_out,
+            &repeat_in, &repeat_rows, &repeat_items, &repeat_out};
   }
   Context() = default;
   Context(const Context &) = delete;
@@ -507,6 +522,8 @@ struct EncodeStats : wp_stats {
   int32_t neardup_call;
   wp_overlap_stats overlap;  // wp_get_overlap_stats: filled by an overlap call (overlap_call 1), zero otherwise
   int32_t overlap_call;
+  wp_repeat_stats repeat;  // wp_get_repeat_stats: filled by a repeat call (repeat_call 1), zero otherwise
+  int32_t repeat_call;
 };
 
 #ifndef WP_LATE_REFINE_DEFAULT

@@ -2,7 +2,7 @@
 // device code is compiled in: the entry points (out-pointers, the answers that need no device, uploads and downloads),
 // the pinned pool, the multi-GPU, batch, stream, file and external calls.  The device path itself: linear_path.h
 // (word_piece::linear, stage by stage) and fast_path.h (word_piece::fast); the layers on top of it, one host header
-// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h; what a handle owns
+// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h; what a handle owns
 // on a device: context.h.
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -34,6 +34,7 @@
 #include "mask_path.h"
 #include "neardup_path.h"
 #include "overlap_path.h"
+#include "repeat_path.h"
 #include "pack_path.h"
 #include "rows_path.h"
 #include "special_path.h"
@@ -1601,6 +1602,74 @@ int wp_overlap_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row
     }
     overlap_on_device(v, get_context(v), RaggedIn{d_data, reinterpret_cast<const long long *>(d_row_off), n_rows, plan.elem_bytes},
                       RaggedIn{d_ref_data, reinterpret_cast<const long long *>(d_ref_off), n_ref, plan.elem_bytes}, plan, d_out);
+  });
+}
+
+}  // extern "C"
+
+// ---- repeated spans (include/wordpiece_amd.h, section "repeated spans"; host path: repeat_path.h) ----------------------
+extern "C" {
+
+int wp_get_repeat_stats(const wp_vocab *v, wp_repeat_stats *out) {
+  *out = v->stats.repeat;
+  if (!v->stats.repeat_call) out->n_rows = -1;
+  return WP_OK;
+}
+
+int wp_repeat_rows(wp_vocab *v, const void *data, const int64_t *row_off, size_t n_rows, const wp_repeat_spec *spec, wp_repeat_result *out) {
+  return guarded([&] {
+    if (out) *out = wp_repeat_result{};
+    const RepeatPlan plan = check_repeat_spec(spec, out);
+    check_repeat_rows(row_off, n_rows);
+    const unsigned long long n_elems = check_ragged_host("repeat", data, row_off, n_rows, plan.elem_bytes);
+    if (n_rows == 0) {  // (nothing to hand out: every pointer of the result stays NULL)
+      begin_repeat_stats(v, 0);
+      return;
+    }
+    if (host_windows(row_off, n_rows, plan.ngram) == 0) {
+      *out = repeat_no_window(v, plan, data, row_off, n_rows);
+      return;
+    }
+    Context *c = get_context(v);
+    const uint32_t eb = plan.elem_bytes;
+    const RaggedIn in = upload_ragged(c->repeat_in, c->stream, data, row_off, n_rows, static_cast<size_t>(n_elems) * eb, eb);
+    wp_repeat_result d;
+    repeat_on_device(v, c, in, plan, &d);
+    wp_repeat_result h = d;
+    h.repeats = h.first_repeat = h.first_src_pos = h.covered = h.src = h.row_off = h.cut_off = nullptr;
+    h.first_src_row = h.kept = nullptr;
+    h.mask = nullptr;
+    h.data = h.cut_data = nullptr;
+    Downloads down(c->stream);
+    down.add(&h.repeats, d.repeats, n_rows * sizeof(int64_t));
+    down.add(&h.first_repeat, d.first_repeat, n_rows * sizeof(int64_t));
+    down.add(&h.first_src_pos, d.first_src_pos, n_rows * sizeof(int64_t));
+    down.add(&h.covered, d.covered, n_rows * sizeof(int64_t));
+    down.add(&h.first_src_row, d.first_src_row, n_rows * sizeof(int32_t));
+    if (d.mask) down.add(&h.mask, d.mask, static_cast<size_t>(n_elems));
+    if (d.src) down.add(&h.src, d.src, static_cast<size_t>(n_elems) * sizeof(int64_t));
+    if (d.kept) down.add(&h.kept, d.kept, static_cast<size_t>(d.n_kept) * sizeof(int32_t));
+    if (d.row_off) down.add(&h.row_off, d.row_off, static_cast<size_t>(d.n_kept + 1) * sizeof(int64_t));
+    if (d.data) down.add(&h.data, d.data, static_cast<size_t>(d.n_elems) * eb);
+    if (d.cut_off) down.add(&h.cut_off, d.cut_off, (n_rows + 1) * sizeof(int64_t));
+    if (d.cut_data) down.add(&h.cut_data, d.cut_data, static_cast<size_t>(d.n_cut_elems) * eb);
+    down.finish();
+    *out = h;
+  });
+}
+
+int wp_repeat_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row_off, size_t n_rows, const wp_repeat_spec *spec, wp_repeat_result *d_out) {
+  return guarded([&] {
+    if (d_out) *d_out = wp_repeat_result{};
+    const RepeatPlan plan = check_repeat_spec(spec, d_out);
+    check_repeat_rows(d_row_off, n_rows);
+    check_aligned(d_row_off, 8, "repeat: row_off must be 8-byte aligned");
+    check_aligned(d_data, 4, "repeat: data must be 4-byte aligned");
+    if (n_rows == 0) {  // (nothing to read and nothing to hand out: every pointer of the result stays NULL)
+      begin_repeat_stats(v, 0);
+      return;
+    }
+    repeat_on_device(v, get_context(v), RaggedIn{d_data, reinterpret_cast<const long long *>(d_row_off), n_rows, plan.elem_bytes}, plan, d_out);
   });
 }
 

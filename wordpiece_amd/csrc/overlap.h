@@ -97,13 +97,14 @@ __device__ __forceinline__ uint32_t ovl_elem(const uint32_t *__restrict__ d32, s
 // window; valid[n_elems] = 0 closes the flags for their scan.  Otherwise (the corpus): the key's bucket (bucket: two
 // words per bucket, [first, last) in the entries; shift: the narrowed key's bits below the bucket number), the lower
 // bound of the key among the bucket's entries, and valid[e] = 1, ent_out[e] = that entry where its key is the same: a
-// candidate.
+// candidate.  utf8 != 0 (bytes; the repeat layer, repeat.h — the overlap call passes 0): a window also has to begin at a
+// byte that is no continuation byte and to end in front of one that is none, or at the end of its row.
 __global__ __launch_bounds__(kBlock) void ovl_keys_kernel(const uint32_t *__restrict__ d32, size_t n_elems, const uint32_t *__restrict__ byte_off,
                                                           size_t n_rows, uint32_t elem_bytes, uint32_t k, OvlPowers pw, uint64_t mask,
                                                           uint64_t *__restrict__ key_out, uint32_t *__restrict__ valid,
                                                           const uint64_t *__restrict__ ent_key, const uint32_t *__restrict__ n_ent_dev,
                                                           const uint32_t *__restrict__ bucket, uint32_t shift, size_t n_buckets,
-                                                          uint32_t *__restrict__ ent_out) {
+                                                          uint32_t *__restrict__ ent_out, uint32_t utf8) {
   __shared__ uint32_t s_x[kOvlSpan];
   __shared__ uint64_t s_q[kOvlSpan + 1];
   __shared__ uint64_t s_wave[kBlock / kWave];
@@ -159,7 +160,8 @@ __global__ __launch_bounds__(kBlock) void ovl_keys_kernel(const uint32_t *__rest
     if (e >= n_elems) break;
     const size_t addr = e * elem_bytes;
     const uint32_t r = ovl_row_of(byte_off, r_lo, r_hi, addr);
-    const bool fits = addr + win_bytes <= byte_off[r + 1];
+    bool fits = addr + win_bytes <= byte_off[r + 1];
+    if (utf8 && fits) fits = (s_x[p] & 0xc0u) != 0x80u && (addr + win_bytes == byte_off[r + 1] || (s_x[p + k] & 0xc0u) != 0x80u);
     const uint64_t key = count_mix(s_q[p + k] - s_q[p] * pw.bk) & mask;
     if (!ent_key) {
       key_out[e] = key;

@@ -264,7 +264,7 @@ static void overlap_on_device(wp_vocab *v, Context *c, const RaggedIn &in, const
   if (table) {
     hipLaunchKernelGGL(ovl_keys_kernel, dim3(cdiv(nre, kOvlTile)), dim3(kBlock), 0, st, r32, nre, static_cast<const uint32_t *>(d_rboff), nr, eb, k, pw, mask,
                        d_rkey, d_rvalid, static_cast<const uint64_t *>(nullptr), static_cast<const uint32_t *>(nullptr),
-                       static_cast<const uint32_t *>(nullptr), 0u, size_t(0), static_cast<uint32_t *>(nullptr));
+                       static_cast<const uint32_t *>(nullptr), 0u, size_t(0), static_cast<uint32_t *>(nullptr), 0u);
     device_exclusive_scan(d_rvalid, d_rvpos, nre1, d_itmp, nullptr, st);
     hipLaunchKernelGGL(ovl_list_kernel, count_grid(nre), dim3(kBlock), 0, st, static_cast<const uint64_t *>(d_rkey), static_cast<const uint32_t *>(d_rvalid),
                        static_cast<const uint32_t *>(d_rvpos), nre, m, d_k0, d_v0);
@@ -291,7 +291,7 @@ static void overlap_on_device(wp_vocab *v, Context *c, const RaggedIn &in, const
   if (search) {
     hipLaunchKernelGGL(ovl_keys_kernel, dim3(cdiv(ne, kOvlTile)), dim3(kBlock), 0, st, c32, ne, static_cast<const uint32_t *>(d_boff), n, eb, k, pw, mask,
                        static_cast<uint64_t *>(nullptr), d_flag, static_cast<const uint64_t *>(d_ent_key), static_cast<const uint32_t *>(d_n_ent),
-                       static_cast<const uint32_t *>(d_bucket), shift, n_buckets, d_ent);
+                       static_cast<const uint32_t *>(d_bucket), shift, n_buckets, d_ent, 0u);
     device_exclusive_scan(d_flag, d_scan, ne, d_itmp, c->d_scalars + kScalarOvlCands, st);
     compact_flagged(d_flag, d_scan, ne, nullptr, d_ce, st);
     compact_flagged(d_flag, d_scan, ne, d_ent, d_ct, st);

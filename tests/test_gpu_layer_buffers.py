@@ -1,7 +1,8 @@
 """GPU tests (-m gpu) of the device buffers of the layers on top of the encoder (csrc/rows_path.h, inputs_path.h,
 mask_path.h, detok_path.h, pack_path.h, the pre-pass of csrc/normalize.h, and the grouping layers: count_path.h,
-learn_path.h, dedup_path.h, neardup_path.h over group_path.h) across the calls of one handle.  Every layer
-lays its buffers out with an Arena over a DeviceBuffer that grows when a call needs more than it holds, and two mistakes
+learn_path.h, dedup_path.h, neardup_path.h over group_path.h, overlap_path.h and repeat_path.h over window_path.h) across
+the calls of one handle.  Every layer lays its buffers out with an Arena over a DeviceBuffer that grows when a call needs
+more than it holds, and two mistakes
 show only from one call to the next: a sequence of allocations that differs between the planning pass and the real one,
 and a pointer kept across a regrowth.  So every layer is called small, then large enough to make its buffers grow, then
 small again, all on ONE handle (the per-document route needs a vocabulary of its own, hence a second handle for it alone),
@@ -24,7 +25,9 @@ import learn_model as LM
 import mask_model as MM
 import neardup_model as NDM
 import normalize_model as NM
+import overlap_model as OM
 import pack_model as PM
+import repeat_model as RM
 import rows_model as R
 import wordpiece_amd as W
 
@@ -456,3 +459,70 @@ def test_neardup_rows(gv):
     # elements in neardup_items; the inverse alone in neardup_out
     assert 8 * (N_RAGGED + 1) > GROW and (12 + 4) * 4 * N_RAGGED > GROW and 60 * 2 * n_live > GROW and 4 * N_RAGGED > GROW
     small_then_large(gv, run, _cells(31, 0, 98), large, _cells(8, 4, 99))
+
+
+# ---- the window layers (window_path.h) ----------------------------------------------------------------------------------
+
+
+def _window_equal(got, exp, keys):
+    """the arrays of an overlap or repeat result against the model's; `keys`: what the call was asked for"""
+    assert sorted(got) == sorted(keys)
+    for k in got:
+        if k in ("data", "cut_data"):
+            assert (got[k] if isinstance(got[k], bytes) else got[k].tobytes()) == exp[k], k
+        else:
+            assert got[k].tolist() == exp[k], k
+
+
+@pytest.mark.gpu
+def test_overlap_rows(gv):
+    base = ("hits", "first_hit", "first_ref", "covered")
+
+    def run(case):
+        (data, off), (rdata, roff) = case
+        exp = known.get(id(case)) or OM.overlap_rows(data.tobytes(), off, rdata.tobytes(), roff, data.dtype.itemsize, ngram=3)
+        for want in (True, False):  # (the two layouts of overlap_items, overlap_rows and overlap_out alternate)
+            got = gv.overlap_rows(data, off, rdata, roff, ngram=3, mask=want, ref=want, compact=want, raw=True)
+            _window_equal(got, exp, base + (("mask", "ref_hits", "kept", "data", "row_off") if want else ()))
+            st = gv.overlap_stats()
+            assert {k: st[k] for k in exp["stats"]} == exp["stats"]
+
+    large = (_ragged_rows(N_RAGGED, 95), _ragged_rows(N_RAGGED, 100))
+    exp = OM.overlap_rows(large[0][0].tobytes(), large[0][1], large[1][0].tobytes(), large[1][1], 1, ngram=3)
+    known = {id(large): exp}
+    n_elems, n_ref_elems, n_kept = large[0][0].size, large[1][0].size, len(exp["kept"])
+    assert 0 < n_kept < N_RAGGED and exp["stats"]["n_ref_distinct"] == 64  # (long runs; the kept rows are a real subset)
+    # the data and the offsets in overlap_in and in overlap_ref_in; 13 words per corpus row in overlap_rows; 7 words per
+    # corpus element in overlap_items; the kept rows, their offsets and the room of the input in overlap_out
+    assert n_elems + 8 * (N_RAGGED + 1) > GROW and n_ref_elems + 8 * (N_RAGGED + 1) > GROW and 13 * 4 * N_RAGGED > GROW
+    assert 7 * 4 * n_elems > GROW and 12 * n_kept + n_elems > GROW
+    small31, small8 = _cells(31, 0, 101), _cells(8, 4, 102)
+    small_then_large(gv, run, (small31, small31), large, (small8, small8))
+
+
+@pytest.mark.gpu
+def test_repeat_rows(gv):
+    base = ("repeats", "first_repeat", "first_src_row", "first_src_pos", "covered")
+
+    def text(cells):  # (WP_REPEAT_UTF8 takes text)
+        return (cells[0] % 4 + 97).astype(np.uint8), cells[1]
+
+    def run(case):
+        data, off = case
+        exp = known.get(id(case)) or RM.repeat_rows(data.tobytes(), off, 1, ngram=3, scope=0, utf8=True)
+        for want in (True, False):  # (the two layouts of repeat_items and repeat_out alternate; the wait of utf8 comes and goes)
+            got = gv.repeat_rows(data, off, ngram=3, scope=0, mask=want, src=want, compact=want, cut=want, utf8=want)
+            _window_equal(got, exp, base + (("mask", "src", "kept", "data", "row_off", "cut_data", "cut_off") if want else ()))
+            st = gv.repeat_stats()
+            assert {k: st[k] for k in exp["stats"]} == dict(exp["stats"], n_cut_elems=exp["stats"]["n_cut_elems"] if want else 0)
+
+    large = _ragged_rows(N_RAGGED, 95)  # (ASCII: every window lies between code point boundaries, with the flag and without)
+    exp = RM.repeat_rows(large[0].tobytes(), large[1], 1, ngram=3, scope=0, utf8=True)
+    known = {id(large): exp}
+    n_elems, n_kept = large[0].size, len(exp["kept"])
+    assert 0 < n_kept < N_RAGGED and exp["stats"]["n_distinct"] == 64
+    # the data and the offsets in repeat_in; 14 words per row in repeat_rows; 5 words per element in repeat_items; the
+    # kept rows and the cut, each with its offsets and the room of the input, in repeat_out
+    assert n_elems + 8 * (N_RAGGED + 1) > GROW and 14 * 4 * N_RAGGED > GROW and 5 * 4 * n_elems > GROW
+    assert 12 * n_kept + 8 * (N_RAGGED + 1) + 2 * n_elems > GROW
+    small_then_large(gv, run, text(_cells(31, 0, 103)), large, text(_cells(8, 4, 104)))

@@ -1385,31 +1385,13 @@ class Vocab:
         np.int64 [n_unique]}, with inverse "inverse": np.int32 [n_rows] (first[i] == kept[inverse[i]]), with compact
         "data" and "row_off" of the kept rows back to back.  raw: text data comes back as np.uint8 rather than bytes.
         hash_bits: for tests of the collision rounds."""
-        if isinstance(data, (str, bytes, bytearray, memoryview)):
-            data = np.frombuffer(_bytes(data), dtype=np.uint8)
-        else:
-            data = np.ascontiguousarray(data)
-        if data.dtype not in (np.uint8, np.int32) or data.ndim != 1:
-            raise WordPieceError("dedup: data must be text (bytes, uint8) or a flat int32 array")
-        if row_off is None:
-            if data.dtype != np.uint8:
-                raise WordPieceError("dedup: the lines form takes text")
-            data, row_off = line_rows(data)
-        off = np.ascontiguousarray(row_off, dtype=np.int64)
-        n = off.size - 1
-        if off.ndim != 1 or n < 0:
-            raise WordPieceError("dedup: row_off needs n_rows + 1 entries")
-        if n and off[n] > data.size:  # (the library reads row_off[n_rows] elements of data)
-            raise WordPieceError("dedup: row_off ends behind the data")
+        data, off, n = _ragged_batch("dedup", data, row_off)
         want = (WP_DEDUP_WANT_INVERSE if inverse else 0) | (WP_DEDUP_WANT_COMPACT if compact else 0)
         spec = DedupSpec(data.dtype.itemsize, want, int(hash_bits), 0)
         out = DedupResult()
         _check(lib().wp_dedup_rows(self._h, data.ctypes.data if data.size else None, off.ctypes.data if n else None, n, C.byref(spec),
                                    C.byref(out)))
-
-        def block(ptr, k, dtype):
-            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(np.ctypeslib.as_ctypes_type(dtype))), (k,)).copy() if k and ptr else \
-                np.zeros(0, dtype=dtype)
+        block = _host_block
         try:
             u = out.n_unique
             res = {"first": block(out.first, n, np.int32), "kept": block(out.kept, u, np.int32), "counts": block(out.counts, u, np.int64)}
@@ -1420,9 +1402,7 @@ class Vocab:
                 res["data"] = kept_data if raw or data.dtype != np.uint8 else kept_data.tobytes()
                 res["row_off"] = block(out.row_off, u + 1, np.int64)
         finally:
-            for blk in (out.first, out.kept, out.inverse, out.counts, out.row_off, out.data):
-                if blk:
-                    lib().wp_free(blk)
+            _free_blocks(out.first, out.kept, out.inverse, out.counts, out.row_off, out.data)
         return res
 
     def dedup_rows_tensor(self, data, row_off, inverse=False, compact=False, copy=True, hash_bits=0):
@@ -1434,32 +1414,18 @@ class Vocab:
         import torch
         if data.dtype not in (torch.uint8, torch.int32) or row_off.dtype != torch.int64:
             raise WordPieceError("dedup_rows_tensor needs uint8 or int32 data and int64 row_off")
-        for t in (data, row_off):
-            if not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
-                raise WordPieceError("dedup_rows_tensor needs flat contiguous CUDA/HIP tensors")
-        if self._device is not None and data.device.index != self._device:  # (raw pointers go to the handle's device)
-            raise WordPieceError("the tensors lie on %s, the handle on device %d" % (data.device, self._device))
+        _flat_device_tensors("dedup_rows_tensor", self._device, data, row_off)
         n = row_off.numel() - 1
         if n < 0:
             raise WordPieceError("dedup: row_off needs n_rows + 1 entries")
-        nbytes = data.numel() * data.element_size()
-        if data.dtype == torch.uint8 and (data.data_ptr() % 4 != 0 or nbytes % 4 != 0):  # (the kernels read whole aligned words)
-            padded = torch.zeros((nbytes + 19) // 16 * 16, dtype=torch.uint8, device=data.device)
-            padded[:nbytes] = data
-            data = padded
         want = (WP_DEDUP_WANT_INVERSE if inverse else 0) | (WP_DEDUP_WANT_COMPACT if compact else 0)
         spec = DedupSpec(data.element_size(), want, int(hash_bits), 0)
         dev = data.device
-        torch.cuda.current_stream(dev).synchronize()  # the library runs on its own HIP streams
+        (data, nbytes), = _whole_words(data)
         out = DedupResult()
         _check(lib().wp_dedup_rows_device(self._h, C.c_void_p(data.data_ptr()) if nbytes else None, C.c_void_p(row_off.data_ptr()), n,
                                           C.byref(spec), C.byref(out)))
-
-        def view(ptr, k, typestr, dtype):
-            if not k or not ptr:
-                return torch.zeros(0, dtype=dtype, device=dev)
-            t = torch.as_tensor(DeviceIds(ptr, k, typestr=typestr), device=dev)
-            return t.clone() if copy else t
+        view = _DeviceViews(dev, copy)
         u = out.n_unique
         res = {"first": view(out.first, n, "<i4", torch.int32), "kept": view(out.kept, u, "<i4", torch.int32),
                "counts": view(out.counts, u, "<i8", torch.int64)}
@@ -1500,30 +1466,12 @@ class Vocab:
         [n_unique], "counts": np.int64 [n_unique]}, with inverse "inverse", with compact "data" and "row_off" of the kept
         rows back to back, with signatures "signatures": np.uint32 [n_rows, n_perm].  raw: text data comes back as
         np.uint8 rather than bytes."""
-        if isinstance(data, (str, bytes, bytearray, memoryview)):
-            data = np.frombuffer(_bytes(data), dtype=np.uint8)
-        else:
-            data = np.ascontiguousarray(data)
-        if data.dtype not in (np.uint8, np.int32) or data.ndim != 1:
-            raise WordPieceError("neardup: data must be text (bytes, uint8) or a flat int32 array")
-        if row_off is None:
-            if data.dtype != np.uint8:
-                raise WordPieceError("neardup: the lines form takes text")
-            data, row_off = line_rows(data)
-        off = np.ascontiguousarray(row_off, dtype=np.int64)
-        n = off.size - 1
-        if off.ndim != 1 or n < 0:
-            raise WordPieceError("neardup: row_off needs n_rows + 1 entries")
-        if n and off[n] > data.size:  # (the library reads row_off[n_rows] elements of data)
-            raise WordPieceError("neardup: row_off ends behind the data")
+        data, off, n = _ragged_batch("neardup", data, row_off)
         spec = self._neardup_spec(data.dtype.itemsize, shingle, n_perm, bands, min_agree, seed, inverse, compact, signatures)
         out = NearDupResult()
         _check(lib().wp_neardup_rows(self._h, data.ctypes.data if data.size else None, off.ctypes.data if n else None, n, C.byref(spec),
                                      C.byref(out)))
-
-        def block(ptr, k, dtype):
-            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(np.ctypeslib.as_ctypes_type(dtype))), (k,)).copy() if k and ptr else \
-                np.zeros(0, dtype=dtype)
+        block = _host_block
         try:
             u = out.n_unique
             res = {"cluster": block(out.cluster, n, np.int32), "kept": block(out.kept, u, np.int32), "counts": block(out.counts, u, np.int64)}
@@ -1536,9 +1484,7 @@ class Vocab:
             if signatures:
                 res["signatures"] = block(out.signatures, n * int(n_perm), np.uint32).reshape(n, int(n_perm))
         finally:
-            for blk in (out.cluster, out.kept, out.inverse, out.counts, out.row_off, out.data, out.signatures):
-                if blk:
-                    lib().wp_free(blk)
+            _free_blocks(out.cluster, out.kept, out.inverse, out.counts, out.row_off, out.data, out.signatures)
         return res
 
     def neardup_rows_tensor(self, data, row_off, shingle=5, n_perm=128, bands=16, min_agree=0, seed=0, inverse=False, compact=False,
@@ -1553,31 +1499,17 @@ class Vocab:
         import torch
         if data.dtype not in (torch.uint8, torch.int32) or row_off.dtype != torch.int64:
             raise WordPieceError("neardup_rows_tensor needs uint8 or int32 data and int64 row_off")
-        for t in (data, row_off):
-            if not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
-                raise WordPieceError("neardup_rows_tensor needs flat contiguous CUDA/HIP tensors")
-        if self._device is not None and data.device.index != self._device:  # (raw pointers go to the handle's device)
-            raise WordPieceError("the tensors lie on %s, the handle on device %d" % (data.device, self._device))
+        _flat_device_tensors("neardup_rows_tensor", self._device, data, row_off)
         n = row_off.numel() - 1
         if n < 0:
             raise WordPieceError("neardup: row_off needs n_rows + 1 entries")
-        nbytes = data.numel() * data.element_size()
-        if data.dtype == torch.uint8 and (data.data_ptr() % 4 != 0 or nbytes % 4 != 0):  # (the kernels read whole aligned words)
-            padded = torch.zeros((nbytes + 19) // 16 * 16, dtype=torch.uint8, device=data.device)
-            padded[:nbytes] = data
-            data = padded
         spec = self._neardup_spec(data.element_size(), shingle, n_perm, bands, min_agree, seed, inverse, compact, signatures)
         dev = data.device
-        torch.cuda.current_stream(dev).synchronize()  # the library runs on its own HIP streams
+        (data, nbytes), = _whole_words(data)
         out = NearDupResult()
         _check(lib().wp_neardup_rows_device(self._h, C.c_void_p(data.data_ptr()) if nbytes else None, C.c_void_p(row_off.data_ptr()), n,
                                             C.byref(spec), C.byref(out)))
-
-        def view(ptr, k, typestr, dtype):
-            if not k or not ptr:
-                return torch.zeros(0, dtype=dtype, device=dev)
-            t = torch.as_tensor(DeviceIds(ptr, k, typestr=typestr), device=dev)
-            return t.clone() if copy else t
+        view = _DeviceViews(dev, copy)
         u = out.n_unique
         res = {"cluster": view(out.cluster, n, "<i4", torch.int32), "kept": view(out.kept, u, "<i4", torch.int32),
                "counts": view(out.counts, u, "<i8", torch.int64)}
@@ -1612,24 +1544,8 @@ class Vocab:
 
     @staticmethod
     def _overlap_batch(data, row_off, name):
-        """one batch of a host overlap call -> (flat uint8 / int32 array, int64 offsets, n_rows)"""
-        if isinstance(data, (str, bytes, bytearray, memoryview)):
-            data = np.frombuffer(_bytes(data), dtype=np.uint8)
-        else:
-            data = np.ascontiguousarray(data)
-        if data.dtype not in (np.uint8, np.int32) or data.ndim != 1:
-            raise WordPieceError("overlap: %s must be text (bytes, uint8) or a flat int32 array" % name)
-        if row_off is None:
-            if data.dtype != np.uint8:
-                raise WordPieceError("overlap: the lines form takes text")
-            data, row_off = line_rows(data)
-        off = np.ascontiguousarray(row_off, dtype=np.int64)
-        n = off.size - 1
-        if off.ndim != 1 or n < 0:
-            raise WordPieceError("overlap: the offsets of %s need n_rows + 1 entries" % name)
-        if n and off[n] > data.size:  # (the library reads the last offset's elements of the data)
-            raise WordPieceError("overlap: the offsets of %s end behind the data" % name)
-        return data, off, n
+        """one batch of a host overlap call, and the batch of a repeat call, whose messages read the same"""
+        return _ragged_batch("overlap", data, row_off, name, "the offsets of " + name, "")
 
     def overlap_rows(self, data, row_off, ref_data, ref_off, ngram=13, max_hits=0, mask=False, ref=False, compact=False, hash_bits=0,
                      raw=False):
@@ -1650,10 +1566,7 @@ class Vocab:
         out = OverlapResult()
         _check(lib().wp_overlap_rows(self._h, data.ctypes.data if data.size else None, off.ctypes.data if n else None, n,
                                      rdata.ctypes.data if rdata.size else None, roff.ctypes.data if nr else None, nr, C.byref(spec), C.byref(out)))
-
-        def block(ptr, k, dtype):
-            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(np.ctypeslib.as_ctypes_type(dtype))), (k,)).copy() if k and ptr else \
-                np.zeros(0, dtype=dtype)
+        block = _host_block
         try:
             res = {"hits": block(out.hits, n, np.int64), "first_hit": block(out.first_hit, n, np.int64),
                    "first_ref": block(out.first_ref, n, np.int32), "covered": block(out.covered, n, np.int64)}
@@ -1667,9 +1580,7 @@ class Vocab:
                 res["data"] = kept_data if raw or data.dtype != np.uint8 else kept_data.tobytes()
                 res["row_off"] = block(out.row_off, out.n_kept + 1, np.int64) if n else np.zeros(1, dtype=np.int64)
         finally:
-            for blk in (out.hits, out.first_hit, out.covered, out.ref_hits, out.row_off, out.first_ref, out.kept, out.mask, out.data):
-                if blk:
-                    lib().wp_free(blk)
+            _free_blocks(out.hits, out.first_hit, out.covered, out.ref_hits, out.row_off, out.first_ref, out.kept, out.mask, out.data)
         return res
 
     def overlap_rows_tensor(self, data, row_off, ref_data, ref_off, ngram=13, max_hits=0, mask=False, ref=False, compact=False, copy=True,
@@ -1683,38 +1594,19 @@ class Vocab:
         import torch
         if data.dtype not in (torch.uint8, torch.int32) or ref_data.dtype != data.dtype or row_off.dtype != torch.int64 or ref_off.dtype != torch.int64:
             raise WordPieceError("overlap_rows_tensor needs uint8 or int32 data of one kind and int64 offsets")
-        for t in (data, row_off, ref_data, ref_off):
-            if not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
-                raise WordPieceError("overlap_rows_tensor needs flat contiguous CUDA/HIP tensors")
-            if self._device is not None and t.device.index != self._device:  # (raw pointers go to the handle's device)
-                raise WordPieceError("the tensors lie on %s, the handle on device %d" % (t.device, self._device))
+        _flat_device_tensors("overlap_rows_tensor", self._device, data, row_off, ref_data, ref_off)
         n, nr = row_off.numel() - 1, ref_off.numel() - 1
         if n < 0 or nr < 0:
             raise WordPieceError("overlap: offsets need n_rows + 1 entries")
-
-        def aligned(t):
-            nbytes = t.numel() * t.element_size()
-            if t.dtype == torch.uint8 and (t.data_ptr() % 4 != 0 or nbytes % 4 != 0):  # (the kernels read whole aligned words)
-                padded = torch.zeros((nbytes + 19) // 16 * 16, dtype=torch.uint8, device=t.device)
-                padded[:nbytes] = t
-                return padded, nbytes
-            return t, nbytes
         n_elems = data.numel()
-        data, nbytes = aligned(data)
-        ref_data, ref_nbytes = aligned(ref_data)
         spec = self._overlap_spec(data.element_size(), ngram, max_hits, mask, ref, compact, hash_bits)
         dev = data.device
-        torch.cuda.current_stream(dev).synchronize()  # the library runs on its own HIP streams
+        (data, nbytes), (ref_data, ref_nbytes) = _whole_words(data, ref_data)
         out = OverlapResult()
         _check(lib().wp_overlap_rows_device(self._h, C.c_void_p(data.data_ptr()) if nbytes else None, C.c_void_p(row_off.data_ptr()), n,
                                             C.c_void_p(ref_data.data_ptr()) if ref_nbytes else None, C.c_void_p(ref_off.data_ptr()), nr,
                                             C.byref(spec), C.byref(out)))
-
-        def view(ptr, k, typestr, dtype):
-            if not k or not ptr:
-                return torch.zeros(0, dtype=dtype, device=dev)
-            t = torch.as_tensor(DeviceIds(ptr, k, typestr=typestr), device=dev)
-            return t.clone() if copy else t
+        view = _DeviceViews(dev, copy)
         res = {"hits": view(out.hits, n, "<i8", torch.int64), "first_hit": view(out.first_hit, n, "<i8", torch.int64),
                "first_ref": view(out.first_ref, n, "<i4", torch.int32), "covered": view(out.covered, n, "<i8", torch.int64)}
         if mask:
@@ -1770,10 +1662,7 @@ class Vocab:
         spec = self._repeat_spec(data.dtype.itemsize, ngram, scope, max_repeats, mask, src, compact, cut, utf8, hash_bits)
         out = RepeatResult()
         _check(lib().wp_repeat_rows(self._h, data.ctypes.data if data.size else None, off.ctypes.data if n else None, n, C.byref(spec), C.byref(out)))
-
-        def block(ptr, k, dtype):
-            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(np.ctypeslib.as_ctypes_type(dtype))), (k,)).copy() if k and ptr else \
-                np.zeros(0, dtype=dtype)
+        block = _host_block
 
         def elems(ptr, k):
             a = block(ptr, k, data.dtype)
@@ -1795,10 +1684,8 @@ class Vocab:
                 res["cut_data"] = elems(out.cut_data, out.n_cut_elems)
                 res["cut_off"] = block(out.cut_off, n + 1, np.int64) if n else np.zeros(1, dtype=np.int64)
         finally:
-            for blk in (out.repeats, out.first_repeat, out.first_src_pos, out.covered, out.src, out.row_off, out.cut_off, out.first_src_row, out.kept,
-                        out.mask, out.data, out.cut_data):
-                if blk:
-                    lib().wp_free(blk)
+            _free_blocks(out.repeats, out.first_repeat, out.first_src_pos, out.covered, out.src, out.row_off, out.cut_off, out.first_src_row, out.kept,
+                         out.mask, out.data, out.cut_data)
         return res
 
     def repeat_rows_tensor(self, data, row_off, ngram=50, scope=0, max_repeats=0, mask=False, src=False, compact=False, cut=False, utf8=None,
@@ -1811,32 +1698,18 @@ class Vocab:
         import torch
         if data.dtype not in (torch.uint8, torch.int32) or row_off.dtype != torch.int64:
             raise WordPieceError("repeat_rows_tensor needs uint8 or int32 data and int64 offsets")
-        for t in (data, row_off):
-            if not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
-                raise WordPieceError("repeat_rows_tensor needs flat contiguous CUDA/HIP tensors")
-            if self._device is not None and t.device.index != self._device:  # (raw pointers go to the handle's device)
-                raise WordPieceError("the tensors lie on %s, the handle on device %d" % (t.device, self._device))
+        _flat_device_tensors("repeat_rows_tensor", self._device, data, row_off)
         n = row_off.numel() - 1
         if n < 0:
             raise WordPieceError("repeat: offsets need n_rows + 1 entries")
         n_elems = data.numel()
-        nbytes = n_elems * data.element_size()
-        if data.dtype == torch.uint8 and (data.data_ptr() % 4 != 0 or nbytes % 4 != 0):  # (the kernels read whole aligned words)
-            padded = torch.zeros((nbytes + 19) // 16 * 16, dtype=torch.uint8, device=data.device)
-            padded[:nbytes] = data
-            data = padded
         spec = self._repeat_spec(data.element_size(), ngram, scope, max_repeats, mask, src, compact, cut, utf8, hash_bits)
         dev = data.device
-        torch.cuda.current_stream(dev).synchronize()  # the library runs on its own HIP streams
+        (data, nbytes), = _whole_words(data)
         out = RepeatResult()
         _check(lib().wp_repeat_rows_device(self._h, C.c_void_p(data.data_ptr()) if nbytes else None, C.c_void_p(row_off.data_ptr()), n,
                                            C.byref(spec), C.byref(out)))
-
-        def view(ptr, k, typestr, dtype):
-            if not k or not ptr:
-                return torch.zeros(0, dtype=dtype, device=dev)
-            t = torch.as_tensor(DeviceIds(ptr, k, typestr=typestr), device=dev)
-            return t.clone() if copy else t
+        view = _DeviceViews(dev, copy)
         etype = "|u1" if data.dtype == torch.uint8 else "<i4"
         res = {"repeats": view(out.repeats, n, "<i8", torch.int64), "first_repeat": view(out.first_repeat, n, "<i8", torch.int64),
                "first_src_row": view(out.first_src_row, n, "<i4", torch.int32), "first_src_pos": view(out.first_src_pos, n, "<i8", torch.int64),
@@ -2303,6 +2176,81 @@ def line_rows(text):
         t = np.concatenate((t, np.array([10], dtype=np.uint8)))
     ends = np.flatnonzero(t == 10).astype(np.int64) + 1
     return t, np.concatenate((np.zeros(1, dtype=np.int64), ends))
+
+
+# ---- what the wrappers of the ragged-batch layers share (dedup, neardup, overlap, repeat; host and tensor forms) ------
+def _ragged_batch(prefix, data, row_off, name="data", offsets="row_off", s="s"):
+    """One batch of a host call -> (flat uint8 / int32 array, int64 offsets, n_rows).  name, offsets, s: what the layer's
+    messages call the data and the offsets, and the ending of the verb behind the latter."""
+    if isinstance(data, (str, bytes, bytearray, memoryview)):
+        data = np.frombuffer(_bytes(data), dtype=np.uint8)
+    else:
+        data = np.ascontiguousarray(data)
+    if data.dtype not in (np.uint8, np.int32) or data.ndim != 1:
+        raise WordPieceError("%s: %s must be text (bytes, uint8) or a flat int32 array" % (prefix, name))
+    if row_off is None:
+        if data.dtype != np.uint8:
+            raise WordPieceError("%s: the lines form takes text" % prefix)
+        data, row_off = line_rows(data)
+    off = np.ascontiguousarray(row_off, dtype=np.int64)
+    n = off.size - 1
+    if off.ndim != 1 or n < 0:
+        raise WordPieceError("%s: %s need%s n_rows + 1 entries" % (prefix, offsets, s))
+    if n and off[n] > data.size:  # (the library reads the last offset's elements of the data)
+        raise WordPieceError("%s: %s end%s behind the data" % (prefix, offsets, s))
+    return data, off, n
+
+
+def _host_block(ptr, k, dtype):
+    """a copy of the k elements of a block the library returned (NULL or k == 0: an empty array)"""
+    if not k or not ptr:
+        return np.zeros(0, dtype=dtype)
+    return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(np.ctypeslib.as_ctypes_type(dtype))), (k,)).copy()
+
+
+def _free_blocks(*blocks):
+    for blk in blocks:
+        if blk:
+            lib().wp_free(blk)
+
+
+def _flat_device_tensors(fn, device, *tensors):
+    """the tensors of a device call: flat, contiguous, on the handle's device (raw pointers go there)"""
+    for t in tensors:
+        if not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
+            raise WordPieceError("%s needs flat contiguous CUDA/HIP tensors" % fn)
+        if device is not None and t.device.index != device:
+            raise WordPieceError("the tensors lie on %s, the handle on device %d" % (t.device, device))
+
+
+def _whole_words(*tensors):
+    """The data tensors of a device call where the kernels can read whole aligned words -> [(the tensor, or a padded copy
+    of uint8 data that is not such, its bytes)]; then waits for torch's stream: the library runs on its own HIP streams."""
+    import torch
+    out = []
+    for t in tensors:
+        nbytes = t.numel() * t.element_size()
+        if t.dtype == torch.uint8 and (t.data_ptr() % 4 != 0 or nbytes % 4 != 0):
+            padded = torch.zeros((nbytes + 19) // 16 * 16, dtype=torch.uint8, device=t.device)
+            padded[:nbytes] = t
+            t = padded
+        out.append((t, nbytes))
+    torch.cuda.current_stream(tensors[0].device).synchronize()
+    return out
+
+
+class _DeviceViews:
+    """the arrays of a device result as tensors on dev: clones, or with copy=False views of the library's buffers"""
+
+    def __init__(self, dev, copy):
+        self.dev, self.copy = dev, copy
+
+    def __call__(self, ptr, k, typestr, dtype):
+        import torch
+        if not k or not ptr:
+            return torch.zeros(0, dtype=dtype, device=self.dev)
+        t = torch.as_tensor(DeviceIds(ptr, k, typestr=typestr), device=self.dev)
+        return t.clone() if self.copy else t
 
 
 def join_spans(spans):

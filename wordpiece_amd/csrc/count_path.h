@@ -25,14 +25,14 @@ static CountPlan check_count_spec(const wp_count_spec *spec, const wp_word_count
     throw std::invalid_argument("count: max_word_bytes must be 0 (256) or in [1, 1024]");
   }
   if (spec->terminator < -1 || spec->terminator > 255) throw std::invalid_argument("count: terminator must be in [-1, 255]");
-  if ((spec->want & ~WP_COUNT_WANT_INDEX) != 0) throw std::invalid_argument("count: want has bits outside 1");
-  if (spec->hash_bits != 0 && (spec->hash_bits < 8 || spec->hash_bits > 64)) throw std::invalid_argument("count: hash_bits must be 0 (64) or in [8, 64]");
+  check_want("count", spec->want, WP_COUNT_WANT_INDEX);
+  const int hash_bits = checked_hash_bits("count", spec->hash_bits);
   if (spec->reserved != 0) throw std::invalid_argument("count: reserved must be 0");
   if (spec->min_count < 0) throw std::invalid_argument("count: min_count must not be negative");
   CountPlan p;
   p.order = spec->order;
   p.terminator = spec->terminator;
-  p.hash_bits = spec->hash_bits == 0 ? 64 : spec->hash_bits;
+  p.hash_bits = hash_bits;
   p.max_bytes = spec->max_word_bytes == 0 ? 256u : static_cast<uint32_t>(spec->max_word_bytes);
   p.want_index = (spec->want & WP_COUNT_WANT_INDEX) != 0;
   p.min_count = spec->min_count == 0 ? 1ull : static_cast<unsigned long long>(spec->min_count);

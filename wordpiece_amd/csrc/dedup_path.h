@@ -18,20 +18,16 @@ struct DedupPlan {
 static DedupPlan check_dedup_spec(const wp_dedup_spec *spec, const wp_dedup_result *out) {
   if (!spec) throw std::invalid_argument("dedup: spec is NULL");
   if (!out) throw std::invalid_argument("dedup: out is NULL");
-  if (spec->elem_bytes != 1 && spec->elem_bytes != 4) throw std::invalid_argument("dedup: elem_bytes must be 1 or 4");
-  if ((spec->want & ~(WP_DEDUP_WANT_INVERSE | WP_DEDUP_WANT_COMPACT)) != 0) throw std::invalid_argument("dedup: want has bits outside 3");
-  if (spec->hash_bits != 0 && (spec->hash_bits < 8 || spec->hash_bits > 64)) throw std::invalid_argument("dedup: hash_bits must be 0 (64) or in [8, 64]");
+  check_elem_bytes("dedup", spec->elem_bytes);
+  check_want("dedup", spec->want, WP_DEDUP_WANT_INVERSE | WP_DEDUP_WANT_COMPACT);
+  const int hash_bits = checked_hash_bits("dedup", spec->hash_bits);
   if (spec->reserved != 0) throw std::invalid_argument("dedup: reserved must be 0");
   DedupPlan p;
   p.elem_bytes = static_cast<uint32_t>(spec->elem_bytes);
-  p.hash_bits = spec->hash_bits == 0 ? 64 : spec->hash_bits;
+  p.hash_bits = hash_bits;
   p.want_inverse = (spec->want & WP_DEDUP_WANT_INVERSE) != 0;
   p.want_compact = (spec->want & WP_DEDUP_WANT_COMPACT) != 0;
   return p;
-}
-
-static void check_dedup_rows(size_t n_rows) {
-  if (n_rows >= (size_t(1) << 31)) throw std::length_error("dedup: 2^31 rows or more");
 }
 
 // the statistics of a dedup call before anything is known of its rows

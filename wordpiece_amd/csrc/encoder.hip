@@ -385,6 +385,14 @@ class Downloads {
     items.emplace_back(id_pool().take(bytes), out);
     WP_HIP(hipMemcpyAsync(items.back().first, d_src, bytes, hipMemcpyDeviceToHost, st));
   }
+  // a field of a result copied from the device's: the device range it names is queued and the field cleared until
+  // finish(); a field that is NULL stays NULL
+  template <typename T>
+  void swap(T **field, size_t bytes) {
+    const void *d_src = *field;
+    *field = nullptr;
+    if (d_src) add(field, d_src, bytes);
+  }
   void finish() {
     WP_HIP(hipStreamSynchronize(st));
     for (auto &it : items) std::memcpy(it.second, &it.first, sizeof(void *));  // (*out = block, for every T * alike)
@@ -392,17 +400,27 @@ class Downloads {
   }
 };
 
-// the five fields that the results of dedup and neardup share: h's pointers cleared, d's ranges queued
+// the compact form in a result h copied from the device's: n_kept rows (kept: their indices, where the result lists them)
 template <typename Result>
-void add_table_downloads(Downloads &down, Result &h, const Result &d, uint32_t elem_bytes) {
-  h.kept = h.inverse = nullptr;
-  h.counts = h.row_off = nullptr;
-  h.data = nullptr;
-  down.add(&h.kept, d.kept, static_cast<size_t>(d.n_unique) * sizeof(int32_t));
-  down.add(&h.counts, d.counts, static_cast<size_t>(d.n_unique) * sizeof(int64_t));
-  if (d.inverse) down.add(&h.inverse, d.inverse, static_cast<size_t>(d.n_rows) * sizeof(int32_t));
-  if (d.row_off) down.add(&h.row_off, d.row_off, static_cast<size_t>(d.n_unique + 1) * sizeof(int64_t));
-  if (d.data) down.add(&h.data, d.data, static_cast<size_t>(d.n_elems) * elem_bytes);
+void swap_compact(Downloads &down, Result &h, int64_t n_kept, uint32_t elem_bytes) {
+  down.swap(&h.kept, static_cast<size_t>(n_kept) * sizeof(int32_t));
+  down.swap(&h.row_off, static_cast<size_t>(n_kept + 1) * sizeof(int64_t));
+  down.swap(&h.data, static_cast<size_t>(h.n_elems) * elem_bytes);
+}
+// the five fields that the results of dedup and neardup share
+template <typename Result>
+void swap_table(Downloads &down, Result &h, uint32_t elem_bytes) {
+  down.swap(&h.counts, static_cast<size_t>(h.n_unique) * sizeof(int64_t));
+  down.swap(&h.inverse, static_cast<size_t>(h.n_rows) * sizeof(int32_t));
+  swap_compact(down, h, h.n_unique, elem_bytes);
+}
+
+// the batch of a device call: the alignment its arrays need, under the names a message calls them
+RaggedIn device_batch(const char *layer, const void *d_data, const int64_t *d_row_off, size_t n_rows, uint32_t elem_bytes, const char *off_name = "row_off",
+                      const char *data_name = "data") {
+  if ((reinterpret_cast<uintptr_t>(d_row_off) & 7) != 0) throw std::invalid_argument(std::string(layer) + ": " + off_name + " must be 8-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(d_data) & 3) != 0) throw std::invalid_argument(std::string(layer) + ": " + data_name + " must be 4-byte aligned");
+  return RaggedIn{d_data, reinterpret_cast<const long long *>(d_row_off), n_rows, elem_bytes};
 }
 
 using wp_clock = std::chrono::steady_clock;
@@ -1438,7 +1456,7 @@ int wp_dedup_rows(wp_vocab *v, const void *data, const int64_t *row_off, size_t 
     if (out) *out = wp_dedup_result{};
     const DedupPlan plan = check_dedup_spec(spec, out);
     if (n_rows != 0 && !row_off) throw std::invalid_argument("dedup: row_off is NULL");
-    check_dedup_rows(n_rows);
+    check_row_count("dedup", n_rows);
     const unsigned long long n_elems = check_ragged_host("dedup", data, row_off, n_rows, plan.elem_bytes);
     if (n_elems == 0) {
       *out = dedup_all_empty(v, n_rows, plan);
@@ -1449,10 +1467,9 @@ int wp_dedup_rows(wp_vocab *v, const void *data, const int64_t *row_off, size_t 
     wp_dedup_result d;
     dedup_on_device(v, c, in, plan, &d);
     wp_dedup_result h = d;
-    h.first = nullptr;
     Downloads down(c->stream);
-    down.add(&h.first, d.first, n_rows * sizeof(int32_t));
-    add_table_downloads(down, h, d, plan.elem_bytes);
+    down.swap(&h.first, n_rows * sizeof(int32_t));
+    swap_table(down, h, plan.elem_bytes);
     down.finish();
     *out = h;
   });
@@ -1464,14 +1481,13 @@ int wp_dedup_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row_o
     if (d_out) *d_out = wp_dedup_result{};
     const DedupPlan plan = check_dedup_spec(spec, d_out);
     if (n_rows != 0 && !d_row_off) throw std::invalid_argument("dedup: row_off is NULL");
-    check_dedup_rows(n_rows);
-    check_aligned(d_row_off, 8, "dedup: row_off must be 8-byte aligned");
-    check_aligned(d_data, 4, "dedup: data must be 4-byte aligned");
+    check_row_count("dedup", n_rows);
+    const RaggedIn in = device_batch("dedup", d_data, d_row_off, n_rows, plan.elem_bytes);
     if (n_rows == 0) {  // (nothing to read and nothing to hand out: every pointer of the result stays NULL)
       begin_dedup_stats(v, 0);
       return;
     }
-    dedup_on_device(v, get_context(v), RaggedIn{d_data, reinterpret_cast<const long long *>(d_row_off), n_rows, plan.elem_bytes}, plan, d_out);
+    dedup_on_device(v, get_context(v), in, plan, d_out);
   });
 }
 
@@ -1502,12 +1518,10 @@ int wp_neardup_rows(wp_vocab *v, const void *data, const int64_t *row_off, size_
     wp_neardup_result d;
     neardup_on_device(v, c, in, plan, &d);
     wp_neardup_result h = d;
-    h.cluster = nullptr;
-    h.signatures = nullptr;
     Downloads down(c->stream);
-    down.add(&h.cluster, d.cluster, n_rows * sizeof(int32_t));
-    add_table_downloads(down, h, d, plan.elem_bytes);
-    if (d.signatures) down.add(&h.signatures, d.signatures, n_rows * plan.n_perm * sizeof(uint32_t));
+    down.swap(&h.cluster, n_rows * sizeof(int32_t));
+    swap_table(down, h, plan.elem_bytes);
+    down.swap(&h.signatures, n_rows * plan.n_perm * sizeof(uint32_t));
     down.finish();
     *out = h;
   });
@@ -1520,13 +1534,12 @@ int wp_neardup_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row
     const NearDupPlan plan = check_neardup_spec(spec, d_out);
     if (n_rows != 0 && !d_row_off) throw std::invalid_argument("neardup: row_off is NULL");
     check_neardup_rows(n_rows, plan);
-    check_aligned(d_row_off, 8, "neardup: row_off must be 8-byte aligned");
-    check_aligned(d_data, 4, "neardup: data must be 4-byte aligned");
+    const RaggedIn in = device_batch("neardup", d_data, d_row_off, n_rows, plan.elem_bytes);
     if (n_rows == 0) {  // (nothing to read and nothing to hand out: every pointer of the result stays NULL)
       begin_neardup_stats(v, 0);
       return;
     }
-    neardup_on_device(v, get_context(v), RaggedIn{d_data, reinterpret_cast<const long long *>(d_row_off), n_rows, plan.elem_bytes}, plan, d_out);
+    neardup_on_device(v, get_context(v), in, plan, d_out);
   });
 }
 
@@ -1566,20 +1579,14 @@ int wp_overlap_rows(wp_vocab *v, const void *data, const int64_t *row_off, size_
     wp_overlap_result d;
     overlap_on_device(v, c, in, ref, plan, &d);
     wp_overlap_result h = d;
-    h.hits = h.first_hit = h.covered = h.ref_hits = h.row_off = nullptr;
-    h.first_ref = h.kept = nullptr;
-    h.mask = nullptr;
-    h.data = nullptr;
     Downloads down(c->stream);
-    down.add(&h.hits, d.hits, n_rows * sizeof(int64_t));
-    down.add(&h.first_hit, d.first_hit, n_rows * sizeof(int64_t));
-    down.add(&h.covered, d.covered, n_rows * sizeof(int64_t));
-    down.add(&h.first_ref, d.first_ref, n_rows * sizeof(int32_t));
-    if (d.mask) down.add(&h.mask, d.mask, static_cast<size_t>(n_elems));
-    if (d.ref_hits) down.add(&h.ref_hits, d.ref_hits, n_ref * sizeof(int64_t));
-    if (d.kept) down.add(&h.kept, d.kept, static_cast<size_t>(d.n_kept) * sizeof(int32_t));
-    if (d.row_off) down.add(&h.row_off, d.row_off, static_cast<size_t>(d.n_kept + 1) * sizeof(int64_t));
-    if (d.data) down.add(&h.data, d.data, static_cast<size_t>(d.n_elems) * eb);
+    down.swap(&h.hits, n_rows * sizeof(int64_t));
+    down.swap(&h.first_hit, n_rows * sizeof(int64_t));
+    down.swap(&h.covered, n_rows * sizeof(int64_t));
+    down.swap(&h.first_ref, n_rows * sizeof(int32_t));
+    down.swap(&h.mask, static_cast<size_t>(n_elems));
+    down.swap(&h.ref_hits, n_ref * sizeof(int64_t));
+    swap_compact(down, h, h.n_kept, eb);
     down.finish();
     *out = h;
   });
@@ -1591,17 +1598,14 @@ int wp_overlap_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row
     if (d_out) *d_out = wp_overlap_result{};
     const OverlapPlan plan = check_overlap_spec(spec, d_out);
     check_overlap_rows(d_row_off, n_rows, d_ref_off, n_ref);
-    check_aligned(d_row_off, 8, "overlap: row_off must be 8-byte aligned");
-    check_aligned(d_ref_off, 8, "overlap: ref_off must be 8-byte aligned");
-    check_aligned(d_data, 4, "overlap: data must be 4-byte aligned");
-    check_aligned(d_ref_data, 4, "overlap: ref_data must be 4-byte aligned");
+    const RaggedIn in = device_batch("overlap", d_data, d_row_off, n_rows, plan.elem_bytes);
+    const RaggedIn ref = device_batch("overlap", d_ref_data, d_ref_off, n_ref, plan.elem_bytes, "ref_off", "ref_data");
     if (n_rows == 0) {  // (nothing to read and nothing to hand out: every pointer of the result stays NULL)
       begin_overlap_stats(v, 0, n_ref);
       d_out->n_ref = static_cast<int64_t>(n_ref);
       return;
     }
-    overlap_on_device(v, get_context(v), RaggedIn{d_data, reinterpret_cast<const long long *>(d_row_off), n_rows, plan.elem_bytes},
-                      RaggedIn{d_ref_data, reinterpret_cast<const long long *>(d_ref_off), n_ref, plan.elem_bytes}, plan, d_out);
+    overlap_on_device(v, get_context(v), in, ref, plan, d_out);
   });
 }
 
@@ -1636,23 +1640,17 @@ int wp_repeat_rows(wp_vocab *v, const void *data, const int64_t *row_off, size_t
     wp_repeat_result d;
     repeat_on_device(v, c, in, plan, &d);
     wp_repeat_result h = d;
-    h.repeats = h.first_repeat = h.first_src_pos = h.covered = h.src = h.row_off = h.cut_off = nullptr;
-    h.first_src_row = h.kept = nullptr;
-    h.mask = nullptr;
-    h.data = h.cut_data = nullptr;
     Downloads down(c->stream);
-    down.add(&h.repeats, d.repeats, n_rows * sizeof(int64_t));
-    down.add(&h.first_repeat, d.first_repeat, n_rows * sizeof(int64_t));
-    down.add(&h.first_src_pos, d.first_src_pos, n_rows * sizeof(int64_t));
-    down.add(&h.covered, d.covered, n_rows * sizeof(int64_t));
-    down.add(&h.first_src_row, d.first_src_row, n_rows * sizeof(int32_t));
-    if (d.mask) down.add(&h.mask, d.mask, static_cast<size_t>(n_elems));
-    if (d.src) down.add(&h.src, d.src, static_cast<size_t>(n_elems) * sizeof(int64_t));
-    if (d.kept) down.add(&h.kept, d.kept, static_cast<size_t>(d.n_kept) * sizeof(int32_t));
-    if (d.row_off) down.add(&h.row_off, d.row_off, static_cast<size_t>(d.n_kept + 1) * sizeof(int64_t));
-    if (d.data) down.add(&h.data, d.data, static_cast<size_t>(d.n_elems) * eb);
-    if (d.cut_off) down.add(&h.cut_off, d.cut_off, (n_rows + 1) * sizeof(int64_t));
-    if (d.cut_data) down.add(&h.cut_data, d.cut_data, static_cast<size_t>(d.n_cut_elems) * eb);
+    down.swap(&h.repeats, n_rows * sizeof(int64_t));
+    down.swap(&h.first_repeat, n_rows * sizeof(int64_t));
+    down.swap(&h.first_src_pos, n_rows * sizeof(int64_t));
+    down.swap(&h.covered, n_rows * sizeof(int64_t));
+    down.swap(&h.first_src_row, n_rows * sizeof(int32_t));
+    down.swap(&h.mask, static_cast<size_t>(n_elems));
+    down.swap(&h.src, static_cast<size_t>(n_elems) * sizeof(int64_t));
+    swap_compact(down, h, h.n_kept, eb);
+    down.swap(&h.cut_off, (n_rows + 1) * sizeof(int64_t));
+    down.swap(&h.cut_data, static_cast<size_t>(h.n_cut_elems) * eb);
     down.finish();
     *out = h;
   });
@@ -1663,13 +1661,12 @@ int wp_repeat_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row_
     if (d_out) *d_out = wp_repeat_result{};
     const RepeatPlan plan = check_repeat_spec(spec, d_out);
     check_repeat_rows(d_row_off, n_rows);
-    check_aligned(d_row_off, 8, "repeat: row_off must be 8-byte aligned");
-    check_aligned(d_data, 4, "repeat: data must be 4-byte aligned");
+    const RaggedIn in = device_batch("repeat", d_data, d_row_off, n_rows, plan.elem_bytes);
     if (n_rows == 0) {  // (nothing to read and nothing to hand out: every pointer of the result stays NULL)
       begin_repeat_stats(v, 0);
       return;
     }
-    repeat_on_device(v, get_context(v), RaggedIn{d_data, reinterpret_cast<const long long *>(d_row_off), n_rows, plan.elem_bytes}, plan, d_out);
+    repeat_on_device(v, get_context(v), in, plan, d_out);
   });
 }
 

@@ -1,7 +1,8 @@
 // group_path.h — what the layers that group items by a 64-bit key share on a context (word counts: count_path.h, the
-// vocabulary learner: learn_path.h, duplicate rows: dedup_path.h, near-duplicate rows: neardup_path.h, n-gram overlap: overlap_path.h; kernels: count.h,
-// and dedup.h for the table): the launch grid, the arena-guard check, the stage timing of a call, the run heads of a
-// sorted key list, the end of a collision round, a ragged batch on the device and the table with its compact form.
+// vocabulary learner: learn_path.h, duplicate rows: dedup_path.h, near-duplicate rows: neardup_path.h, and through
+// window_path.h n-gram overlap: overlap_path.h and repeated spans: repeat_path.h; kernels: count.h, and dedup.h for the
+// table): the spec rules with one wording, the launch grid, the arena-guard check, the stage timing of a call, the run heads of
+// a sorted key list, the end of a collision round, a ragged batch on the device, the compact form and the table in front of it.
 #pragma once
 #include "context.h"
 #include "count.h"
@@ -10,6 +11,23 @@
 namespace wp {
 
 static dim3 count_grid(size_t n) { return dim3(std::max(1u, cdiv(n, kBlock))); }
+
+// ---- the rules of a spec that read the same in every layer, under the layer's prefix -----------------------------------
+// known: the WANT bits of the layer, 2^b - 1; checked_hash_bits returns the bits of a key, 64 for 0; where: what follows
+// "2^31 rows or more" in the layer's message ("", or " in " and the name of the offsets)
+static void check_elem_bytes(const char *layer, int elem_bytes) {
+  if (elem_bytes != 1 && elem_bytes != 4) throw std::invalid_argument(std::string(layer) + ": elem_bytes must be 1 or 4");
+}
+static void check_want(const char *layer, int want, int known) {
+  if ((want & ~known) != 0) throw std::invalid_argument(std::string(layer) + ": want has bits outside " + std::to_string(known));
+}
+static int checked_hash_bits(const char *layer, int hash_bits) {
+  if (hash_bits != 0 && (hash_bits < 8 || hash_bits > 64)) throw std::invalid_argument(std::string(layer) + ": hash_bits must be 0 (64) or in [8, 64]");
+  return hash_bits == 0 ? 64 : hash_bits;
+}
+static void check_row_count(const char *layer, size_t n_rows, const char *where = "") {
+  if (n_rows >= (size_t(1) << 31)) throw std::length_error(std::string(layer) + ": 2^31 rows or more" + where);
+}
 
 // the guard zones of one arena of the call, checked behind the kernels that wrote into it
 static void check_arena_guard(Context *c, const Arena &a, hipStream_t st, const char *layer) {
@@ -51,6 +69,16 @@ static float mark_ms(Context *c, int from, int to) {
   float ms = 0;
   WP_HIP(hipEventElapsedTime(&ms, c->ev[from], c->ev[to]));
   return ms;
+}
+// the end of a call with all five marks: four stage times in the fields an encode times itself in (what each holds: the layer's section of the header)
+static void end_four_stage_timing(wp_vocab *v, Context *c) {
+  v->stats.ms_normalize = 0;
+  v->stats.ms_decode = mark_ms(c, kMarkStart, kMarkCounted);
+  v->stats.ms_sa = mark_ms(c, kMarkCounted, kMarkSorted);
+  v->stats.ms_scan = mark_ms(c, kMarkSorted, kMarkScanned);
+  v->stats.ms_walk = mark_ms(c, kMarkScanned, kMarkWalked);
+  v->stats.ms_total = v->stats.ms_decode + v->stats.ms_sa + v->stats.ms_scan + v->stats.ms_walk;
+  end_stage_timing(v, c);
 }
 
 // ---- the round protocol ----------------------------------------------------------------------------------
@@ -147,7 +175,24 @@ static size_t check_ragged_device(const char *layer, const RaggedIn &in, uint32_
   return static_cast<size_t>(n_elems) * in.elem_bytes;
 }
 
-// ---- the table and the compact form ----------------------------------------------------------------------
+// ---- the compact form ------------------------------------------------------------------------------------
+// The n_kept rows d_kept of `in`, ascending, back to back.  d_out_len: their lengths in bytes and a 0 behind them;
+// d_out_pos: room for the scan of the lengths; d_boff: the byte offsets of the rows of `in`.  Queues the offsets of the
+// compact form (d_out_off, in elements), its rows (d_out, room: the n_bytes of the input) and the copy of its size in
+// bytes into slot_out_bytes.  No wait: the caller's last one brings that slot.
+static void compact_rows(Context *c, const RaggedIn &in, const uint32_t *d_boff, const int32_t *d_kept, size_t n_kept, size_t n_bytes, uint32_t *d_out_len,
+                         uint32_t *d_out_pos, uint32_t *d_stmp, long long *d_out_off, uint32_t *d_out, int slot_out_bytes, hipStream_t st) {
+  device_exclusive_scan(d_out_len, d_out_pos, n_kept + 1, d_stmp, nullptr, st);
+  hipLaunchKernelGGL(dedup_out_off_kernel, count_grid(n_kept + 1), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_out_pos), n_kept, in.elem_bytes, d_out_off);
+  if (n_bytes != 0 && n_kept != 0) {
+    hipLaunchKernelGGL(dedup_gather_kernel, count_grid((n_bytes + 3) / 4), dim3(kBlock), 0, st, static_cast<const uint8_t *>(in.d_data), n_bytes, d_boff, d_kept,
+                       static_cast<const uint32_t *>(d_out_pos), n_kept, in.n_rows, n_bytes, d_out);
+  }
+  // (the size of the compact form: the last entry of its offsets)
+  WP_HIP(hipMemcpyAsync(c->d_scalars + slot_out_bytes, d_out_pos + n_kept, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+}
+
+// ---- the table in front of it ------------------------------------------------------------------------------------------
 // device pointers into the output buffer of the call, with the arena that laid them out (for the caller's guard check)
 struct GroupTable {
   Arena oa;
@@ -170,8 +215,8 @@ struct GroupTable {
 
 // d_rep[i]: the representative of row i (itself where the row is kept); d_keep_pos: the scan of the kept flags;
 // d_rcount: the rows each kept row stands for; d_boff: the byte offsets of the rows of `in`.  Lays `out` out, queues the
-// table, with want_compact the kept rows back to back (room: the n_bytes of the input) and the copy of their size into
-// slot_out_bytes.  No wait: the caller's last one brings that slot.  d_out_len, d_out_pos: n_rows + 1 words of scratch.
+// table and with want_compact compact_rows over the n_unique >= 1 kept rows.  No wait.  d_out_len, d_out_pos: n_rows + 1
+// words of scratch.
 static GroupTable group_table(Context *c, const RaggedIn &in, const int32_t *d_rep, const uint32_t *d_keep_pos, const uint32_t *d_rcount, const uint32_t *d_boff,
                               size_t n_unique, size_t n_bytes, bool want_inverse, bool want_compact, DeviceBuffer *out, bool guard, uint32_t *d_out_len,
                               uint32_t *d_out_pos, uint32_t *d_stmp, int slot_out_bytes, hipStream_t st) {
@@ -190,17 +235,7 @@ static GroupTable group_table(Context *c, const RaggedIn &in, const int32_t *d_r
   t.oa.arm(st);
   hipLaunchKernelGGL(dedup_table_kernel, count_grid(n), dim3(kBlock), 0, st, d_rep, d_keep_pos, d_rcount, d_boff, n, n_unique, t.d_kept, t.d_counts,
                      t.d_inverse, want_compact ? d_out_len : static_cast<uint32_t *>(nullptr));
-  if (want_compact) {
-    device_exclusive_scan(d_out_len, d_out_pos, n_unique + 1, d_stmp, nullptr, st);
-    hipLaunchKernelGGL(dedup_out_off_kernel, count_grid(n_unique + 1), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_out_pos), n_unique,
-                       in.elem_bytes, t.d_out_off);
-    if (n_bytes != 0) {
-      hipLaunchKernelGGL(dedup_gather_kernel, count_grid((n_bytes + 3) / 4), dim3(kBlock), 0, st, static_cast<const uint8_t *>(in.d_data), n_bytes, d_boff,
-                         static_cast<const int32_t *>(t.d_kept), static_cast<const uint32_t *>(d_out_pos), n_unique, n, n_bytes, t.d_out);
-    }
-    // (the size of the compact form: the last entry of its offsets)
-    WP_HIP(hipMemcpyAsync(c->d_scalars + slot_out_bytes, d_out_pos + n_unique, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-  }
+  if (want_compact) compact_rows(c, in, d_boff, t.d_kept, n_unique, n_bytes, d_out_len, d_out_pos, d_stmp, t.d_out_off, t.d_out, slot_out_bytes, st);
   return t;
 }
 

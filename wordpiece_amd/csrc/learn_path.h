@@ -32,7 +32,7 @@ static LearnPlan check_learn_spec(const wp_learn_spec *spec, const wp_learned_vo
   if (spec->slack < 0) throw std::invalid_argument("learn: slack must not be negative");
   if (spec->max_unique_chars < 0) throw std::invalid_argument("learn: max_unique_chars must not be negative");
   if (spec->terminator < -1 || spec->terminator > 255) throw std::invalid_argument("learn: terminator must be in [-1, 255]");
-  if (spec->hash_bits != 0 && (spec->hash_bits < 8 || spec->hash_bits > 64)) throw std::invalid_argument("learn: hash_bits must be 0 (64) or in [8, 64]");
+  const int hash_bits = checked_hash_bits("learn", spec->hash_bits);
   if (spec->reserved != 0) throw std::invalid_argument("learn: reserved must be 0");
   if (spec->n_reserved < 0 || spec->n_reserved > (1 << 20)) throw std::invalid_argument("learn: n_reserved must be in [0, 2^20]");
   if (spec->n_reserved != 0 && (!spec->reserved_tokens || !spec->reserved_off)) throw std::invalid_argument("learn: reserved_tokens or reserved_off is NULL");
@@ -55,7 +55,7 @@ static LearnPlan check_learn_spec(const wp_learn_spec *spec, const wp_learned_vo
   p.max_chars = spec->max_token_chars;
   p.max_unique = spec->max_unique_chars;
   p.terminator = spec->terminator;
-  p.hash_bits = spec->hash_bits == 0 ? 64 : spec->hash_bits;
+  p.hash_bits = hash_bits;
   return p;
 }
 

@@ -23,10 +23,8 @@ struct NearDupPlan {
 static NearDupPlan check_neardup_spec(const wp_neardup_spec *spec, const wp_neardup_result *out) {
   if (!spec) throw std::invalid_argument("neardup: spec is NULL");
   if (!out) throw std::invalid_argument("neardup: out is NULL");
-  if (spec->elem_bytes != 1 && spec->elem_bytes != 4) throw std::invalid_argument("neardup: elem_bytes must be 1 or 4");
-  if ((spec->want & ~(WP_NEARDUP_WANT_INVERSE | WP_NEARDUP_WANT_COMPACT | WP_NEARDUP_WANT_SIGNATURES)) != 0) {
-    throw std::invalid_argument("neardup: want has bits outside 7");
-  }
+  check_elem_bytes("neardup", spec->elem_bytes);
+  check_want("neardup", spec->want, WP_NEARDUP_WANT_INVERSE | WP_NEARDUP_WANT_COMPACT | WP_NEARDUP_WANT_SIGNATURES);
   if (spec->shingle < 1 || spec->shingle > kNearMaxShingle) throw std::invalid_argument("neardup: shingle must be in [1, 64]");
   if (spec->n_perm < 1 || spec->n_perm > kNearMaxPerm) throw std::invalid_argument("neardup: n_perm must be in [1, 256]");
   if (spec->bands < 1 || spec->n_perm % spec->bands != 0) throw std::invalid_argument("neardup: bands must be at least 1 and divide n_perm");
@@ -46,7 +44,7 @@ static NearDupPlan check_neardup_spec(const wp_neardup_spec *spec, const wp_near
 }
 
 static void check_neardup_rows(size_t n_rows, const NearDupPlan &plan) {
-  if (n_rows >= (size_t(1) << 31)) throw std::length_error("neardup: 2^31 rows or more");
+  check_row_count("neardup", n_rows);
   if (static_cast<unsigned long long>(n_rows) * plan.n_perm >= (1ull << 32)) throw std::length_error("neardup: n_rows * n_perm reaches 2^32");
   if (static_cast<unsigned long long>(n_rows) * plan.bands >= (1ull << 32)) throw std::length_error("neardup: n_rows * bands reaches 2^32");
 }

@@ -1,12 +1,12 @@
 // overlap_path.h — the n-gram overlap search on a context (include/wordpiece_amd.h, section "n-gram overlap"; kernels:
 // overlap.h): the argument rules, the answer of a call without windows, the launches over two device batches and the
-// buffers of a call.
+// buffers of a call.  Shared with repeat_path.h, in window_path.h: the intake, the window table, the kept rows.
 #pragma once
 #include <algorithm>
 
 #include "context.h"
-#include "group_path.h"
 #include "overlap.h"
+#include "window_path.h"
 
 namespace wp {
 
@@ -21,13 +21,11 @@ struct OverlapPlan {
 static OverlapPlan check_overlap_spec(const wp_overlap_spec *spec, const wp_overlap_result *out) {
   if (!spec) throw std::invalid_argument("overlap: spec is NULL");
   if (!out) throw std::invalid_argument("overlap: out is NULL");
-  if (spec->elem_bytes != 1 && spec->elem_bytes != 4) throw std::invalid_argument("overlap: elem_bytes must be 1 or 4");
-  if ((spec->want & ~(WP_OVERLAP_WANT_MASK | WP_OVERLAP_WANT_REF | WP_OVERLAP_WANT_COMPACT)) != 0) {
-    throw std::invalid_argument("overlap: want has bits outside 7");
-  }
-  if (spec->ngram < 1 || spec->ngram > kOvlMaxNgram) throw std::invalid_argument("overlap: ngram must be in [1, 64]");
+  check_elem_bytes("overlap", spec->elem_bytes);
+  check_want("overlap", spec->want, WP_OVERLAP_WANT_MASK | WP_OVERLAP_WANT_REF | WP_OVERLAP_WANT_COMPACT);
+  check_ngram("overlap", spec->ngram);
   if (spec->max_hits < 0) throw std::invalid_argument("overlap: max_hits must not be negative");
-  if (spec->hash_bits != 0 && (spec->hash_bits < 8 || spec->hash_bits > 64)) throw std::invalid_argument("overlap: hash_bits must be 0 (64) or in [8, 64]");
+  const int hash_bits = checked_hash_bits("overlap", spec->hash_bits);
   for (int32_t r : spec->reserved) {
     if (r != 0) throw std::invalid_argument("overlap: reserved must be 0");
   }
@@ -35,7 +33,7 @@ static OverlapPlan check_overlap_spec(const wp_overlap_spec *spec, const wp_over
   p.elem_bytes = static_cast<uint32_t>(spec->elem_bytes);
   p.ngram = static_cast<uint32_t>(spec->ngram);
   p.max_hits = static_cast<uint32_t>(spec->max_hits);
-  p.hash_bits = spec->hash_bits == 0 ? 64 : spec->hash_bits;
+  p.hash_bits = hash_bits;
   p.want_mask = (spec->want & WP_OVERLAP_WANT_MASK) != 0;
   p.want_ref = (spec->want & WP_OVERLAP_WANT_REF) != 0;
   p.want_compact = (spec->want & WP_OVERLAP_WANT_COMPACT) != 0;
@@ -46,8 +44,8 @@ static OverlapPlan check_overlap_spec(const wp_overlap_spec *spec, const wp_over
 static void check_overlap_rows(const void *row_off, size_t n_rows, const void *ref_off, size_t n_ref) {
   if (n_rows != 0 && !row_off) throw std::invalid_argument("overlap: row_off is NULL");
   if (n_ref != 0 && !ref_off) throw std::invalid_argument("overlap: ref_off is NULL");
-  if (n_rows >= (size_t(1) << 31)) throw std::length_error("overlap: 2^31 rows or more in row_off");
-  if (n_ref >= (size_t(1) << 31)) throw std::length_error("overlap: 2^31 rows or more in ref_off");
+  check_row_count("overlap", n_rows, " in row_off");
+  check_row_count("overlap", n_ref, " in ref_off");
 }
 
 // the statistics of an overlap call before anything is known of its rows
@@ -57,16 +55,6 @@ static wp_overlap_stats &begin_overlap_stats(wp_vocab *v, size_t n_rows, size_t 
   v->stats.overlap.n_rows = static_cast<int64_t>(n_rows);
   v->stats.overlap.n_ref = static_cast<int64_t>(n_ref);
   return v->stats.overlap;
-}
-
-// the windows of a batch in host memory (its offsets are checked)
-static unsigned long long host_windows(const int64_t *row_off, size_t n_rows, uint32_t k) {
-  unsigned long long w = 0;
-  for (size_t r = 0; r < n_rows; r++) {
-    const unsigned long long len = static_cast<unsigned long long>(row_off[r + 1] - row_off[r]);
-    if (len >= k) w += len - k + 1;
-  }
-  return w;
 }
 
 // A host call whose corpus or whose reference set has no window (n_rows >= 1): no device needed.  Nothing hits; every
@@ -120,20 +108,6 @@ static wp_overlap_result overlap_no_window(wp_vocab *v, const OverlapPlan &plan,
   return h;
 }
 
-static OvlPowers overlap_powers(uint32_t k) {
-  OvlPowers pw{};
-  uint64_t p = 1;
-  for (int i = 0; i < kOvlItems; i++) p *= kOvlB;
-  for (int i = 0; i < 6; i++) {
-    pw.step[i] = p;
-    p *= p;
-  }
-  pw.wave = p;  // (B^(kOvlItems * 64))
-  pw.bk = 1;
-  for (uint32_t i = 0; i < k; i++) pw.bk *= kOvlB;
-  return pw;
-}
-
 // The corpus `in` (n_rows >= 1) against the reference set `ref` (any number of rows), on c's stream.  The results are
 // device pointers into c->overlap_rows (the per-row arrays), c->overlap_items (mask) and c->overlap_out (the compact
 // form), valid until the handle's next call.  Waits: the sizes of both batches (the offset checks, the elements, the
@@ -179,24 +153,15 @@ static void overlap_on_device(wp_vocab *v, Context *c, const RaggedIn &in, const
   unsigned long long *d_counters = reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarOvl);
   clear_scalars(c, kScalarOvlBad, kScalarOvl, st);
   WP_HIP(hipMemsetAsync(c->d_scalars + kScalarOvlBad, 0xff, 2 * sizeof(uint32_t), st));  // (both bad-row words)
-  hipLaunchKernelGGL(ovl_rows_kernel, count_grid(n1), dim3(kBlock), 0, st, in.d_row_off, n, eb, k, d_boff, c->d_scalars + kScalarOvlBad,
-                     reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarOvlElems),
-                     reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarOvlWindows));
-  if (nr != 0) {
-    hipLaunchKernelGGL(ovl_rows_kernel, count_grid(nr1), dim3(kBlock), 0, st, ref.d_row_off, nr, eb, k, d_rboff, c->d_scalars + kScalarOvlRefBad,
-                       reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarOvlRefElems),
-                       reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarOvlRefWindows));
-  }
+  queue_window_rows(c, in, k, d_boff, kScalarOvlBad, kScalarOvlElems, kScalarOvlWindows, st);
+  if (nr != 0) queue_window_rows(c, ref, k, d_rboff, kScalarOvlRefBad, kScalarOvlRefElems, kScalarOvlRefWindows, st);
   WP_LAUNCH_CHECK();
   if (timing) WP_HIP(hipEventRecord(c->ev[kMarkCounted], st));
   queue_scalar_slots(c, kScalarOvlBad, kScalarOvlRefWindows, st);
   WP_HIP(hipStreamSynchronize(st));
-  unsigned long long sizes[4];  // elements, reference elements, windows, reference windows
-  std::memcpy(sizes, c->h_scalars + kScalarOvlElems, sizeof(sizes));
-  const size_t n_bytes = check_ragged_device("overlap", in, c->h_scalars[kScalarOvlBad], sizes[0]);
-  const size_t n_ref_bytes = check_ragged_device("overlap", ref, c->h_scalars[kScalarOvlRefBad], sizes[1], "ref_off", "ref_data");
-  if (sizes[2] > sizes[0] || sizes[3] > sizes[1]) throw HipError("overlap: more windows than elements");
-  const size_t ne = static_cast<size_t>(sizes[0]), nre = static_cast<size_t>(sizes[1]), nw = static_cast<size_t>(sizes[2]), m = static_cast<size_t>(sizes[3]);
+  const WindowSizes cs = read_window_rows(c, "overlap", in, kScalarOvlBad, kScalarOvlElems, kScalarOvlWindows);
+  const WindowSizes fs = read_window_rows(c, "overlap", ref, kScalarOvlRefBad, kScalarOvlRefElems, kScalarOvlRefWindows, "ref_off", "ref_data");
+  const size_t n_bytes = cs.n_bytes, n_ref_bytes = fs.n_bytes, ne = cs.n_elems, nre = fs.n_elems, nw = cs.n_windows, m = fs.n_windows;
   os.n_elems = static_cast<int64_t>(ne);
   os.n_ref_elems = static_cast<int64_t>(nre);
   os.n_windows = static_cast<int64_t>(nw);
@@ -214,13 +179,11 @@ static void overlap_on_device(wp_vocab *v, Context *c, const RaggedIn &in, const
   const uint32_t shift = static_cast<uint32_t>(hb - bb);
   const uint64_t mask = hb >= 64 ? ~0ull : (1ull << hb) - 1ull;
   const size_t ne1 = ne + 1, nre1 = nre + 1, m1 = m + 1;
-  const size_t tmp_words = radix_tmp_words<uint64_t>(m);
   Arena ia(&c->overlap_items, guard);
-  uint32_t *d_flag = nullptr, *d_scan = nullptr, *d_ent = nullptr, *d_ce = nullptr, *d_ct = nullptr, *d_hit = nullptr, *d_H = nullptr, *d_rvalid = nullptr,
-           *d_rvpos = nullptr, *d_v0 = nullptr, *d_v1 = nullptr, *d_head = nullptr, *d_run = nullptr, *d_head_pos = nullptr, *d_differ = nullptr,
-           *d_rep = nullptr, *d_entry = nullptr, *d_entry_pos = nullptr, *d_ent_of = nullptr, *d_ent_pos = nullptr, *d_ent_hit = nullptr,
-           *d_rtmp = nullptr, *d_bucket = nullptr, *d_itmp = nullptr;
-  uint64_t *d_rkey = nullptr, *d_k0 = nullptr, *d_k1 = nullptr, *d_ent_key = nullptr;
+  WindowTable t;  // of the reference set
+  uint32_t *d_flag = nullptr, *d_scan = nullptr, *d_ent = nullptr, *d_ce = nullptr, *d_ct = nullptr, *d_hit = nullptr, *d_H = nullptr, *d_ent_of = nullptr,
+           *d_ent_pos = nullptr, *d_ent_hit = nullptr, *d_bucket = nullptr, *d_itmp = nullptr;
+  uint64_t *d_ent_key = nullptr;
   uint8_t *d_mask = nullptr;
   for (int pass = 0; pass < 2; pass++) {
     d_flag = ia.take<uint32_t>(ne1);   // the candidate flags, then the cover flags
@@ -231,67 +194,35 @@ static void overlap_on_device(wp_vocab *v, Context *c, const RaggedIn &in, const
     d_hit = ia.take<uint32_t>(ne1);
     d_H = ia.take<uint32_t>(ne1);
     if (plan.want_mask) d_mask = ia.take<uint8_t>(ne);
-    d_rkey = ia.take<uint64_t>(nre);
-    d_rvalid = ia.take<uint32_t>(nre1);  // the window flags of the reference set, then (want_ref) the hit flags of its windows
-    d_rvpos = ia.take<uint32_t>(nre1);   // their scans
-    d_k0 = ia.take<uint64_t>(m);
-    d_k1 = ia.take<uint64_t>(m);
-    d_v0 = ia.take<uint32_t>(m);
-    d_v1 = ia.take<uint32_t>(m);
-    d_head = ia.take<uint32_t>(m1);
-    d_run = ia.take<uint32_t>(m1);
-    d_head_pos = ia.take<uint32_t>(m1);
-    d_differ = ia.take<uint32_t>(m);
-    d_rep = ia.take<uint32_t>(m);
-    d_entry = ia.take<uint32_t>(m1);
-    d_entry_pos = ia.take<uint32_t>(m1);
+    t.take(ia, nre, m);
     d_ent_of = ia.take<uint32_t>(m);
     d_ent_key = ia.take<uint64_t>(m);
     d_ent_pos = ia.take<uint32_t>(m);
     d_ent_hit = ia.take<uint32_t>(m);
-    d_rtmp = ia.take<uint32_t>(tmp_words);
     d_bucket = ia.take<uint32_t>(2 * n_buckets);
     d_itmp = ia.take<uint32_t>(cdiv(std::max(std::max(ne1, nre1), m1), kScanTile) + 8);
     if (pass == 0) ia.commit();
   }
   ia.arm(st);
   WP_HIP(hipMemsetAsync(d_hit, 0, ne1 * sizeof(uint32_t), st));
-  const OvlPowers pw = overlap_powers(k);
   uint32_t *d_n_ent = c->d_scalars + kScalarOvlEntries;
-  const uint32_t *vals = nullptr;
 
-  // ---- the reference table: keys, one sort, the representatives, the bucket index ------------------------------------------
+  // ---- the reference table: the window table of the reference set, its entries, the bucket index ----------------------------
   if (table) {
-    hipLaunchKernelGGL(ovl_keys_kernel, dim3(cdiv(nre, kOvlTile)), dim3(kBlock), 0, st, r32, nre, static_cast<const uint32_t *>(d_rboff), nr, eb, k, pw, mask,
-                       d_rkey, d_rvalid, static_cast<const uint64_t *>(nullptr), static_cast<const uint32_t *>(nullptr),
-                       static_cast<const uint32_t *>(nullptr), 0u, size_t(0), static_cast<uint32_t *>(nullptr), 0u);
-    device_exclusive_scan(d_rvalid, d_rvpos, nre1, d_itmp, nullptr, st);
-    hipLaunchKernelGGL(ovl_list_kernel, count_grid(nre), dim3(kBlock), 0, st, static_cast<const uint64_t *>(d_rkey), static_cast<const uint32_t *>(d_rvalid),
-                       static_cast<const uint32_t *>(d_rvpos), nre, m, d_k0, d_v0);
-    const int cur = radix_sort_pairs<uint64_t>(d_k0, d_v0, d_k1, d_v1, m, 0, hb, d_rtmp, tmp_words, st, rs, false);
-    const uint64_t *keys = cur ? d_k1 : d_k0;
-    vals = cur ? d_v1 : d_v0;
-    group_runs(keys, m, d_head, d_run, d_head_pos, d_itmp, c->d_scalars + kScalarOvlRuns, st);
-    hipLaunchKernelGGL(ovl_ref_head_kernel, count_grid(m), dim3(kBlock), 0, st, r32, n_ref_bytes, vals, static_cast<const uint32_t *>(d_head),
-                       static_cast<const uint32_t *>(d_run), static_cast<const uint32_t *>(d_head_pos), m, eb, k, d_differ, d_counters);
-    hipLaunchKernelGGL(ovl_ref_rep_kernel, count_grid(m), dim3(kBlock), 0, st, r32, n_ref_bytes, vals, static_cast<const uint32_t *>(d_head),
-                       static_cast<const uint32_t *>(d_run), static_cast<const uint32_t *>(d_head_pos), static_cast<const uint32_t *>(d_differ), m, eb, k,
-                       d_rep, d_entry);
-    device_exclusive_scan(d_entry, d_entry_pos, m1, d_itmp, d_n_ent, st);
-    hipLaunchKernelGGL(ovl_table_kernel, count_grid(m), dim3(kBlock), 0, st, keys, vals, static_cast<const uint32_t *>(d_rep),
-                       static_cast<const uint32_t *>(d_entry_pos), m, d_ent_of, d_ent_key, d_ent_pos, d_ent_hit);
+    t.list(ref, nre, d_rboff, k, mask, false, d_itmp, nullptr, st);
+    t.group(ref, nre, n_ref_bytes, m, k, hb, d_itmp, c->d_scalars + kScalarOvlRuns, d_counters, d_n_ent, rs, st);
+    hipLaunchKernelGGL(ovl_table_kernel, count_grid(m), dim3(kBlock), 0, st, t.keys, t.vals, t.d_rep, t.entry_pos(), m, d_ent_of, d_ent_key, d_ent_pos,
+                       d_ent_hit);
     WP_HIP(hipMemsetAsync(d_bucket, 0, 2 * n_buckets * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(ovl_bucket_kernel, count_grid(m), dim3(kBlock), 0, st, static_cast<const uint64_t *>(d_ent_key), static_cast<const uint32_t *>(d_n_ent),
-                       m, shift, n_buckets, d_bucket);
+    hipLaunchKernelGGL(ovl_bucket_kernel, count_grid(m), dim3(kBlock), 0, st, d_ent_key, d_n_ent, m, shift, n_buckets, d_bucket);
     WP_LAUNCH_CHECK();
   }
   if (timing) WP_HIP(hipEventRecord(c->ev[kMarkSorted], st));
 
   // ---- the corpus windows: keys and lookup in one kernel, the candidates compacted and compared ----------------------------
   if (search) {
-    hipLaunchKernelGGL(ovl_keys_kernel, dim3(cdiv(ne, kOvlTile)), dim3(kBlock), 0, st, c32, ne, static_cast<const uint32_t *>(d_boff), n, eb, k, pw, mask,
-                       static_cast<uint64_t *>(nullptr), d_flag, static_cast<const uint64_t *>(d_ent_key), static_cast<const uint32_t *>(d_n_ent),
-                       static_cast<const uint32_t *>(d_bucket), shift, n_buckets, d_ent, 0u);
+    hipLaunchKernelGGL(ovl_keys_kernel, dim3(cdiv(ne, kOvlTile)), dim3(kBlock), 0, st, c32, ne, d_boff, n, eb, k, overlap_powers(k), mask,
+                       nullptr, d_flag, d_ent_key, d_n_ent, d_bucket, shift, n_buckets, d_ent, 0u);
     device_exclusive_scan(d_flag, d_scan, ne, d_itmp, c->d_scalars + kScalarOvlCands, st);
     compact_flagged(d_flag, d_scan, ne, nullptr, d_ce, st);
     compact_flagged(d_flag, d_scan, ne, d_ent, d_ct, st);
@@ -304,9 +235,8 @@ static void overlap_on_device(wp_vocab *v, Context *c, const RaggedIn &in, const
   os.n_ref_distinct = static_cast<int64_t>(n_entries);
   os.n_candidates = static_cast<int64_t>(n_cand);
   if (n_cand != 0) {
-    hipLaunchKernelGGL(ovl_verify_kernel, count_grid(n_cand * kOvlLanes), dim3(kBlock), 0, st, c32, n_bytes, r32, n_ref_bytes,
-                       static_cast<const uint32_t *>(d_ce), static_cast<const uint32_t *>(d_ct), n_cand, static_cast<const uint64_t *>(d_ent_key),
-                       static_cast<const uint32_t *>(d_ent_pos), static_cast<const uint32_t *>(d_n_ent), m, eb, k, d_hit, d_ent, d_ent_hit);
+    hipLaunchKernelGGL(ovl_verify_kernel, count_grid(n_cand * kOvlLanes), dim3(kBlock), 0, st, c32, n_bytes, r32, n_ref_bytes, d_ce, d_ct,
+                       n_cand, d_ent_key, d_ent_pos, d_n_ent, m, eb, k, d_hit, d_ent, d_ent_hit);
     WP_LAUNCH_CHECK();
   }
   if (timing) WP_HIP(hipEventRecord(c->ev[kMarkScanned], st));
@@ -317,55 +247,32 @@ static void overlap_on_device(wp_vocab *v, Context *c, const RaggedIn &in, const
   WP_HIP(hipMemsetAsync(d_first_ref, 0xff, n * sizeof(int32_t), st));
   WP_HIP(hipMemsetAsync(d_flag + ne, 0, sizeof(uint32_t), st));  // (a batch without elements: the cover kernel does not run)
   if (ne != 0) {
-    hipLaunchKernelGGL(ovl_cover_kernel, count_grid(ne), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_hit), static_cast<const uint32_t *>(d_H),
-                       static_cast<const uint32_t *>(d_ent), static_cast<const uint32_t *>(d_ent_pos), m, static_cast<const uint32_t *>(d_boff), n,
-                       static_cast<const uint32_t *>(d_rboff), nr, ne, eb, k, d_flag, d_mask, d_first_hit, d_first_ref);
+    hipLaunchKernelGGL(ovl_cover_kernel, count_grid(ne), dim3(kBlock), 0, st, d_hit, d_H, d_ent, d_ent_pos, m, d_boff, n, d_rboff, nr, ne, eb, k, d_flag,
+                       d_mask, d_first_hit, d_first_ref);
   }
   device_exclusive_scan(d_flag, d_scan, ne1, d_itmp, c->d_scalars + kScalarOvlCovered, st);
-  hipLaunchKernelGGL(ovl_row_results_kernel, count_grid(n1), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_H), static_cast<const uint32_t *>(d_scan),
-                     static_cast<const uint32_t *>(d_boff), n, eb, plan.max_hits, d_hits, d_covered, d_keep, d_counters);
+  hipLaunchKernelGGL(ovl_row_results_kernel, count_grid(n1), dim3(kBlock), 0, st, d_H, d_scan, d_boff, n, eb, plan.max_hits, d_hits, d_covered, d_keep,
+                     d_counters);
   if (plan.want_ref && nr != 0) {
-    uint32_t *d_rhit = d_rvalid, *d_R = d_rvpos;  // (the window flags are listed: their arrays are free)
+    uint32_t *d_rhit = t.d_valid, *d_R = t.d_vpos;  // (the window flags are listed: their arrays are free)
     WP_HIP(hipMemsetAsync(d_rhit, 0, nre1 * sizeof(uint32_t), st));
-    if (table) {
-      hipLaunchKernelGGL(ovl_ref_mark_kernel, count_grid(m), dim3(kBlock), 0, st, vals, static_cast<const uint32_t *>(d_ent_of),
-                         static_cast<const uint32_t *>(d_ent_hit), m, nre, d_rhit);
-    }
+    if (table) hipLaunchKernelGGL(ovl_ref_mark_kernel, count_grid(m), dim3(kBlock), 0, st, t.vals, d_ent_of, d_ent_hit, m, nre, d_rhit);
     device_exclusive_scan(d_rhit, d_R, nre1, d_itmp, nullptr, st);
-    hipLaunchKernelGGL(ovl_ref_rows_kernel, count_grid(nr), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_R), static_cast<const uint32_t *>(d_rboff), nr,
-                       eb, d_ref_hits);
+    hipLaunchKernelGGL(ovl_ref_rows_kernel, count_grid(nr), dim3(kBlock), 0, st, d_R, d_rboff, nr, eb, d_ref_hits);
   }
   WP_LAUNCH_CHECK();
 
-  // ---- the compact form: dedup's kernels over the kept rows ----------------------------------------------------------------
+  // ---- the compact form of the kept rows -------------------------------------------------------------------------------------
   Arena oa(&c->overlap_out, guard);
-  int32_t *d_kept = nullptr;
-  long long *d_out_off = nullptr;
-  uint32_t *d_out = nullptr;
-  size_t n_kept = 0;
+  KeptRows kept;
   if (plan.want_compact) {
-    device_exclusive_scan(d_keep, d_keep_pos, n1, d_stmp, c->d_scalars + kScalarOvlKept, st);
-    queue_scalar_slots(c, kScalarOvlKept, kScalarOvlKept, st);
-    WP_HIP(hipStreamSynchronize(st));
-    n_kept = c->h_scalars[kScalarOvlKept];
-    if (n_kept > n) throw HipError("overlap: more kept rows than rows");
+    kept.count(c, "overlap", d_keep, d_keep_pos, n, d_stmp, kScalarOvlKept, st);
     for (int pass = 0; pass < 2; pass++) {
-      d_kept = oa.take<int32_t>(n_kept);
-      d_out_off = oa.take<long long>(n_kept + 1);
-      d_out = oa.take<uint32_t>(n_bytes / 4 + 1);
+      kept.take(oa, n_bytes);
       if (pass == 0) oa.commit();
     }
     oa.arm(st);
-    hipLaunchKernelGGL(ovl_kept_kernel, count_grid(n), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_keep), static_cast<const uint32_t *>(d_keep_pos),
-                       static_cast<const uint32_t *>(d_boff), n, n_kept, d_kept, d_out_len);
-    device_exclusive_scan(d_out_len, d_out_pos, n_kept + 1, d_stmp, nullptr, st);
-    hipLaunchKernelGGL(dedup_out_off_kernel, count_grid(n_kept + 1), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_out_pos), n_kept, eb, d_out_off);
-    if (n_bytes != 0 && n_kept != 0) {
-      hipLaunchKernelGGL(dedup_gather_kernel, count_grid((n_bytes + 3) / 4), dim3(kBlock), 0, st, static_cast<const uint8_t *>(in.d_data), n_bytes,
-                         static_cast<const uint32_t *>(d_boff), static_cast<const int32_t *>(d_kept), static_cast<const uint32_t *>(d_out_pos), n_kept, n,
-                         n_bytes, d_out);
-    }
-    WP_HIP(hipMemcpyAsync(c->d_scalars + kScalarOvlOutBytes, d_out_pos + n_kept, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    kept.queue(c, in, d_keep, d_keep_pos, d_boff, n_bytes, d_out_len, d_out_pos, d_stmp, kScalarOvlOutBytes, st);
     WP_LAUNCH_CHECK();
   }
   if (timing) WP_HIP(hipEventRecord(c->ev[kMarkWalked], st));
@@ -377,17 +284,7 @@ static void overlap_on_device(wp_vocab *v, Context *c, const RaggedIn &in, const
   os.n_covered = static_cast<int64_t>(c->h_scalars[kScalarOvlCovered]);
   os.n_hit_rows = static_cast<int64_t>(counters[kOvlHitRows]);
   os.n_collided = static_cast<int64_t>(counters[kOvlCollided]);
-  if (timing) {  // wp_stats, as the header's section says: the stage times of this call in the fields an encode times itself in
-    const float check = mark_ms(c, kMarkStart, kMarkCounted), table = mark_ms(c, kMarkCounted, kMarkSorted), look = mark_ms(c, kMarkSorted, kMarkScanned),
-                rows = mark_ms(c, kMarkScanned, kMarkWalked);
-    v->stats.ms_normalize = 0;
-    v->stats.ms_decode = check;
-    v->stats.ms_sa = table;
-    v->stats.ms_scan = look;
-    v->stats.ms_walk = rows;
-    v->stats.ms_total = check + table + look + rows;
-    end_stage_timing(v, c);
-  }
+  if (timing) end_four_stage_timing(v, c);  // (check, table, lookup, rows: the header's section)
   throw_if_oob(kSiteOverlap, "n-gram overlap", "gathers or stores outside the window, table, candidate or result arrays skipped");
   throw_if_oob(kSiteDedup, "n-gram overlap", "gathers outside the rows of the compact form skipped");
   throw_if_oob(kSiteCount, "n-gram overlap", "stores outside the compacted lists skipped");
@@ -400,14 +297,7 @@ static void overlap_on_device(wp_vocab *v, Context *c, const RaggedIn &in, const
   R->first_ref = d_first_ref;
   if (plan.want_mask && ne != 0) R->mask = d_mask;
   if (plan.want_ref && nr != 0) R->ref_hits = reinterpret_cast<int64_t *>(d_ref_hits);
-  if (plan.want_compact) {
-    const size_t out_bytes = c->h_scalars[kScalarOvlOutBytes];
-    R->n_kept = static_cast<int64_t>(n_kept);
-    R->kept = n_kept ? d_kept : nullptr;
-    R->row_off = reinterpret_cast<int64_t *>(d_out_off);
-    R->data = out_bytes ? d_out : nullptr;
-    R->n_elems = static_cast<int64_t>(out_bytes / eb);
-  }
+  if (plan.want_compact) kept.hand_out(R, c->h_scalars[kScalarOvlOutBytes], eb);
 }
 
 }  // namespace wp

@@ -1,13 +1,13 @@
 // repeat_path.h — the repeated-span search on a context (include/wordpiece_amd.h, section "repeated spans"; kernels:
 // repeat.h, and overlap.h for the windows and their grouping): the argument rules, the answer of a call without windows,
-// the launches over one device batch and the buffers of a call.
+// the launches over one device batch and the buffers of a call.  Shared with overlap_path.h, in window_path.h: the intake,
+// the window table, the kept rows.
 #pragma once
 #include <algorithm>
 
 #include "context.h"
-#include "group_path.h"
-#include "overlap_path.h"  // overlap_powers, host_windows
 #include "repeat.h"
+#include "window_path.h"
 
 namespace wp {
 
@@ -22,14 +22,12 @@ struct RepeatPlan {
 static RepeatPlan check_repeat_spec(const wp_repeat_spec *spec, const wp_repeat_result *out) {
   if (!spec) throw std::invalid_argument("repeat: spec is NULL");
   if (!out) throw std::invalid_argument("repeat: out is NULL");
-  if (spec->elem_bytes != 1 && spec->elem_bytes != 4) throw std::invalid_argument("repeat: elem_bytes must be 1 or 4");
-  if ((spec->want & ~(WP_REPEAT_WANT_MASK | WP_REPEAT_WANT_SRC | WP_REPEAT_WANT_COMPACT | WP_REPEAT_WANT_CUT)) != 0) {
-    throw std::invalid_argument("repeat: want has bits outside 15");
-  }
-  if (spec->ngram < 1 || spec->ngram > kOvlMaxNgram) throw std::invalid_argument("repeat: ngram must be in [1, 64]");
+  check_elem_bytes("repeat", spec->elem_bytes);
+  check_want("repeat", spec->want, WP_REPEAT_WANT_MASK | WP_REPEAT_WANT_SRC | WP_REPEAT_WANT_COMPACT | WP_REPEAT_WANT_CUT);
+  check_ngram("repeat", spec->ngram);
   if (spec->scope != 0 && spec->scope != 1) throw std::invalid_argument("repeat: scope must be 0 (anywhere) or 1 (earlier rows)");
   if (spec->max_repeats < 0) throw std::invalid_argument("repeat: max_repeats must not be negative");
-  if (spec->hash_bits != 0 && (spec->hash_bits < 8 || spec->hash_bits > 64)) throw std::invalid_argument("repeat: hash_bits must be 0 (64) or in [8, 64]");
+  const int hash_bits = checked_hash_bits("repeat", spec->hash_bits);
   if ((spec->flags & ~WP_REPEAT_UTF8) != 0) throw std::invalid_argument("repeat: flags has bits outside WP_REPEAT_UTF8");
   if ((spec->flags & WP_REPEAT_UTF8) != 0 && spec->elem_bytes != 1) throw std::invalid_argument("repeat: flags: WP_REPEAT_UTF8 needs elem_bytes 1");
   if (spec->reserved != 0) throw std::invalid_argument("repeat: reserved must be 0");
@@ -38,7 +36,7 @@ static RepeatPlan check_repeat_spec(const wp_repeat_spec *spec, const wp_repeat_
   p.ngram = static_cast<uint32_t>(spec->ngram);
   p.scope = static_cast<uint32_t>(spec->scope);
   p.max_repeats = static_cast<uint32_t>(spec->max_repeats);
-  p.hash_bits = spec->hash_bits == 0 ? 64 : spec->hash_bits;
+  p.hash_bits = hash_bits;
   p.want_mask = (spec->want & WP_REPEAT_WANT_MASK) != 0;
   p.want_src = (spec->want & WP_REPEAT_WANT_SRC) != 0;
   p.want_compact = (spec->want & WP_REPEAT_WANT_COMPACT) != 0;
@@ -50,7 +48,7 @@ static RepeatPlan check_repeat_spec(const wp_repeat_spec *spec, const wp_repeat_
 // the pointer and the row count of the batch
 static void check_repeat_rows(const void *row_off, size_t n_rows) {
   if (n_rows != 0 && !row_off) throw std::invalid_argument("repeat: row_off is NULL");
-  if (n_rows >= (size_t(1) << 31)) throw std::length_error("repeat: 2^31 rows or more in row_off");
+  check_row_count("repeat", n_rows, " in row_off");
 }
 
 // the statistics of a repeat call before anything is known of its rows
@@ -148,18 +146,13 @@ static void repeat_on_device(wp_vocab *v, Context *c, const RaggedIn &in, const 
   unsigned long long *d_counters = reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarRep);
   clear_scalars(c, kScalarRepBad, kScalarRep, st);
   WP_HIP(hipMemsetAsync(c->d_scalars + kScalarRepBad, 0xff, sizeof(uint32_t), st));
-  hipLaunchKernelGGL(ovl_rows_kernel, count_grid(n1), dim3(kBlock), 0, st, in.d_row_off, n, eb, k, d_boff, c->d_scalars + kScalarRepBad,
-                     reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarRepElems),
-                     reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarRepWindows));
+  queue_window_rows(c, in, k, d_boff, kScalarRepBad, kScalarRepElems, kScalarRepWindows, st);
   WP_LAUNCH_CHECK();
   if (timing) WP_HIP(hipEventRecord(c->ev[kMarkCounted], st));
   queue_scalar_slots(c, kScalarRepBad, kScalarRepWindows, st);
   WP_HIP(hipStreamSynchronize(st));
-  unsigned long long sizes[2];  // elements, windows
-  std::memcpy(sizes, c->h_scalars + kScalarRepElems, sizeof(sizes));
-  const size_t n_bytes = check_ragged_device("repeat", in, c->h_scalars[kScalarRepBad], sizes[0]);
-  if (sizes[1] > sizes[0]) throw HipError("repeat: more windows than elements");
-  const size_t ne = static_cast<size_t>(sizes[0]), nw = static_cast<size_t>(sizes[1]);
+  const WindowSizes sizes = read_window_rows(c, "repeat", in, kScalarRepBad, kScalarRepElems, kScalarRepWindows);
+  const size_t n_bytes = sizes.n_bytes, ne = sizes.n_elems, nw = sizes.n_windows;
   ps.n_elems = static_cast<int64_t>(ne);
   const uint32_t *d32 = static_cast<const uint32_t *>(in.d_data);
 
@@ -167,50 +160,30 @@ static void repeat_on_device(wp_vocab *v, Context *c, const RaggedIn &in, const 
   const int hb = plan.hash_bits;
   const uint64_t mask = hb >= 64 ? ~0ull : (1ull << hb) - 1ull;
   const size_t ne1 = ne + 1, nw1 = nw + 1;
-  const size_t tmp_words = radix_tmp_words<uint64_t>(nw);
   Arena ia(&c->repeat_items, guard);
-  uint32_t *d_valid = nullptr, *d_vpos = nullptr, *d_first = nullptr, *d_hit = nullptr, *d_H = nullptr, *d_cover = nullptr, *d_C = nullptr, *d_v0 = nullptr,
-           *d_v1 = nullptr, *d_head = nullptr, *d_run = nullptr, *d_head_pos = nullptr, *d_differ = nullptr, *d_rep = nullptr, *d_entry = nullptr,
-           *d_rtmp = nullptr, *d_itmp = nullptr;
-  uint64_t *d_key = nullptr, *d_k0 = nullptr, *d_k1 = nullptr;
+  WindowTable t;  // of the batch itself
+  uint32_t *d_first = nullptr, *d_hit = nullptr, *d_H = nullptr, *d_cover = nullptr, *d_C = nullptr, *d_itmp = nullptr;
   uint8_t *d_mask = nullptr;
   long long *d_src = nullptr;
   for (int pass = 0; pass < 2; pass++) {
-    d_key = ia.take<uint64_t>(ne);
-    d_valid = ia.take<uint32_t>(ne1);  // the window flags
-    d_vpos = ia.take<uint32_t>(ne1);   // their scan
-    d_first = ia.take<uint32_t>(ne);   // the first occurrence of the window at an element
+    d_first = ia.take<uint32_t>(ne);  // the first occurrence of the window at an element
     d_hit = ia.take<uint32_t>(ne1);
     d_H = ia.take<uint32_t>(ne1);
     d_cover = ia.take<uint32_t>(ne1);
     d_C = ia.take<uint32_t>(ne1);
     if (plan.want_mask) d_mask = ia.take<uint8_t>(ne);
     if (plan.want_src) d_src = ia.take<long long>(ne);
-    d_k0 = ia.take<uint64_t>(nw);
-    d_k1 = ia.take<uint64_t>(nw);
-    d_v0 = ia.take<uint32_t>(nw);
-    d_v1 = ia.take<uint32_t>(nw);
-    d_head = ia.take<uint32_t>(nw1);  // the run heads, then the scan of the entry flags
-    d_run = ia.take<uint32_t>(nw1);
-    d_head_pos = ia.take<uint32_t>(nw1);
-    d_differ = ia.take<uint32_t>(nw);
-    d_rep = ia.take<uint32_t>(nw);
-    d_entry = ia.take<uint32_t>(nw1);
-    d_rtmp = ia.take<uint32_t>(tmp_words);
+    t.take(ia, ne, nw);
     d_itmp = ia.take<uint32_t>(cdiv(std::max(ne1, nw1), kScanTile) + 8);
     if (pass == 0) ia.commit();
   }
   ia.arm(st);
 
-  // ---- keys, one stable sort, the runs, the first member with the same bytes: the first occurrence -------------------------
+  // ---- the window table of the batch; the first member of a run with the same bytes is the first occurrence -----------------
   size_t m = 0;  // the listed windows
   if (ne != 0) WP_HIP(hipMemsetAsync(d_first, 0xff, ne * sizeof(uint32_t), st));  // (kRepNone)
   if (nw != 0) {
-    const OvlPowers pw = overlap_powers(k);
-    hipLaunchKernelGGL(ovl_keys_kernel, dim3(cdiv(ne, kOvlTile)), dim3(kBlock), 0, st, d32, ne, static_cast<const uint32_t *>(d_boff), n, eb, k, pw, mask,
-                       d_key, d_valid, static_cast<const uint64_t *>(nullptr), static_cast<const uint32_t *>(nullptr),
-                       static_cast<const uint32_t *>(nullptr), 0u, size_t(0), static_cast<uint32_t *>(nullptr), plan.utf8 ? 1u : 0u);
-    device_exclusive_scan(d_valid, d_vpos, ne1, d_itmp, c->d_scalars + kScalarRepListed, st);
+    t.list(in, ne, d_boff, k, mask, plan.utf8, d_itmp, c->d_scalars + kScalarRepListed, st);
     m = nw;
     if (plan.utf8) {  // (the eligible windows are known to the device alone)
       queue_scalar_slots(c, kScalarRepListed, kScalarRepListed, st);
@@ -220,19 +193,8 @@ static void repeat_on_device(wp_vocab *v, Context *c, const RaggedIn &in, const 
     }
   }
   if (m != 0) {
-    hipLaunchKernelGGL(ovl_list_kernel, count_grid(ne), dim3(kBlock), 0, st, static_cast<const uint64_t *>(d_key), static_cast<const uint32_t *>(d_valid),
-                       static_cast<const uint32_t *>(d_vpos), ne, m, d_k0, d_v0);
-    const int cur = radix_sort_pairs<uint64_t>(d_k0, d_v0, d_k1, d_v1, m, 0, hb, d_rtmp, tmp_words, st, rs, false);
-    const uint64_t *keys = cur ? d_k1 : d_k0;
-    const uint32_t *vals = cur ? d_v1 : d_v0;
-    group_runs(keys, m, d_head, d_run, d_head_pos, d_itmp, c->d_scalars + kScalarRepRuns, st);
-    hipLaunchKernelGGL(ovl_ref_head_kernel, count_grid(m), dim3(kBlock), 0, st, d32, n_bytes, vals, static_cast<const uint32_t *>(d_head),
-                       static_cast<const uint32_t *>(d_run), static_cast<const uint32_t *>(d_head_pos), m, eb, k, d_differ, d_counters);
-    hipLaunchKernelGGL(ovl_ref_rep_kernel, count_grid(m), dim3(kBlock), 0, st, d32, n_bytes, vals, static_cast<const uint32_t *>(d_head),
-                       static_cast<const uint32_t *>(d_run), static_cast<const uint32_t *>(d_head_pos), static_cast<const uint32_t *>(d_differ), m, eb, k,
-                       d_rep, d_entry);
-    device_exclusive_scan(d_entry, d_head, m + 1, d_itmp, c->d_scalars + kScalarRepDistinct, st);
-    hipLaunchKernelGGL(rep_back_kernel, count_grid(m), dim3(kBlock), 0, st, vals, static_cast<const uint32_t *>(d_rep), m, ne, d_first);
+    t.group(in, ne, n_bytes, m, k, hb, d_itmp, c->d_scalars + kScalarRepRuns, d_counters, c->d_scalars + kScalarRepDistinct, rs, st);
+    hipLaunchKernelGGL(rep_back_kernel, count_grid(m), dim3(kBlock), 0, st, t.vals, t.d_rep, m, ne, d_first);
     WP_LAUNCH_CHECK();
   }
   if (timing) WP_HIP(hipEventRecord(c->ev[kMarkSorted], st));
@@ -243,42 +205,27 @@ static void repeat_on_device(wp_vocab *v, Context *c, const RaggedIn &in, const 
   WP_HIP(hipMemsetAsync(d_first_repeat, 0xff, n * sizeof(long long), st));  // (-1)
   WP_HIP(hipMemsetAsync(d_first_src_pos, 0xff, n * sizeof(long long), st));
   WP_HIP(hipMemsetAsync(d_first_src_row, 0xff, n * sizeof(int32_t), st));
-  if (ne != 0) {
-    hipLaunchKernelGGL(rep_flag_kernel, dim3(cdiv(ne, kRepTile)), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_first),
-                       static_cast<const uint32_t *>(d_boff), n, ne, eb, plan.scope, d_hit, d_src);
-  }
+  if (ne != 0) hipLaunchKernelGGL(rep_flag_kernel, dim3(cdiv(ne, kRepTile)), dim3(kBlock), 0, st, d_first, d_boff, n, ne, eb, plan.scope, d_hit, d_src);
   device_exclusive_scan(d_hit, d_H, ne1, d_itmp, c->d_scalars + kScalarRepRepeats, st);
   if (ne != 0) {
-    hipLaunchKernelGGL(rep_cover_kernel, dim3(cdiv(ne, kRepTile)), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_hit),
-                       static_cast<const uint32_t *>(d_H), static_cast<const uint32_t *>(d_first), static_cast<const uint32_t *>(d_boff), n, ne, eb, k,
-                       d_cover, d_mask, d_first_repeat, d_first_src_row, d_first_src_pos);
+    hipLaunchKernelGGL(rep_cover_kernel, dim3(cdiv(ne, kRepTile)), dim3(kBlock), 0, st, d_hit, d_H, d_first, d_boff, n, ne, eb, k, d_cover, d_mask,
+                       d_first_repeat, d_first_src_row, d_first_src_pos);
   }
   device_exclusive_scan(d_cover, d_C, ne1, d_itmp, c->d_scalars + kScalarRepCovered, st);
   WP_LAUNCH_CHECK();
   if (timing) WP_HIP(hipEventRecord(c->ev[kMarkScanned], st));
 
   // ---- the per-row results, the cut, the compact form ----------------------------------------------------------------------
-  hipLaunchKernelGGL(ovl_row_results_kernel, count_grid(n1), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_H), static_cast<const uint32_t *>(d_C),
-                     static_cast<const uint32_t *>(d_boff), n, eb, plan.max_repeats, d_repeats, d_covered, d_keep, d_counters);
+  hipLaunchKernelGGL(ovl_row_results_kernel, count_grid(n1), dim3(kBlock), 0, st, d_H, d_C, d_boff, n, eb, plan.max_repeats, d_repeats, d_covered, d_keep,
+                     d_counters);
   WP_LAUNCH_CHECK();
-  size_t n_kept = 0;
-  if (plan.want_compact) {
-    device_exclusive_scan(d_keep, d_keep_pos, n1, d_stmp, c->d_scalars + kScalarRepKept, st);
-    queue_scalar_slots(c, kScalarRepKept, kScalarRepKept, st);
-    WP_HIP(hipStreamSynchronize(st));
-    n_kept = c->h_scalars[kScalarRepKept];
-    if (n_kept > n) throw HipError("repeat: more kept rows than rows");
-  }
+  KeptRows kept;
+  if (plan.want_compact) kept.count(c, "repeat", d_keep, d_keep_pos, n, d_stmp, kScalarRepKept, st);
   Arena oa(&c->repeat_out, guard);
-  int32_t *d_kept = nullptr;
-  long long *d_out_off = nullptr, *d_cut_off = nullptr;
-  uint32_t *d_out = nullptr, *d_cut = nullptr;
+  long long *d_cut_off = nullptr;
+  uint32_t *d_cut = nullptr;
   for (int pass = 0; pass < 2 && (plan.want_compact || plan.want_cut); pass++) {
-    if (plan.want_compact) {
-      d_kept = oa.take<int32_t>(n_kept);
-      d_out_off = oa.take<long long>(n_kept + 1);
-      d_out = oa.take<uint32_t>(n_bytes / 4 + 1);
-    }
+    if (plan.want_compact) kept.take(oa, n_bytes);
     if (plan.want_cut) {
       d_cut_off = oa.take<long long>(n1);
       d_cut = oa.take<uint32_t>(n_bytes / 4 + 1);
@@ -287,28 +234,16 @@ static void repeat_on_device(wp_vocab *v, Context *c, const RaggedIn &in, const 
   }
   if (plan.want_compact || plan.want_cut) oa.arm(st);
   if (plan.want_cut) {
-    hipLaunchKernelGGL(rep_cut_off_kernel, count_grid(n1), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_C), static_cast<const uint32_t *>(d_boff), n,
-                       ne, eb, d_cut_off);
+    hipLaunchKernelGGL(rep_cut_off_kernel, count_grid(n1), dim3(kBlock), 0, st, d_C, d_boff, n, ne, eb, d_cut_off);
     if (ne != 0 && eb == 4) {
-      hipLaunchKernelGGL(rep_cut_ids_kernel, count_grid(ne), dim3(kBlock), 0, st, d32, static_cast<const uint32_t *>(d_cover),
-                         static_cast<const uint32_t *>(d_C), ne, d_cut);
+      hipLaunchKernelGGL(rep_cut_ids_kernel, count_grid(ne), dim3(kBlock), 0, st, d32, d_cover, d_C, ne, d_cut);
     } else if (ne != 0) {
-      hipLaunchKernelGGL(rep_cut_bytes_kernel, dim3(cdiv(ne, kRepCutTile)), dim3(kBlock), 0, st, d32, static_cast<const uint32_t *>(d_cover),
-                         static_cast<const uint32_t *>(d_C), ne, n_bytes, d_cut);
+      hipLaunchKernelGGL(rep_cut_bytes_kernel, dim3(cdiv(ne, kRepCutTile)), dim3(kBlock), 0, st, d32, d_cover, d_C, ne, n_bytes, d_cut);
     }
     WP_LAUNCH_CHECK();
   }
   if (plan.want_compact) {
-    hipLaunchKernelGGL(ovl_kept_kernel, count_grid(n), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_keep), static_cast<const uint32_t *>(d_keep_pos),
-                       static_cast<const uint32_t *>(d_boff), n, n_kept, d_kept, d_out_len);
-    device_exclusive_scan(d_out_len, d_out_pos, n_kept + 1, d_stmp, nullptr, st);
-    hipLaunchKernelGGL(dedup_out_off_kernel, count_grid(n_kept + 1), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_out_pos), n_kept, eb, d_out_off);
-    if (n_bytes != 0 && n_kept != 0) {
-      hipLaunchKernelGGL(dedup_gather_kernel, count_grid((n_bytes + 3) / 4), dim3(kBlock), 0, st, static_cast<const uint8_t *>(in.d_data), n_bytes,
-                         static_cast<const uint32_t *>(d_boff), static_cast<const int32_t *>(d_kept), static_cast<const uint32_t *>(d_out_pos), n_kept, n,
-                         n_bytes, d_out);
-    }
-    WP_HIP(hipMemcpyAsync(c->d_scalars + kScalarRepOutBytes, d_out_pos + n_kept, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    kept.queue(c, in, d_keep, d_keep_pos, d_boff, n_bytes, d_out_len, d_out_pos, d_stmp, kScalarRepOutBytes, st);
     WP_LAUNCH_CHECK();
   }
   if (timing) WP_HIP(hipEventRecord(c->ev[kMarkWalked], st));
@@ -325,17 +260,7 @@ static void repeat_on_device(wp_vocab *v, Context *c, const RaggedIn &in, const 
   ps.n_repeat_rows = static_cast<int64_t>(counters[kRepRepeatRows]);
   ps.n_collided = static_cast<int64_t>(counters[kRepCollided]);
   ps.n_cut_elems = plan.want_cut ? static_cast<int64_t>(ne - n_covered) : 0;
-  if (timing) {  // wp_stats, as the header's section says: the stage times of this call in the fields an encode times itself in
-    const float check = mark_ms(c, kMarkStart, kMarkCounted), group = mark_ms(c, kMarkCounted, kMarkSorted), cover = mark_ms(c, kMarkSorted, kMarkScanned),
-                rows = mark_ms(c, kMarkScanned, kMarkWalked);
-    v->stats.ms_normalize = 0;
-    v->stats.ms_decode = check;
-    v->stats.ms_sa = group;
-    v->stats.ms_scan = cover;
-    v->stats.ms_walk = rows;
-    v->stats.ms_total = check + group + cover + rows;
-    end_stage_timing(v, c);
-  }
+  if (timing) end_four_stage_timing(v, c);  // (check, grouping, cover, rows: the header's section)
   throw_if_oob(kSiteRepeat, "repeated spans", "gathers or stores outside the element, window or cut arrays skipped");
   throw_if_oob(kSiteOverlap, "repeated spans", "gathers or stores outside the window or result arrays skipped");
   throw_if_oob(kSiteDedup, "repeated spans", "gathers outside the rows of the compact form skipped");
@@ -349,14 +274,7 @@ static void repeat_on_device(wp_vocab *v, Context *c, const RaggedIn &in, const 
   R->first_src_row = d_first_src_row;
   if (plan.want_mask && ne != 0) R->mask = d_mask;
   if (plan.want_src && ne != 0) R->src = reinterpret_cast<int64_t *>(d_src);
-  if (plan.want_compact) {
-    const size_t out_bytes = c->h_scalars[kScalarRepOutBytes];
-    R->n_kept = static_cast<int64_t>(n_kept);
-    R->kept = n_kept ? d_kept : nullptr;
-    R->row_off = reinterpret_cast<int64_t *>(d_out_off);
-    R->data = out_bytes ? d_out : nullptr;
-    R->n_elems = static_cast<int64_t>(out_bytes / eb);
-  }
+  if (plan.want_compact) kept.hand_out(R, c->h_scalars[kScalarRepOutBytes], eb);
   if (plan.want_cut) {
     R->n_cut_elems = ps.n_cut_elems;
     R->cut_off = reinterpret_cast<int64_t *>(d_cut_off);

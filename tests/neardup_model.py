@@ -14,7 +14,7 @@ WANT_INVERSE, WANT_COMPACT, WANT_SIGNATURES = 1, 2, 4
 
 
 def mix(h):
-    """count_mix: the 64-bit finaliser, on a Python int"""
+    """mix64 (csrc/group.h): the 64-bit finaliser, on a Python int"""
     h &= MASK64
     h ^= h >> 33
     h = (h * 0xff51afd7ed558ccd) & MASK64

@@ -275,7 +275,7 @@ def test_handle_state():
 @pytest.mark.gpu
 def test_bounds_checking_build(tmp_path):
     """(child on the bounds-checking build with WP_ARENA_GUARD=1; the host form, whose device half is the device form's) tile edges, long words, the collision rounds and both
-    orders: no store or gather outside an array (kSiteCount), no guard zone of the call's arenas overwritten"""
+    orders: no store or gather outside an array (kSiteCount, kSiteGroup), no guard zone of the call's arenas overwritten"""
     dbg = os.path.join(PKG, "libwordpiece_amd_dbg.so")
     assert os.path.exists(dbg), "run `python -m wordpiece_amd.build`"
     script = tmp_path / "count_dbg_run.py"

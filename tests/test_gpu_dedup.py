@@ -375,7 +375,7 @@ def test_end_to_end_with_the_encoder_the_packer_and_the_detokenizer():
 @pytest.mark.parametrize("lib_name,guard", [("libwordpiece_amd_dbg.so", "0"), ("libwordpiece_amd.so", "1")])
 def test_hardened_runs(tmp_path, lib_name, guard):
     """(a fresh child: once on the bounds-checking build, once with WP_ARENA_GUARD=1) the chunk-edge and the collision
-    cases: no store or gather outside an array (kSiteDedup), no guard zone of the call's arenas overwritten"""
+    cases: no store or gather outside an array (kSiteDedup, kSiteGroup), no guard zone of the call's arenas overwritten"""
     lib = os.path.join(PKG, lib_name)
     assert os.path.exists(lib), "run `python -m wordpiece_amd.build`"
     script = tmp_path / "dedup_hard_run.py"

@@ -368,7 +368,7 @@ def test_random_parity():
 @pytest.mark.parametrize("lib_name,guard", [("libwordpiece_amd_dbg.so", "0"), ("libwordpiece_amd.so", "1")])
 def test_hardened_runs(tmp_path, lib_name, guard):
     """(a fresh child: once on the bounds-checking build, once with WP_ARENA_GUARD=1) the tile-edge, the collision and the
-    long-row cases: no gather or store outside an array (kSiteOverlap, kSiteDedup, kSiteCount), no guard zone of the call's
+    long-row cases: no gather or store outside an array (kSiteOverlap, kSiteGroup), no guard zone of the call's
     arenas overwritten"""
     lib = os.path.join(PKG, lib_name)
     assert os.path.exists(lib), "run `python -m wordpiece_amd.build`"

@@ -31,8 +31,8 @@ def test_literal_values_pin_the_functions():
 def test_mix_is_the_finaliser_of_the_kernels():
     import os
     import re
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "wordpiece_amd", "csrc", "count.h")).read()
-    body = re.search(r"uint64_t count_mix\(uint64_t h\) \{(.*?)\n\}", src, re.S).group(1)
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "wordpiece_amd", "csrc", "group.h")).read()
+    body = re.search(r"uint64_t mix64\(uint64_t h\) \{(.*?)\n\}", src, re.S).group(1)
     assert re.sub(r"\s+", " ", body).strip() == ("h ^= h >> 33; h *= 0xff51afd7ed558ccdull; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53ull; "
                                                   "h ^= h >> 33; return h;")
 

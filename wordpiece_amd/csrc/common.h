@@ -54,11 +54,14 @@ enum BoundSite {
   kSiteAlign = 14,    // span alignment: the sample of a row and the gathers from the span list (align.h)
   kSiteCount = 15,    // word counts: the stores of the word list, the groups and the table, the gathers behind them (count.h)
   kSiteLearn = 16,    // vocabulary learner: the stores of the items, the groups and the list, the gathers behind them (learn.h)
-  kSiteDedup = 17,    // duplicate rows: the stores of the chunk list, the runs and the table, the gathers behind them (dedup.h)
+  kSiteDedup = 17,    // duplicate rows: the stores of the chunk list and the runs, the gathers behind them (dedup.h)
   kSiteNearDup = 18,  // near-duplicate rows: the gathers of the shingles and signatures, the stores of the edges and labels (neardup.h)
   kSiteOverlap = 19,  // n-gram overlap: the gathers of the windows and table entries, the stores of the table, the candidates and the results (overlap.h)
   kSiteRepeat = 20,   // repeated spans: the stores of the first occurrences, the gathers of the flag and cover passes, the stores of the cut (repeat.h)
-  kBoundSites = 21
+  // the kernels that more than one grouping layer runs: the stores of the run heads, the compacted lists, the table and
+  // the compact form, the gathers behind them (group.h); read by the end check of every such layer (group_path.h)
+  kSiteGroup = 21,
+  kBoundSites = 22
 };
 #ifdef WP_DEBUG_BOUNDS
 __device__ unsigned int g_wp_oob[kBoundSites];
@@ -69,6 +72,8 @@ __device__ __forceinline__ bool wp_in_bounds(bool ok, int site) {
 #else
 __device__ __forceinline__ bool wp_in_bounds(bool, int) { return true; }
 #endif
+// a check that every build makes (an index follows from it) and the debug build counts: returns ok
+__device__ __forceinline__ bool wp_checked(bool ok, int site) { return wp_in_bounds(ok, site) && ok; }
 
 // ---- character classes: utf8.cpp:10-29 of the reference --------------------------------
 constexpr uint32_t kSpaceToken = 9601;  // utf8.hpp:14 (U+2581)

@@ -9,7 +9,7 @@
 #pragma once
 #include "common.h"
 #include "decode.h"  // class_of_cp
-#include "primitives.h"
+#include "group.h"   // mix64, absorb_bytes, last_le, run_of; the kernels of a grouping round run beside these
 
 namespace wp {
 
@@ -94,11 +94,11 @@ __global__ __launch_bounds__(kBlock) void count_starts_kernel(const uint8_t *__r
     for (int j = 0; j < kCountItems; j++) {
       const uint32_t p = static_cast<uint32_t>(base + static_cast<size_t>(threadIdx.x) * kCountItems + j);
       if (is_start & (1u << j)) {
-        if (wp_in_bounds(rs < n_words, kSiteCount) && rs < n_words) start[rs] = p;
+        if (wp_checked(rs < n_words, kSiteCount)) start[rs] = p;
         rs++;
       }
       if (is_end & (1u << j)) {
-        if (wp_in_bounds(re < n_words, kSiteCount) && re < n_words) end[re] = p;
+        if (wp_checked(re < n_words, kSiteCount)) end[re] = p;
         re++;
       }
     }
@@ -114,23 +114,6 @@ __global__ __launch_bounds__(kBlock) void count_listed_kernel(const uint32_t *__
   word_group[w] = -1;
 }
 
-// out[pos[i]] = src ? src[i] : i wherever flag[i] (pos: the exclusive scan of flag)
-__global__ __launch_bounds__(kBlock) void count_compact_kernel(const uint32_t *__restrict__ flag, const uint32_t *__restrict__ pos, size_t n,
-                                                               const uint32_t *__restrict__ src, uint32_t *__restrict__ out, size_t cap) {
-  const size_t i = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
-  if (i >= n || !flag[i]) return;
-  if (wp_in_bounds(pos[i] < cap, kSiteCount)) out[pos[i]] = src ? src[i] : static_cast<uint32_t>(i);
-}
-
-__device__ __forceinline__ uint64_t count_mix(uint64_t h) {
-  h ^= h >> 33;
-  h *= 0xff51afd7ed558ccdull;
-  h ^= h >> 33;
-  h *= 0xc4ceb9fe1a85ec53ull;
-  h ^= h >> 33;
-  return h;
-}
-
 // key[j] = the seeded hash of the bytes of word items[j], masked; a lane reads at most max_bytes bytes
 __global__ __launch_bounds__(kBlock) void count_keys_kernel(const uint8_t *__restrict__ text, const uint32_t *__restrict__ start,
                                                             const uint32_t *__restrict__ end, const uint32_t *__restrict__ items, size_t m,
@@ -139,34 +122,7 @@ __global__ __launch_bounds__(kBlock) void count_keys_kernel(const uint8_t *__res
   if (j >= m) return;
   const uint32_t w = items[j], b = start[w];
   const uint32_t len = min(end[w] - b, max_bytes);
-  uint64_t h = count_mix(seed ^ 0x9e3779b97f4a7c15ull) ^ len;
-  uint32_t i = 0;
-  for (; i + 8 <= len; i += 8) {
-    uint64_t x = 0;
-#pragma unroll
-    for (int q = 0; q < 8; q++) x |= static_cast<uint64_t>(text[b + i + q]) << (8 * q);
-    h = count_mix(h ^ x) + 0x9e3779b97f4a7c15ull;
-  }
-  uint64_t x = 0;
-  for (int q = 0; i < len; i++, q++) x |= static_cast<uint64_t>(text[b + i]) << (8 * q);
-  h = count_mix(h ^ x);
-  key[j] = h & mask;
-}
-
-// head[s] = 1 where sorted position s opens a run of equal keys
-__global__ __launch_bounds__(kBlock) void count_heads_kernel(const uint64_t *__restrict__ key, size_t m, uint32_t *__restrict__ head) {
-  const size_t s = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
-  if (s >= m) return;
-  head[s] = (s == 0 || key[s] != key[s - 1]) ? 1u : 0u;
-}
-
-// head_pos[r] = the sorted position of the head of run r; head_pos[n_runs] = m (run: the exclusive scan of head)
-__global__ __launch_bounds__(kBlock) void count_head_pos_kernel(const uint32_t *__restrict__ head, const uint32_t *__restrict__ run, size_t m,
-                                                                const uint32_t *__restrict__ n_runs, uint32_t *__restrict__ head_pos) {
-  const size_t s = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
-  if (s == 0 && wp_in_bounds(*n_runs <= m, kSiteCount)) head_pos[*n_runs] = static_cast<uint32_t>(m);
-  if (s >= m || !head[s]) return;
-  if (wp_in_bounds(run[s] < m, kSiteCount)) head_pos[run[s]] = static_cast<uint32_t>(s);
+  key[j] = absorb_bytes(mix64(seed ^ kGolden) ^ len, text + b, len) & mask;
 }
 
 // Every member of a run against the run's head, length and bytes (at most max_bytes of them): agree[s] = 1 where they
@@ -182,7 +138,7 @@ __global__ __launch_bounds__(kBlock) void count_verify_kernel(const uint8_t *__r
   const size_t s = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (s == 0) agree[m] = 0;
   if (s >= m) return;
-  const uint32_t r = run[s] + head[s] - 1u;  // (the exclusive scan counts the heads in front of s)
+  const uint32_t r = run_of(head, run, s);
   const uint32_t j = val[s];
   if (!wp_in_bounds(r < m && j < m, kSiteCount)) return;
   const uint32_t hs = head_pos[r];
@@ -273,26 +229,14 @@ __global__ __launch_bounds__(kBlock) void count_emit_kernel(const uint32_t *__re
   group_final[g] = static_cast<int32_t>(t);
 }
 
-// word_off[t] = the bytes of the words in front of t, each with `term` (0 or 1) terminator bytes; t in [0, n_kept]
-__global__ __launch_bounds__(kBlock) void count_offsets_kernel(const uint32_t *__restrict__ len_pos, size_t n_kept, int term,
-                                                               long long *__restrict__ word_off) {
-  const size_t t = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
-  if (t > n_kept) return;
-  word_off[t] = static_cast<long long>(len_pos[t]) + static_cast<long long>(t) * term;
-}
-
 // The pool, one byte per lane and consecutive lanes on consecutive bytes: the word of byte p is found by bisection in
-// word_off (at most 32 steps), its byte comes from the text, and the last byte of a word's slot is the terminator.
+// word_off (group_offsets_kernel wrote it), its byte comes from the text, and the last byte of a word's slot is the terminator.
 __global__ __launch_bounds__(kBlock) void count_gather_kernel(const uint8_t *__restrict__ text, size_t text_bytes, const long long *__restrict__ word_off,
                                                               const uint32_t *__restrict__ src, size_t n_kept, int terminator, size_t pool_bytes,
                                                               uint8_t *__restrict__ pool) {
   const size_t p = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (p >= pool_bytes) return;
-  size_t lo = 0, hi = n_kept;  // the last t with word_off[t] <= p
-  while (hi - lo > 1) {
-    const size_t mid = (lo + hi) >> 1;
-    if (static_cast<size_t>(word_off[mid]) <= p) lo = mid; else hi = mid;
-  }
+  const size_t lo = last_le(word_off, size_t(0), n_kept, p);
   const size_t k = p - static_cast<size_t>(word_off[lo]);
   uint8_t b;
   if (terminator >= 0 && p + 1 == static_cast<size_t>(word_off[lo + 1])) {

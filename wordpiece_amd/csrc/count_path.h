@@ -214,7 +214,7 @@ static void count_on_device(wp_vocab *v, Context *c, const uint8_t *d_text, size
     hipLaunchKernelGGL(count_emit_kernel, count_grid(n_kept), dim3(kBlock), 0, st, cur ? d_v1 : d_v0, d_kept_group, d_gfirst, d_gcount, d_start, d_end,
                        n_kept, n_groups, d_counts, d_len, d_src, d_gfinal);
     device_exclusive_scan(d_len, d_len_pos, n_kept + 1, d_stmp, nullptr, st);
-    hipLaunchKernelGGL(count_offsets_kernel, count_grid(n_kept + 1), dim3(kBlock), 0, st, d_len_pos, n_kept, term, d_word_off);
+    hipLaunchKernelGGL(group_offsets_kernel, count_grid(n_kept + 1), dim3(kBlock), 0, st, d_len_pos, n_kept, term, d_word_off);
     hipLaunchKernelGGL(count_gather_kernel, count_grid(pool_bytes), dim3(kBlock), 0, st, text, nb, d_word_off, d_src, n_kept, plan.terminator,
                        pool_bytes, d_pool);
   } else {
@@ -235,7 +235,7 @@ static void count_on_device(wp_vocab *v, Context *c, const uint8_t *d_text, size
     v->stats.ms_total = norm.ms + words + rounds + table;
     end_stage_timing(v, c);
   }
-  throw_if_oob(kSiteCount, "word counts", "stores or gathers outside the word, group or table arrays skipped");
+  throw_if_group_oob(kSiteCount, "word counts", "stores or gathers outside the word, group or table arrays skipped");
   check_arena_guard(c, aux, st, "count");
   check_arena_guard(c, wa, st, "count");
   check_arena_guard(c, oa, st, "count");

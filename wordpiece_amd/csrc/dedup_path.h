@@ -172,7 +172,7 @@ static void dedup_on_device(wp_vocab *v, Context *c, const RaggedIn &in, const D
 
   // ---- the table and the compact form ----------------------------------------------------------------------------------
   uint32_t *d_keep = d_head, *d_keep_pos = d_run, *d_out_len = d_agree, *d_out_pos = d_agree_pos;  // (the rounds are over)
-  hipLaunchKernelGGL(dedup_keep_kernel, count_grid(n1), dim3(kBlock), 0, st, d_first, n, d_keep);
+  hipLaunchKernelGGL(group_keep_kernel, count_grid(n1), dim3(kBlock), 0, st, d_first, n, d_keep);
   device_exclusive_scan(d_keep, d_keep_pos, n1, d_stmp, c->d_scalars + kScalarDedupUnique, st);
   // (the size of the compact form comes through the word the round totals came in)
   const GroupTable t = group_table(c, in, d_first, d_keep_pos, d_rcount, d_boff, n_unique, n_bytes, plan.want_inverse, plan.want_compact, &c->dedup_out, guard,
@@ -193,7 +193,7 @@ static void dedup_on_device(wp_vocab *v, Context *c, const RaggedIn &in, const D
     v->stats.ms_total = list + rounds + table;
     end_stage_timing(v, c);
   }
-  throw_if_oob(kSiteDedup, "duplicate rows", "stores or gathers outside the row, chunk or table arrays skipped");
+  throw_if_group_oob(kSiteDedup, "duplicate rows", "stores or gathers outside the row, chunk or table arrays skipped");
   check_arena_guard(c, ra, st, "dedup");
   check_arena_guard(c, t.oa, st, "dedup");
   R->first = d_first;

@@ -1,12 +1,12 @@
 // group_path.h — what the layers that group items by a 64-bit key share on a context (word counts: count_path.h, the
 // vocabulary learner: learn_path.h, duplicate rows: dedup_path.h, near-duplicate rows: neardup_path.h, and through
-// window_path.h n-gram overlap: overlap_path.h and repeated spans: repeat_path.h; kernels: count.h, and dedup.h for the
-// table): the spec rules with one wording, the launch grid, the arena-guard check, the stage timing of a call, the run heads of
-// a sorted key list, the end of a collision round, a ragged batch on the device, the compact form and the table in front of it.
+// window_path.h n-gram overlap: overlap_path.h and repeated spans: repeat_path.h; device side: group.h): the spec rules
+// with one wording, the launch grid, the arena-guard check, the end check of the bounds-checking build, the stage timing
+// of a call, the run heads of a sorted key list, the end of a collision round, a ragged batch on the device, the compact
+// form and the table in front of it.
 #pragma once
 #include "context.h"
-#include "count.h"
-#include "dedup.h"  // the table kernels, kDedupNoBad
+#include "group.h"
 
 namespace wp {
 
@@ -41,6 +41,26 @@ static void check_arena_guard(Context *c, const Arena &a, hipStream_t st, const 
     throw HipError(std::string("arena guard: ") + layer + ": " + std::to_string(c->h_scalars[kScalarGuardBad]) + " guard zone(s) overwritten, first behind allocation #" +
                    std::to_string(c->h_scalars[kScalarGuardFirst] - 1));
   }
+}
+
+// Behind the last kernel of a grouping layer's call, in the bounds-checking build: the layer's own site, the site the
+// kernels of group.h count at whichever layer ran them, and where a layer runs another layer's kernels, that layer's
+// site (`also`, with its text; -1: none).  All are taken before any of them fails the call, so nothing is left behind
+// for the next one.
+static void throw_if_group_oob(int site, const char *layer, const char *skipped, int also = -1, const char *also_skipped = "") {
+#ifdef WP_DEBUG_BOUNDS
+  unsigned int own = 0, shared = 0, other = 0;
+  take_oob(site, 1, &own);
+  take_oob(kSiteGroup, 1, &shared);
+  if (also >= 0) take_oob(also, 1, &other);
+  const std::string head = std::string("debug bounds: ") + layer + ": ";
+  if (own != 0) throw HipError(head + std::to_string(own) + " " + skipped);
+  if (other != 0) throw HipError(head + std::to_string(other) + " " + also_skipped);
+  if (shared != 0) {
+    throw HipError(head + std::to_string(shared) +
+                   " stores or gathers outside the run, list, table or compact-form arrays of the shared grouping kernels skipped");
+  }
+#endif
 }
 
 // ---- WP_OPT_STAGE_TIMING ----------------------------------------------------------------------------------------------
@@ -86,15 +106,15 @@ static void end_four_stage_timing(wp_vocab *v, Context *c) {
 // d_head_pos[r] the position of the head of run r (and m behind the last), *d_runs the number of runs.
 static void group_runs(const uint64_t *keys, size_t m, uint32_t *d_head, uint32_t *d_run, uint32_t *d_head_pos, uint32_t *d_stmp, uint32_t *d_runs,
                        hipStream_t st) {
-  hipLaunchKernelGGL(count_heads_kernel, count_grid(m), dim3(kBlock), 0, st, keys, m, d_head);
+  hipLaunchKernelGGL(group_heads_kernel, count_grid(m), dim3(kBlock), 0, st, keys, m, d_head);
   device_exclusive_scan(d_head, d_run, m, d_stmp, d_runs, st);
-  hipLaunchKernelGGL(count_head_pos_kernel, count_grid(m), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_head), static_cast<const uint32_t *>(d_run),
+  hipLaunchKernelGGL(group_head_pos_kernel, count_grid(m), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_head), static_cast<const uint32_t *>(d_run),
                      m, static_cast<const uint32_t *>(d_runs), d_head_pos);
 }
 
 // out[pos[i]] = src ? src[i] : i for the flagged i < n, in order (out has room for n)
 static void compact_flagged(const uint32_t *flag, const uint32_t *pos, size_t n, const uint32_t *src, uint32_t *out, hipStream_t st) {
-  hipLaunchKernelGGL(count_compact_kernel, count_grid(n), dim3(kBlock), 0, st, flag, pos, n, src, out, n);
+  hipLaunchKernelGGL(group_compact_kernel, count_grid(n), dim3(kBlock), 0, st, flag, pos, n, src, out, n);
 }
 
 // The end of a collision round, in two steps so that a layer can queue work on `next` in front of the round's one wait.
@@ -166,10 +186,10 @@ static RaggedIn upload_ragged(DeviceBuffer &buf, hipStream_t st, const void *dat
 }
 
 // what the layer's row kernel found, behind the wait that brought it: `bad` the first row whose offsets fail the check
-// (kDedupNoBad: none), n_elems the last offset.  Returns the bytes of the data.
+// (kNoBadRow: none), n_elems the last offset.  Returns the bytes of the data.
 static size_t check_ragged_device(const char *layer, const RaggedIn &in, uint32_t bad, unsigned long long n_elems, const char *off_name = "row_off",
                                   const char *data_name = "data") {
-  if (bad != kDedupNoBad) throw_bad_row(layer, bad, off_name);
+  if (bad != kNoBadRow) throw_bad_row(layer, bad, off_name);
   check_ragged_bytes(layer, n_elems, in.elem_bytes);
   if (n_elems != 0 && !in.d_data) throw std::invalid_argument(std::string(layer) + ": " + data_name + " is NULL");
   return static_cast<size_t>(n_elems) * in.elem_bytes;
@@ -183,9 +203,9 @@ static size_t check_ragged_device(const char *layer, const RaggedIn &in, uint32_
 static void compact_rows(Context *c, const RaggedIn &in, const uint32_t *d_boff, const int32_t *d_kept, size_t n_kept, size_t n_bytes, uint32_t *d_out_len,
                          uint32_t *d_out_pos, uint32_t *d_stmp, long long *d_out_off, uint32_t *d_out, int slot_out_bytes, hipStream_t st) {
   device_exclusive_scan(d_out_len, d_out_pos, n_kept + 1, d_stmp, nullptr, st);
-  hipLaunchKernelGGL(dedup_out_off_kernel, count_grid(n_kept + 1), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_out_pos), n_kept, in.elem_bytes, d_out_off);
+  hipLaunchKernelGGL(group_out_off_kernel, count_grid(n_kept + 1), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_out_pos), n_kept, in.elem_bytes, d_out_off);
   if (n_bytes != 0 && n_kept != 0) {
-    hipLaunchKernelGGL(dedup_gather_kernel, count_grid((n_bytes + 3) / 4), dim3(kBlock), 0, st, static_cast<const uint8_t *>(in.d_data), n_bytes, d_boff, d_kept,
+    hipLaunchKernelGGL(group_gather_kernel, count_grid((n_bytes + 3) / 4), dim3(kBlock), 0, st, static_cast<const uint8_t *>(in.d_data), n_bytes, d_boff, d_kept,
                        static_cast<const uint32_t *>(d_out_pos), n_kept, in.n_rows, n_bytes, d_out);
   }
   // (the size of the compact form: the last entry of its offsets)
@@ -233,7 +253,7 @@ static GroupTable group_table(Context *c, const RaggedIn &in, const int32_t *d_r
     if (pass == 0) t.oa.commit();
   }
   t.oa.arm(st);
-  hipLaunchKernelGGL(dedup_table_kernel, count_grid(n), dim3(kBlock), 0, st, d_rep, d_keep_pos, d_rcount, d_boff, n, n_unique, t.d_kept, t.d_counts,
+  hipLaunchKernelGGL(group_table_kernel, count_grid(n), dim3(kBlock), 0, st, d_rep, d_keep_pos, d_rcount, d_boff, n, n_unique, t.d_kept, t.d_counts,
                      t.d_inverse, want_compact ? d_out_len : static_cast<uint32_t *>(nullptr));
   if (want_compact) compact_rows(c, in, d_boff, t.d_kept, n_unique, n_bytes, d_out_len, d_out_pos, d_stmp, t.d_out_off, t.d_out, slot_out_bytes, st);
   return t;

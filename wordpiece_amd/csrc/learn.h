@@ -10,8 +10,7 @@
 // groups that reach the threshold and takes their count from every group up the parent chain.
 #pragma once
 #include "common.h"
-#include "count.h"  // count_mix, and the head / compact kernels of a grouping round
-#include "primitives.h"
+#include "group.h"  // mix64, absorb_bytes, last_le, run_of; the kernels of a grouping round run beside these
 
 namespace wp {
 
@@ -173,11 +172,7 @@ __global__ __launch_bounds__(kBlock) void learn_items_kernel(const uint32_t *__r
                                                              uint32_t *__restrict__ list) {
   const size_t i = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (i >= n_items) return;
-  size_t lo = 0, hi = n_words;  // the last w with item_off[w] <= i
-  while (hi - lo > 1) {
-    const size_t mid = (lo + hi) >> 1;
-    if (item_off[mid] <= i) lo = mid; else hi = mid;
-  }
+  const size_t lo = last_le(item_off, size_t(0), n_words, i);
   const uint32_t n = wlen[lo];
   uint32_t r = static_cast<uint32_t>(i - item_off[lo]), s = 0;
   while (s < n && r >= n - s) {
@@ -220,18 +215,8 @@ __global__ __launch_bounds__(kBlock) void learn_keys_kernel(const uint8_t *__res
   const uint32_t len = sp.b - sp.a;
   // (length and flag are mixed before the first bytes come in: xored into the same word, the flag would cancel against
   // a bit of the text, and "##abcdb" would collide with "abcdc")
-  uint64_t h = count_mix(count_mix(seed ^ 0x9e3779b97f4a7c15ull) ^ (static_cast<uint64_t>(len) | (static_cast<uint64_t>(sp.joined) << 32)));
-  uint32_t i = 0;
-  for (; i + 8 <= len; i += 8) {
-    uint64_t x = 0;
-#pragma unroll
-    for (int q = 0; q < 8; q++) x |= static_cast<uint64_t>(pool[sp.a + i + q]) << (8 * q);
-    h = count_mix(h ^ x) + 0x9e3779b97f4a7c15ull;
-  }
-  uint64_t x = 0;
-  for (int q = 0; i < len; i++, q++) x |= static_cast<uint64_t>(pool[sp.a + i]) << (8 * q);
-  h = count_mix(h ^ x);
-  key[j] = h & mask;
+  const uint64_t h = mix64(mix64(seed ^ kGolden) ^ (static_cast<uint64_t>(len) | (static_cast<uint64_t>(sp.joined) << 32)));
+  key[j] = absorb_bytes(h, pool + sp.a, len) & mask;
 }
 
 // Every member of a run against the run's head: flag, length, then bytes.  Where they agree the item belongs to group
@@ -245,7 +230,7 @@ __global__ __launch_bounds__(kBlock) void learn_verify_kernel(const uint8_t *__r
                                                               int32_t *__restrict__ item_group) {
   const size_t s = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (s >= m) return;
-  const uint32_t r = run[s] + head[s] - 1u;  // (the exclusive scan counts the heads in front of s)
+  const uint32_t r = run_of(head, run, s);
   const uint32_t j = val[s];
   if (!wp_in_bounds(r < m && j < m, kSiteLearn)) return;
   const uint32_t hs = head_pos[r];
@@ -322,11 +307,7 @@ __global__ __launch_bounds__(kBlock) void learn_char_groups_kernel(const uint8_t
   if (!wp_in_bounds(g < n_groups && group_first[g] < n_items, kSiteLearn)) return;
   const LearnSpan sp = learn_span(group_first[g], item_word, item_se, cell_off, cell);
   const uint32_t cp = decode_one(pool + sp.a, 4);
-  size_t lo = 0, hi = n_chars;  // the last k with char_cp[k] <= cp
-  while (hi - lo > 1) {
-    const size_t mid = (lo + hi) >> 1;
-    if (char_cp[mid] <= cp) lo = mid; else hi = mid;
-  }
+  const size_t lo = last_le(char_cp, size_t(0), n_chars, cp);  // (char_cp ascends: the slot of cp, if it is listed)
   if (!wp_in_bounds(n_chars != 0 && char_cp[lo] == cp, kSiteLearn)) return;
   char_group[2 * lo + sp.joined] = static_cast<int32_t>(g);
 }
@@ -510,11 +491,7 @@ __global__ __launch_bounds__(kBlock) void learn_gather_kernel(const uint8_t *__r
                                                               uint8_t *__restrict__ out) {
   const size_t p = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (p >= cap || p >= static_cast<size_t>(token_off[n_entries])) return;  // (cap: the room of out, a bound the host knew before the scan)
-  size_t lo = 0, hi = n_entries;  // the last t with token_off[t] <= p
-  while (hi - lo > 1) {
-    const size_t mid = (lo + hi) >> 1;
-    if (static_cast<size_t>(token_off[mid]) <= p) lo = mid; else hi = mid;
-  }
+  const size_t lo = last_le(token_off, size_t(0), n_entries, p);
   size_t k = p - static_cast<size_t>(token_off[lo]);
   const uint32_t how = from[lo] & 3u, joined = from[lo] >> 2;
   uint8_t b = 0;

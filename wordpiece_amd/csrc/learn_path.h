@@ -385,7 +385,7 @@ static void learn_on_device(wp_vocab *v, Context *c, const LearnIn &in, const Le
   hipLaunchKernelGGL(learn_emit_kernel, count_grid(E + 1), dim3(kBlock), 0, st, d_res_off, n_res, d_char_cp, d_char_group, n_chars, d_ordered, n_listed,
                      d_gfirst, d_item_word, d_item_se, d_cell_off, d_cell, d_kept, d_sum, G, M, d_scores, d_len, d_src, d_from);
   device_exclusive_scan(d_len, d_len_pos, E + 1, d_ostmp, c->d_scalars + kScalarLearnOutBytes, st);
-  hipLaunchKernelGGL(count_offsets_kernel, count_grid(E + 1), dim3(kBlock), 0, st, d_len_pos, E, 0, d_token_off);
+  hipLaunchKernelGGL(group_offsets_kernel, count_grid(E + 1), dim3(kBlock), 0, st, d_len_pos, E, 0, d_token_off);
   hipLaunchKernelGGL(learn_gather_kernel, count_grid(text_cap), dim3(kBlock), 0, st, in.d_pool, in.n_bytes, d_res, res_bytes, d_token_off, d_src, d_from, E,
                      text_cap, d_text);
   WP_LAUNCH_CHECK();
@@ -403,8 +403,7 @@ static void learn_on_device(wp_vocab *v, Context *c, const LearnIn &in, const Le
     v->stats.ms_walk = list;
     v->stats.ms_total = table + groups + search + list;
   }
-  throw_if_oob(kSiteLearn, "vocabulary learner", "stores or gathers outside the item, group or list arrays skipped");
-  throw_if_oob(kSiteCount, "vocabulary learner", "stores outside the run arrays of a grouping round skipped");
+  throw_if_group_oob(kSiteLearn, "vocabulary learner", "stores or gathers outside the item, group or list arrays skipped");
   check_arena_guard(c, aux, st, "learn");
   check_arena_guard(c, ia, st, "learn");
   check_arena_guard(c, ga, st, "learn");

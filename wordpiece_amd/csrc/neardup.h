@@ -7,16 +7,14 @@
 // l + 64, ... in registers: every lane of a wave is at the same position, so a row boundary is the same branch in all
 // of them.  A row that lies inside one segment leaves with a plain coalesced store, a row that spans segments with
 // atomicMin on signatures that start at 0xffffffff.  Band keys are one lane per (row, band); the buckets are the runs
-// of one stable sort over all of them (count.h's head kernels as they are); the members of a run that are not of the
+// of one stable sort over all of them (the head kernels of group.h); the members of a run that are not of the
 // head's row are compacted into the candidate list, every candidate is compared with its head by a group of 16 lanes,
 // and the surviving (member, head) pairs are the edges.  Components: rounds of
 // "hook the larger label to the smaller" by atomicMin over the edge list, each followed by pointer jumping; no kernel
-// waits for another workgroup.  The label array then goes through dedup's table and compact kernels as they are.
+// waits for another workgroup.  The label array then goes through the table and compact-form kernels of group.h.
 #pragma once
 #include "common.h"
-#include "count.h"  // count_mix, and the head / compact kernels of the grouping
-#include "dedup.h"  // dedup_word, kDedupNoBad, the table and compact kernels
-#include "primitives.h"
+#include "group.h"  // mix64, word_at, last_le, run_of, ragged_row; the round, table and compact-form kernels run beside these
 
 namespace wp {
 
@@ -27,16 +25,14 @@ constexpr int kNearMaxPerm = 256;                            // permutations, at
 constexpr int kNearMaxSlots = kNearMaxPerm / kWave;          // permutations a lane holds, at most
 constexpr int kNearEdgeLanes = 16;                           // lanes that compare one member with its head
 constexpr uint32_t kNearNoRow = 0xffffffffu;
-constexpr uint64_t kNearG = 0x9e3779b97f4a7c15ull;
+constexpr uint64_t kNearG = kGolden;                          // (the contract's name for it)
 static_assert(kNearSeg % kWave == 0 && kNearTile == kNearSeg * (kBlock / kWave), "a wave walks whole chunks of 64 positions");
 
 // the counters of a call, 64 bits each, in d_scalars from kScalarNear on
 enum NearCounter { kNearEmpty = 0, kNearBuckets = 1, kNearCounters = 4 };
 
-// Row i: its offsets checked as dedup checks them (the smallest bad row wins), its start in bytes, its shingle
-// positions, whether it has any, and its first label (itself).  Entry n_rows closes byte_off (the end of the data),
-// n_pos and has (0) for their scans; its lane leaves row_off[n_rows] in *n_elems.  The arithmetic is 64-bit and
-// clamped: wild offsets give a bad row or a size the host refuses, never an index.
+// Row i through ragged_row (offsets checked, byte_off, *n_elems), then its shingle positions, whether it has any, and
+// its first label (itself).  Entry n_rows closes n_pos and has (0) for their scans.  Counted: the empty rows.
 __global__ __launch_bounds__(kBlock) void near_rows_kernel(const long long *__restrict__ row_off, size_t n_rows, uint32_t elem_bytes, uint32_t k,
                                                            uint32_t *__restrict__ byte_off, uint32_t *__restrict__ n_pos,
                                                            uint32_t *__restrict__ has, int32_t *__restrict__ label, uint32_t *__restrict__ bad,
@@ -44,22 +40,16 @@ __global__ __launch_bounds__(kBlock) void near_rows_kernel(const long long *__re
   const size_t i = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
   bool empty = false;
   if (i <= n_rows) {
-    const long long a = row_off[i];
-    const unsigned long long ab = static_cast<unsigned long long>(a) * elem_bytes;
-    byte_off[i] = a < 0 || ab > 0xffffffffull ? 0xffffffffu : static_cast<uint32_t>(ab);
-    if (i == n_rows) {
+    const RaggedRow r = ragged_row(row_off, n_rows, elem_bytes, i, byte_off, bad, n_elems);
+    if (!r.row) {
       n_pos[i] = 0;
       has[i] = 0;
-      *n_elems = static_cast<unsigned long long>(a);
     } else {
-      const long long b = row_off[i + 1];
-      if (b < a || (i == 0 && a != 0)) atomicMin(bad, static_cast<uint32_t>(i));
-      const unsigned long long len = b < a ? 0ull : static_cast<unsigned long long>(b - a);
-      const unsigned long long np = len == 0 ? 0ull : (len >= k ? len - k + 1 : 1ull);
+      const unsigned long long np = r.len == 0 ? 0ull : (r.len >= k ? r.len - k + 1 : 1ull);
       n_pos[i] = static_cast<uint32_t>(np > 0xffffffffull ? 0xffffffffull : np);
-      has[i] = len != 0 ? 1u : 0u;
+      has[i] = r.len != 0 ? 1u : 0u;
       label[i] = static_cast<int32_t>(i);
-      empty = len == 0;
+      empty = r.len == 0;
     }
   }
   const uint32_t e = wave_reduce_sum(empty ? 1u : 0u);
@@ -67,25 +57,25 @@ __global__ __launch_bounds__(kBlock) void near_rows_kernel(const long long *__re
 }
 
 // The 32-bit value of the shingle at the bytes [s, s + B) of the data (1 <= B <= 256): the contract's shingle hash.
-// The loads are dedup_word's: aligned words that begin below s + B, masked behind it.
+// The loads are word_at's: aligned words that begin below s + B, masked behind it.
 __device__ __forceinline__ uint32_t near_shingle_x32(const uint32_t *__restrict__ d32, size_t s, uint32_t B, uint64_t seed) {
   const size_t e = s + B;
-  uint64_t h = count_mix(count_mix(seed ^ kNearG) ^ (static_cast<uint64_t>(B) | (1ull << 41)));
+  uint64_t h = mix64(mix64(seed ^ kNearG) ^ (static_cast<uint64_t>(B) | (1ull << 41)));
   const uint32_t full = min(B >> 3, static_cast<uint32_t>(kNearMaxShingle * 4 / 8));
   for (uint32_t q = 0; q < full; q++) {
-    const uint64_t x = static_cast<uint64_t>(dedup_word(d32, s, e, 2 * q)) | (static_cast<uint64_t>(dedup_word(d32, s, e, 2 * q + 1)) << 32);
-    h = count_mix(h ^ x) + kNearG;
+    const uint64_t x = static_cast<uint64_t>(word_at(d32, s, e, 2 * q)) | (static_cast<uint64_t>(word_at(d32, s, e, 2 * q + 1)) << 32);
+    h = mix64(h ^ x) + kNearG;
   }
   const uint32_t rest = B & 7u;
   uint64_t x = 0;
-  if (rest != 0) x = dedup_word(d32, s, e, 2 * full);
-  if (rest > 4) x |= static_cast<uint64_t>(dedup_word(d32, s, e, 2 * full + 1)) << 32;
-  h = count_mix(h ^ x);
+  if (rest != 0) x = word_at(d32, s, e, 2 * full);
+  if (rest > 4) x |= static_cast<uint64_t>(word_at(d32, s, e, 2 * full + 1)) << 32;
+  h = mix64(h ^ x);
   return static_cast<uint32_t>(h ^ (h >> 32));
 }
 
 // Tile blockIdx.x of the shingle positions [0, n_positions) (pos_off: the exclusive scan of n_pos, n_rows + 1 entries).
-// Phase 1, one lane per position: its row by bisection (at most 32 steps), its shingle's value and its row into LDS.
+// Phase 1, one lane per position: its row by bisection, its shingle's value and its row into LDS.
 // Phase 2, wave w over the positions [w * kNearSeg, (w + 1) * kNearSeg) of the tile: lane l keeps the running minimum
 // of the permutations l + 64 q, q < SLOTS, and the wave stores them where the row changes and at the end of the
 // segment — plainly where the row's positions lie inside the segment, by atomicMin where they do not (sig starts at
@@ -103,18 +93,14 @@ __global__ __launch_bounds__(kBlock) void near_sig_kernel(const uint32_t *__rest
     const size_t p = p0 + t;
     uint32_t x = 0, row = kNearNoRow;
     if (p < n_positions) {
-      size_t lo = 0, hi = n_rows;  // the last r with pos_off[r] <= p: the row that holds p (rows without positions are passed)
-      for (int step = 0; step < 32 && hi - lo > 1; step++) {
-        const size_t mid = (lo + hi) >> 1;
-        if (pos_off[mid] <= p) lo = mid; else hi = mid;
-      }
+      const size_t lo = last_le(pos_off, size_t(0), n_rows, p);  // the row that holds p (rows without positions are passed)
       const size_t r0 = byte_off[lo], r1 = byte_off[lo + 1];
       const size_t at = (p - pos_off[lo]) * elem_bytes;
       const bool inside = r0 < r1 && r1 <= n_bytes && pos_off[lo] <= p && at < r1 - r0;
-      if (wp_in_bounds(inside, kSiteNearDup) && inside) {
+      if (wp_checked(inside, kSiteNearDup)) {
         const uint32_t B = static_cast<uint32_t>(min(r1 - r0, static_cast<size_t>(k) * elem_bytes));
         const bool fits = r0 + at + B <= r1;
-        if (wp_in_bounds(fits, kSiteNearDup) && fits) {
+        if (wp_checked(fits, kSiteNearDup)) {
           x = near_shingle_x32(d32, r0 + at, B, seed);
           row = static_cast<uint32_t>(lo);
         }
@@ -135,8 +121,8 @@ __global__ __launch_bounds__(kBlock) void near_sig_kernel(const uint32_t *__rest
 #pragma unroll
   for (int q = 0; q < SLOTS; q++) {
     const uint64_t j = static_cast<uint64_t>(lane + kWave * q);
-    a[q] = count_mix(seed + (2 * j + 1) * kNearG);
-    b[q] = count_mix(seed + (2 * j + 2) * kNearG);
+    a[q] = mix64(seed + (2 * j + 1) * kNearG);
+    b[q] = mix64(seed + (2 * j + 2) * kNearG);
     m[q] = 0xffffffffu;
   }
   // the minima of row `row` so far leave the wave, and start again
@@ -182,10 +168,10 @@ __global__ __launch_bounds__(kBlock) void near_band_keys_kernel(const uint32_t *
   if (q >= n_items) return;
   const uint32_t row = rows[q / bands], band = static_cast<uint32_t>(q % bands);
   const uint32_t r = min(n_perm / bands, static_cast<uint32_t>(kNearMaxPerm));
-  uint64_t h = count_mix(count_mix(seed ^ kNearG) ^ (static_cast<uint64_t>(band) + (1ull << 42)));
-  if (wp_in_bounds(row < n_rows, kSiteNearDup) && row < n_rows) {
+  uint64_t h = mix64(mix64(seed ^ kNearG) ^ (static_cast<uint64_t>(band) + (1ull << 42)));
+  if (wp_checked(row < n_rows, kSiteNearDup)) {
     const uint32_t *s = sig + static_cast<size_t>(row) * n_perm + static_cast<size_t>(band) * r;
-    for (uint32_t t = 0; t < r; t++) h = count_mix(h ^ s[t]) + kNearG;
+    for (uint32_t t = 0; t < r; t++) h = mix64(h ^ s[t]) + kNearG;
   }
   key[q] = h;
 }
@@ -202,14 +188,13 @@ __global__ __launch_bounds__(kBlock) void near_match_kernel(const uint32_t *__re
   bool is_cand = false, bucket = false;
   uint32_t mrow = 0, hrow = 0;
   if (s < n_items) {
-    const uint32_t r = run[s] + head[s] - 1u;  // (the exclusive scan counts the heads in front of s)
-    if (wp_in_bounds(r < n_items && val[s] < n_items, kSiteNearDup) && r < n_items && val[s] < n_items) {
+    const uint32_t r = run_of(head, run, s);
+    if (wp_checked(r < n_items && val[s] < n_items, kSiteNearDup)) {
       const uint32_t hs = head_pos[r];
-      if (wp_in_bounds(hs <= s && val[hs] < n_items, kSiteNearDup) && hs <= s && val[hs] < n_items) {
+      if (wp_checked(hs <= s && val[hs] < n_items, kSiteNearDup)) {
         mrow = rows[val[s] / bands];
         hrow = rows[val[hs] / bands];
-        const bool ok = mrow < n_rows && hrow <= mrow;
-        if (wp_in_bounds(ok, kSiteNearDup) && ok) {
+        if (wp_checked(mrow < n_rows && hrow <= mrow, kSiteNearDup)) {
           is_cand = hs != s && mrow != hrow;
           bucket = hs == s && head_pos[r + 1] - hs > 1u;
         }
@@ -233,8 +218,7 @@ __global__ __launch_bounds__(kBlock) void near_agree_kernel(const uint32_t *__re
   uint32_t agree = 0;
   if (c < n_cand) {
     const uint32_t mrow = member_row[c], hrow = head_row[c];
-    const bool ok = mrow < n_rows && hrow < n_rows;
-    if (wp_in_bounds(ok, kSiteNearDup) && ok) {
+    if (wp_checked(mrow < n_rows && hrow < n_rows, kSiteNearDup)) {
       const uint32_t *ms = sig + static_cast<size_t>(mrow) * n_perm, *hs = sig + static_cast<size_t>(hrow) * n_perm;
       for (uint32_t j = sub; j < n_perm && j < static_cast<uint32_t>(kNearMaxPerm); j += kNearEdgeLanes) agree += ms[j] == hs[j] ? 1u : 0u;
     }
@@ -252,13 +236,11 @@ __global__ __launch_bounds__(kBlock) void near_hook_kernel(const uint32_t *__res
   const size_t e = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (e >= n_edges) return;
   const uint32_t u = eu[e], v = ev[e];
-  const bool ok = u < n_rows && v < n_rows;
-  if (!wp_in_bounds(ok, kSiteNearDup) || !ok) return;
+  if (!wp_checked(u < n_rows && v < n_rows, kSiteNearDup)) return;
   const int32_t lu = label[u], lv = label[v];
   if (lu == lv) return;
   const int32_t lo = min(lu, lv), hi = max(lu, lv);
-  const bool rows_ok = lo >= 0 && static_cast<size_t>(hi) < n_rows;
-  if (!wp_in_bounds(rows_ok, kSiteNearDup) || !rows_ok) return;
+  if (!wp_checked(lo >= 0 && static_cast<size_t>(hi) < n_rows, kSiteNearDup)) return;
   if (atomicMin(label + hi, lo) > lo) *changed = 1u;
 }
 
@@ -270,7 +252,7 @@ __global__ __launch_bounds__(kBlock) void near_jump_kernel(int32_t *label, size_
   int32_t l = label[i];
   for (size_t step = 0; step < n_rows; step++) {
     const bool ok = l >= 0 && static_cast<size_t>(l) < n_rows;
-    if (!wp_in_bounds(ok, kSiteNearDup) || !ok) return;
+    if (!wp_checked(ok, kSiteNearDup)) return;
     const int32_t up = label[l];
     if (up >= l) break;
     l = up;
@@ -283,8 +265,7 @@ __global__ __launch_bounds__(kBlock) void near_sizes_kernel(const int32_t *__res
   const size_t i = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (i >= n_rows) return;
   const int32_t c = cluster[i];
-  const bool ok = c >= 0 && static_cast<size_t>(c) <= i;
-  if (wp_in_bounds(ok, kSiteNearDup) && ok) atomicAdd(row_count + c, 1u);
+  if (wp_checked(c >= 0 && static_cast<size_t>(c) <= i, kSiteNearDup)) atomicAdd(row_count + c, 1u);
 }
 
 }  // namespace wp

@@ -270,7 +270,7 @@ static void neardup_on_device(wp_vocab *v, Context *c, const RaggedIn &in, const
 
   // ---- the kept rows and their sizes ----------------------------------------------------------------------------------------
   hipLaunchKernelGGL(near_sizes_kernel, count_grid(n), dim3(kBlock), 0, st, static_cast<const int32_t *>(d_cluster), n, d_rcount);
-  hipLaunchKernelGGL(dedup_keep_kernel, count_grid(n1), dim3(kBlock), 0, st, static_cast<const int32_t *>(d_cluster), n, d_keep);
+  hipLaunchKernelGGL(group_keep_kernel, count_grid(n1), dim3(kBlock), 0, st, static_cast<const int32_t *>(d_cluster), n, d_keep);
   device_exclusive_scan(d_keep, d_keep_pos, n1, d_stmp, c->d_scalars + kScalarNearUnique, st);
   WP_LAUNCH_CHECK();
   queue_scalar_slots(c, kScalarNearUnique, kScalarNearUnique, st);
@@ -299,9 +299,7 @@ static void neardup_on_device(wp_vocab *v, Context *c, const RaggedIn &in, const
     v->stats.ms_total = list + sigs + group + table;
     end_stage_timing(v, c);
   }
-  throw_if_oob(kSiteNearDup, "near-duplicate rows", "gathers or stores outside the row, item or edge arrays skipped");
-  throw_if_oob(kSiteDedup, "near-duplicate rows", "stores or gathers outside the table arrays skipped");
-  throw_if_oob(kSiteCount, "near-duplicate rows", "stores outside the compacted lists skipped");
+  throw_if_group_oob(kSiteNearDup, "near-duplicate rows", "gathers or stores outside the row, item or edge arrays skipped");
   check_arena_guard(c, ra, st, "neardup");
   check_arena_guard(c, ia, st, "neardup");
   check_arena_guard(c, t.oa, st, "neardup");

@@ -22,9 +22,7 @@
 // Nothing is an atomic on a result; the counters are integer sums.
 #pragma once
 #include "common.h"
-#include "count.h"  // count_mix, and the head / compact kernels of the grouping
-#include "dedup.h"  // dedup_word, kDedupNoBad, the compact-form kernels
-#include "primitives.h"
+#include "group.h"  // mix64, word_at, same_words, last_le, run_of, ragged_row; the round and compact-form kernels run beside these
 
 namespace wp {
 
@@ -34,7 +32,7 @@ constexpr int kOvlSpan = kBlock * kOvlItems;          // elements a workgroup of
 constexpr int kOvlTile = 1216;                        // T: window positions per workgroup of the key kernel
 constexpr int kOvlLanes = 16;                         // lanes that compare one candidate with a table entry
 constexpr int kOvlMaxBucketBits = 26;
-constexpr uint64_t kOvlB = 0x9e3779b97f4a7c15ull;     // B (odd)
+constexpr uint64_t kOvlB = kGolden;                   // B (odd)
 constexpr uint64_t kOvlG = 0xd6e8feb86659fd93ull;     // G (odd)
 static_assert(kOvlTile + kOvlMaxNgram <= kOvlSpan, "the halo of the last position of a tile lies inside the span");
 
@@ -48,27 +46,16 @@ struct OvlPowers {
   uint64_t bk;       // B^k
 };
 
-// Row i of a batch: its offsets checked as dedup checks them (the smallest bad row wins) and its start in bytes.
-// Entry n_rows closes byte_off (the end of the data); its lane leaves row_off[n_rows] in *n_elems.  *n_windows: the
-// windows of the batch, summed per wave.  The arithmetic is 64-bit and clamped: wild offsets give a bad row or a size
-// the host refuses, never an index.
+// Row i of a batch through ragged_row (offsets checked, byte_off, *n_elems).  *n_windows: the windows of the batch,
+// summed per wave.
 __global__ __launch_bounds__(kBlock) void ovl_rows_kernel(const long long *__restrict__ row_off, size_t n_rows, uint32_t elem_bytes, uint32_t k,
                                                           uint32_t *__restrict__ byte_off, uint32_t *__restrict__ bad,
                                                           unsigned long long *__restrict__ n_elems, unsigned long long *__restrict__ n_windows) {
   const size_t i = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
   unsigned long long w = 0;
   if (i <= n_rows) {
-    const long long a = row_off[i];
-    const unsigned long long ab = static_cast<unsigned long long>(a) * elem_bytes;
-    byte_off[i] = a < 0 || ab > 0xffffffffull ? 0xffffffffu : static_cast<uint32_t>(ab);
-    if (i == n_rows) {
-      *n_elems = static_cast<unsigned long long>(a);
-    } else {
-      const long long b = row_off[i + 1];
-      if (b < a || (i == 0 && a != 0)) atomicMin(bad, static_cast<uint32_t>(i));
-      const unsigned long long len = b < a ? 0ull : static_cast<unsigned long long>(b - a);
-      w = len >= k ? len - k + 1 : 0ull;
-    }
+    const RaggedRow r = ragged_row(row_off, n_rows, elem_bytes, i, byte_off, bad, n_elems);
+    if (r.row && r.len >= k) w = r.len - k + 1;
   }
   w = wave_reduce_sum64(w);
   if (lane_id() == 0 && w != 0) atomicAdd(n_windows, w);
@@ -76,12 +63,7 @@ __global__ __launch_bounds__(kBlock) void ovl_rows_kernel(const long long *__res
 
 // the last r in [lo, hi] with byte_off[r] <= addr (byte_off[lo] <= addr): the row that holds the byte, empty rows passed
 __device__ __forceinline__ uint32_t ovl_row_of(const uint32_t *__restrict__ byte_off, uint32_t lo, uint32_t hi, size_t addr) {
-  hi += 1;
-  for (int step = 0; step < 32 && hi - lo > 1; step++) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (byte_off[mid] <= addr) lo = mid; else hi = mid;
-  }
-  return lo;
+  return last_le(byte_off, lo, hi + 1u, addr);
 }
 
 // element e of the data (e < n_elems): a byte or an id, read as part of its aligned word
@@ -162,7 +144,7 @@ __global__ __launch_bounds__(kBlock) void ovl_keys_kernel(const uint32_t *__rest
     const uint32_t r = ovl_row_of(byte_off, r_lo, r_hi, addr);
     bool fits = addr + win_bytes <= byte_off[r + 1];
     if (utf8 && fits) fits = (s_x[p] & 0xc0u) != 0x80u && (addr + win_bytes == byte_off[r + 1] || (s_x[p + k] & 0xc0u) != 0x80u);
-    const uint64_t key = count_mix(s_q[p + k] - s_q[p] * pw.bk) & mask;
+    const uint64_t key = mix64(s_q[p + k] - s_q[p] * pw.bk) & mask;
     if (!ent_key) {
       key_out[e] = key;
       valid[e] = fits ? 1u : 0u;
@@ -170,9 +152,9 @@ __global__ __launch_bounds__(kBlock) void ovl_keys_kernel(const uint32_t *__rest
     }
     uint32_t cand = 0, ent = 0;
     const size_t b = static_cast<size_t>(key >> shift);
-    if (fits && wp_in_bounds(b < n_buckets, kSiteOverlap) && b < n_buckets) {
+    if (fits && wp_checked(b < n_buckets, kSiteOverlap)) {
       uint32_t lo = bucket[2 * b], hi = bucket[2 * b + 1];
-      if (wp_in_bounds(lo <= hi && hi <= n_ent, kSiteOverlap) && lo <= hi && hi <= n_ent) {
+      if (wp_checked(lo <= hi && hi <= n_ent, kSiteOverlap)) {
         const uint32_t end = hi;
         while (lo < hi) {  // the first entry of the bucket whose key is not below this one
           const uint32_t mid = lo + ((hi - lo) >> 1);
@@ -197,19 +179,10 @@ __global__ __launch_bounds__(kBlock) void ovl_list_kernel(const uint64_t *__rest
   const size_t e = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (e >= n_elems || !valid[e]) return;
   const uint32_t j = pos[e];
-  if (wp_in_bounds(j < m, kSiteOverlap) && j < m) {
+  if (wp_checked(j < m, kSiteOverlap)) {
     k0[j] = key[e];
     v0[j] = static_cast<uint32_t>(e);
   }
-}
-
-// whether the win_bytes bytes at a of data da equal those at b of data db; one lane reads them all
-__device__ __forceinline__ bool ovl_same(const uint32_t *__restrict__ da, size_t a, const uint32_t *__restrict__ db, size_t b, uint32_t win_bytes) {
-  const uint32_t words = (win_bytes + 3u) >> 2;
-  for (uint32_t i = 0; i < words; i++) {
-    if (dedup_word(da, a, a + win_bytes, i) != dedup_word(db, b, b + win_bytes, i)) return false;
-  }
-  return true;
 }
 
 // Sorted position s of the m reference windows (val: their flat positions): differ[s] = 1 where the window is not the
@@ -221,14 +194,13 @@ __global__ __launch_bounds__(kBlock) void ovl_ref_head_kernel(const uint32_t *__
   const size_t s = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
   uint32_t d = 0;
   if (s < m) {
-    const uint32_t r = run[s] + head[s] - 1u;  // (the exclusive scan counts the heads in front of s)
-    if (wp_in_bounds(r < m, kSiteOverlap) && r < m) {
+    const uint32_t r = run_of(head, run, s);
+    if (wp_checked(r < m, kSiteOverlap)) {
       const uint32_t hs = head_pos[r];
       const uint32_t wb = k * elem_bytes;
-      if (hs != s && wp_in_bounds(hs < s, kSiteOverlap) && hs < s) {
+      if (hs != s && wp_checked(hs < s, kSiteOverlap)) {
         const size_t a = static_cast<size_t>(val[s]) * elem_bytes, b = static_cast<size_t>(val[hs]) * elem_bytes;
-        const bool ok = a + wb <= n_bytes && b + wb <= n_bytes;
-        if (wp_in_bounds(ok, kSiteOverlap) && ok) d = ovl_same(d32, a, d32, b, wb) ? 0u : 1u;
+        if (wp_checked(a + wb <= n_bytes && b + wb <= n_bytes, kSiteOverlap)) d = same_words(d32, a, d32, b, wb) ? 0u : 1u;
       }
     }
     differ[s] = d;
@@ -249,10 +221,10 @@ __global__ __launch_bounds__(kBlock) void ovl_ref_rep_kernel(const uint32_t *__r
   if (s == 0) entry[m] = 0;
   if (s >= m) return;
   uint32_t rp = static_cast<uint32_t>(s);
-  const uint32_t r = run[s] + head[s] - 1u;
-  if (wp_in_bounds(r < m, kSiteOverlap) && r < m) {
+  const uint32_t r = run_of(head, run, s);
+  if (wp_checked(r < m, kSiteOverlap)) {
     const uint32_t hs = head_pos[r];
-    if (wp_in_bounds(hs <= s, kSiteOverlap) && hs <= s) {
+    if (wp_checked(hs <= s, kSiteOverlap)) {
       if (!differ[s]) {
         rp = hs;
       } else {
@@ -261,8 +233,7 @@ __global__ __launch_bounds__(kBlock) void ovl_ref_rep_kernel(const uint32_t *__r
         for (uint32_t t = hs + 1; t < s; t++) {
           if (!differ[t]) continue;
           const size_t b = static_cast<size_t>(val[t]) * elem_bytes;
-          const bool ok = a + wb <= n_bytes && b + wb <= n_bytes;
-          if (wp_in_bounds(ok, kSiteOverlap) && ok && ovl_same(d32, a, d32, b, wb)) {
+          if (wp_checked(a + wb <= n_bytes && b + wb <= n_bytes, kSiteOverlap) && same_words(d32, a, d32, b, wb)) {
             rp = t;
             break;
           }
@@ -283,9 +254,9 @@ __global__ __launch_bounds__(kBlock) void ovl_table_kernel(const uint64_t *__res
   const size_t s = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (s >= m) return;
   const uint32_t rp = rep[s];
-  if (!wp_in_bounds(rp <= s, kSiteOverlap) || rp > s) return;
+  if (!wp_checked(rp <= s, kSiteOverlap)) return;
   const uint32_t t = entry_pos[rp];
-  if (!wp_in_bounds(t < m, kSiteOverlap) || t >= m) return;
+  if (!wp_checked(t < m, kSiteOverlap)) return;
   ent_of[s] = t;
   if (rp == s) {
     ent_key[t] = key[s];
@@ -302,7 +273,7 @@ __global__ __launch_bounds__(kBlock) void ovl_bucket_kernel(const uint64_t *__re
   const size_t n_ent = min(static_cast<size_t>(*n_ent_dev), m);
   if (t >= n_ent) return;
   const size_t b = static_cast<size_t>(ent_key[t] >> shift);
-  if (!wp_in_bounds(b < n_buckets, kSiteOverlap) || b >= n_buckets) return;
+  if (!wp_checked(b < n_buckets, kSiteOverlap)) return;
   if (t == 0 || static_cast<size_t>(ent_key[t - 1] >> shift) != b) bucket[2 * b] = static_cast<uint32_t>(t);
   if (t + 1 == n_ent || static_cast<size_t>(ent_key[t + 1] >> shift) != b) bucket[2 * b + 1] = static_cast<uint32_t>(t + 1);
 }
@@ -323,15 +294,14 @@ __global__ __launch_bounds__(kBlock) void ovl_verify_kernel(const uint32_t *__re
   const uint32_t e = cand_e[c], t0 = cand_t[c];
   const uint32_t wb = k * elem_bytes, words = (wb + 3u) >> 2;
   const size_t a = static_cast<size_t>(e) * elem_bytes;
-  const bool ok = t0 < n_ent && a + wb <= n_bytes;
-  if (!wp_in_bounds(ok, kSiteOverlap) || !ok) return;
+  if (!wp_checked(t0 < n_ent && a + wb <= n_bytes, kSiteOverlap)) return;
   const uint64_t key = ent_key[t0];
   for (size_t t = t0; t < n_ent && ent_key[t] == key; t++) {
     const size_t b = static_cast<size_t>(ent_pos[t]) * elem_bytes;
     const bool inside = b + wb <= n_ref_bytes;
-    uint32_t differ = wp_in_bounds(inside, kSiteOverlap) && inside ? 0u : 1u;
+    uint32_t differ = wp_checked(inside, kSiteOverlap) ? 0u : 1u;
     if (inside) {
-      for (uint32_t i = sub; i < words && !differ; i += kOvlLanes) differ = dedup_word(c32, a, a + wb, i) != dedup_word(r32, b, b + wb, i) ? 1u : 0u;
+      for (uint32_t i = sub; i < words && !differ; i += kOvlLanes) differ = word_at(c32, a, a + wb, i) != word_at(r32, b, b + wb, i) ? 1u : 0u;
     }
 #pragma unroll
     for (int d = kOvlLanes / 2; d > 0; d >>= 1) differ |= __shfl_xor(differ, d, kWave);
@@ -367,7 +337,7 @@ __global__ __launch_bounds__(kBlock) void ovl_cover_kernel(const uint32_t *__res
   if (hit[e] && H[e] == H[s]) {
     first_hit[r] = static_cast<long long>(e - s);
     const uint32_t t = ent_at[e];
-    if (wp_in_bounds(t < m && n_ref != 0, kSiteOverlap) && t < m && n_ref != 0) {
+    if (wp_checked(t < m && n_ref != 0, kSiteOverlap)) {
       first_ref[r] = static_cast<int32_t>(ovl_row_of(ref_byte_off, 0, static_cast<uint32_t>(n_ref - 1), static_cast<size_t>(ent_pos[t]) * elem_bytes));
     }
   }
@@ -402,8 +372,7 @@ __global__ __launch_bounds__(kBlock) void ovl_ref_mark_kernel(const uint32_t *__
   const size_t s = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (s >= m) return;
   const uint32_t t = ent_of[s], p = val[s];
-  const bool ok = t < m && p < n_ref_elems;
-  if (wp_in_bounds(ok, kSiteOverlap) && ok) ref_hit[p] = ent_hit[t];
+  if (wp_checked(t < m && p < n_ref_elems, kSiteOverlap)) ref_hit[p] = ent_hit[t];
 }
 
 // Reference row j (R: the exclusive scan of ref_hit over n_ref_elems + 1 entries): its windows that some corpus window equals
@@ -423,7 +392,7 @@ __global__ __launch_bounds__(kBlock) void ovl_kept_kernel(const uint32_t *__rest
   if (i == 0) out_len[n_kept] = 0;
   if (i >= n_rows || !keep[i]) return;
   const uint32_t j = keep_pos[i];
-  if (!wp_in_bounds(j < n_kept, kSiteOverlap) || j >= n_kept) return;
+  if (!wp_checked(j < n_kept, kSiteOverlap)) return;
   kept[j] = static_cast<int32_t>(i);
   out_len[j] = byte_off[i + 1] - byte_off[i];
 }

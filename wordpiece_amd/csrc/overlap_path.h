@@ -285,9 +285,7 @@ static void overlap_on_device(wp_vocab *v, Context *c, const RaggedIn &in, const
   os.n_hit_rows = static_cast<int64_t>(counters[kOvlHitRows]);
   os.n_collided = static_cast<int64_t>(counters[kOvlCollided]);
   if (timing) end_four_stage_timing(v, c);  // (check, table, lookup, rows: the header's section)
-  throw_if_oob(kSiteOverlap, "n-gram overlap", "gathers or stores outside the window, table, candidate or result arrays skipped");
-  throw_if_oob(kSiteDedup, "n-gram overlap", "gathers outside the rows of the compact form skipped");
-  throw_if_oob(kSiteCount, "n-gram overlap", "stores outside the compacted lists skipped");
+  throw_if_group_oob(kSiteOverlap, "n-gram overlap", "gathers or stores outside the window, table, candidate or result arrays skipped");
   check_arena_guard(c, ra, st, "overlap");
   check_arena_guard(c, ia, st, "overlap");
   check_arena_guard(c, oa, st, "overlap");

@@ -19,7 +19,9 @@
 // two words it shares with its neighbours are written byte by byte.  No byte is written twice and no value depends on
 // an order of execution.
 #pragma once
-#include "overlap.h"  // the window keys, the list, the head comparison, the representatives, the per-row results, the kept rows
+// overlap.h wholesale, and group.h through it: the window keys, the list, the head comparison, the representatives, the
+// per-row results, the kept rows, ovl_row_of
+#include "overlap.h"
 
 namespace wp {
 
@@ -41,10 +43,9 @@ __global__ __launch_bounds__(kBlock) void rep_back_kernel(const uint32_t *__rest
   const size_t s = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (s >= m) return;
   const uint32_t rp = rep[s];
-  if (!wp_in_bounds(rp <= s, kSiteRepeat) || rp > s) return;
+  if (!wp_checked(rp <= s, kSiteRepeat)) return;
   const uint32_t p = val[s], q = val[rp];
-  const bool ok = p < n_elems && q <= p;
-  if (wp_in_bounds(ok, kSiteRepeat) && ok) first[p] = q;
+  if (wp_checked(p < n_elems && q <= p, kSiteRepeat)) first[p] = q;
 }
 
 // the rows of the first and of the last element of the tile that begins at `base`, by two waves, into s_rows
@@ -106,13 +107,13 @@ __global__ __launch_bounds__(kBlock) void rep_cover_kernel(const uint32_t *__res
     const size_t from = e + 1 >= s + k ? e + 1 - k : s;
     const bool inside = s <= e && from >= lo;
     uint32_t cov = 0;
-    if (wp_in_bounds(inside, kSiteRepeat) && inside) cov = s_H[e + 1 - lo] != s_H[from - lo] ? 1u : 0u;
+    if (wp_checked(inside, kSiteRepeat)) cov = s_H[e + 1 - lo] != s_H[from - lo] ? 1u : 0u;
     cover[e] = cov;
     if (mask) mask[e] = static_cast<uint8_t>(cov);
     if (inside && hit[e] && s_H[e - lo] == H[s]) {
       first_repeat[r] = static_cast<long long>(e - s);
       const uint32_t f = first[e];
-      if (wp_in_bounds(f < e, kSiteRepeat) && f < e) {
+      if (wp_checked(f < e, kSiteRepeat)) {
         const uint32_t fr = ovl_row_of(byte_off, 0, static_cast<uint32_t>(n_rows - 1), static_cast<size_t>(f) * elem_bytes);
         first_src_row[r] = static_cast<int32_t>(fr);
         first_src_pos[r] = static_cast<long long>(f) - static_cast<long long>(byte_off[fr] / elem_bytes);
@@ -128,7 +129,7 @@ __global__ __launch_bounds__(kBlock) void rep_cut_off_kernel(const uint32_t *__r
   const size_t i = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (i > n_rows) return;
   const size_t a = byte_off[i] / elem_bytes;
-  if (!wp_in_bounds(a <= n_elems, kSiteRepeat) || a > n_elems) return;
+  if (!wp_checked(a <= n_elems, kSiteRepeat)) return;
   cut_off[i] = static_cast<long long>(a) - static_cast<long long>(Cv[a]);
 }
 
@@ -138,7 +139,7 @@ __global__ __launch_bounds__(kBlock) void rep_cut_ids_kernel(const uint32_t *__r
   const size_t e = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (e >= n_elems || cover[e]) return;
   const uint32_t c = Cv[e];
-  if (wp_in_bounds(c <= e, kSiteRepeat) && c <= e) out[e - c] = d32[e];
+  if (wp_checked(c <= e, kSiteRepeat)) out[e - c] = d32[e];
 }
 
 // The cut of bytes, tile blockIdx.x of kRepCutTile bytes.  Its kept bytes are [o0, o1) of the output.  A lane takes
@@ -153,7 +154,7 @@ __global__ __launch_bounds__(kBlock) void rep_cut_bytes_kernel(const uint32_t *_
   const size_t end = min(base + kRepCutTile, n_elems);
   const size_t c0 = Cv[base], c1 = Cv[end];
   const bool sane = c0 <= base && c1 <= end && c0 <= c1 && c1 - c0 <= end - base && end - c1 <= cap;
-  if (!wp_in_bounds(sane, kSiteRepeat) || !sane) return;  // (the whole workgroup leaves together)
+  if (!wp_checked(sane, kSiteRepeat)) return;  // (the whole workgroup leaves together)
   const size_t o0 = base - c0, o1 = end - c1, w0 = o0 & ~static_cast<size_t>(3);
 #pragma unroll
   for (int it = 0; it < kRepCutWords; it++) {
@@ -164,7 +165,7 @@ __global__ __launch_bounds__(kBlock) void rep_cut_bytes_kernel(const uint32_t *_
     for (uint32_t b = 0; b < 4 && e0 + b < end; b++) {
       if (cover[e0 + b]) continue;
       const size_t at = o - w0;
-      if (wp_in_bounds(o >= o0 && at < kRepCutTile + 4, kSiteRepeat) && o >= o0 && at < kRepCutTile + 4) sb[at] = static_cast<uint8_t>(x >> (8u * b));
+      if (wp_checked(o >= o0 && at < kRepCutTile + 4, kSiteRepeat)) sb[at] = static_cast<uint8_t>(x >> (8u * b));
       o++;
     }
   }

@@ -261,9 +261,9 @@ static void repeat_on_device(wp_vocab *v, Context *c, const RaggedIn &in, const 
   ps.n_collided = static_cast<int64_t>(counters[kRepCollided]);
   ps.n_cut_elems = plan.want_cut ? static_cast<int64_t>(ne - n_covered) : 0;
   if (timing) end_four_stage_timing(v, c);  // (check, grouping, cover, rows: the header's section)
-  throw_if_oob(kSiteRepeat, "repeated spans", "gathers or stores outside the element, window or cut arrays skipped");
-  throw_if_oob(kSiteOverlap, "repeated spans", "gathers or stores outside the window or result arrays skipped");
-  throw_if_oob(kSiteDedup, "repeated spans", "gathers outside the rows of the compact form skipped");
+  // (kSiteOverlap: overlap.h's kernels run here too)
+  throw_if_group_oob(kSiteRepeat, "repeated spans", "gathers or stores outside the element, window or cut arrays skipped", kSiteOverlap,
+                     "gathers or stores outside the window or result arrays skipped");
   check_arena_guard(c, ra, st, "repeat");
   check_arena_guard(c, ia, st, "repeat");
   check_arena_guard(c, oa, st, "repeat");

@@ -37,7 +37,7 @@ static OvlPowers overlap_powers(uint32_t k) {
 }
 
 // ---- the per-row intake of one batch ------------------------------------------------------------------------------------
-// d_boff: the byte offsets of the rows; slot_bad: the first bad row (set to kDedupNoBad by the caller); the 64-bit slots
+// d_boff: the byte offsets of the rows; slot_bad: the first bad row (set to kNoBadRow by the caller); the 64-bit slots
 // slot_elems and slot_windows (cleared by the caller): the elements and the windows of k elements
 static void queue_window_rows(Context *c, const RaggedIn &in, uint32_t k, uint32_t *d_boff, int slot_bad, int slot_elems, int slot_windows, hipStream_t st) {
   hipLaunchKernelGGL(ovl_rows_kernel, count_grid(in.n_rows + 1), dim3(kBlock), 0, st, in.d_row_off, in.n_rows, in.elem_bytes, k, d_boff, c->d_scalars + slot_bad,

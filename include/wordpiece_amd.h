@@ -848,6 +848,97 @@ int wp_repeat_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row_
 typedef struct { int64_t n_rows, n_elems, n_windows, n_distinct, n_repeats, n_repeat_rows, n_covered, n_cut_elems, n_collided; } wp_repeat_stats;
 int wp_get_repeat_stats(const wp_vocab *v, wp_repeat_stats *out);   /* n_rows == -1: no such call yet, or an encode since */
 
+/* ---- quality signals (an addition: per document of a ragged batch of text a fixed set of exact integer signals, a list
+ * of threshold rules over them, and the passing documents in compact form: the heuristic filters that Gopher, C4 and
+ * FineWeb put in front of deduplication.  This section is the contract; tests/quality_model.py is its executable form) ----
+ * wp_quality_rows[_device](v, data, row_off, n_rows, spec, out).  data: text bytes (elem_bytes 1 only); row_off int64
+ * [n_rows + 1], ascending from 0, as wp_dedup_rows takes it; a row may start at any byte.  No vocabulary is read and no
+ * normalisation applied (case is a signal); the handle lends its context.  Every signal of row i is a function of that
+ * row's bytes alone.
+ * Characters.  A row is decoded on its own by the decoder's rule: a lead byte starts a character iff the bytes its length
+ * calls for lie inside the row and form a valid sequence; every byte no such sequence covers is an invalid byte, a
+ * character of its own without a class (no space, no spacing character, not alphabetic).  The rule is local: within 3
+ * bytes either way.
+ * Classes.  Space, punctuation and CJK as everywhere in this library (the spacing characters are their union).  alpha is
+ * general category L*, digit Nd, upper Lu, from a table generated by tools/gen_class_tables.py from Python's unicodedata
+ * (csrc/class_tables.h, WP_CLASS_UNICODE_VERSION).
+ * Words.  The rule of the word counts, per row: character p starts a word iff it is no space and (it is the row's first
+ * character, or it or the character in front of it is a spacing character); a word ends in front of the next space or
+ * word start, or with the row.  A punctuation character is therefore a word of its own.
+ * Lines.  A line is a maximal run of bytes other than 0x0A inside a row, so none is empty.  Its first and last character
+ * are its first and last non-space characters; a line of spaces only has neither.
+ * Signals.  signals int64 [WP_QUALITY_SIGNALS][n_rows], signal-major, indices WP_QS_*: BYTES; CHARS (an invalid byte is
+ * one); INVALID; SPACE_CHARS, ALPHA_CHARS, DIGIT_CHARS, UPPER_CHARS, PUNCT_CHARS; WORDS; TEXT_WORDS (words whose first
+ * character is no punctuation) and TEXT_WORD_CHARS (their characters); ALPHA_WORDS (words that hold an alpha character);
+ * STOP_WORDS (words equal to a listed stop word, ASCII A-Z of the text folded to lower case, nothing else folded, compared
+ * byte for byte); HASHES ('#' bytes); ELLIPSES (U+2026 characters, plus maximal runs of three or more '.' inside the row,
+ * each run once); NEWLINES (0x0A bytes); LINES; BULLET_LINES (first character '-' or U+2022); ELLIPSIS_LINES (last
+ * character U+2026, or '.' with ".." directly in front of it inside the line); TERMINAL_LINES (last character one of
+ * . ! ? " '); SHORT_LINES (at most short_line_chars characters, 0: 30; the line feed does not count); DUP_LINES (lines whose
+ * bytes equal an earlier line of the same row; the line feed is no part of the comparison, so a last line without one
+ * can duplicate an earlier line that has one) and DUP_LINE_CHARS (their characters).  The last two are 0 without
+ * WP_QUALITY_WANT_DUP_LINES.
+ * Stop words: n_stop_words words, word t the bytes stop_pool[stop_off[t] .. stop_off[t + 1]) in host memory; at most 64,
+ * each 1 to 32 bytes without ASCII upper case; none is allowed.
+ * Rules.  limit int64 [WP_QUALITY_RULES], each -1 (off) or in [0, 10^9], indices WP_QR_*.  A row fails rule r by its
+ * integer inequality and nothing else (zero denominators need no case: both sides are 0 and the rule passes; every
+ * product fits 64 bits): MIN_TEXT_WORDS: TEXT_WORDS < L; MAX_TEXT_WORDS: TEXT_WORDS > L; MIN_MEAN_WORD_X1000:
+ * TEXT_WORD_CHARS * 1000 < L * TEXT_WORDS; MAX_MEAN_WORD_X1000: the same with >; MAX_HASH_PER_WORD: HASHES * 1000 > L *
+ * WORDS; MAX_ELLIPSIS_PER_WORD: ELLIPSES * 1000 > L * WORDS; MAX_BULLET_LINES: BULLET_LINES * 1000 > L * LINES;
+ * MAX_ELLIPSIS_LINES: ELLIPSIS_LINES * 1000 > L * LINES; MIN_ALPHA_WORDS: ALPHA_WORDS * 1000 < L * WORDS; MIN_STOP_WORDS:
+ * STOP_WORDS < L; MAX_DUP_LINES: DUP_LINES * 1000 > L * LINES; MAX_DUP_LINE_CHARS: DUP_LINE_CHARS * 1000 > L * CHARS;
+ * MIN_TERMINAL_LINES: TERMINAL_LINES * 1000 < L * LINES; MAX_SHORT_LINES: SHORT_LINES * 1000 > L * LINES;
+ * MAX_NEWLINES_PER_WORD: NEWLINES * 1000 > L * WORDS; rule 15 is reserved and must be -1.  The two duplicate-line rules
+ * need WP_QUALITY_WANT_DUP_LINES.  The published thresholds of Gopher and FineWeb can be stated in these rules (the Python
+ * wrapper has them as presets), over THIS contract's words and lines: parity with another tokeniser's word count, such
+ * as DataTrove's, is not claimed.
+ * Results.  reasons uint32 [n_rows], bit r set where rule r failed; a row is kept iff its reasons are 0.  With
+ * WP_QUALITY_WANT_COMPACT: kept int32 [n_kept] ascending, and the kept rows whole and back to back as data and row_off
+ * int64 [n_kept + 1], n_elems bytes, as the compact form of wp_overlap_rows.
+ * Exactness.  No result depends on a hash, a seed or an order of execution: every combination across lanes is an integer
+ * sum (per-tile partial sums met by integer atomics), and the duplicate lines come from the exact duplicate-row search.
+ * WP_ERR_ARG, before a device is touched and with the field named: spec or out NULL, elem_bytes not 1, want with a bit
+ * outside 3, short_line_chars negative, a limit outside {-1} and [0, 10^9], limit[15] not -1, limit[10] or limit[11] on
+ * without WP_QUALITY_WANT_DUP_LINES, a bad stop list (n_stop_words outside [0, 64], stop_pool or stop_off NULL with words,
+ * stop_off not ascending from 0, a word of 0 or more than 32 bytes or with ASCII upper case), reserved not 0, row_off NULL
+ * with n_rows > 0; data NULL with bytes.  Offsets that do not start at 0 or descend give WP_ERR_ARG with the first bad
+ * row: the host form checks on the host, the device form by a kernel, before anything reads through them.
+ * WP_ERR_TOO_LARGE: n_rows >= 2^31, the batch over UINT32_MAX bytes, or 2^30 lines or more with
+ * WP_QUALITY_WANT_DUP_LINES.
+ * Host form: the blocks of *out are malloc'd, each freed with wp_free.  n_rows == 0 returns all NULL; a batch of 0 bytes
+ * is answered on the host (signals 0, reasons the rules over zeros).  Device form: the buffer contract of
+ * wp_dedup_rows_device; the arrays of *d_out are device memory owned by the handle until its next call (the next dedup
+ * call included: the duplicate-line stage uses its buffers); nothing behind the data influences a result.
+ * Cost.  All work is flat over bytes, words or lines, never over rows.
+ * Waits of a call, set by the spec alone: one for the sizes (the offset check, the bytes), one for the numbers of words
+ * and lines; with WP_QUALITY_WANT_DUP_LINES, where there is a line, those of the duplicate-row search over the lines (its
+ * sizes, one per round — one unless 64-bit keys collide — and its end); with WP_QUALITY_WANT_COMPACT one for the kept
+ * count; one that ends the call.  With WP_OPT_STAGE_TIMING a call leaves its device times in wp_stats: ms_decode (the
+ * offset check), ms_sa (both class passes, the word pass, the line pass), ms_scan (the duplicate-line stage), ms_walk (the
+ * rules, the compact form), ms_total (their sum); ms_normalize is 0.  A quality call leaves the statistics of every
+ * other layer as they were, those of wp_get_dedup_stats included. */
+#define WP_QUALITY_SIGNALS 23
+#define WP_QUALITY_RULES   16
+#define WP_QUALITY_WANT_DUP_LINES 1
+#define WP_QUALITY_WANT_COMPACT   2
+enum { WP_QS_BYTES = 0, WP_QS_CHARS, WP_QS_INVALID, WP_QS_SPACE_CHARS, WP_QS_ALPHA_CHARS, WP_QS_DIGIT_CHARS, WP_QS_UPPER_CHARS, WP_QS_PUNCT_CHARS,
+       WP_QS_WORDS, WP_QS_TEXT_WORDS, WP_QS_TEXT_WORD_CHARS, WP_QS_ALPHA_WORDS, WP_QS_STOP_WORDS, WP_QS_HASHES, WP_QS_ELLIPSES, WP_QS_NEWLINES,
+       WP_QS_LINES, WP_QS_BULLET_LINES, WP_QS_ELLIPSIS_LINES, WP_QS_TERMINAL_LINES, WP_QS_SHORT_LINES, WP_QS_DUP_LINES, WP_QS_DUP_LINE_CHARS };
+enum { WP_QR_MIN_TEXT_WORDS = 0, WP_QR_MAX_TEXT_WORDS, WP_QR_MIN_MEAN_WORD_X1000, WP_QR_MAX_MEAN_WORD_X1000, WP_QR_MAX_HASH_PER_WORD,
+       WP_QR_MAX_ELLIPSIS_PER_WORD, WP_QR_MAX_BULLET_LINES, WP_QR_MAX_ELLIPSIS_LINES, WP_QR_MIN_ALPHA_WORDS, WP_QR_MIN_STOP_WORDS,
+       WP_QR_MAX_DUP_LINES, WP_QR_MAX_DUP_LINE_CHARS, WP_QR_MIN_TERMINAL_LINES, WP_QR_MAX_SHORT_LINES, WP_QR_MAX_NEWLINES_PER_WORD, WP_QR_RESERVED };
+typedef struct { int32_t elem_bytes, want, short_line_chars, n_stop_words; const void *stop_pool; const int64_t *stop_off; int64_t limit[WP_QUALITY_RULES]; int64_t reserved; } wp_quality_spec;
+typedef struct { int64_t *signals, *row_off; uint32_t *reasons; int32_t *kept; void *data; int64_t n_rows, n_kept, n_elems; } wp_quality_result;
+int wp_quality_rows(wp_vocab *v, const void *data, const int64_t *row_off, size_t n_rows, const wp_quality_spec *spec, wp_quality_result *out);
+int wp_quality_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row_off, size_t n_rows, const wp_quality_spec *spec, wp_quality_result *d_out);
+/* The statistics of the last quality call, in a struct of its own: the rows, the sums of BYTES, CHARS, INVALID, WORDS,
+ * LINES and DUP_LINES over them, the kept rows, and rule_failed[r], the rows rule r failed: what a pipeline report prints. */
+typedef struct { int64_t n_rows, n_bytes, n_chars, n_invalid, n_words, n_lines, n_dup_lines, n_kept, rule_failed[WP_QUALITY_RULES]; } wp_quality_stats;
+int wp_get_quality_stats(const wp_vocab *v, wp_quality_stats *out);   /* n_rows == -1: no such call yet, or an encode since */
+/* the class bits of tools/gen_class_tables.py for a code point (1 alpha, 2 digit, 4 upper; -1: no code point): the table the
+ * kernels read, for its test */
+int32_t wp_quality_class(uint32_t cp);
+
 /* The same call sharded over several GPUs of the node, behind the boundary: the reference's own
  * precedent is the in-library chunking at whitespace of linear.cpp:283-299 (thread chunks) and
  * linear.cpp:355-367 (encodeExternal batches).  The text is cut at ASCII whitespace into one shard

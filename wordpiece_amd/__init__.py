@@ -67,6 +67,7 @@ ABI_SYMBOLS = [
     "wp_neardup_rows", "wp_neardup_rows_device", "wp_get_neardup_stats",
     "wp_overlap_rows", "wp_overlap_rows_device", "wp_get_overlap_stats",
     "wp_repeat_rows", "wp_repeat_rows_device", "wp_get_repeat_stats",
+    "wp_quality_rows", "wp_quality_rows_device", "wp_get_quality_stats", "wp_quality_class",
 ]
 
 
@@ -359,6 +360,51 @@ class RepeatStats(C.Structure):
                 ("n_repeat_rows", C.c_int64), ("n_covered", C.c_int64), ("n_cut_elems", C.c_int64), ("n_collided", C.c_int64)]
 
 
+WP_QUALITY_WANT_DUP_LINES = 1
+WP_QUALITY_WANT_COMPACT = 2
+# the signals and the rules of a quality call, by index (WP_QS_*, WP_QR_*)
+QUALITY_SIGNALS = ("bytes", "chars", "invalid", "space_chars", "alpha_chars", "digit_chars", "upper_chars", "punct_chars", "words", "text_words",
+                   "text_word_chars", "alpha_words", "stop_words", "hashes", "ellipses", "newlines", "lines", "bullet_lines", "ellipsis_lines",
+                   "terminal_lines", "short_lines", "dup_lines", "dup_line_chars")
+QUALITY_RULES = ("min_text_words", "max_text_words", "min_mean_word_x1000", "max_mean_word_x1000", "max_hash_per_word", "max_ellipsis_per_word",
+                 "max_bullet_lines", "max_ellipsis_lines", "min_alpha_words", "min_stop_words", "max_dup_lines", "max_dup_line_chars",
+                 "min_terminal_lines", "max_short_lines", "max_newlines_per_word", "reserved")
+_QUALITY_PRESETS = {
+    # the thresholds of the MassiveText (Gopher) quality and repetition filters, over this library's words and lines
+    "gopher": dict(min_text_words=50, max_text_words=100000, min_mean_word_x1000=3000, max_mean_word_x1000=10000, max_hash_per_word=100,
+                   max_ellipsis_per_word=100, max_bullet_lines=900, max_ellipsis_lines=300, min_alpha_words=800, min_stop_words=2,
+                   max_dup_lines=300, max_dup_line_chars=200, stop_words=("the", "be", "to", "of", "and", "that", "have", "with")),
+    # the thresholds of FineWeb's custom filters
+    "fineweb": dict(min_terminal_lines=120, max_short_lines=670, max_dup_line_chars=10, max_newlines_per_word=300),
+}
+
+
+def quality_rules(name):
+    """The rules of a published pipeline as keyword arguments of the quality calls: "gopher" or "fineweb".  They are those
+    papers' thresholds over THIS library's words and lines; parity with another tokeniser's word count is not claimed."""
+    if name not in _QUALITY_PRESETS:
+        raise WordPieceError("quality: no such preset: %r (known: %s)" % (name, ", ".join(sorted(_QUALITY_PRESETS))))
+    return dict(_QUALITY_PRESETS[name])
+
+
+class QualitySpec(C.Structure):
+    """wp_quality_spec: the arguments of a quality call (want: WP_QUALITY_WANT_*; limit: -1 or the threshold of rule r)."""
+    _fields_ = [("elem_bytes", C.c_int32), ("want", C.c_int32), ("short_line_chars", C.c_int32), ("n_stop_words", C.c_int32),
+                ("stop_pool", C.c_void_p), ("stop_off", C.c_void_p), ("limit", C.c_int64 * 16), ("reserved", C.c_int64)]
+
+
+class QualityResult(C.Structure):
+    """wp_quality_result: the arrays of a quality call (host blocks, or device memory owned by the handle)."""
+    _fields_ = [("signals", C.c_void_p), ("row_off", C.c_void_p), ("reasons", C.c_void_p), ("kept", C.c_void_p), ("data", C.c_void_p),
+                ("n_rows", C.c_int64), ("n_kept", C.c_int64), ("n_elems", C.c_int64)]
+
+
+class QualityStats(C.Structure):
+    """wp_quality_stats: the statistics of the last quality call (Vocab.quality_stats())."""
+    _fields_ = [("n_rows", C.c_int64), ("n_bytes", C.c_int64), ("n_chars", C.c_int64), ("n_invalid", C.c_int64), ("n_words", C.c_int64),
+                ("n_lines", C.c_int64), ("n_dup_lines", C.c_int64), ("n_kept", C.c_int64), ("rule_failed", C.c_int64 * 16)]
+
+
 def lsh_min_agree(threshold, n_perm):
     """The min_agree that stands for a Jaccard threshold: ceil(threshold * n_perm) signature slots."""
     return int(math.ceil(threshold * n_perm))
@@ -478,6 +524,12 @@ def lib():
             L.wp_repeat_rows.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(RepeatSpec), C.POINTER(RepeatResult)]
             L.wp_repeat_rows_device.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(RepeatSpec), C.POINTER(RepeatResult)]
             L.wp_get_repeat_stats.argtypes = [vp, C.POINTER(RepeatStats)]
+        if hasattr(L, "wp_quality_rows"):  # (WP_LIB, as above)
+            L.wp_quality_rows.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(QualitySpec), C.POINTER(QualityResult)]
+            L.wp_quality_rows_device.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(QualitySpec), C.POINTER(QualityResult)]
+            L.wp_get_quality_stats.argtypes = [vp, C.POINTER(QualityStats)]
+            L.wp_quality_class.argtypes = [C.c_uint32]
+            L.wp_quality_class.restype = C.c_int32
         L.wp_linear_encode_multi.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.POINTER(i32p),
                                              C.POINTER(C.c_size_t)]
         L.wp_reserve.argtypes = [vp, C.c_size_t]
@@ -1745,6 +1797,104 @@ class Vocab:
                 b = b[:-1]
             out.append(b.decode("utf8") if isinstance(d, str) else b)
         return out, r["covered"]
+
+    def quality_stats(self):
+        """wp_quality_stats of the last quality call as a dict (n_rows -1: no such call yet; rule_failed: a list by rule)."""
+        s = QualityStats()
+        _check(lib().wp_get_quality_stats(self._h, C.byref(s)))
+        return {k: (list(getattr(s, k)) if k == "rule_failed" else int(getattr(s, k))) for k, _ in s._fields_}
+
+    @staticmethod
+    def _quality_spec(rules, stop_words, short_line_chars, dup_lines, compact):
+        """-> (QualitySpec, what it points into).  rules: {rule name: threshold}, and "stop_words" among them as a preset has it"""
+        rules = quality_rules(rules) if isinstance(rules, str) else dict(rules or {})
+        if "stop_words" in rules:
+            preset_stop = rules.pop("stop_words")
+            stop_words = preset_stop if stop_words is None else stop_words
+        limit = [-1] * len(QUALITY_RULES)
+        for name, value in rules.items():
+            if name not in QUALITY_RULES or name == "reserved":
+                raise WordPieceError("quality: no such rule: %r" % (name,))
+            limit[QUALITY_RULES.index(name)] = int(value)
+        if dup_lines is None:  # (on where a rule needs it)
+            dup_lines = limit[10] >= 0 or limit[11] >= 0
+        words = [_bytes(w) for w in (stop_words or ())]
+        pool = np.frombuffer(b"".join(words) + b"\0", dtype=np.uint8)
+        off = np.zeros(len(words) + 1, dtype=np.int64)
+        if words:
+            off[1:] = np.cumsum([len(w) for w in words])
+        want = (WP_QUALITY_WANT_DUP_LINES if dup_lines else 0) | (WP_QUALITY_WANT_COMPACT if compact else 0)
+        spec = QualitySpec(1, want, int(short_line_chars), len(words), pool.ctypes.data if words else None, off.ctypes.data if words else None,
+                           (C.c_int64 * 16)(*limit), 0)
+        return spec, (pool, off)
+
+    def quality_rows(self, data, row_off, rules=None, stop_words=None, short_line_chars=0, dup_lines=None, compact=False, raw=False):
+        """The quality signals of every row of a ragged batch of text and the rules over them, on the device, exactly
+        (wp_quality_rows).  data / row_off: the batch as dedup_rows takes it (offsets None: the lines of a text).  rules:
+        {name of QUALITY_RULES: threshold} (quality_rules("gopher") is such a dict); stop_words: at most 64 lower-case
+        words; short_line_chars (0: 30); dup_lines (None: on where a rule needs it): the duplicate-line signals.  ->
+        {"signals": np.int64 [23, n_rows] (rows of QUALITY_SIGNALS), "reasons": np.uint32 [n_rows] (bit r: rule r
+        failed)}, with compact "kept": np.int32 (the rows that failed no rule) and their "data" and "row_off" back to
+        back.  raw: the data comes back as np.uint8 rather than bytes."""
+        data, off, n = _ragged_batch("quality", data, row_off)
+        if data.dtype != np.uint8:
+            raise WordPieceError("quality: data must be text")
+        spec, keep = self._quality_spec(rules, stop_words, short_line_chars, dup_lines, compact)
+        out = QualityResult()
+        _check(lib().wp_quality_rows(self._h, data.ctypes.data if data.size else None, off.ctypes.data if n else None, n, C.byref(spec), C.byref(out)))
+        del keep
+        block = _host_block
+        try:
+            res = {"signals": block(out.signals, n * len(QUALITY_SIGNALS), np.int64).reshape(len(QUALITY_SIGNALS), n),
+                   "reasons": block(out.reasons, n, np.uint32)}
+            if compact:
+                kept_data = block(out.data, out.n_elems, np.uint8)
+                res["kept"] = block(out.kept, out.n_kept, np.int32)
+                res["data"] = kept_data if raw else kept_data.tobytes()
+                res["row_off"] = block(out.row_off, out.n_kept + 1, np.int64) if n else np.zeros(1, dtype=np.int64)
+        finally:
+            _free_blocks(out.signals, out.row_off, out.reasons, out.kept, out.data)
+        return res
+
+    def quality_rows_tensor(self, data, row_off, rules=None, stop_words=None, short_line_chars=0, dup_lines=None, compact=False, copy=True):
+        """quality_rows for a batch in tensors on this handle's GPU (wp_quality_rows_device): data uint8, row_off int64 — a
+        joined text and its doc_off, the compact form of another layer.  -> a dict of tensors on that device: "signals"
+        (torch.int64 [23, n_rows]), "reasons" (the uint32 bitmasks as torch.int32), with compact "kept", "data" and
+        "row_off" (what dedup_rows_tensor and, once encoded, pack_sequences_tensor take).  copy=False: views of the
+        library's buffers, valid until the next call on this handle."""
+        import torch
+        if data.dtype != torch.uint8 or row_off.dtype != torch.int64:
+            raise WordPieceError("quality_rows_tensor needs uint8 data and int64 offsets")
+        _flat_device_tensors("quality_rows_tensor", self._device, data, row_off)
+        n = row_off.numel() - 1
+        if n < 0:
+            raise WordPieceError("quality: offsets need n_rows + 1 entries")
+        spec, keep = self._quality_spec(rules, stop_words, short_line_chars, dup_lines, compact)
+        dev = data.device
+        (data, nbytes), = _whole_words(data)
+        out = QualityResult()
+        _check(lib().wp_quality_rows_device(self._h, C.c_void_p(data.data_ptr()) if nbytes else None, C.c_void_p(row_off.data_ptr()), n,
+                                            C.byref(spec), C.byref(out)))
+        del keep
+        view = _DeviceViews(dev, copy)
+        res = {"signals": view(out.signals, n * len(QUALITY_SIGNALS), "<i8", torch.int64).reshape(len(QUALITY_SIGNALS), n),
+               "reasons": view(out.reasons, n, "<i4", torch.int32)}
+        if compact:
+            res["kept"] = view(out.kept, out.n_kept, "<i4", torch.int32)
+            res["data"] = view(out.data, out.n_elems, "|u1", torch.uint8)
+            res["row_off"] = view(out.row_off, out.n_kept + 1, "<i8", torch.int64) if n else torch.zeros(1, dtype=torch.int64, device=dev)
+        return res
+
+    def quality_docs(self, docs, rules=None, stop_words=None, short_line_chars=0):
+        """The documents of a list (str / bytes) that fail none of `rules` -> ([those documents as given], np.uint32
+        reasons of every document of docs); through quality_rows over the documents back to back (no byte is added)."""
+        docs = list(docs)
+        bs = [_bytes(d) for d in docs]
+        off = np.zeros(len(bs) + 1, dtype=np.int64)
+        if bs:
+            off[1:] = np.cumsum([len(b) for b in bs])
+        r = self.quality_rows(b"".join(bs), off, rules=rules, stop_words=stop_words, short_line_chars=short_line_chars)
+        return [d for d, x in zip(docs, r["reasons"]) if x == 0], r["reasons"]
 
     def align_stats(self):
         """wp_align_stats of the last call as a dict (n_rows -1: it was no align call)."""

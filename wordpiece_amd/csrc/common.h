@@ -61,7 +61,8 @@ enum BoundSite {
   // the kernels that more than one grouping layer runs: the stores of the run heads, the compacted lists, the table and
   // the compact form, the gathers behind them (group.h); read by the end check of every such layer (group_path.h)
   kSiteGroup = 21,
-  kBoundSites = 22
+  kSiteQuality = 22,  // quality signals: the gathers of the class pass, the stores of the word and line lists, the sums per row (quality.h)
+  kBoundSites = 23
 };
 #ifdef WP_DEBUG_BOUNDS
 __device__ unsigned int g_wp_oob[kBoundSites];

@@ -1,6 +1,6 @@
 // context.h — what a vocabulary handle owns on a device: streams, vocabulary tables, bump arenas, the pool of parked
 // contexts (the C ABI itself is in encoder.hip; the device path in linear_path.h and fast_path.h, the layers on top of
-// it in rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h and repeat_path.h).
+// it in rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h and quality_path.h).
 #pragma once
 #include <array>
 #include <cstring>
@@ -155,7 +155,7 @@ static int bit_length(uint64_t v) {
 // c->d_scalars: kScalars 32-bit words that kernels and scans leave their totals in; c->h_scalars: the pinned mirror the
 // host reads them from.  Every word has a name here and nowhere else; no call site names a number.  An encode clears
 // the whole block when it starts (and the pre-pass of WP_OPT_NORMALIZE in front of it does the same, see below).
-constexpr int kScalars = 194;
+constexpr int kScalars = 252;
 constexpr int kScalarCps = 0;       // code points of the text, 32 bits: the decode scan (linear, fast) -> host
 constexpr int kScalarAlphabet = 1;  // alphabet size: alphabet_prefix_kernel -> host
 constexpr int kScalarInvalid = 2;   // invalid sequences, 64 bits (words 2, 3): decode_count_kernel / norm_count_kernel -> host
@@ -235,6 +235,11 @@ constexpr int kScalarOvlCovered = 162, kScalarOvlKept = 163, kScalarOvlOutBytes 
 constexpr int kScalarRepBad = 174, kScalarRepRuns = 175, kScalarRepElems = 176, kScalarRepWindows = 178, kScalarRepListed = 180;
 constexpr int kScalarRepDistinct = 181, kScalarRepRepeats = 182, kScalarRepCovered = 183, kScalarRepKept = 184, kScalarRepOutBytes = 185;
 constexpr int kScalarRep = 186;
+// quality signals (quality.h): the first bad row (~0: none) / the kept rows / row_off[n_rows], 64 bits (words 196, 197) /
+// what the shared row kernel counts as windows, 64 bits (words 198, 199: the bytes again, not read) / the words / the
+// lines / the bytes of the compact form / a free word / the 64-bit counters of a call (words 204..251, QualCounter)
+constexpr int kScalarQualBad = 194, kScalarQualKept = 195, kScalarQualElems = 196, kScalarQualWindows = 198, kScalarQualWords = 200;
+constexpr int kScalarQualLines = 201, kScalarQualOutBytes = 202, kScalarFree203 = 203, kScalarQual = 204;
 // normalize_on_device runs in front of the encode, which clears the block again: while it runs, four slots mean
 constexpr int kScalarNormBytes = kScalarCps;           // bytes of the normalised text, 32 bits: its scan
 constexpr int kScalarNormCps = kScalarAlphabet;        // code points of the normalised text (offsets mode) -> host
@@ -273,7 +278,10 @@ constexpr ScalarRange kScalarLayout[] = {
     {kScalarOvlOutBytes, 1}, {kScalarFree165, 1},     {kScalarOvl, 8},
     {kScalarRepBad, 1},      {kScalarRepRuns, 1},     {kScalarRepElems, 2},       {kScalarRepWindows, 2},
     {kScalarRepListed, 1},   {kScalarRepDistinct, 1}, {kScalarRepRepeats, 1},     {kScalarRepCovered, 1},
-    {kScalarRepKept, 1},     {kScalarRepOutBytes, 1}, {kScalarRep, 8}};
+    {kScalarRepKept, 1},     {kScalarRepOutBytes, 1}, {kScalarRep, 8},
+    {kScalarQualBad, 1},     {kScalarQualKept, 1},    {kScalarQualElems, 2},      {kScalarQualWindows, 2},
+    {kScalarQualWords, 1},   {kScalarQualLines, 1},   {kScalarQualOutBytes, 1},   {kScalarFree203, 1},
+    {kScalarQual, 48}};
 // one past the last word of the range `slot` lies in: where a download or a clear "through" that slot ends
 constexpr int scalar_end(int slot) {
   for (const ScalarRange &r : kScalarLayout) {
@@ -392,6 +400,12 @@ struct Context {
   // first_src_row, first_src_pos and covered of the last call), the per-element and per-window arrays (with mask and
   // src), and the cut and the compact form of the last call
   DeviceBuffer repeat_in, repeat_rows, repeat_items, repeat_out;
+  // quality signals (quality.h): the data and the offsets of a host call, the per-row arrays (with signals and reasons
+  // of the last call), the tile counts and the stop table, the per-word and per-line lists with the arrays of the
+  // duplicate-line stage, and the compact form of the last call; the class table (uploaded with the first quality call)
+  DeviceBuffer quality_in, quality_rows, quality_items, quality_lists, quality_out;
+  uint16_t *d_class_index = nullptr;
+  uint8_t *d_class_pages = nullptr;
   // WP_OPT_NORMALIZE (normalize.h): the tables (uploaded with the first normalising call), the normalised text, the
   // tile counts of the pre-pass, and the source of every normalised code point (offsets mode)
   uint16_t *d_norm_index = nullptr;
@@ -435,14 +449,15 @@ struct Context {
     size_t n = 0, n_text = 0;
   } dbg;
   // every DeviceBuffer above, for destroy_context, release_arenas and park_context: a new buffer is one more name here
-  std::array<DeviceBuffer *, 49> buffers() {
+  std::array<DeviceBuffer *, 54> buffers() {
     return {&text_buf, &a_buf,    &b_buf,   &fmt_buf,    &text_buf2, &ids_stage[0], &ids_stage[1], &rows_in,   &rows_out,
             &pad_buf,  &inputs_buf, &norm_buf, &norm_aux, &norm_map, &detok_in,     &detok_aux,    &detok_out,
             &pack_in,  &pack_plan,  &pack_tab, &pack_out, &special_text, &special_in, &special_lit, &special_out,
             &count_aux, &count_words, &count_out, &learn_in, &learn_aux, &learn_items, &learn_groups, &learn_out,
             &dedup_in, &dedup_rows, &dedup_out, &neardup_in, &neardup_rows, &neardup_items, &neardup_out,
             &overlap_in, &overlap_ref_in, &overlap_rows, &overlap_items, &overlap_out,
-            &repeat_in, &repeat_rows, &repeat_items, &repeat_out};
+            &repeat_in, &repeat_rows, &repeat_items, &repeat_out,
+            &quality_in, &quality_rows, &quality_items, &quality_lists, &quality_out};
   }
   Context() = default;
   Context(const Context &) = delete;
@@ -524,6 +539,8 @@ struct EncodeStats : wp_stats {
   int32_t overlap_call;
   wp_repeat_stats repeat;  // wp_get_repeat_stats: filled by a repeat call (repeat_call 1), zero otherwise
   int32_t repeat_call;
+  wp_quality_stats quality;  // wp_get_quality_stats: filled by a quality call (quality_call 1), zero otherwise
+  int32_t quality_call;
 };
 
 #ifndef WP_LATE_REFINE_DEFAULT
@@ -586,7 +603,8 @@ static void destroy_context(Context *c) {
   (void)hipSetDevice(c->device);
   free_vocab_tables(c);
   // the tables of the context itself: they stay while it is parked
-  free_dev(c->d_used, c->d_lut, c->d_scan_tmp, c->d_scalars, c->d_code, c->d_symhist, c->d_norm_index, c->d_norm_pages, c->d_norm_pool);
+  free_dev(c->d_used, c->d_lut, c->d_scan_tmp, c->d_scalars, c->d_code, c->d_symhist, c->d_norm_index, c->d_norm_pages, c->d_norm_pool, c->d_class_index,
+           c->d_class_pages);
   if (c->h_scalars) (void)hipHostFree(c->h_scalars);
   if (c->h_code) (void)hipHostFree(c->h_code);
   c->h_scalars = nullptr;

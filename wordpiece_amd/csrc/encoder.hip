@@ -2,7 +2,7 @@
 // device code is compiled in: the entry points (out-pointers, the answers that need no device, uploads and downloads),
 // the pinned pool, the multi-GPU, batch, stream, file and external calls.  The device path itself: linear_path.h
 // (word_piece::linear, stage by stage) and fast_path.h (word_piece::fast); the layers on top of it, one host header
-// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h; what a handle owns
+// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h, quality_path.h; what a handle owns
 // on a device: context.h.
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -34,6 +34,7 @@
 #include "mask_path.h"
 #include "neardup_path.h"
 #include "overlap_path.h"
+#include "quality_path.h"
 #include "repeat_path.h"
 #include "pack_path.h"
 #include "rows_path.h"
@@ -1667,6 +1668,64 @@ int wp_repeat_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row_
       return;
     }
     repeat_on_device(v, get_context(v), in, plan, d_out);
+  });
+}
+
+}  // extern "C"
+
+// ---- quality signals (include/wordpiece_amd.h, section "quality signals"; host path: quality_path.h) -------------------
+extern "C" {
+
+int wp_get_quality_stats(const wp_vocab *v, wp_quality_stats *out) {
+  *out = v->stats.quality;
+  if (!v->stats.quality_call) out->n_rows = -1;
+  return WP_OK;
+}
+
+int32_t wp_quality_class(uint32_t cp) {
+  if (cp >= 0x110000u || (cp >= 0xd800u && cp < 0xe000u)) return -1;
+  return quality_class_bits(cp, kClassIndex, kClassPageData) >> 3;
+}
+
+int wp_quality_rows(wp_vocab *v, const void *data, const int64_t *row_off, size_t n_rows, const wp_quality_spec *spec, wp_quality_result *out) {
+  return guarded([&] {
+    if (out) *out = wp_quality_result{};
+    const QualityPlan plan = check_quality_spec(spec, out);
+    check_quality_rows(row_off, n_rows);
+    const unsigned long long n_bytes = check_ragged_host("quality", data, row_off, n_rows, 1);
+    if (n_rows == 0) {  // (nothing to hand out: every pointer of the result stays NULL)
+      begin_quality_stats(v, 0);
+      return;
+    }
+    if (n_bytes == 0) {
+      *out = quality_no_bytes(v, plan, n_rows);
+      return;
+    }
+    Context *c = get_context(v);
+    const RaggedIn in = upload_ragged(c->quality_in, c->stream, data, row_off, n_rows, static_cast<size_t>(n_bytes), 1);
+    wp_quality_result d;
+    quality_on_device(v, c, in, plan, &d);
+    wp_quality_result h = d;
+    Downloads down(c->stream);
+    down.swap(&h.signals, n_rows * WP_QUALITY_SIGNALS * sizeof(int64_t));
+    down.swap(&h.reasons, n_rows * sizeof(uint32_t));
+    swap_compact(down, h, h.n_kept, 1);
+    down.finish();
+    *out = h;
+  });
+}
+
+int wp_quality_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row_off, size_t n_rows, const wp_quality_spec *spec, wp_quality_result *d_out) {
+  return guarded([&] {
+    if (d_out) *d_out = wp_quality_result{};
+    const QualityPlan plan = check_quality_spec(spec, d_out);
+    check_quality_rows(d_row_off, n_rows);
+    const RaggedIn in = device_batch("quality", d_data, d_row_off, n_rows, 1);
+    if (n_rows == 0) {  // (nothing to read and nothing to hand out: every pointer of the result stays NULL)
+      begin_quality_stats(v, 0);
+      return;
+    }
+    quality_on_device(v, get_context(v), in, plan, d_out);
   });
 }
 

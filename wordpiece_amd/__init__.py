@@ -410,6 +410,46 @@ def lsh_min_agree(threshold, n_perm):
     return int(math.ceil(threshold * n_perm))
 
 
+# ---- the corpus layers as data ("The Python side of a corpus layer") -------------------------------------------
+_BATCH = [C.c_void_p, C.c_void_p, C.c_size_t]  # data, offsets, n_rows
+# layer: (host entry point ("_device": its twin), Spec, Result, Stats, what stands between the handle and the spec: host, device)
+_CORPUS_LAYERS = {
+    "count": ("wp_count_words", CountSpec, WordCounts, CountStats, [C.c_char_p, C.c_size_t], [C.c_void_p, C.c_size_t]),
+    "learn": ("wp_learn_vocab", LearnSpec, LearnedVocab, LearnStats, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t],
+              [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "dedup": ("wp_dedup_rows", DedupSpec, DedupResult, DedupStats, _BATCH, _BATCH),
+    "neardup": ("wp_neardup_rows", NearDupSpec, NearDupResult, NearDupStats, _BATCH, _BATCH),
+    "overlap": ("wp_overlap_rows", OverlapSpec, OverlapResult, OverlapStats, _BATCH * 2, _BATCH * 2),
+    "repeat": ("wp_repeat_rows", RepeatSpec, RepeatResult, RepeatStats, _BATCH, _BATCH),
+    "quality": ("wp_quality_rows", QualitySpec, QualityResult, QualityStats, _BATCH, _BATCH),
+}
+# element kind: (numpy dtype of a host result, typestr and torch dtype of a device result)
+_KINDS = {"u8": (np.uint8, "|u1", "uint8"), "i32": (np.int32, "<i4", "int32"), "i64": (np.int64, "<i8", "int64"),
+          "u32": (np.uint32, "<i4", "int32")}  # (torch has no uint32 arithmetic: the device form gives the bit patterns as int32)
+# The arrays of a layer's result, in the order of the dict: (key = field of the Result struct, element kind, shape, the
+# keyword that switches it on).  Kinds beside _KINDS: "elem", the batch's own, and "off", int64 offsets with one entry
+# more than the shape says.  A size is a count field of the struct, or "rows" / "ref" (the rows of the batch / of the
+# reference), "elems" (the elements of the batch), "n_perm", "n_signals".
+_RESULTS = {
+    "count": (("words", "u8", ("n_bytes",), None), ("word_off", "off", ("n_distinct",), None), ("counts", "i64", ("n_distinct",), None),
+              ("word_index", "i32", ("n_words",), "index")),
+    "learn": (("tokens", "u8", ("n_bytes",), None), ("token_off", "off", ("n_tokens",), None), ("scores", "i64", ("n_tokens",), None)),
+    "dedup": (("first", "i32", ("rows",), None), ("kept", "i32", ("n_unique",), None), ("counts", "i64", ("n_unique",), None),
+              ("inverse", "i32", ("rows",), "inverse"), ("data", "elem", ("n_elems",), "compact"), ("row_off", "off", ("n_unique",), "compact")),
+    "neardup": (("cluster", "i32", ("rows",), None), ("kept", "i32", ("n_unique",), None), ("counts", "i64", ("n_unique",), None),
+                ("inverse", "i32", ("rows",), "inverse"), ("data", "elem", ("n_elems",), "compact"), ("row_off", "off", ("n_unique",), "compact"),
+                ("signatures", "u32", ("rows", "n_perm"), "signatures")),
+    "overlap": (("hits", "i64", ("rows",), None), ("first_hit", "i64", ("rows",), None), ("first_ref", "i32", ("rows",), None),
+                ("covered", "i64", ("rows",), None), ("mask", "u8", ("elems",), "mask"), ("ref_hits", "i64", ("ref",), "ref"),
+                ("kept", "i32", ("n_kept",), "compact"), ("data", "elem", ("n_elems",), "compact"), ("row_off", "off", ("n_kept",), "compact")),
+    "repeat": (("repeats", "i64", ("rows",), None), ("first_repeat", "i64", ("rows",), None), ("first_src_row", "i32", ("rows",), None),
+               ("first_src_pos", "i64", ("rows",), None), ("covered", "i64", ("rows",), None), ("mask", "u8", ("elems",), "mask"),
+               ("src", "i64", ("elems",), "src"), ("kept", "i32", ("n_kept",), "compact"), ("data", "elem", ("n_elems",), "compact"),
+               ("row_off", "off", ("n_kept",), "compact"), ("cut_data", "elem", ("n_cut_elems",), "cut"), ("cut_off", "off", ("rows",), "cut")),
+    "quality": (("signals", "i64", ("n_signals", "rows"), None), ("reasons", "u32", ("rows",), None), ("kept", "i32", ("n_kept",), "compact"),
+                ("data", "elem", ("n_elems",), "compact"), ("row_off", "off", ("n_kept",), "compact")),
+}
+
 _TEXT_SOURCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t))
 _IDS_SINK = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.c_size_t)
 
@@ -500,34 +540,12 @@ def lib():
                                         C.POINTER(i32p)]
             L.wp_align_rows_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, vp, C.c_size_t, ap, vp, vp]
             L.wp_get_align_stats.argtypes = [vp, C.POINTER(AlignStats)]
-        if hasattr(L, "wp_count_words"):  # (WP_LIB, as above)
-            L.wp_count_words.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(CountSpec), C.POINTER(WordCounts)]
-            L.wp_count_words_device.argtypes = [vp, vp, C.c_size_t, C.POINTER(CountSpec), C.POINTER(WordCounts)]
-            L.wp_get_count_stats.argtypes = [vp, C.POINTER(CountStats)]
-        if hasattr(L, "wp_learn_vocab"):  # (WP_LIB, as above)
-            L.wp_learn_vocab.argtypes = [vp, vp, vp, vp, C.c_size_t, C.POINTER(LearnSpec), C.POINTER(LearnedVocab)]
-            L.wp_learn_vocab_device.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(LearnSpec), C.POINTER(LearnedVocab)]
-            L.wp_get_learn_stats.argtypes = [vp, C.POINTER(LearnStats)]
-        if hasattr(L, "wp_dedup_rows"):  # (WP_LIB, as above)
-            L.wp_dedup_rows.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(DedupSpec), C.POINTER(DedupResult)]
-            L.wp_dedup_rows_device.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(DedupSpec), C.POINTER(DedupResult)]
-            L.wp_get_dedup_stats.argtypes = [vp, C.POINTER(DedupStats)]
-        if hasattr(L, "wp_neardup_rows"):  # (WP_LIB, as above)
-            L.wp_neardup_rows.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(NearDupSpec), C.POINTER(NearDupResult)]
-            L.wp_neardup_rows_device.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(NearDupSpec), C.POINTER(NearDupResult)]
-            L.wp_get_neardup_stats.argtypes = [vp, C.POINTER(NearDupStats)]
-        if hasattr(L, "wp_overlap_rows"):  # (WP_LIB, as above)
-            L.wp_overlap_rows.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(OverlapSpec), C.POINTER(OverlapResult)]
-            L.wp_overlap_rows_device.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(OverlapSpec), C.POINTER(OverlapResult)]
-            L.wp_get_overlap_stats.argtypes = [vp, C.POINTER(OverlapStats)]
-        if hasattr(L, "wp_repeat_rows"):  # (WP_LIB, as above)
-            L.wp_repeat_rows.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(RepeatSpec), C.POINTER(RepeatResult)]
-            L.wp_repeat_rows_device.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(RepeatSpec), C.POINTER(RepeatResult)]
-            L.wp_get_repeat_stats.argtypes = [vp, C.POINTER(RepeatStats)]
-        if hasattr(L, "wp_quality_rows"):  # (WP_LIB, as above)
-            L.wp_quality_rows.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(QualitySpec), C.POINTER(QualityResult)]
-            L.wp_quality_rows_device.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(QualitySpec), C.POINTER(QualityResult)]
-            L.wp_get_quality_stats.argtypes = [vp, C.POINTER(QualityStats)]
+        for layer, (fn, spec, result, stats, host_args, device_args) in _CORPUS_LAYERS.items():
+            if hasattr(L, fn):  # (WP_LIB, as above)
+                getattr(L, fn).argtypes = [vp] + host_args + [C.POINTER(spec), C.POINTER(result)]
+                getattr(L, fn + "_device").argtypes = [vp] + device_args + [C.POINTER(spec), C.POINTER(result)]
+                getattr(L, "wp_get_%s_stats" % layer).argtypes = [vp, C.POINTER(stats)]
+        if hasattr(L, "wp_quality_class"):  # (WP_LIB, as above)
             L.wp_quality_class.argtypes = [C.c_uint32]
             L.wp_quality_class.restype = C.c_int32
         L.wp_linear_encode_multi.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.POINTER(i32p),
@@ -584,9 +602,7 @@ class Vocab:
             _check(lib().wp_vocab_from_file(_bytes(file), C.byref(self._h)))
         else:
             ls = [_bytes(w) for w in lines]
-            off = np.zeros(len(ls) + 1, dtype=np.int64)
-            if ls:
-                off[1:] = np.cumsum([len(w) for w in ls])
+            off = _offsets_of([len(w) for w in ls])
             _check(lib().wp_vocab_create_packed(b"".join(ls), off.ctypes.data_as(C.POINTER(C.c_int64)), len(ls),
                                                 C.byref(self._h)))
         self._device = None if device is None else int(device)  # (None: the device that is current at the first call)
@@ -641,12 +657,7 @@ class Vocab:
         import torch
         if text.dtype != torch.uint8 or not text.is_cuda or not text.is_contiguous():
             raise WordPieceError("normalize_tensor needs a contiguous uint8 CUDA/HIP tensor")
-        nbytes = text.numel()
-        if text.data_ptr() % 4 != 0 or nbytes % 4 != 0:  # (as encode_tensor: the decoder reads whole aligned words)
-            padded = torch.zeros((nbytes + 19) // 16 * 16, dtype=torch.uint8, device=text.device)
-            padded[:nbytes] = text
-            text = padded
-        torch.cuda.current_stream(text.device).synchronize()  # the library runs on its own HIP streams
+        (text, nbytes), = _whole_words(text)
         d_out = C.c_void_p()
         n = C.c_size_t()
         _check(lib().wp_normalize_device(self._h, C.c_void_p(text.data_ptr()), nbytes,
@@ -665,33 +676,32 @@ class Vocab:
         d.update({k: getattr(ns, k) for k, _ in ns._fields_})
         return d
 
+    def _stats(self, struct, getter, drop=()):
+        """one of the smaller statistics structs of the last call as a dict (an array field as a list), without `drop`"""
+        s = struct()
+        _check(getattr(lib(), getter)(self._h, C.byref(s)))
+        values = ((k, getattr(s, k)) for k, _ in s._fields_ if k not in drop)
+        return {k: list(x) if isinstance(x, C.Array) else x for k, x in values}
+
     def walk_stats(self):
         """wp_walk_stats of the last encode (Linear or fast) as a dict: n_wide_words, n_long_words, lean,
         max_anchor_gap."""
-        ws = WalkStats()
-        _check(lib().wp_get_walk_stats(self._h, C.byref(ws)))
-        return {k: int(getattr(ws, k)) for k, _ in ws._fields_}
+        return self._stats(WalkStats, "wp_get_walk_stats")
 
     def refine_stats(self):
         """wp_refine_stats of the last encode as a dict: n_groups, n_entries, n_large_groups, n_large_entries,
         trie_nodes, sort_bits, key_lookup, symbol_bytes."""
-        rs = RefineStats()
-        _check(lib().wp_get_refine_stats(self._h, C.byref(rs)))
-        return {k: int(getattr(rs, k)) for k, _ in rs._fields_ if k != "reserved"}
+        return self._stats(RefineStats, "wp_get_refine_stats", drop=("reserved",))
 
     def refine_sched(self):
         """wp_refine_sched of the last encode as a dict: early (1: the refinement ran beside the round-0 passes),
         ms_sort_to_scan (WP_OPT_STAGE_TIMING: last round-0 pass to the scanline stage, in ms)."""
-        rs = RefineSched()
-        _check(lib().wp_get_refine_sched(self._h, C.byref(rs)))
-        return {"early": int(rs.early), "ms_sort_to_scan": float(rs.ms_sort_to_scan)}
+        return self._stats(RefineSched, "wp_get_refine_sched", drop=("reserved",))
 
     def step_stats(self):
         """wp_step_stats of the last encode as a dict: n_marks, n_steps, n_tiles, n_groups_of_tiles, bucket_shift,
         bucket_shift_all, key_shift, key_shift_all, packed, key_lookup."""
-        ss = StepStats()
-        _check(lib().wp_get_step_stats(self._h, C.byref(ss)))
-        return {k: int(getattr(ss, k)) for k, _ in ss._fields_}
+        return self._stats(StepStats, "wp_get_step_stats")
 
     def encode(self, text):
         """Host UTF-8 bytes/str -> numpy int32 ids (wp_linear_encode)."""
@@ -760,17 +770,12 @@ class Vocab:
         import torch
         if text.dtype != torch.uint8 or not text.is_cuda or not text.is_contiguous():
             raise WordPieceError("a documents call on tensors needs a contiguous uint8 CUDA/HIP text tensor")
-        nbytes = text.numel()
-        if text.data_ptr() % 4 != 0 or nbytes % 4 != 0:  # (as encode_tensor: the decoder reads whole aligned words)
-            padded = torch.zeros((nbytes + 19) // 16 * 16, dtype=torch.uint8, device=text.device)
-            padded[:nbytes] = text
-            text = padded
         if doc_offsets is not None:
             if doc_offsets.dtype != torch.int64 or doc_offsets.device != text.device or doc_offsets.dim() != 1 or \
                     doc_offsets.numel() < 1:
                 raise WordPieceError("doc_offsets must be a 1-d int64 tensor on the text's device")
             doc_offsets = doc_offsets.contiguous()
-        torch.cuda.current_stream(text.device).synchronize()  # the library runs on its own HIP streams
+        (text, nbytes), = _whole_words(text)  # (last: it waits for torch's stream, the copy above included)
         return text, nbytes, doc_offsets
 
     def encode_rows_tensor(self, text, doc_offsets=None, offsets=None, copy=True):
@@ -833,9 +838,7 @@ class Vocab:
 
     def inputs_stats(self):
         """wp_inputs_stats of the last call as a dict (n_out -1: it was no inputs call)."""
-        s = InputsStats()
-        _check(lib().wp_get_inputs_stats(self._h, C.byref(s)))
-        return {k: int(getattr(s, k)) for k, _ in s._fields_ if k != "reserved"}
+        return self._stats(InputsStats, "wp_get_inputs_stats", drop=("reserved",))
 
     def encode_inputs(self, a=None, b=None, text=None, doc_offsets=None, pairs=None, max_len=128, cls_id=None, sep_id=None,
                       pad_id=0, truncation="longest_first", stride=None, offsets=None):
@@ -937,9 +940,7 @@ class Vocab:
 
     def mask_stats(self):
         """wp_mask_stats of the last call as a dict (n_rows -1: it was no mask or word-ids call)."""
-        s = MaskStats()
-        _check(lib().wp_get_mask_stats(self._h, C.byref(s)))
-        return {k: int(getattr(s, k)) for k, _ in s._fields_ if k != "reserved"}
+        return self._stats(MaskStats, "wp_get_mask_stats", drop=("reserved",))
 
     def word_ids(self, input_ids, lengths=None, cls_id=None, sep_id=None, pad_id=None):
         """The word index of every cell of an id batch (wp_word_ids): input_ids int32 [n_rows, max_len] (and lengths
@@ -1025,9 +1026,7 @@ class Vocab:
 
     def detok_stats(self):
         """wp_detok_stats of the last detokenize call as a dict (n_rows -1: no such call yet)."""
-        s = DetokStats()
-        _check(lib().wp_get_detok_stats(self._h, C.byref(s)))
-        return {k: int(getattr(s, k)) for k, _ in s._fields_}
+        return self._stats(DetokStats, "wp_get_detok_stats")
 
     def detok_piece(self, id, form, cleanup=True):
         """The bytes id `id` contributes to a row's text (wp_detok_piece; no GPU needed): form 0 as the first kept
@@ -1133,9 +1132,7 @@ class Vocab:
 
     def pack_stats(self):
         """wp_pack_stats of the last pack call as a dict (n_docs -1: no such call yet)."""
-        s = PackStats()
-        _check(lib().wp_get_pack_stats(self._h, C.byref(s)))
-        return {k: int(getattr(s, k)) for k, _ in s._fields_}
+        return self._stats(PackStats, "wp_get_pack_stats")
 
     def pack_sequences(self, ids, row_splits, max_len=128, mode="next_fit", bos_id=None, eos_id=None, pad_id=0,
                        long_docs="truncate", want=("segment_ids", "position_ids", "source")):
@@ -1233,25 +1230,14 @@ class Vocab:
 
     def count_stats(self):
         """wp_count_stats of the last count call as a dict (n_words -1: no such call yet)."""
-        s = CountStats()
-        _check(lib().wp_get_count_stats(self._h, C.byref(s)))
-        return {k: int(getattr(s, k)) for k, _ in s._fields_}
+        return self._stats(CountStats, "wp_get_count_stats")
 
     @staticmethod
     def _count_spec(order, min_count, max_word_bytes, terminator, index, hash_bits):
         if order not in _COUNT_ORDERS:
             raise WordPieceError("count: order must be 'first' or 'count'")
-        if terminator is None:
-            term = -1
-        elif isinstance(terminator, int):
-            term = terminator
-        else:
-            t = _bytes(terminator)
-            if len(t) != 1:
-                raise WordPieceError("count: terminator must be one byte")
-            term = t[0]
-        return CountSpec(_COUNT_ORDERS[order], int(max_word_bytes), term, WP_COUNT_WANT_INDEX if index else 0, int(hash_bits), 0,
-                         int(min_count))
+        return CountSpec(_COUNT_ORDERS[order], int(max_word_bytes), _terminator_byte("count", terminator), WP_COUNT_WANT_INDEX if index else 0,
+                         int(hash_bits), 0, int(min_count))
 
     def count_words(self, text, order="first", min_count=1, max_word_bytes=256, terminator=None, index=False, raw=False,
                     hash_bits=0):
@@ -1264,27 +1250,10 @@ class Vocab:
         spec = self._count_spec(order, min_count, max_word_bytes, terminator, index, hash_bits)
         out = WordCounts()
         _check(lib().wp_count_words(self._h, b, len(b), C.byref(spec), C.byref(out)))
-        try:
-            n = out.n_distinct
-            pool = np.ctypeslib.as_array(C.cast(out.words, C.POINTER(C.c_uint8)), (out.n_bytes,)).copy() if out.n_bytes else \
-                np.zeros(0, dtype=np.uint8)
-            off = np.ctypeslib.as_array(C.cast(out.word_off, C.POINTER(C.c_int64)), (n + 1,)).copy()
-            counts = np.ctypeslib.as_array(C.cast(out.counts, C.POINTER(C.c_int64)), (n,)).copy() if n else np.zeros(0, dtype=np.int64)
-            widx = None
-            if index:
-                widx = np.ctypeslib.as_array(C.cast(out.word_index, C.POINTER(C.c_int32)), (out.n_words,)).copy() if out.n_words else \
-                    np.zeros(0, dtype=np.int32)
-        finally:
-            for blk in (out.words, out.word_off, out.counts, out.word_index):
-                if blk:
-                    lib().wp_free(blk)
-        if raw:
-            res = {"words": pool, "word_off": off, "counts": counts}
-        else:
-            data, cut = pool.tobytes(), 1 if spec.terminator >= 0 else 0
-            res = {"words": [data[off[k]:off[k + 1] - cut].decode("utf8") for k in range(n)], "counts": counts}
-        if index:
-            res["word_index"] = widx
+        res = _host_result("count", out, dict(index=index))
+        if not raw:
+            data, off, cut = res["words"].tobytes(), res.pop("word_off"), 1 if spec.terminator >= 0 else 0
+            res["words"] = [data[off[k]:off[k + 1] - cut].decode("utf8") for k in range(len(off) - 1)]
         return res
 
     def count_words_tensor(self, text, order="first", min_count=1, max_word_bytes=256, terminator=None, index=False, copy=True,
@@ -1296,56 +1265,27 @@ class Vocab:
         if text.dtype != torch.uint8 or not text.is_cuda or not text.is_contiguous():
             raise WordPieceError("count_words_tensor needs a contiguous uint8 CUDA/HIP tensor")
         spec = self._count_spec(order, min_count, max_word_bytes, terminator, index, hash_bits)
-        nbytes = text.numel()
-        if text.data_ptr() % 4 != 0 or nbytes % 4 != 0:  # (as encode_tensor: the decoder reads whole aligned words)
-            padded = torch.zeros((nbytes + 19) // 16 * 16, dtype=torch.uint8, device=text.device)
-            padded[:nbytes] = text
-            text = padded
-        dev = text.device
-        torch.cuda.current_stream(dev).synchronize()  # the library runs on its own HIP streams
+        (text, nbytes), = _whole_words(text)
         out = WordCounts()
         _check(lib().wp_count_words_device(self._h, C.c_void_p(text.data_ptr()), nbytes, C.byref(spec), C.byref(out)))
-
-        def view(ptr, n, typestr, dtype):
-            if not n:
-                return torch.zeros(0, dtype=dtype, device=dev)
-            t = torch.as_tensor(DeviceIds(ptr, n, typestr=typestr), device=dev)
-            return t.clone() if copy else t
-        res = {"words": view(out.words, out.n_bytes, "|u1", torch.uint8),
-               "word_off": view(out.word_off, out.n_distinct + 1, "<i8", torch.int64),
-               "counts": view(out.counts, out.n_distinct, "<i8", torch.int64)}
-        if index:
-            res["word_index"] = view(out.word_index, out.n_words, "<i4", torch.int32)
-        return res
+        return _layer_result("count", out, _DeviceViews(text.device, copy), dict(index=index))
 
     def learn_stats(self):
         """wp_learn_stats of the last learn call as a dict (n_words -1: no such call yet)."""
-        s = LearnStats()
-        _check(lib().wp_get_learn_stats(self._h, C.byref(s)))
-        return {k: int(getattr(s, k)) for k, _ in s._fields_}
+        return self._stats(LearnStats, "wp_get_learn_stats")
 
     @staticmethod
     def _learn_spec(vocab_size, reserved, lower_thresh, upper_thresh, num_iterations, max_token_chars, max_unique_chars, slack_ratio,
                     slack, terminator, hash_bits):
         """-> (LearnSpec, what it points into: keep both alive over the call)"""
         res = [_bytes(r) for r in reserved]
-        off = np.zeros(len(res) + 1, dtype=np.int64)
-        if res:
-            off[1:] = np.cumsum([len(r) for r in res])
+        off = _offsets_of([len(r) for r in res])
         pool = b"".join(res)
-        if terminator is None:
-            term = -1
-        elif isinstance(terminator, int):
-            term = terminator
-        else:
-            t = _bytes(terminator)
-            if len(t) != 1:
-                raise WordPieceError("learn: terminator must be one byte")
-            term = t[0]
         if slack is None:
             slack = int(slack_ratio * vocab_size)
         spec = LearnSpec(pool, off.ctypes.data_as(C.POINTER(C.c_int64)), len(res), int(vocab_size), int(lower_thresh), int(upper_thresh),
-                         int(slack), int(num_iterations), int(max_token_chars), int(max_unique_chars), term, int(hash_bits), 0)
+                         int(slack), int(num_iterations), int(max_token_chars), int(max_unique_chars), _terminator_byte("learn", terminator),
+                         int(hash_bits), 0)
         return spec, (pool, off)
 
     def learn_vocab(self, table, vocab_size, reserved=DEFAULT_RESERVED, lower_thresh=10, upper_thresh=10_000_000, num_iterations=4,
@@ -1362,9 +1302,7 @@ class Vocab:
         else:
             ws = [_bytes(w) for w in table["words"]]
             pool = np.frombuffer(b"".join(ws), dtype=np.uint8)
-            off = np.zeros(len(ws) + 1, dtype=np.int64)
-            if ws:
-                off[1:] = np.cumsum([len(w) for w in ws])
+            off = _offsets_of([len(w) for w in ws])
             terminator = None
         n = len(off) - 1
         if n < 0 or len(counts) != n:
@@ -1376,17 +1314,11 @@ class Vocab:
         out = LearnedVocab()
         _check(lib().wp_learn_vocab(self._h, pool.ctypes.data if pool.size else None, off.ctypes.data if n else None,
                                     counts.ctypes.data if n else None, n, C.byref(spec), C.byref(out)))
-        del keep
-        try:
-            k = out.n_tokens
-            data = C.string_at(out.tokens, out.n_bytes) if out.n_bytes else b""
-            toff = np.ctypeslib.as_array(C.cast(out.token_off, C.POINTER(C.c_int64)), (k + 1,)).copy()
-            scores = np.ctypeslib.as_array(C.cast(out.scores, C.POINTER(C.c_int64)), (k,)).copy() if k else np.zeros(0, dtype=np.int64)
-        finally:
-            for blk in (out.tokens, out.token_off, out.scores):
-                if blk:
-                    lib().wp_free(blk)
-        return {"tokens": [data[toff[j]:toff[j + 1] - 1].decode("utf8") for j in range(k)], "scores": scores, "thresh": int(out.thresh)}
+        res = _host_result("learn", out)
+        data, toff = res["tokens"].tobytes(), res.pop("token_off")
+        res["tokens"] = [data[toff[j]:toff[j + 1] - 1].decode("utf8") for j in range(len(toff) - 1)]
+        res["thresh"] = int(out.thresh)
+        return res
 
     def learn_vocab_tensor(self, words, word_off, counts, vocab_size, reserved=DEFAULT_RESERVED, lower_thresh=10, upper_thresh=10_000_000,
                            num_iterations=4, max_token_chars=50, max_unique_chars=1000, slack_ratio=0.05, slack=None, terminator=None,
@@ -1406,28 +1338,47 @@ class Vocab:
             raise WordPieceError("learn: word_off needs one entry more than counts")
         spec, keep = self._learn_spec(vocab_size, reserved, lower_thresh, upper_thresh, num_iterations, max_token_chars, max_unique_chars,
                                       slack_ratio, slack, terminator, hash_bits)
-        dev = words.device
-        torch.cuda.current_stream(dev).synchronize()  # the library runs on its own HIP streams
+        torch.cuda.current_stream(words.device).synchronize()  # the library runs on its own HIP streams
         out = LearnedVocab()
         _check(lib().wp_learn_vocab_device(self._h, C.c_void_p(words.data_ptr()) if words.numel() else None, words.numel(),
                                            C.c_void_p(word_off.data_ptr()), C.c_void_p(counts.data_ptr()) if n else None, n,
                                            C.byref(spec), C.byref(out)))
-        del keep
+        res = _layer_result("learn", out, _DeviceViews(words.device, copy))
+        res["thresh"] = int(out.thresh)
+        return res
 
-        def view(ptr, k, typestr, dtype):
-            if not k:
-                return torch.zeros(0, dtype=dtype, device=dev)
-            t = torch.as_tensor(DeviceIds(ptr, k, typestr=typestr), device=dev)
-            return t.clone() if copy else t
-        return {"tokens": view(out.tokens, out.n_bytes, "|u1", torch.uint8),
-                "token_off": view(out.token_off, out.n_tokens + 1, "<i8", torch.int64),
-                "scores": view(out.scores, out.n_tokens, "<i8", torch.int64), "thresh": int(out.thresh)}
+    def _rows_host(self, layer, spec, batches, on, raw=False, **sizes):
+        """The host form of a ragged-batch layer: its entry point over the batches _ragged_batch returned -> the dict of
+        its arrays (_RESULTS), text as bytes unless raw."""
+        data, off, n = batches[0]
+        out = _CORPUS_LAYERS[layer][2]()
+        args = [a for d, o, k in batches for a in (d.ctypes.data if d.size else None, o.ctypes.data if k else None, k)]
+        _check(getattr(lib(), _CORPUS_LAYERS[layer][0])(self._h, *args, C.byref(spec), C.byref(out)))
+        text = data.dtype == np.uint8
+        res = _host_result(layer, out, on, "u8" if text else "i32", rows=n, ref=batches[-1][-1], elems=int(off[n]) if n else 0, **sizes)
+        if text and not raw:
+            res.update((k, res[k].tobytes()) for k in ("data", "cut_data") if k in res)
+        return res
+
+    def _rows_device(self, layer, spec, batches, on, copy, **sizes):
+        """The tensor form of a ragged-batch layer: its device entry point over the batches _ragged_tensors returned -> the
+        dict of its arrays (_RESULTS) as tensors on the batch's device."""
+        data, nbytes, row_off, n = batches[0]
+        out = _CORPUS_LAYERS[layer][2]()
+        args = [a for d, nb, o, k in batches for a in (C.c_void_p(d.data_ptr()) if nb else None, C.c_void_p(o.data_ptr()), k)]
+        _check(getattr(lib(), _CORPUS_LAYERS[layer][0] + "_device")(self._h, *args, C.byref(spec), C.byref(out)))
+        n_elems = nbytes // data.element_size()
+        return _layer_result(layer, out, _DeviceViews(data.device, copy), on, "u8" if data.element_size() == 1 else "i32", rows=n,
+                             ref=batches[-1][-1], elems=lambda: min(n_elems, int(row_off[n])) if n else 0, **sizes)
 
     def dedup_stats(self):
         """wp_dedup_stats of the last dedup call as a dict (n_rows -1: no such call yet)."""
-        s = DedupStats()
-        _check(lib().wp_get_dedup_stats(self._h, C.byref(s)))
-        return {k: int(getattr(s, k)) for k, _ in s._fields_}
+        return self._stats(DedupStats, "wp_get_dedup_stats")
+
+    @staticmethod
+    def _dedup_spec(elem_bytes, inverse, compact, hash_bits):
+        want = (WP_DEDUP_WANT_INVERSE if inverse else 0) | (WP_DEDUP_WANT_COMPACT if compact else 0)
+        return DedupSpec(elem_bytes, want, int(hash_bits), 0)
 
     def dedup_rows(self, data, row_off=None, inverse=False, compact=False, hash_bits=0, raw=False):
         """The duplicate rows of a ragged batch dropped on the device, exactly (wp_dedup_rows).  data: bytes / str / a
@@ -1437,25 +1388,9 @@ class Vocab:
         np.int64 [n_unique]}, with inverse "inverse": np.int32 [n_rows] (first[i] == kept[inverse[i]]), with compact
         "data" and "row_off" of the kept rows back to back.  raw: text data comes back as np.uint8 rather than bytes.
         hash_bits: for tests of the collision rounds."""
-        data, off, n = _ragged_batch("dedup", data, row_off)
-        want = (WP_DEDUP_WANT_INVERSE if inverse else 0) | (WP_DEDUP_WANT_COMPACT if compact else 0)
-        spec = DedupSpec(data.dtype.itemsize, want, int(hash_bits), 0)
-        out = DedupResult()
-        _check(lib().wp_dedup_rows(self._h, data.ctypes.data if data.size else None, off.ctypes.data if n else None, n, C.byref(spec),
-                                   C.byref(out)))
-        block = _host_block
-        try:
-            u = out.n_unique
-            res = {"first": block(out.first, n, np.int32), "kept": block(out.kept, u, np.int32), "counts": block(out.counts, u, np.int64)}
-            if inverse:
-                res["inverse"] = block(out.inverse, n, np.int32)
-            if compact:
-                kept_data = block(out.data, out.n_elems, data.dtype)
-                res["data"] = kept_data if raw or data.dtype != np.uint8 else kept_data.tobytes()
-                res["row_off"] = block(out.row_off, u + 1, np.int64)
-        finally:
-            _free_blocks(out.first, out.kept, out.inverse, out.counts, out.row_off, out.data)
-        return res
+        batch = _ragged_batch("dedup", data, row_off)
+        spec = self._dedup_spec(batch[0].dtype.itemsize, inverse, compact, hash_bits)
+        return self._rows_host("dedup", spec, [batch], dict(inverse=inverse, compact=compact), raw)
 
     def dedup_rows_tensor(self, data, row_off, inverse=False, compact=False, copy=True, hash_bits=0):
         """dedup_rows for a batch in tensors on this handle's GPU (wp_dedup_rows_device): data uint8 (text) or int32
@@ -1463,30 +1398,9 @@ class Vocab:
         the words and word_off of count_words_tensor.  -> a dict of tensors on that device: "first", "kept", "counts",
         with inverse "inverse", with compact "data" and "row_off" (what encode_rows_tensor and pack_sequences_tensor
         take).  copy=False: views of the library's buffers, valid until the next call on this handle."""
-        import torch
-        if data.dtype not in (torch.uint8, torch.int32) or row_off.dtype != torch.int64:
-            raise WordPieceError("dedup_rows_tensor needs uint8 or int32 data and int64 row_off")
-        _flat_device_tensors("dedup_rows_tensor", self._device, data, row_off)
-        n = row_off.numel() - 1
-        if n < 0:
-            raise WordPieceError("dedup: row_off needs n_rows + 1 entries")
-        want = (WP_DEDUP_WANT_INVERSE if inverse else 0) | (WP_DEDUP_WANT_COMPACT if compact else 0)
-        spec = DedupSpec(data.element_size(), want, int(hash_bits), 0)
-        dev = data.device
-        (data, nbytes), = _whole_words(data)
-        out = DedupResult()
-        _check(lib().wp_dedup_rows_device(self._h, C.c_void_p(data.data_ptr()) if nbytes else None, C.c_void_p(row_off.data_ptr()), n,
-                                          C.byref(spec), C.byref(out)))
-        view = _DeviceViews(dev, copy)
-        u = out.n_unique
-        res = {"first": view(out.first, n, "<i4", torch.int32), "kept": view(out.kept, u, "<i4", torch.int32),
-               "counts": view(out.counts, u, "<i8", torch.int64)}
-        if inverse:
-            res["inverse"] = view(out.inverse, n, "<i4", torch.int32)
-        if compact:
-            res["data"] = view(out.data, out.n_elems, "|u1" if data.dtype == torch.uint8 else "<i4", data.dtype)
-            res["row_off"] = view(out.row_off, u + 1, "<i8", torch.int64) if n else torch.zeros(1, dtype=torch.int64, device=dev)
-        return res
+        batches = _ragged_tensors("dedup", self._device, [(data, row_off)])
+        spec = self._dedup_spec(data.element_size(), inverse, compact, hash_bits)
+        return self._rows_device("dedup", spec, batches, dict(inverse=inverse, compact=compact), copy)
 
     def dedup_docs(self, docs):
         """The documents of a list (str / bytes) without their repeats, in order of first occurrence, and how often each
@@ -1498,9 +1412,7 @@ class Vocab:
 
     def neardup_stats(self):
         """wp_neardup_stats of the last neardup call as a dict (n_rows -1: no such call yet)."""
-        s = NearDupStats()
-        _check(lib().wp_get_neardup_stats(self._h, C.byref(s)))
-        return {k: int(getattr(s, k)) for k, _ in s._fields_}
+        return self._stats(NearDupStats, "wp_get_neardup_stats")
 
     @staticmethod
     def _neardup_spec(elem_bytes, shingle, n_perm, bands, min_agree, seed, inverse, compact, signatures):
@@ -1518,26 +1430,9 @@ class Vocab:
         [n_unique], "counts": np.int64 [n_unique]}, with inverse "inverse", with compact "data" and "row_off" of the kept
         rows back to back, with signatures "signatures": np.uint32 [n_rows, n_perm].  raw: text data comes back as
         np.uint8 rather than bytes."""
-        data, off, n = _ragged_batch("neardup", data, row_off)
-        spec = self._neardup_spec(data.dtype.itemsize, shingle, n_perm, bands, min_agree, seed, inverse, compact, signatures)
-        out = NearDupResult()
-        _check(lib().wp_neardup_rows(self._h, data.ctypes.data if data.size else None, off.ctypes.data if n else None, n, C.byref(spec),
-                                     C.byref(out)))
-        block = _host_block
-        try:
-            u = out.n_unique
-            res = {"cluster": block(out.cluster, n, np.int32), "kept": block(out.kept, u, np.int32), "counts": block(out.counts, u, np.int64)}
-            if inverse:
-                res["inverse"] = block(out.inverse, n, np.int32)
-            if compact:
-                kept_data = block(out.data, out.n_elems, data.dtype)
-                res["data"] = kept_data if raw or data.dtype != np.uint8 else kept_data.tobytes()
-                res["row_off"] = block(out.row_off, u + 1, np.int64)
-            if signatures:
-                res["signatures"] = block(out.signatures, n * int(n_perm), np.uint32).reshape(n, int(n_perm))
-        finally:
-            _free_blocks(out.cluster, out.kept, out.inverse, out.counts, out.row_off, out.data, out.signatures)
-        return res
+        batch = _ragged_batch("neardup", data, row_off)
+        spec = self._neardup_spec(batch[0].dtype.itemsize, shingle, n_perm, bands, min_agree, seed, inverse, compact, signatures)
+        return self._rows_host("neardup", spec, [batch], dict(inverse=inverse, compact=compact, signatures=signatures), raw, n_perm=int(n_perm))
 
     def neardup_rows_tensor(self, data, row_off, shingle=5, n_perm=128, bands=16, min_agree=0, seed=0, inverse=False, compact=False,
                             signatures=False, copy=True):
@@ -1548,31 +1443,9 @@ class Vocab:
         signatures "signatures" (int32 bit patterns of the uint32 values, [n_rows, n_perm]: torch has no uint32
         arithmetic; .cpu().numpy().view(np.uint32) reads them).  copy=False: views of the library's buffers, valid until
         the next call on this handle."""
-        import torch
-        if data.dtype not in (torch.uint8, torch.int32) or row_off.dtype != torch.int64:
-            raise WordPieceError("neardup_rows_tensor needs uint8 or int32 data and int64 row_off")
-        _flat_device_tensors("neardup_rows_tensor", self._device, data, row_off)
-        n = row_off.numel() - 1
-        if n < 0:
-            raise WordPieceError("neardup: row_off needs n_rows + 1 entries")
+        batches = _ragged_tensors("neardup", self._device, [(data, row_off)])
         spec = self._neardup_spec(data.element_size(), shingle, n_perm, bands, min_agree, seed, inverse, compact, signatures)
-        dev = data.device
-        (data, nbytes), = _whole_words(data)
-        out = NearDupResult()
-        _check(lib().wp_neardup_rows_device(self._h, C.c_void_p(data.data_ptr()) if nbytes else None, C.c_void_p(row_off.data_ptr()), n,
-                                            C.byref(spec), C.byref(out)))
-        view = _DeviceViews(dev, copy)
-        u = out.n_unique
-        res = {"cluster": view(out.cluster, n, "<i4", torch.int32), "kept": view(out.kept, u, "<i4", torch.int32),
-               "counts": view(out.counts, u, "<i8", torch.int64)}
-        if inverse:
-            res["inverse"] = view(out.inverse, n, "<i4", torch.int32)
-        if compact:
-            res["data"] = view(out.data, out.n_elems, "|u1" if data.dtype == torch.uint8 else "<i4", data.dtype)
-            res["row_off"] = view(out.row_off, u + 1, "<i8", torch.int64) if n else torch.zeros(1, dtype=torch.int64, device=dev)
-        if signatures:
-            res["signatures"] = view(out.signatures, n * int(n_perm), "<i4", torch.int32).reshape(n, int(n_perm))
-        return res
+        return self._rows_device("neardup", spec, batches, dict(inverse=inverse, compact=compact, signatures=signatures), copy, n_perm=int(n_perm))
 
     def neardup_docs(self, docs, **kw):
         """The documents of a list (str / bytes) without their near-duplicates: the first document of every cluster, in
@@ -1585,9 +1458,7 @@ class Vocab:
 
     def overlap_stats(self):
         """wp_overlap_stats of the last overlap call as a dict (n_rows -1: no such call yet)."""
-        s = OverlapStats()
-        _check(lib().wp_get_overlap_stats(self._h, C.byref(s)))
-        return {k: int(getattr(s, k)) for k, _ in s._fields_}
+        return self._stats(OverlapStats, "wp_get_overlap_stats")
 
     @staticmethod
     def _overlap_spec(elem_bytes, ngram, max_hits, mask, ref, compact, hash_bits):
@@ -1610,30 +1481,11 @@ class Vocab:
         per element, with ref "ref_hits": np.int64 [n_ref] (the windows of a reference row found in the corpus), with
         compact "kept": np.int32 (the rows with hits <= max_hits) and their "data" and "row_off" back to back.  raw: text
         data comes back as np.uint8 rather than bytes.  hash_bits: for tests of key collisions."""
-        data, off, n = self._overlap_batch(data, row_off, "data")
-        rdata, roff, nr = self._overlap_batch(ref_data, ref_off, "ref_data")
-        if data.dtype != rdata.dtype:
+        batches = [self._overlap_batch(data, row_off, "data"), self._overlap_batch(ref_data, ref_off, "ref_data")]
+        if batches[0][0].dtype != batches[1][0].dtype:
             raise WordPieceError("overlap: data and ref_data must both be text or both be ids")
-        spec = self._overlap_spec(data.dtype.itemsize, ngram, max_hits, mask, ref, compact, hash_bits)
-        out = OverlapResult()
-        _check(lib().wp_overlap_rows(self._h, data.ctypes.data if data.size else None, off.ctypes.data if n else None, n,
-                                     rdata.ctypes.data if rdata.size else None, roff.ctypes.data if nr else None, nr, C.byref(spec), C.byref(out)))
-        block = _host_block
-        try:
-            res = {"hits": block(out.hits, n, np.int64), "first_hit": block(out.first_hit, n, np.int64),
-                   "first_ref": block(out.first_ref, n, np.int32), "covered": block(out.covered, n, np.int64)}
-            if mask:
-                res["mask"] = block(out.mask, int(off[n]) if n else 0, np.uint8)
-            if ref:
-                res["ref_hits"] = block(out.ref_hits, nr, np.int64)
-            if compact:
-                kept_data = block(out.data, out.n_elems, data.dtype)
-                res["kept"] = block(out.kept, out.n_kept, np.int32)
-                res["data"] = kept_data if raw or data.dtype != np.uint8 else kept_data.tobytes()
-                res["row_off"] = block(out.row_off, out.n_kept + 1, np.int64) if n else np.zeros(1, dtype=np.int64)
-        finally:
-            _free_blocks(out.hits, out.first_hit, out.covered, out.ref_hits, out.row_off, out.first_ref, out.kept, out.mask, out.data)
-        return res
+        spec = self._overlap_spec(batches[0][0].dtype.itemsize, ngram, max_hits, mask, ref, compact, hash_bits)
+        return self._rows_host("overlap", spec, batches, dict(mask=mask, ref=ref, compact=compact), raw)
 
     def overlap_rows_tensor(self, data, row_off, ref_data, ref_off, ngram=13, max_hits=0, mask=False, ref=False, compact=False, copy=True,
                             hash_bits=0):
@@ -1643,33 +1495,9 @@ class Vocab:
         device: "hits", "first_hit", "first_ref", "covered", with mask "mask" (torch.uint8), with ref "ref_hits", with
         compact "kept", "data" and "row_off" (what pack_sequences_tensor takes).  copy=False: views of the library's
         buffers, valid until the next call on this handle."""
-        import torch
-        if data.dtype not in (torch.uint8, torch.int32) or ref_data.dtype != data.dtype or row_off.dtype != torch.int64 or ref_off.dtype != torch.int64:
-            raise WordPieceError("overlap_rows_tensor needs uint8 or int32 data of one kind and int64 offsets")
-        _flat_device_tensors("overlap_rows_tensor", self._device, data, row_off, ref_data, ref_off)
-        n, nr = row_off.numel() - 1, ref_off.numel() - 1
-        if n < 0 or nr < 0:
-            raise WordPieceError("overlap: offsets need n_rows + 1 entries")
-        n_elems = data.numel()
+        batches = _ragged_tensors("overlap", self._device, [(data, row_off), (ref_data, ref_off)], offsets="offsets", s="")
         spec = self._overlap_spec(data.element_size(), ngram, max_hits, mask, ref, compact, hash_bits)
-        dev = data.device
-        (data, nbytes), (ref_data, ref_nbytes) = _whole_words(data, ref_data)
-        out = OverlapResult()
-        _check(lib().wp_overlap_rows_device(self._h, C.c_void_p(data.data_ptr()) if nbytes else None, C.c_void_p(row_off.data_ptr()), n,
-                                            C.c_void_p(ref_data.data_ptr()) if ref_nbytes else None, C.c_void_p(ref_off.data_ptr()), nr,
-                                            C.byref(spec), C.byref(out)))
-        view = _DeviceViews(dev, copy)
-        res = {"hits": view(out.hits, n, "<i8", torch.int64), "first_hit": view(out.first_hit, n, "<i8", torch.int64),
-               "first_ref": view(out.first_ref, n, "<i4", torch.int32), "covered": view(out.covered, n, "<i8", torch.int64)}
-        if mask:
-            res["mask"] = view(out.mask, min(n_elems, int(row_off[n])) if n and out.mask else 0, "|u1", torch.uint8)
-        if ref:
-            res["ref_hits"] = view(out.ref_hits, nr, "<i8", torch.int64)
-        if compact:
-            res["kept"] = view(out.kept, out.n_kept, "<i4", torch.int32)
-            res["data"] = view(out.data, out.n_elems, "|u1" if data.dtype == torch.uint8 else "<i4", data.dtype)
-            res["row_off"] = view(out.row_off, out.n_kept + 1, "<i8", torch.int64) if n else torch.zeros(1, dtype=torch.int64, device=dev)
-        return res
+        return self._rows_device("overlap", spec, batches, dict(mask=mask, ref=ref, compact=compact), copy)
 
     def overlap_docs(self, docs, ref_docs, ngram=13, max_hits=0):
         """The documents of a list (str / bytes) that share at most max_hits windows of `ngram` bytes with the documents
@@ -1683,9 +1511,7 @@ class Vocab:
 
     def repeat_stats(self):
         """wp_repeat_stats of the last repeat call as a dict (n_rows -1: no such call yet)."""
-        s = RepeatStats()
-        _check(lib().wp_get_repeat_stats(self._h, C.byref(s)))
-        return {k: int(getattr(s, k)) for k, _ in s._fields_}
+        return self._stats(RepeatStats, "wp_get_repeat_stats")
 
     @staticmethod
     def _repeat_spec(elem_bytes, ngram, scope, max_repeats, mask, src, compact, cut, utf8, hash_bits):
@@ -1710,35 +1536,9 @@ class Vocab:
         bytes.  hash_bits: for tests of key collisions."""
         if lines and row_off is not None:
             raise WordPieceError("repeat: the lines form takes no offsets")
-        data, off, n = self._overlap_batch(data, row_off, "data")
-        spec = self._repeat_spec(data.dtype.itemsize, ngram, scope, max_repeats, mask, src, compact, cut, utf8, hash_bits)
-        out = RepeatResult()
-        _check(lib().wp_repeat_rows(self._h, data.ctypes.data if data.size else None, off.ctypes.data if n else None, n, C.byref(spec), C.byref(out)))
-        block = _host_block
-
-        def elems(ptr, k):
-            a = block(ptr, k, data.dtype)
-            return a.tobytes() if data.dtype == np.uint8 else a
-        try:
-            n_elems = int(off[n]) if n else 0
-            res = {"repeats": block(out.repeats, n, np.int64), "first_repeat": block(out.first_repeat, n, np.int64),
-                   "first_src_row": block(out.first_src_row, n, np.int32), "first_src_pos": block(out.first_src_pos, n, np.int64),
-                   "covered": block(out.covered, n, np.int64)}
-            if mask:
-                res["mask"] = block(out.mask, n_elems, np.uint8)
-            if src:
-                res["src"] = block(out.src, n_elems, np.int64)
-            if compact:
-                res["kept"] = block(out.kept, out.n_kept, np.int32)
-                res["data"] = elems(out.data, out.n_elems)
-                res["row_off"] = block(out.row_off, out.n_kept + 1, np.int64) if n else np.zeros(1, dtype=np.int64)
-            if cut:
-                res["cut_data"] = elems(out.cut_data, out.n_cut_elems)
-                res["cut_off"] = block(out.cut_off, n + 1, np.int64) if n else np.zeros(1, dtype=np.int64)
-        finally:
-            _free_blocks(out.repeats, out.first_repeat, out.first_src_pos, out.covered, out.src, out.row_off, out.cut_off, out.first_src_row, out.kept,
-                         out.mask, out.data, out.cut_data)
-        return res
+        batch = self._overlap_batch(data, row_off, "data")
+        spec = self._repeat_spec(batch[0].dtype.itemsize, ngram, scope, max_repeats, mask, src, compact, cut, utf8, hash_bits)
+        return self._rows_host("repeat", spec, [batch], dict(mask=mask, src=src, compact=compact, cut=cut))
 
     def repeat_rows_tensor(self, data, row_off, ngram=50, scope=0, max_repeats=0, mask=False, src=False, compact=False, cut=False, utf8=None,
                            hash_bits=0, copy=True):
@@ -1747,39 +1547,9 @@ class Vocab:
         joined text and its doc_off.  -> a dict of tensors on that device with the keys of repeat_rows; "data" + "row_off"
         and "cut_data" + "cut_off" are what pack_sequences_tensor takes.  copy=False: views of the library's buffers,
         valid until the next call on this handle."""
-        import torch
-        if data.dtype not in (torch.uint8, torch.int32) or row_off.dtype != torch.int64:
-            raise WordPieceError("repeat_rows_tensor needs uint8 or int32 data and int64 offsets")
-        _flat_device_tensors("repeat_rows_tensor", self._device, data, row_off)
-        n = row_off.numel() - 1
-        if n < 0:
-            raise WordPieceError("repeat: offsets need n_rows + 1 entries")
-        n_elems = data.numel()
+        batches = _ragged_tensors("repeat", self._device, [(data, row_off)], offsets="offsets", s="")
         spec = self._repeat_spec(data.element_size(), ngram, scope, max_repeats, mask, src, compact, cut, utf8, hash_bits)
-        dev = data.device
-        (data, nbytes), = _whole_words(data)
-        out = RepeatResult()
-        _check(lib().wp_repeat_rows_device(self._h, C.c_void_p(data.data_ptr()) if nbytes else None, C.c_void_p(row_off.data_ptr()), n,
-                                           C.byref(spec), C.byref(out)))
-        view = _DeviceViews(dev, copy)
-        etype = "|u1" if data.dtype == torch.uint8 else "<i4"
-        res = {"repeats": view(out.repeats, n, "<i8", torch.int64), "first_repeat": view(out.first_repeat, n, "<i8", torch.int64),
-               "first_src_row": view(out.first_src_row, n, "<i4", torch.int32), "first_src_pos": view(out.first_src_pos, n, "<i8", torch.int64),
-               "covered": view(out.covered, n, "<i8", torch.int64)}
-        if mask or src:
-            last = min(n_elems, int(row_off[n])) if n else 0
-            if mask:
-                res["mask"] = view(out.mask, last if out.mask else 0, "|u1", torch.uint8)
-            if src:
-                res["src"] = view(out.src, last if out.src else 0, "<i8", torch.int64)
-        if compact:
-            res["kept"] = view(out.kept, out.n_kept, "<i4", torch.int32)
-            res["data"] = view(out.data, out.n_elems, etype, data.dtype)
-            res["row_off"] = view(out.row_off, out.n_kept + 1, "<i8", torch.int64) if n else torch.zeros(1, dtype=torch.int64, device=dev)
-        if cut:
-            res["cut_data"] = view(out.cut_data, out.n_cut_elems, etype, data.dtype)
-            res["cut_off"] = view(out.cut_off, n + 1, "<i8", torch.int64) if n else torch.zeros(1, dtype=torch.int64, device=dev)
-        return res
+        return self._rows_device("repeat", spec, batches, dict(mask=mask, src=src, compact=compact, cut=cut), copy)
 
     def repeat_docs(self, docs, ngram=50, scope=0):
         """The documents of a list (str / bytes) with the spans cut out that occurred before in the list (windows of
@@ -1800,9 +1570,7 @@ class Vocab:
 
     def quality_stats(self):
         """wp_quality_stats of the last quality call as a dict (n_rows -1: no such call yet; rule_failed: a list by rule)."""
-        s = QualityStats()
-        _check(lib().wp_get_quality_stats(self._h, C.byref(s)))
-        return {k: (list(getattr(s, k)) if k == "rule_failed" else int(getattr(s, k))) for k, _ in s._fields_}
+        return self._stats(QualityStats, "wp_get_quality_stats")
 
     @staticmethod
     def _quality_spec(rules, stop_words, short_line_chars, dup_lines, compact):
@@ -1820,9 +1588,7 @@ class Vocab:
             dup_lines = limit[10] >= 0 or limit[11] >= 0
         words = [_bytes(w) for w in (stop_words or ())]
         pool = np.frombuffer(b"".join(words) + b"\0", dtype=np.uint8)
-        off = np.zeros(len(words) + 1, dtype=np.int64)
-        if words:
-            off[1:] = np.cumsum([len(w) for w in words])
+        off = _offsets_of([len(w) for w in words])
         want = (WP_QUALITY_WANT_DUP_LINES if dup_lines else 0) | (WP_QUALITY_WANT_COMPACT if compact else 0)
         spec = QualitySpec(1, want, int(short_line_chars), len(words), pool.ctypes.data if words else None, off.ctypes.data if words else None,
                            (C.c_int64 * 16)(*limit), 0)
@@ -1836,25 +1602,11 @@ class Vocab:
         {"signals": np.int64 [23, n_rows] (rows of QUALITY_SIGNALS), "reasons": np.uint32 [n_rows] (bit r: rule r
         failed)}, with compact "kept": np.int32 (the rows that failed no rule) and their "data" and "row_off" back to
         back.  raw: the data comes back as np.uint8 rather than bytes."""
-        data, off, n = _ragged_batch("quality", data, row_off)
-        if data.dtype != np.uint8:
+        batch = _ragged_batch("quality", data, row_off)
+        if batch[0].dtype != np.uint8:
             raise WordPieceError("quality: data must be text")
         spec, keep = self._quality_spec(rules, stop_words, short_line_chars, dup_lines, compact)
-        out = QualityResult()
-        _check(lib().wp_quality_rows(self._h, data.ctypes.data if data.size else None, off.ctypes.data if n else None, n, C.byref(spec), C.byref(out)))
-        del keep
-        block = _host_block
-        try:
-            res = {"signals": block(out.signals, n * len(QUALITY_SIGNALS), np.int64).reshape(len(QUALITY_SIGNALS), n),
-                   "reasons": block(out.reasons, n, np.uint32)}
-            if compact:
-                kept_data = block(out.data, out.n_elems, np.uint8)
-                res["kept"] = block(out.kept, out.n_kept, np.int32)
-                res["data"] = kept_data if raw else kept_data.tobytes()
-                res["row_off"] = block(out.row_off, out.n_kept + 1, np.int64) if n else np.zeros(1, dtype=np.int64)
-        finally:
-            _free_blocks(out.signals, out.row_off, out.reasons, out.kept, out.data)
-        return res
+        return self._rows_host("quality", spec, [batch], dict(compact=compact), raw, n_signals=len(QUALITY_SIGNALS))
 
     def quality_rows_tensor(self, data, row_off, rules=None, stop_words=None, short_line_chars=0, dup_lines=None, compact=False, copy=True):
         """quality_rows for a batch in tensors on this handle's GPU (wp_quality_rows_device): data uint8, row_off int64 — a
@@ -1862,45 +1614,21 @@ class Vocab:
         (torch.int64 [23, n_rows]), "reasons" (the uint32 bitmasks as torch.int32), with compact "kept", "data" and
         "row_off" (what dedup_rows_tensor and, once encoded, pack_sequences_tensor take).  copy=False: views of the
         library's buffers, valid until the next call on this handle."""
-        import torch
-        if data.dtype != torch.uint8 or row_off.dtype != torch.int64:
-            raise WordPieceError("quality_rows_tensor needs uint8 data and int64 offsets")
-        _flat_device_tensors("quality_rows_tensor", self._device, data, row_off)
-        n = row_off.numel() - 1
-        if n < 0:
-            raise WordPieceError("quality: offsets need n_rows + 1 entries")
+        batches = _ragged_tensors("quality", self._device, [(data, row_off)], ids=False, offsets="offsets", s="")
         spec, keep = self._quality_spec(rules, stop_words, short_line_chars, dup_lines, compact)
-        dev = data.device
-        (data, nbytes), = _whole_words(data)
-        out = QualityResult()
-        _check(lib().wp_quality_rows_device(self._h, C.c_void_p(data.data_ptr()) if nbytes else None, C.c_void_p(row_off.data_ptr()), n,
-                                            C.byref(spec), C.byref(out)))
-        del keep
-        view = _DeviceViews(dev, copy)
-        res = {"signals": view(out.signals, n * len(QUALITY_SIGNALS), "<i8", torch.int64).reshape(len(QUALITY_SIGNALS), n),
-               "reasons": view(out.reasons, n, "<i4", torch.int32)}
-        if compact:
-            res["kept"] = view(out.kept, out.n_kept, "<i4", torch.int32)
-            res["data"] = view(out.data, out.n_elems, "|u1", torch.uint8)
-            res["row_off"] = view(out.row_off, out.n_kept + 1, "<i8", torch.int64) if n else torch.zeros(1, dtype=torch.int64, device=dev)
-        return res
+        return self._rows_device("quality", spec, batches, dict(compact=compact), copy, n_signals=len(QUALITY_SIGNALS))
 
     def quality_docs(self, docs, rules=None, stop_words=None, short_line_chars=0):
         """The documents of a list (str / bytes) that fail none of `rules` -> ([those documents as given], np.uint32
         reasons of every document of docs); through quality_rows over the documents back to back (no byte is added)."""
         docs = list(docs)
         bs = [_bytes(d) for d in docs]
-        off = np.zeros(len(bs) + 1, dtype=np.int64)
-        if bs:
-            off[1:] = np.cumsum([len(b) for b in bs])
-        r = self.quality_rows(b"".join(bs), off, rules=rules, stop_words=stop_words, short_line_chars=short_line_chars)
+        r = self.quality_rows(b"".join(bs), _offsets_of([len(b) for b in bs]), rules=rules, stop_words=stop_words, short_line_chars=short_line_chars)
         return [d for d, x in zip(docs, r["reasons"]) if x == 0], r["reasons"]
 
     def align_stats(self):
         """wp_align_stats of the last call as a dict (n_rows -1: it was no align call)."""
-        s = AlignStats()
-        _check(lib().wp_get_align_stats(self._h, C.byref(s)))
-        return {k: int(getattr(s, k)) for k, _ in s._fields_}
+        return self._stats(AlignStats, "wp_get_align_stats")
 
     def align_spans(self, batch=None, spans=None, side=0, outside_label=0, inside_add=0, ignore_id=-100, no_answer=0,
                     labels=True, span_index=False, positions=False, offsets=None, token_type_ids=None, lengths=None,
@@ -2051,9 +1779,7 @@ class Vocab:
 
     def special_stats(self):
         """wp_special_stats of the last special-tokens call as a dict (n_literals -1: no such call yet)."""
-        s = SpecialStats()
-        _check(lib().wp_get_special_stats(self._h, C.byref(s)))
-        return {k: int(getattr(s, k)) for k, _ in s._fields_}
+        return self._stats(SpecialStats, "wp_get_special_stats")
 
     def special_ids(self, tokens=None):
         """Strings -> ids for the special_ids= of the encode_special calls.  tokens=None: every line that may be listed
@@ -2257,13 +1983,7 @@ class Vocab:
         import torch
         if text.dtype != torch.uint8 or not text.is_cuda or not text.is_contiguous():
             raise WordPieceError("encode_tensor needs a contiguous uint8 CUDA/HIP tensor")
-        nbytes = text.numel()
-        if text.data_ptr() % 4 != 0 or nbytes % 4 != 0:
-            # the device entry point reads whole 4-byte words: pad into an aligned staging tensor
-            padded = torch.zeros((nbytes + 19) // 16 * 16, dtype=torch.uint8, device=text.device)
-            padded[:nbytes] = text
-            text = padded
-        torch.cuda.current_stream(text.device).synchronize()  # the library runs on its own HIP streams
+        (text, nbytes), = _whole_words(text)
         if offsets:
             d_ids, d_offs, n = self.encode_device_with_offsets(text.data_ptr(), nbytes, unit)
             if n == 0:
@@ -2312,10 +2032,28 @@ def join_docs(docs):
     """The joined form of a list of documents (str / bytes): every document followed by one "\\n" -> (bytes, int64
     offsets [n_docs + 1]); document i is bytes[offsets[i]:offsets[i + 1] - 1]."""
     bs = [_bytes(d) for d in docs]
-    off = np.zeros(len(bs) + 1, dtype=np.int64)
-    if bs:
-        off[1:] = np.cumsum([len(b) + 1 for b in bs])
-    return b"".join(b + b"\n" for b in bs), off
+    return b"".join(b + b"\n" for b in bs), _offsets_of([len(b) + 1 for b in bs])
+
+
+def _offsets_of(lengths):
+    """int64 offsets [n + 1] of n pieces back to back: 0, then the running sums of their lengths"""
+    off = np.zeros(len(lengths) + 1, dtype=np.int64)
+    if len(lengths):
+        off[1:] = np.cumsum(lengths)
+    return off
+
+
+def _terminator_byte(prefix, terminator):
+    """The terminator of a count, learn or detokenize call as the C ABI takes it: a one-byte str / bytes or an int -> that
+    byte, None -> -1 (none).  prefix: the layer's name in front of the message; None: the detokenize calls' wording."""
+    if terminator is None:
+        return -1
+    if not isinstance(terminator, (str, bytes, bytearray, memoryview)):
+        return int(terminator)
+    t = _bytes(terminator)
+    if len(t) != 1:
+        raise WordPieceError("%s: terminator must be one byte" % prefix if prefix else "the terminator is one byte")
+    return t[0]
 
 
 def line_rows(text):
@@ -2328,7 +2066,7 @@ def line_rows(text):
     return t, np.concatenate((np.zeros(1, dtype=np.int64), ends))
 
 
-# ---- what the wrappers of the ragged-batch layers share (dedup, neardup, overlap, repeat; host and tensor forms) ------
+# ---- what the wrappers of the corpus layers share (count, learn, dedup, neardup, overlap, repeat, quality; both forms) --
 def _ragged_batch(prefix, data, row_off, name="data", offsets="row_off", s="s"):
     """One batch of a host call -> (flat uint8 / int32 array, int64 offsets, n_rows).  name, offsets, s: what the layer's
     messages call the data and the offsets, and the ending of the verb behind the latter."""
@@ -2351,17 +2089,69 @@ def _ragged_batch(prefix, data, row_off, name="data", offsets="row_off", s="s"):
     return data, off, n
 
 
-def _host_block(ptr, k, dtype):
-    """a copy of the k elements of a block the library returned (NULL or k == 0: an empty array)"""
+def _ragged_tensors(prefix, device, batches, ids=True, offsets="row_off", s="s"):
+    """The batches [(data, offsets)] of a tensor call, as _ragged_batch takes those of a host call -> [(the data or its
+    padded copy (_whole_words), its bytes, the offsets, n_rows)]; torch's stream has been waited for.  ids: int32 data is
+    taken beside uint8; offsets, s: what the layer's messages call the offsets, and the ending of the verb behind them."""
+    import torch
+    fn = prefix + "_rows_tensor"
+    kinds = (torch.uint8, torch.int32) if ids else (torch.uint8,)
+    if any(d.dtype not in kinds or d.dtype != batches[0][0].dtype or o.dtype != torch.int64 for d, o in batches):
+        words = ("uint8 or int32 data" if ids else "uint8 data") + (" of one kind" if len(batches) > 1 else "")
+        raise WordPieceError("%s needs %s and int64 %s" % (fn, words, offsets))
+    _flat_device_tensors(fn, device, *[t for batch in batches for t in batch])
+    if any(o.numel() < 1 for _, o in batches):
+        raise WordPieceError("%s: %s need%s n_rows + 1 entries" % (prefix, offsets, s))
+    padded = _whole_words(*[d for d, _ in batches])
+    return [(d, nbytes, o, o.numel() - 1) for (d, nbytes), (_, o) in zip(padded, batches)]
+
+
+def _host_block(ptr, k, kind, absent=0):
+    """a copy of the k elements of a block the library returned (k == 0: an empty array; NULL: `absent` zeros)"""
     if not k or not ptr:
-        return np.zeros(0, dtype=dtype)
-    return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(np.ctypeslib.as_ctypes_type(dtype))), (k,)).copy()
+        return np.zeros(0 if ptr else absent, dtype=_KINDS[kind][0])
+    return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(np.ctypeslib.as_ctypes_type(_KINDS[kind][0]))), (k,)).copy()
 
 
-def _free_blocks(*blocks):
-    for blk in blocks:
-        if blk:
-            lib().wp_free(blk)
+def _free_blocks(result):
+    """frees the blocks of a host result: every pointer field of the struct, so no list of them can go stale"""
+    for name, ctype in result._fields_:
+        if (ctype is C.c_void_p or issubclass(ctype, C._Pointer)) and getattr(result, name):
+            lib().wp_free(getattr(result, name))
+
+
+def _layer_result(layer, out, read, on=None, elem=None, **sizes):
+    """The dict of a corpus call from its filled Result struct, by the layer's rows of _RESULTS.  read: _host_block, or a
+    _DeviceViews; on: {keyword: whether it is switched on}; elem: the kind of the batch's own elements; sizes: what the
+    struct does not count.  A size that is a function is called once, and only for an array that came back: the tensor
+    form reads one offset from the device for "elems"."""
+    def size(name, ptr):
+        k = sizes[name] if name in sizes else getattr(out, name)
+        if callable(k):
+            if not ptr:
+                return 0
+            k = sizes[name] = k()
+        return k
+    res = {}
+    for key, kind, shape, flag in _RESULTS[layer]:
+        if flag is not None and not (on and on.get(flag)):
+            continue
+        ptr = getattr(out, key)
+        dims = [size(name, ptr) for name in shape]
+        if kind == "off":  # (one entry more, and [0] where the library handed none out: a call without rows)
+            res[key] = read(ptr, dims[0] + 1, "i64", absent=1)
+        else:
+            a = read(ptr, math.prod(dims), elem if kind == "elem" else kind)
+            res[key] = a.reshape(dims) if len(dims) > 1 else a
+    return res
+
+
+def _host_result(layer, out, on=None, elem=None, **sizes):
+    """_layer_result of a host call: copies of the library's blocks, which are freed here"""
+    try:
+        return _layer_result(layer, out, _host_block, on, elem, **sizes)
+    finally:
+        _free_blocks(out)
 
 
 def _flat_device_tensors(fn, device, *tensors):
@@ -2395,10 +2185,11 @@ class _DeviceViews:
     def __init__(self, dev, copy):
         self.dev, self.copy = dev, copy
 
-    def __call__(self, ptr, k, typestr, dtype):
+    def __call__(self, ptr, k, kind, absent=0):
         import torch
-        if not k or not ptr:
-            return torch.zeros(0, dtype=dtype, device=self.dev)
+        _, typestr, dtype = _KINDS[kind]
+        if not k or not ptr:  # (k == 0: an empty tensor; NULL: `absent` zeros)
+            return torch.zeros(0 if ptr else absent, dtype=getattr(torch, dtype), device=self.dev)
         t = torch.as_tensor(DeviceIds(ptr, k, typestr=typestr), device=self.dev)
         return t.clone() if self.copy else t
 
@@ -2407,9 +2198,7 @@ def join_spans(spans):
     """The flat form of labelled spans given per sample: a list, per sample, of (begin, end) or (begin, end, label)
     (label 0 where there is none) -> (span_splits int64 [n_samples + 1], spans uint32 [n_spans, 2], span_labels int32
     [n_spans]), what the align calls take.  The rules — non-empty, sorted, disjoint — are the library's to check."""
-    splits = np.zeros(len(spans) + 1, dtype=np.int64)
-    if len(spans):
-        splits[1:] = np.cumsum([len(s) for s in spans])
+    splits = _offsets_of([len(s) for s in spans])
     flat = [t for s in spans for t in s]
     sp = np.array([(t[0], t[1]) for t in flat], dtype=np.uint32).reshape(-1, 2)
     sl = np.array([t[2] if len(t) > 2 else 0 for t in flat], dtype=np.int32)
@@ -2527,12 +2316,7 @@ def _detok_spec(max_len, skip_ids, cleanup, terminator):
     skip = [int(i) for i in skip_ids]
     if len(skip) > 8:
         raise WordPieceError("at most 8 skip ids")
-    if isinstance(terminator, (str, bytes)):
-        if len(_bytes(terminator)) != 1:
-            raise WordPieceError("the terminator is one byte")
-        terminator = _bytes(terminator)[0]
-    return DetokSpec(int(max_len), int(bool(cleanup)), -1 if terminator is None else int(terminator), len(skip),
-                     (C.c_int32 * 8)(*skip))
+    return DetokSpec(int(max_len), int(bool(cleanup)), _terminator_byte(None, terminator), len(skip), (C.c_int32 * 8)(*skip))
 
 
 def _special(i):
@@ -2632,10 +2416,8 @@ def learn_vocab(text_or_docs, vocab_size, normalize=0, device=None, min_count=1,
         data = b"\n".join(_bytes(d) for d in text_or_docs)
     boot = Vocab(["[UNK]"], device=device, normalize=normalize)
     dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
-    text = torch.zeros((len(data) + 19) // 16 * 16, dtype=torch.uint8, device=dev)
-    if data:
-        text[:len(data)] = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev)
-    table = boot.count_words_tensor(text[:len(data)], order="count", min_count=min_count, max_word_bytes=max_word_bytes, copy=False)
+    text = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev) if data else torch.zeros(0, dtype=torch.uint8, device=dev)
+    table = boot.count_words_tensor(text, order="count", min_count=min_count, max_word_bytes=max_word_bytes, copy=False)
     r = boot.learn_vocab_tensor(table["words"], table["word_off"], table["counts"], vocab_size, copy=False, **kw)
     lines = bytes(r["tokens"].cpu().numpy()).split(b"\n")[:-1]
     return Vocab(lines, device=device, normalize=normalize)

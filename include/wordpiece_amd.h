@@ -1230,11 +1230,13 @@ typedef struct {
 int wp_get_inputs_stats(const wp_vocab *v, wp_inputs_stats *out);
 
 /* ---- debug fetch (WP_OPT_KEEP_DEBUG): copies device intermediates to host ----
- * which: 0 S (dense symbols as int32, n), 1 SA (n), 2 rank (n; the full inverse SA is kept only with this option —
- * the default layout otherwise stores ranks for the suffixes of needed groups alone), 3 lcp (n-1; -1 = "at least
+ * which: 0 S (dense symbols as int32, n), 1 SA (n), 2 rank (n; the inverse SA is kept only with this option, full
+ * depth or the reference layout — the default layout otherwise has no rank table: the slots of the suffixes of needed
+ * groups stand in the place of their round-0 keys, and the call fails), 3 lcp (n-1; -1 = "at least
  * sorted_depth"), 4 best_prefix (n), 5 best_suffix (n), 6 code points (n_text), 7 class bytes (n_text, as int32:
  * 1 is_space, 2 is_spacing_char, 4 soft spacing char, 8 is_punctuation; the Linear path's anchor kernels add 16 at a
- * word-prefix position and 32 at an anchor of the walk).
+ * word-prefix position and 32 at an anchor of the walk; 64, "the key's word holds the slot", is set only where the
+ * key lookup is on, which this option turns off).
  * WP_OPT_KEEP_DEBUG = 2 keeps four views by text position instead (n_text each; the others fail), written by one kernel
  * in front of the walk through the walk's own lookup (key-space table, then rank and slot-space table for the key of a
  * needed group): 8 / 9 the id of the longest prefix-class / ##-class token that matches at the position, -1 for none

@@ -64,8 +64,13 @@ enum BoundSite {
   kSiteQuality = 22,  // quality signals: the gathers of the class pass, the stores of the word and line lists, the sums per row (quality.h)
   kBoundSites = 23
 };
+// One more counter behind the sites of the enum (no address): a lookup of the Linear walk at which the class byte's
+// kClsRanked and the key-space table's kStepNeeded disagree — the two sets are equal by construction (walk.h, step_at).
+// Read with the Linear path's own sites at the end of an encode (linear_path.h, finish).
+constexpr int kSiteRankFlag = kBoundSites;
+constexpr int kCountedSites = kBoundSites + 1;
 #ifdef WP_DEBUG_BOUNDS
-__device__ unsigned int g_wp_oob[kBoundSites];
+__device__ unsigned int g_wp_oob[kCountedSites];
 __device__ __forceinline__ bool wp_in_bounds(bool ok, int site) {
   if (!ok) atomicAdd(&g_wp_oob[site], 1u);
   return ok;
@@ -111,6 +116,16 @@ constexpr uint8_t kClsPunct = 8;    // is_punctuation (the fast path's word rule
 // per position it lands on: a word-prefix position (linear.cpp:215-219); an anchor of the walk (class or coverage rule)
 constexpr uint8_t kClsWordPrefix = 16;
 constexpr uint8_t kClsAnchor = 32;
+// key lookup (walk.h, step_at): the position is an entry of the needed list, and the word of the round-0 key array at
+// this position holds its slot instead of its key — set by the rank store behind the trie round, kept by the anchor kernels
+constexpr uint8_t kClsRanked = 64;
+// bounds-checking build: the key stays where it is, the slot goes to a rank table of its own as before, and every
+// lookup checks the flag against the key-space table's answer (kSiteRankFlag)
+#ifdef WP_DEBUG_BOUNDS
+constexpr bool kRankOverKey = false;
+#else
+constexpr bool kRankOverKey = true;
+#endif
 
 // ---- UTF-8: utf8.cpp:31-90 ----------------------------------------------------------------
 // Decodes the sequence starting at p[0] with `size` bytes available.  Returns the code point or

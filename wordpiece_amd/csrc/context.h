@@ -334,9 +334,11 @@ struct RowsCall {
 //                              (second side stream, beside the step starts and their sort)
 //   kEvStartsSorted / kEvTablesIndexed  the step starts are sorted (main stream) / the bucket indices, kstart and the flags
 //                              of the needed groups are built (second side stream, beside the step values)
+//   kEvRankStored              early refinement, key lookup: the rank scatter (main stream) has set kClsRanked in the class
+//                              bytes of the needed list; the side stream's anchor_write_kernel, which rewrites them, waits
 enum SideEvent { kEvFork, kEvJoin, kEvScalars, kEvKeysFree, kEvPartition, kEvTrieNodes, kEvLargeSorted, kEvKeysBuilt, kEvCandCount,
                  kEvSpine, kEvKept, kEvSorted, kEvListBuilt, kEvRoundDone, kEvAnchorScalars,
-                 kEvMarks, kEvCovered, kEvStartsSorted, kEvTablesIndexed, kSideEvents };
+                 kEvMarks, kEvCovered, kEvStartsSorted, kEvTablesIndexed, kEvRankStored, kSideEvents };
 // c->ev: the marks of WP_OPT_STAGE_TIMING in the order an encode passes them: its start / code points counted / symbols,
 // classes and keys written / suffix array refined / LCP / scanlines / walk (the fast path: start, counted, symbols,
 // walked).  normalize_on_device: its start, and its end in the mark the encode behind it records next.
@@ -487,7 +489,7 @@ static void take_oob(int first, int count, unsigned int *oob) {
   bool any = false;
   for (int i = 0; i < count; i++) any = any || oob[i] != 0;
   if (!any) return;
-  const unsigned int zero[kBoundSites] = {};
+  const unsigned int zero[kCountedSites] = {};
   WP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_wp_oob), zero, count * sizeof(unsigned int), first * sizeof(unsigned int)));
 }
 #endif

@@ -1973,11 +1973,12 @@ int wp_linear_encode_inputs_device(wp_vocab *v, const void *d_utf8, size_t nbyte
 int wp_reserve(wp_vocab *v, size_t nbytes) {
   return guarded([&] {
     Context *c = get_context(v);
-    // arenas as an encode of `nbytes` of ASCII text would size them in the default layout (43
-    // bytes per symbol + the refinement list for an eighth of the text; an estimate — an encode that needs more,
-    // a larger alphabet or the reference layout, grows them as before)
+    // arenas as an encode of `nbytes` of ASCII text would size them in the default layout (39
+    // bytes per symbol — no rank table: the ranks of the needed list stand over their keys — + the refinement list for
+    // an eighth of the text; an estimate — an encode that needs more, a larger alphabet or the reference layout, grows
+    // them as before; the bounds-checking build keeps the rank table)
     const size_t n = nbytes + 1 + v->hv.stream.size();
-    const size_t per_symbol = (v->keep_debug || v->vocab_in_s || v->full_depth) ? 108 : 56;
+    const size_t per_symbol = (v->keep_debug || v->vocab_in_s || v->full_depth) ? 108 : (kRankOverKey ? 52 : 56);
     c->text_buf.ensure(text_room(nbytes), false);
     c->a_buf.ensure(nbytes + nbytes / 512 + (size_t(1) << 20) + (v->keep_debug ? 4 * nbytes : 0), false);
     c->b_buf.ensure(per_symbol * n + (v->keep_debug ? 4 * n : 0) + (v->keep_step_views ? 16 * n : 0) + (size_t(64) << 20), false);
@@ -2430,7 +2431,10 @@ int wp_linear_debug_fetch(const wp_vocab *v, int which, int32_t *out, size_t cap
         if (!d.sa) throw std::invalid_argument("the suffix array is kept only with WP_OPT_KEEP_DEBUG");
         src = d.sa;
         break;
-      case 2: src = d.rank; break;
+      case 2:  // (key lookup: the ranks of the needed list stand over their keys, there is no table; linear_path.h, rank_out)
+        if (!d.rank) throw std::invalid_argument("the rank table is kept only with WP_OPT_KEEP_DEBUG, full depth or the reference layout");
+        src = d.rank;
+        break;
       case 3: src = d.lcp; cnt = d.n - 1; break;
       case 4:
       case 5: {  // materialise the reference's per-slot arrays from the step functions

@@ -122,6 +122,8 @@ struct LinearPath : DecodedText {
   // keys_only: the needed groups are built from the candidate runs and refined beside the round-0 passes (ranks_round0,
   // "the early refinement"; WP_OPT_LATE_REFINE: behind the sort as before)
   bool early_refine;
+  // key_lookup: the trie round's rank store writes a needed position's slot over its round-0 key (rank_out())
+  bool rank_in_key;
   bool wide_ran = false;  // the walk took the wide branch: scalar 13 holds its count of words (wp_walk_stats)
   uint32_t need_depth;
   int M, P, P_cap, hb_n, win_mid;
@@ -225,6 +227,7 @@ struct LinearPath : DecodedText {
     // the suffixes and its test, packing and sort cost more than the value column (33.1 against 31.1 ms per step)
     keys_only = key_lookup && !v->indexed_round0 && sizeof(SymT) == 1;
     early_refine = keys_only && !v->late_refine;
+    rank_in_key = key_lookup;
     sl_tiles = cdiv(n, kSlTile);
     sl_groups = cdiv(sl_tiles, kSlGroup);
     P = kStepsPerMark * M + 1;  // steps of the scanline result (scanline.h)
@@ -297,11 +300,12 @@ struct LinearPath : DecodedText {
 
   // ---- HBM layout (arena B) -------------------------------------------------------------------------------------
   // Per symbol, default layout with 8-bit symbols: sym 1, keys 4 + 4, values 4 + 4, digit bytes 1 + 1, rank-store
-  // scratch 4 + 4, rank 4, trie nodes by slot 4, id scratch 4, anchors 4 = 43 B, + ~80 B per entry of the active list
-  // (an eighth of the text unless the last encode needed more) + vocabulary-sized tables.  The reference layout and
-  // the debug views add their own arrays.  Roles of the n-sized slabs by stage:
+  // scratch 4 + 4, trie nodes by slot 4, id scratch 4, anchors 4 = 39 B, + ~80 B per entry of the active list
+  // (an eighth of the text unless the last encode needed more) + vocabulary-sized tables.  The reference layout, the
+  // debug views and the bounds-checking build add their own arrays, the rank table (4 B) among them: with the key
+  // lookup the ranks of the needed list stand in KA, over their keys (rank_out()).  Roles of the n-sized slabs by stage:
   //   sort        KA/KB keys, VA/VB values
-  //   rank store  X0/X1 first partition pass, (other values, keys) second, d_rank <- windows
+  //   rank store  X0/X1 first partition pass, (other values, keys) second, d_rank <- windows (no key lookup)
   //   walk        see walk(): ids, id lists, wide / long-word / coverage scratch in KA KB VA VB X0 X1
   void plan() {
     const bool ref = !text_only;                       // S = text . 1 . vocab: LCP-driven scanlines, doubling rounds
@@ -319,7 +323,9 @@ struct LinearPath : DecodedText {
       X1 = ar.take<uint32_t>(n + 16);
       DG0 = use_digit_bytes ? ar.take<uint8_t>(n + 64) : nullptr;
       DG1 = use_digit_bytes ? ar.take<uint8_t>(n + 64) : nullptr;
-      d_rank = ar.take<RankEntry>(n);
+      // (key lookup: the ranks of the needed list go over their keys in KA, rank_out(); no kernel of the trie path
+      // dereferences the table it is handed — its second keys are trie nodes)
+      d_rank = (rank_in_key && kRankOverKey) ? nullptr : ar.take<RankEntry>(n);
       d_node_of_slot = use_trie ? ar.take<uint32_t>(n) : nullptr;
       d_lcp = want_lcp ? ar.take<int32_t>(n) : nullptr;  // (default layout: nothing reads LCPs)
       d_sa = (v->keep_debug || v->lcp_kasai) ? ar.take<uint32_t>(n) : nullptr;
@@ -439,13 +445,16 @@ struct LinearPath : DecodedText {
   // side stream: the anchor list (and the cleared emit array of the sparse id path) only need the class bytes; they
   // run next to the small latency-bound kernels of the scanline stage, not next to the radix passes (key_lookup: on
   // the main stream, next to the needed-group searches and the trie round of the side stream, ranks_round0)
-  void launch_anchors(hipStream_t as) {
+  // behind_store: the rank store runs on another stream and sets kClsRanked in the class bytes (rank_flags()), which
+  // anchor_write_kernel rewrites — that kernel waits for kEvRankStored; the count and the scan touch no class byte
+  void launch_anchors(hipStream_t as, bool behind_store = false) {
     anchors_queued = true;
     const unsigned atiles = cdiv(n_text, kAnchorTile);
     if (!staged_possible) WP_HIP(hipMemsetAsync(d_emit, 0x80, n_text * sizeof(int32_t), as));
     hipLaunchKernelGGL(anchor_count_kernel, dim3(atiles), dim3(kBlock), 0, as, d_cls, static_cast<const uint8_t *>(nullptr),
                        n_text, d_anchor_cnt);
     device_exclusive_scan(d_anchor_cnt, d_anchor_cnt, atiles, d_anchor_tmp, c->d_scalars + kScalarAnchors, as);
+    if (behind_store) WP_HIP(hipStreamWaitEvent(as, c->evs[kEvRankStored], 0));
     hipLaunchKernelGGL(anchor_write_kernel, dim3(atiles), dim3(kBlock), 0, as, d_cls, static_cast<const uint8_t *>(nullptr),
                        n_text, d_anchor_cnt, d_anchors);
     hipLaunchKernelGGL(anchor_gap_kernel, dim3(std::min<size_t>(atiles, 1024)), dim3(kBlock), 0, as, d_anchors,
@@ -696,11 +705,18 @@ struct LinearPath : DecodedText {
       const int bc = radix_sort_pairs<uint32_t>(dst, val, t_dst, t_val, m, std::max(0, hb - 8), hb, d_radix_tmp, radix_words, st,
                                                 nullptr, false, hb + 1, DigitBytes(), true);
       hipLaunchKernelGGL(scatter_pairs_kernel, dim3(cdiv(m, kSpTile)), dim3(kBlock), 0, st, bc ? t_dst : dst, bc ? t_val : val, m,
-                         d_rank, n, 1);
+                         rank_out(), n, 1, rank_flags(), n_text);
     } else {
-      hipLaunchKernelGGL(scatter_pairs_kernel, dim3(cdiv(m, kSpTile)), dim3(kBlock), 0, st, dst, val, m, d_rank, n, 0);
+      hipLaunchKernelGGL(scatter_pairs_kernel, dim3(cdiv(m, kSpTile)), dim3(kBlock), 0, st, dst, val, m, rank_out(), n, 0, rank_flags(),
+                         n_text);
     }
   }
+  // Where the rank store writes.  Key lookup ("rank in the key's place", walk.h, step_at): over the round-0 key of the
+  // position in KA — the only ranks anything reads are those of the needed list, whose keys answer kStepNeeded and are
+  // never looked at again — with kClsRanked set in the position's class byte; there is no rank table.  The
+  // bounds-checking build keeps the table and the keys and sets the flag alone (kRankOverKey).
+  RankEntry *rank_out() const { return (rank_in_key && kRankOverKey) ? reinterpret_cast<RankEntry *>(KA) : d_rank; }
+  uint8_t *rank_flags() const { return rank_in_key ? d_cls : nullptr; }
 
   // The rank store of round 0 at full size.  val == nullptr: the values are the slots themselves, made up by the first
   // pass.  The passes go through the scratch pairs a = (X0, X1) and b = (the value buffer the sort did not end in, the
@@ -995,20 +1011,23 @@ struct LinearPath : DecodedText {
     }
     if (early_refine) {  // the main stream goes on behind the round; the anchor list follows it on the side stream, behind the sort
       WP_HIP(hipEventRecord(c->evs[kEvRoundDone], st2));
-      if (n_text > 0) {
-        WP_HIP(hipStreamWaitEvent(st2, c->evs[kEvSorted], 0));
-        launch_anchors(st2);
-      }
       WP_HIP(hipStreamWaitEvent(st, c->evs[kEvRoundDone], 0));
+      // (the store is queued first: the side stream's anchor_write_kernel waits for the event behind it)
       if (n_act > 0) {  // hd: list positions of the subgroup heads; the scatter moves them to the group's slots
         if (n_act >= (1u << 22)) {
           hipLaunchKernelGGL(list_rank_base_kernel, dim3(cdiv(n_act, kBlock)), dim3(kBlock), 0, st, hd, AG, d_gfirst, d_ghead, n_act);
           store_ranks(spare_vals, hd, reinterpret_cast<uint32_t *>(hd) + list_cap + 2, reinterpret_cast<uint32_t *>(skeys), n_act);
         } else {
           hipLaunchKernelGGL(scatter_list_ranks_kernel, dim3(cdiv(n_act, kBlock)), dim3(kBlock), 0, st, spare_vals, hd, AG, d_gfirst,
-                             d_ghead, n_act, d_rank, n);
+                             d_ghead, n_act, rank_out(), n, rank_flags(), n_text);
         }
         rounds = 2;
+      }
+      if (n_text > 0) {
+        const bool flags_stored = n_act > 0 && rank_flags() != nullptr;
+        if (flags_stored) WP_HIP(hipEventRecord(c->evs[kEvRankStored], st));
+        WP_HIP(hipStreamWaitEvent(st2, c->evs[kEvSorted], 0));
+        launch_anchors(st2, flags_stored);
       }
       WP_LAUNCH_CHECK();
       return;
@@ -1509,16 +1528,17 @@ struct LinearPath : DecodedText {
     }
 #ifdef WP_DEBUG_BOUNDS
     {
-      unsigned int oob[kBoundSites] = {};
+      unsigned int oob[kCountedSites] = {};
       WP_HIP(hipStreamSynchronize(st));
-      take_oob(0, kBoundSites, oob);
-      if (oob[0] | oob[1] | oob[2] | oob[3] | oob[4] | oob[5] | oob[6] | oob[7] | oob[8]) {
+      take_oob(0, kCountedSites, oob);
+      if (oob[0] | oob[1] | oob[2] | oob[3] | oob[4] | oob[5] | oob[6] | oob[7] | oob[8] | oob[kSiteRankFlag]) {
         throw HipError("debug bounds: out-of-range addresses skipped: radix scatter " + std::to_string(oob[0]) + ", rank store " +
                        std::to_string(oob[1]) + ", token id " + std::to_string(oob[2]) + ", list slot " + std::to_string(oob[3]) +
                        "; key-space step starts inside a run of equal keys " + std::to_string(oob[4]) +
                        "; candidate runs unlike their group " + std::to_string(oob[5]) + "; offsets " + std::to_string(oob[6]) +
                        "; step values used at blanks " + std::to_string(oob[7]) +
-                       "; round-0 sorted array: descents, blank keys left, multiset unlike the kept keys " + std::to_string(oob[8]));
+                       "; round-0 sorted array: descents, blank keys left, multiset unlike the kept keys " + std::to_string(oob[8]) +
+                       "; lookups whose ranked flag and key-space answer disagree " + std::to_string(oob[kSiteRankFlag]));
       }
       S.reserved0 = 1;  // this is the bounds-checking build
     }

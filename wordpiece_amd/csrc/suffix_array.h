@@ -264,9 +264,21 @@ __device__ __forceinline__ int32_t lcp_compare(const SymT *__restrict__ sym, siz
 #endif
 constexpr int kSpItems = WP_SP_ITEMS;
 constexpr int kSpTile = kBlock * kSpItems;
+// flag_cls != nullptr (key lookup: `out` is the round-0 key array, the rank takes its key's place; walk.h, step_at): the
+// class byte of every destination inside the text gets kClsRanked.  A byte-wide read-modify-write: a destination occurs
+// once in the list, so nobody else writes that byte while this kernel runs (the anchor kernels, which rewrite the
+// class bytes, are ordered against the store by the caller), and two entries may share a word.
+// Measured cost (config 2, 2.96 M entries, profiles/r09_*): scatter_list_ranks_kernel 87 -> 133 us per encode, its
+// FETCH_SIZE 17.9 -> 192.8 MB and WRITE_SIZE 94.8 -> 188.7 MB raw per launch — the dominant new cost of the rank in the
+// key's place, on the main stream.  The cheaper forms are open: an atomicOr on the aligned word whose value nobody
+// waits for, or a plain byte store where the class byte is known without the load.
+__device__ __forceinline__ void flag_ranked(uint8_t *__restrict__ flag_cls, size_t flag_n, uint32_t d) {
+  if (flag_cls && d < flag_n) flag_cls[d] = static_cast<uint8_t>(flag_cls[d] | kClsRanked);
+}
 __global__ __launch_bounds__(kBlock) void scatter_pairs_kernel(const uint32_t *__restrict__ dst,
                                                                const RankEntry *__restrict__ val, size_t m,
-                                                               RankEntry *__restrict__ out, size_t out_n, int xcd) {
+                                                               RankEntry *__restrict__ out, size_t out_n, int xcd,
+                                                               uint8_t *__restrict__ flag_cls, size_t flag_n) {
   unsigned b = blockIdx.x;
   if (xcd) {
     const unsigned nb = gridDim.x, q = nb / 8, r = nb % 8, x = b % 8;
@@ -283,7 +295,10 @@ __global__ __launch_bounds__(kBlock) void scatter_pairs_kernel(const uint32_t *_
   }
 #pragma unroll
   for (int j = 0; j < kSpItems; j++) {
-    if (v[j] != kRankUnchanged && wp_in_bounds(d[j] < out_n, kSiteRankStore)) out[d[j]] = v[j];
+    if (v[j] != kRankUnchanged && wp_in_bounds(d[j] < out_n, kSiteRankStore)) {
+      out[d[j]] = v[j];
+      flag_ranked(flag_cls, flag_n, d[j]);
+    }
   }
 }
 
@@ -295,12 +310,16 @@ __global__ __launch_bounds__(kBlock) void scatter_list_ranks_kernel(const uint32
                                                                     const uint32_t *__restrict__ gid,
                                                                     const uint32_t *__restrict__ gfirst,
                                                                     const uint32_t *__restrict__ ghead, size_t m,
-                                                                    RankEntry *__restrict__ out, size_t out_n) {
+                                                                    RankEntry *__restrict__ out, size_t out_n,
+                                                                    uint8_t *__restrict__ flag_cls, size_t flag_n) {
   const size_t k = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (k >= m) return;
   const uint32_t g = gid[k], d = dst[k];
   const RankEntry v = val[k] + (gfirst[g] - ghead[g]);
-  if (wp_in_bounds(d < out_n && v < out_n, kSiteRankStore)) out[d] = v;
+  if (wp_in_bounds(d < out_n && v < out_n, kSiteRankStore)) {
+    out[d] = v;
+    flag_ranked(flag_cls, flag_n, d);  // (scatter_pairs_kernel)
+  }
 }
 // ... and for a list long enough for the partitioned store (store_ranks): the base is added in place first
 __global__ __launch_bounds__(kBlock) void list_rank_base_kernel(RankEntry *__restrict__ val, const uint32_t *__restrict__ gid,

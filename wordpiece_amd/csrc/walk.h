@@ -34,8 +34,9 @@ struct WalkArgs {
   const uint32_t *ns_from_tile;  // with aflags: first non-space position >= t * kReachTile (n_text: none)
   int all_hard;  // no spacing char occurs inside an eligible multi-char token (every sane vocabulary)
   int32_t n_tokens;  // vocab lines (debug build: range check of the ids that come out of the step table)
-  // default layout: the step table in key space and the round-0 key of every position (scanline.h); nullptr: every
-  // lookup goes through rank[] (reference layout, debug views).  rank[] then only holds the slots of needed groups.
+  // default layout: the step table in key space and the round-0 key of every position (scanline.h) — or, where the
+  // class byte has kClsRanked, the position's slot in its place (step_at); rank is nullptr then, except in the
+  // bounds-checking build.  pkey == nullptr: every lookup goes through rank[] (reference layout, debug views).
   const uint32_t *pkey;
   StepTable ksteps;
   int blanks_dropped;  // round 0 sorted no blank-start suffix: the key-space table has no answer for a blank position
@@ -52,24 +53,46 @@ __device__ __forceinline__ void check_blank_lookup(const WalkArgs &a, uint8_t cl
 #endif
 }
 
-// The value of the step for text position q, from the loads issued for it: the position's round-0 key and rank (the
-// rank is loaded whether it is needed or not: the key-space answer decides that only after two more loads, and a load
-// behind that branch would add a whole chain to the lanes that take it).  The slot-space table answers only for the
-// keys of needed groups — and for every position when the key-space table is off.
-__device__ __forceinline__ int32_t step_value_of(const WalkArgs &a, uint32_t key, uint32_t r, bool prefix) {
-  if (a.pkey) {
-    const int32_t v = step_raw(a.ksteps, key, prefix);
-    if (v != kStepNeeded) return v;
-  }
-  return step_raw(a.steps, r, prefix);
+// The value of the step for text position q — the one lookup of every walk kernel.  cb: the class byte of q, which the
+// caller holds anyway (it is loaded beside the word below, not behind it).
+//
+// Key lookup, "rank in the key's place": ONE 4-byte word per position, pkey[q].  It is the position's round-0 key, and the
+// key-space table answers — except where the class byte carries kClsRanked: there the rank store has put the position's
+// slot over its key (linear_path.h, rank_out) and the slot-space table answers.  The flag selects the table, the lookup
+// itself is the same single chain: nobody waits for a rank, and no rank table is streamed beside the keys (a load
+// behind a kStepNeeded branch instead would put one more dependent load into nearly every iteration of every wave: with
+// 3 % needed lookups, 1 - 0.97^64 = 86 % of the wave iterations have a lane that takes it).
+//
+// Why the flagged positions are exactly those whose key answers kStepNeeded, at every position a walk can stand on:
+// the key table answers kStepNeeded exactly for the keys of the groups on the needed list (key_steps_flag_kernel marks
+// the steps inside [gfirst, gend) of every such group); every kept suffix with such a key is an entry of that list (a
+// group's run is the equal range of its key, kSiteCandRun), and the trie round's final split stores a rank for every
+// entry; blank-start suffixes, which round 0 may have dropped, are never looked up.  So the fall-through from a
+// kStepNeeded answer to a second lookup does not exist in the release build.  The bounds-checking build keeps the key in
+// pkey[q] and the slot in rank[q], and counts every lookup at which flag and answer disagree (kSiteRankFlag).
+//
+// Without pkey (reference layout, full depth, debug views): every lookup goes through rank[].
+__device__ __forceinline__ int32_t step_at(const WalkArgs &a, size_t q, uint8_t cb, bool prefix) {
+  check_blank_lookup(a, cb);
+  if (!a.pkey) return step_raw(a.steps, rank_of(a.rank[q]), prefix);
+  const uint32_t x = a.pkey[q];
+  const bool ranked = (cb & kClsRanked) != 0;
+#ifdef WP_DEBUG_BOUNDS  // (kRankOverKey is false: x is the key, the slot is in rank[q])
+  const int32_t v = step_raw(a.ksteps, x, prefix);
+  const bool agree = wp_in_bounds((v == kStepNeeded) == ranked, kSiteRankFlag);
+  if (v != kStepNeeded) return v;
+  return agree ? step_raw(a.steps, rank_of(a.rank[q]), prefix) : -1;  // (no flag: no slot was stored here)
+#else
+  StepTable t = a.ksteps;  // a select of the table, field by field (both are kernel arguments: scalar registers)
+  t.pstart = ranked ? a.steps.pstart : t.pstart;
+  t.pval_prefix = ranked ? a.steps.pval_prefix : t.pval_prefix;
+  t.pval_suffix = ranked ? a.steps.pval_suffix : t.pval_suffix;
+  t.shift = ranked ? a.steps.shift : t.shift;
+  t.bfast = ranked ? a.steps.bfast : t.bfast;
+  return step_raw(t, x, prefix);
+#endif
 }
-__device__ __forceinline__ uint32_t step_key(const WalkArgs &a, size_t q) { return a.pkey ? a.pkey[q] : 0u; }
-__device__ __forceinline__ int32_t step_value(const WalkArgs &a, size_t q, bool prefix) {
-  check_blank_lookup(a, a.cls[q]);
-  const uint32_t key = step_key(a, q);
-  const uint32_t r = rank_of(a.rank[q]);
-  return step_value_of(a, key, r, prefix);
-}
+__device__ __forceinline__ int32_t step_value(const WalkArgs &a, size_t q, bool prefix) { return step_at(a, q, a.cls[q], prefix); }
 
 // WP_OPT_KEEP_DEBUG = 2 (wp_linear_debug_fetch 8..11): the lookup of the walk at every text position, for both classes —
 // out[0 .. n_text) the prefix-class id, then the ##-class id, then the two lengths (0 where the id is -1).  Blank
@@ -314,10 +337,7 @@ __device__ __forceinline__ bool walk_finish(const WalkArgs &a, WalkState &s, Out
 template <typename Out>
 __device__ __forceinline__ bool walk_step(const WalkArgs &a, WalkState &s, Out &o) {
   const StepWin W = step_window(a, s.p);
-  check_blank_lookup(a, step_cb(a, W, s.p));
-  const uint32_t key = step_key(a, s.p);
-  const uint32_t r = rank_of(a.rank[s.p]);
-  return walk_finish(a, s, o, W, step_value_of(a, key, r, step_word_prefix(a, W, s.p)));
+  return walk_finish(a, s, o, W, step_at(a, s.p, step_cb(a, W, s.p), step_word_prefix(a, W, s.p)));
 }
 
 template <typename Out>
@@ -423,7 +443,8 @@ __global__ __launch_bounds__(kBlock) void anchor_write_kernel(uint8_t *__restric
       // 4 mask bits -> bit 0 of 4 bytes
       const uint32_t wq = (((wp >> (4 * q)) & 15u) * 0x00204081u) & 0x01010101u;
       const uint32_t aq = (((m >> (4 * q)) & 15u) * 0x00204081u) & 0x01010101u;
-      w[q] = (w[q] & 0x0f0f0f0fu) | (wq << 4) | (aq << 5);
+      // (bit 6, kClsRanked, is the rank store's and stays: both the 16-byte path and the partial tail write w back)
+      w[q] = (w[q] & 0x4f4f4f4fu) | (wq << 4) | (aq << 5);
     }
     if (cnt == kAnchorBytes) {
       *reinterpret_cast<uint4 *>(cls + i) = uint4{w[0], w[1], w[2], w[3]};
@@ -1166,8 +1187,8 @@ __global__ __launch_bounds__(kBlock) void walk_balanced_kernel(Args a, const uin
 // The Linear walk, lean.  The kernel above is generic (Fast and Linear steps) and its Linear step is instruction bound,
 // not memory bound: 200 vector + 150 scalar instructions per token step (class tests through two 64-bit windows,
 // 64-bit positions, the step table's search), with 7 waves per SIMD all wanting the issue port (SQ counters:
-// 12 % of a wave's life issuing x 7 waves).  Here the common step is straight: the rank and 16 class bytes from p on
-// are loaded together, the step table answers from its bucket entry (scanline.h, step_raw), the class byte of the
+// 12 % of a wave's life issuing x 7 waves).  Here the common step is straight: the key (or the slot in its place,
+// step_at) and 16 class bytes from p on are loaded together, the step table answers from its bucket entry (scanline.h, step_raw), the class byte of the
 // landing position — which carries its word-prefix and anchor bits (anchor_write_kernel) — comes out of the 16 by
 // one field extract, positions are 32-bit.  Everything else (no token: [UNK] and roll back; blank runs; a landing
 // position beyond the window) goes through the generic walk_finish, which redoes the step from the same state.
@@ -1222,12 +1243,10 @@ __global__ __launch_bounds__(kBlock) void walk_lean_kernel(WalkArgs a, const uin
     if (active) {
       bool done = true;
       if (p < end) {
-        const uint32_t key = step_key(a, p);
-        const uint32_t r = rank_of(a.rank[p]);
         uint32_t cw[4];  // class bytes of p .. p + 15 (the array has 16 bytes of slack behind the text)
         __builtin_memcpy(cw, a.cls + p, 16);
-        const int32_t raw = step_value_of(a, key, r, (cw[0] & kClsWordPrefix) != 0);
-        check_blank_lookup(a, static_cast<uint8_t>(cw[0]));
+        // (the key — or the slot in its place — is loaded beside the class bytes; cw[0] says which table it is for)
+        const int32_t raw = step_at(a, p, static_cast<uint8_t>(cw[0]), (cw[0] & kClsWordPrefix) != 0);
         const int32_t id = step_id(a.steps, raw);
         bool fast = id >= 0 && wp_in_bounds(id < a.n_tokens, kSiteTokenId);
         uint32_t len = 0, p2 = 0, f = 0;

@@ -2,7 +2,7 @@
 // device code is compiled in: the entry points (out-pointers, the answers that need no device, uploads and downloads),
 // the pinned pool, the multi-GPU, batch, stream, file and external calls.  The device path itself: linear_path.h
 // (word_piece::linear, stage by stage) and fast_path.h (word_piece::fast); the layers on top of it, one host header
-// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h, quality_path.h; what a handle owns
+// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h, quality_path.h, repetition_path.h; what a handle owns
 // on a device: context.h.
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -35,6 +35,7 @@
 #include "neardup_path.h"
 #include "overlap_path.h"
 #include "quality_path.h"
+#include "repetition_path.h"
 #include "repeat_path.h"
 #include "pack_path.h"
 #include "rows_path.h"
@@ -1726,6 +1727,60 @@ int wp_quality_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row
       return;
     }
     quality_on_device(v, get_context(v), in, plan, d_out);
+  });
+}
+
+}  // extern "C"
+
+// ---- repetition signals (include/wordpiece_amd_repetition.h; host path: repetition_path.h) ----------------------------
+extern "C" {
+
+int wp_get_repetition_stats(const wp_vocab *v, wp_repetition_stats *out) {
+  *out = v->stats.repetition;
+  if (!v->stats.repetition_call) out->n_rows = -1;
+  return WP_OK;
+}
+
+int wp_repetition_rows(wp_vocab *v, const void *data, const int64_t *row_off, size_t n_rows, const wp_repetition_spec *spec, wp_repetition_result *out) {
+  return guarded([&] {
+    if (out) *out = wp_repetition_result{};
+    const RepetitionPlan plan = check_repetition_spec(spec, out);
+    check_repetition_rows(row_off, n_rows);
+    const unsigned long long n_bytes = check_ragged_host("repetition", data, row_off, n_rows, 1);
+    if (n_rows == 0) {  // (nothing to hand out: every pointer of the result stays NULL)
+      begin_repetition_stats(v, 0);
+      return;
+    }
+    if (n_bytes == 0) {
+      *out = repetition_no_bytes(v, plan, n_rows);
+      return;
+    }
+    Context *c = get_context(v);
+    const RaggedIn in = upload_ragged(c->repetition_in, c->stream, data, row_off, n_rows, static_cast<size_t>(n_bytes), 1);
+    wp_repetition_result d;
+    repetition_on_device(v, c, in, plan, &d);
+    wp_repetition_result h = d;
+    Downloads down(c->stream);
+    down.swap(&h.signals, n_rows * WP_RPT_SIGNALS * sizeof(int64_t));
+    down.swap(&h.reasons, n_rows * sizeof(uint32_t));
+    swap_compact(down, h, h.n_kept, 1);
+    down.finish();
+    *out = h;
+  });
+}
+
+int wp_repetition_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row_off, size_t n_rows, const wp_repetition_spec *spec,
+                              wp_repetition_result *d_out) {
+  return guarded([&] {
+    if (d_out) *d_out = wp_repetition_result{};
+    const RepetitionPlan plan = check_repetition_spec(spec, d_out);
+    check_repetition_rows(d_row_off, n_rows);
+    const RaggedIn in = device_batch("repetition", d_data, d_row_off, n_rows, 1);
+    if (n_rows == 0) {  // (nothing to read and nothing to hand out: every pointer of the result stays NULL)
+      begin_repetition_stats(v, 0);
+      return;
+    }
+    repetition_on_device(v, get_context(v), in, plan, d_out);
   });
 }
 

@@ -101,6 +101,8 @@ struct QualLists {
   // per line: the same with the characters
   uint32_t *lstart, *lrow, *lc0, *lend, *lc1;
   size_t n_words, n_lines;
+  // optional, per word as lc0 and lc1 per line: the characters in front of its start and of its end (repetition.h)
+  uint32_t *wc0, *wc1;
 };
 
 // Tile blockIdx.x of the bytes (n_bytes >= 1, n_rows >= 1).  tiles: kQualKinds arrays of nt1 entries.  WRITE false: the
@@ -307,6 +309,7 @@ __global__ __launch_bounds__(kBlock) void qual_class_kernel(const uint8_t *__res
           out.wstart[iw] = p;
           out.wrow[iw] = rj[j];
           out.wa0[iw] = al;
+          if (out.wc0) out.wc0[iw] = ch;
         }
         iw++;
       }
@@ -317,6 +320,7 @@ __global__ __launch_bounds__(kBlock) void qual_class_kernel(const uint8_t *__res
         if (wp_checked(ie < out.n_words, kSiteQuality)) {
           out.wend[ie] = p + (len ? len : 1);
           out.wa1[ie] = al;
+          if (out.wc1) out.wc1[ie] = ch;
         }
         ie++;
       }

@@ -1,6 +1,6 @@
 // context.h — what a vocabulary handle owns on a device: streams, vocabulary tables, bump arenas, the pool of parked
 // contexts (the C ABI itself is in encoder.hip; the device path in linear_path.h and fast_path.h, the layers on top of
-// it in rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h, quality_path.h and repetition_path.h).
+// it in rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h, quality_path.h, repetition_path.h and lines_path.h).
 #pragma once
 #include <array>
 #include <cstring>
@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/wordpiece_amd.h"
+#include "../../include/wordpiece_amd_lines.h"
 #include "../../include/wordpiece_amd_repetition.h"
 #include "code.h"
 #include "decode.h"
@@ -156,7 +157,7 @@ static int bit_length(uint64_t v) {
 // c->d_scalars: kScalars 32-bit words that kernels and scans leave their totals in; c->h_scalars: the pinned mirror the
 // host reads them from.  Every word has a name here and nowhere else; no call site names a number.  An encode clears
 // the whole block when it starts (and the pre-pass of WP_OPT_NORMALIZE in front of it does the same, see below).
-constexpr int kScalars = 288;
+constexpr int kScalars = 330;
 constexpr int kScalarCps = 0;       // code points of the text, 32 bits: the decode scan (linear, fast) -> host
 constexpr int kScalarAlphabet = 1;  // alphabet size: alphabet_prefix_kernel -> host
 constexpr int kScalarInvalid = 2;   // invalid sequences, 64 bits (words 2, 3): decode_count_kernel / norm_count_kernel -> host
@@ -247,6 +248,11 @@ constexpr int kScalarQualLines = 201, kScalarQualOutBytes = 202, kScalarFree203 
 // two free words
 constexpr int kScalarRptBad = 252, kScalarRptKept = 253, kScalarRptElems = 254, kScalarRptWindows = 256, kScalarRptWords = 258;
 constexpr int kScalarRptLines = 259, kScalarRptOutBytes = 260, kScalarFree261 = 261, kScalarRpt = 262, kScalarFree286 = 286;
+// line filter (lines.h): the first bad row (~0: none) / the kept rows / row_off[n_rows], 64 bits (words 290, 291) / what
+// the shared row kernel counts as windows, 64 bits (words 292, 293: the bytes again, not read) / the words / the lines /
+// the bytes of the compact form / the bytes the dropped lines own / the 64-bit counters of a call (words 298..329, LfCounter)
+constexpr int kScalarLfBad = 288, kScalarLfKept = 289, kScalarLfElems = 290, kScalarLfWindows = 292, kScalarLfWords = 294;
+constexpr int kScalarLfLines = 295, kScalarLfOutBytes = 296, kScalarLfDropped = 297, kScalarLf = 298;
 // normalize_on_device runs in front of the encode, which clears the block again: while it runs, four slots mean
 constexpr int kScalarNormBytes = kScalarCps;           // bytes of the normalised text, 32 bits: its scan
 constexpr int kScalarNormCps = kScalarAlphabet;        // code points of the normalised text (offsets mode) -> host
@@ -291,7 +297,10 @@ constexpr ScalarRange kScalarLayout[] = {
     {kScalarQual, 48},
     {kScalarRptBad, 1},      {kScalarRptKept, 1},     {kScalarRptElems, 2},       {kScalarRptWindows, 2},
     {kScalarRptWords, 1},    {kScalarRptLines, 1},    {kScalarRptOutBytes, 1},    {kScalarFree261, 1},
-    {kScalarRpt, 24},        {kScalarFree286, 2}};
+    {kScalarRpt, 24},        {kScalarFree286, 2},
+    {kScalarLfBad, 1},       {kScalarLfKept, 1},      {kScalarLfElems, 2},        {kScalarLfWindows, 2},
+    {kScalarLfWords, 1},     {kScalarLfLines, 1},     {kScalarLfOutBytes, 1},     {kScalarLfDropped, 1},
+    {kScalarLf, 32}};
 // one past the last word of the range `slot` lies in: where a download or a clear "through" that slot ends
 constexpr int scalar_end(int slot) {
   for (const ScalarRange &r : kScalarLayout) {
@@ -420,6 +429,10 @@ struct Context {
   // reasons of the last call), the tile counts, the per-word arrays of the lists, the sorts and the run passes, and the
   // compact form of the last call
   DeviceBuffer repetition_in, repetition_rows, repetition_items, repetition_lists, repetition_out;
+  // line filter (lines.h): the data and the offsets of a host call, the per-row arrays (with signals and reasons of the
+  // last call), the tile counts and the phrase table, the lists with the per-line arrays and those of the duplicate
+  // stage, and the cut with the compact form of the last call
+  DeviceBuffer lines_in, lines_rows, lines_items, lines_lists, lines_out;
   uint16_t *d_class_index = nullptr;
   uint8_t *d_class_pages = nullptr;
   // WP_OPT_NORMALIZE (normalize.h): the tables (uploaded with the first normalising call), the normalised text, the
@@ -465,7 +478,7 @@ struct Context {
     size_t n = 0, n_text = 0;
   } dbg;
   // every DeviceBuffer above, for destroy_context, release_arenas and park_context: a new buffer is one more name here
-  std::array<DeviceBuffer *, 59> buffers() {
+  std::array<DeviceBuffer *, 64> buffers() {
     return {&text_buf, &a_buf,    &b_buf,   &fmt_buf,    &text_buf2, &ids_stage[0], &ids_stage[1], &rows_in,   &rows_out,
             &pad_buf,  &inputs_buf, &norm_buf, &norm_aux, &norm_map, &detok_in,     &detok_aux,    &detok_out,
             &pack_in,  &pack_plan,  &pack_tab, &pack_out, &special_text, &special_in, &special_lit, &special_out,
@@ -474,7 +487,8 @@ struct Context {
             &overlap_in, &overlap_ref_in, &overlap_rows, &overlap_items, &overlap_out,
             &repeat_in, &repeat_rows, &repeat_items, &repeat_out,
             &quality_in, &quality_rows, &quality_items, &quality_lists, &quality_out,
-            &repetition_in, &repetition_rows, &repetition_items, &repetition_lists, &repetition_out};
+            &repetition_in, &repetition_rows, &repetition_items, &repetition_lists, &repetition_out,
+            &lines_in, &lines_rows, &lines_items, &lines_lists, &lines_out};
   }
   Context() = default;
   Context(const Context &) = delete;
@@ -560,6 +574,8 @@ struct EncodeStats : wp_stats {
   int32_t quality_call;
   wp_repetition_stats repetition;  // wp_get_repetition_stats: filled by a repetition call (repetition_call 1), zero otherwise
   int32_t repetition_call;
+  wp_lines_stats lines;  // wp_get_lines_stats: filled by a line-filter call (lines_call 1), zero otherwise
+  int32_t lines_call;
 };
 
 #ifndef WP_LATE_REFINE_DEFAULT

@@ -2,7 +2,7 @@
 // device code is compiled in: the entry points (out-pointers, the answers that need no device, uploads and downloads),
 // the pinned pool, the multi-GPU, batch, stream, file and external calls.  The device path itself: linear_path.h
 // (word_piece::linear, stage by stage) and fast_path.h (word_piece::fast); the layers on top of it, one host header
-// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h, quality_path.h, repetition_path.h; what a handle owns
+// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h, quality_path.h, repetition_path.h, lines_path.h; what a handle owns
 // on a device: context.h.
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -33,6 +33,7 @@
 #include "linear_path.h"
 #include "mask_path.h"
 #include "neardup_path.h"
+#include "lines_path.h"
 #include "overlap_path.h"
 #include "quality_path.h"
 #include "repetition_path.h"
@@ -1781,6 +1782,66 @@ int wp_repetition_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_
       return;
     }
     repetition_on_device(v, get_context(v), in, plan, d_out);
+  });
+}
+
+}  // extern "C"
+
+// ---- line filter (include/wordpiece_amd_lines.h; host path: lines_path.h) ----------------------------------------------
+extern "C" {
+
+int wp_get_lines_stats(const wp_vocab *v, wp_lines_stats *out) {
+  *out = v->stats.lines;
+  if (!v->stats.lines_call) out->n_rows = -1;
+  return WP_OK;
+}
+
+int wp_filter_lines(wp_vocab *v, const void *data, const int64_t *row_off, size_t n_rows, const wp_lines_spec *spec, wp_lines_result *out) {
+  return guarded([&] {
+    if (out) *out = wp_lines_result{};
+    const LinesPlan plan = check_lines_spec(spec, out);
+    check_lines_rows(row_off, n_rows);
+    const unsigned long long n_bytes = check_ragged_host("lines", data, row_off, n_rows, 1);
+    if (n_rows == 0) {  // (nothing to hand out: every pointer of the result stays NULL)
+      begin_lines_stats(v, 0);
+      return;
+    }
+    if (n_bytes == 0) {
+      *out = lines_no_bytes(v, plan, n_rows);
+      return;
+    }
+    Context *c = get_context(v);
+    const RaggedIn in = upload_ragged(c->lines_in, c->stream, data, row_off, n_rows, static_cast<size_t>(n_bytes), 1);
+    wp_lines_result d;
+    lines_on_device(v, c, in, plan, &d);
+    wp_lines_result h = d;
+    Downloads down(c->stream);
+    const size_t nl = static_cast<size_t>(h.n_lines);
+    down.swap(&h.signals, n_rows * WP_LF_SIGNALS * sizeof(int64_t));
+    down.swap(&h.reasons, n_rows * sizeof(uint32_t));
+    down.swap(&h.line_row, nl * sizeof(int32_t));
+    down.swap(&h.line_start, nl * sizeof(int64_t));
+    down.swap(&h.line_len, nl * sizeof(int32_t));
+    down.swap(&h.line_reasons, nl * sizeof(uint32_t));
+    down.swap(&h.cut_off, (n_rows + 1) * sizeof(int64_t));
+    down.swap(&h.cut_data, static_cast<size_t>(h.n_cut_elems));
+    swap_compact(down, h, h.n_kept, 1);
+    down.finish();
+    *out = h;
+  });
+}
+
+int wp_filter_lines_device(wp_vocab *v, const void *d_data, const int64_t *d_row_off, size_t n_rows, const wp_lines_spec *spec, wp_lines_result *d_out) {
+  return guarded([&] {
+    if (d_out) *d_out = wp_lines_result{};
+    const LinesPlan plan = check_lines_spec(spec, d_out);
+    check_lines_rows(d_row_off, n_rows);
+    const RaggedIn in = device_batch("lines", d_data, d_row_off, n_rows, 1);
+    if (n_rows == 0) {  // (nothing to read and nothing to hand out: every pointer of the result stays NULL)
+      begin_lines_stats(v, 0);
+      return;
+    }
+    lines_on_device(v, get_context(v), in, plan, d_out);
   });
 }
 

@@ -2,6 +2,7 @@
 words and lines from tests/quality_model.py; phrases by a fold and a slice comparison at every position; duplicate lines
 through a dict over the line bytes; the cut by joining what is not owned by a dropped line."""
 import bisect
+import itertools
 
 import quality_model as Q
 
@@ -113,7 +114,7 @@ def filter_lines(data, row_off, rules=None, phrases=(), doc_phrases=(), bounded=
         sig.append(s)
         reasons.append(doc_reasons(s, doc_limit))
     kept = [i for i in range(n) if reasons[i] == 0]
-    offsets = lambda rows: [sum(len(r) for r in rows[:k]) for k in range(len(rows) + 1)]
+    offsets = lambda rows: list(itertools.accumulate((len(r) for r in rows), initial=0))
     total = lambda name: sum(s[S[name]] for s in sig)
     stats = dict(n_rows=n, n_bytes=total("bytes"), n_lines=len(lines), n_kept_lines=total("kept_lines"), n_kept_bytes=total("kept_bytes"), n_kept=len(kept),
                  line_failed=[total("failed_%d" % k) for k in range(6)], rule_failed=[sum(1 for r in reasons if r >> k & 1) for k in range(4)],

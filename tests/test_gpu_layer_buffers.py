@@ -1,7 +1,7 @@
 """GPU tests (-m gpu) of the device buffers of the layers on top of the encoder (csrc/rows_path.h, inputs_path.h,
 mask_path.h, detok_path.h, pack_path.h, the pre-pass of csrc/normalize.h, and the grouping layers: count_path.h,
-learn_path.h, dedup_path.h, neardup_path.h over group_path.h, overlap_path.h and repeat_path.h over window_path.h) across
-the calls of one handle.  Every layer lays its buffers out with an Arena over a DeviceBuffer that grows when a call needs
+learn_path.h, dedup_path.h, neardup_path.h over group_path.h, overlap_path.h and repeat_path.h over window_path.h,
+quality_path.h, repetition_path.h and lines_path.h over text_path.h) across the calls of one handle.  Every layer lays its buffers out with an Arena over a DeviceBuffer that grows when a call needs
 more than it holds, and two mistakes
 show only from one call to the next: a sequence of allocations that differs between the planning pass and the real one,
 and a pointer kept across a regrowth.  So every layer is called small, then large enough to make its buffers grow, then
@@ -12,6 +12,7 @@ A DeviceBuffer keeps bytes / 16 + 1 MiB of slack: a layer's sequence starts from
 small call allocates about 1 MiB and the large one needs GROW bytes or more (asserted case by case).  The small cases
 hold 31 rows and 64 ids: 32 row_splits and 64 ids are 256 bytes each, where the arena's rounding to 256 bytes adds
 nothing behind an array; 8 rows is the other small size."""
+import functools
 import random
 
 import numpy as np
@@ -22,14 +23,19 @@ import dedup_model as DDM
 import detok_model as DM
 import inputs_model as I
 import learn_model as LM
+import lines_model as LFM
 import mask_model as MM
 import neardup_model as NDM
 import normalize_model as NM
 import overlap_model as OM
 import pack_model as PM
+import quality_model as QM
 import repeat_model as RM
+import repetition_model as RPM
 import rows_model as R
 import wordpiece_amd as W
+from wordpiece_amd import lines as LF
+from wordpiece_amd import repetition as RP
 
 LETTERS = "abcdefghijklmnopqrstuvwxyz"
 VOCAB = ["[UNK]", "[CLS]", "[SEP]", "[PAD]", "[MASK]"] + list(LETTERS) + ["##" + ch for ch in LETTERS] + ["é", "##é"]
@@ -526,3 +532,158 @@ def test_repeat_rows(gv):
     assert n_elems + 8 * (N_RAGGED + 1) > GROW and 14 * 4 * N_RAGGED > GROW and 5 * 4 * n_elems > GROW
     assert 12 * n_kept + 8 * (N_RAGGED + 1) + 2 * n_elems > GROW
     small_then_large(gv, run, text(_cells(31, 0, 103)), large, text(_cells(8, 4, 104)))
+
+
+# ---- the text-signal layers (quality_path.h, repetition_path.h, lines_path.h) --------------------------------------------
+
+N_TEXT = 6000  # rows of the large batch of the three layers
+
+
+def _text_doc(rng, n_lines, n_same):
+    """n_lines lines of 1 to 8 words, the first one of six words said n_same times more: a duplicate line and 5-gram per row"""
+    word = lambda: "".join(rng.choice(LETTERS[:8]) for _ in range(rng.randint(2, 6)))
+    lines = [" ".join(word() for _ in range(6 if k == 0 else rng.randint(1, 8))) + rng.choice((".", "", "!")) for k in range(n_lines)]
+    return "\n".join(lines + lines[:1] * n_same).encode()
+
+
+def _text_pool():
+    rng = random.Random(105)
+    return [_text_doc(rng, rng.randint(4, 14), rng.choice((1, 1, 2, 6))) for _ in range(48)]
+
+
+TEXT_POOL = _text_pool()
+
+
+def _text_rows(n_rows, seed):
+    """n_rows documents drawn from TEXT_POOL: (data uint8, row_off)"""
+    rng = random.Random(seed)
+    rows = [rng.choice(TEXT_POOL) for _ in range(n_rows)]
+    off = np.zeros(n_rows + 1, dtype=np.int64)
+    np.cumsum([len(r) for r in rows], out=off[1:])
+    return np.frombuffer(b"".join(rows), dtype=np.uint8), off
+
+
+def _text_small(cells):
+    """the 64 / 32 cells of a small case as text: letters, spaces and line feeds"""
+    return np.frombuffer(b"ab \nab c\n"[:8], dtype=np.uint8)[cells[0] % 8].copy(), cells[1]
+
+
+def _text_equal(got, exp, keys, n_signals):
+    """the arrays of a quality, repetition or line-filter result against the model's; `keys`: what the call was asked for"""
+    assert sorted(got) == sorted(keys)
+    for k in got:
+        if k in ("data", "cut_data"):
+            assert got[k].tobytes() == exp[k], k
+        elif k == "signals":
+            assert np.array_equal(got[k], np.asarray(exp[k], dtype=np.int64).reshape(n_signals, -1)), k
+        else:
+            assert got[k].tolist() == exp[k], k
+
+
+@pytest.fixture
+def per_document(monkeypatch):
+    """the per-row functions of the three models behind a cache by document: the large batch draws its rows from TEXT_POOL"""
+    monkeypatch.setattr(QM, "signals_of_row", functools.lru_cache(maxsize=None)(QM.signals_of_row))
+    monkeypatch.setattr(RPM, "signals_of_row", functools.lru_cache(maxsize=None)(RPM.signals_of_row))
+    lines_of_row = functools.lru_cache(maxsize=None)(LFM.lines_of_row)
+
+    def fresh(row, line_limit, phrases):  # (filter_lines writes the duplicate bit into the dicts it gets)
+        ls, doc_hits, hits = lines_of_row(row, tuple(line_limit), tuple(phrases))
+        return [dict(ln) for ln in ls], doc_hits, hits
+    monkeypatch.setattr(LFM, "lines_of_row", fresh)
+
+
+def _text_sizes(large, exp_stats):
+    """(n_bytes, n_words, n_lines) of the large batch, the words from the per-document model"""
+    data, off = large
+    n_words = sum(QM.signals_of_row(data[off[i]:off[i + 1]].tobytes(), (), 30, True)[QM.S["words"]] for i in range(len(off) - 1))
+    return data.size, n_words, exp_stats["n_lines"]
+
+
+@pytest.mark.gpu
+def test_quality_rows(gv, per_document):
+    rules = dict(min_text_words=40)
+
+    def model(case, dup):
+        return QM.quality(case[0].tobytes(), case[1].tolist(), limit=QM.limits(**rules), dup_lines=dup)
+
+    def run(case):
+        data, off = case
+        for want in (True, False):  # (the two layouts of quality_lists and quality_out alternate)
+            exp = model(case, want)
+            got = gv.quality_rows(data, off, rules=rules, dup_lines=want, compact=want, raw=True)
+            _text_equal(got, exp, ("signals", "reasons") + (("kept", "data", "row_off") if want else ()), len(QM.SIGNALS))
+            assert gv.quality_stats() == exp["stats"]
+
+    large = _text_rows(N_TEXT, 106)
+    exp = model(large, True)
+    n_bytes, n_words, n_lines = _text_sizes(large, exp["stats"])
+    n_kept = len(exp["kept"])
+    assert 0 < n_kept < N_TEXT and min(exp["signals"][QM.S["dup_lines"]]) >= 1
+    # the data and the offsets in quality_in; a word, 23 signals and 5 words per row in quality_rows; 5 words per word and
+    # 6 per line in quality_lists; the kept rows, their offsets and the room of the input in quality_out.  quality_items
+    # holds 6 counts per 2048 bytes of text and the stop table: no text a test can afford makes it grow.
+    assert n_bytes + 8 * (N_TEXT + 1) > GROW and (23 * 8 + 6 * 4) * N_TEXT > GROW and 4 * (5 * n_words + 6 * n_lines) > GROW
+    assert 12 * n_kept + n_bytes > GROW
+    small_then_large(gv, run, _text_small(_cells(31, 0, 107)), large, _text_small(_cells(8, 4, 108)))
+
+
+@pytest.mark.gpu
+def test_repetition_rows(gv, per_document):
+    rules = dict(max_dup_5_chars=250)
+
+    def model(case):
+        return RPM.repetition(case[0].tobytes(), case[1].tolist(), limit=RPM.limits(**rules))
+
+    def run(case):
+        data, off = case
+        exp = model(case)
+        for want in (True, False):  # (the two layouts of repetition_out alternate)
+            got = RP.repetition_rows(gv, data, off, rules=rules, compact=want, raw=True)
+            _text_equal(got, exp, ("signals", "reasons") + (("kept", "data", "row_off") if want else ()), len(RPM.SIGNALS))
+            assert RP.repetition_stats(gv) == exp["stats"]
+
+    large = _text_rows(N_TEXT, 109)
+    exp = model(large)
+    n_bytes, n_words, n_kept = large[0].size, exp["stats"]["n_words"], len(exp["kept"])
+    assert 0 < n_kept < N_TEXT and min(exp["signals"][RPM.S["dup_5_chars"]]) >= 1
+    # the data and the offsets in repetition_in; a word, 14 + 3 + 23 sums and 5 words per row in repetition_rows; more than
+    # 30 words per word in repetition_lists; the kept rows, their offsets and the room of the input in repetition_out.
+    # repetition_items holds 6 counts per 2048 bytes of text: no text a test can afford makes it grow.
+    assert n_bytes + 8 * (N_TEXT + 1) > GROW and ((14 + 3 + 23) * 8 + 6 * 4) * N_TEXT > GROW and 30 * 4 * n_words > GROW
+    assert 12 * n_kept + n_bytes > GROW
+    small_then_large(gv, run, _text_small(_cells(31, 0, 110)), large, _text_small(_cells(8, 4, 111)))
+
+
+@pytest.mark.gpu
+def test_filter_lines(gv, per_document):
+    rules = dict(min_words=3, min_kept_lines=6)
+    known = {}
+
+    def model(case, scope):  # (scope 2: one run over the whole batch, kept for the calls that ask for it again)
+        key = (id(case), scope)
+        if key not in known:
+            known[key] = LFM.filter_lines(case[0].tobytes(), case[1].tolist(), rules=rules, dup_scope=scope)
+        return known[key]
+
+    def run(case):
+        data, off = case
+        # (the layouts of lines_lists and lines_out alternate: the per-line arrays, the sort of scope 1, the cut, the compact form)
+        for scope, want in ((0, True), (1, False), (2, True), (1, True), (2, False)):
+            exp = model(case, scope)
+            got = LF.filter_lines(gv, data, off, rules=rules, dup_scope=scope, lines=want, cut=want, compact=want, raw=True)
+            asked = ("line_row", "line_start", "line_len", "line_reasons", "cut_data", "cut_off", "kept", "data", "row_off") if want else ()
+            _text_equal(got, exp, ("signals", "reasons") + asked, len(LFM.SIGNALS))
+            assert LF.lines_stats(gv) == exp["stats"]
+
+    large = _text_rows(N_TEXT, 112)
+    n_bytes, n_words, n_lines = _text_sizes(large, model(large, 0)["stats"])
+    for scope in (0, 1, 2):
+        assert 0 < len(model(large, scope)["kept"]) < N_TEXT
+    assert min(model(large, 1)["signals"][LFM.S["failed_5"]]) >= 1  # (a duplicate line in every row)
+    # the data and the offsets in lines_in; two words, 15 + 23 sums and 5 words per row in lines_rows; 5 words per word
+    # and 11 per line in lines_lists; the offsets of the cut and the room of the input in lines_out, without the compact
+    # form.  lines_items holds 6 counts per 2048 bytes of text and the phrase table: no text a test can afford makes it grow.
+    assert n_bytes + 8 * (N_TEXT + 1) > GROW and ((15 + 23) * 8 + 7 * 4) * N_TEXT > GROW and 4 * (5 * n_words + 11 * n_lines) > GROW
+    assert 8 * (N_TEXT + 1) + n_bytes > GROW
+    small_then_large(gv, run, _text_small(_cells(31, 0, 113)), large, _text_small(_cells(8, 4, 114)))

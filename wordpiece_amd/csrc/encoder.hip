@@ -2,7 +2,7 @@
 // device code is compiled in: the entry points (out-pointers, the answers that need no device, uploads and downloads),
 // the pinned pool, the multi-GPU, batch, stream, file and external calls.  The device path itself: linear_path.h
 // (word_piece::linear, stage by stage) and fast_path.h (word_piece::fast); the layers on top of it, one host header
-// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h, quality_path.h, repetition_path.h, lines_path.h; what a handle owns
+// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h, quality_path.h, repetition_path.h, lines_path.h (the last three over text_path.h); what a handle owns
 // on a device: context.h.
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -1675,6 +1675,57 @@ int wp_repeat_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row_
 
 }  // extern "C"
 
+// ---- the text-signal layers (host paths over text_path.h): the skeleton of their host and of their device entry points --
+// check_spec, begin_stats, no_bytes and on_device: the layer's functions of those names; n_signals: its signals per row;
+// in_buf: where its host batch goes up; more(down, h): the downloads of what it returns beside signals, reasons and
+// the compact form.
+template <typename Result, typename Spec, typename CheckSpec, typename BeginStats, typename NoBytes, typename OnDevice, typename More>
+static int text_rows_host(wp_vocab *v, const TextLayer &L, const void *data, const int64_t *row_off, size_t n_rows, const Spec *spec, Result *out, int n_signals,
+                          DeviceBuffer Context::*in_buf, CheckSpec check_spec, BeginStats begin_stats, NoBytes no_bytes, OnDevice on_device, More more) {
+  return guarded([&] {
+    if (out) *out = Result{};
+    const auto plan = check_spec(spec, out);
+    check_text_rows(L.name, row_off, n_rows);
+    const unsigned long long n_bytes = check_ragged_host(L.name, data, row_off, n_rows, 1);
+    if (n_rows == 0) {  // (nothing to hand out: every pointer of the result stays NULL)
+      begin_stats(v, 0);
+      return;
+    }
+    if (n_bytes == 0) {
+      *out = no_bytes(v, plan, n_rows);
+      return;
+    }
+    Context *c = get_context(v);
+    const RaggedIn in = upload_ragged(c->*in_buf, c->stream, data, row_off, n_rows, static_cast<size_t>(n_bytes), 1);
+    Result d;
+    on_device(v, c, in, plan, &d);
+    Result h = d;
+    Downloads down(c->stream);
+    down.swap(&h.signals, n_rows * n_signals * sizeof(int64_t));
+    down.swap(&h.reasons, n_rows * sizeof(uint32_t));
+    more(down, h);
+    swap_compact(down, h, h.n_kept, 1);
+    down.finish();
+    *out = h;
+  });
+}
+
+template <typename Result, typename Spec, typename CheckSpec, typename BeginStats, typename OnDevice>
+static int text_rows_device(wp_vocab *v, const TextLayer &L, const void *d_data, const int64_t *d_row_off, size_t n_rows, const Spec *spec, Result *d_out,
+                            CheckSpec check_spec, BeginStats begin_stats, OnDevice on_device) {
+  return guarded([&] {
+    if (d_out) *d_out = Result{};
+    const auto plan = check_spec(spec, d_out);
+    check_text_rows(L.name, d_row_off, n_rows);
+    const RaggedIn in = device_batch(L.name, d_data, d_row_off, n_rows, 1);
+    if (n_rows == 0) {  // (nothing to read and nothing to hand out: every pointer of the result stays NULL)
+      begin_stats(v, 0);
+      return;
+    }
+    on_device(v, get_context(v), in, plan, d_out);
+  });
+}
+
 // ---- quality signals (include/wordpiece_amd.h, section "quality signals"; host path: quality_path.h) -------------------
 extern "C" {
 
@@ -1690,45 +1741,12 @@ int32_t wp_quality_class(uint32_t cp) {
 }
 
 int wp_quality_rows(wp_vocab *v, const void *data, const int64_t *row_off, size_t n_rows, const wp_quality_spec *spec, wp_quality_result *out) {
-  return guarded([&] {
-    if (out) *out = wp_quality_result{};
-    const QualityPlan plan = check_quality_spec(spec, out);
-    check_quality_rows(row_off, n_rows);
-    const unsigned long long n_bytes = check_ragged_host("quality", data, row_off, n_rows, 1);
-    if (n_rows == 0) {  // (nothing to hand out: every pointer of the result stays NULL)
-      begin_quality_stats(v, 0);
-      return;
-    }
-    if (n_bytes == 0) {
-      *out = quality_no_bytes(v, plan, n_rows);
-      return;
-    }
-    Context *c = get_context(v);
-    const RaggedIn in = upload_ragged(c->quality_in, c->stream, data, row_off, n_rows, static_cast<size_t>(n_bytes), 1);
-    wp_quality_result d;
-    quality_on_device(v, c, in, plan, &d);
-    wp_quality_result h = d;
-    Downloads down(c->stream);
-    down.swap(&h.signals, n_rows * WP_QUALITY_SIGNALS * sizeof(int64_t));
-    down.swap(&h.reasons, n_rows * sizeof(uint32_t));
-    swap_compact(down, h, h.n_kept, 1);
-    down.finish();
-    *out = h;
-  });
+  return text_rows_host(v, kQualLayer, data, row_off, n_rows, spec, out, WP_QUALITY_SIGNALS, &Context::quality_in, check_quality_spec, begin_quality_stats,
+                        quality_no_bytes, quality_on_device, [](Downloads &, wp_quality_result &) {});
 }
 
 int wp_quality_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row_off, size_t n_rows, const wp_quality_spec *spec, wp_quality_result *d_out) {
-  return guarded([&] {
-    if (d_out) *d_out = wp_quality_result{};
-    const QualityPlan plan = check_quality_spec(spec, d_out);
-    check_quality_rows(d_row_off, n_rows);
-    const RaggedIn in = device_batch("quality", d_data, d_row_off, n_rows, 1);
-    if (n_rows == 0) {  // (nothing to read and nothing to hand out: every pointer of the result stays NULL)
-      begin_quality_stats(v, 0);
-      return;
-    }
-    quality_on_device(v, get_context(v), in, plan, d_out);
-  });
+  return text_rows_device(v, kQualLayer, d_data, d_row_off, n_rows, spec, d_out, check_quality_spec, begin_quality_stats, quality_on_device);
 }
 
 }  // extern "C"
@@ -1743,46 +1761,13 @@ int wp_get_repetition_stats(const wp_vocab *v, wp_repetition_stats *out) {
 }
 
 int wp_repetition_rows(wp_vocab *v, const void *data, const int64_t *row_off, size_t n_rows, const wp_repetition_spec *spec, wp_repetition_result *out) {
-  return guarded([&] {
-    if (out) *out = wp_repetition_result{};
-    const RepetitionPlan plan = check_repetition_spec(spec, out);
-    check_repetition_rows(row_off, n_rows);
-    const unsigned long long n_bytes = check_ragged_host("repetition", data, row_off, n_rows, 1);
-    if (n_rows == 0) {  // (nothing to hand out: every pointer of the result stays NULL)
-      begin_repetition_stats(v, 0);
-      return;
-    }
-    if (n_bytes == 0) {
-      *out = repetition_no_bytes(v, plan, n_rows);
-      return;
-    }
-    Context *c = get_context(v);
-    const RaggedIn in = upload_ragged(c->repetition_in, c->stream, data, row_off, n_rows, static_cast<size_t>(n_bytes), 1);
-    wp_repetition_result d;
-    repetition_on_device(v, c, in, plan, &d);
-    wp_repetition_result h = d;
-    Downloads down(c->stream);
-    down.swap(&h.signals, n_rows * WP_RPT_SIGNALS * sizeof(int64_t));
-    down.swap(&h.reasons, n_rows * sizeof(uint32_t));
-    swap_compact(down, h, h.n_kept, 1);
-    down.finish();
-    *out = h;
-  });
+  return text_rows_host(v, kRptLayer, data, row_off, n_rows, spec, out, WP_RPT_SIGNALS, &Context::repetition_in, check_repetition_spec, begin_repetition_stats,
+                        repetition_no_bytes, repetition_on_device, [](Downloads &, wp_repetition_result &) {});
 }
 
 int wp_repetition_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row_off, size_t n_rows, const wp_repetition_spec *spec,
                               wp_repetition_result *d_out) {
-  return guarded([&] {
-    if (d_out) *d_out = wp_repetition_result{};
-    const RepetitionPlan plan = check_repetition_spec(spec, d_out);
-    check_repetition_rows(d_row_off, n_rows);
-    const RaggedIn in = device_batch("repetition", d_data, d_row_off, n_rows, 1);
-    if (n_rows == 0) {  // (nothing to read and nothing to hand out: every pointer of the result stays NULL)
-      begin_repetition_stats(v, 0);
-      return;
-    }
-    repetition_on_device(v, get_context(v), in, plan, d_out);
-  });
+  return text_rows_device(v, kRptLayer, d_data, d_row_off, n_rows, spec, d_out, check_repetition_spec, begin_repetition_stats, repetition_on_device);
 }
 
 }  // extern "C"
@@ -1797,52 +1782,20 @@ int wp_get_lines_stats(const wp_vocab *v, wp_lines_stats *out) {
 }
 
 int wp_filter_lines(wp_vocab *v, const void *data, const int64_t *row_off, size_t n_rows, const wp_lines_spec *spec, wp_lines_result *out) {
-  return guarded([&] {
-    if (out) *out = wp_lines_result{};
-    const LinesPlan plan = check_lines_spec(spec, out);
-    check_lines_rows(row_off, n_rows);
-    const unsigned long long n_bytes = check_ragged_host("lines", data, row_off, n_rows, 1);
-    if (n_rows == 0) {  // (nothing to hand out: every pointer of the result stays NULL)
-      begin_lines_stats(v, 0);
-      return;
-    }
-    if (n_bytes == 0) {
-      *out = lines_no_bytes(v, plan, n_rows);
-      return;
-    }
-    Context *c = get_context(v);
-    const RaggedIn in = upload_ragged(c->lines_in, c->stream, data, row_off, n_rows, static_cast<size_t>(n_bytes), 1);
-    wp_lines_result d;
-    lines_on_device(v, c, in, plan, &d);
-    wp_lines_result h = d;
-    Downloads down(c->stream);
-    const size_t nl = static_cast<size_t>(h.n_lines);
-    down.swap(&h.signals, n_rows * WP_LF_SIGNALS * sizeof(int64_t));
-    down.swap(&h.reasons, n_rows * sizeof(uint32_t));
-    down.swap(&h.line_row, nl * sizeof(int32_t));
-    down.swap(&h.line_start, nl * sizeof(int64_t));
-    down.swap(&h.line_len, nl * sizeof(int32_t));
-    down.swap(&h.line_reasons, nl * sizeof(uint32_t));
-    down.swap(&h.cut_off, (n_rows + 1) * sizeof(int64_t));
-    down.swap(&h.cut_data, static_cast<size_t>(h.n_cut_elems));
-    swap_compact(down, h, h.n_kept, 1);
-    down.finish();
-    *out = h;
-  });
+  return text_rows_host(v, kLfLayer, data, row_off, n_rows, spec, out, WP_LF_SIGNALS, &Context::lines_in, check_lines_spec, begin_lines_stats, lines_no_bytes,
+                        lines_on_device, [n_rows](Downloads &down, wp_lines_result &h) {
+                          const size_t nl = static_cast<size_t>(h.n_lines);
+                          down.swap(&h.line_row, nl * sizeof(int32_t));
+                          down.swap(&h.line_start, nl * sizeof(int64_t));
+                          down.swap(&h.line_len, nl * sizeof(int32_t));
+                          down.swap(&h.line_reasons, nl * sizeof(uint32_t));
+                          down.swap(&h.cut_off, (n_rows + 1) * sizeof(int64_t));
+                          down.swap(&h.cut_data, static_cast<size_t>(h.n_cut_elems));
+                        });
 }
 
 int wp_filter_lines_device(wp_vocab *v, const void *d_data, const int64_t *d_row_off, size_t n_rows, const wp_lines_spec *spec, wp_lines_result *d_out) {
-  return guarded([&] {
-    if (d_out) *d_out = wp_lines_result{};
-    const LinesPlan plan = check_lines_spec(spec, d_out);
-    check_lines_rows(d_row_off, n_rows);
-    const RaggedIn in = device_batch("lines", d_data, d_row_off, n_rows, 1);
-    if (n_rows == 0) {  // (nothing to read and nothing to hand out: every pointer of the result stays NULL)
-      begin_lines_stats(v, 0);
-      return;
-    }
-    lines_on_device(v, get_context(v), in, plan, d_out);
-  });
+  return text_rows_device(v, kLfLayer, d_data, d_row_off, n_rows, spec, d_out, check_lines_spec, begin_lines_stats, lines_on_device);
 }
 
 }  // extern "C"

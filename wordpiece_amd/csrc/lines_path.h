@@ -1,17 +1,15 @@
 // lines_path.h — the line filter on a context (include/wordpiece_amd_lines.h; kernels: lines.h): the argument rules and
 // the phrase table, the answer of a call without bytes, the launches over one device batch and the buffers of a call.
-// The intake and the kept rows are window_path.h's, the class passes and the lists quality.h's, and the duplicate lines
-// come from dedup_path.h's search over the lines.
+// The intake, the class pass with the lists, the order of the lines by (row, first equal line) and the end of a call are
+// text_path.h's.
 #pragma once
 #include <algorithm>
 #include <numeric>
 #include <vector>
 
 #include "context.h"
-#include "dedup_path.h"
 #include "lines.h"
-#include "quality_path.h"
-#include "window_path.h"
+#include "text_path.h"
 
 namespace wp {
 
@@ -99,10 +97,10 @@ static LinesPlan check_lines_spec(const wp_lines_spec *spec, const wp_lines_resu
   return p;
 }
 
-static void check_lines_rows(const void *row_off, size_t n_rows) {
-  if (n_rows != 0 && !row_off) throw std::invalid_argument("lines: row_off is NULL");
-  check_row_count("lines", n_rows, " in row_off");
-}
+static_assert(kLfCounters <= kTextMaxCounters, "the counters of a text-signal layer");
+constexpr TextLayer kLfLayer{"lines", "line filter", "gathers or stores outside the tile, word, line, signal or cut arrays skipped",
+                             kScalarLfBad, kScalarLfKept, kScalarLfElems, kScalarLfWindows, kScalarLfWords, kScalarLfLines, kScalarLfOutBytes,
+                             kScalarLf, kLfCounters};
 
 static wp_lines_stats &begin_lines_stats(wp_vocab *v, size_t n_rows) {
   v->stats.lines_call = 1;
@@ -111,29 +109,13 @@ static wp_lines_stats &begin_lines_stats(wp_vocab *v, size_t n_rows) {
   return v->stats.lines;
 }
 
-// A host call whose batch has no byte (n_rows >= 1): no device needed.  Every signal is 0, no row has a line, and the
-// reasons are the document rules over zeros, the same for every row; the cut rows are the empty rows themselves.
+// A host call whose batch has no byte (n_rows >= 1): the document rules over zeros (text_path.h); no row has a line, and
+// the cut rows are the empty rows themselves.
 static wp_lines_result lines_no_bytes(wp_vocab *v, const LinesPlan &plan, size_t n_rows) {
-  wp_lines_stats &ps = begin_lines_stats(v, n_rows);
   const long long zeros[WP_LF_SIGNALS] = {};
-  const uint32_t reasons = lines_reasons(zeros, plan.lim);
-  wp_lines_result h{};
-  h.n_rows = static_cast<int64_t>(n_rows);
-  h.signals = static_cast<int64_t *>(zeroed(n_rows * WP_LF_SIGNALS * sizeof(int64_t)));
-  h.reasons = static_cast<uint32_t *>(zeroed(n_rows * sizeof(uint32_t)));
-  std::fill(h.reasons, h.reasons + n_rows, reasons);
-  const size_t n_kept = reasons == 0 ? n_rows : 0;
-  ps.n_kept = static_cast<int64_t>(n_kept);
-  for (int k = 0; k < WP_LF_DOC_RULES; k++) ps.rule_failed[k] = (reasons >> k) & 1u ? static_cast<int64_t>(n_rows) : 0;
+  wp_lines_result h = text_no_bytes<wp_lines_result>(begin_lines_stats(v, n_rows), n_rows, WP_LF_SIGNALS, WP_LF_DOC_RULES, lines_reasons(zeros, plan.lim),
+                                                     plan.want_compact);
   if (plan.want_cut) h.cut_off = static_cast<int64_t *>(zeroed((n_rows + 1) * sizeof(int64_t)));
-  if (plan.want_compact) {
-    h.n_kept = static_cast<int64_t>(n_kept);
-    if (n_kept != 0) {
-      h.kept = static_cast<int32_t *>(zeroed(n_kept * sizeof(int32_t)));
-      for (size_t r = 0; r < n_kept; r++) h.kept[r] = static_cast<int32_t>(r);
-    }
-    h.row_off = static_cast<int64_t *>(zeroed((n_kept + 1) * sizeof(int64_t)));
-  }
   return h;
 }
 
@@ -145,6 +127,7 @@ static wp_lines_result lines_no_bytes(wp_vocab *v, const LinesPlan &plan, size_t
 // so a segmented sum would also do, but it would need the row boundaries in the line list and a pass per signal; the
 // atomics are one pass, order-free because they are integer adds, and a line adds only what is not zero.
 static void lines_on_device(wp_vocab *v, Context *c, const RaggedIn &in, const LinesPlan &plan, wp_lines_result *R) {
+  const TextLayer &L = kLfLayer;
   const size_t n = in.n_rows;
   wp_lines_stats &ps = begin_lines_stats(v, n);
   *R = wp_lines_result{};
@@ -159,89 +142,53 @@ static void lines_on_device(wp_vocab *v, Context *c, const RaggedIn &in, const L
   // ---- the per-row arrays, the offset check --------------------------------------------------------------------------------
   const size_t n1 = n + 1;
   Arena ra(&c->lines_rows, guard);
-  uint32_t *d_boff = nullptr, *d_cut_boff = nullptr, *d_reasons = nullptr, *d_keep = nullptr, *d_keep_pos = nullptr, *d_out_len = nullptr, *d_out_pos = nullptr,
-           *d_stmp = nullptr;
-  long long *d_sig = nullptr;
+  TextRows rows;
+  uint32_t *d_cut_boff = nullptr;
   unsigned long long *d_qsig = nullptr;
   for (int pass = 0; pass < 2; pass++) {
-    d_boff = ra.take<uint32_t>(n1);
+    rows.take(ra, n, WP_LF_SIGNALS);
     d_cut_boff = ra.take<uint32_t>(n1);
-    d_sig = ra.take<long long>(n * WP_LF_SIGNALS);
     d_qsig = ra.take<unsigned long long>(n * WP_QUALITY_SIGNALS);  // what the class pass sums beside its counts: not read
-    d_reasons = ra.take<uint32_t>(n);
-    d_keep = ra.take<uint32_t>(n1);
-    d_keep_pos = ra.take<uint32_t>(n1);
-    d_out_len = ra.take<uint32_t>(n1);
-    d_out_pos = ra.take<uint32_t>(n1);
-    d_stmp = ra.take<uint32_t>(cdiv(n1, kScanTile) + 8);
     if (pass == 0) ra.commit();
   }
   ra.arm(st);
   unsigned long long *d_counters = reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarLf);
-  unsigned long long *d_usig = reinterpret_cast<unsigned long long *>(d_sig);
-  clear_scalars(c, kScalarLfBad, kScalarLf, st);
-  WP_HIP(hipMemsetAsync(c->d_scalars + kScalarLfBad, 0xff, sizeof(uint32_t), st));
-  WP_HIP(hipMemsetAsync(d_sig, 0, n * WP_LF_SIGNALS * sizeof(long long), st));
+  unsigned long long *d_usig = rows.usig();
+  const uint32_t *d_boff = rows.d_boff;
   WP_HIP(hipMemsetAsync(d_qsig, 0, n * WP_QUALITY_SIGNALS * sizeof(unsigned long long), st));
-  queue_window_rows(c, in, 1, d_boff, kScalarLfBad, kScalarLfElems, kScalarLfWindows, st);
-  WP_LAUNCH_CHECK();
-  queue_scalar_slots(c, kScalarLfBad, kScalarLfWindows, st);
-  WP_HIP(hipStreamSynchronize(st));
-  const size_t nb = read_window_rows(c, "lines", in, kScalarLfBad, kScalarLfElems, kScalarLfWindows).n_bytes;
+  rows.queue(c, L, in, st);
+  const size_t nb = rows.read(c, L, in, st);
   ps.n_bytes = static_cast<int64_t>(nb);
   const uint8_t *d_text = static_cast<const uint8_t *>(in.d_data);
   const uint32_t *d32 = static_cast<const uint32_t *>(in.d_data);
 
-  // ---- the class pass of quality.h: counts, the scan of the tile counts, the numbers of words and lines ----------------------
-  const size_t n_tiles = cdiv(nb, kQualTile), nt1 = n_tiles + 1, n_counts = kQualKinds * nt1;
+  // ---- the class pass of quality.h: the numbers of words and lines -------------------------------------------------------------
   Arena ia(&c->lines_items, guard);
-  uint32_t *d_tiles = nullptr, *d_ttmp = nullptr, *d_table = nullptr;
+  ClassPass cls;
+  uint32_t *d_table = nullptr;
   for (int pass = 0; pass < 2; pass++) {
-    d_tiles = ia.take<uint32_t>(n_counts);
-    d_ttmp = ia.take<uint32_t>(cdiv(n_counts, kScanTile) + 8);
+    cls.take(ia, nb);
     d_table = ia.take<uint32_t>(kLfTabWords);
     if (pass == 0) ia.commit();
   }
   ia.arm(st);
-  size_t nw = 0, nl = 0;
-  QualLists lists{};
-  if (nb != 0) {
-    ensure_class_table(c, st);
-    if (plan.n_phrases != 0) WP_HIP(hipMemcpyAsync(d_table, plan.table.data(), plan.table.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    WP_HIP(hipMemsetAsync(d_tiles, 0, n_counts * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(qual_class_kernel<false>, dim3(n_tiles), dim3(kBlock), 0, st, d_text, nb, d_boff, n, c->d_class_index, c->d_class_pages, d_tiles, nt1, d_qsig,
-                       lists);
-    device_exclusive_scan(d_tiles, d_tiles, n_counts, d_ttmp, nullptr, st);
-    hipLaunchKernelGGL(qual_totals_kernel, dim3(1), dim3(kWave), 0, st, d_tiles, nt1, c->d_scalars + kScalarLfWords, c->d_scalars + kScalarLfLines);
-    WP_LAUNCH_CHECK();
-    queue_scalar_slots(c, kScalarLfWords, kScalarLfLines, st);
-    WP_HIP(hipStreamSynchronize(st));
-    nw = c->h_scalars[kScalarLfWords];
-    nl = c->h_scalars[kScalarLfLines];
-    if (nw > nb || nl > nb) throw HipError("lines: the starts and the ends of the words or lines do not pair up");
-  }
+  if (nb != 0 && plan.n_phrases != 0) WP_HIP(hipMemcpyAsync(d_table, plan.table.data(), plan.table.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  const ClassPass::Counts counts = cls.count(c, L, in, rows, d_qsig, st);
+  const size_t nw = counts.n_words, nl = counts.n_lines;
   if (plan.dup_scope != 0 && nl >= (size_t(1) << 30)) throw std::length_error("lines: 2^30 lines or more with dup_scope != 0");
 
   // ---- the lists and the per-line arrays --------------------------------------------------------------------------------------
   const bool dup = plan.dup_scope != 0 && nl != 0, sorted = dup && plan.dup_scope == 1;
-  const size_t nl1 = nl + 1, dup_rows = 2 * nl + 1, tmp_words = radix_tmp_words<uint64_t>(nl);
+  const size_t nl1 = nl + 1;
   Arena la(&c->lines_lists, guard);
+  QualLists lists{};
   LfLines ln{};
-  uint32_t *d_drop = nullptr, *d_D = nullptr, *d_ltmp = nullptr, *d_v0 = nullptr, *d_v1 = nullptr, *d_head = nullptr, *d_rtmp = nullptr;
-  uint64_t *d_k0 = nullptr, *d_k1 = nullptr;
+  ItemOrder order;
+  uint32_t *d_drop = nullptr, *d_D = nullptr, *d_ltmp = nullptr;
   long long *d_dup_off = nullptr, *d_line_start = nullptr;
   int32_t *d_line_row = nullptr, *d_line_len = nullptr;
   for (int pass = 0; pass < 2; pass++) {
-    lists.wstart = la.take<uint32_t>(nw);
-    lists.wrow = la.take<uint32_t>(nw);
-    lists.wa0 = la.take<uint32_t>(nw);
-    lists.wend = la.take<uint32_t>(nw);
-    lists.wa1 = la.take<uint32_t>(nw);
-    lists.lstart = la.take<uint32_t>(nl);
-    lists.lrow = la.take<uint32_t>(nl);
-    lists.lc0 = la.take<uint32_t>(nl);
-    lists.lend = la.take<uint32_t>(nl);
-    lists.lc1 = la.take<uint32_t>(nl);
+    lists = ClassPass::take_lists(la, nw, nl, false);
     ln.words = la.take<uint32_t>(nl);
     ln.chars = la.take<uint32_t>(nl);
     ln.own_end = la.take<uint32_t>(nl);
@@ -254,119 +201,73 @@ static void lines_on_device(wp_vocab *v, Context *c, const RaggedIn &in, const L
       d_line_row = la.take<int32_t>(nl);
       d_line_len = la.take<int32_t>(nl);
     }
-    if (dup) d_dup_off = la.take<long long>(dup_rows + 1);
-    if (sorted) {
-      d_k0 = la.take<uint64_t>(nl);
-      d_k1 = la.take<uint64_t>(nl);
-      d_v0 = la.take<uint32_t>(nl);
-      d_v1 = la.take<uint32_t>(nl);
-      d_head = la.take<uint32_t>(nl1);
-      d_rtmp = la.take<uint32_t>(tmp_words);
-    }
+    if (dup) d_dup_off = la.take<long long>(2 * nl + 2);
+    if (sorted) order.take(la, nl);
     if (pass == 0) la.commit();
   }
   la.arm(st);
-  lists.n_words = nw;
-  lists.n_lines = nl;
-  if (nb != 0) {
-    hipLaunchKernelGGL(qual_class_kernel<true>, dim3(n_tiles), dim3(kBlock), 0, st, d_text, nb, d_boff, n, c->d_class_index, c->d_class_pages, d_tiles, nt1, d_qsig,
-                       lists);
-    if (nl != 0) WP_HIP(hipMemsetAsync(ln.reasons, 0, nl * sizeof(uint32_t), st));
-    WP_LAUNCH_CHECK();
-  }
+  cls.write(c, in, rows, d_qsig, lists, st);
+  if (nl != 0) WP_HIP(hipMemsetAsync(ln.reasons, 0, nl * sizeof(uint32_t), st));
+  WP_LAUNCH_CHECK();
   if (timing) WP_HIP(hipEventRecord(c->ev[kMarkCounted], st));
 
   // ---- the phrase scan, the line pass ------------------------------------------------------------------------------------------
   if (nb != 0 && plan.n_phrases != 0) {
-    hipLaunchKernelGGL(lf_phrase_kernel, dim3(std::min<size_t>(n_tiles, 1024)), dim3(kBlock), 0, st, d32, nb, static_cast<const uint32_t *>(d_boff), n,
-                       static_cast<const uint32_t *>(d_table), plan.n_one, plan.n_phrases, plan.pool_words, lists, ln.reasons, d_usig, d_counters + kLfMatches);
+    hipLaunchKernelGGL(lf_phrase_kernel, dim3(std::min<size_t>(cls.n_tiles, 1024)), dim3(kBlock), 0, st, d32, nb, d_boff, n, static_cast<const uint32_t *>(d_table),
+                       plan.n_one, plan.n_phrases, plan.pool_words, lists, ln.reasons, d_usig, d_counters + kLfMatches);
   }
-  if (nl != 0) hipLaunchKernelGGL(lf_lines_kernel, count_grid(nl), dim3(kBlock), 0, st, d_text, nb, static_cast<const uint32_t *>(d_boff), lists, n, plan.lim, ln, d_dup_off);
+  if (nl != 0) hipLaunchKernelGGL(lf_lines_kernel, count_grid(nl), dim3(kBlock), 0, st, d_text, nb, d_boff, lists, n, plan.lim, ln, d_dup_off);
   WP_LAUNCH_CHECK();
   if (timing) WP_HIP(hipEventRecord(c->ev[kMarkSorted], st));
 
-  // ---- duplicate lines: the duplicate-row search over the lines; scope 1: one sort of (row, first row with the same bytes) -----
+  // ---- duplicate lines: the first line with the same bytes; scope 1: the lines ordered by (row, that line) --------------------
   if (dup) {
-    wp_dedup_result first{};
-    {
-      BorrowedDedup borrowed(v);
-      dedup_on_device(v, c, RaggedIn{in.d_data, d_dup_off, dup_rows, 1}, DedupPlan{}, &first);
-    }
-    const uint32_t *vals = nullptr;
-    if (sorted) {
-      const int id_bits = bit_length(dup_rows), row_bits = std::max(1, bit_length(n - 1));
-      hipLaunchKernelGGL(qual_dup_keys_kernel, count_grid(nl), dim3(kBlock), 0, st, lists.lrow, first.first, nl, id_bits, d_k0);
-      const int cur = radix_sort_pairs<uint64_t>(d_k0, d_v0, d_k1, d_v1, nl, 0, id_bits + row_bits, d_rtmp, tmp_words, st, rs, true);
-      hipLaunchKernelGGL(group_heads_kernel, count_grid(nl), dim3(kBlock), 0, st, static_cast<const uint64_t *>(cur ? d_k1 : d_k0), nl, d_head);
-      vals = cur ? d_v1 : d_v0;
-    }
-    hipLaunchKernelGGL(lf_dup_kernel, count_grid(nl), dim3(kBlock), 0, st, static_cast<const int32_t *>(first.first), vals, static_cast<const uint32_t *>(d_head), nl,
+    const int32_t *first = first_equal_items(v, c, in, d_dup_off, nl);
+    if (sorted) order.sort(lists.lrow, first, nl, n, rs, st);
+    hipLaunchKernelGGL(lf_dup_kernel, count_grid(nl), dim3(kBlock), 0, st, first, order.vals, static_cast<const uint32_t *>(order.d_head), nl,
                        static_cast<const uint32_t *>(ln.chars), plan.dup_min_chars, ln.reasons);
     WP_LAUNCH_CHECK();
   }
   if (timing) WP_HIP(hipEventRecord(c->ev[kMarkScanned], st));
 
-  // ---- the sums, D, the document rules, the kept rows ----------------------------------------------------------------------------
+  // ---- the sums, D, the document rules, the kept rows; the cut, and the compact form over it -----------------------------------
   hipLaunchKernelGGL(lf_sums_kernel, count_grid(nl1), dim3(kBlock), 0, st, lists, ln, n, d_usig, d_drop, d_line_row, d_line_start, d_line_len);
   device_exclusive_scan(d_drop, d_D, nl1, d_ltmp, c->d_scalars + kScalarLfDropped, st);
-  hipLaunchKernelGGL(lf_docs_kernel, count_grid(n1), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_boff), n, plan.lim, d_sig, d_reasons, d_keep, d_counters);
+  hipLaunchKernelGGL(lf_docs_kernel, count_grid(n1), dim3(kBlock), 0, st, d_boff, n, plan.lim, rows.d_sig, rows.d_reasons, rows.d_keep, d_counters);
   WP_LAUNCH_CHECK();
-  KeptRows kept;
-  if (plan.want_compact) {
-    kept.count(c, "lines", d_keep, d_keep_pos, n, d_stmp, kScalarLfKept, st);
-  } else {
-    device_exclusive_scan(d_keep, d_keep_pos, n1, d_stmp, c->d_scalars + kScalarLfKept, st);
-  }
-
-  // ---- the cut, and the compact form over it --------------------------------------------------------------------------------------
   const bool cut = plan.want_cut || plan.want_compact;
   Arena oa(&c->lines_out, guard);
+  TextTail tail;
   long long *d_cut_off = nullptr;
   uint32_t *d_cut = nullptr;
-  for (int pass = 0; pass < 2 && cut; pass++) {
-    d_cut_off = oa.take<long long>(n1);
-    d_cut = oa.take<uint32_t>(nb / 4 + 1);
-    if (plan.want_compact) kept.take(oa, nb);
-    if (pass == 0) oa.commit();
-  }
+  tail.begin(c, L, rows, nb, plan.want_compact, cut, oa, st, [&](Arena &a) {
+    d_cut_off = a.take<long long>(n1);
+    d_cut = a.take<uint32_t>(nb / 4 + 1);
+  });
   if (cut) {
-    oa.arm(st);
     hipLaunchKernelGGL(lf_cut_off_kernel, count_grid(n1), dim3(kBlock), 0, st, static_cast<const uint32_t *>(d_D), static_cast<const uint32_t *>(lists.lstart), nl,
-                       static_cast<const uint32_t *>(d_boff), n, d_cut_off, d_cut_boff);
+                       d_boff, n, d_cut_off, d_cut_boff);
     if (nb != 0) {
       hipLaunchKernelGGL(lf_cut_kernel, dim3(cdiv(nb, kLfCutTile)), dim3(kBlock), 0, st, d32, nb, static_cast<const uint32_t *>(lists.lstart),
                          static_cast<const uint32_t *>(ln.own_end), static_cast<const uint32_t *>(d_D), nl, d_cut);
     }
     WP_LAUNCH_CHECK();
   }
-  if (plan.want_compact) {  // (nb bounds the bytes of the cut, which the last wait brings)
-    kept.queue(c, RaggedIn{d_cut, d_cut_off, n, 1}, d_keep, d_keep_pos, d_cut_boff, nb, d_out_len, d_out_pos, d_stmp, kScalarLfOutBytes, st);
-    WP_LAUNCH_CHECK();
-  }
-  if (timing) WP_HIP(hipEventRecord(c->ev[kMarkWalked], st));
-  queue_scalar_slots(c, kScalarLfKept, kScalarLf, st);
-  WP_HIP(hipStreamSynchronize(st));
-  unsigned long long counters[kLfCounters];
-  std::memcpy(counters, c->h_scalars + kScalarLf, sizeof(counters));
-  const size_t dropped = c->h_scalars[kScalarLfDropped];
-  if (counters[kLfLinesTotal] != nl || dropped > nb) throw HipError("lines: the rows do not sum to the lines of the text");
-  ps.n_lines = static_cast<int64_t>(nl);
-  ps.n_kept_lines = static_cast<int64_t>(counters[kLfKeptLines]);
-  ps.n_kept_bytes = static_cast<int64_t>(counters[kLfKeptBytes]);
-  ps.n_kept = static_cast<int64_t>(c->h_scalars[kScalarLfKept]);
-  ps.n_phrase_matches = static_cast<int64_t>(counters[kLfMatches]);
-  for (int k = 0; k < WP_LF_LINE_RULES; k++) ps.line_failed[k] = static_cast<int64_t>(counters[kLfLineFailed + k]);
-  for (int k = 0; k < WP_LF_DOC_RULES; k++) ps.rule_failed[k] = static_cast<int64_t>(counters[kLfRuleFailed + k]);
-  if (timing) end_four_stage_timing(v, c);  // (lists, phrases and lines, duplicates, rules and cut: the header's section)
-  // (kSiteOverlap: the row kernel and the kept rows of overlap.h run here too)
-  throw_if_group_oob(kSiteQuality, "line filter", "gathers or stores outside the tile, word, line, signal or cut arrays skipped", kSiteOverlap,
-                     "gathers or stores outside the row arrays skipped");
-  check_arena_guard(c, ra, st, "lines");
-  check_arena_guard(c, ia, st, "lines");
-  check_arena_guard(c, la, st, "lines");
-  check_arena_guard(c, oa, st, "lines");
-  R->signals = reinterpret_cast<int64_t *>(d_sig);
-  R->reasons = d_reasons;
+  // (the compact form is taken from the cut: nb bounds its bytes, which the last wait brings; stage timing: lists,
+  // phrases and lines, duplicates, rules and cut: the header's section)
+  size_t dropped = 0;
+  tail.end(v, c, L, rows, RaggedIn{d_cut, d_cut_off, n, 1}, d_cut_boff, nb, plan.want_compact, {&ra, &ia, &la, &oa}, R,
+           [&](const unsigned long long *counters, int64_t n_kept) {
+             dropped = c->h_scalars[kScalarLfDropped];
+             if (counters[kLfLinesTotal] != nl || dropped > nb) throw HipError("lines: the rows do not sum to the lines of the text");
+             ps.n_lines = static_cast<int64_t>(nl);
+             ps.n_kept_lines = static_cast<int64_t>(counters[kLfKeptLines]);
+             ps.n_kept_bytes = static_cast<int64_t>(counters[kLfKeptBytes]);
+             ps.n_kept = n_kept;
+             ps.n_phrase_matches = static_cast<int64_t>(counters[kLfMatches]);
+             for (int k = 0; k < WP_LF_LINE_RULES; k++) ps.line_failed[k] = static_cast<int64_t>(counters[kLfLineFailed + k]);
+             for (int k = 0; k < WP_LF_DOC_RULES; k++) ps.rule_failed[k] = static_cast<int64_t>(counters[kLfRuleFailed + k]);
+           });
   if (plan.want_lines) {
     R->n_lines = static_cast<int64_t>(nl);
     if (nl != 0) {
@@ -381,7 +282,6 @@ static void lines_on_device(wp_vocab *v, Context *c, const RaggedIn &in, const L
     R->cut_off = reinterpret_cast<int64_t *>(d_cut_off);
     R->cut_data = R->n_cut_elems ? d_cut : nullptr;
   }
-  if (plan.want_compact) kept.hand_out(R, c->h_scalars[kScalarLfOutBytes], 1);
 }
 
 }  // namespace wp

@@ -1153,16 +1153,7 @@ class Vocab:
         out, n = Packed(), C.c_size_t()
         _check(lib().wp_pack_sequences(self._h, _i32_ptr(a), _i64_ptr(splits), len(splits) - 1, C.byref(spec), C.byref(out),
                                        C.byref(n)))
-        rows, L = n.value, int(max_len)
-        keys = ["input_ids"] + [k for k, bit in _PACK_WANT.items() if spec.want & bit]
-        if rows == 0:
-            res = {k: np.zeros((0, L), np.int32) for k in keys}
-            res["lengths"] = np.zeros(0, np.int32)
-            return res
-        i32p = C.POINTER(C.c_int32)
-        res = {k: _adopt_block(C.cast(getattr(out, k), i32p), (rows, L)) for k in keys}
-        res["lengths"] = _adopt_block(C.cast(out.lengths, i32p), (rows,))
-        return res
+        return _packed_result(out, n.value, int(max_len), spec.want)
 
     def pack_sequences_tensor(self, ids, row_splits, max_len=128, mode="next_fit", bos_id=None, eos_id=None, pad_id=0,
                               long_docs="truncate", want=("segment_ids", "position_ids", "source"), n_out=None, out=None):
@@ -1172,52 +1163,16 @@ class Vocab:
         bound will do); without it the rows are sized by the stream bound ceil((n + 2 n_docs) / max_len) in stream mode
         and by min(n_docs, twice that bound + 1) otherwise, and the call runs twice when that was too small (split mode).  out=dict of caller-owned
         tensors (the same keys) to write into: views of the first n_out rows are returned."""
-        import torch
-        if ids.dtype != torch.int32 or not ids.is_cuda or not ids.is_contiguous() or ids.dim() != 1:
-            raise WordPieceError("pack on tensors needs a contiguous 1-d int32 CUDA/HIP tensor of ids")
-        dev = ids.device
-        if self._device is not None and dev.index != self._device:  # (raw pointers go to the handle's device)
-            raise WordPieceError("the tensors lie on %s, the handle on device %d" % (dev, self._device))
-        if row_splits.dtype != torch.int64 or row_splits.device != dev or row_splits.dim() != 1 or row_splits.numel() < 1 or \
-                not row_splits.is_contiguous():
-            raise WordPieceError("row_splits must be a contiguous 1-d int64 tensor on the device of ids")
-        for t in (ids, row_splits):  # (a view of a tensor may start anywhere)
-            if t.data_ptr() % t.element_size() != 0:
-                raise WordPieceError("the tensors must be aligned to their element size")
+        n_docs = _pack_tensor_args(self, ids, row_splits)
         L = int(max_len)
         spec = _pack_spec(L, mode, bos_id, eos_id, pad_id, long_docs, want)
-        n_docs = row_splits.numel() - 1
-        keys = ["input_ids"] + [k for k, bit in _PACK_WANT.items() if spec.want & bit] + ["lengths"]
         if n_out is not None:
             cap = int(n_out)
         elif spec.mode == WP_PACK_STREAM:
             cap = (ids.numel() + 2 * n_docs + L - 1) // L
         else:  # (two neighbouring rows hold more than max_len cells between them, and a document gives a row at most)
             cap = min(n_docs, 2 * (ids.numel() + 2 * n_docs) // L + 1)
-        rows = C.c_size_t()
-        for _ in range(2):
-            if out is not None:
-                t = {k: out[k] for k in keys}
-                for k, x in t.items():
-                    if x.dtype != torch.int32 or not x.is_contiguous() or x.device != dev or \
-                            not (x.dim() == 1 if k == "lengths" else x.dim() == 2 and x.shape[1] == L):
-                        raise WordPieceError("out must hold contiguous int32 tensors [rows, max_len] and lengths [rows] on the "
-                                             "device of ids")
-                cap = min(x.shape[0] for x in t.values())
-            else:
-                t = {k: torch.empty(cap if k == "lengths" else (cap, L), dtype=torch.int32, device=dev) for k in keys}
-            bufs = Packed(*[t[k].data_ptr() if k in t and cap else None
-                            for k in ("input_ids", "segment_ids", "position_ids", "source", "lengths")])
-            torch.cuda.current_stream(dev).synchronize()  # the library runs on its own HIP streams
-            rc = lib().wp_pack_sequences_device(
-                self._h, C.c_void_p(ids.data_ptr()) if ids.numel() else None, C.c_void_p(row_splits.data_ptr()), n_docs,
-                C.byref(spec), C.byref(bufs), cap, C.byref(rows))
-            if rc != 0 and out is None and rows.value > cap:  # (guess too small: the call said how many)
-                cap = rows.value
-                continue
-            _check(rc)
-            break
-        return {k: t[k][:rows.value] for k in keys}
+        return _pack_tensors(self, lib().wp_pack_sequences_device, spec, ids, row_splits, L, cap, out)
 
     def encode_packed_tensor(self, text, doc_offsets=None, max_len=128, mode="next_fit", bos_id=None, eos_id=None, pad_id=0,
                              long_docs="truncate", want=("segment_ids", "position_ids", "source"), n_out=None):
@@ -2294,6 +2249,67 @@ def _mask_spec(max_len, mask_id, prob, mask_share, random_share, whole_word, see
     return MaskSpec(int(max_len), _special(cls_id), _special(sep_id), _special(pad_id), int(mask_id), int(ignore_id),
                     int(whole_word), 0, q32(prob), q32(mask_share), q32(random_share), int(seed) & (2 ** 64 - 1),
                     int(row_base) & (2 ** 64 - 1))
+
+
+def _packed_result(out, rows, L, want):
+    """the blocks of a host pack call (Packed) as a dict of numpy arrays that free them"""
+    keys = ["input_ids"] + [k for k, bit in _PACK_WANT.items() if want & bit]
+    if rows == 0:
+        res = {k: np.zeros((0, L), np.int32) for k in keys}
+        res["lengths"] = np.zeros(0, np.int32)
+        return res
+    i32p = C.POINTER(C.c_int32)
+    res = {k: _adopt_block(C.cast(getattr(out, k), i32p), (rows, L)) for k in keys}
+    res["lengths"] = _adopt_block(C.cast(out.lengths, i32p), (rows,))
+    return res
+
+
+def _pack_tensor_args(v, ids, row_splits):
+    """the tensor rules of a device pack call -> n_docs"""
+    import torch
+    if ids.dtype != torch.int32 or not ids.is_cuda or not ids.is_contiguous() or ids.dim() != 1:
+        raise WordPieceError("pack on tensors needs a contiguous 1-d int32 CUDA/HIP tensor of ids")
+    dev = ids.device
+    if v._device is not None and dev.index != v._device:  # (raw pointers go to the handle's device)
+        raise WordPieceError("the tensors lie on %s, the handle on device %d" % (dev, v._device))
+    if row_splits.dtype != torch.int64 or row_splits.device != dev or row_splits.dim() != 1 or row_splits.numel() < 1 or \
+            not row_splits.is_contiguous():
+        raise WordPieceError("row_splits must be a contiguous 1-d int64 tensor on the device of ids")
+    for t in (ids, row_splits):  # (a view of a tensor may start anywhere)
+        if t.data_ptr() % t.element_size() != 0:
+            raise WordPieceError("the tensors must be aligned to their element size")
+    return row_splits.numel() - 1
+
+
+def _pack_tensors(v, call, spec, ids, row_splits, L, cap, out):
+    """A device pack call (call: wp_pack_sequences_device or one with its arguments) into torch.empty tensors of cap rows,
+    or into out; where the call says it needs more rows than the guess, once more with that count.  -> the result dict"""
+    import torch
+    dev, n_docs = ids.device, row_splits.numel() - 1
+    keys = ["input_ids"] + [k for k, bit in _PACK_WANT.items() if spec.want & bit] + ["lengths"]
+    rows = C.c_size_t()
+    for _ in range(2):
+        if out is not None:
+            t = {k: out[k] for k in keys}
+            for k, x in t.items():
+                if x.dtype != torch.int32 or not x.is_contiguous() or x.device != dev or \
+                        not (x.dim() == 1 if k == "lengths" else x.dim() == 2 and x.shape[1] == L):
+                    raise WordPieceError("out must hold contiguous int32 tensors [rows, max_len] and lengths [rows] on the "
+                                         "device of ids")
+            cap = min(x.shape[0] for x in t.values())
+        else:
+            t = {k: torch.empty(cap if k == "lengths" else (cap, L), dtype=torch.int32, device=dev) for k in keys}
+        bufs = Packed(*[t[k].data_ptr() if k in t and cap else None
+                        for k in ("input_ids", "segment_ids", "position_ids", "source", "lengths")])
+        torch.cuda.current_stream(dev).synchronize()  # the library runs on its own HIP streams
+        rc = call(v._h, C.c_void_p(ids.data_ptr()) if ids.numel() else None, C.c_void_p(row_splits.data_ptr()), n_docs,
+                  C.byref(spec), C.byref(bufs), cap, C.byref(rows))
+        if rc != 0 and out is None and rows.value > cap:  # (guess too small: the call said how many)
+            cap = rows.value
+            continue
+        _check(rc)
+        break
+    return {k: t[k][:rows.value] for k in keys}
 
 
 def _pack_spec(max_len, mode, bos_id, eos_id, pad_id, long_docs, want):

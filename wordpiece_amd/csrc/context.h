@@ -1,6 +1,6 @@
 // context.h — what a vocabulary handle owns on a device: streams, vocabulary tables, bump arenas, the pool of parked
 // contexts (the C ABI itself is in encoder.hip; the device path in linear_path.h and fast_path.h, the layers on top of
-// it in rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h, quality_path.h, repetition_path.h and lines_path.h, the last three over text_path.h).
+// it in rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, binpack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h, quality_path.h, repetition_path.h and lines_path.h, the last three over text_path.h).
 #pragma once
 #include <array>
 #include <cstring>
@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/wordpiece_amd.h"
+#include "../../include/wordpiece_amd_binpack.h"
 #include "../../include/wordpiece_amd_lines.h"
 #include "../../include/wordpiece_amd_repetition.h"
 #include "code.h"
@@ -397,6 +398,10 @@ struct Context {
   // packing (packing.h): ids and row_splits of a host call, the per-document plan, the per-piece tables and row starts,
   // the batch of a host call
   DeviceBuffer pack_in, pack_plan, pack_tab, pack_out;
+  // best-fit packing (binpack.h) shares them; its own: the runs and row ranges of the plan, and the pinned mirror of the
+  // length histogram (kBinMaxLen + 1 counters, made by the first such call)
+  DeviceBuffer binpack_plan;
+  int64_t *h_binpack_hist = nullptr;
   // special tokens (special.h): the blanked copy of the text, the listed lines and the tile counts of the match, the
   // literal list, and the merged result with the tables its placement needs
   DeviceBuffer special_text, special_in, special_lit, special_out;
@@ -478,10 +483,10 @@ struct Context {
     size_t n = 0, n_text = 0;
   } dbg;
   // every DeviceBuffer above, for destroy_context, release_arenas and park_context: a new buffer is one more name here
-  std::array<DeviceBuffer *, 64> buffers() {
+  std::array<DeviceBuffer *, 65> buffers() {
     return {&text_buf, &a_buf,    &b_buf,   &fmt_buf,    &text_buf2, &ids_stage[0], &ids_stage[1], &rows_in,   &rows_out,
             &pad_buf,  &inputs_buf, &norm_buf, &norm_aux, &norm_map, &detok_in,     &detok_aux,    &detok_out,
-            &pack_in,  &pack_plan,  &pack_tab, &pack_out, &special_text, &special_in, &special_lit, &special_out,
+            &pack_in,  &pack_plan,  &pack_tab, &pack_out, &binpack_plan, &special_text, &special_in, &special_lit, &special_out,
             &count_aux, &count_words, &count_out, &learn_in, &learn_aux, &learn_items, &learn_groups, &learn_out,
             &dedup_in, &dedup_rows, &dedup_out, &neardup_in, &neardup_rows, &neardup_items, &neardup_out,
             &overlap_in, &overlap_ref_in, &overlap_rows, &overlap_items, &overlap_out,
@@ -576,6 +581,8 @@ struct EncodeStats : wp_stats {
   int32_t repetition_call;
   wp_lines_stats lines;  // wp_get_lines_stats: filled by a line-filter call (lines_call 1), zero otherwise
   int32_t lines_call;
+  wp_binpack_stats binpack;  // wp_get_binpack_stats: filled by a best-fit pack call (binpack_call 1), zero otherwise
+  int32_t binpack_call;
 };
 
 #ifndef WP_LATE_REFINE_DEFAULT
@@ -631,7 +638,7 @@ static void destroy_events(hipEvent_t (&events)[N]) {
 static void destroy_context(Context *c) {
   if (!c) return;
   bool owns = c->stream || c->stream2 || c->stream3 || c->d_used || c->d_lut || c->d_scan_tmp || c->d_scalars || c->d_code ||
-              c->d_symhist || c->h_scalars || c->h_code || c->d_stream;
+              c->d_symhist || c->h_scalars || c->h_code || c->h_binpack_hist || c->d_stream;
   for (DeviceBuffer *b : c->buffers()) owns = owns || b->p;
   if (!owns) return;
   DeviceGuard keep;
@@ -642,6 +649,8 @@ static void destroy_context(Context *c) {
            c->d_class_pages);
   if (c->h_scalars) (void)hipHostFree(c->h_scalars);
   if (c->h_code) (void)hipHostFree(c->h_code);
+  if (c->h_binpack_hist) (void)hipHostFree(c->h_binpack_hist);
+  c->h_binpack_hist = nullptr;
   c->h_scalars = nullptr;
   c->h_code = nullptr;
   for (DeviceBuffer *b : c->buffers()) b->release();

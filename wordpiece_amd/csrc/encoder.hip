@@ -2,7 +2,7 @@
 // device code is compiled in: the entry points (out-pointers, the answers that need no device, uploads and downloads),
 // the pinned pool, the multi-GPU, batch, stream, file and external calls.  The device path itself: linear_path.h
 // (word_piece::linear, stage by stage) and fast_path.h (word_piece::fast); the layers on top of it, one host header
-// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h, quality_path.h, repetition_path.h, lines_path.h (the last three over text_path.h); what a handle owns
+// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, binpack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h, quality_path.h, repetition_path.h, lines_path.h (the last three over text_path.h); what a handle owns
 // on a device: context.h.
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -22,6 +22,7 @@
 
 #include "../../include/wordpiece_amd.h"
 #include "align_path.h"
+#include "binpack_path.h"
 #include "context.h"
 #include "count_path.h"
 #include "dedup_path.h"
@@ -1068,6 +1069,41 @@ int wp_detokenize_device(wp_vocab *v, const int32_t *d_ids, const int64_t *d_row
 }  // extern "C"
 
 // ---- pack (include/wordpiece_amd.h, section "pack"; host path: pack_path.h) ------------------------------------------
+// the wanted blocks of a host call's batch come down (pack and best fit)
+static void download_packed(Context *c, const PackOut &o, size_t rows, const PackGeom &g, wp_packed *out) {
+  const size_t cells = rows * static_cast<size_t>(g.max_len) * sizeof(int32_t);
+  Downloads down(c->stream);
+  down.add(&out->input_ids, o.input_ids, cells);
+  if (g.want & WP_PACK_WANT_SEGMENTS) down.add(&out->segment_ids, o.segment_ids, cells);
+  if (g.want & WP_PACK_WANT_POSITIONS) down.add(&out->position_ids, o.position_ids, cells);
+  if (g.want & WP_PACK_WANT_SOURCE) down.add(&out->source, o.source, cells);
+  down.add(&out->lengths, o.lengths, rows * sizeof(int32_t));
+  down.finish();
+}
+
+// the pointer and alignment rules of a device call (pack and best fit) -> the wanted buffers
+static PackOut check_pack_device_args(const char *layer, int want, const int32_t *d_ids, const int64_t *d_row_splits, const wp_packed *d_out,
+                                      size_t capacity_rows) {
+  const std::string l(layer);
+  if (!d_row_splits) throw std::invalid_argument(l + ": row_splits is NULL");
+  if (!d_out) throw std::invalid_argument(l + ": an out-pointer is NULL");
+  // (buffers of no rows may be NULL: any row at all then fails the capacity rule, with the count)
+  if (capacity_rows > 0 && (!d_out->input_ids || !d_out->lengths || ((want & WP_PACK_WANT_SEGMENTS) && !d_out->segment_ids) ||
+                            ((want & WP_PACK_WANT_POSITIONS) && !d_out->position_ids) || ((want & WP_PACK_WANT_SOURCE) && !d_out->source))) {
+    throw std::invalid_argument(l + ": an output buffer is NULL");
+  }
+  const PackOut o{d_out->input_ids, (want & WP_PACK_WANT_SEGMENTS) ? d_out->segment_ids : nullptr,
+                  (want & WP_PACK_WANT_POSITIONS) ? d_out->position_ids : nullptr, (want & WP_PACK_WANT_SOURCE) ? d_out->source : nullptr,
+                  d_out->lengths};
+  for (const int32_t *p : {d_ids, static_cast<const int32_t *>(o.input_ids), static_cast<const int32_t *>(o.segment_ids),
+                           static_cast<const int32_t *>(o.position_ids), static_cast<const int32_t *>(o.source),
+                           static_cast<const int32_t *>(o.lengths)}) {
+    check_aligned(p, 4, (l + ": device ids and outputs must be 4-byte aligned").c_str());
+  }
+  check_aligned(d_row_splits, 8, (l + ": device row_splits must be 8-byte aligned").c_str());
+  return o;
+}
+
 extern "C" {
 
 int wp_get_pack_stats(const wp_vocab *v, wp_pack_stats *out) {
@@ -1085,24 +1121,12 @@ int wp_pack_sequences(wp_vocab *v, const int32_t *ids, const int64_t *row_splits
     const PackGeom g = check_pack_spec(spec, n_docs);
     if (!row_splits) throw std::invalid_argument("pack: row_splits is NULL");
     const size_t n_ids = static_cast<size_t>(check_row_splits("pack", row_splits, n_docs));
-    const unsigned long long s = static_cast<unsigned long long>(g.max_len - g.budget), B = static_cast<unsigned long long>(g.budget);
-    unsigned long long n_cells = 0, n_pieces = 0, n_empty = 0;
-    for (size_t r = 0; r < n_docs; r++) {
-      const unsigned long long l = static_cast<unsigned long long>(row_splits[r + 1] - row_splits[r]);
-      if (l == 0) {
-        n_empty++;
-        continue;
-      }
-      const unsigned long long np = g.split ? (l - 1) / B + 1 : 1ull;
-      n_pieces += np;
-      n_cells += (g.stream || g.split ? l : std::min(l, B)) + np * s;  // (l < 2^63, np * s <= 2 l: no wrap before the check of n_ids)
-      if (n_cells > (1ull << 62)) n_cells = 1ull << 62;
-    }
-    check_pack_totals(n_ids, n_cells);
-    if (g.stream) check_pack_rows((n_cells + g.max_len - 1) / static_cast<unsigned long long>(g.max_len), g.max_len);
+    const PackHostTotals t = pack_host_totals(row_splits, n_docs, g);
+    check_pack_totals("pack", n_ids, t.n_cells);
+    if (g.stream) check_pack_rows("pack", (t.n_cells + g.max_len - 1) / static_cast<unsigned long long>(g.max_len), g.max_len);
     if (n_ids > 0 && !ids) throw std::invalid_argument("pack: ids is NULL");
-    if (n_pieces == 0) {  // no document, or empty ones only: no device
-      begin_pack_stats(v, n_docs).n_empty = static_cast<int64_t>(n_empty);
+    if (t.n_pieces == 0) {  // no document, or empty ones only: no device
+      begin_pack_stats(v, n_docs).n_empty = static_cast<int64_t>(t.n_empty);
       return;
     }
     Context *c = get_context(v);
@@ -1110,14 +1134,7 @@ int wp_pack_sequences(wp_vocab *v, const int32_t *ids, const int64_t *row_splits
     PackOut o{};
     const size_t rows = pack_on_device(v, c, in.d_ids, in.d_rows, n_docs, g, [&](size_t n) { return o = pack_batch(c, n, g.max_len); });
     if (rows == 0) return;
-    const size_t cells = rows * static_cast<size_t>(g.max_len) * sizeof(int32_t);
-    Downloads down(c->stream);
-    down.add(&out->input_ids, o.input_ids, cells);
-    if (g.want & WP_PACK_WANT_SEGMENTS) down.add(&out->segment_ids, o.segment_ids, cells);
-    if (g.want & WP_PACK_WANT_POSITIONS) down.add(&out->position_ids, o.position_ids, cells);
-    if (g.want & WP_PACK_WANT_SOURCE) down.add(&out->source, o.source, cells);
-    down.add(&out->lengths, o.lengths, rows * sizeof(int32_t));
-    down.finish();
+    download_packed(c, o, rows, g, out);
     *n_out = rows;
   });
 }
@@ -1128,22 +1145,7 @@ int wp_pack_sequences_device(wp_vocab *v, const int32_t *d_ids, const int64_t *d
     if (!n_out) throw std::invalid_argument("pack: an out-pointer is NULL");
     *n_out = 0;
     const PackGeom g = check_pack_spec(spec, n_docs);
-    if (!d_row_splits) throw std::invalid_argument("pack: row_splits is NULL");
-    if (!d_out) throw std::invalid_argument("pack: an out-pointer is NULL");
-    // (buffers of no rows may be NULL: any row at all then fails the capacity rule, with the count)
-    if (capacity_rows > 0 && (!d_out->input_ids || !d_out->lengths || ((g.want & WP_PACK_WANT_SEGMENTS) && !d_out->segment_ids) ||
-                              ((g.want & WP_PACK_WANT_POSITIONS) && !d_out->position_ids) || ((g.want & WP_PACK_WANT_SOURCE) && !d_out->source))) {
-      throw std::invalid_argument("pack: an output buffer is NULL");
-    }
-    PackOut o{d_out->input_ids, (g.want & WP_PACK_WANT_SEGMENTS) ? d_out->segment_ids : nullptr,
-              (g.want & WP_PACK_WANT_POSITIONS) ? d_out->position_ids : nullptr, (g.want & WP_PACK_WANT_SOURCE) ? d_out->source : nullptr,
-              d_out->lengths};
-    for (const int32_t *p : {d_ids, static_cast<const int32_t *>(o.input_ids), static_cast<const int32_t *>(o.segment_ids),
-                             static_cast<const int32_t *>(o.position_ids), static_cast<const int32_t *>(o.source),
-                             static_cast<const int32_t *>(o.lengths)}) {
-      check_aligned(p, 4, "pack: device ids and outputs must be 4-byte aligned");
-    }
-    check_aligned(d_row_splits, 8, "pack: device row_splits must be 8-byte aligned");
+    const PackOut o = check_pack_device_args("pack", g.want, d_ids, d_row_splits, d_out, capacity_rows);
     if (n_docs == 0) {
       begin_pack_stats(v, 0);
       return;
@@ -1160,7 +1162,87 @@ int wp_pack_sequences_device(wp_vocab *v, const int32_t *d_ids, const int64_t *d
 
 }  // extern "C"
 
-// ---- span alignment (include/wordpiece_amd.h, section "span alignment"; host path: align_path.h) ---------------------
+// ---- best-fit packing (include/wordpiece_amd_binpack.h; host path: binpack_path.h) -----------------------------------
+extern "C" {
+
+int wp_get_binpack_stats(const wp_vocab *v, wp_binpack_stats *out) {
+  *out = v->stats.binpack;
+  if (!v->stats.binpack_call) out->n_docs = -1;
+  return WP_OK;
+}
+
+int wp_binpack_plan(const int64_t *hist, int32_t max_len, wp_binpack_plan_result *out) {
+  return guarded([&] {
+    if (!out) throw std::invalid_argument("binpack: an out-pointer is NULL");
+    *out = wp_binpack_plan_result{};
+    if (!hist) throw std::invalid_argument("binpack: hist is NULL");
+    if (max_len < 1 || max_len > WP_BINPACK_MAX_LEN) throw std::invalid_argument("binpack: max_len must be in [1, 8192]");
+    const BinPlan plan = binpack_plan_host(hist, max_len);
+    const size_t run_bytes = plan.runs.size() * sizeof(wp_binpack_run), range_bytes = plan.ranges.size() * sizeof(wp_binpack_row_range);
+    if (run_bytes) {  // (no units: no run and no row range)
+      out->runs = static_cast<wp_binpack_run *>(zeroed(run_bytes));
+      out->row_ranges = static_cast<wp_binpack_row_range *>(zeroed(range_bytes));
+      std::memcpy(out->runs, plan.runs.data(), run_bytes);
+      std::memcpy(out->row_ranges, plan.ranges.data(), range_bytes);
+    }
+    out->n_out = plan.n_out;
+    out->n_units = plan.n_units;
+    out->n_cells = plan.n_cells;
+    out->n_runs = static_cast<int64_t>(plan.runs.size());
+    out->n_row_ranges = static_cast<int64_t>(plan.ranges.size());
+  });
+}
+
+int wp_pack_best_fit(wp_vocab *v, const int32_t *ids, const int64_t *row_splits, size_t n_docs, const wp_binpack_spec *spec, wp_packed *out,
+                     size_t *n_out) {
+  return guarded([&] {
+    if (!out || !n_out) throw std::invalid_argument("binpack: an out-pointer is NULL");
+    *out = wp_packed{};
+    *n_out = 0;
+    const PackGeom g = check_binpack_spec(spec, n_docs);
+    if (!row_splits) throw std::invalid_argument("binpack: row_splits is NULL");
+    const size_t n_ids = static_cast<size_t>(check_row_splits("binpack", row_splits, n_docs));
+    const PackHostTotals t = pack_host_totals(row_splits, n_docs, g);
+    check_pack_totals("binpack", n_ids, t.n_cells);
+    if (n_ids > 0 && !ids) throw std::invalid_argument("binpack: ids is NULL");
+    if (t.n_pieces == 0) {  // no document, or empty ones only: no device
+      begin_binpack_stats(v, n_docs).n_empty = static_cast<int64_t>(t.n_empty);
+      return;
+    }
+    Context *c = get_context(v);
+    const StagedRows in = stage_ids_and_rows(c->pack_in, c->stream, ids, n_ids, row_splits, (n_docs + 1) * sizeof(int64_t), n_docs);
+    PackOut o{};
+    const size_t rows = binpack_on_device(v, c, in.d_ids, in.d_rows, n_docs, g, [&](size_t n) { return o = pack_batch(c, n, g.max_len); });
+    if (rows == 0) return;
+    download_packed(c, o, rows, g, out);
+    *n_out = rows;
+  });
+}
+
+int wp_pack_best_fit_device(wp_vocab *v, const int32_t *d_ids, const int64_t *d_row_splits, size_t n_docs, const wp_binpack_spec *spec,
+                            const wp_packed *d_out, size_t capacity_rows, size_t *n_out) {
+  return guarded([&] {
+    if (!n_out) throw std::invalid_argument("binpack: an out-pointer is NULL");
+    *n_out = 0;
+    const PackGeom g = check_binpack_spec(spec, n_docs);
+    const PackOut o = check_pack_device_args("binpack", g.want, d_ids, d_row_splits, d_out, capacity_rows);
+    if (n_docs == 0) {
+      begin_binpack_stats(v, 0);
+      return;
+    }
+    *n_out = binpack_on_device(v, get_context(v), d_ids, reinterpret_cast<const long long *>(d_row_splits), n_docs, g, [&](size_t n) {
+      if (n > capacity_rows) {
+        *n_out = n;
+        throw std::invalid_argument("binpack: capacity_rows is smaller than the number of output rows");
+      }
+      return o;
+    });
+  });
+}
+
+}  // extern "C"
+
+// ---- span alignment(include/wordpiece_amd.h, section "span alignment"; host path: align_path.h) ---------------------
 // the host entry points behind their argument rules: align_from_host, then the blocks the caller asked for come down
 static void align_host_call(wp_vocab *v, const AlignIn &in, const AlignGeom &g, bool ragged, int want, int32_t **labels, int32_t **span_index,
                             int32_t **start, int32_t **end) {

@@ -38,14 +38,89 @@ static wp_pack_stats &begin_pack_stats(wp_vocab *v, size_t n_docs) {
   return v->stats.pack;
 }
 
-static void check_pack_totals(unsigned long long n_ids, unsigned long long n_cells) {
-  if (n_ids > static_cast<unsigned long long>(INT32_MAX)) throw std::length_error("pack: more ids than INT32_MAX");
-  if (n_cells > static_cast<unsigned long long>(INT32_MAX)) throw std::length_error("pack: more cells in the units than INT32_MAX");
+static void check_pack_totals(const char *layer, unsigned long long n_ids, unsigned long long n_cells) {
+  if (n_ids > static_cast<unsigned long long>(INT32_MAX)) throw std::length_error(std::string(layer) + ": more ids than INT32_MAX");
+  if (n_cells > static_cast<unsigned long long>(INT32_MAX)) throw std::length_error(std::string(layer) + ": more cells in the units than INT32_MAX");
 }
-static void check_pack_rows(unsigned long long n_out, int max_len) {
+static void check_pack_rows(const char *layer, unsigned long long n_out, int max_len) {
   if (n_out * static_cast<unsigned long long>(max_len) > static_cast<unsigned long long>(INT32_MAX)) {
-    throw std::length_error("pack: n_out * max_len exceeds INT32_MAX");
+    throw std::length_error(std::string(layer) + ": n_out * max_len exceeds INT32_MAX");
   }
+}
+
+// what a host entry point counts over row_splits before a device is touched (the pieces and cells of the plan kernel)
+struct PackHostTotals {
+  unsigned long long n_cells = 0, n_pieces = 0, n_empty = 0;
+};
+static PackHostTotals pack_host_totals(const int64_t *row_splits, size_t n_docs, const PackGeom &g) {
+  const unsigned long long s = static_cast<unsigned long long>(g.max_len - g.budget), B = static_cast<unsigned long long>(g.budget);
+  PackHostTotals t;
+  for (size_t r = 0; r < n_docs; r++) {
+    const unsigned long long l = static_cast<unsigned long long>(row_splits[r + 1] - row_splits[r]);
+    if (l == 0) {
+      t.n_empty++;
+      continue;
+    }
+    const unsigned long long np = g.split ? (l - 1) / B + 1 : 1ull;
+    t.n_pieces += np;
+    t.n_cells += (g.stream || g.split ? l : std::min(l, B)) + np * s;  // (l < 2^63, np * s <= 2 l: no wrap before the check of n_ids)
+    if (t.n_cells > (1ull << 62)) t.n_cells = 1ull << 62;
+  }
+  return t;
+}
+
+// The plan of a call on c's stream (pack and best fit alike): the row_splits checked in a kernel, the pieces and cells
+// of every document, the 64-bit totals read and checked.  Fills g.n_ids, g.n_cells, g.n_pieces and the first
+// statistics of ps.  Nothing is written through the caller's pointers.
+struct PackDocs {
+  uint32_t *d_piece_base = nullptr, *d_cell_base = nullptr, *d_scan_tmp = nullptr;
+  unsigned long long *d_tot = nullptr;
+  const unsigned long long *h_tot = nullptr;
+};
+template <typename Stats>
+static PackDocs pack_plan_docs(Context *c, const char *layer, const int32_t *d_ids, const long long *d_splits, size_t n_docs, PackGeom &g,
+                               Stats &ps) {
+  hipStream_t st = c->stream;
+  const dim3 block(kBlock);
+  Arena plan(&c->pack_plan);
+  PackDocs d;
+  for (int pass = 0; pass < 2; pass++) {
+    d.d_piece_base = plan.take<uint32_t>(n_docs);                        // pieces per document, scanned in place
+    d.d_cell_base = plan.take<uint32_t>(n_docs);                         // cells per document, scanned in place
+    d.d_scan_tmp = plan.take<uint32_t>(cdiv(n_docs, kScanTile) + 1);     // the scans' tile sums (device_exclusive_scan: + 1)
+    if (pass == 0) plan.commit();
+  }
+  d.d_tot = reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarPack);
+  d.h_tot = reinterpret_cast<const unsigned long long *>(c->h_scalars + kScalarPack);
+  clear_scalars(c, kScalarPackLast, kScalarPack, st);
+  hipLaunchKernelGGL(check_splits_kernel, dim3(std::min<unsigned>(cdiv(n_docs + 1, kBlock), 1024u)), block, 0, st, d_splits, n_docs,
+                     c->d_scalars + kScalarPackBad, reinterpret_cast<long long *>(c->d_scalars + kScalarPackLast));
+  hipLaunchKernelGGL(seqpack_plan_kernel, dim3(std::min<unsigned>(cdiv(n_docs, kBlock), kPackMaxGrid)), block, 0, st, d_splits, n_docs, g,
+                     d.d_piece_base, d.d_cell_base, d.d_tot);
+  WP_LAUNCH_CHECK();
+  queue_scalar_slots(c, kScalarPackLast, kScalarPack, st);
+  WP_HIP(hipStreamSynchronize(st));
+  if (c->h_scalars[kScalarPackBad] != 0) throw std::invalid_argument(std::string(layer) + ": row_splits must start at 0 and never descend");
+  long long last;
+  std::memcpy(&last, c->h_scalars + kScalarPackLast, sizeof(last));
+  check_pack_totals(layer, static_cast<unsigned long long>(last), d.h_tot[kPackStream]);
+  if (last > 0 && !d_ids) throw std::invalid_argument(std::string(layer) + ": ids is NULL");
+  ps.n_empty = static_cast<int64_t>(d.h_tot[kPackEmpty]);
+  ps.n_cut = static_cast<int64_t>(d.h_tot[kPackCut]);
+  ps.n_ids_cut = static_cast<int64_t>(d.h_tot[kPackIdsCut]);
+  ps.n_pieces = static_cast<int64_t>(d.h_tot[kPackPieces]);
+  g.n_ids = static_cast<uint32_t>(last);
+  g.n_cells = static_cast<uint32_t>(d.h_tot[kPackStream]);
+  g.n_pieces = static_cast<uint32_t>(d.h_tot[kPackPieces]);  // (every unit holds a cell: n_pieces <= n_cells)
+  return d;
+}
+// P[n_p + 1] and src0[n_p] of the planned pieces: the two scans, then one thread per piece
+static void pack_pieces(Context *c, const PackDocs &d, const long long *d_splits, size_t n_docs, const PackGeom &g, uint32_t *d_P, int32_t *d_src0) {
+  device_exclusive_scan(d.d_piece_base, d.d_piece_base, n_docs, d.d_scan_tmp, nullptr, c->stream);
+  device_exclusive_scan(d.d_cell_base, d.d_cell_base, n_docs, d.d_scan_tmp, nullptr, c->stream);
+  hipLaunchKernelGGL(seqpack_pieces_kernel, dim3(cdiv(g.n_pieces, kBlock)), dim3(kBlock), 0, c->stream, d_splits, static_cast<uint32_t>(n_docs),
+                     d.d_piece_base, d.d_cell_base, g, d_P, d_src0);
+  WP_LAUNCH_CHECK();
 }
 
 // The passes over device buffers on c's stream; the row_splits are checked here in a kernel.  place(n_out): the
@@ -58,36 +133,9 @@ static size_t pack_on_device(wp_vocab *v, Context *c, const int32_t *d_ids, cons
   if (n_docs == 0) return 0;
   hipStream_t st = c->stream;
   const dim3 block(kBlock);
-  Arena plan(&c->pack_plan);
-  uint32_t *d_piece_base = nullptr, *d_cell_base = nullptr, *d_scan_tmp = nullptr;
-  for (int pass = 0; pass < 2; pass++) {
-    d_piece_base = plan.take<uint32_t>(n_docs);                        // pieces per document, scanned in place
-    d_cell_base = plan.take<uint32_t>(n_docs);                         // cells per document, scanned in place
-    d_scan_tmp = plan.take<uint32_t>(cdiv(n_docs, kScanTile) + 1);     // the scans' tile sums (device_exclusive_scan: + 1)
-    if (pass == 0) plan.commit();
-  }
-  unsigned long long *d_tot = reinterpret_cast<unsigned long long *>(c->d_scalars + kScalarPack);
-  const unsigned long long *h_tot = reinterpret_cast<const unsigned long long *>(c->h_scalars + kScalarPack);
-  clear_scalars(c, kScalarPackLast, kScalarPack, st);
-  hipLaunchKernelGGL(check_splits_kernel, dim3(std::min<unsigned>(cdiv(n_docs + 1, kBlock), 1024u)), block, 0, st, d_splits, n_docs,
-                     c->d_scalars + kScalarPackBad, reinterpret_cast<long long *>(c->d_scalars + kScalarPackLast));
-  hipLaunchKernelGGL(seqpack_plan_kernel, dim3(std::min<unsigned>(cdiv(n_docs, kBlock), kPackMaxGrid)), block, 0, st, d_splits, n_docs, g,
-                     d_piece_base, d_cell_base, d_tot);
-  WP_LAUNCH_CHECK();
-  queue_scalar_slots(c, kScalarPackLast, kScalarPack, st);
-  WP_HIP(hipStreamSynchronize(st));
-  if (c->h_scalars[kScalarPackBad] != 0) throw std::invalid_argument("pack: row_splits must start at 0 and never descend");
-  long long last;
-  std::memcpy(&last, c->h_scalars + kScalarPackLast, sizeof(last));
-  check_pack_totals(static_cast<unsigned long long>(last), h_tot[kPackStream]);
-  if (last > 0 && !d_ids) throw std::invalid_argument("pack: ids is NULL");
-  ps.n_empty = static_cast<int64_t>(h_tot[kPackEmpty]);
-  ps.n_cut = static_cast<int64_t>(h_tot[kPackCut]);
-  ps.n_ids_cut = static_cast<int64_t>(h_tot[kPackIdsCut]);
-  ps.n_pieces = static_cast<int64_t>(h_tot[kPackPieces]);
-  g.n_ids = static_cast<uint32_t>(last);
-  g.n_cells = static_cast<uint32_t>(h_tot[kPackStream]);
-  g.n_pieces = static_cast<uint32_t>(h_tot[kPackPieces]);  // (every unit holds a cell: n_pieces <= n_cells)
+  const PackDocs docs = pack_plan_docs(c, "pack", d_ids, d_splits, n_docs, g, ps);
+  unsigned long long *d_tot = docs.d_tot;
+  const unsigned long long *h_tot = docs.h_tot;
   if (g.n_pieces == 0) return 0;
   const size_t n_p = g.n_pieces, n_tiles = cdiv(n_p, kPackPieceTile);
   Arena tab(&c->pack_tab);  // its own arena: the number of pieces is known only behind the wait above
@@ -105,11 +153,7 @@ static size_t pack_on_device(wp_vocab *v, Context *c, const int32_t *d_ids, cons
     d_rec = tab.take<unsigned long long>(n_p);
     if (pass == 0) tab.commit();
   }
-  device_exclusive_scan(d_piece_base, d_piece_base, n_docs, d_scan_tmp, nullptr, st);
-  device_exclusive_scan(d_cell_base, d_cell_base, n_docs, d_scan_tmp, nullptr, st);
-  hipLaunchKernelGGL(seqpack_pieces_kernel, dim3(cdiv(n_p, kBlock)), block, 0, st, d_splits, static_cast<uint32_t>(n_docs), d_piece_base,
-                     d_cell_base, g, d_P, d_src0);
-  WP_LAUNCH_CHECK();
+  pack_pieces(c, docs, d_splits, n_docs, g, d_P, d_src0);
   unsigned long long n_out = (static_cast<unsigned long long>(g.n_cells) + g.max_len - 1) / static_cast<unsigned long long>(g.max_len);
   if (!g.stream) {
     WP_HIP(hipMemsetAsync(d_tile_entry, 0xFF, n_tiles * sizeof(uint32_t), st));
@@ -122,7 +166,7 @@ static size_t pack_on_device(wp_vocab *v, Context *c, const int32_t *d_ids, cons
     n_out = h_tot[kPackRows];
   }
   ps.n_out = static_cast<int64_t>(n_out);
-  check_pack_rows(n_out, g.max_len);
+  check_pack_rows("pack", n_out, g.max_len);
   g.n_out = static_cast<uint32_t>(n_out);
   const PackOut o = place(static_cast<size_t>(n_out));
   if (!g.stream) {

@@ -1,6 +1,6 @@
 // context.h — what a vocabulary handle owns on a device: streams, vocabulary tables, bump arenas, the pool of parked
 // contexts (the C ABI itself is in encoder.hip; the device path in linear_path.h and fast_path.h, the layers on top of
-// it in rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, binpack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h, quality_path.h, repetition_path.h and lines_path.h, the last three over text_path.h).
+// it in rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, binpack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h, quality_path.h, repetition_path.h, lines_path.h and scrub_path.h, the last four over text_path.h).
 #pragma once
 #include <array>
 #include <cstring>
@@ -12,6 +12,7 @@
 #include "../../include/wordpiece_amd.h"
 #include "../../include/wordpiece_amd_binpack.h"
 #include "../../include/wordpiece_amd_lines.h"
+#include "../../include/wordpiece_amd_scrub.h"
 #include "../../include/wordpiece_amd_repetition.h"
 #include "code.h"
 #include "decode.h"
@@ -158,7 +159,7 @@ static int bit_length(uint64_t v) {
 // c->d_scalars: kScalars 32-bit words that kernels and scans leave their totals in; c->h_scalars: the pinned mirror the
 // host reads them from.  Every word has a name here and nowhere else; no call site names a number.  An encode clears
 // the whole block when it starts (and the pre-pass of WP_OPT_NORMALIZE in front of it does the same, see below).
-constexpr int kScalars = 330;
+constexpr int kScalars = 356;
 constexpr int kScalarCps = 0;       // code points of the text, 32 bits: the decode scan (linear, fast) -> host
 constexpr int kScalarAlphabet = 1;  // alphabet size: alphabet_prefix_kernel -> host
 constexpr int kScalarInvalid = 2;   // invalid sequences, 64 bits (words 2, 3): decode_count_kernel / norm_count_kernel -> host
@@ -254,6 +255,11 @@ constexpr int kScalarRptLines = 259, kScalarRptOutBytes = 260, kScalarFree261 = 
 // the bytes of the compact form / the bytes the dropped lines own / the 64-bit counters of a call (words 298..329, LfCounter)
 constexpr int kScalarLfBad = 288, kScalarLfKept = 289, kScalarLfElems = 290, kScalarLfWindows = 292, kScalarLfWords = 294;
 constexpr int kScalarLfLines = 295, kScalarLfOutBytes = 296, kScalarLfDropped = 297, kScalarLf = 298;
+// scrub (scrub.h): the first bad row (~0: none) / the kept rows / row_off[n_rows], 64 bits (words 332, 333) / what the
+// shared row kernel counts as windows, 64 bits (words 334, 335: the bytes again, not read) / the matches / a free word /
+// the bytes of the compact form / a free word / the 64-bit counters of a call (words 340..355, ScrubCounter)
+constexpr int kScalarScrubBad = 330, kScalarScrubKept = 331, kScalarScrubElems = 332, kScalarScrubWindows = 334, kScalarScrubMatches = 336;
+constexpr int kScalarScrubFree = 337, kScalarScrubOutBytes = 338, kScalarFree339 = 339, kScalarScrub = 340;
 // normalize_on_device runs in front of the encode, which clears the block again: while it runs, four slots mean
 constexpr int kScalarNormBytes = kScalarCps;           // bytes of the normalised text, 32 bits: its scan
 constexpr int kScalarNormCps = kScalarAlphabet;        // code points of the normalised text (offsets mode) -> host
@@ -301,7 +307,10 @@ constexpr ScalarRange kScalarLayout[] = {
     {kScalarRpt, 24},        {kScalarFree286, 2},
     {kScalarLfBad, 1},       {kScalarLfKept, 1},      {kScalarLfElems, 2},        {kScalarLfWindows, 2},
     {kScalarLfWords, 1},     {kScalarLfLines, 1},     {kScalarLfOutBytes, 1},     {kScalarLfDropped, 1},
-    {kScalarLf, 32}};
+    {kScalarLf, 32},
+    {kScalarScrubBad, 1},    {kScalarScrubKept, 1},   {kScalarScrubElems, 2},     {kScalarScrubWindows, 2},
+    {kScalarScrubMatches, 1}, {kScalarScrubFree, 1},  {kScalarScrubOutBytes, 1},  {kScalarFree339, 1},
+    {kScalarScrub, 16}};
 // one past the last word of the range `slot` lies in: where a download or a clear "through" that slot ends
 constexpr int scalar_end(int slot) {
   for (const ScalarRange &r : kScalarLayout) {
@@ -438,6 +447,10 @@ struct Context {
   // last call), the tile counts and the phrase table, the lists with the per-line arrays and those of the duplicate
   // stage, and the cut with the compact form of the last call
   DeviceBuffer lines_in, lines_rows, lines_items, lines_lists, lines_out;
+  // scrub (scrub.h): the data and the offsets of a host call, the per-row arrays (with signals, reasons and out_off of
+  // the last call), the tile counts and the replacement pool, the arrays per match with their scan, and the text with the
+  // compact form of the last call
+  DeviceBuffer scrub_in, scrub_rows, scrub_tiles, scrub_items, scrub_out;
   uint16_t *d_class_index = nullptr;
   uint8_t *d_class_pages = nullptr;
   // WP_OPT_NORMALIZE (normalize.h): the tables (uploaded with the first normalising call), the normalised text, the
@@ -483,7 +496,7 @@ struct Context {
     size_t n = 0, n_text = 0;
   } dbg;
   // every DeviceBuffer above, for destroy_context, release_arenas and park_context: a new buffer is one more name here
-  std::array<DeviceBuffer *, 65> buffers() {
+  std::array<DeviceBuffer *, 70> buffers() {
     return {&text_buf, &a_buf,    &b_buf,   &fmt_buf,    &text_buf2, &ids_stage[0], &ids_stage[1], &rows_in,   &rows_out,
             &pad_buf,  &inputs_buf, &norm_buf, &norm_aux, &norm_map, &detok_in,     &detok_aux,    &detok_out,
             &pack_in,  &pack_plan,  &pack_tab, &pack_out, &binpack_plan, &special_text, &special_in, &special_lit, &special_out,
@@ -493,7 +506,8 @@ struct Context {
             &repeat_in, &repeat_rows, &repeat_items, &repeat_out,
             &quality_in, &quality_rows, &quality_items, &quality_lists, &quality_out,
             &repetition_in, &repetition_rows, &repetition_items, &repetition_lists, &repetition_out,
-            &lines_in, &lines_rows, &lines_items, &lines_lists, &lines_out};
+            &lines_in, &lines_rows, &lines_items, &lines_lists, &lines_out,
+            &scrub_in, &scrub_rows, &scrub_tiles, &scrub_items, &scrub_out};
   }
   Context() = default;
   Context(const Context &) = delete;
@@ -581,6 +595,8 @@ struct EncodeStats : wp_stats {
   int32_t repetition_call;
   wp_lines_stats lines;  // wp_get_lines_stats: filled by a line-filter call (lines_call 1), zero otherwise
   int32_t lines_call;
+  wp_scrub_stats scrub;  // wp_get_scrub_stats: filled by a scrub call (scrub_call 1), zero otherwise
+  int32_t scrub_call;
   wp_binpack_stats binpack;  // wp_get_binpack_stats: filled by a best-fit pack call (binpack_call 1), zero otherwise
   int32_t binpack_call;
 };

@@ -2,7 +2,7 @@
 // device code is compiled in: the entry points (out-pointers, the answers that need no device, uploads and downloads),
 // the pinned pool, the multi-GPU, batch, stream, file and external calls.  The device path itself: linear_path.h
 // (word_piece::linear, stage by stage) and fast_path.h (word_piece::fast); the layers on top of it, one host header
-// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, binpack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h, quality_path.h, repetition_path.h, lines_path.h (the last three over text_path.h); what a handle owns
+// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, binpack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h, quality_path.h, repetition_path.h, lines_path.h, scrub_path.h (the last four over text_path.h); what a handle owns
 // on a device: context.h.
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -35,6 +35,7 @@
 #include "mask_path.h"
 #include "neardup_path.h"
 #include "lines_path.h"
+#include "scrub_path.h"
 #include "overlap_path.h"
 #include "quality_path.h"
 #include "repetition_path.h"
@@ -1878,6 +1879,35 @@ int wp_filter_lines(wp_vocab *v, const void *data, const int64_t *row_off, size_
 
 int wp_filter_lines_device(wp_vocab *v, const void *d_data, const int64_t *d_row_off, size_t n_rows, const wp_lines_spec *spec, wp_lines_result *d_out) {
   return text_rows_device(v, kLfLayer, d_data, d_row_off, n_rows, spec, d_out, check_lines_spec, begin_lines_stats, lines_on_device);
+}
+
+}  // extern "C"
+
+// ---- scrub (include/wordpiece_amd_scrub.h; host path: scrub_path.h) ------------------------------------------------------
+extern "C" {
+
+int wp_get_scrub_stats(const wp_vocab *v, wp_scrub_stats *out) {
+  *out = v->stats.scrub;
+  if (!v->stats.scrub_call) out->n_rows = -1;
+  return WP_OK;
+}
+
+int wp_scrub_rows(wp_vocab *v, const void *data, const int64_t *row_off, size_t n_rows, const wp_scrub_spec *spec, wp_scrub_result *out) {
+  return text_rows_host(v, kScrubLayer, data, row_off, n_rows, spec, out, WP_SCRUB_SIGNALS, &Context::scrub_in, check_scrub_spec, begin_scrub_stats, scrub_no_bytes,
+                        scrub_on_device, [n_rows](Downloads &down, wp_scrub_result &h) {
+                          const size_t nm = static_cast<size_t>(h.n_matches);
+                          down.swap(&h.match_row, nm * sizeof(int32_t));
+                          down.swap(&h.match_start, nm * sizeof(int64_t));
+                          down.swap(&h.match_len, nm * sizeof(int32_t));
+                          down.swap(&h.match_kind, nm * sizeof(int32_t));
+                          down.swap(&h.match_repl, nm * sizeof(int32_t));
+                          down.swap(&h.out_off, (n_rows + 1) * sizeof(int64_t));
+                          down.swap(&h.out_data, static_cast<size_t>(h.n_out_elems));
+                        });
+}
+
+int wp_scrub_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row_off, size_t n_rows, const wp_scrub_spec *spec, wp_scrub_result *d_out) {
+  return text_rows_device(v, kScrubLayer, d_data, d_row_off, n_rows, spec, d_out, check_scrub_spec, begin_scrub_stats, scrub_on_device);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // context.h — what a vocabulary handle owns on a device: streams, vocabulary tables, bump arenas, the pool of parked
 // contexts (the C ABI itself is in encoder.hip; the device path in linear_path.h and fast_path.h, the layers on top of
-// it in rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, binpack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h, quality_path.h, repetition_path.h, lines_path.h and scrub_path.h, the last four over text_path.h).
+// it in rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, binpack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h, quality_path.h, repetition_path.h, lines_path.h and scrub_path.h, the last four over text_path.h, and seen_path.h).
 #pragma once
 #include <array>
 #include <cstring>
@@ -13,6 +13,7 @@
 #include "../../include/wordpiece_amd_binpack.h"
 #include "../../include/wordpiece_amd_lines.h"
 #include "../../include/wordpiece_amd_scrub.h"
+#include "../../include/wordpiece_amd_seen.h"
 #include "../../include/wordpiece_amd_repetition.h"
 #include "code.h"
 #include "decode.h"
@@ -159,7 +160,7 @@ static int bit_length(uint64_t v) {
 // c->d_scalars: kScalars 32-bit words that kernels and scans leave their totals in; c->h_scalars: the pinned mirror the
 // host reads them from.  Every word has a name here and nowhere else; no call site names a number.  An encode clears
 // the whole block when it starts (and the pre-pass of WP_OPT_NORMALIZE in front of it does the same, see below).
-constexpr int kScalars = 356;
+constexpr int kScalars = 380;
 constexpr int kScalarCps = 0;       // code points of the text, 32 bits: the decode scan (linear, fast) -> host
 constexpr int kScalarAlphabet = 1;  // alphabet size: alphabet_prefix_kernel -> host
 constexpr int kScalarInvalid = 2;   // invalid sequences, 64 bits (words 2, 3): decode_count_kernel / norm_count_kernel -> host
@@ -260,6 +261,11 @@ constexpr int kScalarLfLines = 295, kScalarLfOutBytes = 296, kScalarLfDropped = 
 // the bytes of the compact form / a free word / the 64-bit counters of a call (words 340..355, ScrubCounter)
 constexpr int kScalarScrubBad = 330, kScalarScrubKept = 331, kScalarScrubElems = 332, kScalarScrubWindows = 334, kScalarScrubMatches = 336;
 constexpr int kScalarScrubFree = 337, kScalarScrubOutBytes = 338, kScalarFree339 = 339, kScalarScrub = 340;
+// seen rows (seen.h): the first bad row (~0: none) / the runs of the sort / row_off[n_rows], 64 bits (words 358, 359) / the
+// chunks, 64 bits (words 360, 361) / the kept (new) rows / the bytes of the compact form / the 64-bit counters of the shared
+// row kernel (words 364..371, DedupCounter) / the 32-bit counters of a call (words 372..379, SeenCounter)
+constexpr int kScalarSeenBad = 356, kScalarSeenRuns = 357, kScalarSeenElems = 358, kScalarSeenChunks = 360, kScalarSeenKept = 362;
+constexpr int kScalarSeenOutBytes = 363, kScalarSeenDedup = 364, kScalarSeen = 372;
 // normalize_on_device runs in front of the encode, which clears the block again: while it runs, four slots mean
 constexpr int kScalarNormBytes = kScalarCps;           // bytes of the normalised text, 32 bits: its scan
 constexpr int kScalarNormCps = kScalarAlphabet;        // code points of the normalised text (offsets mode) -> host
@@ -310,7 +316,9 @@ constexpr ScalarRange kScalarLayout[] = {
     {kScalarLf, 32},
     {kScalarScrubBad, 1},    {kScalarScrubKept, 1},   {kScalarScrubElems, 2},     {kScalarScrubWindows, 2},
     {kScalarScrubMatches, 1}, {kScalarScrubFree, 1},  {kScalarScrubOutBytes, 1},  {kScalarFree339, 1},
-    {kScalarScrub, 16}};
+    {kScalarScrub, 16},
+    {kScalarSeenBad, 1},     {kScalarSeenRuns, 1},    {kScalarSeenElems, 2},      {kScalarSeenChunks, 2},
+    {kScalarSeenKept, 1},    {kScalarSeenOutBytes, 1}, {kScalarSeenDedup, 8},     {kScalarSeen, 8}};
 // one past the last word of the range `slot` lies in: where a download or a clear "through" that slot ends
 constexpr int scalar_end(int slot) {
   for (const ScalarRange &r : kScalarLayout) {
@@ -451,6 +459,10 @@ struct Context {
   // the last call), the tile counts and the replacement pool, the arrays per match with their scan, and the text with the
   // compact form of the last call
   DeviceBuffer scrub_in, scrub_rows, scrub_tiles, scrub_items, scrub_out;
+  // seen rows (seen.h): the data and the offsets (or the keys) of a host call, the per-row arrays (with state, first and
+  // keys of the last call; the arrays of an export), and the compact form of the last call.  The set itself is the
+  // handle's (wp_vocab::seen): a parked context moves on to another handle.
+  DeviceBuffer seen_in, seen_rows, seen_out;
   uint16_t *d_class_index = nullptr;
   uint8_t *d_class_pages = nullptr;
   // WP_OPT_NORMALIZE (normalize.h): the tables (uploaded with the first normalising call), the normalised text, the
@@ -496,7 +508,7 @@ struct Context {
     size_t n = 0, n_text = 0;
   } dbg;
   // every DeviceBuffer above, for destroy_context, release_arenas and park_context: a new buffer is one more name here
-  std::array<DeviceBuffer *, 70> buffers() {
+  std::array<DeviceBuffer *, 73> buffers() {
     return {&text_buf, &a_buf,    &b_buf,   &fmt_buf,    &text_buf2, &ids_stage[0], &ids_stage[1], &rows_in,   &rows_out,
             &pad_buf,  &inputs_buf, &norm_buf, &norm_aux, &norm_map, &detok_in,     &detok_aux,    &detok_out,
             &pack_in,  &pack_plan,  &pack_tab, &pack_out, &binpack_plan, &special_text, &special_in, &special_lit, &special_out,
@@ -507,7 +519,7 @@ struct Context {
             &quality_in, &quality_rows, &quality_items, &quality_lists, &quality_out,
             &repetition_in, &repetition_rows, &repetition_items, &repetition_lists, &repetition_out,
             &lines_in, &lines_rows, &lines_items, &lines_lists, &lines_out,
-            &scrub_in, &scrub_rows, &scrub_tiles, &scrub_items, &scrub_out};
+            &scrub_in, &scrub_rows, &scrub_tiles, &scrub_items, &scrub_out, &seen_in, &seen_rows, &seen_out};
   }
   Context() = default;
   Context(const Context &) = delete;
@@ -605,8 +617,21 @@ struct EncodeStats : wp_stats {
 #define WP_LATE_REFINE_DEFAULT 0
 #endif
 
+// The set of row keys a handle has seen (seen.h, seen_path.h): the table in device memory, a raw allocation on `device`
+// that lives until wp_seen_clear or the end of the handle, what the host knows of it, and the statistics of the last
+// call (kept here, outside EncodeStats: an encode rewrites that block).
+struct SeenSet {
+  uint64_t *d_slots = nullptr, *d_old = nullptr;  // d_old: the table a growth replaced, freed behind the call's last wait
+  size_t capacity = 0, n_keys = 0;                // n_keys: exact behind the last wait of every call
+  int device = -1;
+  int64_t n_grown = 0;
+  wp_seen_stats last{};
+  bool called = false;
+};
+
 struct wp_vocab {
   HostVocab hv;
+  SeenSet seen;
   std::unique_ptr<Context> ctx;                  // the handle's own device context
   std::vector<std::unique_ptr<Context>> multi;  // one per entry of the device list of wp_linear_encode_multi
   int device = -1;

@@ -2,7 +2,7 @@
 // device code is compiled in: the entry points (out-pointers, the answers that need no device, uploads and downloads),
 // the pinned pool, the multi-GPU, batch, stream, file and external calls.  The device path itself: linear_path.h
 // (word_piece::linear, stage by stage) and fast_path.h (word_piece::fast); the layers on top of it, one host header
-// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, binpack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h, quality_path.h, repetition_path.h, lines_path.h, scrub_path.h (the last four over text_path.h); what a handle owns
+// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, binpack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h, quality_path.h, repetition_path.h, lines_path.h, scrub_path.h (the last four over text_path.h), seen_path.h; what a handle owns
 // on a device: context.h.
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -36,6 +36,7 @@
 #include "neardup_path.h"
 #include "lines_path.h"
 #include "scrub_path.h"
+#include "seen_path.h"
 #include "overlap_path.h"
 #include "quality_path.h"
 #include "repetition_path.h"
@@ -46,6 +47,7 @@
 
 
 wp_vocab::~wp_vocab() {
+  seen_release(this);
   park_context(std::move(ctx));
   for (auto &c : multi) park_context(std::move(c));
 }
@@ -1908,6 +1910,143 @@ int wp_scrub_rows(wp_vocab *v, const void *data, const int64_t *row_off, size_t 
 
 int wp_scrub_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row_off, size_t n_rows, const wp_scrub_spec *spec, wp_scrub_result *d_out) {
   return text_rows_device(v, kScrubLayer, d_data, d_row_off, n_rows, spec, d_out, check_scrub_spec, begin_scrub_stats, scrub_on_device);
+}
+
+}  // extern "C"
+
+// ---- seen rows (include/wordpiece_amd_seen.h; host path: seen_path.h) ------------------------------------------------------
+// state and first of a host call on their way to the caller, with whatever else the result names
+static void swap_seen(Downloads &down, wp_seen_result &h, uint32_t elem_bytes) {
+  const size_t n = static_cast<size_t>(h.n_rows);
+  down.swap(&h.state, n * sizeof(int32_t));
+  down.swap(&h.first, n * sizeof(int32_t));
+  down.swap(&h.keys, n * sizeof(uint64_t));
+  swap_compact(down, h, h.n_kept, elem_bytes);
+}
+
+extern "C" {
+
+int wp_get_seen_stats(const wp_vocab *v, wp_seen_stats *out) {
+  *out = v->seen.last;
+  if (!v->seen.called) out->n_rows = -1;
+  out->n_keys = static_cast<int64_t>(v->seen.n_keys);
+  out->capacity = static_cast<int64_t>(v->seen.capacity);
+  out->n_grown = v->seen.n_grown;
+  return WP_OK;
+}
+
+int wp_seen_rows(wp_vocab *v, const void *data, const int64_t *row_off, size_t n_rows, const wp_seen_spec *spec, wp_seen_result *out) {
+  return guarded([&] {
+    if (out) *out = wp_seen_result{};
+    const SeenPlan plan = check_seen_spec(spec, out, true);
+    if (n_rows != 0 && !row_off) throw std::invalid_argument("seen: row_off is NULL");
+    check_row_count("seen", n_rows);
+    const unsigned long long n_elems = check_ragged_host("seen", data, row_off, n_rows, plan.elem_bytes);
+    if (n_rows == 0) {
+      begin_seen_stats(v, 0);
+      return;
+    }
+    Context *c = get_context(v);
+    const uint32_t none = 0;  // (rows that are all empty have a key all the same: the call goes to the set as any other)
+    const RaggedIn in = upload_ragged(c->seen_in, c->stream, n_elems ? data : &none, row_off, n_rows, static_cast<size_t>(n_elems) * plan.elem_bytes, plan.elem_bytes);
+    wp_seen_result h;
+    seen_rows_on_device(v, c, in, plan, &h);
+    Downloads down(c->stream);
+    swap_seen(down, h, plan.elem_bytes);
+    down.finish();
+    *out = h;
+  });
+}
+
+int wp_seen_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row_off, size_t n_rows, const wp_seen_spec *spec, wp_seen_result *d_out) {
+  return guarded([&] {
+    if (d_out) *d_out = wp_seen_result{};
+    const SeenPlan plan = check_seen_spec(spec, d_out, true);
+    if (n_rows != 0 && !d_row_off) throw std::invalid_argument("seen: row_off is NULL");
+    check_row_count("seen", n_rows);
+    const RaggedIn in = device_batch("seen", d_data, d_row_off, n_rows, plan.elem_bytes);
+    if (n_rows == 0) {
+      begin_seen_stats(v, 0);
+      return;
+    }
+    seen_rows_on_device(v, get_context(v), in, plan, d_out);
+  });
+}
+
+int wp_seen_keys(wp_vocab *v, const uint64_t *keys, size_t n, const wp_seen_spec *spec, wp_seen_result *out) {
+  return guarded([&] {
+    if (out) *out = wp_seen_result{};
+    const SeenPlan plan = check_seen_spec(spec, out, false);
+    if (n != 0 && !keys) throw std::invalid_argument("seen: keys is NULL");
+    check_row_count("seen", n, " in keys");
+    if (n == 0) {
+      begin_seen_stats(v, 0);
+      return;
+    }
+    Context *c = get_context(v);
+    c->seen_in.ensure(n * sizeof(uint64_t));
+    WP_HIP(hipMemcpyAsync(c->seen_in.p, keys, n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    wp_seen_result h;
+    seen_keys_on_device(v, c, static_cast<const uint64_t *>(c->seen_in.p), n, plan, &h);
+    Downloads down(c->stream);
+    swap_seen(down, h, 1);
+    down.finish();
+    *out = h;
+  });
+}
+
+int wp_seen_keys_device(wp_vocab *v, const uint64_t *d_keys, size_t n, const wp_seen_spec *spec, wp_seen_result *d_out) {
+  return guarded([&] {
+    if (d_out) *d_out = wp_seen_result{};
+    const SeenPlan plan = check_seen_spec(spec, d_out, false);
+    if (n != 0 && !d_keys) throw std::invalid_argument("seen: keys is NULL");
+    check_row_count("seen", n, " in keys");
+    check_aligned(d_keys, 8, "seen: keys must be 8-byte aligned");
+    if (n == 0) {
+      begin_seen_stats(v, 0);
+      return;
+    }
+    seen_keys_on_device(v, get_context(v), d_keys, n, plan, d_out);
+  });
+}
+
+// both forms of the export: the count, and the keys where the caller has room for them
+static int seen_export(wp_vocab *v, uint64_t *keys_out, size_t room, size_t *n, hipMemcpyKind kind) {
+  return guarded([&] {
+    if (!n) throw std::invalid_argument("seen: n is NULL");
+    *n = v->seen.n_keys;
+    if (room != 0 && !keys_out) throw std::invalid_argument("seen: keys_out is NULL");
+    if (v->seen.n_keys == 0 || room < v->seen.n_keys) return;
+    Context *c = get_context(v);
+    const uint64_t *d_sorted = seen_export_on_device(v, c);
+    WP_HIP(hipMemcpyAsync(keys_out, d_sorted, v->seen.n_keys * sizeof(uint64_t), kind, c->stream));
+    WP_HIP(hipStreamSynchronize(c->stream));
+  });
+}
+
+int wp_seen_export(wp_vocab *v, uint64_t *keys_out, size_t room, size_t *n) { return seen_export(v, keys_out, room, n, hipMemcpyDeviceToHost); }
+
+int wp_seen_export_device(wp_vocab *v, uint64_t *d_keys_out, size_t room, size_t *n) {
+  return seen_export(v, d_keys_out, room, n, hipMemcpyDeviceToDevice);
+}
+
+int wp_seen_reserve(wp_vocab *v, size_t n_keys) {
+  return guarded([&] {
+    const size_t want = seen_slots_for(std::max(n_keys, v->seen.n_keys));  // (the size rule comes before the device)
+    if (n_keys == 0 || want <= v->seen.capacity) return;
+    Context *c = get_context(v);
+    clear_scalars(c, kScalarSeen, kScalarSeen, c->stream);
+    seen_ensure(v, c, std::max(n_keys, v->seen.n_keys), v->seen.d_slots ? size_t(WP_SEEN_MIN_SLOTS) : want);
+    WP_LAUNCH_CHECK();
+    queue_scalar_slots(c, kScalarSeen, kScalarSeen, c->stream);
+    WP_HIP(hipStreamSynchronize(c->stream));
+    seen_drop_old(v);
+    if (c->h_scalars[kScalarSeen + kSeenRanOut] != 0) throw HipError("seen: a probe of the rehash ran through the whole table");
+  });
+}
+
+int wp_seen_clear(wp_vocab *v) {
+  return guarded([&] { seen_release(v); });
 }
 
 }  // extern "C"

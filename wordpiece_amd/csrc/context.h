@@ -1,6 +1,6 @@
 // context.h — what a vocabulary handle owns on a device: streams, vocabulary tables, bump arenas, the pool of parked
 // contexts (the C ABI itself is in encoder.hip; the device path in linear_path.h and fast_path.h, the layers on top of
-// it in rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, binpack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h, quality_path.h, repetition_path.h, lines_path.h and scrub_path.h, the last four over text_path.h, and seen_path.h).
+// it in rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, binpack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h, quality_path.h, repetition_path.h, lines_path.h and scrub_path.h, the last four over text_path.h, seen_path.h and classify_path.h).
 #pragma once
 #include <array>
 #include <cstring>
@@ -14,7 +14,9 @@
 #include "../../include/wordpiece_amd_lines.h"
 #include "../../include/wordpiece_amd_scrub.h"
 #include "../../include/wordpiece_amd_seen.h"
+#include "../../include/wordpiece_amd_classify.h"
 #include "../../include/wordpiece_amd_repetition.h"
+#include "classify.h"
 #include "code.h"
 #include "decode.h"
 #include "detok.h"
@@ -160,7 +162,7 @@ static int bit_length(uint64_t v) {
 // c->d_scalars: kScalars 32-bit words that kernels and scans leave their totals in; c->h_scalars: the pinned mirror the
 // host reads them from.  Every word has a name here and nowhere else; no call site names a number.  An encode clears
 // the whole block when it starts (and the pre-pass of WP_OPT_NORMALIZE in front of it does the same, see below).
-constexpr int kScalars = 380;
+constexpr int kScalars = 394;
 constexpr int kScalarCps = 0;       // code points of the text, 32 bits: the decode scan (linear, fast) -> host
 constexpr int kScalarAlphabet = 1;  // alphabet size: alphabet_prefix_kernel -> host
 constexpr int kScalarInvalid = 2;   // invalid sequences, 64 bits (words 2, 3): decode_count_kernel / norm_count_kernel -> host
@@ -266,6 +268,12 @@ constexpr int kScalarScrubFree = 337, kScalarScrubOutBytes = 338, kScalarFree339
 // row kernel (words 364..371, DedupCounter) / the 32-bit counters of a call (words 372..379, SeenCounter)
 constexpr int kScalarSeenBad = 356, kScalarSeenRuns = 357, kScalarSeenElems = 358, kScalarSeenChunks = 360, kScalarSeenKept = 362;
 constexpr int kScalarSeenOutBytes = 363, kScalarSeenDedup = 364, kScalarSeen = 372;
+// classifier (classify.h): the first bad row (~0: none) / the kept rows / row_off[n_rows], 64 bits (words 382, 383) / what
+// the shared row kernel counts as windows, 64 bits (words 384, 385: the bytes again, not read) / the tokens of the text /
+// those with a word id / the bytes of the compact form / the listed features, 32 bits, and 64 bits (words 390, 391) / the
+// 64-bit counter of a call (words 392, 393: the sum of F)
+constexpr int kScalarClsBad = 380, kScalarClsKept = 381, kScalarClsElems = 382, kScalarClsWindows = 384, kScalarClsTokens = 386;
+constexpr int kScalarClsFound = 387, kScalarClsOutBytes = 388, kScalarClsFeatures = 389, kScalarClsFeatures64 = 390, kScalarCls = 392;
 // normalize_on_device runs in front of the encode, which clears the block again: while it runs, four slots mean
 constexpr int kScalarNormBytes = kScalarCps;           // bytes of the normalised text, 32 bits: its scan
 constexpr int kScalarNormCps = kScalarAlphabet;        // code points of the normalised text (offsets mode) -> host
@@ -318,7 +326,10 @@ constexpr ScalarRange kScalarLayout[] = {
     {kScalarScrubMatches, 1}, {kScalarScrubFree, 1},  {kScalarScrubOutBytes, 1},  {kScalarFree339, 1},
     {kScalarScrub, 16},
     {kScalarSeenBad, 1},     {kScalarSeenRuns, 1},    {kScalarSeenElems, 2},      {kScalarSeenChunks, 2},
-    {kScalarSeenKept, 1},    {kScalarSeenOutBytes, 1}, {kScalarSeenDedup, 8},     {kScalarSeen, 8}};
+    {kScalarSeenKept, 1},    {kScalarSeenOutBytes, 1}, {kScalarSeenDedup, 8},     {kScalarSeen, 8},
+    {kScalarClsBad, 1},      {kScalarClsKept, 1},     {kScalarClsElems, 2},       {kScalarClsWindows, 2},
+    {kScalarClsTokens, 1},   {kScalarClsFound, 1},    {kScalarClsOutBytes, 1},    {kScalarClsFeatures, 1},
+    {kScalarClsFeatures64, 2}, {kScalarCls, 2}};
 // one past the last word of the range `slot` lies in: where a download or a clear "through" that slot ends
 constexpr int scalar_end(int slot) {
   for (const ScalarRange &r : kScalarLayout) {
@@ -463,6 +474,10 @@ struct Context {
   // keys of the last call; the arrays of an export), and the compact form of the last call.  The set itself is the
   // handle's (wp_vocab::seen): a parked context moves on to another handle.
   DeviceBuffer seen_in, seen_rows, seen_out;
+  // classifier (classify.h): the data and the offsets of a host call, the per-row arrays (with label, prob, n_features,
+  // reasons and logits of the last call), the tile counts with the per-byte arrays, the token list, the feature list with
+  // the partial sums, and the compact form of the last call.  The models are the handle's (wp_vocab::classify).
+  DeviceBuffer classify_in, classify_rows, classify_tiles, classify_toks, classify_feats, classify_out;
   uint16_t *d_class_index = nullptr;
   uint8_t *d_class_pages = nullptr;
   // WP_OPT_NORMALIZE (normalize.h): the tables (uploaded with the first normalising call), the normalised text, the
@@ -508,7 +523,7 @@ struct Context {
     size_t n = 0, n_text = 0;
   } dbg;
   // every DeviceBuffer above, for destroy_context, release_arenas and park_context: a new buffer is one more name here
-  std::array<DeviceBuffer *, 73> buffers() {
+  std::array<DeviceBuffer *, 79> buffers() {
     return {&text_buf, &a_buf,    &b_buf,   &fmt_buf,    &text_buf2, &ids_stage[0], &ids_stage[1], &rows_in,   &rows_out,
             &pad_buf,  &inputs_buf, &norm_buf, &norm_aux, &norm_map, &detok_in,     &detok_aux,    &detok_out,
             &pack_in,  &pack_plan,  &pack_tab, &pack_out, &binpack_plan, &special_text, &special_in, &special_lit, &special_out,
@@ -519,7 +534,8 @@ struct Context {
             &quality_in, &quality_rows, &quality_items, &quality_lists, &quality_out,
             &repetition_in, &repetition_rows, &repetition_items, &repetition_lists, &repetition_out,
             &lines_in, &lines_rows, &lines_items, &lines_lists, &lines_out,
-            &scrub_in, &scrub_rows, &scrub_tiles, &scrub_items, &scrub_out, &seen_in, &seen_rows, &seen_out};
+            &scrub_in, &scrub_rows, &scrub_tiles, &scrub_items, &scrub_out, &seen_in, &seen_rows, &seen_out,
+            &classify_in, &classify_rows, &classify_tiles, &classify_toks, &classify_feats, &classify_out};
   }
   Context() = default;
   Context(const Context &) = delete;
@@ -629,9 +645,21 @@ struct SeenSet {
   bool called = false;
 };
 
+// One slot of classifier models on a handle (classify.h, classify_path.h): the matrices, the dictionary table and the word
+// pool in device memory, raw allocations on `device` that live until wp_classify_clear, a new load or the end of the
+// handle; the sizes the statistics name; and the statistics of the slot's last call (outside EncodeStats, as SeenSet's).
+struct ClassifySlot {
+  ClsModel m{};
+  int64_t n_words = 0, bucket = 0;
+  int device = -1;
+  bool loaded = false, called = false;
+  wp_classify_stats last{};
+};
+
 struct wp_vocab {
   HostVocab hv;
   SeenSet seen;
+  ClassifySlot classify[WP_CLASSIFY_SLOTS];
   std::unique_ptr<Context> ctx;                  // the handle's own device context
   std::vector<std::unique_ptr<Context>> multi;  // one per entry of the device list of wp_linear_encode_multi
   int device = -1;

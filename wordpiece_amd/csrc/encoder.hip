@@ -2,7 +2,7 @@
 // device code is compiled in: the entry points (out-pointers, the answers that need no device, uploads and downloads),
 // the pinned pool, the multi-GPU, batch, stream, file and external calls.  The device path itself: linear_path.h
 // (word_piece::linear, stage by stage) and fast_path.h (word_piece::fast); the layers on top of it, one host header
-// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, binpack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h, quality_path.h, repetition_path.h, lines_path.h, scrub_path.h (the last four over text_path.h), seen_path.h; what a handle owns
+// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, binpack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h, quality_path.h, repetition_path.h, lines_path.h, scrub_path.h (the last four over text_path.h), seen_path.h, classify_path.h; what a handle owns
 // on a device: context.h.
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -37,6 +37,7 @@
 #include "lines_path.h"
 #include "scrub_path.h"
 #include "seen_path.h"
+#include "classify_path.h"
 #include "overlap_path.h"
 #include "quality_path.h"
 #include "repetition_path.h"
@@ -48,6 +49,7 @@
 
 wp_vocab::~wp_vocab() {
   seen_release(this);
+  for (int slot = 0; slot < WP_CLASSIFY_SLOTS; slot++) classify_release(this, slot);
   park_context(std::move(ctx));
   for (auto &c : multi) park_context(std::move(c));
 }
@@ -2047,6 +2049,82 @@ int wp_seen_reserve(wp_vocab *v, size_t n_keys) {
 
 int wp_seen_clear(wp_vocab *v) {
   return guarded([&] { seen_release(v); });
+}
+
+}  // extern "C"
+
+// ---- classifier (include/wordpiece_amd_classify.h; host path: classify_path.h) -------------------------------------------
+extern "C" {
+
+int wp_get_classify_stats(const wp_vocab *v, int slot, wp_classify_stats *out) {
+  return guarded([&] {
+    if (!out) throw std::invalid_argument("classify: out is NULL");
+    const ClassifySlot &s = v->classify[check_classify_slot(slot)];
+    *out = s.last;
+    if (!s.called) out->n_rows = -1;
+    out->n_words = s.n_words;
+    out->bucket = s.bucket;
+    out->dim = s.m.dim;
+    out->n_labels = s.m.n_labels;
+    out->minn = s.m.minn;
+    out->maxn = s.m.maxn;
+    out->word_ngrams = s.m.word_ngrams;
+  });
+}
+
+int wp_classify_load(wp_vocab *v, int slot, const wp_classify_model *m) {
+  return guarded([&] {
+    check_classify_slot(slot);
+    check_classify_model(m);
+    classify_load_on_device(v, get_context(v), slot, m);
+  });
+}
+
+int wp_classify_clear(wp_vocab *v, int slot) {
+  return guarded([&] { classify_release(v, check_classify_slot(slot)); });
+}
+
+int wp_classify_rows(wp_vocab *v, const void *data, const int64_t *row_off, size_t n_rows, const wp_classify_spec *spec, wp_classify_result *out) {
+  return guarded([&] {
+    if (out) *out = wp_classify_result{};
+    ClassifyPlan plan = check_classify_spec(spec, out);
+    check_text_rows("classify", row_off, n_rows);
+    const unsigned long long n_bytes = check_ragged_host("classify", data, row_off, n_rows, 1);
+    check_classify_labels(v, spec, &plan);
+    if (n_rows == 0) {  // (nothing to hand out: every pointer of the result stays NULL)
+      begin_classify_stats(v, plan.slot, 0);
+      return;
+    }
+    Context *c = get_context(v);
+    const uint32_t none = 0;  // (documents that are all empty still have their "</s>": the call goes to the device as any other)
+    const RaggedIn in = upload_ragged(c->classify_in, c->stream, n_bytes ? data : &none, row_off, n_rows, static_cast<size_t>(n_bytes), 1);
+    wp_classify_result h;
+    classify_on_device(v, c, in, plan, &h);
+    Downloads down(c->stream);
+    down.swap(&h.label, n_rows * sizeof(int32_t));
+    down.swap(&h.prob, n_rows * sizeof(float));
+    down.swap(&h.logits, n_rows * static_cast<size_t>(h.n_labels) * sizeof(float));
+    down.swap(&h.n_features, n_rows * sizeof(int64_t));
+    down.swap(&h.reasons, n_rows * sizeof(uint32_t));
+    swap_compact(down, h, h.n_kept, 1);
+    down.finish();
+    *out = h;
+  });
+}
+
+int wp_classify_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row_off, size_t n_rows, const wp_classify_spec *spec, wp_classify_result *d_out) {
+  return guarded([&] {
+    if (d_out) *d_out = wp_classify_result{};
+    ClassifyPlan plan = check_classify_spec(spec, d_out);
+    check_text_rows("classify", d_row_off, n_rows);
+    const RaggedIn in = device_batch("classify", d_data, d_row_off, n_rows, 1);
+    check_classify_labels(v, spec, &plan);
+    if (n_rows == 0) {  // (nothing to read and nothing to hand out: every pointer of the result stays NULL)
+      begin_classify_stats(v, plan.slot, 0);
+      return;
+    }
+    classify_on_device(v, get_context(v), in, plan, d_out);
+  });
 }
 
 }  // extern "C"

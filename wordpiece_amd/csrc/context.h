@@ -1,6 +1,6 @@
 // context.h — what a vocabulary handle owns on a device: streams, vocabulary tables, bump arenas, the pool of parked
 // contexts (the C ABI itself is in encoder.hip; the device path in linear_path.h and fast_path.h, the layers on top of
-// it in rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, binpack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h, quality_path.h, repetition_path.h, lines_path.h and scrub_path.h, the last four over text_path.h, seen_path.h and classify_path.h).
+// it in rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, binpack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h, quality_path.h, repetition_path.h, lines_path.h and scrub_path.h, the last four over text_path.h, seen_path.h, classify_path.h and bpe_path.h).
 #pragma once
 #include <array>
 #include <cstring>
@@ -14,8 +14,10 @@
 #include "../../include/wordpiece_amd_lines.h"
 #include "../../include/wordpiece_amd_scrub.h"
 #include "../../include/wordpiece_amd_seen.h"
+#include "../../include/wordpiece_amd_bpe.h"
 #include "../../include/wordpiece_amd_classify.h"
 #include "../../include/wordpiece_amd_repetition.h"
+#include "bpe.h"
 #include "classify.h"
 #include "code.h"
 #include "decode.h"
@@ -162,7 +164,7 @@ static int bit_length(uint64_t v) {
 // c->d_scalars: kScalars 32-bit words that kernels and scans leave their totals in; c->h_scalars: the pinned mirror the
 // host reads them from.  Every word has a name here and nowhere else; no call site names a number.  An encode clears
 // the whole block when it starts (and the pre-pass of WP_OPT_NORMALIZE in front of it does the same, see below).
-constexpr int kScalars = 394;
+constexpr int kScalars = 406;
 constexpr int kScalarCps = 0;       // code points of the text, 32 bits: the decode scan (linear, fast) -> host
 constexpr int kScalarAlphabet = 1;  // alphabet size: alphabet_prefix_kernel -> host
 constexpr int kScalarInvalid = 2;   // invalid sequences, 64 bits (words 2, 3): decode_count_kernel / norm_count_kernel -> host
@@ -274,6 +276,11 @@ constexpr int kScalarSeenOutBytes = 363, kScalarSeenDedup = 364, kScalarSeen = 3
 // 64-bit counter of a call (words 392, 393: the sum of F)
 constexpr int kScalarClsBad = 380, kScalarClsKept = 381, kScalarClsElems = 382, kScalarClsWindows = 384, kScalarClsTokens = 386;
 constexpr int kScalarClsFound = 387, kScalarClsOutBytes = 388, kScalarClsFeatures = 389, kScalarClsFeatures64 = 390, kScalarCls = 392;
+// byte-level BPE (bpe.h): the first bad row (~0: none) / the medium pieces / row_off[n_rows], 64 bits (words 396, 397) / what
+// the shared row kernel counts as windows, 64 bits (words 398, 399: the bytes again, not read) / the pieces / the long
+// pieces / their bytes / the ids of the call / the longest piece, 64 bits (words 404, 405)
+constexpr int kScalarBpeBad = 394, kScalarBpeMedium = 395, kScalarBpeElems = 396, kScalarBpeWindows = 398, kScalarBpePieces = 400;
+constexpr int kScalarBpeLong = 401, kScalarBpeLongBytes = 402, kScalarBpeIds = 403, kScalarBpe = 404;
 // normalize_on_device runs in front of the encode, which clears the block again: while it runs, four slots mean
 constexpr int kScalarNormBytes = kScalarCps;           // bytes of the normalised text, 32 bits: its scan
 constexpr int kScalarNormCps = kScalarAlphabet;        // code points of the normalised text (offsets mode) -> host
@@ -329,7 +336,10 @@ constexpr ScalarRange kScalarLayout[] = {
     {kScalarSeenKept, 1},    {kScalarSeenOutBytes, 1}, {kScalarSeenDedup, 8},     {kScalarSeen, 8},
     {kScalarClsBad, 1},      {kScalarClsKept, 1},     {kScalarClsElems, 2},       {kScalarClsWindows, 2},
     {kScalarClsTokens, 1},   {kScalarClsFound, 1},    {kScalarClsOutBytes, 1},    {kScalarClsFeatures, 1},
-    {kScalarClsFeatures64, 2}, {kScalarCls, 2}};
+    {kScalarClsFeatures64, 2}, {kScalarCls, 2},
+    {kScalarBpeBad, 1},      {kScalarBpeMedium, 1},   {kScalarBpeElems, 2},       {kScalarBpeWindows, 2},
+    {kScalarBpePieces, 1},   {kScalarBpeLong, 1},     {kScalarBpeLongBytes, 1},   {kScalarBpeIds, 1},
+    {kScalarBpe, 2}};
 // one past the last word of the range `slot` lies in: where a download or a clear "through" that slot ends
 constexpr int scalar_end(int slot) {
   for (const ScalarRange &r : kScalarLayout) {
@@ -478,6 +488,10 @@ struct Context {
   // reasons and logits of the last call), the tile counts with the per-byte arrays, the token list, the feature list with
   // the partial sums, and the compact form of the last call.  The models are the handle's (wp_vocab::classify).
   DeviceBuffer classify_in, classify_rows, classify_tiles, classify_toks, classify_feats, classify_out;
+  // byte-level BPE (bpe.h): the data and the offsets of a host call, the per-row arrays, the document bits with the start
+  // bitmap and the tile counts, the piece list with the provisional cells, the lists and the scratch of the medium and long
+  // pieces, and the arrays of the last call.  The models are the handle's (wp_vocab::bpe).
+  DeviceBuffer bpe_in, bpe_rows, bpe_tiles, bpe_pieces, bpe_scratch, bpe_out;
   uint16_t *d_class_index = nullptr;
   uint8_t *d_class_pages = nullptr;
   // WP_OPT_NORMALIZE (normalize.h): the tables (uploaded with the first normalising call), the normalised text, the
@@ -523,7 +537,7 @@ struct Context {
     size_t n = 0, n_text = 0;
   } dbg;
   // every DeviceBuffer above, for destroy_context, release_arenas and park_context: a new buffer is one more name here
-  std::array<DeviceBuffer *, 79> buffers() {
+  std::array<DeviceBuffer *, 85> buffers() {
     return {&text_buf, &a_buf,    &b_buf,   &fmt_buf,    &text_buf2, &ids_stage[0], &ids_stage[1], &rows_in,   &rows_out,
             &pad_buf,  &inputs_buf, &norm_buf, &norm_aux, &norm_map, &detok_in,     &detok_aux,    &detok_out,
             &pack_in,  &pack_plan,  &pack_tab, &pack_out, &binpack_plan, &special_text, &special_in, &special_lit, &special_out,
@@ -535,7 +549,8 @@ struct Context {
             &repetition_in, &repetition_rows, &repetition_items, &repetition_lists, &repetition_out,
             &lines_in, &lines_rows, &lines_items, &lines_lists, &lines_out,
             &scrub_in, &scrub_rows, &scrub_tiles, &scrub_items, &scrub_out, &seen_in, &seen_rows, &seen_out,
-            &classify_in, &classify_rows, &classify_tiles, &classify_toks, &classify_feats, &classify_out};
+            &classify_in, &classify_rows, &classify_tiles, &classify_toks, &classify_feats, &classify_out,
+            &bpe_in, &bpe_rows, &bpe_tiles, &bpe_pieces, &bpe_scratch, &bpe_out};
   }
   Context() = default;
   Context(const Context &) = delete;
@@ -656,10 +671,21 @@ struct ClassifySlot {
   wp_classify_stats last{};
 };
 
+// One slot of byte-level BPE models on a handle (bpe.h, bpe_path.h): the byte ids, the merges, the pair table and the class
+// tables in device memory, raw allocations on `device` that live until wp_bpe_clear, a new load or the end of the handle;
+// and the statistics of the slot's last call (outside EncodeStats, as SeenSet's).
+struct BpeSlot {
+  BpeModel m{};
+  int device = -1;
+  bool loaded = false, called = false;
+  wp_bpe_stats last{};
+};
+
 struct wp_vocab {
   HostVocab hv;
   SeenSet seen;
   ClassifySlot classify[WP_CLASSIFY_SLOTS];
+  BpeSlot bpe[WP_BPE_SLOTS];
   std::unique_ptr<Context> ctx;                  // the handle's own device context
   std::vector<std::unique_ptr<Context>> multi;  // one per entry of the device list of wp_linear_encode_multi
   int device = -1;

@@ -2,7 +2,7 @@
 // device code is compiled in: the entry points (out-pointers, the answers that need no device, uploads and downloads),
 // the pinned pool, the multi-GPU, batch, stream, file and external calls.  The device path itself: linear_path.h
 // (word_piece::linear, stage by stage) and fast_path.h (word_piece::fast); the layers on top of it, one host header
-// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, binpack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h, quality_path.h, repetition_path.h, lines_path.h, scrub_path.h (the last four over text_path.h), seen_path.h, classify_path.h; what a handle owns
+// each: rows_path.h, inputs_path.h, mask_path.h, detok_path.h, pack_path.h, binpack_path.h, special_path.h, align_path.h, count_path.h, learn_path.h, dedup_path.h, neardup_path.h, overlap_path.h, repeat_path.h, quality_path.h, repetition_path.h, lines_path.h, scrub_path.h (the last four over text_path.h), seen_path.h, classify_path.h, bpe_path.h; what a handle owns
 // on a device: context.h.
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -37,6 +37,7 @@
 #include "lines_path.h"
 #include "scrub_path.h"
 #include "seen_path.h"
+#include "bpe_path.h"
 #include "classify_path.h"
 #include "overlap_path.h"
 #include "quality_path.h"
@@ -50,6 +51,7 @@
 wp_vocab::~wp_vocab() {
   seen_release(this);
   for (int slot = 0; slot < WP_CLASSIFY_SLOTS; slot++) classify_release(this, slot);
+  for (int slot = 0; slot < WP_BPE_SLOTS; slot++) bpe_release(this, slot);
   park_context(std::move(ctx));
   for (auto &c : multi) park_context(std::move(c));
 }
@@ -2124,6 +2126,77 @@ int wp_classify_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_ro
       return;
     }
     classify_on_device(v, get_context(v), in, plan, d_out);
+  });
+}
+
+}  // extern "C"
+
+// ---- byte-level BPE (include/wordpiece_amd_bpe.h; host path: bpe_path.h) ---------------------------------------------------
+extern "C" {
+
+int wp_get_bpe_stats(const wp_vocab *v, int slot, wp_bpe_stats *out) {
+  return guarded([&] {
+    if (!out) throw std::invalid_argument("bpe: out is NULL");
+    const BpeSlot &s = v->bpe[check_bpe_slot(slot)];
+    *out = s.last;
+    if (!s.called) out->n_rows = -1;
+    out->n_merges = s.m.n_merges;
+    out->model_ids = s.m.n_ids;
+    out->table_slots = s.loaded ? static_cast<int64_t>(s.m.table_mask) + 1 : 0;
+  });
+}
+
+int wp_bpe_load(wp_vocab *v, int slot, const wp_bpe_model *m) {
+  return guarded([&] {
+    check_bpe_slot(slot);
+    const std::vector<uint4> table = check_bpe_model(m);
+    bpe_load_on_device(v, get_context(v), slot, m, table);
+  });
+}
+
+int wp_bpe_clear(wp_vocab *v, int slot) {
+  return guarded([&] { bpe_release(v, check_bpe_slot(slot)); });
+}
+
+int wp_bpe_encode_rows(wp_vocab *v, const void *data, const int64_t *row_off, size_t n_rows, const wp_bpe_spec *spec, wp_bpe_result *out) {
+  return guarded([&] {
+    if (out) *out = wp_bpe_result{};
+    const BpePlan plan = check_bpe_spec(spec, out);
+    check_text_rows("bpe", row_off, n_rows);
+    const unsigned long long n_bytes = check_ragged_host("bpe", data, row_off, n_rows, 1);
+    check_bpe_loaded(v, plan);
+    if (n_rows == 0) {  // (nothing to hand out: every pointer of the result stays NULL)
+      begin_bpe_stats(v, plan.slot, 0);
+      return;
+    }
+    Context *c = get_context(v);
+    const uint32_t none = 0;  // (documents that are all empty still have their row_splits: the call goes to the device as any other)
+    const RaggedIn in = upload_ragged(c->bpe_in, c->stream, n_bytes ? data : &none, row_off, n_rows, static_cast<size_t>(n_bytes), 1);
+    wp_bpe_result h;
+    bpe_on_device(v, c, in, plan, &h);
+    Downloads down(c->stream);
+    down.swap(&h.ids, static_cast<size_t>(h.n_ids) * sizeof(int32_t));
+    down.swap(&h.row_splits, (n_rows + 1) * sizeof(int64_t));
+    down.swap(&h.begin, static_cast<size_t>(h.n_ids) * sizeof(int32_t));
+    down.swap(&h.end, static_cast<size_t>(h.n_ids) * sizeof(int32_t));
+    down.swap(&h.piece_splits, static_cast<size_t>(h.n_pieces + 1) * sizeof(int64_t));
+    down.finish();
+    *out = h;
+  });
+}
+
+int wp_bpe_encode_rows_device(wp_vocab *v, const void *d_data, const int64_t *d_row_off, size_t n_rows, const wp_bpe_spec *spec, wp_bpe_result *d_out) {
+  return guarded([&] {
+    if (d_out) *d_out = wp_bpe_result{};
+    const BpePlan plan = check_bpe_spec(spec, d_out);
+    check_text_rows("bpe", d_row_off, n_rows);
+    const RaggedIn in = device_batch("bpe", d_data, d_row_off, n_rows, 1);
+    check_bpe_loaded(v, plan);
+    if (n_rows == 0) {  // (nothing to read and nothing to hand out: every pointer of the result stays NULL)
+      begin_bpe_stats(v, plan.slot, 0);
+      return;
+    }
+    bpe_on_device(v, get_context(v), in, plan, d_out);
   });
 }
 
